@@ -36,6 +36,8 @@ The JSON line also carries
                 `sclk_mhz_steady_state` over the steady_state leg
   single_trajectory.cadence_us   where a single trajectory's cadence goes: period, the launches' own durations, bubbles
   `--leg NAME` runs one secondary leg alone and prints it.
+  `--dump-outputs DIR` writes the headline filter's state after its last timed step to DIR/*.npy (dump_outputs): the
+  inputs are seeded, so two builds run with the same arguments can be compared array for array.
   (rank 0, N = 1 only, except sclk_mhz and rank_dt_ms).
 """
 from __future__ import annotations
@@ -74,9 +76,47 @@ def make_streams(sd_syn, traj_ids, n_landmarks, steps, m, variable=None):
     return streams, lin, ang, idx, zr, zb, mm
 
 
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: at most this much in all
+DUMP_COV_SAMPLES = 1 << 17     # covariance entries kept per trajectory (a fixed, seeded sample)
+
+
+def dump_outputs(f, out_dir, prefix=""):
+    """What a caller of the timed path receives after its last step -- every trajectory's mean and covariance -- as float64
+    .npy files in `out_dir`: `mean` (B, n), `cov_diag` (B, n), `cov_pose` (B, 3, 3) and `cov_sample` (B, S), the
+    covariance entries at the positions `cov_sample_index` (S, 2: row, column) drawn with a fixed seed (the whole
+    covariance of the headline is 32 x 128 MB).  Where B trajectories do not fit the budget, a seeded subset of them
+    is written and listed in `trajectories` (always written).  Everything together stays within DUMP_LIMIT_BYTES."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = f.size(0)
+    rng = np.random.default_rng(20251015)
+    fixed = 8 * (2 * n + 9)                                        # mean + diagonal + pose block of one trajectory
+    keep = max(1, min(f.batch, (DUMP_LIMIT_BYTES // 2) // fixed))
+    bs = np.arange(f.batch) if keep == f.batch else np.sort(rng.choice(f.batch, keep, replace=False))
+    budget = DUMP_LIMIT_BYTES - len(bs) * fixed - 8 * len(bs)
+    samples = int(min(n * n, DUMP_COV_SAMPLES, budget // (8 * (len(bs) + 2))))
+    flat = np.sort(rng.choice(n * n, samples, replace=False)) if samples < n * n else np.arange(n * n)
+    rows, cols = flat // n, flat % n
+    out = {"trajectories": bs.astype(np.float64), "mean": np.empty((len(bs), n)), "cov_diag": np.empty((len(bs), n)),
+           "cov_pose": np.empty((len(bs), 3, 3)), "cov_sample": np.empty((len(bs), samples)),
+           "cov_sample_index": np.stack([rows, cols], axis=1).astype(np.float64)}
+    for i, b in enumerate(bs):
+        if f.size(int(b)) != n:
+            raise SystemExit("--dump-outputs: the trajectories of the bank differ in size")
+        mu, P = f.state(int(b))
+        out["mean"][i] = mu
+        out["cov_diag"][i] = np.diagonal(P)
+        out["cov_pose"][i] = P[:3, :3]
+        out["cov_sample"][i] = P[rows, cols]
+        del P
+    assert sum(a.nbytes for a in out.values()) <= DUMP_LIMIT_BYTES
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+
+
 def time_filter(sd, sd_syn, shard, grp, device, traj_ids, n_landmarks, m, steps, warmup, profile_leg=True, options=(), clock=None,
-                variable=None):
+                variable=None, dump_dir=None, dump_prefix=""):
     """Returns (max-over-ranks seconds for `steps` steps, pass_ms_total, pass_launches, device_ms).
+    `dump_dir`: after the timed steps, write the filter's outputs there (dump_outputs).
     The timed region is sharding.timed_region (device sync + barrier on both sides, max over ranks): the function
     the world_size-2 gloo test covers."""
     n = 3 + 2 * n_landmarks
@@ -134,6 +174,8 @@ def time_filter(sd, sd_syn, shard, grp, device, traj_ids, n_landmarks, m, steps,
     flags = [f.flags(b) for b in range(len(traj_ids))]
     mu = f.mean(0)
     assert not any(flags) and np.isfinite(mu).all(), "filter diverged during the benchmark"
+    if dump_dir is not None:
+        dump_outputs(f, dump_dir, dump_prefix)
     f.close()
     return dt, pass_ms, launches, dev_ms
 
@@ -652,7 +694,11 @@ def main():
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="ekf_set_option knob, e.g. flush_every=3 (default: library defaults)")
     ap.add_argument("--leg", default=None, help="run ONE secondary leg (see SECONDARY_LEGS) and print it as a JSON line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the headline filter's final state to DIR/*.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     if args.leg:
         if not any(o.startswith("active_bound=") for o in args.option):
             args.option = ["active_bound=0"] + args.option
@@ -695,7 +741,8 @@ def main():
     traj_ids = shard.shard_trajectories(B * world, world, rank)
     clk = ClockSampler(local_rank)
     dt, pass_ms, launches, dev_ms = time_filter(sd, sd_syn, shard, grp, local_rank, traj_ids, args.landmarks, args.obs,
-                                                args.steps, args.warmup, options=args.option, clock=clk)
+                                                args.steps, args.warmup, options=args.option, clock=clk,
+                                                dump_dir=args.dump_outputs, dump_prefix=f"rank{rank}_" if world > 1 else "")
     value = shard.aggregate_steps_per_second(len(traj_ids) * args.steps, grp, dt)
     rank_dts = grp.gather_over_ranks(getattr(shard.timed_region, "last_local_seconds", dt))
     rank_dev_ms = grp.gather_over_ranks(dev_ms / args.steps)

@@ -73,7 +73,10 @@ class RankGroup:
 
     def barrier(self):
         if self._dist is not None:
-            self._dist.barrier()
+            # an all-reduce of one host tensor: no rank leaves before every rank has entered.  (dist.barrier() would first
+            # ask torch for the machine's accelerator, which opens the GPU in every rank, also in ranks that never use it.)
+            import torch
+            self._dist.all_reduce(torch.zeros(1))
 
     def max_over_ranks(self, x: float) -> float:
         if self._dist is None:
@@ -104,7 +107,7 @@ class RankGroup:
 
     def close(self):
         if self._dist is not None:
-            self._dist.barrier()
+            self.barrier()
             self._dist.destroy_process_group()
             self._dist = None
 

@@ -53,20 +53,37 @@ def test_vicon_ground_truth_matches_the_reference_decoder_on_the_recorded_data()
                               float(g["end_capture_time"]), float(g["first_timestamp"]) + 500.0)
 
 
-def test_vicon_csv_loader_reads_the_reference_files():
-    """The loader on the reference's own files gives the fixture's fields (only where /root/reference exists)."""
-    import os
+def _vicon_csv_text(fields, lens, names):
+    """A Vicon export (five header lines, then comma-separated rows) holding exactly the fixture's recorded fields: the
+    fixture keeps every field as an exact integer count of 1e-12 (oracle/gen_golden.py::scaled_ints), so its decimal text
+    is the recorded text up to trailing zeros; an empty field is written empty, a row holds `lens[i]` fields."""
+    from decimal import Decimal
+    missing = np.iinfo(np.int64).min
+    lines = ["Objects", "100", ",," + ",".join(["duckiebot"] * (len(names) - 2)), ",".join(names),
+             ",," + ",".join(["mm"] * (len(names) - 2))]
+    for row, n in zip(fields, lens):
+        lines.append(",".join("" if v == missing else format(Decimal(int(v)).scaleb(-12).normalize(), "f") for v in row[:n]))
+    return "\n".join(lines) + "\n"
+
+
+def test_vicon_csv_loader_reads_the_reference_files(tmp_path):
+    """The loader on the reference's two Vicon exports (bags/quackgpt_small_town_joystick.csv, _trajectories.csv), laid
+    out as recorded and rebuilt from the fields tests/golden/vicon_alignment.npz keeps of them, gives those fields."""
     import slam_duckietown_amd.evaluation as ev
     from tests import golden_util as gu
     from tests import vicon_scenario as vs
-    prefix = "/root/reference/bags/quackgpt_small_town_joystick"
-    if not os.path.exists(prefix + ".csv"):
-        pytest.skip("reference data not present (GPU box)")
     g = gu.load("vicon_alignment")
-    for path, key in ((prefix + ".csv", "robot"), (prefix + "_trajectories.csv", "marker")):
-        fields, lens = ev.load_vicon_csv(path)
+    robot_names = ["Frame", "Sub Frame", "RX", "RY", "RZ", "TX", "TY", "TZ"]
+    marker_names = ["Frame", "Sub Frame"] + [c for k in range(13) for c in (f"X{k}", f"Y{k}", f"Z{k}")]
+    for name, key, cols in (("quackgpt_small_town_joystick.csv", "robot", robot_names),
+                            ("quackgpt_small_town_joystick_trajectories.csv", "marker", marker_names)):
+        assert len(cols) == g[key + "_fields"].shape[1]
+        path = tmp_path / name
+        path.write_text(_vicon_csv_text(g[key + "_fields"], g[key + "_len"], cols))
+        fields, lens = ev.load_vicon_csv(str(path))
         assert np.array_equal(lens, g[key + "_len"])
         assert np.array_equal(fields, vs.decode(g[key + "_fields"]), equal_nan=True)
+        assert np.isnan(fields).any() == (key == "marker")      # markers out of view: empty fields, read as NaN
 
 
 def test_vicon_track_scenario_oracle_ate():
