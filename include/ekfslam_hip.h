@@ -268,11 +268,9 @@ long ekf_debug_fetch_retries(ekf_handle *h);
 /* Raw device views behind a stream synchronisation, no flush: the fused cadence's record of trajectory b (returns its
  * size; copies min(bytes, size)); `which` = 0 P_base (allocated doubles), 1 V, 2 W, 3 the mean buffer the next step reads,
  * 4 the other mean buffer, 5 (chained runs, every trajectory: b is ignored) the mean at the positions of the last chained
- * cadence, 128 doubles per trajectory (dst == NULL: the count); the words behind the row-slab pass's queue heads
- * (where a -DRS_STAMPS build leaves its time stamps). */
+ * cadence, 128 doubles per trajectory (dst == NULL: the count). */
 long ekf_debug_cad(ekf_handle *h, int b, void *dst, long bytes);
 long ekf_debug_snapshot(ekf_handle *h, int b, int which, double *dst, long count);
-int ekf_debug_read(ekf_handle *h, void *dst, long bytes);
 /* The planning arithmetic of the row-slab pass, host side only (no handle, no device): every unit of the eight per-XCD
  * work queues in hand-out order (returns their number), and the static shares (workgroups x 16 pieces x 4 ints; returns the
  * pieces of the longest share, 0 if one would need more than 16). */

@@ -1598,7 +1598,7 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
           if (!h->dcad2[i]) HIP_TRY(h, hipMalloc(&h->dcad2[i], sizeof(CadOut) * h->batch));
           if (!h->dpre[i]) HIP_TRY(h, hipMalloc(&h->dpre[i], sizeof(CadPre) * h->batch));
         }
-        if (!h->dgmu) HIP_TRY(h, hipMalloc(&h->dgmu, sizeof(double) * (128 * h->batch + 32)));   // (+ 32 words: the stamps of a -DCHAIN_STAMPS build)
+        if (!h->dgmu) HIP_TRY(h, hipMalloc(&h->dgmu, sizeof(double) * 128 * h->batch));
         // the pose rows "before the first cadence": where the previous cadence's panel launch would have left them
         launch_snap_pose(h->stream, h->dP, h->dn, h->ld, h->pstride, h->batch, n_hi, h->dprow3[h->cpar ^ 1]);
         HIP_TRY(h, hipGetLastError());
@@ -1777,17 +1777,6 @@ extern "C" int ekf_profile_read_class(ekf_handle* h, int cls, double* ms_total, 
 
 extern "C" long long ekf_profile_passes(ekf_handle* h) { return h ? (long long)h->prof_seen : -1; }
 
-// (diagnostics section of the header: the words behind the queue heads, where a -DRS_STAMPS build of
-//  k_flush_rs leaves its time stamps)
-extern "C" int ekf_debug_read(ekf_handle* h, void* dst, long bytes) {
-  if (!h || !dst) return EKF_ERR_ARG;
-  HIP_TRY(h, hipSetDevice(h->device));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  const long have = (long)sizeof(unsigned) * flush_rs_queue_words();
-  HIP_TRY(h, hipMemcpy(dst, h->dqueue, (size_t)std::min(bytes, have), hipMemcpyDeviceToHost));
-  return EKF_OK;
-}
-
 // (diagnostics section of the header; no device needed) the equal static shares of the row-slab pass for a
 // few long trajectories: out = workgroups x 16 pieces x (trajectory, slab, first strip, strips); returns the pieces of
 // the longest share (0: no table) -- tests/test_cpu_host.py checks that every strip of every slab is covered exactly once
@@ -1847,7 +1836,7 @@ extern "C" long ekf_debug_snapshot(ekf_handle* h, int b, int which, double* dst,
     case 2: src = h->dW + (size_t)b * KTOT * h->ld; have = (long)KTOT * h->ld; break;
     case 3: src = h->dmu2[h->cur] + (size_t)b * h->ld; have = h->ld; break;
     case 6: src = h->dgbuf ? h->dgbuf + (size_t)b * 84 * 88 : nullptr; have = h->dgbuf ? 84L * 88 : 0; break;   // (chained solves: the last chained block of trajectory b, 84 x 88)
-    case 5: src = h->dgmu; have = h->dgmu ? 128L * h->batch + 32 : 0; break;   // (chained solves: the means at the positions, all trajectories; then a -DCHAIN_STAMPS build's stamps)
+    case 5: src = h->dgmu; have = h->dgmu ? 128L * h->batch : 0; break;   // (chained solves: the means at the positions, all trajectories)
     default: src = h->dmu2[h->cur ^ 1] + (size_t)b * h->ld; have = h->ld; break;
   }
   if (dst && count > 0 &&

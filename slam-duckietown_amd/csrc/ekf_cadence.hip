@@ -35,31 +35,7 @@
 
 namespace ekf {
 
-// Diagnostic build (-DCAD_STAMPS): s_memtime stamps of the solve's phases for landmark slots CAD_STAMP_S0.. (3 slots x 16
-// stamps) into the record's `prow` area; tools/cad_stamps.py reads them through ekf_debug_cad.
-#ifdef CAD_STAMPS
-#ifndef CAD_STAMP_S0
-#define CAD_STAMP_S0 16
-#endif
-#define CSTAMP(w, s, k)                                                                          \
-  do {                                                                                           \
-    if (wave == (w) && (s) >= CAD_STAMP_S0 && (s) < CAD_STAMP_S0 + 3) {                          \
-      __builtin_amdgcn_sched_barrier(0);                                                         \
-      unsigned long long t_;                                                                     \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                \
-      __builtin_amdgcn_sched_barrier(0);                                                         \
-      if (lane == 0) reinterpret_cast<unsigned long long*>(&o.prow[0][0])[((s) - CAD_STAMP_S0) * 16 + (k)] = t_;   \
-    }                                                                                            \
-  } while (0)
-#else
-#define CSTAMP(w, s, k) do { } while (0)
-#endif
-
-#ifndef CAD_KS_WAVES_OVERRIDE
 constexpr int CAD_KS_WAVES = 512;       // panel launches of up to this many waves of state indices take the row-split form
-#else
-constexpr int CAD_KS_WAVES = CAD_KS_WAVES_OVERRIDE;   // (diagnostic builds: the row-split form everywhere / nowhere)
-#endif
 typedef double v2d_u __attribute__((ext_vector_type(2), aligned(8)));   // two adjacent doubles, 8-byte aligned: one 16-byte load
 constexpr int CAD_CS = 88;              // LDS row stride of the block (doubles): 83 columns, rows 16-byte aligned
 constexpr int CAD_ROWS = 84;
@@ -513,7 +489,6 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
   const int ds = wave == 0 ? 0 : wave - 1;             // down-date slot of this wave (waves 0, 2 .. CAD_NW - 2)
   if (wave == 1) motion(0);
   WG_LDS_BARRIER();
-#ifndef CAD_STAMPS
   if (wave == 0) {                                     // (diagnostic record) rows 0, 1 of the block before the cadence
     if (lane < CU) {
       o.prow[0][lane] = Pc[0][lane];
@@ -524,7 +499,6 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
       o.prow[1][64 + lane] = 64 + lane < CU ? Pc[1][64 + lane] : 0.0;
     }
   }
-#endif
 
   double dd0 = 0.0, dd1 = 0.0;                         // (wave 0, lanes 0..2) in-place change of P_base(0, l), P_base(1, l)
   for (int t = 0; t < nsteps; ++t) {
@@ -586,8 +560,6 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
       const bool two_j = pa + 2 > 64;                  // columns 64.. still in use
       const bool last = j + 1 == m && t + 1 == nsteps; // nothing reads the block after this landmark
       double2 hpa = make_double2(0.0, 0.0), hpb = make_double2(0.0, 0.0);   // (H P)[:, l] of this wave's columns
-      CSTAMP(0, s, 0);
-      CSTAMP(1, s, 8);
       if (wave == 0) {
         // phase A: rows sel = {0, 1, 2, pa, pa + 1} of P at column l give (H P)[:, l]; P is symmetric, so P H^T is the
         // transpose and the gain needs no second product
@@ -629,7 +601,6 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
           hpS[64 + lane] = hpb;
         }
         WAVE_LDS_SYNC();
-        CSTAMP(0, s, 1);
         // phase B: S = H P H^T + Q (:473) from the five pairs at sel, every lane redundantly
         double2 hv[5];
 #pragma unroll
@@ -651,23 +622,15 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
           siS[0] = make_double2(i00, i01);
           siS[1] = make_double2(i10, i11);
         }
-        CSTAMP(0, s, 2);
       }
-      CSTAMP(0, s, 3);
-      CSTAMP(1, s, 9);
       WG_LDS_BARRIER();                                // b1: K, (H P) and S^-1 of this landmark are in LDS
-      CSTAMP(0, s, 4);
-      CSTAMP(1, s, 10);
       if (wave == 1) {
         // the mean (:476); then the next landmark's Jacobian at the new mean, or the next step's motion model
         const double2 k0 = kcS[lane], k1 = kcS[64 + lane];
         if (lane < pa + 2) mu0 += k0.x * y0 + k0.y * y1;
         if (64 + lane < pa + 2) mu1 += k1.x * y0 + k1.y * y1;
-        CSTAMP(1, s, 13);
-#ifndef CADS_SKIP_JAC                                    /* diagnostic build: no re-linearisation (wrong results) */
         if (j + 1 < m) jacobian_at_mean(pa - 2, (s + 1) & 1);
         else if (t + 1 < nsteps) motion(t + 1);
-#endif
       } else if (rec_wave) {
         // the record of this landmark for the panel kernel, and the pose's own entries of the new ranks
         double2* rec2 = reinterpret_cast<double2*>(o.rec + G::rec_off(s));
@@ -683,11 +646,7 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
           vw[0] = hp;
           vw[1] = make_double2(-ka.x, -ka.y);
         }
-#ifdef CADS_SKIP_DD                                     /* diagnostic build: the block is never down-dated (wrong results) */
-      } else if (false) {
-#else
       } else if (CHAIN || !last) {                     // (CHAIN: the last landmark too -- the pose block behind it is a result)
-#endif
         // down-date (:480) of what lives on: P[r][l] -= K[r, :] . (H P)[:, l] for r, l < pa; rows ds, ds + CAD_DW, ... are
         // this wave's.  Every access is unconditional and every address one base plus a compile-time offset: a row or a
         // column >= pa is dead (nothing reads it again), so what lands there does not matter, and rows up to
@@ -733,17 +692,12 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
           }
         }
       }
-      CSTAMP(0, s, 5);
-      CSTAMP(1, s, 11);
       WG_LDS_BARRIER();                                // b2: block down-dated; next Jacobian (or the next step's G) published
-      CSTAMP(0, s, 6);
       if (wave == 1 && j + 1 < m) {
         const double2 z = zS[s + 1];
         innovation(lg, z.x, z.y, y0, y1);
         if (lane == 0) yS[(s + 1) & 1] = make_double2(y0, y1);
       }
-      CSTAMP(1, s, 12);
-      CSTAMP(0, s, 7);
     }
     if (m == 0) {                                      // (uniform) no landmark whose tail could carry the next motion model
       if (wave == 1 && t + 1 < nsteps) motion(t + 1);
@@ -975,16 +929,6 @@ __device__ __forceinline__ void fnmac_row_bcast(double& x, double k, double e) {
 // PER READ -- lane l takes row 16 g + (l & 15) of group g -- and handed to the FMAs by the DPP broadcast within each row of 16
 // lanes: <= 6 reads per landmark; N = 2000 x 32: 75 - 77 -> 66 - 68 us (profiles/r06_panel_launch.txt).  The same fused
 // operations in the same order as the broadcast reads of k_panels_cad_ks: the shapes still agree bit for bit.
-#ifdef CADP_STAMPS                                      /* diagnostic build: s_memtime stamps of one wave of the panel launch, printed */
-#define PSTAMP(k)                                                                  \
-  do {                                                                             \
-    __builtin_amdgcn_sched_barrier(0);                                             \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pst_[k])::"memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                             \
-  } while (0)
-#else
-#define PSTAMP(k) do { } while (0)
-#endif
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void k_panels_cad(double* __restrict__ P, double* __restrict__ V,
                                                         double* __restrict__ W, const double* __restrict__ mu_in,
@@ -1022,16 +966,6 @@ __global__ __launch_bounds__(64 * NW) void k_panels_cad(double* __restrict__ P, 
   const bool actw = act && i >= 3;                     // the pose's state indices are the solve's
   const bool busy = nslots > 0 || npred > 0;           // (uniform) this trajectory does something in this cadence
   const bool live = i0 < neff && i0 < n && busy;       // (uniform) this wave replays
-#ifdef CADP_STAMPS
-  unsigned long long pst_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-  PSTAMP(0);
-#ifdef CADP_STAGGER                                     /* diagnostic build: every other workgroup starts late (x 3.4 us) */
-  if (NW == 4 && (blockIdx.x & 1)) {
-#pragma unroll
-    for (int z = 0; z < CADP_STAGGER; ++z) __builtin_amdgcn_s_sleep(127);
-  }
-#endif
   // The records of the cadence (what a workgroup shares) are REQUESTED first, then the gather -- nothing of it depends on the
   // staged records -- and only then are the records written to LDS: one memory round trip for both.  (Round 6.  The staging loop
   // used to follow the gather and wait for every load in flight at each of its eight iterations: nine round trips.)
@@ -1074,10 +1008,6 @@ __global__ __launch_bounds__(64 * NW) void k_panels_cad(double* __restrict__ P, 
 #pragma unroll
       for (int a = 3; a < CU; a += 2) {
         const int c0 = o.C[a], c1 = o.C[a + 1];
-#ifdef CADP_SKIP_GATHER                                 /* diagnostic build: every gather reads the row direction */
-        X[a] = Pb[p_index(ld, min(c0, 2), ii)];
-        X[a + 1] = Pb[p_index(ld, min(c1, 2), ii)];
-#else
         // entry (c, ii) for ii >= c, (ii, c) below it (positions beyond the cadence's carry index 0: row 0, which nothing uses)
         const long u0 = (long)c0 * p_lds(ld) + col_ii, l0 = row_ii + p_col(ld, c0);
         const long u1 = (long)c1 * p_lds(ld) + col_ii, l1 = row_ii + p_col(ld, c1);
@@ -1094,7 +1024,6 @@ __global__ __launch_bounds__(64 * NW) void k_panels_cad(double* __restrict__ P, 
           X[a] = *q0;                                  // (without the column gather the mirrored pairs of neighbouring landmarks
           X[a + 1] = *q1;                              //  share cache lines: through the caches)
         }
-#endif
       }
     };
     if (colbuf) gather(std::true_type{});
@@ -1103,7 +1032,6 @@ __global__ __launch_bounds__(64 * NW) void k_panels_cad(double* __restrict__ P, 
 #pragma unroll
     for (int a = 0; a < CU; ++a) X[a] = 0.0;
   }
-  PSTAMP(1);
   if (stage) {
 #pragma unroll
     for (int q = 0; q < SQ; ++q)
@@ -1126,9 +1054,7 @@ __global__ __launch_bounds__(64 * NW) void k_panels_cad(double* __restrict__ P, 
       sG[tid] = make_double2(sgx, sgy);
     }
   }
-  PSTAMP(2);
   __syncthreads();
-  PSTAMP(3);
   if (i0 >= n) return;
   if (!live) {
     // beyond the active bound the rows and columns of P are exactly zero off the diagonal (and an idle trajectory appends
@@ -1165,11 +1091,6 @@ __global__ __launch_bounds__(64 * NW) void k_panels_cad(double* __restrict__ P, 
   // (the slots as a compile-time sequence: s, and with it every index of X and of the records, is a constant)
   auto slot = [&](auto sc) {
     constexpr int s = decltype(sc)::value;
-    if constexpr (s == 0) PSTAMP(4);
-    if constexpr (s == 1) PSTAMP(5);
-    if constexpr (s == 10) PSTAMP(6);
-    if constexpr (s == 20) PSTAMP(7);
-    if constexpr (s == 30) PSTAMP(8);
     if (s >= s0) {                                     // (uniform)
       predictions_before(s);
       constexpr int pa = G::pa(s), off = G::rec_off(s);
@@ -1196,11 +1117,7 @@ __global__ __launch_bounds__(64 * NW) void k_panels_cad(double* __restrict__ P, 
       const double f0 = e0 * s01.x + e1 * s23.x;       // K_s[i, :] = (H_s P_s)[:, i]^T S^-1  (P symmetric)
       const double f1 = e0 * s01.y + e1 * s23.y;
       dm += f0 * yy.x + f1 * yy.y;                     // :476
-#ifdef CADP_SKIP_STORE                                  /* diagnostic build: no rank stores (a value that is never -7 keeps e, f alive) */
-      if (actw && e0 == -7.0 && f0 == -7.0) {
-#else
       if (actw) {
-#endif
         Vb[(long)kr * ld + i] = e0;
         Vb[(long)(kr + 1) * ld + i] = e1;
         if (!skipw) {                                  // (uniform)
@@ -1210,11 +1127,7 @@ __global__ __launch_bounds__(64 * NW) void k_panels_cad(double* __restrict__ P, 
       }
       // x[a] -= K_s[C_u[a], :] . (H_s P_s)[:, i], what lives on (behind the last slot: the pose rows, for the predictions of
       // steps that observe nothing)
-#ifdef CADP_SKIP_DD                                     /* diagnostic build: only the rows the next landmark reads are down-dated */
-      constexpr int ND = pa < 5 ? pa : 5;
-#else
       constexpr int ND = pa;
-#endif
       // X[a] = fma(-K[a].x, e0, X[a]); X[a] = fma(-K[a].y, e1, X[a]) -- per group of 16 rows first every e0 term, then every e1
       // term (the order within a row is what it was; two dependent DPP operations back to back cost a wait state each)
       static_for_slots([&](auto gc) {
@@ -1231,7 +1144,6 @@ __global__ __launch_bounds__(64 * NW) void k_panels_cad(double* __restrict__ P, 
     }
   };
   static_for_slots(slot, std::make_integer_sequence<int, GM>{});
-  PSTAMP(9);
   predictions_before(GM);                              // steps behind the last landmark
   if (actw) {
     for (int k = 2 * nslots; k < nrp; ++k) {           // fewer ranks than the bank's busiest trajectory (and the k-tile pad): zeros
@@ -1246,14 +1158,6 @@ __global__ __launch_bounds__(64 * NW) void k_panels_cad(double* __restrict__ P, 
       for (int a = 0; a < 3; ++a) prow3[((long)b * 3 + a) * ld + i] = X[a];
     }
   }
-#ifdef CADP_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  PSTAMP(10);
-  if (NW == 4 && (blockIdx.x == 7 || blockIdx.x == 1) && (b == 5 || b == 20) && tid == 64 && nslots == GM)
-    printf("PST bx %d b %d: gather-issued %llu staged %llu barrier %llu slot0 %llu slot1 %llu slot10 %llu slot20 %llu slot30 %llu end-slots %llu drained %llu\n",
-           (int)blockIdx.x, b, pst_[1] - pst_[0], pst_[2] - pst_[0], pst_[3] - pst_[0], pst_[4] - pst_[0], pst_[5] - pst_[0], pst_[6] - pst_[0],
-           pst_[7] - pst_[0], pst_[8] - pst_[0], pst_[9] - pst_[0], pst_[10] - pst_[0]);
-#endif
   if (blockIdx.x == 0 && wave == 0) pose_epilogue(o, Pb, Vb, Wb, so, queue, b, ld, lane, nrp, tail_word, tail_target, flags, start_sigma);
 }
 
@@ -1489,22 +1393,6 @@ __global__ __launch_bounds__(256) void k_panels_cad_ks(double* __restrict__ P, d
 // workgroup forms its coefficients; a POSITIONS workgroup forms the inputs of the cadence after the next (CadPre).
 // Operands in LDS.  One chain workgroup per trajectory.
 // ---------------------------------------------------------------------------------------------
-// Diagnostic build (-DCHAIN_STAMPS): s_memtime stamps of k_chain_cad's phases (wave 0 of trajectory 0) behind the means in gmu
-// (batch x 128 doubles, then 32 stamps); tools/chain_stamps.py reads them through ekf_debug_snapshot(which = 5).
-#ifdef CHAIN_STAMPS
-#define CHSTAMP(k)                                                                               \
-  do {                                                                                           \
-    if (wave == 0 && b == 0) {                                                                   \
-      __builtin_amdgcn_sched_barrier(0);                                                         \
-      unsigned long long t_;                                                                     \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                \
-      __builtin_amdgcn_sched_barrier(0);                                                         \
-      if (lane == 0) reinterpret_cast<unsigned long long*>(gmu + (long)batch * 128)[k] = t_;     \
-    }                                                                                            \
-  } while (0)
-#else
-#define CHSTAMP(k) do { } while (0)
-#endif
 constexpr int CH_NC = 80;               // columns: the landmark positions of the next cadence (5 MFMA tiles)
 constexpr int CH_S = 81;                // LDS row stride of A (odd: rows and columns both spread over the banks)
 constexpr int CH_R = 96;                // rows of the padded operands (6 MFMA tiles: 80 rank rows, the 3 pose rows)
@@ -1783,7 +1671,6 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_chain_cad(const double* __restr
   const int nk = min(op.nslots, CAD_SLOTS), s0k = CAD_SLOTS - nk;   // this cadence: landmarks, first slot
   // this launch runs: the solve in front of it on the stream has completed -- what the gate on the other stream waits for
   if (tid == 0) __hip_atomic_store(sync + SYNC_SOLVE * SYNC_STRIDE, sigma, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  CHSTAMP(0);
   chain_stage_records(op, nk, s0k, R, tid);
   int nslots;
   if (pre_in) {                                        // (uniform) the next cadence's positions, formed one cadence ahead
@@ -1799,10 +1686,8 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_chain_cad(const double* __restr
     for (int e = tid; e < CH_R * CH_CS / 2; e += 64 * CAD_NW) z[e] = make_double2(0.0, 0.0);
   }
   __syncthreads();
-  CHSTAMP(1);
   chain_coefficient_blocks(op, nk, s0k, R, Cm, tid);
   __syncthreads();
-  CHSTAMP(2);
   const int li = lane & 15, lq = lane >> 4;
   // ---- the diagonal blocks: Linv_i = (I + C_ii)^-1 by substitution on the identity (wave i, a column per lane), then
   // Linv_i C_{i,<i} in place (tiles of 16 x 16 over the waves) -- so that a block step of the solve is ONE product ----
@@ -1812,7 +1697,6 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_chain_cad(const double* __restr
   }
   chain_invert_diagonal(Cm, Li, wave, lane);
   __syncthreads();
-  CHSTAMP(3);
   // ---- the gathered rows: everything this workgroup reads of them is requested here, the products below run under the
   // round trip ----
   constexpr int RQ = (CAD_ROWS + CAD_NW - 1) / CAD_NW;               // rows per wave (11)
@@ -1848,7 +1732,6 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_chain_cad(const double* __restr
     lb1[u] = hb ? ld_dev(xgb + (long)(paq + 1) * CAD_CS + jb) : 0.0;
   }
   chain_scale_blocks(Cm, Li, nk, wave, lane);
-  CHSTAMP(4);
   // ---- the right-hand side A X, row by row: A_q = H_q[:, 0..2] G^{(q,-1)} at the pose positions, H_q[:, 3..4] at the landmark's
   // own -- five rows of X per landmark, each landmark row of X read exactly once (straight from xg, coalesced); the pose rows
   // behind the cadence start from G^{(end,-1)} X[0..2].  Columns over lanes (64 + 16), landmarks over waves ----
@@ -1881,7 +1764,6 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_chain_cad(const double* __restr
     }
   }
   __syncthreads();
-  CHSTAMP(5);
   // ---- Linv_i (A X)_i in place: 5 blocks x 5 column tiles over the waves ----
   for (int job = wave; job < 25; job += CAD_NW) {
     const int i = job / 5, ct = job - 5 * i;
@@ -1895,7 +1777,6 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_chain_cad(const double* __restr
     }
   }
   __syncthreads();
-  CHSTAMP(6);
   // ---- the block steps: E_i = Linv_i (A X)_i - (Linv_i C_{i,<i}) E_{<i}; i = 5: the pose rows A_end X - C_end E.  One column
   // tile per wave (waves 0..4), the landmarks solved so far as k ----
   for (int i = 1; i <= 5; ++i) {
@@ -1916,7 +1797,6 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_chain_cad(const double* __restr
       __syncthreads();
     }
   }
-  CHSTAMP(7);
   // ---- -F = -(E S^-1) per landmark: f = e S^-1 is K at the position (P symmetric), W = -f; and the mean update's partial sums ----
   for (int e = tid; e < 5 * CH_NC; e += 64 * CAD_NW) {
     const int g8 = e / CH_NC, c = e - g8 * CH_NC;
@@ -1935,7 +1815,6 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_chain_cad(const double* __restr
     dmS[g8][c] = dm;
   }
   __syncthreads();
-  CHSTAMP(8);
   // the mean at C' (src/replay_no_ros.py:476 summed over the cadence): mean_0 + sum_q f_q . y_q
   if (tid < 128) {
     double v = 0.0;
@@ -1966,7 +1845,6 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_chain_cad(const double* __restr
     }
   }
   __syncthreads();
-  CHSTAMP(9);
 #pragma unroll
   for (int u = 0; u < TPW; ++u) {
     const int t = wave + CAD_NW * u;
@@ -2009,7 +1887,6 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_chain_cad(const double* __restr
       }
     }
   }
-  CHSTAMP(10);
 }
 
 // ---------------------------------------------------------------------------------------------

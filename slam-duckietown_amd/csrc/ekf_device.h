@@ -33,16 +33,10 @@ __host__ __device__ constexpr int ranks_for(int mcap) { return 2 * mcap; }
 // strip never straddles a panel (4096 is a multiple of 64), so a kernel that walks a row strip by strip only needs the
 // strip's column offset p_col(ld, j0) and the row stride p_lds(ld).  V, W and the mean keep the plain stride ld.
 constexpr int PPW = 4096;
-#ifdef P_ROWMAJOR_PROBE                                  /* diagnostic build: the plain row-major layout at every size (A/B timing) */
-__host__ __device__ __forceinline__ int p_lds(int ld) { return ld; }
-__host__ __device__ __forceinline__ long p_col(int ld, int j) { return j; }
-__host__ __device__ __forceinline__ unsigned p_col8(int ld, unsigned j) { return j * 8u; }
-#else
 __host__ __device__ __forceinline__ int p_lds(int ld) { return ld < PPW ? ld : PPW; }
 __host__ __device__ __forceinline__ long p_col(int ld, int j) { return (long)(j >> 12) * ((long)ld * PPW) + (j & (PPW - 1)); }
 // the same as a 32-bit byte offset (ekf_create bounds one covariance by 4 GiB)
 __host__ __device__ __forceinline__ unsigned p_col8(int ld, unsigned j) { return (j >> 12) * ((unsigned)ld * (unsigned)(PPW * 8)) + (j & (unsigned)(PPW - 1)) * 8u; }
-#endif
 __host__ __device__ __forceinline__ long p_index(int ld, int i, int j) { return p_col(ld, j) + (long)i * p_lds(ld); }
 // panels / doubles allocated per trajectory (every panel keeps all `rows` rows: downloads and the dense product get the
 // mirrored matrix in place)
@@ -97,9 +91,6 @@ struct alignas(16) SolveHead {
 };
 struct alignas(16) SolveOut : SolveHead {
   SolveIter it[MMAX];
-#ifdef EKF_STAMPS
-  unsigned long long stamps[128];   // diagnostic build only (tools/solve_probe.hip)
-#endif
 };
 static_assert(sizeof(SolveHead) % 16 == 0, "SolveHead must stay 16-byte granular");
 // (SolveOut = head, then the records: `it` starts at sizeof(SolveHead))

@@ -22,20 +22,6 @@
 
 #include "ekf_device.h"
 
-// Diagnostic stamps (tools/solve_probe.hip builds with -DEKF_STAMPS); compiled out of the product.
-#ifdef EKF_STAMPS
-#define STAMP(o, i)                                                                          \
-  do {                                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                       \
-    unsigned long long t_;                                                                   \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");               \
-    __builtin_amdgcn_sched_barrier(0);                                                       \
-    if (threadIdx.x == 0) (o).stamps[i] = t_;                                                \
-  } while (0)
-#else
-#define STAMP(o, i) do { } while (0)
-#endif
-
 #include "ekf_devfn.h"
 #include "ekf_host_plan.h"
 
@@ -157,7 +143,6 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
   auto& Cs = L.Cs;
   auto& hS = L.hS;
 
-  STAMP(o, 0);
   // inputs: the index list is fetched unconditionally so that it travels with flags/m (one round trip)
   const int my_idx = (lane >= 3 && lane < CMAX) ? s.idx[(lane - 3) >> 1] : 0;
   const bool do_pred = (s.flags & FLAG_PREDICT) != 0;
@@ -182,7 +167,6 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
 #pragma unroll
   for (int sh = 32; sh > 0; sh >>= 1) cmax = max(cmax, __shfl_xor(cmax, sh));
   WG_LDS_BARRIER();
-  STAMP(o, 1);
   // current P[C,C] = P_base[C,C] + W[C,:] V[:,C] + diag(dacc): the base loads are issued first ...
   // (thread = (wave w, lane): column C[lane] of rows w, w+4, ...: no integer division on the path)
   constexpr int GQ = (CMAX + 3) / 4;                   // 9 rows per wave at most
@@ -199,7 +183,6 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
       gv[q] = Pb[p_index(ld, min(Cr, Cl), max(Cr, Cl))];                       // the upper triangle is authoritative
     }
   }
-  STAMP(o, 110);
   // ... then waves 0-2 gather the pending factors at C while wave 3 runs the motion model
   // (src/replay_no_ros.py:368-417; two sincos, a division and a wrap: ~1900 cycles of a lone wave)
   StageRegs SR;
@@ -238,7 +221,6 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
       L.mot[4] = g1;
     }
   }
-  STAMP(o, 112);
   if (kbase > 0) {
     if (gw < 3) {
       stage_commit(SR, c, kbase, 0, gw, lane, F, writer ? fac_b : nullptr);
@@ -249,7 +231,6 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
     }
     WG_LDS_BARRIER();
   }
-  STAMP(o, 113);
   // pending ranks: M = W[C,:] V[:,C] (c x c, 16x16 tiles dealt to the four waves, v_mfma_f64_16x16x4 with both
   // operands straight from the staged factors, four k-tiles of fragments fetched per round trip to LDS), parked in
   // Pc; entry (r, l) of the gathered block then takes M[r][l] where P(C[r], C[l]) is stored that way round and
@@ -304,7 +285,6 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
       }
     }
     WG_LDS_BARRIER();
-    STAMP(o, 114);
 #pragma unroll
     for (int q = 0; q < GQ; ++q) {
       const int r = gw + 4 * q;
@@ -409,10 +389,8 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
       if (__any(bad) && lane == 0) atomicOr(flag_b, EKF_FLAG_NONFINITE);
     }
   } else {
-  STAMP(o, 2);
   const double rd0 = do_pred ? cfg.rd[0] : 0.0, rd1 = do_pred ? cfg.rd[1] : 0.0,
                rd2 = do_pred ? cfg.rd[2] : 0.0;
-  STAMP(o, 3);
   // P'[C,C] = Gc P[C,C] Gc^T + Rt  (:428-430 restricted to C).  Only rows 0,1 and columns 0,1 of the block change
   // (row ops X = Gc P on rows 0,1 with row 2, then column ops X Gc^T on columns 0,1 with column 2 of X), and the
   // gathered block is exactly symmetric: lane r holds P[0..2][r] = P[r][0..2] and produces P'[r][0], P'[r][1],
@@ -465,7 +443,6 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
   }
   WG_LDS_BARRIER();                                    // S0 (helper waves wait here too)
 
-  STAMP(o, 4);
   // ---- sequential per-landmark recurrences (:436-480) on the compressed system ----
   double h[2][5];
   if (m > 0) {                                         // landmark 0 was linearised by wave 1
@@ -476,11 +453,9 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
       h[1][k] = t.y;
     }
   }
-  STAMP(o, 5);
   for (int j = 0; j < m; ++j) {
     const int a = 3 + 2 * j;
     SolveIter& it = its[j];
-    STAMP(o, 8 + 6 * j);
     // phase A: rows sel of P_j at column C[lane] give (H P)[:, C[lane]]; P is symmetric (only its upper
     // triangle is stored), so P H^T is the transpose and the gain needs no second product.
     // The instruction count is what matters for a lone wave: S is formed from the five hp pairs the
@@ -496,7 +471,6 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
     }
     if (on) hpS[lane] = make_double2(hp0, hp1);
     WAVE_LDS_SYNC();
-    STAMP(o, 9 + 6 * j);
     // phase B: S = H P H^T + Q (:473), every lane redundantly
     double2 hv[5];
 #pragma unroll
@@ -522,10 +496,8 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
       *reinterpret_cast<double2*>(&it.si[2]) = make_double2(i10, i11);
     }
     WG_LDS_BARRIER();                                  // b1(j): wave 1 starts the next linearisation
-    STAMP(o, 10 + 6 * j);
     // phase C: down-date (:480), this wave's third of the rows (waves 2, 3 take the others, wave 1 linearises
     // landmark j+1 meanwhile)
-    STAMP(o, 11 + 6 * j);
     if (j + 1 < m) downdate_rows(0, make_double2(hp0, hp1));
     WG_LDS_BARRIER();                                  // b2(j)
     if (j + 1 < m) {
@@ -536,9 +508,7 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
         h[1][k] = t.y;
       }
     }
-    STAMP(o, 12 + 6 * j);
   }
-  STAMP(o, 6);
   }   // wave 0
 }
 
@@ -706,11 +676,7 @@ __device__ __forceinline__ void panel_base_gather(const PanelIdx& t, const int* 
 #pragma unroll
   for (int a = 0; a < CC; ++a) {
     const int row = Crow[a];
-#ifdef PANELS_SKIP_COLG                                 /* diagnostic build: no column-direction gathers */
-    X[a] = t.Pb[p_index(t.ld, min(row, t.i0), max(row, t.ii))];
-#else
     X[a] = t.Pb[p_index(t.ld, min(row, t.ii), max(row, t.ii))];
-#endif
   }
 }
 // Beyond the active bound the rows and columns of P are exactly zero off the diagonal: this step's ranks are zero
@@ -1071,11 +1037,7 @@ __device__ __forceinline__ void panels_mono(double* __restrict__ P, double* __re
 #pragma unroll
     for (int a = 0; a < CC; ++a) {
       const int row = early ? __builtin_amdgcn_readlane(Cl, a) : o.C[a];
-#ifdef PANELS_SKIP_COLG                                 /* diagnostic build: no column-direction gathers */
-      X[a] = Pb[p_index(ld, min(row, i0), max(row, ii))];
-#else
       X[a] = Pb[p_index(ld, min(row, ii), max(row, ii))];
-#endif
     }
   } else {
 #pragma unroll
@@ -1185,12 +1147,10 @@ __device__ __forceinline__ void panels_mono(double* __restrict__ P, double* __re
     }
   }
   };
-#ifndef PANELS_SKIP_PEND                                  /* diagnostic build: no pending-rank gather */
   if (kb > 0) {                                        // (uniform) right after a covariance pass nothing is pending
     if (cmaxv > i0) gather_pending(std::true_type{});
     else gather_pending(std::false_type{});
   }
-#endif
   if constexpr (SPLIT) {
     if (early) {
       // Wait for the solve of this trajectory (every wave for itself: some waves of the last block have left), then
@@ -1768,9 +1728,6 @@ __device__ __forceinline__ double2 ldb16(__amdgpu_buffer_rsrc_t rs, unsigned lan
 // profiles/r04_pass_drift.txt; round 3 had measured "no difference" on single runs).
 template <bool NT>
 __device__ __forceinline__ void stb16(__amdgpu_buffer_rsrc_t rs, unsigned lane_bytes, unsigned tile_bytes, double2 v) {
-#ifdef RS_SKIP_PMEM
-  if (v.x == 1.2345e-300) /* never: keeps the value alive, drops the traffic */
-#endif
   {
   const uint2v_t a = __builtin_bit_cast(uint2v_t, v.x), b = __builtin_bit_cast(uint2v_t, v.y);
   const uint4v_t d{a.x, a.y, b.x, b.y};
@@ -1779,20 +1736,6 @@ __device__ __forceinline__ void stb16(__amdgpu_buffer_rsrc_t rs, unsigned lane_b
   }
 }
 #define RS_CBAR() asm volatile("" ::: "memory")
-// Diagnostic build (-DRS_STAMPS): wave 0 of every workgroup records s_memtime at fixed points of its first units into
-// the words behind the queue heads (tools/rs_stamps.py reads them through ekf_debug_read).
-#ifdef RS_STAMPS
-#define RS_STAMP(k)                                                                             \
-  do {                                                                                          \
-    if (wave == 0 && unit_no < 3) {                                                             \
-      unsigned long long t_;                                                                    \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                \
-      if (lane == 0) stamp_buf[unit_no * 20 + (k)] = t_;                                        \
-    }                                                                                           \
-  } while (0)
-#else
-#define RS_STAMP(k) do { } while (0)
-#endif
 
 // (the work queues and the equal static shares of k_flush_rs: plain integer code for host and device, ekf_host_plan.h)
 // PAN: the covariance lies in column panels (ld > 4096); otherwise the column offset of a strip is plain j * 8 -- the
@@ -1834,10 +1777,6 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
   // next unit: own queue first, then the others (thread 0 only; -1 = every queue is empty).  While the own queue has
   // units the head is bumped without looking first (one round trip instead of two); a queue found empty is only
   // looked at from then on (the heads are never bumped far beyond their counts).
-#ifdef RS_STAMPS
-  unsigned long long* stamp_buf = reinterpret_cast<unsigned long long*>(queue + 8 * RS_QSTRIDE) + blockIdx.x * 64;
-  int unit_no = -1;
-#endif
   bool own_empty = false;
   // a unit from this XCD's queue, else from the next non-empty one (see rs_queue_count / rs_queue_unit)
   auto pop = [&]() -> int {
@@ -1858,12 +1797,7 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
   };
   int piece = 0;                                       // (mode 4) next piece of this workgroup's share
   for (;;) {
-#ifdef RS_STAMPS
-    ++unit_no;
-#endif
-    RS_STAMP(0);
     __syncthreads();                                   // every wave is done with the LDS of the previous unit
-    RS_STAMP(1);
     int b, rb, u_start, u_count;                       // the unit: strips [u_start, u_start + u_count) of slab rb of trajectory b
     if (mode == 4) {                                   // equal static shares: this workgroup's own list, no queue
       if (piece >= RS_PIECES) return;
@@ -1885,7 +1819,6 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
       u_count = code == 1023 ? (1 << 20) : cs_arg;     // strips per unit: the whole slab, or a chunk of it
       u_start = code == 1023 ? 0 : code * cs_arg;
     }
-    RS_STAMP(2);
     const int n = min(nact[b], so[b].neff);            // rows/cols beyond the active bound are untouched
     const int i0 = rb * RS_ROWS;
     if (i0 >= n) continue;
@@ -1958,11 +1891,7 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
       return prow + (PAN ? p_col8(ld, j) : j * 8u);
     };
     auto gload = [&](int t) {
-#ifdef RS_SKIP_PMEM                                     /* diagnostic build: the compute side alone */
-      const bool ok = false;
-#else
       const bool ok = t < Sw;
-#endif
       const __amdgpu_buffer_rsrc_t rs = rs_rsrc(ok ? (const void*)Pb : (const void*)so);
       const unsigned off = ok ? tile_off(t) : 0u, ld8d = ok ? pl8 : 0u, loffd = ok ? loff : lane8 * 2u;
 #pragma unroll
@@ -1977,7 +1906,6 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
     // fragments of the NEXT tile): the reads of the next k-tile are always in flight under this one's MFMAs
     double bf[2][4];
 
-    RS_STAMP(3);
     // ---- prologue: W fragments, strip 0, tile 0 -> accs[0], tile 1 in flight ----
     {
       double vs[RPW];
@@ -2016,11 +1944,9 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
         }
       }
       stage_store(vbuf[0], I0_{}, IR_{}, vs);
-      RS_STAMP(4);
 #pragma unroll
       for (int q = 0; q < 8; ++q) *reinterpret_cast<double2*>(&T[rm_base + 128 * q]) = g[q];
       RS_CBAR();
-      RS_STAMP(5);
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
@@ -2028,7 +1954,6 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
       RS_CBAR();
       gload(1);
       wg_barrier();
-      RS_STAMP(6);
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) bf[0][ct] = vbuf[0][ct * 64 + lane];
     }
@@ -2056,11 +1981,7 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
                     OC = OE2B + NE, OVB = OC, ON1 = OVB + NV, ON3 = ON1 + 8, ON2 = ON3 + 8, OWB = ON2 + 16, NSIDE = OWB + NV;
       const __amdgpu_buffer_rsrc_t rsP = rs_rsrc(Pb);
       const unsigned off_prev = tile_off(t - 1);       // tile t-1 (FIRST: unused)
-#ifdef RS_SKIP_PMEM
-      const bool ok2 = false;
-#else
       const bool ok2 = t + 2 < Sw;
-#endif
       const __amdgpu_buffer_rsrc_t rs2 = rs_rsrc(ok2 ? (const void*)Pb : (const void*)so);
       const unsigned off2 = ok2 ? tile_off(t + 2) : 0u, ld8d = ok2 ? pl8 : 0u, loffd = ok2 ? loff : lane8 * 2u;
       double* vnext = vbuf[(t + 1) & 1];
@@ -2112,11 +2033,7 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
         __builtin_amdgcn_sched_barrier(0);             // (the scheduler would sink the reads below the MFMAs to reuse registers)
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
-#ifdef RS_SKIP_MFMA                                     /* diagnostic build: the memory side alone */
-          acc[ct][0] += wf[kt] * bf[kt & 1][ct];
-#else
           acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(wf[kt], bf[kt & 1][ct], acc[ct], 0, 0, 0);
-#endif
         if (kt == 0) {
           if (NV) side(OVA);
         } else if (kt < NKT - 1) {
@@ -2161,17 +2078,11 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
       body(T_{}, F_{}, P0{}, 0);
     } else {
       body(T_{}, T_{}, P0{}, 0);
-      RS_STAMP(7);
       int t = 1;
       for (; t + 1 < S - 1; t += 2) {
         body(F_{}, T_{}, P1{}, t);
-        if (t == 1) RS_STAMP(8);
         body(F_{}, T_{}, P0{}, t + 1);
-        if (t == 1) RS_STAMP(9);
-        if (t == 3) RS_STAMP(10);
-        if (t == 5) RS_STAMP(11);
       }
-      RS_STAMP(12);
       if (t < S - 1) {                                 // (t is odd here)
         body(F_{}, T_{}, P1{}, t);
         ++t;
@@ -2181,13 +2092,8 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
         else body(F_{}, F_{}, P0{}, S - 1);
       }
     }
-    RS_STAMP(13);
     if ((Sw - 1) & 1) drain(P1{});
     else drain(P0{});
-    RS_STAMP(14);
-#ifdef RS_STAMPS
-    if (wave == 0 && lane == 0 && unit_no < 3) stamp_buf[unit_no * 20 + 15] = (unsigned long long)S;
-#endif
   }
 }
 
@@ -2657,11 +2563,7 @@ void launch_flush_rs(hipStream_t st, bool streaming, double* P, const double* V,
 #undef EKF_FLUSH_RS
 }
 
-#ifdef RS_STAMPS
-int flush_rs_queue_words() { return 8 * RS_QSTRIDE + 256 * 64 * 2; }
-#else
 int flush_rs_queue_words() { return 8 * RS_QSTRIDE; }
-#endif
 
 void launch_predict_rc(hipStream_t st, double* P, const double* mu_in, double* mu_out, const int* nact,
                        const SolveOut* so, int ld, long pstride, int batch, int n_hi) {

@@ -120,12 +120,7 @@ __device__ __forceinline__ void small_step(double* __restrict__ Pl, double* __re
     const LinGeom g = linearize_h(mu[0], mu[1], mu[2], mu[t], mu[t + 1], h);     // every thread: broadcast LDS reads
     if (tid >= NT - 64) {                                   // (wave 3) the innovation, under the other waves' (H P)
       double y0, y1;
-#ifdef SM_SKIP_INNOVATION                                /* diagnostic build (timing only, wrong results): no atan2 / wrap */
-      y0 = s.range[j] - g.sq;
-      y1 = s.bearing[j] - g.th;
-#else
       innovation(g, s.range[j], s.bearing[j], y0, y1);
-#endif
       if (tid == NT - 64) {
         sc[2] = y0;
         sc[3] = y1;
@@ -155,11 +150,7 @@ __device__ __forceinline__ void small_step(double* __restrict__ Pl, double* __re
       S10 = fma(a1, h[0][k], S10);
       S11 = fma(a1, h[1][k], S11);
     }
-#ifdef SM_FAST_RCP                                       /* diagnostic build (timing only): hardware reciprocal estimate */
-    const double rdet = __builtin_amdgcn_rcp(S00 * S11 - S01 * S10);
-#else
     const double rdet = 1.0 / (S00 * S11 - S01 * S10);
-#endif
     const double i00 = S11 * rdet, i01 = -S01 * rdet, i10 = -S10 * rdet, i11 = S00 * rdet;
     for (int c = tid; c < n; c += NT) {                     // K[c, :] = (H P)[:, c]^T S^-1   (P symmetric)
       const double a0 = hp[c], a1 = hp[n + c];
@@ -171,7 +162,6 @@ __device__ __forceinline__ void small_step(double* __restrict__ Pl, double* __re
     // P <- P - K (H P) on the upper triangle, mirrored (:480): 16 x 16 tiles (i <= j), thread (ty, tx) -> entry (16 i + ty, 16 j + tx)
     // (every load of a row of tiles is unconditional, at clamped addresses, and in flight before the first FMA; only the
     //  stores are predicated -- with the loads under the `a <= b` branch each tile was its own trip to LDS: 8 of 16 us per step)
-#ifndef SM_SKIP_UPDATE                                   /* diagnostic build (timing only, wrong results): no covariance down-date */
     {
       // ALL tiles in flight at once -- one round trip to LDS for the whole down-date
       constexpr int NTILE = TM * (TM + 1) / 2;
@@ -200,7 +190,6 @@ __device__ __forceinline__ void small_step(double* __restrict__ Pl, double* __re
           }
         }
     }
-#endif
     for (int c = tid; c < n; c += NT) mu[c] += kk[c] * y0 + kk[n + c] * y1;     // :476
     __syncthreads();
   }

@@ -73,14 +73,11 @@ class EkfConfig:
 
 
 def library_path() -> str:
-    """The in-tree library.  EKFSLAM_HIP_VARIANT=<tag> selects a diagnostic build libekfslam_hip_<tag>.so made with
-    `make -C csrc variant TAG=<tag> EXTRA=...` (kernel experiments; never set in production)."""
-    tag = os.environ.get("EKFSLAM_HIP_VARIANT")
-    if tag:
-        warnings.warn(f"EKFSLAM_HIP_VARIANT={tag}: loading the diagnostic build libekfslam_hip_{tag}.so instead of the "
-                      "product library -- such builds may knowingly compute wrong covariances (timing experiments only)",
-                      RuntimeWarning, stacklevel=2)
-    return os.path.join(_HERE, f"libekfslam_hip_{tag}.so" if tag else _LIB_NAME)
+    """The in-tree library."""
+    if os.environ.get("EKFSLAM_HIP_VARIANT"):
+        raise EkfError("EKFSLAM_HIP_VARIANT is set, but diagnostic builds of the library no longer exist: "
+                       "unset it to load the product library")
+    return os.path.join(_HERE, _LIB_NAME)
 
 
 def build_library(force: bool = False) -> str:
@@ -154,7 +151,6 @@ ABI = {
     "ekf_debug_fetch_retries": (C.c_long, [C.c_void_p]),
     "ekf_debug_cad": (C.c_long, [C.c_void_p, C.c_int, C.c_void_p, C.c_long]),
     "ekf_debug_snapshot": (C.c_long, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_long]),
-    "ekf_debug_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),
     "ekf_debug_pass_units": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_int]),
     "ekf_debug_pass_shares": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip]),
 }

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
-"""Average duration of the covariance-pass kernel (HIP events on the handle's stream) for a library variant.
-  EKFSLAM_HIP_VARIANT=<tag> python3 tools/flush_time.py [--landmarks N] [--trajectories B] [--obs m] [--option k=v ...]
-Diagnostic variants (make -C slam-duckietown_amd/csrc variant TAG=... EXTRA=-D...) may compute wrong covariances:
-nothing is checked here, only timed."""
+"""Average duration of the covariance-pass kernel (HIP events on the handle's stream).
+  python3 tools/flush_time.py [--landmarks N] [--trajectories B] [--obs m] [--option k=v ...]
+Nothing is checked here, only timed."""
 import argparse
 import os
 import sys
@@ -54,7 +53,7 @@ def main():
     ms, cnt = f.profile_read()
     tri = n * (n + 1) / 2.0
     per = ms / max(cnt, 1)
-    print(f"variant={os.environ.get('EKFSLAM_HIP_VARIANT', 'default'):10s} options={args.option} nmax={args.nmax} {'dense start ' if args.dense_start else ''}launches={cnt} "
+    print(f"options={args.option} nmax={args.nmax} {'dense start ' if args.dense_start else ''}launches={cnt} "
           f"avg={per * 1e3:8.1f} us  {B * 16.0 * tri / (per * 1e-3) / 1e12:6.3f} TB/s algorithmic")
     f.close()
 
