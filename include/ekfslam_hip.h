@@ -90,6 +90,22 @@ int ekf_download_mean(ekf_handle *h, int b, double *mu, int n);
 /* rows [r0, r0+rows) x cols [c0, c0+cols) of the covariance into out (row-major rows x cols), e.g. the 3x3
  * pose block for consistency statistics without shipping n^2 doubles.  Flushes the pending update. */
 int ekf_download_block(ekf_handle *h, int b, int r0, int c0, int rows, int cols, double *out);
+/* Marginal covariances of trajectories [b0, b0+count) without applying the pending update: pose (count x 9: the 3x3
+ * pose block, row-major) and, if landmarks != NULL, every landmark's 2x2 block (count x cap x 4, row-major; blocks
+ * beyond a trajectory's landmark count are NaN); n_landmarks (may be NULL) receives each count.  For NEES at every
+ * step, the ellipses of a plot, a pose covariance to publish: one kernel reads P_base at the blocks and the W rows / V
+ * columns of their indices over the pending ranks -- O(n k) per trajectory -- and writes pinned destinations (e.g.
+ * from ekf_host_alloc) directly, anything else through one copy.
+ * Blocking, and stream-ordered behind everything enqueued.  It runs no covariance pass and no mirror, and changes
+ * nothing that decides later scheduling: after the call the same calls give bit-identical results and the same
+ * ekf_debug_cadences / ekf_debug_chained / ekf_debug_lookaheads / ekf_profile_passes counts as without it.  The
+ * result equals a flushed ekf_download_block to rounding (the pending ranks are summed in another order), and is
+ * bit-identical where nothing is pending.  Valid on every path: per-step kernels, single-launch steps, fused cadences
+ * ended mid-cadence, chained and look-ahead runs, the small-state path.  Device-side sizes are refreshed first.
+ * EKF_ERR_ARG for a bad range, NULL pose, or cap below the largest landmark count in the range; EKF_ERR_STATE if a
+ * trajectory of the range carries EKF_FLAG_INTERNAL or an earlier call failed half way (as the other downloads). */
+int ekf_download_marginals(ekf_handle *h, int b0, int count, double *pose, double *landmarks, int cap,
+                           int *n_landmarks);
 int ekf_state_size(ekf_handle *h, int b, int *n);
 
 /* State augmentation, src/replay_no_ros.py:341-360: append k landmarks (indices must continue the

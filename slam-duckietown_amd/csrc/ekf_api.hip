@@ -61,6 +61,8 @@ void launch_panels_cad(hipStream_t, double*, double*, double*, const double*, do
                        SolveOut*, unsigned*, int, long, int, int, int, const double*, double*, unsigned*, unsigned, unsigned, unsigned*,
                        bool, unsigned, int, bool);
 bool panels_cad_latency_regime(int, int);
+void launch_marginals(hipStream_t, const double*, const double*, const double*, const double*, const int*, const SolveOut*, int,
+                      long, int, int, int, int, double*, double*);
 }  // namespace ekf
 
 using namespace ekf;
@@ -235,6 +237,8 @@ struct ekf_handle : ekf::HostPlan {
   std::vector<unsigned> flags_host;
   unsigned* h_flags = nullptr;    // pinned: the sticky flags are read back with a stream-ordered copy
   double* h_pack = nullptr;       // pinned: where k_pack_small leaves a small state (n x n covariance, mean, flags)
+  double* dmarg = nullptr;        // ekf_download_marginals: device staging of destinations that are not pinned (allocated on use)
+  size_t marg_cap = 0;            // ... its size in doubles
   // Set when an enqueueing call failed half way (e.g. a launch of the look-ahead failed after the next cadence's solve had
   // already run): the device state of every trajectory is undefined until it is uploaded again; see check_internal
   std::vector<unsigned char> host_bad;
@@ -319,7 +323,7 @@ static void free_all(ekf_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   void* ptrs[] = {h->dP, h->dmu2[0], h->dmu2[1], h->dV, h->dW, h->ddacc2[0], h->ddacc2[1], h->dscratch, h->dn, h->dflags, h->dso, h->dfac,
                   h->d_ring, h->d_stream, h->dF, h->dQ, h->dTmp, h->dPlin, h->dtagmap, h->dneff, h->d_det, h->d_assoc_step, h->dfloor, h->dqueue, h->dready, h->dmbox,
-                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf};
+                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
   if (h->h_det) (void)hipHostFree(h->h_det);
@@ -705,6 +709,63 @@ extern "C" int ekf_download_block(ekf_handle* h, int b, int r0, int c0, int rows
   if (int rc = materialize(h, b)) return rc;
   HIP_TRY(h, copy_cov(h, b, out, cols, r0, c0, rows, cols, false));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return EKF_OK;
+}
+
+// The diagonal blocks of the covariance as the pass would leave them, without running it (k_marginals, ekf_marginals.hip): reads
+// P_base, V, W, the pending pose noise, the sizes and the active bounds the pass reads, writes only the destinations.  Nothing
+// of the handle's scheduling state changes (pending ranks and steps, the streams' order, the statistics).
+extern "C" int ekf_download_marginals(ekf_handle* h, int b0, int count, double* pose, double* landmarks, int cap,
+                                      int* n_landmarks) {
+  if (int rc = check_b(h, 0, "ekf_download_marginals")) return rc;   // (refreshes the sizes a device-side association grew)
+  if (b0 < 0 || count <= 0 || b0 > h->batch - count)
+    return fail(h, EKF_ERR_ARG, "ekf_download_marginals: trajectory range outside the bank");
+  if (!pose) return fail(h, EKF_ERR_ARG, "ekf_download_marginals: NULL pose");
+  int nl_hi = 0;
+  for (int b = b0; b < b0 + count; ++b) nl_hi = std::max(nl_hi, (h->n[b] - 3) / 2);
+  if (landmarks && cap < nl_hi)
+    return fail(h, EKF_ERR_ARG, "ekf_download_marginals: cap " + std::to_string(cap) + " is below the largest landmark count " +
+                                    std::to_string(nl_hi));
+  if (!landmarks) cap = 0;
+  for (int b = b0; b < b0 + count; ++b)
+    if (h->host_bad[b]) return check_internal(h, b, "ekf_download_marginals");
+  HIP_TRY(h, hipSetDevice(h->device));
+  // pinned destinations are written by the kernel; the others go through the staging buffer and one copy each
+  auto device_view = [](double* p) -> double* {
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeHost)
+      return static_cast<double*>(attr.devicePointer);
+    (void)hipGetLastError();                           // (an ordinary pointer is "invalid value" to the query)
+    return nullptr;
+  };
+  const size_t pose_words = (size_t)count * 9, lm_words = (size_t)count * (size_t)cap * 4;
+  double* dpose = device_view(pose);
+  double* dlm = landmarks ? device_view(landmarks) : nullptr;
+  const size_t stage = (dpose ? 0 : pose_words) + (landmarks && !dlm ? lm_words : 0);
+  if (stage > h->marg_cap) {
+    if (h->dmarg) HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the old buffer may still be read by a copy in flight)
+    if (h->dmarg) HIP_TRY(h, hipFree(h->dmarg));
+    h->dmarg = nullptr;
+    h->marg_cap = 0;
+    HIP_TRY(h, hipMalloc(&h->dmarg, sizeof(double) * stage));
+    h->marg_cap = stage;
+  }
+  double* spose = dpose ? dpose : h->dmarg;
+  double* slm = !landmarks ? nullptr : (dlm ? dlm : h->dmarg + (dpose ? 0 : pose_words));
+  const int kb = (h->pending_k + 3) & ~3;              // what flush_pending's pass would apply (plan_pass: 4 nkt ranks)
+  launch_marginals(h->stream, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dn, h->dso, h->ld, h->pstride, b0, count, kb, cap,
+                   spose, slm);
+  HIP_TRY(h, hipGetLastError());
+  if (!dpose) HIP_TRY(h, hipMemcpyAsync(pose, spose, sizeof(double) * pose_words, hipMemcpyDeviceToHost, h->stream));
+  if (landmarks && !dlm && lm_words)
+    HIP_TRY(h, hipMemcpyAsync(landmarks, slm, sizeof(double) * lm_words, hipMemcpyDeviceToHost, h->stream));
+  // one synchronisation: the flags come back behind the results (check_internal's copy, then its wait)
+  HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->dflags, sizeof(unsigned) * h->batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (int b = b0; b < b0 + count; ++b)
+    if (h->h_flags[b] & EKF_FLAG_INTERNAL) return check_internal(h, b, "ekf_download_marginals");
+  if (n_landmarks)
+    for (int b = b0; b < b0 + count; ++b) n_landmarks[b - b0] = (h->n[b] - 3) / 2;
   return EKF_OK;
 }
 

@@ -107,6 +107,7 @@ ABI = {
     "ekf_download_state": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, C.c_int]),
     "ekf_download_mean": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int]),
     "ekf_download_block": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
+    "ekf_download_marginals": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _ip]),
     "ekf_state_size": (C.c_int, [C.c_void_p, C.c_int, _ip]),
     "ekf_add_landmarks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int]),
     "ekf_predict": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -425,6 +426,28 @@ class EkfSlam:
         out = np.empty((rows, cols))
         self._check(self._lib.ekf_download_block(self._h, b, r0, c0, rows, cols, _p(out)))
         return out
+
+    def marginals(self, b: Optional[int] = None):
+        """Marginal covariances of the pose and of every landmark, without applying the pending update (no covariance
+        pass, no mirror: one read-only kernel over P_base and the pending ranks, O(n k) per trajectory).  Equal to the
+        blocks ``covariance_block`` returns after ``flush()`` to rounding, bit-identical where nothing is pending.
+
+        ``b`` given: ``(pose (3, 3), landmarks (N_b, 2, 2))`` of trajectory b.
+        ``b`` None: the whole bank in one call, ``(pose (B, 3, 3), landmarks (B, N_hi, 2, 2), counts (B,))`` with the
+        blocks beyond a trajectory's landmark count NaN."""
+        if b is None:
+            b0, count = 0, self.batch
+        else:
+            b0, count = int(b), 1
+        cap = max((self.size(t) - 3) // 2 for t in range(b0, b0 + count))
+        pose = _pinned.empty(self._lib, (count, 3, 3))
+        lms = _pinned.empty(self._lib, (count, cap, 2, 2)) if cap > 0 else np.empty((count, 0, 2, 2))
+        counts = np.empty(count, dtype=np.int32)
+        self._check(self._lib.ekf_download_marginals(self._h, b0, count, _p(pose), _p(lms) if cap > 0 else None, cap,
+                                                     _p(counts, _ip)))
+        if b is not None:
+            return pose[0], lms[0, :counts[0]]
+        return pose, lms, counts
 
     def state(self, b: int = 0):
         n = self.size(b)

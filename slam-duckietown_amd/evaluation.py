@@ -5,12 +5,14 @@
 * ATE / RMSE of an estimated path against ground truth (what the reference only eyeballs in its plots,
   src/replay_no_ros.py:520-529).
 * NEES of the pose over a batch of Monte-Carlo trajectories with chi-square consistency bounds: the
-  batched filter bank (`EkfSlam(batch=B)`) is exactly the Monte-Carlo tool this needs.
+  batched filter bank (`EkfSlam(batch=B)`) is exactly the Monte-Carlo tool this needs.  `marginal_nees` takes the
+  pose and landmark blocks of the whole bank from one `marginals()` call (no covariance pass): cheap enough for
+  every step of a run.
 """
 from __future__ import annotations
 
 import math
-from typing import Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -163,3 +165,37 @@ def pose_nees(filter_bank, true_poses: Sequence[Sequence[float]]):
         covs.append(filter_bank.covariance_block(0, 0, 3, 3, b))
     vals = nees(np.array(errs), np.array(covs))
     return vals, float(vals.mean()), chi2_bounds(3, filter_bank.batch)
+
+
+class MarginalNees(NamedTuple):
+    pose: np.ndarray                          # (B,) pose NEES per trajectory
+    pose_anees: float                         # their average
+    pose_bounds: Tuple[float, float]          # 95 % ANEES bounds, chi2_bounds(3, B)
+    landmarks: Optional[np.ndarray]           # (B, N) 2-dof NEES per landmark (NaN where a trajectory has fewer), or None
+    landmark_bounds: Optional[Tuple[float, float]]   # chi2_bounds(2, B), or None
+
+
+def marginal_nees(filter_bank, true_poses, true_landmarks=None) -> MarginalNees:
+    """Pose NEES of every trajectory of a bank and, given `true_landmarks` (B, N, 2), every landmark's 2-dof NEES -- from
+    ONE ``filter_bank.marginals()`` call (the diagonal blocks of the current covariance, no covariance pass) plus one mean
+    download per trajectory (which never flushes).  Unlike `pose_nees` it leaves the filter's pass cadence alone, so it
+    can be sampled at every step."""
+    B = filter_bank.batch
+    true_poses = np.asarray(true_poses, dtype=float).reshape(B, 3)
+    pose, lms, counts = filter_bank.marginals()
+    means = [np.asarray(filter_bank.mean(b), dtype=float) for b in range(B)]
+    errs = np.array([m[:3] for m in means]) - true_poses
+    errs[:, 2] = wrap_angle(errs[:, 2])
+    vals = nees(errs, pose)
+    lm_vals, lm_bounds = None, None
+    if true_landmarks is not None:
+        truth = np.asarray(true_landmarks, dtype=float)
+        truth = truth.reshape(B, -1, 2)
+        lm_vals = np.full(truth.shape[:2], np.nan)
+        for b in range(B):
+            k = min(int(counts[b]), truth.shape[1])
+            if k:
+                e = means[b][3:3 + 2 * k].reshape(k, 2) - truth[b, :k]
+                lm_vals[b, :k] = nees(e, lms[b, :k])
+        lm_bounds = chi2_bounds(2, B)
+    return MarginalNees(vals, float(vals.mean()), chi2_bounds(3, B), lm_vals, lm_bounds)
