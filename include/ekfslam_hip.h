@@ -206,49 +206,44 @@ long long ekf_profile_passes(ekf_handle *h);
  * fused cadence carry event pairs too: cls 1 the solve launch, 2 the chain (or look-ahead gather) launch, 3 the panel launch,
  * 0 the pass.  Does not reset: read before ekf_profile_read. */
 int ekf_profile_read_class(ekf_handle *h, int cls, double *ms_total, long long *launches);
-/* Tuning knobs: "flush_every" (steps per covariance pass, 0 = auto), "rank_limit" (auto cadence: pending
- * ranks that trigger the pass, 2..80), "pass_rows_per_block", "pass_streaming" (-1 auto / 0 resident /
- * 1 nontemporal), "active_bound" (0 = treat every state index as correlated), "pass_kernel" (-1 = auto:
- * the row-slab kernel where the launch streams through HBM and gives every CU work, else k_flush; 0 = k_flush, the
- * column-strip form, 2 = k_flush_rs, the row-slab form; both give the same result bit for bit), "pass_chunk" (row-slab pass: strips per work unit, 0 = auto), "pass_workgroups" (row-slab pass:
- * persistent workgroups, 0 = one per CU; fewer leaves whole CUs to other streams), "fused_step" (1 = small launches
- * run a step as one kernel, the panels gathered beside the solve -- same results; 0 = always two kernels; 2 =
- * diagnostic: the solve never publishes its completion, every bounded wait times out with EKF_FLAG_INTERNAL),
- * "fused_cadence" (1 = ekf_stream_run replays everything between two covariance passes -- a trajectory's next 40 landmark
- * updates, src/replay_no_ros.py:368-480 for each, and every prediction in between -- with one solve launch and one panel launch;
- * "col_gather" = 1: the mirrored column entries of that panel launch are fetched beside the solve by the CUs its chain leaves idle,
- * 0: the panel launch gathers everything itself, same results bit for bit; the fused path is equal to the per-step kernels to
- * rounding (1e-10 relative guaranteed, 1e-13 .. 1e-12 measured; the tests assert 1e-11), not bit for bit; 0 = one step at a time), "lookahead" (1 = where the pass is a
- * small launch, the next cadence's solve runs beside it on the handle's second stream; 0 = strictly in sequence),
- * "pass_share_order" (row-slab pass on static shares: 1 = shares dealt to the XCDs by starting column, 0 = as cut; same
- * result bit for bit), "small_state" (1 = a handle with n_max <= 79 -- up to 38 landmarks; n_max <= 131, 64 landmarks, for a bank of at least 128
- * trajectories -- runs every step, or a whole
- * uploaded stream, as ONE workgroup per trajectory with the covariance resident in LDS: nothing is ever pending; 0 = the
- * general kernels; the default can be set for new handles with the environment variable EKFSLAM_HIP_SMALL_STATE),
- * "zero_copy_inputs" (1 = the small-state kernel reads an online step's record straight from the pinned input ring, 0 = a
- * staged copy first), "fetch_spin" (1 = ekf_step_fetch on the small-state path polls the sequence word its launch releases
- * behind the state it wrote to pinned memory, 0 = it waits for the stream; same results.  The polled hand-over assumes that
- * the kernel's posted writes to coherent pinned memory become visible in fence -> release order -- validated on MI355X;
- * every hand-over carries a second copy of its sequence number written by another wave, compared before the data is
- * trusted, and "fetch_verify" = 1 (the default since round 6; ~1 us per call) also compares an XOR checksum of the whole payload -- a platform that reorders posted writes could deliver the trailer before other payload lines --; a mismatch waits for the stream
- * instead and is counted, ekf_debug_fetch_retries), "pack_dense" (downloads of a whole
- * state into PINNED host memory, e.g. from ekf_host_alloc: 1 = up to 40 MB a kernel mirrors the stored triangle straight into
- * the destination, no mirror pass and no copy engine; 2 = at every size; 0 = never: mirror pass + rectangle copy; same bytes),
- * "panel_shape" (diagnostics: 0 = a fused cadence's panel launch takes the shape its size selects, 1 .. 3 force the row-split
- * latency form / one wave per workgroup / four waves per workgroup; the same result bit for bit),
- * "w_from_v" (1, default: where a fused cadence's covariance pass follows its panel launch at once in the row-slab form, the
- * panel launch writes V only and the pass forms its W fragments from V and the cadence's records -- W = -(V S^-1) per
- * landmark is half of what that launch would write; the same result bit for bit; ekf_debug_snapshot's W view is then stale);
- * unknown names fail.
- * "fused_cadence", "lookahead" and "chain" (1 = where the next cadence's solve runs beside this one's pass -- banks of up to 40
- * trajectories whose pass leaves CUs free: every size with "chain" = 1, from "lookahead_min_mb" = 48 MB of covariance with the
- * round-3 look-ahead --, its block is formed from this cadence's records and the solves of a run follow one another on the
- * handle's stream, panel launch and pass of every cadence on the second one; 0 = the round-3 look-ahead: the block gathered behind
- * the panel launch; sub-options of the chained order: "panel_tform" (1) (small panel launches as a triangular solve on
- * the matrix cores instead of the replay of the landmarks one after the other), "panel_own_gate" (default 0; 1 = small panel launches wait for
- * their solve themselves instead of behind a one-lane gate launch), "pre_positions" (1: a cadence's inputs are formed one cadence
- * ahead), "beside_min_mb" (0: chain at every size)) change the ORDER in which a step's pending ranks are summed (and whether the look-ahead
- * applies depends on the device's CU count and the size of the launch): results are equal to rounding across these
+/* Options: name (default, allowed values) meaning.  Unknown names and values out of range fail with EKF_ERR_ARG.
+ *   "flush_every"         (0, 0..64)    steps per covariance pass; 0 = auto, by "rank_limit"
+ *   "rank_limit"          (80, 2..80)   auto cadence: pending ranks that trigger the pass
+ *   "pass_kernel"         (-1, -1/0/2)  covariance pass: -1 auto, 0 column strips (k_flush), 2 row slabs (k_flush_rs); same bits
+ *   "pass_chunk"          (0, 0..4096)  row-slab pass: strips per work unit, 0 = auto
+ *   "pass_workgroups"     (0, 0..4096)  row-slab pass: persistent workgroups, 0 = one per CU (fewer leave CUs to other streams)
+ *   "pass_rows_per_block" (0, 0..4096)  column-strip pass: rows per workgroup (multiple of 16), 0 = auto
+ *   "pass_streaming"      (-1, -1..1)   -1 auto by working-set size, 0 resident, 1 nontemporal
+ *   "active_bound"        (1, 0..1)     0 = treat every state index as correlated (flushes first)
+ *   "small_state"         (1, 0..1)     1 = n_max <= 79 (<= 131 for banks of >= 128) runs as one workgroup per trajectory with P
+ *                                       in LDS, nothing ever pending; env EKFSLAM_HIP_SMALL_STATE sets it for new handles (flushes first)
+ *   "fused_step"          (1, 0..2)     1 = small launches run a step as one kernel, 0 = always two; 2 = diagnostic: the solve never
+ *                                       publishes its completion, every bounded wait times out with EKF_FLAG_INTERNAL
+ *   "fused_cadence"       (1, 0..1)     1 = ekf_stream_run runs everything between two passes (a trajectory's next 40 landmark
+ *                                       updates and the predictions between them) as one solve + one panel launch; equal to the
+ *                                       per-step kernels to rounding (the tests assert 1e-11); 0 = one step at a time
+ *   "col_gather"          (1, 0..1)     1 = the panel launch's mirrored column entries are gathered beside the solve; same bits
+ *   "w_from_v"            (1, 0..1)     1 = a row-slab pass right behind the panel launch forms W from V and the records, the panel
+ *                                       launch writes V only; same bits (ekf_debug_snapshot's W view is then stale)
+ *   "panel_shape"         (0, 0..3)     diagnostics: 0 = the panel launch's shape by its size, 1 .. 3 force row-split / one wave /
+ *                                       four waves per workgroup; same bits
+ *   "lookahead"           (1, 0..1)     1 = where the pass is a small launch, the next cadence's solve runs beside it
+ *   "chain"               (1, 0..1)     1 = banks of up to 40 whose pass leaves CUs free chain their solves on the handle's stream,
+ *                                       panel launch and pass on the second one, at every size; 0 = the round-3 look-ahead, from
+ *                                       48 MB of covariance.  Set 0 under rocprofv3 --pmc or any kernel-serialising profiler
+ *   "panel_tform"         (1, 0..1)     chained runs: small panel launches as a triangular solve on the matrix cores
+ *   "run_end_flush"       (0, 0..1)     1 = every ekf_stream_run call ends with the pass of what it left pending
+ *   "pack_dense"          (1, 0..2)     downloads into pinned memory: 1 = a kernel writes up to 40 MB straight into the destination,
+ *                                       2 = at every size, 0 = never (mirror pass + copy); same bytes
+ *   "fetch_spin"          (1, 0..1)     ekf_step_fetch on the small-state path polls the sequence word its launch releases behind
+ *                                       the state in pinned memory (the ordering this assumes: INTEGRATION.md section 3), 0 =
+ *                                       waits for the stream; env EKFSLAM_HIP_FETCH_SPIN sets it for new handles
+ *   "fetch_verify"        (1, 0..1)     1 = a polled hand-over is trusted only if the XOR checksum of its payload matches (~1 us);
+ *                                       0 = the second sequence number only.  A mismatch waits for the stream (ekf_debug_fetch_retries)
+ *   "profile_kernels"     (0, 0..1)     measurement: event pairs around every launch of a fused cadence (ekf_profile_read_class)
+ *   "profile_stride"      (1, 1..1024)  measurement: every k-th pass launch carries an event pair
+ * "fused_cadence", "lookahead" and "chain" change the ORDER in which a step's pending ranks are summed (and whether the
+ * look-ahead applies depends on the device's CU count and the size of the launch): results are equal to rounding across these
  * settings and across devices, bit-identical only for a fixed setting on a fixed device type. */
 int ekf_set_option(ekf_handle *h, const char *name, int value);
 /* Which form of the covariance pass the last launch used (-1 = none yet; values as for "pass_kernel"), how many

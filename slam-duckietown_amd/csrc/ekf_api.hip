@@ -50,7 +50,6 @@ void launch_chain_cad(hipStream_t, const double*, const double*, const double*, 
                       unsigned*, int, unsigned, const CadPre*, CadPre*, const CadPlan*, bool);
 void launch_mark(hipStream_t, unsigned*, unsigned);
 void launch_gate(hipStream_t, unsigned*, unsigned, unsigned*, int);
-int panels_cad_workgroups(int, int);
 int chain_gather_workgroups(int, int);
 int chain_sync_words();
 void launch_snap_pose(hipStream_t, const double*, const int*, int, long, int, int, double*);
@@ -58,7 +57,7 @@ void launch_gather_cad(hipStream_t, const double*, const double*, const double*,
                        int, const DeviceConfig&, int, long, double*);
 long cadence_gbuf_doubles();
 void launch_panels_cad(hipStream_t, double*, double*, double*, const double*, double*, const int*, const CadOut*,
-                       SolveOut*, unsigned*, int, long, int, int, int, const double*, double*, unsigned*, unsigned, unsigned, unsigned*,
+                       SolveOut*, unsigned*, int, long, int, int, int, const double*, double*, unsigned*, unsigned, unsigned*,
                        bool, unsigned, int, bool);
 bool panels_cad_latency_regime(int, int);
 void launch_marginals(hipStream_t, const double*, const double*, const double*, const double*, const int*, const SolveOut*, int,
@@ -149,7 +148,7 @@ struct ekf_handle : ekf::HostPlan {
   hipEvent_t shares_ev[2] = {nullptr, nullptr};   // the upload out of hshares2[i] has been executed
   bool shares_ev_used[2] = {false, false};
   int shares_cur = 0;
-  int shares_key[5] = {0, 0, 0, 0, 0};   // (batch, slabs, last strip, workgroups, order) the current table was built for
+  int shares_key[4] = {0, 0, 0, 0};   // (batch, slabs, last strip, workgroups) the current table was built for
   int shares_ok = 0;              // pieces of its longest share (0: no table for this key -- the queue modes are used)
   unsigned* dready = nullptr;     // per trajectory: sequence number of the last solve that completed (k_step_split)
   SolveOut* dmbox = nullptr;      // per trajectory: that solve's header and records, written through (mailbox_publish)
@@ -174,20 +173,10 @@ struct ekf_handle : ekf::HostPlan {
   CadPre* dpre[2] = {nullptr, nullptr};
   long pre_serial[2] = {-1, -1};
   long cad_serial = 0;
-  int opt_pre_positions = 1;
-  // covariance (MB, whole bank) from which the next solve runs beside the pass in a chained run.  0: always -- with the counters'
-  // hand-overs chaining wins at every size tried (N = 12 .. 1000, banks of 1 .. 32: +25 .. +43 %); the round-3 look-ahead, whose
-  // hand-overs are events (~25 us per cadence), keeps its 48 MB
-  int opt_beside_min_mb = 0;
-  int opt_lookahead_min_mb = 48;
   hipEvent_t ev_pass = nullptr;   // recorded on the second stream when a chain of cadences ends (join_aux): the only event of the chained order
   bool chain_run = false;         // the run in flight records the transforms (every solve is k_solve_cad<true>)
   bool aux_pass = false;          // a covariance pass is in flight on the second stream (ev_pass recorded behind it)
   int opt_chain = 1;
-  // 0 (default) = a one-lane gate launch in front of every chained panel launch: ~5 us of the second stream, which has them to
-  // spare (no measurable cost: 62.2 against 61.5 k at N = 2000 x 1, profiles/r06_chained_solves.txt), and no workgroup of a large
-  // launch ever spins; 1 = small panel launches (each workgroup a CU to itself) are their own gate (panel_head_wait)
-  int opt_panel_own_gate = 0;
   // 1 = where a fused cadence's covariance pass follows its panel launch at once, in the row-slab form, the panel launch writes V
   // only and the pass forms its W fragments from V and the records' S^-1 (half of the panel launch's stores); bit-identical
   int opt_w_from_v = 1;
@@ -230,7 +219,6 @@ struct ekf_handle : ekf::HostPlan {
   int opt_fetch_spin = 1;
   int opt_fetch_verify = 1;       // 1 (default) = ekf_step_fetch checks the payload's XOR checksum before it trusts a polled hand-over (~1 us of the 10 - 15 us the polling saves); 0 = the trailer's second sequence number only
   long fetch_retries = 0;         // statistics: hand-overs whose integrity trailer did not match (answered after a stream sync)
-  int opt_zero_copy_inputs = 1;   // small-state online steps read their records from the pinned ring (no staged copy)
   int last_kernel = -1, last_nkt = 0, last_streaming = 0;   // what the last covariance pass launched
   int last_wv = 0;                // ... and whether it formed its W fragments from V ("w_from_v")
   int last_shares = 0;            // ... and whether it ran on equal static shares (k_flush_rs, a few long trajectories)
@@ -843,7 +831,7 @@ static int flush_pending(ekf_handle* h, hipStream_t st, const CadOut* wv) {
     // build_pass_shares depends on the size only through the number of slabs and the last strip: with the active bound
     // on and a growing map the bound changes at almost every pass, the table only when it crosses a strip
     const int nrb = (p.e_hi + 127) / 128, s_last = (p.e_hi - 1) >> 6;
-    const int key[5] = {h->batch, nrb, s_last, p.rs_workgroups, h->opt_share_order};
+    const int key[4] = {h->batch, nrb, s_last, p.rs_workgroups};
     if (std::memcmp(key, h->shares_key, sizeof key) != 0) {
       const size_t words = (size_t)h->cu_count * pass_share_pieces() * 4;
       const int nb = h->shares_cur ^ 1;
@@ -856,7 +844,7 @@ static int flush_pending(ekf_handle* h, hipStream_t st, const CadOut* wv) {
       // (the pinned copy is free once its previous upload has been executed: two tables back, long ago)
       if (h->shares_ev_used[nb]) HIP_TRY(h, hipEventSynchronize(h->shares_ev[nb]));
       h->shares_ok = build_pass_shares(h->batch, p.e_hi, p.rs_workgroups, h->hshares2[nb]);
-      if (h->shares_ok > 0 && h->opt_share_order) order_pass_shares(p.rs_workgroups, pass_share_pieces(), h->hshares2[nb], words);
+      if (h->shares_ok > 0) order_pass_shares(p.rs_workgroups, pass_share_pieces(), h->hshares2[nb], words);
       // stream-ordered: the launch below, on the same stream, reads the table after the copy; the pass that read the
       // other table -- possibly still running on the handle's other stream -- is not touched
       HIP_TRY(h, hipMemcpyAsync(h->dshares2[nb], h->hshares2[nb], sizeof(int) * words, hipMemcpyHostToDevice, st));
@@ -1025,6 +1013,10 @@ static int upload_run_plan(ekf_handle* h) {
 //     { pass_c on the second stream | solve_{c+1} } -> join.
 // `presolved` says that this cadence's solve has already been enqueued one of these ways; *next_presolved that the next
 // one's now is.
+// Covariance (MB, whole bank) from which the round-3 look-ahead runs beside a column-strip pass.  The chained order, whose
+// hand-overs are counters instead of events, does at every size: it wins at every size tried (N = 12 .. 1000, banks of 1 .. 32:
+// +25 .. +43 %).
+constexpr int LOOKAHEAD_MIN_MB = 48;
 static bool beside_the_pass(const ekf_handle* h, const PassPlan& plan) {
   // (worth it where the pass is the column-strip kernel -- the row-slab pass fills every CU by itself -- and long enough
   //  to pay for the gather and the two cross-stream hand-overs, ~25 us together: from ~48 MB of covariance.  N = 2000 x 1:
@@ -1035,7 +1027,7 @@ static bool beside_the_pass(const ekf_handle* h, const PassPlan& plan) {
   // the bank (17 us at 32 trajectories, 71 us at 256) -- N = 500 x 32 +5 %, N = 300 x 48 -5 %, N = 200 x 128 -21 %,
   // N = 100 x 256 -36 % with the look-ahead (bench.py --option lookahead=0; round 4)
   const bool small_pass = plan.kernel == 0 && h->batch <= 40 &&
-                          (double)h->batch * 8.0 * plan.e_hi * plan.e_hi >= 1.0e6 * (h->opt_chain ? h->opt_beside_min_mb : h->opt_lookahead_min_mb);
+                          (h->opt_chain || (double)h->batch * 8.0 * plan.e_hi * plan.e_hi >= 1.0e6 * LOOKAHEAD_MIN_MB);
   const bool shares_pass = plan.kernel == 2 && (plan.beside || (plan.long_few && h->batch < 8 && h->opt_pass_workgroups > 0 &&
                                                                   h->opt_pass_workgroups + h->batch <= h->cu_count));
   return small_pass || shares_pass;
@@ -1113,7 +1105,7 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
   }
   hipStream_t pst = h->stream;                         // the panel launch's stream
   unsigned* psync = nullptr;
-  unsigned head_sigma = 0u, tail_target = 0u;
+  unsigned tail_target = 0u;
   const CadPlan* dpl2 = dpl + h->batch;
   int rc = EKF_OK;
   if (chain_next) {
@@ -1131,8 +1123,8 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     ProfBracket pbc, pbs;
     if (int rc2 = prof_open(h, 2, h->stream, &pbc)) return rc2;
     // the next cadence's inputs if an earlier chain launch formed them; the one after it: formed by this launch
-    const CadPre* pre_in = (h->opt_pre_positions && h->pre_serial[(serial + 1) & 1] == serial + 1) ? h->dpre[(serial + 1) & 1] : nullptr;
-    CadPre* pre_out = (h->opt_pre_positions && c + 2 < rp.ncad) ? h->dpre[(serial + 2) & 1] : nullptr;
+    const CadPre* pre_in = h->pre_serial[(serial + 1) & 1] == serial + 1 ? h->dpre[(serial + 1) & 1] : nullptr;
+    CadPre* pre_out = c + 2 < rp.ncad ? h->dpre[(serial + 2) & 1] : nullptr;
     launch_chain_cad(h->stream, h->dP, h->dprow3[h->cpar ^ 1], h->dmu2[h->cur], h->dmu2[h->cur ^ 1], dcad, h->d_stream,
                      dpl2, h->batch, h->dcfg, h->ld, h->pstride, h->dgbuf, h->dgmu, h->dxg, h->dbg, h->dsync, h->gather_count,
                      h->dflags, gw, h->sigma, pre_in, pre_out, pre_out ? dpl2 + h->batch : nullptr, h->aux_pass);
@@ -1147,10 +1139,9 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     // undone.  Whatever happens the streams are joined, and a failure marks every trajectory undefined (EKF_ERR_STATE from
     // then on, until it is uploaded again).
     if (hipGetLastError() != hipSuccess) rc = fail(h, EKF_ERR_HIP, "chained solves: launch of the next cadence's solve failed");
-    // (a one-lane gate in front of the panel launch; with "panel_own_gate" a small panel launch -- each of its workgroups and each
-    //  solve workgroup a CU to itself -- waits for its solve itself)
-    if (h->opt_panel_own_gate && panels_cad_workgroups(h->batch, n_hi) + 2 * h->batch <= h->cu_count / 2) head_sigma = h->sigma;
-    else launch_gate(h->aux, h->dsync, h->sigma, h->dflags, h->batch);
+    // (a one-lane gate in front of the panel launch: ~5 us of the second stream, which has them to spare, and no workgroup of
+    //  a large launch ever spins)
+    launch_gate(h->aux, h->dsync, h->sigma, h->dflags, h->batch);
     pst = h->aux;
     psync = h->dsync;
     tail_target = h->gather_count;
@@ -1161,7 +1152,7 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     ProfBracket pb;
     if (int rc2 = prof_open(h, 3, pst, &pb)) return rc2;
     launch_panels_cad(pst, h->dP, h->dV, h->dW, mu_in, mu_out, h->dn, dcad, h->dso, h->dqueue, h->ld,
-                      h->pstride, h->batch, n_hi, nrp, h->colbuf_live ? h->dcolbuf : nullptr, prow_out, psync, head_sigma, tail_target, h->dflags,
+                      h->pstride, h->batch, n_hi, nrp, h->colbuf_live ? h->dcolbuf : nullptr, prow_out, psync, tail_target, h->dflags,
                       chain_next && h->opt_panel_tform && !h->colbuf_live && panels_cad_latency_regime(h->batch, n_hi),
                       chain_next ? h->sigma : 0u, h->opt_panel_shape, wv);
     if (int rc2 = prof_close(h, &pb)) return rc2;
@@ -1307,7 +1298,7 @@ static int do_step(ekf_handle* h, int base_flags, const double* lin, const doubl
       h->neff_enq[b] = h->opt_active_bound ? h->neff[b] : h->n[b];
     }
     h->fetch_b = p == passes - 1 ? fetch_b : -1;
-    if (small_path(h) && h->opt_zero_copy_inputs) {
+    if (small_path(h)) {
       // small-state path: the one workgroup per trajectory fetches its 352-byte record straight from the pinned ring (one
       // coalesced read over PCIe, ~1.5 us) -- a staged host-to-device copy in front of the kernel costs 5 - 10 us of latency
       // per step, which at these sizes is a third of the step
@@ -1489,7 +1480,7 @@ extern "C" int ekf_step_fetch(ekf_handle* h, const double* lin, const double* an
   if (n != h->n[b]) return fail(h, EKF_ERR_ARG, "ekf_step_fetch: n does not match the state size");
   h->fetched = false;
   int want = -1;
-  if (n <= PACK_SMALL_N && small_path(h) && h->opt_zero_copy_inputs) {
+  if (n <= PACK_SMALL_N && small_path(h)) {
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = pack_buffer(h)) return rc;
     want = b;
@@ -1921,158 +1912,52 @@ extern "C" int ekf_last_pass(ekf_handle* h, int* kernel, int* k_tiles, int* stre
   return EKF_OK;
 }
 
+// ekf_set_option's names: the handle member each sets and its allowed range (include/ekfslam_hip.h documents them)
+struct OptionSpec {
+  const char* name;
+  int ekf_handle::*member;
+  int lo, hi;
+};
+static const OptionSpec k_options[] = {
+    {"flush_every", &ekf_handle::opt_flush_every, 0, 64},
+    {"rank_limit", &ekf_handle::opt_rank_limit, 2, KTOT},
+    {"pass_kernel", &ekf_handle::opt_pass_kernel, -1, 2},   // (not 1: the producer/consumer form, removed in round 3)
+    {"pass_chunk", &ekf_handle::opt_pass_chunk, 0, 4096},
+    {"pass_workgroups", &ekf_handle::opt_pass_workgroups, 0, 4096},
+    {"pass_rows_per_block", &ekf_handle::opt_rows_per_block, 0, 4096},
+    {"pass_streaming", &ekf_handle::opt_streaming, -1, 1},
+    {"active_bound", &ekf_handle::opt_active_bound, 0, 1},
+    {"small_state", &ekf_handle::opt_small_state, 0, 1},
+    {"fused_step", &ekf_handle::opt_fused_step, 0, 2},      // (2, diagnostic: every bounded wait times out; garbage results)
+    {"fused_cadence", &ekf_handle::opt_fused_cadence, 0, 1},
+    {"col_gather", &ekf_handle::opt_col_gather, 0, 1},
+    {"w_from_v", &ekf_handle::opt_w_from_v, 0, 1},
+    {"panel_shape", &ekf_handle::opt_panel_shape, 0, 3},
+    {"lookahead", &ekf_handle::opt_lookahead, 0, 1},
+    {"chain", &ekf_handle::opt_chain, 0, 1},
+    {"panel_tform", &ekf_handle::opt_panel_tform, 0, 1},
+    {"run_end_flush", &ekf_handle::opt_run_end_flush, 0, 1},
+    {"pack_dense", &ekf_handle::opt_pack_dense, 0, 2},
+    {"fetch_spin", &ekf_handle::opt_fetch_spin, 0, 1},
+    {"fetch_verify", &ekf_handle::opt_fetch_verify, 0, 1},
+    {"profile_kernels", &ekf_handle::opt_profile_kernels, 0, 1},
+    {"profile_stride", &ekf_handle::profile_stride, 1, 1024},
+};
+
 extern "C" int ekf_set_option(ekf_handle* h, const char* name, int value) {
   if (!h || !name) return EKF_ERR_ARG;
-  if (std::strcmp(name, "pass_kernel") == 0) {
-    if (value != -1 && value != 0 && value != 2)         // (1 was the producer/consumer form, removed in round 3: never faster)
-      return fail(h, EKF_ERR_ARG, "pass_kernel: -1 (auto), 0 (column strips) or 2 (row slabs)");
-    h->opt_pass_kernel = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "rank_limit") == 0) {
-    if (value < 2 || value > KTOT) return fail(h, EKF_ERR_ARG, "rank_limit out of range");
-    h->opt_rank_limit = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "pass_rows_per_block") == 0) {
-    if (value < 0 || value > 4096) return fail(h, EKF_ERR_ARG, "pass_rows_per_block out of range");
-    h->opt_rows_per_block = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "pass_chunk") == 0) {
-    if (value < 0 || value > 4096) return fail(h, EKF_ERR_ARG, "pass_chunk out of range");
-    h->opt_pass_chunk = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "small_state") == 0) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "small_state must be 0 or 1");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = flush_pending(h)) return rc;          // (the small-state path runs only with nothing pending)
-    h->opt_small_state = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "zero_copy_inputs") == 0) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "zero_copy_inputs must be 0 or 1");
-    h->opt_zero_copy_inputs = value;
-    return EKF_OK;
-  }
-  if (!std::strcmp(name, "pack_dense")) {
-    if (value < 0 || value > 2) return fail(h, EKF_ERR_ARG, "pack_dense must be 0, 1 or 2");
-    h->opt_pack_dense = value;
-    return EKF_OK;
-  }
-  if (!std::strcmp(name, "col_gather")) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "col_gather must be 0 or 1");
-    h->opt_col_gather = value;
-    return EKF_OK;
-  }
-  if (!std::strcmp(name, "fetch_verify")) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "fetch_verify must be 0 or 1");
-    h->opt_fetch_verify = value;
-    return EKF_OK;
-  }
-  if (!std::strcmp(name, "fetch_spin")) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "fetch_spin must be 0 or 1");
-    h->opt_fetch_spin = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "pass_share_order") == 0) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "pass_share_order must be 0 or 1");
-    h->opt_share_order = value;                        // (part of the cached table's key: it is rebuilt)
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "fused_step") == 0) {
-    // (2 = diagnostic: the solve never publishes its completion, so that every panel workgroup's bounded wait must
-    //  time out and raise EKF_FLAG_INTERNAL -- the results of such a step are garbage)
-    if (value < 0 || value > 2) return fail(h, EKF_ERR_ARG, "fused_step must be 0, 1 or 2 (diagnostic)");
-    h->opt_fused_step = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "lookahead") == 0) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "lookahead must be 0 or 1");
-    h->opt_lookahead = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "lookahead_min_mb") == 0) {
-    if (value < 0 || value > 100000) return fail(h, EKF_ERR_ARG, "lookahead_min_mb out of range");
-    h->opt_lookahead_min_mb = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "beside_min_mb") == 0) {
-    if (value < 0 || value > 100000) return fail(h, EKF_ERR_ARG, "beside_min_mb out of range");
-    h->opt_beside_min_mb = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "pre_positions") == 0) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "pre_positions must be 0 or 1");
-    h->opt_pre_positions = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "panel_own_gate") == 0) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "panel_own_gate must be 0 or 1");
-    h->opt_panel_own_gate = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "w_from_v") == 0) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "w_from_v must be 0 or 1");
-    h->opt_w_from_v = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "panel_shape") == 0) {
-    if (value < 0 || value > 3) return fail(h, EKF_ERR_ARG, "panel_shape must be 0 .. 3");
-    h->opt_panel_shape = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "panel_tform") == 0) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "panel_tform must be 0 or 1");
-    h->opt_panel_tform = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "run_end_flush") == 0) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "run_end_flush must be 0 or 1");
-    h->opt_run_end_flush = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "profile_kernels") == 0) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "profile_kernels must be 0 or 1");
-    h->opt_profile_kernels = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "profile_stride") == 0) {
-    if (value < 1 || value > 1024) return fail(h, EKF_ERR_ARG, "profile_stride must be in [1, 1024]");
-    h->profile_stride = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "chain") == 0) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "chain must be 0 or 1");
-    h->opt_chain = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "fused_cadence") == 0) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "fused_cadence must be 0 or 1");
-    h->opt_fused_cadence = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "pass_workgroups") == 0) {
-    if (value < 0 || value > 4096) return fail(h, EKF_ERR_ARG, "pass_workgroups out of range");
-    h->opt_pass_workgroups = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "active_bound") == 0) {
-    if (value != 0 && value != 1) return fail(h, EKF_ERR_ARG, "active_bound must be 0 or 1");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = flush_pending(h)) return rc;
-    h->opt_active_bound = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "flush_every") == 0) {
-    if (value < 0 || value > 64) return fail(h, EKF_ERR_ARG, "flush_every must be in [0, 64] (0 = auto)");
-    h->opt_flush_every = value;
-    return EKF_OK;
-  }
-  if (std::strcmp(name, "pass_streaming") == 0) {
-    if (value < -1 || value > 1) return fail(h, EKF_ERR_ARG, "pass_streaming must be -1 (auto), 0 or 1");
-    h->opt_streaming = value;
+  for (const OptionSpec& o : k_options) {
+    if (std::strcmp(name, o.name) != 0) continue;
+    if (value < o.lo || value > o.hi)
+      return fail(h, EKF_ERR_ARG, std::string(o.name) + " must be in [" + std::to_string(o.lo) + ", " + std::to_string(o.hi) + "]");
+    if (o.member == &ekf_handle::opt_pass_kernel && value == 1)
+      return fail(h, EKF_ERR_ARG, "pass_kernel must be -1 (auto), 0 (column strips) or 2 (row slabs)");
+    if (o.member == &ekf_handle::opt_small_state || o.member == &ekf_handle::opt_active_bound) {
+      // (the small-state path runs only with nothing pending; the pending ranks were formed under the old active bound)
+      HIP_TRY(h, hipSetDevice(h->device));
+      if (int rc = flush_pending(h)) return rc;
+    }
+    h->*o.member = value;
     return EKF_OK;
   }
   return fail(h, EKF_ERR_ARG, std::string("unknown option ") + name);

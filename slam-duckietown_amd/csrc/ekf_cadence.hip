@@ -737,17 +737,6 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
 // next covariance pass reads, and (trajectory 0) the work-queue heads of the row-slab pass, which start every pass at zero.
 // nrp == 0 -- no trajectory of the bank observed anything in this cadence, no pass will follow for it -- : the predictions'
 // noise goes to the pose diagonal here (what k_predict_rc does for a single prediction-only step).
-// (chained runs, small launches) the panel launch is its own gate: every workgroup waits for the cadence's solve to have
-// completed (announced by the chain launch behind that solve), then drops what its L2 may hold of the records' previous use.  Only where every workgroup of the launch has a CU to itself and the solve workgroups theirs (ekf_api.hip): a waiting
-// workgroup must not keep the solve it waits for from being placed; larger launches get the one-lane gate launch (k_gate).
-__device__ __forceinline__ void panel_head_wait(unsigned* sync, unsigned sigma, unsigned* flags) {
-  if (threadIdx.x == 0) {
-    if (!sync_wait(sync + SYNC_SOLVE * SYNC_STRIDE, sigma)) atomicOr(flags + blockIdx.y, EKF_FLAG_INTERNAL);
-  }
-  __syncthreads();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-}
-
 // `tail_word` (chained runs): the covariance pass behind this launch rewrites P_base, which the gather workgroups of the next
 // chain launch -- on the other stream -- may still be reading: the launch does not end before they have counted themselves
 // off (one lane of the whole launch waits; bounded).
@@ -936,14 +925,13 @@ __global__ __launch_bounds__(64 * NW) void k_panels_cad(double* __restrict__ P, 
                                                         const CadOut* __restrict__ co, SolveOut* __restrict__ so,
                                                         unsigned* __restrict__ queue, int ld, long pstride, int nrp,
                                                         const double* __restrict__ colbuf, double* __restrict__ prow3,
-                                                        unsigned* __restrict__ sync, unsigned head_sigma, unsigned tail_target,
+                                                        unsigned* __restrict__ sync, unsigned tail_target,
                                                         unsigned* __restrict__ flags, unsigned start_sigma, int skipw) {
   // (`skipw`, "w_from_v": the covariance pass behind this launch forms its W fragments from V and the records' S^-1 -- W is
   //  half of what this launch writes, and it is bound by what it writes; the pose's entries, pose_epilogue, are kept)
   using G = CadGeom;
   constexpr int CU = G::CU, GM = G::GM, NT = 64 * NW;
   const unsigned* tail_word = sync ? sync + SYNC_GATHER * SYNC_STRIDE : nullptr;
-  if (sync && head_sigma) panel_head_wait(sync, head_sigma, flags);
   __shared__ __attribute__((aligned(16))) double sRec[G::REC + 32];   // (+ what the last records' grouped K reads overshoot)
   __shared__ double2 sG[CAD_SLOTS];
   __shared__ int sF[CAD_SLOTS];
@@ -1176,13 +1164,12 @@ __global__ __launch_bounds__(256) void k_panels_cad_ks(double* __restrict__ P, d
                                                        const CadOut* __restrict__ co, SolveOut* __restrict__ so,
                                                        unsigned* __restrict__ queue, int ld, long pstride, int nrp,
                                                        const double* __restrict__ colbuf, double* __restrict__ prow3,
-                                                       unsigned* __restrict__ sync, unsigned head_sigma, unsigned tail_target,
+                                                       unsigned* __restrict__ sync, unsigned tail_target,
                                                        unsigned* __restrict__ flags, unsigned start_sigma) {
   using G = CadGeom;
   constexpr int GM = G::GM, CU = G::CU;
   constexpr int LP = (GM + 3) / 4;                     // landmark position-slots per wave
   const unsigned* tail_word = sync ? sync + SYNC_GATHER * SYNC_STRIDE : nullptr;
-  if (sync && head_sigma) panel_head_wait(sync, head_sigma, flags);
   __shared__ __attribute__((aligned(16))) double sRec[G::REC + 32];   // (+ what the last record's K reads may overshoot)
   __shared__ double2 sG[CAD_SLOTS];
   __shared__ int sF[CAD_SLOTS];
@@ -1909,7 +1896,7 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_panels_cad_tf(double* __restric
                                                                const CadOut* __restrict__ co, SolveOut* __restrict__ so,
                                                                unsigned* __restrict__ queue, int ld, long pstride, int nrp,
                                                                double* __restrict__ prow3, unsigned* __restrict__ sync,
-                                                               unsigned head_sigma, unsigned tail_target,
+                                                               unsigned tail_target,
                                                                unsigned* __restrict__ flags, unsigned start_sigma) {
   using G = CadGeom;
   constexpr int GM = G::GM, CU = G::CU;
@@ -1921,7 +1908,6 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_panels_cad_tf(double* __restric
   __shared__ double dmS[5][64];
   __shared__ int Ck[128];
   const unsigned* tail_word = sync ? sync + SYNC_GATHER * SYNC_STRIDE : nullptr;
-  if (sync && head_sigma) panel_head_wait(sync, head_sigma, flags);
   const int b = blockIdx.y;
   const int n = nact[b];
   const int i0 = blockIdx.x * 64;
@@ -2182,12 +2168,7 @@ void launch_mark(hipStream_t st, unsigned* sync, unsigned sigma) { hipLaunchKern
 void launch_gate(hipStream_t st, unsigned* sync, unsigned sigma, unsigned* flags, int batch) {
   hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, st, sync, sigma, flags, batch);
 }
-// workgroups of the panel launch (what decides between the launch being its own gate and the gate launch)
 bool panels_cad_latency_regime(int batch, int n_hi) { return (long)((n_hi + 63) / 64) * batch <= CAD_KS_WAVES; }
-int panels_cad_workgroups(int batch, int n_hi) {
-  const long waves = (long)((n_hi + 63) / 64) * batch;
-  return (int)(waves <= 1024 ? waves : (long)((n_hi + 255) / 256) * batch);
-}
 
 void launch_snap_pose(hipStream_t st, const double* P, const int* nact, int ld, long pstride, int batch, int n_hi, double* prow3) {
   hipLaunchKernelGGL(k_snap_pose, dim3((n_hi + 255) / 256, batch), dim3(256), 0, st, P, nact, ld, pstride, prow3);
@@ -2196,13 +2177,13 @@ void launch_snap_pose(hipStream_t st, const double* P, const int* nact, int ld, 
 // `nrp`: the ranks the bank's busiest trajectory appends, padded to a whole k-tile (every trajectory writes that many)
 void launch_panels_cad(hipStream_t st, double* P, double* V, double* W, const double* mu_in, double* mu_out,
                        const int* nact, const CadOut* co, SolveOut* so, unsigned* queue, int ld, long pstride, int batch,
-                       int n_hi, int nrp, const double* colbuf, double* prow3, unsigned* sync, unsigned head_sigma, unsigned tail_target,
+                       int n_hi, int nrp, const double* colbuf, double* prow3, unsigned* sync, unsigned tail_target,
                        unsigned* flags, bool tform, unsigned start_sigma, int shape, bool skipw) {
   // (`skipw`: only the replay shapes 2 and 3 honour it -- the caller asks for it only where the launch takes one of them)
   // (chained cadences in the latency regime: the triangular-solve form, one 8-wave workgroup per 64 state indices)
   if (tform) {
     hipLaunchKernelGGL(k_panels_cad_tf, dim3((n_hi + 63) / 64, batch), dim3(64 * CAD_NW), 0, st, P, V, W, mu_in, mu_out, nact, co, so,
-                       queue, ld, pstride, nrp, prow3, sync, head_sigma, tail_target, flags, start_sigma);
+                       queue, ld, pstride, nrp, prow3, sync, tail_target, flags, start_sigma);
     return;
   }
   // few state indices (the latency regime): four waves split the rows of the panel of 64 state indices (k_panels_cad_ks);
@@ -2212,13 +2193,13 @@ void launch_panels_cad(hipStream_t st, double* P, double* V, double* W, const do
   if (shape == 0) shape = waves <= CAD_KS_WAVES ? 1 : (waves <= 1024 ? 2 : 3);
   if (shape == 1)
     hipLaunchKernelGGL(k_panels_cad_ks, dim3((n_hi + 63) / 64, batch), dim3(256), 0, st, P, V, W, mu_in, mu_out,
-                       nact, co, so, queue, ld, pstride, nrp, colbuf, prow3, sync, head_sigma, tail_target, flags, start_sigma);
+                       nact, co, so, queue, ld, pstride, nrp, colbuf, prow3, sync, tail_target, flags, start_sigma);
   else if (shape == 2)
     hipLaunchKernelGGL((k_panels_cad<1>), dim3((n_hi + 63) / 64, batch), dim3(64), 0, st, P, V, W, mu_in, mu_out,
-                       nact, co, so, queue, ld, pstride, nrp, colbuf, prow3, sync, head_sigma, tail_target, flags, start_sigma, skipw ? 1 : 0);
+                       nact, co, so, queue, ld, pstride, nrp, colbuf, prow3, sync, tail_target, flags, start_sigma, skipw ? 1 : 0);
   else
     hipLaunchKernelGGL((k_panels_cad<4>), dim3((n_hi + 255) / 256, batch), dim3(256), 0, st, P, V, W, mu_in,
-                       mu_out, nact, co, so, queue, ld, pstride, nrp, colbuf, prow3, sync, head_sigma, tail_target, flags, start_sigma, skipw ? 1 : 0);
+                       mu_out, nact, co, so, queue, ld, pstride, nrp, colbuf, prow3, sync, tail_target, flags, start_sigma, skipw ? 1 : 0);
 }
 
 }  // namespace ekf

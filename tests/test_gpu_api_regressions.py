@@ -639,3 +639,29 @@ def test_a_bank_s_observations_as_arrays_equal_the_lists(sd):
             assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
         with pytest.raises(ValueError):
             f.step(lin, ang, idx[:3], zr[:3], zb[:3])
+
+
+# every name ekf_set_option accepts and its allowed range (include/ekfslam_hip.h)
+OPTION_RANGES = {
+    "flush_every": (0, 64), "rank_limit": (2, 80), "pass_kernel": (-1, 2), "pass_chunk": (0, 4096),
+    "pass_workgroups": (0, 4096), "pass_rows_per_block": (0, 4096), "pass_streaming": (-1, 1), "active_bound": (0, 1),
+    "small_state": (0, 1), "fused_step": (0, 2), "fused_cadence": (0, 1), "col_gather": (0, 1), "w_from_v": (0, 1),
+    "panel_shape": (0, 3), "lookahead": (0, 1), "chain": (0, 1), "panel_tform": (0, 1), "run_end_flush": (0, 1),
+    "pack_dense": (0, 2), "fetch_spin": (0, 1), "fetch_verify": (0, 1), "profile_kernels": (0, 1), "profile_stride": (1, 1024),
+}
+
+
+def test_set_option_ranges_and_removed_names(sd):
+    """ekf_set_option accepts both ends of every option's range and refuses the values just beyond them with an error that
+    names the option; `pass_kernel` = 1 (a removed form) is refused too.  Names of options that no longer exist are unknown."""
+    with sd.EkfSlam(23) as f:
+        for name, (lo, hi) in OPTION_RANGES.items():
+            f.set_option(name, lo)
+            f.set_option(name, hi)
+            for bad in (lo - 1, hi + 1) + ((1,) if name == "pass_kernel" else ()):
+                with pytest.raises(sd.EkfError, match=name):
+                    f.set_option(name, bad)
+        for name in ("panel_own_gate", "pre_positions", "pass_share_order", "zero_copy_inputs", "lookahead_min_mb",
+                     "beside_min_mb"):
+            with pytest.raises(sd.EkfError, match="unknown option " + name):
+                f.set_option(name, 0)
