@@ -108,6 +108,29 @@ int ekf_download_marginals(ekf_handle *h, int b0, int count, double *pose, doubl
                            int *n_landmarks);
 int ekf_state_size(ekf_handle *h, int b, int *n);
 
+/* Innovation log: every landmark update's landmark index, innovation y (2), innovation covariance S (2x2, row-major) and
+ * NIS = y^T S^-1 y -- the consistency check that needs no ground truth; the sum of -(NIS + log det 2 pi S) / 2 over a run is
+ * its log-likelihood (how MOTION_MODEL_VARIANCE / MEASUREMENT_MODEL_VARIANCE, src/replay_no_ros.py:15-16, are tuned).  Off by
+ * default.  The log is a device ring of the last `capacity` logged steps, EKF_AMAX entries per step and trajectory, filled on
+ * every path that applies landmark updates (per-step kernels, single-launch steps, fused cadences, chained and look-ahead
+ * runs, the small-state path); switching it on or off changes nothing about the filter (same bits, same scheduling and
+ * counters).  A logged STEP is one call of ekf_update, ekf_step, ekf_step_fetch or ekf_step_detections, or one stream step
+ * ekf_stream_run runs (a lone ekf_predict is not one); each trajectory writes its own column of a step row.  A step's m is the
+ * number of updates it applied, in application order: both update passes of a step with more than EKF_MMAX landmarks, the
+ * device association's order (ekf_download_tags), and a stream step cut by a cadence boundary all count as one step.  A
+ * step that applies more than EKF_AMAX updates keeps the first EKF_AMAX and reports its true m.
+ * ekf_log_innovations: capacity > 0 allocates the ring (capacity x batch x EKF_AMAX entries) and restarts the count at 0;
+ * 0 switches the log off and frees it (after a stream synchronisation).
+ * ekf_innovation_steps: steps logged since the log was switched on.
+ * ekf_download_innovations: steps [first, first + count) into m (count x batch), idx (count x batch x EKF_AMAX), y (x 2),
+ * S (x 4) and nis (x 1); idx, y, S and nis may be NULL.  Entries beyond a step's m are -1 / NaN.  Blocking and
+ * stream-ordered behind everything enqueued; runs no covariance pass or mirror and changes nothing that decides later
+ * scheduling.  EKF_ERR_ARG if the range is not inside the last `capacity` logged steps, EKF_ERR_STATE with the log off or
+ * under EKF_FLAG_INTERNAL (as the other downloads). */
+int ekf_log_innovations(ekf_handle *h, int capacity);
+int ekf_innovation_steps(ekf_handle *h, long long *logged);
+int ekf_download_innovations(ekf_handle *h, long long first, int count, int *m, int *idx, double *y, double *S, double *nis);
+
 /* State augmentation, src/replay_no_ros.py:341-360: append k landmarks (indices must continue the
  * current count), mean = xy[2*i..], variance = landmark_init_var, zero cross terms. */
 int ekf_add_landmarks(ekf_handle *h, int b, int first_index, const double *xy, int k);

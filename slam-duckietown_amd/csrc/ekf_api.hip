@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -36,8 +37,11 @@ void launch_mirror(hipStream_t, double*, const int*, int, long, int, int);
 void launch_pack_small(hipStream_t, const double*, const double*, const unsigned*, int, int, double*);
 void launch_pack_dense(hipStream_t, const double*, int, int, double*);
 int small_state_limit(int batch);
+void launch_innov_step(hipStream_t, const StepIn*, const SolveOut*, int, int, const InnovLog&);
+void launch_innov_cad(hipStream_t, const StepIn*, const CadPlan*, const CadOut*, int, int, const InnovLog&);
 int launch_small_stream(hipStream_t, double*, const double*, double*, const int*, const StepIn*, int, int, unsigned*,
-                        const DeviceConfig&, int, long, int, double*, int, unsigned long long*, unsigned long long, bool);
+                        const DeviceConfig&, int, long, int, double*, int, unsigned long long*, unsigned long long, bool,
+                        const InnovLog*);
 void launch_associate(hipStream_t, const DetIn*, int*, int*, int*, double*, double*, double*, double*, StepIn*,
                       AssocOut*, unsigned*, const AssocConfig&, int, long, int, int, int);
 void launch_fill_diag(hipStream_t, double*, int, int, const double*);
@@ -227,6 +231,15 @@ struct ekf_handle : ekf::HostPlan {
   double* h_pack = nullptr;       // pinned: where k_pack_small leaves a small state (n x n covariance, mean, flags)
   double* dmarg = nullptr;        // ekf_download_marginals: device staging of destinations that are not pinned (allocated on use)
   size_t marg_cap = 0;            // ... its size in doubles
+  // The innovation log (ekf_log_innovations; nullptr: off): a ring of innov_cap step rows, innov_steps steps logged so far.
+  // While an entry point enqueues a logged step, lg_slot is the ring row of its next launch (-1: that launch is not logged) and
+  // lg_jbase the position of its first landmark; ekf_stream_run logs stream step t in row (lg_tslot + t) % innov_cap.
+  InnovRec* dinnov = nullptr;
+  int* dinnov_m = nullptr;
+  int innov_cap = 0;
+  long long innov_steps = 0;
+  long lg_slot = -1, lg_tslot = -1;
+  int lg_jbase = 0;
   // Set when an enqueueing call failed half way (e.g. a launch of the look-ahead failed after the next cadence's solve had
   // already run): the device state of every trajectory is undefined until it is uploaded again; see check_internal
   std::vector<unsigned char> host_bad;
@@ -311,7 +324,7 @@ static void free_all(ekf_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   void* ptrs[] = {h->dP, h->dmu2[0], h->dmu2[1], h->dV, h->dW, h->ddacc2[0], h->ddacc2[1], h->dscratch, h->dn, h->dflags, h->dso, h->dfac,
                   h->d_ring, h->d_stream, h->dF, h->dQ, h->dTmp, h->dPlin, h->dtagmap, h->dneff, h->d_det, h->d_assoc_step, h->dfloor, h->dqueue, h->dready, h->dmbox,
-                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg};
+                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dinnov, h->dinnov_m};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
   if (h->h_det) (void)hipHostFree(h->h_det);
@@ -757,6 +770,86 @@ extern "C" int ekf_download_marginals(ekf_handle* h, int b0, int count, double* 
   return EKF_OK;
 }
 
+// ---- the innovation log (ekf_innovations.hip) ----
+extern "C" int ekf_log_innovations(ekf_handle* h, int capacity) {
+  if (!h) return EKF_ERR_ARG;
+  if (capacity < 0) return fail(h, EKF_ERR_ARG, "ekf_log_innovations: capacity must be >= 0");
+  const size_t rows = (size_t)capacity * h->batch;
+  if (capacity > 0 && rows * AMAX * sizeof(InnovRec) > ((size_t)1 << 36))
+    return fail(h, EKF_ERR_ARG, "ekf_log_innovations: the ring would exceed 64 GiB");
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (h->dinnov) {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // (a copy kernel may still be writing to the ring)
+    HIP_TRY(h, hipFree(h->dinnov));
+    HIP_TRY(h, hipFree(h->dinnov_m));
+    h->dinnov = nullptr;
+    h->dinnov_m = nullptr;
+  }
+  h->innov_cap = 0;
+  h->innov_steps = 0;
+  if (capacity == 0) return EKF_OK;
+  if (hipMalloc(&h->dinnov, sizeof(InnovRec) * rows * AMAX) != hipSuccess ||
+      hipMalloc(&h->dinnov_m, sizeof(int) * rows) != hipSuccess) {
+    (void)hipGetLastError();
+    if (h->dinnov) (void)hipFree(h->dinnov);
+    h->dinnov = nullptr;
+    h->dinnov_m = nullptr;
+    return fail(h, EKF_ERR_HIP, "ekf_log_innovations: cannot allocate the ring of " + std::to_string(capacity) + " steps");
+  }
+  h->innov_cap = capacity;
+  return EKF_OK;
+}
+
+extern "C" int ekf_innovation_steps(ekf_handle* h, long long* logged) {
+  if (!h || !logged) return EKF_ERR_ARG;
+  *logged = h->innov_steps;
+  return EKF_OK;
+}
+
+// Steps [first, first + count) of the log: copies of their ring rows (one or two pieces each: the ring may wrap), behind
+// everything enqueued; the entries beyond a step's count are set here.  Runs nothing else on the device.
+extern "C" int ekf_download_innovations(ekf_handle* h, long long first, int count, int* m, int* idx, double* y, double* S,
+                                        double* nis) {
+  if (!h) return EKF_ERR_ARG;
+  if (!h->dinnov) return fail(h, EKF_ERR_STATE, "ekf_download_innovations: the innovation log is off (ekf_log_innovations)");
+  if (count < 0 || first < 0 || first + count > h->innov_steps || first < h->innov_steps - h->innov_cap)
+    return fail(h, EKF_ERR_ARG, "ekf_download_innovations: steps [" + std::to_string(first) + ", " + std::to_string(first + count) +
+                                    ") are not among the last " + std::to_string(h->innov_cap) + " of the " +
+                                    std::to_string(h->innov_steps) + " logged");
+  if (count > 0 && !m) return fail(h, EKF_ERR_ARG, "ekf_download_innovations: NULL m");
+  const int B = h->batch;
+  std::vector<int> hm((size_t)count * B);
+  std::vector<InnovRec> hr((size_t)count * B * AMAX);
+  HIP_TRY(h, hipSetDevice(h->device));
+  for (long long done = 0; done < count;) {
+    const long slot = (long)((first + done) % h->innov_cap);
+    const long piece = std::min<long long>(count - done, h->innov_cap - slot);
+    HIP_TRY(h, hipMemcpyAsync(hm.data() + done * B, h->dinnov_m + slot * B, sizeof(int) * piece * B, hipMemcpyDeviceToHost,
+                              h->stream));
+    HIP_TRY(h, hipMemcpyAsync(hr.data() + done * B * AMAX, h->dinnov + slot * B * AMAX, sizeof(InnovRec) * piece * B * AMAX,
+                              hipMemcpyDeviceToHost, h->stream));
+    done += piece;
+  }
+  if (int rc = check_internal(h, -1, "ekf_download_innovations")) return rc;   // (synchronises: the copies above are done)
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (size_t e = 0; e < (size_t)count * B; ++e) {
+    m[e] = hm[e];
+    const int kept = std::min(hm[e], AMAX);
+    for (int j = 0; j < AMAX; ++j) {
+      const size_t q = e * AMAX + j;
+      const InnovRec& r = hr[q];
+      const bool on = j < kept;
+      if (idx) idx[q] = on ? r.idx : -1;
+      if (y)
+        for (int k = 0; k < 2; ++k) y[2 * q + k] = on ? r.y[k] : nan;
+      if (S)
+        for (int k = 0; k < 4; ++k) S[4 * q + k] = on ? r.S[k] : nan;
+      if (nis) nis[q] = on ? r.nis : nan;
+    }
+  }
+  return EKF_OK;
+}
+
 extern "C" int ekf_download_mean(ekf_handle* h, int b, double* mu, int n) {
   return ekf_download_state(h, b, mu, nullptr, n);
 }
@@ -892,16 +985,25 @@ static int enqueue_small(ekf_handle* h, const StepIn* d_in, int nsteps) {
   const int n_hi = h->sizes_dirty ? h->n_max : *std::max_element(h->n.begin(), h->n.end());
   const int out_b = h->fetch_b;                        // (ekf_step_fetch, last pass of its step: see there)
   h->fetch_b = -1;
+  const InnovLog lg{h->dinnov, h->dinnov_m, h->lg_slot, h->innov_cap, h->lg_jbase};   // (this path writes the log itself)
   if (launch_small_stream(h->stream, h->dP, h->dmu2[h->cur], h->dmu2[h->cur ^ 1], h->dn, d_in, h->batch, nsteps, h->dflags,
                           h->dcfg, h->ld, h->pstride, n_hi, out_b >= 0 ? h->h_pack : nullptr, out_b,
                           out_b >= 0 ? reinterpret_cast<unsigned long long*>(h->h_pack + PACK_WORDS - 1) : nullptr,
-                          out_b >= 0 ? ++h->fetch_seq : 0ull, h->batch > 3 * h->cu_count) != 0)
+                          out_b >= 0 ? ++h->fetch_seq : 0ull, h->batch > 3 * h->cu_count,
+                          h->dinnov && h->lg_slot >= 0 ? &lg : nullptr) != 0)
     return fail(h, EKF_ERR_HIP, "small-state launch: hipFuncSetAttribute failed");
   HIP_TRY(h, hipGetLastError());
   h->fetched = out_b >= 0;
   h->cur ^= 1;
   h->small_launches += 1;
   return EKF_OK;
+}
+
+// The innovation log of a per-step pass: its records (h->dso) copied out right behind its solve, before the next solve reuses them.
+static void log_pass(ekf_handle* h, const StepIn* d_in) {
+  if (!h->dinnov || h->lg_slot < 0) return;
+  launch_innov_step(h->stream, d_in, h->dso, h->dcfg.enable_measurement_model, h->batch,
+                    InnovLog{h->dinnov, h->dinnov_m, h->lg_slot, h->innov_cap, h->lg_jbase});
 }
 
 // Enqueue one device pass with inputs already at d_in (StepIn[batch]); m_hi = max m over the batch.
@@ -919,6 +1021,7 @@ static int enqueue_pass(ekf_handle* h, const StepIn* d_in, int m_hi) {
     launch_solve(h->stream, h->dP, h->dV, h->dW, dacc_in, dacc_out, mu_in, mu_out, h->dn, d_in, h->dso, h->dflags,
                  h->dfac, h->dfloor, h->dqueue, h->dcfg, h->ld, h->pstride, h->batch, 0);
     launch_predict_rc(h->stream, h->dP, mu_in, mu_out, h->dn, h->dso, h->ld, h->pstride, h->batch, n_hi);
+    log_pass(h, d_in);
     // k_predict_rc applied the noise itself (and nothing reads the pending-noise buffers while no rank is pending)
     HIP_TRY(h, hipGetLastError());
     h->cur ^= 1;
@@ -951,6 +1054,7 @@ static int enqueue_pass(ekf_handle* h, const StepIn* d_in, int m_hi) {
     launch_panels(h->stream, mcap, h->dP, h->dV, h->dW, mu_in, mu_out, h->dn, h->dso, h->dfac, h->ld, h->pstride,
                   h->batch, n_hi);
   }
+  log_pass(h, d_in);
   HIP_TRY(h, hipGetLastError());
   h->dcur ^= 1;
   h->cur ^= 1;
@@ -1042,6 +1146,14 @@ static int join_aux(ekf_handle* h) {
   return EKF_OK;
 }
 
+// The innovation log of a cadence solve that used plan `dpl` and wrote `co` (on the handle's stream right behind it: the records
+// are read before the next solve into the same copy -- two solves later -- starts).
+static void log_cadence(ekf_handle* h, const CadPlan* dpl, const CadOut* co) {
+  if (!h->dinnov || h->lg_tslot < 0) return;
+  launch_innov_cad(h->stream, h->d_stream, dpl, co, h->dcfg.enable_measurement_model, h->batch,
+                   InnovLog{h->dinnov, h->dinnov_m, h->lg_tslot, h->innov_cap, 0});
+}
+
 static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_presolved) {
   *next_presolved = false;
   const RunPlan& rp = h->run_plan;
@@ -1079,6 +1191,7 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     launch_solve_cad(h->stream, h->dP, mu_in, mu_out, h->ddacc2[h->dcur ^ 1], h->dn, h->d_stream, dpl, h->batch, dcad,
                      h->dflags, h->dcfg, h->ld, h->pstride, nullptr, 0, colbuf, n_hi, col_wgs, h->chain_run, nullptr, nullptr, 0u, nullptr);
     if (int rc = prof_close(h, &pb)) return rc;
+    log_cadence(h, dpl, dcad);
     h->colbuf_live = colbuf != nullptr;
   }
   const int ranks = 2 * rp.slots_hi[c], nrp = (ranks + 3) & ~3;   // every trajectory writes the busiest one's ranks (zeros beyond its own)
@@ -1135,6 +1248,7 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
                      h->batch, h->dcad2[h->cpar ^ 1], h->dflags, h->dcfg, h->ld, h->pstride, h->dgbuf, 1, nullptr, n_hi, 0, true, h->dgmu,
                      h->dsync, h->sigma, pre_in);
     if (int rc2 = prof_close(h, &pbs)) return rc2;
+    log_cadence(h, dpl2, h->dcad2[h->cpar ^ 1]);       // (enqueued before the gate: it waits for nothing)
     // From here on the next cadence's solve overwrites the pose mean and the pending-noise buffer: a failure below cannot be
     // undone.  Whatever happens the streams are joined, and a failure marks every trajectory undefined (EKF_ERR_STATE from
     // then on, until it is uploaded again).
@@ -1217,6 +1331,7 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
                      h->chain_run, nullptr, nullptr, 0u, nullptr);
     if (int rc2 = prof_close(h, &pb)) return rc2;
   }
+  log_cadence(h, dpl2, h->dcad2[h->cpar]);
   h->colbuf_live = false;                              // (beside the pass P_base is in motion: that cadence's panel launch gathers itself)
   // From here on the next cadence's solve has overwritten the pose mean and the pending-noise buffer: a failure
   // below cannot be undone.  Whatever happens the two streams are joined again, and a failure marks every trajectory
@@ -1259,9 +1374,20 @@ static int ring_done(ekf_handle* h, int slot) {
   return EKF_OK;
 }
 
+// While an entry point enqueues: which launches log innovations (see ekf_handle::lg_slot); nothing is logged outside one.
+struct LogScope {
+  ekf_handle* h;
+  ~LogScope() {
+    h->lg_slot = -1;
+    h->lg_tslot = -1;
+    h->lg_jbase = 0;
+  }
+};
+
 static int do_step(ekf_handle* h, int base_flags, const double* lin, const double* ang, const int* idx,
                    const double* range, const double* bearing, const int* m, int stride, int fetch_b = -1) {
   if (!h) return EKF_ERR_ARG;
+  LogScope log_scope{h};
   if (int rc = check_host_bad(h, "ekf_step")) return rc;
   if (int rc = refresh_sizes(h)) return rc;
   const bool upd = (base_flags & FLAG_UPDATE) != 0, pred = (base_flags & FLAG_PREDICT) != 0;
@@ -1282,7 +1408,10 @@ static int do_step(ekf_handle* h, int base_flags, const double* lin, const doubl
   HIP_TRY(h, hipSetDevice(h->device));
   if (int rc = push_floor(h, false)) return rc;
   const int passes = std::max(1, (m_hi + MMAX - 1) / MMAX);
+  const bool logged = h->dinnov && upd;                // (a lone prediction is not a logged step)
   for (int p = 0; p < passes; ++p) {
+    h->lg_slot = logged ? (long)(h->innov_steps % h->innov_cap) : -1;
+    h->lg_jbase = MMAX * p;
     int slot;
     if (int rc = ring_take(h, &slot)) return rc;
     StepIn* hs = h->h_ring + (size_t)slot * h->batch;
@@ -1311,6 +1440,7 @@ static int do_step(ekf_handle* h, int base_flags, const double* lin, const doubl
     if (int rc = enqueue_pass(h, ds, m_pass_hi)) return rc;
   }
   h->fetch_b = -1;
+  if (logged) h->innov_steps += 1;
   return EKF_OK;
 }
 
@@ -1377,6 +1507,8 @@ extern "C" int ekf_step_detections(ekf_handle* h, const double* lin, const doubl
     m_hi = std::max(m_hi, std::min(distinct, AMAX));
   }
   if (!h->cfg.enable_measurement_model) m_hi = 0;
+  LogScope log_scope{h};
+  h->lg_slot = h->dinnov ? (long)(h->innov_steps % h->innov_cap) : -1;
   // the host's view of the active bound must be on the device before the first device-side window
   if (!h->sizes_dirty)
     HIP_TRY(h, hipMemcpyAsync(h->dneff, h->neff.data(), sizeof(int) * h->batch, hipMemcpyHostToDevice, h->stream));
@@ -1396,7 +1528,10 @@ extern "C" int ekf_step_detections(ekf_handle* h, const double* lin, const doubl
   // (more than EKF_MMAX distinct tags in some trajectory's window: a second pass with the rest -- an update without a
   //  prediction; trajectories that had fewer find m = 0 there)
   if (int rc = enqueue_pass(h, h->d_assoc_step, std::min(m_hi, MMAX))) return rc;
-  if (m_hi > MMAX) return enqueue_pass(h, h->d_assoc_step + h->batch, m_hi - MMAX);
+  h->lg_jbase = MMAX;
+  if (m_hi > MMAX)
+    if (int rc = enqueue_pass(h, h->d_assoc_step + h->batch, m_hi - MMAX)) return rc;
+  if (h->dinnov) h->innov_steps += 1;
   return EKF_OK;
 }
 
@@ -1596,13 +1731,21 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
       return fail(h, EKF_ERR_STATE, "ekf_stream_run: the uploaded stream observes landmarks the current state does not have");
   HIP_TRY(h, hipSetDevice(h->device));
   if (int rc = push_floor(h, true)) return rc;
+  // (innovation log: stream step t goes to ring row (lg_tslot + t) % innov_cap, i.e. step `first` to row innov_steps)
+  LogScope log_scope{h};
+  const long cap = h->innov_cap;
+  if (h->dinnov) h->lg_tslot = (long)(((h->innov_steps - first) % cap + cap) % cap);
+  auto log_at = [&](int k) { h->lg_slot = h->dinnov ? (h->lg_tslot + k) % cap : -1; };
   if (small_path(h) && count > 0) {
     // the whole range as ONE launch (in pieces of 4096 steps: a bounded kernel), P resident in LDS across all its steps
-    for (int k = first; k < first + count; k += 4096)
+    for (int k = first; k < first + count; k += 4096) {
+      log_at(k);
       if (int rc = enqueue_small(h, h->d_stream + (size_t)k * h->batch, std::min(4096, first + count - k))) return rc;
+    }
     for (int b = 0; b < h->batch; ++b)
       h->neff[b] = std::max(h->neff[b], std::min(h->n[b], h->stream_own[(size_t)(first + count - 1) * h->batch + b]));
     h->neff_enq = h->neff;
+    if (h->dinnov) h->innov_steps += count;
     return EKF_OK;
   }
   for (int k = first; k < first + count;) {
@@ -1666,9 +1809,11 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
     }
     for (int b = 0; b < h->batch; ++b)
       h->neff_enq[b] = std::min(h->n[b], std::max(h->floor_host[b], h->stream_own[(size_t)k * h->batch + b]));
+    log_at(k);
     if (int rc = enqueue_pass(h, h->d_stream + (size_t)k * h->batch, h->stream_mhi[k])) return rc;
     ++k;
   }
+  if (h->dinnov) h->innov_steps += count;
   if (count > 0)
     for (int b = 0; b < h->batch; ++b)
       h->neff[b] = std::max(h->neff[b], std::min(h->n[b], h->stream_own[(size_t)(first + count - 1) * h->batch + b]));

@@ -200,6 +200,28 @@ struct AssocConfig {
   int ignore[IGNMAX];                   // IGNORE_TAGS (:36, :286)
 };
 
+// The innovation log (ekf_log_innovations): a device ring of `cap` step rows, each batch x AMAX entries (landmark index, y, S,
+// NIS: ekf_innovations.hip) plus batch counts.  InnovLog names where a launch writes: its step t goes to ring row
+// (slot0 + t) % cap -- a one-step launch has t = 0 -- at positions jbase + j (jbase = 16 p for update pass p of a step).
+struct alignas(16) InnovRec {
+  double y[2];
+  double S[4];          // row-major
+  double nis;
+  int idx;
+  int pad;
+};
+static_assert(sizeof(InnovRec) == 64, "InnovRec is 64 bytes");
+struct InnovLog {
+  InnovRec* rec;        // [cap][batch][AMAX]
+  int* m;               // [cap][batch]: landmark updates each step applied (more than AMAX: only the first AMAX are kept)
+  long slot0;
+  int cap, jbase;
+};
+// y^T S^-1 y with S^-1 = [[a, b], [c, d]]
+__host__ __device__ __forceinline__ double innov_nis(double y0, double y1, double a, double b, double c, double d) {
+  return y0 * (a * y0 + b * y1) + y1 * (c * y0 + d * y1);
+}
+
 struct DeviceConfig {
   double rd[3];         // diag of R  (src/replay_no_ros.py:421)
   double qd[2];         // diag of Q  (:438)

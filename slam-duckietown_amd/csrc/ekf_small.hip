@@ -29,11 +29,13 @@ constexpr int SMALL_N_MAX_BANK = 131;   // ... but not for a bank that fills the
 constexpr int SMALL_BANK_MIN = 128;     // workgroup per CU): N = 64 x 256 10.4 M against 7.9 M steps/s, x 1024 against 5.4 M
 
 // One step's landmark updates and prediction on the LDS-resident state.  `Pl` is n x ps (ps odd: row and column walks are
-// both conflict-free), `mu` the mean, `hp` / `kk` 2 x n scratch.
-template <int NT, int TM>
+// both conflict-free), `mu` the mean, `hp` / `kk` 2 x n scratch.  LOG: landmark j's index, y, S and NIS go to lrow[jbase + j]
+// (the innovation log, ekf_innovations.hip), written by the wave that computed y; the LOG = false instantiations are the
+// kernels as they were.
+template <int NT, int TM, bool LOG>
 __device__ __forceinline__ void small_step(double* __restrict__ Pl, double* __restrict__ mu, double* __restrict__ hp,
                                            double* __restrict__ kk, double* __restrict__ sc, const StepIn& s,
-                                           const DeviceConfig& cfg, int n, int ps) {
+                                           const DeviceConfig& cfg, int n, int ps, InnovRec* __restrict__ lrow, int jbase) {
   const int tid = threadIdx.x;
   const bool do_pred = (s.flags & FLAG_PREDICT) != 0;
   int m = ((s.flags & FLAG_UPDATE) && cfg.enable_measurement_model) ? s.m : 0;
@@ -191,19 +193,42 @@ __device__ __forceinline__ void small_step(double* __restrict__ Pl, double* __re
         }
     }
     for (int c = tid; c < n; c += NT) mu[c] += kk[c] * y0 + kk[n + c] * y1;     // :476
+    if constexpr (LOG) {
+      if (tid == NT - 64 && jbase + j < AMAX) {
+        // y and S pass through empty asm statements and S^-1 is formed again from those copies, as above: an extra use of
+        // the filter's own S^-1 lets the compiler contract K = (H P)^T S^-1 differently (other bits); this way the LOG
+        // instantiations compute exactly what the others do
+        double v[6] = {y0, y1, S00, S01, S10, S11};
+#pragma unroll
+        for (int q = 0; q < 6; ++q) asm volatile("" : "+v"(v[q]));
+        const double ld = 1.0 / (v[2] * v[5] - v[3] * v[4]);
+        InnovRec& r = lrow[jbase + j];
+        r.y[0] = v[0];
+        r.y[1] = v[1];
+        r.S[0] = v[2];
+        r.S[1] = v[3];
+        r.S[2] = v[4];
+        r.S[3] = v[5];
+        r.nis = innov_nis(v[0], v[1], v[5] * ld, -v[3] * ld, -v[4] * ld, v[2] * ld);
+        r.idx = lm;
+        r.pad = 0;
+      }
+    }
     __syncthreads();
   }
 }
 
 // One workgroup per trajectory runs `nsteps` steps: in[k * batch + b], k = 0 .. nsteps - 1.
 // TM: column tiles of 16 the state spans at most (n <= 16 TM): the down-date's loads are unrolled over them.
-template <int NT, int TM>
+// LOG: step k is logged in ring row (lg.slot0 + k) % lg.cap (InnovLog, ekf_device.h).
+template <int NT, int TM, bool LOG>
 __device__ __forceinline__ void small_stream_body(double* __restrict__ P, const double* __restrict__ mu_in,
                                                   double* __restrict__ mu_out, const int* __restrict__ nact,
                                                   const StepIn* __restrict__ in, int batch, int nsteps,
                                                   unsigned* __restrict__ flags, const DeviceConfig& cfg, int ld, long pstride,
                                                   double* __restrict__ host_out, int out_b,
-                                                  unsigned long long* __restrict__ host_seq, unsigned long long out_seq) {
+                                                  unsigned long long* __restrict__ host_seq, unsigned long long out_seq,
+                                                  const InnovLog& lg) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int n = min(min(nact[b], SMALL_N_MAX_BANK), 16 * TM);
@@ -257,7 +282,17 @@ __device__ __forceinline__ void small_stream_body(double* __restrict__ P, const 
     unsigned long long nxt = 0;
     const bool more = k + 1 < nsteps;
     if (more && tid < RW) nxt = reinterpret_cast<const unsigned long long*>(in + (long)(k + 1) * batch + b)[tid];
-    small_step<NT, TM>(Pl, mu, hp, kk, sc, *reinterpret_cast<const StepIn*>(recw + (k & 1) * RW), cfg, n, ps);
+    const StepIn& sk = *reinterpret_cast<const StepIn*>(recw + (k & 1) * RW);
+    InnovRec* lrow = nullptr;
+    if constexpr (LOG) {
+      const long row = ((lg.slot0 + k) % lg.cap) * batch + b;
+      lrow = lg.rec + row * AMAX;
+      if (tid == 0) {
+        const int ms = ((sk.flags & FLAG_UPDATE) && cfg.enable_measurement_model) ? min(sk.m, MMAX) : 0;
+        lg.m[row] = lg.jbase == 0 ? ms : lg.m[row] + ms;
+      }
+    }
+    small_step<NT, TM, LOG>(Pl, mu, hp, kk, sc, sk, cfg, n, ps, lrow, lg.jbase);
     if (more && tid < RW) recw[((k + 1) & 1) * RW + tid] = nxt;
     __syncthreads();
   }
@@ -332,32 +367,53 @@ __device__ __forceinline__ void small_stream_body(double* __restrict__ P, const 
 // The latency form: whatever registers the compiler wants (148 / 203 VGPRs: three / two workgroups resident per CU) ...
 template <int NT, int TM>
 __global__ __launch_bounds__(NT) void k_small_stream(SMALL_STREAM_ARGS) {
-  small_stream_body<NT, TM>(SMALL_STREAM_PASS);
+  small_stream_body<NT, TM, false>(SMALL_STREAM_PASS, InnovLog{});
 }
 // ... and the throughput form for banks that more than fill the chip at that occupancy: the same code held to 128 VGPRs (a few
 // spilled registers: one trajectory alone is 10 % slower), four workgroups per CU -- banks of 1024 +34 %, of 4096 +14 %
 // (tools/small_bank_sweep.py).  Same instructions on the data: bit-identical results.
 template <int NT, int TM>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_small_stream_occ(SMALL_STREAM_ARGS) {
-  small_stream_body<NT, TM>(SMALL_STREAM_PASS);
+  small_stream_body<NT, TM, false>(SMALL_STREAM_PASS, InnovLog{});
 }
 // ... and the 7-tile form (81 <= n <= 112, banks only) held to 256 VGPRs instead of 266: two workgroups per CU where LDS allows
 // (n <= 93: 69 KB each).
 template <int NT, int TM>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_small_stream_two(SMALL_STREAM_ARGS) {
-  small_stream_body<NT, TM>(SMALL_STREAM_PASS);
+  small_stream_body<NT, TM, false>(SMALL_STREAM_PASS, InnovLog{});
+}
+// The same three forms with the innovation log on (ekf_log_innovations): the filter's arithmetic is the same instructions,
+// the log adds stores behind each landmark's S.
+template <int NT, int TM>
+__global__ __launch_bounds__(NT) void k_small_stream_log(SMALL_STREAM_ARGS, InnovLog lg) {
+  small_stream_body<NT, TM, true>(SMALL_STREAM_PASS, lg);
+}
+template <int NT, int TM>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_small_stream_occ_log(SMALL_STREAM_ARGS, InnovLog lg) {
+  small_stream_body<NT, TM, true>(SMALL_STREAM_PASS, lg);
+}
+template <int NT, int TM>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_small_stream_two_log(SMALL_STREAM_ARGS, InnovLog lg) {
+  small_stream_body<NT, TM, true>(SMALL_STREAM_PASS, lg);
 }
 
 int small_state_limit(int batch) { return batch >= SMALL_BANK_MIN ? SMALL_N_MAX_BANK : SMALL_N_MAX; }
 
 int launch_small_stream(hipStream_t st, double* P, const double* mu_in, double* mu_out, const int* nact, const StepIn* in,
                         int batch, int nsteps, unsigned* flags, const DeviceConfig& cfg, int ld, long pstride, int n_hi,
-                        double* host_out, int out_b, unsigned long long* host_seq, unsigned long long out_seq, bool many) {
+                        double* host_out, int out_b, unsigned long long* host_seq, unsigned long long out_seq, bool many,
+                        const InnovLog* lg) {
   const int n = n_hi < SMALL_N_MAX_BANK ? n_hi : SMALL_N_MAX_BANK, ps = n | 1;
   const size_t bytes = sizeof(double) * ((size_t)n * ps + 5 * (size_t)n + 4) + 2 * sizeof(StepIn);
 #define EKF_SMALL(K, TM)                                                                                                 \
-  hipLaunchKernelGGL((K<256, TM>), dim3(batch), dim3(256), bytes, st, P, mu_in, mu_out, nact, in, batch, nsteps, flags, cfg, ld, \
-                     pstride, host_out, out_b, host_seq, out_seq)
+  do {                                                                                                                   \
+    if (lg)                                                                                                              \
+      hipLaunchKernelGGL((K##_log<256, TM>), dim3(batch), dim3(256), bytes, st, P, mu_in, mu_out, nact, in, batch, nsteps, \
+                         flags, cfg, ld, pstride, host_out, out_b, host_seq, out_seq, *lg);                              \
+    else                                                                                                                 \
+      hipLaunchKernelGGL((K<256, TM>), dim3(batch), dim3(256), bytes, st, P, mu_in, mu_out, nact, in, batch, nsteps, flags, \
+                         cfg, ld, pstride, host_out, out_b, host_seq, out_seq);                                          \
+  } while (0)
   // (more than 64 KB of dynamic LDS has to be asked for, once per kernel and device)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1;
@@ -368,7 +424,9 @@ int launch_small_stream(hipStream_t st, double* P, const double* mu_in, double* 
       const size_t most = sizeof(double) * ((size_t)SMALL_N_MAX_BANK * (SMALL_N_MAX_BANK | 1) + 5 * SMALL_N_MAX_BANK + 4) + \
                           2 * sizeof(StepIn);                                                                            \
       if (hipFuncSetAttribute(reinterpret_cast<const void*>(&K<256, TM>), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                              (int)most) != hipSuccess)                                                                  \
+                              (int)most) != hipSuccess ||                                                                \
+          hipFuncSetAttribute(reinterpret_cast<const void*>(&K##_log<256, TM>),                                          \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)most) != hipSuccess)                      \
         return 1;                                                                                                        \
       asked.fetch_or(1ull << dev, std::memory_order_relaxed);                                                            \
     }                                                                                                                    \

@@ -22,6 +22,7 @@ import dataclasses
 import os
 import subprocess
 import threading
+import typing
 import warnings
 import weakref
 from typing import Optional, Sequence
@@ -109,6 +110,9 @@ ABI = {
     "ekf_download_block": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "ekf_download_marginals": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _ip]),
     "ekf_state_size": (C.c_int, [C.c_void_p, C.c_int, _ip]),
+    "ekf_log_innovations": (C.c_int, [C.c_void_p, C.c_int]),
+    "ekf_innovation_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    "ekf_download_innovations": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, _ip, _ip, _dp, _dp, _dp]),
     "ekf_add_landmarks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int]),
     "ekf_predict": (C.c_int, [C.c_void_p, _dp, _dp]),
     "ekf_update": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _ip, C.c_int]),
@@ -283,6 +287,17 @@ class _PinnedPool:
 _pinned = _PinnedPool()
 
 
+class Innovations(typing.NamedTuple):
+    """What ``EkfSlam.innovations()`` returns: K logged steps of a bank of B trajectories, W entries per step (NaN / -1
+    beyond a step's m)."""
+    steps: np.ndarray     # (K,)        step numbers since the log was switched on
+    m: np.ndarray         # (K, B)      landmark updates each step applied (its true count, even beyond EKF_AMAX)
+    idx: np.ndarray       # (K, B, W)   landmark index of each update, in application order
+    y: np.ndarray         # (K, B, W, 2)     innovation
+    S: np.ndarray         # (K, B, W, 2, 2)  innovation covariance
+    nis: np.ndarray       # (K, B, W)   y^T S^-1 y
+
+
 class EkfSlam:
     """A bank of ``batch`` independent EKF-SLAM filters resident on one MI355X.
 
@@ -448,6 +463,40 @@ class EkfSlam:
         if b is not None:
             return pose[0], lms[0, :counts[0]]
         return pose, lms, counts
+
+    def log_innovations(self, capacity: int):
+        """Switch the innovation log on with a ring of the last `capacity` steps (restarting the step count at 0), or off
+        with 0.  Every landmark update of every logged step -- each ``update`` / ``step`` / ``step_state`` /
+        ``step_detections`` call and each stream step ``stream_run`` runs -- leaves its landmark index, innovation y, its
+        covariance S and its NIS.  The filter's results and scheduling are the same bits with the log on or off."""
+        self._check(self._lib.ekf_log_innovations(self._h, int(capacity)))
+        self._innov_cap = int(capacity)
+
+    def innovations(self, first: Optional[int] = None, count: Optional[int] = None) -> "Innovations":
+        """Steps [first, first + count) of the innovation log (default: every step still in the ring), as
+        ``Innovations(steps (K,), m (K, B), idx (K, B, W), y (K, B, W, 2), S (K, B, W, 2, 2), nis (K, B, W))``.  W is the
+        largest m in the range (at most EKF_AMAX); entries beyond a step's m are -1 / NaN.  Blocking; runs no covariance
+        pass.  ``evaluation.nis_consistency`` turns it into consistency statistics and a log-likelihood."""
+        logged = C.c_longlong(0)
+        self._check(self._lib.ekf_innovation_steps(self._h, C.byref(logged)))
+        total = logged.value
+        if first is None:
+            first = max(0, total - getattr(self, "_innov_cap", 0)) if count is None else max(0, total - int(count))
+        if count is None:
+            count = total - int(first)
+        first, count = int(first), int(count)
+        B = self.batch
+        shape = (max(count, 0), B)
+        m = np.empty(shape, dtype=np.int32)
+        idx = np.empty(shape + (EKF_AMAX,), dtype=np.int32)
+        y = np.empty(shape + (EKF_AMAX, 2))
+        S = np.empty(shape + (EKF_AMAX, 2, 2))
+        nis = np.empty(shape + (EKF_AMAX,))
+        self._check(self._lib.ekf_download_innovations(self._h, first, count, _p(m, _ip), _p(idx, _ip), _p(y), _p(S),
+                                                       _p(nis)))
+        W = min(int(m.max()), EKF_AMAX) if m.size else 0
+        return Innovations(np.arange(first, first + count, dtype=np.int64), m, idx[..., :W].copy(), y[..., :W, :].copy(),
+                           S[..., :W, :, :].copy(), nis[..., :W].copy())
 
     def state(self, b: int = 0):
         n = self.size(b)

@@ -4,6 +4,7 @@
   rotate the Vicon points about the robot's first pose by its first heading, subtract that pose, mm -> m.
 * ATE / RMSE of an estimated path against ground truth (what the reference only eyeballs in its plots,
   src/replay_no_ros.py:520-529).
+* NIS of every landmark update from the innovation log (`nis_consistency`): consistency without ground truth.
 * NEES of the pose over a batch of Monte-Carlo trajectories with chi-square consistency bounds: the
   batched filter bank (`EkfSlam(batch=B)`) is exactly the Monte-Carlo tool this needs.  `marginal_nees` takes the
   pose and landmark blocks of the whole bank from one `marginals()` call (no covariance pass): cheap enough for
@@ -199,3 +200,50 @@ def marginal_nees(filter_bank, true_poses, true_landmarks=None) -> MarginalNees:
                 lm_vals[b, :k] = nees(e, lms[b, :k])
         lm_bounds = chi2_bounds(2, B)
     return MarginalNees(vals, float(vals.mean()), chi2_bounds(3, B), lm_vals, lm_bounds)
+
+
+class NisConsistency(NamedTuple):
+    step_anis: np.ndarray            # (K,) per step: the bank's NIS summed over its updates, divided by B (NaN: no update)
+    step_bounds: np.ndarray          # (K, 2) two-sided bounds of step_anis: chi2(2 sum m) / B
+    traj_anis: np.ndarray            # (B,) per trajectory: its NIS summed over the run, divided by K (NaN: no update)
+    traj_bounds: np.ndarray          # (B, 2) two-sided bounds of traj_anis: chi2(2 sum m) / K
+    gate: float                      # the chi2_2 quantile at `confidence`
+    above_gate: float                # share of all updates whose NIS exceeds it (about 1 - confidence when consistent)
+    loglik: np.ndarray               # (B,) per trajectory: sum of -(NIS + log det(2 pi S)) / 2 over its updates
+    updates: int                     # updates counted (NaN padding excluded)
+
+
+def nis_consistency(innov, confidence: float = 0.95) -> NisConsistency:
+    """Consistency statistics of an innovation log (``EkfSlam.innovations()``: ``nis`` (K, B, W), ``S`` (K, B, W, 2, 2),
+    NaN-padded) -- the check that needs no ground truth.  Each update's NIS = y^T S^-1 y is chi2 with 2 dof for a consistent
+    filter, so a sum over u updates is chi2 with 2u dof: the per-step bank average and the per-trajectory time average come
+    with two-sided bounds at `confidence` for their own update counts (an average above its upper bound: the filter is
+    over-confident; below the lower one: conservative).  ``loglik`` is each trajectory's Gaussian log-likelihood of its
+    innovations, the quantity to maximise when tuning the motion and measurement variances."""
+    from scipy.stats import chi2
+    nis = np.asarray(innov.nis, dtype=float)
+    S = np.asarray(innov.S, dtype=float)
+    K, B = nis.shape[:2]
+    ok = np.isfinite(nis)
+    v = np.where(ok, nis, 0.0)
+    a = (1.0 - confidence) / 2.0
+
+    def bounds(n_updates, runs):
+        dof = 2.0 * np.asarray(n_updates, dtype=float)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            lo = np.where(dof > 0, chi2.ppf(a, np.maximum(dof, 1.0)), np.nan) / runs
+            hi = np.where(dof > 0, chi2.ppf(1.0 - a, np.maximum(dof, 1.0)), np.nan) / runs
+        return np.stack([lo, hi], axis=-1)
+
+    per_step = ok.reshape(K, -1).sum(axis=1)
+    per_traj = ok.sum(axis=(0, 2)) if K else np.zeros(B, dtype=int)
+    step_anis = np.where(per_step > 0, v.reshape(K, -1).sum(axis=1) / max(B, 1), np.nan)
+    traj_anis = np.where(per_traj > 0, v.sum(axis=(0, 2)) / max(K, 1), np.nan) if K else np.full(B, np.nan)
+    gate = float(chi2.ppf(confidence, 2))
+    total = int(ok.sum())
+    above = float((v[ok] > gate).sum()) / total if total else float("nan")
+    Sg = np.where(ok[..., None, None], S, np.eye(2) / (2.0 * np.pi))    # (padding: det(2 pi S) = 1, contributes 0)
+    _sign, logdet = np.linalg.slogdet(2.0 * np.pi * Sg)
+    loglik = -0.5 * np.where(ok, v + logdet, 0.0).sum(axis=(0, 2)) if K else np.zeros(B)
+    return NisConsistency(step_anis, bounds(per_step, max(B, 1)), traj_anis, bounds(per_traj, max(K, 1)), gate, above,
+                          loglik, total)
