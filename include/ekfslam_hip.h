@@ -131,6 +131,24 @@ int ekf_log_innovations(ekf_handle *h, int capacity);
 int ekf_innovation_steps(ekf_handle *h, long long *logged);
 int ekf_download_innovations(ekf_handle *h, long long first, int count, int *m, int *idx, double *y, double *S, double *nis);
 
+/* NIS validation gate: landmark update j is REJECTED when NIS = y^T S^-1 y > threshold, with the y and S^-1 the filter is about
+ * to use -- after the step's prediction and the updates before it, the same NIS the innovation log reports.  A rejected update
+ * moves neither mean nor covariance; later updates see the state as if it had never been given.  It still takes its 2 rank
+ * slots, so cadence packing and every scheduling counter are the same with the gate on or off.  A NaN NIS is not rejected
+ * (EKF_FLAG_NONFINITE as before).  One threshold per handle, on every path that applies landmark updates; off by default, and
+ * off means the same bits and launches as without the gate.  For a confidence p the chi-square quantile of 2 degrees of
+ * freedom is -2 ln(1 - p) (p = 0.99: 9.21).
+ * ekf_set_nis_gate: INFINITY switches the gate off, a finite threshold > 0 on; <= 0 or NaN: EKF_ERR_ARG.  It applies to the
+ * launches enqueued after the call, and clears the rejection counters (stream-ordered).
+ * ekf_download_gate_counts: updates each trajectory b0 .. b0 + count - 1 rejected since the last ekf_set_nis_gate.  Blocking
+ * and stream-ordered, like the other downloads; EKF_ERR_STATE under EKF_FLAG_INTERNAL.
+ * ekf_download_innovation_rejections: the innovation log's steps [first, first + count), range rules as
+ * ekf_download_innovations, into rejected (count x batch x EKF_AMAX): 1 rejected, 0 applied, -1 beyond a step's m.  The log
+ * keeps the true y, S and NIS of a rejected update. */
+int ekf_set_nis_gate(ekf_handle *h, double threshold);
+int ekf_download_gate_counts(ekf_handle *h, int b0, int count, long long *rejected);
+int ekf_download_innovation_rejections(ekf_handle *h, long long first, int count, int *rejected);
+
 /* State augmentation, src/replay_no_ros.py:341-360: append k landmarks (indices must continue the
  * current count), mean = xy[2*i..], variance = landmark_init_var, zero cross terms. */
 int ekf_add_landmarks(ekf_handle *h, int b, int first_index, const double *xy, int k);

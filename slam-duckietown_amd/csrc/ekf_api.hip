@@ -37,8 +37,8 @@ void launch_mirror(hipStream_t, double*, const int*, int, long, int, int);
 void launch_pack_small(hipStream_t, const double*, const double*, const unsigned*, int, int, double*);
 void launch_pack_dense(hipStream_t, const double*, int, int, double*);
 int small_state_limit(int batch);
-void launch_innov_step(hipStream_t, const StepIn*, const SolveOut*, int, int, const InnovLog&);
-void launch_innov_cad(hipStream_t, const StepIn*, const CadPlan*, const CadOut*, int, int, const InnovLog&);
+void launch_innov_step(hipStream_t, const StepIn*, const SolveOut*, int, int, int, const InnovLog&);
+void launch_innov_cad(hipStream_t, const StepIn*, const CadPlan*, const CadOut*, int, int, int, const InnovLog&);
 int launch_small_stream(hipStream_t, double*, const double*, double*, const int*, const StepIn*, int, int, unsigned*,
                         const DeviceConfig&, int, long, int, double*, int, unsigned long long*, unsigned long long, bool,
                         const InnovLog*);
@@ -240,6 +240,10 @@ struct ekf_handle : ekf::HostPlan {
   long long innov_steps = 0;
   long lg_slot = -1, lg_tslot = -1;
   int lg_jbase = 0;
+  // The NIS gate (ekf_set_nis_gate): per-trajectory rejection counters, allocated when the gate is first switched on.  While
+  // the gate is on dcfg.gate_rej points at them and dcfg.nis_gate holds the threshold (kernel arguments: every launch
+  // enqueued after the call sees the new value).
+  unsigned long long* dgate = nullptr;
   // Set when an enqueueing call failed half way (e.g. a launch of the look-ahead failed after the next cadence's solve had
   // already run): the device state of every trajectory is undefined until it is uploaded again; see check_internal
   std::vector<unsigned char> host_bad;
@@ -324,7 +328,7 @@ static void free_all(ekf_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   void* ptrs[] = {h->dP, h->dmu2[0], h->dmu2[1], h->dV, h->dW, h->ddacc2[0], h->ddacc2[1], h->dscratch, h->dn, h->dflags, h->dso, h->dfac,
                   h->d_ring, h->d_stream, h->dF, h->dQ, h->dTmp, h->dPlin, h->dtagmap, h->dneff, h->d_det, h->d_assoc_step, h->dfloor, h->dqueue, h->dready, h->dmbox,
-                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dinnov, h->dinnov_m};
+                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dinnov, h->dinnov_m, h->dgate};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
   if (h->h_det) (void)hipHostFree(h->h_det);
@@ -807,19 +811,16 @@ extern "C" int ekf_innovation_steps(ekf_handle* h, long long* logged) {
 }
 
 // Steps [first, first + count) of the log: copies of their ring rows (one or two pieces each: the ring may wrap), behind
-// everything enqueued; the entries beyond a step's count are set here.  Runs nothing else on the device.
-extern "C" int ekf_download_innovations(ekf_handle* h, long long first, int count, int* m, int* idx, double* y, double* S,
-                                        double* nis) {
-  if (!h) return EKF_ERR_ARG;
-  if (!h->dinnov) return fail(h, EKF_ERR_STATE, "ekf_download_innovations: the innovation log is off (ekf_log_innovations)");
+// everything enqueued, into hm (count x batch counts) and hr (count x batch x AMAX entries).  Runs nothing else on the device.
+static int read_log(ekf_handle* h, long long first, int count, const char* fn, std::vector<int>& hm, std::vector<InnovRec>& hr) {
+  if (!h->dinnov) return fail(h, EKF_ERR_STATE, std::string(fn) + ": the innovation log is off (ekf_log_innovations)");
   if (count < 0 || first < 0 || first + count > h->innov_steps || first < h->innov_steps - h->innov_cap)
-    return fail(h, EKF_ERR_ARG, "ekf_download_innovations: steps [" + std::to_string(first) + ", " + std::to_string(first + count) +
+    return fail(h, EKF_ERR_ARG, std::string(fn) + ": steps [" + std::to_string(first) + ", " + std::to_string(first + count) +
                                     ") are not among the last " + std::to_string(h->innov_cap) + " of the " +
                                     std::to_string(h->innov_steps) + " logged");
-  if (count > 0 && !m) return fail(h, EKF_ERR_ARG, "ekf_download_innovations: NULL m");
   const int B = h->batch;
-  std::vector<int> hm((size_t)count * B);
-  std::vector<InnovRec> hr((size_t)count * B * AMAX);
+  hm.resize((size_t)count * B);
+  hr.resize((size_t)count * B * AMAX);
   HIP_TRY(h, hipSetDevice(h->device));
   for (long long done = 0; done < count;) {
     const long slot = (long)((first + done) % h->innov_cap);
@@ -830,7 +831,18 @@ extern "C" int ekf_download_innovations(ekf_handle* h, long long first, int coun
                               hipMemcpyDeviceToHost, h->stream));
     done += piece;
   }
-  if (int rc = check_internal(h, -1, "ekf_download_innovations")) return rc;   // (synchronises: the copies above are done)
+  return check_internal(h, -1, fn);                    // (synchronises: the copies above are done)
+}
+
+// The entries beyond a step's count are set here.
+extern "C" int ekf_download_innovations(ekf_handle* h, long long first, int count, int* m, int* idx, double* y, double* S,
+                                        double* nis) {
+  if (!h) return EKF_ERR_ARG;
+  if (count > 0 && !m && h->dinnov) return fail(h, EKF_ERR_ARG, "ekf_download_innovations: NULL m");
+  std::vector<int> hm;
+  std::vector<InnovRec> hr;
+  if (int rc = read_log(h, first, count, "ekf_download_innovations", hm, hr)) return rc;
+  const int B = h->batch;
   const double nan = std::numeric_limits<double>::quiet_NaN();
   for (size_t e = 0; e < (size_t)count * B; ++e) {
     m[e] = hm[e];
@@ -847,6 +859,48 @@ extern "C" int ekf_download_innovations(ekf_handle* h, long long first, int coun
       if (nis) nis[q] = on ? r.nis : nan;
     }
   }
+  return EKF_OK;
+}
+
+extern "C" int ekf_download_innovation_rejections(ekf_handle* h, long long first, int count, int* rejected) {
+  if (!h) return EKF_ERR_ARG;
+  if (count > 0 && !rejected && h->dinnov) return fail(h, EKF_ERR_ARG, "ekf_download_innovation_rejections: NULL rejected");
+  std::vector<int> hm;
+  std::vector<InnovRec> hr;
+  if (int rc = read_log(h, first, count, "ekf_download_innovation_rejections", hm, hr)) return rc;
+  for (size_t e = 0; e < (size_t)count * h->batch; ++e) {
+    const int kept = std::min(hm[e], AMAX);
+    for (int j = 0; j < AMAX; ++j) rejected[e * AMAX + j] = j < kept ? hr[e * AMAX + j].rejected : -1;
+  }
+  return EKF_OK;
+}
+
+// ---- the NIS gate (solve kernels: ekf_kernels.hip solve_body, ekf_cadence.hip k_solve_cad, ekf_small.hip small_step) ----
+extern "C" int ekf_set_nis_gate(ekf_handle* h, double threshold) {
+  if (!h) return EKF_ERR_ARG;
+  if (!(threshold > 0.0))                              // (NaN too)
+    return fail(h, EKF_ERR_ARG, "ekf_set_nis_gate: the threshold must be > 0 (INFINITY: off)");
+  HIP_TRY(h, hipSetDevice(h->device));
+  const bool on = !std::isinf(threshold);
+  if (on && !h->dgate) HIP_TRY(h, hipMalloc(&h->dgate, sizeof(unsigned long long) * h->batch));
+  // (stream-ordered behind every launch enqueued so far, which may still count rejections under the old threshold)
+  if (h->dgate) HIP_TRY(h, hipMemsetAsync(h->dgate, 0, sizeof(unsigned long long) * h->batch, h->stream));
+  h->dcfg.nis_gate = threshold;
+  h->dcfg.gate_rej = on ? h->dgate : nullptr;
+  return EKF_OK;
+}
+
+extern "C" int ekf_download_gate_counts(ekf_handle* h, int b0, int count, long long* rejected) {
+  if (!h) return EKF_ERR_ARG;
+  if (b0 < 0 || count <= 0 || b0 > h->batch - count)
+    return fail(h, EKF_ERR_ARG, "ekf_download_gate_counts: trajectory range outside the bank");
+  if (!rejected) return fail(h, EKF_ERR_ARG, "ekf_download_gate_counts: NULL rejected");
+  HIP_TRY(h, hipSetDevice(h->device));
+  std::vector<unsigned long long> hc((size_t)count, 0ull);
+  if (h->dgate)
+    HIP_TRY(h, hipMemcpyAsync(hc.data(), h->dgate + b0, sizeof(unsigned long long) * count, hipMemcpyDeviceToHost, h->stream));
+  if (int rc = check_internal(h, -1, "ekf_download_gate_counts")) return rc;   // (synchronises: the copy above is done)
+  for (int b = 0; b < count; ++b) rejected[b] = (long long)hc[b];
   return EKF_OK;
 }
 
@@ -985,12 +1039,14 @@ static int enqueue_small(ekf_handle* h, const StepIn* d_in, int nsteps) {
   const int n_hi = h->sizes_dirty ? h->n_max : *std::max_element(h->n.begin(), h->n.end());
   const int out_b = h->fetch_b;                        // (ekf_step_fetch, last pass of its step: see there)
   h->fetch_b = -1;
-  const InnovLog lg{h->dinnov, h->dinnov_m, h->lg_slot, h->innov_cap, h->lg_jbase};   // (this path writes the log itself)
+  // (this path writes the log itself, and applies the NIS gate in the same instantiations)
+  const bool logged = h->dinnov && h->lg_slot >= 0;
+  const InnovLog lg = logged ? InnovLog{h->dinnov, h->dinnov_m, h->lg_slot, h->innov_cap, h->lg_jbase} : InnovLog{};
   if (launch_small_stream(h->stream, h->dP, h->dmu2[h->cur], h->dmu2[h->cur ^ 1], h->dn, d_in, h->batch, nsteps, h->dflags,
                           h->dcfg, h->ld, h->pstride, n_hi, out_b >= 0 ? h->h_pack : nullptr, out_b,
                           out_b >= 0 ? reinterpret_cast<unsigned long long*>(h->h_pack + PACK_WORDS - 1) : nullptr,
                           out_b >= 0 ? ++h->fetch_seq : 0ull, h->batch > 3 * h->cu_count,
-                          h->dinnov && h->lg_slot >= 0 ? &lg : nullptr) != 0)
+                          logged || h->dcfg.gate_rej ? &lg : nullptr) != 0)
     return fail(h, EKF_ERR_HIP, "small-state launch: hipFuncSetAttribute failed");
   HIP_TRY(h, hipGetLastError());
   h->fetched = out_b >= 0;
@@ -1002,7 +1058,7 @@ static int enqueue_small(ekf_handle* h, const StepIn* d_in, int nsteps) {
 // The innovation log of a per-step pass: its records (h->dso) copied out right behind its solve, before the next solve reuses them.
 static void log_pass(ekf_handle* h, const StepIn* d_in) {
   if (!h->dinnov || h->lg_slot < 0) return;
-  launch_innov_step(h->stream, d_in, h->dso, h->dcfg.enable_measurement_model, h->batch,
+  launch_innov_step(h->stream, d_in, h->dso, h->dcfg.enable_measurement_model, h->dcfg.gate_rej != nullptr, h->batch,
                     InnovLog{h->dinnov, h->dinnov_m, h->lg_slot, h->innov_cap, h->lg_jbase});
 }
 
@@ -1150,7 +1206,7 @@ static int join_aux(ekf_handle* h) {
 // are read before the next solve into the same copy -- two solves later -- starts).
 static void log_cadence(ekf_handle* h, const CadPlan* dpl, const CadOut* co) {
   if (!h->dinnov || h->lg_tslot < 0) return;
-  launch_innov_cad(h->stream, h->d_stream, dpl, co, h->dcfg.enable_measurement_model, h->batch,
+  launch_innov_cad(h->stream, h->d_stream, dpl, co, h->dcfg.enable_measurement_model, h->dcfg.gate_rej != nullptr, h->batch,
                    InnovLog{h->dinnov, h->dinnov_m, h->lg_tslot, h->innov_cap, 0});
 }
 

@@ -137,7 +137,7 @@ __device__ __forceinline__ int cad_positions(const CadPlan& pl, const StepIn* __
 // (ekf_api.hip: enqueue_cadence).  It also down-dates the pose block behind the LAST landmark and records it
 // (CadOut::posefin): with the per-landmark records that is all k_chain_cad needs to form the next cadence's block without
 // this cadence's panel launch and covariance pass.  `gmu` (with gbuf): the mean at the cadence's positions, from k_chain_cad.
-template <bool CHAIN>
+template <bool CHAIN, bool GATE>
 __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restrict__ P,
                                                     const double* __restrict__ mu_in, double* __restrict__ mu_out,
                                                     double* __restrict__ dacc_out, const int* __restrict__ nact,
@@ -487,6 +487,11 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
   // panel kernel gets goes to memory from there, off the chain), the others: down-date
   const bool rec_wave = wave == CAD_NW - 1;
   const int ds = wave == 0 ? 0 : wave - 1;             // down-date slot of this wave (waves 0, 2 .. CAD_NW - 2)
+  // The NIS gate (GATE: the instantiations launched while ekf_set_nis_gate has it on; the others are the kernel without it): at
+  // b1 y and S^-1 of the slot are in LDS and every wave forms the decision itself from them.  A rejected slot moves nothing: the mean wave skips its mean update, the down-date
+  // waves skip the down-date, and the record wave writes the slot's record with H, the K rows and the pose's rank entries
+  // zero (y and S^-1 kept), so that the panel launches, w_from_v and k_chain_cad all see two exact zero ranks.
+  unsigned long long rmask = 0ull;                     // (record wave) slots rejected
   if (wave == 1) motion(0);
   WG_LDS_BARRIER();
   if (wave == 0) {                                     // (diagnostic record) rows 0, 1 of the block before the cadence
@@ -624,11 +629,22 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
         }
       }
       WG_LDS_BARRIER();                                // b1: K, (H P) and S^-1 of this landmark are in LDS
+      bool rej = false;
+      if constexpr (GATE) {
+        const double2 gy = yS[s & 1], ga = siS[0], gc = siS[1];
+        rej = innov_reject(gy.x, gy.y, ga.x, ga.y, gc.x, gc.y, cfg.nis_gate);
+      }
       if (wave == 1) {
         // the mean (:476); then the next landmark's Jacobian at the new mean, or the next step's motion model
+        // (the sums are spelled out as the compiler had contracted them before the gate existed -- the gate's branch would
+        //  let it contract them differently: other bits -- with the first products behind empty asm statements)
         const double2 k0 = kcS[lane], k1 = kcS[64 + lane];
-        if (lane < pa + 2) mu0 += k0.x * y0 + k0.y * y1;
-        if (64 + lane < pa + 2) mu1 += k1.x * y0 + k1.y * y1;
+        double p0 = k0.x * y0, p1 = k1.y * y1;
+        asm volatile("" : "+v"(p0), "+v"(p1));
+        if (!rej) {
+          if (lane < pa + 2) mu0 += fma(k0.y, y1, p0);
+          if (64 + lane < pa + 2) mu1 += fma(k1.x, y0, p1);
+        }
         if (j + 1 < m) jacobian_at_mean(pa - 2, (s + 1) & 1);
         else if (t + 1 < nsteps) motion(t + 1);
       } else if (rec_wave) {
@@ -646,7 +662,19 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
           vw[0] = hp;
           vw[1] = make_double2(-ka.x, -ka.y);
         }
-      } else if (CHAIN || !last) {                     // (CHAIN: the last landmark too -- the pose block behind it is a result)
+        if (rej) {                                     // (NIS gate) the same places again, zero: H, the K rows, the pose's ranks
+          const double2 z = make_double2(0.0, 0.0);
+          if (lane < pa) rec2[8 + lane] = z;
+          if (two_j && 64 + lane < pa) rec2[8 + 64 + lane] = z;
+          if (lane < 5) rec2[lane] = z;
+          if (lane < 3) {
+            double2* vw = reinterpret_cast<double2*>(o.posevw[s][lane]);
+            vw[0] = z;
+            vw[1] = z;
+          }
+          rmask |= 1ull << s;
+        }
+      } else if ((CHAIN || !last) && !rej) {                     // (CHAIN: the last landmark too -- the pose block behind it is a result)
         // down-date (:480) of what lives on: P[r][l] -= K[r, :] . (H P)[:, l] for r, l < pa; rows ds, ds + CAD_DW, ... are
         // this wave's.  Every access is unconditional and every address one base plus a compile-time offset: a row or a
         // column >= pa is dead (nothing reads it again), so what lands there does not matter, and rows up to
@@ -728,6 +756,10 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
   }
   if constexpr (CHAIN) {
     if (rec_wave && lane < 16) o.posefin[lane >> 2][lane & 3] = ((lane >> 2) < 3 && (lane & 3) < 3) ? Pc[lane >> 2][lane & 3] : 0.0;
+  }
+  if (GATE && rec_wave && lane == 0) {
+    o.rej = rmask;
+    if (rmask) cfg.gate_rej[b] += (unsigned long long)__popcll(rmask);
   }
 }
 
@@ -2136,14 +2168,20 @@ void launch_solve_cad(hipStream_t st, const double* P, const double* mu_in, doub
                       const int* nact, const StepIn* in, const CadPlan* plan, int batch, CadOut* out, unsigned* flags,
                       const DeviceConfig& cfg, int ld, long pstride, const double* gbuf, int gparts, double* colbuf, int n_hi,
                       int col_wgs, bool chain, const double* gmu, unsigned* sync, unsigned start_sigma, const CadPre* pre) {
-  if (chain)
-    hipLaunchKernelGGL(k_solve_cad<true>, dim3(batch + (colbuf ? col_wgs : 0)), dim3(64 * CAD_NW), 0, st, P, mu_in, mu_out, dacc_out,
-                       nact, in, plan, batch, out, flags, cfg, ld, pstride, gbuf, gparts, colbuf, col_wgs, n_hi, gmu, sync, start_sigma,
-                       pre);
+  const bool gate = cfg.gate_rej != nullptr;
+  const dim3 grid(batch + (colbuf ? col_wgs : 0)), block(64 * CAD_NW);
+  if (chain && gate)
+    hipLaunchKernelGGL((k_solve_cad<true, true>), grid, block, 0, st, P, mu_in, mu_out, dacc_out, nact, in, plan, batch, out, flags,
+                       cfg, ld, pstride, gbuf, gparts, colbuf, col_wgs, n_hi, gmu, sync, start_sigma, pre);
+  else if (chain)
+    hipLaunchKernelGGL((k_solve_cad<true, false>), grid, block, 0, st, P, mu_in, mu_out, dacc_out, nact, in, plan, batch, out, flags,
+                       cfg, ld, pstride, gbuf, gparts, colbuf, col_wgs, n_hi, gmu, sync, start_sigma, pre);
+  else if (gate)
+    hipLaunchKernelGGL((k_solve_cad<false, true>), grid, block, 0, st, P, mu_in, mu_out, dacc_out, nact, in, plan, batch, out, flags,
+                       cfg, ld, pstride, gbuf, gparts, colbuf, col_wgs, n_hi, nullptr, nullptr, 0u, nullptr);
   else
-    hipLaunchKernelGGL(k_solve_cad<false>, dim3(batch + (colbuf ? col_wgs : 0)), dim3(64 * CAD_NW), 0, st, P, mu_in, mu_out, dacc_out,
-                       nact, in, plan, batch, out, flags, cfg, ld, pstride, gbuf, gparts, colbuf, col_wgs, n_hi, nullptr, nullptr, 0u,
-                       nullptr);
+    hipLaunchKernelGGL((k_solve_cad<false, false>), grid, block, 0, st, P, mu_in, mu_out, dacc_out, nact, in, plan, batch, out, flags,
+                       cfg, ld, pstride, gbuf, gparts, colbuf, col_wgs, n_hi, nullptr, nullptr, 0u, nullptr);
 }
 
 // (chained runs) the next cadence's block and mean from the records `prev` of the cadence whose solve has just run

@@ -81,7 +81,7 @@ struct alignas(16) SolveHead {
   double p22h;          // 0.5 * P[2,2] before the step
   double dacc_old[3];   // pose-block noise already pending before this step
   int cmax;             // largest gathered state index (panel waves starting beyond it never read W)
-  int pad0;
+  unsigned rej;         // NIS gate (ekf_set_nis_gate): bit j set = landmark j of this pass was rejected (its record is zero)
   int c;                // 3 + 2m
   int m;
   int kbase;            // ranks pending before this step (multiple of 4)
@@ -153,6 +153,8 @@ struct alignas(16) CadOut : CadHead {
   double rec[CAD_REC_MAX];
   double posevw[CAD_SLOTS][3][4];   // the new ranks' entries at the pose's state indices l < 3: V[2s][l], V[2s+1][l], W[l][2s], W[l][2s+1]
   double posefin[4][4];             // (k_solve_cad<true>: chained runs) the pose block P(l, l') after the cadence, motion noise included
+  unsigned long long rej;           // (NIS gate on) bit s set = slot s was rejected: its record and posevw entries are zero
+  unsigned long long pad1[3];       // (CadOut stays 32-byte granular)
 };
 // (chained runs) a cadence's inputs as k_solve_cad needs them -- positions, per-step counts and slots, motion inputs,
 // measurements -- formed ONE CADENCE AHEAD by an otherwise idle workgroup of the chain launch (cad_positions is two dependent
@@ -208,7 +210,7 @@ struct alignas(16) InnovRec {
   double S[4];          // row-major
   double nis;
   int idx;
-  int pad;
+  int rejected;         // NIS gate: 1 = the update was rejected (the solve's decision, copied), 0 = applied
 };
 static_assert(sizeof(InnovRec) == 64, "InnovRec is 64 bytes");
 struct InnovLog {
@@ -222,11 +224,20 @@ __host__ __device__ __forceinline__ double innov_nis(double y0, double y1, doubl
   return y0 * (a * y0 + b * y1) + y1 * (c * y0 + d * y1);
 }
 
+// The NIS validation gate (ekf_set_nis_gate): landmark update j is rejected -- its mean, covariance and ranks untouched --
+// when NIS = y^T S^-1 y exceeds the threshold.  Every wave that acts on the decision forms it itself from the same y and S^-1
+// with this one expression (a NaN NIS is never rejected).
+__host__ __device__ __forceinline__ bool innov_reject(double y0, double y1, double a, double b, double c, double d, double gate) {
+  return innov_nis(y0, y1, a, b, c, d) > gate;
+}
+
 struct DeviceConfig {
   double rd[3];         // diag of R  (src/replay_no_ros.py:421)
   double qd[2];         // diag of Q  (:438)
   double arc_threshold; // :376
   int enable_measurement_model, enable_circular_interpolation, disable_motion_model;
+  double nis_gate;                      // NIS gate threshold (ekf_set_nis_gate; read only while gate_rej is set)
+  unsigned long long* gate_rej;         // per trajectory: updates the gate rejected; nullptr = the gate is off
 };
 
 }  // namespace ekf

@@ -13,7 +13,7 @@ namespace ekf {
 
 // one entry: S = (S^-1)^-1 and the NIS with the S^-1 the filter actually used
 __device__ __forceinline__ void innov_from_si(InnovRec* __restrict__ r, int idx, const double* __restrict__ y,
-                                              const double* __restrict__ si) {
+                                              const double* __restrict__ si, int rejected) {
   const double y0 = y[0], y1 = y[1];
   const double a = si[0], b = si[1], c = si[2], d = si[3];
   const double rdet = 1.0 / (a * d - b * c);
@@ -25,21 +25,23 @@ __device__ __forceinline__ void innov_from_si(InnovRec* __restrict__ r, int idx,
   r->S[3] = a * rdet;
   r->nis = innov_nis(y0, y1, a, b, c, d);
   r->idx = idx;
-  r->pad = 0;
+  r->rejected = rejected;
 }
 
 // Per-step kernels (k_solve, k_step_split, k_panels_mono's solve workgroup): one update pass of one step per trajectory.  The
 // pass's landmarks j < m go to positions jbase + j of the step's row (jbase = 16 p for pass p of a step with more than EKF_MMAX
-// landmarks); pass 0 sets the row's count, later passes add to it.  One workgroup of 64 threads per trajectory.
+// landmarks); pass 0 sets the row's count, later passes add to it.  One workgroup of 64 threads per trajectory.  `gate`: the
+// NIS gate is on and SolveHead::rej holds the solve's decisions (copied: the log never decides again).
 __global__ __launch_bounds__(64) void k_innov_step(const StepIn* __restrict__ in, const SolveOut* __restrict__ so, int meas,
-                                                   int batch, InnovLog lg) {
+                                                   int gate, int batch, InnovLog lg) {
   const int b = blockIdx.x, j = threadIdx.x;
   const StepIn& s = in[b];
   const int m = ((s.flags & FLAG_UPDATE) && meas) ? min(s.m, MMAX) : 0;
   const long row = lg.slot0 * batch + b;
   if (j == 0) lg.m[row] = lg.jbase == 0 ? m : lg.m[row] + m;
   if (j < m && lg.jbase + j < AMAX)
-    innov_from_si(lg.rec + row * AMAX + lg.jbase + j, s.idx[j], so[b].it[j].y, so[b].it[j].si);
+    innov_from_si(lg.rec + row * AMAX + lg.jbase + j, s.idx[j], so[b].it[j].y, so[b].it[j].si,
+                  gate ? (int)((so[b].rej >> j) & 1u) : 0);
 }
 
 // A fused cadence (k_solve_cad, any instantiation): trajectory b's slots s0 .. CAD_SLOTS - 1 (right-aligned) belong to the
@@ -50,7 +52,7 @@ __global__ __launch_bounds__(64) void k_innov_step(const StepIn* __restrict__ in
 // launch overwrites in the ring (cap < ns) are skipped, so no two threads write one place.  One workgroup of 64 threads per
 // trajectory; cad_positions' arithmetic (ekf_cadence.hip), restated.
 __global__ __launch_bounds__(64) void k_innov_cad(const StepIn* __restrict__ in, const CadPlan* __restrict__ plan,
-                                                  const CadOut* __restrict__ co, int meas, int batch, InnovLog lg) {
+                                                  const CadOut* __restrict__ co, int meas, int gate, int batch, InnovLog lg) {
   static_assert(CAD_SLOTS <= 64, "one thread per touched step");
   __shared__ int cntS[CAD_SLOTS + 1], loS[CAD_SLOTS + 1], firstS[CAD_SLOTS + 1];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -80,6 +82,7 @@ __global__ __launch_bounds__(64) void k_innov_cad(const StepIn* __restrict__ in,
   const int nslots = min(firstS[CAD_SLOTS], CAD_SLOTS);
   const int s0 = CAD_SLOTS - nslots;
   const double* rec = co[b].rec;
+  const unsigned long long rej = gate ? co[b].rej : 0ull;   // (CadHead::rej: the solve's decisions, by slot)
   for (int e = tid; e < ns * MMAX; e += 64) {
     const int p = e / MMAX, q = e - p * MMAX, j = q - loS[p];
     if (p < pskip || j < 0 || j >= cntS[p]) continue;
@@ -88,17 +91,18 @@ __global__ __launch_bounds__(64) void k_innov_cad(const StepIn* __restrict__ in,
     const long t = pl.t0 + p;
     const long row = ((lg.slot0 + t) % lg.cap) * batch + b;
     const double* r = rec + cad_rec_off(sl);
-    innov_from_si(lg.rec + row * AMAX + q, in[t * batch + b].idx[q], r + 14, r + 10);
+    innov_from_si(lg.rec + row * AMAX + q, in[t * batch + b].idx[q], r + 14, r + 10, (int)((rej >> sl) & 1ull));
   }
 }
 
-void launch_innov_step(hipStream_t st, const StepIn* in, const SolveOut* so, int meas, int batch, const InnovLog& lg) {
-  hipLaunchKernelGGL(k_innov_step, dim3(batch), dim3(64), 0, st, in, so, meas, batch, lg);
+void launch_innov_step(hipStream_t st, const StepIn* in, const SolveOut* so, int meas, int gate, int batch,
+                       const InnovLog& lg) {
+  hipLaunchKernelGGL(k_innov_step, dim3(batch), dim3(64), 0, st, in, so, meas, gate, batch, lg);
 }
 
-void launch_innov_cad(hipStream_t st, const StepIn* in, const CadPlan* plan, const CadOut* co, int meas, int batch,
+void launch_innov_cad(hipStream_t st, const StepIn* in, const CadPlan* plan, const CadOut* co, int meas, int gate, int batch,
                       const InnovLog& lg) {
-  hipLaunchKernelGGL(k_innov_cad, dim3(batch), dim3(64), 0, st, in, plan, co, meas, batch, lg);
+  hipLaunchKernelGGL(k_innov_cad, dim3(batch), dim3(64), 0, st, in, plan, co, meas, gate, batch, lg);
 }
 
 }  // namespace ekf

@@ -120,21 +120,24 @@ struct SolveCore {
   int Cs[CPAD];
   double mot[6];                                       // motion model (wave 3): predicted x, y, theta, G[0,2], G[1,2]
   double2 hS[6];                                       // next linearisation: {h[0][k], h[1][k]} k<5
+  // (NIS gate) y, then the two rows of S^-1 of the landmark at b1: in a row of Ms no step reaches (rows < c <= CMAX)
+  __device__ __forceinline__ double2* gS() { return reinterpret_cast<double2*>(&Ms[CPAD - 2][0]); }
 };
+static_assert(CMAX <= CPAD - 2 && PCS >= 6, "the gate's row of Ms is never part of a gathered block");
 struct SolveLds : SolveCore {
   double Wc[CMAX][WCS];
   double Vc[KTOT][PCS];
   __device__ __forceinline__ FacStd fac_view() { return FacStd{Wc, Vc}; }
 };
 
-template <class Fac>
+template <class Fac, bool GATE>
 __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const double* __restrict__ Pb,
                                            const double* __restrict__ Vb, const double* __restrict__ Wb,
                                            const double* __restrict__ dacc_in, double* __restrict__ dacc_out,
                                            const double* __restrict__ mu_in_b, double* __restrict__ mu_out_b,
                                            const StepIn& s, SolveOut& o, SolveIter* its, unsigned* flag_b,
                                            double* __restrict__ fac_b, const DeviceConfig& cfg, int ld, int kbase,
-                                           bool writer, int neff_eff) {
+                                           bool writer, int neff_eff, unsigned long long* __restrict__ rej_b) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   auto& Pc = L.Pc;
@@ -337,6 +340,16 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
       }
     }
   };
+  // The NIS gate (GATE: the instantiations launched while ekf_set_nis_gate has it on, rej_b this trajectory's rejection
+  // counter; the others are the kernels without it): at b1(j) y_j (from wave 1) and S_j^-1 (from wave 0) are in LDS and every
+  // wave forms the decision itself from them.  A rejected landmark moves nothing: wave 1 skips its mean update, the
+  // down-date waves skip the down-date and wave 0 zeroes its record (H and the K rows), so that the panel kernels replay it
+  // as two exact zero ranks.
+  constexpr bool gate = GATE;
+  auto rejected_at_b1 = [&]() -> bool {
+    const double2 gy = L.gS()[0], ga = L.gS()[1], gc = L.gS()[2];
+    return innov_reject(gy.x, gy.y, ga.x, ga.y, gc.x, gc.y, cfg.nis_gate);
+  };
   if (tid >= 64) {
     // Helper waves.  Wave 1 owns the mean: it publishes the predicted mean and linearises landmark 0 while wave 0
     // forms the predicted covariance block; in iteration j it adds K_j y_j (:476) as soon as wave 0 has published
@@ -362,21 +375,26 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
       if (m > 0) g = jacobian_at_mean(3);
       WG_LDS_BARRIER();                                // S0: predicted covariance block and hS published
       if (m > 0) innovation(g, read_lane(zr, 0), read_lane(zb, 0), y0, y1);
+      if constexpr (GATE)
+        if (lane == 0) L.gS()[0] = make_double2(y0, y1);
     } else {
       WG_LDS_BARRIER();                                // S0
     }
     for (int j = 0; j < m; ++j) {
       WG_LDS_BARRIER();                                // b1(j): K_j and (H P) of landmark j are in LDS
+      const bool rej = gate && rejected_at_b1();
       if (hw == 1) {
         const double2 kj = kcS[ll];
-        if (on) mu_cur += kj.x * y0 + kj.y * y1;      // :476
+        if (on && !rej) mu_cur += kj.x * y0 + kj.y * y1;   // :476
         if (lane == 0) *reinterpret_cast<double2*>(its[j].y) = make_double2(y0, y1);
         LinGeom g{};
         if (j + 1 < m) g = jacobian_at_mean(3 + 2 * (j + 1));
         WG_LDS_BARRIER();                              // b2(j): hS ready, covariance block down-dated
         if (j + 1 < m) innovation(g, read_lane(zr, j + 1), read_lane(zb, j + 1), y0, y1);
+        if constexpr (GATE)
+          if (lane == 0) L.gS()[0] = make_double2(y0, y1);
       } else {
-        if (j + 1 < m) downdate_rows(hw - 1, hpS[ll]);   // waves 2, 3: their third of the rows
+        if (j + 1 < m && !rej) downdate_rows(hw - 1, hpS[ll]);   // waves 2, 3: their third of the rows
         WG_LDS_BARRIER();                              // b2(j)
       }
     }
@@ -437,6 +455,7 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
     o.m = m;
     o.kbase = kbase;
     o.neff = neff_eff;
+    if constexpr (GATE) o.rej = 0u;
     dacc_out[0] = d0 + rd0;                            // the pose-block noise joins the pending update
     dacc_out[1] = d1 + rd1;
     dacc_out[2] = d2 + rd2;
@@ -444,6 +463,7 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
   WG_LDS_BARRIER();                                    // S0 (helper waves wait here too)
 
   // ---- sequential per-landmark recurrences (:436-480) on the compressed system ----
+  unsigned rmask = 0u;                                 // (NIS gate) landmarks rejected
   double h[2][5];
   if (m > 0) {                                         // landmark 0 was linearised by wave 1
 #pragma unroll
@@ -494,11 +514,24 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
       for (int k = 0; k < 5; ++k) *reinterpret_cast<double2*>(it.h5t[k]) = make_double2(h[0][k], h[1][k]);
       *reinterpret_cast<double2*>(&it.si[0]) = make_double2(i00, i01);
       *reinterpret_cast<double2*>(&it.si[2]) = make_double2(i10, i11);
+      if constexpr (GATE) {
+        L.gS()[1] = make_double2(i00, i01);
+        L.gS()[2] = make_double2(i10, i11);
+      }
     }
     WG_LDS_BARRIER();                                  // b1(j): wave 1 starts the next linearisation
+    const bool rej = gate && rejected_at_b1();
+    if (rej) {                                         // (NIS gate) the record of a rejected landmark: H = 0, K = 0
+      if (lane < CMAX) *reinterpret_cast<double2*>(it.kc[lane]) = make_double2(0.0, 0.0);
+      if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) *reinterpret_cast<double2*>(it.h5t[k]) = make_double2(0.0, 0.0);
+      }
+      rmask |= 1u << j;
+    }
     // phase C: down-date (:480), this wave's third of the rows (waves 2, 3 take the others, wave 1 linearises
     // landmark j+1 meanwhile)
-    if (j + 1 < m) downdate_rows(0, make_double2(hp0, hp1));
+    if (j + 1 < m && !rej) downdate_rows(0, make_double2(hp0, hp1));
     WG_LDS_BARRIER();                                  // b2(j)
     if (j + 1 < m) {
 #pragma unroll
@@ -509,9 +542,14 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
       }
     }
   }
+  if (GATE && rmask && lane == 0 && writer) {
+    o.rej = rmask;
+    *rej_b += (unsigned long long)__popc(rmask);
+  }
   }   // wave 0
 }
 
+template <bool GATE>
 __global__ __launch_bounds__(256) void k_solve(const double* __restrict__ P, const double* __restrict__ V,
                                                const double* __restrict__ W,
                                                const double* __restrict__ dacc_in,
@@ -532,9 +570,9 @@ __global__ __launch_bounds__(256) void k_solve(const double* __restrict__ P, con
   // active bound of this step: what the host baked into the record, raised to the handle's floor (the bound the
   // state had when the enqueueing call started: a stream uploaded earlier knows only its own observations)
   const int neff_eff = min(nact[b], max(in[b].neff, neff_floor[b]));
-  solve_body(L, L.fac_view(), P + (long)b * pstride, V + (long)b * KTOT * ld, W + (long)b * KTOT * ld, dacc_in + 4 * b,
+  solve_body<FacStd, GATE>(L, L.fac_view(), P + (long)b * pstride, V + (long)b * KTOT * ld, W + (long)b * KTOT * ld, dacc_in + 4 * b,
              dacc_out + 4 * b, mu_in + (long)b * ld, mu_out + (long)b * ld, in[b], out[b], out[b].it,
-             flags + b, fac + (long)b * FACS, cfg, ld, kbase, true, neff_eff);
+             flags + b, fac + (long)b * FACS, cfg, ld, kbase, true, neff_eff, cfg.gate_rej ? cfg.gate_rej + b : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -881,7 +919,7 @@ struct Empty {};
 //  two waves per SIMD, and a second __launch_bounds__ argument -- which cannot be left out conditionally -- makes the
 //  compiler move a dynamically indexed private array of the rank-split shape into LDS: 8 KB more per workgroup and
 //  that kernel 2.4 x slower at 8 trajectories.)
-template <int MCAP, int NW, bool KSPLIT, bool SPLIT>
+template <int MCAP, int NW, bool KSPLIT, bool SPLIT, bool GATE = false>
 __device__ __forceinline__ void panels_mono(double* __restrict__ P, double* __restrict__ V,
                                             double* __restrict__ W, const double* __restrict__ mu_in,
                                             double* __restrict__ mu_out, const int* __restrict__ nact,
@@ -921,8 +959,9 @@ __device__ __forceinline__ void panels_mono(double* __restrict__ P, double* __re
     const int neff_eff = min(n, max(sa.in[b].neff, sa.neff_floor[b]));
     if (solver) {
       if (b == 0 && tid < 8) sa.queue[tid * RS_QSTRIDE] = 0u;   // (see k_solve)
-      solve_body(sL, FacPanel<CC>{sF}, Pb, Vb, Wb, sa.dacc_in + 4 * b, sa.dacc_out + 4 * b, mu_in_b, mu_out_b, sa.in[b],
-                 sa.out[b], sa.out[b].it, sa.flags + b, sa.fac + (long)b * FACS, sa.cfg, ld, sa.kbase, true, neff_eff);
+      solve_body<FacPanel<CC>, GATE>(sL, FacPanel<CC>{sF}, Pb, Vb, Wb, sa.dacc_in + 4 * b, sa.dacc_out + 4 * b, mu_in_b, mu_out_b, sa.in[b],
+                 sa.out[b], sa.out[b].it, sa.flags + b, sa.fac + (long)b * FACS, sa.cfg, ld, sa.kbase, true, neff_eff,
+                 sa.cfg.gate_rej ? sa.cfg.gate_rej + b : nullptr);
       {
         int ms = ((sa.in[b].flags & FLAG_UPDATE) && sa.cfg.enable_measurement_model) ? sa.in[b].m : 0;
         mailbox_publish(sa.out[b], sa.mbox + b, min(ms, MMAX), sa.ready + b, sa.seq, sa.publish);
@@ -1288,12 +1327,12 @@ __global__ __launch_bounds__(64 * NW) void k_panels(double* __restrict__ P, doub
                                                     const double* __restrict__ fac, int ld, long pstride) {
   panels_mono<MCAP, NW, KSPLIT, false>(P, V, W, mu_in, mu_out, nact, so, fac, ld, pstride, SplitArgs{});
 }
-template <int MCAP>
+template <int MCAP, bool GATE>
 __global__ __launch_bounds__(256, 2) void k_panels_split(double* __restrict__ P, double* __restrict__ V,
                                                          double* __restrict__ W, const double* __restrict__ mu_in,
                                                          double* __restrict__ mu_out, const int* __restrict__ nact,
                                                          int ld, long pstride, SplitArgs sa) {
-  panels_mono<MCAP, 4, false, true>(P, V, W, mu_in, mu_out, nact, nullptr, nullptr, ld, pstride, sa);
+  panels_mono<MCAP, 4, false, true, GATE>(P, V, W, mu_in, mu_out, nact, nullptr, nullptr, ld, pstride, sa);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1310,7 +1349,7 @@ __global__ __launch_bounds__(256, 2) void k_panels_split(double* __restrict__ P,
 // smaller linear index (dispatched before it), the wait is bounded, and a timeout raises EKF_FLAG_INTERNAL.
 // ---------------------------------------------------------------------------------------------
 
-template <int MCAP>
+template <int MCAP, bool GATE>
 __global__ __launch_bounds__(256) void k_step_split(double* __restrict__ P, double* __restrict__ V,
                                                     double* __restrict__ W, const double* __restrict__ dacc_in,
                                                     double* __restrict__ dacc_out, const double* __restrict__ mu_in,
@@ -1336,9 +1375,9 @@ __global__ __launch_bounds__(256) void k_step_split(double* __restrict__ P, doub
   const int neff_eff = min(n, max(in[b].neff, neff_floor[b]));
   if (blockIdx.x == 0) {                               // ---- the solve of trajectory b ----
     if (b == 0 && tid < 8) queue[tid * RS_QSTRIDE] = 0u;   // (see k_solve)
-    solve_body(U.L, U.L.fac_view(), P + (long)b * pstride, V + (long)b * KTOT * ld, W + (long)b * KTOT * ld, dacc_in + 4 * b,
+    solve_body<FacStd, GATE>(U.L, U.L.fac_view(), P + (long)b * pstride, V + (long)b * KTOT * ld, W + (long)b * KTOT * ld, dacc_in + 4 * b,
                dacc_out + 4 * b, mu_in + (long)b * ld, mu_out + (long)b * ld, in[b], out[b], out[b].it, flags + b,
-               fac + (long)b * FACS, cfg, ld, kbase, true, neff_eff);
+               fac + (long)b * FACS, cfg, ld, kbase, true, neff_eff, cfg.gate_rej ? cfg.gate_rej + b : nullptr);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); // this wave's stores are visible device-wide ...
     __syncthreads();                                   // ... every wave's are ...
     // ... then the word (publish = 0: a test of the panels' bounded wait -- they must time out, not hang)
@@ -2383,8 +2422,12 @@ void launch_solve(hipStream_t st, const double* P, const double* V, const double
                   double* dacc_out, const double* mu_in, double* mu_out, const int* nact, const StepIn* in,
                   SolveOut* out, unsigned* flags, double* fac, const int* neff_floor, unsigned* queue,
                   const DeviceConfig& cfg, int ld, long pstride, int batch, int kbase) {
-  hipLaunchKernelGGL(k_solve, dim3(batch), dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out, nact, in,
-                     out, flags, fac, neff_floor, queue, cfg, ld, pstride, kbase);
+  if (cfg.gate_rej)                                    // (the NIS gate is on)
+    hipLaunchKernelGGL(k_solve<true>, dim3(batch), dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out, nact, in,
+                       out, flags, fac, neff_floor, queue, cfg, ld, pstride, kbase);
+  else
+    hipLaunchKernelGGL(k_solve<false>, dim3(batch), dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out, nact, in,
+                       out, flags, fac, neff_floor, queue, cfg, ld, pstride, kbase);
 }
 
 template <int MCAP>
@@ -2421,7 +2464,12 @@ void launch_step_split_tp(hipStream_t st, int mcap, double* P, double* V, double
   const dim3 grid(1 + (n_hi + 255) / 256, batch);
   SplitArgs sa{dacc_in, dacc_out, in, out, flags, fac, neff_floor, queue, mbox, ready, seq, publish, kbase, cfg};
 #define EKF_SPLIT_TP(M)                                                                                              \
-  hipLaunchKernelGGL((k_panels_split<M>), grid, dim3(256), 0, st, P, V, W, mu_in, mu_out, nact, ld, pstride, sa)
+  do {                                                                                                               \
+    if (cfg.gate_rej)                                                                                                \
+      hipLaunchKernelGGL((k_panels_split<M, true>), grid, dim3(256), 0, st, P, V, W, mu_in, mu_out, nact, ld, pstride, sa); \
+    else                                                                                                             \
+      hipLaunchKernelGGL((k_panels_split<M, false>), grid, dim3(256), 0, st, P, V, W, mu_in, mu_out, nact, ld, pstride, sa); \
+  } while (0)
   switch (mcap) {
     case 1: EKF_SPLIT_TP(1); break;
     case 2: EKF_SPLIT_TP(2); break;
@@ -2442,8 +2490,14 @@ void launch_step_split(hipStream_t st, int mcap, double* P, double* V, double* W
                        int publish, const DeviceConfig& cfg, int ld, long pstride, int batch, int n_hi, int kbase) {
   const dim3 grid(1 + (n_hi + 63) / 64, batch);
 #define EKF_SPLIT(M)                                                                                                \
-  hipLaunchKernelGGL((k_step_split<M>), grid, dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out, nact, in, out, \
-                     flags, fac, neff_floor, queue, ready, seq, publish, cfg, ld, pstride, kbase)
+  do {                                                                                                              \
+    if (cfg.gate_rej)                                                                                               \
+      hipLaunchKernelGGL((k_step_split<M, true>), grid, dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out, nact, in, \
+                         out, flags, fac, neff_floor, queue, ready, seq, publish, cfg, ld, pstride, kbase);         \
+    else                                                                                                            \
+      hipLaunchKernelGGL((k_step_split<M, false>), grid, dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out, nact, in, \
+                         out, flags, fac, neff_floor, queue, ready, seq, publish, cfg, ld, pstride, kbase);         \
+  } while (0)
   switch (mcap) {
     case 1: EKF_SPLIT(1); break;
     case 2: EKF_SPLIT(2); break;

@@ -29,13 +29,16 @@ constexpr int SMALL_N_MAX_BANK = 131;   // ... but not for a bank that fills the
 constexpr int SMALL_BANK_MIN = 128;     // workgroup per CU): N = 64 x 256 10.4 M against 7.9 M steps/s, x 1024 against 5.4 M
 
 // One step's landmark updates and prediction on the LDS-resident state.  `Pl` is n x ps (ps odd: row and column walks are
-// both conflict-free), `mu` the mean, `hp` / `kk` 2 x n scratch.  LOG: landmark j's index, y, S and NIS go to lrow[jbase + j]
-// (the innovation log, ekf_innovations.hip), written by the wave that computed y; the LOG = false instantiations are the
-// kernels as they were.
+// both conflict-free), `mu` the mean, `hp` / `kk` 2 x n scratch.  LOG: the instantiations that serve the innovation log and
+// the NIS gate.  With `lrow` set, landmark j's index, y, S, NIS and the gate's decision go to lrow[jbase + j] (the innovation
+// log, ekf_innovations.hip).  With the gate on (cfg.gate_rej set), a landmark whose NIS exceeds cfg.nis_gate gets K = 0 -- the
+// down-date and the mean update then subtract and add exact zeros -- and is counted in `nrej`.  The LOG = false
+// instantiations are the kernels as they were.
 template <int NT, int TM, bool LOG>
 __device__ __forceinline__ void small_step(double* __restrict__ Pl, double* __restrict__ mu, double* __restrict__ hp,
                                            double* __restrict__ kk, double* __restrict__ sc, const StepIn& s,
-                                           const DeviceConfig& cfg, int n, int ps, InnovRec* __restrict__ lrow, int jbase) {
+                                           const DeviceConfig& cfg, int n, int ps, InnovRec* __restrict__ lrow, int jbase,
+                                           int& nrej) {
   const int tid = threadIdx.x;
   const bool do_pred = (s.flags & FLAG_PREDICT) != 0;
   int m = ((s.flags & FLAG_UPDATE) && cfg.enable_measurement_model) ? s.m : 0;
@@ -154,10 +157,45 @@ __device__ __forceinline__ void small_step(double* __restrict__ Pl, double* __re
     }
     const double rdet = 1.0 / (S00 * S11 - S01 * S10);
     const double i00 = S11 * rdet, i01 = -S01 * rdet, i10 = -S10 * rdet, i11 = S00 * rdet;
+    // (NIS gate, innovation log) y (published by wave 3 before the barrier above), S and 1 / det S pass through empty asm
+    // statements and S^-1 is formed again from those copies -- the same values as the filter's: an extra use of the filter's
+    // own S^-1 lets the compiler contract K = (H P)^T S^-1 differently (other bits); this way the filter computes exactly what
+    // it computes without them.  Every thread forms the same NIS, so the decision is the workgroup's.
+    const bool gate = cfg.gate_rej != nullptr;
+    bool rej = false;
+    if (LOG && (lrow || gate)) {                            // (uniform)
+      double v[7] = {sc[2], sc[3], S00, S01, S10, S11, rdet};
+#pragma unroll
+      for (int q = 0; q < 7; ++q) asm volatile("" : "+v"(v[q]));
+      const double ld = v[6];
+      const double nis = innov_nis(v[0], v[1], v[5] * ld, -v[3] * ld, -v[4] * ld, v[2] * ld);
+      rej = gate && nis > cfg.nis_gate;                     // (innov_reject's test: a NaN NIS is applied)
+      if constexpr (LOG) {
+        if (lrow && tid == NT - 64 && jbase + j < AMAX) {
+          InnovRec& r = lrow[jbase + j];
+          r.y[0] = v[0];
+          r.y[1] = v[1];
+          r.S[0] = v[2];
+          r.S[1] = v[3];
+          r.S[2] = v[4];
+          r.S[3] = v[5];
+          r.nis = nis;
+          r.idx = lm;
+          r.rejected = rej ? 1 : 0;
+        }
+      }
+    }
     for (int c = tid; c < n; c += NT) {                     // K[c, :] = (H P)[:, c]^T S^-1   (P symmetric)
       const double a0 = hp[c], a1 = hp[n + c];
       kk[c] = a0 * i00 + a1 * i10;
       kk[n + c] = a0 * i01 + a1 * i11;
+    }
+    if (rej) {                                              // (uniform) a rejected landmark: K = 0, so that the down-date
+      for (int c = tid; c < n; c += NT) {                   // and the mean update below leave P and the mean as they are
+        kk[c] = 0.0;
+        kk[n + c] = 0.0;
+      }
+      nrej += 1;
     }
     __syncthreads();
     const double y0 = sc[2], y1 = sc[3];
@@ -193,34 +231,13 @@ __device__ __forceinline__ void small_step(double* __restrict__ Pl, double* __re
         }
     }
     for (int c = tid; c < n; c += NT) mu[c] += kk[c] * y0 + kk[n + c] * y1;     // :476
-    if constexpr (LOG) {
-      if (tid == NT - 64 && jbase + j < AMAX) {
-        // y and S pass through empty asm statements and S^-1 is formed again from those copies, as above: an extra use of
-        // the filter's own S^-1 lets the compiler contract K = (H P)^T S^-1 differently (other bits); this way the LOG
-        // instantiations compute exactly what the others do
-        double v[6] = {y0, y1, S00, S01, S10, S11};
-#pragma unroll
-        for (int q = 0; q < 6; ++q) asm volatile("" : "+v"(v[q]));
-        const double ld = 1.0 / (v[2] * v[5] - v[3] * v[4]);
-        InnovRec& r = lrow[jbase + j];
-        r.y[0] = v[0];
-        r.y[1] = v[1];
-        r.S[0] = v[2];
-        r.S[1] = v[3];
-        r.S[2] = v[4];
-        r.S[3] = v[5];
-        r.nis = innov_nis(v[0], v[1], v[5] * ld, -v[3] * ld, -v[4] * ld, v[2] * ld);
-        r.idx = lm;
-        r.pad = 0;
-      }
-    }
     __syncthreads();
   }
 }
 
 // One workgroup per trajectory runs `nsteps` steps: in[k * batch + b], k = 0 .. nsteps - 1.
 // TM: column tiles of 16 the state spans at most (n <= 16 TM): the down-date's loads are unrolled over them.
-// LOG: step k is logged in ring row (lg.slot0 + k) % lg.cap (InnovLog, ekf_device.h).
+// LOG: with lg.rec set, step k is logged in ring row (lg.slot0 + k) % lg.cap (InnovLog, ekf_device.h).
 template <int NT, int TM, bool LOG>
 __device__ __forceinline__ void small_stream_body(double* __restrict__ P, const double* __restrict__ mu_in,
                                                   double* __restrict__ mu_out, const int* __restrict__ nact,
@@ -278,6 +295,7 @@ __device__ __forceinline__ void small_stream_body(double* __restrict__ P, const 
   for (int c = tid; c < n; c += NT) mu[c] = mu_in[(long)b * ld + c];
   if (tid < RW) recw[tid] = reinterpret_cast<const unsigned long long*>(in + b)[tid];
   __syncthreads();
+  int nrej = 0;                                             // (NIS gate) landmarks this launch rejected (every thread counts)
   for (int k = 0; k < nsteps; ++k) {
     unsigned long long nxt = 0;
     const bool more = k + 1 < nsteps;
@@ -285,17 +303,20 @@ __device__ __forceinline__ void small_stream_body(double* __restrict__ P, const 
     const StepIn& sk = *reinterpret_cast<const StepIn*>(recw + (k & 1) * RW);
     InnovRec* lrow = nullptr;
     if constexpr (LOG) {
-      const long row = ((lg.slot0 + k) % lg.cap) * batch + b;
-      lrow = lg.rec + row * AMAX;
-      if (tid == 0) {
-        const int ms = ((sk.flags & FLAG_UPDATE) && cfg.enable_measurement_model) ? min(sk.m, MMAX) : 0;
-        lg.m[row] = lg.jbase == 0 ? ms : lg.m[row] + ms;
+      if (lg.rec) {                                         // (uniform)
+        const long row = ((lg.slot0 + k) % lg.cap) * batch + b;
+        lrow = lg.rec + row * AMAX;
+        if (tid == 0) {
+          const int ms = ((sk.flags & FLAG_UPDATE) && cfg.enable_measurement_model) ? min(sk.m, MMAX) : 0;
+          lg.m[row] = lg.jbase == 0 ? ms : lg.m[row] + ms;
+        }
       }
     }
-    small_step<NT, TM, LOG>(Pl, mu, hp, kk, sc, sk, cfg, n, ps, lrow, lg.jbase);
+    small_step<NT, TM, LOG>(Pl, mu, hp, kk, sc, sk, cfg, n, ps, lrow, lg.jbase, nrej);
     if (more && tid < RW) recw[((k + 1) & 1) * RW + tid] = nxt;
     __syncthreads();
   }
+  if (nrej && tid == 0) cfg.gate_rej[b] += (unsigned long long)nrej;
   bool bad = false;
   for (int c = tid; c < n; c += NT) {
     const double v = mu[c];
@@ -382,8 +403,9 @@ template <int NT, int TM>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_small_stream_two(SMALL_STREAM_ARGS) {
   small_stream_body<NT, TM, false>(SMALL_STREAM_PASS, InnovLog{});
 }
-// The same three forms with the innovation log on (ekf_log_innovations): the filter's arithmetic is the same instructions,
-// the log adds stores behind each landmark's S.
+// The same three forms with the innovation log (ekf_log_innovations) or the NIS gate (ekf_set_nis_gate) on: the filter's
+// arithmetic is the same instructions; the log adds stores behind each landmark's S, the gate a test and, for a rejected
+// landmark, K = 0.
 template <int NT, int TM>
 __global__ __launch_bounds__(NT) void k_small_stream_log(SMALL_STREAM_ARGS, InnovLog lg) {
   small_stream_body<NT, TM, true>(SMALL_STREAM_PASS, lg);

@@ -19,6 +19,7 @@ from __future__ import annotations
 import collections
 import ctypes as C
 import dataclasses
+import math
 import os
 import subprocess
 import threading
@@ -113,6 +114,9 @@ ABI = {
     "ekf_log_innovations": (C.c_int, [C.c_void_p, C.c_int]),
     "ekf_innovation_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "ekf_download_innovations": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, _ip, _ip, _dp, _dp, _dp]),
+    "ekf_set_nis_gate": (C.c_int, [C.c_void_p, C.c_double]),
+    "ekf_download_gate_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
+    "ekf_download_innovation_rejections": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, _ip]),
     "ekf_add_landmarks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int]),
     "ekf_predict": (C.c_int, [C.c_void_p, _dp, _dp]),
     "ekf_update": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _ip, C.c_int]),
@@ -296,6 +300,7 @@ class Innovations(typing.NamedTuple):
     y: np.ndarray         # (K, B, W, 2)     innovation
     S: np.ndarray         # (K, B, W, 2, 2)  innovation covariance
     nis: np.ndarray       # (K, B, W)   y^T S^-1 y
+    rejected: Optional[np.ndarray] = None   # (K, B, W) 1: the NIS gate rejected the update, 0: applied, -1 beyond m
 
 
 class EkfSlam:
@@ -494,9 +499,44 @@ class EkfSlam:
         nis = np.empty(shape + (EKF_AMAX,))
         self._check(self._lib.ekf_download_innovations(self._h, first, count, _p(m, _ip), _p(idx, _ip), _p(y), _p(S),
                                                        _p(nis)))
+        rej = np.empty(shape + (EKF_AMAX,), dtype=np.int32)
+        self._check(self._lib.ekf_download_innovation_rejections(self._h, first, count, _p(rej, _ip)))
         W = min(int(m.max()), EKF_AMAX) if m.size else 0
         return Innovations(np.arange(first, first + count, dtype=np.int64), m, idx[..., :W].copy(), y[..., :W, :].copy(),
-                           S[..., :W, :, :].copy(), nis[..., :W].copy())
+                           S[..., :W, :, :].copy(), nis[..., :W].copy(), rej[..., :W].copy())
+
+    @staticmethod
+    def nis_gate_threshold(threshold: Optional[float] = None, confidence: Optional[float] = None) -> float:
+        """The threshold ``set_nis_gate`` passes to the library: `threshold` itself, or for a `confidence` p the chi-square
+        quantile of 2 degrees of freedom in closed form, -2 ln(1 - p) (what ``scipy.stats.chi2.ppf(p, 2)`` gives, and the
+        gate ``evaluation.nis_consistency(confidence=p)`` counts against); +inf (off) when both are None."""
+        if threshold is not None and confidence is not None:
+            raise ValueError("set_nis_gate: give a threshold or a confidence, not both")
+        if confidence is not None:
+            p = float(confidence)
+            if not 0.0 < p < 1.0:
+                raise ValueError(f"set_nis_gate: confidence must lie in (0, 1), got {confidence!r}")
+            return -2.0 * math.log1p(-p)
+        if threshold is None:
+            return math.inf
+        g = float(threshold)
+        if not g > 0.0:                                  # (NaN too)
+            raise ValueError(f"set_nis_gate: the threshold must be > 0, got {threshold!r}")
+        return g
+
+    def set_nis_gate(self, threshold: Optional[float] = None, confidence: Optional[float] = None):
+        """Switch the NIS validation gate on: a landmark update whose NIS = y^T S^-1 y exceeds the threshold -- `threshold`,
+        or the chi2_2 quantile at `confidence` -- is rejected on the device: mean and covariance stay as they were, later
+        updates see the state as if it had never been given.  None for both switches it off (the default: same results and
+        scheduling as without the gate).  Applies to the work enqueued after the call and clears ``gate_counts()``."""
+        g = self.nis_gate_threshold(threshold, confidence)
+        self._check(self._lib.ekf_set_nis_gate(self._h, g))
+
+    def gate_counts(self) -> np.ndarray:
+        """(B,) int64: landmark updates each trajectory's gate rejected since the last ``set_nis_gate``.  Blocking."""
+        out = np.zeros(self.batch, dtype=np.int64)
+        self._check(self._lib.ekf_download_gate_counts(self._h, 0, self.batch, out.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return out
 
     def state(self, b: int = 0):
         n = self.size(b)
