@@ -16,19 +16,18 @@ namespace ekf {
 void launch_solve(hipStream_t, const double*, const double*, const double*, const double*, double*, const double*,
                   double*, const int*, const StepIn*, SolveOut*, unsigned*, double*, const int*, unsigned*, const DeviceConfig&,
                   int, long, int, int);
-bool step_is_split(int batch, int n_hi, int cus);
 void launch_step_split(hipStream_t, int, double*, double*, double*, const double*, double*, const double*, double*,
                        const int*, const StepIn*, SolveOut*, unsigned*, double*, const int*, unsigned*, unsigned*, unsigned,
                        int, const DeviceConfig&, int, long, int, int, int);
 void launch_step_split_tp(hipStream_t, int, double*, double*, double*, const double*, double*, const double*, double*,
                           const int*, const StepIn*, SolveOut*, unsigned*, double*, const int*, unsigned*, SolveOut*,
                           unsigned*, unsigned, int, const DeviceConfig&, int, long, int, int, int);
-void launch_panels(hipStream_t, int, double*, double*, double*, const double*, double*, const int*,
+void launch_panels(hipStream_t, int, bool, double*, double*, double*, const double*, double*, const int*,
                    const SolveOut*, const double*, int, long, int, int);
-void launch_flush(hipStream_t, bool, double*, const double*, const double*, const double*, const int*,
-                  const SolveOut*, int, long, int, int, int, int);
-void launch_flush_rs(hipStream_t, bool, double*, const double*, const double*, const double*, const int*,
-                     const SolveOut*, int, long, int, int, int, int, unsigned*, int, const int*, const CadOut*);
+void launch_flush(hipStream_t, const PassPlan&, double*, const double*, const double*, const double*, const int*,
+                  const SolveOut*, int, long, int);
+void launch_flush_rs(hipStream_t, const PassPlan&, double*, const double*, const double*, const double*, const int*,
+                     const SolveOut*, int, long, int, unsigned*, const int*, const CadOut*);
 int flush_rs_queue_words();
 void launch_predict_rc(hipStream_t, double*, const double*, double*, const int*, const SolveOut*, int, long,
                        int, int);
@@ -36,11 +35,10 @@ void launch_add_landmarks(hipStream_t, double*, double*, int, int, int, double, 
 void launch_mirror(hipStream_t, double*, const int*, int, long, int, int);
 void launch_pack_small(hipStream_t, const double*, const double*, const unsigned*, int, int, double*);
 void launch_pack_dense(hipStream_t, const double*, int, int, double*);
-int small_state_limit(int batch);
 void launch_innov_step(hipStream_t, const StepIn*, const SolveOut*, int, int, int, const InnovLog&);
 void launch_innov_cad(hipStream_t, const StepIn*, const CadPlan*, const CadOut*, int, int, int, const InnovLog&);
 int launch_small_stream(hipStream_t, double*, const double*, double*, const int*, const StepIn*, int, int, unsigned*,
-                        const DeviceConfig&, int, long, int, double*, int, unsigned long long*, unsigned long long, bool,
+                        const DeviceConfig&, int, long, int, double*, int, unsigned long long*, unsigned long long, int,
                         const InnovLog*);
 void launch_associate(hipStream_t, const DetIn*, int*, int*, int*, double*, double*, double*, double*, StepIn*,
                       AssocOut*, unsigned*, const AssocConfig&, int, long, int, int, int);
@@ -54,7 +52,6 @@ void launch_chain_cad(hipStream_t, const double*, const double*, const double*, 
                       unsigned*, int, unsigned, const CadPre*, CadPre*, const CadPlan*, bool);
 void launch_mark(hipStream_t, unsigned*, unsigned);
 void launch_gate(hipStream_t, unsigned*, unsigned, unsigned*, int);
-int chain_gather_workgroups(int, int);
 int chain_sync_words();
 void launch_snap_pose(hipStream_t, const double*, const int*, int, long, int, int, double*);
 void launch_gather_cad(hipStream_t, const double*, const double*, const double*, const double*, const StepIn*, const CadPlan*, int,
@@ -62,8 +59,7 @@ void launch_gather_cad(hipStream_t, const double*, const double*, const double*,
 long cadence_gbuf_doubles();
 void launch_panels_cad(hipStream_t, double*, double*, double*, const double*, double*, const int*, const CadOut*,
                        SolveOut*, unsigned*, int, long, int, int, int, const double*, double*, unsigned*, unsigned, unsigned*,
-                       bool, unsigned, int, bool);
-bool panels_cad_latency_regime(int, int);
+                       int, unsigned, bool);
 void launch_marginals(hipStream_t, const double*, const double*, const double*, const double*, const int*, const SolveOut*, int,
                       long, int, int, int, int, double*, double*);
 }  // namespace ekf
@@ -178,23 +174,13 @@ struct ekf_handle : ekf::HostPlan {
   long pre_serial[2] = {-1, -1};
   long cad_serial = 0;
   hipEvent_t ev_pass = nullptr;   // recorded on the second stream when a chain of cadences ends (join_aux): the only event of the chained order
-  bool chain_run = false;         // the run in flight records the transforms (every solve is k_solve_cad<true>)
   bool aux_pass = false;          // a covariance pass is in flight on the second stream (ev_pass recorded behind it)
-  int opt_chain = 1;
-  // 1 = where a fused cadence's covariance pass follows its panel launch at once, in the row-slab form, the panel launch writes V
-  // only and the pass forms its W fragments from V and the records' S^-1 (half of the panel launch's stores); bit-identical
-  int opt_w_from_v = 1;
-  long w_from_v_passes = 0;       // statistics
-  int opt_panel_shape = 0;        // diagnostics: 0 = the panel launch's shape by its size; 1 k_panels_cad_ks, 2 k_panels_cad<1>, 3 k_panels_cad<4> whatever the size
-  int opt_panel_tform = 1;        // 1 = a chained cadence's panel launch in the latency regime takes the triangular-solve form (k_panels_cad_tf)
+  long w_from_v_passes = 0;       // statistics: passes that formed W from V ("w_from_v")
   int opt_run_end_flush = 0;      // 1 = ekf_stream_run applies what its last cadence left pending, so that the next call starts fused
   long chained = 0;               // statistics: cadences whose block came from k_chain_cad
   // The mirrored column entries of a cadence's panel launch, gathered by extra workgroups of its solve launch and laid down
-  // as rows (batch x 83 x ld doubles, allocated on first use; not for banks where that would exceed 1 GiB).  `colbuf_live`:
-  // the solve in flight has filled it (a solve launched beside a covariance pass -- look-ahead -- cannot: P_base is in motion)
+  // as rows (batch x 83 x ld doubles, allocated on first use; not for banks where that would exceed 1 GiB; "col_gather")
   double* dcolbuf = nullptr;
-  bool colbuf_live = false;
-  int opt_col_gather = 1;         // 1 = gather them beside the solve, 0 = the panel launch gathers everything itself
   long cadences = 0, cadence_traj_steps = 0;   // statistics: fused cadences launched, trajectory-steps they completed
   // The packed cadences of the ekf_stream_run in flight (ekf_host_plan.h: plan_cadences): one CadPlan per (cadence,
   // trajectory), planned on the host for the whole run and uploaded once, stream-ordered, out of pinned memory.  Two copies,
@@ -1015,13 +1001,10 @@ static int flush_pending(ekf_handle* h, hipStream_t st, const CadOut* wv) {
   h->last_nkt = p.nkt;
   h->last_streaming = p.streaming ? 1 : 0;
   h->last_shares = shares ? h->shares_ok : 0;
-  if (p.kernel == 2) {                                 // (the step before left the queue heads at zero)
-    launch_flush_rs(st, p.streaming, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dn, h->dso, h->ld, h->pstride,
-                    h->batch, p.e_hi, p.nkt, p.rs_workgroups, h->dqueue, h->opt_pass_chunk, shares, p.kernel == 2 ? wv : nullptr);
-  } else {
-    launch_flush(st, p.streaming, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dn, h->dso, h->ld, h->pstride, h->batch,
-                 p.e_hi, p.nkt, flush_rows_per_block(h, p.streaming, p.e_hi));
-  }
+  if (p.kernel == 2)                                   // (the step before left the queue heads at zero)
+    launch_flush_rs(st, p, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dn, h->dso, h->ld, h->pstride, h->batch, h->dqueue, shares, wv);
+  else
+    launch_flush(st, p, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dn, h->dso, h->ld, h->pstride, h->batch);
   if (timed) HIP_TRY(h, hipEventRecord(e1, st));
   HIP_TRY(h, hipGetLastError());
   h->pending_k = 0;                                    // (with no rank pending k_solve takes the pending noise as zero: no clearing)
@@ -1030,11 +1013,7 @@ static int flush_pending(ekf_handle* h, hipStream_t st, const CadOut* wv) {
 }
 static int flush_pending(ekf_handle* h) { return flush_pending(h, nullptr); }
 
-// The small-state path (ekf_small.hip): a filter bank whose covariances fit the LDS of a CU runs `nsteps` steps per trajectory
-// inside one workgroup, P resident in LDS; nothing is ever pending on it.
-static bool small_path(const ekf_handle* h) {
-  return h->opt_small_state && h->n_max <= small_state_limit(h->batch) && h->pending_k == 0;
-}
+// The small-state path (ekf_small.hip, ekf_host_plan.h: small_path): `nsteps` steps per trajectory in one launch.
 static int enqueue_small(ekf_handle* h, const StepIn* d_in, int nsteps) {
   const int n_hi = h->sizes_dirty ? h->n_max : *std::max_element(h->n.begin(), h->n.end());
   const int out_b = h->fetch_b;                        // (ekf_step_fetch, last pass of its step: see there)
@@ -1045,7 +1024,7 @@ static int enqueue_small(ekf_handle* h, const StepIn* d_in, int nsteps) {
   if (launch_small_stream(h->stream, h->dP, h->dmu2[h->cur], h->dmu2[h->cur ^ 1], h->dn, d_in, h->batch, nsteps, h->dflags,
                           h->dcfg, h->ld, h->pstride, n_hi, out_b >= 0 ? h->h_pack : nullptr, out_b,
                           out_b >= 0 ? reinterpret_cast<unsigned long long*>(h->h_pack + PACK_WORDS - 1) : nullptr,
-                          out_b >= 0 ? ++h->fetch_seq : 0ull, h->batch > 3 * h->cu_count,
+                          out_b >= 0 ? ++h->fetch_seq : 0ull, plan_small(h, n_hi),
                           logged || h->dcfg.gate_rej ? &lg : nullptr) != 0)
     return fail(h, EKF_ERR_HIP, "small-state launch: hipFuncSetAttribute failed");
   HIP_TRY(h, hipGetLastError());
@@ -1066,16 +1045,13 @@ static void log_pass(ekf_handle* h, const StepIn* d_in) {
 static int enqueue_pass(ekf_handle* h, const StepIn* d_in, int m_hi) {
   if (small_path(h)) return enqueue_small(h, d_in, 1);
   const int n_hi = h->sizes_dirty ? h->n_max : *std::max_element(h->n.begin(), h->n.end());
-  const int mcap = cap_for(m_hi);
-  const int ktp = ranks_for(mcap);
+  const StepPlan sp = plan_step(h, m_hi, n_hi);
   const double* mu_in = h->dmu2[h->cur];
   double* mu_out = h->dmu2[h->cur ^ 1];
-  const double* dacc_in = h->ddacc2[h->dcur];
-  double* dacc_out = h->ddacc2[h->dcur ^ 1];
-  if (m_hi == 0 && h->pending_k == 0) {
+  if (sp.form == STEP_PREDICT) {
     // prediction only, nothing pending: rows/cols 0,1 of P_base directly, O(n)
-    launch_solve(h->stream, h->dP, h->dV, h->dW, dacc_in, dacc_out, mu_in, mu_out, h->dn, d_in, h->dso, h->dflags,
-                 h->dfac, h->dfloor, h->dqueue, h->dcfg, h->ld, h->pstride, h->batch, 0);
+    launch_solve(h->stream, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->ddacc2[h->dcur ^ 1], mu_in, mu_out, h->dn, d_in, h->dso,
+                 h->dflags, h->dfac, h->dfloor, h->dqueue, h->dcfg, h->ld, h->pstride, h->batch, 0);
     launch_predict_rc(h->stream, h->dP, mu_in, mu_out, h->dn, h->dso, h->ld, h->pstride, h->batch, n_hi);
     log_pass(h, d_in);
     // k_predict_rc applied the noise itself (and nothing reads the pending-noise buffers while no rank is pending)
@@ -1083,32 +1059,23 @@ static int enqueue_pass(ekf_handle* h, const StepIn* d_in, int m_hi) {
     h->cur ^= 1;
     return EKF_OK;
   }
-  // The kernels WRITE the rank slots of `mcap` landmarks behind the pending ones (zeros where a trajectory observes fewer) plus
-  // the k-tile pad; the step is CHARGED the ranks of the busiest trajectory only (round 5: 2 per landmark, as the packed
-  // cadences do) -- the next step starts right behind them and overwrites the zeros.  m = 5: 7 steps per pass (until round 4:
-  // 5, the count rounded up to 8 landmarks), m = 12: 3 (2).
-  if (((h->pending_k + ktp + 3) & ~3) > KTOT)
+  if (sp.flush_before)
     if (int rc = flush_pending(h)) return rc;
-  dacc_in = h->ddacc2[h->dcur];
-  dacc_out = h->ddacc2[h->dcur ^ 1];
-  if (h->opt_fused_step && step_is_split(h->batch, n_hi, h->cu_count)) {
-    // few workgroups (the latency regime): the whole step as one launch, the panels gathered beside the solve
-    launch_step_split(h->stream, mcap, h->dP, h->dV, h->dW, dacc_in, dacc_out, mu_in, mu_out, h->dn, d_in, h->dso,
+  const double* dacc_in = h->ddacc2[h->dcur];
+  double* dacc_out = h->ddacc2[h->dcur ^ 1];
+  if (sp.form == STEP_SPLIT) {
+    launch_step_split(h->stream, sp.mcap, h->dP, h->dV, h->dW, dacc_in, dacc_out, mu_in, mu_out, h->dn, d_in, h->dso,
                       h->dflags, h->dfac, h->dfloor, h->dqueue, h->dready, ++h->step_seq, h->opt_fused_step == 1, h->dcfg, h->ld,
-                      h->pstride,
-                      h->batch, n_hi, h->pending_k);
-  } else if (h->opt_fused_step && mcap <= 8 && (long)((n_hi + 63) / 64) * h->batch > 512 &&
-             (long)(1 + (n_hi + 255) / 256) * h->batch <= 2L * h->cu_count) {
-    // the throughput shape of the panels with room left on the chip for one more workgroup per trajectory: still one
-    // launch -- workgroup 0 of a trajectory solves, the others gather their panels meanwhile (k_panels<.., SPLIT>)
-    launch_step_split_tp(h->stream, mcap, h->dP, h->dV, h->dW, dacc_in, dacc_out, mu_in, mu_out, h->dn, d_in, h->dso,
+                      h->pstride, h->batch, n_hi, h->pending_k);
+  } else if (sp.form == STEP_SPLIT_TP) {
+    launch_step_split_tp(h->stream, sp.mcap, h->dP, h->dV, h->dW, dacc_in, dacc_out, mu_in, mu_out, h->dn, d_in, h->dso,
                          h->dflags, h->dfac, h->dfloor, h->dqueue, h->dmbox, h->dready, ++h->step_seq, h->opt_fused_step == 1,
                          h->dcfg, h->ld, h->pstride, h->batch, n_hi, h->pending_k);
   } else {
     launch_solve(h->stream, h->dP, h->dV, h->dW, dacc_in, dacc_out, mu_in, mu_out, h->dn, d_in, h->dso, h->dflags,
                  h->dfac, h->dfloor, h->dqueue, h->dcfg, h->ld, h->pstride, h->batch, h->pending_k);
-    launch_panels(h->stream, mcap, h->dP, h->dV, h->dW, mu_in, mu_out, h->dn, h->dso, h->dfac, h->ld, h->pstride,
-                  h->batch, n_hi);
+    launch_panels(h->stream, sp.mcap, sp.panels_latency, h->dP, h->dV, h->dW, mu_in, mu_out, h->dn, h->dso, h->dfac, h->ld,
+                  h->pstride, h->batch, n_hi);
   }
   log_pass(h, d_in);
   HIP_TRY(h, hipGetLastError());
@@ -1116,11 +1083,7 @@ static int enqueue_pass(ekf_handle* h, const StepIn* d_in, int m_hi) {
   h->cur ^= 1;
   h->pending_k += 2 * m_hi;
   h->pending_steps += 1;
-  // cadence of the covariance pass: a fixed number of steps if asked for, otherwise as many steps as fit
-  // `rank_limit` pending ranks (default 80) -- 5 steps at m = 8, 10 at m = 4, 40 at m = 1
-  const bool due = h->opt_flush_every > 0 ? h->pending_steps >= h->opt_flush_every
-                                          : h->pending_k + std::max(2 * m_hi, 2) > h->opt_rank_limit;   // (a step like this one would not fit)
-  if (due || h->pending_k + 2 > KTOT)
+  if (pass_due_after_step(h, m_hi))
     if (int rc = flush_pending(h)) return rc;
   return EKF_OK;
 }
@@ -1173,25 +1136,7 @@ static int upload_run_plan(ekf_handle* h) {
 //     { pass_c on the second stream | solve_{c+1} } -> join.
 // `presolved` says that this cadence's solve has already been enqueued one of these ways; *next_presolved that the next
 // one's now is.
-// Covariance (MB, whole bank) from which the round-3 look-ahead runs beside a column-strip pass.  The chained order, whose
-// hand-overs are counters instead of events, does at every size: it wins at every size tried (N = 12 .. 1000, banks of 1 .. 32:
-// +25 .. +43 %).
-constexpr int LOOKAHEAD_MIN_MB = 48;
-static bool beside_the_pass(const ekf_handle* h, const PassPlan& plan) {
-  // (worth it where the pass is the column-strip kernel -- the row-slab pass fills every CU by itself -- and long enough
-  //  to pay for the gather and the two cross-stream hand-overs, ~25 us together: from ~48 MB of covariance.  N = 2000 x 1:
-  //  38.7 k -> 45.1 k steps/s, x 2: 57.6 k -> 61.9 k, x 4: 89.5 k -> 92.1 k; N = 500 x 1 and N = 20 x 1 lose 4 - 9 %;
-  //  N = 8000 x 1 on static shares, the pass on 255 workgroups: 9.35 - 9.58 k -> 9.82 - 10.2 k)
-  // ... or the row-slab pass on static shares that leaves the solves their CUs (a few long trajectories: N = 8000 x 1)
-  // ... and for banks of up to 40 trajectories: every solve workgroup has to find a CU beside the pass, and the gather grows with
-  // the bank (17 us at 32 trajectories, 71 us at 256) -- N = 500 x 32 +5 %, N = 300 x 48 -5 %, N = 200 x 128 -21 %,
-  // N = 100 x 256 -36 % with the look-ahead (bench.py --option lookahead=0; round 4)
-  const bool small_pass = plan.kernel == 0 && h->batch <= 40 &&
-                          (h->opt_chain || (double)h->batch * 8.0 * plan.e_hi * plan.e_hi >= 1.0e6 * LOOKAHEAD_MIN_MB);
-  const bool shares_pass = plan.kernel == 2 && (plan.beside || (plan.long_few && h->batch < 8 && h->opt_pass_workgroups > 0 &&
-                                                                  h->opt_pass_workgroups + h->batch <= h->cu_count));
-  return small_pass || shares_pass;
-}
+// (ekf_host_plan.h: plan_cadence_step decides all of it, beside_the_pass where a pass leaves CUs to the next solve.)
 
 // whatever is still running on the second stream is waited for by the handle's own stream
 static int join_aux(ekf_handle* h) {
@@ -1223,55 +1168,27 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
   for (int b = 0; b < h->batch; ++b) h->neff_enq[b] = rp.entries[(size_t)c * h->batch + b].neff;
   const double* mu_in = h->dmu2[h->cur];
   double* mu_out = h->dmu2[h->cur ^ 1];
+  // what follows the panel launch is decided before anything is launched (chained: it goes to the second stream)
+  CadStepPlan cp = plan_cadence_step(h, rp, c, n_hi, presolved);
+  if (cp.gather_cols && !h->dcolbuf && hipMalloc(&h->dcolbuf, sizeof(double) * (size_t)h->batch * CAD_CU * h->ld) != hipSuccess) {
+    // (an optional optimisation: where its buffer cannot be had the panel launch gathers everything itself, bit-identically)
+    (void)hipGetLastError();
+    h->dcolbuf = nullptr;
+    h->opt_col_gather = 0;
+    cp = plan_cadence_step(h, rp, c, n_hi, presolved);
+  }
+  double* colbuf = cp.gather_cols ? h->dcolbuf : nullptr;
   if (!presolved) {
     if (int rc = join_aux(h)) return rc;
-    // (the chain runs on one CU per trajectory: the rest of the chip gathers the panel launch's mirrored column entries
-    //  meanwhile -- where there is a rest, and something to gather)
-    const size_t cb_bytes = sizeof(double) * (size_t)h->batch * CAD_CU * h->ld;
-    double* colbuf = nullptr;
-    // (while its items -- trajectories x strips of 64 state indices -- are at most four rounds of the idle CUs' waves: N = 2000:
-    //  up to ~80 trajectories; x 64 +1 - 2 %, x 128 -2 % on scattered landmarks, profiles/r05_scattered_indices.txt)
-    const long col_items = (long)h->batch * ((n_hi + 63) / 64), col_waves = 8L * (h->cu_count - h->batch);
-    if (h->opt_col_gather && cb_bytes <= ((size_t)1 << 30) && col_waves > 0 && col_items <= 4 * col_waves && rp.slots_hi[c] > 0) {
-      // (an optional optimisation: where its buffer cannot be had the panel launch gathers everything itself, bit-identically)
-      if (!h->dcolbuf && hipMalloc(&h->dcolbuf, cb_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        h->dcolbuf = nullptr;
-        h->opt_col_gather = 0;
-      }
-      colbuf = h->dcolbuf;
-    }
-    const int col_wgs = h->cu_count - h->batch;
     ProfBracket pb;
     if (int rc = prof_open(h, 1, h->stream, &pb)) return rc;
     launch_solve_cad(h->stream, h->dP, mu_in, mu_out, h->ddacc2[h->dcur ^ 1], h->dn, h->d_stream, dpl, h->batch, dcad,
-                     h->dflags, h->dcfg, h->ld, h->pstride, nullptr, 0, colbuf, n_hi, col_wgs, h->chain_run, nullptr, nullptr, 0u, nullptr);
+                     h->dflags, h->dcfg, h->ld, h->pstride, nullptr, 0, colbuf, n_hi, cp.col_wgs, h->chain_run, nullptr, nullptr, 0u, nullptr);
     if (int rc = prof_close(h, &pb)) return rc;
     log_cadence(h, dpl, dcad);
-    h->colbuf_live = colbuf != nullptr;
   }
+  const bool due = cp.due, beside = cp.beside, chain_next = cp.chain_next, wv = cp.w_from_v;
   const int ranks = 2 * rp.slots_hi[c], nrp = (ranks + 3) & ~3;   // every trajectory writes the busiest one's ranks (zeros beyond its own)
-  // what follows the panel launch is decided before it is launched (chained: it goes to the second stream)
-  const bool more = c + 1 < rp.ncad;
-  const int pend_after = h->pending_k + ranks, steps_after = h->pending_steps + rp.steps_hi[c];
-  const bool due = pend_after > 0 && (more || pend_after + 2 > std::min(KTOT, h->opt_rank_limit) ||
-                                      (h->opt_flush_every > 0 && steps_after >= h->opt_flush_every));
-  bool beside = false;
-  if (due && more && h->opt_lookahead) {
-    const int pk = h->pending_k;
-    h->pending_k = pend_after;                         // (plan_pass reads the handle)
-    beside = beside_the_pass(h, plan_pass(h));
-    h->pending_k = pk;
-  }
-  const bool chain_next = beside && h->chain_run;
-  // ("w_from_v") the pass follows this panel launch at once, nothing else is pending, both take the forms that know how
-  bool wv = false;
-  if (h->opt_w_from_v && due && !beside && h->pending_k == 0 && ranks > 0 &&      // (... and the panel launch takes a replay shape)
-      (h->opt_panel_shape >= 2 || (h->opt_panel_shape == 0 && !panels_cad_latency_regime(h->batch, n_hi)))) {
-    h->pending_k = pend_after;
-    wv = plan_pass(h).kernel == 2;
-    h->pending_k = 0;
-  }
   hipStream_t pst = h->stream;                         // the panel launch's stream
   unsigned* psync = nullptr;
   unsigned tail_target = 0u;
@@ -1322,12 +1239,10 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     ProfBracket pb;
     if (int rc2 = prof_open(h, 3, pst, &pb)) return rc2;
     launch_panels_cad(pst, h->dP, h->dV, h->dW, mu_in, mu_out, h->dn, dcad, h->dso, h->dqueue, h->ld,
-                      h->pstride, h->batch, n_hi, nrp, h->colbuf_live ? h->dcolbuf : nullptr, prow_out, psync, tail_target, h->dflags,
-                      chain_next && h->opt_panel_tform && !h->colbuf_live && panels_cad_latency_regime(h->batch, n_hi),
-                      chain_next ? h->sigma : 0u, h->opt_panel_shape, wv);
+                      h->pstride, h->batch, n_hi, nrp, colbuf, prow_out, psync, tail_target, h->dflags, cp.panel,
+                      chain_next ? h->sigma : 0u, wv);
     if (int rc2 = prof_close(h, &pb)) return rc2;
   }
-  h->colbuf_live = false;
   if (hipGetLastError() != hipSuccess && rc == EKF_OK) rc = fail(h, EKF_ERR_HIP, "fused cadence: launch of the panel kernel failed");
   h->dcur ^= 1;
   h->cur ^= 1;
@@ -1388,7 +1303,6 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     if (int rc2 = prof_close(h, &pb)) return rc2;
   }
   log_cadence(h, dpl2, h->dcad2[h->cpar]);
-  h->colbuf_live = false;                              // (beside the pass P_base is in motion: that cadence's panel launch gathers itself)
   // From here on the next cadence's solve has overwritten the pose mean and the pending-noise buffer: a failure
   // below cannot be undone.  Whatever happens the two streams are joined again, and a failure marks every trajectory
   // undefined (EKF_ERR_STATE from then on, until it is uploaded again).
@@ -1815,21 +1729,9 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
       const int piece_end = std::min(first + count, k + 8192);
       plan_cadences(h, k, piece_end, h->run_plan);
       if (int rc = upload_run_plan(h)) return rc;
-      // chained solves: decided per piece -- every solve of it then records its cadence's transform; whether a cadence is
-      // chained to the next is decided where the pass between them is planned (enqueue_cadence).  (Banks of up to 40, as the
-      // look-ahead: every solve and chain workgroup has to find a CU beside the pass.)
-      h->chain_run = h->opt_chain && h->opt_lookahead && h->run_plan.ncad >= 2 && h->batch <= 40;
-      if (h->chain_run) {
-        // ... and only where a pass of this bank can leave CUs to a solve beside it at all (with every state index active and a
-        // full cadence pending: the headline's 32 x N = 2000 never does -- its solves stay the plain instantiation)
-        const std::vector<int> enq = h->neff_enq;
-        const int pk = h->pending_k;
-        h->neff_enq = h->n;
-        h->pending_k = KTOT;
-        h->chain_run = beside_the_pass(h, plan_pass(h));
-        h->neff_enq = enq;
-        h->pending_k = pk;
-      }
+      // chained solves: decided per piece; whether a cadence is chained to the next is decided where the pass between them
+      // is planned (plan_cadence_step)
+      h->chain_run = plan_chain_run(h, h->run_plan.ncad);
       if (h->chain_run) {
         const int n_hi = *std::max_element(h->n.begin(), h->n.end());
         for (int i = 0; i < 2; ++i)

@@ -32,10 +32,10 @@
 #include <utility>
 
 #include "ekf_devfn.h"
+#include "ekf_host_plan.h"
 
 namespace ekf {
 
-constexpr int CAD_KS_WAVES = 512;       // panel launches of up to this many waves of state indices take the row-split form
 typedef double v2d_u __attribute__((ext_vector_type(2), aligned(8)));   // two adjacent doubles, 8-byte aligned: one 16-byte load
 constexpr int CAD_CS = 88;              // LDS row stride of the block (doubles): 83 columns, rows 16-byte aligned
 constexpr int CAD_ROWS = 84;
@@ -1416,7 +1416,6 @@ constexpr int CH_NC = 80;               // columns: the landmark positions of th
 constexpr int CH_S = 81;                // LDS row stride of A (odd: rows and columns both spread over the banks)
 constexpr int CH_R = 96;                // rows of the padded operands (6 MFMA tiles: 80 rank rows, the 3 pose rows)
 constexpr int CH_CS = 82;               // LDS row stride of B / the coefficient matrix (even: a 2 x 2 block's row is one 16-byte read)
-constexpr int CH_GW = 12;               // gather workgroups per trajectory at most (12: a row of X and of P_0(C', C') per wave)
 
 // ---- pieces shared by k_chain_cad and k_panels_cad_tf: the cadence's records as the triangular system (I + C) E = A X ----
 struct ChainRec {                       // (LDS) the small parts of the records, by landmark q = slot s0k + q
@@ -2168,26 +2167,18 @@ void launch_solve_cad(hipStream_t st, const double* P, const double* mu_in, doub
                       const int* nact, const StepIn* in, const CadPlan* plan, int batch, CadOut* out, unsigned* flags,
                       const DeviceConfig& cfg, int ld, long pstride, const double* gbuf, int gparts, double* colbuf, int n_hi,
                       int col_wgs, bool chain, const double* gmu, unsigned* sync, unsigned start_sigma, const CadPre* pre) {
-  const bool gate = cfg.gate_rej != nullptr;
   const dim3 grid(batch + (colbuf ? col_wgs : 0)), block(64 * CAD_NW);
-  if (chain && gate)
-    hipLaunchKernelGGL((k_solve_cad<true, true>), grid, block, 0, st, P, mu_in, mu_out, dacc_out, nact, in, plan, batch, out, flags,
-                       cfg, ld, pstride, gbuf, gparts, colbuf, col_wgs, n_hi, gmu, sync, start_sigma, pre);
-  else if (chain)
-    hipLaunchKernelGGL((k_solve_cad<true, false>), grid, block, 0, st, P, mu_in, mu_out, dacc_out, nact, in, plan, batch, out, flags,
-                       cfg, ld, pstride, gbuf, gparts, colbuf, col_wgs, n_hi, gmu, sync, start_sigma, pre);
-  else if (gate)
-    hipLaunchKernelGGL((k_solve_cad<false, true>), grid, block, 0, st, P, mu_in, mu_out, dacc_out, nact, in, plan, batch, out, flags,
-                       cfg, ld, pstride, gbuf, gparts, colbuf, col_wgs, n_hi, nullptr, nullptr, 0u, nullptr);
-  else
-    hipLaunchKernelGGL((k_solve_cad<false, false>), grid, block, 0, st, P, mu_in, mu_out, dacc_out, nact, in, plan, batch, out, flags,
-                       cfg, ld, pstride, gbuf, gparts, colbuf, col_wgs, n_hi, nullptr, nullptr, 0u, nullptr);
+  with_flag(chain, [&](auto C) {
+    with_flag(cfg.gate_rej != nullptr, [&](auto G) {
+      hipLaunchKernelGGL((k_solve_cad<C.value, G.value>), grid, block, 0, st, P, mu_in, mu_out, dacc_out, nact, in, plan, batch, out,
+                         flags, cfg, ld, pstride, gbuf, gparts, colbuf, col_wgs, n_hi, C.value ? gmu : nullptr, C.value ? sync : nullptr,
+                         C.value ? start_sigma : 0u, C.value ? pre : nullptr);
+    });
+  });
 }
 
-// (chained runs) the next cadence's block and mean from the records `prev` of the cadence whose solve has just run
-// gather workgroups per trajectory: each counts itself off on the launch's gather counter.  (Every workgroup of the launch
-// reserves the chain workgroup's LDS, a CU apiece: as many as leave the chip half free for what runs beside the launch.)
-int chain_gather_workgroups(int batch, int cus) { return std::max(1, std::min(CH_GW, (cus / 2 - batch) / std::max(batch, 1))); }
+// (chained runs) the next cadence's block and mean from the records `prev` of the cadence whose solve has just run; `gw` gather
+// workgroups per trajectory (ekf_host_plan.h: chain_gather_workgroups)
 int chain_sync_words() { return SYNC_WORDS; }
 void launch_chain_cad(hipStream_t st, const double* P, const double* prow3, const double* mu_land, const double* mu_pose,
                       const CadOut* prev, const StepIn* in, const CadPlan* plan, int batch, const DeviceConfig& cfg, int ld,
@@ -2206,33 +2197,24 @@ void launch_mark(hipStream_t st, unsigned* sync, unsigned sigma) { hipLaunchKern
 void launch_gate(hipStream_t st, unsigned* sync, unsigned sigma, unsigned* flags, int batch) {
   hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, st, sync, sigma, flags, batch);
 }
-bool panels_cad_latency_regime(int batch, int n_hi) { return (long)((n_hi + 63) / 64) * batch <= CAD_KS_WAVES; }
 
 void launch_snap_pose(hipStream_t st, const double* P, const int* nact, int ld, long pstride, int batch, int n_hi, double* prow3) {
   hipLaunchKernelGGL(k_snap_pose, dim3((n_hi + 255) / 256, batch), dim3(256), 0, st, P, nact, ld, pstride, prow3);
 }
 
-// `nrp`: the ranks the bank's busiest trajectory appends, padded to a whole k-tile (every trajectory writes that many)
+// `nrp`: the ranks the bank's busiest trajectory appends, padded to a whole k-tile (every trajectory writes that many);
+// `form`: ekf_host_plan.h's PanelForm (plan_cadence_step); `skipw` (w_from_v): the replay forms write V only
 void launch_panels_cad(hipStream_t st, double* P, double* V, double* W, const double* mu_in, double* mu_out,
                        const int* nact, const CadOut* co, SolveOut* so, unsigned* queue, int ld, long pstride, int batch,
                        int n_hi, int nrp, const double* colbuf, double* prow3, unsigned* sync, unsigned tail_target,
-                       unsigned* flags, bool tform, unsigned start_sigma, int shape, bool skipw) {
-  // (`skipw`: only the replay shapes 2 and 3 honour it -- the caller asks for it only where the launch takes one of them)
-  // (chained cadences in the latency regime: the triangular-solve form, one 8-wave workgroup per 64 state indices)
-  if (tform) {
+                       unsigned* flags, int form, unsigned start_sigma, bool skipw) {
+  if (form == PANEL_TF)
     hipLaunchKernelGGL(k_panels_cad_tf, dim3((n_hi + 63) / 64, batch), dim3(64 * CAD_NW), 0, st, P, V, W, mu_in, mu_out, nact, co, so,
                        queue, ld, pstride, nrp, prow3, sync, tail_target, flags, start_sigma);
-    return;
-  }
-  // few state indices (the latency regime): four waves split the rows of the panel of 64 state indices (k_panels_cad_ks);
-  // up to one wave per SIMD: one wave per workgroup
-  // (`shape`: 0 = by the size of the launch; 1 .. 3 force a shape -- diagnostics, option "panel_shape")
-  const long waves = (long)((n_hi + 63) / 64) * batch;
-  if (shape == 0) shape = waves <= CAD_KS_WAVES ? 1 : (waves <= 1024 ? 2 : 3);
-  if (shape == 1)
+  else if (form == PANEL_KS)
     hipLaunchKernelGGL(k_panels_cad_ks, dim3((n_hi + 63) / 64, batch), dim3(256), 0, st, P, V, W, mu_in, mu_out,
                        nact, co, so, queue, ld, pstride, nrp, colbuf, prow3, sync, tail_target, flags, start_sigma);
-  else if (shape == 2)
+  else if (form == PANEL_ONE)
     hipLaunchKernelGGL((k_panels_cad<1>), dim3((n_hi + 63) / 64, batch), dim3(64), 0, st, P, V, W, mu_in, mu_out,
                        nact, co, so, queue, ld, pstride, nrp, colbuf, prow3, sync, tail_target, flags, start_sigma, skipw ? 1 : 0);
   else

@@ -1,7 +1,27 @@
 // Device-side helpers shared by the kernel translation units (ekf_kernels.hip, ekf_cadence.hip): LDS hand-off
 // macros, the measurement model of src/replay_no_ros.py:443-469, buffer-instruction accessors.  gfx950 only.
 #pragma once
+#include <type_traits>
+
 #include "ekf_device.h"
+
+// (launchers) a run-time choice as a template argument: f(std::integral_constant<...>{}), the argument's ::value being the flag /
+// the slot count (1, 2, 4, 8, 16: ekf_host_plan.h cap_for) -- one launch statement instead of a ladder per instantiation
+template <typename F>
+inline void with_flag(bool flag, F&& f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <typename F>
+inline void with_mcap(int mcap, F&& f) {
+  switch (mcap) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    default: f(std::integral_constant<int, 16>{}); break;
+  }
+}
 
 // LDS hand-off between lanes of ONE wave (the other waves of the workgroup have exited): LDS
 // operations of a wave execute in issue order, so only the compiler must be kept from reordering.

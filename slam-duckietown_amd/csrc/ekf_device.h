@@ -22,6 +22,12 @@ constexpr int NKT = KTOT / 4;           // the same in MFMA k-tiles (v_mfma_f64_
 // to a whole k-tile (the step that is last so far zero-fills the pad ranks)
 __host__ __device__ constexpr int ranks_for(int mcap) { return 2 * mcap; }
 
+// ---- size limits of the small-state path (ekf_small.hip: the kernel's LDS, ekf_host_plan.h: small_state_limit) ----
+constexpr int SMALL_N_MAX = 79;         // 3 + 2 * 38 (<= 5 column tiles of 16; 50 KB of LDS): beyond, the general kernels are faster
+                                        // for ONE trajectory (latency) ...
+constexpr int SMALL_N_MAX_BANK = 131;   // ... but not for a bank that fills the chip (3 + 2 * 64; 9 column tiles, 137 KB of LDS: one
+constexpr int SMALL_BANK_MIN = 128;     // workgroup per CU): N = 64 x 256 10.4 M against 7.9 M steps/s, x 1024 against 5.4 M
+
 // ---- layout of one trajectory's P_base (round 4) ----
 // Row-major with row stride ld while ld <= 4096 (ld is then a power of two).  Beyond that the covariance is cut into
 // COLUMN PANELS of PPW = 4096 doubles: panel p holds the columns [4096 p, 4096 (p + 1)) of every row, row-major with a row

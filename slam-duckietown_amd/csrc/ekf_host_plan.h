@@ -1,7 +1,8 @@
 // Host-side planning logic of the EKF-SLAM core: everything that decides WHAT is launched -- the covariance pass's kernel and
-// launch shape, its work queues and static shares, how many steps of an uploaded stream form a fused cadence, the step
-// records and their active bound, the validation of observation lists -- as plain C++ on plain data (no HIP type, no device
-// call).  ekf_api.hip's handle derives from HostPlan and calls these; the same header compiles with plain g++
+// launch shape, its work queues and static shares, the form of a step's update, how many steps of an uploaded stream form a
+// fused cadence and what follows each one, the small-state kernel, the step records and their active bound, the validation of
+// observation lists -- as plain C++ on plain data (no HIP type, no device call).  ekf_api.hip's handle derives from HostPlan
+// and calls these, the launchers only map their answers to kernel instantiations; the same header compiles with plain g++
 // (-DEKF_HOST_ONLY), and tests/host_plan_check.cpp runs it under -fsanitize=address,undefined: enumerations of the queue /
 // share arithmetic plus randomised invariants of the planning functions (tests/test_cpu_host.py builds and runs it).
 #pragma once
@@ -39,6 +40,14 @@ struct HostPlan {
   int opt_fused_step = 1;         // 1 = one launch per step where the launch is small (k_step_split), 0 = always two
   int opt_fused_cadence = 1;      // 1 = uploaded streams run whole cadences as one solve + one panel launch (ekf_cadence.hip)
   int opt_lookahead = 1;
+  int opt_chain = 1;              // 1 = chained solves where a pass can leave CUs to a solve beside it (plan_chain_run)
+  // 1 = where a fused cadence's covariance pass follows its panel launch at once, in the row-slab form, the panel launch writes V
+  // only and the pass forms its W fragments from V and the records' S^-1 (half of the panel launch's stores); bit-identical
+  int opt_w_from_v = 1;
+  int opt_panel_shape = 0;        // diagnostics: 0 = the panel launch's shape by its size; 1 k_panels_cad_ks, 2 k_panels_cad<1>, 3 k_panels_cad<4> whatever the size
+  int opt_panel_tform = 1;        // 1 = a chained cadence's panel launch in the latency regime takes the triangular-solve form (k_panels_cad_tf)
+  int opt_col_gather = 1;         // 1 = the solve gathers the panel launch's mirrored column entries beside it, 0 = the panel launch gathers everything itself
+  bool chain_run = false;         // the run in flight records the transforms (every solve is k_solve_cad<true>)
   int opt_small_state = 1;        // 1 = small filters (n_max <= 79: up to 38 landmarks) run in ONE workgroup, P in LDS (ekf_small.hip)
   int opt_rows_per_block = 0;     // 0 = auto (flush kernel: rows per workgroup, multiple of 16)
   int opt_pass_chunk = 0;         // 0 = auto (k_flush_rs: strips per unit)
@@ -256,19 +265,22 @@ inline bool streaming_pass(const HostPlan* h, int n_hi) {
 }
 
 // What the next covariance pass will launch (decided from the handle's state alone, so that the caller can ask before
-// it launches).
+// it launches).  `pending_k` ranks pending; `all_active`: as if every state index were active (the question "could a pass of
+// this bank ever ...", asked before a run).
 struct PassPlan {
   int n_hi, e_hi, nkt, kernel, rs_workgroups;
   bool streaming, long_few, beside;                    // beside: the row-slab pass leaves CUs free for a solve beside it
+  int rows_per_block;                                  // (kernel 0) rows per workgroup of k_flush
+  int rs_mode, rs_nch, rs_cs, rs_grid;                 // (kernel 2, on its work queues) hand-out (rs_queue_count) and workgroups launched
 };
-inline PassPlan plan_pass(const HostPlan* h) {
-  PassPlan p;
+inline PassPlan plan_pass(const HostPlan* h, int pending_k, bool all_active = false) {
+  PassPlan p{};
   p.n_hi = h->sizes_dirty ? h->n_max : *std::max_element(h->n.begin(), h->n.end());
   p.e_hi = 3;                                          // the grid covers the largest active bound of the batch
-  for (int b = 0; b < h->batch; ++b) p.e_hi = std::max(p.e_hi, std::min(h->n[b], h->neff_enq[b]));
+  for (int b = 0; b < h->batch; ++b) p.e_hi = std::max(p.e_hi, std::min(h->n[b], all_active ? h->n[b] : h->neff_enq[b]));
   if (h->sizes_dirty) p.e_hi = h->n_max;
   p.streaming = streaming_pass(h, p.n_hi);
-  p.nkt = (h->pending_k + 3) / 4;
+  p.nkt = (pending_k + 3) / 4;
   p.kernel = h->opt_pass_kernel;
   p.rs_workgroups = h->opt_pass_workgroups > 0 ? std::min(h->opt_pass_workgroups, h->cu_count) : h->cu_count;
   // A few LONG trajectories (N = 8000 x 1: 126 slabs of up to 251 strips for 256 CUs): the row-slab pass with one equal
@@ -298,7 +310,98 @@ inline PassPlan plan_pass(const HostPlan* h) {
   p.beside = p.kernel == 2 && p.long_few && h->batch < 8 && h->opt_lookahead && h->opt_pass_workgroups == 0 &&
              h->cu_count > 8 * h->batch;
   if (p.beside) p.rs_workgroups = h->cu_count - h->batch;
+  if (p.kernel == 0) p.rows_per_block = flush_rows_per_block(h, p.streaming, p.e_hi);
+  if (p.kernel != 2) return p;
+  // Units of the work queues (the modes at rs_queue_count; equal static shares, where the pass takes them, replace them).
+  // With an even number of trajectories per queue whole slabs taken trajectory by trajectory balance perfectly (16
+  // trajectories: 366 us against 430 us in chunks of 22 strips); the last trajectory of an odd number finds no partner and
+  // its slabs -- only they -- are cut in two (N=2000: 8 trajectories 203 us against 256 us with the former rule and 328 us
+  // whole; 24: 557 us against 668 us); a batch that is no multiple of 8 would leave the queues with unequal work, so its
+  // last trajectories are dealt over all queues slab by slab -- profiles/r02_chunk_sweep.txt, profiles/r02_batch_sweep.txt.
+  // Below 8 trajectories (the row-slab kernel then only runs for long ones, N=8000) every slab is cut so that there are
+  // about three units per CU.
+  const int batch = h->batch, nrb = (p.e_hi + RS_ROWS - 1) / RS_ROWS, s_max = (p.e_hi + 63) / 64;   // strips of the longest slab
+  int cs = s_max, nch = 1, mode = 0;
+  if (h->opt_pass_chunk > 0) {                         // ("pass_chunk" option: every slab of every trajectory)
+    cs = std::min(std::max(h->opt_pass_chunk, 1), s_max);
+    nch = (s_max + cs - 1) / cs;
+  } else if (batch >= 8) {
+    if (batch % 8 == 0) {                              // pairs; an unpaired trajectory (8: each queue's only one) cut in two
+      mode = 1;
+      if (s_max >= 4) {
+        cs = (s_max + 1) / 2;
+        nch = 2;
+      }
+    } else if (batch <= 12 && s_max >= 8) {             // (N=2000: 9 trajectories 253 us against 329 us whole, 10: 284 / 333,
+                                                       //  12: 327 / 342; 14: 360 / 344 -- from 13 on whole slabs)
+      mode = 3;                                        // equal work per queue, half slabs, longest first
+      nch = (s_max + 3) / 4;                           // h: half a chunk; chunks of cs = 2 h strips
+      cs = 2 * nch;
+    } else {
+      mode = 2;                                        // equal work per queue, longest slabs first
+    }
+  } else {                                             // a few long trajectories (N=8000): about three units per CU
+    long steps = 0;
+    for (int rb = 0; rb < nrb; ++rb) steps += std::max(1, s_max - 2 * rb);
+    steps *= batch;
+    if ((long)nrb * batch < 3L * p.rs_workgroups) {
+      cs = (int)std::max<long>(2, (steps + 3L * p.rs_workgroups - 1) / (3L * p.rs_workgroups));
+      nch = (s_max + cs - 1) / cs;
+    }
+  }
+  const long units = (long)nrb * (mode == 0 ? nch : mode == 3 ? 2 : 1) * batch;   // (modes 1, 2: at least; only the grid size depends on it)
+  p.rs_mode = mode;
+  p.rs_nch = nch;
+  p.rs_cs = cs;
+  p.rs_grid = (int)std::min<long>(p.rs_workgroups, units);
   return p;
+}
+inline PassPlan plan_pass(const HostPlan* h) { return plan_pass(h, h->pending_k); }
+
+// ---- the per-step update (ekf_api.hip: enqueue_pass) ----
+// Whether a step of this shape is run as one launch (the latency regime, see k_step_split): while every panel
+// workgroup has a CU to itself.  N=2000: 1 trajectory 33.7 k steps/s against 28.0 k with two launches, 4 trajectories
+// 79.2 k against 73.6 k, but 8 trajectories (504 panel workgroups) 85.8 k against 98.8 k.
+inline bool step_is_split(int batch, int n_hi, int cus) { return (long)((n_hi + 63) / 64) * batch <= (long)cus; }
+enum StepForm {
+  STEP_PREDICT,        // prediction only, nothing pending: k_solve + k_predict_rc on rows / columns 0, 1 of P_base, O(n)
+  STEP_SPLIT,          // one launch, the panels gathered beside the solve (k_step_split: few workgroups, the latency regime)
+  STEP_SPLIT_TP,       // one launch in the throughput shape of the panels: workgroup 0 of a trajectory solves (k_panels_split)
+  STEP_TWO,            // k_solve, then k_panels
+};
+struct StepPlan {
+  int form, mcap;
+  bool panels_latency;     // (STEP_TWO) k_panels<M, 4, true>: four waves split the pending ranks of 64 indices; else <M, 4, false>
+  bool flush_before;       // the pending ranks are applied first: this step's would not fit behind them
+};
+inline StepPlan plan_step(const HostPlan* h, int m_hi, int n_hi) {
+  StepPlan s{};
+  s.mcap = cap_for(m_hi);
+  s.panels_latency = (long)((n_hi + 63) / 64) * h->batch <= 512;
+  if (m_hi == 0 && h->pending_k == 0) {
+    s.form = STEP_PREDICT;
+    return s;
+  }
+  // The kernels WRITE the rank slots of `mcap` landmarks behind the pending ones (zeros where a trajectory observes fewer) plus
+  // the k-tile pad; the step is CHARGED the ranks of the busiest trajectory only (round 5: 2 per landmark, as the packed
+  // cadences do) -- the next step starts right behind them and overwrites the zeros.  m = 5: 7 steps per pass (until round 4:
+  // 5, the count rounded up to 8 landmarks), m = 12: 3 (2).
+  s.flush_before = ((h->pending_k + ranks_for(s.mcap) + 3) & ~3) > KTOT;
+  if (h->opt_fused_step && step_is_split(h->batch, n_hi, h->cu_count))
+    s.form = STEP_SPLIT;
+  else if (h->opt_fused_step && s.mcap <= 8 && !s.panels_latency && (long)(1 + (n_hi + 255) / 256) * h->batch <= 2L * h->cu_count)
+    s.form = STEP_SPLIT_TP;   // (room left on the chip for one more workgroup per trajectory; 16 landmarks: registers for one wave per SIMD only)
+  else
+    s.form = STEP_TWO;
+  return s;
+}
+// Behind a step that appended 2 m_hi ranks (pending_k / pending_steps count it): the cadence of the covariance pass -- a fixed
+// number of steps if asked for, otherwise as many steps as fit `rank_limit` pending ranks (default 80): 5 steps at m = 8, 10 at
+// m = 4, 40 at m = 1.
+inline bool pass_due_after_step(const HostPlan* h, int m_hi) {
+  const bool due = h->opt_flush_every > 0 ? h->pending_steps >= h->opt_flush_every
+                                          : h->pending_k + std::max(2 * m_hi, 2) > h->opt_rank_limit;   // (a step like this one would not fit)
+  return due || h->pending_k + 2 > KTOT;
 }
 
 // Which workgroup gets which static share.  build_pass_shares cuts the strips slab by slab, so consecutive shares are
@@ -405,6 +508,105 @@ inline void plan_cadences(const HostPlan* h, int k, int end, RunPlan& rp) {
     rp.steps_sum.push_back(steps_sum);
     rp.ncad += 1;
   }
+}
+
+// ---- a fused cadence and what follows it (ekf_api.hip: enqueue_cadence, ekf_stream_run) ----
+// Small launches, where the covariance pass leaves CUs free, run the next cadence's solve beside the pass (look-ahead) or chain
+// the solves (see enqueue_cadence).  Worth it where the pass is the column-strip kernel -- the row-slab pass fills every CU by
+// itself -- and long enough to pay for the gather and the two cross-stream hand-overs, ~25 us together: from ~48 MB of
+// covariance (LOOKAHEAD_MIN_MB; the chained order, whose hand-overs are counters instead of events, at every size: it wins at
+// every size tried, N = 12 .. 1000, banks of 1 .. 32: +25 .. +43 %).  N = 2000 x 1: 38.7 k -> 45.1 k steps/s, x 2: 57.6 k ->
+// 61.9 k, x 4: 89.5 k -> 92.1 k; N = 500 x 1 and N = 20 x 1 lose 4 - 9 %; N = 8000 x 1 on static shares, the pass on 255
+// workgroups: 9.35 - 9.58 k -> 9.82 - 10.2 k
+// ... or the row-slab pass on static shares that leaves the solves their CUs (a few long trajectories: N = 8000 x 1)
+// ... and for banks of up to 40 trajectories: every solve workgroup has to find a CU beside the pass, and the gather grows with
+// the bank (17 us at 32 trajectories, 71 us at 256) -- N = 500 x 32 +5 %, N = 300 x 48 -5 %, N = 200 x 128 -21 %,
+// N = 100 x 256 -36 % with the look-ahead (bench.py --option lookahead=0; round 4)
+constexpr int LOOKAHEAD_MIN_MB = 48;
+inline bool beside_the_pass(const HostPlan* h, const PassPlan& plan) {
+  const bool small_pass = plan.kernel == 0 && h->batch <= 40 &&
+                          (h->opt_chain || (double)h->batch * 8.0 * plan.e_hi * plan.e_hi >= 1.0e6 * LOOKAHEAD_MIN_MB);
+  const bool shares_pass = plan.kernel == 2 && (plan.beside || (plan.long_few && h->batch < 8 && h->opt_pass_workgroups > 0 &&
+                                                                  h->opt_pass_workgroups + h->batch <= h->cu_count));
+  return small_pass || shares_pass;
+}
+// Chained solves, decided per planned piece of a run (every solve of it then records its cadence's transform): banks of up to
+// 40, as the look-ahead, and only where a pass of this bank can leave CUs to a solve beside it at all -- with every state index
+// active and a full cadence pending (the headline's 32 x N = 2000 never does: its solves stay the plain instantiation).
+inline bool plan_chain_run(const HostPlan* h, int ncad) {
+  return h->opt_chain && h->opt_lookahead && ncad >= 2 && h->batch <= 40 && beside_the_pass(h, plan_pass(h, KTOT, true));
+}
+// Gather workgroups per trajectory of a chain launch: each counts itself off on the launch's gather counter.  (Every workgroup
+// of the launch reserves the chain workgroup's LDS, a CU apiece: as many as leave the chip half free for what runs beside it.)
+constexpr int CH_GW = 12;               // at most (12: a row of X and of P_0(C', C') per wave)
+inline int chain_gather_workgroups(int batch, int cus) { return std::max(1, std::min(CH_GW, (cus / 2 - batch) / std::max(batch, 1))); }
+// Panel launches of up to CAD_KS_WAVES waves of state indices (the latency regime) take the row-split form.
+constexpr int CAD_KS_WAVES = 512;
+inline bool panels_cad_latency_regime(int batch, int n_hi) { return (long)((n_hi + 63) / 64) * batch <= CAD_KS_WAVES; }
+enum PanelForm {
+  PANEL_TF,            // k_panels_cad_tf: chained cadences in the latency regime, the triangular-solve form
+  PANEL_KS,            // k_panels_cad_ks: four waves split the rows of the panel of 64 state indices (the latency regime)
+  PANEL_ONE,           // k_panels_cad<1>: one wave per workgroup (up to one wave per SIMD)
+  PANEL_FOUR,          // k_panels_cad<4>
+};
+struct CadStepPlan {
+  bool gather_cols;    // the solve's col_wgs extra workgroups gather the panel launch's mirrored column entries
+  int col_wgs;
+  bool due;            // the covariance pass follows the panel launch
+  bool beside;         // ... beside the next cadence's solve (look-ahead)
+  bool chain_next;     // ... and the next cadence's solve is chained to this one's
+  bool w_from_v;       // the panel launch writes V only, the pass forms W from V
+  int panel;           // PanelForm
+};
+// Cadence c of the run plan `rp` (neff_enq holding its active bounds); `presolved`: its solve has been enqueued already (chained
+// / look-ahead).  The handle's pending ranks and steps are what the cadences before it left.
+inline CadStepPlan plan_cadence_step(const HostPlan* h, const RunPlan& rp, int c, int n_hi, bool presolved) {
+  CadStepPlan p{};
+  // (the chain runs on one CU per trajectory: the rest of the chip gathers the panel launch's mirrored column entries meanwhile
+  //  -- where there is a rest, and something to gather -- while its items, trajectories x strips of 64 state indices, are at
+  //  most four rounds of the idle CUs' waves: N = 2000: up to ~80 trajectories; x 64 +1 - 2 %, x 128 -2 % on scattered
+  //  landmarks, profiles/r05_scattered_indices.txt.  A solve launched beside a pass cannot: P_base is in motion.)
+  const size_t cb_bytes = sizeof(double) * (size_t)h->batch * CAD_CU * h->ld;
+  const long col_items = (long)h->batch * ((n_hi + 63) / 64), col_waves = 8L * (h->cu_count - h->batch);
+  p.col_wgs = h->cu_count - h->batch;
+  p.gather_cols = !presolved && h->opt_col_gather && cb_bytes <= ((size_t)1 << 30) && col_waves > 0 && col_items <= 4 * col_waves &&
+                  rp.slots_hi[c] > 0;
+  // the pass: behind every cadence but the run's last, and behind that one when its slots are used up
+  const int ranks = 2 * rp.slots_hi[c];
+  const bool more = c + 1 < rp.ncad;
+  const int pend_after = h->pending_k + ranks, steps_after = h->pending_steps + rp.steps_hi[c];
+  p.due = pend_after > 0 && (more || pend_after + 2 > std::min(KTOT, h->opt_rank_limit) ||
+                             (h->opt_flush_every > 0 && steps_after >= h->opt_flush_every));
+  p.beside = p.due && more && h->opt_lookahead && beside_the_pass(h, plan_pass(h, pend_after));
+  p.chain_next = p.beside && h->chain_run;
+  const bool latency = panels_cad_latency_regime(h->batch, n_hi);
+  const long waves = (long)((n_hi + 63) / 64) * h->batch;
+  if (p.chain_next && h->opt_panel_tform && !p.gather_cols && latency) p.panel = PANEL_TF;
+  else if (h->opt_panel_shape > 0) p.panel = PANEL_KS + h->opt_panel_shape - 1;   // ("panel_shape": forced, diagnostics)
+  else p.panel = latency ? PANEL_KS : (waves <= 1024 ? PANEL_ONE : PANEL_FOUR);
+  // ("w_from_v") the pass follows this panel launch at once, nothing else is pending, both take the forms that know how
+  p.w_from_v = h->opt_w_from_v && p.due && !p.beside && h->pending_k == 0 && ranks > 0 &&
+               (p.panel == PANEL_ONE || p.panel == PANEL_FOUR) && plan_pass(h, pend_after).kernel == 2;
+  return p;
+}
+
+// ---- the small-state path (ekf_small.hip): a filter bank whose covariances fit the LDS of a CU runs whole streams of steps per
+// trajectory inside one workgroup, P resident in LDS; nothing is ever pending on it ----
+inline int small_state_limit(int batch) { return batch >= SMALL_BANK_MIN ? SMALL_N_MAX_BANK : SMALL_N_MAX; }
+inline bool small_path(const HostPlan* h) {
+  return h->opt_small_state && h->n_max <= small_state_limit(h->batch) && h->pending_k == 0;
+}
+enum SmallForm {       // the kernel (ekf_small.hip) and its column tiles of 16
+  SMALL_OCC_3,         // k_small_stream_occ<256, 3>: many small filters (more than three per CU), four waves per SIMD
+  SMALL_3,             // k_small_stream<256, 3>
+  SMALL_5,             // k_small_stream<256, 5>
+  SMALL_TWO_7,         // k_small_stream_two<256, 7>: two workgroups per CU where LDS allows
+  SMALL_9,             // k_small_stream<256, 9>
+};
+inline int plan_small(const HostPlan* h, int n_hi) {
+  const int n = std::min(n_hi, SMALL_N_MAX_BANK);
+  if (h->batch > 3 * h->cu_count && n <= 48) return SMALL_OCC_3;
+  return n <= 48 ? SMALL_3 : n <= 80 ? SMALL_5 : n <= 112 ? SMALL_TWO_7 : SMALL_9;
 }
 
 // Validate one trajectory's whole observation list (all device passes of it) before any handle state changes:

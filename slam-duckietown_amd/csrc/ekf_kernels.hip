@@ -2430,29 +2430,23 @@ void launch_solve(hipStream_t st, const double* P, const double* V, const double
                        out, flags, fac, neff_floor, queue, cfg, ld, pstride, kbase);
 }
 
+// `latency` (ekf_host_plan.h: plan_step): four waves split the pending ranks of 64 indices; else the throughput form, a
+// workgroup is four independent waves of 64 state indices sharing one staging
 template <int MCAP>
-static void launch_panels_t(hipStream_t st, double* P, double* V, double* W, const double* mu_in,
+static void launch_panels_t(hipStream_t st, bool latency, double* P, double* V, double* W, const double* mu_in,
                             double* mu_out, const int* nact, const SolveOut* so, const double* fac, int ld,
                             long pstride, int batch, int n_hi) {
-  // throughput form: a workgroup is four independent waves of 64 state indices sharing one staging
-  const long waves = (long)((n_hi + 63) / 64) * batch;
-  if (waves <= 512)                                     // latency-bound: four waves split the pending ranks of 64 indices
+  if (latency)
     hipLaunchKernelGGL((k_panels<MCAP, 4, true>), dim3((n_hi + 63) / 64, batch), dim3(256), 0, st, P, V, W, mu_in,
                        mu_out, nact, so, fac, ld, pstride);
   else
     hipLaunchKernelGGL((k_panels<MCAP, 4, false>), dim3((n_hi + 255) / 256, batch), dim3(256), 0, st, P, V, W,
                        mu_in, mu_out, nact, so, fac, ld, pstride);
 }
-void launch_panels(hipStream_t st, int mcap, double* P, double* V, double* W, const double* mu_in,
+void launch_panels(hipStream_t st, int mcap, bool latency, double* P, double* V, double* W, const double* mu_in,
                    double* mu_out, const int* nact, const SolveOut* so, const double* fac, int ld, long pstride,
                    int batch, int n_hi) {
-  switch (mcap) {
-    case 1: launch_panels_t<1>(st, P, V, W, mu_in, mu_out, nact, so, fac, ld, pstride, batch, n_hi); break;
-    case 2: launch_panels_t<2>(st, P, V, W, mu_in, mu_out, nact, so, fac, ld, pstride, batch, n_hi); break;
-    case 4: launch_panels_t<4>(st, P, V, W, mu_in, mu_out, nact, so, fac, ld, pstride, batch, n_hi); break;
-    case 8: launch_panels_t<8>(st, P, V, W, mu_in, mu_out, nact, so, fac, ld, pstride, batch, n_hi); break;
-    default: launch_panels_t<16>(st, P, V, W, mu_in, mu_out, nact, so, fac, ld, pstride, batch, n_hi); break;
-  }
+  with_mcap(mcap, [&](auto M) { launch_panels_t<M.value>(st, latency, P, V, W, mu_in, mu_out, nact, so, fac, ld, pstride, batch, n_hi); });
 }
 
 // The throughput shape of the single-launch step: k_panels<.., SPLIT> (see there).
@@ -2463,49 +2457,25 @@ void launch_step_split_tp(hipStream_t st, int mcap, double* P, double* V, double
                           long pstride, int batch, int n_hi, int kbase) {
   const dim3 grid(1 + (n_hi + 255) / 256, batch);
   SplitArgs sa{dacc_in, dacc_out, in, out, flags, fac, neff_floor, queue, mbox, ready, seq, publish, kbase, cfg};
-#define EKF_SPLIT_TP(M)                                                                                              \
-  do {                                                                                                               \
-    if (cfg.gate_rej)                                                                                                \
-      hipLaunchKernelGGL((k_panels_split<M, true>), grid, dim3(256), 0, st, P, V, W, mu_in, mu_out, nact, ld, pstride, sa); \
-    else                                                                                                             \
-      hipLaunchKernelGGL((k_panels_split<M, false>), grid, dim3(256), 0, st, P, V, W, mu_in, mu_out, nact, ld, pstride, sa); \
-  } while (0)
-  switch (mcap) {
-    case 1: EKF_SPLIT_TP(1); break;
-    case 2: EKF_SPLIT_TP(2); break;
-    case 4: EKF_SPLIT_TP(4); break;
-    case 8: EKF_SPLIT_TP(8); break;
-    default: break;                                    // (16 landmarks per pass: registers for one wave per SIMD only; the caller
-  }                                                    //  takes the two-launch path)
-#undef EKF_SPLIT_TP
+  with_mcap(mcap, [&](auto M) {
+    if constexpr (M.value <= 8)                        // (16 landmarks per pass: never planned, see plan_step)
+      with_flag(cfg.gate_rej != nullptr, [&](auto G) {
+        hipLaunchKernelGGL((k_panels_split<M.value, G.value>), grid, dim3(256), 0, st, P, V, W, mu_in, mu_out, nact, ld, pstride, sa);
+      });
+  });
 }
 
-// Whether a step of this shape is run as one launch (the latency regime, see k_step_split): while every panel
-// workgroup has a CU to itself.  N=2000: 1 trajectory 33.7 k steps/s against 28.0 k with two launches, 4 trajectories
-// 79.2 k against 73.6 k, but 8 trajectories (504 panel workgroups) 85.8 k against 98.8 k.
-bool step_is_split(int batch, int n_hi, int cus) { return (long)((n_hi + 63) / 64) * batch <= (long)cus; }
 void launch_step_split(hipStream_t st, int mcap, double* P, double* V, double* W, const double* dacc_in, double* dacc_out,
                        const double* mu_in, double* mu_out, const int* nact, const StepIn* in, SolveOut* out,
                        unsigned* flags, double* fac, const int* neff_floor, unsigned* queue, unsigned* ready, unsigned seq,
                        int publish, const DeviceConfig& cfg, int ld, long pstride, int batch, int n_hi, int kbase) {
   const dim3 grid(1 + (n_hi + 63) / 64, batch);
-#define EKF_SPLIT(M)                                                                                                \
-  do {                                                                                                              \
-    if (cfg.gate_rej)                                                                                               \
-      hipLaunchKernelGGL((k_step_split<M, true>), grid, dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out, nact, in, \
-                         out, flags, fac, neff_floor, queue, ready, seq, publish, cfg, ld, pstride, kbase);         \
-    else                                                                                                            \
-      hipLaunchKernelGGL((k_step_split<M, false>), grid, dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out, nact, in, \
-                         out, flags, fac, neff_floor, queue, ready, seq, publish, cfg, ld, pstride, kbase);         \
-  } while (0)
-  switch (mcap) {
-    case 1: EKF_SPLIT(1); break;
-    case 2: EKF_SPLIT(2); break;
-    case 4: EKF_SPLIT(4); break;
-    case 8: EKF_SPLIT(8); break;
-    default: EKF_SPLIT(16); break;
-  }
-#undef EKF_SPLIT
+  with_mcap(mcap, [&](auto M) {
+    with_flag(cfg.gate_rej != nullptr, [&](auto G) {
+      hipLaunchKernelGGL((k_step_split<M.value, G.value>), grid, dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out, nact, in,
+                         out, flags, fac, neff_floor, queue, ready, seq, publish, cfg, ld, pstride, kbase);
+    });
+  });
 }
 
 template <int NKTM, int NKL, bool NT>
@@ -2520,9 +2490,10 @@ static void launch_flush_t(hipStream_t st, double* P, const double* V, const dou
 }
 
 // streaming = the batch's covariances do not fit the Infinity Cache: nontemporal accesses
-void launch_flush(hipStream_t st, bool streaming, double* P, const double* V, const double* W,
-                  const double* dacc, const int* nact, const SolveOut* so, int ld, long pstride, int batch,
-                  int n_hi, int nkt, int rows_per_block) {
+void launch_flush(hipStream_t st, const PassPlan& p, double* P, const double* V, const double* W,
+                  const double* dacc, const int* nact, const SolveOut* so, int ld, long pstride, int batch) {
+  const bool streaming = p.streaming;
+  const int n_hi = p.e_hi, nkt = p.nkt, rows_per_block = p.rows_per_block;
 #define EKF_FLUSH(N, L)                                                                                   \
   do {                                                                                                    \
     if (streaming) launch_flush_t<N, L, true>(st, P, V, W, dacc, nact, so, ld, pstride, batch, n_hi, nkt, rows_per_block); \
@@ -2536,77 +2507,35 @@ void launch_flush(hipStream_t st, bool streaming, double* P, const double* V, co
 #undef EKF_FLUSH
 }
 
-// the row-slab form of the pass (k_flush_rs): persistent workgroups, `queue` = 8 x RS_QSTRIDE zeroed words
+// the row-slab form of the pass (k_flush_rs): persistent workgroups, `queue` = 8 x RS_QSTRIDE zeroed words; the work queues'
+// hand-out as planned (plan_pass), or one equal static share per workgroup (mode 4) where `shares` is given
 template <int NKT, bool NT, bool PAN>
-static void launch_flush_rs_t(hipStream_t st, double* P, const double* V, const double* W, const double* dacc,
-                              const int* nact, const SolveOut* so, int ld, long pstride, int batch, int n_hi, int nkt,
-                              int workgroups, unsigned* queue, int chunk, const int* shares, const CadOut* wv) {
-  const int nrb = (n_hi + RS_ROWS - 1) / RS_ROWS;
-  if (shares) {                                        // equal static shares (mode 4): one per workgroup
-    if (wv)
-      hipLaunchKernelGGL((k_flush_rs<NKT, NT, PAN, true>), dim3((unsigned)workgroups), dim3(512), 0, st, P, V, W, dacc, nact, so, ld,
-                         pstride, nkt, batch, nrb, 1, 0, 4, queue, shares, wv);
-    else
-      hipLaunchKernelGGL((k_flush_rs<NKT, NT, PAN, false>), dim3((unsigned)workgroups), dim3(512), 0, st, P, V, W, dacc, nact, so, ld,
-                         pstride, nkt, batch, nrb, 1, 0, 4, queue, shares, wv);
-    return;
-  }
-  // Units (see the three modes at k_flush_rs's `pop`).  With an even number of trajectories per queue whole slabs taken
-  // trajectory by trajectory balance perfectly (16 trajectories: 366 us against 430 us in chunks of 22 strips); the
-  // last trajectory of an odd number finds no partner and its slabs -- only they -- are cut in two (N=2000: 8
-  // trajectories 203 us against 256 us with the former rule and 328 us whole; 24: 557 us against 668 us); a batch that
-  // is no multiple of 8 would leave the queues with unequal work, so its last trajectories are dealt over all queues
-  // slab by slab -- profiles/r02_chunk_sweep.txt, profiles/r02_batch_sweep.txt.  Below 8 trajectories (the row-slab
-  // kernel then only runs for long ones, N=8000) every slab is cut so that there are about three units per CU.
-  const int s_max = (n_hi + 63) / 64;                  // strips of the longest slab
-  int cs = s_max, nch = 1, mode = 0;
-  if (chunk > 0) {                                     // ("pass_chunk" option: every slab of every trajectory)
-    cs = std::min(std::max(chunk, 1), s_max);
-    nch = (s_max + cs - 1) / cs;
-  } else if (batch >= 8) {
-    if (batch % 8 == 0) {                              // pairs; an unpaired trajectory (8: each queue's only one) cut in two
-      mode = 1;
-      if (s_max >= 4) {
-        cs = (s_max + 1) / 2;
-        nch = 2;
-      }
-    } else if (batch <= 12 && s_max >= 8) {             // (N=2000: 9 trajectories 253 us against 329 us whole, 10: 284 / 333,
-                                                       //  12: 327 / 342; 14: 360 / 344 -- from 13 on whole slabs)
-      mode = 3;                                        // equal work per queue, half slabs, longest first
-      nch = (s_max + 3) / 4;                           // h: half a chunk; chunks of cs = 2 h strips
-      cs = 2 * nch;
-    } else {
-      mode = 2;                                        // equal work per queue, longest slabs first
-    }
-  } else {                                             // a few long trajectories (N=8000): about three units per CU
-    long steps = 0;
-    for (int rb = 0; rb < nrb; ++rb) steps += std::max(1, s_max - 2 * rb);
-    steps *= batch;
-    if ((long)nrb * batch < 3L * workgroups) {
-      cs = (int)std::max<long>(2, (steps + 3L * workgroups - 1) / (3L * workgroups));
-      nch = (s_max + cs - 1) / cs;
-    }
-  }
-  const long units = (long)nrb * (mode == 0 ? nch : mode == 3 ? 2 : 1) * batch;   // (modes 1, 2: at least; only the grid size depends on it)
+static void launch_flush_rs_t(hipStream_t st, const PassPlan& p, double* P, const double* V, const double* W, const double* dacc,
+                              const int* nact, const SolveOut* so, int ld, long pstride, int batch, unsigned* queue,
+                              const int* shares, const CadOut* wv) {
+  const int nrb = (p.e_hi + RS_ROWS - 1) / RS_ROWS;
+  const unsigned grid = shares ? p.rs_workgroups : p.rs_grid;
+  const int nch = shares ? 1 : p.rs_nch, cs = shares ? 0 : p.rs_cs, mode = shares ? 4 : p.rs_mode;
   if (wv)
-    hipLaunchKernelGGL((k_flush_rs<NKT, NT, PAN, true>), dim3((unsigned)std::min<long>(workgroups, units)), dim3(512), 0, st, P, V, W,
-                       dacc, nact, so, ld, pstride, nkt, batch, nrb, nch, cs, mode, queue, nullptr, wv);
+    hipLaunchKernelGGL((k_flush_rs<NKT, NT, PAN, true>), dim3(grid), dim3(512), 0, st, P, V, W, dacc, nact, so, ld, pstride, p.nkt,
+                       batch, nrb, nch, cs, mode, queue, shares, wv);
   else
-    hipLaunchKernelGGL((k_flush_rs<NKT, NT, PAN, false>), dim3((unsigned)std::min<long>(workgroups, units)), dim3(512), 0, st, P, V, W,
-                       dacc, nact, so, ld, pstride, nkt, batch, nrb, nch, cs, mode, queue, nullptr, wv);
+    hipLaunchKernelGGL((k_flush_rs<NKT, NT, PAN, false>), dim3(grid), dim3(512), 0, st, P, V, W, dacc, nact, so, ld, pstride, p.nkt,
+                       batch, nrb, nch, cs, mode, queue, shares, wv);
 }
 
-void launch_flush_rs(hipStream_t st, bool streaming, double* P, const double* V, const double* W, const double* dacc,
-                     const int* nact, const SolveOut* so, int ld, long pstride, int batch, int n_hi, int nkt,
-                     int workgroups, unsigned* queue, int chunk, const int* shares, const CadOut* wv) {
+void launch_flush_rs(hipStream_t st, const PassPlan& p, double* P, const double* V, const double* W, const double* dacc,
+                     const int* nact, const SolveOut* so, int ld, long pstride, int batch, unsigned* queue, const int* shares,
+                     const CadOut* wv) {
+  const int nkt = p.nkt;
 #define EKF_FLUSH_RS(N)                                                                                   \
   do {                                                                                                    \
     if (ld > PPW) {                                                                                       \
-      if (streaming) launch_flush_rs_t<N, true, true>(st, P, V, W, dacc, nact, so, ld, pstride, batch, n_hi, nkt, workgroups, queue, chunk, shares, wv); \
-      else launch_flush_rs_t<N, false, true>(st, P, V, W, dacc, nact, so, ld, pstride, batch, n_hi, nkt, workgroups, queue, chunk, shares, wv);          \
+      if (p.streaming) launch_flush_rs_t<N, true, true>(st, p, P, V, W, dacc, nact, so, ld, pstride, batch, queue, shares, wv); \
+      else launch_flush_rs_t<N, false, true>(st, p, P, V, W, dacc, nact, so, ld, pstride, batch, queue, shares, wv);          \
     } else {                                                                                              \
-      if (streaming) launch_flush_rs_t<N, true, false>(st, P, V, W, dacc, nact, so, ld, pstride, batch, n_hi, nkt, workgroups, queue, chunk, shares, wv); \
-      else launch_flush_rs_t<N, false, false>(st, P, V, W, dacc, nact, so, ld, pstride, batch, n_hi, nkt, workgroups, queue, chunk, shares, wv);          \
+      if (p.streaming) launch_flush_rs_t<N, true, false>(st, p, P, V, W, dacc, nact, so, ld, pstride, batch, queue, shares, wv); \
+      else launch_flush_rs_t<N, false, false>(st, p, P, V, W, dacc, nact, so, ld, pstride, batch, queue, shares, wv);          \
     }                                                                                                     \
   } while (0)
   if (nkt <= 4) EKF_FLUSH_RS(4);

@@ -20,13 +20,9 @@
 // device-side association, the dense product -- works on P_base as it stands.
 #include <atomic>
 #include "ekf_devfn.h"
+#include "ekf_host_plan.h"
 
 namespace ekf {
-
-constexpr int SMALL_N_MAX = 79;         // 3 + 2 * 38 (<= 5 column tiles of 16; 50 KB of LDS): beyond, the general kernels are faster
-                                        // for ONE trajectory (latency) ...
-constexpr int SMALL_N_MAX_BANK = 131;   // ... but not for a bank that fills the chip (3 + 2 * 64; 9 column tiles, 137 KB of LDS: one
-constexpr int SMALL_BANK_MIN = 128;     // workgroup per CU): N = 64 x 256 10.4 M against 7.9 M steps/s, x 1024 against 5.4 M
 
 // One step's landmark updates and prediction on the LDS-resident state.  `Pl` is n x ps (ps odd: row and column walks are
 // both conflict-free), `mu` the mean, `hp` / `kk` 2 x n scratch.  LOG: the instantiations that serve the innovation log and
@@ -419,12 +415,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   small_stream_body<NT, TM, true>(SMALL_STREAM_PASS, lg);
 }
 
-int small_state_limit(int batch) { return batch >= SMALL_BANK_MIN ? SMALL_N_MAX_BANK : SMALL_N_MAX; }
-
 int launch_small_stream(hipStream_t st, double* P, const double* mu_in, double* mu_out, const int* nact, const StepIn* in,
                         int batch, int nsteps, unsigned* flags, const DeviceConfig& cfg, int ld, long pstride, int n_hi,
-                        double* host_out, int out_b, unsigned long long* host_seq, unsigned long long out_seq, bool many,
-                        const InnovLog* lg) {
+                        double* host_out, int out_b, unsigned long long* host_seq, unsigned long long out_seq, int form,
+                        const InnovLog* lg) {   // form: ekf_host_plan.h's SmallForm (plan_small)
   const int n = n_hi < SMALL_N_MAX_BANK ? n_hi : SMALL_N_MAX_BANK, ps = n | 1;
   const size_t bytes = sizeof(double) * ((size_t)n * ps + 5 * (size_t)n + 4) + 2 * sizeof(StepIn);
 #define EKF_SMALL(K, TM)                                                                                                 \
@@ -454,10 +448,10 @@ int launch_small_stream(hipStream_t st, double* P, const double* mu_in, double* 
     }                                                                                                                    \
     EKF_SMALL(K, TM);                                                                                                    \
   } while (0)
-  if (many && n <= 48) EKF_SMALL(k_small_stream_occ, 3);
-  else if (n <= 48) EKF_SMALL(k_small_stream, 3);
-  else if (n <= 80) EKF_SMALL(k_small_stream, 5);
-  else if (n <= 112) EKF_SMALL_BIG(k_small_stream_two, 7);
+  if (form == SMALL_OCC_3) EKF_SMALL(k_small_stream_occ, 3);
+  else if (form == SMALL_3) EKF_SMALL(k_small_stream, 3);
+  else if (form == SMALL_5) EKF_SMALL(k_small_stream, 5);
+  else if (form == SMALL_TWO_7) EKF_SMALL_BIG(k_small_stream_two, 7);
   else EKF_SMALL_BIG(k_small_stream, 9);
 #undef EKF_SMALL_BIG
 #undef EKF_SMALL

@@ -2,7 +2,7 @@
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DEKF_HOST_ONLY
 //       -I slam-duckietown_amd/csrc -I include tests/host_plan_check.cpp -o host_plan_check
 // Everything below runs the SAME source the library ships (slam-duckietown_amd/csrc/ekf_host_plan.h, ekf_device.h): the
-// work queues and equal static shares of the row-slab covariance pass, the cadence / pass planning, the step records and
+// work queues and equal static shares of the row-slab covariance pass, the cadence / pass / step planning, the step records and
 // their active bound, the validation of observation lists, the covariance's device layout.  Enumerations (every unit /
 // strip / matrix entry exactly once) plus randomised invariants; any sanitizer report or failed check ends the run with a
 // non-zero status.  tests/test_cpu_host.py::test_host_planning_logic_under_the_sanitizers builds and runs it (CPU only).
@@ -275,6 +275,113 @@ static void check_planning(std::mt19937& rng) {
   }
 }
 
+// ---- what the launchers are handed: the pass's hand-out, the per-step form, the fused cadence's follow-up, the small path ----
+// (every unit of a row-slab plan's work queues names a (trajectory, slab) of the batch; each one comes whole or as all its chunks)
+static void check_handout(int batch, int nrb, int nch, int mode, int grid, std::vector<int>& buf) {
+  const int total = debug_pass_units(batch, nrb, nch, mode, nullptr, 0);
+  buf.assign((size_t)total, -1);
+  CHECK(debug_pass_units(batch, nrb, nch, mode, buf.data(), total) == total, "unit count");
+  CHECK(grid >= 1 && grid <= total, "grid %d for %d units (batch %d nrb %d nch %d mode %d)", grid, total, batch, nrb, nch, mode);
+  const int chunks_per_slab = mode == 3 ? 2 : nch;
+  std::vector<int> whole((size_t)batch * nrb, 0), parts((size_t)batch * nrb, 0);
+  std::set<long> keys;
+  for (int u = 0; u < total; ++u) {
+    const int code = buf[u] & 1023, slab = buf[u] >> 10;
+    CHECK(buf[u] >= 0 && slab < batch * nrb, "unit %d of mode %d", buf[u], mode);
+    if (code == 1023) ++whole[slab];
+    else {
+      CHECK(code < chunks_per_slab && keys.insert((long)slab * 1024 + code).second, "chunk %d of slab %d", code, slab);
+      ++parts[slab];
+    }
+  }
+  for (int slab = 0; slab < batch * nrb; ++slab)
+    CHECK((whole[slab] == 1 && parts[slab] == 0) || (whole[slab] == 0 && parts[slab] == chunks_per_slab),
+          "batch %d nrb %d nch %d mode %d: slab %d %d whole, %d chunks", batch, nrb, nch, mode, slab, whole[slab], parts[slab]);
+}
+
+static void check_launch_plans(std::mt19937& rng) {
+  std::vector<int> buf;
+  for (int it = 0; it < 6000; ++it) {
+    HostPlan h = random_plan(rng);
+    if (rng() % 8 == 0) {                              // (banks of small filters)
+      h.batch = 1 + rng() % 1200;
+      h.n.assign(h.batch, h.n_max);
+      h.neff.assign(h.batch, h.n_max);
+      h.neff_enq.assign(h.batch, h.n_max);
+      h.floor_host.assign(h.batch, 3);
+    }
+    h.pending_k = rng() % 3 == 0 ? 0 : 2 * (int)(rng() % 41);
+    h.pending_steps = (int)(rng() % 41);
+    h.opt_fused_step = (int)(rng() % 3);
+    h.opt_small_state = rng() % 4 != 0;
+    h.opt_chain = rng() % 4 != 0;
+    h.opt_w_from_v = rng() % 4 != 0;
+    h.opt_panel_shape = rng() % 3 == 0 ? (int)(rng() % 4) : 0;
+    h.opt_panel_tform = rng() % 4 != 0;
+    h.opt_col_gather = rng() % 4 != 0;
+    h.chain_run = rng() % 2;
+    // the covariance pass, as the handle stands and as asked about (any pending ranks, every index active)
+    for (int q = 0; q < 2; ++q) {
+      const PassPlan p = q == 0 ? plan_pass(&h) : plan_pass(&h, KTOT, true);
+      if (q == 1) CHECK(p.nkt == NKT && p.e_hi >= (h.sizes_dirty ? h.n_max : p.n_hi), "hypothetical pass %d %d", p.nkt, p.e_hi);
+      if (p.kernel == 0) CHECK(p.rows_per_block == flush_rows_per_block(&h, p.streaming, p.e_hi), "rows per block");
+      if (p.kernel == 2 && (long)h.batch * ((p.e_hi + 127) / 128) * ((p.e_hi + 63) / 64) <= 400000)
+        check_handout(h.batch, (p.e_hi + RS_ROWS - 1) / RS_ROWS, p.rs_nch, p.rs_mode, p.rs_grid, buf);
+    }
+    // the per-step update
+    const int n_hi = h.sizes_dirty ? h.n_max : *std::max_element(h.n.begin(), h.n.end());
+    for (int m_hi : {0, 1, 3, 5, 8, 9, 16}) {
+      const StepPlan s = plan_step(&h, m_hi, n_hi);
+      CHECK(s.mcap >= m_hi && s.mcap <= 16, "mcap %d for %d", s.mcap, m_hi);
+      CHECK((s.form == STEP_PREDICT) == (m_hi == 0 && h.pending_k == 0), "prediction-only form");
+      if (s.form == STEP_SPLIT || s.form == STEP_SPLIT_TP) CHECK(h.opt_fused_step != 0, "single launch without fused_step");
+      if (s.form == STEP_SPLIT_TP) CHECK(s.mcap <= 8 && !s.panels_latency, "throughput form with mcap %d", s.mcap);
+      if (s.form == STEP_SPLIT) CHECK(step_is_split(h.batch, n_hi, h.cu_count), "split form");
+      CHECK(s.flush_before == (s.form != STEP_PREDICT && ((h.pending_k + 2 * s.mcap + 3) & ~3) > KTOT), "flush before");
+      // behind the step (its ranks appended): no pending count beyond the rank slots survives
+      HostPlan a = h;
+      a.pending_k = (s.flush_before ? 0 : h.pending_k) + 2 * m_hi;
+      a.pending_steps = (s.flush_before ? 0 : h.pending_steps) + 1;
+      if (a.pending_k + 2 > KTOT) CHECK(pass_due_after_step(&a, m_hi), "ranks left pending beyond the slots");
+    }
+    // the small-state path: the kernel's tiles cover the state, its forms stay within their size limits
+    if (small_path(&h)) CHECK(h.pending_k == 0 && h.n_max <= small_state_limit(h.batch) && h.n_max <= SMALL_N_MAX_BANK, "small path");
+    const int sf = plan_small(&h, n_hi), sn = std::min(n_hi, SMALL_N_MAX_BANK);
+    const int tiles[] = {3, 3, 5, 7, 9};
+    CHECK(sf >= SMALL_OCC_3 && sf <= SMALL_9 && 16 * tiles[sf] >= sn, "small form %d for n %d", sf, sn);
+    if (sf == SMALL_OCC_3) CHECK(h.batch > 3 * h.cu_count && sn <= 48, "many small filters");
+    if (sf == SMALL_3 || sf == SMALL_5) CHECK(sn <= (sf == SMALL_3 ? 48 : 80), "small form %d for n %d", sf, sn);
+    if (sf == SMALL_TWO_7) CHECK(sn > 80 && sn <= 112, "two-per-CU form for n %d", sn);
+    // chained runs and the fused cadence's follow-up
+    const int gw = chain_gather_workgroups(h.batch, h.cu_count);
+    CHECK(gw >= 1 && gw <= CH_GW, "gather workgroups %d", gw);
+    RunPlan rp;
+    rp.ncad = 1 + (int)(rng() % 4);
+    for (int c = 0; c < rp.ncad; ++c) {
+      rp.slots_hi.push_back(rng() % 5 == 0 ? 0 : 1 + (int)(rng() % CAD_SLOTS));
+      rp.steps_hi.push_back((int)(rng() % (CAD_SLOTS + 1)));
+    }
+    if (plan_chain_run(&h, rp.ncad))
+      CHECK(h.batch <= 40 && rp.ncad >= 2 && h.opt_chain && h.opt_lookahead, "chained run of %d cadences, batch %d", rp.ncad, h.batch);
+    if (h.sizes_dirty) continue;                       // (cadences run on sizes read back)
+    for (int c = 0; c < rp.ncad; ++c)
+      for (int pre = 0; pre < 2; ++pre) {
+        const CadStepPlan p = plan_cadence_step(&h, rp, c, n_hi, pre);
+        const bool latency = panels_cad_latency_regime(h.batch, n_hi);
+        CHECK(p.panel >= PANEL_TF && p.panel <= PANEL_FOUR, "panel form %d", p.panel);
+        if (p.gather_cols) CHECK(!pre && rp.slots_hi[c] > 0 && p.col_wgs > 0 && h.opt_col_gather, "column gather");
+        if (p.beside) CHECK(p.due && c + 1 < rp.ncad && h.opt_lookahead, "beside");
+        if (p.chain_next) CHECK(p.beside && h.chain_run && p.due, "chain_next");
+        if (p.w_from_v)
+          CHECK(p.due && !p.beside && h.pending_k == 0 && plan_pass(&h, 2 * rp.slots_hi[c]).kernel == 2 &&
+                (p.panel == PANEL_ONE || p.panel == PANEL_FOUR), "w_from_v");
+        if (p.panel == PANEL_TF) CHECK(p.chain_next && !p.gather_cols && latency && h.opt_panel_tform, "triangular-solve form");
+        else if (h.opt_panel_shape > 0) CHECK(p.panel == PANEL_KS + h.opt_panel_shape - 1, "panel_shape %d: form %d", h.opt_panel_shape, p.panel);
+        else CHECK((p.panel == PANEL_KS) == latency, "panel form %d", p.panel);
+      }
+  }
+}
+
 static void check_step_records(std::mt19937& rng) {
   for (int it = 0; it < 3000; ++it) {
     HostPlan h;
@@ -323,6 +430,7 @@ int main() {
   check_queues();
   check_shares(rng);
   check_planning(rng);
+  check_launch_plans(rng);
   check_step_records(rng);
   std::printf("host_plan_check: %ld checks passed\n", checks);
   return 0;
