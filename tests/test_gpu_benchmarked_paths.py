@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from oracle import ekf_oracle as orc
+from tests import parity_blocks as pb
 
 pytestmark = pytest.mark.gpu
 
@@ -154,6 +155,7 @@ def test_steady_state_leg_n2000_x32_as_benchmarked(sd):
             close(got[t][0], om)
             close(got[t][1], oP)
             close(got[t][1].sum(axis=1), oP.sum(axis=1))
+            pb.assert_filter_close(*got[t], om, oP, pb.observed_landmarks(streams[t][4]), what=f"trajectory {t}: ")
 
 
 def test_variable_m_leg_n2000_x32_as_benchmarked(sd):
@@ -274,6 +276,7 @@ def test_config5_n8000_active_bound_bit_identical(sd):
         om, oP = orc.ekf_step_structured(om, oP, lin[k], ang[k], idx[k], zr[k], zb[k], cfg)
     close(out[0][0][:top], om)
     close(P[:top, :top], oP)
+    pb.assert_filter_close(out[0][0], P, om, oP, pb.observed_landmarks(idx), mean0=mean0, diag0=diag0)
 
 
 def test_config5_n8000_dense_leg_as_benchmarked(sd):
@@ -308,6 +311,7 @@ def test_config5_n8000_dense_leg_as_benchmarked(sd):
     close(mu[:top], om)
     close(P[:top, :top], oP)
     assert np.array_equal(mu[top:], mean0[top:])
+    pb.assert_filter_close(mu, P, om, oP, pb.observed_landmarks(idx), mean0=mean0, diag0=diag0)
 
 
 def test_two_handles_from_two_host_threads(sd):
@@ -370,12 +374,30 @@ def test_banks_driven_from_one_host_thread(sd):
         f.stream_upload(*[np.stack([s[i] for s in mine], axis=1) for i in (2, 3, 4, 5, 6)])
         return f
 
+    lib = sd.load_library()
+
+    def drive(fs):
+        # run_banks one slice at a time, every bank's flags read after every slice (a bounded device-side wait that fires
+        # raises EKF_FLAG_INTERNAL); the same slices as run_banks(fs, 0, steps, slice_steps=6)
+        for k in range(0, steps, 6):
+            run_banks(fs, k, min(6, steps - k), slice_steps=6)
+            for f in fs:
+                assert [f.flags(b) for b in range(f.batch)] == [0] * f.batch, (k, lib.ekf_last_error(f._h))
+        for f in fs:
+            assert lib.ekf_debug_chained(f._h) > 0                   # the banks run chained solves, alone and together
+
     alone = {}
     for ids in groups:
         with make(ids) as f:
             run_banks([f], 0, steps, slice_steps=6)    # (the same slices: where a cadence ends depends on them)
             for b, t in enumerate(ids):
                 alone[t] = f.state(b)
+            assert lib.ekf_debug_chained(f._h) > 0
+        with make(ids) as f:
+            drive([f])
+            for b, t in enumerate(ids):
+                mu, P = f.state(b)
+                assert np.array_equal(mu, alone[t][0]) and np.array_equal(P, alone[t][1]), t
     banks = [make(ids) for ids in groups]
     try:
         run_banks(banks, 0, steps, slice_steps=6)
@@ -385,6 +407,17 @@ def test_banks_driven_from_one_host_thread(sd):
             for b, t in enumerate(ids):
                 mu, P = f.state(b)
                 assert f.flags(b) == 0
+                assert np.array_equal(mu, alone[t][0]) and np.array_equal(P, alone[t][1]), t
+            assert lib.ekf_debug_chained(f._h) > 0
+    finally:
+        for f in banks:
+            f.close()
+    banks = [make(ids) for ids in groups]
+    try:
+        drive(banks)
+        for f, ids in zip(banks, groups):
+            for b, t in enumerate(ids):
+                mu, P = f.state(b)
                 assert np.array_equal(mu, alone[t][0]) and np.array_equal(P, alone[t][1]), t
     finally:
         for f in banks:
@@ -396,3 +429,4 @@ def test_banks_driven_from_one_host_thread(sd):
         om, oP = orc.ekf_step_structured(om, oP, s[2][k], s[3][k], s[4][k], s[5][k], s[6][k], cfg)
     close(alone[5][0], om)
     close(alone[5][1], oP)
+    pb.assert_filter_close(*alone[5], om, oP, pb.observed_landmarks(s[4]), mean0=s[0], diag0=s[1])

@@ -19,6 +19,7 @@ import pytest
 
 from oracle import ekf_oracle as orc
 from tests import golden_util as gu
+from tests import parity_blocks as pb
 
 pytestmark = pytest.mark.gpu
 
@@ -201,12 +202,15 @@ def test_block_diagonal_start_with_the_active_bound(sd):
         assert fused[b][0].shape == (sizes[b],)
         for other in (plain, dense):
             assert orc.rel_fro(fused[b][0], other[b][0]) < PATH_TOL and orc.rel_fro(fused[b][1], other[b][1]) < PATH_TOL
+            pb.assert_filter_close(*fused[b], *other[b], pb.observed_landmarks(idx[:, b], mm[:, b]), mean0=means[b],
+                                   diag0=diags[b], tol=PATH_TOL, corr_tol=pb.PATH_CORR_TOL, what=f"trajectory {b}: ")
     cfg = orc.EkfConfig()
     om, oP = means[1].copy(), np.diag(diags[1])
     for k in range(steps):
         om, oP = orc.ekf_step_dense(om, oP, streams[1][2][k], streams[1][3][k], idx[k, 1, :mm[k, 1]],
                                     streams[1][5][k][:mm[k, 1]], streams[1][6][k][:mm[k, 1]], cfg)
     assert orc.rel_fro(fused[1][0], om) < TIGHT and orc.rel_fro(fused[1][1], oP) < TIGHT
+    pb.assert_filter_close(*fused[1], om, oP, pb.observed_landmarks(idx[:, 1], mm[:, 1]), mean0=means[1], diag0=diags[1])
 
 
 @pytest.mark.parametrize("options,expect", [([("rank_limit", 48)], (5, 13)), ([("flush_every", 2)], (7, 13)),
@@ -276,6 +280,8 @@ def test_all_three_shapes_of_the_panel_launch_agree(sd):
                           options=[("active_bound", 0), ("fused_cadence", 0)])
     for b in range(3):
         assert orc.rel_fro(res[3][b][0], plain[b][0]) < PATH_TOL and orc.rel_fro(res[3][b][1], plain[b][1]) < PATH_TOL
+        pb.assert_filter_close(*res[3][b], *plain[b], pb.observed_landmarks(streams[b][4]), mean0=streams[b][0],
+                               diag0=streams[b][1], tol=PATH_TOL, corr_tol=pb.PATH_CORR_TOL, what=f"trajectory {b}: ")
 
 
 def test_forced_panel_shapes_agree_bit_for_bit(sd):

@@ -9,6 +9,7 @@ import pytest
 
 from oracle import ekf_oracle as orc
 from tests import golden_util as gu
+from tests import parity_blocks as pb
 from tests.conftest import path_ran
 
 pytestmark = pytest.mark.gpu
@@ -142,6 +143,7 @@ def test_config2_n500_fifty_steps_vs_dense(sd):
             mu, P = f.state()
             close(mu, om)
             close(P, oP)
+            pb.assert_filter_close(mu, P, om, oP, pb.observed_landmarks(idx[:k + 1]), mean0=mean0, diag0=diag0, what=f"step {k}: ")
 
 
 def test_config3_n2000_stream_vs_structured(sd):
@@ -159,6 +161,7 @@ def test_config3_n2000_stream_vs_structured(sd):
         mu, P = f.state()
     close(mu, om)
     close(P, oP)
+    pb.assert_filter_close(mu, P, om, oP, pb.observed_landmarks(idx), mean0=mean0, diag0=diag0)
     assert np.abs(P - P.T).max() <= 1e-9 * np.abs(P).max()
     d = np.diag(P)
     assert (d[3:] <= diag0[3:] * (1 + 1e-12)).all() and (d > 0).all()
@@ -368,14 +371,17 @@ def test_deferred_covariance_pass(sd, every):
         f.set_state_diag(mean0, diag0)
         for k in range(steps):
             mk = ms[k]
+            seen = pb.observed_landmarks(idx[:k + 1], np.array(ms[:k + 1]))
             f.step(lin[k], ang[k], idx[k][:mk], zr[k][:mk], zb[k][:mk])
             om, oP = orc.ekf_step_dense(om, oP, lin[k], ang[k], idx[k][:mk], zr[k][:mk], zb[k][:mk], cfg)
             close(f.mean(), om)                      # the mean never waits for a flush
             if k in (6, 13, 25):
                 close(f.covariance(), oP)            # reading the covariance flushes
+                pb.assert_filter_close(f.mean(), f.covariance(), om, oP, seen, mean0=mean0, diag0=diag0, what=f"step {k}: ")
         mu, P = f.state()
     close(mu, om)
     close(P, oP)
+    pb.assert_filter_close(mu, P, om, oP, seen, mean0=mean0, diag0=diag0)
 
 
 def test_deferred_pass_batched_n500(sd):
@@ -399,6 +405,8 @@ def test_deferred_pass_batched_n500(sd):
             mu, P = f.state(b)
             close(mu, ref[b][0])
             close(P, ref[b][1])
+            pb.assert_filter_close(mu, P, *ref[b], pb.observed_landmarks(streams[b][4]), mean0=streams[b][0],
+                                   diag0=streams[b][1], what=f"trajectory {b}: ")
 
 
 def test_active_bound_is_exact(sd):
@@ -423,6 +431,7 @@ def test_active_bound_is_exact(sd):
         om, oP = orc.ekf_step_dense(om, oP, lin[k], ang[k], idx[k], zr[k], zb[k], cfg)
     close(out[0][0], om)
     close(out[0][1], oP)
+    pb.assert_filter_close(*out[0], om, oP, pb.observed_landmarks(idx), mean0=mean0, diag0=diag0)
     assert np.array_equal(out[0][1][243:, :243], np.zeros((len(mean0) - 243, 243)))   # never touched
 
 
@@ -466,11 +475,18 @@ def test_max_size_n8000_three_steps(sd):
         f.run_stream(lin, ang, idx, zr, zb)
         mu = f.mean()
         rows = sorted({0, 1, 2, n - 1} | {3 + 2 * int(j) for j in idx.ravel()})
+        got = []
         for r in rows[:12]:
             close(f.covariance_block(r, 0, 1, n)[0], oP[r])
             close(f.covariance_block(0, r, n, 1)[:, 0], oP[:, r])
+            got.append(f.covariance_block(r, 0, 1, n)[0])
         P = f.covariance()
     close(mu, om)
+    # the rows downloaded above, piece by piece: pose block, pose-landmark cross terms, landmark block, the means
+    act = np.array(rows[:12])
+    assert list(act[:3]) == [0, 1, 2]
+    err = pb.active_errors(mu[act], np.array(got)[:, act], om[act], oP[np.ix_(act, act)])
+    pb.check_errors(err, TIGHT)
     close(P.sum(axis=1), oP.sum(axis=1))
     close(P.sum(axis=0), oP.sum(axis=0))
     close(np.diag(P), np.diag(oP))
