@@ -149,6 +149,24 @@ int ekf_set_nis_gate(ekf_handle *h, double threshold);
 int ekf_download_gate_counts(ekf_handle *h, int b0, int count, long long *rejected);
 int ekf_download_innovation_rejections(ekf_handle *h, long long first, int count, int *rejected);
 
+/* Per-trajectory noise constants: trajectories [b0, b0+count) use motion_sigma[i] / meas_sigma[i] (the reference's
+ * MOTION_MODEL_VARIANCE / MEASUREMENT_MODEL_VARIANCE, src/replay_no_ros.py:15-16, :421, :438) instead of the handle's
+ * ekf_config values; a NULL array = the handle's value for that quantity.  Each trajectory's R = diag(s^2, s^2, (s/2)^2) and
+ * Q = diag(q^2, q^2) are formed as ekf_create forms the handle's, so one bank can run a grid of noise pairs (a tuning sweep
+ * on the innovation log's loglik) on every path that predicts or updates.  Stream-ordered like ekf_set_nis_gate: launches
+ * enqueued before the call use the old constants, those enqueued after it the new ones (also between two ekf_stream_run
+ * pieces); pose noise already pending keeps the values it was accumulated with.  The call changes neither mean nor
+ * covariance nor anything that decides scheduling.  While every trajectory's constants equal the handle's (the default, and
+ * again after ekf_set_noise(h, 0, batch, NULL, NULL)) the kernels are the ones without the table: the same bits as a handle
+ * that never called it.
+ * Not affected: the initial P of ekf_create (from the handle's config), ekf_predict_dense (the caller's Q),
+ * landmark_init_var and the association gate.
+ * EKF_ERR_ARG (with the handle usable and nothing changed): a range outside the bank, a non-finite value, motion_sigma < 0,
+ * meas_sigma <= 0 (Q > 0 keeps S invertible).
+ * ekf_get_noise: the values in effect for work enqueued next (a host mirror: does not block); either array may be NULL. */
+int ekf_set_noise(ekf_handle *h, int b0, int count, const double *motion_sigma, const double *meas_sigma);
+int ekf_get_noise(ekf_handle *h, int b0, int count, double *motion_sigma, double *meas_sigma);
+
 /* State augmentation, src/replay_no_ros.py:341-360: append k landmarks (indices must continue the
  * current count), mean = xy[2*i..], variance = landmark_init_var, zero cross terms. */
 int ekf_add_landmarks(ekf_handle *h, int b, int first_index, const double *xy, int k);

@@ -230,6 +230,15 @@ struct ekf_handle : ekf::HostPlan {
   // the gate is on dcfg.gate_rej points at them and dcfg.nis_gate holds the threshold (kernel arguments: every launch
   // enqueued after the call sees the new value).
   unsigned long long* dgate = nullptr;
+  // Per-trajectory noise constants (ekf_set_noise), allocated on the first call: noise_ms / noise_qs are the sigmas in effect
+  // for work enqueued next (ekf_get_noise reads them), dnoise the device table of their rows.  dcfg.noise points at dnoise
+  // while some row differs from the handle's constants, nullptr otherwise (the kernels without the table).  The upload goes
+  // through the pinned hnoise_stage, which is written again only once noise_ev (recorded behind that copy) has completed.
+  std::vector<double> noise_ms, noise_qs;
+  double* dnoise = nullptr;
+  double* hnoise_stage = nullptr;
+  hipEvent_t noise_ev = nullptr;
+  bool noise_ev_used = false;
   // Set when an enqueueing call failed half way (e.g. a launch of the look-ahead failed after the next cadence's solve had
   // already run): the device state of every trajectory is undefined until it is uploaded again; see check_internal
   std::vector<unsigned char> host_bad;
@@ -314,7 +323,7 @@ static void free_all(ekf_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   void* ptrs[] = {h->dP, h->dmu2[0], h->dmu2[1], h->dV, h->dW, h->ddacc2[0], h->ddacc2[1], h->dscratch, h->dn, h->dflags, h->dso, h->dfac,
                   h->d_ring, h->d_stream, h->dF, h->dQ, h->dTmp, h->dPlin, h->dtagmap, h->dneff, h->d_det, h->d_assoc_step, h->dfloor, h->dqueue, h->dready, h->dmbox,
-                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dinnov, h->dinnov_m, h->dgate};
+                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dinnov, h->dinnov_m, h->dgate, h->dnoise};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
   if (h->h_det) (void)hipHostFree(h->h_det);
@@ -326,6 +335,8 @@ static void free_all(ekf_handle* h) {
   }
   if (h->h_flags) (void)hipHostFree(h->h_flags);
   if (h->h_pack) (void)hipHostFree(h->h_pack);
+  if (h->hnoise_stage) (void)hipHostFree(h->hnoise_stage);
+  if (h->noise_ev) (void)hipEventDestroy(h->noise_ev);
   for (auto& e : h->ring_ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : h->prof_pool) (void)hipEventDestroy(e);
   if (h->t0) (void)hipEventDestroy(h->t0);
@@ -876,6 +887,84 @@ extern "C" int ekf_set_nis_gate(ekf_handle* h, double threshold) {
   return EKF_OK;
 }
 
+// ---- per-trajectory noise constants (solve kernels: ekf_kernels.hip solve_body, ekf_cadence.hip k_solve_cad, ekf_small.hip
+// small_step) ----
+// Row of the table for motion sigma s and measurement sigma q: the expressions ekf_create folds the handle's config with, so
+// that a row of the handle's own sigmas is the same doubles as dcfg.rd / dcfg.qd.
+static void noise_row_of(double s, double q, double* r) {
+  r[0] = s * s;                                        // src/replay_no_ros.py:421
+  r[1] = s * s;
+  r[2] = (s / 2) * (s / 2);
+  r[3] = q * q;                                        // :438
+  r[4] = q * q;
+}
+
+extern "C" int ekf_set_noise(ekf_handle* h, int b0, int count, const double* motion_sigma, const double* meas_sigma) {
+  if (!h) return EKF_ERR_ARG;
+  if (b0 < 0 || count <= 0 || b0 > h->batch - count)
+    return fail(h, EKF_ERR_ARG, "ekf_set_noise: trajectory range outside the bank");
+  for (int i = 0; i < count; ++i) {
+    if (motion_sigma && !std::isfinite(motion_sigma[i]))
+      return fail(h, EKF_ERR_ARG, "ekf_set_noise: motion_sigma[" + std::to_string(i) + "] is not finite");
+    if (motion_sigma && motion_sigma[i] < 0.0)
+      return fail(h, EKF_ERR_ARG, "ekf_set_noise: motion_sigma[" + std::to_string(i) + "] < 0");
+    if (meas_sigma && !std::isfinite(meas_sigma[i]))
+      return fail(h, EKF_ERR_ARG, "ekf_set_noise: meas_sigma[" + std::to_string(i) + "] is not finite");
+    if (meas_sigma && !(meas_sigma[i] > 0.0))          // (Q > 0 keeps S invertible: ekf_devfn.h)
+      return fail(h, EKF_ERR_ARG, "ekf_set_noise: meas_sigma[" + std::to_string(i) + "] <= 0");
+  }
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t B = (size_t)h->batch;
+  if (h->noise_ms.empty()) {
+    h->noise_ms.assign(B, h->cfg.motion_sigma);
+    h->noise_qs.assign(B, h->cfg.meas_sigma);
+  }
+  for (int i = 0; i < count; ++i) {
+    h->noise_ms[(size_t)b0 + i] = motion_sigma ? motion_sigma[i] : h->cfg.motion_sigma;
+    h->noise_qs[(size_t)b0 + i] = meas_sigma ? meas_sigma[i] : h->cfg.meas_sigma;
+  }
+  // the table is on while some row differs from the handle's constants; off, every kernel is the one without it
+  std::vector<double> rows(B * NOISE_ROW);
+  bool differs = false;
+  for (size_t b = 0; b < B; ++b) {
+    double* r = rows.data() + b * NOISE_ROW;
+    noise_row_of(h->noise_ms[b], h->noise_qs[b], r);
+    differs |= r[0] != h->dcfg.rd[0] || r[1] != h->dcfg.rd[1] || r[2] != h->dcfg.rd[2] || r[3] != h->dcfg.qd[0] ||
+               r[4] != h->dcfg.qd[1];
+  }
+  if (!differs) {
+    h->dcfg.noise = nullptr;
+    return EKF_OK;
+  }
+  const size_t bytes = sizeof(double) * rows.size();
+  if (!h->dnoise) {
+    HIP_TRY(h, hipMalloc(&h->dnoise, bytes));
+    HIP_TRY(h, hipHostMalloc(&h->hnoise_stage, bytes, hipHostMallocDefault));
+    HIP_TRY(h, hipEventCreateWithFlags(&h->noise_ev, hipEventDisableTiming));
+  }
+  // (stream-ordered: launches enqueued before read the old rows, those enqueued after the new ones; every launch that reads
+  // the table is on h->stream)
+  if (h->noise_ev_used) HIP_TRY(h, hipEventSynchronize(h->noise_ev));   // (the previous upload out of the staging has run)
+  std::memcpy(h->hnoise_stage, rows.data(), bytes);
+  HIP_TRY(h, hipMemcpyAsync(h->dnoise, h->hnoise_stage, bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipEventRecord(h->noise_ev, h->stream));
+  h->noise_ev_used = true;
+  h->dcfg.noise = h->dnoise;
+  return EKF_OK;
+}
+
+extern "C" int ekf_get_noise(ekf_handle* h, int b0, int count, double* motion_sigma, double* meas_sigma) {
+  if (!h) return EKF_ERR_ARG;
+  if (b0 < 0 || count <= 0 || b0 > h->batch - count)
+    return fail(h, EKF_ERR_ARG, "ekf_get_noise: trajectory range outside the bank");
+  for (int i = 0; i < count; ++i) {
+    const size_t b = (size_t)b0 + i;
+    if (motion_sigma) motion_sigma[i] = h->noise_ms.empty() ? h->cfg.motion_sigma : h->noise_ms[b];
+    if (meas_sigma) meas_sigma[i] = h->noise_qs.empty() ? h->cfg.meas_sigma : h->noise_qs[b];
+  }
+  return EKF_OK;
+}
+
 extern "C" int ekf_download_gate_counts(ekf_handle* h, int b0, int count, long long* rejected) {
   if (!h) return EKF_ERR_ARG;
   if (b0 < 0 || count <= 0 || b0 > h->batch - count)
@@ -1018,14 +1107,14 @@ static int enqueue_small(ekf_handle* h, const StepIn* d_in, int nsteps) {
   const int n_hi = h->sizes_dirty ? h->n_max : *std::max_element(h->n.begin(), h->n.end());
   const int out_b = h->fetch_b;                        // (ekf_step_fetch, last pass of its step: see there)
   h->fetch_b = -1;
-  // (this path writes the log itself, and applies the NIS gate in the same instantiations)
+  // (this path writes the log itself, and applies the NIS gate and the noise table in the same instantiations)
   const bool logged = h->dinnov && h->lg_slot >= 0;
   const InnovLog lg = logged ? InnovLog{h->dinnov, h->dinnov_m, h->lg_slot, h->innov_cap, h->lg_jbase} : InnovLog{};
   if (launch_small_stream(h->stream, h->dP, h->dmu2[h->cur], h->dmu2[h->cur ^ 1], h->dn, d_in, h->batch, nsteps, h->dflags,
                           h->dcfg, h->ld, h->pstride, n_hi, out_b >= 0 ? h->h_pack : nullptr, out_b,
                           out_b >= 0 ? reinterpret_cast<unsigned long long*>(h->h_pack + PACK_WORDS - 1) : nullptr,
                           out_b >= 0 ? ++h->fetch_seq : 0ull, plan_small(h, n_hi),
-                          logged || h->dcfg.gate_rej ? &lg : nullptr) != 0)
+                          logged || h->dcfg.gate_rej || h->dcfg.noise ? &lg : nullptr) != 0)
     return fail(h, EKF_ERR_HIP, "small-state launch: hipFuncSetAttribute failed");
   HIP_TRY(h, hipGetLastError());
   h->fetched = out_b >= 0;

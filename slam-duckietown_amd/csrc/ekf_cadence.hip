@@ -137,7 +137,7 @@ __device__ __forceinline__ int cad_positions(const CadPlan& pl, const StepIn* __
 // (ekf_api.hip: enqueue_cadence).  It also down-dates the pose block behind the LAST landmark and records it
 // (CadOut::posefin): with the per-landmark records that is all k_chain_cad needs to form the next cadence's block without
 // this cadence's panel launch and covariance pass.  `gmu` (with gbuf): the mean at the cadence's positions, from k_chain_cad.
-template <bool CHAIN, bool GATE>
+template <bool CHAIN, bool GATE, bool NZ>
 __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restrict__ P,
                                                     const double* __restrict__ mu_in, double* __restrict__ mu_out,
                                                     double* __restrict__ dacc_out, const int* __restrict__ nact,
@@ -350,6 +350,9 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
     o.pad0 = 0;
   }
 
+  // (NZ) this trajectory's row of the noise table (ekf_set_noise), loaded once; the other instantiations read cfg.rd / cfg.qd
+  const NoiseRow nz = NZ ? noise_row(cfg, b) : NoiseRow{};
+
   // ---- the mean wave (wave 1): lane l holds the mean at positions l and 64 + l ----
   double mu0 = 0.0, mu1 = 0.0, y0 = 0.0, y1 = 0.0;
   double rdsum0 = 0.0, rdsum1 = 0.0, rdsum2 = 0.0;     // (wave 1) pose-block noise of the whole cadence
@@ -386,9 +389,9 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
     }
     if (lane < 3) mu0 = lane == 0 ? nx : (lane == 1 ? ny : nth);
     if (do_pred) {
-      rdsum0 += cfg.rd[0];
-      rdsum1 += cfg.rd[1];
-      rdsum2 += cfg.rd[2];
+      rdsum0 += NZ ? nz.rd[0] : cfg.rd[0];
+      rdsum1 += NZ ? nz.rd[1] : cfg.rd[1];
+      rdsum2 += NZ ? nz.rd[2] : cfg.rd[2];
     }
     if (lane == 0) {
       mot[0] = g0;
@@ -517,7 +520,8 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
     if (wave == 0) {
       const bool do_pred = (fS[t] & FLAG_PREDICT) != 0;
       const double g0 = mot[0], g1 = mot[1];
-      const double rd0 = do_pred ? cfg.rd[0] : 0.0, rd1 = do_pred ? cfg.rd[1] : 0.0, rd2 = do_pred ? cfg.rd[2] : 0.0;
+      const double rd0 = do_pred ? (NZ ? nz.rd[0] : cfg.rd[0]) : 0.0, rd1 = do_pred ? (NZ ? nz.rd[1] : cfg.rd[1]) : 0.0,
+                   rd2 = do_pred ? (NZ ? nz.rd[2] : cfg.rd[2]) : 0.0;
       const double s20 = Pc[2][0], s21 = Pc[2][1], p22 = Pc[2][2];
       const int r0 = min(lane, ca - 1), r1 = min(64 + lane, CAD_CS - 1);
       const double p0 = Pc[0][r0], p1 = Pc[1][r0], p2 = Pc[2][r0];
@@ -610,7 +614,7 @@ __global__ __launch_bounds__(64 * CAD_NW) void k_solve_cad(const double* __restr
         double2 hv[5];
 #pragma unroll
         for (int k = 0; k < 5; ++k) hv[k] = hpS[k < 3 ? k : pa + (k - 3)];
-        double S00 = cfg.qd[0], S01 = 0.0, S10 = 0.0, S11 = cfg.qd[1];
+        double S00 = NZ ? nz.qd[0] : cfg.qd[0], S01 = 0.0, S10 = 0.0, S11 = NZ ? nz.qd[1] : cfg.qd[1];
 #pragma unroll
         for (int k = 0; k < 5; ++k) {
           S00 = fma(hv[k].x, h[0][k], S00);
@@ -2170,9 +2174,11 @@ void launch_solve_cad(hipStream_t st, const double* P, const double* mu_in, doub
   const dim3 grid(batch + (colbuf ? col_wgs : 0)), block(64 * CAD_NW);
   with_flag(chain, [&](auto C) {
     with_flag(cfg.gate_rej != nullptr, [&](auto G) {
-      hipLaunchKernelGGL((k_solve_cad<C.value, G.value>), grid, block, 0, st, P, mu_in, mu_out, dacc_out, nact, in, plan, batch, out,
-                         flags, cfg, ld, pstride, gbuf, gparts, colbuf, col_wgs, n_hi, C.value ? gmu : nullptr, C.value ? sync : nullptr,
-                         C.value ? start_sigma : 0u, C.value ? pre : nullptr);
+      with_flag(cfg.noise != nullptr, [&](auto Z) {
+        hipLaunchKernelGGL((k_solve_cad<C.value, G.value, Z.value>), grid, block, 0, st, P, mu_in, mu_out, dacc_out, nact, in, plan,
+                           batch, out, flags, cfg, ld, pstride, gbuf, gparts, colbuf, col_wgs, n_hi, C.value ? gmu : nullptr,
+                           C.value ? sync : nullptr, C.value ? start_sigma : 0u, C.value ? pre : nullptr);
+      });
     });
   });
 }

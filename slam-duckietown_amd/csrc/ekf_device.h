@@ -244,6 +244,19 @@ struct DeviceConfig {
   int enable_measurement_model, enable_circular_interpolation, disable_motion_model;
   double nis_gate;                      // NIS gate threshold (ekf_set_nis_gate; read only while gate_rej is set)
   unsigned long long* gate_rej;         // per trajectory: updates the gate rejected; nullptr = the gate is off
+  const double* noise;                  // per trajectory (ekf_set_noise): NOISE_ROW doubles {rd0, rd1, rd2, qd0, qd1};
+                                        // nullptr = rd / qd above for every trajectory
 };
+
+// Trajectory b's noise constants (ekf_set_noise).  NZ: the instantiations launched while the handle's table is set
+// (cfg.noise != nullptr); the others never call this and read cfg.rd / cfg.qd at their sites as they always have.
+constexpr int NOISE_ROW = 5;
+struct NoiseRow {
+  double rd[3], qd[2];
+};
+__device__ __forceinline__ NoiseRow noise_row(const DeviceConfig& cfg, int b) {
+  const double* r = cfg.noise + (long)NOISE_ROW * b;
+  return NoiseRow{{r[0], r[1], r[2]}, {r[3], r[4]}};
+}
 
 }  // namespace ekf

@@ -130,14 +130,15 @@ struct SolveLds : SolveCore {
   __device__ __forceinline__ FacStd fac_view() { return FacStd{Wc, Vc}; }
 };
 
-template <class Fac, bool GATE>
+template <class Fac, bool GATE, bool NZ>
 __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const double* __restrict__ Pb,
                                            const double* __restrict__ Vb, const double* __restrict__ Wb,
                                            const double* __restrict__ dacc_in, double* __restrict__ dacc_out,
                                            const double* __restrict__ mu_in_b, double* __restrict__ mu_out_b,
                                            const StepIn& s, SolveOut& o, SolveIter* its, unsigned* flag_b,
                                            double* __restrict__ fac_b, const DeviceConfig& cfg, int ld, int kbase,
-                                           bool writer, int neff_eff, unsigned long long* __restrict__ rej_b) {
+                                           bool writer, int neff_eff, unsigned long long* __restrict__ rej_b,
+                                           const NoiseRow& nz) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   auto& Pc = L.Pc;
@@ -407,8 +408,9 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
       if (__any(bad) && lane == 0) atomicOr(flag_b, EKF_FLAG_NONFINITE);
     }
   } else {
-  const double rd0 = do_pred ? cfg.rd[0] : 0.0, rd1 = do_pred ? cfg.rd[1] : 0.0,
-               rd2 = do_pred ? cfg.rd[2] : 0.0;
+  // (NZ: this trajectory's row of the noise table, ekf_set_noise, loaded once by the kernel)
+  const double rd0 = do_pred ? (NZ ? nz.rd[0] : cfg.rd[0]) : 0.0, rd1 = do_pred ? (NZ ? nz.rd[1] : cfg.rd[1]) : 0.0,
+               rd2 = do_pred ? (NZ ? nz.rd[2] : cfg.rd[2]) : 0.0;
   // P'[C,C] = Gc P[C,C] Gc^T + Rt  (:428-430 restricted to C).  Only rows 0,1 and columns 0,1 of the block change
   // (row ops X = Gc P on rows 0,1 with row 2, then column ops X Gc^T on columns 0,1 with column 2 of X), and the
   // gathered block is exactly symmetric: lane r holds P[0..2][r] = P[r][0..2] and produces P'[r][0], P'[r][1],
@@ -495,7 +497,7 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
     double2 hv[5];
 #pragma unroll
     for (int k = 0; k < 5; ++k) hv[k] = hpS[(k < 3) ? k : a + (k - 3)];
-    double S00 = cfg.qd[0], S01 = 0.0, S10 = 0.0, S11 = cfg.qd[1];
+    double S00 = NZ ? nz.qd[0] : cfg.qd[0], S01 = 0.0, S10 = 0.0, S11 = NZ ? nz.qd[1] : cfg.qd[1];
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
       S00 = fma(hv[k].x, h[0][k], S00);
@@ -549,7 +551,7 @@ __device__ __forceinline__ void solve_body(SolveCore& L, const Fac& F, const dou
   }   // wave 0
 }
 
-template <bool GATE>
+template <bool GATE, bool NZ>
 __global__ __launch_bounds__(256) void k_solve(const double* __restrict__ P, const double* __restrict__ V,
                                                const double* __restrict__ W,
                                                const double* __restrict__ dacc_in,
@@ -570,9 +572,10 @@ __global__ __launch_bounds__(256) void k_solve(const double* __restrict__ P, con
   // active bound of this step: what the host baked into the record, raised to the handle's floor (the bound the
   // state had when the enqueueing call started: a stream uploaded earlier knows only its own observations)
   const int neff_eff = min(nact[b], max(in[b].neff, neff_floor[b]));
-  solve_body<FacStd, GATE>(L, L.fac_view(), P + (long)b * pstride, V + (long)b * KTOT * ld, W + (long)b * KTOT * ld, dacc_in + 4 * b,
+  solve_body<FacStd, GATE, NZ>(L, L.fac_view(), P + (long)b * pstride, V + (long)b * KTOT * ld, W + (long)b * KTOT * ld, dacc_in + 4 * b,
              dacc_out + 4 * b, mu_in + (long)b * ld, mu_out + (long)b * ld, in[b], out[b], out[b].it,
-             flags + b, fac + (long)b * FACS, cfg, ld, kbase, true, neff_eff, cfg.gate_rej ? cfg.gate_rej + b : nullptr);
+             flags + b, fac + (long)b * FACS, cfg, ld, kbase, true, neff_eff, cfg.gate_rej ? cfg.gate_rej + b : nullptr,
+             NZ ? noise_row(cfg, b) : NoiseRow{});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -919,7 +922,7 @@ struct Empty {};
 //  two waves per SIMD, and a second __launch_bounds__ argument -- which cannot be left out conditionally -- makes the
 //  compiler move a dynamically indexed private array of the rank-split shape into LDS: 8 KB more per workgroup and
 //  that kernel 2.4 x slower at 8 trajectories.)
-template <int MCAP, int NW, bool KSPLIT, bool SPLIT, bool GATE = false>
+template <int MCAP, int NW, bool KSPLIT, bool SPLIT, bool GATE = false, bool NZ = false>
 __device__ __forceinline__ void panels_mono(double* __restrict__ P, double* __restrict__ V,
                                             double* __restrict__ W, const double* __restrict__ mu_in,
                                             double* __restrict__ mu_out, const int* __restrict__ nact,
@@ -959,9 +962,9 @@ __device__ __forceinline__ void panels_mono(double* __restrict__ P, double* __re
     const int neff_eff = min(n, max(sa.in[b].neff, sa.neff_floor[b]));
     if (solver) {
       if (b == 0 && tid < 8) sa.queue[tid * RS_QSTRIDE] = 0u;   // (see k_solve)
-      solve_body<FacPanel<CC>, GATE>(sL, FacPanel<CC>{sF}, Pb, Vb, Wb, sa.dacc_in + 4 * b, sa.dacc_out + 4 * b, mu_in_b, mu_out_b, sa.in[b],
+      solve_body<FacPanel<CC>, GATE, NZ>(sL, FacPanel<CC>{sF}, Pb, Vb, Wb, sa.dacc_in + 4 * b, sa.dacc_out + 4 * b, mu_in_b, mu_out_b, sa.in[b],
                  sa.out[b], sa.out[b].it, sa.flags + b, sa.fac + (long)b * FACS, sa.cfg, ld, sa.kbase, true, neff_eff,
-                 sa.cfg.gate_rej ? sa.cfg.gate_rej + b : nullptr);
+                 sa.cfg.gate_rej ? sa.cfg.gate_rej + b : nullptr, NZ ? noise_row(sa.cfg, b) : NoiseRow{});
       {
         int ms = ((sa.in[b].flags & FLAG_UPDATE) && sa.cfg.enable_measurement_model) ? sa.in[b].m : 0;
         mailbox_publish(sa.out[b], sa.mbox + b, min(ms, MMAX), sa.ready + b, sa.seq, sa.publish);
@@ -1327,12 +1330,12 @@ __global__ __launch_bounds__(64 * NW) void k_panels(double* __restrict__ P, doub
                                                     const double* __restrict__ fac, int ld, long pstride) {
   panels_mono<MCAP, NW, KSPLIT, false>(P, V, W, mu_in, mu_out, nact, so, fac, ld, pstride, SplitArgs{});
 }
-template <int MCAP, bool GATE>
+template <int MCAP, bool GATE, bool NZ>
 __global__ __launch_bounds__(256, 2) void k_panels_split(double* __restrict__ P, double* __restrict__ V,
                                                          double* __restrict__ W, const double* __restrict__ mu_in,
                                                          double* __restrict__ mu_out, const int* __restrict__ nact,
                                                          int ld, long pstride, SplitArgs sa) {
-  panels_mono<MCAP, 4, false, true, GATE>(P, V, W, mu_in, mu_out, nact, nullptr, nullptr, ld, pstride, sa);
+  panels_mono<MCAP, 4, false, true, GATE, NZ>(P, V, W, mu_in, mu_out, nact, nullptr, nullptr, ld, pstride, sa);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1349,7 +1352,7 @@ __global__ __launch_bounds__(256, 2) void k_panels_split(double* __restrict__ P,
 // smaller linear index (dispatched before it), the wait is bounded, and a timeout raises EKF_FLAG_INTERNAL.
 // ---------------------------------------------------------------------------------------------
 
-template <int MCAP, bool GATE>
+template <int MCAP, bool GATE, bool NZ>
 __global__ __launch_bounds__(256) void k_step_split(double* __restrict__ P, double* __restrict__ V,
                                                     double* __restrict__ W, const double* __restrict__ dacc_in,
                                                     double* __restrict__ dacc_out, const double* __restrict__ mu_in,
@@ -1375,9 +1378,10 @@ __global__ __launch_bounds__(256) void k_step_split(double* __restrict__ P, doub
   const int neff_eff = min(n, max(in[b].neff, neff_floor[b]));
   if (blockIdx.x == 0) {                               // ---- the solve of trajectory b ----
     if (b == 0 && tid < 8) queue[tid * RS_QSTRIDE] = 0u;   // (see k_solve)
-    solve_body<FacStd, GATE>(U.L, U.L.fac_view(), P + (long)b * pstride, V + (long)b * KTOT * ld, W + (long)b * KTOT * ld, dacc_in + 4 * b,
+    solve_body<FacStd, GATE, NZ>(U.L, U.L.fac_view(), P + (long)b * pstride, V + (long)b * KTOT * ld, W + (long)b * KTOT * ld, dacc_in + 4 * b,
                dacc_out + 4 * b, mu_in + (long)b * ld, mu_out + (long)b * ld, in[b], out[b], out[b].it, flags + b,
-               fac + (long)b * FACS, cfg, ld, kbase, true, neff_eff, cfg.gate_rej ? cfg.gate_rej + b : nullptr);
+               fac + (long)b * FACS, cfg, ld, kbase, true, neff_eff, cfg.gate_rej ? cfg.gate_rej + b : nullptr,
+               NZ ? noise_row(cfg, b) : NoiseRow{});
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); // this wave's stores are visible device-wide ...
     __syncthreads();                                   // ... every wave's are ...
     // ... then the word (publish = 0: a test of the panels' bounded wait -- they must time out, not hang)
@@ -2422,12 +2426,12 @@ void launch_solve(hipStream_t st, const double* P, const double* V, const double
                   double* dacc_out, const double* mu_in, double* mu_out, const int* nact, const StepIn* in,
                   SolveOut* out, unsigned* flags, double* fac, const int* neff_floor, unsigned* queue,
                   const DeviceConfig& cfg, int ld, long pstride, int batch, int kbase) {
-  if (cfg.gate_rej)                                    // (the NIS gate is on)
-    hipLaunchKernelGGL(k_solve<true>, dim3(batch), dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out, nact, in,
-                       out, flags, fac, neff_floor, queue, cfg, ld, pstride, kbase);
-  else
-    hipLaunchKernelGGL(k_solve<false>, dim3(batch), dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out, nact, in,
-                       out, flags, fac, neff_floor, queue, cfg, ld, pstride, kbase);
+  with_flag(cfg.gate_rej != nullptr, [&](auto G) {     // (the NIS gate is on)
+    with_flag(cfg.noise != nullptr, [&](auto Z) {      // (the noise table is set)
+      hipLaunchKernelGGL((k_solve<G.value, Z.value>), dim3(batch), dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out,
+                         nact, in, out, flags, fac, neff_floor, queue, cfg, ld, pstride, kbase);
+    });
+  });
 }
 
 // `latency` (ekf_host_plan.h: plan_step): four waves split the pending ranks of 64 indices; else the throughput form, a
@@ -2460,7 +2464,10 @@ void launch_step_split_tp(hipStream_t st, int mcap, double* P, double* V, double
   with_mcap(mcap, [&](auto M) {
     if constexpr (M.value <= 8)                        // (16 landmarks per pass: never planned, see plan_step)
       with_flag(cfg.gate_rej != nullptr, [&](auto G) {
-        hipLaunchKernelGGL((k_panels_split<M.value, G.value>), grid, dim3(256), 0, st, P, V, W, mu_in, mu_out, nact, ld, pstride, sa);
+        with_flag(cfg.noise != nullptr, [&](auto Z) {
+          hipLaunchKernelGGL((k_panels_split<M.value, G.value, Z.value>), grid, dim3(256), 0, st, P, V, W, mu_in, mu_out, nact, ld,
+                             pstride, sa);
+        });
       });
   });
 }
@@ -2472,8 +2479,10 @@ void launch_step_split(hipStream_t st, int mcap, double* P, double* V, double* W
   const dim3 grid(1 + (n_hi + 63) / 64, batch);
   with_mcap(mcap, [&](auto M) {
     with_flag(cfg.gate_rej != nullptr, [&](auto G) {
-      hipLaunchKernelGGL((k_step_split<M.value, G.value>), grid, dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out, nact, in,
-                         out, flags, fac, neff_floor, queue, ready, seq, publish, cfg, ld, pstride, kbase);
+      with_flag(cfg.noise != nullptr, [&](auto Z) {
+        hipLaunchKernelGGL((k_step_split<M.value, G.value, Z.value>), grid, dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out,
+                           nact, in, out, flags, fac, neff_floor, queue, ready, seq, publish, cfg, ld, pstride, kbase);
+      });
     });
   });
 }

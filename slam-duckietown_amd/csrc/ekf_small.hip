@@ -28,13 +28,14 @@ namespace ekf {
 // both conflict-free), `mu` the mean, `hp` / `kk` 2 x n scratch.  LOG: the instantiations that serve the innovation log and
 // the NIS gate.  With `lrow` set, landmark j's index, y, S, NIS and the gate's decision go to lrow[jbase + j] (the innovation
 // log, ekf_innovations.hip).  With the gate on (cfg.gate_rej set), a landmark whose NIS exceeds cfg.nis_gate gets K = 0 -- the
-// down-date and the mean update then subtract and add exact zeros -- and is counted in `nrej`.  The LOG = false
-// instantiations are the kernels as they were.
-template <int NT, int TM, bool LOG>
+// down-date and the mean update then subtract and add exact zeros -- and is counted in `nrej`.  NZ (only with LOG: the
+// instantiations launched while the noise table of ekf_set_noise is set): R and Q are `nz`, this trajectory's row of the table;
+// the others read cfg.rd / cfg.qd.  The LOG = false instantiations are the kernels as they were.
+template <int NT, int TM, bool LOG, bool NZ>
 __device__ __forceinline__ void small_step(double* __restrict__ Pl, double* __restrict__ mu, double* __restrict__ hp,
                                            double* __restrict__ kk, double* __restrict__ sc, const StepIn& s,
                                            const DeviceConfig& cfg, int n, int ps, InnovRec* __restrict__ lrow, int jbase,
-                                           int& nrej) {
+                                           int& nrej, const NoiseRow& nz) {
   const int tid = threadIdx.x;
   const bool do_pred = (s.flags & FLAG_PREDICT) != 0;
   int m = ((s.flags & FLAG_UPDATE) && cfg.enable_measurement_model) ? s.m : 0;
@@ -98,7 +99,7 @@ __device__ __forceinline__ void small_step(double* __restrict__ Pl, double* __re
         Y[r][1] = fma(g1, X[r][2], X[r][1]);
         Y[r][2] = X[r][2];
       }
-      for (int r = 0; r < 3; ++r) Y[r][r] += cfg.rd[r];      // + F^T R F (:421-430)
+      for (int r = 0; r < 3; ++r) Y[r][r] += NZ ? nz.rd[r] : cfg.rd[r];    // + F^T R F (:421-430)
       for (int r = 0; r < 3; ++r)
         for (int c = r; c < 3; ++c) {                        // the upper triangle is authoritative
           Pl[r * ps + c] = Y[r][c];
@@ -141,7 +142,7 @@ __device__ __forceinline__ void small_step(double* __restrict__ Pl, double* __re
     }
     __syncthreads();
     // S = H P H^T + Q (:473), every thread redundantly from the five pairs at sel; closed-form inverse
-    double S00 = cfg.qd[0], S01 = 0.0, S10 = 0.0, S11 = cfg.qd[1];
+    double S00 = NZ ? nz.qd[0] : cfg.qd[0], S01 = 0.0, S10 = 0.0, S11 = NZ ? nz.qd[1] : cfg.qd[1];
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
       const int c = (k < 3) ? k : t + (k - 3);
@@ -233,8 +234,8 @@ __device__ __forceinline__ void small_step(double* __restrict__ Pl, double* __re
 
 // One workgroup per trajectory runs `nsteps` steps: in[k * batch + b], k = 0 .. nsteps - 1.
 // TM: column tiles of 16 the state spans at most (n <= 16 TM): the down-date's loads are unrolled over them.
-// LOG: with lg.rec set, step k is logged in ring row (lg.slot0 + k) % lg.cap (InnovLog, ekf_device.h).
-template <int NT, int TM, bool LOG>
+// LOG: with lg.rec set, step k is logged in ring row (lg.slot0 + k) % lg.cap (InnovLog, ekf_device.h).  NZ: see small_step.
+template <int NT, int TM, bool LOG, bool NZ = false>
 __device__ __forceinline__ void small_stream_body(double* __restrict__ P, const double* __restrict__ mu_in,
                                                   double* __restrict__ mu_out, const int* __restrict__ nact,
                                                   const StepIn* __restrict__ in, int batch, int nsteps,
@@ -292,6 +293,7 @@ __device__ __forceinline__ void small_stream_body(double* __restrict__ P, const 
   if (tid < RW) recw[tid] = reinterpret_cast<const unsigned long long*>(in + b)[tid];
   __syncthreads();
   int nrej = 0;                                             // (NIS gate) landmarks this launch rejected (every thread counts)
+  const NoiseRow nz = NZ ? noise_row(cfg, b) : NoiseRow{};   // (NZ) R and Q diagonals of trajectory b, loaded once
   for (int k = 0; k < nsteps; ++k) {
     unsigned long long nxt = 0;
     const bool more = k + 1 < nsteps;
@@ -308,7 +310,7 @@ __device__ __forceinline__ void small_stream_body(double* __restrict__ P, const 
         }
       }
     }
-    small_step<NT, TM, LOG>(Pl, mu, hp, kk, sc, sk, cfg, n, ps, lrow, lg.jbase, nrej);
+    small_step<NT, TM, LOG, NZ>(Pl, mu, hp, kk, sc, sk, cfg, n, ps, lrow, lg.jbase, nrej, nz);
     if (more && tid < RW) recw[((k + 1) & 1) * RW + tid] = nxt;
     __syncthreads();
   }
@@ -399,20 +401,20 @@ template <int NT, int TM>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_small_stream_two(SMALL_STREAM_ARGS) {
   small_stream_body<NT, TM, false>(SMALL_STREAM_PASS, InnovLog{});
 }
-// The same three forms with the innovation log (ekf_log_innovations) or the NIS gate (ekf_set_nis_gate) on: the filter's
-// arithmetic is the same instructions; the log adds stores behind each landmark's S, the gate a test and, for a rejected
-// landmark, K = 0.
-template <int NT, int TM>
+// The same three forms with the innovation log (ekf_log_innovations), the NIS gate (ekf_set_nis_gate) or the noise table
+// (ekf_set_noise) on: the filter's arithmetic is the same instructions; the log adds stores behind each landmark's S, the gate
+// a test and, for a rejected landmark, K = 0.  NZ: the forms with the noise table (R and Q from trajectory b's row).
+template <int NT, int TM, bool NZ>
 __global__ __launch_bounds__(NT) void k_small_stream_log(SMALL_STREAM_ARGS, InnovLog lg) {
-  small_stream_body<NT, TM, true>(SMALL_STREAM_PASS, lg);
+  small_stream_body<NT, TM, true, NZ>(SMALL_STREAM_PASS, lg);
 }
-template <int NT, int TM>
+template <int NT, int TM, bool NZ>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_small_stream_occ_log(SMALL_STREAM_ARGS, InnovLog lg) {
-  small_stream_body<NT, TM, true>(SMALL_STREAM_PASS, lg);
+  small_stream_body<NT, TM, true, NZ>(SMALL_STREAM_PASS, lg);
 }
-template <int NT, int TM>
+template <int NT, int TM, bool NZ>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_small_stream_two_log(SMALL_STREAM_ARGS, InnovLog lg) {
-  small_stream_body<NT, TM, true>(SMALL_STREAM_PASS, lg);
+  small_stream_body<NT, TM, true, NZ>(SMALL_STREAM_PASS, lg);
 }
 
 int launch_small_stream(hipStream_t st, double* P, const double* mu_in, double* mu_out, const int* nact, const StepIn* in,
@@ -423,9 +425,12 @@ int launch_small_stream(hipStream_t st, double* P, const double* mu_in, double* 
   const size_t bytes = sizeof(double) * ((size_t)n * ps + 5 * (size_t)n + 4) + 2 * sizeof(StepIn);
 #define EKF_SMALL(K, TM)                                                                                                 \
   do {                                                                                                                   \
-    if (lg)                                                                                                              \
-      hipLaunchKernelGGL((K##_log<256, TM>), dim3(batch), dim3(256), bytes, st, P, mu_in, mu_out, nact, in, batch, nsteps, \
-                         flags, cfg, ld, pstride, host_out, out_b, host_seq, out_seq, *lg);                              \
+    if (lg && cfg.noise)                                                                                                 \
+      hipLaunchKernelGGL((K##_log<256, TM, true>), dim3(batch), dim3(256), bytes, st, P, mu_in, mu_out, nact, in, batch,   \
+                         nsteps, flags, cfg, ld, pstride, host_out, out_b, host_seq, out_seq, *lg);                      \
+    else if (lg)                                                                                                         \
+      hipLaunchKernelGGL((K##_log<256, TM, false>), dim3(batch), dim3(256), bytes, st, P, mu_in, mu_out, nact, in, batch,  \
+                         nsteps, flags, cfg, ld, pstride, host_out, out_b, host_seq, out_seq, *lg);                      \
     else                                                                                                                 \
       hipLaunchKernelGGL((K<256, TM>), dim3(batch), dim3(256), bytes, st, P, mu_in, mu_out, nact, in, batch, nsteps, flags, \
                          cfg, ld, pstride, host_out, out_b, host_seq, out_seq);                                          \
@@ -441,7 +446,9 @@ int launch_small_stream(hipStream_t st, double* P, const double* mu_in, double* 
                           2 * sizeof(StepIn);                                                                            \
       if (hipFuncSetAttribute(reinterpret_cast<const void*>(&K<256, TM>), hipFuncAttributeMaxDynamicSharedMemorySize,   \
                               (int)most) != hipSuccess ||                                                                \
-          hipFuncSetAttribute(reinterpret_cast<const void*>(&K##_log<256, TM>),                                          \
+          hipFuncSetAttribute(reinterpret_cast<const void*>(&K##_log<256, TM, false>),                                   \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)most) != hipSuccess ||                    \
+          hipFuncSetAttribute(reinterpret_cast<const void*>(&K##_log<256, TM, true>),                                    \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)most) != hipSuccess)                      \
         return 1;                                                                                                        \
       asked.fetch_or(1ull << dev, std::memory_order_relaxed);                                                            \

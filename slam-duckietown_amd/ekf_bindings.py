@@ -117,6 +117,8 @@ ABI = {
     "ekf_set_nis_gate": (C.c_int, [C.c_void_p, C.c_double]),
     "ekf_download_gate_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
     "ekf_download_innovation_rejections": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, _ip]),
+    "ekf_set_noise": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
+    "ekf_get_noise": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
     "ekf_add_landmarks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int]),
     "ekf_predict": (C.c_int, [C.c_void_p, _dp, _dp]),
     "ekf_update": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _ip, C.c_int]),
@@ -537,6 +539,46 @@ class EkfSlam:
         out = np.zeros(self.batch, dtype=np.int64)
         self._check(self._lib.ekf_download_gate_counts(self._h, 0, self.batch, out.ctypes.data_as(C.POINTER(C.c_longlong))))
         return out
+
+    @staticmethod
+    def noise_arrays(batch: int, motion_sigma=None, meas_sigma=None):
+        """The arrays ``set_noise`` passes to the library: each argument a scalar (every trajectory), a (batch,) array or None
+        (the handle's config value: a NULL array), as float64 (batch,) arrays.  ValueError for another shape, a non-finite
+        value, motion_sigma < 0 or meas_sigma <= 0."""
+        out = []
+        for x, name, floor_ok in ((motion_sigma, "motion_sigma", True), (meas_sigma, "meas_sigma", False)):
+            if x is None:
+                out.append(None)
+                continue
+            a = np.asarray(x, dtype=np.float64)
+            if a.ndim == 0:
+                a = np.full(batch, float(a))
+            elif a.shape != (batch,):
+                raise ValueError(f"set_noise: {name} must be a scalar or shaped ({batch},), got {a.shape}")
+            if not np.all(np.isfinite(a)):
+                raise ValueError(f"set_noise: {name} must be finite")
+            if floor_ok and np.any(a < 0.0):
+                raise ValueError(f"set_noise: {name} must be >= 0")
+            if not floor_ok and np.any(a <= 0.0):
+                raise ValueError(f"set_noise: {name} must be > 0")
+            out.append(np.ascontiguousarray(a))
+        return out[0], out[1]
+
+    def set_noise(self, motion_sigma=None, meas_sigma=None):
+        """Per-trajectory noise constants: trajectory b predicts with motion_sigma[b] and updates with meas_sigma[b] (the
+        reference's MOTION_MODEL_VARIANCE / MEASUREMENT_MODEL_VARIANCE) instead of the handle's config.  Each argument is a
+        scalar, a (B,) array or None (the config's value).  Applies to the work enqueued after the call; ``set_noise()``
+        returns to the handle's constants (the same results as a handle that never called it).  The initial covariance,
+        ``predict_dense`` and the association gate do not use these."""
+        ms, qs = self.noise_arrays(self.batch, motion_sigma, meas_sigma)
+        self._check(self._lib.ekf_set_noise(self._h, 0, self.batch, None if ms is None else _p(ms),
+                                            None if qs is None else _p(qs)))
+
+    def noise(self):
+        """(motion (B,), meas (B,)): the noise sigmas in effect for work enqueued next.  Does not block."""
+        ms, qs = np.empty(self.batch), np.empty(self.batch)
+        self._check(self._lib.ekf_get_noise(self._h, 0, self.batch, _p(ms), _p(qs)))
+        return ms, qs
 
     def state(self, b: int = 0):
         n = self.size(b)

@@ -5,6 +5,8 @@
 * ATE / RMSE of an estimated path against ground truth (what the reference only eyeballs in its plots,
   src/replay_no_ros.py:520-529).
 * NIS of every landmark update from the innovation log (`nis_consistency`): consistency without ground truth.
+* A tuning sweep of the motion and measurement noise (`tune_noise`): a grid of noise pairs as the trajectories of one
+  bank (``EkfSlam.set_noise``), each scored by the log-likelihood of its innovations.
 * NEES of the pose over a batch of Monte-Carlo trajectories with chi-square consistency bounds: the
   batched filter bank (`EkfSlam(batch=B)`) is exactly the Monte-Carlo tool this needs.  `marginal_nees` takes the
   pose and landmark blocks of the whole bank from one `marginals()` call (no covariance pass): cheap enough for
@@ -247,3 +249,87 @@ def nis_consistency(innov, confidence: float = 0.95) -> NisConsistency:
     loglik = -0.5 * np.where(ok, v + logdet, 0.0).sum(axis=(0, 2)) if K else np.zeros(B)
     return NisConsistency(step_anis, bounds(per_step, max(B, 1)), traj_anis, bounds(per_traj, max(K, 1)), gate, above,
                           loglik, total)
+
+
+class NoiseTuning(NamedTuple):
+    motion_sigmas: np.ndarray        # (Gm,) the grid's motion sigmas (rows)
+    meas_sigmas: np.ndarray          # (Gq,) the grid's measurement sigmas (columns)
+    loglik: np.ndarray               # (Gm, Gq) nis_consistency's loglik of each grid point's run
+    traj_anis: np.ndarray            # (Gm, Gq) its time-averaged NIS ...
+    traj_bounds: np.ndarray          # (Gm, Gq, 2) ... with the two-sided bounds at `confidence`
+    best: Tuple[float, float]        # (motion sigma, measurement sigma) of the largest loglik
+    bank_sizes: Tuple[int, ...]      # trajectories of each bank that ran
+
+
+_TUNE_BANK_BYTES = 2 << 30           # (one bank holds the whole grid while its covariances and pending factors fit this)
+
+
+def tune_noise(stream, motion_sigmas, meas_sigmas, mean0, diag0, *, n_max: Optional[int] = None,
+               bank_size: Optional[int] = None, confidence: float = 0.95, device: int = 0, config=None,
+               filter_factory=None) -> NoiseTuning:
+    """Tune the motion and measurement noise (the reference's MOTION_MODEL_VARIANCE / MEASUREMENT_MODEL_VARIANCE,
+    src/replay_no_ros.py:15-16) on one recorded stream by maximum likelihood of the innovations.
+
+    `stream` is ONE trajectory's input as ``EkfSlam.stream_upload`` takes it, (lin, ang, idx, ranges, bearings[, m]) with
+    lin, ang, m of shape (steps,) and idx, ranges, bearings (steps, stride).  The grid is every pair of `motion_sigmas` x
+    `meas_sigmas` (G points); each point is one trajectory of a bank (``set_noise``), all running the same stream from the
+    same mean `mean0`, with the diagonal covariance `diag0` -- (n,), or (G, n) in grid order (row-major: motion, then
+    measurement), e.g. for a pose block tied to the motion sigma.  Banks hold at most `bank_size` trajectories (default: the
+    whole grid in one bank where it fits, else ``sharding.split_banks``' size).  Every bank logs the innovations of the whole
+    run and is scored by ``nis_consistency`` once.  `config` is the handles' EkfConfig (its sigmas are replaced by the grid);
+    `filter_factory(n_max, batch, device, config)` makes the banks (default ``EkfSlam``)."""
+    from . import sharding
+    from .ekf_bindings import EkfConfig, EkfSlam
+    if isinstance(stream, dict):
+        stream = tuple(stream[k] for k in ("lin", "ang", "idx", "ranges", "bearings")) + (stream.get("m"),)
+    if len(stream) not in (5, 6):
+        raise ValueError("tune_noise: stream is (lin, ang, idx, ranges, bearings[, m])")
+    lin, ang = np.asarray(stream[0], dtype=float).reshape(-1), np.asarray(stream[1], dtype=float).reshape(-1)
+    steps = lin.shape[0]
+    idx = np.asarray(stream[2], dtype=np.int32).reshape(steps, -1)
+    zr = np.asarray(stream[3], dtype=float).reshape(idx.shape)
+    zb = np.asarray(stream[4], dtype=float).reshape(idx.shape)
+    m = None if len(stream) < 6 or stream[5] is None else np.asarray(stream[5], dtype=np.int32).reshape(steps)
+    ms_grid = np.asarray(motion_sigmas, dtype=float).reshape(-1)
+    qs_grid = np.asarray(meas_sigmas, dtype=float).reshape(-1)
+    Gm, Gq = len(ms_grid), len(qs_grid)
+    G = Gm * Gq
+    if G == 0 or steps == 0:
+        raise ValueError("tune_noise: an empty grid or stream")
+    mean0 = np.asarray(mean0, dtype=float).reshape(-1)
+    n = mean0.shape[0]
+    diag0 = np.asarray(diag0, dtype=float)
+    if diag0.shape == (n,):
+        diag0 = np.broadcast_to(diag0, (G, n))
+    elif diag0.shape != (G, n):
+        raise ValueError(f"tune_noise: diag0 must be shaped ({n},) or ({G}, {n}), got {diag0.shape}")
+    n_max = n if n_max is None else int(n_max)
+    pm = np.repeat(ms_grid, Gq)                          # grid point g = (motion index g // Gq, measurement index g % Gq)
+    pq = np.tile(qs_grid, Gm)
+    if bank_size is None:
+        per = 8 * (n_max * n_max + 2 * 160 * n_max)      # a trajectory's covariance and pending factors, roughly
+        bank_size = G if G * per <= _TUNE_BANK_BYTES else 32
+    banks = sharding.split_banks(list(range(G)), int(bank_size))
+    cfg = config if config is not None else EkfConfig()
+    make = filter_factory or (lambda n_max_, batch, dev, c: EkfSlam(n_max_, batch=batch, device=dev, config=c))
+    loglik, anis = np.empty(G), np.empty(G)
+    bounds = np.empty((G, 2))
+    for ids in banks:
+        B = len(ids)
+        f = make(n_max, B, device, cfg)
+        try:
+            f.set_noise(pm[ids], pq[ids])
+            for k, g in enumerate(ids):
+                f.set_state_diag(mean0, diag0[g], k)
+            f.log_innovations(steps)
+            f.stream_upload(np.repeat(lin[:, None], B, 1), np.repeat(ang[:, None], B, 1),
+                            np.repeat(idx[:, None, :], B, 1), np.repeat(zr[:, None, :], B, 1), np.repeat(zb[:, None, :], B, 1),
+                            None if m is None else np.repeat(m[:, None], B, 1))
+            f.stream_run(0, steps)
+            nc = nis_consistency(f.innovations(0, steps), confidence)
+        finally:
+            f.close()
+        loglik[ids], anis[ids], bounds[ids] = nc.loglik, nc.traj_anis, nc.traj_bounds
+    g_best = int(np.nanargmax(loglik))
+    return NoiseTuning(ms_grid, qs_grid, loglik.reshape(Gm, Gq), anis.reshape(Gm, Gq), bounds.reshape(Gm, Gq, 2),
+                       (float(pm[g_best]), float(pq[g_best])), tuple(len(b) for b in banks))
