@@ -171,6 +171,18 @@ int ekf_get_noise(ekf_handle *h, int b0, int count, double *motion_sigma, double
  * current count), mean = xy[2*i..], variance = landmark_init_var, zero cross terms. */
 int ekf_add_landmarks(ekf_handle *h, int b, int first_index, const double *xy, int k);
 
+/* Landmark removal: marginalise the k landmarks landmarks[0..k) out of trajectory b (b < 0: out of every trajectory, one
+ * launch).  Exact for a Gaussian: their rows and columns are deleted, the other landmarks keep their order and every index
+ * above a removed one moves down -- mean and covariance equal np.delete, on both axes, of what ekf_download_state returned
+ * just before (bit for bit: the pending update is applied first, then stored values only move, on the device, in place).
+ * The active bound loses 2 per removed landmark below it.  The device tag table maps a removed tag to -1 (seen again, it
+ * is a new landmark appended with landmark_init_var) and renumbers the others; ekf_download_tags drops the removed ones of
+ * the last window.  An uploaded stream is refused by ekf_stream_run (EKF_ERR_STATE) until the next ekf_stream_upload.
+ * The innovation log, gate counts and noise table are not changed.  Blocking.  k = 0 does nothing; removing every landmark
+ * leaves n = 3.  EKF_ERR_ARG (nothing changed): k < 0, an index outside [0, N) of a trajectory concerned, an index twice;
+ * EKF_ERR_STATE under EKF_FLAG_INTERNAL or after a call failed half way (as the downloads). */
+int ekf_remove_landmarks(ekf_handle *h, int b, const int *landmarks, int k);
+
 /* Pinned (page-locked, device-visible) host memory for the arrays a binding hands to its caller.  The reference's loop
  * gets a fresh n x n covariance back from every call (src/replay_no_ros.py:229-237, :482): in freshly allocated pageable
  * memory a 128 MB download first faults in and pins 32 768 pages (5 ms on top of 2.3 ms of PCIe time at N = 2000); the

@@ -62,6 +62,8 @@ void launch_panels_cad(hipStream_t, double*, double*, double*, const double*, do
                        int, unsigned, bool);
 void launch_marginals(hipStream_t, const double*, const double*, const double*, const double*, const int*, const SolveOut*, int,
                       long, int, int, int, int, double*, double*);
+void launch_remove(hipStream_t, int, double*, double*, const int*, const int*, const int*, unsigned*, unsigned*, int, int, int, int,
+                   int, unsigned, int, long);
 }  // namespace ekf
 
 using namespace ekf;
@@ -242,6 +244,13 @@ struct ekf_handle : ekf::HostPlan {
   // Set when an enqueueing call failed half way (e.g. a launch of the look-ahead failed after the next cadence's solve had
   // already run): the device state of every trajectory is undefined until it is uploaded again; see check_internal
   std::vector<unsigned char> host_bad;
+  // ekf_remove_landmarks (allocated on first use): the launch's index tables (src then dst, ld ints each), the row
+  // announcements of k_remove (batch x ld words) and the sequence number the last launch announced with.  stream_stale: the
+  // uploaded stream was validated against sizes a removal has changed since (ekf_stream_run refuses it)
+  int* drm_tab = nullptr;
+  unsigned* drm_flag = nullptr;
+  unsigned rm_seq = 0;
+  bool stream_stale = false;
   std::string err;
 };
 
@@ -323,7 +332,7 @@ static void free_all(ekf_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   void* ptrs[] = {h->dP, h->dmu2[0], h->dmu2[1], h->dV, h->dW, h->ddacc2[0], h->ddacc2[1], h->dscratch, h->dn, h->dflags, h->dso, h->dfac,
                   h->d_ring, h->d_stream, h->dF, h->dQ, h->dTmp, h->dPlin, h->dtagmap, h->dneff, h->d_det, h->d_assoc_step, h->dfloor, h->dqueue, h->dready, h->dmbox,
-                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dinnov, h->dinnov_m, h->dgate, h->dnoise};
+                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dinnov, h->dinnov_m, h->dgate, h->dnoise, h->drm_tab, h->drm_flag};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
   if (h->h_det) (void)hipHostFree(h->h_det);
@@ -1009,6 +1018,84 @@ extern "C" int ekf_add_landmarks(ekf_handle* h, int b, int first_index, const do
   if (int rc = set_size(h, b, n_new)) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return EKF_OK;
+}
+
+// Marginalise landmarks out (k_remove, ekf_remove.hip): apply what is pending, compact P_base's stored triangle and the mean in
+// place, then the bookkeeping -- sizes, active bound and its floor, the device tag table and the last window's tags, the
+// uploaded stream (refused from now on).  b < 0: every trajectory, one launch.
+extern "C" int ekf_remove_landmarks(ekf_handle* h, int b, const int* landmarks, int k) {
+  if (!h) return EKF_ERR_ARG;
+  if (int rc = (b < 0 ? refresh_sizes(h) : check_b(h, b, "ekf_remove_landmarks"))) return rc;
+  const int b0 = b < 0 ? 0 : b, nb = b < 0 ? h->batch : 1;
+  RemovePlan rp;
+  if (const char* why = plan_remove(h, b0, nb, landmarks, k, rp)) return fail(h, EKF_ERR_ARG, why);
+  if (k == 0) return EKF_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (int rc = check_internal(h, b, "ekf_remove_landmarks")) return rc;
+  if (!h->drm_tab) {
+    HIP_TRY(h, hipMalloc(&h->drm_tab, sizeof(int) * 2 * (size_t)h->ld));
+    HIP_TRY(h, hipMalloc(&h->drm_flag, sizeof(unsigned) * (size_t)h->ld * h->batch));
+    HIP_TRY(h, hipMemsetAsync(h->drm_flag, 0, sizeof(unsigned) * (size_t)h->ld * h->batch, h->stream));
+  }
+  if (int rc = flush_pending(h)) return rc;
+  const size_t nt = rp.src.size();
+  HIP_TRY(h, hipMemcpyAsync(h->drm_tab, rp.src.data(), sizeof(int) * nt, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->drm_tab + h->ld, rp.dst.data(), sizeof(int) * nt, hipMemcpyHostToDevice, h->stream));
+  h->rm_seq += 1;
+  if (h->rm_seq == 0) h->rm_seq = 1;                   // (0 is what the announcements start at)
+  launch_remove(h->stream, rp.nq, h->dP, h->dmu2[h->cur], h->dn, h->drm_tab, h->drm_tab + h->ld, h->drm_flag, h->dflags, b0, nb,
+                rp.rows, rp.k2, rp.r0, h->rm_seq, h->ld, h->pstride);
+  HIP_TRY(h, hipGetLastError());
+  // the active bound loses the removed indices below it; everything at or beyond it was, and still is, uncorrelated
+  for (int t = b0; t < b0 + nb; ++t) {
+    int below = 0;
+    for (int i = 0; i < k; ++i) below += (3 + 2 * landmarks[i] < h->neff[t]) ? 2 : 0;
+    h->neff[t] -= below;
+    h->neff_enq[t] = h->neff[t];
+    h->n[t] -= rp.k2;
+  }
+  HIP_TRY(h, hipMemcpyAsync(h->dn, h->n.data(), sizeof(int) * h->batch, hipMemcpyHostToDevice, h->stream));
+  if (int rc = push_floor(h, true)) return rc;
+  // the device tag table (removed tags: -1, seen again = new) and the last window's tags_positions record, renumbered
+  std::vector<int> tm;
+  if (h->dtagmap) {
+    tm.resize((size_t)TAGMAX * nb);
+    HIP_TRY(h, hipMemcpyAsync(tm.data(), h->dtagmap + (size_t)b0 * TAGMAX, sizeof(int) * tm.size(), hipMemcpyDeviceToHost, h->stream));
+  }
+  std::vector<AssocOut> ao;
+  if (h->d_assoc_out) {
+    ao.resize(nb);
+    HIP_TRY(h, hipMemcpyAsync(ao.data(), h->d_assoc_out + b0, sizeof(AssocOut) * nb, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  auto renum = [&](int lm) { return lm < 0 || 3 + 2 * lm >= (int)rp.dst.size() ? lm : (rp.dst[3 + 2 * lm] < 0 ? -1 : (rp.dst[3 + 2 * lm] - 3) / 2); };
+  if (h->dtagmap) {
+    for (int& v : tm) v = renum(v);
+    HIP_TRY(h, hipMemcpyAsync(h->dtagmap + (size_t)b0 * TAGMAX, tm.data(), sizeof(int) * tm.size(), hipMemcpyHostToDevice, h->stream));
+  }
+  if (h->d_assoc_out) {
+    for (AssocOut& a : ao) {
+      int m = 0;
+      for (int i = 0; i < std::min(a.m, AMAX); ++i) {
+        const int lm = renum(a.idx[i]);
+        if (lm < 0) continue;
+        a.idx[m] = lm;
+        a.tag_id[m] = a.tag_id[i];
+        a.xw[m] = a.xw[i];
+        a.yw[m] = a.yw[i];
+        a.err[m] = a.err[i];
+        a.range[m] = a.range[i];
+        a.bearing[m] = a.bearing[i];
+        ++m;
+      }
+      a.m = m;
+      a.n_after = std::max(3, a.n_after - rp.k2);
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->d_assoc_out + b0, ao.data(), sizeof(AssocOut) * nb, hipMemcpyHostToDevice, h->stream));
+  }
+  if (h->stream_steps > 0) h->stream_stale = true;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return check_internal(h, b, "ekf_remove_landmarks");   // (a wait of k_remove that ran into its bound)
 }
 
 // ---- step machinery -------------------------------------------------------------------------
@@ -1776,6 +1863,7 @@ extern "C" int ekf_stream_upload(ekf_handle* h, int steps, const double* lin, co
   HIP_TRY(h, hipMemcpyAsync(h->d_stream, host.data(), sizeof(StepIn) * count, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));      // inputs are resident in HBM from here on
   h->stream_steps = steps;
+  h->stream_stale = false;
   return EKF_OK;
 }
 
@@ -1785,6 +1873,9 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
   if (int rc = refresh_sizes(h)) return rc;
   if (first < 0 || count < 0 || first + count > h->stream_steps)
     return fail(h, EKF_ERR_STATE, "ekf_stream_run: range outside the uploaded stream");
+  if (h->stream_stale)
+    return fail(h, EKF_ERR_STATE, "ekf_stream_run: landmarks were removed (ekf_remove_landmarks) after the stream was uploaded: its "
+                                  "landmark indices and sizes refer to the state before; upload the stream again");
   for (int b = 0; b < h->batch; ++b)                   // the state may have been replaced since the upload
     if (h->stream_maxlm[b] > (h->n[b] - 3) / 2)
       return fail(h, EKF_ERR_STATE, "ekf_stream_run: the uploaded stream observes landmarks the current state does not have");

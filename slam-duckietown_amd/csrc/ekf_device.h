@@ -39,6 +39,7 @@ constexpr int SMALL_BANK_MIN = 128;     // workgroup per CU): N = 64 x 256 10.4 
 // strip never straddles a panel (4096 is a multiple of 64), so a kernel that walks a row strip by strip only needs the
 // strip's column offset p_col(ld, j0) and the row stride p_lds(ld).  V, W and the mean keep the plain stride ld.
 constexpr int PPW = 4096;
+constexpr int RM_THREADS = 256;         // k_remove (ekf_remove.hip): threads per workgroup, one row each
 __host__ __device__ __forceinline__ int p_lds(int ld) { return ld < PPW ? ld : PPW; }
 __host__ __device__ __forceinline__ long p_col(int ld, int j) { return (long)(j >> 12) * ((long)ld * PPW) + (j & (PPW - 1)); }
 // the same as a 32-bit byte offset (ekf_create bounds one covariance by 4 GiB)

@@ -625,6 +625,49 @@ inline const char* validate_obs(const HostPlan* h, int b, const int* idx, int m,
   return nullptr;
 }
 
+// ekf_remove_landmarks (k_remove, ekf_remove.hip): the removal list of trajectories [b0, b0 + nb) checked -- every index
+// inside every trajectory's landmark count, none twice, k >= 0 -- and turned into what the launch reads: src (new state index
+// -> old) and dst (old -> new, -1 removed), one table for all of them (their sizes differ, the list does not), the first
+// removed state index r0, the grid's rows (largest new size) and the columns per thread, nq (a whole row in registers).
+struct RemovePlan {
+  int k2 = 0, r0 = 0, rows = 0, nq = 0;
+  std::vector<int> src, dst;
+};
+inline const char* plan_remove(const HostPlan* h, int b0, int nb, const int* lm, int k, RemovePlan& rp) {
+  if (k < 0) return "ekf_remove_landmarks: k must be >= 0";
+  if (k > 0 && !lm) return "ekf_remove_landmarks: NULL landmarks";
+  int n_hi = 3, nl_lo = h->n[b0];
+  for (int b = b0; b < b0 + nb; ++b) {
+    n_hi = std::max(n_hi, h->n[b]);
+    nl_lo = std::min(nl_lo, (h->n[b] - 3) / 2);
+  }
+  std::vector<unsigned char> gone((size_t)std::max(nl_lo, 1), 0);
+  for (int i = 0; i < k; ++i) {
+    if (lm[i] < 0 || lm[i] >= nl_lo) return "ekf_remove_landmarks: landmark index outside the state";
+    if (gone[lm[i]]) return "ekf_remove_landmarks: landmark index given twice";
+    gone[lm[i]] = 1;
+  }
+  rp.k2 = 2 * k;
+  rp.src.assign((size_t)n_hi, 0);
+  rp.dst.assign((size_t)n_hi, -1);
+  rp.r0 = n_hi;
+  int t = 0;
+  for (int x = 0; x < n_hi; ++x) {
+    const int l = (x - 3) >> 1;
+    if (x >= 3 && l < nl_lo && gone[l]) {
+      rp.r0 = std::min(rp.r0, x);
+      continue;
+    }
+    rp.src[t] = x;
+    rp.dst[x] = t++;
+  }
+  rp.rows = n_hi - rp.k2;
+  rp.nq = 1;
+  while (rp.nq < 64 && RM_THREADS * rp.nq < rp.rows) rp.nq *= 2;
+  if (RM_THREADS * rp.nq < rp.rows) rp.nq = 96;        // (EKF_N_MAX_LIMIT <= 256 x 96)
+  return nullptr;
+}
+
 // Fill StepIn for pass `p` (landmarks [p*MMAX, ...)) of a validated list; `bound` is the trajectory's running
 // active bound (monotone): an observed landmark and everything below it may be correlated from now on.
 inline void fill_step(StepIn& s, int n_b, int& bound, double lin, double ang, int flags, const int* idx,

@@ -30,7 +30,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .frontend import associate
+from .frontend import associate, remap_tag_index
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libekfslam_hip.so"
@@ -120,6 +120,7 @@ ABI = {
     "ekf_set_noise": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
     "ekf_get_noise": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
     "ekf_add_landmarks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int]),
+    "ekf_remove_landmarks": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_int]),
     "ekf_predict": (C.c_int, [C.c_void_p, _dp, _dp]),
     "ekf_update": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _ip, C.c_int]),
     "ekf_step": (C.c_int, [C.c_void_p, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
@@ -595,6 +596,32 @@ class EkfSlam:
         xy = _f64(xy).reshape(-1, 2)
         first = (self.size(b) - 3) // 2
         self._check(self._lib.ekf_add_landmarks(self._h, b, first, _p(xy), xy.shape[0]))
+
+    def remove_landmarks(self, landmarks, b: Optional[int] = 0) -> np.ndarray:
+        """Marginalise the landmarks with these indices out of trajectory b (None: out of every trajectory, one launch).  The
+        others keep their order and the indices above a removed one move down: mean and covariance become ``np.delete`` of
+        ``state(b)`` taken just before, on both axes, bit for bit.  ``tag_index()`` / ``tags_positions()`` follow (a removed
+        tag seen again is a new landmark at the end); an uploaded stream must be uploaded again before ``stream_run``.  The
+        innovation log keeps the indices it logged.  Returns ``old_to_new`` (int32, one entry per old landmark, -1 for the
+        removed ones; with b None for the bank's largest landmark count -- the same map for every trajectory).  Blocking;
+        ``EkfError`` for an index outside the state or given twice, with nothing changed."""
+        lm = np.ascontiguousarray(np.asarray(landmarks, dtype=np.int64).ravel())
+        if lm.size and (lm.min() < np.iinfo(np.int32).min or lm.max() > np.iinfo(np.int32).max):
+            raise EkfError("remove_landmarks: landmark index outside the state")
+        lm = lm.astype(np.int32)
+        traj = range(self.batch) if b is None else (int(b),)
+        n_lm = max((self.size(t) - 3) // 2 for t in traj)
+        self._check(self._lib.ekf_remove_landmarks(self._h, -1 if b is None else int(b), _p(lm, _ip) if lm.size else None,
+                                                   int(lm.size)))
+        keep = np.ones(n_lm, dtype=bool)
+        keep[lm] = False
+        old_to_new = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int32)
+        for t in traj:
+            if t in self._host_index:                  # (untagged landmarks' placeholder ids are made again on the next window)
+                self._host_index[t] = remap_tag_index({k: j for k, j in self._host_index[t].items() if k >= 0}, old_to_new)
+            if t in self._host_tags:
+                self._host_tags[t] = {int(old_to_new[j]): v for j, v in self._host_tags[t].items() if old_to_new[j] >= 0}
+        return old_to_new
 
     def flags(self, b: int = 0) -> int:
         f = C.c_uint()

@@ -251,6 +251,32 @@ def nis_consistency(innov, confidence: float = 0.95) -> NisConsistency:
                           loglik, total)
 
 
+class LandmarkRejections(NamedTuple):
+    applied: np.ndarray              # (B, L) int64: updates of landmark l that trajectory b applied
+    rejected: np.ndarray             # (B, L) int64: ... that the NIS gate rejected (L = largest logged index + 1)
+
+
+def landmark_rejections(innov) -> LandmarkRejections:
+    """Per trajectory and landmark, how many of its logged updates were applied and how many the NIS gate rejected, from an
+    innovation log (``EkfSlam.innovations()``).  A landmark whose later sightings are all rejected was most likely initialised
+    from a bad first detection (a new landmark's first update never reaches the gate): the evidence for
+    ``EkfSlam.remove_landmarks``.  Entries beyond a step's m (index -1) are not counted; a log without rejection data counts
+    every update as applied.  Indices are as they were when each step was logged."""
+    idx = np.asarray(innov.idx)
+    K, B = idx.shape[:2]
+    W = idx.shape[2] if idx.ndim == 3 else 0
+    m = np.minimum(np.asarray(innov.m).reshape(K, B), W)
+    valid = (np.arange(W)[None, None, :] < m[..., None]) & (idx >= 0)
+    rej = np.zeros(idx.shape, dtype=bool) if innov.rejected is None else np.asarray(innov.rejected) == 1
+    L = int(idx[valid].max()) + 1 if valid.any() else 0
+    applied = np.zeros((B, L), dtype=np.int64)
+    rejected = np.zeros((B, L), dtype=np.int64)
+    bb = np.broadcast_to(np.arange(B)[None, :, None], idx.shape)
+    np.add.at(applied, (bb[valid & ~rej], idx[valid & ~rej]), 1)
+    np.add.at(rejected, (bb[valid & rej], idx[valid & rej]), 1)
+    return LandmarkRejections(applied, rejected)
+
+
 class NoiseTuning(NamedTuple):
     motion_sigmas: np.ndarray        # (Gm,) the grid's motion sigmas (rows)
     meas_sigmas: np.ndarray          # (Gq,) the grid's measurement sigmas (columns)

@@ -79,3 +79,17 @@ def associate(detections, tag_index: Dict[int, int], pose, gate_range: float = 1
         brg = np.arctan2(y_r, x_r)
         result[lm] = [x0 + rng * np.cos(brg + th), y0 + rng * np.sin(brg + th), err, tid, rng, brg]
     return result
+
+
+def remap_tag_index(tag_index: Dict[int, int], old_to_new) -> Dict[int, int]:
+    """TAG_INDEX after ``EkfSlam.remove_landmarks``: the tags of removed landmarks (``old_to_new[j] == -1``) dropped, every
+    other tag renumbered -- values stay 0..len-1 in first-sighting order.  For callers that keep their own TAG_INDEX with
+    ``associate``; a removed tag seen again gets the next index, a new landmark."""
+    o2n = np.asarray(old_to_new)
+    out = {}
+    for tag, j in tag_index.items():
+        if not 0 <= j < len(o2n):
+            raise ValueError(f"remap_tag_index: landmark index {j} of tag {tag} outside old_to_new ({len(o2n)} landmarks)")
+        if o2n[j] >= 0:
+            out[tag] = int(o2n[j])
+    return out
