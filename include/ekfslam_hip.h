@@ -131,6 +131,29 @@ int ekf_log_innovations(ekf_handle *h, int capacity);
 int ekf_innovation_steps(ekf_handle *h, long long *logged);
 int ekf_download_innovations(ekf_handle *h, long long first, int count, int *m, int *idx, double *y, double *S, double *nis);
 
+/* Pose log: the pose mean [x, y, theta] and the pose block P[0:3, 0:3] as they stand AFTER every step -- after its prediction
+ * and its last landmark update, motion noise included, NIS-gate rejections honoured: the trajectory with its covariance over
+ * time (ATE, pose NEES against ground truth) out of an uploaded stream, which otherwise returns only its last pose.  Off by
+ * default.  The log is a device ring of the last `capacity` logged steps, written on every path (per-step kernels, single-launch
+ * steps, fused cadences incl. chained and look-ahead runs, the small-state path); switching it on or off changes nothing about
+ * the filter (same bits, same scheduling and counters).  A logged STEP is one call of ekf_predict, ekf_update, ekf_step,
+ * ekf_step_fetch or ekf_step_detections, or one stream step of ekf_stream_run / ekf_run_stream, whether or not it observes
+ * anything.  A step with more than EKF_MMAX landmarks is ONE row (the state after its last pass); a stream step cut by a
+ * cadence boundary is one row, written by the cadence that finishes it.  Nothing else writes a row (ekf_add_landmarks,
+ * ekf_remove_landmarks, ekf_predict_dense, uploads).  This counter is INDEPENDENT of the innovation log's: a lone ekf_predict
+ * is a row here and no step there; both logs may be on together.
+ * ekf_log_poses: capacity > 0 allocates the ring (capacity x batch x 12 doubles) and restarts the count at 0; 0 switches the
+ * log off and frees it (after a stream synchronisation).
+ * ekf_pose_steps: steps logged since the log was switched on.
+ * ekf_download_poses: steps [first, first + count) into pose (count x batch x 3) and cov (count x batch x 9, row-major,
+ * exactly symmetric; may be NULL).  Blocking and stream-ordered behind everything enqueued; runs no covariance pass or mirror
+ * and changes nothing that decides later scheduling.  The last row equals ekf_download_mean's pose bit for bit and a flushed
+ * ekf_download_block(0, 0, 3, 3) to rounding.  EKF_ERR_ARG if the range is not inside the last `capacity` logged steps,
+ * EKF_ERR_STATE with the log off. */
+int ekf_log_poses(ekf_handle *h, int capacity);
+int ekf_pose_steps(ekf_handle *h, long long *logged);
+int ekf_download_poses(ekf_handle *h, long long first, int count, double *pose, double *cov);
+
 /* NIS validation gate: landmark update j is REJECTED when NIS = y^T S^-1 y > threshold, with the y and S^-1 the filter is about
  * to use -- after the step's prediction and the updates before it, the same NIS the innovation log reports.  A rejected update
  * moves neither mean nor covariance; later updates see the state as if it had never been given.  It still takes its 2 rank

@@ -39,14 +39,16 @@ void launch_innov_step(hipStream_t, const StepIn*, const SolveOut*, int, int, in
 void launch_innov_cad(hipStream_t, const StepIn*, const CadPlan*, const CadOut*, int, int, int, const InnovLog&);
 int launch_small_stream(hipStream_t, double*, const double*, double*, const int*, const StepIn*, int, int, unsigned*,
                         const DeviceConfig&, int, long, int, double*, int, unsigned long long*, unsigned long long, int,
-                        const InnovLog*);
+                        const InnovLog*, const PoseLog*);
+void launch_pose_step(hipStream_t, const double*, const double*, const double*, const double*, const double*, int, long, int, int,
+                      const PoseLog&);
 void launch_associate(hipStream_t, const DetIn*, int*, int*, int*, double*, double*, double*, double*, StepIn*,
                       AssocOut*, unsigned*, const AssocConfig&, int, long, int, int, int);
 void launch_fill_diag(hipStream_t, double*, int, int, const double*);
 int dense_propagate(hipStream_t, double* P, double* tmp, const double* F, const double* Q, int n, int ld);
 void launch_solve_cad(hipStream_t, const double*, const double*, double*, double*, const int*, const StepIn*, const CadPlan*, int,
                       CadOut*, unsigned*, const DeviceConfig&, int, long, const double*, int, double*, int, int, bool, const double*,
-                      unsigned*, unsigned, const CadPre*);
+                      unsigned*, unsigned, const CadPre*, const PoseLog*);
 void launch_chain_cad(hipStream_t, const double*, const double*, const double*, const double*, const CadOut*, const StepIn*,
                       const CadPlan*, int, const DeviceConfig&, int, long, double*, double*, double*, double*, unsigned*, unsigned,
                       unsigned*, int, unsigned, const CadPre*, CadPre*, const CadPlan*, bool);
@@ -228,6 +230,14 @@ struct ekf_handle : ekf::HostPlan {
   long long innov_steps = 0;
   long lg_slot = -1, lg_tslot = -1;
   int lg_jbase = 0;
+  // The pose log (ekf_log_poses; nullptr: off): a ring of pose_cap step rows (batch x POSE_ROW doubles each), pose_steps steps
+  // logged so far; a counter of its own -- a lone prediction is a row here and none in the innovation log.  While an entry
+  // point enqueues a step, pl_slot is its ring row (-1: nothing is logged); ekf_stream_run logs stream step t in row
+  // (pl_tslot + t) % pose_cap.
+  double* dpose = nullptr;
+  int pose_cap = 0;
+  long long pose_steps = 0;
+  long pl_slot = -1, pl_tslot = -1;
   // The NIS gate (ekf_set_nis_gate): per-trajectory rejection counters, allocated when the gate is first switched on.  While
   // the gate is on dcfg.gate_rej points at them and dcfg.nis_gate holds the threshold (kernel arguments: every launch
   // enqueued after the call sees the new value).
@@ -332,7 +342,7 @@ static void free_all(ekf_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   void* ptrs[] = {h->dP, h->dmu2[0], h->dmu2[1], h->dV, h->dW, h->ddacc2[0], h->ddacc2[1], h->dscratch, h->dn, h->dflags, h->dso, h->dfac,
                   h->d_ring, h->d_stream, h->dF, h->dQ, h->dTmp, h->dPlin, h->dtagmap, h->dneff, h->d_det, h->d_assoc_step, h->dfloor, h->dqueue, h->dready, h->dmbox,
-                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dinnov, h->dinnov_m, h->dgate, h->dnoise, h->drm_tab, h->drm_flag};
+                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dinnov, h->dinnov_m, h->dgate, h->dnoise, h->drm_tab, h->drm_flag, h->dpose};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
   if (h->h_det) (void)hipHostFree(h->h_det);
@@ -780,6 +790,67 @@ extern "C" int ekf_download_marginals(ekf_handle* h, int b0, int count, double* 
   return EKF_OK;
 }
 
+// ---- the pose log (ekf_pose_log.hip) ----
+extern "C" int ekf_log_poses(ekf_handle* h, int capacity) {
+  if (!h) return EKF_ERR_ARG;
+  if (capacity < 0) return fail(h, EKF_ERR_ARG, "ekf_log_poses: capacity must be >= 0");
+  const size_t rows = (size_t)capacity * h->batch;
+  if (capacity > 0 && rows * POSE_ROW * sizeof(double) > ((size_t)1 << 36))
+    return fail(h, EKF_ERR_ARG, "ekf_log_poses: the ring would exceed 64 GiB");
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (h->dpose) {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // (launches in flight still write the old ring)
+    HIP_TRY(h, hipFree(h->dpose));
+    h->dpose = nullptr;
+  }
+  h->pose_cap = 0;
+  h->pose_steps = 0;
+  if (capacity == 0) return EKF_OK;
+  if (hipMalloc(&h->dpose, sizeof(double) * rows * POSE_ROW) != hipSuccess) {
+    (void)hipGetLastError();
+    h->dpose = nullptr;
+    return fail(h, EKF_ERR_HIP, "ekf_log_poses: cannot allocate the ring of " + std::to_string(capacity) + " steps");
+  }
+  h->pose_cap = capacity;
+  return EKF_OK;
+}
+
+extern "C" int ekf_pose_steps(ekf_handle* h, long long* logged) {
+  if (!h || !logged) return EKF_ERR_ARG;
+  *logged = h->pose_steps;
+  return EKF_OK;
+}
+
+// The range rules are read_log's (the innovation log below).  The block is returned exactly symmetric: its upper triangle, mirrored.
+extern "C" int ekf_download_poses(ekf_handle* h, long long first, int count, double* pose, double* cov) {
+  if (!h) return EKF_ERR_ARG;
+  if (!h->dpose) return fail(h, EKF_ERR_STATE, "ekf_download_poses: the pose log is off (ekf_log_poses)");
+  if (count < 0 || first < 0 || first + count > h->pose_steps || first < h->pose_steps - h->pose_cap)
+    return fail(h, EKF_ERR_ARG, "ekf_download_poses: steps [" + std::to_string(first) + ", " + std::to_string(first + count) +
+                                    ") are not among the last " + std::to_string(h->pose_cap) + " of the " +
+                                    std::to_string(h->pose_steps) + " logged");
+  if (count > 0 && !pose) return fail(h, EKF_ERR_ARG, "ekf_download_poses: NULL pose");
+  HIP_TRY(h, hipSetDevice(h->device));
+  const long B = h->batch;
+  std::vector<double> hr((size_t)count * B * POSE_ROW);
+  for (long done = 0; done < count;) {                 // (the range may wrap round the ring: two pieces at most)
+    const long slot = (long)((first + done) % h->pose_cap);
+    const long piece = std::min<long long>(count - done, h->pose_cap - slot);
+    HIP_TRY(h, hipMemcpyAsync(hr.data() + done * B * POSE_ROW, h->dpose + slot * B * POSE_ROW, sizeof(double) * piece * B * POSE_ROW,
+                              hipMemcpyDeviceToHost, h->stream));
+    done += piece;
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (size_t q = 0; q < (size_t)count * B; ++q) {
+    const double* r = hr.data() + q * POSE_ROW;
+    for (int i = 0; i < 3; ++i) pose[q * 3 + i] = r[i];
+    if (cov)
+      for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) cov[q * 9 + 3 * i + j] = r[3 + 3 * std::min(i, j) + std::max(i, j)];
+  }
+  return EKF_OK;
+}
+
 // ---- the innovation log (ekf_innovations.hip) ----
 extern "C" int ekf_log_innovations(ekf_handle* h, int capacity) {
   if (!h) return EKF_ERR_ARG;
@@ -1197,11 +1268,14 @@ static int enqueue_small(ekf_handle* h, const StepIn* d_in, int nsteps) {
   // (this path writes the log itself, and applies the NIS gate and the noise table in the same instantiations)
   const bool logged = h->dinnov && h->lg_slot >= 0;
   const InnovLog lg = logged ? InnovLog{h->dinnov, h->dinnov_m, h->lg_slot, h->innov_cap, h->lg_jbase} : InnovLog{};
+  // (the pose log likewise: every pass of a step writes the step's row, the last one last)
+  const bool posed = h->dpose && h->pl_slot >= 0;
+  const PoseLog plg = posed ? PoseLog{h->dpose, h->pl_slot, h->pose_cap} : PoseLog{};
   if (launch_small_stream(h->stream, h->dP, h->dmu2[h->cur], h->dmu2[h->cur ^ 1], h->dn, d_in, h->batch, nsteps, h->dflags,
                           h->dcfg, h->ld, h->pstride, n_hi, out_b >= 0 ? h->h_pack : nullptr, out_b,
                           out_b >= 0 ? reinterpret_cast<unsigned long long*>(h->h_pack + PACK_WORDS - 1) : nullptr,
                           out_b >= 0 ? ++h->fetch_seq : 0ull, plan_small(h, n_hi),
-                          logged || h->dcfg.gate_rej || h->dcfg.noise ? &lg : nullptr) != 0)
+                          logged || h->dcfg.gate_rej || h->dcfg.noise ? &lg : nullptr, posed ? &plg : nullptr) != 0)
     return fail(h, EKF_ERR_HIP, "small-state launch: hipFuncSetAttribute failed");
   HIP_TRY(h, hipGetLastError());
   h->fetched = out_b >= 0;
@@ -1215,6 +1289,17 @@ static void log_pass(ekf_handle* h, const StepIn* d_in) {
   if (!h->dinnov || h->lg_slot < 0) return;
   launch_innov_step(h->stream, d_in, h->dso, h->dcfg.enable_measurement_model, h->dcfg.gate_rej != nullptr, h->batch,
                     InnovLog{h->dinnov, h->dinnov_m, h->lg_slot, h->innov_cap, h->lg_jbase});
+}
+
+// The pose log's row of a step that ran on the per-step kernels: formed from what is in memory behind the step's last pass
+// (k_pose_step: the new mean, P_base, the pending ranks and noise, as ekf_download_marginals reads them).  The small-state
+// path has written the row itself.
+static int log_pose_step(ekf_handle* h) {
+  if (!h->dpose || h->pl_slot < 0 || small_path(h)) return EKF_OK;
+  launch_pose_step(h->stream, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dmu2[h->cur], h->ld, h->pstride, (h->pending_k + 3) & ~3,
+                   h->batch, PoseLog{h->dpose, h->pl_slot, h->pose_cap});
+  HIP_TRY(h, hipGetLastError());
+  return EKF_OK;
 }
 
 // Enqueue one device pass with inputs already at d_in (StepIn[batch]); m_hi = max m over the batch.
@@ -1334,6 +1419,9 @@ static void log_cadence(ekf_handle* h, const CadPlan* dpl, const CadOut* co) {
 static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_presolved) {
   *next_presolved = false;
   const RunPlan& rp = h->run_plan;
+  // (the pose log: k_solve_cad_plog writes stream step t's row (pl_tslot + t) % pose_cap itself; nullptr: off)
+  const PoseLog plg_on{h->dpose, h->pl_tslot, h->pose_cap};
+  const PoseLog* plg = h->dpose && h->pl_tslot >= 0 ? &plg_on : nullptr;
   const int n_hi = *std::max_element(h->n.begin(), h->n.end());
   const CadPlan* dpl = h->dplan2[h->plan_cur] + (size_t)c * h->batch;
   for (int i = 0; i < 2; ++i)
@@ -1359,7 +1447,7 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     ProfBracket pb;
     if (int rc = prof_open(h, 1, h->stream, &pb)) return rc;
     launch_solve_cad(h->stream, h->dP, mu_in, mu_out, h->ddacc2[h->dcur ^ 1], h->dn, h->d_stream, dpl, h->batch, dcad,
-                     h->dflags, h->dcfg, h->ld, h->pstride, nullptr, 0, colbuf, n_hi, cp.col_wgs, h->chain_run, nullptr, nullptr, 0u, nullptr);
+                     h->dflags, h->dcfg, h->ld, h->pstride, nullptr, 0, colbuf, n_hi, cp.col_wgs, h->chain_run, nullptr, nullptr, 0u, nullptr, plg);
     if (int rc = prof_close(h, &pb)) return rc;
     log_cadence(h, dpl, dcad);
   }
@@ -1395,7 +1483,7 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     if (int rc2 = prof_open(h, 1, h->stream, &pbs)) return rc2;
     launch_solve_cad(h->stream, h->dP, h->dmu2[h->cur ^ 1], h->dmu2[h->cur], h->ddacc2[h->dcur], h->dn, h->d_stream, dpl2,
                      h->batch, h->dcad2[h->cpar ^ 1], h->dflags, h->dcfg, h->ld, h->pstride, h->dgbuf, 1, nullptr, n_hi, 0, true, h->dgmu,
-                     h->dsync, h->sigma, pre_in);
+                     h->dsync, h->sigma, pre_in, plg);
     if (int rc2 = prof_close(h, &pbs)) return rc2;
     log_cadence(h, dpl2, h->dcad2[h->cpar ^ 1]);       // (enqueued before the gate: it waits for nothing)
     // From here on the next cadence's solve overwrites the pose mean and the pending-noise buffer: a failure below cannot be
@@ -1475,7 +1563,7 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     if (int rc2 = prof_open(h, 1, h->stream, &pb)) return rc2;
     launch_solve_cad(h->stream, h->dP, h->dmu2[h->cur], h->dmu2[h->cur ^ 1], h->ddacc2[h->dcur ^ 1], h->dn, h->d_stream, dpl2,
                      h->batch, h->dcad2[h->cpar], h->dflags, h->dcfg, h->ld, h->pstride, h->dgbuf, (kb + 7) / 8, nullptr, n_hi, 0,
-                     h->chain_run, nullptr, nullptr, 0u, nullptr);
+                     h->chain_run, nullptr, nullptr, 0u, nullptr, plg);
     if (int rc2 = prof_close(h, &pb)) return rc2;
   }
   log_cadence(h, dpl2, h->dcad2[h->cpar]);
@@ -1527,6 +1615,8 @@ struct LogScope {
     h->lg_slot = -1;
     h->lg_tslot = -1;
     h->lg_jbase = 0;
+    h->pl_slot = -1;
+    h->pl_tslot = -1;
   }
 };
 
@@ -1555,6 +1645,7 @@ static int do_step(ekf_handle* h, int base_flags, const double* lin, const doubl
   if (int rc = push_floor(h, false)) return rc;
   const int passes = std::max(1, (m_hi + MMAX - 1) / MMAX);
   const bool logged = h->dinnov && upd;                // (a lone prediction is not a logged step)
+  h->pl_slot = h->dpose ? (long)(h->pose_steps % h->pose_cap) : -1;   // (the pose log: every call is a row)
   for (int p = 0; p < passes; ++p) {
     h->lg_slot = logged ? (long)(h->innov_steps % h->innov_cap) : -1;
     h->lg_jbase = MMAX * p;
@@ -1587,6 +1678,8 @@ static int do_step(ekf_handle* h, int base_flags, const double* lin, const doubl
   }
   h->fetch_b = -1;
   if (logged) h->innov_steps += 1;
+  if (int rc = log_pose_step(h)) return rc;
+  if (h->dpose) h->pose_steps += 1;
   return EKF_OK;
 }
 
@@ -1655,6 +1748,7 @@ extern "C" int ekf_step_detections(ekf_handle* h, const double* lin, const doubl
   if (!h->cfg.enable_measurement_model) m_hi = 0;
   LogScope log_scope{h};
   h->lg_slot = h->dinnov ? (long)(h->innov_steps % h->innov_cap) : -1;
+  h->pl_slot = h->dpose ? (long)(h->pose_steps % h->pose_cap) : -1;
   // the host's view of the active bound must be on the device before the first device-side window
   if (!h->sizes_dirty)
     HIP_TRY(h, hipMemcpyAsync(h->dneff, h->neff.data(), sizeof(int) * h->batch, hipMemcpyHostToDevice, h->stream));
@@ -1678,6 +1772,8 @@ extern "C" int ekf_step_detections(ekf_handle* h, const double* lin, const doubl
   if (m_hi > MMAX)
     if (int rc = enqueue_pass(h, h->d_assoc_step + h->batch, m_hi - MMAX)) return rc;
   if (h->dinnov) h->innov_steps += 1;
+  if (int rc = log_pose_step(h)) return rc;
+  if (h->dpose) h->pose_steps += 1;
   return EKF_OK;
 }
 
@@ -1885,7 +1981,12 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
   LogScope log_scope{h};
   const long cap = h->innov_cap;
   if (h->dinnov) h->lg_tslot = (long)(((h->innov_steps - first) % cap + cap) % cap);
-  auto log_at = [&](int k) { h->lg_slot = h->dinnov ? (h->lg_tslot + k) % cap : -1; };
+  const long pcap = h->pose_cap;                       // (the pose log: the same numbering on its own counter)
+  if (h->dpose) h->pl_tslot = (long)(((h->pose_steps - first) % pcap + pcap) % pcap);
+  auto log_at = [&](int k) {
+    h->lg_slot = h->dinnov ? (h->lg_tslot + k) % cap : -1;
+    h->pl_slot = h->dpose ? (h->pl_tslot + k) % pcap : -1;
+  };
   if (small_path(h) && count > 0) {
     // the whole range as ONE launch (in pieces of 4096 steps: a bounded kernel), P resident in LDS across all its steps
     for (int k = first; k < first + count; k += 4096) {
@@ -1896,6 +1997,7 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
       h->neff[b] = std::max(h->neff[b], std::min(h->n[b], h->stream_own[(size_t)(first + count - 1) * h->batch + b]));
     h->neff_enq = h->neff;
     if (h->dinnov) h->innov_steps += count;
+    if (h->dpose) h->pose_steps += count;
     return EKF_OK;
   }
   for (int k = first; k < first + count;) {
@@ -1949,9 +2051,11 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
       h->neff_enq[b] = std::min(h->n[b], std::max(h->floor_host[b], h->stream_own[(size_t)k * h->batch + b]));
     log_at(k);
     if (int rc = enqueue_pass(h, h->d_stream + (size_t)k * h->batch, h->stream_mhi[k])) return rc;
+    if (int rc = log_pose_step(h)) return rc;
     ++k;
   }
   if (h->dinnov) h->innov_steps += count;
+  if (h->dpose) h->pose_steps += count;
   if (count > 0)
     for (int b = 0; b < h->batch; ++b)
       h->neff[b] = std::max(h->neff[b], std::min(h->n[b], h->stream_own[(size_t)(first + count - 1) * h->batch + b]));

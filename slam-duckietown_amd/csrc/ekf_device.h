@@ -226,6 +226,15 @@ struct InnovLog {
   long slot0;
   int cap, jbase;
 };
+// The pose log (ekf_log_poses): a device ring of `cap` step rows, each batch x POSE_ROW doubles: the pose mean x, y, theta and
+// the pose block P[0:3, 0:3] row-major, as they stand after the step.  PoseLog names where a launch writes: its step t goes to
+// ring row (slot0 + t) % cap -- a one-step launch has t = 0.  row == nullptr: the launch logs no pose.
+constexpr int POSE_ROW = 12;
+struct PoseLog {
+  double* row;          // [cap][batch][POSE_ROW]
+  long slot0;
+  int cap;
+};
 // y^T S^-1 y with S^-1 = [[a, b], [c, d]]
 __host__ __device__ __forceinline__ double innov_nis(double y0, double y1, double a, double b, double c, double d) {
   return y0 * (a * y0 + b * y1) + y1 * (c * y0 + d * y1);

@@ -235,14 +235,17 @@ __device__ __forceinline__ void small_step(double* __restrict__ Pl, double* __re
 // One workgroup per trajectory runs `nsteps` steps: in[k * batch + b], k = 0 .. nsteps - 1.
 // TM: column tiles of 16 the state spans at most (n <= 16 TM): the down-date's loads are unrolled over them.
 // LOG: with lg.rec set, step k is logged in ring row (lg.slot0 + k) % lg.cap (InnovLog, ekf_device.h).  NZ: see small_step.
-template <int NT, int TM, bool LOG, bool NZ = false>
+// PLOG (the pose log, ekf_log_poses; only with LOG): behind step k the pose mean and the pose block go from LDS to ring row
+// (plg.slot0 + k) % plg.cap (PoseLog), twelve lanes' stores and one more barrier per step -- the next step's prediction
+// rewrites both.  Rows a later step of the same launch overwrites (cap < nsteps) are skipped.
+template <int NT, int TM, bool LOG, bool NZ = false, bool PLOG = false>
 __device__ __forceinline__ void small_stream_body(double* __restrict__ P, const double* __restrict__ mu_in,
                                                   double* __restrict__ mu_out, const int* __restrict__ nact,
                                                   const StepIn* __restrict__ in, int batch, int nsteps,
                                                   unsigned* __restrict__ flags, const DeviceConfig& cfg, int ld, long pstride,
                                                   double* __restrict__ host_out, int out_b,
                                                   unsigned long long* __restrict__ host_seq, unsigned long long out_seq,
-                                                  const InnovLog& lg) {
+                                                  const InnovLog& lg, const PoseLog& plg = PoseLog{}) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int n = min(min(nact[b], SMALL_N_MAX_BANK), 16 * TM);
@@ -313,6 +316,13 @@ __device__ __forceinline__ void small_stream_body(double* __restrict__ P, const 
     small_step<NT, TM, LOG, NZ>(Pl, mu, hp, kk, sc, sk, cfg, n, ps, lrow, lg.jbase, nrej, nz);
     if (more && tid < RW) recw[((k + 1) & 1) * RW + tid] = nxt;
     __syncthreads();
+    if constexpr (PLOG) {
+      if (k >= nsteps - plg.cap && tid < POSE_ROW) {
+        const int e = tid < 3 ? 0 : tid - 3;
+        plg.row[((long)((plg.slot0 + k) % plg.cap) * batch + b) * POSE_ROW + tid] = tid < 3 ? mu[tid] : Pl[(e / 3) * ps + e % 3];
+      }
+      __syncthreads();
+    }
   }
   if (nrej && tid == 0) cfg.gate_rej[b] += (unsigned long long)nrej;
   bool bad = false;
@@ -417,15 +427,35 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   small_stream_body<NT, TM, true, NZ>(SMALL_STREAM_PASS, lg);
 }
 
+// ... and with the pose log (ekf_log_poses) on as well: the LOG forms that also write a pose row behind every step
+template <int NT, int TM, bool NZ>
+__global__ __launch_bounds__(NT) void k_small_stream_plog(SMALL_STREAM_ARGS, InnovLog lg, PoseLog plg) {
+  small_stream_body<NT, TM, true, NZ, true>(SMALL_STREAM_PASS, lg, plg);
+}
+template <int NT, int TM, bool NZ>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_small_stream_occ_plog(SMALL_STREAM_ARGS, InnovLog lg, PoseLog plg) {
+  small_stream_body<NT, TM, true, NZ, true>(SMALL_STREAM_PASS, lg, plg);
+}
+template <int NT, int TM, bool NZ>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_small_stream_two_plog(SMALL_STREAM_ARGS, InnovLog lg, PoseLog plg) {
+  small_stream_body<NT, TM, true, NZ, true>(SMALL_STREAM_PASS, lg, plg);
+}
+
 int launch_small_stream(hipStream_t st, double* P, const double* mu_in, double* mu_out, const int* nact, const StepIn* in,
                         int batch, int nsteps, unsigned* flags, const DeviceConfig& cfg, int ld, long pstride, int n_hi,
                         double* host_out, int out_b, unsigned long long* host_seq, unsigned long long out_seq, int form,
-                        const InnovLog* lg) {   // form: ekf_host_plan.h's SmallForm (plan_small)
+                        const InnovLog* lg, const PoseLog* plg) {   // form: ekf_host_plan.h's SmallForm (plan_small)
   const int n = n_hi < SMALL_N_MAX_BANK ? n_hi : SMALL_N_MAX_BANK, ps = n | 1;
   const size_t bytes = sizeof(double) * ((size_t)n * ps + 5 * (size_t)n + 4) + 2 * sizeof(StepIn);
 #define EKF_SMALL(K, TM)                                                                                                 \
   do {                                                                                                                   \
-    if (lg && cfg.noise)                                                                                                 \
+    if (plg && cfg.noise)                                                                                                \
+      hipLaunchKernelGGL((K##_plog<256, TM, true>), dim3(batch), dim3(256), bytes, st, P, mu_in, mu_out, nact, in, batch,  \
+                         nsteps, flags, cfg, ld, pstride, host_out, out_b, host_seq, out_seq, lg ? *lg : InnovLog{}, *plg); \
+    else if (plg)                                                                                                        \
+      hipLaunchKernelGGL((K##_plog<256, TM, false>), dim3(batch), dim3(256), bytes, st, P, mu_in, mu_out, nact, in, batch, \
+                         nsteps, flags, cfg, ld, pstride, host_out, out_b, host_seq, out_seq, lg ? *lg : InnovLog{}, *plg); \
+    else if (lg && cfg.noise)                                                                                                 \
       hipLaunchKernelGGL((K##_log<256, TM, true>), dim3(batch), dim3(256), bytes, st, P, mu_in, mu_out, nact, in, batch,   \
                          nsteps, flags, cfg, ld, pstride, host_out, out_b, host_seq, out_seq, *lg);                      \
     else if (lg)                                                                                                         \
@@ -449,6 +479,10 @@ int launch_small_stream(hipStream_t st, double* P, const double* mu_in, double* 
           hipFuncSetAttribute(reinterpret_cast<const void*>(&K##_log<256, TM, false>),                                   \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)most) != hipSuccess ||                    \
           hipFuncSetAttribute(reinterpret_cast<const void*>(&K##_log<256, TM, true>),                                    \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)most) != hipSuccess ||                    \
+          hipFuncSetAttribute(reinterpret_cast<const void*>(&K##_plog<256, TM, false>),                                  \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)most) != hipSuccess ||                    \
+          hipFuncSetAttribute(reinterpret_cast<const void*>(&K##_plog<256, TM, true>),                                   \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)most) != hipSuccess)                      \
         return 1;                                                                                                        \
       asked.fetch_or(1ull << dev, std::memory_order_relaxed);                                                            \

@@ -114,6 +114,9 @@ ABI = {
     "ekf_log_innovations": (C.c_int, [C.c_void_p, C.c_int]),
     "ekf_innovation_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "ekf_download_innovations": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, _ip, _ip, _dp, _dp, _dp]),
+    "ekf_log_poses": (C.c_int, [C.c_void_p, C.c_int]),
+    "ekf_pose_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    "ekf_download_poses": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, _dp, _dp]),
     "ekf_set_nis_gate": (C.c_int, [C.c_void_p, C.c_double]),
     "ekf_download_gate_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
     "ekf_download_innovation_rejections": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, _ip]),
@@ -306,6 +309,13 @@ class Innovations(typing.NamedTuple):
     rejected: Optional[np.ndarray] = None   # (K, B, W) 1: the NIS gate rejected the update, 0: applied, -1 beyond m
 
 
+class PoseTrace(typing.NamedTuple):
+    """What ``EkfSlam.poses()`` returns: T logged steps of a bank of B trajectories, each row the state AFTER its step."""
+    first: int            # step number of row 0 since the log was switched on
+    mean: np.ndarray      # (T, B, 3)     x, y, theta
+    cov: np.ndarray       # (T, B, 3, 3)  the pose block P[0:3, 0:3], exactly symmetric
+
+
 class EkfSlam:
     """A bank of ``batch`` independent EKF-SLAM filters resident on one MI355X.
 
@@ -338,6 +348,7 @@ class EkfSlam:
         self._plin, self._pang, self._pm = _p(self._lin), _p(self._ang), _p(self._m, _ip)
         self._stages = {}
         self._out = None
+        self._pose_cap = 0                                   # ring size of the pose log (log_poses); 0: off
 
     # -- plumbing ------------------------------------------------------------------------------
     def _check(self, rc: int):
@@ -507,6 +518,38 @@ class EkfSlam:
         W = min(int(m.max()), EKF_AMAX) if m.size else 0
         return Innovations(np.arange(first, first + count, dtype=np.int64), m, idx[..., :W].copy(), y[..., :W, :].copy(),
                            S[..., :W, :, :].copy(), nis[..., :W].copy(), rej[..., :W].copy())
+
+    def log_poses(self, capacity: int):
+        """Switch the pose log on with a ring of the last `capacity` steps (restarting the step count at 0), or off with 0.
+        Every ``predict`` / ``update`` / ``step`` / ``step_state`` / ``step_detections`` call and every stream step of
+        ``stream_run`` / ``run_stream`` leaves the pose mean and the 3 x 3 pose block as they stand after it -- the whole
+        trajectory out of one uploaded stream.  The filter's results and scheduling are the same bits with the log on or
+        off.  Its step count is independent of the innovation log's (a lone ``predict`` is a row here)."""
+        self._check(self._lib.ekf_log_poses(self._h, int(capacity)))
+        self._pose_cap = int(capacity)
+
+    @property
+    def pose_steps(self) -> int:
+        """Steps logged since ``log_poses`` switched the pose log on."""
+        logged = C.c_longlong(0)
+        self._check(self._lib.ekf_pose_steps(self._h, C.byref(logged)))
+        return int(logged.value)
+
+    def poses(self, first: Optional[int] = None, count: Optional[int] = None) -> "PoseTrace":
+        """Steps [first, first + count) of the pose log (default: every step still in the ring), as
+        ``PoseTrace(first, mean (T, B, 3), cov (T, B, 3, 3))``.  Blocking, one copy; runs no covariance pass.
+        ``evaluation.trajectory_ate`` and ``evaluation.pose_nees_series`` judge it against ground truth."""
+        total = self.pose_steps
+        if first is None:
+            first = max(0, total - self._pose_cap) if count is None else max(0, total - int(count))
+        if count is None:
+            count = total - int(first)
+        first, count = int(first), int(count)
+        shape = (max(count, 0), self.batch)
+        mean = np.empty(shape + (3,))
+        cov = np.empty(shape + (3, 3))
+        self._check(self._lib.ekf_download_poses(self._h, first, count, _p(mean), _p(cov)))
+        return PoseTrace(first, mean, cov)
 
     @staticmethod
     def nis_gate_threshold(threshold: Optional[float] = None, confidence: Optional[float] = None) -> float:

@@ -170,6 +170,56 @@ def pose_nees(filter_bank, true_poses: Sequence[Sequence[float]]):
     return vals, float(vals.mean()), chi2_bounds(3, filter_bank.batch)
 
 
+def trajectory_ate(trace, truth_xy, align: bool = False) -> np.ndarray:
+    """``ate_rmse`` of every trajectory of a pose trace (``EkfSlam.poses()``) over its logged steps: (B,).
+
+    `truth_xy` is (T, 2) -- one ground-truth path shared by the bank -- or (T, B, 2), row k the truth at the time of the
+    trace's row k."""
+    mean = np.asarray(trace.mean, dtype=float)
+    T, B = mean.shape[0], mean.shape[1]
+    truth = np.asarray(truth_xy, dtype=float)
+    if truth.shape == (T, 2):
+        truth = np.broadcast_to(truth[:, None, :], (T, B, 2))
+    if truth.shape != (T, B, 2):
+        raise ValueError("truth_xy must be (T, 2) or (T, B, 2) for a trace of T steps and B trajectories")
+    return np.array([ate_rmse(mean[:, b, :2], truth[:, b], align=align) for b in range(B)])
+
+
+class PoseNeesSeries(NamedTuple):
+    nees: np.ndarray      # (T, B)  e^T P^-1 e of [x, y, theta] per step and trajectory
+    anees: np.ndarray     # (T,)    its mean over the bank
+    lower: float          # two-sided bounds of the bank average for a consistent filter (chi2_bounds(3, B, confidence))
+    upper: float
+    inside: float         # share of the steps with lower <= anees <= upper
+
+
+def pose_nees_series(trace, true_poses, confidence: float = 0.95) -> PoseNeesSeries:
+    """Pose NEES at every logged step of a pose trace (``EkfSlam.poses()``) against ground truth.
+
+    `true_poses` is (T, 3) -- shared by the bank -- or (T, B, 3): [x, y, theta] at the time of the trace's row k; the
+    theta error is wrapped (``wrap_angle``).  ``anees`` averages over the B trajectories of the bank, which are independent
+    runs: a consistent filter keeps it within ``chi2_bounds(3, B, confidence)`` at about `confidence` of the steps
+    (Bar-Shalom's ANEES test); above the upper bound the filter is over-confident, below the lower one conservative.
+    Only the bank average per step is tested against bounds.  The NEES values along ONE trajectory are correlated in
+    time (every step's error carries the errors before it), so their time average is not chi-square with T x 3 degrees
+    of freedom and no time-averaged bound is offered."""
+    mean = np.asarray(trace.mean, dtype=float)
+    cov = np.asarray(trace.cov, dtype=float)
+    T, B = mean.shape[0], mean.shape[1]
+    truth = np.asarray(true_poses, dtype=float)
+    if truth.shape == (T, 3):
+        truth = np.broadcast_to(truth[:, None, :], (T, B, 3))
+    if truth.shape != (T, B, 3):
+        raise ValueError("true_poses must be (T, 3) or (T, B, 3) for a trace of T steps and B trajectories")
+    e = mean - truth
+    e[..., 2] = wrap_angle(e[..., 2])
+    vals = nees(e.reshape(T * B, 3), cov.reshape(T * B, 3, 3)).reshape(T, B)
+    anees = vals.mean(axis=1) if B else np.zeros(T)
+    lower, upper = chi2_bounds(3, B, confidence)
+    inside = float(np.mean((anees >= lower) & (anees <= upper))) if T else float("nan")
+    return PoseNeesSeries(vals, anees, float(lower), float(upper), inside)
+
+
 class MarginalNees(NamedTuple):
     pose: np.ndarray                          # (B,) pose NEES per trajectory
     pose_anees: float                         # their average
