@@ -206,6 +206,30 @@ int ekf_add_landmarks(ekf_handle *h, int b, int first_index, const double *xy, i
  * EKF_ERR_STATE under EKF_FLAG_INTERNAL or after a call failed half way (as the downloads). */
 int ekf_remove_landmarks(ekf_handle *h, int b, const int *landmarks, int k);
 
+/* Fork / checkpoint on the device: copy the complete filter state of trajectory src_b[i] of `src` to trajectory dst_b[i] of
+ * `dst`, i < k, without leaving HBM.  src == dst is allowed (fork inside a bank); otherwise both handles must be on the same
+ * device.  One source may fan out to many destinations (one launch for all pairs; a source tile is read once for up to 32 of
+ * its destinations).  Afterwards ekf_download_state(dst, d) equals ekf_download_state(src, s) bit for bit, mean and
+ * covariance, and ekf_state_size is equal; the active bound, the device tag table's row and the last window's tags
+ * (ekf_download_tags, ekf_download_tag_index) and the sticky flags EKF_FLAG_NONFINITE / EKF_FLAG_ASSOC are the source's --
+ * they describe that state's history -- so that the same calls on both from there on give the same bits.
+ * NOT copied, being properties of the slot and not of the state: the slot's noise row (ekf_set_noise), gate counters,
+ * innovation-log and pose-log rows (the call writes no log row, like ekf_remove_landmarks), the inputs of an uploaded stream.
+ * The uploaded stream of `dst` stays usable exactly as after ekf_upload_state: ekf_stream_run checks that the state has the
+ * landmarks it observes.
+ * The pending update of BOTH handles is applied first (as by every call that rewrites a covariance: a pass the caller pays
+ * for, like ekf_upload_state, and ekf_debug_cadences / ekf_profile_passes and what is pending afterwards change accordingly);
+ * stored values then only move.  The handles may differ in n_max and hence in device layout (row stride, column panels);
+ * the source's n must fit the destination's n_max.  Blocking, and stream-ordered behind everything enqueued on both handles.
+ * k = 0 does nothing.  EKF_ERR_ARG (nothing changed, both handles usable; the message is `dst`'s ekf_last_error): k < 0, a
+ * NULL array with k > 0, an index outside its bank, a destination named twice, with src == dst a trajectory that is both a
+ * source and a destination (s == d included), handles on different devices, a source n above the destination's n_max.
+ * EKF_ERR_STATE: a source carries EKF_FLAG_INTERNAL or an earlier call on `src` failed half way.  A DESTINATION in that
+ * condition is cleared by the copy, as by an upload: a spare slot or handle is a recovery path.
+ * Measured (profiles/copy_trajectories.txt): a 1 -> 31 fork at 32 x N = 2000 (2.05 GB moved) takes 0.43 ms, 0.77 of the
+ * measured 6.29 TB/s copy rate of the part, against 62 ms through ekf_download_state + 31 x ekf_upload_state. */
+int ekf_copy_trajectories(ekf_handle *dst, const int *dst_b, ekf_handle *src, const int *src_b, int k);
+
 /* Pinned (page-locked, device-visible) host memory for the arrays a binding hands to its caller.  The reference's loop
  * gets a fresh n x n covariance back from every call (src/replay_no_ros.py:229-237, :482): in freshly allocated pageable
  * memory a 128 MB download first faults in and pins 32 768 pages (5 ms on top of 2.3 ms of PCIe time at N = 2000); the

@@ -66,6 +66,8 @@ void launch_marginals(hipStream_t, const double*, const double*, const double*, 
                       long, int, int, int, int, double*, double*);
 void launch_remove(hipStream_t, int, double*, double*, const int*, const int*, const int*, unsigned*, unsigned*, int, int, int, int,
                    int, unsigned, int, long);
+void launch_copy_traj(hipStream_t, bool, const double*, double*, const double*, double*, int*, const unsigned*, unsigned*, const int*,
+                      int, int, int, long, int, long);
 }  // namespace ekf
 
 using namespace ekf;
@@ -261,6 +263,9 @@ struct ekf_handle : ekf::HostPlan {
   unsigned* drm_flag = nullptr;
   unsigned rm_seq = 0;
   bool stream_stale = false;
+  // ekf_copy_trajectories (allocated on first use, in the DESTINATION handle): the launch's table of groups (plan_copy)
+  int* dcp_tab = nullptr;
+  size_t cp_cap = 0;
   std::string err;
 };
 
@@ -342,7 +347,7 @@ static void free_all(ekf_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   void* ptrs[] = {h->dP, h->dmu2[0], h->dmu2[1], h->dV, h->dW, h->ddacc2[0], h->ddacc2[1], h->dscratch, h->dn, h->dflags, h->dso, h->dfac,
                   h->d_ring, h->d_stream, h->dF, h->dQ, h->dTmp, h->dPlin, h->dtagmap, h->dneff, h->d_det, h->d_assoc_step, h->dfloor, h->dqueue, h->dready, h->dmbox,
-                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dinnov, h->dinnov_m, h->dgate, h->dnoise, h->drm_tab, h->drm_flag, h->dpose};
+                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dinnov, h->dinnov_m, h->dgate, h->dnoise, h->drm_tab, h->drm_flag, h->dpose, h->dcp_tab};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
   if (h->h_det) (void)hipHostFree(h->h_det);
@@ -1830,6 +1835,97 @@ extern "C" int ekf_upload_tag_index(ekf_handle* h, int b, const int* tag_of_inde
   }
   HIP_TRY(h, hipMemcpyAsync(h->dtagmap + (size_t)b * TAGMAX, tm.data(), sizeof(int) * TAGMAX, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return EKF_OK;
+}
+
+// Copy whole filter states between trajectories, on the device (k_copy_traj, ekf_copy.hip): src_b[i] of `src` -> dst_b[i] of
+// `dst`.  What is pending on either handle is applied first, then stored values only move: the stored upper triangle, the mean
+// (dmu2[cur] of each side), the size word and the sticky flags in ONE launch on the destination's stream, the tag table row and
+// the last window's AssocOut by two small copies behind it, the host's mirrors (n, neff, neff_enq, the floor) here.
+// The rest of what a handle holds per trajectory, one by one -- each is either a property of the SLOT (kept) or dead once
+// nothing is pending (flush_pending has run on both handles, and every ekf_stream_run has joined its second stream):
+//   dV, dW, dfac, dso      the pending ranks, their restriction to the gathered indices and the last solve's records: read by the
+//                          panel launch and the pass of the step that wrote them; with pending_k = 0 the next solve starts at rank
+//                          0 and rewrites what it reads.  neff_enq (what dso[b].neff holds for the planner) is set to the bound.
+//   ddacc2                 pending pose-block noise: taken as zero while no rank is pending (flush_pending), then rewritten.
+//   dready, dmbox          a single-launch step's completion word and mailbox: compared with the HANDLE's step_seq, which goes
+//                          on counting; written and consumed inside one launch.
+//   dcad2, dcolbuf         a cadence's records and gathered columns: consumed by its own panel launch and pass.
+//   dprow3                 pose rows behind a chained cadence: every chained run starts by taking them from P_base (launch_snap_pose).
+//   dgmu, dgbuf, dxg, dbg  the next cadence's block and mean, formed inside a run for its next solve; a run's last cadence forms none.
+//   dpre, pre_serial       inputs formed one cadence ahead: looked up by the handle's cadence serial, which only grows, and never
+//                          formed beyond the run's last cadence.
+//   dsync, dqueue, drm_flag, rm_seq, step_seq, sigma, gather_count   counters of the handle, not of a trajectory.
+//   dfloor                 uploaded from the host's bound by push_floor below.
+//   dneff                  the device's copy of the bound: written from the host's before the next device-side window (the sizes
+//                          of both handles are refreshed first, so the host's are current).
+//   dnoise, dgate, dinnov, dinnov_m, dpose, d_stream and its host tables   the slot's noise row, gate counter, log rows and
+//                          uploaded inputs: NOT copied.  ekf_stream_run's stream_maxlm check decides whether the destination's
+//                          uploaded stream still fits; stream_stale is not set.
+// A source under EKF_FLAG_INTERNAL or host_bad is refused and a destination in that condition becomes good again -- the
+// conditions check_internal / clear_internal test and clear for ekf_upload_state; here the kernel overwrites the flag word.
+extern "C" int ekf_copy_trajectories(ekf_handle* dst, const int* dst_b, ekf_handle* src, const int* src_b, int k) {
+  if (!dst || !src) return EKF_ERR_ARG;
+  if (int rc = refresh_sizes(src)) return src == dst ? rc : fail(dst, rc, "ekf_copy_trajectories: source: " + src->err);
+  if (int rc = refresh_sizes(dst)) return rc;
+  CopyPlan cp;
+  if (const char* why = plan_copy(dst, dst_b, src, src_b, k, cp)) return fail(dst, EKF_ERR_ARG, why);
+  if (k == 0) return EKF_OK;
+  HIP_TRY(dst, hipSetDevice(dst->device));
+  // (the source's flags, behind everything enqueued on its stream)
+  HIP_TRY(dst, hipMemcpyAsync(src->h_flags, src->dflags, sizeof(unsigned) * src->batch, hipMemcpyDeviceToHost, src->stream));
+  HIP_TRY(dst, hipStreamSynchronize(src->stream));
+  for (int g = 0; g < cp.groups; ++g) {
+    const int s = cp.tab[(size_t)COPY_GROUP_WORDS * g];
+    if (src->host_bad[s] || (src->h_flags[s] & EKF_FLAG_INTERNAL))
+      return fail(dst, EKF_ERR_STATE, "ekf_copy_trajectories: source trajectory " + std::to_string(s) +
+                                          " is undefined (EKF_FLAG_INTERNAL, or an earlier call failed half way): upload it again");
+  }
+  if (int rc = flush_pending(src)) return src == dst ? rc : fail(dst, rc, "ekf_copy_trajectories: source: " + src->err);
+  if (src != dst)
+    if (int rc = flush_pending(dst)) return rc;
+  HIP_TRY(dst, hipStreamSynchronize(src->stream));
+  if (src->aux) HIP_TRY(dst, hipStreamSynchronize(src->aux));
+  if (dst->cp_cap < cp.tab.size()) {
+    HIP_TRY(dst, hipStreamSynchronize(dst->stream));   // (an earlier launch may still read the old table)
+    if (dst->dcp_tab) HIP_TRY(dst, hipFree(dst->dcp_tab));
+    dst->dcp_tab = nullptr;
+    dst->cp_cap = 0;
+    const size_t cap = std::max(cp.tab.size(), (size_t)(COPY_GROUP_WORDS + 1) * dst->batch);
+    HIP_TRY(dst, hipMalloc(&dst->dcp_tab, sizeof(int) * cap));
+    dst->cp_cap = cap;
+  }
+  HIP_TRY(dst, hipMemcpyAsync(dst->dcp_tab, cp.tab.data(), sizeof(int) * cp.tab.size(), hipMemcpyHostToDevice, dst->stream));
+  // (nontemporal stores unless EKFSLAM_HIP_COPY_NT=0: tools/copy_trajectories_time.py measures both, profiles/copy_trajectories.txt)
+  bool nt = true;
+  if (const char* e = std::getenv("EKFSLAM_HIP_COPY_NT")) nt = std::atoi(e) != 0;
+  launch_copy_traj(dst->stream, nt, src->dP, dst->dP, src->dmu2[src->cur], dst->dmu2[dst->cur], dst->dn, src->dflags, dst->dflags,
+                   dst->dcp_tab, cp.groups, cp.n_hi, src->ld, src->pstride, dst->ld, dst->pstride);
+  HIP_TRY(dst, hipGetLastError());
+  // the device tag table and the last window's tags: the source's, or "no window yet" where the source has never had one
+  if (src->dtagmap)
+    if (int rc = assoc_init(dst)) return rc;
+  for (int g = 0; g < cp.groups; ++g) {
+    const int* head = cp.tab.data() + (size_t)COPY_GROUP_WORDS * g;
+    const int s = head[0];
+    for (int q = 0; q < head[2]; ++q) {
+      const int d = cp.tab[(size_t)COPY_GROUP_WORDS * cp.groups + head[1] + q];
+      if (src->dtagmap) {
+        HIP_TRY(dst, hipMemcpyAsync(dst->dtagmap + (size_t)d * TAGMAX, src->dtagmap + (size_t)s * TAGMAX, sizeof(int) * TAGMAX,
+                                    hipMemcpyDeviceToDevice, dst->stream));
+        HIP_TRY(dst, hipMemcpyAsync(dst->d_assoc_out + d, src->d_assoc_out + s, sizeof(AssocOut), hipMemcpyDeviceToDevice, dst->stream));
+      } else if (dst->dtagmap) {
+        HIP_TRY(dst, hipMemsetAsync(dst->dtagmap + (size_t)d * TAGMAX, 0xFF, sizeof(int) * TAGMAX, dst->stream));
+        HIP_TRY(dst, hipMemsetAsync(dst->d_assoc_out + d, 0, sizeof(AssocOut), dst->stream));
+      }
+      dst->n[d] = src->n[s];
+      dst->neff[d] = src->neff[s];
+      dst->neff_enq[d] = src->neff[s];
+      dst->host_bad[d] = 0;
+    }
+  }
+  if (int rc = push_floor(dst, true)) return rc;
+  HIP_TRY(dst, hipStreamSynchronize(dst->stream));
   return EKF_OK;
 }
 

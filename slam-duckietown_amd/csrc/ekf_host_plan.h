@@ -668,6 +668,67 @@ inline const char* plan_remove(const HostPlan* h, int b0, int nb, const int* lm,
   return nullptr;
 }
 
+// ekf_copy_trajectories (k_copy_traj, ekf_copy.hip): the k pairs (src_b[i] of `src` -> dst_b[i] of `dst`) checked -- indices
+// inside their banks, no destination twice, inside one handle no trajectory both read and written, the same device, every
+// source's size within the destination's n_max -- and grouped by source: a group is one source and up to COPY_FANOUT of its
+// destinations (a workgroup loads a tile of the source once and stores it to each of them; a source with more destinations
+// has several groups, so that a wide fork of small states still spreads over the chip).  The table the launch reads:
+// COPY_GROUP_WORDS ints per group {source, first entry of its destinations, their number, the source's n}, then the
+// destinations, `groups * COPY_GROUP_WORDS` on.  The sizes must be current (refresh_sizes) on both handles.
+constexpr int COPY_FANOUT = 32;
+constexpr int COPY_GROUP_WORDS = 4;
+struct CopyPlan {
+  int groups = 0, n_hi = 3;
+  std::vector<int> tab;
+};
+inline const char* plan_copy(const HostPlan* dst, const int* dst_b, const HostPlan* src, const int* src_b, int k, CopyPlan& cp) {
+  if (k < 0) return "ekf_copy_trajectories: k must be >= 0";
+  if (k > 0 && (!dst_b || !src_b)) return "ekf_copy_trajectories: NULL index array";
+  if (dst->device != src->device) return "ekf_copy_trajectories: the two handles are on different devices";
+  std::vector<unsigned char> written((size_t)dst->batch, 0), read((size_t)src->batch, 0);
+  for (int i = 0; i < k; ++i) {
+    const int s = src_b[i], d = dst_b[i];
+    if (s < 0 || s >= src->batch) return "ekf_copy_trajectories: source trajectory index out of range";
+    if (d < 0 || d >= dst->batch) return "ekf_copy_trajectories: destination trajectory index out of range";
+    if (written[d]) return "ekf_copy_trajectories: a destination trajectory is named twice";
+    written[d] = 1;
+    read[s] = 1;
+    if (src->n[s] > dst->n_max) return "ekf_copy_trajectories: a source state is larger than the destination's n_max";
+  }
+  if (dst == src)
+    for (int b = 0; b < dst->batch; ++b)
+      if (written[b] && read[b]) return "ekf_copy_trajectories: inside one handle a trajectory cannot be both a source and a destination";
+  std::vector<int> order((size_t)k);
+  for (int i = 0; i < k; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return src_b[a] < src_b[b]; });
+  std::vector<int> head, list;
+  cp.n_hi = 3;
+  for (int i = 0; i < k;) {
+    const int s = src_b[order[i]];
+    int cnt = 0;
+    const int first = (int)list.size();
+    while (i < k && src_b[order[i]] == s && cnt < COPY_FANOUT) {
+      list.push_back(dst_b[order[i]]);
+      ++i;
+      ++cnt;
+    }
+    head.push_back(s);
+    head.push_back(first);
+    head.push_back(cnt);
+    head.push_back(src->n[s]);
+    cp.n_hi = std::max(cp.n_hi, src->n[s]);
+  }
+  cp.groups = (int)head.size() / COPY_GROUP_WORDS;
+  cp.tab = head;
+  cp.tab.insert(cp.tab.end(), list.begin(), list.end());
+  return nullptr;
+}
+// tiles of 64 x 64 that reach the stored upper triangle of a state of size n (what k_copy_traj's grid enumerates)
+inline int copy_tiles(int n) {
+  const int t = (n + 63) / 64;
+  return t * (t + 1) / 2;
+}
+
 // Fill StepIn for pass `p` (landmarks [p*MMAX, ...)) of a validated list; `bound` is the trajectory's running
 // active bound (monotone): an observed landmark and everything below it may be correlated from now on.
 inline void fill_step(StepIn& s, int n_b, int& bound, double lin, double ang, int flags, const int* idx,

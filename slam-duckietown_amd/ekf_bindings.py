@@ -124,6 +124,7 @@ ABI = {
     "ekf_get_noise": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
     "ekf_add_landmarks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int]),
     "ekf_remove_landmarks": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_int]),
+    "ekf_copy_trajectories": (C.c_int, [C.c_void_p, _ip, C.c_void_p, _ip, C.c_int]),
     "ekf_predict": (C.c_int, [C.c_void_p, _dp, _dp]),
     "ekf_update": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _ip, C.c_int]),
     "ekf_step": (C.c_int, [C.c_void_p, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
@@ -665,6 +666,47 @@ class EkfSlam:
             if t in self._host_tags:
                 self._host_tags[t] = {int(old_to_new[j]): v for j, v in self._host_tags[t].items() if old_to_new[j] >= 0}
         return old_to_new
+
+    def copy_from(self, other: "EkfSlam", src=0, dst=0):
+        """Copy the complete filter state of trajectory ``src`` of `other` (another handle on the same GPU, or ``self``) into
+        trajectory ``dst`` of this one, on the device: afterwards ``state(dst)`` equals ``other.state(src)`` bit for bit, and
+        so do size, active bound, ``tag_index`` / ``tags_positions`` and the sticky flags -- the same calls on both from
+        there on give the same bits.  ``src`` and ``dst`` are ints or equal-length sequences (one launch for all pairs; a
+        source may appear several times, a destination once).  The slot's noise row, gate counter, log rows and uploaded
+        stream are NOT copied.  What is pending on either handle is applied first.  Blocking; ``EkfError`` with nothing
+        changed for an index outside its bank, a destination named twice, a trajectory both read and written inside one
+        handle, handles on different devices, or a state larger than this handle's ``n_max``.  A second handle of the same
+        shape plus ``copy_from`` is a checkpoint: ``spare.copy_from(f)`` parks a state, ``f.copy_from(spare)`` restores it."""
+        s = np.atleast_1d(np.asarray(src, dtype=np.int64)).ravel()
+        d = np.atleast_1d(np.asarray(dst, dtype=np.int64)).ravel()
+        if s.shape != d.shape:
+            raise ValueError(f"copy_from: src and dst must have the same length, got {s.size} and {d.size}")
+        lim = np.iinfo(np.int32)
+        if s.size and (min(s.min(), d.min()) < lim.min or max(s.max(), d.max()) > lim.max):
+            raise EkfError("copy_from: trajectory index out of range")
+        s, d = np.ascontiguousarray(s, dtype=np.int32), np.ascontiguousarray(d, dtype=np.int32)
+        self._check(self._lib.ekf_copy_trajectories(self._h, _p(d, _ip) if d.size else None, other._h,
+                                                    _p(s, _ip) if s.size else None, int(s.size)))
+        # (what the host association keeps per trajectory follows the state: step_detections)
+        hi = {int(b): dict(other._host_index[int(a)]) if int(a) in other._host_index else None for a, b in zip(s, d)}
+        ht = {int(b): dict(other._host_tags[int(a)]) if int(a) in other._host_tags else None for a, b in zip(s, d)}
+        for table, new in ((self._host_index, hi), (self._host_tags, ht)):
+            for b, v in new.items():
+                if v is None:
+                    table.pop(b, None)
+                else:
+                    table[b] = v
+
+    def fork(self, src: int = 0, dst=None):
+        """Fork trajectory ``src`` inside the bank, on the device: ``dst`` (an int, a sequence, or None for every other
+        trajectory) becomes a bit-exact twin of it -- ``copy_from(self, src, dst)`` with one source: the source's covariance
+        is read once however many twins are made.  Each twin keeps its own noise row, gate counter and log rows: set the
+        noise bank, fork, and the bank is a tuning grid or a Monte-Carlo bank starting from one mapped state."""
+        src = int(src)
+        if dst is None:
+            dst = [b for b in range(self.batch) if b != src]
+        d = np.atleast_1d(np.asarray(dst, dtype=np.int64)).ravel()
+        self.copy_from(self, np.full(d.shape, src, dtype=np.int64), d)
 
     def flags(self, b: int = 0) -> int:
         f = C.c_uint()

@@ -342,7 +342,7 @@ _TUNE_BANK_BYTES = 2 << 30           # (one bank holds the whole grid while its 
 
 def tune_noise(stream, motion_sigmas, meas_sigmas, mean0, diag0, *, n_max: Optional[int] = None,
                bank_size: Optional[int] = None, confidence: float = 0.95, device: int = 0, config=None,
-               filter_factory=None) -> NoiseTuning:
+               filter_factory=None, start=None) -> NoiseTuning:
     """Tune the motion and measurement noise (the reference's MOTION_MODEL_VARIANCE / MEASUREMENT_MODEL_VARIANCE,
     src/replay_no_ros.py:15-16) on one recorded stream by maximum likelihood of the innovations.
 
@@ -353,7 +353,12 @@ def tune_noise(stream, motion_sigmas, meas_sigmas, mean0, diag0, *, n_max: Optio
     measurement), e.g. for a pose block tied to the motion sigma.  Banks hold at most `bank_size` trajectories (default: the
     whole grid in one bank where it fits, else ``sharding.split_banks``' size).  Every bank logs the innovations of the whole
     run and is scored by ``nis_consistency`` once.  `config` is the handles' EkfConfig (its sigmas are replaced by the grid);
-    `filter_factory(n_max, batch, device, config)` makes the banks (default ``EkfSlam``)."""
+    `filter_factory(n_max, batch, device, config)` makes the banks (default ``EkfSlam``).
+
+    `start` = ``(filter, b)`` or ``filter`` (b = 0) starts every grid point from trajectory b of a RUNNING filter on the same
+    device instead -- tune the localisation phase of a run from the dense map its mapping phase built: every bank takes the
+    state into its slot 0 with ``copy_from(filter, b, 0)`` and forks it to the rest (``fork(0)``), on the device.  `mean0`
+    and `diag0` may then be None (they are not used), and `n_max` defaults to the start filter's."""
     from . import sharding
     from .ekf_bindings import EkfConfig, EkfSlam
     if isinstance(stream, dict):
@@ -372,13 +377,19 @@ def tune_noise(stream, motion_sigmas, meas_sigmas, mean0, diag0, *, n_max: Optio
     G = Gm * Gq
     if G == 0 or steps == 0:
         raise ValueError("tune_noise: an empty grid or stream")
-    mean0 = np.asarray(mean0, dtype=float).reshape(-1)
-    n = mean0.shape[0]
-    diag0 = np.asarray(diag0, dtype=float)
-    if diag0.shape == (n,):
-        diag0 = np.broadcast_to(diag0, (G, n))
-    elif diag0.shape != (G, n):
-        raise ValueError(f"tune_noise: diag0 must be shaped ({n},) or ({G}, {n}), got {diag0.shape}")
+    start_f = start_b = None
+    if start is not None:
+        start_f, start_b = start if isinstance(start, tuple) else (start, 0)
+        start_b = int(start_b)
+        n = int(start_f.n_max)
+    else:
+        mean0 = np.asarray(mean0, dtype=float).reshape(-1)
+        n = mean0.shape[0]
+        diag0 = np.asarray(diag0, dtype=float)
+        if diag0.shape == (n,):
+            diag0 = np.broadcast_to(diag0, (G, n))
+        elif diag0.shape != (G, n):
+            raise ValueError(f"tune_noise: diag0 must be shaped ({n},) or ({G}, {n}), got {diag0.shape}")
     n_max = n if n_max is None else int(n_max)
     pm = np.repeat(ms_grid, Gq)                          # grid point g = (motion index g // Gq, measurement index g % Gq)
     pq = np.tile(qs_grid, Gm)
@@ -395,8 +406,12 @@ def tune_noise(stream, motion_sigmas, meas_sigmas, mean0, diag0, *, n_max: Optio
         f = make(n_max, B, device, cfg)
         try:
             f.set_noise(pm[ids], pq[ids])
-            for k, g in enumerate(ids):
-                f.set_state_diag(mean0, diag0[g], k)
+            if start_f is not None:
+                f.copy_from(start_f, start_b, 0)
+                f.fork(0)
+            else:
+                for k, g in enumerate(ids):
+                    f.set_state_diag(mean0, diag0[g], k)
             f.log_innovations(steps)
             f.stream_upload(np.repeat(lin[:, None], B, 1), np.repeat(ang[:, None], B, 1),
                             np.repeat(idx[:, None, :], B, 1), np.repeat(zr[:, None, :], B, 1), np.repeat(zb[:, None, :], B, 1),
