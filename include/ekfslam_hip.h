@@ -106,6 +106,30 @@ int ekf_download_block(ekf_handle *h, int b, int r0, int c0, int rows, int cols,
  * trajectory of the range carries EKF_FLAG_INTERNAL or an earlier call failed half way (as the other downloads). */
 int ekf_download_marginals(ekf_handle *h, int b0, int count, double *pose, double *landmarks, int cap,
                            int *n_landmarks);
+/* Likelihood association of UNLABELLED observations: trajectories [b0, b0+count) each bring m[b] <= stride <= EKF_MMAX
+ * range/bearing observations (range, bearing: count x stride) and every landmark l of the trajectory's map is scored against
+ * every observation q on the device.  Per landmark, once: the current joint 5x5 covariance of (pose, landmark l) -- P_base plus
+ * the pending ranks, read with ekf_download_marginals' bounds, no covariance pass --, the measurement model at the current mean
+ * (what ekf_download_mean returns), S = H P5 H^T + Q_b with the measurement noise in effect for the trajectory (ekf_set_noise's
+ * row if set, else the handle's), S^-1 and ln det S.  Per observation: y = z - z^ (bearing wrapped), NIS = y^T S^-1 y -- the
+ * quantity of the innovation log and the NIS gate -- and the ranking score d = NIS + ln det S (the negative log-likelihood up
+ * to constants; plain NIS would always prefer the most uncertain landmark).
+ * cand (count x stride x 2) receives the landmarks of the two smallest d, cand_nis and cand_logdet (same shape, may be NULL)
+ * their NIS and ln det S, min_nis (count x stride, may be NULL) the smallest NIS over ALL landmarks ("does this observation fit
+ * nothing?").  The reduction is deterministic: ties go to the lower index, a NaN score never wins; a trajectory without
+ * landmarks or whose scores are all NaN, and the rows q >= m[b], get index -1 and NaN.  all_nis and all_logdet (count x
+ * stride x cap, both or neither, may be NULL) receive the full matrices; entries beyond a trajectory's landmark count are NaN.
+ * Pinned destinations (e.g. from ekf_host_alloc) are written directly, anything else through one copy.
+ * Blocking, and stream-ordered behind everything enqueued.  It runs no covariance pass, and changes nothing that decides
+ * later scheduling: after the call the same calls give bit-identical results and the same ekf_debug_cadences /
+ * ekf_debug_chained / ekf_debug_lookaheads / ekf_profile_passes counts as without it.  Valid on every path: per-step kernels,
+ * single-launch steps, fused cadences ended mid-cadence, chained and look-ahead runs, the small-state path.  Device-side sizes
+ * are refreshed first.
+ * EKF_ERR_ARG for a bad trajectory range, stride outside 1..EKF_MMAX, m[b] outside 0..stride, a non-finite observation, NULL
+ * cand, or all_* given with cap below the largest landmark count of the range; EKF_ERR_STATE if a trajectory of the range
+ * carries EKF_FLAG_INTERNAL or an earlier call failed half way (as the other downloads). */
+int ekf_associate(ekf_handle *h, int b0, int count, const double *range, const double *bearing, const int *m, int stride,
+                  int *cand, double *cand_nis, double *cand_logdet, double *min_nis, double *all_nis, double *all_logdet, int cap);
 int ekf_state_size(ekf_handle *h, int b, int *n);
 
 /* Innovation log: every landmark update's landmark index, innovation y (2), innovation covariance S (2x2, row-major) and

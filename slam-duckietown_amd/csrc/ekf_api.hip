@@ -64,6 +64,10 @@ void launch_panels_cad(hipStream_t, double*, double*, double*, const double*, do
                        int, unsigned, bool);
 void launch_marginals(hipStream_t, const double*, const double*, const double*, const double*, const int*, const SolveOut*, int,
                       long, int, int, int, int, double*, double*);
+long assoc_query_part_doubles(int, int, int);
+void launch_assoc_query(hipStream_t, const double*, const double*, const double*, const double*, const double*, const int*,
+                        const SolveOut*, const DeviceConfig&, int, long, int, int, int, int, int, int, const double*, const double*,
+                        const int*, double*, double*, double*, int*, double*, double*, double*);
 void launch_remove(hipStream_t, int, double*, double*, const int*, const int*, const int*, unsigned*, unsigned*, int, int, int, int,
                    int, unsigned, int, long);
 void launch_copy_traj(hipStream_t, bool, const double*, double*, const double*, double*, int*, const unsigned*, unsigned*, const int*,
@@ -223,6 +227,8 @@ struct ekf_handle : ekf::HostPlan {
   double* h_pack = nullptr;       // pinned: where k_pack_small leaves a small state (n x n covariance, mean, flags)
   double* dmarg = nullptr;        // ekf_download_marginals: device staging of destinations that are not pinned (allocated on use)
   size_t marg_cap = 0;            // ... its size in doubles
+  double* dassq = nullptr;        // ekf_associate: observations, partial records, staging of destinations that are not pinned (allocated on use)
+  size_t assq_cap = 0;            // ... its size in doubles
   // The innovation log (ekf_log_innovations; nullptr: off): a ring of innov_cap step rows, innov_steps steps logged so far.
   // While an entry point enqueues a logged step, lg_slot is the ring row of its next launch (-1: that launch is not logged) and
   // lg_jbase the position of its first landmark; ekf_stream_run logs stream step t in row (lg_tslot + t) % innov_cap.
@@ -347,7 +353,7 @@ static void free_all(ekf_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   void* ptrs[] = {h->dP, h->dmu2[0], h->dmu2[1], h->dV, h->dW, h->ddacc2[0], h->ddacc2[1], h->dscratch, h->dn, h->dflags, h->dso, h->dfac,
                   h->d_ring, h->d_stream, h->dF, h->dQ, h->dTmp, h->dPlin, h->dtagmap, h->dneff, h->d_det, h->d_assoc_step, h->dfloor, h->dqueue, h->dready, h->dmbox,
-                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dinnov, h->dinnov_m, h->dgate, h->dnoise, h->drm_tab, h->drm_flag, h->dpose, h->dcp_tab};
+                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dassq, h->dinnov, h->dinnov_m, h->dgate, h->dnoise, h->drm_tab, h->drm_flag, h->dpose, h->dcp_tab};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
   if (h->h_det) (void)hipHostFree(h->h_det);
@@ -792,6 +798,95 @@ extern "C" int ekf_download_marginals(ekf_handle* h, int b0, int count, double* 
     if (h->h_flags[b] & EKF_FLAG_INTERNAL) return check_internal(h, b, "ekf_download_marginals");
   if (n_landmarks)
     for (int b = b0; b < b0 + count; ++b) n_landmarks[b - b0] = (h->n[b] - 3) / 2;
+  return EKF_OK;
+}
+
+// Likelihood association of unlabelled observations (k_assoc_query / k_assoc_finish, ekf_associate.hip): reads what
+// ekf_download_marginals reads plus the mean and the measurement noise in effect, writes only the destinations.  Nothing of the
+// handle's scheduling state changes.
+extern "C" int ekf_associate(ekf_handle* h, int b0, int count, const double* range, const double* bearing, const int* m, int stride,
+                             int* cand, double* cand_nis, double* cand_logdet, double* min_nis, double* all_nis, double* all_logdet,
+                             int cap) {
+  if (int rc = check_b(h, 0, "ekf_associate")) return rc;            // (refreshes the sizes a device-side association grew)
+  if (b0 < 0 || count <= 0 || b0 > h->batch - count)
+    return fail(h, EKF_ERR_ARG, "ekf_associate: trajectory range outside the bank");
+  if (stride < 1 || stride > EKF_MMAX)
+    return fail(h, EKF_ERR_ARG, "ekf_associate: stride must lie in 1.." + std::to_string(EKF_MMAX));
+  if (!range || !bearing || !m) return fail(h, EKF_ERR_ARG, "ekf_associate: NULL observations");
+  if (!cand) return fail(h, EKF_ERR_ARG, "ekf_associate: NULL cand");
+  if ((all_nis == nullptr) != (all_logdet == nullptr))
+    return fail(h, EKF_ERR_ARG, "ekf_associate: all_nis and all_logdet are given together or not at all");
+  for (int bi = 0; bi < count; ++bi) {
+    if (m[bi] < 0 || m[bi] > stride)
+      return fail(h, EKF_ERR_ARG, "ekf_associate: m[" + std::to_string(bi) + "] outside 0..stride");
+    for (int q = 0; q < m[bi]; ++q)
+      if (!std::isfinite(range[(size_t)bi * stride + q]) || !std::isfinite(bearing[(size_t)bi * stride + q]))
+        return fail(h, EKF_ERR_ARG, "ekf_associate: non-finite observation " + std::to_string(q) + " of trajectory " +
+                                        std::to_string(b0 + bi));
+  }
+  const bool full = all_nis != nullptr;
+  const AssocQueryPlan plan = plan_assoc_query(h, b0, count, full ? std::max(cap, 0) : 0);
+  if (full && cap < plan.nl_hi)
+    return fail(h, EKF_ERR_ARG, "ekf_associate: cap " + std::to_string(cap) + " is below the largest landmark count " +
+                                    std::to_string(plan.nl_hi));
+  if (!full) cap = 0;
+  for (int b = b0; b < b0 + count; ++b)
+    if (h->host_bad[b]) return check_internal(h, b, "ekf_associate");
+  HIP_TRY(h, hipSetDevice(h->device));
+  // pinned destinations are written by the kernels; the others go through the staging buffer and one copy each
+  auto device_view = [](void* p) -> void* {
+    hipPointerAttribute_t attr{};
+    if (p && hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeHost) return attr.devicePointer;
+    (void)hipGetLastError();                           // (an ordinary pointer is "invalid value" to the query)
+    return nullptr;
+  };
+  const size_t obs = (size_t)count * stride, full_words = obs * (size_t)cap;
+  // layout (doubles): range, bearing, m (ints, rounded up), the partial records, then whatever destination needs staging
+  const size_t m_words = ((size_t)count + 1) / 2, part_words = (size_t)assoc_query_part_doubles(count, plan.chunks, stride);
+  struct Dst { void* host; void* dev; size_t words; size_t bytes; };
+  Dst dst[6] = {{cand, nullptr, obs, sizeof(int) * obs * 2},          {cand_nis, nullptr, obs * 2, sizeof(double) * obs * 2},
+                {cand_logdet, nullptr, obs * 2, sizeof(double) * obs * 2}, {min_nis, nullptr, obs, sizeof(double) * obs},
+                {all_nis, nullptr, full_words, sizeof(double) * full_words}, {all_logdet, nullptr, full_words, sizeof(double) * full_words}};
+  size_t need = 2 * obs + m_words + part_words;
+  bool staged[6] = {false, false, false, false, false, false};
+  size_t at[6] = {0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < 6; ++i) {
+    if (!dst[i].host || dst[i].words == 0) continue;
+    dst[i].dev = device_view(dst[i].host);
+    if (!dst[i].dev) {
+      staged[i] = true;
+      at[i] = need;
+      need += dst[i].words;
+    }
+  }
+  if (need > h->assq_cap) {
+    if (h->dassq) HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the old buffer may still be read by a copy in flight)
+    if (h->dassq) HIP_TRY(h, hipFree(h->dassq));
+    h->dassq = nullptr;
+    h->assq_cap = 0;
+    HIP_TRY(h, hipMalloc(&h->dassq, sizeof(double) * need));
+    h->assq_cap = need;
+  }
+  for (int i = 0; i < 6; ++i)
+    if (staged[i]) dst[i].dev = h->dassq + at[i];
+  double *dzr = h->dassq, *dzb = h->dassq + obs, *dpart = h->dassq + 2 * obs + m_words;
+  int* dzm = reinterpret_cast<int*>(h->dassq + 2 * obs);
+  HIP_TRY(h, hipMemcpyAsync(dzr, range, sizeof(double) * obs, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(dzb, bearing, sizeof(double) * obs, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(dzm, m, sizeof(int) * count, hipMemcpyHostToDevice, h->stream));
+  const int kb = (h->pending_k + 3) & ~3;              // what flush_pending's pass would apply (plan_pass: 4 nkt ranks)
+  launch_assoc_query(h->stream, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dmu2[h->cur], h->dn, h->dso, h->dcfg, h->ld, h->pstride,
+                     b0, count, kb, stride, cap, plan.chunks, dzr, dzb, dzm, dpart, static_cast<double*>(dst[4].dev),
+                     static_cast<double*>(dst[5].dev), static_cast<int*>(dst[0].dev), static_cast<double*>(dst[1].dev),
+                     static_cast<double*>(dst[2].dev), static_cast<double*>(dst[3].dev));
+  HIP_TRY(h, hipGetLastError());
+  for (int i = 0; i < 6; ++i)
+    if (staged[i]) HIP_TRY(h, hipMemcpyAsync(dst[i].host, dst[i].dev, dst[i].bytes, hipMemcpyDeviceToHost, h->stream));
+  // one synchronisation: the flags come back behind the results (check_internal's copy, then its wait)
+  HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->dflags, sizeof(unsigned) * h->batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (int b = b0; b < b0 + count; ++b)
+    if (h->h_flags[b] & EKF_FLAG_INTERNAL) return check_internal(h, b, "ekf_associate");
   return EKF_OK;
 }
 

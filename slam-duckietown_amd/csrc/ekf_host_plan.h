@@ -729,6 +729,22 @@ inline int copy_tiles(int n) {
   return t * (t + 1) / 2;
 }
 
+// ekf_associate (k_assoc_query / k_assoc_finish, ekf_associate.hip): the launch shape of the query over trajectories
+// [b0, b0 + count).  lane = landmark, a workgroup per chunk of AQ_CHUNK landmarks and trajectory, as k_marginals: N = 2000 x 1 is
+// 32 workgroups on 32 CUs, 32 x N = 2000 is 1024 (four per CU of 256), N = 20 x 256 one per trajectory.  The grid covers the
+// largest landmark count of the range -- or `cap`, where the full matrices are asked for (their NaN padding is written by the
+// workgroups beyond a trajectory's landmarks) -- and at least one chunk, so that every observation gets a record.
+struct AssocQueryPlan {
+  int nl_hi;           // largest landmark count of the range
+  int chunks;          // grid.x; grid.y = count
+};
+inline AssocQueryPlan plan_assoc_query(const HostPlan* h, int b0, int count, int cap) {
+  AssocQueryPlan p{};
+  for (int b = b0; b < b0 + count; ++b) p.nl_hi = std::max(p.nl_hi, (h->n[b] - 3) / 2);
+  p.chunks = std::max(1, (std::max(p.nl_hi, cap) + AQ_CHUNK - 1) / AQ_CHUNK);
+  return p;
+}
+
 // Fill StepIn for pass `p` (landmarks [p*MMAX, ...)) of a validated list; `bound` is the trajectory's running
 // active bound (monotone): an observed landmark and everything below it may be correlated from now on.
 inline void fill_step(StepIn& s, int n_b, int& bound, double lin, double ang, int flags, const int* idx,

@@ -30,7 +30,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .frontend import associate, remap_tag_index
+from .frontend import associate, remap_tag_index, resolve_associations
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libekfslam_hip.so"
@@ -110,6 +110,7 @@ ABI = {
     "ekf_download_mean": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int]),
     "ekf_download_block": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "ekf_download_marginals": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _ip]),
+    "ekf_associate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int]),
     "ekf_state_size": (C.c_int, [C.c_void_p, C.c_int, _ip]),
     "ekf_log_innovations": (C.c_int, [C.c_void_p, C.c_int]),
     "ekf_innovation_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
@@ -317,6 +318,17 @@ class PoseTrace(typing.NamedTuple):
     cov: np.ndarray       # (T, B, 3, 3)  the pose block P[0:3, 0:3], exactly symmetric
 
 
+class Associations(typing.NamedTuple):
+    """What ``EkfSlam.associate()`` returns for a bank of B trajectories with up to S observations each (rows beyond a
+    trajectory's m, and trajectories without landmarks: -1 / NaN)."""
+    cand: np.ndarray      # (B, S, 2)  int32: the landmarks of the two smallest scores d = NIS + ln det S, best first
+    nis: np.ndarray       # (B, S, 2)  their NIS = y^T S^-1 y
+    logdet: np.ndarray    # (B, S, 2)  their ln det S
+    min_nis: np.ndarray   # (B, S)     the smallest NIS over ALL landmarks
+    all_nis: Optional[np.ndarray] = None      # (B, S, N_hi)  with full=True: every landmark's NIS (NaN beyond the map)
+    all_logdet: Optional[np.ndarray] = None   # (B, S, N_hi)  ... and ln det S
+
+
 class EkfSlam:
     """A bank of ``batch`` independent EKF-SLAM filters resident on one MI355X.
 
@@ -483,6 +495,86 @@ class EkfSlam:
         if b is not None:
             return pose[0], lms[0, :counts[0]]
         return pose, lms, counts
+
+    def _unlabelled(self, ranges, bearings, m):
+        """Unlabelled observations as padded (B, stride) float64 arrays + m (B,) int32: (B, S) arrays with `m` (default: S
+        each), or one list per trajectory (a flat list for a single trajectory)."""
+        if m is None and not isinstance(ranges, np.ndarray):
+            if self.batch == 1 and (len(ranges) == 0 or np.ndim(ranges[0]) == 0):
+                ranges, bearings = (ranges,), (bearings,)
+            if len(ranges) != self.batch or len(bearings) != self.batch:
+                raise ValueError("observations: one list per trajectory expected")
+            lens = [len(r) for r in ranges]
+            stride = max(1, max(lens))
+            R, Bg = np.zeros((self.batch, stride)), np.zeros((self.batch, stride))
+            for b, mb in enumerate(lens):
+                if len(bearings[b]) != mb:
+                    raise ValueError("ranges / bearings lengths differ")
+                R[b, :mb], Bg[b, :mb] = ranges[b], bearings[b]
+            return R, Bg, np.array(lens, dtype=np.int32)
+        R = _f64(ranges).reshape(self.batch, -1)
+        Bg = _f64(bearings).reshape(self.batch, -1)
+        if R.shape != Bg.shape:
+            raise ValueError("observations: [batch, m] arrays of equal shape expected")
+        mm = np.full(self.batch, R.shape[1], dtype=np.int32) if m is None else _i32(np.broadcast_to(m, (self.batch,)))
+        if R.shape[1] == 0:
+            R, Bg = np.zeros((self.batch, 1)), np.zeros((self.batch, 1))
+        return R, Bg, mm
+
+    def associate(self, ranges, bearings, m=None, full: bool = False) -> "Associations":
+        """Score every landmark of every trajectory's map against its UNLABELLED range/bearing observations, on the device
+        (``ekf_associate``): per observation the two landmarks of smallest d = NIS + ln det S with their NIS and ln det S,
+        and the smallest NIS over all landmarks.  The covariance is the current one -- pending ranks included -- read
+        without a covariance pass; the noise is the trajectory's (``set_noise``).  Blocking; changes nothing of the filter
+        or its scheduling.  Observations: (B, S) arrays with ``m`` (B,) valid per trajectory (default S), or one list per
+        trajectory; at most EKF_MMAX each.  ``full=True`` adds the (B, S, N_hi) matrices of NIS and ln det S.
+        ``frontend.resolve_associations`` turns one trajectory's rows into an assignment."""
+        R, Bg, mm = self._unlabelled(ranges, bearings, m)
+        B, S = R.shape
+        cand = np.empty((B, S, 2), dtype=np.int32)
+        nis, logdet, mn = np.empty((B, S, 2)), np.empty((B, S, 2)), np.empty((B, S))
+        all_nis = all_ld = None
+        cap = 0
+        if full:
+            cap = max((self.size(t) - 3) // 2 for t in range(B))
+            all_nis = _pinned.empty(self._lib, (B, S, cap)) if cap > 0 else np.empty((B, S, 0))
+            all_ld = _pinned.empty(self._lib, (B, S, cap)) if cap > 0 else np.empty((B, S, 0))
+        self._check(self._lib.ekf_associate(self._h, 0, B, _p(R), _p(Bg), _p(mm, _ip), S, _p(cand, _ip), _p(nis), _p(logdet),
+                                            _p(mn), _p(all_nis) if full else None, _p(all_ld) if full else None, cap))
+        return Associations(cand, nis, logdet, mn, all_nis, all_ld)
+
+    def step_unlabelled(self, lin, ang, ranges, bearings, m=None, accept: float = 9.21, create: float = 18.42):
+        """One step from UNLABELLED observations: ``predict``, ``associate``, ``frontend.resolve_associations`` per
+        trajectory, ``add_landmarks`` for the observations that fit nothing (world position from the predicted pose, as
+        ``frontend.associate`` places a new tag), then ``update`` with the pairs in observation order.  ``accept`` /
+        ``create`` are NIS thresholds (defaults: the chi-square quantiles of 2 degrees of freedom at 0.99 and 0.9999): an
+        observation is matched when its candidate's NIS <= accept, a new landmark when even the best-fitting landmark's
+        NIS > create, dropped as ambiguous in between.  Returns one int array per trajectory: the landmark each
+        observation updated (new ones included), -1 for a dropped one.  Only existing calls are made: a run whose
+        associations equal the truth is bit-identical to the labelled predict / add_landmarks / update run."""
+        self.predict(lin, ang)
+        R, Bg, mm = self._unlabelled(ranges, bearings, m)
+        a = self.associate(R, Bg, mm)
+        out, idx, zr, zb = [], [], [], []
+        for b in range(self.batch):
+            mb = int(mm[b])
+            assign, new_obs, _dropped = resolve_associations(a.cand[b, :mb], a.nis[b, :mb], a.min_nis[b, :mb], accept, create)
+            if len(new_obs):
+                n_lm = (self.size(b) - 3) // 2
+                if 3 + 2 * (n_lm + len(new_obs)) > self.n_max:
+                    raise EkfError(f"step_unlabelled: trajectory {b}'s map would grow to {n_lm + len(new_obs)} landmarks, "
+                                   f"beyond this handle's capacity n_max = {self.n_max}")
+                x0, y0, th = self.mean(b)[:3]
+                xy = [(x0 + R[b, q] * np.cos(Bg[b, q] + th), y0 + R[b, q] * np.sin(Bg[b, q] + th)) for q in new_obs]
+                self.add_landmarks(np.array(xy), b)
+                assign[np.asarray(new_obs)] = n_lm + np.arange(len(new_obs))
+            keep = np.flatnonzero(assign >= 0)
+            out.append(assign)
+            idx.append(assign[keep].astype(np.int32))
+            zr.append(R[b, keep])
+            zb.append(Bg[b, keep])
+        self.update(idx, zr, zb)
+        return out
 
     def log_innovations(self, capacity: int):
         """Switch the innovation log on with a ring of the last `capacity` steps (restarting the step count at 0), or off

@@ -11,6 +11,8 @@
   batched filter bank (`EkfSlam(batch=B)`) is exactly the Monte-Carlo tool this needs.  `marginal_nees` takes the
   pose and landmark blocks of the whole bank from one `marginals()` call (no covariance pass): cheap enough for
   every step of a run.
+* `association_check`: labelled observations judged by the likelihood query (``EkfSlam.associate``) -- the misread-tag
+  detector.
 """
 from __future__ import annotations
 
@@ -424,3 +426,45 @@ def tune_noise(stream, motion_sigmas, meas_sigmas, mean0, diag0, *, n_max: Optio
     g_best = int(np.nanargmax(loglik))
     return NoiseTuning(ms_grid, qs_grid, loglik.reshape(Gm, Gq), anis.reshape(Gm, Gq), bounds.reshape(Gm, Gq, 2),
                        (float(pm[g_best]), float(pq[g_best])), tuple(len(b) for b in banks))
+
+
+class AssociationFlag(NamedTuple):
+    """One labelled observation `association_check` reports."""
+    b: int                # trajectory
+    q: int                # observation number in its list
+    labelled: int         # the landmark its label names
+    best: int             # the landmark of the smallest score d = NIS + ln det S (-1: none)
+    d_labelled: float     # the labelled landmark's score
+    d_other: float        # the smallest score of any OTHER landmark (inf: there is none)
+
+
+def association_check(f, idx, ranges, bearings, margin: float = 0.0):
+    """Labelled observations against the filter's own likelihood (``f.associate(..., full=True)``: one device query, no
+    covariance pass, nothing of the filter changes): reports every observation whose labelled landmark is not the best
+    candidate, or whose lead in d = NIS + ln det S over the best OTHER landmark is below ``margin`` -- a misread tag id, or a
+    label that the geometry cannot tell from its neighbour.  ``idx`` / ``ranges`` / ``bearings``: as ``EkfSlam.update``
+    takes them (one list per trajectory, a flat list for a single trajectory, or (B, m) arrays).  Returns a list of
+    ``AssociationFlag`` in (trajectory, observation) order; empty: every label is the clear best."""
+    B = f.batch
+    if isinstance(idx, np.ndarray) and idx.ndim == 2:
+        idx, ranges, bearings = list(idx), list(np.asarray(ranges)), list(np.asarray(bearings))
+    elif B == 1 and (len(idx) == 0 or np.ndim(idx[0]) == 0):
+        idx, ranges, bearings = [idx], [ranges], [bearings]
+    if len(idx) != B:
+        raise ValueError("association_check: one list per trajectory expected")
+    a = f.associate([list(r) for r in ranges], [list(z) for z in bearings], full=True)
+    d = a.all_nis + a.all_logdet
+    flags = []
+    for b in range(B):
+        n_lm = d.shape[2]
+        for q, j in enumerate(idx[b]):
+            j = int(j)
+            if not 0 <= j < n_lm or np.isnan(d[b, q, j]):
+                raise ValueError(f"association_check: trajectory {b}: label {j} names no landmark of the map")
+            others = np.delete(d[b, q], j)
+            others = others[~np.isnan(others)]
+            d_other = float(others.min()) if others.size else math.inf
+            best = int(a.cand[b, q, 0])
+            if best != j or d_other - d[b, q, j] < margin:
+                flags.append(AssociationFlag(b, q, j, best, float(d[b, q, j]), d_other))
+    return flags

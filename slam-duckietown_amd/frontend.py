@@ -6,6 +6,9 @@ odometry scalars.  O(#detections) Python, mirrors the reference's semantics exac
   associate      src/replay_no_ros.py:280-337
   delta_phi      src/replay_no_ros.py:250-266
   displacement   src/replay_no_ros.py:484-497
+
+`resolve_associations` has no counterpart in the reference (which trusts tag ids): it turns the candidates the device's
+likelihood query (``EkfSlam.associate``) returns for one trajectory's unlabelled observations into an assignment.
 """
 from __future__ import annotations
 
@@ -93,3 +96,37 @@ def remap_tag_index(tag_index: Dict[int, int], old_to_new) -> Dict[int, int]:
         if o2n[j] >= 0:
             out[tag] = int(o2n[j])
     return out
+
+
+def resolve_associations(cand, nis, min_nis, accept: float, create: float):
+    """One trajectory's unlabelled observations -> landmarks, from what ``EkfSlam.associate`` returns for it: ``cand``
+    (m, 2) the two best landmarks of every observation (best first, -1: none), ``nis`` (m, 2) their NIS, ``min_nis`` (m,) the
+    smallest NIS over all landmarks.
+
+    Greedy, one landmark per observation: the observations are taken in ascending order of their best candidate's NIS
+    (stable sort; NaN last) and each takes its first candidate that no earlier one took.  It is ACCEPTED when that
+    candidate's NIS <= ``accept``.  Otherwise -- also when both its candidates are taken -- it is a NEW landmark when it
+    fits nothing at all (``min_nis > create``, or the map is empty), else it is DROPPED as ambiguous: too far from its
+    candidate to update with, too close to some landmark to start another.
+
+    Returns ``(assign, new_obs, dropped_obs)``: ``assign`` (m,) int64, the landmark of every accepted observation and -1 for
+    the others; the observation numbers of the new and of the dropped ones, ascending."""
+    cand = np.asarray(cand, dtype=np.int64).reshape(-1, 2)
+    nis = np.asarray(nis, dtype=np.float64).reshape(-1, 2)
+    min_nis = np.asarray(min_nis, dtype=np.float64).reshape(-1)
+    m = cand.shape[0]
+    assign = np.full(m, -1, dtype=np.int64)
+    new_obs: List[int] = []
+    dropped: List[int] = []
+    taken = set()
+    for q in np.argsort(nis[:, 0], kind="stable"):
+        q = int(q)
+        pick = next((c for c in range(2) if cand[q, c] >= 0 and int(cand[q, c]) not in taken), None)
+        if pick is not None and nis[q, pick] <= accept:
+            assign[q] = cand[q, pick]
+            taken.add(int(cand[q, pick]))
+        elif cand[q, 0] < 0 or min_nis[q] > create:
+            new_obs.append(q)
+        else:
+            dropped.append(q)
+    return assign, sorted(new_obs), sorted(dropped)
