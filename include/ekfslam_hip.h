@@ -50,6 +50,7 @@ extern "C" {
                                  or more than EKF_AMAX distinct tags in one window */
 #define EKF_DMAX 256          /* detections per window for ekf_step_detections (the reference's normal mode: a 0.7 s window
                                  of every camera frame, src/replay_no_ros.py:17 -- 21 frames x a dozen tags) */
+#define EKF_JMAX 64           /* landmarks per trajectory in one ekf_download_joint (sub-state of up to 3 + 2*64 = 131) */
 #define EKF_AMAX 32           /* distinct tags per window the device-side association takes (two update passes of EKF_MMAX) */
 
 typedef struct ekf_handle ekf_handle;
@@ -130,6 +131,32 @@ int ekf_download_marginals(ekf_handle *h, int b0, int count, double *pose, doubl
  * carries EKF_FLAG_INTERNAL or an earlier call failed half way (as the other downloads). */
 int ekf_associate(ekf_handle *h, int b0, int count, const double *range, const double *bearing, const int *m, int stride,
                   int *cand, double *cand_nis, double *cand_logdet, double *min_nis, double *all_nis, double *all_logdet, int cap);
+/* Joint covariance (and mean) of the pose and a chosen SUBSET of landmarks, cross-covariances included, without applying the
+ * pending update: what joint-compatibility association, a submap hand-off or the separation of two landmarks need, and what
+ * otherwise takes ekf_flush + ekf_download_block per block pair.  Trajectories [b0, b0+count) each name k[bi] <= stride <=
+ * EKF_JMAX landmarks in landmarks[bi*stride + 0..k[bi]), in any order; the sub-state of trajectory bi is [x, y, theta,
+ * l_j0 x, l_j0 y, l_j1 x, ...] in the order given, ns = 3 + 2*stride.  cov (count x ns x ns, row-major) receives the CURRENT
+ * covariance of that sub-state -- P_base plus the pending ranks plus the pending pose noise, read with
+ * ekf_download_marginals' bounds --, mean (count x ns, may be NULL) its mean, bit for bit what ekf_download_mean returns at
+ * those indices.  Rows and columns beyond 3 + 2*k[bi] are NaN in both; k[bi] = 0 returns the pose alone.
+ * Every entry is formed once, from the stored upper triangle (the smaller state index as the row), and mirrored: cov is
+ * exactly symmetric.  The ranks of an entry are summed in a fixed order that does not depend on the selection: a permuted
+ * selection gives the permuted result bit for bit, a subset the corresponding entries of a superset bit for bit, and where
+ * nothing is pending the result is the stored value bit for bit; against a flushed download it is equal to rounding (the
+ * ranks are summed in another order).
+ * One gather kernel (a workgroup per trajectory and 32 x 32 tile of the sub-matrix) writes pinned destinations (e.g. from
+ * ekf_host_alloc) directly, anything else through a staging buffer of the handle and one copy.
+ * Blocking, and stream-ordered behind everything enqueued.  It runs no covariance pass and no mirror, writes nothing the
+ * filter owns and changes nothing that decides later scheduling: after the call the same calls give bit-identical results
+ * and the same ekf_debug_cadences / ekf_debug_chained / ekf_debug_lookaheads / ekf_profile_passes counts as without it.
+ * Valid on every path: per-step kernels, single-launch steps, fused cadences ended mid-cadence, chained and look-ahead runs,
+ * the small-state path.  Device-side sizes are refreshed first.
+ * EKF_ERR_ARG (nothing changed, the handle usable) for a bad trajectory range, stride outside 1..EKF_JMAX, k[bi] outside
+ * 0..stride, a landmark index outside the trajectory's map or named twice in one trajectory, NULL landmarks, k or cov;
+ * EKF_ERR_STATE if a trajectory of the range carries EKF_FLAG_INTERNAL or an earlier call failed half way (as the other
+ * downloads). */
+int ekf_download_joint(ekf_handle *h, int b0, int count, const int *landmarks, const int *k, int stride,
+                       double *mean, double *cov);
 int ekf_state_size(ekf_handle *h, int b, int *n);
 
 /* Innovation log: every landmark update's landmark index, innovation y (2), innovation covariance S (2x2, row-major) and

@@ -68,6 +68,8 @@ long assoc_query_part_doubles(int, int, int);
 void launch_assoc_query(hipStream_t, const double*, const double*, const double*, const double*, const double*, const int*,
                         const SolveOut*, const DeviceConfig&, int, long, int, int, int, int, int, int, const double*, const double*,
                         const int*, double*, double*, double*, int*, double*, double*, double*);
+void launch_joint(hipStream_t, const double*, const double*, const double*, const double*, const double*, const int*,
+                  const SolveOut*, int, long, int, int, int, int, int, int, const int*, double*, double*);
 void launch_remove(hipStream_t, int, double*, double*, const int*, const int*, const int*, unsigned*, unsigned*, int, int, int, int,
                    int, unsigned, int, long);
 void launch_copy_traj(hipStream_t, bool, const double*, double*, const double*, double*, int*, const unsigned*, unsigned*, const int*,
@@ -229,6 +231,10 @@ struct ekf_handle : ekf::HostPlan {
   size_t marg_cap = 0;            // ... its size in doubles
   double* dassq = nullptr;        // ekf_associate: observations, partial records, staging of destinations that are not pinned (allocated on use)
   size_t assq_cap = 0;            // ... its size in doubles
+  double* djoint = nullptr;       // ekf_download_joint: the selection (ints), staging of destinations that are not pinned (allocated on use)
+  size_t joint_cap = 0;           // ... its size in doubles
+  std::vector<int> joint_sel;     // ... and the selection as the host sorted it (plan_joint_query)
+  std::vector<std::pair<int, int>> joint_order;   // ... scratch of the sort (handle-owned: no allocation per query)
   // The innovation log (ekf_log_innovations; nullptr: off): a ring of innov_cap step rows, innov_steps steps logged so far.
   // While an entry point enqueues a logged step, lg_slot is the ring row of its next launch (-1: that launch is not logged) and
   // lg_jbase the position of its first landmark; ekf_stream_run logs stream step t in row (lg_tslot + t) % innov_cap.
@@ -353,7 +359,7 @@ static void free_all(ekf_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   void* ptrs[] = {h->dP, h->dmu2[0], h->dmu2[1], h->dV, h->dW, h->ddacc2[0], h->ddacc2[1], h->dscratch, h->dn, h->dflags, h->dso, h->dfac,
                   h->d_ring, h->d_stream, h->dF, h->dQ, h->dTmp, h->dPlin, h->dtagmap, h->dneff, h->d_det, h->d_assoc_step, h->dfloor, h->dqueue, h->dready, h->dmbox,
-                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dassq, h->dinnov, h->dinnov_m, h->dgate, h->dnoise, h->drm_tab, h->drm_flag, h->dpose, h->dcp_tab};
+                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dassq, h->djoint, h->dinnov, h->dinnov_m, h->dgate, h->dnoise, h->drm_tab, h->drm_flag, h->dpose, h->dcp_tab};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
   if (h->h_det) (void)hipHostFree(h->h_det);
@@ -887,6 +893,59 @@ extern "C" int ekf_associate(ekf_handle* h, int b0, int count, const double* ran
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   for (int b = b0; b < b0 + count; ++b)
     if (h->h_flags[b] & EKF_FLAG_INTERNAL) return check_internal(h, b, "ekf_associate");
+  return EKF_OK;
+}
+
+// The joint covariance and mean of the pose and a subset of landmarks as the pass would leave them, without running it (k_joint,
+// ekf_joint.hip): reads what ekf_download_marginals reads plus the mean, writes only the destinations.  Nothing of the handle's
+// scheduling state changes.
+extern "C" int ekf_download_joint(ekf_handle* h, int b0, int count, const int* landmarks, const int* k, int stride, double* mean,
+                                  double* cov) {
+  if (int rc = check_b(h, 0, "ekf_download_joint")) return rc;       // (refreshes the sizes a device-side association grew)
+  if (!cov) return fail(h, EKF_ERR_ARG, "ekf_download_joint: NULL cov");
+  JointQueryPlan jp{};
+  if (const char* why = plan_joint_query(h, b0, count, landmarks, k, stride, jp, h->joint_sel, h->joint_order))
+    return fail(h, EKF_ERR_ARG, std::string("ekf_download_joint: ") + why);
+  for (int b = b0; b < b0 + count; ++b)
+    if (h->host_bad[b]) return check_internal(h, b, "ekf_download_joint");
+  HIP_TRY(h, hipSetDevice(h->device));
+  // pinned destinations are written by the kernel; the others go through the staging buffer and one copy each
+  auto device_view = [](double* p) -> double* {
+    hipPointerAttribute_t attr{};
+    if (p && hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeHost)
+      return static_cast<double*>(attr.devicePointer);
+    (void)hipGetLastError();                           // (an ordinary pointer is "invalid value" to the query)
+    return nullptr;
+  };
+  // layout (doubles): the selection (ints, rounded up), then whatever destination needs staging
+  const size_t sel_words = (h->joint_sel.size() + 1) / 2;
+  const size_t mean_words = (size_t)count * jp.ns, cov_words = mean_words * jp.ns;
+  double* dmean = mean ? device_view(mean) : nullptr;
+  double* dcov = device_view(cov);
+  const size_t need = sel_words + (mean && !dmean ? mean_words : 0) + (dcov ? 0 : cov_words);
+  if (need > h->joint_cap) {
+    if (h->djoint) HIP_TRY(h, hipStreamSynchronize(h->stream));  // (the old buffer may still be read by a copy in flight)
+    if (h->djoint) HIP_TRY(h, hipFree(h->djoint));
+    h->djoint = nullptr;
+    h->joint_cap = 0;
+    HIP_TRY(h, hipMalloc(&h->djoint, sizeof(double) * need));
+    h->joint_cap = need;
+  }
+  int* dsel = reinterpret_cast<int*>(h->djoint);
+  double* smean = !mean ? nullptr : (dmean ? dmean : h->djoint + sel_words);
+  double* scov = dcov ? dcov : h->djoint + sel_words + (mean && !dmean ? mean_words : 0);
+  HIP_TRY(h, hipMemcpyAsync(dsel, h->joint_sel.data(), sizeof(int) * h->joint_sel.size(), hipMemcpyHostToDevice, h->stream));
+  const int kb = (h->pending_k + 3) & ~3;              // what flush_pending's pass would apply (plan_pass: 4 nkt ranks)
+  launch_joint(h->stream, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dmu2[h->cur], h->dn, h->dso, h->ld, h->pstride, b0, count,
+               kb, jp.ns, jp.nt, jp.tiles, dsel, smean, scov);
+  HIP_TRY(h, hipGetLastError());
+  if (mean && !dmean) HIP_TRY(h, hipMemcpyAsync(mean, smean, sizeof(double) * mean_words, hipMemcpyDeviceToHost, h->stream));
+  if (!dcov) HIP_TRY(h, hipMemcpyAsync(cov, scov, sizeof(double) * cov_words, hipMemcpyDeviceToHost, h->stream));
+  // one synchronisation: the flags come back behind the results (check_internal's copy, then its wait)
+  HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->dflags, sizeof(unsigned) * h->batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (int b = b0; b < b0 + count; ++b)
+    if (h->h_flags[b] & EKF_FLAG_INTERNAL) return check_internal(h, b, "ekf_download_joint");
   return EKF_OK;
 }
 

@@ -41,6 +41,8 @@ constexpr int SMALL_BANK_MIN = 128;     // workgroup per CU): N = 64 x 256 10.4 
 constexpr int PPW = 4096;
 constexpr int RM_THREADS = 256;         // k_remove (ekf_remove.hip): threads per workgroup, one row each
 constexpr int AQ_CHUNK = 64;            // k_assoc_query (ekf_associate.hip): landmarks per workgroup, one per lane of a wave
+constexpr int JQ_TILE = 32;             // k_joint (ekf_joint.hip): rows / columns of a workgroup's tile of the sub-matrix
+constexpr int JMAX = EKF_JMAX;          // landmarks per trajectory in one ekf_download_joint
 __host__ __device__ __forceinline__ int p_lds(int ld) { return ld < PPW ? ld : PPW; }
 __host__ __device__ __forceinline__ long p_col(int ld, int j) { return (long)(j >> 12) * ((long)ld * PPW) + (j & (PPW - 1)); }
 // the same as a 32-bit byte offset (ekf_create bounds one covariance by 4 GiB)

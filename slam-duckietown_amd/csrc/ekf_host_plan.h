@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "ekf_device.h"
@@ -743,6 +744,55 @@ inline AssocQueryPlan plan_assoc_query(const HostPlan* h, int b0, int count, int
   for (int b = b0; b < b0 + count; ++b) p.nl_hi = std::max(p.nl_hi, (h->n[b] - 3) / 2);
   p.chunks = std::max(1, (std::max(p.nl_hi, cap) + AQ_CHUNK - 1) / AQ_CHUNK);
   return p;
+}
+
+// ekf_download_joint (k_joint, ekf_joint.hip): validates the selections of trajectories [b0, b0 + count) -- k[bi] <= stride
+// landmarks each, in any order -- and decides the launch: a workgroup per (trajectory, JQ_TILE x JQ_TILE tile of the upper
+// triangle of the ns x ns sub-matrix), ns = 3 + 2 stride: 15 tiles at stride = EKF_JMAX, 480 workgroups for a bank of 32, one
+// at stride <= 14.  `sel` becomes what the kernel reads, per trajectory 2 * nsp ints (nsp = ns rounded up to whole tiles): the
+// sub-state SORTED by state index -- the stored upper triangle of P is then the upper triangle of the sub-matrix -- as
+// sidx[t], the state index of sorted entry t, and spos[t], its row / column of the output.  Entries beyond a trajectory's own
+// 3 + 2 k[bi] are sidx = -1 with spos = t (NaN rows and columns), the padding beyond ns is spos = -1 (never written).
+// Returns nullptr, or what is wrong with the arguments (then nothing of `jp` or `sel` is to be used).
+struct JointQueryPlan {
+  int ns;              // rows / columns of one trajectory's output
+  int nt;              // tiles per row of the sub-matrix
+  int tiles;           // grid.x = nt (nt + 1) / 2; grid.y = count
+  int nsp;             // nt * JQ_TILE
+};
+inline const char* plan_joint_query(const HostPlan* h, int b0, int count, const int* landmarks, const int* k, int stride,
+                                    JointQueryPlan& jp, std::vector<int>& sel, std::vector<std::pair<int, int>>& order) {
+  if (b0 < 0 || count <= 0 || b0 > h->batch - count) return "trajectory range outside the bank";
+  if (stride < 1 || stride > JMAX) return "stride outside 1..EKF_JMAX";
+  if (!landmarks || !k) return "NULL landmarks or k";
+  jp.ns = 3 + 2 * stride;
+  jp.nt = (jp.ns + JQ_TILE - 1) / JQ_TILE;
+  jp.tiles = jp.nt * (jp.nt + 1) / 2;
+  jp.nsp = jp.nt * JQ_TILE;
+  sel.assign((size_t)count * 2 * jp.nsp, -1);
+  for (int bi = 0; bi < count; ++bi) {
+    const int nl = (h->n[b0 + bi] - 3) / 2, kk = k[bi];
+    if (kk < 0 || kk > stride) return "k[b] outside 0..stride";
+    const int* lm = landmarks + (size_t)bi * stride;
+    order.clear();                                     // (landmark, its place in the selection)
+    for (int p = 0; p < kk; ++p) {
+      if (lm[p] < 0 || lm[p] >= nl) return "landmark index outside the state";
+      order.emplace_back(lm[p], p);
+    }
+    std::sort(order.begin(), order.end());
+    for (int p = 1; p < kk; ++p)
+      if (order[p].first == order[p - 1].first) return "landmark index named twice";
+    int* sidx = sel.data() + (size_t)bi * 2 * jp.nsp;
+    int* spos = sidx + jp.nsp;
+    for (int a = 0; a < 3; ++a) sidx[a] = spos[a] = a;
+    for (int p = 0; p < kk; ++p)
+      for (int d = 0; d < 2; ++d) {
+        sidx[3 + 2 * p + d] = 3 + 2 * order[p].first + d;
+        spos[3 + 2 * p + d] = 3 + 2 * order[p].second + d;
+      }
+    for (int t = 3 + 2 * kk; t < jp.ns; ++t) spos[t] = t;
+  }
+  return nullptr;
 }
 
 // Fill StepIn for pass `p` (landmarks [p*MMAX, ...)) of a validated list; `bound` is the trajectory's running

@@ -30,11 +30,12 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .frontend import associate, remap_tag_index, resolve_associations
+from .frontend import associate, joint_compatibility, remap_tag_index, resolve_associations
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libekfslam_hip.so"
 EKF_MMAX = 16
+EKF_JMAX = 64                     # landmarks per trajectory in one joint() query
 EKF_FLAG_NONFINITE = 1
 EKF_FLAG_ASSOC = 2
 EKF_FLAG_INTERNAL = 4             # a bounded wait of a single-launch step timed out: sync()/state()/mean() raise EkfError
@@ -111,6 +112,7 @@ ABI = {
     "ekf_download_block": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "ekf_download_marginals": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _ip]),
     "ekf_associate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int]),
+    "ekf_download_joint": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, C.c_int, _dp, _dp]),
     "ekf_state_size": (C.c_int, [C.c_void_p, C.c_int, _ip]),
     "ekf_log_innovations": (C.c_int, [C.c_void_p, C.c_int]),
     "ekf_innovation_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
@@ -496,6 +498,42 @@ class EkfSlam:
             return pose[0], lms[0, :counts[0]]
         return pose, lms, counts
 
+    def joint(self, landmarks, b: Optional[int] = None):
+        """Mean and full joint covariance -- cross-covariances included -- of the pose and a chosen subset of landmarks,
+        without applying the pending update (``ekf_download_joint``: no covariance pass, no mirror, one read-only gather
+        kernel).  The sub-state is [x, y, theta, l_j0 x, l_j0 y, l_j1 x, ...] in the order the indices are given (any order,
+        none twice, at most EKF_JMAX).  Equal to ``state(b)[1][np.ix_(s, s)]`` after ``flush()`` to rounding, bit-identical
+        where nothing is pending; a permuted or a smaller selection returns the same bits at the corresponding entries.
+
+        ``b`` given: ``(mean (3 + 2k,), cov (3 + 2k, 3 + 2k))`` of trajectory b for a 1-D index list.
+        ``b`` None: one list per trajectory, ``(mean (B, ns), cov (B, ns, ns), k (B,))`` with ns = 3 + 2 max(k, 1) and the
+        rows and columns beyond a trajectory's own 3 + 2 k NaN."""
+        if b is None:
+            b0, count = 0, self.batch
+            lists = [np.asarray(x, dtype=np.int64).reshape(-1) for x in landmarks]
+            if len(lists) != count:
+                raise ValueError("joint: one landmark list per trajectory expected")
+        else:
+            b0, count = int(b), 1
+            lists = [np.asarray(landmarks, dtype=np.int64).reshape(-1)]
+        kk = np.array([len(x) for x in lists], dtype=np.int32)
+        if kk.max() > EKF_JMAX:
+            raise ValueError(f"joint: at most EKF_JMAX = {EKF_JMAX} landmarks per trajectory, got {int(kk.max())}")
+        stride = max(1, int(kk.max()))
+        lm = np.zeros((count, stride), dtype=np.int32)
+        for t, x in enumerate(lists):
+            if x.size and (x.min() < np.iinfo(np.int32).min or x.max() > np.iinfo(np.int32).max):
+                raise ValueError("joint: landmark index outside the state")
+            lm[t, :len(x)] = x
+        ns = 3 + 2 * stride
+        mean = _pinned.empty(self._lib, (count, ns))
+        cov = _pinned.empty(self._lib, (count, ns, ns))
+        self._check(self._lib.ekf_download_joint(self._h, b0, count, _p(lm, _ip), _p(kk, _ip), stride, _p(mean), _p(cov)))
+        if b is not None:
+            n = 3 + 2 * int(kk[0])
+            return mean[0, :n], cov[0, :n, :n]
+        return mean, cov, kk
+
     def _unlabelled(self, ranges, bearings, m):
         """Unlabelled observations as padded (B, stride) float64 arrays + m (B,) int32: (B, S) arrays with `m` (default: S
         each), or one list per trajectory (a flat list for a single trajectory)."""
@@ -543,7 +581,8 @@ class EkfSlam:
                                             _p(mn), _p(all_nis) if full else None, _p(all_ld) if full else None, cap))
         return Associations(cand, nis, logdet, mn, all_nis, all_ld)
 
-    def step_unlabelled(self, lin, ang, ranges, bearings, m=None, accept: float = 9.21, create: float = 18.42):
+    def step_unlabelled(self, lin, ang, ranges, bearings, m=None, accept: float = 9.21, create: float = 18.42,
+                        joint: bool = False):
         """One step from UNLABELLED observations: ``predict``, ``associate``, ``frontend.resolve_associations`` per
         trajectory, ``add_landmarks`` for the observations that fit nothing (world position from the predicted pose, as
         ``frontend.associate`` places a new tag), then ``update`` with the pairs in observation order.  ``accept`` /
@@ -551,14 +590,39 @@ class EkfSlam:
         observation is matched when its candidate's NIS <= accept, a new landmark when even the best-fitting landmark's
         NIS > create, dropped as ambiguous in between.  Returns one int array per trajectory: the landmark each
         observation updated (new ones included), -1 for a dropped one.  Only existing calls are made: a run whose
-        associations equal the truth is bit-identical to the labelled predict / add_landmarks / update run."""
+        associations equal the truth is bit-identical to the labelled predict / add_landmarks / update run.
+
+        ``joint=True`` replaces the greedy individual test by joint compatibility: per trajectory the candidates of an
+        observation are its (at most two) ``associate`` candidates with NIS <= accept, one ``joint()`` call fetches the
+        covariance of the pose and the union of all candidates for the whole bank, and
+        ``frontend.joint_compatibility`` picks the largest jointly consistent set of pairings -- a pose error larger than
+        the landmark spacing no longer shifts every observation onto its neighbour.  The observations it leaves unmatched
+        become new landmarks or are dropped by the same ``create`` rule."""
         self.predict(lin, ang)
         R, Bg, mm = self._unlabelled(ranges, bearings, m)
         a = self.associate(R, Bg, mm)
+        if joint:
+            cands, sels = [], []
+            for b in range(self.batch):
+                mb = int(mm[b])
+                # (associate() ranks by d = NIS + ln det S; joint_compatibility takes ascending individual NIS: stable sort)
+                cb = [[j for _, j in sorted(((float(a.nis[b, q, c]), int(a.cand[b, q, c])) for c in range(2)
+                                             if a.cand[b, q, c] >= 0 and a.nis[b, q, c] <= accept), key=lambda x: x[0])]
+                      for q in range(mb)]
+                cands.append(cb)
+                sels.append(sorted({j for c in cb for j in c}))
+            jm, jc, _ = self.joint(sels)
+            qs = self.noise()[1]
         out, idx, zr, zb = [], [], [], []
         for b in range(self.batch):
             mb = int(mm[b])
-            assign, new_obs, _dropped = resolve_associations(a.cand[b, :mb], a.nis[b, :mb], a.min_nis[b, :mb], accept, create)
+            if joint:
+                assign, _nis, _done = joint_compatibility(R[b, :mb], Bg[b, :mb], cands[b], sels[b], jm[b], jc[b],
+                                                          (qs[b] ** 2, qs[b] ** 2))
+                rest = np.flatnonzero(assign < 0)
+                new_obs = [int(q) for q in rest if a.cand[b, q, 0] < 0 or a.min_nis[b, q] > create]
+            else:
+                assign, new_obs, _dropped = resolve_associations(a.cand[b, :mb], a.nis[b, :mb], a.min_nis[b, :mb], accept, create)
             if len(new_obs):
                 n_lm = (self.size(b) - 3) // 2
                 if 3 + 2 * (n_lm + len(new_obs)) > self.n_max:

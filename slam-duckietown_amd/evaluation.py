@@ -468,3 +468,39 @@ def association_check(f, idx, ranges, bearings, margin: float = 0.0):
             if best != j or d_other - d[b, q, j] < margin:
                 flags.append(AssociationFlag(b, q, j, best, float(d[b, q, j]), d_other))
     return flags
+
+
+def landmark_separation(f, pairs, b: int = 0):
+    """How far apart are landmarks i and j of trajectory b, and is that significant?  For index pairs ``(i, j)`` returns
+    ``(distance (K,), sigma (K,), mahalanobis (K,))``: the Euclidean distance of the two means, its first-order standard
+    deviation from the 4 x 4 joint covariance of the two landmarks (the cross-covariance included -- two landmarks mapped
+    from the same poses are far better known relative to each other than their marginals say), and the Mahalanobis
+    separation  d^T (P_ii + P_jj - P_ij - P_ji)^-1 d,  d = l_i - l_j  (chi-square with 2 degrees of freedom if both were
+    the same landmark: the test a duplicate-landmark detector needs).  Read-only: ``EkfSlam.joint`` calls over the distinct
+    landmarks, EKF_JMAX // 2 pairs at a time; no covariance pass."""
+    from .ekf_bindings import EKF_JMAX
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    K = pairs.shape[0]
+    dist, sigma, maha = np.empty(K), np.empty(K), np.empty(K)
+    per = EKF_JMAX // 2
+    for k0 in range(0, K, per):
+        chunk = pairs[k0:k0 + per]
+        lms = sorted({int(x) for x in chunk.ravel()})
+        place = {j: 3 + 2 * p for p, j in enumerate(lms)}
+        mean, cov = f.joint(lms, b)
+        for t, (i, j) in enumerate(chunk):
+            if i == j:
+                raise ValueError(f"landmark_separation: pair ({i}, {j}) names one landmark twice")
+            a, c = place[int(i)], place[int(j)]
+            s = [a, a + 1, c, c + 1]
+            P4 = cov[np.ix_(s, s)]
+            d = mean[a:a + 2] - mean[c:c + 2]
+            r = float(np.hypot(d[0], d[1]))
+            D = np.array([[1.0, 0.0, -1.0, 0.0], [0.0, 1.0, 0.0, -1.0]])
+            Pd = D @ P4 @ D.T                                  # P_ii + P_jj - P_ij - P_ji
+            with np.errstate(divide="ignore", invalid="ignore"):
+                g = d / r                                      # gradient of |d| by d
+            dist[k0 + t] = r
+            sigma[k0 + t] = math.sqrt(max(float(g @ Pd @ g), 0.0)) if r > 0.0 else float("nan")
+            maha[k0 + t] = float(d @ np.linalg.solve(Pd, d))
+    return dist, sigma, maha

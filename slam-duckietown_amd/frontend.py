@@ -130,3 +130,120 @@ def resolve_associations(cand, nis, min_nis, accept: float, create: float):
         else:
             dropped.append(q)
     return assign, sorted(new_obs), sorted(dropped)
+
+
+def wrap_pi(a):
+    """(a + pi) % 2 pi - pi with NumPy remainder semantics, [-pi, pi): how the device wraps a bearing residual."""
+    return (a + np.pi) % (2.0 * np.pi) - np.pi
+
+
+def measurement_h(pose, landmark_xy):
+    """Range/bearing model of one landmark seen from ``pose`` (x, y, theta): ``(zhat (2,), H5 (2, 5))``, the predicted
+    observation and its Jacobian on (x, y, theta, lx, ly) -- src/replay_no_ros.py:443-469 as the device evaluates them
+    (a landmark at the pose's position gives NaN / inf like the reference's 0/0)."""
+    pose = np.asarray(pose, dtype=np.float64)
+    lm = np.asarray(landmark_xy, dtype=np.float64)
+    dx, dy = lm[0] - pose[0], lm[1] - pose[1]                      # :443
+    q = dx * dx + dy * dy                                          # :446
+    sq = np.sqrt(q)
+    zhat = np.array([sq, np.arctan2(dy, dx) - pose[2]])            # :451-454
+    with np.errstate(divide="ignore", invalid="ignore"):
+        h5 = np.array([[-sq * dx, -sq * dy, 0.0, sq * dx, sq * dy],
+                       [dy, -dx, -q, -dy, dx]], dtype=np.float64) / q    # :466-469
+    return zhat, h5
+
+
+def joint_compatibility(ranges, bearings, candidates, sel, mean, cov, meas_var, confidence: float = 0.99,
+                        max_nodes: int = 20000):
+    """Joint-compatibility branch and bound (Neira & Tardos) for one trajectory's unlabelled observations.
+
+    ``candidates[q]`` lists the landmarks individually plausible for observation q, best first; all are members of ``sel``,
+    the landmark list ``EkfSlam.joint(sel, b)`` returned ``mean`` and ``cov`` for (sub-state [x, y, theta, l_sel0, ...]).
+    ``meas_var`` (2,) is the diagonal of the trajectory's Q: ``noise()[1][b] ** 2`` twice.
+
+    Depth first over the observations in order; each tries its candidates that no earlier one holds, in the given order,
+    then "unmatched".  A hypothesis with p pairings is feasible when its joint NIS  y^T (H cov H^T + I_p (x) Q)^-1 y  --
+    all innovations stacked, bearings wrapped, H the rows of ``measurement_h`` scattered to the sub-state's columns -- is
+    <= the chi-square quantile of 2p degrees of freedom at ``confidence``; individually plausible pairings that share one
+    pose error the wrong way fail it.  Two cuts, both exact: a branch whose pairings plus the observations left stay below
+    the best count of pairings, and a branch whose joint NIS already exceeds the quantile of the most pairings it can still
+    reach (adding pairings never lowers a joint NIS).  The best hypothesis has the most pairings, then the smaller joint
+    NIS, then is the first found.
+
+    Returns ``(assign (m,) int64 landmark or -1, joint_nis, exhausted)``; ``exhausted`` is False when ``max_nodes`` -- a
+    guard against 3^16 worst cases -- ended the search, the best hypothesis so far is still returned."""
+    from scipy.stats import chi2
+    ranges = np.asarray(ranges, dtype=np.float64).reshape(-1)
+    bearings = np.asarray(bearings, dtype=np.float64).reshape(-1)
+    sel = [int(j) for j in np.asarray(sel).reshape(-1)]
+    mean = np.asarray(mean, dtype=np.float64)
+    cov = np.asarray(cov, dtype=np.float64)
+    meas_var = np.asarray(meas_var, dtype=np.float64).reshape(2)
+    m = len(ranges)
+    ns = 3 + 2 * len(sel)
+    place = {j: p for p, j in enumerate(sel)}
+    cands = [[int(j) for j in c] for c in candidates]
+    if len(cands) != m or len(bearings) != m:
+        raise ValueError("joint_compatibility: one candidate list and one bearing per observation expected")
+    for c in cands:
+        for j in c:
+            if j not in place:
+                raise ValueError(f"joint_compatibility: candidate {j} is not a member of sel")
+    # every (observation, candidate) pairing once: its innovation and its two rows of H on the sub-state
+    rows = {}
+    for q, c in enumerate(cands):
+        for j in c:
+            t = 3 + 2 * place[j]
+            zhat, h5 = measurement_h(mean[:3], mean[t:t + 2])
+            H = np.zeros((2, ns))
+            H[:, :3] = h5[:, :3]
+            H[:, t:t + 2] = h5[:, 3:]
+            rows[q, j] = (np.array([ranges[q] - zhat[0], wrap_pi(bearings[q] - zhat[1])]), H)
+    limit = [0.0] + [float(chi2.ppf(confidence, 2 * p)) for p in range(1, m + 1)]
+    P = cov[:ns, :ns]
+
+    def joint_nis(pairs):
+        if not pairs:
+            return 0.0
+        y = np.concatenate([rows[p][0] for p in pairs])
+        H = np.vstack([rows[p][1] for p in pairs])
+        S = H @ P @ H.T + np.diag(np.tile(meas_var, len(pairs)))
+        return float(y @ np.linalg.solve(S, y))
+
+    best = {"pairs": None, "nis": 0.0}
+    nodes = [0]
+    exhausted = [True]
+
+    def descend(q, pairs, nis):
+        if q == m:
+            if not nis <= limit[len(pairs)]:                 # (a NaN is infeasible)
+                return
+            if best["pairs"] is None or len(pairs) > len(best["pairs"]) or (len(pairs) == len(best["pairs"]) and nis < best["nis"]):
+                best["pairs"], best["nis"] = list(pairs), nis
+            return
+        if best["pairs"] is not None and len(pairs) + (m - q) < len(best["pairs"]):   # cannot reach the best count any more
+            return
+        used = {j for _, j in pairs}
+        for j in cands[q] + [-1]:
+            if j in used:
+                continue
+            if nodes[0] >= max_nodes:
+                exhausted[0] = False
+                return
+            nodes[0] += 1
+            if j < 0:
+                descend(q + 1, pairs, nis)
+            else:
+                pairs.append((q, j))
+                v = joint_nis(pairs)
+                if v <= limit[len(pairs) + (m - q - 1)]:     # some completion may still be feasible
+                    descend(q + 1, pairs, v)
+                pairs.pop()
+            if not exhausted[0]:
+                return
+
+    descend(0, [], 0.0)
+    assign = np.full(m, -1, dtype=np.int64)
+    for q, j in best["pairs"] or []:
+        assign[q] = j
+    return assign, best["nis"], exhausted[0]
