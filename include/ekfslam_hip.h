@@ -257,6 +257,42 @@ int ekf_add_landmarks(ekf_handle *h, int b, int first_index, const double *xy, i
  * EKF_ERR_STATE under EKF_FLAG_INTERNAL or after a call failed half way (as the downloads). */
 int ekf_remove_landmarks(ekf_handle *h, int b, const int *landmarks, int k);
 
+/* Direct measurements: tell the filter something in the world frame -- z = x[s] + v, v ~ N(0, R), s a set of state indices.
+ * A fix's target is EKF_DIRECT_POSE (x, y, theta from an external localiser, a relocalisation hit, a known start: 3 rows),
+ * EKF_DIRECT_POSITION (x, y only: 2 rows) or a landmark index l >= 0 (a surveyed landmark's x, y: 2 rows; anchoring two of them
+ * fixes the gauge of the whole map).  Trajectories [b0, b0+count) each bring m[bi] <= stride <= EKF_MMAX fixes: target[bi*stride
+ * + j], z (count x stride x 3; the third entry is ignored for 2-row targets) and R (count x stride x 9, row-major 3 x 3: the
+ * leading d x d block is the fix's noise covariance, only its upper triangle is read).  All fixes of a trajectory are applied
+ * JOINTLY (independent noise: the same posterior as one after the other): their D = sum of d rows are stacked in the order
+ * given, R block-diagonal over the fixes,
+ *     y = z - mu[s] (the theta row wrapped to [-pi, pi)),  S = P[s,s] + R,  K = P[:,s] S^-1,  mu += K y,  P -= K S K^T
+ * on the stored upper triangle; theta of the mean is not re-wrapped (the landmark update does not re-wrap it either).  P is the
+ * CURRENT covariance: the pending update is applied first -- a covariance pass the caller pays for, as with ekf_add_landmarks
+ * and ekf_remove_landmarks -- then one kernel (k_direct, a workgroup per trajectory: gather of P[s,:], Cholesky of S, the
+ * mean, the update's D ranks) and ONE more covariance pass apply the fixes of the whole call.
+ * nis[bi] = y^T S^-1 y and dof[bi] = D (either may be NULL; 0 and 0 for m[bi] = 0).  gate (count doubles; NULL or INFINITY:
+ * none): a trajectory whose NIS exceeds gate[bi] is REJECTED AS A WHOLE, its mean and covariance stay bit for bit (the chi-square
+ * quantile of D degrees of freedom is the natural threshold; the handle's NIS gate is one of 2 degrees and does not apply
+ * here).  A trajectory whose S fails to factor (a pivot <= 0 or not finite) is rejected the same way, on the device, and gets
+ * EKF_FLAG_NONFINITE.  applied[bi] (may be NULL): 1 applied, 0 rejected or m[bi] = 0.  A trajectory with m[bi] = 0, or outside
+ * the range, is untouched bit for bit (the pass adds exact zeros to it).
+ * Blocking, and stream-ordered behind everything enqueued.  Writes no innovation-log or pose-log row (like ekf_add_landmarks
+ * and ekf_remove_landmarks), changes no gate counter, noise row, size, tag table or uploaded stream (which stays runnable) and
+ * leaves the active bound as it is: a direct update changes P(a, b) only where both a and b are correlated with s, it creates no
+ * correlation (a fix on a never-observed landmark touches its own 2 x 2 block and mean only).  Afterwards nothing is pending:
+ * a following ekf_stream_run forms fused cadences as after any flush; a handle on the small-state path stays on it.
+ * EKF_ERR_ARG (nothing changed, the handle usable): a bad trajectory range, stride outside 1..EKF_MMAX, m[bi] outside
+ * 0..stride, a landmark index outside that trajectory's map, the same target twice in one trajectory, EKF_DIRECT_POSE and
+ * EKF_DIRECT_POSITION (or one of them twice) in one trajectory, a non-finite z, R or gate, gate[bi] <= 0, an R block that is
+ * not positive definite (leading minors of the d x d block), NULL target, z, R or m.  EKF_ERR_STATE if a trajectory of the
+ * range carries EKF_FLAG_INTERNAL or an earlier call failed half way (as the downloads).
+ * Not measured yet (tools/direct_update_time.py writes profiles/direct_update.txt). */
+#define EKF_DIRECT_POSE (-1)     /* target: x, y, theta (3 rows) */
+#define EKF_DIRECT_POSITION (-2) /* target: x, y        (2 rows) */
+                                 /* target l >= 0: landmark l's x, y (2 rows) */
+int ekf_update_direct(ekf_handle *h, int b0, int count, const int *target, const double *z, const double *R,
+                      const int *m, int stride, const double *gate, double *nis, int *dof, int *applied);
+
 /* Fork / checkpoint on the device: copy the complete filter state of trajectory src_b[i] of `src` to trajectory dst_b[i] of
  * `dst`, i < k, without leaving HBM.  src == dst is allowed (fork inside a bank); otherwise both handles must be on the same
  * device.  One source may fan out to many destinations (one launch for all pairs; a source tile is read once for up to 32 of
@@ -373,7 +409,7 @@ int ekf_profile_read(ekf_handle *h, double *pass_ms_total, long long *pass_launc
 long long ekf_profile_passes(ekf_handle *h);
 /* With ekf_set_option("profile_kernels", 1) (a diagnostic run: every record costs its stream ~6 us) the other launches of a
  * fused cadence carry event pairs too: cls 1 the solve launch, 2 the chain (or look-ahead gather) launch, 3 the panel launch,
- * 0 the pass.  Does not reset: read before ekf_profile_read. */
+ * 0 the pass; 4 the k_direct launch of ekf_update_direct.  Does not reset: read before ekf_profile_read. */
 int ekf_profile_read_class(ekf_handle *h, int cls, double *ms_total, long long *launches);
 /* Options: name (default, allowed values) meaning.  Unknown names and values out of range fail with EKF_ERR_ARG.
  *   "flush_every"         (0, 0..64)    steps per covariance pass; 0 = auto, by "rank_limit"

@@ -72,6 +72,8 @@ void launch_joint(hipStream_t, const double*, const double*, const double*, cons
                   const SolveOut*, int, long, int, int, int, int, int, int, const int*, double*, double*);
 void launch_remove(hipStream_t, int, double*, double*, const int*, const int*, const int*, unsigned*, unsigned*, int, int, int, int,
                    int, unsigned, int, long);
+void launch_direct(hipStream_t, int, double*, double*, double*, double*, double*, const int*, SolveOut*, unsigned*, unsigned*,
+                   const int*, const double*, double*, int, long, int, int);
 void launch_copy_traj(hipStream_t, bool, const double*, double*, const double*, double*, int*, const unsigned*, unsigned*, const int*,
                       int, int, int, long, int, long);
 }  // namespace ekf
@@ -278,6 +280,12 @@ struct ekf_handle : ekf::HostPlan {
   // ekf_copy_trajectories (allocated on first use, in the DESTINATION handle): the launch's table of groups (plan_copy)
   int* dcp_tab = nullptr;
   size_t cp_cap = 0;
+  // ekf_update_direct (allocated on first use): per trajectory of the bank the row plan (DIRECT_INTS ints), the measurements
+  // (DIRECT_DBLS doubles) and the results (NIS, applied) of k_direct, and their host sides
+  double* ddirect = nullptr;
+  ekf::DirectPlan direct_plan;
+  std::vector<int> direct_ints;
+  std::vector<double> direct_dbls, direct_out;
   std::string err;
 };
 
@@ -359,7 +367,7 @@ static void free_all(ekf_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   void* ptrs[] = {h->dP, h->dmu2[0], h->dmu2[1], h->dV, h->dW, h->ddacc2[0], h->ddacc2[1], h->dscratch, h->dn, h->dflags, h->dso, h->dfac,
                   h->d_ring, h->d_stream, h->dF, h->dQ, h->dTmp, h->dPlin, h->dtagmap, h->dneff, h->d_det, h->d_assoc_step, h->dfloor, h->dqueue, h->dready, h->dmbox,
-                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dassq, h->djoint, h->dinnov, h->dinnov_m, h->dgate, h->dnoise, h->drm_tab, h->drm_flag, h->dpose, h->dcp_tab};
+                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dassq, h->djoint, h->dinnov, h->dinnov_m, h->dgate, h->dnoise, h->drm_tab, h->drm_flag, h->dpose, h->dcp_tab, h->ddirect};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
   if (h->h_det) (void)hipHostFree(h->h_det);
@@ -1418,6 +1426,72 @@ static int flush_pending(ekf_handle* h, hipStream_t st, const CadOut* wv) {
   return EKF_OK;
 }
 static int flush_pending(ekf_handle* h) { return flush_pending(h, nullptr); }
+
+// Direct measurements (k_direct, ekf_direct.hip): apply what is pending, let k_direct form the mean and the update's ranks --
+// V = P[s, :], W = -(S^-1 V)^T, zeros for every trajectory that brings nothing or is rejected -- from P_base, then run the
+// covariance pass on them as on any pending ranks.  The launch covers the bank: it also leaves each trajectory's active bound
+// where the pass reads it (dso[b].neff may be stale, e.g. behind an upload) and zeroes the pending pose noise the pass adds.
+extern "C" int ekf_update_direct(ekf_handle* h, int b0, int count, const int* target, const double* z, const double* R,
+                                 const int* m, int stride, const double* gate, double* nis, int* dof, int* applied) {
+  if (int rc = check_b(h, 0, "ekf_update_direct")) return rc;        // (refreshes the sizes a device-side association grew)
+  DirectPlan& dp = h->direct_plan;
+  if (const char* why = plan_direct(h, b0, count, target, z, R, m, stride, gate, dp))
+    return fail(h, EKF_ERR_ARG, std::string("ekf_update_direct: ") + why);
+  HIP_TRY(h, hipSetDevice(h->device));
+  for (int b = b0; b < b0 + count; ++b)
+    if (int rc = check_internal(h, b, "ekf_update_direct")) return rc;
+  const size_t B = (size_t)h->batch;
+  const size_t int_words = (B * DIRECT_INTS + 1) / 2;  // layout (doubles): the plan (ints, rounded up), measurements, results
+  if (!h->ddirect) HIP_TRY(h, hipMalloc(&h->ddirect, sizeof(double) * (int_words + B * DIRECT_DBLS + 2 * B)));
+  if (int rc = flush_pending(h)) return rc;
+  h->direct_ints.assign(B * DIRECT_INTS, 0);
+  h->direct_dbls.assign(B * DIRECT_DBLS, 0.0);
+  h->direct_out.assign(2 * B, 0.0);
+  for (size_t b = 0; b < B; ++b) {
+    int* pi = h->direct_ints.data() + b * DIRECT_INTS;
+    pi[1] = h->opt_active_bound ? std::min(h->neff[b], h->n[b]) : h->n[b];
+    for (int k = 0; k < DIRECT_ROWS; ++k) pi[2 + k] = -1;
+  }
+  for (int bi = 0; bi < count; ++bi) {
+    int* pi = h->direct_ints.data() + (size_t)(b0 + bi) * DIRECT_INTS;
+    double* pd = h->direct_dbls.data() + (size_t)(b0 + bi) * DIRECT_DBLS;
+    pi[0] = dp.D[bi];
+    std::copy_n(dp.s.data() + (size_t)bi * DIRECT_ROWS, DIRECT_ROWS, pi + 2);
+    std::copy_n(dp.src.data() + (size_t)bi * DIRECT_ROWS, DIRECT_ROWS, pi + 2 + DIRECT_ROWS);
+    std::copy_n(z + (size_t)bi * stride * 3, (size_t)m[bi] * 3, pd);
+    std::copy_n(R + (size_t)bi * stride * 9, (size_t)m[bi] * 9, pd + 3 * MMAX);
+    pd[DIRECT_DBLS - 2] = gate ? gate[bi] : INFINITY;
+  }
+  if (dp.kpad > 0) {
+    int* dplan = reinterpret_cast<int*>(h->ddirect);
+    double* dmeas = h->ddirect + int_words;
+    double* dout = dmeas + B * DIRECT_DBLS;
+    HIP_TRY(h, hipMemcpyAsync(dplan, h->direct_ints.data(), sizeof(int) * h->direct_ints.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(dmeas, h->direct_dbls.data(), sizeof(double) * h->direct_dbls.size(), hipMemcpyHostToDevice, h->stream));
+    ProfBracket pb;
+    if (int rc = prof_open(h, 4, h->stream, &pb)) return rc;
+    launch_direct(h->stream, direct_rows_cap(dp.kpad), h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dmu2[h->cur], h->dn, h->dso,
+                  h->dflags, h->dqueue, dplan, dmeas, dout, h->ld, h->pstride, h->batch, dp.kpad);
+    if (int rc = prof_close(h, &pb)) return rc;
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(h->direct_out.data(), dout, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->stream));
+    // the pass: the ranks k_direct left, over the bounds it left (neff_enq mirrors dso[b].neff for the planner)
+    for (size_t b = 0; b < B; ++b) h->neff_enq[b] = h->direct_ints[b * DIRECT_INTS + 1];
+    h->pending_k = dp.kpad;
+    if (int rc = flush_pending(h)) {
+      for (int b = b0; b < b0 + count; ++b) h->host_bad[b] = 1;       // (the mean has moved, the covariance has not)
+      return rc;
+    }
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (int bi = 0; bi < count; ++bi) {
+    const bool any = dp.D[bi] > 0;
+    if (nis) nis[bi] = any ? h->direct_out[2 * (size_t)(b0 + bi)] : 0.0;
+    if (dof) dof[bi] = dp.D[bi];
+    if (applied) applied[bi] = any && h->direct_out[2 * (size_t)(b0 + bi) + 1] != 0.0 ? 1 : 0;
+  }
+  return EKF_OK;
+}
 
 // The small-state path (ekf_small.hip, ekf_host_plan.h: small_path): `nsteps` steps per trajectory in one launch.
 static int enqueue_small(ekf_handle* h, const StepIn* d_in, int nsteps) {

@@ -43,6 +43,14 @@ constexpr int RM_THREADS = 256;         // k_remove (ekf_remove.hip): threads pe
 constexpr int AQ_CHUNK = 64;            // k_assoc_query (ekf_associate.hip): landmarks per workgroup, one per lane of a wave
 constexpr int JQ_TILE = 32;             // k_joint (ekf_joint.hip): rows / columns of a workgroup's tile of the sub-matrix
 constexpr int JMAX = EKF_JMAX;          // landmarks per trajectory in one ekf_download_joint
+// ekf_update_direct (k_direct, ekf_direct.hip): a trajectory brings up to MMAX fixes, at most one of them a pose fix of 3 rows:
+// 3 + 2 (MMAX - 1) = 33 rows, 36 as whole k-tiles.  What the launch reads per trajectory of the BANK (trajectories outside the
+// call's range carry D = 0): DIRECT_INTS ints {D, active bound, state index of row k (DIRECT_ROWS), 4 * fix + component of row k
+// (DIRECT_ROWS)} and DIRECT_DBLS doubles {z (MMAX x 3), R (MMAX x 9, row-major 3 x 3 per fix), gate, pad}.
+constexpr int DIRECT_ROWS = 36;
+constexpr int DIRECT_INTS = 2 + 2 * DIRECT_ROWS;
+constexpr int DIRECT_DBLS = MMAX * 12 + 2;
+static_assert(3 + 2 * (MMAX - 1) <= DIRECT_ROWS && DIRECT_ROWS % 4 == 0 && DIRECT_ROWS <= KTOT, "a direct update's rows fit the pending ranks");
 __host__ __device__ __forceinline__ int p_lds(int ld) { return ld < PPW ? ld : PPW; }
 __host__ __device__ __forceinline__ long p_col(int ld, int j) { return (long)(j >> 12) * ((long)ld * PPW) + (j & (PPW - 1)); }
 // the same as a 32-bit byte offset (ekf_create bounds one covariance by 4 GiB)

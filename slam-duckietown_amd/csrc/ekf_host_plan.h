@@ -669,6 +669,73 @@ inline const char* plan_remove(const HostPlan* h, int b0, int nb, const int* lm,
   return nullptr;
 }
 
+// ekf_update_direct (k_direct, ekf_direct.hip): the fixes of trajectories [b0, b0 + count) checked -- the range inside the
+// bank, stride in 1..EKF_MMAX, m[bi] in 0..stride, every target a landmark of its trajectory's map or EKF_DIRECT_POSE /
+// EKF_DIRECT_POSITION, no target twice and not both pose kinds in one trajectory, finite z, R and gate, gate > 0, every R block
+// positive definite (leading minors of its upper triangle) -- and turned into the row plan: per trajectory of the range its
+// D = sum of d stacked rows in the order given, the state index s of each row and where its measurement lives (4 * fix +
+// component), and `kpad`, the largest D padded to a whole k-tile (what the covariance pass behind the launch applies).
+// Returns nullptr, or what is wrong with the arguments (then nothing of `dp` is to be used).
+struct DirectPlan {
+  int kpad = 0;
+  std::vector<int> D;              // count
+  std::vector<int> s, src;         // count x DIRECT_ROWS (-1 / 0 beyond D)
+};
+inline int direct_rows(int target) { return target == EKF_DIRECT_POSE ? 3 : 2; }
+inline const char* plan_direct(const HostPlan* h, int b0, int count, const int* target, const double* z, const double* R,
+                               const int* m, int stride, const double* gate, DirectPlan& dp) {
+  if (b0 < 0 || count <= 0 || b0 > h->batch - count) return "trajectory range outside the bank";
+  if (stride < 1 || stride > MMAX) return "stride outside 1..EKF_MMAX";
+  if (!target || !z || !R || !m) return "NULL target, z, R or m";
+  dp.kpad = 0;
+  dp.D.assign((size_t)count, 0);
+  dp.s.assign((size_t)count * DIRECT_ROWS, -1);
+  dp.src.assign((size_t)count * DIRECT_ROWS, 0);
+  std::vector<int> seen;
+  for (int bi = 0; bi < count; ++bi) {
+    const int nl = (h->n[b0 + bi] - 3) / 2, mb = m[bi];
+    if (mb < 0 || mb > stride) return "m[b] outside 0..stride";
+    if (gate && !(gate[bi] > 0.0)) return "gate[b] must be > 0 (INFINITY: none) and not NaN";
+    seen.clear();
+    bool posed = false;
+    int D = 0;
+    for (int j = 0; j < mb; ++j) {
+      const size_t f = (size_t)bi * stride + j;
+      const int t = target[f], d = direct_rows(t);
+      if (t < EKF_DIRECT_POSITION || t >= nl) return "target is neither a landmark of the trajectory's map nor a pose fix";
+      if (t < 0) {
+        if (posed) return "more than one pose / position fix in one trajectory";
+        posed = true;
+      } else {
+        if (std::find(seen.begin(), seen.end(), t) != seen.end()) return "landmark target named twice in one trajectory";
+        seen.push_back(t);
+      }
+      const double* zz = z + 3 * f;
+      const double* rr = R + 9 * f;
+      for (int a = 0; a < d; ++a) {
+        if (!std::isfinite(zz[a])) return "non-finite z";
+        for (int c = a; c < d; ++c)
+          if (!std::isfinite(rr[3 * a + c])) return "non-finite R";
+      }
+      const double m2 = rr[0] * rr[4] - rr[1] * rr[1];
+      bool pd = rr[0] > 0.0 && m2 > 0.0;
+      if (pd && d == 3)
+        pd = rr[0] * (rr[4] * rr[8] - rr[5] * rr[5]) - rr[1] * (rr[1] * rr[8] - rr[5] * rr[2]) + rr[2] * (rr[1] * rr[5] - rr[4] * rr[2]) > 0.0;
+      if (!pd) return "an R block is not positive definite";
+      if (D + d > DIRECT_ROWS) return "too many rows in one trajectory";
+      for (int a = 0; a < d; ++a, ++D) {
+        dp.s[(size_t)bi * DIRECT_ROWS + D] = t < 0 ? a : 3 + 2 * t + a;
+        dp.src[(size_t)bi * DIRECT_ROWS + D] = 4 * j + a;
+      }
+    }
+    dp.D[bi] = D;
+    dp.kpad = std::max(dp.kpad, (D + 3) & ~3);
+  }
+  return nullptr;
+}
+// the instantiation of k_direct that serves `kpad` rows: the smallest compile-time row count that holds them
+inline int direct_rows_cap(int kpad) { return kpad <= 4 ? 4 : kpad <= 8 ? 8 : kpad <= 16 ? 16 : DIRECT_ROWS; }
+
 // ekf_copy_trajectories (k_copy_traj, ekf_copy.hip): the k pairs (src_b[i] of `src` -> dst_b[i] of `dst`) checked -- indices
 // inside their banks, no destination twice, inside one handle no trajectory both read and written, the same device, every
 // source's size within the destination's n_max -- and grouped by source: a group is one source and up to COPY_FANOUT of its

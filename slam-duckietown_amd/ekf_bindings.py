@@ -36,6 +36,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libekfslam_hip.so"
 EKF_MMAX = 16
 EKF_JMAX = 64                     # landmarks per trajectory in one joint() query
+EKF_DIRECT_POSE = -1              # update_direct target: x, y, theta (3 rows)
+EKF_DIRECT_POSITION = -2          # update_direct target: x, y (2 rows); a target l >= 0 is landmark l's x, y
 EKF_FLAG_NONFINITE = 1
 EKF_FLAG_ASSOC = 2
 EKF_FLAG_INTERNAL = 4             # a bounded wait of a single-launch step timed out: sync()/state()/mean() raise EkfError
@@ -113,6 +115,7 @@ ABI = {
     "ekf_download_marginals": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _ip]),
     "ekf_associate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int]),
     "ekf_download_joint": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, C.c_int, _dp, _dp]),
+    "ekf_update_direct": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _dp, _dp, _ip, C.c_int, _dp, _dp, _ip, _ip]),
     "ekf_state_size": (C.c_int, [C.c_void_p, C.c_int, _ip]),
     "ekf_log_innovations": (C.c_int, [C.c_void_p, C.c_int]),
     "ekf_innovation_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
@@ -331,6 +334,15 @@ class Associations(typing.NamedTuple):
     all_logdet: Optional[np.ndarray] = None   # (B, S, N_hi)  ... and ln det S
 
 
+class DirectUpdate(typing.NamedTuple):
+    """What ``update_direct`` reports per trajectory of the bank: the joint NIS y^T S^-1 y of its fixes, their stacked row
+    count D (the NIS's degrees of freedom) and whether they were applied (False: rejected by the gate or a singular S, or
+    the trajectory brought no fix)."""
+    nis: np.ndarray        # (B,)
+    dof: np.ndarray        # (B,) int32
+    applied: np.ndarray    # (B,) bool
+
+
 class EkfSlam:
     """A bank of ``batch`` independent EKF-SLAM filters resident on one MI355X.
 
@@ -533,6 +545,90 @@ class EkfSlam:
             n = 3 + 2 * int(kk[0])
             return mean[0, :n], cov[0, :n, :n]
         return mean, cov, kk
+
+    # -- direct measurements -------------------------------------------------------------------
+    @staticmethod
+    def _chi2_gate(confidence, dof):
+        from scipy.stats import chi2
+        if not 0.0 < confidence < 1.0:
+            raise ValueError("confidence must lie in (0, 1)")
+        return np.where(np.asarray(dof) > 0, chi2.ppf(confidence, np.maximum(dof, 1)), np.inf)
+
+    def update_direct(self, targets, z, R, m=None, gate=None) -> "DirectUpdate":
+        """Direct measurements ``z = x[s] + v, v ~ N(0, R)`` of the whole bank in one call (``ekf_update_direct``): per
+        trajectory a list of targets -- ``EKF_DIRECT_POSE`` (x, y, theta), ``EKF_DIRECT_POSITION`` (x, y) or a landmark index
+        (its x, y) --, for each its measurement ``z`` (3 or 2 values) and noise covariance ``R`` (3 x 3 or 2 x 2).  All fixes of
+        a trajectory are applied jointly.  ``targets`` / ``z`` / ``R`` are one ragged list per trajectory (a flat list for a
+        single trajectory), or padded arrays (B, S), (B, S, 3), (B, S, 3, 3) with ``m`` (B,) counts.  ``gate`` (scalar or (B,),
+        None: no gate): a trajectory whose joint NIS exceeds it is rejected as a whole.  The pending update is applied first
+        (a covariance pass), the fixes cost one kernel and one more pass whatever their number."""
+        B = self.batch
+        if m is None:
+            if B == 1 and (len(targets) == 0 or np.ndim(targets[0]) == 0):
+                targets, z, R = (targets,), (z,), (R,)
+            if len(targets) != B or len(z) != B or len(R) != B:
+                raise ValueError("update_direct: one list of targets, z and R per trajectory expected")
+            mm = np.array([len(t) for t in targets], dtype=np.int32)
+            stride = max(1, int(mm.max()))
+            T = np.zeros((B, stride), dtype=np.int32)
+            Z, RR = np.zeros((B, stride, 3)), np.zeros((B, stride, 3, 3))
+            for b in range(B):
+                if len(z[b]) != mm[b] or len(R[b]) != mm[b]:
+                    raise ValueError("update_direct: targets / z / R lengths differ")
+                for j in range(mm[b]):
+                    d = 3 if int(targets[b][j]) == EKF_DIRECT_POSE else 2
+                    T[b, j] = int(targets[b][j])
+                    zj, Rj = np.asarray(z[b][j], dtype=np.float64), np.asarray(R[b][j], dtype=np.float64)
+                    if zj.ndim != 1 or Rj.ndim != 2 or len(zj) < d or min(Rj.shape) < d:
+                        raise ValueError(f"update_direct: a {d}-row fix needs {d} values and a {d} x {d} covariance")
+                    Z[b, j, :d] = zj[:d]                     # (a padded 3-vector / 3 x 3 block is taken by its leading part)
+                    RR[b, j, :d, :d] = Rj[:d, :d]
+        else:
+            T = _i32(targets)
+            stride = T.shape[1] if T.ndim == 2 else 0
+            Z, RR, mm = _f64(z, (B, stride, 3)), _f64(R, (B, stride, 3, 3)), _i32(m)
+            if T.shape != (B, stride) or mm.shape != (B,) or stride < 1:
+                raise ValueError("update_direct: (B, S) targets, (B, S, 3) z, (B, S, 3, 3) R and (B,) m expected")
+        if stride > EKF_MMAX:
+            raise ValueError(f"update_direct: at most EKF_MMAX = {EKF_MMAX} fixes per trajectory, got {stride}")
+        g = None
+        if gate is not None:
+            g = np.empty(B)
+            self._per_traj(gate, "gate", g)
+        nis, dof, applied = np.empty(B), np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
+        self._check(self._lib.ekf_update_direct(self._h, 0, B, _p(T, _ip), _p(Z), _p(RR), _p(mm, _ip), stride,
+                                                _p(g) if g is not None else None, _p(nis), _p(dof, _ip), _p(applied, _ip)))
+        return DirectUpdate(nis, dof, applied.astype(bool))
+
+    def fix_pose(self, pose, cov, b: Optional[int] = None, position_only: bool = False, confidence: Optional[float] = None):
+        """An absolute pose fix [x, y, theta] with covariance `cov` (3 x 3) -- or, ``position_only``, [x, y] with a 2 x 2
+        one.  ``b`` None: a row of `pose` (and a `cov`, or one for all) per trajectory; else trajectory b alone.
+        ``confidence`` gates the fix at the chi-square quantile of its 3 (2) degrees of freedom.  Returns ``DirectUpdate``."""
+        d = 2 if position_only else 3
+        bs = list(range(self.batch)) if b is None else [int(b)]
+        pose = np.broadcast_to(np.asarray(pose, dtype=np.float64), (len(bs), d))
+        cov = np.broadcast_to(np.asarray(cov, dtype=np.float64), (len(bs), d, d))
+        tg = EKF_DIRECT_POSITION if position_only else EKF_DIRECT_POSE
+        targets, z, R = [[] for _ in range(self.batch)], [[] for _ in range(self.batch)], [[] for _ in range(self.batch)]
+        for i, t in enumerate(bs):
+            targets[t], z[t], R[t] = [tg], [pose[i]], [cov[i]]
+        gate = None if confidence is None else self._chi2_gate(confidence, np.array([len(x) * d for x in targets]))
+        return self.update_direct(targets, z, R, gate=gate)
+
+    def anchor_landmarks(self, landmarks, xy, cov, b: Optional[int] = None, confidence: Optional[float] = None):
+        """Surveyed landmarks: landmark ``landmarks[j]`` is known to lie at ``xy[j]`` with covariance `cov` (2 x 2, one for
+        all, or one per landmark; at most EKF_MMAX per call).  ``b`` None: the same survey for every trajectory of the bank;
+        else trajectory b alone.  Two anchored landmarks fix the gauge of the whole map.  ``confidence`` gates the joint update
+        at the chi-square quantile of its 2 k degrees of freedom.  Returns ``DirectUpdate``."""
+        lm = [int(j) for j in np.asarray(landmarks).reshape(-1)]
+        xy = _f64(xy, (len(lm), 2))
+        cov = np.broadcast_to(np.asarray(cov, dtype=np.float64), (len(lm), 2, 2))
+        bs = list(range(self.batch)) if b is None else [int(b)]
+        targets, z, R = [[] for _ in range(self.batch)], [[] for _ in range(self.batch)], [[] for _ in range(self.batch)]
+        for t in bs:
+            targets[t], z[t], R[t] = lm, list(xy), list(cov)
+        gate = None if confidence is None else self._chi2_gate(confidence, np.array([2 * len(x) for x in targets]))
+        return self.update_direct(targets, z, R, gate=gate)
 
     def _unlabelled(self, ranges, bearings, m):
         """Unlabelled observations as padded (B, stride) float64 arrays + m (B,) int32: (B, S) arrays with `m` (default: S
@@ -1095,7 +1191,8 @@ class EkfSlam:
         return ms.value, cnt.value
 
     def profile_read_class(self, cls: int):
-        """(total ms, number) of the bracketed launches of class `cls` (1 solve, 2 chain / gather, 3 panel; needs the option
+        """(total ms, number) of the bracketed launches of class `cls` (1 solve, 2 chain / gather, 3 panel, 4 the k_direct launch of
+        update_direct; needs the option
         "profile_kernels"); read before `profile_read`, which resets."""
         ms, cnt = C.c_double(), C.c_longlong()
         self._check(self._lib.ekf_profile_read_class(self._h, int(cls), C.byref(ms), C.byref(cnt)))
