@@ -5,8 +5,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "ekf_device.h"
@@ -62,14 +64,11 @@ long cadence_gbuf_doubles();
 void launch_panels_cad(hipStream_t, double*, double*, double*, const double*, double*, const int*, const CadOut*,
                        SolveOut*, unsigned*, int, long, int, int, int, const double*, double*, unsigned*, unsigned, unsigned*,
                        int, unsigned, bool);
-void launch_marginals(hipStream_t, const double*, const double*, const double*, const double*, const int*, const SolveOut*, int,
-                      long, int, int, int, int, double*, double*);
+void launch_marginals(hipStream_t, const PendingView&, int, double*, double*);
 long assoc_query_part_doubles(int, int, int);
-void launch_assoc_query(hipStream_t, const double*, const double*, const double*, const double*, const double*, const int*,
-                        const SolveOut*, const DeviceConfig&, int, long, int, int, int, int, int, int, const double*, const double*,
+void launch_assoc_query(hipStream_t, const PendingView&, const DeviceConfig&, int, int, int, const double*, const double*,
                         const int*, double*, double*, double*, int*, double*, double*, double*);
-void launch_joint(hipStream_t, const double*, const double*, const double*, const double*, const double*, const int*,
-                  const SolveOut*, int, long, int, int, int, int, int, int, const int*, double*, double*);
+void launch_joint(hipStream_t, const PendingView&, int, int, int, const int*, double*, double*);
 void launch_remove(hipStream_t, int, double*, double*, const int*, const int*, const int*, unsigned*, unsigned*, int, int, int, int,
                    int, unsigned, int, long);
 void launch_direct(hipStream_t, int, double*, double*, double*, double*, double*, const int*, SolveOut*, unsigned*, unsigned*,
@@ -114,6 +113,14 @@ constexpr int RING = 16;
 constexpr int RING_GROUP = 4;             // slots per completion event: an event record between two launches costs the
                                           // stream a barrier packet, ~2 us per online step of a small filter
 constexpr int PACK_SMALL_N = 131;        // states up to 64 landmarks are downloaded by k_pack_small (137 KB of pinned memory)
+
+struct ekf_handle;
+// A device buffer allocated on first use that only grows: `cap` elements at p (nullptr until reserved).
+template <class T> struct DeviceBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  int reserve(ekf_handle* h, hipStream_t st, size_t need, size_t at_least = 0);
+};
 
 struct ekf_handle : ekf::HostPlan {
   DeviceConfig dcfg{};
@@ -229,13 +236,10 @@ struct ekf_handle : ekf::HostPlan {
   std::vector<unsigned> flags_host;
   unsigned* h_flags = nullptr;    // pinned: the sticky flags are read back with a stream-ordered copy
   double* h_pack = nullptr;       // pinned: where k_pack_small leaves a small state (n x n covariance, mean, flags)
-  double* dmarg = nullptr;        // ekf_download_marginals: device staging of destinations that are not pinned (allocated on use)
-  size_t marg_cap = 0;            // ... its size in doubles
-  double* dassq = nullptr;        // ekf_associate: observations, partial records, staging of destinations that are not pinned (allocated on use)
-  size_t assq_cap = 0;            // ... its size in doubles
-  double* djoint = nullptr;       // ekf_download_joint: the selection (ints), staging of destinations that are not pinned (allocated on use)
-  size_t joint_cap = 0;           // ... its size in doubles
-  std::vector<int> joint_sel;     // ... and the selection as the host sorted it (plan_joint_query)
+  // The read-only queries' staging buffer: a query's inputs, then its destinations that are not pinned (StagingPlan).  Every
+  // query synchronises the stream before it returns, so the next one finds the buffer free.
+  DeviceBuf<double> dquery;
+  std::vector<int> joint_sel;     // ekf_download_joint: the selection as the host sorted it (plan_joint_query)
   std::vector<std::pair<int, int>> joint_order;   // ... scratch of the sort (handle-owned: no allocation per query)
   // The innovation log (ekf_log_innovations; nullptr: off): a ring of innov_cap step rows, innov_steps steps logged so far.
   // While an entry point enqueues a logged step, lg_slot is the ring row of its next launch (-1: that launch is not logged) and
@@ -278,8 +282,7 @@ struct ekf_handle : ekf::HostPlan {
   unsigned rm_seq = 0;
   bool stream_stale = false;
   // ekf_copy_trajectories (allocated on first use, in the DESTINATION handle): the launch's table of groups (plan_copy)
-  int* dcp_tab = nullptr;
-  size_t cp_cap = 0;
+  DeviceBuf<int> dcp_tab;
   // ekf_update_direct (allocated on first use): per trajectory of the bank the row plan (DIRECT_INTS ints), the measurements
   // (DIRECT_DBLS doubles) and the results (NIS, applied) of k_direct, and their host sides
   double* ddirect = nullptr;
@@ -294,6 +297,8 @@ static int fail(ekf_handle* h, int code, const std::string& msg) {
   return code;
 }
 
+static int bad_arg(ekf_handle* h, const char* fn, const std::string& why) { return fail(h, EKF_ERR_ARG, std::string(fn) + ": " + why); }
+
 static int flush_pending(ekf_handle* h);
 static int flush_pending(ekf_handle* h, hipStream_t st, const CadOut* wv = nullptr);
 static int materialize(ekf_handle* h, int b);
@@ -304,6 +309,29 @@ static int materialize(ekf_handle* h, int b);
     if (e_ != hipSuccess)                                                                  \
       return fail(h, EKF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
   } while (0)
+
+// Room for `need` elements (a new buffer holds at least `at_least`); the contents are not kept.  The old buffer may still be
+// in use by work in flight on `st`, which is waited for before it is freed.  A failed call leaves the buffer as it was or empty.
+template <class T> int DeviceBuf<T>::reserve(ekf_handle* h, hipStream_t st, size_t need, size_t at_least) {
+  if (need <= cap) return EKF_OK;
+  if (p) HIP_TRY(h, hipStreamSynchronize(st));
+  cap = 0;
+  if (T* old = std::exchange(p, nullptr)) HIP_TRY(h, hipFree(old));
+  const size_t want = std::max(need, at_least);
+  const hipError_t e = hipMalloc(&p, sizeof(T) * want);
+  if (e != hipSuccess) p = nullptr;
+  HIP_TRY(h, e);
+  cap = want;
+  return EKF_OK;
+}
+
+// The device's view of a pinned host allocation (ekf_host_alloc), which a kernel can write in place; nullptr for anything else.
+static void* device_view(void* p) {
+  hipPointerAttribute_t attr{};
+  if (p && hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeHost) return attr.devicePointer;
+  (void)hipGetLastError();                             // (an ordinary pointer is "invalid value" to the query)
+  return nullptr;
+}
 
 // Copies between a host matrix (row-major, `host_pitch` doubles per row) and the block [r0, r0 + rows) x [c0, c0 + cols) of
 // trajectory b's covariance in its device layout (ekf_device.h: row-major up to ld = 4096, column panels of 4096 doubles
@@ -367,7 +395,7 @@ static void free_all(ekf_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   void* ptrs[] = {h->dP, h->dmu2[0], h->dmu2[1], h->dV, h->dW, h->ddacc2[0], h->ddacc2[1], h->dscratch, h->dn, h->dflags, h->dso, h->dfac,
                   h->d_ring, h->d_stream, h->dF, h->dQ, h->dTmp, h->dPlin, h->dtagmap, h->dneff, h->d_det, h->d_assoc_step, h->dfloor, h->dqueue, h->dready, h->dmbox,
-                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dmarg, h->dassq, h->djoint, h->dinnov, h->dinnov_m, h->dgate, h->dnoise, h->drm_tab, h->drm_flag, h->dpose, h->dcp_tab, h->ddirect};
+                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dquery.p, h->dinnov, h->dinnov_m, h->dgate, h->dnoise, h->drm_tab, h->drm_flag, h->dpose, h->dcp_tab.p, h->ddirect};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
   if (h->h_det) (void)hipHostFree(h->h_det);
@@ -614,6 +642,64 @@ static int check_host_bad(ekf_handle* h, const char* fn) {
   return EKF_OK;
 }
 
+static int check_range(ekf_handle* h, const char* fn, int b0, int count) {
+  if (!h) return EKF_ERR_ARG;
+  return bank_range_ok(h, b0, count) ? EKF_OK : bad_arg(h, fn, BANK_RANGE_WHY);
+}
+
+// ---- the read-only queries (ekf_download_marginals, ekf_associate, ekf_download_joint) ----
+// Each reads the filter as the covariance pass would leave it, without running it (PendingView), and writes only its
+// destinations -- pinned ones in place, the others through the handle's staging buffer and one copy each (StagingPlan): nothing
+// of the handle's scheduling state changes.  A query is query_begin, q.add per destination, query_stage, its uploads and
+// launch, query_end.
+struct Query {
+  StagingPlan plan;
+  void *host[STAGE_DSTS], *dev[STAGE_DSTS];            // dev: where the kernels write destination i (nullptr: absent or empty)
+  void add(void* p, size_t words) {
+    host[plan.ndst] = p;
+    dev[plan.ndst] = p && words ? device_view(p) : nullptr;
+    plan.add(p != nullptr, words, dev[plan.ndst] != nullptr);
+  }
+  template <class T> T* out(int i) const { return static_cast<T*>(dev[i]); }
+};
+// The checks in the order a caller sees them: the handle (which refreshes the sizes a device-side association grew), `early`
+// (what is wrong with an argument that the entry point has always tested first; nullptr: nothing), the range, the entry
+// point's own argument checks (`site`: returns its failure), then the trajectories an earlier failure left undefined.
+template <class SiteChecks>
+static int query_begin(ekf_handle* h, const char* fn, int b0, int count, const char* early, SiteChecks site) {
+  if (int rc = check_b(h, 0, fn)) return rc;
+  if (early) return bad_arg(h, fn, early);
+  if (int rc = check_range(h, fn, b0, count)) return rc;
+  if (int rc = site()) return rc;
+  for (int b = b0; b < b0 + count; ++b)
+    if (h->host_bad[b]) return check_internal(h, b, fn);
+  HIP_TRY(h, hipSetDevice(h->device));
+  return EKF_OK;
+}
+// Room for the query's inputs and staged destinations; the inputs start at h->dquery.p.
+static int query_stage(ekf_handle* h, Query& q) {
+  if (int rc = h->dquery.reserve(h, h->stream, plan_staging(q.plan))) return rc;
+  for (int i = 0; i < q.plan.ndst; ++i)
+    if (q.plan.dst[i].staged) q.dev[i] = h->dquery.p + q.plan.dst[i].at;
+  return EKF_OK;
+}
+// Behind the launch: the staged destinations, then the flags (check_internal's copy), and the query's one synchronisation.
+static int query_end(ekf_handle* h, const char* fn, int b0, int count, const Query& q) {
+  HIP_TRY(h, hipGetLastError());
+  for (int i = 0; i < q.plan.ndst; ++i)
+    if (q.plan.dst[i].staged)
+      HIP_TRY(h, hipMemcpyAsync(q.host[i], q.dev[i], sizeof(double) * q.plan.dst[i].words, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->dflags, sizeof(unsigned) * h->batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (int b = b0; b < b0 + count; ++b)
+    if (h->h_flags[b] & EKF_FLAG_INTERNAL) return check_internal(h, b, fn);
+  return EKF_OK;
+}
+static PendingView pending_view(const ekf_handle* h, int b0, int count) {
+  return PendingView{h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dmu2[h->cur], h->dn, h->dso, h->ld, h->pstride, b0, count,
+                     pending_kb(h)};
+}
+
 static int set_size(ekf_handle* h, int b, int n) {
   h->n[b] = n;
   HIP_TRY(h, hipMemcpyAsync(h->dn + b, &h->n[b], sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -675,10 +761,9 @@ extern "C" int ekf_upload_state_diag(ekf_handle* h, int b, const double* mu, con
   return EKF_OK;
 }
 
-// The pinned buffer small states come back through (k_pack_small, k_small_stream's host_out): n x n covariance, mean, flags;
-// its last word is the sequence number ekf_step_fetch polls.
-// (covariance, mean, flags word; behind them the integrity trailer of ekf_step_fetch -- sequence number, XOR checksum --
-//  and, at a fixed place at the end, the sequence word the host polls)
+// The pinned buffer small states come back through (k_pack_small, k_small_stream's host_out): n x n covariance, mean, flags
+// word; behind them the integrity trailer of ekf_step_fetch -- sequence number, XOR checksum -- and, at a fixed place at the
+// end, the sequence word the host polls.
 constexpr size_t PACK_WORDS = (size_t)PACK_SMALL_N * PACK_SMALL_N + PACK_SMALL_N + 4;
 static int pack_buffer(ekf_handle* h) {
   if (h->h_pack) return EKF_OK;
@@ -720,15 +805,10 @@ extern "C" int ekf_download_state(ekf_handle* h, int b, double* mu, double* P, i
   if (P) {
     // a destination in pinned host memory (what the Python binding hands out for large covariances: ekf_host_alloc) is
     // written by a kernel -- mirrored on the way, no SDMA copy (k_pack_dense); anything else by the mirror pass + rectangle copy
-    hipPointerAttribute_t attr{};
-    double* dst = nullptr;
     // (up to 40 MB -- N = 1100: there the kernel is as fast as the copy engine at its best, 38 - 47 GB/s, and does not have
     //  the copy's bad days; beyond, the engine's larger PCIe payloads win: 54.6 against 49.8 GB/s at N = 2000.  tools/download_paths.py)
     const bool pack = h->opt_pack_dense == 2 || (h->opt_pack_dense == 1 && (size_t)n * n * sizeof(double) <= (40u << 20));
-    if (pack && hipPointerGetAttributes(&attr, P) == hipSuccess && attr.type == hipMemoryTypeHost)
-      dst = static_cast<double*>(attr.devicePointer);
-    else
-      (void)hipGetLastError();                     // (an ordinary pointer is "invalid value" to the query)
+    double* dst = pack ? static_cast<double*>(device_view(P)) : nullptr;
     if (dst) {
       if (int rc = flush_pending(h)) return rc;    // the covariance is P_base + pending ranks, upper triangle
       launch_pack_dense(h->stream, h->dP + (size_t)b * h->pstride, h->ld, n, dst);
@@ -758,228 +838,140 @@ extern "C" int ekf_download_block(ekf_handle* h, int b, int r0, int c0, int rows
   return EKF_OK;
 }
 
-// The diagonal blocks of the covariance as the pass would leave them, without running it (k_marginals, ekf_marginals.hip): reads
-// P_base, V, W, the pending pose noise, the sizes and the active bounds the pass reads, writes only the destinations.  Nothing
-// of the handle's scheduling state changes (pending ranks and steps, the streams' order, the statistics).
+// The diagonal blocks of the covariance (k_marginals, ekf_marginals.hip); a read-only query, see query_begin.
 extern "C" int ekf_download_marginals(ekf_handle* h, int b0, int count, double* pose, double* landmarks, int cap,
                                       int* n_landmarks) {
-  if (int rc = check_b(h, 0, "ekf_download_marginals")) return rc;   // (refreshes the sizes a device-side association grew)
-  if (b0 < 0 || count <= 0 || b0 > h->batch - count)
-    return fail(h, EKF_ERR_ARG, "ekf_download_marginals: trajectory range outside the bank");
-  if (!pose) return fail(h, EKF_ERR_ARG, "ekf_download_marginals: NULL pose");
-  int nl_hi = 0;
-  for (int b = b0; b < b0 + count; ++b) nl_hi = std::max(nl_hi, (h->n[b] - 3) / 2);
-  if (landmarks && cap < nl_hi)
-    return fail(h, EKF_ERR_ARG, "ekf_download_marginals: cap " + std::to_string(cap) + " is below the largest landmark count " +
-                                    std::to_string(nl_hi));
+  const char* fn = "ekf_download_marginals";
+  if (int rc = query_begin(h, fn, b0, count, nullptr, [&]() -> int {
+        if (!pose) return bad_arg(h, fn, "NULL pose");
+        int nl_hi = 0;
+        for (int b = b0; b < b0 + count; ++b) nl_hi = std::max(nl_hi, (h->n[b] - 3) / 2);
+        if (landmarks && cap < nl_hi)
+          return bad_arg(h, fn, "cap " + std::to_string(cap) + " is below the largest landmark count " + std::to_string(nl_hi));
+        return EKF_OK;
+      }))
+    return rc;
   if (!landmarks) cap = 0;
-  for (int b = b0; b < b0 + count; ++b)
-    if (h->host_bad[b]) return check_internal(h, b, "ekf_download_marginals");
-  HIP_TRY(h, hipSetDevice(h->device));
-  // pinned destinations are written by the kernel; the others go through the staging buffer and one copy each
-  auto device_view = [](double* p) -> double* {
-    hipPointerAttribute_t attr{};
-    if (hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeHost)
-      return static_cast<double*>(attr.devicePointer);
-    (void)hipGetLastError();                           // (an ordinary pointer is "invalid value" to the query)
-    return nullptr;
-  };
-  const size_t pose_words = (size_t)count * 9, lm_words = (size_t)count * (size_t)cap * 4;
-  double* dpose = device_view(pose);
-  double* dlm = landmarks ? device_view(landmarks) : nullptr;
-  const size_t stage = (dpose ? 0 : pose_words) + (landmarks && !dlm ? lm_words : 0);
-  if (stage > h->marg_cap) {
-    if (h->dmarg) HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the old buffer may still be read by a copy in flight)
-    if (h->dmarg) HIP_TRY(h, hipFree(h->dmarg));
-    h->dmarg = nullptr;
-    h->marg_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->dmarg, sizeof(double) * stage));
-    h->marg_cap = stage;
-  }
-  double* spose = dpose ? dpose : h->dmarg;
-  double* slm = !landmarks ? nullptr : (dlm ? dlm : h->dmarg + (dpose ? 0 : pose_words));
-  const int kb = (h->pending_k + 3) & ~3;              // what flush_pending's pass would apply (plan_pass: 4 nkt ranks)
-  launch_marginals(h->stream, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dn, h->dso, h->ld, h->pstride, b0, count, kb, cap,
-                   spose, slm);
-  HIP_TRY(h, hipGetLastError());
-  if (!dpose) HIP_TRY(h, hipMemcpyAsync(pose, spose, sizeof(double) * pose_words, hipMemcpyDeviceToHost, h->stream));
-  if (landmarks && !dlm && lm_words)
-    HIP_TRY(h, hipMemcpyAsync(landmarks, slm, sizeof(double) * lm_words, hipMemcpyDeviceToHost, h->stream));
-  // one synchronisation: the flags come back behind the results (check_internal's copy, then its wait)
-  HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->dflags, sizeof(unsigned) * h->batch, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  for (int b = b0; b < b0 + count; ++b)
-    if (h->h_flags[b] & EKF_FLAG_INTERNAL) return check_internal(h, b, "ekf_download_marginals");
+  Query q{};
+  q.add(pose, (size_t)count * 9);
+  q.add(landmarks, (size_t)count * (size_t)cap * 4);
+  if (int rc = query_stage(h, q)) return rc;
+  launch_marginals(h->stream, pending_view(h, b0, count), cap, q.out<double>(0), q.out<double>(1));
+  if (int rc = query_end(h, fn, b0, count, q)) return rc;
   if (n_landmarks)
     for (int b = b0; b < b0 + count; ++b) n_landmarks[b - b0] = (h->n[b] - 3) / 2;
   return EKF_OK;
 }
 
-// Likelihood association of unlabelled observations (k_assoc_query / k_assoc_finish, ekf_associate.hip): reads what
-// ekf_download_marginals reads plus the mean and the measurement noise in effect, writes only the destinations.  Nothing of the
-// handle's scheduling state changes.
+// Likelihood association of unlabelled observations (k_assoc_query / k_assoc_finish, ekf_associate.hip), under the measurement
+// noise in effect; a read-only query, see query_begin.
 extern "C" int ekf_associate(ekf_handle* h, int b0, int count, const double* range, const double* bearing, const int* m, int stride,
                              int* cand, double* cand_nis, double* cand_logdet, double* min_nis, double* all_nis, double* all_logdet,
                              int cap) {
-  if (int rc = check_b(h, 0, "ekf_associate")) return rc;            // (refreshes the sizes a device-side association grew)
-  if (b0 < 0 || count <= 0 || b0 > h->batch - count)
-    return fail(h, EKF_ERR_ARG, "ekf_associate: trajectory range outside the bank");
-  if (stride < 1 || stride > EKF_MMAX)
-    return fail(h, EKF_ERR_ARG, "ekf_associate: stride must lie in 1.." + std::to_string(EKF_MMAX));
-  if (!range || !bearing || !m) return fail(h, EKF_ERR_ARG, "ekf_associate: NULL observations");
-  if (!cand) return fail(h, EKF_ERR_ARG, "ekf_associate: NULL cand");
-  if ((all_nis == nullptr) != (all_logdet == nullptr))
-    return fail(h, EKF_ERR_ARG, "ekf_associate: all_nis and all_logdet are given together or not at all");
-  for (int bi = 0; bi < count; ++bi) {
-    if (m[bi] < 0 || m[bi] > stride)
-      return fail(h, EKF_ERR_ARG, "ekf_associate: m[" + std::to_string(bi) + "] outside 0..stride");
-    for (int q = 0; q < m[bi]; ++q)
-      if (!std::isfinite(range[(size_t)bi * stride + q]) || !std::isfinite(bearing[(size_t)bi * stride + q]))
-        return fail(h, EKF_ERR_ARG, "ekf_associate: non-finite observation " + std::to_string(q) + " of trajectory " +
-                                        std::to_string(b0 + bi));
-  }
+  const char* fn = "ekf_associate";
   const bool full = all_nis != nullptr;
-  const AssocQueryPlan plan = plan_assoc_query(h, b0, count, full ? std::max(cap, 0) : 0);
-  if (full && cap < plan.nl_hi)
-    return fail(h, EKF_ERR_ARG, "ekf_associate: cap " + std::to_string(cap) + " is below the largest landmark count " +
-                                    std::to_string(plan.nl_hi));
+  AssocQueryPlan plan{};
+  if (int rc = query_begin(h, fn, b0, count, nullptr, [&]() -> int {
+        if (stride < 1 || stride > EKF_MMAX) return bad_arg(h, fn, "stride must lie in 1.." + std::to_string(EKF_MMAX));
+        if (!range || !bearing || !m) return bad_arg(h, fn, "NULL observations");
+        if (!cand) return bad_arg(h, fn, "NULL cand");
+        if ((all_nis == nullptr) != (all_logdet == nullptr))
+          return bad_arg(h, fn, "all_nis and all_logdet are given together or not at all");
+        for (int bi = 0; bi < count; ++bi) {
+          if (m[bi] < 0 || m[bi] > stride) return bad_arg(h, fn, "m[" + std::to_string(bi) + "] outside 0..stride");
+          for (int q = 0; q < m[bi]; ++q)
+            if (!std::isfinite(range[(size_t)bi * stride + q]) || !std::isfinite(bearing[(size_t)bi * stride + q]))
+              return bad_arg(h, fn, "non-finite observation " + std::to_string(q) + " of trajectory " + std::to_string(b0 + bi));
+        }
+        plan = plan_assoc_query(h, b0, count, full ? std::max(cap, 0) : 0);
+        if (full && cap < plan.nl_hi)
+          return bad_arg(h, fn, "cap " + std::to_string(cap) + " is below the largest landmark count " + std::to_string(plan.nl_hi));
+        return EKF_OK;
+      }))
+    return rc;
   if (!full) cap = 0;
-  for (int b = b0; b < b0 + count; ++b)
-    if (h->host_bad[b]) return check_internal(h, b, "ekf_associate");
-  HIP_TRY(h, hipSetDevice(h->device));
-  // pinned destinations are written by the kernels; the others go through the staging buffer and one copy each
-  auto device_view = [](void* p) -> void* {
-    hipPointerAttribute_t attr{};
-    if (p && hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeHost) return attr.devicePointer;
-    (void)hipGetLastError();                           // (an ordinary pointer is "invalid value" to the query)
-    return nullptr;
-  };
   const size_t obs = (size_t)count * stride, full_words = obs * (size_t)cap;
-  // layout (doubles): range, bearing, m (ints, rounded up), the partial records, then whatever destination needs staging
-  const size_t m_words = ((size_t)count + 1) / 2, part_words = (size_t)assoc_query_part_doubles(count, plan.chunks, stride);
-  struct Dst { void* host; void* dev; size_t words; size_t bytes; };
-  Dst dst[6] = {{cand, nullptr, obs, sizeof(int) * obs * 2},          {cand_nis, nullptr, obs * 2, sizeof(double) * obs * 2},
-                {cand_logdet, nullptr, obs * 2, sizeof(double) * obs * 2}, {min_nis, nullptr, obs, sizeof(double) * obs},
-                {all_nis, nullptr, full_words, sizeof(double) * full_words}, {all_logdet, nullptr, full_words, sizeof(double) * full_words}};
-  size_t need = 2 * obs + m_words + part_words;
-  bool staged[6] = {false, false, false, false, false, false};
-  size_t at[6] = {0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < 6; ++i) {
-    if (!dst[i].host || dst[i].words == 0) continue;
-    dst[i].dev = device_view(dst[i].host);
-    if (!dst[i].dev) {
-      staged[i] = true;
-      at[i] = need;
-      need += dst[i].words;
-    }
-  }
-  if (need > h->assq_cap) {
-    if (h->dassq) HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the old buffer may still be read by a copy in flight)
-    if (h->dassq) HIP_TRY(h, hipFree(h->dassq));
-    h->dassq = nullptr;
-    h->assq_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->dassq, sizeof(double) * need));
-    h->assq_cap = need;
-  }
-  for (int i = 0; i < 6; ++i)
-    if (staged[i]) dst[i].dev = h->dassq + at[i];
-  double *dzr = h->dassq, *dzb = h->dassq + obs, *dpart = h->dassq + 2 * obs + m_words;
-  int* dzm = reinterpret_cast<int*>(h->dassq + 2 * obs);
+  // inputs: range, bearing, m (ints, rounded up to doubles), the partial records
+  const size_t m_words = ((size_t)count + 1) / 2;
+  Query q{};
+  q.plan.inputs = 2 * obs + m_words + (size_t)assoc_query_part_doubles(count, plan.chunks, stride);
+  q.add(cand, obs);                                    // (2 ints per observation)
+  q.add(cand_nis, obs * 2);
+  q.add(cand_logdet, obs * 2);
+  q.add(min_nis, obs);
+  q.add(all_nis, full_words);
+  q.add(all_logdet, full_words);
+  if (int rc = query_stage(h, q)) return rc;
+  double *dzr = h->dquery.p, *dzb = dzr + obs, *dpart = dzb + obs + m_words;
+  int* dzm = reinterpret_cast<int*>(dzb + obs);
   HIP_TRY(h, hipMemcpyAsync(dzr, range, sizeof(double) * obs, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(dzb, bearing, sizeof(double) * obs, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(dzm, m, sizeof(int) * count, hipMemcpyHostToDevice, h->stream));
-  const int kb = (h->pending_k + 3) & ~3;              // what flush_pending's pass would apply (plan_pass: 4 nkt ranks)
-  launch_assoc_query(h->stream, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dmu2[h->cur], h->dn, h->dso, h->dcfg, h->ld, h->pstride,
-                     b0, count, kb, stride, cap, plan.chunks, dzr, dzb, dzm, dpart, static_cast<double*>(dst[4].dev),
-                     static_cast<double*>(dst[5].dev), static_cast<int*>(dst[0].dev), static_cast<double*>(dst[1].dev),
-                     static_cast<double*>(dst[2].dev), static_cast<double*>(dst[3].dev));
-  HIP_TRY(h, hipGetLastError());
-  for (int i = 0; i < 6; ++i)
-    if (staged[i]) HIP_TRY(h, hipMemcpyAsync(dst[i].host, dst[i].dev, dst[i].bytes, hipMemcpyDeviceToHost, h->stream));
-  // one synchronisation: the flags come back behind the results (check_internal's copy, then its wait)
-  HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->dflags, sizeof(unsigned) * h->batch, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  for (int b = b0; b < b0 + count; ++b)
-    if (h->h_flags[b] & EKF_FLAG_INTERNAL) return check_internal(h, b, "ekf_associate");
-  return EKF_OK;
+  launch_assoc_query(h->stream, pending_view(h, b0, count), h->dcfg, stride, cap, plan.chunks, dzr, dzb, dzm, dpart,
+                     q.out<double>(4), q.out<double>(5), q.out<int>(0), q.out<double>(1), q.out<double>(2), q.out<double>(3));
+  return query_end(h, fn, b0, count, q);
 }
 
-// The joint covariance and mean of the pose and a subset of landmarks as the pass would leave them, without running it (k_joint,
-// ekf_joint.hip): reads what ekf_download_marginals reads plus the mean, writes only the destinations.  Nothing of the handle's
-// scheduling state changes.
+// The joint covariance and mean of the pose and a subset of landmarks (k_joint, ekf_joint.hip); a read-only query, see
+// query_begin.
 extern "C" int ekf_download_joint(ekf_handle* h, int b0, int count, const int* landmarks, const int* k, int stride, double* mean,
                                   double* cov) {
-  if (int rc = check_b(h, 0, "ekf_download_joint")) return rc;       // (refreshes the sizes a device-side association grew)
-  if (!cov) return fail(h, EKF_ERR_ARG, "ekf_download_joint: NULL cov");
+  const char* fn = "ekf_download_joint";
   JointQueryPlan jp{};
-  if (const char* why = plan_joint_query(h, b0, count, landmarks, k, stride, jp, h->joint_sel, h->joint_order))
-    return fail(h, EKF_ERR_ARG, std::string("ekf_download_joint: ") + why);
-  for (int b = b0; b < b0 + count; ++b)
-    if (h->host_bad[b]) return check_internal(h, b, "ekf_download_joint");
-  HIP_TRY(h, hipSetDevice(h->device));
-  // pinned destinations are written by the kernel; the others go through the staging buffer and one copy each
-  auto device_view = [](double* p) -> double* {
-    hipPointerAttribute_t attr{};
-    if (p && hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeHost)
-      return static_cast<double*>(attr.devicePointer);
-    (void)hipGetLastError();                           // (an ordinary pointer is "invalid value" to the query)
-    return nullptr;
-  };
-  // layout (doubles): the selection (ints, rounded up), then whatever destination needs staging
-  const size_t sel_words = (h->joint_sel.size() + 1) / 2;
-  const size_t mean_words = (size_t)count * jp.ns, cov_words = mean_words * jp.ns;
-  double* dmean = mean ? device_view(mean) : nullptr;
-  double* dcov = device_view(cov);
-  const size_t need = sel_words + (mean && !dmean ? mean_words : 0) + (dcov ? 0 : cov_words);
-  if (need > h->joint_cap) {
-    if (h->djoint) HIP_TRY(h, hipStreamSynchronize(h->stream));  // (the old buffer may still be read by a copy in flight)
-    if (h->djoint) HIP_TRY(h, hipFree(h->djoint));
-    h->djoint = nullptr;
-    h->joint_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->djoint, sizeof(double) * need));
-    h->joint_cap = need;
-  }
-  int* dsel = reinterpret_cast<int*>(h->djoint);
-  double* smean = !mean ? nullptr : (dmean ? dmean : h->djoint + sel_words);
-  double* scov = dcov ? dcov : h->djoint + sel_words + (mean && !dmean ? mean_words : 0);
+  if (int rc = query_begin(h, fn, b0, count, h && !cov ? "NULL cov" : nullptr, [&]() -> int {
+        const char* why = plan_joint_query(h, b0, count, landmarks, k, stride, jp, h->joint_sel, h->joint_order);
+        return why ? bad_arg(h, fn, why) : EKF_OK;
+      }))
+    return rc;
+  const size_t mean_words = (size_t)count * jp.ns;
+  Query q{};
+  q.plan.inputs = (h->joint_sel.size() + 1) / 2;       // the selection (ints, rounded up to doubles)
+  q.add(mean, mean_words);
+  q.add(cov, mean_words * jp.ns);
+  if (int rc = query_stage(h, q)) return rc;
+  int* dsel = reinterpret_cast<int*>(h->dquery.p);
   HIP_TRY(h, hipMemcpyAsync(dsel, h->joint_sel.data(), sizeof(int) * h->joint_sel.size(), hipMemcpyHostToDevice, h->stream));
-  const int kb = (h->pending_k + 3) & ~3;              // what flush_pending's pass would apply (plan_pass: 4 nkt ranks)
-  launch_joint(h->stream, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dmu2[h->cur], h->dn, h->dso, h->ld, h->pstride, b0, count,
-               kb, jp.ns, jp.nt, jp.tiles, dsel, smean, scov);
-  HIP_TRY(h, hipGetLastError());
-  if (mean && !dmean) HIP_TRY(h, hipMemcpyAsync(mean, smean, sizeof(double) * mean_words, hipMemcpyDeviceToHost, h->stream));
-  if (!dcov) HIP_TRY(h, hipMemcpyAsync(cov, scov, sizeof(double) * cov_words, hipMemcpyDeviceToHost, h->stream));
-  // one synchronisation: the flags come back behind the results (check_internal's copy, then its wait)
-  HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->dflags, sizeof(unsigned) * h->batch, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  for (int b = b0; b < b0 + count; ++b)
-    if (h->h_flags[b] & EKF_FLAG_INTERNAL) return check_internal(h, b, "ekf_download_joint");
-  return EKF_OK;
+  launch_joint(h->stream, pending_view(h, b0, count), jp.ns, jp.nt, jp.tiles, dsel, q.out<double>(0), q.out<double>(1));
+  return query_end(h, fn, b0, count, q);
 }
 
-// ---- the pose log (ekf_pose_log.hip) ----
+// ---- the log rings: the pose log (ekf_pose_log.hip) and the innovation log (ekf_innovations.hip) ----
+// A ring is one or two device arrays of `capacity` step rows, `row_bytes` per (step, trajectory).  ring_resize replaces it by
+// an empty one (capacity 0: switches the log off); `cap` and `steps` are the log's capacity and its count of logged steps.
+struct RingArray { void** p; size_t row_bytes; };
+static int ring_resize(ekf_handle* h, const char* fn, int capacity, std::initializer_list<RingArray> arrays, int* cap,
+                       long long* steps) {
+  if (capacity < 0) return bad_arg(h, fn, "capacity must be >= 0");
+  const size_t rows = (size_t)capacity * h->batch;
+  for (const RingArray& a : arrays)
+    if (rows * a.row_bytes > ((size_t)1 << 36)) return bad_arg(h, fn, "the ring would exceed 64 GiB");
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (*arrays.begin()->p) HIP_TRY(h, hipStreamSynchronize(h->stream));   // (launches in flight still write the old ring)
+  for (const RingArray& a : arrays)
+    if (void* old = std::exchange(*a.p, nullptr)) HIP_TRY(h, hipFree(old));
+  *cap = 0;
+  *steps = 0;
+  for (const RingArray& a : arrays)
+    if (capacity > 0 && hipMalloc(a.p, rows * a.row_bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      *a.p = nullptr;
+      (void)ring_resize(h, fn, 0, arrays, cap, steps);   // (frees what was allocated before it)
+      return fail(h, EKF_ERR_HIP, std::string(fn) + ": cannot allocate the ring of " + std::to_string(capacity) + " steps");
+    }
+  *cap = capacity;
+  return EKF_OK;
+}
+// Steps [first, first + count) must be among the last `cap` of the `steps` logged.
+static int check_ring_range(ekf_handle* h, const char* fn, long long first, int count, long long steps, int cap) {
+  if (ring_range_ok(first, count, steps, cap)) return EKF_OK;
+  return bad_arg(h, fn, "steps [" + std::to_string(first) + ", " + std::to_string(first + count) + ") are not among the last " +
+                            std::to_string(cap) + " of the " + std::to_string(steps) + " logged");
+}
+
 extern "C" int ekf_log_poses(ekf_handle* h, int capacity) {
   if (!h) return EKF_ERR_ARG;
-  if (capacity < 0) return fail(h, EKF_ERR_ARG, "ekf_log_poses: capacity must be >= 0");
-  const size_t rows = (size_t)capacity * h->batch;
-  if (capacity > 0 && rows * POSE_ROW * sizeof(double) > ((size_t)1 << 36))
-    return fail(h, EKF_ERR_ARG, "ekf_log_poses: the ring would exceed 64 GiB");
-  HIP_TRY(h, hipSetDevice(h->device));
-  if (h->dpose) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));       // (launches in flight still write the old ring)
-    HIP_TRY(h, hipFree(h->dpose));
-    h->dpose = nullptr;
-  }
-  h->pose_cap = 0;
-  h->pose_steps = 0;
-  if (capacity == 0) return EKF_OK;
-  if (hipMalloc(&h->dpose, sizeof(double) * rows * POSE_ROW) != hipSuccess) {
-    (void)hipGetLastError();
-    h->dpose = nullptr;
-    return fail(h, EKF_ERR_HIP, "ekf_log_poses: cannot allocate the ring of " + std::to_string(capacity) + " steps");
-  }
-  h->pose_cap = capacity;
-  return EKF_OK;
+  return ring_resize(h, "ekf_log_poses", capacity, {{reinterpret_cast<void**>(&h->dpose), sizeof(double) * POSE_ROW}},
+                     &h->pose_cap, &h->pose_steps);
 }
 
 extern "C" int ekf_pose_steps(ekf_handle* h, long long* logged) {
@@ -988,24 +980,20 @@ extern "C" int ekf_pose_steps(ekf_handle* h, long long* logged) {
   return EKF_OK;
 }
 
-// The range rules are read_log's (the innovation log below).  The block is returned exactly symmetric: its upper triangle, mirrored.
+// The block is returned exactly symmetric: its upper triangle, mirrored.
 extern "C" int ekf_download_poses(ekf_handle* h, long long first, int count, double* pose, double* cov) {
   if (!h) return EKF_ERR_ARG;
   if (!h->dpose) return fail(h, EKF_ERR_STATE, "ekf_download_poses: the pose log is off (ekf_log_poses)");
-  if (count < 0 || first < 0 || first + count > h->pose_steps || first < h->pose_steps - h->pose_cap)
-    return fail(h, EKF_ERR_ARG, "ekf_download_poses: steps [" + std::to_string(first) + ", " + std::to_string(first + count) +
-                                    ") are not among the last " + std::to_string(h->pose_cap) + " of the " +
-                                    std::to_string(h->pose_steps) + " logged");
+  if (int rc = check_ring_range(h, "ekf_download_poses", first, count, h->pose_steps, h->pose_cap)) return rc;
   if (count > 0 && !pose) return fail(h, EKF_ERR_ARG, "ekf_download_poses: NULL pose");
   HIP_TRY(h, hipSetDevice(h->device));
   const long B = h->batch;
   std::vector<double> hr((size_t)count * B * POSE_ROW);
-  for (long done = 0; done < count;) {                 // (the range may wrap round the ring: two pieces at most)
-    const long slot = (long)((first + done) % h->pose_cap);
-    const long piece = std::min<long long>(count - done, h->pose_cap - slot);
-    HIP_TRY(h, hipMemcpyAsync(hr.data() + done * B * POSE_ROW, h->dpose + slot * B * POSE_ROW, sizeof(double) * piece * B * POSE_ROW,
+  const RingPieces rp = ring_pieces(first, count, h->pose_cap);
+  for (int i = 0; i < rp.n; ++i) {
+    const RingPieces::Piece& c = rp.piece[i];
+    HIP_TRY(h, hipMemcpyAsync(hr.data() + c.done * B * POSE_ROW, h->dpose + c.slot * B * POSE_ROW, sizeof(double) * c.rows * B * POSE_ROW,
                               hipMemcpyDeviceToHost, h->stream));
-    done += piece;
   }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   for (size_t q = 0; q < (size_t)count * B; ++q) {
@@ -1018,34 +1006,11 @@ extern "C" int ekf_download_poses(ekf_handle* h, long long first, int count, dou
   return EKF_OK;
 }
 
-// ---- the innovation log (ekf_innovations.hip) ----
 extern "C" int ekf_log_innovations(ekf_handle* h, int capacity) {
   if (!h) return EKF_ERR_ARG;
-  if (capacity < 0) return fail(h, EKF_ERR_ARG, "ekf_log_innovations: capacity must be >= 0");
-  const size_t rows = (size_t)capacity * h->batch;
-  if (capacity > 0 && rows * AMAX * sizeof(InnovRec) > ((size_t)1 << 36))
-    return fail(h, EKF_ERR_ARG, "ekf_log_innovations: the ring would exceed 64 GiB");
-  HIP_TRY(h, hipSetDevice(h->device));
-  if (h->dinnov) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));       // (a copy kernel may still be writing to the ring)
-    HIP_TRY(h, hipFree(h->dinnov));
-    HIP_TRY(h, hipFree(h->dinnov_m));
-    h->dinnov = nullptr;
-    h->dinnov_m = nullptr;
-  }
-  h->innov_cap = 0;
-  h->innov_steps = 0;
-  if (capacity == 0) return EKF_OK;
-  if (hipMalloc(&h->dinnov, sizeof(InnovRec) * rows * AMAX) != hipSuccess ||
-      hipMalloc(&h->dinnov_m, sizeof(int) * rows) != hipSuccess) {
-    (void)hipGetLastError();
-    if (h->dinnov) (void)hipFree(h->dinnov);
-    h->dinnov = nullptr;
-    h->dinnov_m = nullptr;
-    return fail(h, EKF_ERR_HIP, "ekf_log_innovations: cannot allocate the ring of " + std::to_string(capacity) + " steps");
-  }
-  h->innov_cap = capacity;
-  return EKF_OK;
+  return ring_resize(h, "ekf_log_innovations", capacity,
+                     {{reinterpret_cast<void**>(&h->dinnov), sizeof(InnovRec) * AMAX}, {reinterpret_cast<void**>(&h->dinnov_m), sizeof(int)}},
+                     &h->innov_cap, &h->innov_steps);
 }
 
 extern "C" int ekf_innovation_steps(ekf_handle* h, long long* logged) {
@@ -1058,22 +1023,18 @@ extern "C" int ekf_innovation_steps(ekf_handle* h, long long* logged) {
 // everything enqueued, into hm (count x batch counts) and hr (count x batch x AMAX entries).  Runs nothing else on the device.
 static int read_log(ekf_handle* h, long long first, int count, const char* fn, std::vector<int>& hm, std::vector<InnovRec>& hr) {
   if (!h->dinnov) return fail(h, EKF_ERR_STATE, std::string(fn) + ": the innovation log is off (ekf_log_innovations)");
-  if (count < 0 || first < 0 || first + count > h->innov_steps || first < h->innov_steps - h->innov_cap)
-    return fail(h, EKF_ERR_ARG, std::string(fn) + ": steps [" + std::to_string(first) + ", " + std::to_string(first + count) +
-                                    ") are not among the last " + std::to_string(h->innov_cap) + " of the " +
-                                    std::to_string(h->innov_steps) + " logged");
+  if (int rc = check_ring_range(h, fn, first, count, h->innov_steps, h->innov_cap)) return rc;
   const int B = h->batch;
   hm.resize((size_t)count * B);
   hr.resize((size_t)count * B * AMAX);
   HIP_TRY(h, hipSetDevice(h->device));
-  for (long long done = 0; done < count;) {
-    const long slot = (long)((first + done) % h->innov_cap);
-    const long piece = std::min<long long>(count - done, h->innov_cap - slot);
-    HIP_TRY(h, hipMemcpyAsync(hm.data() + done * B, h->dinnov_m + slot * B, sizeof(int) * piece * B, hipMemcpyDeviceToHost,
+  const RingPieces rp = ring_pieces(first, count, h->innov_cap);
+  for (int i = 0; i < rp.n; ++i) {
+    const RingPieces::Piece& c = rp.piece[i];
+    HIP_TRY(h, hipMemcpyAsync(hm.data() + c.done * B, h->dinnov_m + c.slot * B, sizeof(int) * c.rows * B, hipMemcpyDeviceToHost,
                               h->stream));
-    HIP_TRY(h, hipMemcpyAsync(hr.data() + done * B * AMAX, h->dinnov + slot * B * AMAX, sizeof(InnovRec) * piece * B * AMAX,
+    HIP_TRY(h, hipMemcpyAsync(hr.data() + c.done * B * AMAX, h->dinnov + c.slot * B * AMAX, sizeof(InnovRec) * c.rows * B * AMAX,
                               hipMemcpyDeviceToHost, h->stream));
-    done += piece;
   }
   return check_internal(h, -1, fn);                    // (synchronises: the copies above are done)
 }
@@ -1147,9 +1108,7 @@ static void noise_row_of(double s, double q, double* r) {
 }
 
 extern "C" int ekf_set_noise(ekf_handle* h, int b0, int count, const double* motion_sigma, const double* meas_sigma) {
-  if (!h) return EKF_ERR_ARG;
-  if (b0 < 0 || count <= 0 || b0 > h->batch - count)
-    return fail(h, EKF_ERR_ARG, "ekf_set_noise: trajectory range outside the bank");
+  if (int rc = check_range(h, "ekf_set_noise", b0, count)) return rc;
   for (int i = 0; i < count; ++i) {
     if (motion_sigma && !std::isfinite(motion_sigma[i]))
       return fail(h, EKF_ERR_ARG, "ekf_set_noise: motion_sigma[" + std::to_string(i) + "] is not finite");
@@ -1201,9 +1160,7 @@ extern "C" int ekf_set_noise(ekf_handle* h, int b0, int count, const double* mot
 }
 
 extern "C" int ekf_get_noise(ekf_handle* h, int b0, int count, double* motion_sigma, double* meas_sigma) {
-  if (!h) return EKF_ERR_ARG;
-  if (b0 < 0 || count <= 0 || b0 > h->batch - count)
-    return fail(h, EKF_ERR_ARG, "ekf_get_noise: trajectory range outside the bank");
+  if (int rc = check_range(h, "ekf_get_noise", b0, count)) return rc;
   for (int i = 0; i < count; ++i) {
     const size_t b = (size_t)b0 + i;
     if (motion_sigma) motion_sigma[i] = h->noise_ms.empty() ? h->cfg.motion_sigma : h->noise_ms[b];
@@ -1213,9 +1170,7 @@ extern "C" int ekf_get_noise(ekf_handle* h, int b0, int count, double* motion_si
 }
 
 extern "C" int ekf_download_gate_counts(ekf_handle* h, int b0, int count, long long* rejected) {
-  if (!h) return EKF_ERR_ARG;
-  if (b0 < 0 || count <= 0 || b0 > h->batch - count)
-    return fail(h, EKF_ERR_ARG, "ekf_download_gate_counts: trajectory range outside the bank");
+  if (int rc = check_range(h, "ekf_download_gate_counts", b0, count)) return rc;
   if (!rejected) return fail(h, EKF_ERR_ARG, "ekf_download_gate_counts: NULL rejected");
   HIP_TRY(h, hipSetDevice(h->device));
   std::vector<unsigned long long> hc((size_t)count, 0ull);
@@ -1529,7 +1484,7 @@ static void log_pass(ekf_handle* h, const StepIn* d_in) {
 // path has written the row itself.
 static int log_pose_step(ekf_handle* h) {
   if (!h->dpose || h->pl_slot < 0 || small_path(h)) return EKF_OK;
-  launch_pose_step(h->stream, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dmu2[h->cur], h->ld, h->pstride, (h->pending_k + 3) & ~3,
+  launch_pose_step(h->stream, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dmu2[h->cur], h->ld, h->pstride, pending_kb(h),
                    h->batch, PoseLog{h->dpose, h->pl_slot, h->pose_cap});
   HIP_TRY(h, hipGetLastError());
   return EKF_OK;
@@ -1778,7 +1733,7 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
   }
   if (!h->dgbuf) HIP_TRY(h, hipMalloc(&h->dgbuf, sizeof(double) * cadence_gbuf_doubles() * h->batch));
   // ---- look-ahead: gather (stream) -> { pass (second stream) | solve of the next cadence (stream) } -> join ----
-  const int kb = (h->pending_k + 3) & ~3;
+  const int kb = pending_kb(h);
   {
     ProfBracket pb;
     if (int rc2 = prof_open(h, 2, h->stream, &pb)) return rc2;
@@ -2114,21 +2069,13 @@ extern "C" int ekf_copy_trajectories(ekf_handle* dst, const int* dst_b, ekf_hand
     if (int rc = flush_pending(dst)) return rc;
   HIP_TRY(dst, hipStreamSynchronize(src->stream));
   if (src->aux) HIP_TRY(dst, hipStreamSynchronize(src->aux));
-  if (dst->cp_cap < cp.tab.size()) {
-    HIP_TRY(dst, hipStreamSynchronize(dst->stream));   // (an earlier launch may still read the old table)
-    if (dst->dcp_tab) HIP_TRY(dst, hipFree(dst->dcp_tab));
-    dst->dcp_tab = nullptr;
-    dst->cp_cap = 0;
-    const size_t cap = std::max(cp.tab.size(), (size_t)(COPY_GROUP_WORDS + 1) * dst->batch);
-    HIP_TRY(dst, hipMalloc(&dst->dcp_tab, sizeof(int) * cap));
-    dst->cp_cap = cap;
-  }
-  HIP_TRY(dst, hipMemcpyAsync(dst->dcp_tab, cp.tab.data(), sizeof(int) * cp.tab.size(), hipMemcpyHostToDevice, dst->stream));
+  if (int rc = dst->dcp_tab.reserve(dst, dst->stream, cp.tab.size(), (size_t)(COPY_GROUP_WORDS + 1) * dst->batch)) return rc;
+  HIP_TRY(dst, hipMemcpyAsync(dst->dcp_tab.p, cp.tab.data(), sizeof(int) * cp.tab.size(), hipMemcpyHostToDevice, dst->stream));
   // (nontemporal stores unless EKFSLAM_HIP_COPY_NT=0: tools/copy_trajectories_time.py measures both, profiles/copy_trajectories.txt)
   bool nt = true;
   if (const char* e = std::getenv("EKFSLAM_HIP_COPY_NT")) nt = std::atoi(e) != 0;
   launch_copy_traj(dst->stream, nt, src->dP, dst->dP, src->dmu2[src->cur], dst->dmu2[dst->cur], dst->dn, src->dflags, dst->dflags,
-                   dst->dcp_tab, cp.groups, cp.n_hi, src->ld, src->pstride, dst->ld, dst->pstride);
+                   dst->dcp_tab.p, cp.groups, cp.n_hi, src->ld, src->pstride, dst->ld, dst->pstride);
   HIP_TRY(dst, hipGetLastError());
   // the device tag table and the last window's tags: the source's, or "no window yet" where the source has never had one
   if (src->dtagmap)

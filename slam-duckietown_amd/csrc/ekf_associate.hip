@@ -360,13 +360,13 @@ __global__ __launch_bounds__(64) void k_assoc_finish(const double* __restrict__ 
 
 long assoc_query_part_doubles(int count, int chunks, int stride) { return (long)count * chunks * stride * AQ_PART; }
 
-void launch_assoc_query(hipStream_t st, const double* P, const double* V, const double* W, const double* dacc, const double* mu,
-                        const int* nact, const SolveOut* so, const DeviceConfig& cfg, int ld, long pstride, int b0, int count,
-                        int kb, int stride, int cap, int chunks, const double* zr, const double* zb, const int* zm, double* part,
-                        double* all_nis, double* all_logdet, int* cand, double* cand_nis, double* cand_logdet, double* min_nis) {
-  hipLaunchKernelGGL(k_assoc_query, dim3(chunks, count), dim3(64 * AQ_WAVES), 0, st, P, V, W, dacc, mu, nact, so, cfg, ld,
-                     pstride, b0, kb, stride, cap, zr, zb, zm, part, all_nis, all_logdet);
-  hipLaunchKernelGGL(k_assoc_finish, dim3(count), dim3(64), 0, st, part, chunks, stride, zm, cand, cand_nis, cand_logdet, min_nis);
+void launch_assoc_query(hipStream_t st, const PendingView& f, const DeviceConfig& cfg, int stride, int cap, int chunks,
+                        const double* zr, const double* zb, const int* zm, double* part, double* all_nis, double* all_logdet,
+                        int* cand, double* cand_nis, double* cand_logdet, double* min_nis) {
+  hipLaunchKernelGGL(k_assoc_query, dim3(chunks, f.count), dim3(64 * AQ_WAVES), 0, st, f.P, f.V, f.W, f.dacc, f.mu, f.nact, f.so,
+                     cfg, f.ld, f.pstride, f.b0, f.kb, stride, cap, zr, zb, zm, part, all_nis, all_logdet);
+  hipLaunchKernelGGL(k_assoc_finish, dim3(f.count), dim3(64), 0, st, part, chunks, stride, zm, cand, cand_nis, cand_logdet,
+                     min_nis);
 }
 
 }  // namespace ekf

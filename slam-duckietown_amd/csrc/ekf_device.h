@@ -246,6 +246,14 @@ struct PoseLog {
   long slot0;
   int cap;
 };
+// What a read-only query reads of the filter (ekf_api.hip: pending_view; the launchers of k_marginals, k_assoc_query, k_joint):
+// P_base, the kb pending ranks, pose noise, mean, sizes and last solve's records of trajectories [b0, b0 + count).
+struct PendingView {
+  const double *P, *V, *W, *dacc, *mu;
+  const int* nact;
+  const SolveOut* so;
+  int ld; long pstride; int b0, count, kb;
+};
 // y^T S^-1 y with S^-1 = [[a, b], [c, d]]
 __host__ __device__ __forceinline__ double innov_nis(double y0, double y1, double a, double b, double c, double d) {
   return y0 * (a * y0 + b * y1) + y1 * (c * y0 + d * y1);

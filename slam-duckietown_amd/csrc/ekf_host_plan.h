@@ -358,6 +358,52 @@ inline PassPlan plan_pass(const HostPlan* h, int pending_k, bool all_active = fa
   return p;
 }
 inline PassPlan plan_pass(const HostPlan* h) { return plan_pass(h, h->pending_k); }
+// The pending ranks as that pass would apply them: whole k-tiles (4 nkt).  What every kernel that reads P_base + W V takes.
+inline int pending_kb(const HostPlan* h) { return (h->pending_k + 3) & ~3; }
+
+// ---- the scaffold of the read-only queries and the log rings (ekf_api.hip: query_begin / query_end, ring_resize) ----
+// Trajectories [b0, b0 + count) lie inside the bank (written so that no sum can overflow).
+constexpr const char* BANK_RANGE_WHY = "trajectory range outside the bank";
+inline bool bank_range_ok(const HostPlan* h, int b0, int count) { return b0 >= 0 && count > 0 && b0 <= h->batch - count; }
+
+// Where a query's kernels write: the handle's staging buffer holds the `inputs` doubles the query uploads or uses as scratch,
+// then one region per destination the device cannot write in place (ordinary host memory: copied back by query_end).  The site
+// adds its destinations in order; plan_staging gives each no region -- absent, empty, or device-visible (pinned) -- or the
+// next offset behind the ones before it, and returns the doubles the buffer must hold.  All sizes in doubles.
+constexpr int STAGE_DSTS = 6;
+struct StagingPlan {
+  size_t inputs = 0;
+  int ndst = 0;
+  struct Dst { bool present, device, staged; size_t words, at; } dst[STAGE_DSTS];   // staged: region [at, at + words)
+  void add(bool present, size_t words, bool device) { dst[ndst++] = Dst{present, device, false, words, 0}; }
+};
+inline size_t plan_staging(StagingPlan& s) {
+  size_t total = s.inputs;
+  for (int i = 0; i < s.ndst; ++i) {
+    StagingPlan::Dst& d = s.dst[i];
+    d.staged = d.present && d.words > 0 && !d.device;
+    d.at = d.staged ? total : 0;
+    total += d.staged ? d.words : 0;
+  }
+  return total;
+}
+
+// Steps [first, first + count) of a log are among the last `cap` of the `steps` logged ...
+inline bool ring_range_ok(long long first, int count, long long steps, int cap) {
+  return count >= 0 && first >= 0 && first <= steps - count && first >= steps - cap;
+}
+// ... and where they lie in its ring of `cap` rows: one piece, or two where the range wraps.  Piece i is `rows` ring rows from
+// `slot` on, the range's steps from first + `done` on.
+struct RingPieces { int n = 0; struct Piece { long slot, done, rows; } piece[2]; };
+inline RingPieces ring_pieces(long long first, int count, int cap) {
+  RingPieces r;
+  for (long done = 0; done < count && r.n < 2; ++r.n) {   // (count <= cap: ring_range_ok)
+    const long slot = (long)((first + done) % cap), rows = std::min<long>(count - done, cap - slot);
+    r.piece[r.n] = {slot, done, rows};
+    done += rows;
+  }
+  return r;
+}
 
 // ---- the per-step update (ekf_api.hip: enqueue_pass) ----
 // Whether a step of this shape is run as one launch (the latency regime, see k_step_split): while every panel
@@ -684,7 +730,7 @@ struct DirectPlan {
 inline int direct_rows(int target) { return target == EKF_DIRECT_POSE ? 3 : 2; }
 inline const char* plan_direct(const HostPlan* h, int b0, int count, const int* target, const double* z, const double* R,
                                const int* m, int stride, const double* gate, DirectPlan& dp) {
-  if (b0 < 0 || count <= 0 || b0 > h->batch - count) return "trajectory range outside the bank";
+  if (!bank_range_ok(h, b0, count)) return BANK_RANGE_WHY;
   if (stride < 1 || stride > MMAX) return "stride outside 1..EKF_MMAX";
   if (!target || !z || !R || !m) return "NULL target, z, R or m";
   dp.kpad = 0;
@@ -829,7 +875,7 @@ struct JointQueryPlan {
 };
 inline const char* plan_joint_query(const HostPlan* h, int b0, int count, const int* landmarks, const int* k, int stride,
                                     JointQueryPlan& jp, std::vector<int>& sel, std::vector<std::pair<int, int>>& order) {
-  if (b0 < 0 || count <= 0 || b0 > h->batch - count) return "trajectory range outside the bank";
+  if (!bank_range_ok(h, b0, count)) return BANK_RANGE_WHY;
   if (stride < 1 || stride > JMAX) return "stride outside 1..EKF_JMAX";
   if (!landmarks || !k) return "NULL landmarks or k";
   jp.ns = 3 + 2 * stride;

@@ -113,11 +113,10 @@ __global__ __launch_bounds__(JQ_THREADS) void k_joint(const double* __restrict__
   }
 }
 
-void launch_joint(hipStream_t st, const double* P, const double* V, const double* W, const double* dacc, const double* mu,
-                  const int* nact, const SolveOut* so, int ld, long pstride, int b0, int count, int kb, int ns, int nt,
-                  int tiles, const int* sel, double* mean_out, double* cov_out) {
-  hipLaunchKernelGGL(k_joint, dim3(tiles, count), dim3(JQ_THREADS), 0, st, P, V, W, dacc, mu, nact, so, ld, pstride, b0, kb, ns,
-                     nt, sel, mean_out, cov_out);
+void launch_joint(hipStream_t st, const PendingView& f, int ns, int nt, int tiles, const int* sel, double* mean_out,
+                  double* cov_out) {
+  hipLaunchKernelGGL(k_joint, dim3(tiles, f.count), dim3(JQ_THREADS), 0, st, f.P, f.V, f.W, f.dacc, f.mu, f.nact, f.so, f.ld,
+                     f.pstride, f.b0, f.kb, ns, nt, sel, mean_out, cov_out);
 }
 
 }  // namespace ekf

@@ -176,12 +176,10 @@ __global__ __launch_bounds__(64 * MG_WAVES) void k_marginals(const double* __res
   }
 }
 
-void launch_marginals(hipStream_t st, const double* P, const double* V, const double* W, const double* dacc, const int* nact,
-                      const SolveOut* so, int ld, long pstride, int b0, int count, int kb, int cap, double* pose_out,
-                      double* lm_out) {
+void launch_marginals(hipStream_t st, const PendingView& f, int cap, double* pose_out, double* lm_out) {
   const int gx = lm_out && cap > 0 ? (cap + 63) / 64 : 1;
-  hipLaunchKernelGGL(k_marginals, dim3(gx, count), dim3(64 * MG_WAVES), 0, st, P, V, W, dacc, nact, so, ld, pstride, b0, kb,
-                     cap, pose_out, lm_out);
+  hipLaunchKernelGGL(k_marginals, dim3(gx, f.count), dim3(64 * MG_WAVES), 0, st, f.P, f.V, f.W, f.dacc, f.nact, f.so, f.ld,
+                     f.pstride, f.b0, f.kb, cap, pose_out, lm_out);
 }
 
 }  // namespace ekf

@@ -3,9 +3,11 @@
 //       -I slam-duckietown_amd/csrc -I include tests/host_plan_check.cpp -o host_plan_check
 // Everything below runs the SAME source the library ships (slam-duckietown_amd/csrc/ekf_host_plan.h, ekf_device.h): the
 // work queues and equal static shares of the row-slab covariance pass, the cadence / pass / step planning, the step records and
-// their active bound, the validation of observation lists, the covariance's device layout.  Enumerations (every unit /
+// their active bound, the validation of observation lists, the covariance's device layout, the staging layout of the read-only
+// queries and the ranges of the log rings.  Enumerations (every unit /
 // strip / matrix entry exactly once) plus randomised invariants; any sanitizer report or failed check ends the run with a
 // non-zero status.  tests/test_cpu_host.py::test_host_planning_logic_under_the_sanitizers builds and runs it (CPU only).
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -424,6 +426,135 @@ static void check_step_records(std::mt19937& rng) {
   }
 }
 
+// The scaffold of the read-only queries and the log rings: bank_range_ok, pending_kb, plan_staging, ring_range_ok, ring_pieces.
+static void check_scaffold(std::mt19937& rng) {
+  // the range check against its plain statement, sums in 64 bits; counts near INT_MAX must not overflow
+  const int edge[] = {INT_MIN, INT_MIN + 1, -7, -1, 0, 1, 2, 3, 4, 5, 6, 7, INT_MAX - 6, INT_MAX - 1, INT_MAX};
+  for (int batch = 1; batch <= 6; ++batch) {
+    HostPlan h;
+    h.batch = batch;
+    for (int b0 : edge)
+      for (int count : edge) {
+        bool inside = count >= 1;
+        for (long long b = b0; inside && b < (long long)b0 + std::min(count, 8); ++b) inside = b >= 0 && b < batch;
+        if (count > 8) inside = false;                 // (more trajectories than any bank here)
+        CHECK(bank_range_ok(&h, b0, count) == inside, "batch %d range (%d, %d)", batch, b0, count);
+      }
+  }
+  for (int k = 0; k <= KTOT; ++k) {
+    HostPlan h;
+    h.batch = 1;
+    h.n = {3};
+    h.neff_enq = {3};
+    h.cu_count = 256;
+    h.pending_k = k;
+    CHECK(pending_kb(&h) == 4 * plan_pass(&h).nkt && pending_kb(&h) >= k && pending_kb(&h) < k + 4, "pending_kb(%d)", k);
+  }
+  // the staging layout: random tables ...
+  for (int it = 0; it < 20000; ++it) {
+    StagingPlan s;
+    s.inputs = rng() % 3 == 0 ? 0 : rng() % 5000;
+    const int nd = (int)(rng() % (STAGE_DSTS + 1));
+    for (int i = 0; i < nd; ++i) s.add(rng() % 4 != 0, rng() % 3 == 0 ? 0 : (size_t)(rng() % 100000), rng() % 2 == 0);
+    const size_t total = plan_staging(s);
+    size_t sum = s.inputs, prev_end = s.inputs;
+    for (int i = 0; i < nd; ++i) {
+      const StagingPlan::Dst& d = s.dst[i];
+      CHECK(d.staged == (d.present && d.words > 0 && !d.device), "destination %d staged %d", i, (int)d.staged);
+      if (!d.staged) continue;
+      CHECK(d.at == prev_end && d.at >= s.inputs && d.at + d.words <= total, "region %d [%zu, %zu) behind %zu of %zu", i, d.at,
+            d.at + d.words, prev_end, total);           // (table order, back to back: disjoint)
+      prev_end = d.at + d.words;
+      sum += d.words;
+    }
+    CHECK(total == sum && total == prev_end, "total %zu, sum %zu", total, sum);
+  }
+  {                                                    // (arithmetic in size_t: two regions of 3 G doubles)
+    StagingPlan s;
+    s.add(true, (size_t)3 << 30, false);
+    s.add(true, (size_t)3 << 30, false);
+    CHECK(plan_staging(s) == (size_t)6 << 30 && s.dst[1].at == (size_t)3 << 30, "size_t arithmetic");
+  }
+  // ... and the three queries' tables against the sums their entry points formed by hand before they shared the planner
+  for (int it = 0; it < 20000; ++it) {
+    const size_t count = 1 + rng() % 40, stride = 1 + rng() % MMAX, cap = rng() % 3 == 0 ? 0 : rng() % 300;
+    bool pin[STAGE_DSTS], have[STAGE_DSTS];
+    for (int i = 0; i < STAGE_DSTS; ++i) {
+      pin[i] = rng() % 2 == 0;
+      have[i] = rng() % 3 != 0;
+    }
+    {                                                  // ekf_download_marginals(pose, landmarks): pose is never NULL
+      const size_t mcap = have[1] ? cap : 0, pose_words = count * 9, lm_words = count * mcap * 4;
+      StagingPlan s;
+      s.add(true, pose_words, pin[0]);
+      s.add(have[1], lm_words, pin[1]);
+      CHECK(plan_staging(s) == (pin[0] ? 0 : pose_words) + (have[1] && !pin[1] ? lm_words : 0), "marginals layout");
+    }
+    {                                                  // ekf_associate: cand is never NULL, the full matrices come together
+      const bool full = have[4];
+      const size_t obs = count * stride, full_words = obs * (full ? cap : 0);
+      const size_t m_words = (count + 1) / 2, part_words = count * (1 + rng() % 6) * stride * 8;
+      const size_t words[STAGE_DSTS] = {obs, obs * 2, obs * 2, obs, full_words, full_words};
+      const bool given[STAGE_DSTS] = {true, have[1], have[2], have[3], full, full};
+      StagingPlan s;
+      s.inputs = 2 * obs + m_words + part_words;
+      size_t need = 2 * obs + m_words + part_words;
+      for (int i = 0; i < STAGE_DSTS; ++i) {
+        s.add(given[i], words[i], given[i] && words[i] && pin[i]);
+        if (given[i] && words[i] && !pin[i]) need += words[i];
+      }
+      CHECK(plan_staging(s) == need, "associate layout");
+    }
+    {                                                  // ekf_download_joint(mean, cov): cov is never NULL
+      const size_t ns = 3 + 2 * (1 + rng() % JMAX), nsp = (ns + JQ_TILE - 1) / JQ_TILE * JQ_TILE;
+      const size_t sel_words = (count * 2 * nsp + 1) / 2, mean_words = count * ns, cov_words = mean_words * ns;
+      StagingPlan s;
+      s.inputs = sel_words;
+      s.add(have[0], mean_words, pin[0]);
+      s.add(true, cov_words, pin[1]);
+      CHECK(plan_staging(s) == sel_words + (have[0] && !pin[0] ? mean_words : 0) + (pin[1] ? 0 : cov_words), "joint layout");
+    }
+  }
+  // the rings: "among the last cap of the steps logged", stated step by step, and the pieces of a range
+  for (int cap = 1; cap <= 5; ++cap)
+    for (long long steps = 0; steps <= 12; ++steps)
+      for (long long first = -2; first <= 14; ++first)
+        for (int count = -1; count <= 7; ++count) {
+          bool ok = count >= 0 && first >= 0;
+          for (long long t = first; ok && t < first + count; ++t) ok = t < steps && t >= steps - cap;
+          // (an empty range is held to the same window: it names a position, [first, first) with first in [steps - cap, steps])
+          if (count == 0) ok = first >= 0 && first <= steps && first >= steps - cap;
+          CHECK(ring_range_ok(first, count, steps, cap) == ok, "ring range (%lld, %d) of %lld, cap %d", first, count, steps, cap);
+          if (!ok) continue;
+          const RingPieces rp = ring_pieces(first, count, cap);
+          CHECK(rp.n <= 2 && (rp.n > 0) == (count > 0), "%d pieces", rp.n);
+          long done = 0;
+          for (int i = 0; i < rp.n; ++i) {
+            const RingPieces::Piece& c = rp.piece[i];
+            CHECK(c.done == done && c.rows >= 1 && c.slot == (long)((first + done) % cap) && c.slot + c.rows <= cap,
+                  "piece %d: slot %ld, %ld rows from %ld (cap %d)", i, c.slot, c.rows, c.done, cap);
+            done += c.rows;
+          }
+          CHECK(done == count, "pieces cover %ld of %d", done, count);
+        }
+  CHECK(!ring_range_ok(LLONG_MAX - 1, 5, LLONG_MAX, 8) && ring_range_ok(LLONG_MAX - 5, 5, LLONG_MAX, 8), "ring range at the top");
+  for (int it = 0; it < 20000; ++it) {                 // larger rings, random ranges inside the window
+    const int cap = 1 + (int)(rng() % 1000);
+    const long long steps = (long long)(rng() % 100000);
+    const int count = (int)(rng() % (std::min<long long>(cap, steps) + 1));
+    const long long lo = std::max<long long>(0, steps - cap), first = lo + (long long)(rng() % (steps - count - lo + 1));
+    CHECK(ring_range_ok(first, count, steps, cap), "ring range (%lld, %d) of %lld, cap %d", first, count, steps, cap);
+    const RingPieces rp = ring_pieces(first, count, cap);
+    long done = 0;
+    for (int i = 0; i < rp.n; ++i) {
+      CHECK(rp.piece[i].done == done && rp.piece[i].slot == (long)((first + done) % cap) && rp.piece[i].rows >= 1 &&
+            rp.piece[i].slot + rp.piece[i].rows <= cap, "piece %d", i);
+      done += rp.piece[i].rows;
+    }
+    CHECK(rp.n <= 2 && done == count, "%d pieces cover %ld of %d", rp.n, done, count);
+  }
+}
+
 int main() {
   std::mt19937 rng(20261004);
   check_layout();
@@ -432,6 +563,7 @@ int main() {
   check_planning(rng);
   check_launch_plans(rng);
   check_step_records(rng);
+  check_scaffold(rng);
   std::printf("host_plan_check: %ld checks passed\n", checks);
   return 0;
 }

@@ -267,8 +267,12 @@ def test_every_entry_point_selects_its_device():
         body = bodies[name][2]
         if "hipSetDevice(h->device)" in body:
             return True
-        if gpu.search(body):
-            return False
+        first = gpu.search(body)
+        if first:
+            # ... unless, before its first device call, it has gone through a function that selects the device in its own
+            # body (query_begin: the entry points of the read-only queries)
+            before = set(re.findall(r"\b([A-Za-z_]\w*)\s*\(", body[:first.start()]))
+            return any("hipSetDevice(h->device)" in bodies[c][2] for c in before if c in bodies and c != name)
         return all(selects(c, seen + (name,)) for c in callees(name) if c not in seen and touches(c))
 
     missing = sorted(n for n in exported if touches(n) and not selects(n))
