@@ -13,69 +13,7 @@
 
 #include "ekf_device.h"
 #include "ekf_host_plan.h"
-
-namespace ekf {
-void launch_solve(hipStream_t, const double*, const double*, const double*, const double*, double*, const double*,
-                  double*, const int*, const StepIn*, SolveOut*, unsigned*, double*, const int*, unsigned*, const DeviceConfig&,
-                  int, long, int, int);
-void launch_step_split(hipStream_t, int, double*, double*, double*, const double*, double*, const double*, double*,
-                       const int*, const StepIn*, SolveOut*, unsigned*, double*, const int*, unsigned*, unsigned*, unsigned,
-                       int, const DeviceConfig&, int, long, int, int, int);
-void launch_step_split_tp(hipStream_t, int, double*, double*, double*, const double*, double*, const double*, double*,
-                          const int*, const StepIn*, SolveOut*, unsigned*, double*, const int*, unsigned*, SolveOut*,
-                          unsigned*, unsigned, int, const DeviceConfig&, int, long, int, int, int);
-void launch_panels(hipStream_t, int, bool, double*, double*, double*, const double*, double*, const int*,
-                   const SolveOut*, const double*, int, long, int, int);
-void launch_flush(hipStream_t, const PassPlan&, double*, const double*, const double*, const double*, const int*,
-                  const SolveOut*, int, long, int);
-void launch_flush_rs(hipStream_t, const PassPlan&, double*, const double*, const double*, const double*, const int*,
-                     const SolveOut*, int, long, int, unsigned*, const int*, const CadOut*);
-int flush_rs_queue_words();
-void launch_predict_rc(hipStream_t, double*, const double*, double*, const int*, const SolveOut*, int, long,
-                       int, int);
-void launch_add_landmarks(hipStream_t, double*, double*, int, int, int, double, const double*);
-void launch_mirror(hipStream_t, double*, const int*, int, long, int, int);
-void launch_pack_small(hipStream_t, const double*, const double*, const unsigned*, int, int, double*);
-void launch_pack_dense(hipStream_t, const double*, int, int, double*);
-void launch_innov_step(hipStream_t, const StepIn*, const SolveOut*, int, int, int, const InnovLog&);
-void launch_innov_cad(hipStream_t, const StepIn*, const CadPlan*, const CadOut*, int, int, int, const InnovLog&);
-int launch_small_stream(hipStream_t, double*, const double*, double*, const int*, const StepIn*, int, int, unsigned*,
-                        const DeviceConfig&, int, long, int, double*, int, unsigned long long*, unsigned long long, int,
-                        const InnovLog*, const PoseLog*);
-void launch_pose_step(hipStream_t, const double*, const double*, const double*, const double*, const double*, int, long, int, int,
-                      const PoseLog&);
-void launch_associate(hipStream_t, const DetIn*, int*, int*, int*, double*, double*, double*, double*, StepIn*,
-                      AssocOut*, unsigned*, const AssocConfig&, int, long, int, int, int);
-void launch_fill_diag(hipStream_t, double*, int, int, const double*);
-int dense_propagate(hipStream_t, double* P, double* tmp, const double* F, const double* Q, int n, int ld);
-void launch_solve_cad(hipStream_t, const double*, const double*, double*, double*, const int*, const StepIn*, const CadPlan*, int,
-                      CadOut*, unsigned*, const DeviceConfig&, int, long, const double*, int, double*, int, int, bool, const double*,
-                      unsigned*, unsigned, const CadPre*, const PoseLog*);
-void launch_chain_cad(hipStream_t, const double*, const double*, const double*, const double*, const CadOut*, const StepIn*,
-                      const CadPlan*, int, const DeviceConfig&, int, long, double*, double*, double*, double*, unsigned*, unsigned,
-                      unsigned*, int, unsigned, const CadPre*, CadPre*, const CadPlan*, bool);
-void launch_mark(hipStream_t, unsigned*, unsigned);
-void launch_gate(hipStream_t, unsigned*, unsigned, unsigned*, int);
-int chain_sync_words();
-void launch_snap_pose(hipStream_t, const double*, const int*, int, long, int, int, double*);
-void launch_gather_cad(hipStream_t, const double*, const double*, const double*, const double*, const StepIn*, const CadPlan*, int,
-                       int, const DeviceConfig&, int, long, double*);
-long cadence_gbuf_doubles();
-void launch_panels_cad(hipStream_t, double*, double*, double*, const double*, double*, const int*, const CadOut*,
-                       SolveOut*, unsigned*, int, long, int, int, int, const double*, double*, unsigned*, unsigned, unsigned*,
-                       int, unsigned, bool);
-void launch_marginals(hipStream_t, const PendingView&, int, double*, double*);
-long assoc_query_part_doubles(int, int, int);
-void launch_assoc_query(hipStream_t, const PendingView&, const DeviceConfig&, int, int, int, const double*, const double*,
-                        const int*, double*, double*, double*, int*, double*, double*, double*);
-void launch_joint(hipStream_t, const PendingView&, int, int, int, const int*, double*, double*);
-void launch_remove(hipStream_t, int, double*, double*, const int*, const int*, const int*, unsigned*, unsigned*, int, int, int, int,
-                   int, unsigned, int, long);
-void launch_direct(hipStream_t, int, double*, double*, double*, double*, double*, const int*, SolveOut*, unsigned*, unsigned*,
-                   const int*, const double*, double*, int, long, int, int);
-void launch_copy_traj(hipStream_t, bool, const double*, double*, const double*, double*, int*, const unsigned*, unsigned*, const int*,
-                      int, int, int, long, int, long);
-}  // namespace ekf
+#include "ekf_launch.h"
 
 using namespace ekf;
 
@@ -700,6 +638,30 @@ static PendingView pending_view(const ekf_handle* h, int b0, int count) {
                      pending_kb(h)};
 }
 
+static BankView bank_view(const ekf_handle* h) { return BankView{h->dP, h->dV, h->dW, h->dn, h->dso, h->dflags, h->dqueue, h->ld, h->pstride, h->batch}; }
+// The halves of the double-buffered arrays a step's or a cadence's launches read and write; the enqueueing function flips cur,
+// dcur (and cpar) behind the step.  dmu2[cur] is the mean the step reads -- of cadence c: its landmark entries are the mean
+// before the cadence --, dmu2[cur ^ 1] the one it writes (the one cadence c's solve leaves the pose in); ddacc2[dcur] the
+// pending pose noise, ddacc2[dcur ^ 1] what the step leaves pending; dcad2[cpar] cadence c's records; dprow3[cpar ^ 1] the pose
+// rows BEFORE it (taken from P_base by launch_snap_pose in front of a chained run's first cadence), dprow3[cpar] where its panel
+// launch leaves them.  CAD_NEXT: the cadence after the handle's current one -- every parity the other way round --, for the
+// solve enqueue_cadence runs ahead (chained: before it flips the handle; look-ahead: behind the flip, the same copies).
+enum CadWhich { CAD_THIS = 0, CAD_NEXT = 1 };
+static StepBufs step_bufs(const ekf_handle* h, CadWhich which = CAD_THIS) {
+  const int cur = h->cur ^ which, dcur = h->dcur ^ which, cpar = h->cpar ^ which;
+  return StepBufs{h->dmu2[cur], h->dmu2[cur ^ 1], h->ddacc2[dcur], h->ddacc2[dcur ^ 1], h->dcad2[cpar], h->dprow3[cpar ^ 1],
+                  h->dprow3[cpar]};
+}
+// Where a launch logs: ring row `slot` of the innovation log (positions from jbase on) and of the pose log.
+static InnovLog innov_log(const ekf_handle* h, long slot, int jbase) { return InnovLog{h->dinnov, h->dinnov_m, slot, h->innov_cap, jbase}; }
+static PoseLog pose_log(const ekf_handle* h, long slot) { return PoseLog{h->dpose, slot, h->pose_cap}; }
+// The largest state of the bank: what sizes a launch's grid.  `device_grown` (the per-step paths, which ekf_step_detections
+// runs without reading the sizes back): while sizes_dirty only n_max bounds the states.  ekf_stream_run refreshes the sizes
+// before it plans its cadences from h->n, so its launches pass false and read h->n whatever the flag says.
+static int bank_n_hi(const ekf_handle* h, bool device_grown) {
+  return device_grown && h->sizes_dirty ? h->n_max : *std::max_element(h->n.begin(), h->n.end());
+}
+
 static int set_size(ekf_handle* h, int b, int n) {
   h->n[b] = n;
   HIP_TRY(h, hipMemcpyAsync(h->dn + b, &h->n[b], sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -1236,8 +1198,7 @@ extern "C" int ekf_remove_landmarks(ekf_handle* h, int b, const int* landmarks, 
   HIP_TRY(h, hipMemcpyAsync(h->drm_tab + h->ld, rp.dst.data(), sizeof(int) * nt, hipMemcpyHostToDevice, h->stream));
   h->rm_seq += 1;
   if (h->rm_seq == 0) h->rm_seq = 1;                   // (0 is what the announcements start at)
-  launch_remove(h->stream, rp.nq, h->dP, h->dmu2[h->cur], h->dn, h->drm_tab, h->drm_tab + h->ld, h->drm_flag, h->dflags, b0, nb,
-                rp.rows, rp.k2, rp.r0, h->rm_seq, h->ld, h->pstride);
+  launch_remove(h->stream, bank_view(h), h->dmu2[h->cur], rp, h->drm_tab, h->drm_tab + h->ld, h->drm_flag, b0, nb, h->rm_seq);
   HIP_TRY(h, hipGetLastError());
   // the active bound loses the removed indices below it; everything at or beyond it was, and still is, uncorrelated
   for (int t = b0; t < b0 + nb; ++t) {
@@ -1371,9 +1332,9 @@ static int flush_pending(ekf_handle* h, hipStream_t st, const CadOut* wv) {
   h->last_streaming = p.streaming ? 1 : 0;
   h->last_shares = shares ? h->shares_ok : 0;
   if (p.kernel == 2)                                   // (the step before left the queue heads at zero)
-    launch_flush_rs(st, p, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dn, h->dso, h->ld, h->pstride, h->batch, h->dqueue, shares, wv);
+    launch_flush_rs(st, p, bank_view(h), step_bufs(h).dacc_in, shares, wv);
   else
-    launch_flush(st, p, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dn, h->dso, h->ld, h->pstride, h->batch);
+    launch_flush(st, p, bank_view(h), step_bufs(h).dacc_in);
   if (timed) HIP_TRY(h, hipEventRecord(e1, st));
   HIP_TRY(h, hipGetLastError());
   h->pending_k = 0;                                    // (with no rank pending k_solve takes the pending noise as zero: no clearing)
@@ -1425,8 +1386,7 @@ extern "C" int ekf_update_direct(ekf_handle* h, int b0, int count, const int* ta
     HIP_TRY(h, hipMemcpyAsync(dmeas, h->direct_dbls.data(), sizeof(double) * h->direct_dbls.size(), hipMemcpyHostToDevice, h->stream));
     ProfBracket pb;
     if (int rc = prof_open(h, 4, h->stream, &pb)) return rc;
-    launch_direct(h->stream, direct_rows_cap(dp.kpad), h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dmu2[h->cur], h->dn, h->dso,
-                  h->dflags, h->dqueue, dplan, dmeas, dout, h->ld, h->pstride, h->batch, dp.kpad);
+    launch_direct(h->stream, direct_rows_cap(dp.kpad), bank_view(h), h->ddacc2[h->dcur], h->dmu2[h->cur], dplan, dmeas, dout, dp.kpad);
     if (int rc = prof_close(h, &pb)) return rc;
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(h->direct_out.data(), dout, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->stream));
@@ -1450,19 +1410,18 @@ extern "C" int ekf_update_direct(ekf_handle* h, int b0, int count, const int* ta
 
 // The small-state path (ekf_small.hip, ekf_host_plan.h: small_path): `nsteps` steps per trajectory in one launch.
 static int enqueue_small(ekf_handle* h, const StepIn* d_in, int nsteps) {
-  const int n_hi = h->sizes_dirty ? h->n_max : *std::max_element(h->n.begin(), h->n.end());
+  const int n_hi = bank_n_hi(h, true);
   const int out_b = h->fetch_b;                        // (ekf_step_fetch, last pass of its step: see there)
   h->fetch_b = -1;
   // (this path writes the log itself, and applies the NIS gate and the noise table in the same instantiations)
   const bool logged = h->dinnov && h->lg_slot >= 0;
-  const InnovLog lg = logged ? InnovLog{h->dinnov, h->dinnov_m, h->lg_slot, h->innov_cap, h->lg_jbase} : InnovLog{};
+  const InnovLog lg = logged ? innov_log(h, h->lg_slot, h->lg_jbase) : InnovLog{};
   // (the pose log likewise: every pass of a step writes the step's row, the last one last)
   const bool posed = h->dpose && h->pl_slot >= 0;
-  const PoseLog plg = posed ? PoseLog{h->dpose, h->pl_slot, h->pose_cap} : PoseLog{};
-  if (launch_small_stream(h->stream, h->dP, h->dmu2[h->cur], h->dmu2[h->cur ^ 1], h->dn, d_in, h->batch, nsteps, h->dflags,
-                          h->dcfg, h->ld, h->pstride, n_hi, out_b >= 0 ? h->h_pack : nullptr, out_b,
-                          out_b >= 0 ? reinterpret_cast<unsigned long long*>(h->h_pack + PACK_WORDS - 1) : nullptr,
-                          out_b >= 0 ? ++h->fetch_seq : 0ull, plan_small(h, n_hi),
+  const PoseLog plg = posed ? pose_log(h, h->pl_slot) : PoseLog{};
+  SmallFetch fetch;
+  if (out_b >= 0) fetch = SmallFetch{h->h_pack, out_b, reinterpret_cast<unsigned long long*>(h->h_pack + PACK_WORDS - 1), ++h->fetch_seq};
+  if (launch_small_stream(h->stream, bank_view(h), step_bufs(h), d_in, nsteps, h->dcfg, n_hi, plan_small(h, n_hi), fetch,
                           logged || h->dcfg.gate_rej || h->dcfg.noise ? &lg : nullptr, posed ? &plg : nullptr) != 0)
     return fail(h, EKF_ERR_HIP, "small-state launch: hipFuncSetAttribute failed");
   HIP_TRY(h, hipGetLastError());
@@ -1476,7 +1435,7 @@ static int enqueue_small(ekf_handle* h, const StepIn* d_in, int nsteps) {
 static void log_pass(ekf_handle* h, const StepIn* d_in) {
   if (!h->dinnov || h->lg_slot < 0) return;
   launch_innov_step(h->stream, d_in, h->dso, h->dcfg.enable_measurement_model, h->dcfg.gate_rej != nullptr, h->batch,
-                    InnovLog{h->dinnov, h->dinnov_m, h->lg_slot, h->innov_cap, h->lg_jbase});
+                    innov_log(h, h->lg_slot, h->lg_jbase));
 }
 
 // The pose log's row of a step that ran on the per-step kernels: formed from what is in memory behind the step's last pass
@@ -1484,8 +1443,7 @@ static void log_pass(ekf_handle* h, const StepIn* d_in) {
 // path has written the row itself.
 static int log_pose_step(ekf_handle* h) {
   if (!h->dpose || h->pl_slot < 0 || small_path(h)) return EKF_OK;
-  launch_pose_step(h->stream, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dmu2[h->cur], h->ld, h->pstride, pending_kb(h),
-                   h->batch, PoseLog{h->dpose, h->pl_slot, h->pose_cap});
+  launch_pose_step(h->stream, pending_view(h, 0, h->batch), pose_log(h, h->pl_slot));
   HIP_TRY(h, hipGetLastError());
   return EKF_OK;
 }
@@ -1493,15 +1451,14 @@ static int log_pose_step(ekf_handle* h) {
 // Enqueue one device pass with inputs already at d_in (StepIn[batch]); m_hi = max m over the batch.
 static int enqueue_pass(ekf_handle* h, const StepIn* d_in, int m_hi) {
   if (small_path(h)) return enqueue_small(h, d_in, 1);
-  const int n_hi = h->sizes_dirty ? h->n_max : *std::max_element(h->n.begin(), h->n.end());
+  const int n_hi = bank_n_hi(h, true);
   const StepPlan sp = plan_step(h, m_hi, n_hi);
-  const double* mu_in = h->dmu2[h->cur];
-  double* mu_out = h->dmu2[h->cur ^ 1];
+  const BankView bank = bank_view(h);
+  const StepBufs bufs = step_bufs(h);
   if (sp.form == STEP_PREDICT) {
     // prediction only, nothing pending: rows/cols 0,1 of P_base directly, O(n)
-    launch_solve(h->stream, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->ddacc2[h->dcur ^ 1], mu_in, mu_out, h->dn, d_in, h->dso,
-                 h->dflags, h->dfac, h->dfloor, h->dqueue, h->dcfg, h->ld, h->pstride, h->batch, 0);
-    launch_predict_rc(h->stream, h->dP, mu_in, mu_out, h->dn, h->dso, h->ld, h->pstride, h->batch, n_hi);
+    launch_solve(h->stream, bank, bufs, StepArgs{d_in, h->dfac, h->dfloor, 0}, h->dcfg);
+    launch_predict_rc(h->stream, bank, bufs, n_hi);
     log_pass(h, d_in);
     // k_predict_rc applied the noise itself (and nothing reads the pending-noise buffers while no rank is pending)
     HIP_TRY(h, hipGetLastError());
@@ -1510,21 +1467,15 @@ static int enqueue_pass(ekf_handle* h, const StepIn* d_in, int m_hi) {
   }
   if (sp.flush_before)
     if (int rc = flush_pending(h)) return rc;
-  const double* dacc_in = h->ddacc2[h->dcur];
-  double* dacc_out = h->ddacc2[h->dcur ^ 1];
-  if (sp.form == STEP_SPLIT) {
-    launch_step_split(h->stream, sp.mcap, h->dP, h->dV, h->dW, dacc_in, dacc_out, mu_in, mu_out, h->dn, d_in, h->dso,
-                      h->dflags, h->dfac, h->dfloor, h->dqueue, h->dready, ++h->step_seq, h->opt_fused_step == 1, h->dcfg, h->ld,
-                      h->pstride, h->batch, n_hi, h->pending_k);
-  } else if (sp.form == STEP_SPLIT_TP) {
-    launch_step_split_tp(h->stream, sp.mcap, h->dP, h->dV, h->dW, dacc_in, dacc_out, mu_in, mu_out, h->dn, d_in, h->dso,
-                         h->dflags, h->dfac, h->dfloor, h->dqueue, h->dmbox, h->dready, ++h->step_seq, h->opt_fused_step == 1,
-                         h->dcfg, h->ld, h->pstride, h->batch, n_hi, h->pending_k);
+  StepArgs sa{d_in, h->dfac, h->dfloor, h->pending_k};
+  if (sp.form == STEP_SPLIT || sp.form == STEP_SPLIT_TP) {
+    sa.mbox = h->dmbox;                                // (the throughput shape's; k_step_split has none)
+    sa.ready = h->dready, sa.seq = ++h->step_seq, sa.publish = h->opt_fused_step == 1;
+    if (sp.form == STEP_SPLIT) launch_step_split(h->stream, sp.mcap, bank, bufs, sa, h->dcfg, n_hi);
+    else launch_step_split_tp(h->stream, sp.mcap, bank, bufs, sa, h->dcfg, n_hi);
   } else {
-    launch_solve(h->stream, h->dP, h->dV, h->dW, dacc_in, dacc_out, mu_in, mu_out, h->dn, d_in, h->dso, h->dflags,
-                 h->dfac, h->dfloor, h->dqueue, h->dcfg, h->ld, h->pstride, h->batch, h->pending_k);
-    launch_panels(h->stream, sp.mcap, sp.panels_latency, h->dP, h->dV, h->dW, mu_in, mu_out, h->dn, h->dso, h->dfac, h->ld,
-                  h->pstride, h->batch, n_hi);
+    launch_solve(h->stream, bank, bufs, sa, h->dcfg);
+    launch_panels(h->stream, sp.mcap, sp.panels_latency, bank, bufs, h->dfac, n_hi);
   }
   log_pass(h, d_in);
   HIP_TRY(h, hipGetLastError());
@@ -1601,25 +1552,25 @@ static int join_aux(ekf_handle* h) {
 static void log_cadence(ekf_handle* h, const CadPlan* dpl, const CadOut* co) {
   if (!h->dinnov || h->lg_tslot < 0) return;
   launch_innov_cad(h->stream, h->d_stream, dpl, co, h->dcfg.enable_measurement_model, h->dcfg.gate_rej != nullptr, h->batch,
-                   InnovLog{h->dinnov, h->dinnov_m, h->lg_tslot, h->innov_cap, 0});
+                   innov_log(h, h->lg_tslot, 0));
 }
 
 static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_presolved) {
   *next_presolved = false;
   const RunPlan& rp = h->run_plan;
   // (the pose log: k_solve_cad_plog writes stream step t's row (pl_tslot + t) % pose_cap itself; nullptr: off)
-  const PoseLog plg_on{h->dpose, h->pl_tslot, h->pose_cap};
+  const PoseLog plg_on = pose_log(h, h->pl_tslot);
   const PoseLog* plg = h->dpose && h->pl_tslot >= 0 ? &plg_on : nullptr;
-  const int n_hi = *std::max_element(h->n.begin(), h->n.end());
+  const int n_hi = bank_n_hi(h, false);
   const CadPlan* dpl = h->dplan2[h->plan_cur] + (size_t)c * h->batch;
   for (int i = 0; i < 2; ++i)
     if (!h->dcad2[i]) HIP_TRY(h, hipMalloc(&h->dcad2[i], sizeof(CadOut) * h->batch));
-  CadOut* dcad = h->dcad2[h->cpar];
-  double* prow_out = h->chain_run ? h->dprow3[h->cpar] : nullptr;
+  const BankView bank = bank_view(h);
+  StepBufs cad = step_bufs(h, CAD_THIS);               // this cadence's buffers ...
+  const StepBufs next = step_bufs(h, CAD_NEXT);        // ... and the next one's, for the solve enqueued ahead (chained, look-ahead)
+  if (!h->chain_run) cad.prow3_out = nullptr;          // (only a chained run keeps the pose rows)
   const long serial = h->cad_serial++;                 // this cadence's number (CadPre copies are looked up by it)
   for (int b = 0; b < h->batch; ++b) h->neff_enq[b] = rp.entries[(size_t)c * h->batch + b].neff;
-  const double* mu_in = h->dmu2[h->cur];
-  double* mu_out = h->dmu2[h->cur ^ 1];
   // what follows the panel launch is decided before anything is launched (chained: it goes to the second stream)
   CadStepPlan cp = plan_cadence_step(h, rp, c, n_hi, presolved);
   if (cp.gather_cols && !h->dcolbuf && hipMalloc(&h->dcolbuf, sizeof(double) * (size_t)h->batch * CAD_CU * h->ld) != hipSuccess) {
@@ -1634,16 +1585,17 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     if (int rc = join_aux(h)) return rc;
     ProfBracket pb;
     if (int rc = prof_open(h, 1, h->stream, &pb)) return rc;
-    launch_solve_cad(h->stream, h->dP, mu_in, mu_out, h->ddacc2[h->dcur ^ 1], h->dn, h->d_stream, dpl, h->batch, dcad,
-                     h->dflags, h->dcfg, h->ld, h->pstride, nullptr, 0, colbuf, n_hi, cp.col_wgs, h->chain_run, nullptr, nullptr, 0u, nullptr, plg);
+    SolveCadArgs sx;
+    sx.colbuf = colbuf, sx.col_wgs = cp.col_wgs;
+    sx.chain = h->chain_run;
+    launch_solve_cad(h->stream, bank, cad, h->d_stream, dpl, h->dcfg, n_hi, sx, plg);
     if (int rc = prof_close(h, &pb)) return rc;
-    log_cadence(h, dpl, dcad);
+    log_cadence(h, dpl, cad.cad);
   }
   const bool due = cp.due, beside = cp.beside, chain_next = cp.chain_next, wv = cp.w_from_v;
   const int ranks = 2 * rp.slots_hi[c], nrp = (ranks + 3) & ~3;   // every trajectory writes the busiest one's ranks (zeros beyond its own)
   hipStream_t pst = h->stream;                         // the panel launch's stream
-  unsigned* psync = nullptr;
-  unsigned tail_target = 0u;
+  PanelCadArgs px{nrp, cp.panel, wv, colbuf};
   const CadPlan* dpl2 = dpl + h->batch;
   int rc = EKF_OK;
   if (chain_next) {
@@ -1656,24 +1608,25 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     h->sigma += 1u;
     const int gw = chain_gather_workgroups(h->batch, h->cu_count);
     h->gather_count += (unsigned)(h->batch * gw);
-    // (dmu2[cur] is the mean cadence c reads -- its landmark entries are the mean before the cadence --, dmu2[cur ^ 1] the one
-    //  its solve left the pose in; dcad2[cpar] cadence c's records, dprow3[cpar ^ 1] the pose rows BEFORE it)
     ProfBracket pbc, pbs;
     if (int rc2 = prof_open(h, 2, h->stream, &pbc)) return rc2;
     // the next cadence's inputs if an earlier chain launch formed them; the one after it: formed by this launch
     const CadPre* pre_in = h->pre_serial[(serial + 1) & 1] == serial + 1 ? h->dpre[(serial + 1) & 1] : nullptr;
     CadPre* pre_out = c + 2 < rp.ncad ? h->dpre[(serial + 2) & 1] : nullptr;
-    launch_chain_cad(h->stream, h->dP, h->dprow3[h->cpar ^ 1], h->dmu2[h->cur], h->dmu2[h->cur ^ 1], dcad, h->d_stream,
-                     dpl2, h->batch, h->dcfg, h->ld, h->pstride, h->dgbuf, h->dgmu, h->dxg, h->dbg, h->dsync, h->gather_count,
-                     h->dflags, gw, h->sigma, pre_in, pre_out, pre_out ? dpl2 + h->batch : nullptr, h->aux_pass);
+    ChainArgs cx{h->dgbuf, h->dgmu, h->dxg, h->dbg, h->dsync};
+    cx.sigma = h->sigma, cx.gather_target = h->gather_count, cx.gw = gw, cx.wait_pass = h->aux_pass;
+    cx.pre_in = pre_in, cx.pre_out = pre_out, cx.plan2 = pre_out ? dpl2 + h->batch : nullptr;
+    launch_chain_cad(h->stream, bank, cad, h->d_stream, dpl2, h->dcfg, cx);
     if (pre_out) h->pre_serial[(serial + 2) & 1] = serial + 2;
     if (int rc2 = prof_close(h, &pbc)) return rc2;
     if (int rc2 = prof_open(h, 1, h->stream, &pbs)) return rc2;
-    launch_solve_cad(h->stream, h->dP, h->dmu2[h->cur ^ 1], h->dmu2[h->cur], h->ddacc2[h->dcur], h->dn, h->d_stream, dpl2,
-                     h->batch, h->dcad2[h->cpar ^ 1], h->dflags, h->dcfg, h->ld, h->pstride, h->dgbuf, 1, nullptr, n_hi, 0, true, h->dgmu,
-                     h->dsync, h->sigma, pre_in, plg);
+    SolveCadArgs sx;                                   // (block and mean from the chain launch: one part, no columns to gather)
+    sx.gbuf = h->dgbuf, sx.gparts = 1;
+    sx.chain = true;
+    sx.gmu = h->dgmu, sx.sync = h->dsync, sx.start_sigma = h->sigma, sx.pre = pre_in;
+    launch_solve_cad(h->stream, bank, next, h->d_stream, dpl2, h->dcfg, n_hi, sx, plg);
     if (int rc2 = prof_close(h, &pbs)) return rc2;
-    log_cadence(h, dpl2, h->dcad2[h->cpar ^ 1]);       // (enqueued before the gate: it waits for nothing)
+    log_cadence(h, dpl2, next.cad);                    // (enqueued before the gate: it waits for nothing)
     // From here on the next cadence's solve overwrites the pose mean and the pending-noise buffer: a failure below cannot be
     // undone.  Whatever happens the streams are joined, and a failure marks every trajectory undefined (EKF_ERR_STATE from
     // then on, until it is uploaded again).
@@ -1682,17 +1635,14 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     //  a large launch ever spins)
     launch_gate(h->aux, h->dsync, h->sigma, h->dflags, h->batch);
     pst = h->aux;
-    psync = h->dsync;
-    tail_target = h->gather_count;
+    px.sync = h->dsync, px.tail_target = h->gather_count, px.start_sigma = h->sigma;
   } else if (int rc2 = join_aux(h)) {
     return rc2;
   }
   {
     ProfBracket pb;
     if (int rc2 = prof_open(h, 3, pst, &pb)) return rc2;
-    launch_panels_cad(pst, h->dP, h->dV, h->dW, mu_in, mu_out, h->dn, dcad, h->dso, h->dqueue, h->ld,
-                      h->pstride, h->batch, n_hi, nrp, colbuf, prow_out, psync, tail_target, h->dflags, cp.panel,
-                      chain_next ? h->sigma : 0u, wv);
+    launch_panels_cad(pst, bank, cad, n_hi, px);
     if (int rc2 = prof_close(h, &pb)) return rc2;
   }
   if (hipGetLastError() != hipSuccess && rc == EKF_OK) rc = fail(h, EKF_ERR_HIP, "fused cadence: launch of the panel kernel failed");
@@ -1729,7 +1679,7 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
   if (!due) return EKF_OK;
   if (!beside) {
     if (wv) h->w_from_v_passes += 1;
-    return flush_pending(h, nullptr, wv ? dcad : nullptr);
+    return flush_pending(h, nullptr, wv ? cad.cad : nullptr);
   }
   if (!h->dgbuf) HIP_TRY(h, hipMalloc(&h->dgbuf, sizeof(double) * cadence_gbuf_doubles() * h->batch));
   // ---- look-ahead: gather (stream) -> { pass (second stream) | solve of the next cadence (stream) } -> join ----
@@ -1737,8 +1687,7 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
   {
     ProfBracket pb;
     if (int rc2 = prof_open(h, 2, h->stream, &pb)) return rc2;
-    launch_gather_cad(h->stream, h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->d_stream, dpl2, h->batch, kb, h->dcfg, h->ld,
-                      h->pstride, h->dgbuf);
+    launch_gather_cad(h->stream, bank, next.dacc_in, h->d_stream, dpl2, kb, h->dcfg, h->dgbuf);
     if (int rc2 = prof_close(h, &pb)) return rc2;
   }
   HIP_TRY(h, hipGetLastError());
@@ -1749,12 +1698,13 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
   {
     ProfBracket pb;
     if (int rc2 = prof_open(h, 1, h->stream, &pb)) return rc2;
-    launch_solve_cad(h->stream, h->dP, h->dmu2[h->cur], h->dmu2[h->cur ^ 1], h->ddacc2[h->dcur ^ 1], h->dn, h->d_stream, dpl2,
-                     h->batch, h->dcad2[h->cpar], h->dflags, h->dcfg, h->ld, h->pstride, h->dgbuf, (kb + 7) / 8, nullptr, n_hi, 0,
-                     h->chain_run, nullptr, nullptr, 0u, nullptr, plg);
+    SolveCadArgs sx;                                   // (the block in the gather's parts; the mean is the handle's)
+    sx.gbuf = h->dgbuf, sx.gparts = (kb + 7) / 8;
+    sx.chain = h->chain_run;
+    launch_solve_cad(h->stream, bank, next, h->d_stream, dpl2, h->dcfg, n_hi, sx, plg);
     if (int rc2 = prof_close(h, &pb)) return rc2;
   }
-  log_cadence(h, dpl2, h->dcad2[h->cpar]);
+  log_cadence(h, dpl2, next.cad);
   // From here on the next cadence's solve has overwritten the pose mean and the pending-noise buffer: a failure
   // below cannot be undone.  Whatever happens the two streams are joined again, and a failure marks every trajectory
   // undefined (EKF_ERR_STATE from then on, until it is uploaded again).
@@ -1946,8 +1896,8 @@ extern "C" int ekf_step_detections(ekf_handle* h, const double* lin, const doubl
   if (((h->pending_k + ranks_for(mcap) + 3) & ~3) > KTOT)   // (what the step's kernels will write: see enqueue_pass)
     if (int rc = flush_pending(h)) return rc;
   h->acfg.active_bound = h->opt_active_bound;
-  launch_associate(h->stream, ds, h->dtagmap, h->dn, h->dneff, h->dmu2[h->cur], h->dP, h->dV, h->dW, h->d_assoc_step,
-                   h->d_assoc_out, h->dflags, h->acfg, h->ld, h->pstride, h->n_max, h->pending_k, h->batch);
+  launch_associate(h->stream, bank_view(h), ds, h->dtagmap, h->dneff, h->dmu2[h->cur], h->d_assoc_step, h->d_assoc_out, h->acfg,
+                   h->n_max, h->pending_k);
   HIP_TRY(h, hipGetLastError());
   h->sizes_dirty = true;
   // m_hi == 0 only when no trajectory has a detection (or the measurement model is off): then, with nothing
@@ -2074,8 +2024,8 @@ extern "C" int ekf_copy_trajectories(ekf_handle* dst, const int* dst_b, ekf_hand
   // (nontemporal stores unless EKFSLAM_HIP_COPY_NT=0: tools/copy_trajectories_time.py measures both, profiles/copy_trajectories.txt)
   bool nt = true;
   if (const char* e = std::getenv("EKFSLAM_HIP_COPY_NT")) nt = std::atoi(e) != 0;
-  launch_copy_traj(dst->stream, nt, src->dP, dst->dP, src->dmu2[src->cur], dst->dmu2[dst->cur], dst->dn, src->dflags, dst->dflags,
-                   dst->dcp_tab.p, cp.groups, cp.n_hi, src->ld, src->pstride, dst->ld, dst->pstride);
+  launch_copy_traj(dst->stream, nt, bank_view(src), bank_view(dst), src->dmu2[src->cur], dst->dmu2[dst->cur], dst->dcp_tab.p,
+                   cp.groups, cp.n_hi);
   HIP_TRY(dst, hipGetLastError());
   // the device tag table and the last window's tags: the source's, or "no window yet" where the source has never had one
   if (src->dtagmap)
@@ -2286,7 +2236,7 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
       // is planned (plan_cadence_step)
       h->chain_run = plan_chain_run(h, h->run_plan.ncad);
       if (h->chain_run) {
-        const int n_hi = *std::max_element(h->n.begin(), h->n.end());
+        const int n_hi = bank_n_hi(h, false);
         for (int i = 0; i < 2; ++i)
           if (!h->dprow3[i]) HIP_TRY(h, hipMalloc(&h->dprow3[i], sizeof(double) * 3 * (size_t)h->ld * h->batch));
         if (!h->dxg) {
@@ -2306,7 +2256,7 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
         }
         if (!h->dgmu) HIP_TRY(h, hipMalloc(&h->dgmu, sizeof(double) * 128 * h->batch));
         // the pose rows "before the first cadence": where the previous cadence's panel launch would have left them
-        launch_snap_pose(h->stream, h->dP, h->dn, h->ld, h->pstride, h->batch, n_hi, h->dprow3[h->cpar ^ 1]);
+        launch_snap_pose(h->stream, bank_view(h), n_hi, step_bufs(h).prow3_in);
         HIP_TRY(h, hipGetLastError());
       }
       bool presolved = false;                          // the next cadence's solve has been enqueued already (chained / look-ahead)

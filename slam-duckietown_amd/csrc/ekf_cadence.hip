@@ -33,6 +33,7 @@
 
 #include "ekf_devfn.h"
 #include "ekf_host_plan.h"
+#include "ekf_launch.h"
 
 namespace ekf {
 
@@ -1568,89 +1569,65 @@ __global__ __launch_bounds__(256) void k_snap_pose(const double* __restrict__ P,
 }
 
 // ---------------------------------------------------------------------------------------------
-// launchers (called from ekf_api.hip)
+// launchers (called from ekf_api.hip; declared and described in ekf_launch.h)
 // ---------------------------------------------------------------------------------------------
-
-long cadence_gbuf_doubles() { return (long)CAD_GP * CAD_ROWS * CAD_CS; }   // per trajectory: CAD_GP parts
-
-// (look-ahead) the next cadence's block while `kb` ranks are pending -> gbuf
-void launch_gather_cad(hipStream_t st, const double* P, const double* V, const double* W, const double* dacc,
-                       const StepIn* in, const CadPlan* plan, int batch, int kb, const DeviceConfig& cfg, int ld, long pstride,
-                       double* gbuf) {
-  hipLaunchKernelGGL(k_gather_cad, dim3((kb + 7) / 8, batch), dim3(64 * CAD_GW), 0, st, P, V, W, dacc, in, plan, batch, kb, cfg,
-                     ld, pstride, gbuf);
+long cadence_gbuf_doubles() { return (long)CAD_GP * CAD_ROWS * CAD_CS; }
+void launch_gather_cad(hipStream_t st, const BankView& k, const double* dacc, const StepIn* in, const CadPlan* plan, int kb,
+                       const DeviceConfig& cfg, double* gbuf) {
+  hipLaunchKernelGGL(k_gather_cad, dim3((kb + 7) / 8, k.batch), dim3(64 * CAD_GW), 0, st, k.P, k.V, k.W, dacc, in, plan, k.batch, kb,
+                     cfg, k.ld, k.pstride, gbuf);
 }
-
-// `colbuf` (batch x CAD_CU x ld doubles, or nullptr): the launch also gathers the mirrored column entries of the panel launch
-// behind it, on `col_wgs` extra workgroups -- only where P_base is current (not beside a pass: look-ahead)
-// `chain`: the instantiation that also records the pose block behind the cadence (CadOut::posefin) for k_chain_cad; `gmu`
-// (with gbuf, one part): block and mean come from k_chain_cad
-void launch_solve_cad(hipStream_t st, const double* P, const double* mu_in, double* mu_out, double* dacc_out,
-                      const int* nact, const StepIn* in, const CadPlan* plan, int batch, CadOut* out, unsigned* flags,
-                      const DeviceConfig& cfg, int ld, long pstride, const double* gbuf, int gparts, double* colbuf, int n_hi,
-                      int col_wgs, bool chain, const double* gmu, unsigned* sync, unsigned start_sigma, const CadPre* pre,
-                      const PoseLog* plg) {
-  const dim3 grid(batch + (colbuf ? col_wgs : 0)), block(64 * CAD_NW);
-  with_flag(chain, [&](auto C) {
+void launch_solve_cad(hipStream_t st, const BankView& k, const StepBufs& s, const StepIn* in, const CadPlan* plan,
+                      const DeviceConfig& cfg, int n_hi, const SolveCadArgs& a, const PoseLog* plg) {
+  const dim3 grid(k.batch + (a.colbuf ? a.col_wgs : 0)), block(64 * CAD_NW);
+  with_flag(a.chain, [&](auto C) {
     with_flag(cfg.gate_rej != nullptr, [&](auto G) {
       with_flag(cfg.noise != nullptr, [&](auto Z) {
         if (plg)                                       // the pose log is on: the instantiations that write its rows
-          hipLaunchKernelGGL((k_solve_cad_plog<C.value, G.value, Z.value>), grid, block, 0, st, P, mu_in, mu_out, dacc_out, nact,
-                             in, plan, batch, out, flags, cfg, ld, pstride, gbuf, gparts, colbuf, col_wgs, n_hi,
-                             C.value ? gmu : nullptr, C.value ? sync : nullptr, C.value ? start_sigma : 0u,
-                             C.value ? pre : nullptr, *plg);
+          hipLaunchKernelGGL((k_solve_cad_plog<C.value, G.value, Z.value>), grid, block, 0, st, k.P, s.mu_in, s.mu_out, s.dacc_out,
+                             k.nact, in, plan, k.batch, s.cad, k.flags, cfg, k.ld, k.pstride, a.gbuf, a.gparts, a.colbuf, a.col_wgs,
+                             n_hi, C.value ? a.gmu : nullptr, C.value ? a.sync : nullptr, C.value ? a.start_sigma : 0u,
+                             C.value ? a.pre : nullptr, *plg);
         else
-        hipLaunchKernelGGL((k_solve_cad<C.value, G.value, Z.value>), grid, block, 0, st, P, mu_in, mu_out, dacc_out, nact, in, plan,
-                           batch, out, flags, cfg, ld, pstride, gbuf, gparts, colbuf, col_wgs, n_hi, C.value ? gmu : nullptr,
-                           C.value ? sync : nullptr, C.value ? start_sigma : 0u, C.value ? pre : nullptr);
+          hipLaunchKernelGGL((k_solve_cad<C.value, G.value, Z.value>), grid, block, 0, st, k.P, s.mu_in, s.mu_out, s.dacc_out,
+                             k.nact, in, plan, k.batch, s.cad, k.flags, cfg, k.ld, k.pstride, a.gbuf, a.gparts, a.colbuf, a.col_wgs,
+                             n_hi, C.value ? a.gmu : nullptr, C.value ? a.sync : nullptr, C.value ? a.start_sigma : 0u,
+                             C.value ? a.pre : nullptr);
       });
     });
   });
 }
-
-// (chained runs) the next cadence's block and mean from the records `prev` of the cadence whose solve has just run; `gw` gather
-// workgroups per trajectory (ekf_host_plan.h: chain_gather_workgroups)
 int chain_sync_words() { return SYNC_WORDS; }
-void launch_chain_cad(hipStream_t st, const double* P, const double* prow3, const double* mu_land, const double* mu_pose,
-                      const CadOut* prev, const StepIn* in, const CadPlan* plan, int batch, const DeviceConfig& cfg, int ld,
-                      long pstride, double* gbuf, double* gmu, double* xg, double* bg, unsigned* sync, unsigned gather_target,
-                      unsigned* flags, int gw, unsigned sigma, const CadPre* pre_in, CadPre* pre_out, const CadPlan* plan2,
-                      bool wait_pass) {
+void launch_chain_cad(hipStream_t st, const BankView& k, const StepBufs& prev, const StepIn* in, const CadPlan* plan,
+                      const DeviceConfig& cfg, const ChainArgs& a) {
   // (workgroups: the chain workgroup of every trajectory, its gather workgroups, and -- where a cadence follows the next one --
   //  the positions workgroup that forms that cadence's inputs ahead)
-  hipLaunchKernelGGL(k_chain_cad, dim3(batch * (1 + gw + (pre_out ? 1 : 0))), dim3(64 * CAD_NW), 0, st, P, prow3, mu_land, mu_pose,
-                     prev, in, plan, batch, cfg, ld, pstride, gbuf, gmu, xg, bg, sync, gather_target, flags, gw, sigma, pre_in, pre_out,
-                     plan2, wait_pass ? 1 : 0);
+  hipLaunchKernelGGL(k_chain_cad, dim3(k.batch * (1 + a.gw + (a.pre_out ? 1 : 0))), dim3(64 * CAD_NW), 0, st, k.P, prev.prow3_in,
+                     prev.mu_in, prev.mu_out, prev.cad, in, plan, k.batch, cfg, k.ld, k.pstride, a.gbuf, a.gmu, a.xg, a.bg, a.sync,
+                     a.gather_target, k.flags, a.gw, a.sigma, a.pre_in, a.pre_out, a.plan2, a.wait_pass ? 1 : 0);
 }
-
 void launch_mark(hipStream_t st, unsigned* sync, unsigned sigma) { hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, st, sync, sigma); }
-
 void launch_gate(hipStream_t st, unsigned* sync, unsigned sigma, unsigned* flags, int batch) {
   hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, st, sync, sigma, flags, batch);
 }
-
-void launch_snap_pose(hipStream_t st, const double* P, const int* nact, int ld, long pstride, int batch, int n_hi, double* prow3) {
-  hipLaunchKernelGGL(k_snap_pose, dim3((n_hi + 255) / 256, batch), dim3(256), 0, st, P, nact, ld, pstride, prow3);
+void launch_snap_pose(hipStream_t st, const BankView& k, int n_hi, double* prow3) {
+  hipLaunchKernelGGL(k_snap_pose, dim3((n_hi + 255) / 256, k.batch), dim3(256), 0, st, k.P, k.nact, k.ld, k.pstride, prow3);
 }
-
-// `nrp`: the ranks the bank's busiest trajectory appends, padded to a whole k-tile (every trajectory writes that many);
-// `form`: ekf_host_plan.h's PanelForm (plan_cadence_step); `skipw` (w_from_v): the replay forms write V only
-void launch_panels_cad(hipStream_t st, double* P, double* V, double* W, const double* mu_in, double* mu_out,
-                       const int* nact, const CadOut* co, SolveOut* so, unsigned* queue, int ld, long pstride, int batch,
-                       int n_hi, int nrp, const double* colbuf, double* prow3, unsigned* sync, unsigned tail_target,
-                       unsigned* flags, int form, unsigned start_sigma, bool skipw) {
-  if (form == PANEL_TF)
-    hipLaunchKernelGGL(k_panels_cad_tf, dim3((n_hi + 63) / 64, batch), dim3(64 * CAD_NW), 0, st, P, V, W, mu_in, mu_out, nact, co, so,
-                       queue, ld, pstride, nrp, prow3, sync, tail_target, flags, start_sigma);
-  else if (form == PANEL_KS)
-    hipLaunchKernelGGL(k_panels_cad_ks, dim3((n_hi + 63) / 64, batch), dim3(256), 0, st, P, V, W, mu_in, mu_out,
-                       nact, co, so, queue, ld, pstride, nrp, colbuf, prow3, sync, tail_target, flags, start_sigma);
-  else if (form == PANEL_ONE)
-    hipLaunchKernelGGL((k_panels_cad<1>), dim3((n_hi + 63) / 64, batch), dim3(64), 0, st, P, V, W, mu_in, mu_out,
-                       nact, co, so, queue, ld, pstride, nrp, colbuf, prow3, sync, tail_target, flags, start_sigma, skipw ? 1 : 0);
+void launch_panels_cad(hipStream_t st, const BankView& k, const StepBufs& s, int n_hi, const PanelCadArgs& a) {
+  const dim3 strips((n_hi + 63) / 64, k.batch);
+  if (a.form == PANEL_TF)
+    hipLaunchKernelGGL(k_panels_cad_tf, strips, dim3(64 * CAD_NW), 0, st, k.P, k.V, k.W, s.mu_in, s.mu_out, k.nact, s.cad, k.so,
+                       k.queue, k.ld, k.pstride, a.nrp, s.prow3_out, a.sync, a.tail_target, k.flags, a.start_sigma);
+  else if (a.form == PANEL_KS)
+    hipLaunchKernelGGL(k_panels_cad_ks, strips, dim3(256), 0, st, k.P, k.V, k.W, s.mu_in, s.mu_out, k.nact, s.cad, k.so, k.queue,
+                       k.ld, k.pstride, a.nrp, a.colbuf, s.prow3_out, a.sync, a.tail_target, k.flags, a.start_sigma);
+  else if (a.form == PANEL_ONE)
+    hipLaunchKernelGGL((k_panels_cad<1>), strips, dim3(64), 0, st, k.P, k.V, k.W, s.mu_in, s.mu_out, k.nact, s.cad, k.so, k.queue,
+                       k.ld, k.pstride, a.nrp, a.colbuf, s.prow3_out, a.sync, a.tail_target, k.flags, a.start_sigma, a.skipw ? 1 : 0);
   else
-    hipLaunchKernelGGL((k_panels_cad<4>), dim3((n_hi + 255) / 256, batch), dim3(256), 0, st, P, V, W, mu_in,
-                       mu_out, nact, co, so, queue, ld, pstride, nrp, colbuf, prow3, sync, tail_target, flags, start_sigma, skipw ? 1 : 0);
+    hipLaunchKernelGGL((k_panels_cad<4>), dim3((n_hi + 255) / 256, k.batch), dim3(256), 0, st, k.P, k.V, k.W, s.mu_in, s.mu_out,
+                       k.nact, s.cad, k.so, k.queue, k.ld, k.pstride, a.nrp, a.colbuf, s.prow3_out, a.sync, a.tail_target, k.flags,
+                       a.start_sigma, a.skipw ? 1 : 0);
 }
 
 }  // namespace ekf

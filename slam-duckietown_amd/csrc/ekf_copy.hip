@@ -18,6 +18,7 @@
 // NT: nontemporal stores (the destinations are written once and read much later).  Plain C++, vector stores only.
 #include "ekf_device.h"
 #include "ekf_host_plan.h"
+#include "ekf_launch.h"
 
 namespace ekf {
 
@@ -81,15 +82,16 @@ __global__ __launch_bounds__(CP_THREADS) void k_copy_traj(const double* __restri
   }
 }
 
-// groups x (tiles of the largest source + 1) workgroups; tab: plan_copy's table on the device
-void launch_copy_traj(hipStream_t st, bool nt, const double* Ps, double* Pd, const double* mus, double* mud, int* nd,
-                      const unsigned* fs, unsigned* fd, const int* tab, int groups, int n_hi, int lds, long pss, int ldd, long psd) {
+void launch_copy_traj(hipStream_t st, bool nt, const BankView& src, const BankView& dst, const double* mus, double* mud,
+                      const int* tab, int groups, int n_hi) {
   const int tiles = copy_tiles(n_hi);
   const dim3 grid(groups, tiles + 1);            // (tiles + 1 <= 58 312 at EKF_N_MAX_LIMIT: inside the 65 535 of grid.y)
   if (nt)
-    hipLaunchKernelGGL(k_copy_traj<true>, grid, dim3(CP_THREADS), 0, st, Ps, Pd, mus, mud, nd, fs, fd, tab, groups, tiles, lds, pss, ldd, psd);
+    hipLaunchKernelGGL(k_copy_traj<true>, grid, dim3(CP_THREADS), 0, st, src.P, dst.P, mus, mud, dst.nact, src.flags, dst.flags, tab,
+                       groups, tiles, src.ld, src.pstride, dst.ld, dst.pstride);
   else
-    hipLaunchKernelGGL(k_copy_traj<false>, grid, dim3(CP_THREADS), 0, st, Ps, Pd, mus, mud, nd, fs, fd, tab, groups, tiles, lds, pss, ldd, psd);
+    hipLaunchKernelGGL(k_copy_traj<false>, grid, dim3(CP_THREADS), 0, st, src.P, dst.P, mus, mud, dst.nact, src.flags, dst.flags, tab,
+                       groups, tiles, src.ld, src.pstride, dst.ld, dst.pstride);
 }
 
 }  // namespace ekf

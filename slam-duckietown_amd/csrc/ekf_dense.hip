@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "ekf_device.h"
+#include "ekf_launch.h"
 
 namespace ekf {
 

@@ -254,6 +254,20 @@ struct PendingView {
   const SolveOut* so;
   int ld; long pstride; int b0, count, kb;
 };
+// What the launches that move the filter take of a handle, the same for every launch of a call (ekf_api.hip: bank_view; the
+// launchers of ekf_launch.h unpack it into their kernel's arguments): P_base, the rank slots, sizes, last solve's records,
+// sticky flags, the pass's work-queue words and the layout of the whole bank.
+struct BankView {
+  double *P, *V, *W; int* nact; SolveOut* so; unsigned *flags, *queue;
+  int ld; long pstride; int batch;
+};
+// The halves of the double-buffered arrays one launch reads and writes (ekf_api.hip: step_bufs, which says which copy holds
+// what): mean and pending pose noise in and out; for a cadence's launches also its records and the two copies of the pose rows,
+// as they stood before the cadence (prow3_in) and as its panel launch leaves them (prow3_out).
+struct StepBufs {
+  const double* mu_in; double* mu_out; const double* dacc_in; double* dacc_out; CadOut* cad;
+  double *prow3_in, *prow3_out;         // (prow3_in is written once per chained run: launch_snap_pose)
+};
 // y^T S^-1 y with S^-1 = [[a, b], [c, d]]
 __host__ __device__ __forceinline__ double innov_nis(double y0, double y1, double a, double b, double c, double d) {
   return y0 * (a * y0 + b * y1) + y1 * (c * y0 + d * y1);

@@ -26,6 +26,7 @@
 #include "ekf_device.h"
 
 #include "ekf_devfn.h"
+#include "ekf_launch.h"
 
 namespace ekf {
 
@@ -208,12 +209,11 @@ __global__ __launch_bounds__(DR_THREADS) void k_direct(double* __restrict__ P, d
   }
 }
 
-void launch_direct(hipStream_t st, int rows_cap, double* P, double* V, double* W, double* dacc, double* mu, const int* nact,
-                   SolveOut* so, unsigned* flags, unsigned* queue, const int* plan, const double* meas, double* out, int ld,
-                   long pstride, int batch, int kpad) {
+void launch_direct(hipStream_t st, int rows_cap, const BankView& k, double* dacc, double* mu, const int* plan, const double* meas,
+                   double* out, int kpad) {
   auto go = [&](auto dp) {
-    hipLaunchKernelGGL((k_direct<decltype(dp)::value>), dim3(batch), dim3(DR_THREADS), 0, st, P, V, W, dacc, mu, nact, so, flags,
-                       queue, plan, meas, out, ld, pstride, kpad);
+    hipLaunchKernelGGL((k_direct<decltype(dp)::value>), dim3(k.batch), dim3(DR_THREADS), 0, st, k.P, k.V, k.W, dacc, mu, k.nact, k.so,
+                       k.flags, k.queue, plan, meas, out, k.ld, k.pstride, kpad);
   };
   switch (rows_cap) {
     case 4: go(std::integral_constant<int, 4>{}); break;

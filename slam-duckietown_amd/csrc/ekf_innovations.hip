@@ -8,6 +8,7 @@
 // filter's buffers only and wait for nothing.  (The small-state path keeps no records in memory: k_small_stream's LOG
 // instantiations write the log themselves, ekf_small.hip.)
 #include "ekf_device.h"
+#include "ekf_launch.h"
 
 namespace ekf {
 

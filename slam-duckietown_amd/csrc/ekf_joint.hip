@@ -23,6 +23,7 @@
 #include "ekf_device.h"
 
 #include "ekf_devfn.h"
+#include "ekf_launch.h"
 
 namespace ekf {
 

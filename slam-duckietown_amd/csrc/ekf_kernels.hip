@@ -24,6 +24,7 @@
 
 #include "ekf_devfn.h"
 #include "ekf_host_plan.h"
+#include "ekf_launch.h"
 
 namespace ekf {
 
@@ -2389,11 +2390,10 @@ __global__ __launch_bounds__(64) void k_associate(const DetIn* __restrict__ det,
   }
 }
 
-void launch_associate(hipStream_t st, const DetIn* det, int* tagmap, int* nact, int* neff_dev, double* mu, double* P,
-                      double* V, double* W, StepIn* step_out, AssocOut* assoc_out, unsigned* flags,
-                      const AssocConfig& cfg, int ld, long pstride, int n_max, int pending_k, int batch) {
-  hipLaunchKernelGGL(k_associate, dim3(batch), dim3(64), 0, st, det, tagmap, nact, neff_dev, mu, P, V, W, step_out,
-                     assoc_out, flags, cfg, ld, pstride, n_max, pending_k, batch);
+void launch_associate(hipStream_t st, const BankView& k, const DetIn* det, int* tagmap, int* neff_dev, double* mu, StepIn* step_out,
+                      AssocOut* assoc_out, const AssocConfig& cfg, int n_max, int pending_k) {
+  hipLaunchKernelGGL(k_associate, dim3(k.batch), dim3(64), 0, st, det, tagmap, k.nact, neff_dev, mu, k.P, k.V, k.W, step_out,
+                     assoc_out, k.flags, cfg, k.ld, k.pstride, n_max, pending_k, k.batch);
 }
 
 // Augmentation (src/replay_no_ros.py:341-360): zero rows/cols [n_old, n_new), set the new diagonal.
@@ -2420,147 +2420,91 @@ __global__ __launch_bounds__(256) void k_fill_diag(double* __restrict__ Pb, int 
 }
 
 // ---------------------------------------------------------------------------------------------
-// launchers (called from ekf_api.hip)
+// launchers (called from ekf_api.hip; declared and described in ekf_launch.h)
 // ---------------------------------------------------------------------------------------------
-void launch_solve(hipStream_t st, const double* P, const double* V, const double* W, const double* dacc_in,
-                  double* dacc_out, const double* mu_in, double* mu_out, const int* nact, const StepIn* in,
-                  SolveOut* out, unsigned* flags, double* fac, const int* neff_floor, unsigned* queue,
-                  const DeviceConfig& cfg, int ld, long pstride, int batch, int kbase) {
+void launch_solve(hipStream_t st, const BankView& k, const StepBufs& s, const StepArgs& a, const DeviceConfig& cfg) {
   with_flag(cfg.gate_rej != nullptr, [&](auto G) {     // (the NIS gate is on)
     with_flag(cfg.noise != nullptr, [&](auto Z) {      // (the noise table is set)
-      hipLaunchKernelGGL((k_solve<G.value, Z.value>), dim3(batch), dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out,
-                         nact, in, out, flags, fac, neff_floor, queue, cfg, ld, pstride, kbase);
+      hipLaunchKernelGGL((k_solve<G.value, Z.value>), dim3(k.batch), dim3(256), 0, st, k.P, k.V, k.W, s.dacc_in, s.dacc_out,
+                         s.mu_in, s.mu_out, k.nact, a.in, k.so, k.flags, a.fac, a.neff_floor, k.queue, cfg, k.ld, k.pstride, a.kbase);
     });
   });
 }
-
-// `latency` (ekf_host_plan.h: plan_step): four waves split the pending ranks of 64 indices; else the throughput form, a
-// workgroup is four independent waves of 64 state indices sharing one staging
-template <int MCAP>
-static void launch_panels_t(hipStream_t st, bool latency, double* P, double* V, double* W, const double* mu_in,
-                            double* mu_out, const int* nact, const SolveOut* so, const double* fac, int ld,
-                            long pstride, int batch, int n_hi) {
-  if (latency)
-    hipLaunchKernelGGL((k_panels<MCAP, 4, true>), dim3((n_hi + 63) / 64, batch), dim3(256), 0, st, P, V, W, mu_in,
-                       mu_out, nact, so, fac, ld, pstride);
-  else
-    hipLaunchKernelGGL((k_panels<MCAP, 4, false>), dim3((n_hi + 255) / 256, batch), dim3(256), 0, st, P, V, W,
-                       mu_in, mu_out, nact, so, fac, ld, pstride);
+void launch_panels(hipStream_t st, int mcap, bool latency, const BankView& k, const StepBufs& s, const double* fac, int n_hi) {
+  with_mcap(mcap, [&](auto M) {
+    with_flag(latency, [&](auto L) {
+      hipLaunchKernelGGL((k_panels<M.value, 4, L.value>), dim3((n_hi + (L.value ? 63 : 255)) / (L.value ? 64 : 256), k.batch),
+                         dim3(256), 0, st, k.P, k.V, k.W, s.mu_in, s.mu_out, k.nact, k.so, fac, k.ld, k.pstride);
+    });
+  });
 }
-void launch_panels(hipStream_t st, int mcap, bool latency, double* P, double* V, double* W, const double* mu_in,
-                   double* mu_out, const int* nact, const SolveOut* so, const double* fac, int ld, long pstride,
-                   int batch, int n_hi) {
-  with_mcap(mcap, [&](auto M) { launch_panels_t<M.value>(st, latency, P, V, W, mu_in, mu_out, nact, so, fac, ld, pstride, batch, n_hi); });
-}
-
-// The throughput shape of the single-launch step: k_panels<.., SPLIT> (see there).
-void launch_step_split_tp(hipStream_t st, int mcap, double* P, double* V, double* W, const double* dacc_in,
-                          double* dacc_out, const double* mu_in, double* mu_out, const int* nact, const StepIn* in,
-                          SolveOut* out, unsigned* flags, double* fac, const int* neff_floor, unsigned* queue,
-                          SolveOut* mbox, unsigned* ready, unsigned seq, int publish, const DeviceConfig& cfg, int ld,
-                          long pstride, int batch, int n_hi, int kbase) {
-  const dim3 grid(1 + (n_hi + 255) / 256, batch);
-  SplitArgs sa{dacc_in, dacc_out, in, out, flags, fac, neff_floor, queue, mbox, ready, seq, publish, kbase, cfg};
+void launch_step_split_tp(hipStream_t st, int mcap, const BankView& k, const StepBufs& s, const StepArgs& a,
+                          const DeviceConfig& cfg, int n_hi) {
+  const dim3 grid(1 + (n_hi + 255) / 256, k.batch);
+  SplitArgs sa{s.dacc_in, s.dacc_out, a.in, k.so, k.flags, a.fac, a.neff_floor, k.queue, a.mbox, a.ready, a.seq, a.publish, a.kbase, cfg};
   with_mcap(mcap, [&](auto M) {
     if constexpr (M.value <= 8)                        // (16 landmarks per pass: never planned, see plan_step)
       with_flag(cfg.gate_rej != nullptr, [&](auto G) {
         with_flag(cfg.noise != nullptr, [&](auto Z) {
-          hipLaunchKernelGGL((k_panels_split<M.value, G.value, Z.value>), grid, dim3(256), 0, st, P, V, W, mu_in, mu_out, nact, ld,
-                             pstride, sa);
+          hipLaunchKernelGGL((k_panels_split<M.value, G.value, Z.value>), grid, dim3(256), 0, st, k.P, k.V, k.W, s.mu_in, s.mu_out,
+                             k.nact, k.ld, k.pstride, sa);
         });
       });
   });
 }
-
-void launch_step_split(hipStream_t st, int mcap, double* P, double* V, double* W, const double* dacc_in, double* dacc_out,
-                       const double* mu_in, double* mu_out, const int* nact, const StepIn* in, SolveOut* out,
-                       unsigned* flags, double* fac, const int* neff_floor, unsigned* queue, unsigned* ready, unsigned seq,
-                       int publish, const DeviceConfig& cfg, int ld, long pstride, int batch, int n_hi, int kbase) {
-  const dim3 grid(1 + (n_hi + 63) / 64, batch);
+void launch_step_split(hipStream_t st, int mcap, const BankView& k, const StepBufs& s, const StepArgs& a, const DeviceConfig& cfg, int n_hi) {
+  const dim3 grid(1 + (n_hi + 63) / 64, k.batch);
   with_mcap(mcap, [&](auto M) {
     with_flag(cfg.gate_rej != nullptr, [&](auto G) {
       with_flag(cfg.noise != nullptr, [&](auto Z) {
-        hipLaunchKernelGGL((k_step_split<M.value, G.value, Z.value>), grid, dim3(256), 0, st, P, V, W, dacc_in, dacc_out, mu_in, mu_out,
-                           nact, in, out, flags, fac, neff_floor, queue, ready, seq, publish, cfg, ld, pstride, kbase);
+        hipLaunchKernelGGL((k_step_split<M.value, G.value, Z.value>), grid, dim3(256), 0, st, k.P, k.V, k.W, s.dacc_in, s.dacc_out,
+                           s.mu_in, s.mu_out, k.nact, a.in, k.so, k.flags, a.fac, a.neff_floor, k.queue, a.ready, a.seq, a.publish,
+                           cfg, k.ld, k.pstride, a.kbase);
       });
     });
   });
 }
-
-template <int NKTM, int NKL, bool NT>
-static void launch_flush_t(hipStream_t st, double* P, const double* V, const double* W, const double* dacc,
-                           const int* nact, const SolveOut* so, int ld, long pstride, int batch, int n_hi,
-                           int nkt, int rows_per_block) {
-  const int gx = (n_hi + 255) / 256, gy = (n_hi + rows_per_block - 1) / rows_per_block;
+// (launchers of the pass) the k-tile count as a template argument: f(std::integral_constant<int, 4 | 8 | 12 | 16 | 20>{})
+template <typename F>
+static void with_nkt(int nkt, F&& f) {
+  if (nkt <= 4) f(std::integral_constant<int, 4>{});
+  else if (nkt <= 8) f(std::integral_constant<int, 8>{});
+  else if (nkt <= 12) f(std::integral_constant<int, 12>{});
+  else if (nkt <= 16) f(std::integral_constant<int, 16>{});
+  else f(std::integral_constant<int, 20>{});
+}
+void launch_flush(hipStream_t st, const PassPlan& p, const BankView& k, const double* dacc) {
+  const int n_hi = p.e_hi, gx = (n_hi + 255) / 256, gy = (n_hi + p.rows_per_block - 1) / p.rows_per_block;
   int total = 0;                                       // workgroups that reach the upper triangle
-  for (int by = 0; by < gy; ++by) total += std::max(0, gx - (by * rows_per_block) / 256);
-  hipLaunchKernelGGL((k_flush<NKTM, NKL, NT>), dim3(total, 1, batch), dim3(256), 0, st, P, V, W, dacc, nact, so, ld,
-                     pstride, nkt, rows_per_block, gx);
+  for (int by = 0; by < gy; ++by) total += std::max(0, gx - (by * p.rows_per_block) / 256);
+  with_nkt(p.nkt, [&](auto N) {
+    with_flag(p.streaming, [&](auto NT) {
+      // (beyond 16 k-tiles: 15 of the V strip in registers, the other 5 in LDS)
+      constexpr int NKTM = N.value == 20 ? 15 : N.value, NKL = N.value == 20 ? 5 : 0;
+      hipLaunchKernelGGL((k_flush<NKTM, NKL, NT.value>), dim3(total, 1, k.batch), dim3(256), 0, st, k.P, k.V, k.W, dacc, k.nact,
+                         k.so, k.ld, k.pstride, p.nkt, p.rows_per_block, gx);
+    });
+  });
 }
-
-// streaming = the batch's covariances do not fit the Infinity Cache: nontemporal accesses
-void launch_flush(hipStream_t st, const PassPlan& p, double* P, const double* V, const double* W,
-                  const double* dacc, const int* nact, const SolveOut* so, int ld, long pstride, int batch) {
-  const bool streaming = p.streaming;
-  const int n_hi = p.e_hi, nkt = p.nkt, rows_per_block = p.rows_per_block;
-#define EKF_FLUSH(N, L)                                                                                   \
-  do {                                                                                                    \
-    if (streaming) launch_flush_t<N, L, true>(st, P, V, W, dacc, nact, so, ld, pstride, batch, n_hi, nkt, rows_per_block); \
-    else launch_flush_t<N, L, false>(st, P, V, W, dacc, nact, so, ld, pstride, batch, n_hi, nkt, rows_per_block);          \
-  } while (0)
-  if (nkt <= 4) EKF_FLUSH(4, 0);
-  else if (nkt <= 8) EKF_FLUSH(8, 0);
-  else if (nkt <= 12) EKF_FLUSH(12, 0);
-  else if (nkt <= 16) EKF_FLUSH(16, 0);
-  else EKF_FLUSH(15, 5);
-#undef EKF_FLUSH
-}
-
-// the row-slab form of the pass (k_flush_rs): persistent workgroups, `queue` = 8 x RS_QSTRIDE zeroed words; the work queues'
-// hand-out as planned (plan_pass), or one equal static share per workgroup (mode 4) where `shares` is given
-template <int NKT, bool NT, bool PAN>
-static void launch_flush_rs_t(hipStream_t st, const PassPlan& p, double* P, const double* V, const double* W, const double* dacc,
-                              const int* nact, const SolveOut* so, int ld, long pstride, int batch, unsigned* queue,
-                              const int* shares, const CadOut* wv) {
+void launch_flush_rs(hipStream_t st, const PassPlan& p, const BankView& k, const double* dacc, const int* shares, const CadOut* wv) {
   const int nrb = (p.e_hi + RS_ROWS - 1) / RS_ROWS;
   const unsigned grid = shares ? p.rs_workgroups : p.rs_grid;
   const int nch = shares ? 1 : p.rs_nch, cs = shares ? 0 : p.rs_cs, mode = shares ? 4 : p.rs_mode;
-  if (wv)
-    hipLaunchKernelGGL((k_flush_rs<NKT, NT, PAN, true>), dim3(grid), dim3(512), 0, st, P, V, W, dacc, nact, so, ld, pstride, p.nkt,
-                       batch, nrb, nch, cs, mode, queue, shares, wv);
-  else
-    hipLaunchKernelGGL((k_flush_rs<NKT, NT, PAN, false>), dim3(grid), dim3(512), 0, st, P, V, W, dacc, nact, so, ld, pstride, p.nkt,
-                       batch, nrb, nch, cs, mode, queue, shares, wv);
+  with_nkt(p.nkt, [&](auto N) {
+    with_flag(k.ld > PPW, [&](auto PAN) {
+      with_flag(p.streaming, [&](auto NT) {
+        with_flag(wv != nullptr, [&](auto WV) {
+          hipLaunchKernelGGL((k_flush_rs<N.value, NT.value, PAN.value, WV.value>), dim3(grid), dim3(512), 0, st, k.P, k.V, k.W,
+                             dacc, k.nact, k.so, k.ld, k.pstride, p.nkt, k.batch, nrb, nch, cs, mode, k.queue, shares, wv);
+        });
+      });
+    });
+  });
 }
-
-void launch_flush_rs(hipStream_t st, const PassPlan& p, double* P, const double* V, const double* W, const double* dacc,
-                     const int* nact, const SolveOut* so, int ld, long pstride, int batch, unsigned* queue, const int* shares,
-                     const CadOut* wv) {
-  const int nkt = p.nkt;
-#define EKF_FLUSH_RS(N)                                                                                   \
-  do {                                                                                                    \
-    if (ld > PPW) {                                                                                       \
-      if (p.streaming) launch_flush_rs_t<N, true, true>(st, p, P, V, W, dacc, nact, so, ld, pstride, batch, queue, shares, wv); \
-      else launch_flush_rs_t<N, false, true>(st, p, P, V, W, dacc, nact, so, ld, pstride, batch, queue, shares, wv);          \
-    } else {                                                                                              \
-      if (p.streaming) launch_flush_rs_t<N, true, false>(st, p, P, V, W, dacc, nact, so, ld, pstride, batch, queue, shares, wv); \
-      else launch_flush_rs_t<N, false, false>(st, p, P, V, W, dacc, nact, so, ld, pstride, batch, queue, shares, wv);          \
-    }                                                                                                     \
-  } while (0)
-  if (nkt <= 4) EKF_FLUSH_RS(4);
-  else if (nkt <= 8) EKF_FLUSH_RS(8);
-  else if (nkt <= 12) EKF_FLUSH_RS(12);
-  else if (nkt <= 16) EKF_FLUSH_RS(16);
-  else EKF_FLUSH_RS(20);
-#undef EKF_FLUSH_RS
-}
-
 int flush_rs_queue_words() { return 8 * RS_QSTRIDE; }
-
-void launch_predict_rc(hipStream_t st, double* P, const double* mu_in, double* mu_out, const int* nact,
-                       const SolveOut* so, int ld, long pstride, int batch, int n_hi) {
-  hipLaunchKernelGGL(k_predict_rc, dim3((n_hi + 255) / 256, batch), dim3(256), 0, st, P, mu_in, mu_out,
-                     nact, so, ld, pstride);
+void launch_predict_rc(hipStream_t st, const BankView& k, const StepBufs& s, int n_hi) {
+  hipLaunchKernelGGL(k_predict_rc, dim3((n_hi + 255) / 256, k.batch), dim3(256), 0, st, k.P, s.mu_in, s.mu_out, k.nact, k.so, k.ld,
+                     k.pstride);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,0 +1,108 @@
+// The launch boundary: every launch_* function ekf_api.hip calls, declared once and included by the .hip file that defines it.
+// The launchers take named views of the handle (ekf_device.h: BankView, StepBufs, PendingView) plus what only they need, and
+// unpack them on the host into the kernel's arguments; no kernel takes a view.
+#pragma once
+#include "ekf_device.h"
+
+namespace ekf {
+struct PassPlan; struct RemovePlan;   // ekf_host_plan.h
+// ---- per-step kernels (ekf_kernels.hip) ----
+// What a step's solve takes beside the views; the single-launch step also the handle's dmbox (throughput shape), dready, step_seq
+struct StepArgs {
+  const StepIn* in; double* fac; const int* neff_floor; int kbase;
+  SolveOut* mbox = nullptr; unsigned* ready = nullptr; unsigned seq = 0; int publish = 0;
+};
+void launch_solve(hipStream_t st, const BankView& k, const StepBufs& s, const StepArgs& a, const DeviceConfig& cfg);
+void launch_step_split(hipStream_t st, int mcap, const BankView& k, const StepBufs& s, const StepArgs& a, const DeviceConfig& cfg, int n_hi);
+void launch_step_split_tp(hipStream_t st, int mcap, const BankView& k, const StepBufs& s, const StepArgs& a, const DeviceConfig& cfg,
+                          int n_hi);   // the throughput shape of the single-launch step: k_panels<.., SPLIT> (see there)
+// `latency` (ekf_host_plan.h: plan_step): four waves split the pending ranks of 64 indices; else the throughput form, a
+// workgroup is four independent waves of 64 state indices sharing one staging
+void launch_panels(hipStream_t st, int mcap, bool latency, const BankView& k, const StepBufs& s, const double* fac, int n_hi);
+void launch_predict_rc(hipStream_t st, const BankView& k, const StepBufs& s, int n_hi);
+// p.streaming = the batch's covariances do not fit the Infinity Cache: nontemporal accesses
+void launch_flush(hipStream_t st, const PassPlan& p, const BankView& k, const double* dacc);
+// the row-slab form of the pass (k_flush_rs): persistent workgroups, k.queue = 8 x RS_QSTRIDE zeroed words; the work queues'
+// hand-out as planned (plan_pass), or one equal static share per workgroup (mode 4) where `shares` is given; wv: w_from_v
+void launch_flush_rs(hipStream_t st, const PassPlan& p, const BankView& k, const double* dacc, const int* shares, const CadOut* wv);
+int flush_rs_queue_words();
+void launch_associate(hipStream_t st, const BankView& k, const DetIn* det, int* tagmap, int* neff_dev, double* mu, StepIn* step_out,
+                      AssocOut* assoc_out, const AssocConfig& cfg, int n_max, int pending_k);
+// one trajectory: Pb, mub, flag_b are its covariance, mean and flags word
+void launch_add_landmarks(hipStream_t st, double* Pb, double* mub, int ld, int n_old, int n_new, double var, const double* xy);
+void launch_fill_diag(hipStream_t st, double* Pb, int ld, int n, const double* diag);
+void launch_mirror(hipStream_t st, double* P, const int* nact, int ld, long pstride, int batch, int n_hi);
+void launch_pack_small(hipStream_t st, const double* Pb, const double* mub, const unsigned* flag_b, int ld, int n, double* host_out);
+void launch_pack_dense(hipStream_t st, const double* Pb, int ld, int n, double* host_out);
+// ---- the small-state path (ekf_small.hip) ----
+// ekf_step_fetch: trajectory out_b's state goes to the pinned host_out, released by out_seq in *host_seq (out_b < 0: none)
+struct SmallFetch {
+  double* host_out = nullptr; int out_b = -1;
+  unsigned long long* host_seq = nullptr; unsigned long long out_seq = 0;
+};
+// form: ekf_host_plan.h's SmallForm (plan_small); lg / plg: the logging instantiations.  Non-zero: hipFuncSetAttribute failed.
+int launch_small_stream(hipStream_t st, const BankView& k, const StepBufs& s, const StepIn* in, int nsteps, const DeviceConfig& cfg,
+                        int n_hi, int form, const SmallFetch& f, const InnovLog* lg, const PoseLog* plg);
+// ---- fused cadences (ekf_cadence.hip) ----
+long cadence_gbuf_doubles();   // per trajectory: CAD_GP parts
+int chain_sync_words();
+// (look-ahead) the next cadence's block while `kb` ranks and the noise `dacc` are pending -> gbuf
+void launch_gather_cad(hipStream_t st, const BankView& k, const double* dacc, const StepIn* in, const CadPlan* plan, int kb,
+                       const DeviceConfig& cfg, double* gbuf);
+// `colbuf` (batch x CAD_CU x ld doubles, or nullptr): the launch also gathers the mirrored column entries of the panel launch
+// behind it, on `col_wgs` extra workgroups -- only where P_base is current (not beside a pass: look-ahead)
+// `chain`: the instantiation that also records the pose block behind the cadence (CadOut::posefin) for k_chain_cad; `gmu`
+// (with gbuf, one part): block and mean come from k_chain_cad.  Writes s.mu_out, s.dacc_out and the records s.cad.
+struct SolveCadArgs {
+  const double* gbuf = nullptr; int gparts = 0;
+  double* colbuf = nullptr; int col_wgs = 0;
+  bool chain = false;
+  const double* gmu = nullptr; unsigned* sync = nullptr; unsigned start_sigma = 0; const CadPre* pre = nullptr;
+};
+void launch_solve_cad(hipStream_t st, const BankView& k, const StepBufs& s, const StepIn* in, const CadPlan* plan,
+                      const DeviceConfig& cfg, int n_hi, const SolveCadArgs& a, const PoseLog* plg);
+// (chained runs) the next cadence's block and mean from cadence `prev`, whose solve has just run: its records prev.cad, the mean
+// it read (prev.mu_in: the landmarks) and left the pose in (prev.mu_out), the pose rows before it (prev.prow3_in).  `plan`: the
+// next cadence's; `gw` gather workgroups per trajectory (ekf_host_plan.h: chain_gather_workgroups); pre_out / plan2: the inputs
+// of the cadence after the next, formed ahead (nullptr: none follows)
+struct ChainArgs {
+  double *gbuf, *gmu, *xg, *bg;
+  unsigned* sync; unsigned sigma = 0, gather_target = 0; int gw = 1; bool wait_pass = false;
+  const CadPre* pre_in = nullptr; CadPre* pre_out = nullptr; const CadPlan* plan2 = nullptr;
+};
+void launch_chain_cad(hipStream_t st, const BankView& k, const StepBufs& prev, const StepIn* in, const CadPlan* plan,
+                      const DeviceConfig& cfg, const ChainArgs& a);
+void launch_mark(hipStream_t st, unsigned* sync, unsigned sigma);
+void launch_gate(hipStream_t st, unsigned* sync, unsigned sigma, unsigned* flags, int batch);
+void launch_snap_pose(hipStream_t st, const BankView& k, int n_hi, double* prow3);
+// `nrp`: the ranks the bank's busiest trajectory appends, padded to a whole k-tile (every trajectory writes that many);
+// `form`: ekf_host_plan.h's PanelForm (plan_cadence_step); `skipw` (w_from_v): the replay forms write V only; sync / tail_target /
+// start_sigma: a chained cadence's hand-overs.  Reads the records s.cad, leaves the pose rows in s.prow3_out (nullptr: not kept).
+struct PanelCadArgs {
+  int nrp, form; bool skipw; const double* colbuf;
+  unsigned* sync = nullptr; unsigned tail_target = 0, start_sigma = 0;
+};
+void launch_panels_cad(hipStream_t st, const BankView& k, const StepBufs& s, int n_hi, const PanelCadArgs& a);
+// ---- the logs (ekf_innovations.hip, ekf_pose_log.hip) ----
+void launch_innov_step(hipStream_t st, const StepIn* in, const SolveOut* so, int meas, int gate, int batch, const InnovLog& lg);
+void launch_innov_cad(hipStream_t st, const StepIn* in, const CadPlan* plan, const CadOut* co, int meas, int gate, int batch,
+                      const InnovLog& lg);
+void launch_pose_step(hipStream_t st, const PendingView& f, const PoseLog& lg);
+// ---- the read-only queries (ekf_marginals.hip, ekf_associate.hip, ekf_joint.hip) ----
+void launch_marginals(hipStream_t st, const PendingView& f, int cap, double* pose_out, double* lm_out);
+long assoc_query_part_doubles(int count, int chunks, int stride);
+void launch_assoc_query(hipStream_t st, const PendingView& f, const DeviceConfig& cfg, int stride, int cap, int chunks,
+                        const double* zr, const double* zb, const int* zm, double* part, double* all_nis, double* all_logdet,
+                        int* cand, double* cand_nis, double* cand_logdet, double* min_nis);
+void launch_joint(hipStream_t st, const PendingView& f, int ns, int nt, int tiles, const int* sel, double* mean_out, double* cov_out);
+// ---- state surgery (ekf_remove.hip, ekf_direct.hip, ekf_copy.hip, ekf_dense.hip) ----
+// rp.rows: the launch's largest new size (grid rows); nb trajectories from b0; src / dst: rp's tables on the device
+void launch_remove(hipStream_t st, const BankView& k, double* mu, const RemovePlan& rp, const int* src, const int* dst,
+                   unsigned* rflag, int b0, int nb, unsigned seq);
+void launch_direct(hipStream_t st, int rows_cap, const BankView& k, double* dacc, double* mu, const int* plan, const double* meas,
+                   double* out, int kpad);
+// groups x (tiles of the largest source + 1) workgroups; tab: plan_copy's table on the device
+void launch_copy_traj(hipStream_t st, bool nt, const BankView& src, const BankView& dst, const double* mus, double* mud,
+                      const int* tab, int groups, int n_hi);
+int dense_propagate(hipStream_t st, double* P, double* tmp, const double* F, const double* Q, int n, int ld);
+}  // namespace ekf

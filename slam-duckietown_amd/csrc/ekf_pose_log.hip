@@ -15,6 +15,7 @@
 #include "ekf_device.h"
 
 #include "ekf_devfn.h"
+#include "ekf_launch.h"
 
 namespace ekf {
 
@@ -68,9 +69,8 @@ __global__ __launch_bounds__(64) void k_pose_step(const double* __restrict__ P, 
   }
 }
 
-void launch_pose_step(hipStream_t st, const double* P, const double* V, const double* W, const double* dacc, const double* mu,
-                      int ld, long pstride, int kb, int batch, const PoseLog& lg) {
-  hipLaunchKernelGGL(k_pose_step, dim3(batch), dim3(64), 0, st, P, V, W, dacc, mu, ld, pstride, kb, batch, lg);
+void launch_pose_step(hipStream_t st, const PendingView& f, const PoseLog& lg) {   // (f: the whole bank, b0 = 0)
+  hipLaunchKernelGGL(k_pose_step, dim3(f.count), dim3(64), 0, st, f.P, f.V, f.W, f.dacc, f.mu, f.ld, f.pstride, f.kb, f.count, lg);
 }
 
 }  // namespace ekf

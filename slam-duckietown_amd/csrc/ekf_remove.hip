@@ -21,7 +21,8 @@
 // every entry of the columns they add, as after an upload of a smaller state).
 // One workgroup of 256 threads per (trajectory, new row), NQ columns per thread (ekf_host_plan.h: plan_remove); blockIdx.x = 0
 // compacts the mean, blockIdx.x = 1 + t takes row t.  Vector stores only.
-#include "ekf_device.h"
+#include "ekf_host_plan.h"
+#include "ekf_launch.h"
 
 namespace ekf {
 
@@ -91,13 +92,12 @@ __global__ __launch_bounds__(RM_THREADS) void k_remove(double* __restrict__ P, d
   }
 }
 
-// rows: the launch's largest new size (grid rows); nb trajectories from b0
-void launch_remove(hipStream_t st, int nq, double* P, double* mu, const int* nact, const int* src, const int* dst, unsigned* rflag,
-                   unsigned* flags, int b0, int nb, int rows, int k2, int r0, unsigned seq, int ld, long pstride) {
-  const dim3 grid(1 + rows, nb);
+void launch_remove(hipStream_t st, const BankView& k, double* mu, const RemovePlan& rp, const int* src, const int* dst,
+                   unsigned* rflag, int b0, int nb, unsigned seq) {
+  const dim3 grid(1 + rp.rows, nb);
 #define EKF_RM_CASE(Q) \
-  case Q: hipLaunchKernelGGL(k_remove<Q>, grid, dim3(RM_THREADS), 0, st, P, mu, nact, src, dst, rflag, flags, b0, k2, r0, seq, ld, pstride); break;
-  switch (nq) {
+  case Q: hipLaunchKernelGGL(k_remove<Q>, grid, dim3(RM_THREADS), 0, st, k.P, mu, k.nact, src, dst, rflag, k.flags, b0, rp.k2, rp.r0, seq, k.ld, k.pstride); break;
+  switch (rp.nq) {
     EKF_RM_CASE(1)
     EKF_RM_CASE(2)
     EKF_RM_CASE(4)
@@ -105,7 +105,7 @@ void launch_remove(hipStream_t st, int nq, double* P, double* mu, const int* nac
     EKF_RM_CASE(16)
     EKF_RM_CASE(32)
     EKF_RM_CASE(64)
-    default: hipLaunchKernelGGL(k_remove<96>, grid, dim3(RM_THREADS), 0, st, P, mu, nact, src, dst, rflag, flags, b0, k2, r0, seq, ld, pstride);
+    default: hipLaunchKernelGGL(k_remove<96>, grid, dim3(RM_THREADS), 0, st, k.P, mu, k.nact, src, dst, rflag, k.flags, b0, rp.k2, rp.r0, seq, k.ld, k.pstride);
   }
 #undef EKF_RM_CASE
 }

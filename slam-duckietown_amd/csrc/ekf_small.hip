@@ -21,6 +21,7 @@
 #include <atomic>
 #include "ekf_devfn.h"
 #include "ekf_host_plan.h"
+#include "ekf_launch.h"
 
 namespace ekf {
 
@@ -441,29 +442,25 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   small_stream_body<NT, TM, true, NZ, true>(SMALL_STREAM_PASS, lg, plg);
 }
 
-int launch_small_stream(hipStream_t st, double* P, const double* mu_in, double* mu_out, const int* nact, const StepIn* in,
-                        int batch, int nsteps, unsigned* flags, const DeviceConfig& cfg, int ld, long pstride, int n_hi,
-                        double* host_out, int out_b, unsigned long long* host_seq, unsigned long long out_seq, int form,
-                        const InnovLog* lg, const PoseLog* plg) {   // form: ekf_host_plan.h's SmallForm (plan_small)
+int launch_small_stream(hipStream_t st, const BankView& k, const StepBufs& s, const StepIn* in, int nsteps, const DeviceConfig& cfg,
+                        int n_hi, int form, const SmallFetch& f, const InnovLog* lg, const PoseLog* plg) {
   const int n = n_hi < SMALL_N_MAX_BANK ? n_hi : SMALL_N_MAX_BANK, ps = n | 1;
   const size_t bytes = sizeof(double) * ((size_t)n * ps + 5 * (size_t)n + 4) + 2 * sizeof(StepIn);
+  const dim3 grid(k.batch);
+#define EKF_SMALL_ARGS                                                                                                   \
+  k.P, s.mu_in, s.mu_out, k.nact, in, k.batch, nsteps, k.flags, cfg, k.ld, k.pstride, f.host_out, f.out_b, f.host_seq, f.out_seq
 #define EKF_SMALL(K, TM)                                                                                                 \
   do {                                                                                                                   \
     if (plg && cfg.noise)                                                                                                \
-      hipLaunchKernelGGL((K##_plog<256, TM, true>), dim3(batch), dim3(256), bytes, st, P, mu_in, mu_out, nact, in, batch,  \
-                         nsteps, flags, cfg, ld, pstride, host_out, out_b, host_seq, out_seq, lg ? *lg : InnovLog{}, *plg); \
+      hipLaunchKernelGGL((K##_plog<256, TM, true>), grid, dim3(256), bytes, st, EKF_SMALL_ARGS, lg ? *lg : InnovLog{}, *plg);  \
     else if (plg)                                                                                                        \
-      hipLaunchKernelGGL((K##_plog<256, TM, false>), dim3(batch), dim3(256), bytes, st, P, mu_in, mu_out, nact, in, batch, \
-                         nsteps, flags, cfg, ld, pstride, host_out, out_b, host_seq, out_seq, lg ? *lg : InnovLog{}, *plg); \
-    else if (lg && cfg.noise)                                                                                                 \
-      hipLaunchKernelGGL((K##_log<256, TM, true>), dim3(batch), dim3(256), bytes, st, P, mu_in, mu_out, nact, in, batch,   \
-                         nsteps, flags, cfg, ld, pstride, host_out, out_b, host_seq, out_seq, *lg);                      \
+      hipLaunchKernelGGL((K##_plog<256, TM, false>), grid, dim3(256), bytes, st, EKF_SMALL_ARGS, lg ? *lg : InnovLog{}, *plg); \
+    else if (lg && cfg.noise)                                                                                            \
+      hipLaunchKernelGGL((K##_log<256, TM, true>), grid, dim3(256), bytes, st, EKF_SMALL_ARGS, *lg);                      \
     else if (lg)                                                                                                         \
-      hipLaunchKernelGGL((K##_log<256, TM, false>), dim3(batch), dim3(256), bytes, st, P, mu_in, mu_out, nact, in, batch,  \
-                         nsteps, flags, cfg, ld, pstride, host_out, out_b, host_seq, out_seq, *lg);                      \
+      hipLaunchKernelGGL((K##_log<256, TM, false>), grid, dim3(256), bytes, st, EKF_SMALL_ARGS, *lg);                     \
     else                                                                                                                 \
-      hipLaunchKernelGGL((K<256, TM>), dim3(batch), dim3(256), bytes, st, P, mu_in, mu_out, nact, in, batch, nsteps, flags, \
-                         cfg, ld, pstride, host_out, out_b, host_seq, out_seq);                                          \
+      hipLaunchKernelGGL((K<256, TM>), grid, dim3(256), bytes, st, EKF_SMALL_ARGS);                                      \
   } while (0)
   // (more than 64 KB of dynamic LDS has to be asked for, once per kernel and device)
   int dev = 0;
@@ -496,6 +493,7 @@ int launch_small_stream(hipStream_t st, double* P, const double* mu_in, double* 
   else EKF_SMALL_BIG(k_small_stream, 9);
 #undef EKF_SMALL_BIG
 #undef EKF_SMALL
+#undef EKF_SMALL_ARGS
   return 0;
 }
 
