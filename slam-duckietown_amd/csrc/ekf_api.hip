@@ -5,7 +5,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <initializer_list>
 #include <limits>
 #include <string>
 #include <utility>
@@ -14,6 +13,7 @@
 #include "ekf_device.h"
 #include "ekf_host_plan.h"
 #include "ekf_launch.h"
+#include "ekf_resources.h"
 
 using namespace ekf;
 
@@ -52,110 +52,120 @@ constexpr int RING_GROUP = 4;             // slots per completion event: an even
                                           // stream a barrier packet, ~2 us per online step of a small filter
 constexpr int PACK_SMALL_N = 131;        // states up to 64 landmarks are downloaded by k_pack_small (137 KB of pinned memory)
 
-struct ekf_handle;
-// A device buffer allocated on first use that only grows: `cap` elements at p (nullptr until reserved).
-template <class T> struct DeviceBuf {
-  T* p = nullptr;
-  size_t cap = 0;
-  int reserve(ekf_handle* h, hipStream_t st, size_t need, size_t at_least = 0);
+// How the ownership types of ekf_resources.h reach the runtime: the only allocations, frees, event creations and destructions
+// of this file (beside ekf_host_alloc / ekf_host_free, the ABI's own).
+struct HipBackend {
+  using Stream = hipStream_t;
+  using Event = hipEvent_t;
+  static constexpr unsigned pinned_default = hipHostMallocDefault;
+  static int device_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+  static int device_free(void* p) { return hipFree(p); }
+  static int pinned_alloc(void** p, size_t bytes, unsigned flag) { return hipHostMalloc(p, bytes, flag); }
+  static int pinned_free(void* p) { return hipHostFree(p); }
+  static int event_create(Event* e, bool timing) { return timing ? hipEventCreate(e) : hipEventCreateWithFlags(e, hipEventDisableTiming); }
+  static int event_destroy(Event e) { return hipEventDestroy(e); }
+  static int event_record(Event e, Stream st) { return hipEventRecord(e, st); }
+  static int event_wait(Event e) { return hipEventSynchronize(e); }
+  static int stream_wait(Stream st) { return hipStreamSynchronize(st); }
+  static int copy_to_device(void* dst, const void* src, size_t bytes, Stream st) {
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+  }
 };
+template <class T> using DeviceBuf = res::DeviceBuf<T, HipBackend>;
+template <class T> using PinnedBuf = res::PinnedBuf<T, HipBackend>;
+template <class T> using StagedUpload = res::StagedUpload<T, HipBackend>;
+using Event = res::Event<HipBackend>;
 
 struct ekf_handle : ekf::HostPlan {
   DeviceConfig dcfg{};
   hipStream_t stream = nullptr;
-  double *dP = nullptr, *dV = nullptr, *dW = nullptr, *dscratch = nullptr;
-  double* ddacc2[2] = {nullptr, nullptr};  // pending pose-block noise, double-buffered like the mean
+  // Every buffer and event below is owned by its member (ekf_resources.h) and released when the handle is deleted (free_all).
+  DeviceBuf<double> dP, dV, dW, dscratch;
+  DeviceBuf<double> ddacc2[2];    // pending pose-block noise, double-buffered like the mean
   int dcur = 0;
-  double* dmu2[2] = {nullptr, nullptr};   // the mean is double-buffered: a step reads [cur], writes [cur^1]
+  DeviceBuf<double> dmu2[2];      // the mean is double-buffered: a step reads [cur], writes [cur^1]
   int cur = 0;
-  int* dn = nullptr;
-  unsigned* dflags = nullptr;
-  SolveOut* dso = nullptr;
-  double* dfac = nullptr;         // pending factors restricted to the gathered indices (k_solve -> k_panels)
-  StepIn *d_ring = nullptr, *h_ring = nullptr;
-  hipEvent_t ring_ev[RING / RING_GROUP]{};   // one event per group of slots (see ring_take)
-  bool ring_used[RING / RING_GROUP]{};
+  DeviceBuf<int> dn;
+  DeviceBuf<unsigned> dflags;
+  DeviceBuf<SolveOut> dso;
+  DeviceBuf<double> dfac;         // pending factors restricted to the gathered indices (k_solve -> k_panels)
+  DeviceBuf<StepIn> d_ring;
+  PinnedBuf<StepIn> h_ring;
+  Event ring_ev[RING / RING_GROUP];   // one event per group of slots (see ring_take)
   bool ring_open[RING / RING_GROUP]{};
   int ring_pos = 0;
-  StepIn* d_stream = nullptr;
-  size_t stream_cap = 0;
-  int* dfloor = nullptr;          // per trajectory floor of the active bound, applied by k_solve (see push_floor)
-  double *dF = nullptr, *dQ = nullptr, *dTmp = nullptr;   // dense path, allocated on first use
-  double* dPlin = nullptr;        // dense path with P in column panels: its row-major staging copy
-  // device-side association (allocated on first use)
-  int *dtagmap = nullptr, *dneff = nullptr;
-  DetIn *d_det = nullptr, *h_det = nullptr;
-  StepIn* d_assoc_step = nullptr;
-  AssocOut* d_assoc_out = nullptr;
+  DeviceBuf<StepIn> d_stream;
+  DeviceBuf<int> dfloor;          // per trajectory floor of the active bound, applied by k_solve (see push_floor)
+  DeviceBuf<double> dF, dQ, dTmp; // dense path, allocated on first use (one group)
+  DeviceBuf<double> dPlin;        // dense path with P in column panels: its row-major staging copy
+  // device-side association (one group, allocated on first use: assoc_init)
+  DeviceBuf<int> dtagmap, dneff;
+  DeviceBuf<DetIn> d_det;
+  PinnedBuf<DetIn> h_det;
+  DeviceBuf<StepIn> d_assoc_step;
+  DeviceBuf<AssocOut> d_assoc_out;
   AssocConfig acfg{};
-  hipEvent_t t0 = nullptr, t1 = nullptr;
+  Event t0, t1;
   bool profile = false;
   int profile_stride = 1;         // every how many launches of the pass carry an event pair while profiling ("profile_stride")
   long prof_seen = 0;
-  std::vector<hipEvent_t> prof_pool;
+  std::vector<Event> prof_pool;
   size_t prof_used = 0;
   // "profile_kernels" = 1: the cadence's other launches carry event pairs too (a diagnostic run: every record costs its stream
   // ~6 us); class of pair i: 0 the covariance pass, 1 the solve launch, 2 the chain / look-ahead gather launch, 3 the panel launch
   int opt_profile_kernels = 0;
   std::vector<int> prof_cls;
-  unsigned* dqueue = nullptr;     // work-queue heads of k_flush_rs (zeroed before every launch)
-  // k_flush_rs, equal static shares (a few long trajectories): the piece table.  Two copies on the device and in pinned
-  // host memory, used alternately: a rebuilt table is uploaded stream-ordered, without a host synchronisation, while the
-  // pass that read the previous one may still be running.
-  int* dshares2[2] = {nullptr, nullptr};
-  int* hshares2[2] = {nullptr, nullptr};
-  hipEvent_t shares_ev[2] = {nullptr, nullptr};   // the upload out of hshares2[i] has been executed
-  bool shares_ev_used[2] = {false, false};
+  DeviceBuf<unsigned> dqueue;     // work-queue heads of k_flush_rs (zeroed before every launch)
+  // k_flush_rs, equal static shares (a few long trajectories): the piece table.  Two copies, used alternately: a rebuilt
+  // table is uploaded stream-ordered, without a host synchronisation, while the pass that read the previous one may still be
+  // running.
+  StagedUpload<int> shares2[2];
   int shares_cur = 0;
   int shares_key[4] = {0, 0, 0, 0};   // (batch, slabs, last strip, workgroups) the current table was built for
   int shares_ok = 0;              // pieces of its longest share (0: no table for this key -- the queue modes are used)
-  unsigned* dready = nullptr;     // per trajectory: sequence number of the last solve that completed (k_step_split)
-  SolveOut* dmbox = nullptr;      // per trajectory: that solve's header and records, written through (mailbox_publish)
+  DeviceBuf<unsigned> dready;     // per trajectory: sequence number of the last solve that completed (k_step_split)
+  DeviceBuf<SolveOut> dmbox;      // per trajectory: that solve's header and records, written through (mailbox_publish)
   unsigned step_seq = 0;          // sequence number of the last single-launch step
   // per trajectory: head + per-landmark records of a cadence (allocated on first use).  Two copies, used alternately by
   // consecutive cadences (`cpar`): in a chained run the next cadence's solve writes its records while this cadence's panel
   // launch still reads these
-  CadOut* dcad2[2] = {nullptr, nullptr};
+  DeviceBuf<CadOut> dcad2[2];
   int cpar = 0;
   // Chained solves (round 6; "chain"): the solves of a run follow one another on the handle's stream -- the next cadence's
   // block comes from this cadence's records (k_chain_cad) -- while panel launch and covariance pass of every cadence run
   // on the second stream.  dprow3: rows 0..2 of every P after a cadence, left by its panel launch (batch x 3 x ld, two copies
   // like dcad2); dgmu: the mean at the next cadence's positions (batch x 128).
-  double* dprow3[2] = {nullptr, nullptr};
-  double* dgmu = nullptr;
-  double *dxg = nullptr, *dbg = nullptr;   // the chain launch's gathered rows (batch x 84 x 88 each): written by its gather workgroups
-  unsigned* dsync = nullptr;      // device-scope counters of the chained run's hand-overs (ekf_cadence.hip: SYNC_*)
+  DeviceBuf<double> dprow3[2];
+  DeviceBuf<double> dgmu;
+  DeviceBuf<double> dxg, dbg;     // the chain launch's gathered rows (batch x 84 x 88 each): written by its gather workgroups
+  DeviceBuf<unsigned> dsync;      // device-scope counters of the chained run's hand-overs (ekf_cadence.hip: SYNC_*)
   unsigned gather_count = 0;      // gather workgroups launched so far (what the next chain workgroups wait for)
   unsigned sigma = 0;             // chained transitions so far (the value the run's counters SYNC_SOLVE / SYNC_PASS carry)
   // a cadence's inputs formed one cadence ahead (CadPre): two copies, by the cadence's serial number (pre_serial: whose inputs a
   // copy holds; serials count every cadence of the handle)
-  CadPre* dpre[2] = {nullptr, nullptr};
+  DeviceBuf<CadPre> dpre[2];
   long pre_serial[2] = {-1, -1};
   long cad_serial = 0;
-  hipEvent_t ev_pass = nullptr;   // recorded on the second stream when a chain of cadences ends (join_aux): the only event of the chained order
+  Event ev_pass;                  // recorded on the second stream when a chain of cadences ends (join_aux): the only event of the chained order
   bool aux_pass = false;          // a covariance pass is in flight on the second stream (ev_pass recorded behind it)
   long w_from_v_passes = 0;       // statistics: passes that formed W from V ("w_from_v")
   int opt_run_end_flush = 0;      // 1 = ekf_stream_run applies what its last cadence left pending, so that the next call starts fused
   long chained = 0;               // statistics: cadences whose block came from k_chain_cad
   // The mirrored column entries of a cadence's panel launch, gathered by extra workgroups of its solve launch and laid down
   // as rows (batch x 83 x ld doubles, allocated on first use; not for banks where that would exceed 1 GiB; "col_gather")
-  double* dcolbuf = nullptr;
+  DeviceBuf<double> dcolbuf;
   long cadences = 0, cadence_traj_steps = 0;   // statistics: fused cadences launched, trajectory-steps they completed
   // The packed cadences of the ekf_stream_run in flight (ekf_host_plan.h: plan_cadences): one CadPlan per (cadence,
   // trajectory), planned on the host for the whole run and uploaded once, stream-ordered, out of pinned memory.  Two copies,
   // used alternately: the host may plan the next run while the upload of this one has not executed yet.
   RunPlan run_plan;
-  CadPlan* dplan2[2] = {nullptr, nullptr};
-  CadPlan* hplan2[2] = {nullptr, nullptr};
-  size_t plan_cap2[2] = {0, 0};
-  hipEvent_t plan_ev[2] = {nullptr, nullptr};     // the upload out of hplan2[i] has been executed
-  bool plan_ev_used[2] = {false, false};
+  StagedUpload<CadPlan> plan2[2];
   int plan_cur = 0;
   // look-ahead (small launches): the solve of the next cadence runs on the handle's stream beside the covariance pass of
   // this one, which goes to a second stream between two events; see ekf_stream_run
   hipStream_t aux = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  double* dgbuf = nullptr;        // per trajectory: the next cadence's block, gathered while this one's ranks are pending
+  Event ev_fork, ev_join;
+  DeviceBuf<double> dgbuf;        // per trajectory: the next cadence's block, gathered while this one's ranks are pending
   long lookaheads = 0;
   long assoc_fallbacks = 0;       // statistics: windows a binding took through the host association (ekf_debug_note_assoc_fallback)
   long small_launches = 0;        // statistics: launches of the small-state path (k_small_stream)
@@ -172,58 +182,55 @@ struct ekf_handle : ekf::HostPlan {
   int last_wv = 0;                // ... and whether it formed its W fragments from V ("w_from_v")
   int last_shares = 0;            // ... and whether it ran on equal static shares (k_flush_rs, a few long trajectories)
   std::vector<unsigned> flags_host;
-  unsigned* h_flags = nullptr;    // pinned: the sticky flags are read back with a stream-ordered copy
-  double* h_pack = nullptr;       // pinned: where k_pack_small leaves a small state (n x n covariance, mean, flags)
+  PinnedBuf<unsigned> h_flags;    // pinned: the sticky flags are read back with a stream-ordered copy
+  PinnedBuf<double> h_pack{hipHostMallocCoherent};   // pinned, coherent: where k_pack_small leaves a small state (n x n covariance, mean, flags)
   // The read-only queries' staging buffer: a query's inputs, then its destinations that are not pinned (StagingPlan).  Every
   // query synchronises the stream before it returns, so the next one finds the buffer free.
   DeviceBuf<double> dquery;
   std::vector<int> joint_sel;     // ekf_download_joint: the selection as the host sorted it (plan_joint_query)
   std::vector<std::pair<int, int>> joint_order;   // ... scratch of the sort (handle-owned: no allocation per query)
-  // The innovation log (ekf_log_innovations; nullptr: off): a ring of innov_cap step rows, innov_steps steps logged so far.
+  // The innovation log (ekf_log_innovations; empty: off): a ring of innov_cap step rows, innov_steps steps logged so far.
   // While an entry point enqueues a logged step, lg_slot is the ring row of its next launch (-1: that launch is not logged) and
   // lg_jbase the position of its first landmark; ekf_stream_run logs stream step t in row (lg_tslot + t) % innov_cap.
-  InnovRec* dinnov = nullptr;
-  int* dinnov_m = nullptr;
+  DeviceBuf<InnovRec> dinnov;
+  DeviceBuf<int> dinnov_m;
   int innov_cap = 0;
   long long innov_steps = 0;
   long lg_slot = -1, lg_tslot = -1;
   int lg_jbase = 0;
-  // The pose log (ekf_log_poses; nullptr: off): a ring of pose_cap step rows (batch x POSE_ROW doubles each), pose_steps steps
+  // The pose log (ekf_log_poses; empty: off): a ring of pose_cap step rows (batch x POSE_ROW doubles each), pose_steps steps
   // logged so far; a counter of its own -- a lone prediction is a row here and none in the innovation log.  While an entry
   // point enqueues a step, pl_slot is its ring row (-1: nothing is logged); ekf_stream_run logs stream step t in row
   // (pl_tslot + t) % pose_cap.
-  double* dpose = nullptr;
+  DeviceBuf<double> dpose;
   int pose_cap = 0;
   long long pose_steps = 0;
   long pl_slot = -1, pl_tslot = -1;
   // The NIS gate (ekf_set_nis_gate): per-trajectory rejection counters, allocated when the gate is first switched on.  While
   // the gate is on dcfg.gate_rej points at them and dcfg.nis_gate holds the threshold (kernel arguments: every launch
   // enqueued after the call sees the new value).
-  unsigned long long* dgate = nullptr;
+  DeviceBuf<unsigned long long> dgate;
   // Per-trajectory noise constants (ekf_set_noise), allocated on the first call: noise_ms / noise_qs are the sigmas in effect
-  // for work enqueued next (ekf_get_noise reads them), dnoise the device table of their rows.  dcfg.noise points at dnoise
+  // for work enqueued next (ekf_get_noise reads them), `noise` the table of their rows.  dcfg.noise points at its device copy
   // while some row differs from the handle's constants, nullptr otherwise (the kernels without the table).  The upload goes
-  // through the pinned hnoise_stage, which is written again only once noise_ev (recorded behind that copy) has completed.
+  // through its pinned copy, which is written again only once the event recorded behind the previous copy has completed.
   std::vector<double> noise_ms, noise_qs;
-  double* dnoise = nullptr;
-  double* hnoise_stage = nullptr;
-  hipEvent_t noise_ev = nullptr;
-  bool noise_ev_used = false;
+  StagedUpload<double> noise;
   // Set when an enqueueing call failed half way (e.g. a launch of the look-ahead failed after the next cadence's solve had
   // already run): the device state of every trajectory is undefined until it is uploaded again; see check_internal
   std::vector<unsigned char> host_bad;
   // ekf_remove_landmarks (allocated on first use): the launch's index tables (src then dst, ld ints each), the row
   // announcements of k_remove (batch x ld words) and the sequence number the last launch announced with.  stream_stale: the
   // uploaded stream was validated against sizes a removal has changed since (ekf_stream_run refuses it)
-  int* drm_tab = nullptr;
-  unsigned* drm_flag = nullptr;
+  DeviceBuf<int> drm_tab;
+  DeviceBuf<unsigned> drm_flag;
   unsigned rm_seq = 0;
   bool stream_stale = false;
   // ekf_copy_trajectories (allocated on first use, in the DESTINATION handle): the launch's table of groups (plan_copy)
   DeviceBuf<int> dcp_tab;
   // ekf_update_direct (allocated on first use): per trajectory of the bank the row plan (DIRECT_INTS ints), the measurements
   // (DIRECT_DBLS doubles) and the results (NIS, applied) of k_direct, and their host sides
-  double* ddirect = nullptr;
+  DeviceBuf<double> ddirect;
   ekf::DirectPlan direct_plan;
   std::vector<int> direct_ints;
   std::vector<double> direct_dbls, direct_out;
@@ -248,20 +255,16 @@ static int materialize(ekf_handle* h, int b);
       return fail(h, EKF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
   } while (0)
 
-// Room for `need` elements (a new buffer holds at least `at_least`); the contents are not kept.  The old buffer may still be
-// in use by work in flight on `st`, which is waited for before it is freed.  A failed call leaves the buffer as it was or empty.
-template <class T> int DeviceBuf<T>::reserve(ekf_handle* h, hipStream_t st, size_t need, size_t at_least) {
-  if (need <= cap) return EKF_OK;
-  if (p) HIP_TRY(h, hipStreamSynchronize(st));
-  cap = 0;
-  if (T* old = std::exchange(p, nullptr)) HIP_TRY(h, hipFree(old));
-  const size_t want = std::max(need, at_least);
-  const hipError_t e = hipMalloc(&p, sizeof(T) * want);
-  if (e != hipSuccess) p = nullptr;
-  HIP_TRY(h, e);
-  cap = want;
-  return EKF_OK;
+// What an ownership operation (ekf_resources.h) reports, as this file's error: `what` names the buffer or group.
+static int res_fail(ekf_handle* h, const char* what, const res::Status& s) {
+  return fail(h, EKF_ERR_HIP, std::string(what) + (s.bytes ? ": allocation of " + std::to_string(s.bytes) + " bytes" : std::string()) +
+                                  ": " + hipGetErrorString((hipError_t)s.err));
 }
+#define RES_TRY(h, what, expr)                                                             \
+  do {                                                                                     \
+    const res::Status s_ = (expr);                                                         \
+    if (!s_.ok()) return res_fail(h, what, s_);                                            \
+  } while (0)
 
 // The device's view of a pinned host allocation (ekf_host_alloc), which a kernel can write in place; nullptr for anything else.
 static void* device_view(void* p) {
@@ -279,7 +282,7 @@ static hipError_t copy_cov(ekf_handle* h, int b, double* host, int host_pitch, i
                            bool device_to_device = false) {
   for (int p = c0 / PPW; p <= (c0 + cols - 1) / PPW; ++p) {
     const int cs = std::max(c0, p * PPW), ce = std::min(c0 + cols, (p + 1) * PPW);
-    double* dev = h->dP + (size_t)b * h->pstride + p_index(h->ld, r0, cs);
+    double* dev = h->dP.p + (size_t)b * h->pstride + p_index(h->ld, r0, cs);
     double* hst = host + (cs - c0);
     const size_t dpitch = sizeof(double) * (size_t)p_lds(h->ld), hpitch = sizeof(double) * (size_t)host_pitch;
     const size_t width = sizeof(double) * (size_t)(ce - cs);
@@ -327,41 +330,21 @@ extern "C" void ekf_host_free(void* p) {
 
 extern "C" const char* ekf_last_error(ekf_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
+// The handle's members release what they own (ekf_resources.h) when it is deleted: with its device selected and both streams idle.
 static void free_all(ekf_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  void* ptrs[] = {h->dP, h->dmu2[0], h->dmu2[1], h->dV, h->dW, h->ddacc2[0], h->ddacc2[1], h->dscratch, h->dn, h->dflags, h->dso, h->dfac,
-                  h->d_ring, h->d_stream, h->dF, h->dQ, h->dTmp, h->dPlin, h->dtagmap, h->dneff, h->d_det, h->d_assoc_step, h->dfloor, h->dqueue, h->dready, h->dmbox,
-                  h->d_assoc_out, h->dcad2[0], h->dcad2[1], h->dprow3[0], h->dprow3[1], h->dgmu, h->dxg, h->dbg, h->dsync, h->dpre[0], h->dpre[1], h->dshares2[0], h->dshares2[1], h->dgbuf, h->dplan2[0], h->dplan2[1], h->dcolbuf, h->dquery.p, h->dinnov, h->dinnov_m, h->dgate, h->dnoise, h->drm_tab, h->drm_flag, h->dpose, h->dcp_tab.p, h->ddirect};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (h->h_ring) (void)hipHostFree(h->h_ring);
-  if (h->h_det) (void)hipHostFree(h->h_det);
-  for (int i = 0; i < 2; ++i) {
-    if (h->hshares2[i]) (void)hipHostFree(h->hshares2[i]);
-    if (h->shares_ev[i]) (void)hipEventDestroy(h->shares_ev[i]);
-    if (h->hplan2[i]) (void)hipHostFree(h->hplan2[i]);
-    if (h->plan_ev[i]) (void)hipEventDestroy(h->plan_ev[i]);
-  }
-  if (h->h_flags) (void)hipHostFree(h->h_flags);
-  if (h->h_pack) (void)hipHostFree(h->h_pack);
-  if (h->hnoise_stage) (void)hipHostFree(h->hnoise_stage);
-  if (h->noise_ev) (void)hipEventDestroy(h->noise_ev);
-  for (auto& e : h->ring_ev) if (e) (void)hipEventDestroy(e);
-  for (auto& e : h->prof_pool) (void)hipEventDestroy(e);
-  if (h->t0) (void)hipEventDestroy(h->t0);
-  if (h->t1) (void)hipEventDestroy(h->t1);
-  if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-  if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-  if (h->ev_pass) (void)hipEventDestroy(h->ev_pass);
   if (h->aux) (void)hipStreamSynchronize(h->aux);
-  if (h->stream && h->aux) {
-    park_stream_pair(h->device, h->stream, h->aux);    // (see g_pairs: the next handle on this device takes the pair over)
-  } else {
-    if (h->aux) (void)hipStreamDestroy(h->aux);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-  }
+  const int device = h->device;
+  const hipStream_t stream = h->stream, aux = h->aux;
   delete h;
+  if (stream && aux) {
+    park_stream_pair(device, stream, aux);             // (see g_pairs: the next handle on this device takes the pair over)
+  } else {
+    if (aux) (void)hipStreamDestroy(aux);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 }
 
 extern "C" int ekf_create(int device, int n_max, int batch, const ekf_config* cfg, ekf_handle** out) {
@@ -441,6 +424,15 @@ extern "C" int ekf_create(int device, int n_max, int batch, const ekf_config* cf
       return EKF_ERR_HIP;                                                                 \
     }                                                                                     \
   } while (0)
+#define CREATE_RES(what, expr)                                                            \
+  do {                                                                                    \
+    const res::Status s_ = (expr);                                                        \
+    if (!s_.ok()) {                                                                       \
+      (void)res_fail(nullptr, "ekf_create: " what, s_);                                   \
+      free_all(h);                                                                        \
+      return EKF_ERR_HIP;                                                                 \
+    }                                                                                     \
+  } while (0)
   CREATE_TRY(hipSetDevice(device));
   if (!take_stream_pair(device, &h->stream, &h->aux)) {
     CREATE_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
@@ -457,55 +449,56 @@ extern "C" int ekf_create(int device, int n_max, int batch, const ekf_config* cf
       CREATE_TRY(hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking));
     }
   }
-  CREATE_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-  CREATE_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-  CREATE_TRY(hipEventCreateWithFlags(&h->ev_pass, hipEventDisableTiming));
-  const size_t ldz = (size_t)h->ld;
-  CREATE_TRY(hipMalloc(&h->dP, sizeof(double) * (size_t)h->pstride * batch));
-  CREATE_TRY(hipMalloc(&h->dmu2[0], sizeof(double) * ldz * batch));
-  CREATE_TRY(hipMalloc(&h->dmu2[1], sizeof(double) * ldz * batch));
-  CREATE_TRY(hipMalloc(&h->dV, sizeof(double) * ldz * KTOT * batch));
-  CREATE_TRY(hipMalloc(&h->dW, sizeof(double) * ldz * KTOT * batch));
-  CREATE_TRY(hipMalloc(&h->ddacc2[0], sizeof(double) * 4 * batch));
-  CREATE_TRY(hipMalloc(&h->ddacc2[1], sizeof(double) * 4 * batch));
-  CREATE_TRY(hipMalloc(&h->dscratch, sizeof(double) * ldz * 2));
-  CREATE_TRY(hipMalloc(&h->dn, sizeof(int) * batch));
-  CREATE_TRY(hipMalloc(&h->dflags, sizeof(unsigned) * batch));
-  CREATE_TRY(hipMalloc(&h->dfloor, sizeof(int) * batch));
-  CREATE_TRY(hipMalloc(&h->dqueue, sizeof(unsigned) * flush_rs_queue_words()));
-  CREATE_TRY(hipMalloc(&h->dready, sizeof(unsigned) * batch));
-  CREATE_TRY(hipMalloc(&h->dmbox, sizeof(SolveOut) * batch));
-  CREATE_TRY(hipMemsetAsync(h->dmbox, 0, sizeof(SolveOut) * batch, h->stream));
-  CREATE_TRY(hipMemsetAsync(h->dready, 0, sizeof(unsigned) * batch, h->stream));
-  CREATE_TRY(hipMalloc(&h->dso, sizeof(SolveOut) * batch));
-  CREATE_TRY(hipMalloc(&h->dfac, sizeof(double) * FACS * batch));
-  CREATE_TRY(hipMalloc(&h->d_ring, sizeof(StepIn) * batch * RING));
-  CREATE_TRY(hipHostMalloc(&h->h_ring, sizeof(StepIn) * batch * RING, hipHostMallocDefault));
-  CREATE_TRY(hipHostMalloc(&h->h_flags, sizeof(unsigned) * batch, hipHostMallocDefault));
-  for (auto& ev : h->ring_ev) CREATE_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  CREATE_TRY(hipEventCreate(&h->t0));
-  CREATE_TRY(hipEventCreate(&h->t1));
-  CREATE_TRY(hipMemsetAsync(h->dP, 0, sizeof(double) * (size_t)h->pstride * batch, h->stream));
-  CREATE_TRY(hipMemsetAsync(h->dmu2[0], 0, sizeof(double) * ldz * batch, h->stream));
-  CREATE_TRY(hipMemsetAsync(h->dmu2[1], 0, sizeof(double) * ldz * batch, h->stream));
-  CREATE_TRY(hipMemsetAsync(h->dV, 0, sizeof(double) * ldz * KTOT * batch, h->stream));
-  CREATE_TRY(hipMemsetAsync(h->dW, 0, sizeof(double) * ldz * KTOT * batch, h->stream));
-  CREATE_TRY(hipMemsetAsync(h->ddacc2[0], 0, sizeof(double) * 4 * batch, h->stream));
-  CREATE_TRY(hipMemsetAsync(h->ddacc2[1], 0, sizeof(double) * 4 * batch, h->stream));
-  CREATE_TRY(hipMemsetAsync(h->dflags, 0, sizeof(unsigned) * batch, h->stream));
-  CREATE_TRY(hipMemsetAsync(h->dso, 0, sizeof(SolveOut) * batch, h->stream));
-  CREATE_TRY(hipMemsetAsync(h->dfac, 0, sizeof(double) * FACS * batch, h->stream));
+  CREATE_RES("ev_fork", h->ev_fork.ensure());
+  CREATE_RES("ev_join", h->ev_join.ensure());
+  CREATE_RES("ev_pass", h->ev_pass.ensure());
+  const size_t ldz = (size_t)h->ld, B = (size_t)batch;
+  CREATE_RES("dP", h->dP.ensure((size_t)h->pstride * B));
+  CREATE_RES("dmu2[0]", h->dmu2[0].ensure(ldz * B));
+  CREATE_RES("dmu2[1]", h->dmu2[1].ensure(ldz * B));
+  CREATE_RES("dV", h->dV.ensure(ldz * KTOT * B));
+  CREATE_RES("dW", h->dW.ensure(ldz * KTOT * B));
+  CREATE_RES("ddacc2[0]", h->ddacc2[0].ensure(4 * B));
+  CREATE_RES("ddacc2[1]", h->ddacc2[1].ensure(4 * B));
+  CREATE_RES("dscratch", h->dscratch.ensure(ldz * 2));
+  CREATE_RES("dn", h->dn.ensure(B));
+  CREATE_RES("dflags", h->dflags.ensure(B));
+  CREATE_RES("dfloor", h->dfloor.ensure(B));
+  CREATE_RES("dqueue", h->dqueue.ensure((size_t)flush_rs_queue_words()));
+  CREATE_RES("dready", h->dready.ensure(B));
+  CREATE_RES("dmbox", h->dmbox.ensure(B));
+  CREATE_TRY(hipMemsetAsync(h->dmbox.p, 0, sizeof(SolveOut) * batch, h->stream));
+  CREATE_TRY(hipMemsetAsync(h->dready.p, 0, sizeof(unsigned) * batch, h->stream));
+  CREATE_RES("dso", h->dso.ensure(B));
+  CREATE_RES("dfac", h->dfac.ensure((size_t)FACS * B));
+  CREATE_RES("d_ring", h->d_ring.ensure(B * RING));
+  CREATE_RES("h_ring", h->h_ring.ensure(B * RING));
+  CREATE_RES("h_flags", h->h_flags.ensure(B));
+  for (auto& ev : h->ring_ev) CREATE_RES("ring_ev", ev.ensure());
+  CREATE_RES("t0", h->t0.ensure(true));
+  CREATE_RES("t1", h->t1.ensure(true));
+  CREATE_TRY(hipMemsetAsync(h->dP.p, 0, sizeof(double) * (size_t)h->pstride * batch, h->stream));
+  CREATE_TRY(hipMemsetAsync(h->dmu2[0].p, 0, sizeof(double) * ldz * batch, h->stream));
+  CREATE_TRY(hipMemsetAsync(h->dmu2[1].p, 0, sizeof(double) * ldz * batch, h->stream));
+  CREATE_TRY(hipMemsetAsync(h->dV.p, 0, sizeof(double) * ldz * KTOT * batch, h->stream));
+  CREATE_TRY(hipMemsetAsync(h->dW.p, 0, sizeof(double) * ldz * KTOT * batch, h->stream));
+  CREATE_TRY(hipMemsetAsync(h->ddacc2[0].p, 0, sizeof(double) * 4 * batch, h->stream));
+  CREATE_TRY(hipMemsetAsync(h->ddacc2[1].p, 0, sizeof(double) * 4 * batch, h->stream));
+  CREATE_TRY(hipMemsetAsync(h->dflags.p, 0, sizeof(unsigned) * batch, h->stream));
+  CREATE_TRY(hipMemsetAsync(h->dso.p, 0, sizeof(SolveOut) * batch, h->stream));
+  CREATE_TRY(hipMemsetAsync(h->dfac.p, 0, sizeof(double) * FACS * batch, h->stream));
   // reference initial state (src/replay_no_ros.py:69-70): mu = 0, P = MOTION_MODEL_VARIANCE * I3
   {
     std::vector<double> p3(3 * 3, 0.0);
     p3[0] = p3[4] = p3[8] = h->cfg.motion_sigma;
     for (int b = 0; b < batch; ++b)
       CREATE_TRY(copy_cov(h, b, p3.data(), 3, 0, 0, 3, 3, true));
-    CREATE_TRY(hipMemcpyAsync(h->dn, h->n.data(), sizeof(int) * batch, hipMemcpyHostToDevice, h->stream));
-    CREATE_TRY(hipMemcpyAsync(h->dfloor, h->floor_host.data(), sizeof(int) * batch, hipMemcpyHostToDevice, h->stream));
+    CREATE_TRY(hipMemcpyAsync(h->dn.p, h->n.data(), sizeof(int) * batch, hipMemcpyHostToDevice, h->stream));
+    CREATE_TRY(hipMemcpyAsync(h->dfloor.p, h->floor_host.data(), sizeof(int) * batch, hipMemcpyHostToDevice, h->stream));
     CREATE_TRY(hipStreamSynchronize(h->stream));
   }
 #undef CREATE_TRY
+#undef CREATE_RES
   *out = h;
   return EKF_OK;
 }
@@ -520,8 +513,8 @@ extern "C" int ekf_destroy(ekf_handle* h) {
 static int refresh_sizes(ekf_handle* h) {
   if (!h->sizes_dirty) return EKF_OK;
   HIP_TRY(h, hipSetDevice(h->device));
-  HIP_TRY(h, hipMemcpyAsync(h->n.data(), h->dn, sizeof(int) * h->batch, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(h->neff.data(), h->dneff, sizeof(int) * h->batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->n.data(), h->dn.p, sizeof(int) * h->batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->neff.data(), h->dneff.p, sizeof(int) * h->batch, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   h->neff_enq = h->neff;
   h->sizes_dirty = false;
@@ -542,7 +535,7 @@ static int check_b(ekf_handle* h, int b, const char* fn) {
 // it: EKF_ERR_STATE.  b < 0: any trajectory.  Synchronises the handle's stream (the flags come back with a stream-ordered
 // copy into pinned memory, on that stream).
 static int check_internal(ekf_handle* h, int b, const char* fn) {
-  HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->dflags, sizeof(unsigned) * h->batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->h_flags.p, h->dflags.p, sizeof(unsigned) * h->batch, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   for (int t = (b < 0 ? 0 : b); t < (b < 0 ? h->batch : b + 1); ++t) {
     if (h->host_bad[t])
@@ -550,7 +543,7 @@ static int check_internal(ekf_handle* h, int b, const char* fn) {
                   std::string(fn) + ": an earlier call on this handle failed after part of its work had been enqueued; the "
                       "state of trajectory " + std::to_string(t) + " is undefined: upload it again (ekf_upload_state / "
                       "ekf_upload_state_diag)");
-    if (h->h_flags[t] & EKF_FLAG_INTERNAL)
+    if (h->h_flags.p[t] & EKF_FLAG_INTERNAL)
       return fail(h, EKF_ERR_STATE,
                   std::string(fn) + ": trajectory " + std::to_string(t) +
                       " carries EKF_FLAG_INTERNAL (a bounded wait inside a single-launch step timed out; the state is "
@@ -561,12 +554,12 @@ static int check_internal(ekf_handle* h, int b, const char* fn) {
 }
 // (an upload replaces mean and covariance of trajectory b entirely: the trajectory is good again)
 static int clear_internal(ekf_handle* h, int b) {
-  HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->dflags + b, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->h_flags.p, h->dflags.p + b, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  unsigned f = h->h_flags[0];
+  unsigned f = h->h_flags.p[0];
   if (f & EKF_FLAG_INTERNAL) {
     f &= ~EKF_FLAG_INTERNAL;
-    HIP_TRY(h, hipMemcpy(h->dflags + b, &f, sizeof(unsigned), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->dflags.p + b, &f, sizeof(unsigned), hipMemcpyHostToDevice));
   }
   h->host_bad[b] = 0;
   return EKF_OK;
@@ -616,7 +609,7 @@ static int query_begin(ekf_handle* h, const char* fn, int b0, int count, const c
 }
 // Room for the query's inputs and staged destinations; the inputs start at h->dquery.p.
 static int query_stage(ekf_handle* h, Query& q) {
-  if (int rc = h->dquery.reserve(h, h->stream, plan_staging(q.plan))) return rc;
+  RES_TRY(h, "the queries' staging buffer", h->dquery.reserve(plan_staging(q.plan), 0, h->stream));
   for (int i = 0; i < q.plan.ndst; ++i)
     if (q.plan.dst[i].staged) q.dev[i] = h->dquery.p + q.plan.dst[i].at;
   return EKF_OK;
@@ -627,18 +620,18 @@ static int query_end(ekf_handle* h, const char* fn, int b0, int count, const Que
   for (int i = 0; i < q.plan.ndst; ++i)
     if (q.plan.dst[i].staged)
       HIP_TRY(h, hipMemcpyAsync(q.host[i], q.dev[i], sizeof(double) * q.plan.dst[i].words, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->dflags, sizeof(unsigned) * h->batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->h_flags.p, h->dflags.p, sizeof(unsigned) * h->batch, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   for (int b = b0; b < b0 + count; ++b)
-    if (h->h_flags[b] & EKF_FLAG_INTERNAL) return check_internal(h, b, fn);
+    if (h->h_flags.p[b] & EKF_FLAG_INTERNAL) return check_internal(h, b, fn);
   return EKF_OK;
 }
 static PendingView pending_view(const ekf_handle* h, int b0, int count) {
-  return PendingView{h->dP, h->dV, h->dW, h->ddacc2[h->dcur], h->dmu2[h->cur], h->dn, h->dso, h->ld, h->pstride, b0, count,
+  return PendingView{h->dP.p, h->dV.p, h->dW.p, h->ddacc2[h->dcur].p, h->dmu2[h->cur].p, h->dn.p, h->dso.p, h->ld, h->pstride, b0, count,
                      pending_kb(h)};
 }
 
-static BankView bank_view(const ekf_handle* h) { return BankView{h->dP, h->dV, h->dW, h->dn, h->dso, h->dflags, h->dqueue, h->ld, h->pstride, h->batch}; }
+static BankView bank_view(const ekf_handle* h) { return BankView{h->dP.p, h->dV.p, h->dW.p, h->dn.p, h->dso.p, h->dflags.p, h->dqueue.p, h->ld, h->pstride, h->batch}; }
 // The halves of the double-buffered arrays a step's or a cadence's launches read and write; the enqueueing function flips cur,
 // dcur (and cpar) behind the step.  dmu2[cur] is the mean the step reads -- of cadence c: its landmark entries are the mean
 // before the cadence --, dmu2[cur ^ 1] the one it writes (the one cadence c's solve leaves the pose in); ddacc2[dcur] the
@@ -649,12 +642,12 @@ static BankView bank_view(const ekf_handle* h) { return BankView{h->dP, h->dV, h
 enum CadWhich { CAD_THIS = 0, CAD_NEXT = 1 };
 static StepBufs step_bufs(const ekf_handle* h, CadWhich which = CAD_THIS) {
   const int cur = h->cur ^ which, dcur = h->dcur ^ which, cpar = h->cpar ^ which;
-  return StepBufs{h->dmu2[cur], h->dmu2[cur ^ 1], h->ddacc2[dcur], h->ddacc2[dcur ^ 1], h->dcad2[cpar], h->dprow3[cpar ^ 1],
-                  h->dprow3[cpar]};
+  return StepBufs{h->dmu2[cur].p, h->dmu2[cur ^ 1].p, h->ddacc2[dcur].p, h->ddacc2[dcur ^ 1].p, h->dcad2[cpar].p, h->dprow3[cpar ^ 1].p,
+                  h->dprow3[cpar].p};
 }
 // Where a launch logs: ring row `slot` of the innovation log (positions from jbase on) and of the pose log.
-static InnovLog innov_log(const ekf_handle* h, long slot, int jbase) { return InnovLog{h->dinnov, h->dinnov_m, slot, h->innov_cap, jbase}; }
-static PoseLog pose_log(const ekf_handle* h, long slot) { return PoseLog{h->dpose, slot, h->pose_cap}; }
+static InnovLog innov_log(const ekf_handle* h, long slot, int jbase) { return InnovLog{h->dinnov.p, h->dinnov_m.p, slot, h->innov_cap, jbase}; }
+static PoseLog pose_log(const ekf_handle* h, long slot) { return PoseLog{h->dpose.p, slot, h->pose_cap}; }
 // The largest state of the bank: what sizes a launch's grid.  `device_grown` (the per-step paths, which ekf_step_detections
 // runs without reading the sizes back): while sizes_dirty only n_max bounds the states.  ekf_stream_run refreshes the sizes
 // before it plans its cadences from h->n, so its launches pass false and read h->n whatever the flag says.
@@ -664,7 +657,7 @@ static int bank_n_hi(const ekf_handle* h, bool device_grown) {
 
 static int set_size(ekf_handle* h, int b, int n) {
   h->n[b] = n;
-  HIP_TRY(h, hipMemcpyAsync(h->dn + b, &h->n[b], sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->dn.p + b, &h->n[b], sizeof(int), hipMemcpyHostToDevice, h->stream));
   return EKF_OK;
 }
 
@@ -683,7 +676,7 @@ static int push_floor(ekf_handle* h, bool exact) {
   }
   if (!need) return EKF_OK;
   for (int b = 0; b < h->batch; ++b) h->floor_host[b] = h->opt_active_bound ? h->neff[b] : h->n[b];
-  HIP_TRY(h, hipMemcpyAsync(h->dfloor, h->floor_host.data(), sizeof(int) * h->batch, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->dfloor.p, h->floor_host.data(), sizeof(int) * h->batch, hipMemcpyHostToDevice, h->stream));
   return EKF_OK;
 }
 
@@ -699,7 +692,7 @@ extern "C" int ekf_upload_state(ekf_handle* h, int b, const double* mu, const do
   constexpr int UP_ROWS = 512;
   for (int r0 = 0; r0 < n; r0 += UP_ROWS)
     HIP_TRY(h, copy_cov(h, b, const_cast<double*>(P) + (size_t)r0 * n + r0, n, r0, r0, std::min(UP_ROWS, n - r0), n - r0, true));
-  HIP_TRY(h, hipMemcpyAsync(h->dmu2[h->cur] + (size_t)b * h->ld, mu, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->dmu2[h->cur].p + (size_t)b * h->ld, mu, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
   if (int rc = set_size(h, b, n)) return rc;
   h->neff[b] = n;                                      // arbitrary dense covariance: everything is active
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -713,11 +706,11 @@ extern "C" int ekf_upload_state_diag(ekf_handle* h, int b, const double* mu, con
   HIP_TRY(h, hipSetDevice(h->device));
   if (int rc = flush_pending(h)) return rc;
   if (int rc = clear_internal(h, b)) return rc;
-  HIP_TRY(h, hipMemcpyAsync(h->dscratch, diagP, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-  launch_fill_diag(h->stream, h->dP + (size_t)b * h->pstride, h->ld, n, h->dscratch);
+  HIP_TRY(h, hipMemcpyAsync(h->dscratch.p, diagP, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+  launch_fill_diag(h->stream, h->dP.p + (size_t)b * h->pstride, h->ld, n, h->dscratch.p);
   HIP_TRY(h, hipGetLastError());
   h->neff[b] = 3;                                      // diagonal covariance: nothing is correlated yet
-  HIP_TRY(h, hipMemcpyAsync(h->dmu2[h->cur] + (size_t)b * h->ld, mu, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->dmu2[h->cur].p + (size_t)b * h->ld, mu, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
   if (int rc = set_size(h, b, n)) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return EKF_OK;
@@ -728,9 +721,9 @@ extern "C" int ekf_upload_state_diag(ekf_handle* h, int b, const double* mu, con
 // end, the sequence word the host polls.
 constexpr size_t PACK_WORDS = (size_t)PACK_SMALL_N * PACK_SMALL_N + PACK_SMALL_N + 4;
 static int pack_buffer(ekf_handle* h) {
-  if (h->h_pack) return EKF_OK;
-  HIP_TRY(h, hipHostMalloc(&h->h_pack, sizeof(double) * PACK_WORDS, hipHostMallocCoherent));
-  std::memset(h->h_pack, 0, sizeof(double) * PACK_WORDS);
+  if (h->h_pack.p) return EKF_OK;
+  RES_TRY(h, "the small-state download buffer", h->h_pack.ensure(PACK_WORDS));
+  std::memset(h->h_pack.p, 0, sizeof(double) * PACK_WORDS);
   return EKF_OK;
 }
 
@@ -740,7 +733,7 @@ static int materialize(ekf_handle* h, int b) {
   if (int rc = flush_pending(h)) return rc;
   if (h->sizes_dirty)
     if (int rc = refresh_sizes(h)) return rc;
-  launch_mirror(h->stream, h->dP + (size_t)b * h->pstride, h->dn + b, h->ld, h->pstride, 1, h->n[b]);
+  launch_mirror(h->stream, h->dP.p + (size_t)b * h->pstride, h->dn.p + b, h->ld, h->pstride, 1, h->n[b]);
   HIP_TRY(h, hipGetLastError());
   return EKF_OK;
 }
@@ -755,12 +748,12 @@ extern "C" int ekf_download_state(ekf_handle* h, int b, double* mu, double* P, i
     if (h->host_bad[b]) return check_internal(h, b, "ekf_download_state");
     if (int rc = flush_pending(h)) return rc;
     if (int rc = pack_buffer(h)) return rc;
-    launch_pack_small(h->stream, h->dP + (size_t)b * h->pstride, h->dmu2[h->cur] + (size_t)b * h->ld, h->dflags + b, h->ld, n, h->h_pack);
+    launch_pack_small(h->stream, h->dP.p + (size_t)b * h->pstride, h->dmu2[h->cur].p + (size_t)b * h->ld, h->dflags.p + b, h->ld, n, h->h_pack.p);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if ((unsigned)h->h_pack[(size_t)n * n + n] & EKF_FLAG_INTERNAL) return check_internal(h, b, "ekf_download_state");
-    std::memcpy(P, h->h_pack, sizeof(double) * (size_t)n * n);
-    std::memcpy(mu, h->h_pack + (size_t)n * n, sizeof(double) * n);
+    if ((unsigned)h->h_pack.p[(size_t)n * n + n] & EKF_FLAG_INTERNAL) return check_internal(h, b, "ekf_download_state");
+    std::memcpy(P, h->h_pack.p, sizeof(double) * (size_t)n * n);
+    std::memcpy(mu, h->h_pack.p + (size_t)n * n, sizeof(double) * n);
     return EKF_OK;
   }
   if (int rc = check_internal(h, b, "ekf_download_state")) return rc;
@@ -773,7 +766,7 @@ extern "C" int ekf_download_state(ekf_handle* h, int b, double* mu, double* P, i
     double* dst = pack ? static_cast<double*>(device_view(P)) : nullptr;
     if (dst) {
       if (int rc = flush_pending(h)) return rc;    // the covariance is P_base + pending ranks, upper triangle
-      launch_pack_dense(h->stream, h->dP + (size_t)b * h->pstride, h->ld, n, dst);
+      launch_pack_dense(h->stream, h->dP.p + (size_t)b * h->pstride, h->ld, n, dst);
       HIP_TRY(h, hipGetLastError());
       h->dense_packs += 1;
     } else {
@@ -782,7 +775,7 @@ extern "C" int ekf_download_state(ekf_handle* h, int b, double* mu, double* P, i
     }
   }
   if (mu)
-    HIP_TRY(h, hipMemcpyAsync(mu, h->dmu2[h->cur] + (size_t)b * h->ld, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(mu, h->dmu2[h->cur].p + (size_t)b * h->ld, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return EKF_OK;
 }
@@ -900,26 +893,23 @@ extern "C" int ekf_download_joint(ekf_handle* h, int b0, int count, const int* l
 // ---- the log rings: the pose log (ekf_pose_log.hip) and the innovation log (ekf_innovations.hip) ----
 // A ring is one or two device arrays of `capacity` step rows, `row_bytes` per (step, trajectory).  ring_resize replaces it by
 // an empty one (capacity 0: switches the log off); `cap` and `steps` are the log's capacity and its count of logged steps.
-struct RingArray { void** p; size_t row_bytes; };
-static int ring_resize(ekf_handle* h, const char* fn, int capacity, std::initializer_list<RingArray> arrays, int* cap,
-                       long long* steps) {
+// Each array is given as res::want(buffer, elements per (step, trajectory)).
+template <class... Bufs>
+static int ring_resize(ekf_handle* h, const char* fn, int capacity, int* cap, long long* steps, res::Want<Bufs>... arrays) {
   if (capacity < 0) return bad_arg(h, fn, "capacity must be >= 0");
   const size_t rows = (size_t)capacity * h->batch;
-  for (const RingArray& a : arrays)
-    if (rows * a.row_bytes > ((size_t)1 << 36)) return bad_arg(h, fn, "the ring would exceed 64 GiB");
+  if ((... || (rows * arrays.n * sizeof(*arrays.buf->p) > ((size_t)1 << 36)))) return bad_arg(h, fn, "the ring would exceed 64 GiB");
   HIP_TRY(h, hipSetDevice(h->device));
-  if (*arrays.begin()->p) HIP_TRY(h, hipStreamSynchronize(h->stream));   // (launches in flight still write the old ring)
-  for (const RingArray& a : arrays)
-    if (void* old = std::exchange(*a.p, nullptr)) HIP_TRY(h, hipFree(old));
+  // (launches in flight still write the old ring: release_group waits for the stream)
+  RES_TRY(h, fn, res::release_group<HipBackend>(h->stream, *arrays.buf...));
   *cap = 0;
   *steps = 0;
-  for (const RingArray& a : arrays)
-    if (capacity > 0 && hipMalloc(a.p, rows * a.row_bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      *a.p = nullptr;
-      (void)ring_resize(h, fn, 0, arrays, cap, steps);   // (frees what was allocated before it)
-      return fail(h, EKF_ERR_HIP, std::string(fn) + ": cannot allocate the ring of " + std::to_string(capacity) + " steps");
-    }
+  if (capacity == 0) return EKF_OK;
+  const res::Status st = res::ensure_group(nullptr, res::want(*arrays.buf, rows * arrays.n)...);
+  if (!st.ok()) {
+    (void)hipGetLastError();
+    return res_fail(h, (std::string(fn) + ": the ring of " + std::to_string(capacity) + " steps").c_str(), st);
+  }
   *cap = capacity;
   return EKF_OK;
 }
@@ -932,8 +922,7 @@ static int check_ring_range(ekf_handle* h, const char* fn, long long first, int 
 
 extern "C" int ekf_log_poses(ekf_handle* h, int capacity) {
   if (!h) return EKF_ERR_ARG;
-  return ring_resize(h, "ekf_log_poses", capacity, {{reinterpret_cast<void**>(&h->dpose), sizeof(double) * POSE_ROW}},
-                     &h->pose_cap, &h->pose_steps);
+  return ring_resize(h, "ekf_log_poses", capacity, &h->pose_cap, &h->pose_steps, res::want(h->dpose, POSE_ROW));
 }
 
 extern "C" int ekf_pose_steps(ekf_handle* h, long long* logged) {
@@ -945,7 +934,7 @@ extern "C" int ekf_pose_steps(ekf_handle* h, long long* logged) {
 // The block is returned exactly symmetric: its upper triangle, mirrored.
 extern "C" int ekf_download_poses(ekf_handle* h, long long first, int count, double* pose, double* cov) {
   if (!h) return EKF_ERR_ARG;
-  if (!h->dpose) return fail(h, EKF_ERR_STATE, "ekf_download_poses: the pose log is off (ekf_log_poses)");
+  if (!h->dpose.p) return fail(h, EKF_ERR_STATE, "ekf_download_poses: the pose log is off (ekf_log_poses)");
   if (int rc = check_ring_range(h, "ekf_download_poses", first, count, h->pose_steps, h->pose_cap)) return rc;
   if (count > 0 && !pose) return fail(h, EKF_ERR_ARG, "ekf_download_poses: NULL pose");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -954,7 +943,7 @@ extern "C" int ekf_download_poses(ekf_handle* h, long long first, int count, dou
   const RingPieces rp = ring_pieces(first, count, h->pose_cap);
   for (int i = 0; i < rp.n; ++i) {
     const RingPieces::Piece& c = rp.piece[i];
-    HIP_TRY(h, hipMemcpyAsync(hr.data() + c.done * B * POSE_ROW, h->dpose + c.slot * B * POSE_ROW, sizeof(double) * c.rows * B * POSE_ROW,
+    HIP_TRY(h, hipMemcpyAsync(hr.data() + c.done * B * POSE_ROW, h->dpose.p + c.slot * B * POSE_ROW, sizeof(double) * c.rows * B * POSE_ROW,
                               hipMemcpyDeviceToHost, h->stream));
   }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -970,9 +959,8 @@ extern "C" int ekf_download_poses(ekf_handle* h, long long first, int count, dou
 
 extern "C" int ekf_log_innovations(ekf_handle* h, int capacity) {
   if (!h) return EKF_ERR_ARG;
-  return ring_resize(h, "ekf_log_innovations", capacity,
-                     {{reinterpret_cast<void**>(&h->dinnov), sizeof(InnovRec) * AMAX}, {reinterpret_cast<void**>(&h->dinnov_m), sizeof(int)}},
-                     &h->innov_cap, &h->innov_steps);
+  return ring_resize(h, "ekf_log_innovations", capacity, &h->innov_cap, &h->innov_steps, res::want(h->dinnov, AMAX),
+                     res::want(h->dinnov_m, 1));
 }
 
 extern "C" int ekf_innovation_steps(ekf_handle* h, long long* logged) {
@@ -984,7 +972,7 @@ extern "C" int ekf_innovation_steps(ekf_handle* h, long long* logged) {
 // Steps [first, first + count) of the log: copies of their ring rows (one or two pieces each: the ring may wrap), behind
 // everything enqueued, into hm (count x batch counts) and hr (count x batch x AMAX entries).  Runs nothing else on the device.
 static int read_log(ekf_handle* h, long long first, int count, const char* fn, std::vector<int>& hm, std::vector<InnovRec>& hr) {
-  if (!h->dinnov) return fail(h, EKF_ERR_STATE, std::string(fn) + ": the innovation log is off (ekf_log_innovations)");
+  if (!h->dinnov.p) return fail(h, EKF_ERR_STATE, std::string(fn) + ": the innovation log is off (ekf_log_innovations)");
   if (int rc = check_ring_range(h, fn, first, count, h->innov_steps, h->innov_cap)) return rc;
   const int B = h->batch;
   hm.resize((size_t)count * B);
@@ -993,9 +981,9 @@ static int read_log(ekf_handle* h, long long first, int count, const char* fn, s
   const RingPieces rp = ring_pieces(first, count, h->innov_cap);
   for (int i = 0; i < rp.n; ++i) {
     const RingPieces::Piece& c = rp.piece[i];
-    HIP_TRY(h, hipMemcpyAsync(hm.data() + c.done * B, h->dinnov_m + c.slot * B, sizeof(int) * c.rows * B, hipMemcpyDeviceToHost,
+    HIP_TRY(h, hipMemcpyAsync(hm.data() + c.done * B, h->dinnov_m.p + c.slot * B, sizeof(int) * c.rows * B, hipMemcpyDeviceToHost,
                               h->stream));
-    HIP_TRY(h, hipMemcpyAsync(hr.data() + c.done * B * AMAX, h->dinnov + c.slot * B * AMAX, sizeof(InnovRec) * c.rows * B * AMAX,
+    HIP_TRY(h, hipMemcpyAsync(hr.data() + c.done * B * AMAX, h->dinnov.p + c.slot * B * AMAX, sizeof(InnovRec) * c.rows * B * AMAX,
                               hipMemcpyDeviceToHost, h->stream));
   }
   return check_internal(h, -1, fn);                    // (synchronises: the copies above are done)
@@ -1005,7 +993,7 @@ static int read_log(ekf_handle* h, long long first, int count, const char* fn, s
 extern "C" int ekf_download_innovations(ekf_handle* h, long long first, int count, int* m, int* idx, double* y, double* S,
                                         double* nis) {
   if (!h) return EKF_ERR_ARG;
-  if (count > 0 && !m && h->dinnov) return fail(h, EKF_ERR_ARG, "ekf_download_innovations: NULL m");
+  if (count > 0 && !m && h->dinnov.p) return fail(h, EKF_ERR_ARG, "ekf_download_innovations: NULL m");
   std::vector<int> hm;
   std::vector<InnovRec> hr;
   if (int rc = read_log(h, first, count, "ekf_download_innovations", hm, hr)) return rc;
@@ -1031,7 +1019,7 @@ extern "C" int ekf_download_innovations(ekf_handle* h, long long first, int coun
 
 extern "C" int ekf_download_innovation_rejections(ekf_handle* h, long long first, int count, int* rejected) {
   if (!h) return EKF_ERR_ARG;
-  if (count > 0 && !rejected && h->dinnov) return fail(h, EKF_ERR_ARG, "ekf_download_innovation_rejections: NULL rejected");
+  if (count > 0 && !rejected && h->dinnov.p) return fail(h, EKF_ERR_ARG, "ekf_download_innovation_rejections: NULL rejected");
   std::vector<int> hm;
   std::vector<InnovRec> hr;
   if (int rc = read_log(h, first, count, "ekf_download_innovation_rejections", hm, hr)) return rc;
@@ -1049,11 +1037,11 @@ extern "C" int ekf_set_nis_gate(ekf_handle* h, double threshold) {
     return fail(h, EKF_ERR_ARG, "ekf_set_nis_gate: the threshold must be > 0 (INFINITY: off)");
   HIP_TRY(h, hipSetDevice(h->device));
   const bool on = !std::isinf(threshold);
-  if (on && !h->dgate) HIP_TRY(h, hipMalloc(&h->dgate, sizeof(unsigned long long) * h->batch));
+  if (on) RES_TRY(h, "the NIS gate's counters", h->dgate.ensure((size_t)h->batch));
   // (stream-ordered behind every launch enqueued so far, which may still count rejections under the old threshold)
-  if (h->dgate) HIP_TRY(h, hipMemsetAsync(h->dgate, 0, sizeof(unsigned long long) * h->batch, h->stream));
+  if (h->dgate.p) HIP_TRY(h, hipMemsetAsync(h->dgate.p, 0, sizeof(unsigned long long) * h->batch, h->stream));
   h->dcfg.nis_gate = threshold;
-  h->dcfg.gate_rej = on ? h->dgate : nullptr;
+  h->dcfg.gate_rej = on ? h->dgate.p : nullptr;
   return EKF_OK;
 }
 
@@ -1104,20 +1092,13 @@ extern "C" int ekf_set_noise(ekf_handle* h, int b0, int count, const double* mot
     h->dcfg.noise = nullptr;
     return EKF_OK;
   }
-  const size_t bytes = sizeof(double) * rows.size();
-  if (!h->dnoise) {
-    HIP_TRY(h, hipMalloc(&h->dnoise, bytes));
-    HIP_TRY(h, hipHostMalloc(&h->hnoise_stage, bytes, hipHostMallocDefault));
-    HIP_TRY(h, hipEventCreateWithFlags(&h->noise_ev, hipEventDisableTiming));
-  }
   // (stream-ordered: launches enqueued before read the old rows, those enqueued after the new ones; every launch that reads
-  // the table is on h->stream)
-  if (h->noise_ev_used) HIP_TRY(h, hipEventSynchronize(h->noise_ev));   // (the previous upload out of the staging has run)
-  std::memcpy(h->hnoise_stage, rows.data(), bytes);
-  HIP_TRY(h, hipMemcpyAsync(h->dnoise, h->hnoise_stage, bytes, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipEventRecord(h->noise_ev, h->stream));
-  h->noise_ev_used = true;
-  h->dcfg.noise = h->dnoise;
+  // the table is on h->stream.  begin waits until the previous upload out of the pinned copy has run)
+  double* stage = nullptr;
+  RES_TRY(h, "the noise table", h->noise.begin(rows.size(), 0, h->stream, &stage));
+  std::memcpy(stage, rows.data(), sizeof(double) * rows.size());
+  RES_TRY(h, "the noise table's upload", h->noise.commit(rows.size(), h->stream));
+  h->dcfg.noise = h->noise.device();
   return EKF_OK;
 }
 
@@ -1136,8 +1117,8 @@ extern "C" int ekf_download_gate_counts(ekf_handle* h, int b0, int count, long l
   if (!rejected) return fail(h, EKF_ERR_ARG, "ekf_download_gate_counts: NULL rejected");
   HIP_TRY(h, hipSetDevice(h->device));
   std::vector<unsigned long long> hc((size_t)count, 0ull);
-  if (h->dgate)
-    HIP_TRY(h, hipMemcpyAsync(hc.data(), h->dgate + b0, sizeof(unsigned long long) * count, hipMemcpyDeviceToHost, h->stream));
+  if (h->dgate.p)
+    HIP_TRY(h, hipMemcpyAsync(hc.data(), h->dgate.p + b0, sizeof(unsigned long long) * count, hipMemcpyDeviceToHost, h->stream));
   if (int rc = check_internal(h, -1, "ekf_download_gate_counts")) return rc;   // (synchronises: the copy above is done)
   for (int b = 0; b < count; ++b) rejected[b] = (long long)hc[b];
   return EKF_OK;
@@ -1166,9 +1147,9 @@ extern "C" int ekf_add_landmarks(ekf_handle* h, int b, int first_index, const do
   HIP_TRY(h, hipSetDevice(h->device));
   if (int rc = flush_pending(h)) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));   // xy is staged through a single scratch buffer
-  HIP_TRY(h, hipMemcpyAsync(h->dscratch, xy, sizeof(double) * 2 * k, hipMemcpyHostToDevice, h->stream));
-  launch_add_landmarks(h->stream, h->dP + (size_t)b * h->pstride, h->dmu2[h->cur] + (size_t)b * h->ld, h->ld, n_old, n_new,
-                       h->cfg.landmark_init_var, h->dscratch);
+  HIP_TRY(h, hipMemcpyAsync(h->dscratch.p, xy, sizeof(double) * 2 * k, hipMemcpyHostToDevice, h->stream));
+  launch_add_landmarks(h->stream, h->dP.p + (size_t)b * h->pstride, h->dmu2[h->cur].p + (size_t)b * h->ld, h->ld, n_old, n_new,
+                       h->cfg.landmark_init_var, h->dscratch.p);
   HIP_TRY(h, hipGetLastError());
   if (int rc = set_size(h, b, n_new)) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1187,18 +1168,17 @@ extern "C" int ekf_remove_landmarks(ekf_handle* h, int b, const int* landmarks, 
   if (k == 0) return EKF_OK;
   HIP_TRY(h, hipSetDevice(h->device));
   if (int rc = check_internal(h, b, "ekf_remove_landmarks")) return rc;
-  if (!h->drm_tab) {
-    HIP_TRY(h, hipMalloc(&h->drm_tab, sizeof(int) * 2 * (size_t)h->ld));
-    HIP_TRY(h, hipMalloc(&h->drm_flag, sizeof(unsigned) * (size_t)h->ld * h->batch));
-    HIP_TRY(h, hipMemsetAsync(h->drm_flag, 0, sizeof(unsigned) * (size_t)h->ld * h->batch, h->stream));
-  }
+  bool rm_fresh;
+  RES_TRY(h, "ekf_remove_landmarks's tables",
+          res::ensure_group(&rm_fresh, res::want(h->drm_tab, 2 * (size_t)h->ld), res::want(h->drm_flag, (size_t)h->ld * h->batch)));
+  if (rm_fresh) HIP_TRY(h, hipMemsetAsync(h->drm_flag.p, 0, sizeof(unsigned) * (size_t)h->ld * h->batch, h->stream));
   if (int rc = flush_pending(h)) return rc;
   const size_t nt = rp.src.size();
-  HIP_TRY(h, hipMemcpyAsync(h->drm_tab, rp.src.data(), sizeof(int) * nt, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(h->drm_tab + h->ld, rp.dst.data(), sizeof(int) * nt, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->drm_tab.p, rp.src.data(), sizeof(int) * nt, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->drm_tab.p + h->ld, rp.dst.data(), sizeof(int) * nt, hipMemcpyHostToDevice, h->stream));
   h->rm_seq += 1;
   if (h->rm_seq == 0) h->rm_seq = 1;                   // (0 is what the announcements start at)
-  launch_remove(h->stream, bank_view(h), h->dmu2[h->cur], rp, h->drm_tab, h->drm_tab + h->ld, h->drm_flag, b0, nb, h->rm_seq);
+  launch_remove(h->stream, bank_view(h), h->dmu2[h->cur].p, rp, h->drm_tab.p, h->drm_tab.p + h->ld, h->drm_flag.p, b0, nb, h->rm_seq);
   HIP_TRY(h, hipGetLastError());
   // the active bound loses the removed indices below it; everything at or beyond it was, and still is, uncorrelated
   for (int t = b0; t < b0 + nb; ++t) {
@@ -1208,26 +1188,26 @@ extern "C" int ekf_remove_landmarks(ekf_handle* h, int b, const int* landmarks, 
     h->neff_enq[t] = h->neff[t];
     h->n[t] -= rp.k2;
   }
-  HIP_TRY(h, hipMemcpyAsync(h->dn, h->n.data(), sizeof(int) * h->batch, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->dn.p, h->n.data(), sizeof(int) * h->batch, hipMemcpyHostToDevice, h->stream));
   if (int rc = push_floor(h, true)) return rc;
   // the device tag table (removed tags: -1, seen again = new) and the last window's tags_positions record, renumbered
   std::vector<int> tm;
-  if (h->dtagmap) {
+  if (h->dtagmap.p) {
     tm.resize((size_t)TAGMAX * nb);
-    HIP_TRY(h, hipMemcpyAsync(tm.data(), h->dtagmap + (size_t)b0 * TAGMAX, sizeof(int) * tm.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(tm.data(), h->dtagmap.p + (size_t)b0 * TAGMAX, sizeof(int) * tm.size(), hipMemcpyDeviceToHost, h->stream));
   }
   std::vector<AssocOut> ao;
-  if (h->d_assoc_out) {
+  if (h->d_assoc_out.p) {
     ao.resize(nb);
-    HIP_TRY(h, hipMemcpyAsync(ao.data(), h->d_assoc_out + b0, sizeof(AssocOut) * nb, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(ao.data(), h->d_assoc_out.p + b0, sizeof(AssocOut) * nb, hipMemcpyDeviceToHost, h->stream));
   }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   auto renum = [&](int lm) { return lm < 0 || 3 + 2 * lm >= (int)rp.dst.size() ? lm : (rp.dst[3 + 2 * lm] < 0 ? -1 : (rp.dst[3 + 2 * lm] - 3) / 2); };
-  if (h->dtagmap) {
+  if (h->dtagmap.p) {
     for (int& v : tm) v = renum(v);
-    HIP_TRY(h, hipMemcpyAsync(h->dtagmap + (size_t)b0 * TAGMAX, tm.data(), sizeof(int) * tm.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->dtagmap.p + (size_t)b0 * TAGMAX, tm.data(), sizeof(int) * tm.size(), hipMemcpyHostToDevice, h->stream));
   }
-  if (h->d_assoc_out) {
+  if (h->d_assoc_out.p) {
     for (AssocOut& a : ao) {
       int m = 0;
       for (int i = 0; i < std::min(a.m, AMAX); ++i) {
@@ -1245,7 +1225,7 @@ extern "C" int ekf_remove_landmarks(ekf_handle* h, int b, const int* landmarks, 
       a.m = m;
       a.n_after = std::max(3, a.n_after - rp.k2);
     }
-    HIP_TRY(h, hipMemcpyAsync(h->d_assoc_out + b0, ao.data(), sizeof(AssocOut) * nb, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_assoc_out.p + b0, ao.data(), sizeof(AssocOut) * nb, hipMemcpyHostToDevice, h->stream));
   }
   if (h->stream_steps > 0) h->stream_stale = true;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1258,12 +1238,11 @@ static int prof_event(ekf_handle* h, hipEvent_t* ev, int cls = 0) {
     if (h->prof_cls.size() <= h->prof_used / 2) h->prof_cls.resize(h->prof_used / 2 + 1);
     h->prof_cls[h->prof_used / 2] = cls;
   }
-  if (h->prof_used == h->prof_pool.size()) {
-    hipEvent_t e;
-    HIP_TRY(h, hipEventCreate(&e));
-    h->prof_pool.push_back(e);
-  }
-  *ev = h->prof_pool[h->prof_used++];
+  if (h->prof_used == h->prof_pool.size()) h->prof_pool.emplace_back();
+  Event& e = h->prof_pool[h->prof_used];
+  RES_TRY(h, "a profiling event", e.ensure(true));
+  h->prof_used += 1;
+  *ev = e.ev;                                          // (the native handle: the pool may move its events when it grows)
   return EKF_OK;
 }
 // (diagnostic) an event pair around the launches between prof_open and prof_close on stream `st`, class `cls`
@@ -1298,25 +1277,20 @@ static int flush_pending(ekf_handle* h, hipStream_t st, const CadOut* wv) {
     if (std::memcmp(key, h->shares_key, sizeof key) != 0) {
       const size_t words = (size_t)h->cu_count * pass_share_pieces() * 4;
       const int nb = h->shares_cur ^ 1;
-      if (!h->dshares2[nb]) {
-        HIP_TRY(h, hipMalloc(&h->dshares2[nb], sizeof(int) * words));
-        HIP_TRY(h, hipHostMalloc(&h->hshares2[nb], sizeof(int) * words, hipHostMallocDefault));
-        std::memset(h->hshares2[nb], 0, sizeof(int) * words);
-        HIP_TRY(h, hipEventCreateWithFlags(&h->shares_ev[nb], hipEventDisableTiming));
-      }
       // (the pinned copy is free once its previous upload has been executed: two tables back, long ago)
-      if (h->shares_ev_used[nb]) HIP_TRY(h, hipEventSynchronize(h->shares_ev[nb]));
-      h->shares_ok = build_pass_shares(h->batch, p.e_hi, p.rs_workgroups, h->hshares2[nb]);
-      if (h->shares_ok > 0) order_pass_shares(p.rs_workgroups, pass_share_pieces(), h->hshares2[nb], words);
+      int* table = nullptr;
+      bool fresh;
+      RES_TRY(h, "the pass's share table", h->shares2[nb].begin(words, 0, st, &table, &fresh));
+      if (fresh) std::memset(table, 0, sizeof(int) * words);
+      h->shares_ok = build_pass_shares(h->batch, p.e_hi, p.rs_workgroups, table);
+      if (h->shares_ok > 0) order_pass_shares(p.rs_workgroups, pass_share_pieces(), table, words);
       // stream-ordered: the launch below, on the same stream, reads the table after the copy; the pass that read the
       // other table -- possibly still running on the handle's other stream -- is not touched
-      HIP_TRY(h, hipMemcpyAsync(h->dshares2[nb], h->hshares2[nb], sizeof(int) * words, hipMemcpyHostToDevice, st));
-      HIP_TRY(h, hipEventRecord(h->shares_ev[nb], st));
-      h->shares_ev_used[nb] = true;
+      RES_TRY(h, "the share table's upload", h->shares2[nb].commit(words, st));
       h->shares_cur = nb;
       std::memcpy(h->shares_key, key, sizeof key);
     }
-    if (h->shares_ok > 0) shares = h->dshares2[h->shares_cur];
+    if (h->shares_ok > 0) shares = h->shares2[h->shares_cur].device();
   }
   hipEvent_t e0 = nullptr, e1 = nullptr;
   // (profiling: every `profile_stride`-th launch of the pass is bracketed by an event pair -- a record costs its stream ~6 us)
@@ -1358,7 +1332,7 @@ extern "C" int ekf_update_direct(ekf_handle* h, int b0, int count, const int* ta
     if (int rc = check_internal(h, b, "ekf_update_direct")) return rc;
   const size_t B = (size_t)h->batch;
   const size_t int_words = (B * DIRECT_INTS + 1) / 2;  // layout (doubles): the plan (ints, rounded up), measurements, results
-  if (!h->ddirect) HIP_TRY(h, hipMalloc(&h->ddirect, sizeof(double) * (int_words + B * DIRECT_DBLS + 2 * B)));
+  RES_TRY(h, "ekf_update_direct's tables", h->ddirect.ensure(int_words + B * DIRECT_DBLS + 2 * B));
   if (int rc = flush_pending(h)) return rc;
   h->direct_ints.assign(B * DIRECT_INTS, 0);
   h->direct_dbls.assign(B * DIRECT_DBLS, 0.0);
@@ -1379,14 +1353,14 @@ extern "C" int ekf_update_direct(ekf_handle* h, int b0, int count, const int* ta
     pd[DIRECT_DBLS - 2] = gate ? gate[bi] : INFINITY;
   }
   if (dp.kpad > 0) {
-    int* dplan = reinterpret_cast<int*>(h->ddirect);
-    double* dmeas = h->ddirect + int_words;
+    int* dplan = reinterpret_cast<int*>(h->ddirect.p);
+    double* dmeas = h->ddirect.p + int_words;
     double* dout = dmeas + B * DIRECT_DBLS;
     HIP_TRY(h, hipMemcpyAsync(dplan, h->direct_ints.data(), sizeof(int) * h->direct_ints.size(), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(dmeas, h->direct_dbls.data(), sizeof(double) * h->direct_dbls.size(), hipMemcpyHostToDevice, h->stream));
     ProfBracket pb;
     if (int rc = prof_open(h, 4, h->stream, &pb)) return rc;
-    launch_direct(h->stream, direct_rows_cap(dp.kpad), bank_view(h), h->ddacc2[h->dcur], h->dmu2[h->cur], dplan, dmeas, dout, dp.kpad);
+    launch_direct(h->stream, direct_rows_cap(dp.kpad), bank_view(h), h->ddacc2[h->dcur].p, h->dmu2[h->cur].p, dplan, dmeas, dout, dp.kpad);
     if (int rc = prof_close(h, &pb)) return rc;
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(h->direct_out.data(), dout, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->stream));
@@ -1414,13 +1388,13 @@ static int enqueue_small(ekf_handle* h, const StepIn* d_in, int nsteps) {
   const int out_b = h->fetch_b;                        // (ekf_step_fetch, last pass of its step: see there)
   h->fetch_b = -1;
   // (this path writes the log itself, and applies the NIS gate and the noise table in the same instantiations)
-  const bool logged = h->dinnov && h->lg_slot >= 0;
+  const bool logged = h->dinnov.p && h->lg_slot >= 0;
   const InnovLog lg = logged ? innov_log(h, h->lg_slot, h->lg_jbase) : InnovLog{};
   // (the pose log likewise: every pass of a step writes the step's row, the last one last)
-  const bool posed = h->dpose && h->pl_slot >= 0;
+  const bool posed = h->dpose.p && h->pl_slot >= 0;
   const PoseLog plg = posed ? pose_log(h, h->pl_slot) : PoseLog{};
   SmallFetch fetch;
-  if (out_b >= 0) fetch = SmallFetch{h->h_pack, out_b, reinterpret_cast<unsigned long long*>(h->h_pack + PACK_WORDS - 1), ++h->fetch_seq};
+  if (out_b >= 0) fetch = SmallFetch{h->h_pack.p, out_b, reinterpret_cast<unsigned long long*>(h->h_pack.p + PACK_WORDS - 1), ++h->fetch_seq};
   if (launch_small_stream(h->stream, bank_view(h), step_bufs(h), d_in, nsteps, h->dcfg, n_hi, plan_small(h, n_hi), fetch,
                           logged || h->dcfg.gate_rej || h->dcfg.noise ? &lg : nullptr, posed ? &plg : nullptr) != 0)
     return fail(h, EKF_ERR_HIP, "small-state launch: hipFuncSetAttribute failed");
@@ -1431,10 +1405,10 @@ static int enqueue_small(ekf_handle* h, const StepIn* d_in, int nsteps) {
   return EKF_OK;
 }
 
-// The innovation log of a per-step pass: its records (h->dso) copied out right behind its solve, before the next solve reuses them.
+// The innovation log of a per-step pass: its records (h->dso.p) copied out right behind its solve, before the next solve reuses them.
 static void log_pass(ekf_handle* h, const StepIn* d_in) {
-  if (!h->dinnov || h->lg_slot < 0) return;
-  launch_innov_step(h->stream, d_in, h->dso, h->dcfg.enable_measurement_model, h->dcfg.gate_rej != nullptr, h->batch,
+  if (!h->dinnov.p || h->lg_slot < 0) return;
+  launch_innov_step(h->stream, d_in, h->dso.p, h->dcfg.enable_measurement_model, h->dcfg.gate_rej != nullptr, h->batch,
                     innov_log(h, h->lg_slot, h->lg_jbase));
 }
 
@@ -1442,7 +1416,7 @@ static void log_pass(ekf_handle* h, const StepIn* d_in) {
 // (k_pose_step: the new mean, P_base, the pending ranks and noise, as ekf_download_marginals reads them).  The small-state
 // path has written the row itself.
 static int log_pose_step(ekf_handle* h) {
-  if (!h->dpose || h->pl_slot < 0 || small_path(h)) return EKF_OK;
+  if (!h->dpose.p || h->pl_slot < 0 || small_path(h)) return EKF_OK;
   launch_pose_step(h->stream, pending_view(h, 0, h->batch), pose_log(h, h->pl_slot));
   HIP_TRY(h, hipGetLastError());
   return EKF_OK;
@@ -1457,7 +1431,7 @@ static int enqueue_pass(ekf_handle* h, const StepIn* d_in, int m_hi) {
   const StepBufs bufs = step_bufs(h);
   if (sp.form == STEP_PREDICT) {
     // prediction only, nothing pending: rows/cols 0,1 of P_base directly, O(n)
-    launch_solve(h->stream, bank, bufs, StepArgs{d_in, h->dfac, h->dfloor, 0}, h->dcfg);
+    launch_solve(h->stream, bank, bufs, StepArgs{d_in, h->dfac.p, h->dfloor.p, 0}, h->dcfg);
     launch_predict_rc(h->stream, bank, bufs, n_hi);
     log_pass(h, d_in);
     // k_predict_rc applied the noise itself (and nothing reads the pending-noise buffers while no rank is pending)
@@ -1467,15 +1441,15 @@ static int enqueue_pass(ekf_handle* h, const StepIn* d_in, int m_hi) {
   }
   if (sp.flush_before)
     if (int rc = flush_pending(h)) return rc;
-  StepArgs sa{d_in, h->dfac, h->dfloor, h->pending_k};
+  StepArgs sa{d_in, h->dfac.p, h->dfloor.p, h->pending_k};
   if (sp.form == STEP_SPLIT || sp.form == STEP_SPLIT_TP) {
-    sa.mbox = h->dmbox;                                // (the throughput shape's; k_step_split has none)
-    sa.ready = h->dready, sa.seq = ++h->step_seq, sa.publish = h->opt_fused_step == 1;
+    sa.mbox = h->dmbox.p;                                // (the throughput shape's; k_step_split has none)
+    sa.ready = h->dready.p, sa.seq = ++h->step_seq, sa.publish = h->opt_fused_step == 1;
     if (sp.form == STEP_SPLIT) launch_step_split(h->stream, sp.mcap, bank, bufs, sa, h->dcfg, n_hi);
     else launch_step_split_tp(h->stream, sp.mcap, bank, bufs, sa, h->dcfg, n_hi);
   } else {
     launch_solve(h->stream, bank, bufs, sa, h->dcfg);
-    launch_panels(h->stream, sp.mcap, sp.panels_latency, bank, bufs, h->dfac, n_hi);
+    launch_panels(h->stream, sp.mcap, sp.panels_latency, bank, bufs, h->dfac.p, n_hi);
   }
   log_pass(h, d_in);
   HIP_TRY(h, hipGetLastError());
@@ -1492,27 +1466,12 @@ static int enqueue_pass(ekf_handle* h, const StepIn* d_in, int m_hi) {
 static int upload_run_plan(ekf_handle* h) {
   const size_t count = h->run_plan.entries.size();
   const int nb = h->plan_cur ^ 1;
-  if (h->plan_cap2[nb] < count) {
-    const size_t cap = std::max(count, (size_t)64 * h->batch);
-    if (h->plan_ev_used[nb]) HIP_TRY(h, hipEventSynchronize(h->plan_ev[nb]));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));       // (kernels of an earlier run may still read the old device copy)
-    if (h->dplan2[nb]) HIP_TRY(h, hipFree(h->dplan2[nb]));
-    if (h->hplan2[nb]) HIP_TRY(h, hipHostFree(h->hplan2[nb]));
-    h->dplan2[nb] = nullptr;
-    h->hplan2[nb] = nullptr;
-    h->plan_cap2[nb] = 0;
-    HIP_TRY(h, hipMalloc(&h->dplan2[nb], sizeof(CadPlan) * cap));
-    HIP_TRY(h, hipHostMalloc(&h->hplan2[nb], sizeof(CadPlan) * cap, hipHostMallocDefault));
-    if (!h->plan_ev[nb]) HIP_TRY(h, hipEventCreateWithFlags(&h->plan_ev[nb], hipEventDisableTiming));
-    h->plan_cap2[nb] = cap;
-    h->plan_ev_used[nb] = false;
-  }
-  // (the pinned copy is free once its previous upload has been executed: two runs back)
-  if (h->plan_ev_used[nb]) HIP_TRY(h, hipEventSynchronize(h->plan_ev[nb]));
-  std::memcpy(h->hplan2[nb], h->run_plan.entries.data(), sizeof(CadPlan) * count);
-  HIP_TRY(h, hipMemcpyAsync(h->dplan2[nb], h->hplan2[nb], sizeof(CadPlan) * count, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipEventRecord(h->plan_ev[nb], h->stream));
-  h->plan_ev_used[nb] = true;
+  // (the pinned copy is free once its previous upload has been executed: two runs back.  A copy that is too small is replaced
+  //  once the stream is idle: kernels of an earlier run may still read the old device copy)
+  CadPlan* stage = nullptr;
+  RES_TRY(h, "the run plan", h->plan2[nb].begin(count, (size_t)64 * h->batch, h->stream, &stage));
+  std::memcpy(stage, h->run_plan.entries.data(), sizeof(CadPlan) * count);
+  RES_TRY(h, "the run plan's upload", h->plan2[nb].commit(count, h->stream));
   h->plan_cur = nb;
   return EKF_OK;
 }
@@ -1541,8 +1500,8 @@ static int upload_run_plan(ekf_handle* h) {
 // whatever is still running on the second stream is waited for by the handle's own stream
 static int join_aux(ekf_handle* h) {
   if (!h->aux_pass) return EKF_OK;
-  HIP_TRY(h, hipEventRecord(h->ev_pass, h->aux));      // (behind the last chained pass: one event per chain of cadences)
-  HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_pass, 0));
+  RES_TRY(h, "ev_pass", h->ev_pass.record(h->aux));    // (behind the last chained pass: one event per chain of cadences)
+  HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_pass.ev, 0));
   h->aux_pass = false;
   return EKF_OK;
 }
@@ -1550,8 +1509,8 @@ static int join_aux(ekf_handle* h) {
 // The innovation log of a cadence solve that used plan `dpl` and wrote `co` (on the handle's stream right behind it: the records
 // are read before the next solve into the same copy -- two solves later -- starts).
 static void log_cadence(ekf_handle* h, const CadPlan* dpl, const CadOut* co) {
-  if (!h->dinnov || h->lg_tslot < 0) return;
-  launch_innov_cad(h->stream, h->d_stream, dpl, co, h->dcfg.enable_measurement_model, h->dcfg.gate_rej != nullptr, h->batch,
+  if (!h->dinnov.p || h->lg_tslot < 0) return;
+  launch_innov_cad(h->stream, h->d_stream.p, dpl, co, h->dcfg.enable_measurement_model, h->dcfg.gate_rej != nullptr, h->batch,
                    innov_log(h, h->lg_tslot, 0));
 }
 
@@ -1560,11 +1519,9 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
   const RunPlan& rp = h->run_plan;
   // (the pose log: k_solve_cad_plog writes stream step t's row (pl_tslot + t) % pose_cap itself; nullptr: off)
   const PoseLog plg_on = pose_log(h, h->pl_tslot);
-  const PoseLog* plg = h->dpose && h->pl_tslot >= 0 ? &plg_on : nullptr;
+  const PoseLog* plg = h->dpose.p && h->pl_tslot >= 0 ? &plg_on : nullptr;
   const int n_hi = bank_n_hi(h, false);
-  const CadPlan* dpl = h->dplan2[h->plan_cur] + (size_t)c * h->batch;
-  for (int i = 0; i < 2; ++i)
-    if (!h->dcad2[i]) HIP_TRY(h, hipMalloc(&h->dcad2[i], sizeof(CadOut) * h->batch));
+  const CadPlan* dpl = h->plan2[h->plan_cur].device() + (size_t)c * h->batch;
   const BankView bank = bank_view(h);
   StepBufs cad = step_bufs(h, CAD_THIS);               // this cadence's buffers ...
   const StepBufs next = step_bufs(h, CAD_NEXT);        // ... and the next one's, for the solve enqueued ahead (chained, look-ahead)
@@ -1573,14 +1530,13 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
   for (int b = 0; b < h->batch; ++b) h->neff_enq[b] = rp.entries[(size_t)c * h->batch + b].neff;
   // what follows the panel launch is decided before anything is launched (chained: it goes to the second stream)
   CadStepPlan cp = plan_cadence_step(h, rp, c, n_hi, presolved);
-  if (cp.gather_cols && !h->dcolbuf && hipMalloc(&h->dcolbuf, sizeof(double) * (size_t)h->batch * CAD_CU * h->ld) != hipSuccess) {
+  if (cp.gather_cols && !h->dcolbuf.ensure((size_t)h->batch * CAD_CU * h->ld).ok()) {
     // (an optional optimisation: where its buffer cannot be had the panel launch gathers everything itself, bit-identically)
     (void)hipGetLastError();
-    h->dcolbuf = nullptr;
     h->opt_col_gather = 0;
     cp = plan_cadence_step(h, rp, c, n_hi, presolved);
   }
-  double* colbuf = cp.gather_cols ? h->dcolbuf : nullptr;
+  double* colbuf = cp.gather_cols ? h->dcolbuf.p : nullptr;
   if (!presolved) {
     if (int rc = join_aux(h)) return rc;
     ProfBracket pb;
@@ -1588,7 +1544,7 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     SolveCadArgs sx;
     sx.colbuf = colbuf, sx.col_wgs = cp.col_wgs;
     sx.chain = h->chain_run;
-    launch_solve_cad(h->stream, bank, cad, h->d_stream, dpl, h->dcfg, n_hi, sx, plg);
+    launch_solve_cad(h->stream, bank, cad, h->d_stream.p, dpl, h->dcfg, n_hi, sx, plg);
     if (int rc = prof_close(h, &pb)) return rc;
     log_cadence(h, dpl, cad.cad);
   }
@@ -1611,20 +1567,20 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     ProfBracket pbc, pbs;
     if (int rc2 = prof_open(h, 2, h->stream, &pbc)) return rc2;
     // the next cadence's inputs if an earlier chain launch formed them; the one after it: formed by this launch
-    const CadPre* pre_in = h->pre_serial[(serial + 1) & 1] == serial + 1 ? h->dpre[(serial + 1) & 1] : nullptr;
-    CadPre* pre_out = c + 2 < rp.ncad ? h->dpre[(serial + 2) & 1] : nullptr;
-    ChainArgs cx{h->dgbuf, h->dgmu, h->dxg, h->dbg, h->dsync};
+    const CadPre* pre_in = h->pre_serial[(serial + 1) & 1] == serial + 1 ? h->dpre[(serial + 1) & 1].p : nullptr;
+    CadPre* pre_out = c + 2 < rp.ncad ? h->dpre[(serial + 2) & 1].p : nullptr;
+    ChainArgs cx{h->dgbuf.p, h->dgmu.p, h->dxg.p, h->dbg.p, h->dsync.p};
     cx.sigma = h->sigma, cx.gather_target = h->gather_count, cx.gw = gw, cx.wait_pass = h->aux_pass;
     cx.pre_in = pre_in, cx.pre_out = pre_out, cx.plan2 = pre_out ? dpl2 + h->batch : nullptr;
-    launch_chain_cad(h->stream, bank, cad, h->d_stream, dpl2, h->dcfg, cx);
+    launch_chain_cad(h->stream, bank, cad, h->d_stream.p, dpl2, h->dcfg, cx);
     if (pre_out) h->pre_serial[(serial + 2) & 1] = serial + 2;
     if (int rc2 = prof_close(h, &pbc)) return rc2;
     if (int rc2 = prof_open(h, 1, h->stream, &pbs)) return rc2;
     SolveCadArgs sx;                                   // (block and mean from the chain launch: one part, no columns to gather)
-    sx.gbuf = h->dgbuf, sx.gparts = 1;
+    sx.gbuf = h->dgbuf.p, sx.gparts = 1;
     sx.chain = true;
-    sx.gmu = h->dgmu, sx.sync = h->dsync, sx.start_sigma = h->sigma, sx.pre = pre_in;
-    launch_solve_cad(h->stream, bank, next, h->d_stream, dpl2, h->dcfg, n_hi, sx, plg);
+    sx.gmu = h->dgmu.p, sx.sync = h->dsync.p, sx.start_sigma = h->sigma, sx.pre = pre_in;
+    launch_solve_cad(h->stream, bank, next, h->d_stream.p, dpl2, h->dcfg, n_hi, sx, plg);
     if (int rc2 = prof_close(h, &pbs)) return rc2;
     log_cadence(h, dpl2, next.cad);                    // (enqueued before the gate: it waits for nothing)
     // From here on the next cadence's solve overwrites the pose mean and the pending-noise buffer: a failure below cannot be
@@ -1633,9 +1589,9 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     if (hipGetLastError() != hipSuccess) rc = fail(h, EKF_ERR_HIP, "chained solves: launch of the next cadence's solve failed");
     // (a one-lane gate in front of the panel launch: ~5 us of the second stream, which has them to spare, and no workgroup of
     //  a large launch ever spins)
-    launch_gate(h->aux, h->dsync, h->sigma, h->dflags, h->batch);
+    launch_gate(h->aux, h->dsync.p, h->sigma, h->dflags.p, h->batch);
     pst = h->aux;
-    px.sync = h->dsync, px.tail_target = h->gather_count, px.start_sigma = h->sigma;
+    px.sync = h->dsync.p, px.tail_target = h->gather_count, px.start_sigma = h->sigma;
   } else if (int rc2 = join_aux(h)) {
     return rc2;
   }
@@ -1656,7 +1612,7 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
   if (chain_next) {
     // pass_c behind the panel launch on the second stream, then the mark the next chain launch's gather workgroups wait for
     if (rc == EKF_OK) rc = flush_pending(h, h->aux);
-    launch_mark(h->aux, h->dsync, h->sigma);
+    launch_mark(h->aux, h->dsync.p, h->sigma);
     if (hipGetLastError() != hipSuccess && rc == EKF_OK) rc = fail(h, EKF_ERR_HIP, "chained solves: launch of the mark failed");
     h->aux_pass = true;
     if (rc != EKF_OK) {
@@ -1681,27 +1637,27 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     if (wv) h->w_from_v_passes += 1;
     return flush_pending(h, nullptr, wv ? cad.cad : nullptr);
   }
-  if (!h->dgbuf) HIP_TRY(h, hipMalloc(&h->dgbuf, sizeof(double) * cadence_gbuf_doubles() * h->batch));
+  RES_TRY(h, "the look-ahead's block buffer", h->dgbuf.ensure((size_t)cadence_gbuf_doubles() * h->batch));
   // ---- look-ahead: gather (stream) -> { pass (second stream) | solve of the next cadence (stream) } -> join ----
   const int kb = pending_kb(h);
   {
     ProfBracket pb;
     if (int rc2 = prof_open(h, 2, h->stream, &pb)) return rc2;
-    launch_gather_cad(h->stream, bank, next.dacc_in, h->d_stream, dpl2, kb, h->dcfg, h->dgbuf);
+    launch_gather_cad(h->stream, bank, next.dacc_in, h->d_stream.p, dpl2, kb, h->dcfg, h->dgbuf.p);
     if (int rc2 = prof_close(h, &pb)) return rc2;
   }
   HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
-  HIP_TRY(h, hipStreamWaitEvent(h->aux, h->ev_fork, 0));
+  RES_TRY(h, "ev_fork", h->ev_fork.record(h->stream));
+  HIP_TRY(h, hipStreamWaitEvent(h->aux, h->ev_fork.ev, 0));
   // (the solve first: it is ready to go the moment the gather ends, the pass has an event to wait for -- the one
   //  workgroup per trajectory finds its CU before the pass fills the chip)
   {
     ProfBracket pb;
     if (int rc2 = prof_open(h, 1, h->stream, &pb)) return rc2;
     SolveCadArgs sx;                                   // (the block in the gather's parts; the mean is the handle's)
-    sx.gbuf = h->dgbuf, sx.gparts = (kb + 7) / 8;
+    sx.gbuf = h->dgbuf.p, sx.gparts = (kb + 7) / 8;
     sx.chain = h->chain_run;
-    launch_solve_cad(h->stream, bank, next, h->d_stream, dpl2, h->dcfg, n_hi, sx, plg);
+    launch_solve_cad(h->stream, bank, next, h->d_stream.p, dpl2, h->dcfg, n_hi, sx, plg);
     if (int rc2 = prof_close(h, &pb)) return rc2;
   }
   log_cadence(h, dpl2, next.cad);
@@ -1710,8 +1666,8 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
   // undefined (EKF_ERR_STATE from then on, until it is uploaded again).
   if (hipGetLastError() != hipSuccess) rc = fail(h, EKF_ERR_HIP, "look-ahead: launch of the next cadence's solve failed");
   if (rc == EKF_OK) rc = flush_pending(h, h->aux);
-  const hipError_t ej = hipEventRecord(h->ev_join, h->aux);
-  const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(h->stream, h->ev_join, 0) : ej;   // whatever follows on the handle's stream follows the pass
+  const hipError_t ej = (hipError_t)h->ev_join.record(h->aux).err;
+  const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(h->stream, h->ev_join.ev, 0) : ej;   // whatever follows on the handle's stream follows the pass
   if (rc == EKF_OK && ew != hipSuccess) rc = fail(h, EKF_ERR_HIP, std::string("look-ahead: joining the streams failed: ") + hipGetErrorString(ew));
   if (rc != EKF_OK) {
     (void)hipStreamSynchronize(h->aux);
@@ -1731,7 +1687,7 @@ static int ring_take(ekf_handle* h, int* slot) {
   h->ring_pos = (s + 1) % RING;
   if (s % RING_GROUP == 0) {
     if (h->ring_open[g]) HIP_TRY(h, hipStreamSynchronize(h->stream));   // (a failed call left the group without its event)
-    else if (h->ring_used[g]) HIP_TRY(h, hipEventSynchronize(h->ring_ev[g]));
+    else RES_TRY(h, "ring_ev", h->ring_ev[g].wait_if_recorded());
   }
   h->ring_open[g] = true;
   *slot = s;
@@ -1740,8 +1696,7 @@ static int ring_take(ekf_handle* h, int* slot) {
 static int ring_done(ekf_handle* h, int slot) {
   if (slot % RING_GROUP != RING_GROUP - 1) return EKF_OK;
   const int g = slot / RING_GROUP;
-  HIP_TRY(h, hipEventRecord(h->ring_ev[g], h->stream));
-  h->ring_used[g] = true;
+  RES_TRY(h, "ring_ev", h->ring_ev[g].record(h->stream));
   h->ring_open[g] = false;
   return EKF_OK;
 }
@@ -1782,15 +1737,15 @@ static int do_step(ekf_handle* h, int base_flags, const double* lin, const doubl
   HIP_TRY(h, hipSetDevice(h->device));
   if (int rc = push_floor(h, false)) return rc;
   const int passes = std::max(1, (m_hi + MMAX - 1) / MMAX);
-  const bool logged = h->dinnov && upd;                // (a lone prediction is not a logged step)
-  h->pl_slot = h->dpose ? (long)(h->pose_steps % h->pose_cap) : -1;   // (the pose log: every call is a row)
+  const bool logged = h->dinnov.p && upd;                // (a lone prediction is not a logged step)
+  h->pl_slot = h->dpose.p ? (long)(h->pose_steps % h->pose_cap) : -1;   // (the pose log: every call is a row)
   for (int p = 0; p < passes; ++p) {
     h->lg_slot = logged ? (long)(h->innov_steps % h->innov_cap) : -1;
     h->lg_jbase = MMAX * p;
     int slot;
     if (int rc = ring_take(h, &slot)) return rc;
-    StepIn* hs = h->h_ring + (size_t)slot * h->batch;
-    StepIn* ds = h->d_ring + (size_t)slot * h->batch;
+    StepIn* hs = h->h_ring.p + (size_t)slot * h->batch;
+    StepIn* ds = h->d_ring.p + (size_t)slot * h->batch;
     int flags = (upd ? FLAG_UPDATE : 0) | ((pred && p == 0) ? FLAG_PREDICT : 0);
     int m_pass_hi = 0;
     for (int b = 0; b < h->batch; ++b) {
@@ -1817,22 +1772,26 @@ static int do_step(ekf_handle* h, int base_flags, const double* lin, const doubl
   h->fetch_b = -1;
   if (logged) h->innov_steps += 1;
   if (int rc = log_pose_step(h)) return rc;
-  if (h->dpose) h->pose_steps += 1;
+  if (h->dpose.p) h->pose_steps += 1;
   return EKF_OK;
 }
 
 // ---- device-side association ------------------------------------------------------------------
 static int assoc_init(ekf_handle* h) {
-  if (h->dtagmap) return EKF_OK;
+  const size_t B = (size_t)h->batch;
+  auto with_group = [&](auto f) {
+    return f(res::want(h->dtagmap, TAGMAX * B), res::want(h->dneff, B), res::want(h->d_det, B * RING), res::want(h->h_det, B * RING),
+             res::want(h->d_assoc_step, B * 2),         // two update passes: the first 16 landmarks, the rest
+             res::want(h->d_assoc_out, B));
+  };
+  if (with_group([](auto... m) { return res::complete(m...); })) return EKF_OK;   // (every window comes through here)
   HIP_TRY(h, hipSetDevice(h->device));
-  HIP_TRY(h, hipMalloc(&h->dtagmap, sizeof(int) * TAGMAX * h->batch));
-  HIP_TRY(h, hipMemsetAsync(h->dtagmap, 0xFF, sizeof(int) * TAGMAX * h->batch, h->stream));   // -1
-  HIP_TRY(h, hipMalloc(&h->dneff, sizeof(int) * h->batch));
-  HIP_TRY(h, hipMalloc(&h->d_det, sizeof(DetIn) * h->batch * RING));
-  HIP_TRY(h, hipHostMalloc(&h->h_det, sizeof(DetIn) * h->batch * RING, hipHostMallocDefault));
-  HIP_TRY(h, hipMalloc(&h->d_assoc_step, sizeof(StepIn) * h->batch * 2));   // two update passes: the first 16 landmarks, the rest
-  HIP_TRY(h, hipMalloc(&h->d_assoc_out, sizeof(AssocOut) * h->batch));
-  HIP_TRY(h, hipMemsetAsync(h->d_assoc_out, 0, sizeof(AssocOut) * h->batch, h->stream));
+  bool fresh;
+  RES_TRY(h, "the device-side association's buffers", with_group([&](auto... m) { return res::ensure_group(&fresh, m...); }));
+  if (fresh) {
+    HIP_TRY(h, hipMemsetAsync(h->dtagmap.p, 0xFF, sizeof(int) * TAGMAX * h->batch, h->stream));   // -1
+    HIP_TRY(h, hipMemsetAsync(h->d_assoc_out.p, 0, sizeof(AssocOut) * h->batch, h->stream));
+  }
   return EKF_OK;
 }
 
@@ -1858,8 +1817,8 @@ extern "C" int ekf_step_detections(ekf_handle* h, const double* lin, const doubl
   int m_hi = 0;
   int slot;
   if (int rc = ring_take(h, &slot)) return rc;
-  DetIn* hs = h->h_det + (size_t)slot * h->batch;
-  DetIn* ds = h->d_det + (size_t)slot * h->batch;
+  DetIn* hs = h->h_det.p + (size_t)slot * h->batch;
+  DetIn* ds = h->d_det.p + (size_t)slot * h->batch;
   for (int b = 0; b < h->batch; ++b) {
     const int c = count[b];
     if (c < 0 || c > stride || c > DMAX) return fail(h, EKF_ERR_ARG, "ekf_step_detections: count must be <= min(stride, EKF_DMAX)");
@@ -1885,18 +1844,18 @@ extern "C" int ekf_step_detections(ekf_handle* h, const double* lin, const doubl
   }
   if (!h->cfg.enable_measurement_model) m_hi = 0;
   LogScope log_scope{h};
-  h->lg_slot = h->dinnov ? (long)(h->innov_steps % h->innov_cap) : -1;
-  h->pl_slot = h->dpose ? (long)(h->pose_steps % h->pose_cap) : -1;
+  h->lg_slot = h->dinnov.p ? (long)(h->innov_steps % h->innov_cap) : -1;
+  h->pl_slot = h->dpose.p ? (long)(h->pose_steps % h->pose_cap) : -1;
   // the host's view of the active bound must be on the device before the first device-side window
   if (!h->sizes_dirty)
-    HIP_TRY(h, hipMemcpyAsync(h->dneff, h->neff.data(), sizeof(int) * h->batch, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->dneff.p, h->neff.data(), sizeof(int) * h->batch, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(ds, hs, sizeof(DetIn) * h->batch, hipMemcpyHostToDevice, h->stream));
   if (int rc = ring_done(h, slot)) return rc;
   const int mcap = cap_for(std::min(m_hi, MMAX));
   if (((h->pending_k + ranks_for(mcap) + 3) & ~3) > KTOT)   // (what the step's kernels will write: see enqueue_pass)
     if (int rc = flush_pending(h)) return rc;
   h->acfg.active_bound = h->opt_active_bound;
-  launch_associate(h->stream, bank_view(h), ds, h->dtagmap, h->dneff, h->dmu2[h->cur], h->d_assoc_step, h->d_assoc_out, h->acfg,
+  launch_associate(h->stream, bank_view(h), ds, h->dtagmap.p, h->dneff.p, h->dmu2[h->cur].p, h->d_assoc_step.p, h->d_assoc_out.p, h->acfg,
                    h->n_max, h->pending_k);
   HIP_TRY(h, hipGetLastError());
   h->sizes_dirty = true;
@@ -1905,24 +1864,24 @@ extern "C" int ekf_step_detections(ekf_handle* h, const double* lin, const doubl
   // right when the gate leaves nothing (its ranks are zero)
   // (more than EKF_MMAX distinct tags in some trajectory's window: a second pass with the rest -- an update without a
   //  prediction; trajectories that had fewer find m = 0 there)
-  if (int rc = enqueue_pass(h, h->d_assoc_step, std::min(m_hi, MMAX))) return rc;
+  if (int rc = enqueue_pass(h, h->d_assoc_step.p, std::min(m_hi, MMAX))) return rc;
   h->lg_jbase = MMAX;
   if (m_hi > MMAX)
-    if (int rc = enqueue_pass(h, h->d_assoc_step + h->batch, m_hi - MMAX)) return rc;
-  if (h->dinnov) h->innov_steps += 1;
+    if (int rc = enqueue_pass(h, h->d_assoc_step.p + h->batch, m_hi - MMAX)) return rc;
+  if (h->dinnov.p) h->innov_steps += 1;
   if (int rc = log_pose_step(h)) return rc;
-  if (h->dpose) h->pose_steps += 1;
+  if (h->dpose.p) h->pose_steps += 1;
   return EKF_OK;
 }
 
 extern "C" int ekf_download_tags(ekf_handle* h, int b, int* m, int* idx, int* tag_id, double* xw, double* yw,
                                  double* err, double* range, double* bearing) {
   if (int rc = check_b(h, b, "ekf_download_tags")) return rc;
-  if (!h->d_assoc_out) return fail(h, EKF_ERR_STATE, "ekf_download_tags: no device-side association has run");
+  if (!h->d_assoc_out.p) return fail(h, EKF_ERR_STATE, "ekf_download_tags: no device-side association has run");
   HIP_TRY(h, hipSetDevice(h->device));
   if (int rc = check_internal(h, b, "ekf_download_tags")) return rc;
   AssocOut a;
-  HIP_TRY(h, hipMemcpyAsync(&a, h->d_assoc_out + b, sizeof(a), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(&a, h->d_assoc_out.p + b, sizeof(a), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   if (m) *m = a.m;
   for (int i = 0; i < AMAX; ++i) {
@@ -1944,7 +1903,7 @@ extern "C" int ekf_download_tag_index(ekf_handle* h, int b, int* tag_of_index, i
   HIP_TRY(h, hipSetDevice(h->device));
   if (int rc = check_internal(h, b, "ekf_download_tag_index")) return rc;
   std::vector<int> tm(TAGMAX);
-  HIP_TRY(h, hipMemcpyAsync(tm.data(), h->dtagmap + (size_t)b * TAGMAX, sizeof(int) * TAGMAX, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(tm.data(), h->dtagmap.p + (size_t)b * TAGMAX, sizeof(int) * TAGMAX, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   int count = 0;
   for (int id = 0; id < TAGMAX; ++id)
@@ -1966,7 +1925,7 @@ extern "C" int ekf_upload_tag_index(ekf_handle* h, int b, const int* tag_of_inde
     if (tag_of_index[i] < 0 || tag_of_index[i] >= TAGMAX) return fail(h, EKF_ERR_ARG, "ekf_upload_tag_index: tag id outside [0, 1024)");
     tm[tag_of_index[i]] = i;
   }
-  HIP_TRY(h, hipMemcpyAsync(h->dtagmap + (size_t)b * TAGMAX, tm.data(), sizeof(int) * TAGMAX, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->dtagmap.p + (size_t)b * TAGMAX, tm.data(), sizeof(int) * TAGMAX, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return EKF_OK;
 }
@@ -1992,7 +1951,7 @@ extern "C" int ekf_upload_tag_index(ekf_handle* h, int b, const int* tag_of_inde
 //   dfloor                 uploaded from the host's bound by push_floor below.
 //   dneff                  the device's copy of the bound: written from the host's before the next device-side window (the sizes
 //                          of both handles are refreshed first, so the host's are current).
-//   dnoise, dgate, dinnov, dinnov_m, dpose, d_stream and its host tables   the slot's noise row, gate counter, log rows and
+//   noise, dgate, dinnov, dinnov_m, dpose, d_stream and its host tables   the slot's noise row, gate counter, log rows and
 //                          uploaded inputs: NOT copied.  ekf_stream_run's stream_maxlm check decides whether the destination's
 //                          uploaded stream still fits; stream_stale is not set.
 // A source under EKF_FLAG_INTERNAL or host_bad is refused and a destination in that condition becomes good again -- the
@@ -2006,11 +1965,11 @@ extern "C" int ekf_copy_trajectories(ekf_handle* dst, const int* dst_b, ekf_hand
   if (k == 0) return EKF_OK;
   HIP_TRY(dst, hipSetDevice(dst->device));
   // (the source's flags, behind everything enqueued on its stream)
-  HIP_TRY(dst, hipMemcpyAsync(src->h_flags, src->dflags, sizeof(unsigned) * src->batch, hipMemcpyDeviceToHost, src->stream));
+  HIP_TRY(dst, hipMemcpyAsync(src->h_flags.p, src->dflags.p, sizeof(unsigned) * src->batch, hipMemcpyDeviceToHost, src->stream));
   HIP_TRY(dst, hipStreamSynchronize(src->stream));
   for (int g = 0; g < cp.groups; ++g) {
     const int s = cp.tab[(size_t)COPY_GROUP_WORDS * g];
-    if (src->host_bad[s] || (src->h_flags[s] & EKF_FLAG_INTERNAL))
+    if (src->host_bad[s] || (src->h_flags.p[s] & EKF_FLAG_INTERNAL))
       return fail(dst, EKF_ERR_STATE, "ekf_copy_trajectories: source trajectory " + std::to_string(s) +
                                           " is undefined (EKF_FLAG_INTERNAL, or an earlier call failed half way): upload it again");
   }
@@ -2019,29 +1978,29 @@ extern "C" int ekf_copy_trajectories(ekf_handle* dst, const int* dst_b, ekf_hand
     if (int rc = flush_pending(dst)) return rc;
   HIP_TRY(dst, hipStreamSynchronize(src->stream));
   if (src->aux) HIP_TRY(dst, hipStreamSynchronize(src->aux));
-  if (int rc = dst->dcp_tab.reserve(dst, dst->stream, cp.tab.size(), (size_t)(COPY_GROUP_WORDS + 1) * dst->batch)) return rc;
+  RES_TRY(dst, "ekf_copy_trajectories's table", dst->dcp_tab.reserve(cp.tab.size(), (size_t)(COPY_GROUP_WORDS + 1) * dst->batch, dst->stream));
   HIP_TRY(dst, hipMemcpyAsync(dst->dcp_tab.p, cp.tab.data(), sizeof(int) * cp.tab.size(), hipMemcpyHostToDevice, dst->stream));
   // (nontemporal stores unless EKFSLAM_HIP_COPY_NT=0: tools/copy_trajectories_time.py measures both, profiles/copy_trajectories.txt)
   bool nt = true;
   if (const char* e = std::getenv("EKFSLAM_HIP_COPY_NT")) nt = std::atoi(e) != 0;
-  launch_copy_traj(dst->stream, nt, bank_view(src), bank_view(dst), src->dmu2[src->cur], dst->dmu2[dst->cur], dst->dcp_tab.p,
+  launch_copy_traj(dst->stream, nt, bank_view(src), bank_view(dst), src->dmu2[src->cur].p, dst->dmu2[dst->cur].p, dst->dcp_tab.p,
                    cp.groups, cp.n_hi);
   HIP_TRY(dst, hipGetLastError());
   // the device tag table and the last window's tags: the source's, or "no window yet" where the source has never had one
-  if (src->dtagmap)
+  if (src->dtagmap.p)
     if (int rc = assoc_init(dst)) return rc;
   for (int g = 0; g < cp.groups; ++g) {
     const int* head = cp.tab.data() + (size_t)COPY_GROUP_WORDS * g;
     const int s = head[0];
     for (int q = 0; q < head[2]; ++q) {
       const int d = cp.tab[(size_t)COPY_GROUP_WORDS * cp.groups + head[1] + q];
-      if (src->dtagmap) {
-        HIP_TRY(dst, hipMemcpyAsync(dst->dtagmap + (size_t)d * TAGMAX, src->dtagmap + (size_t)s * TAGMAX, sizeof(int) * TAGMAX,
+      if (src->dtagmap.p) {
+        HIP_TRY(dst, hipMemcpyAsync(dst->dtagmap.p + (size_t)d * TAGMAX, src->dtagmap.p + (size_t)s * TAGMAX, sizeof(int) * TAGMAX,
                                     hipMemcpyDeviceToDevice, dst->stream));
-        HIP_TRY(dst, hipMemcpyAsync(dst->d_assoc_out + d, src->d_assoc_out + s, sizeof(AssocOut), hipMemcpyDeviceToDevice, dst->stream));
-      } else if (dst->dtagmap) {
-        HIP_TRY(dst, hipMemsetAsync(dst->dtagmap + (size_t)d * TAGMAX, 0xFF, sizeof(int) * TAGMAX, dst->stream));
-        HIP_TRY(dst, hipMemsetAsync(dst->d_assoc_out + d, 0, sizeof(AssocOut), dst->stream));
+        HIP_TRY(dst, hipMemcpyAsync(dst->d_assoc_out.p + d, src->d_assoc_out.p + s, sizeof(AssocOut), hipMemcpyDeviceToDevice, dst->stream));
+      } else if (dst->dtagmap.p) {
+        HIP_TRY(dst, hipMemsetAsync(dst->dtagmap.p + (size_t)d * TAGMAX, 0xFF, sizeof(int) * TAGMAX, dst->stream));
+        HIP_TRY(dst, hipMemsetAsync(dst->d_assoc_out.p + d, 0, sizeof(AssocOut), dst->stream));
       }
       dst->n[d] = src->n[s];
       dst->neff[d] = src->neff[s];
@@ -2092,7 +2051,7 @@ extern "C" int ekf_step_fetch(ekf_handle* h, const double* lin, const double* an
   if (h->opt_fetch_spin) {
     // poll the sequence word the kernel releases behind its stores (pinned, coherent); every few microseconds make sure the
     // stream is still busy -- a launch that failed would otherwise be waited for forever
-    const unsigned long long* word = reinterpret_cast<const unsigned long long*>(h->h_pack + PACK_WORDS - 1);
+    const unsigned long long* word = reinterpret_cast<const unsigned long long*>(h->h_pack.p + PACK_WORDS - 1);
     for (long spin = 1;; ++spin) {
       if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == h->fetch_seq) break;
       if ((spin & 4095) == 0) {
@@ -2108,10 +2067,10 @@ extern "C" int ekf_step_fetch(ekf_handle* h, const double* lin, const double* an
     // rests on the ordering of the kernel's posted writes (see k_small_stream).  Tripwire: the trailer's copy of the sequence
     // number, written by another wave; with "fetch_verify" also the XOR checksum over the whole payload.  A mismatch falls
     // back to waiting for the launch -- after which every write is visible -- and is counted.
-    const unsigned long long* trailer = reinterpret_cast<const unsigned long long*>(h->h_pack) + (size_t)n * n + n + 1;
+    const unsigned long long* trailer = reinterpret_cast<const unsigned long long*>(h->h_pack.p) + (size_t)n * n + n + 1;
     bool good = __atomic_load_n(trailer, __ATOMIC_ACQUIRE) == h->fetch_seq;
     if (good && h->opt_fetch_verify) {
-      const unsigned long long* w = reinterpret_cast<const unsigned long long*>(h->h_pack);
+      const unsigned long long* w = reinterpret_cast<const unsigned long long*>(h->h_pack.p);
       unsigned long long x = 0ull;
       for (size_t i = 0; i < (size_t)n * n + n + 1; ++i) x ^= w[i];
       good = x == trailer[1];
@@ -2123,9 +2082,9 @@ extern "C" int ekf_step_fetch(ekf_handle* h, const double* lin, const double* an
   } else {
     HIP_TRY(h, hipStreamSynchronize(h->stream));
   }
-  if ((unsigned)h->h_pack[(size_t)n * n + n] & EKF_FLAG_INTERNAL) return check_internal(h, b, "ekf_step_fetch");
-  std::memcpy(P, h->h_pack, sizeof(double) * (size_t)n * n);
-  std::memcpy(mu, h->h_pack + (size_t)n * n, sizeof(double) * n);
+  if ((unsigned)h->h_pack.p[(size_t)n * n + n] & EKF_FLAG_INTERNAL) return check_internal(h, b, "ekf_step_fetch");
+  std::memcpy(P, h->h_pack.p, sizeof(double) * (size_t)n * n);
+  std::memcpy(mu, h->h_pack.p + (size_t)n * n, sizeof(double) * n);
   return EKF_OK;
 }
 
@@ -2169,15 +2128,8 @@ extern "C" int ekf_stream_upload(ekf_handle* h, int steps, const double* lin, co
       for (int i = 0; i < mb; ++i) h->stream_maxlm[b] = std::max(h->stream_maxlm[b], host[e].idx[i] + 1);
     }
   HIP_TRY(h, hipSetDevice(h->device));
-  if (h->stream_cap < count) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->d_stream) HIP_TRY(h, hipFree(h->d_stream));
-    h->d_stream = nullptr;
-    h->stream_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->d_stream, sizeof(StepIn) * count));
-    h->stream_cap = count;
-  }
-  HIP_TRY(h, hipMemcpyAsync(h->d_stream, host.data(), sizeof(StepIn) * count, hipMemcpyHostToDevice, h->stream));
+  RES_TRY(h, "the uploaded stream", h->d_stream.reserve(count, 0, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->d_stream.p, host.data(), sizeof(StepIn) * count, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));      // inputs are resident in HBM from here on
   h->stream_steps = steps;
   h->stream_stale = false;
@@ -2201,24 +2153,24 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
   // (innovation log: stream step t goes to ring row (lg_tslot + t) % innov_cap, i.e. step `first` to row innov_steps)
   LogScope log_scope{h};
   const long cap = h->innov_cap;
-  if (h->dinnov) h->lg_tslot = (long)(((h->innov_steps - first) % cap + cap) % cap);
+  if (h->dinnov.p) h->lg_tslot = (long)(((h->innov_steps - first) % cap + cap) % cap);
   const long pcap = h->pose_cap;                       // (the pose log: the same numbering on its own counter)
-  if (h->dpose) h->pl_tslot = (long)(((h->pose_steps - first) % pcap + pcap) % pcap);
+  if (h->dpose.p) h->pl_tslot = (long)(((h->pose_steps - first) % pcap + pcap) % pcap);
   auto log_at = [&](int k) {
-    h->lg_slot = h->dinnov ? (h->lg_tslot + k) % cap : -1;
-    h->pl_slot = h->dpose ? (h->pl_tslot + k) % pcap : -1;
+    h->lg_slot = h->dinnov.p ? (h->lg_tslot + k) % cap : -1;
+    h->pl_slot = h->dpose.p ? (h->pl_tslot + k) % pcap : -1;
   };
   if (small_path(h) && count > 0) {
     // the whole range as ONE launch (in pieces of 4096 steps: a bounded kernel), P resident in LDS across all its steps
     for (int k = first; k < first + count; k += 4096) {
       log_at(k);
-      if (int rc = enqueue_small(h, h->d_stream + (size_t)k * h->batch, std::min(4096, first + count - k))) return rc;
+      if (int rc = enqueue_small(h, h->d_stream.p + (size_t)k * h->batch, std::min(4096, first + count - k))) return rc;
     }
     for (int b = 0; b < h->batch; ++b)
       h->neff[b] = std::max(h->neff[b], std::min(h->n[b], h->stream_own[(size_t)(first + count - 1) * h->batch + b]));
     h->neff_enq = h->neff;
-    if (h->dinnov) h->innov_steps += count;
-    if (h->dpose) h->pose_steps += count;
+    if (h->dinnov.p) h->innov_steps += count;
+    if (h->dpose.p) h->pose_steps += count;
     return EKF_OK;
   }
   for (int k = first; k < first + count;) {
@@ -2235,26 +2187,27 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
       // chained solves: decided per piece; whether a cadence is chained to the next is decided where the pass between them
       // is planned (plan_cadence_step)
       h->chain_run = plan_chain_run(h, h->run_plan.ncad);
-      if (h->chain_run) {
+      // (everything a cadence touches exists before the piece's first launch: between the enqueue of a chained launch that
+      //  waits on a device-side counter and the enqueue of the launch that advances it the host must not block -- an
+      //  allocation may.  The chained set is one group; it shares the records and the block buffer with the look-ahead's
+      //  set, whose block buffer is allocated where a look-ahead first runs: enqueue_cadence.)
+      const size_t B = (size_t)h->batch;
+      if (!h->chain_run) {
+        RES_TRY(h, "the cadence records", res::ensure_group(nullptr, res::want(h->dcad2[0], B), res::want(h->dcad2[1], B)));
+      } else {
         const int n_hi = bank_n_hi(h, false);
-        for (int i = 0; i < 2; ++i)
-          if (!h->dprow3[i]) HIP_TRY(h, hipMalloc(&h->dprow3[i], sizeof(double) * 3 * (size_t)h->ld * h->batch));
-        if (!h->dxg) {
-          const size_t gw = sizeof(double) * (size_t)h->batch * 84 * 88;
-          HIP_TRY(h, hipMalloc(&h->dxg, gw));
-          HIP_TRY(h, hipMalloc(&h->dbg, gw));
-          HIP_TRY(h, hipMalloc(&h->dsync, sizeof(unsigned) * chain_sync_words()));
-          HIP_TRY(h, hipMemsetAsync(h->dsync, 0, sizeof(unsigned) * chain_sync_words(), h->stream));
+        const size_t gw = B * 84 * 88;
+        bool fresh;
+        RES_TRY(h, "the chained run's buffers",
+                res::ensure_group(&fresh, res::want(h->dcad2[0], B), res::want(h->dcad2[1], B),
+                                  res::want(h->dgbuf, (size_t)cadence_gbuf_doubles() * B),
+                                  res::want(h->dprow3[0], 3 * (size_t)h->ld * B), res::want(h->dprow3[1], 3 * (size_t)h->ld * B),
+                                  res::want(h->dxg, gw), res::want(h->dbg, gw), res::want(h->dsync, (size_t)chain_sync_words()),
+                                  res::want(h->dpre[0], B), res::want(h->dpre[1], B), res::want(h->dgmu, 128 * B)));
+        if (fresh) {
+          HIP_TRY(h, hipMemsetAsync(h->dsync.p, 0, sizeof(unsigned) * chain_sync_words(), h->stream));
           HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the second stream's launches read the counters too)
         }
-        // (everything a chained cadence touches exists before its first launch: between the enqueue of a launch that waits on a
-        //  device-side counter and the enqueue of the launch that advances it the host must not block -- an allocation may)
-        if (!h->dgbuf) HIP_TRY(h, hipMalloc(&h->dgbuf, sizeof(double) * cadence_gbuf_doubles() * h->batch));
-        for (int i = 0; i < 2; ++i) {
-          if (!h->dcad2[i]) HIP_TRY(h, hipMalloc(&h->dcad2[i], sizeof(CadOut) * h->batch));
-          if (!h->dpre[i]) HIP_TRY(h, hipMalloc(&h->dpre[i], sizeof(CadPre) * h->batch));
-        }
-        if (!h->dgmu) HIP_TRY(h, hipMalloc(&h->dgmu, sizeof(double) * 128 * h->batch));
         // the pose rows "before the first cadence": where the previous cadence's panel launch would have left them
         launch_snap_pose(h->stream, bank_view(h), n_hi, step_bufs(h).prow3_in);
         HIP_TRY(h, hipGetLastError());
@@ -2271,12 +2224,12 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
     for (int b = 0; b < h->batch; ++b)
       h->neff_enq[b] = std::min(h->n[b], std::max(h->floor_host[b], h->stream_own[(size_t)k * h->batch + b]));
     log_at(k);
-    if (int rc = enqueue_pass(h, h->d_stream + (size_t)k * h->batch, h->stream_mhi[k])) return rc;
+    if (int rc = enqueue_pass(h, h->d_stream.p + (size_t)k * h->batch, h->stream_mhi[k])) return rc;
     if (int rc = log_pose_step(h)) return rc;
     ++k;
   }
-  if (h->dinnov) h->innov_steps += count;
-  if (h->dpose) h->pose_steps += count;
+  if (h->dinnov.p) h->innov_steps += count;
+  if (h->dpose.p) h->pose_steps += count;
   if (count > 0)
     for (int b = 0; b < h->batch; ++b)
       h->neff[b] = std::max(h->neff[b], std::min(h->n[b], h->stream_own[(size_t)(first + count - 1) * h->batch + b]));
@@ -2304,15 +2257,13 @@ extern "C" int ekf_predict_dense(ekf_handle* h, int b, const double* F, const do
   const size_t bytes = sizeof(double) * (size_t)h->rows * h->ld;
   HIP_TRY(h, hipSetDevice(h->device));
   if (int rc = materialize(h, b)) return rc;           // the product needs the full matrix
-  if (!h->dF) {
-    HIP_TRY(h, hipMalloc(&h->dF, bytes));
-    HIP_TRY(h, hipMalloc(&h->dQ, bytes));
-    HIP_TRY(h, hipMalloc(&h->dTmp, bytes));
-  }
-  HIP_TRY(h, hipMemsetAsync(h->dF, 0, bytes, h->stream));
-  HIP_TRY(h, hipMemcpy2DAsync(h->dF, sizeof(double) * h->ld, F, sizeof(double) * n, sizeof(double) * n, n,
+  const size_t words = (size_t)h->rows * h->ld;
+  RES_TRY(h, "the dense product's operands",
+          res::ensure_group(nullptr, res::want(h->dF, words), res::want(h->dQ, words), res::want(h->dTmp, words)));
+  HIP_TRY(h, hipMemsetAsync(h->dF.p, 0, bytes, h->stream));
+  HIP_TRY(h, hipMemcpy2DAsync(h->dF.p, sizeof(double) * h->ld, F, sizeof(double) * n, sizeof(double) * n, n,
                               hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpy2DAsync(h->dQ, sizeof(double) * h->ld, Q, sizeof(double) * n, sizeof(double) * n, n,
+  HIP_TRY(h, hipMemcpy2DAsync(h->dQ.p, sizeof(double) * h->ld, Q, sizeof(double) * n, sizeof(double) * n, n,
                               hipMemcpyHostToDevice, h->stream));
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (h->profile) {
@@ -2323,15 +2274,15 @@ extern "C" int ekf_predict_dense(ekf_handle* h, int b, const double* F, const do
   h->neff[b] = n;                                      // a general F correlates everything
   // the product works on plain row-major matrices: a covariance kept in column panels (ld > 4096) goes through a
   // row-major copy (device to device, one 2-D copy per panel each way; 4 n^3 flop dwarf it)
-  double* Pdense = h->dP + (size_t)b * h->pstride;
+  double* Pdense = h->dP.p + (size_t)b * h->pstride;
   if (p_panels(h->ld) > 1) {
-    if (!h->dPlin) HIP_TRY(h, hipMalloc(&h->dPlin, bytes));
-    HIP_TRY(h, copy_cov(h, b, h->dPlin, h->ld, 0, 0, n, n, false, true));
-    Pdense = h->dPlin;
+    RES_TRY(h, "the dense product's row-major staging", h->dPlin.ensure(words));
+    HIP_TRY(h, copy_cov(h, b, h->dPlin.p, h->ld, 0, 0, n, n, false, true));
+    Pdense = h->dPlin.p;
   }
-  if (dense_propagate(h->stream, Pdense, h->dTmp, h->dF, h->dQ, n, h->ld) != 0)
+  if (dense_propagate(h->stream, Pdense, h->dTmp.p, h->dF.p, h->dQ.p, n, h->ld) != 0)
     return fail(h, EKF_ERR_HIP, "ekf_predict_dense: launch failed");
-  if (p_panels(h->ld) > 1) HIP_TRY(h, copy_cov(h, b, h->dPlin, h->ld, 0, 0, n, n, true, true));
+  if (p_panels(h->ld) > 1) HIP_TRY(h, copy_cov(h, b, h->dPlin.p, h->ld, 0, 0, n, n, true, true));
   if (h->profile) HIP_TRY(h, hipEventRecord(e1, h->stream));
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2354,7 +2305,7 @@ extern "C" int ekf_status_flags(ekf_handle* h, int b, unsigned* flags) {
   if (int rc = check_b(h, b, "ekf_status_flags")) return rc;
   if (!flags) return fail(h, EKF_ERR_ARG, "ekf_status_flags: NULL");
   HIP_TRY(h, hipSetDevice(h->device));
-  HIP_TRY(h, hipMemcpyAsync(flags, h->dflags + b, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(flags, h->dflags.p + b, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return EKF_OK;
 }
@@ -2362,17 +2313,17 @@ extern "C" int ekf_status_flags(ekf_handle* h, int b, unsigned* flags) {
 extern "C" int ekf_timer_begin(ekf_handle* h) {
   if (!h) return EKF_ERR_ARG;
   HIP_TRY(h, hipSetDevice(h->device));
-  HIP_TRY(h, hipEventRecord(h->t0, h->stream));
+  RES_TRY(h, "t0", h->t0.record(h->stream));
   return EKF_OK;
 }
 
 extern "C" int ekf_timer_end(ekf_handle* h, double* elapsed_ms) {
   if (!h || !elapsed_ms) return EKF_ERR_ARG;
   HIP_TRY(h, hipSetDevice(h->device));
-  HIP_TRY(h, hipEventRecord(h->t1, h->stream));
-  HIP_TRY(h, hipEventSynchronize(h->t1));
+  RES_TRY(h, "t1", h->t1.record(h->stream));
+  RES_TRY(h, "t1", h->t1.wait_if_recorded());
   float ms = 0.f;
-  HIP_TRY(h, hipEventElapsedTime(&ms, h->t0, h->t1));
+  HIP_TRY(h, hipEventElapsedTime(&ms, h->t0.ev, h->t1.ev));
   *elapsed_ms = ms;
   return EKF_OK;
 }
@@ -2387,9 +2338,9 @@ extern "C" int ekf_profile_enable(ekf_handle* h, int on) {
   // (the events a run will use exist before it starts: creating one inside the run costs the host tens of microseconds)
   if (h->profile)
     while (h->prof_pool.size() < (h->opt_profile_kernels ? 1024u : 128u)) {
-      hipEvent_t e;
-      HIP_TRY(h, hipEventCreate(&e));
-      h->prof_pool.push_back(e);
+      Event e;
+      RES_TRY(h, "a profiling event", e.ensure(true));
+      h->prof_pool.push_back(std::move(e));
     }
   return EKF_OK;
 }
@@ -2404,7 +2355,7 @@ extern "C" int ekf_profile_read(ekf_handle* h, double* pass_ms_total, long long*
   for (size_t i = 0; i + 1 < h->prof_used; i += 2) {
     if (h->prof_cls[i / 2] != 0) continue;
     float ms = 0.f;
-    HIP_TRY(h, hipEventElapsedTime(&ms, h->prof_pool[i], h->prof_pool[i + 1]));
+    HIP_TRY(h, hipEventElapsedTime(&ms, h->prof_pool[i].ev, h->prof_pool[i + 1].ev));
     total += ms;
     count += 1;
   }
@@ -2426,7 +2377,7 @@ extern "C" int ekf_profile_read_class(ekf_handle* h, int cls, double* ms_total, 
   for (size_t i = 0; i + 1 < h->prof_used; i += 2) {
     if (h->prof_cls[i / 2] != cls) continue;
     float ms = 0.f;
-    HIP_TRY(h, hipEventElapsedTime(&ms, h->prof_pool[i], h->prof_pool[i + 1]));
+    HIP_TRY(h, hipEventElapsedTime(&ms, h->prof_pool[i].ev, h->prof_pool[i + 1].ev));
     total += ms;
     count += 1;
   }
@@ -2475,10 +2426,10 @@ extern "C" long ekf_debug_fetch_retries(ekf_handle* h) { return h ? h->fetch_ret
 
 // (diagnostics section of the header) the fused cadence's record of trajectory b (head + per-landmark records)
 extern "C" long ekf_debug_cad(ekf_handle* h, int b, void* dst, long bytes) {
-  if (!h || b < 0 || b >= h->batch || !h->dcad2[h->cpar ^ 1]) return -1;
+  if (!h || b < 0 || b >= h->batch || !h->dcad2[h->cpar ^ 1].p) return -1;
   if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return -1;
   const long have = (long)sizeof(CadOut);
-  if (dst && bytes > 0 && hipMemcpy(dst, h->dcad2[h->cpar ^ 1] + b, (size_t)std::min(bytes, have), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (dst && bytes > 0 && hipMemcpy(dst, h->dcad2[h->cpar ^ 1].p + b, (size_t)std::min(bytes, have), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   return have;
 }
 
@@ -2491,13 +2442,13 @@ extern "C" long ekf_debug_snapshot(ekf_handle* h, int b, int which, double* dst,
   const double* src = nullptr;
   long have = 0;
   switch (which) {
-    case 0: src = h->dP + (size_t)b * h->pstride; have = h->pstride; break;
-    case 1: src = h->dV + (size_t)b * KTOT * h->ld; have = (long)KTOT * h->ld; break;
-    case 2: src = h->dW + (size_t)b * KTOT * h->ld; have = (long)KTOT * h->ld; break;
-    case 3: src = h->dmu2[h->cur] + (size_t)b * h->ld; have = h->ld; break;
-    case 6: src = h->dgbuf ? h->dgbuf + (size_t)b * 84 * 88 : nullptr; have = h->dgbuf ? 84L * 88 : 0; break;   // (chained solves: the last chained block of trajectory b, 84 x 88)
-    case 5: src = h->dgmu; have = h->dgmu ? 128L * h->batch : 0; break;   // (chained solves: the means at the positions, all trajectories)
-    default: src = h->dmu2[h->cur ^ 1] + (size_t)b * h->ld; have = h->ld; break;
+    case 0: src = h->dP.p + (size_t)b * h->pstride; have = h->pstride; break;
+    case 1: src = h->dV.p + (size_t)b * KTOT * h->ld; have = (long)KTOT * h->ld; break;
+    case 2: src = h->dW.p + (size_t)b * KTOT * h->ld; have = (long)KTOT * h->ld; break;
+    case 3: src = h->dmu2[h->cur].p + (size_t)b * h->ld; have = h->ld; break;
+    case 6: src = h->dgbuf.p ? h->dgbuf.p + (size_t)b * 84 * 88 : nullptr; have = h->dgbuf.p ? 84L * 88 : 0; break;   // (chained solves: the last chained block of trajectory b, 84 x 88)
+    case 5: src = h->dgmu.p; have = h->dgmu.p ? 128L * h->batch : 0; break;   // (chained solves: the means at the positions, all trajectories)
+    default: src = h->dmu2[h->cur ^ 1].p + (size_t)b * h->ld; have = h->ld; break;
   }
   if (dst && count > 0 &&
       hipMemcpy(dst, src, sizeof(double) * (size_t)std::min(count, have), hipMemcpyDeviceToHost) != hipSuccess)

@@ -255,7 +255,14 @@ def test_every_entry_point_selects_its_device():
         bodies[mt.group(1)] = (mt.group(0).startswith("extern"), mt.group(2), text[mt.end():i])
     exported = {k for k, v in bodies.items() if v[0] and "ekf_handle* h" in v[1]}
     assert {"ekf_step", "ekf_stream_run", "ekf_download_tags", "ekf_set_option", "ekf_flush"} <= exported
-    gpu = re.compile(r"\bhip(?!SetDevice)[A-Z]\w*\s*\(|\blaunch_\w+\s*\(|\bdense_propagate\s*\(")
+    # (device work: a runtime call, a launcher, or an allocating, uploading or event method of the ownership types of
+    #  csrc/ekf_resources.h, through which those runtime calls now go -- `begin` with arguments: not a container's)
+    gpu = re.compile(r"\bhip(?!SetDevice)[A-Z]\w*\s*\(|\blaunch_\w+\s*\(|\bdense_propagate\s*\("
+                     r"|\.(?:ensure|reserve|commit|record|wait_if_recorded)\s*\(|\.begin\s*\(\s*[^\s)]|\b(?:ensure_group|release_group)\b[^(\n]*\(")
+    for site in ("h->dgate.ensure(", "h->noise.begin(rows", "h->noise.commit(", "h->d_stream.reserve(", "res::ensure_group(&fresh",
+                 "res::release_group<HipBackend>(h->stream", "h->t0.record(", "h->ring_ev[g].wait_if_recorded("):
+        assert site in text and gpu.search(site), site       # the pattern sees the sites it is meant for
+    assert not gpu.search("std::max_element(h->n.begin(), h->n.end())")
 
     def callees(name):
         return [c for c in set(re.findall(r"\b([A-Za-z_]\w*)\s*\(", bodies[name][2])) if c in bodies and c != name]
@@ -275,8 +282,45 @@ def test_every_entry_point_selects_its_device():
             return any("hipSetDevice(h->device)" in bodies[c][2] for c in before if c in bodies and c != name)
         return all(selects(c, seen + (name,)) for c in callees(name) if c not in seen and touches(c))
 
+    # (entry points whose only device work goes through an event's methods still count as touching the device)
+    assert touches("ekf_timer_begin") and touches("ekf_timer_end") and touches("ekf_set_nis_gate")
     missing = sorted(n for n in exported if touches(n) and not selects(n))
     assert not missing, f"entry points that use the stream without hipSetDevice(h->device): {missing}"
+
+
+def test_only_the_backend_allocates_and_frees():
+    """Every device buffer, pinned buffer and event of a handle is owned by a member of one of the types of
+    csrc/ekf_resources.h, which reach the runtime through `HipBackend` alone: outside that struct and the ABI's own
+    ekf_host_alloc / ekf_host_free, csrc/ekf_api.hip calls none of hipMalloc, hipHostMalloc, hipFree, hipHostFree,
+    hipEventCreate*, hipEventDestroy -- so nothing can be allocated there that the handle's destruction does not release.
+    Source audit, comments stripped."""
+    text = open(os.path.join(ROOT, "slam-duckietown_amd", "csrc", "ekf_api.hip")).read()
+    text = re.sub(r"//[^\n]*", "", text)
+    calls = re.compile(r"\bhip(?:Malloc|HostMalloc|Free|HostFree|EventCreate\w*|EventDestroy)\s*\(")
+
+    def cut(text, opening):
+        """`text` without the braces block that follows the one occurrence of `opening`; and that block."""
+        assert text.count(opening) == 1, opening
+        start = text.index(opening)
+        i = text.index("{", start) + 1
+        depth = 1
+        while depth:
+            depth += {"{": 1, "}": -1}.get(text[i], 0)
+            i += 1
+        return text[:start] + text[i:], text[start:i]
+
+    rest, backend = cut(text, "struct HipBackend")
+    rest, host_alloc = cut(rest, 'extern "C" void* ekf_host_alloc(')
+    rest, host_free = cut(rest, 'extern "C" void ekf_host_free(')
+    # the backend covers all six; the ABI's pair allocates and frees pinned memory; nothing else does
+    assert {m.rstrip("( ") for m in calls.findall(backend)} == {"hipMalloc", "hipHostMalloc", "hipFree", "hipHostFree", "hipEventCreate",
+                                                               "hipEventCreateWithFlags", "hipEventDestroy"}
+    assert calls.findall(host_alloc) == ["hipHostMalloc("] and calls.findall(host_free) == ["hipHostFree("]
+    found = calls.findall(rest)
+    assert not found, f"runtime allocation calls outside HipBackend: {found}"
+    # and free_all keeps no list of members: it deletes the handle, whose members release
+    body = re.search(r"static void free_all\(ekf_handle\* h\) \{(.*?)\n\}", text, flags=re.S).group(1)
+    assert "delete h;" in body and set(re.findall(r"h->(\w+)", body)) == {"device", "stream", "aux"}, body
 
 
 def test_row_slab_pass_hands_out_every_unit_exactly_once(sd):
@@ -344,6 +388,40 @@ def test_host_planning_logic_under_the_sanitizers(tmp_path):
                "plan_small"):
         assert re.search(r"\b%s\(" % fn, api), fn                      # called from the API ...
         assert not re.search(r"^(static|inline)[^\n;]*\b%s\(" % fn, api, flags=re.M), fn   # ... and defined only in the header
+
+
+def test_handle_ownership_types_under_the_sanitizers(tmp_path):
+    """The ownership types of the handle's device buffers, pinned buffers, events and stream-ordered uploads
+    (csrc/ekf_resources.h: plain C++17, no HIP header) compiled with plain g++ under AddressSanitizer +
+    UndefinedBehaviorSanitizer and run through tests/resources_check.cpp, built and run like host_plan_check.cpp above: a
+    counting backend that can fail its k-th call replays the handle's allocation script once for every k -- nothing live at
+    the end, no double free, a failed group empty and its retry good, no free before the stream has been waited for, no
+    pinned copy handed out under an upload in flight, one "new" report per allocation.  CPU only."""
+    import shutil
+    if shutil.which("g++") is None:
+        pytest.skip("g++ is not available")
+    exe = tmp_path / "resources_check"
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DEKF_HOST_ONLY",
+           "-Wall", "-Werror", "-I", os.path.join(ROOT, "slam-duckietown_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
+           os.path.join(ROOT, "tests", "resources_check.cpp"), "-o", str(exe)]
+    built = subprocess.run(cmd, capture_output=True, text=True)
+    assert built.returncode == 0, built.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300,
+                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "checks passed" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    # the library itself is built from the same header: it includes it, instantiates its types for the HIP backend and
+    # defines none of them itself; the header names nothing of HIP
+    api = open(os.path.join(ROOT, "slam-duckietown_amd", "csrc", "ekf_api.hip")).read()
+    assert '#include "ekf_resources.h"' in api
+    for name in ("DeviceBuf", "PinnedBuf", "StagedUpload", "Event"):
+        assert re.search(r"using %s = res::%s<(T, )?HipBackend>;" % (name, name), api), name
+        assert not re.search(r"\b(struct|class)\s+%s\b" % name, api), name
+    for fn in ("ensure_group", "release_group"):
+        assert re.search(r"\bres::%s\b" % fn, api), fn
+        assert not re.search(r"^(static|inline|template)[^\n;]*\b%s\(" % fn, api, flags=re.M), fn
+    header = open(os.path.join(ROOT, "slam-duckietown_amd", "csrc", "ekf_resources.h")).read()
+    assert not re.search(r"\bhip[A-Z_]|#include\s*<hip", re.sub(r"//[^\n]*", "", header))
 
 
 def test_store_hazard_guard_is_in_the_shipped_machine_code(sd):

@@ -651,6 +651,54 @@ OPTION_RANGES = {
 }
 
 
+def test_handle_churn_leaves_nothing_behind(sd):
+    """Twelve handles at N = 100 x 2, created and closed one after another: each takes over the stream pair its predecessor
+    parked and allocates afresh what that one released when it was deleted -- every first-use buffer of the handle is switched
+    on: device association (one window), both log rings (5 steps, resized to 3, then off), the NIS gate, the noise table
+    (set twice in a row: the second upload waits for the first to leave the staging copy), one removal, one direct update,
+    one fork, a 30-step uploaded stream.  Every handle ends in the first one's state and flags, bit for bit."""
+    from slam_duckietown_amd.ekf_bindings import EKF_DIRECT_POSE
+    N_cap, N, B, m, steps = 100, 96, 2, 8, 30
+    streams = [orc.synthetic_stream(N, steps, m, 9100 + t) for t in range(B)]
+    args = tuple(np.stack([s[i] for s in streams], axis=1) for i in (2, 3, 4, 5, 6))
+    window = [(0.0, [_tag(500 + i, -0.3 + 0.2 * i, 0.6 + 0.05 * i) for i in range(3)])]
+
+    def life():
+        with sd.EkfSlam(3 + 2 * N_cap, batch=B) as f:
+            f.set_option("small_state", 0)
+            for b in range(B):
+                f.set_state_diag(streams[b][0], streams[b][1], b)
+            f.log_innovations(5)
+            f.log_poses(5)
+            f.set_nis_gate(threshold=40.0)
+            f.set_noise([0.1, 0.13], [0.7, 0.8])
+            f.set_noise([0.11, 0.12], [0.75, 0.7])
+            f.step_detections(0.01, 0.005, [window] * B)           # three new tags: 99 landmarks
+            assert f.assoc_fallbacks() == 0 and [f.size(b) for b in range(B)] == [3 + 2 * (N + 3)] * B
+            f.log_innovations(3)
+            f.log_poses(3)
+            f.remove_landmarks([5, N + 1], b=None)
+            pose = np.stack([f.mean(b)[:3] for b in range(B)])
+            got = f.update_direct([[EKF_DIRECT_POSE]] * B, [[pose[b] + [0.01, -0.02, 0.005]] for b in range(B)],
+                                  [[np.diag([0.01, 0.01, 0.002])]] * B)
+            assert got.applied.all()
+            f.fork(0, 1)
+            f.run_stream(*args)
+            assert f.innovations().m.shape[0] == 3 and f.pose_steps == steps
+            f.log_innovations(0)
+            f.log_poses(0)
+            return [f.state(b) for b in range(B)], [f.flags(b) for b in range(B)], f.gate_counts()
+
+    first = life()
+    assert [mu.shape[0] for mu, _P in first[0]] == [3 + 2 * (N + 1)] * B
+    assert not np.array_equal(first[0][0][1], first[0][1][1])      # (the twins diverge again over the stream)
+    for _ in range(11):
+        out, flags, rejected = life()
+        assert flags == first[1] and np.array_equal(rejected, first[2])
+        for b in range(B):
+            assert np.array_equal(out[b][0], first[0][b][0]) and np.array_equal(out[b][1], first[0][b][1])
+
+
 def test_set_option_ranges_and_removed_names(sd):
     """ekf_set_option accepts both ends of every option's range and refuses the values just beyond them with an error that
     names the option; `pass_kernel` = 1 (a removed form) is refused too.  Names of options that no longer exist are unknown."""

@@ -765,6 +765,48 @@ def test_a_run_longer_than_one_planning_piece(sd):
     assert orc.rel_fro(fused[0][0], om) < 1e-8 and orc.rel_fro(fused[0][1], oP) < 1e-8
 
 
+def test_run_plan_copies_regrow_on_one_handle(sd):
+    """The run plan is uploaded through two copies used alternately, each sized on first use (at least 64 cadences per
+    trajectory) and replaced when a run needs more.  One uploaded stream of 1140 steps at 8 landmarks per step -- 5 steps per
+    cadence -- run as pieces of 40, 340, 340 and 420 steps: 8, 68, 68 and 84 cadences.  The second piece sizes its copy on
+    first use, the third outgrows the copy the first piece sized at 64, the fourth the second piece's: both regrows happen
+    on a handle with earlier runs behind it.  Final state against a fresh handle on the per-step path and against the oracle."""
+    N, B, m, steps = 40, 2, 8, 1140
+    n = 3 + 2 * N
+    pieces = (40, 340, 340, 420)
+    streams = [orc.synthetic_stream(N, steps, m, 7300 + t) for t in range(B)]
+    starts = [dense_start(n, 7400 + t) for t in range(B)]
+    means = [s[0] for s in streams]
+    args = (stack(streams, 2), stack(streams, 3), stack(streams, 4), stack(streams, 5), stack(streams, 6))
+    opts = [("active_bound", 0), ("small_state", 0)]
+    need = [cadences_needed(np.full(count, m)) for count in pieces]
+    assert need == [8, 68, 68, 84]                        # against the first room of 64 per trajectory
+    with sd.EkfSlam(n, batch=B) as f:
+        for name, value in opts:
+            f.set_option(name, value)
+        for b in range(B):
+            f.set_state(means[b], starts[b], b)
+        f.stream_upload(*args)
+        k = 0
+        for count in pieces:
+            f.stream_run(k, count)
+            k += count
+        assert k == steps
+        out = [f.state(b) for b in range(B)]
+        assert [f.flags(b) for b in range(B)] == [0] * B
+        assert cadences(sd, f) == (sum(need), steps)
+    plain, (pc, _) = run_stream(sd, n, B, starts, means, *args, options=opts + [("fused_cadence", 0)])
+    assert pc == 0
+    for b in range(B):
+        assert orc.rel_fro(out[b][0], plain[b][0]) < TIGHT and orc.rel_fro(out[b][1], plain[b][1]) < TIGHT
+    cfg = orc.EkfConfig()
+    s = streams[0]
+    om, oP = s[0].copy(), starts[0].copy()
+    for k in range(steps):
+        om, oP = orc.ekf_step_dense(om, oP, s[2][k], s[3][k], s[4][k], s[5][k], s[6][k], cfg)
+    assert orc.rel_fro(out[0][0], om) < 1e-8 and orc.rel_fro(out[0][1], oP) < 1e-8
+
+
 def test_long_runs_without_observations_inside_a_fused_run(sd):
     """Windows in which no tag is seen (the reference's loop then only predicts, src/replay_no_ros.py:435): 45 such steps at
     the head of the stream are one cadence of 40 predictions that appends no rank anywhere in the bank -- no pass follows,
