@@ -157,6 +157,39 @@ int ekf_associate(ekf_handle *h, int b0, int count, const double *range, const d
  * downloads). */
 int ekf_download_joint(ekf_handle *h, int b0, int count, const int *landmarks, const int *k, int stride,
                        double *mean, double *cov);
+/* The Cholesky factor of the WHOLE covariance, on the device: ekf_factor computes U, upper triangular with a positive
+ * diagonal and P = U^T U, for trajectories [b0, b0+count) -- what full-state NEES e^T P^-1 e, the question "is P still a
+ * covariance?" (every update here is P -= K S K^T, not the Joseph form), the entropy of the map (ln det P) and posterior
+ * draws (a square root of P) need, without covariance(b) and a host factorisation per trajectory.  P is the current
+ * covariance: the pending update is applied first (a pass the caller pays for, as ekf_download_block does) and device-side
+ * sizes are refreshed; the filter's own state is never written -- U goes into a workspace of the handle (per trajectory the
+ * square of the range's largest n rounded up to 64, 8 bytes each: 130 MB at n = 4003), and afterwards the filter is bit for
+ * bit where a plain ekf_flush at that point would have left it.  A right-looking blocked factorisation, block 64; the rank-64
+ * down-dates of the trailing triangle run on the fp64 matrix cores; the reduction order is fixed, so a trajectory's U is
+ * bit-identical across repeats, bank positions and ranges.
+ * logdet[bi] = 2 sum_i ln u_ii.  info[bi] follows LAPACK dpotrf: 0 = positive definite, i > 0 = the leading minor of order i is
+ * not (the first pivot that is <= 0 or not finite, 1-based); such a trajectory gets logdet = NaN, does not disturb the others
+ * and sets no sticky flag (this is a query).  Either output may be NULL.  Blocking, and stream-ordered behind everything
+ * enqueued.
+ * The factor is a SNAPSHOT: it stays -- with the range and each trajectory's n at that time -- until the next ekf_factor,
+ * ekf_factor_release or ekf_destroy; later filter calls neither change nor invalidate it.
+ * ekf_factor_solve: rhs is count x nrhs x stride (nrhs in 1..EKF_FACTOR_RHS, stride >= the largest factored n of the range;
+ * a trajectory reads the first n entries of each column); white (same shape) = U^-T rhs, entries beyond a trajectory's n NaN;
+ * quad (count x nrhs) = |white|^2 = rhs^T P^-1 rhs.  Either output may be NULL, not both.
+ * ekf_factor_multiply: out = U^T z, same shapes: cov(out) = P for z ~ N(0, I).
+ * ekf_download_factor: U of trajectory b as n x n row-major, zeros below the diagonal.
+ * Every output of a trajectory whose info != 0 is NaN, and ekf_download_factor returns EKF_ERR_STATE for it.
+ * EKF_ERR_ARG, with nothing changed: a bad range, NULLs, nrhs or stride out of bounds, a non-finite rhs or z, n different from
+ * the factored n.  EKF_ERR_STATE: no factor held, a range outside the factored one; for ekf_factor a trajectory of the range
+ * carries EKF_FLAG_INTERNAL or an earlier call failed half way (as the downloads).  EKF_ERR_HIP: the workspace cannot be
+ * allocated (the message carries the byte count); any previous factor is released and the handle stays usable. */
+#define EKF_FACTOR_RHS 16     /* right-hand sides of one ekf_factor_solve / ekf_factor_multiply */
+int ekf_factor(ekf_handle *h, int b0, int count, double *logdet, int *info);
+int ekf_factor_solve(ekf_handle *h, int b0, int count, const double *rhs, int nrhs, int stride,
+                     double *white, double *quad);
+int ekf_factor_multiply(ekf_handle *h, int b0, int count, const double *z, int nrhs, int stride, double *out);
+int ekf_download_factor(ekf_handle *h, int b, double *U, int n);
+int ekf_factor_release(ekf_handle *h);
 int ekf_state_size(ekf_handle *h, int b, int *n);
 
 /* Innovation log: every landmark update's landmark index, innovation y (2), innovation covariance S (2x2, row-major) and

@@ -189,6 +189,13 @@ struct ekf_handle : ekf::HostPlan {
   DeviceBuf<double> dquery;
   std::vector<int> joint_sel;     // ekf_download_joint: the selection as the host sorted it (plan_joint_query)
   std::vector<std::pair<int, int>> joint_order;   // ... scratch of the sort (handle-owned: no allocation per query)
+  // ekf_factor (allocated on first use, released by ekf_factor_release): the workspace of the Cholesky factors, each factored
+  // trajectory's status words {info, n, nblk, 0} and log-determinant; `factor` is what the host remembers of the snapshot
+  DeviceBuf<double> dfactor, dflog;
+  DeviceBuf<int> dfstat;
+  ekf::FactorHeld factor;
+  std::vector<double> factor_log;
+  std::vector<int> factor_stat;   // ... and the status words as they come back
   // The innovation log (ekf_log_innovations; empty: off): a ring of innov_cap step rows, innov_steps steps logged so far.
   // While an entry point enqueues a logged step, lg_slot is the ring row of its next launch (-1: that launch is not logged) and
   // lg_jbase the position of its first landmark; ekf_stream_run logs stream step t in row (lg_tslot + t) % innov_cap.
@@ -888,6 +895,122 @@ extern "C" int ekf_download_joint(ekf_handle* h, int b0, int count, const int* l
   HIP_TRY(h, hipMemcpyAsync(dsel, h->joint_sel.data(), sizeof(int) * h->joint_sel.size(), hipMemcpyHostToDevice, h->stream));
   launch_joint(h->stream, pending_view(h, b0, count), jp.ns, jp.nt, jp.tiles, dsel, q.out<double>(0), q.out<double>(1));
   return query_end(h, fn, b0, count, q);
+}
+
+// ---- the covariance's Cholesky factor (ekf_factor.hip) ----
+static FactorView factor_view(const ekf_handle* h) { return FactorView{h->dfactor.p, h->factor.tstride, h->factor.lw, h->dfstat.p, h->dflog.p}; }
+static int factor_drop(ekf_handle* h) {
+  h->factor.held = false;
+  RES_TRY(h, "the factor workspace", res::release_group<HipBackend>(h->stream, h->dfactor, h->dfstat, h->dflog));
+  return EKF_OK;
+}
+// P = U^T U of trajectories [b0, b0 + count): the pending update applied, then the blocked factorisation into the handle's
+// workspace; the filter itself is only read.
+extern "C" int ekf_factor(ekf_handle* h, int b0, int count, double* logdet, int* info) {
+  const char* fn = "ekf_factor";
+  if (int rc = check_b(h, 0, fn)) return rc;
+  if (int rc = check_range(h, fn, b0, count)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  // (as the downloads: the flags come back with one stream-ordered copy)
+  HIP_TRY(h, hipMemcpyAsync(h->h_flags.p, h->dflags.p, sizeof(unsigned) * h->batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (int b = b0; b < b0 + count; ++b)
+    if (h->host_bad[b] || (h->h_flags.p[b] & EKF_FLAG_INTERNAL)) return check_internal(h, b, fn);
+  if (int rc = flush_pending(h)) return rc;
+  FactorPlan fp{};
+  if (const char* why = plan_factor(h, b0, count, fp)) return bad_arg(h, fn, why);
+  h->factor.held = false;                              // the workspace is about to be rewritten
+  {
+    const res::Status s0 = h->dfactor.reserve(fp.words, 0, h->stream);
+    const res::Status s1 = s0.ok() ? h->dfstat.reserve(4 * (size_t)count, 4 * (size_t)h->batch, h->stream) : s0;
+    const res::Status s2 = s1.ok() ? h->dflog.reserve((size_t)count, (size_t)h->batch, h->stream) : s1;
+    if (!s2.ok()) {
+      (void)hipGetLastError();
+      (void)factor_drop(h);
+      return res_fail(h, "ekf_factor: the factor workspace", s2);
+    }
+  }
+  h->factor.b0 = b0;
+  h->factor.count = count;
+  h->factor.lw = fp.lw;
+  h->factor.tstride = fp.tstride;
+  h->factor.n.assign(h->n.begin() + b0, h->n.begin() + b0 + count);
+  h->factor.info.assign((size_t)count, 0);
+  h->factor_log.assign((size_t)count, 0.0);
+  launch_factor(h->stream, pending_view(h, b0, count), factor_view(h), fp.nblk);
+  HIP_TRY(h, hipGetLastError());
+  std::vector<int>& st = h->factor_stat;
+  st.assign(4 * (size_t)count, 0);
+  HIP_TRY(h, hipMemcpyAsync(st.data(), h->dfstat.p, sizeof(int) * st.size(), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->factor_log.data(), h->dflog.p, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (int bi = 0; bi < count; ++bi) {
+    h->factor.info[(size_t)bi] = st[4 * (size_t)bi];
+    if (info) info[bi] = st[4 * (size_t)bi];
+    if (logdet) logdet[bi] = st[4 * (size_t)bi] ? std::numeric_limits<double>::quiet_NaN() : h->factor_log[(size_t)bi];
+  }
+  h->factor.held = true;
+  return EKF_OK;
+}
+
+// U^-T rhs (solve) or U^T z (multiply) for trajectories [b0, b0 + count) of the factored range.  The operand is uploaded into
+// the queries' staging buffer, the result formed beside it and copied out.
+static int factor_apply(ekf_handle* h, const char* fn, bool solve, int b0, int count, const double* x, int nrhs, int stride,
+                        double* out, double* quad) {
+  if (!h) return EKF_ERR_ARG;
+  bool state = false;
+  int nblk_hi = 0;
+  if (const char* why = plan_factor_apply(h, h->factor, b0, count, x, nrhs, stride, &state, &nblk_hi))
+    return state ? fail(h, EKF_ERR_STATE, std::string(fn) + ": " + why) : bad_arg(h, fn, why);
+  if (!out && !(solve && quad)) return bad_arg(h, fn, "NULL output");
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t words = (size_t)count * (size_t)nrhs * (size_t)stride, qwords = (size_t)count * (size_t)nrhs;
+  RES_TRY(h, "the queries' staging buffer", h->dquery.reserve(2 * words + qwords, 0, h->stream));
+  double *dx = h->dquery.p, *dout = dx + words, *dquad = dout + words;
+  HIP_TRY(h, hipMemcpyAsync(dx, x, sizeof(double) * words, hipMemcpyHostToDevice, h->stream));
+  const int f0 = b0 - h->factor.b0;
+  if (solve)
+    launch_factor_solve(h->stream, factor_view(h), f0, count, nblk_hi, dx, nrhs, stride, dout, dquad);
+  else
+    launch_factor_multiply(h->stream, factor_view(h), f0, count, nblk_hi, dx, nrhs, stride, dout);
+  HIP_TRY(h, hipGetLastError());
+  if (out) HIP_TRY(h, hipMemcpyAsync(out, dout, sizeof(double) * words, hipMemcpyDeviceToHost, h->stream));
+  if (solve && quad) HIP_TRY(h, hipMemcpyAsync(quad, dquad, sizeof(double) * qwords, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return EKF_OK;
+}
+extern "C" int ekf_factor_solve(ekf_handle* h, int b0, int count, const double* rhs, int nrhs, int stride, double* white,
+                                double* quad) {
+  return factor_apply(h, "ekf_factor_solve", true, b0, count, rhs, nrhs, stride, white, quad);
+}
+extern "C" int ekf_factor_multiply(ekf_handle* h, int b0, int count, const double* z, int nrhs, int stride, double* out) {
+  return factor_apply(h, "ekf_factor_multiply", false, b0, count, z, nrhs, stride, out, nullptr);
+}
+
+extern "C" int ekf_download_factor(ekf_handle* h, int b, double* U, int n) {
+  const char* fn = "ekf_download_factor";
+  if (!h) return EKF_ERR_ARG;
+  if (!U) return bad_arg(h, fn, "NULL U");
+  if (b < 0 || b >= h->batch) return bad_arg(h, fn, "trajectory index out of range");
+  const FactorHeld& fh = h->factor;
+  if (!fh.held) return fail(h, EKF_ERR_STATE, std::string(fn) + ": no factor is held (ekf_factor)");
+  if (b < fh.b0 || b >= fh.b0 + fh.count) return fail(h, EKF_ERR_STATE, std::string(fn) + ": trajectory outside the factored range");
+  const size_t bi = (size_t)(b - fh.b0);
+  if (n != fh.n[bi]) return bad_arg(h, fn, "n does not match the factored n");
+  if (fh.info[bi] != 0)
+    return fail(h, EKF_ERR_STATE, std::string(fn) + ": the covariance of trajectory " + std::to_string(b) +
+                                      " is not positive definite (info = " + std::to_string(fh.info[bi]) + ")");
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipMemcpy2DAsync(U, sizeof(double) * (size_t)n, h->dfactor.p + bi * fh.tstride, sizeof(double) * (size_t)fh.lw,
+                              sizeof(double) * (size_t)n, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return EKF_OK;
+}
+
+extern "C" int ekf_factor_release(ekf_handle* h) {
+  if (!h) return EKF_ERR_ARG;
+  HIP_TRY(h, hipSetDevice(h->device));
+  return factor_drop(h);
 }
 
 // ---- the log rings: the pose log (ekf_pose_log.hip) and the innovation log (ekf_innovations.hip) ----

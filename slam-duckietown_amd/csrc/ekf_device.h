@@ -43,6 +43,8 @@ constexpr int RM_THREADS = 256;         // k_remove (ekf_remove.hip): threads pe
 constexpr int AQ_CHUNK = 64;            // k_assoc_query (ekf_associate.hip): landmarks per workgroup, one per lane of a wave
 constexpr int JQ_TILE = 32;             // k_joint (ekf_joint.hip): rows / columns of a workgroup's tile of the sub-matrix
 constexpr int JMAX = EKF_JMAX;          // landmarks per trajectory in one ekf_download_joint
+constexpr int FB = 64;                  // ekf_factor (ekf_factor.hip): rows / columns of a block of the blocked Cholesky
+constexpr int FACTOR_RHS = EKF_FACTOR_RHS;   // right-hand sides of one ekf_factor_solve / ekf_factor_multiply
 // ekf_update_direct (k_direct, ekf_direct.hip): a trajectory brings up to MMAX fixes, at most one of them a pose fix of 3 rows:
 // 3 + 2 (MMAX - 1) = 33 rows, 36 as whole k-tiles.  What the launch reads per trajectory of the BANK (trajectories outside the
 // call's range carry D = 0): DIRECT_INTS ints {D, active bound, state index of row k (DIRECT_ROWS), 4 * fix + component of row k
@@ -253,6 +255,11 @@ struct PendingView {
   const int* nact;
   const SolveOut* so;
   int ld; long pstride; int b0, count, kb;
+};
+// The factor workspace of ekf_factor (ekf_factor.hip): per factored trajectory lw x lw doubles, row-major, tstride apart; the
+// status words {info, n, nblk, 0} and the log-determinant of each.
+struct FactorView {
+  double* ws; size_t tstride; int lw; int* fstat; double* flog;
 };
 // What the launches that move the filter take of a handle, the same for every launch of a call (ekf_api.hip: bank_view; the
 // launchers of ekf_launch.h unpack it into their kernel's arguments): P_base, the rank slots, sizes, last solve's records,

@@ -908,6 +908,73 @@ inline const char* plan_joint_query(const HostPlan* h, int b0, int count, const 
   return nullptr;
 }
 
+// ekf_factor (ekf_factor.hip): the blocked Cholesky factorisation of trajectories [b0, b0 + count) and what is kept of it.
+// The workspace holds count matrices of lw x lw doubles, lw = the range's largest n rounded up to whole blocks of FB; all of
+// its arithmetic is size_t (n_max = 21823 x 32 trajectories is 122 GB: beyond every 32-bit count, and refused by the
+// allocation, not by an overflow).  Block step k of nblk launches the diagonal block (count workgroups), the row panel
+// (factor_panel_groups x count) and the trailing down-date (t (t + 1) / 2 x count, t = factor_trail_tiles_per_row):
+// 3 nblk - 2 launches behind the load, 188 at n = 4003.  ekf_factor_solve is 2 nblk - 1 launches (the block's substitution, the
+// update of the columns to its right), ekf_factor_multiply one.
+struct FactorPlan {
+  int n_hi;            // largest state of the range
+  int nblk;            // its blocks
+  int lw;              // row stride of the workspace (doubles)
+  size_t tstride;      // trajectory stride (doubles)
+  size_t words;        // doubles of the whole workspace
+  long launches;       // kernel launches of the factorisation
+};
+// column groups of 256 (a thread per column) of block step k's row panel; 0: the last block has none
+inline int factor_panel_groups(int nblk, int k) { return ((nblk - k - 1) * FB + 255) / 256; }
+// 128 x 128 tiles per row of block step k's trailing triangle (two blocks each; the last one may hold a single block)
+inline int factor_trail_tiles_per_row(int nblk, int k) { return (nblk - k - 1 + 1) / 2; }
+inline const char* plan_factor(const HostPlan* h, int b0, int count, FactorPlan& fp) {
+  if (!bank_range_ok(h, b0, count)) return BANK_RANGE_WHY;
+  fp.n_hi = 0;
+  for (int b = b0; b < b0 + count; ++b) fp.n_hi = std::max(fp.n_hi, h->n[b]);
+  fp.nblk = (fp.n_hi + FB - 1) / FB;
+  fp.lw = fp.nblk * FB;
+  fp.tstride = (size_t)fp.lw * (size_t)fp.lw;
+  fp.words = fp.tstride * (size_t)count;
+  fp.launches = 1 + (fp.nblk > 0 ? 3L * fp.nblk - 2 : 0);
+  return nullptr;
+}
+// The factor a handle holds: the range and each trajectory's n and info at the time of ekf_factor.
+struct FactorHeld {
+  bool held = false;
+  int b0 = 0, count = 0, lw = 0;
+  size_t tstride = 0;
+  std::vector<int> n, info;
+};
+// ekf_factor_solve / ekf_factor_multiply on trajectories [b0, b0 + count): the arguments (a message: EKF_ERR_ARG), then the
+// factor (*state = true: EKF_ERR_STATE).  x: count x nrhs x stride, of which the first n of every column must be finite.
+// *nblk_hi: blocks of the range's largest factored state.
+constexpr int FACTOR_STRIDE_MAX = 1 << 20;
+inline const char* plan_factor_apply(const HostPlan* h, const FactorHeld& fh, int b0, int count, const double* x, int nrhs, int stride,
+                                     bool* state, int* nblk_hi) {
+  *state = false;
+  if (!bank_range_ok(h, b0, count)) return BANK_RANGE_WHY;
+  if (!x) return "NULL right-hand sides";
+  if (nrhs < 1 || nrhs > FACTOR_RHS) return "nrhs outside 1..EKF_FACTOR_RHS";
+  if (stride < 1 || stride > FACTOR_STRIDE_MAX) return "stride out of bounds";
+  *state = true;
+  if (!fh.held) return "no factor is held (ekf_factor)";
+  if (b0 < fh.b0 || b0 - fh.b0 > fh.count - count) return "trajectory range outside the factored one";
+  *state = false;
+  int n_hi = 0;
+  for (int bi = 0; bi < count; ++bi) n_hi = std::max(n_hi, fh.n[(size_t)(b0 - fh.b0 + bi)]);
+  if (stride < n_hi) return "stride below the largest factored n of the range";
+  for (int bi = 0; bi < count; ++bi) {
+    const int n = fh.n[(size_t)(b0 - fh.b0 + bi)];
+    for (int q = 0; q < nrhs; ++q) {
+      const double* col = x + ((size_t)bi * nrhs + q) * (size_t)stride;
+      for (int i = 0; i < n; ++i)
+        if (!std::isfinite(col[i])) return "non-finite entry in the right-hand sides";
+    }
+  }
+  *nblk_hi = (n_hi + FB - 1) / FB;
+  return nullptr;
+}
+
 // Fill StepIn for pass `p` (landmarks [p*MMAX, ...)) of a validated list; `bound` is the trajectory's running
 // active bound (monotone): an observed landmark and everything below it may be correlated from now on.
 inline void fill_step(StepIn& s, int n_b, int& bound, double lin, double ang, int flags, const int* idx,

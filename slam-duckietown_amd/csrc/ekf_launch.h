@@ -95,6 +95,16 @@ void launch_assoc_query(hipStream_t st, const PendingView& f, const DeviceConfig
                         const double* zr, const double* zb, const int* zm, double* part, double* all_nis, double* all_logdet,
                         int* cand, double* cand_nis, double* cand_logdet, double* min_nis);
 void launch_joint(hipStream_t st, const PendingView& f, int ns, int nt, int tiles, const int* sel, double* mean_out, double* cov_out);
+// ---- the covariance's Cholesky factor (ekf_factor.hip) ----
+// every launch of the blocked factorisation of trajectories [f.b0, f.b0 + f.count) into w: the load, then per block step the
+// diagonal block, the row panel and the trailing down-date; nblk_hi: blocks of the range's largest state (plan_factor)
+void launch_factor(hipStream_t st, const PendingView& f, const FactorView& w, int nblk_hi);
+// trajectories [f0, f0 + count) OF THE FACTORED RANGE, nblk_hi the blocks of their largest state; x (the right-hand sides: the
+// solve updates them in place) / z, white / out: [count][nrhs][stride] on the device, quad [count][nrhs]
+void launch_factor_solve(hipStream_t st, const FactorView& w, int f0, int count, int nblk_hi, double* x, int nrhs, int stride,
+                         double* white, double* quad);
+void launch_factor_multiply(hipStream_t st, const FactorView& w, int f0, int count, int nblk_hi, const double* z, int nrhs,
+                            int stride, double* out);
 // ---- state surgery (ekf_remove.hip, ekf_direct.hip, ekf_copy.hip, ekf_dense.hip) ----
 // rp.rows: the launch's largest new size (grid rows); nb trajectories from b0; src / dst: rp's tables on the device
 void launch_remove(hipStream_t st, const BankView& k, double* mu, const RemovePlan& rp, const int* src, const int* dst,

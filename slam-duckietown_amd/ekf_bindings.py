@@ -115,6 +115,11 @@ ABI = {
     "ekf_download_marginals": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _ip]),
     "ekf_associate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int]),
     "ekf_download_joint": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, C.c_int, _dp, _dp]),
+    "ekf_factor": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _ip]),
+    "ekf_factor_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
+    "ekf_factor_multiply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp]),
+    "ekf_download_factor": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int]),
+    "ekf_factor_release": (C.c_int, [C.c_void_p]),
     "ekf_update_direct": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _dp, _dp, _ip, C.c_int, _dp, _dp, _ip, _ip]),
     "ekf_state_size": (C.c_int, [C.c_void_p, C.c_int, _ip]),
     "ekf_log_innovations": (C.c_int, [C.c_void_p, C.c_int]),
@@ -343,6 +348,98 @@ class DirectUpdate(typing.NamedTuple):
     applied: np.ndarray    # (B,) bool
 
 
+EKF_FACTOR_RHS = 16       # (include/ekfslam_hip.h)
+
+
+class CovFactor:
+    """The Cholesky factor P = U^T U of a range of trajectories, as ``EkfSlam.factor`` left it on the device: a snapshot,
+    which later filter calls neither change nor invalidate.  ``logdet`` (count,) = ln det P, ``info`` (count,) as LAPACK
+    dpotrf (0: positive definite; i > 0: the leading minor of order i is not -- every result of that trajectory is NaN),
+    ``n`` (count,) the state sizes and ``means`` the means at factor time.  Made for one trajectory (``factor(b)``) the
+    methods take and return that trajectory's arrays without the leading axis.
+
+    A newer ``factor()`` or ``release_factor()`` of the same filter replaces the factor on the device: every method of
+    this object then raises ``EkfError``."""
+
+    def __init__(self, owner, generation, b0, count, single, logdet, info, n, means):
+        self._owner, self._generation, self._b0, self._count, self._single = owner, generation, b0, count, single
+        self.logdet, self.info, self.n, self.means = logdet, info, n, means
+
+    def _live(self):
+        if self._owner._factor_generation != self._generation:
+            raise EkfError("this CovFactor has been replaced by a newer factor() or release_factor() of its filter")
+
+    def _apply(self, x, which):
+        """x: (count, k, n_hi) (or (count, n_hi); one trajectory: (k, n) or (n,)) -> the same shape through ekf_factor_solve
+        (`which` = "white" / "quad") or ekf_factor_multiply ("mul"), EKF_FACTOR_RHS columns per call."""
+        self._live()
+        o = self._owner
+        x = np.asarray(x, dtype=np.float64)
+        if self._single:
+            x = x[None]
+        vec = x.ndim == 2
+        if vec:
+            x = x[:, None, :]
+        stride = int(self.n.max())
+        if x.ndim != 3 or x.shape[0] != self._count or x.shape[2] != stride:
+            raise ValueError(f"expected {self._count} trajectories of vectors of length {stride}, got {x.shape}")
+        k = x.shape[1]
+        out = np.empty((self._count, k) if which == "quad" else x.shape)
+        for k0 in range(0, k, EKF_FACTOR_RHS):
+            part = np.ascontiguousarray(x[:, k0:k0 + EKF_FACTOR_RHS])
+            nr = part.shape[1]
+            res = np.empty(part.shape)
+            if which == "mul":
+                o._check(o._lib.ekf_factor_multiply(o._h, self._b0, self._count, _p(part), nr, stride, _p(res)))
+            else:
+                quad = np.empty((self._count, nr))
+                o._check(o._lib.ekf_factor_solve(o._h, self._b0, self._count, _p(part), nr, stride,
+                                                 _p(res) if which == "white" else None, _p(quad)))
+                if which == "quad":
+                    res = quad
+            out[:, k0:k0 + nr] = res
+        if vec:
+            out = out[:, 0]
+        return out[0] if self._single else out
+
+    def whiten(self, e):
+        """U^-T e: white noise of unit covariance if e ~ N(0, P).  Entries beyond a trajectory's n are NaN."""
+        return self._apply(e, "white")
+
+    def mahalanobis(self, e):
+        """e^T P^-1 e per trajectory (and per vector)."""
+        return self._apply(e, "quad")
+
+    def multiply(self, z):
+        """U^T z: covariance P for z ~ N(0, I)."""
+        return self._apply(z, "mul")
+
+    def upper(self, b: int = 0) -> np.ndarray:
+        """U of trajectory b (an index of the bank), n x n, zeros below the diagonal."""
+        self._live()
+        o = self._owner
+        if not self._b0 <= b < self._b0 + self._count:
+            raise ValueError("trajectory outside the factored range")
+        n = int(self.n[b - self._b0])
+        out = np.empty((n, n))
+        o._check(o._lib.ekf_download_factor(o._h, int(b), _p(out), n))
+        return out
+
+    def sample(self, k: int, rng=None):
+        """k draws from N(mean, P) per trajectory: mean + U^T z, (count, k, n_hi) with NaN beyond a trajectory's n (one
+        trajectory: (k, n))."""
+        self._live()
+        rng = np.random.default_rng() if rng is None else rng
+        stride = int(self.n.max())
+        z = rng.standard_normal((self._count, int(k), stride))
+        means = np.full((self._count, 1, stride), np.nan)
+        for bi in range(self._count):
+            means[bi, 0, :self.n[bi]] = self.means[bi]
+        draws = (z[0] if self._single else z)
+        out = self.multiply(draws)
+        return out + (means[0] if self._single else means)
+
+
 class EkfSlam:
     """A bank of ``batch`` independent EKF-SLAM filters resident on one MI355X.
 
@@ -376,6 +473,7 @@ class EkfSlam:
         self._stages = {}
         self._out = None
         self._pose_cap = 0                                   # ring size of the pose log (log_poses); 0: off
+        self._factor_generation = 0                          # counts factor() and release_factor(): a CovFactor is live while it matches
 
     # -- plumbing ------------------------------------------------------------------------------
     def _check(self, rc: int):
@@ -545,6 +643,23 @@ class EkfSlam:
             n = 3 + 2 * int(kk[0])
             return mean[0, :n], cov[0, :n, :n]
         return mean, cov, kk
+
+    def factor(self, b: Optional[int] = None) -> "CovFactor":
+        """The Cholesky factor P = U^T U of the current covariance of trajectory b, or of the whole bank (``b`` None), formed
+        on the device (``ekf_factor``: the pending update is applied first, the filter itself is only read).  Returns a
+        ``CovFactor``; a later ``factor()`` or ``release_factor()`` replaces it."""
+        b0, count = (0, self.batch) if b is None else (int(b), 1)
+        logdet, info = np.empty(count), np.empty(count, dtype=np.int32)
+        self._factor_generation += 1
+        self._check(self._lib.ekf_factor(self._h, b0, count, _p(logdet), _p(info, _ip)))
+        n = np.array([self.size(t) for t in range(b0, b0 + count)], dtype=np.int32)
+        means = [self.mean(t) for t in range(b0, b0 + count)]
+        return CovFactor(self, self._factor_generation, b0, count, b is not None, logdet, info, n, means)
+
+    def release_factor(self):
+        """Free the factor workspace on the device; a CovFactor made before is no longer usable."""
+        self._factor_generation += 1
+        self._check(self._lib.ekf_factor_release(self._h))
 
     # -- direct measurements -------------------------------------------------------------------
     @staticmethod

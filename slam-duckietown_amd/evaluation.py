@@ -256,6 +256,50 @@ def marginal_nees(filter_bank, true_poses, true_landmarks=None) -> MarginalNees:
     return MarginalNees(vals, float(vals.mean()), chi2_bounds(3, B), lm_vals, lm_bounds)
 
 
+class MapNees(NamedTuple):
+    nees: np.ndarray                          # (B,) full-state NEES e^T P^-1 e per trajectory (NaN where info != 0)
+    dof: np.ndarray                           # (B,) its degrees of freedom: the state size n
+    info: np.ndarray                          # (B,) 0, or the order of the first leading minor of P that is not positive definite
+    anees: Optional[float]                    # average over the bank where every trajectory has the same n, else None
+    bounds: Optional[Tuple[float, float]]     # chi2_bounds(n, B, confidence) for that average, else None
+
+
+def map_nees(filter_bank, true_poses, true_landmarks, confidence: float = 0.95) -> MapNees:
+    """Full-state NEES of every trajectory of a bank: e^T P^-1 e with the WHOLE covariance -- pose, every landmark and all
+    their cross-covariances, where EKF-SLAM's over-confidence lives -- through one ``filter_bank.factor()`` (the Cholesky
+    factor formed on the device) and one ``mahalanobis``.  `true_poses` (B, 3), `true_landmarks` (B, N, 2) with N at least
+    each trajectory's landmark count; the theta error is wrapped.  ``dof`` is n per trajectory; the bank average and its
+    ``chi2_bounds(n, B, confidence)`` are given where all sizes agree.  ``info`` reports an indefinite P (LAPACK dpotrf's
+    convention) instead of folding it into a NaN: that trajectory's NEES is NaN and ``anees`` with it."""
+    B = filter_bank.batch
+    true_poses = np.asarray(true_poses, dtype=float).reshape(B, 3)
+    truth = np.asarray(true_landmarks, dtype=float).reshape(B, -1, 2)
+    fac = filter_bank.factor()
+    n = np.asarray(fac.n)
+    e = np.zeros((B, int(n.max())))
+    for b in range(B):
+        k = (int(n[b]) - 3) // 2
+        if truth.shape[1] < k:
+            raise ValueError(f"true_landmarks holds {truth.shape[1]} landmarks, trajectory {b} has {k}")
+        e[b, :3] = fac.means[b][:3] - true_poses[b]
+        e[b, 2] = wrap_angle(e[b, 2])
+        e[b, 3:n[b]] = fac.means[b][3:] - truth[b, :k].reshape(-1)
+    vals = np.asarray(fac.mahalanobis(e), dtype=float)
+    same = bool((n == n[0]).all())
+    return MapNees(vals, n.copy(), np.asarray(fac.info).copy(), float(vals.mean()) if same else None,
+                   chi2_bounds(int(n[0]), B, confidence) if same else None)
+
+
+def map_entropy(factor) -> np.ndarray:
+    """Differential entropy of N(mean, P) per trajectory of a ``CovFactor``, in nats: (n ln 2 pi e + ln det P) / 2."""
+    return 0.5 * (np.asarray(factor.n) * math.log(2.0 * math.pi * math.e) + np.asarray(factor.logdet))
+
+
+def information_gain(before, after) -> np.ndarray:
+    """Entropy lost between two ``CovFactor``s of the same trajectories, in nats (positive: the map knows more)."""
+    return map_entropy(before) - map_entropy(after)
+
+
 class NisConsistency(NamedTuple):
     step_anis: np.ndarray            # (K,) per step: the bank's NIS summed over its updates, divided by B (NaN: no update)
     step_bounds: np.ndarray          # (K, 2) two-sided bounds of step_anis: chi2(2 sum m) / B

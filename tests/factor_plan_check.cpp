@@ -1,0 +1,120 @@
+// Sanitizer build of plan_factor / plan_factor_apply (slam-duckietown_amd/csrc/ekf_host_plan.h), the host side of ekf_factor,
+// ekf_factor_solve and ekf_factor_multiply:
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DEKF_HOST_ONLY
+//       -I slam-duckietown_amd/csrc -I include tests/factor_plan_check.cpp -o factor_plan_check
+// Bad ranges, the workspace arithmetic at the largest sizes the library accepts (n_max = 21823 x 32 trajectories: beyond every
+// 32-bit count), ragged block counts and the grids of every block step, the refusals of the solve / multiply arguments; any
+// sanitizer report or failed check ends the run with a non-zero status.  tests/test_factor_cpu.py builds and runs it (CPU only).
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <limits>
+#include <vector>
+
+#include "ekf_host_plan.h"
+
+using namespace ekf;
+
+static long checks = 0;
+#define CHECK(cond, ...)                                              \
+  do {                                                                \
+    ++checks;                                                         \
+    if (!(cond)) {                                                    \
+      std::fprintf(stderr, "FAILED %s:%d: %s  [", __FILE__, __LINE__, #cond); \
+      std::fprintf(stderr, __VA_ARGS__);                              \
+      std::fprintf(stderr, "]\n");                                    \
+      std::exit(1);                                                   \
+    }                                                                 \
+  } while (0)
+
+int main() {
+  FactorPlan fp{};
+  {
+    HostPlan h;
+    h.batch = 3;
+    h.n = {3, 43, 193};
+    CHECK(plan_factor(&h, 0, 3, fp) == nullptr, "whole bank");
+    CHECK(fp.n_hi == 193 && fp.nblk == 4 && fp.lw == 256 && fp.tstride == 65536u && fp.words == 3u * 65536u && fp.launches == 11,
+          "%d %d %d %zu %zu %ld", fp.n_hi, fp.nblk, fp.lw, fp.tstride, fp.words, fp.launches);
+    CHECK(plan_factor(&h, 0, 2, fp) == nullptr && fp.n_hi == 43 && fp.nblk == 1 && fp.lw == 64 && fp.launches == 2, "small range");
+    CHECK(plan_factor(&h, 2, 1, fp) == nullptr && fp.n_hi == 193, "last one");
+    CHECK(plan_factor(&h, -1, 1, fp) != nullptr, "negative b0");
+    CHECK(plan_factor(&h, 0, 0, fp) != nullptr, "count 0");
+    CHECK(plan_factor(&h, 0, -2, fp) != nullptr, "negative count");
+    CHECK(plan_factor(&h, 2, 2, fp) != nullptr, "past the bank");
+    CHECK(plan_factor(&h, 3, 1, fp) != nullptr, "b0 = batch");
+    CHECK(plan_factor(&h, std::numeric_limits<int>::max(), 2, fp) != nullptr, "b0 + count would overflow");
+    CHECK(plan_factor(&h, 1, std::numeric_limits<int>::max(), fp) != nullptr, "count would overflow");
+  }
+  {
+    // the largest bank the library can be asked for: no intermediate may pass through 32 bits
+    HostPlan h;
+    h.batch = 32;
+    h.n.assign(32, EKF_N_MAX_LIMIT);
+    CHECK(plan_factor(&h, 0, 32, fp) == nullptr, "largest bank");
+    const size_t lw = 21824;
+    CHECK(fp.lw == 21824 && fp.nblk == 341 && fp.tstride == lw * lw && fp.words == lw * lw * 32, "%d %d %zu %zu", fp.lw, fp.nblk,
+          fp.tstride, fp.words);
+    CHECK(fp.words * sizeof(double) == 121929465856ull && fp.words > (size_t)std::numeric_limits<unsigned>::max(), "%zu", fp.words);
+    CHECK(fp.launches == 1 + 3L * 341 - 2, "%ld", fp.launches);
+  }
+  // every block step of every block count: the panel's threads cover the columns to the right exactly, the tiles cover the
+  // trailing blocks, the last step launches neither
+  for (int nblk = 1; nblk <= 341; ++nblk)
+    for (int k = 0; k < nblk; ++k) {
+      const int right = nblk - k - 1, g = factor_panel_groups(nblk, k), t = factor_trail_tiles_per_row(nblk, k);
+      CHECK(g * 256 >= right * FB && (g - 1) * 256 < right * FB + (right == 0 ? 256 : 0), "panel %d %d: %d", nblk, k, g);
+      CHECK(2 * t >= right && 2 * (t - 1) < right + (right == 0 ? 2 : 0), "tiles %d %d: %d", nblk, k, t);
+      CHECK((right == 0) == (g == 0) && (right == 0) == (t == 0), "last step %d %d", nblk, k);
+      CHECK((long)t * (t + 1) / 2 <= (long)std::numeric_limits<int>::max(), "grid.x %d", t);
+    }
+  // ragged banks: every size's block count and the range's stride
+  for (int n = 3; n <= 4203; n += 2) {
+    HostPlan h;
+    h.batch = 2;
+    h.n = {n, 3};
+    CHECK(plan_factor(&h, 0, 2, fp) == nullptr, "n = %d", n);
+    CHECK(fp.lw >= n && fp.lw - n < FB && fp.lw % FB == 0 && fp.nblk * FB == fp.lw, "n = %d: lw %d", n, fp.lw);
+  }
+
+  // ---- solve / multiply ----
+  HostPlan h;
+  h.batch = 4;
+  h.n = {3, 43, 193, 5};
+  FactorHeld fh;
+  bool state = false;
+  int nblk_hi = 0;
+  std::vector<double> x(2 * 16 * 200, 0.25);
+  auto why = [&](int b0, int count, const double* p, int nrhs, int stride) {
+    return plan_factor_apply(&h, fh, b0, count, p, nrhs, stride, &state, &nblk_hi);
+  };
+  CHECK(why(1, 2, x.data(), 1, 200) != nullptr && state, "no factor held");
+  fh.held = true;
+  fh.b0 = 1;
+  fh.count = 2;
+  fh.n = {43, 193};
+  fh.info = {0, 0};
+  CHECK(why(1, 2, x.data(), 16, 200) == nullptr && nblk_hi == 4, "the good call: %d", nblk_hi);
+  CHECK(why(1, 1, x.data(), 1, 43) == nullptr && nblk_hi == 1, "first of the range: %d", nblk_hi);
+  CHECK(why(2, 1, x.data(), 1, 193) == nullptr && nblk_hi == 4, "second of the range");
+  CHECK(why(0, 2, x.data(), 1, 200) != nullptr && state, "range starts before the factored one");
+  CHECK(why(2, 2, x.data(), 1, 200) != nullptr && state, "range ends behind the factored one");
+  CHECK(why(3, 2, x.data(), 1, 200) != nullptr && !state, "range outside the bank");
+  CHECK(why(-1, 1, x.data(), 1, 200) != nullptr && !state, "negative b0");
+  CHECK(why(1, 0, x.data(), 1, 200) != nullptr && !state, "count 0");
+  CHECK(why(1, 2, nullptr, 1, 200) != nullptr && !state, "NULL");
+  CHECK(why(1, 2, x.data(), 0, 200) != nullptr && !state, "nrhs 0");
+  CHECK(why(1, 2, x.data(), 17, 200) != nullptr && !state, "nrhs 17");
+  CHECK(why(1, 2, x.data(), 1, 192) != nullptr && !state, "stride below n");
+  CHECK(why(1, 2, x.data(), 1, 0) != nullptr && !state, "stride 0");
+  CHECK(why(1, 2, x.data(), 1, std::numeric_limits<int>::max()) != nullptr && !state, "stride beyond the limit");
+  x[200 + 42] = std::nan("");
+  CHECK(why(1, 2, x.data(), 2, 200) != nullptr && !state, "NaN in column 1 of the first trajectory");
+  x[200 + 42] = 0.0;
+  x[200 + 43] = std::nan("");                              // beyond the first trajectory's n: never read
+  CHECK(why(1, 2, x.data(), 2, 200) == nullptr, "entries beyond n are ignored");
+  x[(2 + 1) * 200 + 192] = std::numeric_limits<double>::infinity();
+  CHECK(why(1, 2, x.data(), 2, 200) != nullptr && !state, "infinity in the last entry of the second trajectory");
+  std::printf("%ld checks passed\n", checks);
+  return 0;
+}

@@ -1,0 +1,153 @@
+"""CPU: the host side of the device Cholesky factorisation (ekf_factor): the NumPy model of the blocked algorithm
+(tests/factor_model.py) against np.linalg.cholesky and hand-built indefinite cases, CovFactor's generation check and
+evaluation.map_nees / map_entropy / information_gain on a stand-in filter backed by the model, and plan_factor under the
+sanitizers (tests/factor_plan_check.cpp)."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import factor_model as fm
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EPS = 2.0 ** -53
+
+
+def gamma(k):
+    return k * EPS / (1.0 - k * EPS)
+
+
+@pytest.mark.parametrize("n", [3, 43, 63, 64, 65, 191, 193, 301])
+def test_model_matches_numpy(n):
+    """Structure, Higham's backward bound |U^T U - P|_F <= gamma_{n+1} | |U^T| |U| |_F, and the log-determinant."""
+    P, kappa = fm.spd(n, 100 + n)
+    U, logdet, info = fm.blocked_cholesky(P)
+    assert info == 0 and np.array_equal(U, np.triu(U)) and (np.diag(U) > 0).all()
+    assert np.linalg.norm(U.T @ U - P) <= gamma(n + 1) * np.linalg.norm(np.abs(U.T) @ np.abs(U))
+    ref = np.linalg.cholesky(P).T
+    assert abs(logdet - 2.0 * np.log(np.diag(ref)).sum()) <= 2 * n * gamma(n + 1) * kappa
+    assert abs(logdet - np.linalg.slogdet(P)[1]) <= 2 * n * gamma(n + 1) * kappa
+    assert np.allclose(U, ref, rtol=0, atol=10 * n * EPS * kappa * np.abs(ref).max())
+
+
+def test_model_reads_the_upper_triangle_only():
+    P, _ = fm.spd(70, 5)
+    Q = P.copy()
+    Q[np.tril_indices(70, -1)] = 1e300
+    assert np.array_equal(fm.blocked_cholesky(Q)[0], fm.blocked_cholesky(P)[0])
+
+
+def test_model_info_on_hand_built_cases():
+    """dpotrf's convention: the 1-based index of the first pivot that is <= 0 or not finite."""
+    assert fm.blocked_cholesky(np.diag([1.0, 2.0, 3.0]))[2] == 0
+    assert fm.blocked_cholesky(np.diag([1.0, -2.0, 3.0]))[2] == 2
+    assert fm.blocked_cholesky(np.diag([0.0, 2.0, 3.0]))[2] == 1
+    assert fm.blocked_cholesky(np.array([[1.0, 2.0, 0.0], [2.0, 1.0, 0.0], [0.0, 0.0, 1.0]]))[2] == 2   # 1 - 4 < 0
+    assert fm.blocked_cholesky(np.array([[1.0, 1.0, 0.0], [1.0, 1.0, 0.0], [0.0, 0.0, 1.0]]))[2] == 2   # singular: pivot 0
+    P, _ = fm.spd(193, 9)
+    for index in (0, 50, 63, 64, 100, 192):                 # inside the first block, at block edges, after a down-date, last
+        Q = fm.not_pd_at(P, index)
+        U, logdet, info = fm.blocked_cholesky(Q)
+        assert info == index + 1 and np.isnan(logdet) and np.isnan(U).all()
+        if index >= 1:
+            with pytest.raises(np.linalg.LinAlgError):
+                np.linalg.cholesky(Q)
+    assert fm.not_pd_at(P, 100)[100, 100] > 0               # (negative only once the rows above have been eliminated)
+    Q = P.copy()
+    Q[10, 150] = np.nan                                     # reaches the pivot of column 150 through row 10's panel
+    assert fm.blocked_cholesky(Q)[2] == 151
+    Q = P.copy()
+    Q[70, 70] = np.inf
+    assert fm.blocked_cholesky(Q)[2] == 71
+
+
+def bank(sizes=(43, 43, 43), seed=3):
+    rng = np.random.default_rng(seed)
+    covs = [fm.spd(n, seed + 10 * i)[0] for i, n in enumerate(sizes)]
+    means = [rng.standard_normal(n) for n in sizes]
+    return fm.ModelFactorFilter(means, covs), means, covs
+
+
+def test_covfactor_methods_and_generation_check():
+    from slam_duckietown_amd import EkfError
+    f, means, covs = bank((43, 5, 193))
+    fac = f.factor()
+    assert fac.n.tolist() == [43, 5, 193] and (fac.info == 0).all()
+    rng = np.random.default_rng(0)
+    e = rng.standard_normal((3, 20, 193))                   # 20 vectors: two calls of EKF_FACTOR_RHS
+    q, w = fac.mahalanobis(e), fac.whiten(e)
+    assert q.shape == (3, 20) and w.shape == (3, 20, 193)
+    for b, n in enumerate((43, 5, 193)):
+        ref = np.einsum("ki,ik->k", e[b, :, :n], np.linalg.solve(covs[b], e[b, :, :n].T))
+        assert np.allclose(q[b], ref, rtol=1e-10) and np.isnan(w[b, :, n:]).all()
+        assert np.allclose(fac.multiply(w)[b, :, :n], e[b, :, :n], atol=1e-10)
+        assert np.allclose(fac.upper(b).T @ fac.upper(b), covs[b], atol=1e-10)
+    assert fac.mahalanobis(e[:, 0]).shape == (3,)
+    s = fac.sample(4, np.random.default_rng(1))
+    assert s.shape == (3, 4, 193) and np.isnan(s[1, :, 5:]).all() and not np.isnan(s[1, :, :5]).any()
+    one = f.factor(2)                                       # replaces `fac`
+    assert one.mahalanobis(e[2, 0]).shape == () and one.whiten(e[2, :3]).shape == (3, 193) and one.sample(2).shape == (2, 193)
+    for call in (lambda: fac.mahalanobis(e), lambda: fac.whiten(e), lambda: fac.multiply(e), lambda: fac.upper(0),
+                 lambda: fac.sample(1)):
+        with pytest.raises(EkfError, match="replaced"):
+            call()
+    f.release_factor()
+    with pytest.raises(EkfError, match="replaced"):
+        one.upper(2)
+
+
+def test_sample_covariance_is_p():
+    f, means, covs = bank((5,))
+    s = f.factor(0).sample(16 * 2000, np.random.default_rng(4))
+    assert np.allclose(s.mean(axis=0), means[0], atol=0.05) and np.allclose(np.cov(s.T), covs[0], atol=0.15)
+
+
+def test_map_nees_entropy_and_gain():
+    from slam_duckietown_amd import evaluation as ev
+    f, means, covs = bank((43, 43, 43, 43))
+    rng = np.random.default_rng(8)
+    poses = rng.standard_normal((4, 3))
+    poses[1, 2] = means[1][2] + 2 * np.pi - 0.01            # a theta error that must be wrapped
+    lms = rng.standard_normal((4, 25, 2))                   # more landmarks than the state holds: the first 20 count
+    r = ev.map_nees(f, poses, lms, confidence=0.9)
+    for b in range(4):
+        e = means[b] - np.concatenate([poses[b], lms[b, :20].reshape(-1)])
+        e[2] = ev.wrap_angle(e[2])
+        assert abs(r.nees[b] - e @ np.linalg.solve(covs[b], e)) <= 1e-10 * r.nees[b]
+    assert abs(means[1][2] - poses[1, 2]) > 6 and r.dof.tolist() == [43] * 4 and (r.info == 0).all()
+    assert r.anees == pytest.approx(r.nees.mean()) and r.bounds == ev.chi2_bounds(43, 4, 0.9)
+    fac = f.factor()
+    for b in range(4):
+        assert ev.map_entropy(fac)[b] == pytest.approx(0.5 * (43 * np.log(2 * np.pi * np.e) + np.linalg.slogdet(covs[b])[1]), rel=1e-12)
+    g = fm.ModelFactorFilter(means, [0.5 * P for P in covs])
+    assert np.allclose(ev.information_gain(fac, g.factor()), 0.5 * 43 * np.log(2.0), rtol=1e-12)
+    # sizes that differ: no bank figures; an indefinite P is reported, not folded into a NaN average
+    h = fm.ModelFactorFilter([means[0], means[1][:5]], [covs[0], covs[1][:5, :5]])
+    r = ev.map_nees(h, poses[:2], lms[:2])
+    assert r.anees is None and r.bounds is None and r.dof.tolist() == [43, 5] and np.isfinite(r.nees).all()
+    bad = fm.ModelFactorFilter(means[:2], [covs[0], fm.not_pd_at(covs[1], 7)])
+    r = ev.map_nees(bad, poses[:2], lms[:2])
+    assert r.info.tolist() == [0, 8] and np.isfinite(r.nees[0]) and np.isnan(r.nees[1])
+    with pytest.raises(ValueError):
+        ev.map_nees(f, poses, lms[:, :10])
+
+
+def test_plan_factor_under_the_sanitizers(tmp_path):
+    """tests/factor_plan_check.cpp, built and run as tests/direct_plan_check.cpp is."""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ is not available")
+    exe = tmp_path / "factor_plan_check"
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DEKF_HOST_ONLY",
+           "-Wall", "-Werror", "-I", os.path.join(ROOT, "slam-duckietown_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
+           os.path.join(ROOT, "tests", "factor_plan_check.cpp"), "-o", str(exe)]
+    built = subprocess.run(cmd, capture_output=True, text=True)
+    assert built.returncode == 0, built.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300,
+                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "checks passed" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    api = open(os.path.join(ROOT, "slam-duckietown_amd", "csrc", "ekf_api.hip")).read()
+    for fn in ("plan_factor", "plan_factor_apply"):
+        assert fn + "(" in api
