@@ -51,6 +51,8 @@ extern "C" {
 #define EKF_DMAX 256          /* detections per window for ekf_step_detections (the reference's normal mode: a 0.7 s window
                                  of every camera frame, src/replay_no_ros.py:17 -- 21 frames x a dozen tags) */
 #define EKF_JMAX 64           /* landmarks per trajectory in one ekf_download_joint (sub-state of up to 3 + 2*64 = 131) */
+#define EKF_LINEAR_LMAX 16   /* landmarks in the sub-state of one ekf_update_linear: ns <= 3 + 2*16 = 35 */
+#define EKF_LINEAR_ROWS 32   /* measurement rows D per trajectory of one ekf_update_linear (whole k-tiles of 4) */
 #define EKF_AMAX 32           /* distinct tags per window the device-side association takes (two update passes of EKF_MMAX) */
 
 typedef struct ekf_handle ekf_handle;
@@ -326,6 +328,49 @@ int ekf_remove_landmarks(ekf_handle *h, int b, const int *landmarks, int k);
 int ekf_update_direct(ekf_handle *h, int b0, int count, const int *target, const double *z, const double *R,
                       const int *m, int stride, const double *gate, double *nis, int *dof, int *applied);
 
+/* Linear measurement update: any measurement the caller can write as  r = H_s x[s] + v,  v ~ N(0, R),  over a small SUB-STATE
+ * -- "landmark j lies 0.585 m east of landmark i", "these two landmarks are the same tag" (l_i - l_j = 0, then
+ * ekf_remove_landmarks), a range-only beacon, a bearing-only camera, a lane-relative heading, any model linearised at the
+ * current mean.  The sub-state is named exactly as ekf_download_joint names it: trajectory bi of [b0, b0+count) lists k[bi] <=
+ * lstride <= EKF_LINEAR_LMAX landmarks in landmarks[bi*lstride + 0..k[bi]), in any order and none twice; its sub-state is
+ * [x, y, theta, l_j0 x, l_j0 y, l_j1 x, ...] in the order given, ns = 3 + 2*lstride; k[bi] = 0 is the pose alone.
+ * H is count x dstride x ns (row-major), r count x dstride, R count x dstride x dstride (a dense noise covariance of which only
+ * the upper triangle is read).  Trajectory bi uses the leading d[bi] <= dstride <= EKF_LINEAR_ROWS rows and the leading
+ * 3 + 2*k[bi] columns of H; nothing beyond those is read.
+ * innovation == 0: r is the measurement z and the device forms y = z - H_s mu[s] from the mean it is about to update; no row is
+ * wrapped (a linear constraint that involves theta has to come as an innovation).  innovation == 1: r is the innovation y
+ * itself -- the form for a model linearised by the caller at the mean ekf_download_joint returned (both calls are blocking and
+ * nothing moves between them).  Jointly over all rows,
+ *     S = H_s P[s,s] H_s^T + R,   mu += P[:,s] H_s^T S^-1 y,   P -= P[:,s] H_s^T S^-1 H_s P[s,:]
+ * on the stored upper triangle; theta of the mean is not re-wrapped.
+ * What follows is ekf_update_direct's, word for word where it applies (see there): P is the CURRENT covariance, the pending
+ * update is applied first -- a covariance pass the caller pays for --, then one kernel (k_linear, a workgroup per trajectory)
+ * and ONE more covariance pass for the whole call.  nis[bi] = y^T S^-1 y (may be NULL; 0 for d[bi] = 0).  gate (count doubles;
+ * NULL or INFINITY: none): a trajectory whose NIS exceeds gate[bi] is REJECTED AS A WHOLE, its mean and covariance stay bit for
+ * bit.  A trajectory whose S fails to factor (a pivot <= 0 or not finite) is rejected the same way, on the device, and gets
+ * EKF_FLAG_NONFINITE.  applied[bi] (may be NULL): 1 applied, 0 rejected or d[bi] = 0.  A trajectory with d[bi] = 0, or outside
+ * the range, is untouched bit for bit.  Blocking, and stream-ordered behind everything enqueued.  Writes no innovation-log or
+ * pose-log row, changes no gate counter, noise row, size, tag table or uploaded stream (which stays runnable).  Afterwards
+ * nothing is pending; a handle on the small-state path stays on it.
+ * THE ACTIVE BOUND is where the call differs: a general row ties its targets together, so for every trajectory of the range
+ * with d[bi] > 0 the bound is raised to cover the highest landmark of its sub-state before the kernel runs, as a landmark
+ * update of that landmark raises it (also where the gate then rejects: the bound is conservative).  There is no closed-form
+ * branch for never-observed landmarks.  (The cross terms of P_base beyond the old bound are exact zeros: ekf_upload_state_diag
+ * and ekf_add_landmarks write them, ekf_remove_landmarks moves them unchanged, and nothing writes beyond the bound; the
+ * stream's own rise of the bound relies on the same.)
+ * A zero row of H is legal (S keeps R's row).
+ * EKF_ERR_ARG (nothing changed, the handle usable): a bad trajectory range, lstride outside 1..EKF_LINEAR_LMAX, dstride outside
+ * 1..EKF_LINEAR_ROWS, k[bi] outside 0..lstride, d[bi] outside 0..dstride, a landmark index outside that trajectory's map or
+ * named twice, a non-finite H, r, R or gate, gate[bi] <= 0, an R whose leading d x d block is not positive definite (Cholesky
+ * of its upper triangle), NULL landmarks, k, H, r, R or d.  EKF_ERR_STATE if a trajectory of the range carries
+ * EKF_FLAG_INTERNAL or an earlier call failed half way (as the downloads).
+ * Measured on one MI355X (tools/linear_update_time.py, profiles/linear_update.txt), per call for the whole bank: 32 x N = 2000
+ * 1.3 ms with 4 rows per trajectory, 1.9 ms with 32 (k_linear 0.04 / 0.44 ms, the pass 0.68 ms; ekf_update_direct with as many rows
+ * 1.3 / 2.0 ms); 1 x N = 2000 with 32 rows 0.5 ms, of which k_linear's one workgroup is 0.39 ms. */
+int ekf_update_linear(ekf_handle *h, int b0, int count, const int *landmarks, const int *k, int lstride,
+                      const double *H, const double *r, const double *R, const int *d, int dstride,
+                      int innovation, const double *gate, double *nis, int *applied);
+
 /* Fork / checkpoint on the device: copy the complete filter state of trajectory src_b[i] of `src` to trajectory dst_b[i] of
  * `dst`, i < k, without leaving HBM.  src == dst is allowed (fork inside a bank); otherwise both handles must be on the same
  * device.  One source may fan out to many destinations (one launch for all pairs; a source tile is read once for up to 32 of
@@ -442,7 +487,7 @@ int ekf_profile_read(ekf_handle *h, double *pass_ms_total, long long *pass_launc
 long long ekf_profile_passes(ekf_handle *h);
 /* With ekf_set_option("profile_kernels", 1) (a diagnostic run: every record costs its stream ~6 us) the other launches of a
  * fused cadence carry event pairs too: cls 1 the solve launch, 2 the chain (or look-ahead gather) launch, 3 the panel launch,
- * 0 the pass; 4 the k_direct launch of ekf_update_direct.  Does not reset: read before ekf_profile_read. */
+ * 0 the pass; 4 the k_direct launch of ekf_update_direct; 5 the k_linear launch of ekf_update_linear.  Does not reset: read before ekf_profile_read. */
 int ekf_profile_read_class(ekf_handle *h, int cls, double *ms_total, long long *launches);
 /* Options: name (default, allowed values) meaning.  Unknown names and values out of range fail with EKF_ERR_ARG.
  *   "flush_every"         (0, 0..64)    steps per covariance pass; 0 = auto, by "rank_limit"

@@ -241,6 +241,12 @@ struct ekf_handle : ekf::HostPlan {
   ekf::DirectPlan direct_plan;
   std::vector<int> direct_ints;
   std::vector<double> direct_dbls, direct_out;
+  // ekf_update_linear (allocated on first use): the same for k_linear -- LINEAR_INTS ints, linear_dbls(rows cap, columns) doubles
+  // and the two results per trajectory of the bank
+  DeviceBuf<double> dlinear;
+  ekf::LinearPlan linear_plan;
+  std::vector<int> linear_ints;
+  std::vector<double> linear_dbls, linear_out;
   std::string err;
 };
 
@@ -1501,6 +1507,79 @@ extern "C" int ekf_update_direct(ekf_handle* h, int b0, int count, const int* ta
     if (nis) nis[bi] = any ? h->direct_out[2 * (size_t)(b0 + bi)] : 0.0;
     if (dof) dof[bi] = dp.D[bi];
     if (applied) applied[bi] = any && h->direct_out[2 * (size_t)(b0 + bi) + 1] != 0.0 ? 1 : 0;
+  }
+  return EKF_OK;
+}
+
+// Linear measurements (k_linear, ekf_linear.hip): ekf_update_direct's body with a dense H over a small sub-state -- apply what
+// is pending, let k_linear form the mean and the update's ranks V = H_s P[s, :], W = -(S^-1 V)^T from P_base, then run the
+// covariance pass on them.  Unlike a direct fix a general row correlates its targets: the active bound of every trajectory that
+// brings rows is raised over the highest landmark of its sub-state first, as a landmark update of it would (fill_step).
+extern "C" int ekf_update_linear(ekf_handle* h, int b0, int count, const int* landmarks, const int* k, int lstride, const double* H,
+                                 const double* r, const double* R, const int* d, int dstride, int innovation, const double* gate,
+                                 double* nis, int* applied) {
+  if (int rc = check_b(h, 0, "ekf_update_linear")) return rc;        // (refreshes the sizes a device-side association grew)
+  LinearPlan& lp = h->linear_plan;
+  if (const char* why = plan_linear(h, b0, count, landmarks, k, lstride, H, r, R, d, dstride, gate, lp))
+    return fail(h, EKF_ERR_ARG, std::string("ekf_update_linear: ") + why);
+  HIP_TRY(h, hipSetDevice(h->device));
+  for (int b = b0; b < b0 + count; ++b)
+    if (int rc = check_internal(h, b, "ekf_update_linear")) return rc;
+  const size_t B = (size_t)h->batch;
+  const int dp = linear_rows_cap(lp.kpad), nsl = 3 + 2 * lstride;
+  const size_t int_words = B * LINEAR_INTS / 2, per = (size_t)linear_dbls(dp, nsl);   // layout (doubles): plan, measurements, results
+  RES_TRY(h, "ekf_update_linear's tables", h->dlinear.ensure(int_words + B * per + 2 * B));
+  if (int rc = flush_pending(h)) return rc;
+  for (int bi = 0; bi < count; ++bi)                   // the bound covers the sub-state of every trajectory that brings rows
+    if (lp.D[bi] > 0) h->neff[b0 + bi] = std::min(h->n[b0 + bi], std::max(h->neff[b0 + bi], 3 + 2 * (lp.lmax[bi] + 1)));
+  h->linear_ints.assign(B * LINEAR_INTS, 0);
+  h->linear_dbls.assign(B * per, 0.0);
+  h->linear_out.assign(2 * B, 0.0);
+  for (size_t b = 0; b < B; ++b) {
+    int* pi = h->linear_ints.data() + b * LINEAR_INTS;
+    pi[1] = h->opt_active_bound ? std::min(h->neff[b], h->n[b]) : h->n[b];
+    pi[2] = 3;
+    for (int j = 0; j <= LINEAR_NS; ++j) pi[4 + j] = j < 3 ? j : -1;
+  }
+  for (int bi = 0; bi < count; ++bi) {
+    int* pi = h->linear_ints.data() + (size_t)(b0 + bi) * LINEAR_INTS;
+    double* pd = h->linear_dbls.data() + (size_t)(b0 + bi) * per;
+    const int D = lp.D[bi], ns = lp.ns[bi];
+    pi[0] = D;
+    pi[2] = ns;
+    std::copy_n(lp.s.data() + (size_t)bi * LINEAR_NS, LINEAR_NS, pi + 4);
+    for (int a = 0; a < D; ++a) {
+      std::copy_n(H + ((size_t)bi * dstride + a) * nsl, ns, pd + (size_t)a * nsl);
+      pd[(size_t)dp * nsl + a] = r[(size_t)bi * dstride + a];
+      for (int q = a; q < D; ++q) pd[(size_t)dp * nsl + dp + (size_t)a * dp + q] = R[((size_t)bi * dstride + a) * dstride + q];
+    }
+    pd[(size_t)dp * nsl + dp + (size_t)dp * dp] = gate ? gate[bi] : INFINITY;
+  }
+  if (lp.kpad > 0) {
+    int* dplan = reinterpret_cast<int*>(h->dlinear.p);
+    double* dmeas = h->dlinear.p + int_words;
+    double* dout = dmeas + B * per;
+    HIP_TRY(h, hipMemcpyAsync(dplan, h->linear_ints.data(), sizeof(int) * h->linear_ints.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(dmeas, h->linear_dbls.data(), sizeof(double) * h->linear_dbls.size(), hipMemcpyHostToDevice, h->stream));
+    ProfBracket pb;
+    if (int rc = prof_open(h, 5, h->stream, &pb)) return rc;
+    launch_linear(h->stream, dp, bank_view(h), h->ddacc2[h->dcur].p, h->dmu2[h->cur].p, dplan, dmeas, dout, lp.kpad, nsl, innovation ? 1 : 0);
+    if (int rc = prof_close(h, &pb)) return rc;
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(h->linear_out.data(), dout, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->stream));
+    // the pass: the ranks k_linear left, over the bounds it left (neff_enq mirrors dso[b].neff for the planner)
+    for (size_t b = 0; b < B; ++b) h->neff_enq[b] = h->linear_ints[b * LINEAR_INTS + 1];
+    h->pending_k = lp.kpad;
+    if (int rc = flush_pending(h)) {
+      for (int b = b0; b < b0 + count; ++b) h->host_bad[b] = 1;       // (the mean has moved, the covariance has not)
+      return rc;
+    }
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (int bi = 0; bi < count; ++bi) {
+    const bool any = lp.D[bi] > 0;
+    if (nis) nis[bi] = any ? h->linear_out[2 * (size_t)(b0 + bi)] : 0.0;
+    if (applied) applied[bi] = any && h->linear_out[2 * (size_t)(b0 + bi) + 1] != 0.0 ? 1 : 0;
   }
   return EKF_OK;
 }

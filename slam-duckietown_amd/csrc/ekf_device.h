@@ -53,6 +53,18 @@ constexpr int DIRECT_ROWS = 36;
 constexpr int DIRECT_INTS = 2 + 2 * DIRECT_ROWS;
 constexpr int DIRECT_DBLS = MMAX * 12 + 2;
 static_assert(3 + 2 * (MMAX - 1) <= DIRECT_ROWS && DIRECT_ROWS % 4 == 0 && DIRECT_ROWS <= KTOT, "a direct update's rows fit the pending ranks");
+// ekf_update_linear (k_linear, ekf_linear.hip): a trajectory brings up to LINEAR_ROWS measurement rows over the pose and up to
+// LINEAR_LMAX landmarks.  What the launch reads per trajectory of the BANK (trajectories outside the call's range carry D = 0):
+// LINEAR_INTS ints {D, active bound (already raised over the sub-state), sub-state size ns, 0, state index of sub-state entry j
+// (LINEAR_NS, -1 beyond ns)} and linear_dbls(dp, nsl) doubles packed by the launch's row cap dp and column count nsl = 3 + 2 *
+// lstride: H (dp x nsl, row-major), r (dp), R (dp x dp, row-major, the upper triangle), gate, pad.
+constexpr int LINEAR_LMAX = EKF_LINEAR_LMAX;
+constexpr int LINEAR_ROWS = EKF_LINEAR_ROWS;
+constexpr int LINEAR_NS = 3 + 2 * LINEAR_LMAX;
+constexpr int LINEAR_INTS = 4 + LINEAR_NS + 1;
+__host__ __device__ constexpr int linear_dbls(int dp, int nsl) { return dp * nsl + dp + dp * dp + 2; }
+static_assert(LINEAR_NS <= DIRECT_ROWS && LINEAR_ROWS % 4 == 0 && LINEAR_ROWS <= KTOT && LINEAR_INTS % 2 == 0,
+              "a linear update's rows fit the pending ranks");
 __host__ __device__ __forceinline__ int p_lds(int ld) { return ld < PPW ? ld : PPW; }
 __host__ __device__ __forceinline__ long p_col(int ld, int j) { return (long)(j >> 12) * ((long)ld * PPW) + (j & (PPW - 1)); }
 // the same as a 32-bit byte offset (ekf_create bounds one covariance by 4 GiB)

@@ -782,6 +782,80 @@ inline const char* plan_direct(const HostPlan* h, int b0, int count, const int* 
 // the instantiation of k_direct that serves `kpad` rows: the smallest compile-time row count that holds them
 inline int direct_rows_cap(int kpad) { return kpad <= 4 ? 4 : kpad <= 8 ? 8 : kpad <= 16 ? 16 : DIRECT_ROWS; }
 
+// ekf_update_linear (k_linear, ekf_linear.hip): the measurements of trajectories [b0, b0 + count) checked -- the range inside
+// the bank, lstride in 1..EKF_LINEAR_LMAX, dstride in 1..EKF_LINEAR_ROWS, k[bi] in 0..lstride, d[bi] in 0..dstride, every
+// landmark inside its trajectory's map and none twice, finite H, r, R (what is read of them: the leading d rows, 3 + 2 k
+// columns, R's upper triangle) and gate, gate > 0, every R positive definite (Cholesky of the upper triangle, on the host) --
+// and turned into the plan: per trajectory of the range its row count D, sub-state size ns = 3 + 2 k, the state index of every
+// sub-state entry in the order given, its highest landmark (-1: the pose alone; what the active bound has to cover), and
+// `kpad`, the largest D padded to a whole k-tile (what the covariance pass behind the launch applies).
+// Returns nullptr, or what is wrong with the arguments (then nothing of `lp` is to be used).
+struct LinearPlan {
+  int kpad = 0;
+  std::vector<int> D, ns, lmax;    // count
+  std::vector<int> s;              // count x LINEAR_NS (-1 beyond ns)
+};
+inline const char* plan_linear(const HostPlan* h, int b0, int count, const int* landmarks, const int* k, int lstride,
+                               const double* H, const double* r, const double* R, const int* d, int dstride, const double* gate,
+                               LinearPlan& lp) {
+  if (!bank_range_ok(h, b0, count)) return BANK_RANGE_WHY;
+  if (lstride < 1 || lstride > LINEAR_LMAX) return "lstride outside 1..EKF_LINEAR_LMAX";
+  if (dstride < 1 || dstride > LINEAR_ROWS) return "dstride outside 1..EKF_LINEAR_ROWS";
+  if (!landmarks || !k || !H || !r || !R || !d) return "NULL landmarks, k, H, r, R or d";
+  const int nsl = 3 + 2 * lstride;
+  lp.kpad = 0;
+  lp.D.assign((size_t)count, 0);
+  lp.ns.assign((size_t)count, 3);
+  lp.lmax.assign((size_t)count, -1);
+  lp.s.assign((size_t)count * LINEAR_NS, -1);
+  double c[LINEAR_ROWS][LINEAR_ROWS];
+  for (int bi = 0; bi < count; ++bi) {
+    const int nl = (h->n[b0 + bi] - 3) / 2, kk = k[bi], D = d[bi];
+    if (kk < 0 || kk > lstride) return "k[b] outside 0..lstride";
+    if (D < 0 || D > dstride) return "d[b] outside 0..dstride";
+    if (gate && !(gate[bi] > 0.0)) return "gate[b] must be > 0 (INFINITY: none) and not NaN";
+    const int* lm = landmarks + (size_t)bi * lstride;
+    int* s = lp.s.data() + (size_t)bi * LINEAR_NS;
+    for (int a = 0; a < 3; ++a) s[a] = a;
+    for (int p = 0; p < kk; ++p) {
+      if (lm[p] < 0 || lm[p] >= nl) return "landmark index outside the trajectory's map";
+      for (int q = 0; q < p; ++q)
+        if (lm[q] == lm[p]) return "landmark index named twice in one trajectory";
+      s[3 + 2 * p] = 3 + 2 * lm[p];
+      s[4 + 2 * p] = 4 + 2 * lm[p];
+      lp.lmax[bi] = std::max(lp.lmax[bi], lm[p]);
+    }
+    const int ns = 3 + 2 * kk;
+    const double* Hb = H + (size_t)bi * dstride * nsl;
+    const double* rb = r + (size_t)bi * dstride;
+    const double* Rb = R + (size_t)bi * dstride * dstride;
+    for (int a = 0; a < D; ++a) {
+      if (!std::isfinite(rb[a])) return "non-finite r";
+      for (int j = 0; j < ns; ++j)
+        if (!std::isfinite(Hb[(size_t)a * nsl + j])) return "non-finite H";
+      for (int q = a; q < D; ++q)
+        if (!std::isfinite(Rb[(size_t)a * dstride + q])) return "non-finite R";
+    }
+    for (int j = 0; j < D; ++j) {                        // Cholesky of the upper triangle, lower factor in c
+      double v = Rb[(size_t)j * dstride + j];
+      for (int q = 0; q < j; ++q) v -= c[j][q] * c[j][q];
+      if (!(v > 0.0) || !std::isfinite(v)) return "R is not positive definite";
+      c[j][j] = std::sqrt(v);
+      for (int a = j + 1; a < D; ++a) {
+        double w = Rb[(size_t)j * dstride + a];
+        for (int q = 0; q < j; ++q) w -= c[a][q] * c[j][q];
+        c[a][j] = w / c[j][j];
+      }
+    }
+    lp.D[bi] = D;
+    lp.ns[bi] = ns;
+    lp.kpad = std::max(lp.kpad, (D + 3) & ~3);
+  }
+  return nullptr;
+}
+// the instantiation of k_linear that serves `kpad` rows: the smallest compile-time row count that holds them
+inline int linear_rows_cap(int kpad) { return kpad <= 4 ? 4 : kpad <= 8 ? 8 : kpad <= 16 ? 16 : LINEAR_ROWS; }
+
 // ekf_copy_trajectories (k_copy_traj, ekf_copy.hip): the k pairs (src_b[i] of `src` -> dst_b[i] of `dst`) checked -- indices
 // inside their banks, no destination twice, inside one handle no trajectory both read and written, the same device, every
 // source's size within the destination's n_max -- and grouped by source: a group is one source and up to COPY_FANOUT of its

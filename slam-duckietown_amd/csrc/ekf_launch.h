@@ -105,12 +105,15 @@ void launch_factor_solve(hipStream_t st, const FactorView& w, int f0, int count,
                          double* white, double* quad);
 void launch_factor_multiply(hipStream_t st, const FactorView& w, int f0, int count, int nblk_hi, const double* z, int nrhs,
                             int stride, double* out);
-// ---- state surgery (ekf_remove.hip, ekf_direct.hip, ekf_copy.hip, ekf_dense.hip) ----
+// ---- state surgery (ekf_remove.hip, ekf_direct.hip, ekf_linear.hip, ekf_copy.hip, ekf_dense.hip) ----
 // rp.rows: the launch's largest new size (grid rows); nb trajectories from b0; src / dst: rp's tables on the device
 void launch_remove(hipStream_t st, const BankView& k, double* mu, const RemovePlan& rp, const int* src, const int* dst,
                    unsigned* rflag, int b0, int nb, unsigned seq);
 void launch_direct(hipStream_t st, int rows_cap, const BankView& k, double* dacc, double* mu, const int* plan, const double* meas,
                    double* out, int kpad);
+// rows_cap: linear_rows_cap(kpad); nsl = 3 + 2 * lstride, the columns of the call's H; meas: linear_dbls(rows_cap, nsl) per trajectory
+void launch_linear(hipStream_t st, int rows_cap, const BankView& k, double* dacc, double* mu, const int* plan, const double* meas,
+                   double* out, int kpad, int nsl, int innovation);
 // groups x (tiles of the largest source + 1) workgroups; tab: plan_copy's table on the device
 void launch_copy_traj(hipStream_t st, bool nt, const BankView& src, const BankView& dst, const double* mus, double* mud,
                       const int* tab, int groups, int n_hi);

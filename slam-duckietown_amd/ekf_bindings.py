@@ -38,6 +38,8 @@ EKF_MMAX = 16
 EKF_JMAX = 64                     # landmarks per trajectory in one joint() query
 EKF_DIRECT_POSE = -1              # update_direct target: x, y, theta (3 rows)
 EKF_DIRECT_POSITION = -2          # update_direct target: x, y (2 rows); a target l >= 0 is landmark l's x, y
+EKF_LINEAR_LMAX = 16              # update_linear: landmarks of the sub-state
+EKF_LINEAR_ROWS = 32              # update_linear: measurement rows per trajectory
 EKF_FLAG_NONFINITE = 1
 EKF_FLAG_ASSOC = 2
 EKF_FLAG_INTERNAL = 4             # a bounded wait of a single-launch step timed out: sync()/state()/mean() raise EkfError
@@ -121,6 +123,7 @@ ABI = {
     "ekf_download_factor": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int]),
     "ekf_factor_release": (C.c_int, [C.c_void_p]),
     "ekf_update_direct": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _dp, _dp, _ip, C.c_int, _dp, _dp, _ip, _ip]),
+    "ekf_update_linear": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, C.c_int, _dp, _dp, _dp, _ip, C.c_int, C.c_int, _dp, _dp, _ip]),
     "ekf_state_size": (C.c_int, [C.c_void_p, C.c_int, _ip]),
     "ekf_log_innovations": (C.c_int, [C.c_void_p, C.c_int]),
     "ekf_innovation_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
@@ -343,6 +346,15 @@ class DirectUpdate(typing.NamedTuple):
     """What ``update_direct`` reports per trajectory of the bank: the joint NIS y^T S^-1 y of its fixes, their stacked row
     count D (the NIS's degrees of freedom) and whether they were applied (False: rejected by the gate or a singular S, or
     the trajectory brought no fix)."""
+    nis: np.ndarray        # (B,)
+    dof: np.ndarray        # (B,) int32
+    applied: np.ndarray    # (B,) bool
+
+
+class LinearUpdate(typing.NamedTuple):
+    """What ``update_linear`` reports per trajectory of the bank: the joint NIS y^T S^-1 y of its rows, their number D (the
+    NIS's degrees of freedom) and whether they were applied (False: rejected by the gate or a singular S, or the trajectory
+    brought no row)."""
     nis: np.ndarray        # (B,)
     dof: np.ndarray        # (B,) int32
     applied: np.ndarray    # (B,) bool
@@ -744,6 +756,137 @@ class EkfSlam:
             targets[t], z[t], R[t] = lm, list(xy), list(cov)
         gate = None if confidence is None else self._chi2_gate(confidence, np.array([2 * len(x) for x in targets]))
         return self.update_direct(targets, z, R, gate=gate)
+
+    # -- linear measurements -------------------------------------------------------------------
+    def update_linear(self, landmarks, H, R, z=None, innovation=None, gate=None, b: Optional[int] = None) -> "LinearUpdate":
+        """Linear measurements ``z = H x[s] + v, v ~ N(0, R)`` over the sub-state ``[x, y, theta, l_j0 x, l_j0 y, ...]`` of the
+        pose and the listed landmarks (``ekf_update_linear``; the sub-state is ``joint(landmarks)``'s): per trajectory a
+        landmark list (at most EKF_LINEAR_LMAX, any order, none twice; empty: the pose alone), ``H`` (D, 3 + 2 k), ``R``
+        (D, D; the upper triangle is read) and exactly one of ``z`` (D,: the device forms y = z - H mu[s], no row wrapped) and
+        ``innovation`` (D,: y itself, for a model linearised at the mean ``joint`` returned).  D <= EKF_LINEAR_ROWS; all rows
+        of a trajectory are applied jointly.  ``b`` None: one entry per trajectory of the bank (a trajectory with no rows
+        passes ``H`` of shape (0, ...) or ``None``); or padded arrays -- ``landmarks = (lm (B, L), k (B,))``, ``H`` (B, Ds, 3 + 2 L),
+        ``R`` (B, Ds, Ds), ``z`` / ``innovation`` ``= (values (B, Ds), d (B,))``.  ``b`` given: that trajectory's arrays alone.
+        ``gate`` (scalar or one per trajectory, None: no gate): a trajectory whose joint NIS exceeds it is rejected as a whole.
+        The pending update is applied first (a covariance pass), the rows cost one kernel and one more pass whatever their
+        number.  The active bound rises over the highest landmark named."""
+        if (z is None) == (innovation is None):
+            raise ValueError("update_linear: exactly one of z and innovation expected")
+        rr, mode = (z, 0) if innovation is None else (innovation, 1)
+        B = self.batch
+        if isinstance(landmarks, tuple) and isinstance(rr, tuple) and b is None:
+            lm, kk = _i32(landmarks[0]), _i32(landmarks[1])
+            rv, dd = _f64(rr[0]), _i32(rr[1])
+            if lm.ndim != 2 or rv.ndim != 2 or lm.shape[0] != B or rv.shape[0] != B or kk.shape != (B,) or dd.shape != (B,):
+                raise ValueError("update_linear: (B, L) landmarks with (B,) k and (B, Ds) values with (B,) d expected")
+            ls, ds = lm.shape[1], rv.shape[1]
+            HH, RR = _f64(H, (B, ds, 3 + 2 * ls)), _f64(R, (B, ds, ds))
+            b0, count = 0, B
+        else:
+            if b is not None:
+                b0, count = int(b), 1
+                landmarks, H, R, rr = (landmarks,), (H,), (R,), (rr,)
+            else:
+                b0, count = 0, B
+            if len(landmarks) != count or len(H) != count or len(R) != count or len(rr) != count:
+                raise ValueError("update_linear: one landmark list, H, R and z / innovation per trajectory expected")
+            lists = [np.asarray(x if x is not None else [], dtype=np.int64).reshape(-1) for x in landmarks]
+            vals = [np.asarray(x if x is not None else [], dtype=np.float64).reshape(-1) for x in rr]
+            kk = np.array([len(x) for x in lists], dtype=np.int32)
+            dd = np.array([len(x) for x in vals], dtype=np.int32)
+            ls, ds = max(1, int(kk.max())), max(1, int(dd.max()))
+            lm = np.zeros((count, ls), dtype=np.int32)
+            HH, RR, rv = np.zeros((count, ds, 3 + 2 * ls)), np.zeros((count, ds, ds)), np.zeros((count, ds))
+            for t in range(count):
+                D, ns = int(dd[t]), 3 + 2 * int(kk[t])
+                if lists[t].size and (lists[t].min() < np.iinfo(np.int32).min or lists[t].max() > np.iinfo(np.int32).max):
+                    raise ValueError("update_linear: landmark index outside the state")
+                lm[t, :kk[t]] = lists[t]
+                if D == 0:
+                    continue
+                Ht, Rt = np.asarray(H[t], dtype=np.float64), np.asarray(R[t], dtype=np.float64)
+                if Ht.shape != (D, ns) or Rt.shape != (D, D):
+                    raise ValueError(f"update_linear: {D} rows over {int(kk[t])} landmarks need H ({D}, {ns}) and R ({D}, {D}), "
+                                     f"got {Ht.shape} and {Rt.shape}")
+                HH[t, :D, :ns], RR[t, :D, :D], rv[t, :D] = Ht, Rt, vals[t]
+        if ls > EKF_LINEAR_LMAX or ds > EKF_LINEAR_ROWS:
+            raise ValueError(f"update_linear: at most EKF_LINEAR_LMAX = {EKF_LINEAR_LMAX} landmarks and EKF_LINEAR_ROWS = "
+                             f"{EKF_LINEAR_ROWS} rows per trajectory, got {ls} and {ds}")
+        g = None
+        if gate is not None:
+            g = np.empty(count)
+            if count == B:
+                self._per_traj(gate, "gate", g)
+            else:
+                g[:] = gate
+        nis, applied = np.empty(count), np.empty(count, dtype=np.int32)
+        self._check(self._lib.ekf_update_linear(self._h, b0, count, _p(lm, _ip), _p(kk, _ip), ls, _p(HH), _p(rv), _p(RR), _p(dd, _ip),
+                                                ds, mode, _p(g) if g is not None else None, _p(nis), _p(applied, _ip)))
+        if count != B:                                       # (per trajectory of the bank, as update_direct reports)
+            full = np.zeros(B), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+            full[0][b0], full[1][b0], full[2][b0] = nis[0], dd[0], applied[0]
+            nis, dd, applied = full
+        return LinearUpdate(nis, dd.copy(), applied.astype(bool))
+
+    def constrain_landmarks(self, i, j, offset, cov, b: Optional[int] = None, confidence: Optional[float] = None):
+        """Relative constraints between landmarks: ``l_j - l_i = offset + v, v ~ N(0, cov)`` -- "tag j lies 0.585 m east of
+        tag i" from a surveyed map that knows no world frame, or, with a zero offset and a tiny `cov`, "i and j are the same
+        tag" (then ``remove_landmarks([j])`` merges them).  ``i``, ``j``: one index each or K of them, ``offset`` (K, 2),
+        `cov` 2 x 2 (one for all) or (K, 2, 2); one row pair per constraint, all K applied jointly in one call (the distinct
+        landmarks of a call number at most EKF_LINEAR_LMAX, the constraints EKF_LINEAR_ROWS // 2).  ``b`` None: the same
+        constraints for every trajectory of the bank; else trajectory b alone.  ``confidence`` gates the joint update at the
+        chi-square quantile of its 2 K rows.  Returns ``LinearUpdate``."""
+        ii, jj = np.asarray(i, dtype=np.int64).reshape(-1), np.asarray(j, dtype=np.int64).reshape(-1)
+        K = len(ii)
+        if len(jj) != K or K == 0:
+            raise ValueError("constrain_landmarks: as many i as j, and at least one, expected")
+        if (ii == jj).any():
+            raise ValueError("constrain_landmarks: a constraint names one landmark twice")
+        off = np.broadcast_to(np.asarray(offset, dtype=np.float64), (K, 2))
+        cv = np.broadcast_to(np.asarray(cov, dtype=np.float64), (K, 2, 2))
+        lms = sorted({int(x) for x in ii} | {int(x) for x in jj})
+        place = {l: 3 + 2 * p for p, l in enumerate(lms)}
+        H, R = np.zeros((2 * K, 3 + 2 * len(lms))), np.zeros((2 * K, 2 * K))
+        for c in range(K):
+            for a in range(2):
+                H[2 * c + a, place[int(jj[c])] + a] = 1.0
+                H[2 * c + a, place[int(ii[c])] + a] = -1.0
+            R[2 * c:2 * c + 2, 2 * c:2 * c + 2] = cv[c]
+        gate = None if confidence is None else float(self._chi2_gate(confidence, 2 * K))
+        if b is not None:
+            return self.update_linear(lms, H, R, z=off.reshape(-1), gate=gate, b=b)
+        B = self.batch
+        return self.update_linear([lms] * B, [H] * B, [R] * B, z=[off.reshape(-1)] * B, gate=gate)
+
+    def update_custom(self, landmarks, h, z, R, jac=None, wrap=None, b: int = 0, confidence: Optional[float] = None,
+                      step: float = 1e-5):
+        """A measurement model of the caller's: ``z = h(x_s) + v, v ~ N(0, R)`` with ``x_s`` the sub-state of the pose and
+        `landmarks` of trajectory b (``joint(landmarks, b)``'s order).  Reads the sub-mean (``joint``: no covariance pass),
+        evaluates ``h`` and its Jacobian there -- ``jac(x_s)`` (D, ns), or central differences of ``h`` with the absolute
+        `step` per coordinate when ``jac`` is None (error of a Jacobian entry: step^2 / 6 |h'''| + eps (|h| + |x|) / step) --, forms
+        the innovation ``z - h(x_s)`` with the rows listed in ``wrap`` (angles) wrapped to [-pi, pi), and applies it with
+        ``update_linear`` in innovation mode.  ``confidence`` gates at the chi-square quantile of the D rows."""
+        lms = [int(x) for x in np.asarray(landmarks, dtype=np.int64).reshape(-1)]
+        xs, _ = self.joint(lms, b)
+        xs = np.array(xs, dtype=np.float64)
+        z = np.asarray(z, dtype=np.float64).reshape(-1)
+        h0 = np.asarray(h(xs), dtype=np.float64).reshape(-1)
+        if h0.shape != z.shape:
+            raise ValueError(f"update_custom: h returns {h0.shape[0]} values for {z.shape[0]} measurements")
+        if jac is not None:
+            J = np.asarray(jac(xs), dtype=np.float64).reshape(len(z), len(xs))
+        else:
+            J = np.empty((len(z), len(xs)))
+            for c in range(len(xs)):
+                e = np.zeros(len(xs))
+                e[c] = step
+                J[:, c] = (np.asarray(h(xs + e), dtype=np.float64).reshape(-1) - np.asarray(h(xs - e), dtype=np.float64).reshape(-1)) / (2.0 * step)
+        y = z - h0
+        if wrap is not None:
+            rows = np.asarray(wrap, dtype=np.int64).reshape(-1)
+            y[rows] = (y[rows] + np.pi) % (2.0 * np.pi) - np.pi
+        gate = None if confidence is None else float(self._chi2_gate(confidence, len(z)))
+        return self.update_linear(lms, J, R, innovation=y, gate=gate, b=b)
 
     def _unlabelled(self, ranges, bearings, m):
         """Unlabelled observations as padded (B, stride) float64 arrays + m (B,) int32: (B, S) arrays with `m` (default: S
@@ -1307,7 +1450,7 @@ class EkfSlam:
 
     def profile_read_class(self, cls: int):
         """(total ms, number) of the bracketed launches of class `cls` (1 solve, 2 chain / gather, 3 panel, 4 the k_direct launch of
-        update_direct; needs the option
+        update_direct, 5 the k_linear launch of update_linear; needs the option
         "profile_kernels"); read before `profile_read`, which resets."""
         ms, cnt = C.c_double(), C.c_longlong()
         self._check(self._lib.ekf_profile_read_class(self._h, int(cls), C.byref(ms), C.byref(cnt)))

@@ -1,0 +1,187 @@
+// Sanitizer build of plan_linear (slam-duckietown_amd/csrc/ekf_host_plan.h), the host-side validation and plan of
+// ekf_update_linear:
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DEKF_HOST_ONLY
+//       -I slam-duckietown_amd/csrc -I include tests/linear_plan_check.cpp -o linear_plan_check
+// Every refusal the header lists, a legal zero row, d = 0, the state indices and kpad of permuted selections, and randomised
+// calls at the limits (lstride = EKF_LINEAR_LMAX, dstride = EKF_LINEAR_ROWS) whose arrays are allocated to exactly the size
+// the header states, so that a read beyond them is a sanitizer report; any report or failed check ends the run with a
+// non-zero status.  tests/test_linear_cpu.py builds and runs it (CPU only).
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <limits>
+#include <random>
+#include <vector>
+
+#include "ekf_host_plan.h"
+
+using namespace ekf;
+
+static long checks = 0;
+#define CHECK(cond, ...)                                              \
+  do {                                                                \
+    ++checks;                                                         \
+    if (!(cond)) {                                                    \
+      std::fprintf(stderr, "FAILED %s:%d: %s  [", __FILE__, __LINE__, #cond); \
+      std::fprintf(stderr, __VA_ARGS__);                              \
+      std::fprintf(stderr, "]\n");                                    \
+      std::exit(1);                                                   \
+    }                                                                 \
+  } while (0)
+
+// two trajectories, lstride 3 (ns = 9), dstride 4: trajectory 0 names the landmarks 5, 2, 7 and brings 3 rows, trajectory 1 the
+// landmark 1 (k = 1) and 2 rows
+struct Call {
+  int b0 = 0, count = 2, lstride = 3, dstride = 4;
+  std::vector<int> lm{5, 2, 7, 1, -9, -9}, k{3, 1}, d{3, 2};
+  std::vector<double> H, r, R, gate;
+  bool null_lm = false, null_k = false, null_H = false, null_r = false, null_R = false, null_d = false;
+  Call() : H(2 * 4 * 9, 0.5), r(2 * 4, 0.25), R(2 * 4 * 4, 0.0) {
+    for (int b = 0; b < 2; ++b)
+      for (int a = 0; a < 4; ++a) {
+        for (int q = 0; q < 4; ++q) R[(b * 4 + a) * 4 + q] = q > a ? 0.001 : q == a ? 0.01 : 1e300;   // below the diagonal: never read
+      }
+  }
+  const char* plan(const HostPlan& h, LinearPlan& lp) const {
+    return plan_linear(&h, b0, count, null_lm ? nullptr : lm.data(), null_k ? nullptr : k.data(), lstride,
+                       null_H ? nullptr : H.data(), null_r ? nullptr : r.data(), null_R ? nullptr : R.data(),
+                       null_d ? nullptr : d.data(), dstride, gate.empty() ? nullptr : gate.data(), lp);
+  }
+};
+
+int main() {
+  HostPlan h;
+  h.batch = 3;
+  h.n = {3 + 2 * 40, 3 + 2 * 10, 3 + 2 * 20};
+  const double inf = std::numeric_limits<double>::infinity(), nan = std::nan("");
+  LinearPlan lp;
+  {
+    Call c;
+    CHECK(c.plan(h, lp) == nullptr, "the good call");
+    CHECK(lp.kpad == 4 && lp.D[0] == 3 && lp.D[1] == 2 && lp.ns[0] == 9 && lp.ns[1] == 5, "%d %d %d", lp.kpad, lp.D[0], lp.D[1]);
+    CHECK(lp.lmax[0] == 7 && lp.lmax[1] == 1, "%d %d", lp.lmax[0], lp.lmax[1]);
+    const int want0[9] = {0, 1, 2, 13, 14, 7, 8, 17, 18}, want1[5] = {0, 1, 2, 5, 6};   // the order given, not sorted
+    for (int j = 0; j < 9; ++j) CHECK(lp.s[j] == want0[j], "entry %d", j);
+    for (int j = 0; j < 5; ++j) CHECK(lp.s[LINEAR_NS + j] == want1[j], "entry %d", j);
+    for (int j = 9; j < LINEAR_NS; ++j) CHECK(lp.s[j] == -1, "pad %d", j);
+    for (int j = 5; j < LINEAR_NS; ++j) CHECK(lp.s[LINEAR_NS + j] == -1, "pad %d", j);
+    c.lm = {7, 5, 2, 1, -9, -9};                           // a permuted selection: the same entries, permuted
+    CHECK(c.plan(h, lp) == nullptr && lp.s[3] == 17 && lp.s[5] == 13 && lp.s[7] == 7 && lp.lmax[0] == 7, "permuted");
+    c.gate = {inf, 11.3};
+    CHECK(c.plan(h, lp) == nullptr, "gates");
+    c.d = {0, 0};
+    CHECK(c.plan(h, lp) == nullptr && lp.kpad == 0 && lp.D[0] == 0, "nothing to do");
+    c.d = {0, 4};
+    CHECK(c.plan(h, lp) == nullptr && lp.kpad == 4 && lp.D[0] == 0 && lp.D[1] == 4, "d = 0 beside d = 4");
+    c.k = {0, 0};
+    CHECK(c.plan(h, lp) == nullptr && lp.ns[1] == 3 && lp.lmax[1] == -1 && lp.s[LINEAR_NS + 3] == -1, "the pose alone");
+  }
+  {
+    Call c;                                                // a zero row of H is legal: S keeps R's row
+    for (int j = 0; j < 9; ++j) c.H[1 * 9 + j] = 0.0;
+    CHECK(c.plan(h, lp) == nullptr, "zero row");
+    c.d = {3, 2};                                          // what lies beyond d rows, 3 + 2 k columns and R's upper triangle is not read
+    c.H[3 * 9 + 0] = nan;                                  // trajectory 0, row 3 >= d
+    c.H[(4 + 0) * 9 + 5] = nan;                            // trajectory 1, column 5 >= 3 + 2 k
+    c.r[3] = nan;
+    c.R[3 * 4 + 3] = nan;
+    c.R[0 * 4 + 3] = nan;                                  // trajectory 0, column 3 >= d
+    CHECK(c.plan(h, lp) == nullptr, "ignored entries");
+  }
+  auto refused = [&](const Call& c, const char* what) {
+    const char* why = c.plan(h, lp);
+    CHECK(why != nullptr, "%s was accepted", what);
+  };
+  { Call c; c.b0 = 2; refused(c, "range past the bank"); }
+  { Call c; c.b0 = -1; refused(c, "negative b0"); }
+  { Call c; c.count = 0; refused(c, "count 0"); }
+  { Call c; c.lstride = 0; refused(c, "lstride 0"); }
+  { Call c; c.lstride = EKF_LINEAR_LMAX + 1; refused(c, "lstride 17"); }
+  { Call c; c.dstride = 0; refused(c, "dstride 0"); }
+  { Call c; c.dstride = EKF_LINEAR_ROWS + 1; refused(c, "dstride 33"); }
+  { Call c; c.k[0] = 4; refused(c, "k above lstride"); }
+  { Call c; c.k[1] = -1; refused(c, "negative k"); }
+  { Call c; c.d[0] = 5; refused(c, "d above dstride"); }
+  { Call c; c.d[1] = -1; refused(c, "negative d"); }
+  { Call c; c.lm[3] = 10; refused(c, "landmark outside trajectory 1's map"); }
+  { Call c; c.lm[1] = -1; refused(c, "negative landmark"); }
+  { Call c; c.lm[2] = 5; refused(c, "landmark twice"); }
+  { Call c; c.H[2 * 9 + 8] = nan; refused(c, "NaN H"); }
+  { Call c; c.H[(4 + 1) * 9 + 4] = inf; refused(c, "infinite H"); }
+  { Call c; c.r[4 + 1] = nan; refused(c, "NaN r"); }
+  { Call c; c.R[0 * 4 + 2] = inf; refused(c, "infinite R"); }
+  { Call c; c.R[0 * 4 + 1] = 0.02; refused(c, "R not positive definite"); }
+  { Call c; c.R[(4 + 1) * 4 + 1] = 0.0; refused(c, "zero variance"); }
+  { Call c; c.R[2 * 4 + 2] = -0.01; refused(c, "negative variance"); }
+  { Call c; c.gate = {nan, 1.0}; refused(c, "NaN gate"); }
+  { Call c; c.gate = {1.0, 0.0}; refused(c, "zero gate"); }
+  { Call c; c.gate = {-inf, 1.0}; refused(c, "negative gate"); }
+  { Call c; c.null_lm = true; refused(c, "NULL landmarks"); }
+  { Call c; c.null_k = true; refused(c, "NULL k"); }
+  { Call c; c.null_H = true; refused(c, "NULL H"); }
+  { Call c; c.null_r = true; refused(c, "NULL r"); }
+  { Call c; c.null_R = true; refused(c, "NULL R"); }
+  { Call c; c.null_d = true; refused(c, "NULL d"); }
+
+  // randomised calls up to the limits: every sub-state entry lands on a distinct state index of its trajectory, in the order given
+  std::mt19937 rng(11);
+  std::normal_distribution<double> gauss(0.0, 1.0);
+  for (int it = 0; it < 1500; ++it) {
+    Call c;
+    c.count = 1 + (int)(rng() % 3);
+    c.b0 = (int)(rng() % (4 - c.count));
+    c.lstride = 1 + (int)(rng() % EKF_LINEAR_LMAX);
+    c.dstride = 1 + (int)(rng() % EKF_LINEAR_ROWS);
+    const int nsl = 3 + 2 * c.lstride;
+    c.lm.assign((size_t)c.count * c.lstride, 0);
+    c.k.assign(c.count, 0);
+    c.d.assign(c.count, 0);
+    c.H.assign((size_t)c.count * c.dstride * nsl, 0.0);
+    c.r.assign((size_t)c.count * c.dstride, 0.25);
+    c.R.assign((size_t)c.count * c.dstride * c.dstride, 0.0);
+    for (auto& v : c.H) v = gauss(rng);
+    int d_hi = 0;
+    for (int bi = 0; bi < c.count; ++bi) {
+      const int nl = (h.n[c.b0 + bi] - 3) / 2;
+      c.k[bi] = (int)(rng() % (std::min(c.lstride, nl) + 1));
+      c.d[bi] = (int)(rng() % (c.dstride + 1));
+      d_hi = std::max(d_hi, c.d[bi]);
+      std::vector<int> pool(nl);
+      for (int l = 0; l < nl; ++l) pool[l] = l;
+      std::shuffle(pool.begin(), pool.end(), rng);
+      for (int j = 0; j < c.k[bi]; ++j) c.lm[(size_t)bi * c.lstride + j] = pool[j];
+      // R = G G^T / D + 0.01 I on the upper triangle, rubbish below it
+      const int D = c.dstride;
+      std::vector<double> G((size_t)D * D);
+      for (auto& v : G) v = 0.1 * gauss(rng);
+      for (int a = 0; a < D; ++a)
+        for (int q = 0; q < D; ++q) {
+          double v = a == q ? 0.01 : 0.0;
+          for (int e = 0; e < D; ++e) v += G[(size_t)a * D + e] * G[(size_t)q * D + e] / D;
+          c.R[((size_t)bi * D + a) * D + q] = q >= a ? v : nan;
+        }
+    }
+    CHECK(c.plan(h, lp) == nullptr, "random call %d", it);
+    CHECK(lp.kpad == ((d_hi + 3) & ~3) && lp.kpad <= LINEAR_ROWS && linear_rows_cap(lp.kpad) >= lp.kpad && linear_rows_cap(lp.kpad) <= LINEAR_ROWS,
+          "kpad %d for %d", lp.kpad, d_hi);
+    for (int bi = 0; bi < c.count; ++bi) {
+      std::vector<unsigned char> seen(h.n[c.b0 + bi], 0);
+      CHECK(lp.ns[bi] == 3 + 2 * c.k[bi] && lp.D[bi] == c.d[bi], "sizes");
+      int lmax = -1;
+      for (int j = 0; j < LINEAR_NS; ++j) {
+        const int s = lp.s[(size_t)bi * LINEAR_NS + j];
+        if (j >= lp.ns[bi]) { CHECK(s == -1, "pad"); continue; }
+        CHECK(s >= 0 && s < h.n[c.b0 + bi] && !seen[s], "entry %d -> %d", j, s);
+        seen[s] = 1;
+        if (j >= 3) {
+          const int l = c.lm[(size_t)bi * c.lstride + (j - 3) / 2];
+          CHECK(s == 3 + 2 * l + ((j - 3) & 1), "entry %d of landmark %d -> %d", j, l, s);
+          lmax = std::max(lmax, l);
+        }
+      }
+      CHECK(lp.lmax[bi] == lmax && 3 + 2 * (lmax + 1) <= h.n[c.b0 + bi], "highest landmark %d", lmax);
+    }
+  }
+  std::printf("%ld checks passed\n", checks);
+  return 0;
+}
