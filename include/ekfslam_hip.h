@@ -395,6 +395,42 @@ int ekf_update_linear(ekf_handle *h, int b0, int count, const int *landmarks, co
  * measured 6.29 TB/s copy rate of the part, against 62 ms through ekf_download_state + 31 x ekf_upload_state. */
 int ekf_copy_trajectories(ekf_handle *dst, const int *dst_b, ekf_handle *src, const int *src_b, int k);
 
+/* Map joining on the device: append the map of trajectory src_b[i] of `src` to trajectory dst_b[i] of `dst`, i < k, in one launch
+ * (k_join) -- sequential map joining (map locally in a small filter, join the local map into the global one every so often) and
+ * the merge of two maps related by a rigid transform.  For a pair (A = [r_A; L_A] of n_A = 3 + 2 N_A, B = [r_B; L_B]) a base
+ * frame g = (t, phi) with covariance Sigma and cross terms G (3 x n_A, the covariance of g with A's state) maps every item of B
+ * into A's frame; with R = rot(phi), J2 = [[0, -1], [1, 0]], Jacobians at the current means:
+ *   landmark  l' = t + R l                      A_l = [I2 | J2 R l]                  B_l = R
+ *   pose      p' = (t + R p_xy, phi + theta_B)  A_p = [[I2, J2 R p_xy], [0 0 1]]     B_p = diag(R, 1)   (theta is not re-wrapped)
+ *   P'[c1, c2] = A_c1 Sigma A_c2^T + B_c1 P_B[c1, c2] B_c2^T      P'[a, c] = G[:, a]^T A_c^T      P'[L_A, L_A], L_A: unchanged
+ * T == NULL (sequential): the source's frame IS the destination's current pose -- g = r_A, Sigma = P_A[r, r], G = P_A[r, :] --
+ * and the destination's pose is REPLACED by r_A (+) r_B (rows 0..2 become A_p G over L_A).  N_B = 0 moves the pose alone.
+ * T != NULL (explicit): g = T[i] = (x, y, phi) with covariance covT[i] (3 x 3 row-major, the upper triangle is read, may be all
+ * zero), independent of both maps (G = 0): the destination's pose, its rows and every entry of A stay bit for bit, the source's
+ * pose is dropped, the cross terms between A and the appended part are exact zeros.
+ * Either way the source's N_B landmarks are appended at landmark indices N_A .. N_A + N_B - 1 in the source's order; first[i]
+ * (may be NULL) receives N_A.  The destination's size becomes n_A + 2 N_B, its active bound the new size; existing indices do not
+ * move, so its uploaded stream stays runnable; no log row is written and no gate counter, noise row or sticky flag changes; the
+ * last window's tags (ekf_download_tags) stay.  The source is not written.  A handle on the small-state path stays on it.
+ * Device tag table: an appended landmark keeps its source tag at its new index, unless the destination's map already holds that
+ * tag -- then the destination's entry stays, the appended landmark is untagged, and twin[i * twin_stride + j] (may be NULL) is
+ * the destination landmark that carries the tag of source landmark j; -1 otherwise, and throughout where either side has no
+ * table.  Fusing twins is the caller's: constrain them (ekf_update_linear) and remove one (ekf_remove_landmarks); INTEGRATION.md.
+ * src == dst is allowed; otherwise both handles must be on the same device; a source may be named several times.  What is pending
+ * on BOTH handles is applied first (a pass the caller pays for).  Blocking, and stream-ordered behind everything enqueued on
+ * both handles.  k = 0 does nothing.  Every entry is a fixed sequence of at most 13 products: the same pair gives the same bits
+ * whatever else the launch carries.  With ekf_set_option("profile_kernels", 1) the launch is class 6 of ekf_profile_read_class.
+ * EKF_ERR_ARG (nothing changed, both handles usable; the message is `dst`'s ekf_last_error): k < 0, a NULL index array with
+ * k > 0, an index outside its bank, a destination named twice, with src == dst a trajectory that is both a source and a
+ * destination, handles on different devices, n_A + 2 N_B above the destination's n_max, exactly one of T / covT given, a
+ * non-finite T or covT, a negative diagonal of covT or c_ij^2 > c_ii c_jj, `twin` given with twin_stride below the largest N_B.
+ * EKF_ERR_STATE: a source OR a destination carries EKF_FLAG_INTERNAL or an earlier call on its handle failed half way (a
+ * destination is read here, not only overwritten).
+ * Measured: profiles/join.txt. */
+int ekf_join_maps(ekf_handle *dst, const int *dst_b, ekf_handle *src, const int *src_b, int k,
+                  const double *T /* k x 3 or NULL */, const double *covT /* k x 9 or NULL */,
+                  int *first /* k, may be NULL */, int *twin /* k x twin_stride, may be NULL */, int twin_stride);
+
 /* Pinned (page-locked, device-visible) host memory for the arrays a binding hands to its caller.  The reference's loop
  * gets a fresh n x n covariance back from every call (src/replay_no_ros.py:229-237, :482): in freshly allocated pageable
  * memory a 128 MB download first faults in and pins 32 768 pages (5 ms on top of 2.3 ms of PCIe time at N = 2000); the
@@ -487,7 +523,7 @@ int ekf_profile_read(ekf_handle *h, double *pass_ms_total, long long *pass_launc
 long long ekf_profile_passes(ekf_handle *h);
 /* With ekf_set_option("profile_kernels", 1) (a diagnostic run: every record costs its stream ~6 us) the other launches of a
  * fused cadence carry event pairs too: cls 1 the solve launch, 2 the chain (or look-ahead gather) launch, 3 the panel launch,
- * 0 the pass; 4 the k_direct launch of ekf_update_direct; 5 the k_linear launch of ekf_update_linear.  Does not reset: read before ekf_profile_read. */
+ * 0 the pass; 4 the k_direct launch of ekf_update_direct; 5 the k_linear launch of ekf_update_linear; 6 the k_join launch of ekf_join_maps (with its snapshot launch).  Does not reset: read before ekf_profile_read. */
 int ekf_profile_read_class(ekf_handle *h, int cls, double *ms_total, long long *launches);
 /* Options: name (default, allowed values) meaning.  Unknown names and values out of range fail with EKF_ERR_ARG.
  *   "flush_every"         (0, 0..64)    steps per covariance pass; 0 = auto, by "rank_limit"

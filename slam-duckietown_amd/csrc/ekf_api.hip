@@ -235,6 +235,10 @@ struct ekf_handle : ekf::HostPlan {
   bool stream_stale = false;
   // ekf_copy_trajectories (allocated on first use, in the DESTINATION handle): the launch's table of groups (plan_copy)
   DeviceBuf<int> dcp_tab;
+  // ekf_join_maps (allocated on first use, in the DESTINATION handle): the launch's table of pairs (plan_join) and the snapshot
+  // of every destination's pose, its 3 x 3 block and its three pose rows as they stood before the join (join_snap_doubles per pair)
+  DeviceBuf<int> djn_tab;
+  DeviceBuf<double> djn_snap;
   // ekf_update_direct (allocated on first use): per trajectory of the bank the row plan (DIRECT_INTS ints), the measurements
   // (DIRECT_DBLS doubles) and the results (NIS, applied) of k_direct, and their host sides
   DeviceBuf<double> ddirect;
@@ -2215,6 +2219,100 @@ extern "C" int ekf_copy_trajectories(ekf_handle* dst, const int* dst_b, ekf_hand
   return EKF_OK;
 }
 
+// Append the map of src_b[i] of `src` to trajectory dst_b[i] of `dst`, on the device (k_join, ekf_join.hip; the header has the
+// operation).  As ekf_copy_trajectories: what is pending on either handle is applied first, then ONE launch on the destination's
+// stream (in sequential mode behind the snapshot of the destinations' pose rows) writes the new columns, the new means and the
+// size words -- and, in sequential mode, the pose, its rows and its block.  The host's mirrors follow here: n, the active bound
+// (raised to the new n: the appended landmarks are correlated with everything the pose was), neff_enq, the floor; the device tag
+// table's row is merged on the host from the two downloaded rows, as ekf_remove_landmarks renumbers.  Existing indices do not
+// move, so the destination's uploaded stream stays runnable and its last window's AssocOut stays; no log row, gate counter, noise
+// row or sticky flag changes.  The sources are read only.  Unlike a copy, a join READS its destinations: one under
+// EKF_FLAG_INTERNAL or host_bad is refused like a source.
+extern "C" int ekf_join_maps(ekf_handle* dst, const int* dst_b, ekf_handle* src, const int* src_b, int k, const double* T,
+                             const double* covT, int* first, int* twin, int twin_stride) {
+  if (!dst || !src) return EKF_ERR_ARG;
+  if (int rc = refresh_sizes(src)) return src == dst ? rc : fail(dst, rc, "ekf_join_maps: source: " + src->err);
+  if (int rc = refresh_sizes(dst)) return rc;
+  JoinPlan jp;
+  if (const char* why = plan_join(dst, dst_b, src, src_b, k, T, covT, twin != nullptr, twin_stride, jp)) return fail(dst, EKF_ERR_ARG, why);
+  if (k == 0) return EKF_OK;
+  HIP_TRY(dst, hipSetDevice(dst->device));
+  // (the flags of both sides, behind everything enqueued on their streams)
+  HIP_TRY(dst, hipMemcpyAsync(src->h_flags.p, src->dflags.p, sizeof(unsigned) * src->batch, hipMemcpyDeviceToHost, src->stream));
+  HIP_TRY(dst, hipStreamSynchronize(src->stream));
+  if (src != dst) {
+    HIP_TRY(dst, hipMemcpyAsync(dst->h_flags.p, dst->dflags.p, sizeof(unsigned) * dst->batch, hipMemcpyDeviceToHost, dst->stream));
+    HIP_TRY(dst, hipStreamSynchronize(dst->stream));
+  }
+  for (int i = 0; i < k; ++i) {
+    const int d = jp.tab[(size_t)JOIN_PAIR_WORDS * i], s = jp.tab[(size_t)JOIN_PAIR_WORDS * i + 1];
+    if (src->host_bad[s] || (src->h_flags.p[s] & EKF_FLAG_INTERNAL))
+      return fail(dst, EKF_ERR_STATE, "ekf_join_maps: source trajectory " + std::to_string(s) +
+                                          " is undefined (EKF_FLAG_INTERNAL, or an earlier call failed half way): upload it again");
+    if (dst->host_bad[d] || (dst->h_flags.p[d] & EKF_FLAG_INTERNAL))
+      return fail(dst, EKF_ERR_STATE, "ekf_join_maps: destination trajectory " + std::to_string(d) +
+                                          " is undefined (EKF_FLAG_INTERNAL, or an earlier call failed half way): upload it again");
+  }
+  if (int rc = flush_pending(src)) return src == dst ? rc : fail(dst, rc, "ekf_join_maps: source: " + src->err);
+  if (src != dst)
+    if (int rc = flush_pending(dst)) return rc;
+  HIP_TRY(dst, hipStreamSynchronize(src->stream));
+  if (src->aux) HIP_TRY(dst, hipStreamSynchronize(src->aux));
+  const size_t ss = (size_t)join_snap_doubles(dst->ld, jp.seq);
+  RES_TRY(dst, "ekf_join_maps's table", dst->djn_tab.reserve(jp.tab.size(), (size_t)JOIN_PAIR_WORDS * dst->batch, dst->stream));
+  RES_TRY(dst, "ekf_join_maps's snapshot", dst->djn_snap.reserve(ss * k, ss * k, dst->stream));
+  HIP_TRY(dst, hipMemcpyAsync(dst->djn_tab.p, jp.tab.data(), sizeof(int) * jp.tab.size(), hipMemcpyHostToDevice, dst->stream));
+  if (!jp.seq)
+    HIP_TRY(dst, hipMemcpyAsync(dst->djn_snap.p, jp.frame.data(), sizeof(double) * jp.frame.size(), hipMemcpyHostToDevice, dst->stream));
+  ProfBracket pb;
+  if (int rc = prof_open(dst, 6, dst->stream, &pb)) return rc;
+  launch_join(dst->stream, bank_view(src), bank_view(dst), src->dmu2[src->cur].p, dst->dmu2[dst->cur].p, dst->djn_tab.p, dst->djn_snap.p,
+              k, jp.tiles_hi, jp.na_hi, jp.seq);
+  if (int rc = prof_close(dst, &pb)) return rc;
+  HIP_TRY(dst, hipGetLastError());
+  for (int i = 0; i < k; ++i) {
+    const int* w = jp.tab.data() + (size_t)JOIN_PAIR_WORDS * i;
+    const int d = w[0], n_new = 3 + 2 * (w[2] + w[3]);
+    if (first) first[i] = w[2];
+    dst->n[d] = n_new;
+    dst->neff[d] = n_new;
+    dst->neff_enq[d] = n_new;
+  }
+  if (twin) std::fill_n(twin, (size_t)k * twin_stride, -1);
+  // the device tag table: an appended landmark keeps its tag unless the destination's map holds that tag already (a twin)
+  if (src->dtagmap.p && jp.nb_hi > 0) {
+    const bool had = dst->dtagmap.p != nullptr;
+    if (int rc = assoc_init(dst)) return rc;
+    std::vector<int> ts((size_t)TAGMAX), td((size_t)TAGMAX);
+    for (int i = 0; i < k; ++i) {
+      const int* w = jp.tab.data() + (size_t)JOIN_PAIR_WORDS * i;
+      if (w[3] == 0) continue;
+      HIP_TRY(dst, hipMemcpyAsync(ts.data(), src->dtagmap.p + (size_t)w[1] * TAGMAX, sizeof(int) * TAGMAX, hipMemcpyDeviceToHost, dst->stream));
+      HIP_TRY(dst, hipMemcpyAsync(td.data(), dst->dtagmap.p + (size_t)w[0] * TAGMAX, sizeof(int) * TAGMAX, hipMemcpyDeviceToHost, dst->stream));
+      HIP_TRY(dst, hipStreamSynchronize(dst->stream));
+      bool changed = false;
+      for (int id = 0; id < TAGMAX; ++id) {
+        const int j = ts[id];
+        if (j < 0 || j >= w[3]) continue;
+        if (td[id] >= 0) {
+          if (twin && had) twin[(size_t)i * twin_stride + j] = td[id];
+        } else {
+          td[id] = w[2] + j;
+          changed = true;
+        }
+      }
+      if (changed) {
+        HIP_TRY(dst, hipMemcpyAsync(dst->dtagmap.p + (size_t)w[0] * TAGMAX, td.data(), sizeof(int) * TAGMAX, hipMemcpyHostToDevice, dst->stream));
+        HIP_TRY(dst, hipStreamSynchronize(dst->stream));
+      }
+    }
+  }
+  HIP_TRY(dst, hipMemcpyAsync(dst->dn.p, dst->n.data(), sizeof(int) * dst->batch, hipMemcpyHostToDevice, dst->stream));
+  if (int rc = push_floor(dst, true)) return rc;
+  HIP_TRY(dst, hipStreamSynchronize(dst->stream));
+  return EKF_OK;
+}
+
 extern "C" int ekf_predict(ekf_handle* h, const double* lin, const double* ang) {
   return do_step(h, FLAG_PREDICT, lin, ang, nullptr, nullptr, nullptr, nullptr, 0);
 }
@@ -2568,7 +2666,8 @@ extern "C" int ekf_profile_read(ekf_handle* h, double* pass_ms_total, long long*
 }
 
 // ("profile_kernels" = 1) the same for the cadence's other launches: cls 1 the solve launch, 2 the chain / look-ahead gather
-// launch, 3 the panel launch (0: the covariance pass); does not reset -- read these BEFORE ekf_profile_read
+// launch, 3 the panel launch (0: the covariance pass), 4 k_direct, 5 k_linear, 6 k_join (with its snapshot launch); does not
+// reset -- read these BEFORE ekf_profile_read
 extern "C" int ekf_profile_read_class(ekf_handle* h, int cls, double* ms_total, long long* launches) {
   if (!h || !ms_total || !launches) return EKF_ERR_ARG;
   HIP_TRY(h, hipSetDevice(h->device));

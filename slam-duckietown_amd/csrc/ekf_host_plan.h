@@ -917,6 +917,113 @@ inline int copy_tiles(int n) {
   return t * (t + 1) / 2;
 }
 
+// ekf_join_maps (k_join, ekf_join.hip): append the map of src_b[i] of `src` to trajectory dst_b[i] of `dst`.  The joined state is
+// walked in ITEMS: item 0 is the pose (state indices 0..2), item q >= 1 landmark q - 1 (state indices 1 + 2 q, 2 + 2 q); with
+// NA destination and NB source landmarks there are M = 1 + NA + NB items, the new ones from F = 1 + NA on.  A tile is
+// JOIN_ITEMS x JOIN_ITEMS items (64 x 64 entries but for the pose's third row / column): whole 2 x 2 blocks, whatever the
+// parity of their first column.  What a launch writes of the stored upper triangle: every entry whose COLUMN item is new, and
+// in sequential mode (the destination's pose is replaced) every entry of the pose item's rows -- except the pose block itself,
+// which the launch's extra workgroup writes with the mean and the size word.  join_tiles counts a pair's tiles, join_tile names
+// tile t (row block ib <= column block jb): first the column blocks that hold a new item, block by block, then (sequential)
+// row block 0 of the column blocks in front of them; join_writes says whether item pair (I, J) is written -- by the one tile
+// that holds it.  Plain integer functions, the ones the kernel calls; tests/join_plan_check.cpp enumerates them.
+constexpr int JOIN_ITEMS = 32;
+constexpr int JOIN_PAIR_WORDS = 4;       // per pair {destination, source, NA, NB}
+constexpr int JOIN_HEAD = 16;            // doubles in front of a pair's snapshot rows: g (3), pad, Sigma (3 x 3 row-major), pad
+__host__ __device__ inline int join_tri(int x) { return x * (x + 1) / 2; }
+__host__ __device__ inline int join_new_tiles(int NA, int NB) {
+  return NB > 0 ? join_tri((NA + NB) / JOIN_ITEMS + 1) - join_tri((1 + NA) / JOIN_ITEMS) : 0;
+}
+__host__ __device__ inline int join_pose_tiles(int NA, int NB, bool seq) {
+  return !seq ? 0 : NB > 0 ? (1 + NA) / JOIN_ITEMS : (NA + NB) / JOIN_ITEMS + 1;
+}
+__host__ __device__ inline int join_tiles(int NA, int NB, bool seq) { return join_new_tiles(NA, NB) + join_pose_tiles(NA, NB, seq); }
+// tile t < join_tiles of a pair: its row block *ib and column block *jb
+__host__ __device__ inline void join_tile(int NA, int NB, int t, int* ib, int* jb) {
+  const int nn = join_new_tiles(NA, NB);
+  if (t >= nn) {                                       // (sequential) the pose's rows over the kept landmarks
+    *ib = 0;
+    *jb = t - nn;
+    return;
+  }
+  const int u = t + join_tri((1 + NA) / JOIN_ITEMS);
+  int s = (int)((sqrtf(8.0f * (float)u + 1.0f) - 1.0f) * 0.5f);
+  while (join_tri(s + 1) <= u) ++s;
+  while (join_tri(s) > u) --s;
+  *jb = s;
+  *ib = u - join_tri(s);
+}
+// doubles of one pair's snapshot: the head, and in sequential mode the destination's three pose rows, ld apart
+inline long join_snap_doubles(int ld, bool seq) { return JOIN_HEAD + (seq ? 3L * ld : 0L); }
+// item pair (I, J), I <= J < M: does the launch's tile that holds it write it?
+__host__ __device__ inline bool join_writes(int NA, int I, int J, bool seq) { return J > NA || (seq && I == 0 && J >= 1); }
+
+// The k pairs checked -- indices inside their banks, no destination twice, inside one handle no trajectory both read and written,
+// the same device, every joined size within the destination's n_max, T and covT both or neither, finite, covT (upper triangle) with
+// a non-negative diagonal and c_ij^2 <= c_ii c_jj, twin_stride not below the largest NB where `twin` is given -- and turned into
+// the launch's table (JOIN_PAIR_WORDS ints per pair, in the caller's order), the frames of the explicit mode (JOIN_HEAD doubles
+// per pair: T, then covT mirrored from its upper triangle) and the grid: the most tiles of any pair, the largest NA and NB.
+// The sizes must be current (refresh_sizes) on both handles.
+struct JoinPlan {
+  int pairs = 0, tiles_hi = 0, na_hi = 0, nb_hi = 0;
+  bool seq = true;
+  std::vector<int> tab;
+  std::vector<double> frame;
+};
+inline const char* plan_join(const HostPlan* dst, const int* dst_b, const HostPlan* src, const int* src_b, int k, const double* T,
+                             const double* covT, bool want_twin, int twin_stride, JoinPlan& jp) {
+  if (k < 0) return "ekf_join_maps: k must be >= 0";
+  if (k > 0 && (!dst_b || !src_b)) return "ekf_join_maps: NULL index array";
+  if (dst->device != src->device) return "ekf_join_maps: the two handles are on different devices";
+  if ((T == nullptr) != (covT == nullptr)) return "ekf_join_maps: T and covT must be given together";
+  std::vector<unsigned char> written((size_t)dst->batch, 0), read((size_t)src->batch, 0);
+  jp.pairs = k;
+  jp.seq = T == nullptr;
+  jp.tiles_hi = jp.na_hi = jp.nb_hi = 0;
+  jp.tab.assign((size_t)k * JOIN_PAIR_WORDS, 0);
+  jp.frame.assign(jp.seq ? 0 : (size_t)k * JOIN_HEAD, 0.0);
+  for (int i = 0; i < k; ++i) {
+    const int s = src_b[i], d = dst_b[i];
+    if (s < 0 || s >= src->batch) return "ekf_join_maps: source trajectory index out of range";
+    if (d < 0 || d >= dst->batch) return "ekf_join_maps: destination trajectory index out of range";
+    if (written[d]) return "ekf_join_maps: a destination trajectory is named twice";
+    written[d] = 1;
+    read[s] = 1;
+    const int NA = (dst->n[d] - 3) / 2, NB = (src->n[s] - 3) / 2;
+    if ((long)dst->n[d] + 2L * NB > dst->n_max) return "ekf_join_maps: the joined state is larger than the destination's n_max";
+    if (want_twin && twin_stride < NB) return "ekf_join_maps: twin_stride is below a source's landmark count";
+    if (!jp.seq) {
+      const double *t = T + 3 * (size_t)i, *c = covT + 9 * (size_t)i;
+      double* f = jp.frame.data() + (size_t)i * JOIN_HEAD;
+      for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(t[a])) return "ekf_join_maps: non-finite T";
+        f[a] = t[a];
+        for (int b = a; b < 3; ++b) {
+          if (!std::isfinite(c[3 * a + b])) return "ekf_join_maps: non-finite covT";
+          f[4 + 3 * a + b] = f[4 + 3 * b + a] = c[3 * a + b];
+        }
+      }
+      for (int a = 0; a < 3; ++a) {
+        if (c[4 * a] < 0.0) return "ekf_join_maps: covT has a negative diagonal entry";
+        for (int b = a + 1; b < 3; ++b)
+          if (c[3 * a + b] * c[3 * a + b] > c[4 * a] * c[4 * b]) return "ekf_join_maps: covT is not a covariance (c_ij^2 > c_ii c_jj)";
+      }
+    }
+    int* w = jp.tab.data() + (size_t)i * JOIN_PAIR_WORDS;
+    w[0] = d;
+    w[1] = s;
+    w[2] = NA;
+    w[3] = NB;
+    jp.tiles_hi = std::max(jp.tiles_hi, join_tiles(NA, NB, jp.seq));
+    jp.na_hi = std::max(jp.na_hi, NA);
+    jp.nb_hi = std::max(jp.nb_hi, NB);
+  }
+  if (dst == src)
+    for (int b = 0; b < dst->batch; ++b)
+      if (written[b] && read[b]) return "ekf_join_maps: inside one handle a trajectory cannot be both a source and a destination";
+  return nullptr;
+}
+
 // ekf_associate (k_assoc_query / k_assoc_finish, ekf_associate.hip): the launch shape of the query over trajectories
 // [b0, b0 + count).  lane = landmark, a workgroup per chunk of AQ_CHUNK landmarks and trajectory, as k_marginals: N = 2000 x 1 is
 // 32 workgroups on 32 CUs, 32 x N = 2000 is 1024 (four per CU of 256), N = 20 x 256 one per trajectory.  The grid covers the

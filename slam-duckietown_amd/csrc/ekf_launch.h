@@ -105,7 +105,7 @@ void launch_factor_solve(hipStream_t st, const FactorView& w, int f0, int count,
                          double* white, double* quad);
 void launch_factor_multiply(hipStream_t st, const FactorView& w, int f0, int count, int nblk_hi, const double* z, int nrhs,
                             int stride, double* out);
-// ---- state surgery (ekf_remove.hip, ekf_direct.hip, ekf_linear.hip, ekf_copy.hip, ekf_dense.hip) ----
+// ---- state surgery (ekf_remove.hip, ekf_direct.hip, ekf_linear.hip, ekf_copy.hip, ekf_join.hip, ekf_dense.hip) ----
 // rp.rows: the launch's largest new size (grid rows); nb trajectories from b0; src / dst: rp's tables on the device
 void launch_remove(hipStream_t st, const BankView& k, double* mu, const RemovePlan& rp, const int* src, const int* dst,
                    unsigned* rflag, int b0, int nb, unsigned seq);
@@ -117,5 +117,9 @@ void launch_linear(hipStream_t st, int rows_cap, const BankView& k, double* dacc
 // groups x (tiles of the largest source + 1) workgroups; tab: plan_copy's table on the device
 void launch_copy_traj(hipStream_t st, bool nt, const BankView& src, const BankView& dst, const double* mus, double* mud,
                       const int* tab, int groups, int n_hi);
+// pairs x (tiles_hi + 1) workgroups behind, in sequential mode, the snapshot of the destinations' pose rows into `snap`
+// (join_snap_doubles per pair; explicit mode: the host has uploaded the heads); tab: plan_join's table on the device
+void launch_join(hipStream_t st, const BankView& src, const BankView& dst, const double* mus, double* mud, const int* tab,
+                 double* snap, int pairs, int tiles_hi, int na_hi, bool seq);
 int dense_propagate(hipStream_t st, double* P, double* tmp, const double* F, const double* Q, int n, int ld);
 }  // namespace ekf

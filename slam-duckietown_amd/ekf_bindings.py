@@ -139,6 +139,7 @@ ABI = {
     "ekf_add_landmarks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int]),
     "ekf_remove_landmarks": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_int]),
     "ekf_copy_trajectories": (C.c_int, [C.c_void_p, _ip, C.c_void_p, _ip, C.c_int]),
+    "ekf_join_maps": (C.c_int, [C.c_void_p, _ip, C.c_void_p, _ip, C.c_int, _dp, _dp, _ip, _ip, C.c_int]),
     "ekf_predict": (C.c_int, [C.c_void_p, _dp, _dp]),
     "ekf_update": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _ip, C.c_int]),
     "ekf_step": (C.c_int, [C.c_void_p, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
@@ -358,6 +359,15 @@ class LinearUpdate(typing.NamedTuple):
     nis: np.ndarray        # (B,)
     dof: np.ndarray        # (B,) int32
     applied: np.ndarray    # (B,) bool
+
+
+class MapJoin(typing.NamedTuple):
+    """What ``EkfSlam.join`` reports per pair (scalars and one row for a single pair given as ints): the landmark index of the
+    first appended landmark, the number appended, and per source landmark the destination landmark that already carried
+    its tag (-1: none -- the appended landmark then keeps the tag)."""
+    first: np.ndarray      # (k,) int32
+    count: np.ndarray      # (k,) int32
+    twins: np.ndarray      # (k, N_B hi) int32, -1 beyond a source's landmarks
 
 
 EKF_FACTOR_RHS = 16       # (include/ekfslam_hip.h)
@@ -1207,6 +1217,49 @@ class EkfSlam:
                 else:
                     table[b] = v
 
+    def join(self, other: "EkfSlam", src=0, dst=0, transform=None, cov=None) -> "MapJoin":
+        """Append the map of trajectory ``src`` of `other` (another handle on the same GPU, or ``self``) to trajectory ``dst``
+        of this one, on the device (``ekf_join_maps``).  ``transform`` None: sequential map joining -- the source's frame is
+        this trajectory's current pose, which is replaced by the composition with the source's pose; the source's landmarks
+        are appended with the pose's uncertainty and its correlations with this map.  ``transform`` (x, y, phi) with
+        covariance ``cov`` (3 x 3, default zero): the source's frame in this map's, independent of both; this trajectory's
+        pose and map stay bit for bit, the source's pose is dropped.  ``src`` and ``dst`` are ints or equal-length sequences
+        (one launch; a source may appear several times, a destination once; ``transform`` (k, 3) and ``cov`` (k, 3, 3) then).
+        The source is only read; restart a local filter with ``set_state_diag``.  Returns ``MapJoin``: where the appended
+        landmarks start, how many, and for each the landmark of this map that already carried its tag (``tag_index``) or -1
+        -- fuse such a pair with ``constrain_landmarks(i, j, 0, tiny)`` and ``remove_landmarks([j])``.  What is pending on
+        either handle is applied first.  Blocking; ``EkfError`` with nothing changed for a bad index, a destination twice,
+        a trajectory both read and written, different devices, a joined state above ``n_max``, a non-finite transform or
+        a ``cov`` that is no covariance."""
+        scalar = np.ndim(src) == 0 and np.ndim(dst) == 0
+        s = np.atleast_1d(np.asarray(src, dtype=np.int64)).ravel()
+        d = np.atleast_1d(np.asarray(dst, dtype=np.int64)).ravel()
+        if s.shape != d.shape:
+            raise ValueError(f"join: src and dst must have the same length, got {s.size} and {d.size}")
+        lim = np.iinfo(np.int32)
+        if s.size and (min(s.min(), d.min()) < lim.min or max(s.max(), d.max()) > lim.max):
+            raise EkfError("join: trajectory index out of range")
+        s, d = np.ascontiguousarray(s, dtype=np.int32), np.ascontiguousarray(d, dtype=np.int32)
+        k = int(s.size)
+        T = cT = None
+        if transform is None:
+            if cov is not None:
+                raise ValueError("join: cov without a transform")
+        else:
+            T = np.ascontiguousarray(np.broadcast_to(_f64(transform).reshape(-1, 3), (k, 3)))
+            cT = np.zeros((k, 3, 3)) if cov is None else np.ascontiguousarray(np.broadcast_to(_f64(cov).reshape(-1, 3, 3), (k, 3, 3)))
+        count = np.array([(other.size(int(a)) - 3) // 2 if 0 <= a < other.batch else 0 for a in s], dtype=np.int32)
+        stride = max(1, int(count.max()) if k else 1)
+        first = np.zeros(max(k, 1), dtype=np.int32)
+        twins = np.full((max(k, 1), stride), -1, dtype=np.int32)
+        self._check(self._lib.ekf_join_maps(self._h, _p(d, _ip) if k else None, other._h, _p(s, _ip) if k else None, k,
+                                            None if T is None else _p(T), None if cT is None else _p(cT),
+                                            _p(first, _ip), _p(twins, _ip), stride))
+        first, twins = first[:k], twins[:k, :int(count.max()) if k else 0]
+        if scalar:
+            return MapJoin(int(first[0]), int(count[0]), twins[0].copy())
+        return MapJoin(first, count, twins)
+
     def fork(self, src: int = 0, dst=None):
         """Fork trajectory ``src`` inside the bank, on the device: ``dst`` (an int, a sequence, or None for every other
         trajectory) becomes a bit-exact twin of it -- ``copy_from(self, src, dst)`` with one source: the source's covariance
@@ -1388,7 +1441,7 @@ class EkfSlam:
         tags = np.full(cap, -1, dtype=np.int32)
         cnt = C.c_int()
         self._check(self._lib.ekf_download_tag_index(self._h, b, _p(tags, _ip), cap, C.byref(cnt)))
-        return {int(tags[i]): i for i in range(cnt.value)}
+        return {int(tags[i]): i for i in range(cnt.value) if tags[i] >= 0}    # (a landmark joined in as a twin carries no tag)
 
     def set_tag_index(self, tag_index: dict, b: int = 0):
         order = [t for t, _ in sorted(tag_index.items(), key=lambda kv: kv[1])]
@@ -1450,7 +1503,7 @@ class EkfSlam:
 
     def profile_read_class(self, cls: int):
         """(total ms, number) of the bracketed launches of class `cls` (1 solve, 2 chain / gather, 3 panel, 4 the k_direct launch of
-        update_direct, 5 the k_linear launch of update_linear; needs the option
+        update_direct, 5 the k_linear launch of update_linear, 6 the k_join launch of join; needs the option
         "profile_kernels"); read before `profile_read`, which resets."""
         ms, cnt = C.c_double(), C.c_longlong()
         self._check(self._lib.ekf_profile_read_class(self._h, int(cls), C.byref(ms), C.byref(cnt)))

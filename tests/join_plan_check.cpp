@@ -1,0 +1,194 @@
+// Sanitizer build of plan_join and the tile enumeration of k_join (slam-duckietown_amd/csrc/ekf_host_plan.h), the host-side
+// validation and launch table of ekf_join_maps:
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DEKF_HOST_ONLY
+//       -I slam-duckietown_amd/csrc -I include tests/join_plan_check.cpp -o join_plan_check
+// Every refusal the header lists, the table of accepted calls, and the enumeration join_tiles / join_tile / join_writes (the
+// integer functions the kernel calls): over n_A in {3, 63, 65, 4063}, N_B in {0, 1, 33, 40}, both modes and both layouts of the
+// destination, the tiles' item pairs expanded to entries write every stored entry (row <= column) with column >= n_A exactly
+// once, in sequential mode also every entry of rows 0..2 but the pose block, and nothing else; every address lies inside the
+// destination's allocation and no two entries share one.  Any sanitizer report or failed check ends the run with a non-zero
+// status.  tests/test_join_cpu.py builds and runs it (CPU only).
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <limits>
+#include <vector>
+
+#include "ekf_host_plan.h"
+
+using namespace ekf;
+
+static long checks = 0;
+#define CHECK(cond, ...)                                              \
+  do {                                                                \
+    ++checks;                                                         \
+    if (!(cond)) {                                                    \
+      std::fprintf(stderr, "FAILED %s:%d: %s  [", __FILE__, __LINE__, #cond); \
+      std::fprintf(stderr, __VA_ARGS__);                              \
+      std::fprintf(stderr, "]\n");                                    \
+      std::exit(1);                                                   \
+    }                                                                 \
+  } while (0)
+
+static HostPlan bank(int n_max, std::vector<int> n, int device = 0) {
+  HostPlan h;
+  h.device = device;
+  h.n_max = n_max;
+  h.rows = (n_max + 63) / 64 * 64;
+  h.ld = h.rows;
+  if (n_max <= 4096) {
+    int p2 = 64;
+    while (p2 < n_max) p2 *= 2;
+    h.ld = p2;
+  }
+  h.batch = (int)n.size();
+  h.pstride = p_alloc(h.rows, h.ld);
+  h.n = n;
+  return h;
+}
+
+struct Call {
+  std::vector<int> d{0, 2}, s{1, 1};
+  int k = 2, twin_stride = 8;
+  bool null_d = false, null_s = false, want_twin = true, use_T = false, null_cov = false;
+  std::vector<double> T{0.5, -1.0, 0.3, 0.0, 0.0, 0.0}, cov;
+  Call() : cov(18, 0.0) {
+    const double c[9] = {0.04, 0.01, 0.0, 1e300, 0.09, -0.002, 1e300, 1e300, 0.001};   // below the diagonal: never read
+    for (int i = 0; i < 9; ++i) cov[i] = c[i];
+  }
+  const char* plan(const HostPlan& dst, const HostPlan& src, JoinPlan& jp) const {
+    return plan_join(&dst, null_d ? nullptr : d.data(), &src, null_s ? nullptr : s.data(), k, use_T ? T.data() : nullptr,
+                     use_T && !null_cov ? cov.data() : nullptr, want_twin, twin_stride, jp);
+  }
+};
+
+// the entries the launch writes for one pair, by the kernel's own enumeration
+static void enumerate(int NA, int NB, bool seq, const HostPlan& dst) {
+  const int nA = 3 + 2 * NA, n = nA + 2 * NB, M = 1 + NA + NB;
+  std::vector<unsigned char> hit((size_t)n * n, 0);
+  std::vector<unsigned char> addr((size_t)dst.pstride, 0);
+  const int tiles = join_tiles(NA, NB, seq);
+  for (int t = 0; t < tiles; ++t) {
+    int ib = -1, jb = -1;
+    join_tile(NA, NB, t, &ib, &jb);
+    CHECK(ib >= 0 && ib <= jb && jb * JOIN_ITEMS < M, "tile %d -> (%d, %d)", t, ib, jb);
+    for (int lane = 0; lane < JOIN_ITEMS; ++lane)
+      for (int row = 0; row < JOIN_ITEMS; ++row) {
+        const int I = ib * JOIN_ITEMS + row, J = jb * JOIN_ITEMS + lane;
+        if (J >= M || J < 1 || I > J || !join_writes(NA, I, J, seq)) continue;
+        const int i0 = I == 0 ? 0 : 1 + 2 * I, ni = I == 0 ? 3 : 2, j0 = 1 + 2 * J;
+        for (int a = 0; a < ni; ++a)
+          for (int b = 0; b < 2; ++b) {
+            const int i = i0 + a, j = j0 + b;
+            if (i > j) continue;                       // (a diagonal block's entry below the diagonal)
+            CHECK(i < n && j < n, "entry (%d, %d) outside n = %d", i, j, n);
+            CHECK(!hit[(size_t)i * n + j], "entry (%d, %d) written twice", i, j);
+            hit[(size_t)i * n + j] = 1;
+            const long at = p_index(dst.ld, i, j);
+            CHECK(at >= 0 && at < dst.pstride, "address of (%d, %d) outside the allocation", i, j);
+            CHECK(!addr[(size_t)at], "address of (%d, %d) shared", i, j);
+            addr[(size_t)at] = 1;
+          }
+      }
+  }
+  for (int i = 0; i < n; ++i)
+    for (int j = i; j < n; ++j) {
+      const bool pose_block = i < 3 && j < 3;          // (the launch's extra workgroup)
+      const bool want = !pose_block && (j >= nA || (seq && i < 3));
+      CHECK(hit[(size_t)i * n + j] == (want ? 1 : 0), "NA %d NB %d seq %d: entry (%d, %d) %s", NA, NB, (int)seq, i, j,
+            want ? "is not written" : "is written");
+    }
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < i; ++j) CHECK(!hit[(size_t)i * n + j], "below the diagonal (%d, %d)", i, j);
+}
+
+int main() {
+  const double inf = std::numeric_limits<double>::infinity(), nan = std::nan("");
+  HostPlan dst = bank(3 + 2 * 20, {3 + 2 * 10, 3 + 2 * 4, 3, 3 + 2 * 12});
+  HostPlan src = bank(3 + 2 * 8, {3 + 2 * 8, 3 + 2 * 6});
+  JoinPlan jp;
+  {
+    Call c;
+    CHECK(c.plan(dst, src, jp) == nullptr, "the good call");
+    CHECK(jp.pairs == 2 && jp.seq && jp.nb_hi == 6 && jp.na_hi == 10 && jp.frame.empty(), "%d %d %d", jp.pairs, jp.nb_hi, jp.na_hi);
+    const int want[8] = {0, 1, 10, 6, 2, 1, 0, 6};
+    for (int i = 0; i < 8; ++i) CHECK(jp.tab[i] == want[i], "table word %d = %d", i, jp.tab[i]);
+    CHECK(jp.tiles_hi == join_tiles(10, 6, true) && jp.tiles_hi == 1, "tiles %d", jp.tiles_hi);
+    c.use_T = true;
+    CHECK(c.plan(dst, src, jp) == nullptr && !jp.seq && jp.frame.size() == 2 * JOIN_HEAD, "explicit");
+    CHECK(jp.frame[0] == 0.5 && jp.frame[2] == 0.3 && jp.frame[4] == 0.04 && jp.frame[5] == 0.01 && jp.frame[7] == 0.01 &&
+              jp.frame[9] == -0.002 && jp.frame[11] == -0.002 && jp.frame[12] == 0.001 && jp.frame[JOIN_HEAD + 4] == 0.0,
+          "the frame, mirrored from the upper triangle");
+    c.k = 0;
+    c.null_d = c.null_s = true;
+    CHECK(c.plan(dst, src, jp) == nullptr && jp.pairs == 0, "k = 0");
+    Call e;                                            // exactly at n_max: 10 + 8 = 18 <= 20, 12 + 8 = 20
+    e.d = {0, 3};
+    e.s = {0, 0};
+    CHECK(e.plan(dst, src, jp) == nullptr, "a source twice, the second pair exactly at n_max");
+    Call self;                                         // inside one handle
+    self.d = {0, 2};
+    self.s = {1, 1};
+    CHECK(self.plan(dst, dst, jp) == nullptr, "src == dst with distinct slots");
+    Call nt;
+    nt.want_twin = false;
+    nt.twin_stride = 0;
+    CHECK(nt.plan(dst, src, jp) == nullptr, "no twin array: its stride is not read");
+  }
+  auto refused = [&](const Call& c, const HostPlan& d, const HostPlan& s, const char* what) {
+    JoinPlan p;
+    CHECK(c.plan(d, s, p) != nullptr, "%s was accepted", what);
+  };
+  { Call c; c.k = -1; refused(c, dst, src, "k < 0"); }
+  { Call c; c.null_d = true; refused(c, dst, src, "NULL dst_b"); }
+  { Call c; c.null_s = true; refused(c, dst, src, "NULL src_b"); }
+  { Call c; c.d[1] = 4; refused(c, dst, src, "destination past the bank"); }
+  { Call c; c.d[0] = -1; refused(c, dst, src, "negative destination"); }
+  { Call c; c.s[1] = 2; refused(c, dst, src, "source past the bank"); }
+  { Call c; c.s[0] = -1; refused(c, dst, src, "negative source"); }
+  { Call c; c.d = {2, 2}; refused(c, dst, src, "a destination twice"); }
+  { Call c; c.d = {0, 1}; c.s = {1, 2}; refused(c, dst, dst, "both a source and a destination"); }
+  { Call c; c.d = {1, 0}; c.s = {1, 3}; refused(c, dst, dst, "s == d"); }
+  { Call c; HostPlan far = src; far.device = 1; refused(c, dst, far, "different devices"); }
+  { Call c; c.d = {3, 0}; c.s = {1, 0}; CHECK(c.plan(dst, src, jp) == nullptr, "12 + 6 fits"); c.d = {3, 0}; c.s = {0, 1};
+    CHECK(c.plan(dst, src, jp) == nullptr, "12 + 8 fits exactly"); }
+  { Call c; HostPlan tight = dst; tight.n_max = 3 + 2 * 15; refused(c, tight, src, "10 + 6 above n_max"); }
+  { Call c; c.twin_stride = 5; refused(c, dst, src, "twin_stride below N_B"); }
+  { Call c; c.use_T = true; c.null_cov = true; refused(c, dst, src, "T without covT"); }
+  { Call c; c.use_T = true; c.T[4] = nan; refused(c, dst, src, "NaN T"); }
+  { Call c; c.use_T = true; c.T[2] = inf; refused(c, dst, src, "infinite phi"); }
+  { Call c; c.use_T = true; c.cov[9 + 5] = nan; refused(c, dst, src, "NaN covT"); }
+  { Call c; c.use_T = true; c.cov[0] = -1e-9; refused(c, dst, src, "negative diagonal"); }
+  { Call c; c.use_T = true; c.cov[1] = 0.061; refused(c, dst, src, "c01^2 > c00 c11"); }
+  { Call c; c.use_T = true; c.cov[9 + 2] = 1e-3; refused(c, dst, src, "an off-diagonal entry with a zero diagonal"); }
+  { Call c; c.use_T = true; c.cov[3] = nan; c.cov[6] = -inf; CHECK(c.plan(dst, src, jp) == nullptr, "below the diagonal is ignored"); }
+
+  // the tile enumeration: row-major destination (ld <= 4096) and column panels (n_max = 4203: ld = 4224, two panels)
+  const int NAs[4] = {0, 30, 31, 2030}, NBs[4] = {0, 1, 33, 40};
+  for (int ia = 0; ia < 4; ++ia)
+    for (int ib = 0; ib < 4; ++ib)
+      for (int seq = 0; seq < 2; ++seq) {
+        const int NA = NAs[ia], NB = NBs[ib], n = 3 + 2 * (NA + NB);
+        std::vector<HostPlan> layouts;
+        if (n <= 4096) layouts.push_back(bank(n | 1, {3}));
+        layouts.push_back(bank(4203, {3}));
+        for (const HostPlan& h : layouts) {
+          CHECK(n <= h.n_max && (h.n_max == 4203 ? p_panels(h.ld) == 2 : p_panels(h.ld) == 1), "layout for n = %d", n);
+          enumerate(NA, NB, seq != 0, h);
+        }
+        // and the plan's grid holds the pair
+        HostPlan d1 = bank(4203, {3 + 2 * NA}), s1 = bank(3 + 2 * 40, {3 + 2 * NB});
+        Call c;
+        c.k = 1;
+        c.d = {0};
+        c.s = {0};
+        c.twin_stride = 40;
+        c.use_T = seq == 0;
+        CHECK(c.plan(d1, s1, jp) == nullptr && jp.tiles_hi == join_tiles(NA, NB, seq != 0) && jp.tiles_hi + 1 <= 65535, "grid");
+      }
+  for (int NA = 0; NA < 70; ++NA)                      // every small combination, one layout
+    for (int NB = 0; NB < 70; NB += (NB < 4 ? 1 : 11))
+      for (int seq = 0; seq < 2; ++seq) enumerate(NA, NB, seq != 0, bank(3 + 2 * (NA + NB), {3}));
+  std::printf("%ld checks passed\n", checks);
+  return 0;
+}
