@@ -441,6 +441,45 @@ void ekf_host_free(void *p);
 /* predict(): src/replay_no_ros.py:368-430 for every trajectory (lin[b], ang[b]).  O(n) work. */
 int ekf_predict(ekf_handle *h, const double *lin, const double *ang);
 
+/* Prediction with a motion model of the caller's: wheel odometry that arrives as a pose increment with its own 3 x 3 covariance,
+ * visual odometry, an IMU heading, another kinematic model, slip noise that grows with curvature -- anything the caller can
+ * linearise at the current pose.  Trajectory bi of [b0, b0+count) brings the NEW pose mean pose[3*bi..] = [x, y, theta], taken
+ * verbatim (the caller wraps theta), F[9*bi..] = d(new pose)/d(old pose) (row-major 3 x 3) and the process noise Q[9*bi..]
+ * (row-major 3 x 3, the upper triangle is read, positive SEMI-definite).  For every applied trajectory (apply == NULL: all;
+ * apply[bi] == 0 leaves that trajectory bit for bit), with G = blockdiag(F, I):
+ *     mu[0:3] = pose,   P[r,r] <- F P[r,r] F^T + Q,   P[r,j] <- F P[r,j]  (j >= 3)
+ * on the stored upper triangle: rows 0..2 and nothing else.  P is the CURRENT covariance -- P_base + the pending ranks + the
+ * pending pose noise -- and, like the built-in prediction, the call costs no rank and NEVER a covariance pass, also while ranks
+ * are pending: one kernel (k_predict_pose) gathers the current x = P(0..2, j) as the read-only queries do, with their bounds, and
+ * adds (F - I) x to P_base in place (the pose block: (F P_rr F^T + Q) - P_rr, P_rr the current block); the pending V / W and
+ * pose noise are not written and the pass applies them as ever.  Where nothing is pending F x is written directly, no
+ * difference of nearly equal numbers.  In both forms F = I, Q = 0 leaves the covariance bit for bit.  O(n) per trajectory,
+ * O(n kb) with kb ranks pending; every sum runs in a fixed order: a trajectory's result does not depend on its slot or on its
+ * neighbours.
+ * Left alone: landmark means and every P(a, b) with a, b >= 3, bit for bit; sizes, tag table, noise rows, gate counters, sticky
+ * flags, the uploaded stream (which stays runnable) and the active bound (F mixes the pose rows among themselves only; beyond the
+ * bound they are exact zeros and stay so); ekf_profile_passes and ekf_debug_cadences / _chained / _lookaheads; what is pending
+ * -- the call is never counted for "flush_every" or "rank_limit"; a handle on the small-state path stays on it.
+ * ASYNCHRONOUS, enqueued like ekf_predict: stream-ordered behind everything enqueued (also what a chained run left on the
+ * handle's second stream), the records go up as a step's do, and the host arrays are borrowed for the call only.  It blocks
+ * only where ekf_predict does (the input ring coming round, sizes a device-side association grew).  Pose log: the call is a
+ * logged step, one row, as a lone ekf_predict; innovation log: no step.
+ * With ekf_set_option("profile_kernels", 1) the launch is class 7 of ekf_profile_read_class.
+ * EKF_ERR_ARG (nothing changed, the handle usable): a bad trajectory range, NULL pose, F or Q, and for an applied trajectory a
+ * non-finite entry of pose, F or Q, a Q with a negative diagonal entry, with q_ij^2 > q_ii q_jj, or with a negative determinant
+ * of its symmetrised upper triangle (beyond the rounding of the determinant itself: a Q of rank 1 or 2 is legal).  An all-zero Q
+ * and a singular F are legal.  EKF_ERR_STATE after an earlier call failed half way.  Like ekf_predict the call does not read the
+ * sticky flags back (that would synchronise): a trajectory under EKF_FLAG_INTERNAL is reported by the next blocking call, as
+ * ever.
+ * Measured on one MI355X (tools/predict_linear_time.py, profiles/predict_linear.txt), call + sync for the whole bank beside
+ * ekf_predict at the same state: 32 x N = 2000 28 against 26 us with nothing pending (k_predict_pose 7 us), 43 against 47 us with
+ * 78 ranks pending (k_predict_pose 21 us); 1 x N = 2000 27 against 24 us and, with 78 ranks pending, 37 against 28 us (a
+ * latency-bound gather: 16 us); 1 x N = 8000 under an active bound of 83 27 against 24 us; 256 x N = 20 30 against 26 us.  The
+ * routes it replaces: the host round trip 0.68 s for the bank of 32, ekf_predict_dense 8.8 ms per N = 2000 trajectory. */
+int ekf_predict_linear(ekf_handle *h, int b0, int count,
+                       const double *pose /* count x 3 */, const double *F /* count x 9 */, const double *Q /* count x 9 */,
+                       const int *apply /* count, may be NULL */);
+
 /* update(): src/replay_no_ros.py:436-480, sequential over idx[b*stride + 0..m[b]) in that order. */
 int ekf_update(ekf_handle *h, const int *idx, const double *range, const double *bearing,
                const int *m, int stride);
@@ -523,7 +562,7 @@ int ekf_profile_read(ekf_handle *h, double *pass_ms_total, long long *pass_launc
 long long ekf_profile_passes(ekf_handle *h);
 /* With ekf_set_option("profile_kernels", 1) (a diagnostic run: every record costs its stream ~6 us) the other launches of a
  * fused cadence carry event pairs too: cls 1 the solve launch, 2 the chain (or look-ahead gather) launch, 3 the panel launch,
- * 0 the pass; 4 the k_direct launch of ekf_update_direct; 5 the k_linear launch of ekf_update_linear; 6 the k_join launch of ekf_join_maps (with its snapshot launch).  Does not reset: read before ekf_profile_read. */
+ * 0 the pass; 4 the k_direct launch of ekf_update_direct; 5 the k_linear launch of ekf_update_linear; 6 the k_join launch of ekf_join_maps (with its snapshot launch); 7 the k_predict_pose launch of ekf_predict_linear.  Does not reset: read before ekf_profile_read. */
 int ekf_profile_read_class(ekf_handle *h, int cls, double *ms_total, long long *launches);
 /* Options: name (default, allowed values) meaning.  Unknown names and values out of range fail with EKF_ERR_ARG.
  *   "flush_every"         (0, 0..64)    steps per covariance pass; 0 = auto, by "rank_limit"

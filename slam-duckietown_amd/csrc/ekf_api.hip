@@ -251,6 +251,11 @@ struct ekf_handle : ekf::HostPlan {
   ekf::LinearPlan linear_plan;
   std::vector<int> linear_ints;
   std::vector<double> linear_dbls, linear_out;
+  // ekf_predict_linear (allocated on first use): the input ring of k_predict_pose's records, RING slots of batch records used
+  // in the order of h_ring / d_ring and under the same events (ring_take / ring_done), and the call's plan
+  DeviceBuf<PredictIn> d_pred;
+  PinnedBuf<PredictIn> h_pred;
+  ekf::PredictPlan predict_plan;
   std::string err;
 };
 
@@ -2317,6 +2322,50 @@ extern "C" int ekf_predict(ekf_handle* h, const double* lin, const double* ang) 
   return do_step(h, FLAG_PREDICT, lin, ang, nullptr, nullptr, nullptr, nullptr, 0);
 }
 
+// A prediction with the caller's motion model (k_predict_pose, ekf_predict_linear.hip): enqueued like ekf_predict -- the records go
+// up through a ring slot as do_step's, nothing is waited for -- behind everything on the handle's stream and on the second one
+// (join_aux).  The kernel works on P_base in place, under the pending ranks where there are any: no covariance pass, and neither
+// pending_k / pending_steps nor the bound, the floor or any counter moves; cur / dcur do not flip (the pose mean is written in place).
+// The pose log gets the step's row from k_pose_step on either path (the small-state path writes rows only from its own launch).
+extern "C" int ekf_predict_linear(ekf_handle* h, int b0, int count, const double* pose, const double* F, const double* Q,
+                                  const int* apply) {
+  if (!h) return EKF_ERR_ARG;
+  if (int rc = check_host_bad(h, "ekf_predict_linear")) return rc;
+  if (int rc = refresh_sizes(h)) return rc;
+  PredictPlan& pp = h->predict_plan;
+  if (const char* why = plan_predict_linear(h, b0, count, pose, F, Q, apply, pp)) return bad_arg(h, "ekf_predict_linear", why);
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t B = (size_t)h->batch;
+  RES_TRY(h, "ekf_predict_linear's input ring", res::ensure_group(nullptr, res::want(h->d_pred, B * RING), res::want(h->h_pred, B * RING)));
+  if (int rc = join_aux(h)) return rc;
+  int slot;
+  if (int rc = ring_take(h, &slot)) return rc;
+  PredictIn* hs = h->h_pred.p + (size_t)slot * B;
+  PredictIn* ds = h->d_pred.p + (size_t)slot * B;
+  std::copy(pp.rec.begin(), pp.rec.end(), hs);
+  // (small-state path: the workgroups fetch their record straight from the pinned ring, as that path's steps do -- see do_step)
+  const bool direct = small_path(h);
+  if (!direct) {
+    HIP_TRY(h, hipMemcpyAsync(ds, hs, sizeof(PredictIn) * (size_t)count, hipMemcpyHostToDevice, h->stream));
+    if (int rc = ring_done(h, slot)) return rc;
+  }
+  if (pp.n_hi > 0) {
+    ProfBracket pb;
+    if (int rc = prof_open(h, 7, h->stream, &pb)) return rc;
+    launch_predict_pose(h->stream, pending_view(h, b0, count), h->dP.p, h->dmu2[h->cur].p, direct ? hs : ds, pp.n_hi);
+    if (int rc = prof_close(h, &pb)) return rc;
+    HIP_TRY(h, hipGetLastError());
+  }
+  if (direct)
+    if (int rc = ring_done(h, slot)) return rc;              // (the slot is free once the kernel has run)
+  if (h->dpose.p) {                                    // a logged step, as a lone ekf_predict
+    launch_pose_step(h->stream, pending_view(h, 0, h->batch), pose_log(h, (long)(h->pose_steps % h->pose_cap)));
+    HIP_TRY(h, hipGetLastError());
+    h->pose_steps += 1;
+  }
+  return EKF_OK;
+}
+
 extern "C" int ekf_update(ekf_handle* h, const int* idx, const double* range, const double* bearing,
                           const int* m, int stride) {
   return do_step(h, FLAG_UPDATE, nullptr, nullptr, idx, range, bearing, m, stride);
@@ -2666,8 +2715,8 @@ extern "C" int ekf_profile_read(ekf_handle* h, double* pass_ms_total, long long*
 }
 
 // ("profile_kernels" = 1) the same for the cadence's other launches: cls 1 the solve launch, 2 the chain / look-ahead gather
-// launch, 3 the panel launch (0: the covariance pass), 4 k_direct, 5 k_linear, 6 k_join (with its snapshot launch); does not
-// reset -- read these BEFORE ekf_profile_read
+// launch, 3 the panel launch (0: the covariance pass), 4 k_direct, 5 k_linear, 6 k_join (with its snapshot launch), 7
+// k_predict_pose; does not reset -- read these BEFORE ekf_profile_read
 extern "C" int ekf_profile_read_class(ekf_handle* h, int cls, double* ms_total, long long* launches) {
   if (!h || !ms_total || !launches) return EKF_ERR_ARG;
   HIP_TRY(h, hipSetDevice(h->device));

@@ -65,6 +65,19 @@ constexpr int LINEAR_INTS = 4 + LINEAR_NS + 1;
 __host__ __device__ constexpr int linear_dbls(int dp, int nsl) { return dp * nsl + dp + dp * dp + 2; }
 static_assert(LINEAR_NS <= DIRECT_ROWS && LINEAR_ROWS % 4 == 0 && LINEAR_ROWS <= KTOT && LINEAR_INTS % 2 == 0,
               "a linear update's rows fit the pending ranks");
+// ekf_predict_linear (k_predict_pose, ekf_predict_linear.hip): one trajectory's record (host -> device, 192 B), for the
+// trajectories [b0, b0 + count) of the call: the new pose mean, F = d(new pose)/d(old pose) row-major, Q row-major (the upper
+// triangle is read), whether the trajectory takes part, and its active bound capped by its size (the host's: dso[b].neff may be
+// stale behind an upload).
+struct alignas(16) PredictIn {
+  double pose[3];
+  double F[9];
+  double Q[9];
+  int apply;
+  int bound;
+  double pad[2];
+};
+static_assert(sizeof(PredictIn) == 192, "PredictIn is 192 bytes");
 __host__ __device__ __forceinline__ int p_lds(int ld) { return ld < PPW ? ld : PPW; }
 __host__ __device__ __forceinline__ long p_col(int ld, int j) { return (long)(j >> 12) * ((long)ld * PPW) + (j & (PPW - 1)); }
 // the same as a 32-bit byte offset (ekf_create bounds one covariance by 4 GiB)

@@ -856,6 +856,60 @@ inline const char* plan_linear(const HostPlan* h, int b0, int count, const int* 
 // the instantiation of k_linear that serves `kpad` rows: the smallest compile-time row count that holds them
 inline int linear_rows_cap(int kpad) { return kpad <= 4 ? 4 : kpad <= 8 ? 8 : kpad <= 16 ? 16 : LINEAR_ROWS; }
 
+// ekf_predict_linear (k_predict_pose, ekf_predict_linear.hip): the inputs of trajectories [b0, b0 + count) checked -- the range
+// inside the bank, pose, F and Q given, and for every APPLIED trajectory (apply == NULL: all) finite pose, F and Q (of Q what is
+// read: the upper triangle) and a Q that is a covariance, possibly singular: no negative diagonal entry, q_ij^2 <= q_ii q_jj
+// (plan_join's test for covT) and no negative determinant of the symmetrised upper triangle -- and turned into the launch's
+// records (ekf_device.h: PredictIn), each with its trajectory's active bound capped by its size, plus `n_hi`, the largest bound
+// of an applied trajectory (the grid; 0: nothing is applied).  An all-zero Q and a singular F are legal.
+// Both singular tests allow for the rounding of their own arithmetic, so that a Q of rank 1 or 2 -- a a^T formed in floating
+// point: q_ij^2 and q_ii q_jj then differ by a few roundings either way, and the determinant, exactly zero, comes out at
+// +-1e-16 q_00 q_11 q_22 -- is not refused for it.  Pairwise: q_ij, q_ii and q_jj carry one rounding each, their products one
+// more: "greater" means beyond q_ii q_jj (1 + 8 eps).  The determinant is a sum of six products of three entries, each at most
+// q_00 q_11 q_22 in magnitude once the pairwise test has passed, ~12 roundings of that size: "negative" means below
+// -32 eps q_00 q_11 q_22.
+// Returns nullptr, or what is wrong with the arguments (then nothing of `pp` is to be used).
+struct PredictPlan {
+  int n_hi = 0;
+  std::vector<PredictIn> rec;      // count
+};
+inline const char* plan_predict_linear(const HostPlan* h, int b0, int count, const double* pose, const double* F, const double* Q,
+                                       const int* apply, PredictPlan& pp) {
+  if (!bank_range_ok(h, b0, count)) return BANK_RANGE_WHY;
+  if (!pose || !F || !Q) return "NULL pose, F or Q";
+  constexpr double eps = 2.220446049250313e-16;
+  pp.n_hi = 0;
+  pp.rec.assign((size_t)count, PredictIn{});
+  for (int bi = 0; bi < count; ++bi) {
+    PredictIn& r = pp.rec[(size_t)bi];
+    const int b = b0 + bi;
+    r.apply = !apply || apply[bi] != 0;
+    r.bound = h->opt_active_bound ? std::min(h->neff[b], h->n[b]) : h->n[b];
+    if (!r.apply) continue;
+    const double *p = pose + 3 * (size_t)bi, *f = F + 9 * (size_t)bi, *q = Q + 9 * (size_t)bi;
+    for (int a = 0; a < 3; ++a) {
+      if (!std::isfinite(p[a])) return "non-finite pose";
+      for (int c = 0; c < 3; ++c) {
+        if (!std::isfinite(f[3 * a + c])) return "non-finite F";
+        if (c >= a && !std::isfinite(q[3 * a + c])) return "non-finite Q";
+      }
+    }
+    for (int a = 0; a < 3; ++a) {
+      if (q[4 * a] < 0.0) return "Q has a negative diagonal entry";
+      for (int c = a + 1; c < 3; ++c)
+        if (q[3 * a + c] * q[3 * a + c] > q[4 * a] * q[4 * c] * (1.0 + 8.0 * eps)) return "Q is not a covariance (q_ij^2 > q_ii q_jj)";
+    }
+    const double det = q[0] * (q[4] * q[8] - q[5] * q[5]) - q[1] * (q[1] * q[8] - q[5] * q[2]) + q[2] * (q[1] * q[5] - q[4] * q[2]);
+    if (det < -32.0 * eps * q[0] * q[4] * q[8]) return "Q is not a covariance (negative determinant)";
+    std::copy_n(p, 3, r.pose);
+    std::copy_n(f, 9, r.F);
+    for (int a = 0; a < 3; ++a)
+      for (int c = 0; c < 3; ++c) r.Q[3 * a + c] = q[3 * std::min(a, c) + std::max(a, c)];
+    pp.n_hi = std::max(pp.n_hi, r.bound);
+  }
+  return nullptr;
+}
+
 // ekf_copy_trajectories (k_copy_traj, ekf_copy.hip): the k pairs (src_b[i] of `src` -> dst_b[i] of `dst`) checked -- indices
 // inside their banks, no destination twice, inside one handle no trajectory both read and written, the same device, every
 // source's size within the destination's n_max -- and grouped by source: a group is one source and up to COPY_FANOUT of its

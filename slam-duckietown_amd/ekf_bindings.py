@@ -141,6 +141,7 @@ ABI = {
     "ekf_copy_trajectories": (C.c_int, [C.c_void_p, _ip, C.c_void_p, _ip, C.c_int]),
     "ekf_join_maps": (C.c_int, [C.c_void_p, _ip, C.c_void_p, _ip, C.c_int, _dp, _dp, _ip, _ip, C.c_int]),
     "ekf_predict": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "ekf_predict_linear": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _ip]),
     "ekf_update": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _ip, C.c_int]),
     "ekf_step": (C.c_int, [C.c_void_p, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
     "ekf_host_alloc": (C.c_void_p, [C.c_size_t]),
@@ -228,6 +229,20 @@ def _i32(a):
 
 def _p(a, typ=_dp):
     return a.ctypes.data_as(typ)
+
+
+def compose_pose(pose, delta):
+    """``pose (+) delta``: the pose after a motion increment ``delta = (dx, dy, dtheta)`` given in the robot frame of ``pose =
+    (x, y, theta)`` -- what wheel or visual odometry reports --, theta wrapped to [-pi, pi) (``evaluation.wrap_angle``'s
+    convention).  Returns ``(new pose (3,), F (3, 3), J (3, 3))`` with ``F = d(new pose)/d(pose)`` and ``J = d(new pose)/d(delta)
+    = diag(R(theta), 1)``: the process noise of an increment with covariance ``cov`` is ``J cov J^T``."""
+    x, y, th = (float(v) for v in np.asarray(pose, dtype=np.float64).reshape(3))
+    dx, dy, dth = (float(v) for v in np.asarray(delta, dtype=np.float64).reshape(3))
+    c, s = math.cos(th), math.sin(th)
+    new = np.array([x + c * dx - s * dy, y + s * dx + c * dy, (th + dth + np.pi) % (2.0 * np.pi) - np.pi])
+    F = np.array([[1.0, 0.0, -s * dx - c * dy], [0.0, 1.0, c * dx - s * dy], [0.0, 0.0, 1.0]])
+    J = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+    return new, F, J
 
 
 _SMALL_OUT_N = 131        # (PACK_SMALL_N of csrc/ekf_api.hip: states the library hands over through one pinned buffer)
@@ -898,6 +913,66 @@ class EkfSlam:
         gate = None if confidence is None else float(self._chi2_gate(confidence, len(z)))
         return self.update_linear(lms, J, R, innovation=y, gate=gate, b=b)
 
+    # -- motion models of the caller's -----------------------------------------------------------
+    def predict_linear(self, pose, F, Q, b: Optional[int] = None, apply=None):
+        """A prediction with the caller's motion model (``ekf_predict_linear``): ``pose`` is the NEW pose mean [x, y, theta],
+        taken verbatim (wrap theta yourself), ``F = d(new pose)/d(old pose)`` (3, 3) and ``Q`` (3, 3; the upper triangle is
+        read; positive semi-definite, all zero allowed) the process noise:  mu[0:3] = pose,  P[r, r] = F P[r, r] F^T + Q,
+        P[r, j] = F P[r, j].  ``b`` None: the whole bank -- ``pose`` (B, 3), ``F`` and ``Q`` (B, 3, 3) or one (3, 3) for every
+        trajectory; ``apply`` (B,) leaves the trajectories with a zero entry bit for bit.  ``b`` given: that trajectory alone.
+        Asynchronous like ``predict``: no covariance pass, no rank, also while ranks are pending; one pose-log row."""
+        if b is None:
+            b0, count = 0, self.batch
+        else:
+            b0, count = int(b), 1
+        pp = _f64(np.asarray(pose, dtype=np.float64).reshape(-1, 3), (count, 3))
+        FF = _f64(np.broadcast_to(np.asarray(F, dtype=np.float64), (count, 3, 3)))
+        QQ = _f64(np.broadcast_to(np.asarray(Q, dtype=np.float64), (count, 3, 3)))
+        ap = None
+        if apply is not None:
+            ap = _i32(np.asarray(apply).reshape(-1) != 0)
+            if ap.shape != (count,):
+                raise ValueError(f"predict_linear: apply needs {count} entries")
+        self._check(self._lib.ekf_predict_linear(self._h, b0, count, _p(pp), _p(FF), _p(QQ), _p(ap, _ip) if ap is not None else None))
+
+    def predict_odometry(self, delta, cov, b: Optional[int] = None):
+        """Odometry as a pose increment: ``delta = (dx, dy, dtheta)`` in the robot frame with its 3 x 3 covariance ``cov`` --
+        ``pose' = pose (+) delta`` (``compose_pose``; theta wrapped to [-pi, pi)), ``F = d(pose (+) delta)/d(pose)``,
+        ``Q = J cov J^T`` with ``J = d/d(delta) = diag(R(theta), 1)``.  Reads the poses with ``joint([], ...)`` (no covariance
+        pass), then ``predict_linear``.  ``b`` None: ``delta`` (B, 3) or one for all, ``cov`` (B, 3, 3) or one for all."""
+        if b is None:
+            count = self.batch
+            poses = np.array(self.joint([[]] * count)[0][:, :3])
+        else:
+            count = 1
+            poses = np.array(self.joint([], int(b))[0][:3]).reshape(1, 3)
+        dd = np.broadcast_to(np.asarray(delta, dtype=np.float64), (count, 3))
+        cv = np.broadcast_to(np.asarray(cov, dtype=np.float64), (count, 3, 3))
+        new, FF, QQ = np.empty((count, 3)), np.empty((count, 3, 3)), np.empty((count, 3, 3))
+        for t in range(count):
+            new[t], FF[t], J = compose_pose(poses[t], dd[t])
+            Cu = np.triu(cv[t])
+            QQ[t] = J @ (Cu + np.triu(Cu, 1).T) @ J.T
+        self.predict_linear(new, FF, QQ, b=b)
+
+    def predict_custom(self, f, u=None, Q=None, jac=None, b: int = 0, step: float = 1e-6):
+        """A motion model of the caller's for trajectory b: ``f(pose, u)`` returns the new pose [x, y, theta] (wrapped by the
+        caller where it matters), ``jac(pose, u)`` its 3 x 3 Jacobian by the pose -- or, when ``jac`` is None, central
+        differences of ``f`` with the absolute `step` per coordinate (error of a Jacobian entry: step^2 / 6 times the third
+        derivative plus eps |f| / step; a theta that ``f`` wraps must not cross the seam within `step`).  ``Q`` (3, 3; None: zero)
+        is the process noise.  Reads the pose with ``joint([], b)`` (no covariance pass), then ``predict_linear``."""
+        x = np.array(self.joint([], int(b))[0][:3], dtype=np.float64)
+        new = np.asarray(f(x, u), dtype=np.float64).reshape(3)
+        if jac is not None:
+            J = np.asarray(jac(x, u), dtype=np.float64).reshape(3, 3)
+        else:
+            J = np.empty((3, 3))
+            for c in range(3):
+                e = np.zeros(3)
+                e[c] = step
+                J[:, c] = (np.asarray(f(x + e, u), dtype=np.float64).reshape(3) - np.asarray(f(x - e, u), dtype=np.float64).reshape(3)) / (2.0 * step)
+        self.predict_linear(new, J, np.zeros((3, 3)) if Q is None else Q, b=int(b))
+
     def _unlabelled(self, ranges, bearings, m):
         """Unlabelled observations as padded (B, stride) float64 arrays + m (B,) int32: (B, S) arrays with `m` (default: S
         each), or one list per trajectory (a flat list for a single trajectory)."""
@@ -1503,7 +1578,7 @@ class EkfSlam:
 
     def profile_read_class(self, cls: int):
         """(total ms, number) of the bracketed launches of class `cls` (1 solve, 2 chain / gather, 3 panel, 4 the k_direct launch of
-        update_direct, 5 the k_linear launch of update_linear, 6 the k_join launch of join; needs the option
+        update_direct, 5 the k_linear launch of update_linear, 6 the k_join launch of join, 7 the k_predict_pose launch of predict_linear; needs the option
         "profile_kernels"); read before `profile_read`, which resets."""
         ms, cnt = C.c_double(), C.c_longlong()
         self._check(self._lib.ekf_profile_read_class(self._h, int(cls), C.byref(ms), C.byref(cnt)))

@@ -1,0 +1,193 @@
+// Sanitizer build of plan_predict_linear (slam-duckietown_amd/csrc/ekf_host_plan.h), the host-side validation and plan of
+// ekf_predict_linear:
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DEKF_HOST_ONLY
+//       -I slam-duckietown_amd/csrc -I include tests/predict_plan_check.cpp -o predict_plan_check
+// Every refusal the header lists, the legal singular inputs (an all-zero Q, a Q of rank 1 and 2, a singular F), what a
+// trajectory that is not applied may carry, the records and the grid size, and randomised calls whose arrays are allocated
+// to exactly the size the header states, so that a read beyond them is a sanitizer report; any report or failed check ends
+// the run with a non-zero status.  With a file name as its argument the program reads calls from it instead -- one per
+// line: 3 pose, 9 F, 9 Q values -- and expects every one of them to be accepted: tests/test_predict_linear_cpu.py hands it the
+// inputs of the GPU tests' cases that way (CPU only).
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <limits>
+#include <random>
+#include <vector>
+
+#include "ekf_host_plan.h"
+
+using namespace ekf;
+
+static long checks = 0;
+#define CHECK(cond, ...)                                              \
+  do {                                                                \
+    ++checks;                                                         \
+    if (!(cond)) {                                                    \
+      std::fprintf(stderr, "FAILED %s:%d: %s  [", __FILE__, __LINE__, #cond); \
+      std::fprintf(stderr, __VA_ARGS__);                              \
+      std::fprintf(stderr, "]\n");                                    \
+      std::exit(1);                                                   \
+    }                                                                 \
+  } while (0)
+
+// two trajectories: a rotation-like F with a full Q, and F = I with a diagonal Q; below Q's diagonal: never read
+struct Call {
+  int b0 = 0, count = 2;
+  std::vector<double> pose{1.0, -2.0, 0.5, 0.25, 4.0, -3.0};
+  std::vector<double> F{0.9, -0.2, 0.1, 0.2, 1.1, -0.3, 0.0, 0.05, 1.0, 1, 0, 0, 0, 1, 0, 0, 0, 1};
+  std::vector<double> Q{0.04, 0.01, -0.005, 1e300, 0.03, 0.002, 1e300, 1e300, 0.01, 0.01, 0, 0, 1e300, 0.01, 0, 1e300, 1e300, 0.0025};
+  std::vector<int> apply;
+  bool null_pose = false, null_F = false, null_Q = false;
+  const char* plan(const HostPlan& h, PredictPlan& pp) const {
+    return plan_predict_linear(&h, b0, count, null_pose ? nullptr : pose.data(), null_F ? nullptr : F.data(),
+                               null_Q ? nullptr : Q.data(), apply.empty() ? nullptr : apply.data(), pp);
+  }
+};
+
+static int from_file(const char* path) {
+  std::FILE* fp = std::fopen(path, "r");
+  if (!fp) {
+    std::fprintf(stderr, "cannot open %s\n", path);
+    return 2;
+  }
+  HostPlan h;
+  h.batch = 1;
+  h.n = {3 + 2 * 20};
+  h.neff = {3 + 2 * 20};
+  PredictPlan pp;
+  std::vector<double> v(21);
+  for (;;) {
+    int got = 0;
+    for (; got < 21; ++got)
+      if (std::fscanf(fp, "%lf", &v[(size_t)got]) != 1) break;
+    if (got == 0) break;
+    CHECK(got == 21, "a line of %d values", got);
+    const char* why = plan_predict_linear(&h, 0, 1, v.data(), v.data() + 3, v.data() + 12, nullptr, pp);
+    CHECK(why == nullptr, "case %ld refused: %s", checks, why);
+    CHECK(pp.rec.size() == 1 && pp.rec[0].apply == 1 && pp.n_hi == 43, "record");
+  }
+  std::fclose(fp);
+  std::printf("%ld checks passed\n", checks);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1) return from_file(argv[1]);
+  HostPlan h;
+  h.batch = 3;
+  h.n = {3 + 2 * 40, 3 + 2 * 10, 3 + 2 * 20};
+  h.neff = {3 + 2 * 12, 3 + 2 * 10, 3};
+  const double inf = std::numeric_limits<double>::infinity(), nan = std::nan("");
+  PredictPlan pp;
+  {
+    Call c;
+    CHECK(c.plan(h, pp) == nullptr, "the good call");
+    CHECK(pp.rec.size() == 2 && pp.rec[0].apply == 1 && pp.rec[1].apply == 1, "records");
+    CHECK(pp.rec[0].bound == 27 && pp.rec[1].bound == 23 && pp.n_hi == 27, "%d %d %d", pp.rec[0].bound, pp.rec[1].bound, pp.n_hi);
+    for (int a = 0; a < 3; ++a) {
+      CHECK(pp.rec[1].pose[a] == c.pose[3 + a], "pose %d", a);
+      for (int q = 0; q < 3; ++q) {
+        CHECK(pp.rec[0].F[3 * a + q] == c.F[3 * a + q], "F %d %d", a, q);
+        CHECK(pp.rec[0].Q[3 * a + q] == c.Q[3 * std::min(a, q) + std::max(a, q)], "Q is mirrored from its upper triangle %d %d", a, q);
+      }
+    }
+    h.opt_active_bound = 0;                                // the whole state counts
+    CHECK(c.plan(h, pp) == nullptr && pp.rec[0].bound == 83 && pp.n_hi == 83, "no active bound");
+    h.opt_active_bound = 1;
+    c.b0 = 1;                                              // trajectories 1 and 2: the second one's bound is 3
+    CHECK(c.plan(h, pp) == nullptr && pp.rec[0].bound == 23 && pp.rec[1].bound == 3 && pp.n_hi == 23, "range from 1");
+    c.apply = {0, 1};
+    CHECK(c.plan(h, pp) == nullptr && pp.rec[0].apply == 0 && pp.rec[1].apply == 1 && pp.n_hi == 3, "apply");
+    c.apply = {0, 0};
+    CHECK(c.plan(h, pp) == nullptr && pp.n_hi == 0, "nothing applied");
+    c.apply = {0, 7};                                      // what a trajectory that is not applied brings is not looked at
+    c.pose[0] = nan;
+    c.F[4] = inf;
+    c.Q[0] = -1.0;
+    CHECK(c.plan(h, pp) == nullptr && pp.rec[1].apply == 1, "ignored entries");
+  }
+  {
+    Call c;                                                // the legal singular inputs
+    for (int e = 0; e < 9; ++e) c.Q[e] = e % 4 == 0 || e == 1 || e == 2 || e == 5 ? 0.0 : 1e300;
+    CHECK(c.plan(h, pp) == nullptr, "an all-zero Q");
+    for (int e = 0; e < 9; ++e) c.F[e] = 0.0;
+    CHECK(c.plan(h, pp) == nullptr, "a zero F");
+    const double a[3] = {0.3, -0.7, 0.11}, b[3] = {1.3, 0.2, -0.4};
+    for (int r = 0; r < 3; ++r)
+      for (int q = r; q < 3; ++q) c.Q[3 * r + q] = a[r] * a[q];
+    CHECK(c.plan(h, pp) == nullptr, "a Q of rank 1");
+    for (int r = 0; r < 3; ++r)
+      for (int q = r; q < 3; ++q) c.Q[3 * r + q] = a[r] * a[q] + b[r] * b[q];
+    CHECK(c.plan(h, pp) == nullptr, "a Q of rank 2");
+    c.Q = {0.04, 0, 0, 1e300, 0, 0, 1e300, 1e300, 0, 0.01, 0, 0, 0, 0.01, 0, 0, 0, 0.0025};
+    CHECK(c.plan(h, pp) == nullptr, "noise on x alone");
+  }
+  auto refused = [&](const Call& c, const char* what) {
+    const char* why = c.plan(h, pp);
+    CHECK(why != nullptr, "%s was accepted", what);
+  };
+  { Call c; c.b0 = 2; refused(c, "range past the bank"); }
+  { Call c; c.b0 = -1; refused(c, "negative b0"); }
+  { Call c; c.count = 0; refused(c, "count 0"); }
+  { Call c; c.count = -1; refused(c, "negative count"); }
+  { Call c; c.null_pose = true; refused(c, "NULL pose"); }
+  { Call c; c.null_F = true; refused(c, "NULL F"); }
+  { Call c; c.null_Q = true; refused(c, "NULL Q"); }
+  { Call c; c.pose[2] = nan; refused(c, "NaN pose"); }
+  { Call c; c.pose[3] = inf; refused(c, "infinite pose"); }
+  { Call c; c.F[7] = nan; refused(c, "NaN F"); }
+  { Call c; c.F[9 + 2] = -inf; refused(c, "infinite F"); }
+  { Call c; c.Q[2] = nan; refused(c, "NaN Q"); }
+  { Call c; c.Q[9 + 4] = inf; refused(c, "infinite Q"); }
+  { Call c; c.Q[4] = -0.03; refused(c, "negative variance"); }
+  { Call c; c.Q[9 + 8] = -1e-12; refused(c, "negative variance of theta"); }
+  { Call c; c.Q[1] = 0.05; refused(c, "q_01^2 > q_00 q_11"); }
+  { Call c; c.Q[9 + 5] = 0.01; refused(c, "q_12^2 > q_11 q_22"); }
+  {
+    Call c;                                                // every pair passes, the determinant is negative: correlations 0.9, 0.9, -0.9
+    const double s[3] = {0.2, 0.1, 0.05}, r[3] = {0.9, -0.9, 0.9};   // (0,1), (0,2), (1,2)
+    c.Q[0] = s[0] * s[0], c.Q[4] = s[1] * s[1], c.Q[8] = s[2] * s[2];
+    c.Q[1] = r[0] * s[0] * s[1], c.Q[2] = r[1] * s[0] * s[2], c.Q[5] = r[2] * s[1] * s[2];
+    refused(c, "a negative determinant");
+  }
+
+  // randomised calls: Q = A A^T of rank 0..3 at any scale is accepted, the records carry the inputs, n_hi the largest bound
+  std::mt19937 rng(11);
+  std::normal_distribution<double> gauss(0.0, 1.0);
+  for (int it = 0; it < 3000; ++it) {
+    Call c;
+    c.count = 1 + (int)(rng() % 3);
+    c.b0 = (int)(rng() % (4 - c.count));
+    c.pose.assign((size_t)c.count * 3, 0.0);
+    c.F.assign((size_t)c.count * 9, 0.0);
+    c.Q.assign((size_t)c.count * 9, nan);
+    for (auto& v : c.pose) v = gauss(rng);
+    for (auto& v : c.F) v = gauss(rng);
+    int n_hi = 0;
+    for (int bi = 0; bi < c.count; ++bi) {
+      const int rank = (int)(rng() % 4);
+      const double scale = std::pow(10.0, (double)(rng() % 13) - 8.0);
+      double A[3][3];
+      for (auto& row : A)
+        for (auto& v : row) v = gauss(rng);
+      for (int a = 0; a < 3; ++a)
+        for (int q = a; q < 3; ++q) {
+          double v = 0.0;
+          for (int e = 0; e < rank; ++e) v += A[a][e] * A[q][e];
+          c.Q[(size_t)bi * 9 + 3 * a + q] = v * scale;
+        }
+      n_hi = std::max(n_hi, std::min(h.neff[c.b0 + bi], h.n[c.b0 + bi]));
+    }
+    const char* why = c.plan(h, pp);
+    CHECK(why == nullptr, "random call %d: %s", it, why);
+    CHECK((int)pp.rec.size() == c.count && pp.n_hi == n_hi, "n_hi %d for %d", pp.n_hi, n_hi);
+    for (int bi = 0; bi < c.count; ++bi) {
+      const PredictIn& r = pp.rec[(size_t)bi];
+      CHECK(r.apply == 1 && r.bound <= h.n[c.b0 + bi] && r.bound >= 3, "record %d", bi);
+      for (int e = 0; e < 9; ++e) CHECK(r.F[e] == c.F[(size_t)bi * 9 + e] && std::isfinite(r.Q[e]), "entry %d", e);
+    }
+  }
+  std::printf("%ld checks passed\n", checks);
+  return 0;
+}
