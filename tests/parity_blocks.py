@@ -13,6 +13,11 @@ mean:
 never-observed landmarks (block-diagonal start: `mean0` / `diag0` given):
   mean and variance bit-equal to the start, every off-diagonal entry of their rows and columns exactly 0.
 
+`assert_update_close` judges ONE direct or linear update applied to a known state the same way: the landmarks fall into three
+classes by the state the call found -- active before the call (the pieces above), never observed and first touched by this call
+(own block within 32 eps landmark_init_var, mean within 1e-9, cross terms exact zeros for a direct fix and entrywise for a dense
+H), never observed and not named (mean, variance and whole rows bit for bit, exact zeros) -- and P must be exactly symmetric.
+
 Every assertion message names the piece and the measured value.  A plain module (not a conftest): tests import it.
 """
 import numpy as np
@@ -125,6 +130,95 @@ def assert_filter_close(mu, P, om, oP, observed, mean0=None, diag0=None, tol=1e-
                 nz = np.count_nonzero(rows)
                 assert nz == 0, f"{what}never-observed cross terms: {nz} non-zero entries in rows {r[0]}..{r[-1]}"
     return err
+
+
+UPDATE_PIECES = PIECES + ("touched_block", "touched_mean", "touched_cross")
+
+
+def landmark_classes(before_P, touched, init_var):
+    """The landmarks of a state by what an update finds: (active, first, rest) -- variance below `init_var` in `before_P`
+    (observed, or fixed, at some time), never observed and named in `touched`, never observed and not named."""
+    d = np.diag(np.asarray(before_P))
+    N = (len(d) - 3) // 2
+    never = ~((d[3::2] < init_var) & (d[4::2] < init_var))
+    named = np.zeros(N, dtype=bool)
+    named[[int(l) for l in touched if int(l) >= 0]] = True
+    lms = np.arange(N)
+    return lms[~never], lms[never & named], lms[never & ~named]
+
+
+def assert_update_close(got, want, before, touched, init_var, tol, what="", entry_tol=None, first_cross_tol=None):
+    """ONE update (direct or linear) applied to a known state: `got` = (mean, P) after the call, `want` the reference's
+    result, `before` the state the call found, `touched` the landmarks the call names.  The landmarks fall into three
+    classes by `before` (landmark_classes), each judged on its own scale; returns {piece: measured value}.
+
+    active before the call, and the pose: the pieces of `assert_filter_close` (PIECES) of `got` against `want`, each below
+      `tol`; the per-entry maxima corr_max and mean_landmarks below `entry_tol` where given (a dense H that ties a
+      never-observed landmark in: its 1e4 cancels inside entries of the active part too).
+    first touched by this call (never observed before): own 2 x 2 block within 32 eps init_var absolutely (the update forms
+      v - v^2 / (v + R)), mean within 1e-9 relatively (`touched_block`, `touched_mean`); their cross terms with everything
+      else (`touched_cross`): with `first_cross_tol` None (a direct fix) bit-equal to `before` and exactly zero, else
+      max |dP_ij| / sqrt(wP_ii wP_jj) against the active part and among themselves below it, exactly zero against the rest.
+    untouched and never observed: mean, variance and whole rows of P bit-equal to `before`, cross terms exactly zero.
+    `got`'s covariance must be exactly symmetric."""
+    mu, P = np.asarray(got[0]), np.asarray(got[1])
+    wm, wP = np.asarray(want[0]), np.asarray(want[1])
+    bm, bP = np.asarray(before[0]), np.asarray(before[1])
+    n = len(mu)
+    assert P.shape == (n, n) and wP.shape == (n, n) and bP.shape == (n, n) and len(wm) == n and len(bm) == n, \
+        f"{what}shapes differ: got {P.shape}, want {wP.shape}, before {bP.shape}"
+    for r0 in range(0, n, 512):                        # (in chunks of rows: the panel cases hold 136 MB)
+        assert np.array_equal(P[r0:r0 + 512], P[:, r0:r0 + 512].T), f"{what}asymmetry: P != P^T in rows {r0}..{r0 + 511}"
+    active, first, rest = landmark_classes(bP, touched, init_var)
+    act = np.concatenate([np.arange(3), landmark_rows(active)]).astype(np.int64)
+    err = active_errors(mu[act], P[np.ix_(act, act)], wm[act], wP[np.ix_(act, act)])
+    check_errors(err, tol, what, entry_tol)
+    frows, rrows = landmark_rows(first), landmark_rows(rest)
+    if len(first):
+        eps_v = 32 * np.finfo(float).eps * init_var
+        blk = max(float(np.abs(P[a:a + 2, a:a + 2] - wP[a:a + 2, a:a + 2]).max()) for a in 3 + 2 * first)
+        err["touched_block"] = blk
+        assert blk <= eps_v, f"{what}touched_block: {blk:.3e} exceeds 32 eps init_var = {eps_v:.3e}"
+        dm = max(float(np.abs(mu[a:a + 2] - wm[a:a + 2]).max() / max(1.0, np.abs(wm[a:a + 2]).max())) for a in 3 + 2 * first)
+        err["touched_mean"] = dm
+        assert dm <= 1e-9, f"{what}touched_mean: {dm:.3e} exceeds 1e-9"
+        own = np.zeros((len(frows), n), dtype=bool)    # a first-touched landmark's own 2 x 2 block, in its two rows
+        for i, r in enumerate(frows):
+            a = 3 + 2 * ((r - 3) // 2)
+            own[i, a:a + 2] = True
+        rows = P[frows]
+        if first_cross_tol is None:
+            same = np.array_equal(rows[~own], bP[frows][~own])
+            err["touched_cross"] = float(np.abs(rows[~own]).max())
+            assert same and err["touched_cross"] == 0.0, \
+                f"{what}touched_cross: a direct fix of a never-observed landmark moved its cross terms (max {err['touched_cross']:.3e})"
+        else:
+            cols = np.concatenate([act, frows])
+            d = np.sqrt(np.outer(np.diag(wP)[frows], np.diag(wP)[cols]))
+            dev = np.abs(rows[:, cols] - wP[np.ix_(frows, cols)]) / d
+            dev[own[:, cols]] = 0.0
+            err["touched_cross"] = float(dev.max())
+            assert err["touched_cross"] < first_cross_tol and err["touched_cross"] < REL_TOL, \
+                f"{what}touched_cross: {err['touched_cross']:.3e} exceeds {first_cross_tol:g}"
+            assert not rows[:, rrows].any(), f"{what}touched_cross: non-zero against never-observed landmarks"
+    if len(rest):
+        bad = np.flatnonzero(mu[rrows] != bm[rrows])
+        assert not len(bad), f"{what}never-observed mean: {len(bad)} entries differ from before the call (first at {rrows[bad[0]]})"
+        bad = np.flatnonzero(np.diag(P)[rrows] != np.diag(bP)[rrows])
+        assert not len(bad), f"{what}never-observed variance: {len(bad)} entries differ from before the call (first at {rrows[bad[0]]})"
+        assert not P[np.ix_(act, rrows)].any(), f"{what}never-observed cross terms: non-zero in the active rows"
+        for r0 in range(0, len(rrows), 512):
+            r = rrows[r0:r0 + 512]
+            rows = P[r]
+            assert np.array_equal(rows, bP[r]), f"{what}never-observed rows {r[0]}..{r[-1]} differ from before the call"
+            rows[np.arange(len(r)), r] = 0.0
+            nz = np.count_nonzero(rows)
+            assert nz == 0, f"{what}never-observed cross terms: {nz} non-zero entries in rows {r[0]}..{r[-1]}"
+    return err
+
+
+def fmt_update(err):
+    return " ".join(f"{k}={err[k]:.2e}" for k in UPDATE_PIECES if k in err)
 
 
 def assert_marginals_close(pose, lms, oP, observed, diag0=None, tol=1e-9, what=""):
