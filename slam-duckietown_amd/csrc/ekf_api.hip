@@ -239,18 +239,14 @@ struct ekf_handle : ekf::HostPlan {
   // of every destination's pose, its 3 x 3 block and its three pose rows as they stood before the join (join_snap_doubles per pair)
   DeviceBuf<int> djn_tab;
   DeviceBuf<double> djn_snap;
-  // ekf_update_direct (allocated on first use): per trajectory of the bank the row plan (DIRECT_INTS ints), the measurements
-  // (DIRECT_DBLS doubles) and the results (NIS, applied) of k_direct, and their host sides
-  DeviceBuf<double> ddirect;
+  // ekf_update_direct / ekf_update_linear (allocated on first use, grown to the larger need: the two calls never overlap, each
+  // ends in a synchronise): the table of the front's launch for the bank (ekf_host_plan.h: FrontTable -- the plan's ints, the
+  // measurements, the results NIS and applied), its host sides, and each call's plan
+  DeviceBuf<double> dfront;
+  std::vector<int> front_ints;
+  std::vector<double> front_dbls, front_out;
   ekf::DirectPlan direct_plan;
-  std::vector<int> direct_ints;
-  std::vector<double> direct_dbls, direct_out;
-  // ekf_update_linear (allocated on first use): the same for k_linear -- LINEAR_INTS ints, linear_dbls(rows cap, columns) doubles
-  // and the two results per trajectory of the bank
-  DeviceBuf<double> dlinear;
   ekf::LinearPlan linear_plan;
-  std::vector<int> linear_ints;
-  std::vector<double> linear_dbls, linear_out;
   // ekf_predict_linear (allocated on first use): the input ring of k_predict_pose's records, RING slots of batch records used
   // in the order of h_ring / d_ring and under the same events (ring_take / ring_done), and the call's plan
   DeviceBuf<PredictIn> d_pred;
@@ -1455,141 +1451,97 @@ static int flush_pending(ekf_handle* h, hipStream_t st, const CadOut* wv) {
 }
 static int flush_pending(ekf_handle* h) { return flush_pending(h, nullptr); }
 
-// Direct measurements (k_direct, ekf_direct.hip): apply what is pending, let k_direct form the mean and the update's ranks --
-// V = P[s, :], W = -(S^-1 V)^T, zeros for every trajectory that brings nothing or is rejected -- from P_base, then run the
-// covariance pass on them as on any pending ranks.  The launch covers the bank: it also leaves each trajectory's active bound
-// where the pass reads it (dso[b].neff may be stale, e.g. behind an upload) and zeroes the pending pose noise the pass adds.
-extern "C" int ekf_update_direct(ekf_handle* h, int b0, int count, const int* target, const double* z, const double* R,
-                                 const int* m, int stride, const double* gate, double* nis, int* dof, int* applied) {
-  if (int rc = check_b(h, 0, "ekf_update_direct")) return rc;        // (refreshes the sizes a device-side association grew)
-  DirectPlan& dp = h->direct_plan;
-  if (const char* why = plan_direct(h, b0, count, target, z, R, m, stride, gate, dp))
-    return fail(h, EKF_ERR_ARG, std::string("ekf_update_direct: ") + why);
+// ---- the rank fronts: ekf_update_direct (k_direct) and ekf_update_linear (k_linear; ekf_rank_front.h) ----
+// Each call is check_b (which refreshes the sizes a device-side association grew), its plan function, front_run with its pack
+// function and launcher, front_read.  front_run: the trajectories of the range must be defined; room for the launch's table
+// `tab` (ekf_host_plan.h: FrontTable); what is pending is applied, so that the front reads P_base; `pack` fills h->front_ints /
+// front_dbls for the bank (behind the flush: pack_linear raises the bounds).  Where a trajectory brings rows (kpad > 0): the
+// two uploads, `launch(plan, meas, out)` in a profile bracket of class `cls`, the results' copy, and the covariance pass on the
+// ranks the front left, as on any pending ranks, over the bounds it left -- the launch covers the bank: it leaves each
+// trajectory's active bound where the pass reads it (dso[b].neff may be stale, e.g. behind an upload; neff_enq mirrors it
+// for the planner from the table's bound column) and zeroes the pending pose noise the pass adds.  Ends in the call's one
+// synchronise: the results are in h->front_out.
+template <class Pack, class Launch>
+static int front_run(ekf_handle* h, const char* fn, int b0, int count, const FrontTable& tab, int cls, int kpad, Pack pack,
+                     Launch launch) {
   HIP_TRY(h, hipSetDevice(h->device));
   for (int b = b0; b < b0 + count; ++b)
-    if (int rc = check_internal(h, b, "ekf_update_direct")) return rc;
+    if (int rc = check_internal(h, b, fn)) return rc;
   const size_t B = (size_t)h->batch;
-  const size_t int_words = (B * DIRECT_INTS + 1) / 2;  // layout (doubles): the plan (ints, rounded up), measurements, results
-  RES_TRY(h, "ekf_update_direct's tables", h->ddirect.ensure(int_words + B * DIRECT_DBLS + 2 * B));
+  RES_TRY(h, (std::string(fn) + "'s tables").c_str(), h->dfront.reserve(tab.words(B), 0, h->stream));
   if (int rc = flush_pending(h)) return rc;
-  h->direct_ints.assign(B * DIRECT_INTS, 0);
-  h->direct_dbls.assign(B * DIRECT_DBLS, 0.0);
-  h->direct_out.assign(2 * B, 0.0);
-  for (size_t b = 0; b < B; ++b) {
-    int* pi = h->direct_ints.data() + b * DIRECT_INTS;
-    pi[1] = h->opt_active_bound ? std::min(h->neff[b], h->n[b]) : h->n[b];
-    for (int k = 0; k < DIRECT_ROWS; ++k) pi[2 + k] = -1;
-  }
-  for (int bi = 0; bi < count; ++bi) {
-    int* pi = h->direct_ints.data() + (size_t)(b0 + bi) * DIRECT_INTS;
-    double* pd = h->direct_dbls.data() + (size_t)(b0 + bi) * DIRECT_DBLS;
-    pi[0] = dp.D[bi];
-    std::copy_n(dp.s.data() + (size_t)bi * DIRECT_ROWS, DIRECT_ROWS, pi + 2);
-    std::copy_n(dp.src.data() + (size_t)bi * DIRECT_ROWS, DIRECT_ROWS, pi + 2 + DIRECT_ROWS);
-    std::copy_n(z + (size_t)bi * stride * 3, (size_t)m[bi] * 3, pd);
-    std::copy_n(R + (size_t)bi * stride * 9, (size_t)m[bi] * 9, pd + 3 * MMAX);
-    pd[DIRECT_DBLS - 2] = gate ? gate[bi] : INFINITY;
-  }
-  if (dp.kpad > 0) {
-    int* dplan = reinterpret_cast<int*>(h->ddirect.p);
-    double* dmeas = h->ddirect.p + int_words;
-    double* dout = dmeas + B * DIRECT_DBLS;
-    HIP_TRY(h, hipMemcpyAsync(dplan, h->direct_ints.data(), sizeof(int) * h->direct_ints.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(dmeas, h->direct_dbls.data(), sizeof(double) * h->direct_dbls.size(), hipMemcpyHostToDevice, h->stream));
+  pack();
+  h->front_out.assign(2 * B, 0.0);
+  if (kpad > 0) {
+    int* dplan = reinterpret_cast<int*>(h->dfront.p);
+    double* dmeas = h->dfront.p + tab.int_words(B);
+    double* dout = dmeas + B * tab.dbls;
+    HIP_TRY(h, hipMemcpyAsync(dplan, h->front_ints.data(), sizeof(int) * h->front_ints.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(dmeas, h->front_dbls.data(), sizeof(double) * h->front_dbls.size(), hipMemcpyHostToDevice, h->stream));
     ProfBracket pb;
-    if (int rc = prof_open(h, 4, h->stream, &pb)) return rc;
-    launch_direct(h->stream, direct_rows_cap(dp.kpad), bank_view(h), h->ddacc2[h->dcur].p, h->dmu2[h->cur].p, dplan, dmeas, dout, dp.kpad);
+    if (int rc = prof_open(h, cls, h->stream, &pb)) return rc;
+    launch(dplan, dmeas, dout);
     if (int rc = prof_close(h, &pb)) return rc;
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(h->direct_out.data(), dout, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->stream));
-    // the pass: the ranks k_direct left, over the bounds it left (neff_enq mirrors dso[b].neff for the planner)
-    for (size_t b = 0; b < B; ++b) h->neff_enq[b] = h->direct_ints[b * DIRECT_INTS + 1];
-    h->pending_k = dp.kpad;
+    HIP_TRY(h, hipMemcpyAsync(h->front_out.data(), dout, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->stream));
+    for (size_t b = 0; b < B; ++b) h->neff_enq[b] = h->front_ints[b * tab.ints + 1];
+    h->pending_k = kpad;
     if (int rc = flush_pending(h)) {
       for (int b = b0; b < b0 + count; ++b) h->host_bad[b] = 1;       // (the mean has moved, the covariance has not)
       return rc;
     }
   }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return EKF_OK;
+}
+// what the front found for the trajectories of the range, D[bi] rows each: a trajectory without rows has NIS 0 and is not applied
+static void front_read(const ekf_handle* h, int b0, int count, const std::vector<int>& D, double* nis, int* dof, int* applied) {
   for (int bi = 0; bi < count; ++bi) {
-    const bool any = dp.D[bi] > 0;
-    if (nis) nis[bi] = any ? h->direct_out[2 * (size_t)(b0 + bi)] : 0.0;
-    if (dof) dof[bi] = dp.D[bi];
-    if (applied) applied[bi] = any && h->direct_out[2 * (size_t)(b0 + bi) + 1] != 0.0 ? 1 : 0;
+    const bool any = D[bi] > 0;
+    if (nis) nis[bi] = any ? h->front_out[2 * (size_t)(b0 + bi)] : 0.0;
+    if (dof) dof[bi] = D[bi];
+    if (applied) applied[bi] = any && h->front_out[2 * (size_t)(b0 + bi) + 1] != 0.0 ? 1 : 0;
   }
+}
+
+// Direct measurements: V = P[s, :], W = -(S^-1 V)^T, zeros for every trajectory that brings nothing or is rejected.
+extern "C" int ekf_update_direct(ekf_handle* h, int b0, int count, const int* target, const double* z, const double* R,
+                                 const int* m, int stride, const double* gate, double* nis, int* dof, int* applied) {
+  const char* fn = "ekf_update_direct";
+  if (int rc = check_b(h, 0, fn)) return rc;
+  DirectPlan& dp = h->direct_plan;
+  if (const char* why = plan_direct(h, b0, count, target, z, R, m, stride, gate, dp)) return bad_arg(h, fn, why);
+  if (int rc = front_run(
+          h, fn, b0, count, direct_table(), 4, dp.kpad,
+          [&] { pack_direct(h, dp, b0, count, z, R, m, stride, gate, h->front_ints, h->front_dbls); },
+          [&](const int* dplan, const double* dmeas, double* dout) {
+            launch_direct(h->stream, front_rows_cap(dp.kpad, DIRECT_ROWS), bank_view(h), h->ddacc2[h->dcur].p, h->dmu2[h->cur].p, dplan,
+                          dmeas, dout, dp.kpad);
+          }))
+    return rc;
+  front_read(h, b0, count, dp.D, nis, dof, applied);
   return EKF_OK;
 }
 
-// Linear measurements (k_linear, ekf_linear.hip): ekf_update_direct's body with a dense H over a small sub-state -- apply what
-// is pending, let k_linear form the mean and the update's ranks V = H_s P[s, :], W = -(S^-1 V)^T from P_base, then run the
-// covariance pass on them.  Unlike a direct fix a general row correlates its targets: the active bound of every trajectory that
-// brings rows is raised over the highest landmark of its sub-state first, as a landmark update of it would (fill_step).
+// Linear measurements: a dense H over a small sub-state, V = H_s P[s, :], W = -(S^-1 V)^T.  Unlike a direct fix a general row
+// correlates its targets: pack_linear first raises the active bound of every trajectory that brings rows over its sub-state.
 extern "C" int ekf_update_linear(ekf_handle* h, int b0, int count, const int* landmarks, const int* k, int lstride, const double* H,
                                  const double* r, const double* R, const int* d, int dstride, int innovation, const double* gate,
                                  double* nis, int* applied) {
-  if (int rc = check_b(h, 0, "ekf_update_linear")) return rc;        // (refreshes the sizes a device-side association grew)
+  const char* fn = "ekf_update_linear";
+  if (int rc = check_b(h, 0, fn)) return rc;
   LinearPlan& lp = h->linear_plan;
-  if (const char* why = plan_linear(h, b0, count, landmarks, k, lstride, H, r, R, d, dstride, gate, lp))
-    return fail(h, EKF_ERR_ARG, std::string("ekf_update_linear: ") + why);
-  HIP_TRY(h, hipSetDevice(h->device));
-  for (int b = b0; b < b0 + count; ++b)
-    if (int rc = check_internal(h, b, "ekf_update_linear")) return rc;
-  const size_t B = (size_t)h->batch;
-  const int dp = linear_rows_cap(lp.kpad), nsl = 3 + 2 * lstride;
-  const size_t int_words = B * LINEAR_INTS / 2, per = (size_t)linear_dbls(dp, nsl);   // layout (doubles): plan, measurements, results
-  RES_TRY(h, "ekf_update_linear's tables", h->dlinear.ensure(int_words + B * per + 2 * B));
-  if (int rc = flush_pending(h)) return rc;
-  for (int bi = 0; bi < count; ++bi)                   // the bound covers the sub-state of every trajectory that brings rows
-    if (lp.D[bi] > 0) h->neff[b0 + bi] = std::min(h->n[b0 + bi], std::max(h->neff[b0 + bi], 3 + 2 * (lp.lmax[bi] + 1)));
-  h->linear_ints.assign(B * LINEAR_INTS, 0);
-  h->linear_dbls.assign(B * per, 0.0);
-  h->linear_out.assign(2 * B, 0.0);
-  for (size_t b = 0; b < B; ++b) {
-    int* pi = h->linear_ints.data() + b * LINEAR_INTS;
-    pi[1] = h->opt_active_bound ? std::min(h->neff[b], h->n[b]) : h->n[b];
-    pi[2] = 3;
-    for (int j = 0; j <= LINEAR_NS; ++j) pi[4 + j] = j < 3 ? j : -1;
-  }
-  for (int bi = 0; bi < count; ++bi) {
-    int* pi = h->linear_ints.data() + (size_t)(b0 + bi) * LINEAR_INTS;
-    double* pd = h->linear_dbls.data() + (size_t)(b0 + bi) * per;
-    const int D = lp.D[bi], ns = lp.ns[bi];
-    pi[0] = D;
-    pi[2] = ns;
-    std::copy_n(lp.s.data() + (size_t)bi * LINEAR_NS, LINEAR_NS, pi + 4);
-    for (int a = 0; a < D; ++a) {
-      std::copy_n(H + ((size_t)bi * dstride + a) * nsl, ns, pd + (size_t)a * nsl);
-      pd[(size_t)dp * nsl + a] = r[(size_t)bi * dstride + a];
-      for (int q = a; q < D; ++q) pd[(size_t)dp * nsl + dp + (size_t)a * dp + q] = R[((size_t)bi * dstride + a) * dstride + q];
-    }
-    pd[(size_t)dp * nsl + dp + (size_t)dp * dp] = gate ? gate[bi] : INFINITY;
-  }
-  if (lp.kpad > 0) {
-    int* dplan = reinterpret_cast<int*>(h->dlinear.p);
-    double* dmeas = h->dlinear.p + int_words;
-    double* dout = dmeas + B * per;
-    HIP_TRY(h, hipMemcpyAsync(dplan, h->linear_ints.data(), sizeof(int) * h->linear_ints.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(dmeas, h->linear_dbls.data(), sizeof(double) * h->linear_dbls.size(), hipMemcpyHostToDevice, h->stream));
-    ProfBracket pb;
-    if (int rc = prof_open(h, 5, h->stream, &pb)) return rc;
-    launch_linear(h->stream, dp, bank_view(h), h->ddacc2[h->dcur].p, h->dmu2[h->cur].p, dplan, dmeas, dout, lp.kpad, nsl, innovation ? 1 : 0);
-    if (int rc = prof_close(h, &pb)) return rc;
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(h->linear_out.data(), dout, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->stream));
-    // the pass: the ranks k_linear left, over the bounds it left (neff_enq mirrors dso[b].neff for the planner)
-    for (size_t b = 0; b < B; ++b) h->neff_enq[b] = h->linear_ints[b * LINEAR_INTS + 1];
-    h->pending_k = lp.kpad;
-    if (int rc = flush_pending(h)) {
-      for (int b = b0; b < b0 + count; ++b) h->host_bad[b] = 1;       // (the mean has moved, the covariance has not)
-      return rc;
-    }
-  }
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  for (int bi = 0; bi < count; ++bi) {
-    const bool any = lp.D[bi] > 0;
-    if (nis) nis[bi] = any ? h->linear_out[2 * (size_t)(b0 + bi)] : 0.0;
-    if (applied) applied[bi] = any && h->linear_out[2 * (size_t)(b0 + bi) + 1] != 0.0 ? 1 : 0;
-  }
+  if (const char* why = plan_linear(h, b0, count, landmarks, k, lstride, H, r, R, d, dstride, gate, lp)) return bad_arg(h, fn, why);
+  const int cap = front_rows_cap(lp.kpad, LINEAR_ROWS), nsl = 3 + 2 * lstride;
+  if (int rc = front_run(
+          h, fn, b0, count, linear_table(cap, nsl), 5, lp.kpad,
+          [&] { pack_linear(h, lp, b0, count, lstride, H, r, R, dstride, gate, h->front_ints, h->front_dbls); },
+          [&](const int* dplan, const double* dmeas, double* dout) {
+            launch_linear(h->stream, cap, bank_view(h), h->ddacc2[h->dcur].p, h->dmu2[h->cur].p, dplan, dmeas, dout, lp.kpad, nsl,
+                          innovation ? 1 : 0);
+          }))
+    return rc;
+  front_read(h, b0, count, lp.D, nis, nullptr, applied);
   return EKF_OK;
 }
 
@@ -2141,6 +2093,45 @@ extern "C" int ekf_upload_tag_index(ekf_handle* h, int b, const int* tag_of_inde
   return EKF_OK;
 }
 
+// ---- the two-handle calls (ekf_copy_trajectories, ekf_join_maps) ----
+// Each is pair_begin, its plan function (the sizes of both handles are current), pair_flags, pair_defined for every trajectory
+// it names, pair_flush, then its tables and its launch on the destination's stream.  Every error is the destination's; what fails inside the source is reworded "`fn`: source: ...".
+static int pair_source_fail(ekf_handle* dst, ekf_handle* src, const char* fn, int rc) {
+  return src == dst ? rc : fail(dst, rc, std::string(fn) + ": source: " + src->err);
+}
+static int pair_begin(ekf_handle* dst, ekf_handle* src, const char* fn) {
+  if (!dst || !src) return EKF_ERR_ARG;
+  if (int rc = refresh_sizes(src)) return pair_source_fail(dst, src, fn, rc);
+  return refresh_sizes(dst);
+}
+// trajectory t of `h`, `which` ("source" / "destination") of the call, must be defined (its flags have been read back)
+static int pair_defined(ekf_handle* dst, const char* fn, const ekf_handle* h, const char* which, int t) {
+  if (!h->host_bad[t] && !(h->h_flags.p[t] & EKF_FLAG_INTERNAL)) return EKF_OK;
+  return fail(dst, EKF_ERR_STATE, std::string(fn) + ": " + which + " trajectory " + std::to_string(t) +
+                                      " is undefined (EKF_FLAG_INTERNAL, or an earlier call failed half way): upload it again");
+}
+// Behind the plan: the source's flags, behind everything enqueued on its stream, and the destination's where the call reads
+// its destinations (a join does, a copy overwrites them).  The call's pair_defined checks follow, then pair_flush.
+static int pair_flags(ekf_handle* dst, ekf_handle* src, bool reads_dst) {
+  HIP_TRY(dst, hipSetDevice(dst->device));
+  HIP_TRY(dst, hipMemcpyAsync(src->h_flags.p, src->dflags.p, sizeof(unsigned) * src->batch, hipMemcpyDeviceToHost, src->stream));
+  HIP_TRY(dst, hipStreamSynchronize(src->stream));
+  if (reads_dst && src != dst) {
+    HIP_TRY(dst, hipMemcpyAsync(dst->h_flags.p, dst->dflags.p, sizeof(unsigned) * dst->batch, hipMemcpyDeviceToHost, dst->stream));
+    HIP_TRY(dst, hipStreamSynchronize(dst->stream));
+  }
+  return EKF_OK;
+}
+// what is pending on either handle applied, and the source's streams idle
+static int pair_flush(ekf_handle* dst, ekf_handle* src, const char* fn) {
+  if (int rc = flush_pending(src)) return pair_source_fail(dst, src, fn, rc);
+  if (src != dst)
+    if (int rc = flush_pending(dst)) return rc;
+  HIP_TRY(dst, hipStreamSynchronize(src->stream));
+  if (src->aux) HIP_TRY(dst, hipStreamSynchronize(src->aux));
+  return EKF_OK;
+}
+
 // Copy whole filter states between trajectories, on the device (k_copy_traj, ekf_copy.hip): src_b[i] of `src` -> dst_b[i] of
 // `dst`.  What is pending on either handle is applied first, then stored values only move: the stored upper triangle, the mean
 // (dmu2[cur] of each side), the size word and the sticky flags in ONE launch on the destination's stream, the tag table row and
@@ -2168,27 +2159,15 @@ extern "C" int ekf_upload_tag_index(ekf_handle* h, int b, const int* tag_of_inde
 // A source under EKF_FLAG_INTERNAL or host_bad is refused and a destination in that condition becomes good again -- the
 // conditions check_internal / clear_internal test and clear for ekf_upload_state; here the kernel overwrites the flag word.
 extern "C" int ekf_copy_trajectories(ekf_handle* dst, const int* dst_b, ekf_handle* src, const int* src_b, int k) {
-  if (!dst || !src) return EKF_ERR_ARG;
-  if (int rc = refresh_sizes(src)) return src == dst ? rc : fail(dst, rc, "ekf_copy_trajectories: source: " + src->err);
-  if (int rc = refresh_sizes(dst)) return rc;
+  const char* fn = "ekf_copy_trajectories";
+  if (int rc = pair_begin(dst, src, fn)) return rc;
   CopyPlan cp;
   if (const char* why = plan_copy(dst, dst_b, src, src_b, k, cp)) return fail(dst, EKF_ERR_ARG, why);
   if (k == 0) return EKF_OK;
-  HIP_TRY(dst, hipSetDevice(dst->device));
-  // (the source's flags, behind everything enqueued on its stream)
-  HIP_TRY(dst, hipMemcpyAsync(src->h_flags.p, src->dflags.p, sizeof(unsigned) * src->batch, hipMemcpyDeviceToHost, src->stream));
-  HIP_TRY(dst, hipStreamSynchronize(src->stream));
-  for (int g = 0; g < cp.groups; ++g) {
-    const int s = cp.tab[(size_t)COPY_GROUP_WORDS * g];
-    if (src->host_bad[s] || (src->h_flags.p[s] & EKF_FLAG_INTERNAL))
-      return fail(dst, EKF_ERR_STATE, "ekf_copy_trajectories: source trajectory " + std::to_string(s) +
-                                          " is undefined (EKF_FLAG_INTERNAL, or an earlier call failed half way): upload it again");
-  }
-  if (int rc = flush_pending(src)) return src == dst ? rc : fail(dst, rc, "ekf_copy_trajectories: source: " + src->err);
-  if (src != dst)
-    if (int rc = flush_pending(dst)) return rc;
-  HIP_TRY(dst, hipStreamSynchronize(src->stream));
-  if (src->aux) HIP_TRY(dst, hipStreamSynchronize(src->aux));
+  if (int rc = pair_flags(dst, src, false)) return rc;
+  for (int g = 0; g < cp.groups; ++g)
+    if (int rc = pair_defined(dst, fn, src, "source", cp.tab[(size_t)COPY_GROUP_WORDS * g])) return rc;
+  if (int rc = pair_flush(dst, src, fn)) return rc;
   RES_TRY(dst, "ekf_copy_trajectories's table", dst->dcp_tab.reserve(cp.tab.size(), (size_t)(COPY_GROUP_WORDS + 1) * dst->batch, dst->stream));
   HIP_TRY(dst, hipMemcpyAsync(dst->dcp_tab.p, cp.tab.data(), sizeof(int) * cp.tab.size(), hipMemcpyHostToDevice, dst->stream));
   // (nontemporal stores unless EKFSLAM_HIP_COPY_NT=0: tools/copy_trajectories_time.py measures both, profiles/copy_trajectories.txt)
@@ -2235,34 +2214,17 @@ extern "C" int ekf_copy_trajectories(ekf_handle* dst, const int* dst_b, ekf_hand
 // EKF_FLAG_INTERNAL or host_bad is refused like a source.
 extern "C" int ekf_join_maps(ekf_handle* dst, const int* dst_b, ekf_handle* src, const int* src_b, int k, const double* T,
                              const double* covT, int* first, int* twin, int twin_stride) {
-  if (!dst || !src) return EKF_ERR_ARG;
-  if (int rc = refresh_sizes(src)) return src == dst ? rc : fail(dst, rc, "ekf_join_maps: source: " + src->err);
-  if (int rc = refresh_sizes(dst)) return rc;
+  const char* fn = "ekf_join_maps";
+  if (int rc = pair_begin(dst, src, fn)) return rc;
   JoinPlan jp;
   if (const char* why = plan_join(dst, dst_b, src, src_b, k, T, covT, twin != nullptr, twin_stride, jp)) return fail(dst, EKF_ERR_ARG, why);
   if (k == 0) return EKF_OK;
-  HIP_TRY(dst, hipSetDevice(dst->device));
-  // (the flags of both sides, behind everything enqueued on their streams)
-  HIP_TRY(dst, hipMemcpyAsync(src->h_flags.p, src->dflags.p, sizeof(unsigned) * src->batch, hipMemcpyDeviceToHost, src->stream));
-  HIP_TRY(dst, hipStreamSynchronize(src->stream));
-  if (src != dst) {
-    HIP_TRY(dst, hipMemcpyAsync(dst->h_flags.p, dst->dflags.p, sizeof(unsigned) * dst->batch, hipMemcpyDeviceToHost, dst->stream));
-    HIP_TRY(dst, hipStreamSynchronize(dst->stream));
-  }
+  if (int rc = pair_flags(dst, src, true)) return rc;
   for (int i = 0; i < k; ++i) {
-    const int d = jp.tab[(size_t)JOIN_PAIR_WORDS * i], s = jp.tab[(size_t)JOIN_PAIR_WORDS * i + 1];
-    if (src->host_bad[s] || (src->h_flags.p[s] & EKF_FLAG_INTERNAL))
-      return fail(dst, EKF_ERR_STATE, "ekf_join_maps: source trajectory " + std::to_string(s) +
-                                          " is undefined (EKF_FLAG_INTERNAL, or an earlier call failed half way): upload it again");
-    if (dst->host_bad[d] || (dst->h_flags.p[d] & EKF_FLAG_INTERNAL))
-      return fail(dst, EKF_ERR_STATE, "ekf_join_maps: destination trajectory " + std::to_string(d) +
-                                          " is undefined (EKF_FLAG_INTERNAL, or an earlier call failed half way): upload it again");
+    if (int rc = pair_defined(dst, fn, src, "source", jp.tab[(size_t)JOIN_PAIR_WORDS * i + 1])) return rc;
+    if (int rc = pair_defined(dst, fn, dst, "destination", jp.tab[(size_t)JOIN_PAIR_WORDS * i])) return rc;
   }
-  if (int rc = flush_pending(src)) return src == dst ? rc : fail(dst, rc, "ekf_join_maps: source: " + src->err);
-  if (src != dst)
-    if (int rc = flush_pending(dst)) return rc;
-  HIP_TRY(dst, hipStreamSynchronize(src->stream));
-  if (src->aux) HIP_TRY(dst, hipStreamSynchronize(src->aux));
+  if (int rc = pair_flush(dst, src, fn)) return rc;
   const size_t ss = (size_t)join_snap_doubles(dst->ld, jp.seq);
   RES_TRY(dst, "ekf_join_maps's table", dst->djn_tab.reserve(jp.tab.size(), (size_t)JOIN_PAIR_WORDS * dst->batch, dst->stream));
   RES_TRY(dst, "ekf_join_maps's snapshot", dst->djn_snap.reserve(ss * k, ss * k, dst->stream));

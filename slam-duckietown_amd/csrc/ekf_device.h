@@ -45,19 +45,20 @@ constexpr int JQ_TILE = 32;             // k_joint (ekf_joint.hip): rows / colum
 constexpr int JMAX = EKF_JMAX;          // landmarks per trajectory in one ekf_download_joint
 constexpr int FB = 64;                  // ekf_factor (ekf_factor.hip): rows / columns of a block of the blocked Cholesky
 constexpr int FACTOR_RHS = EKF_FACTOR_RHS;   // right-hand sides of one ekf_factor_solve / ekf_factor_multiply
+// The rank fronts (ekf_rank_front.h): what a launch reads per trajectory of the BANK -- trajectories outside the call's range
+// carry D = 0 -- is a row of ints {D, active bound, ...} and a row of doubles {..., gate, pad}; ekf_host_plan.h packs both
+// (pack_direct / pack_linear) and lays them out in one buffer with the results (FrontTable).
 // ekf_update_direct (k_direct, ekf_direct.hip): a trajectory brings up to MMAX fixes, at most one of them a pose fix of 3 rows:
-// 3 + 2 (MMAX - 1) = 33 rows, 36 as whole k-tiles.  What the launch reads per trajectory of the BANK (trajectories outside the
-// call's range carry D = 0): DIRECT_INTS ints {D, active bound, state index of row k (DIRECT_ROWS), 4 * fix + component of row k
-// (DIRECT_ROWS)} and DIRECT_DBLS doubles {z (MMAX x 3), R (MMAX x 9, row-major 3 x 3 per fix), gate, pad}.
+// 3 + 2 (MMAX - 1) = 33 rows, 36 as whole k-tiles.  DIRECT_INTS ints {D, active bound, state index of row k (DIRECT_ROWS), 4 * fix +
+// component of row k (DIRECT_ROWS)} and DIRECT_DBLS doubles {z (MMAX x 3), R (MMAX x 9, row-major 3 x 3 per fix), gate, pad}.
 constexpr int DIRECT_ROWS = 36;
 constexpr int DIRECT_INTS = 2 + 2 * DIRECT_ROWS;
 constexpr int DIRECT_DBLS = MMAX * 12 + 2;
 static_assert(3 + 2 * (MMAX - 1) <= DIRECT_ROWS && DIRECT_ROWS % 4 == 0 && DIRECT_ROWS <= KTOT, "a direct update's rows fit the pending ranks");
 // ekf_update_linear (k_linear, ekf_linear.hip): a trajectory brings up to LINEAR_ROWS measurement rows over the pose and up to
-// LINEAR_LMAX landmarks.  What the launch reads per trajectory of the BANK (trajectories outside the call's range carry D = 0):
-// LINEAR_INTS ints {D, active bound (already raised over the sub-state), sub-state size ns, 0, state index of sub-state entry j
-// (LINEAR_NS, -1 beyond ns)} and linear_dbls(dp, nsl) doubles packed by the launch's row cap dp and column count nsl = 3 + 2 *
-// lstride: H (dp x nsl, row-major), r (dp), R (dp x dp, row-major, the upper triangle), gate, pad.
+// LINEAR_LMAX landmarks.  LINEAR_INTS ints {D, active bound (already raised over the sub-state), sub-state size ns, 0, state index
+// of sub-state entry j (LINEAR_NS, -1 beyond ns)} and linear_dbls(dp, nsl) doubles packed by the launch's row cap dp and column
+// count nsl = 3 + 2 * lstride: H (dp x nsl, row-major), r (dp), R (dp x dp, row-major, the upper triangle), gate, pad.
 constexpr int LINEAR_LMAX = EKF_LINEAR_LMAX;
 constexpr int LINEAR_ROWS = EKF_LINEAR_ROWS;
 constexpr int LINEAR_NS = 3 + 2 * LINEAR_LMAX;

@@ -715,6 +715,19 @@ inline const char* plan_remove(const HostPlan* h, int b0, int nb, const int* lm,
   return nullptr;
 }
 
+// ---- the rank fronts (ekf_update_direct: k_direct, ekf_update_linear: k_linear; ekf_rank_front.h) ----
+// the instantiation of a front kernel that serves `kpad` rows: the smallest compile-time row count that holds them (`full`:
+// the kernel's own limit, DIRECT_ROWS or LINEAR_ROWS)
+inline int front_rows_cap(int kpad, int full) { return kpad <= 4 ? 4 : kpad <= 8 ? 8 : kpad <= 16 ? 16 : full; }
+// The table a front's launch reads and writes, ONE buffer of doubles for the whole bank of B trajectories: {`ints` ints per
+// trajectory, rounded up to whole doubles | `dbls` doubles per trajectory | the results, NIS and applied per trajectory}.  Column
+// 1 of every trajectory's ints is its active bound.  pack_direct / pack_linear fill the first two parts on the host.
+struct FrontTable {
+  size_t ints, dbls;
+  size_t int_words(size_t B) const { return (B * ints + 1) / 2; }
+  size_t words(size_t B) const { return int_words(B) + B * dbls + 2 * B; }
+};
+
 // ekf_update_direct (k_direct, ekf_direct.hip): the fixes of trajectories [b0, b0 + count) checked -- the range inside the
 // bank, stride in 1..EKF_MMAX, m[bi] in 0..stride, every target a landmark of its trajectory's map or EKF_DIRECT_POSE /
 // EKF_DIRECT_POSITION, no target twice and not both pose kinds in one trajectory, finite z, R and gate, gate > 0, every R block
@@ -779,8 +792,30 @@ inline const char* plan_direct(const HostPlan* h, int b0, int count, const int* 
   }
   return nullptr;
 }
-// the instantiation of k_direct that serves `kpad` rows: the smallest compile-time row count that holds them
-inline int direct_rows_cap(int kpad) { return kpad <= 4 ? 4 : kpad <= 8 ? 8 : kpad <= 16 ? 16 : DIRECT_ROWS; }
+// The host side of k_direct's table (ekf_device.h: DIRECT_INTS, DIRECT_DBLS) for the whole bank, from an accepted plan and the
+// arrays it was made from: every trajectory its active bound and no row, those of the range their rows, fixes and gate.
+inline FrontTable direct_table() { return FrontTable{DIRECT_INTS, DIRECT_DBLS}; }
+inline void pack_direct(const HostPlan* h, const DirectPlan& dp, int b0, int count, const double* z, const double* R, const int* m,
+                        int stride, const double* gate, std::vector<int>& ints, std::vector<double>& dbls) {
+  const size_t B = (size_t)h->batch;
+  ints.assign(B * DIRECT_INTS, 0);
+  dbls.assign(B * DIRECT_DBLS, 0.0);
+  for (size_t b = 0; b < B; ++b) {
+    int* pi = ints.data() + b * DIRECT_INTS;
+    pi[1] = h->opt_active_bound ? std::min(h->neff[b], h->n[b]) : h->n[b];
+    for (int k = 0; k < DIRECT_ROWS; ++k) pi[2 + k] = -1;
+  }
+  for (int bi = 0; bi < count; ++bi) {
+    int* pi = ints.data() + (size_t)(b0 + bi) * DIRECT_INTS;
+    double* pd = dbls.data() + (size_t)(b0 + bi) * DIRECT_DBLS;
+    pi[0] = dp.D[bi];
+    std::copy_n(dp.s.data() + (size_t)bi * DIRECT_ROWS, DIRECT_ROWS, pi + 2);
+    std::copy_n(dp.src.data() + (size_t)bi * DIRECT_ROWS, DIRECT_ROWS, pi + 2 + DIRECT_ROWS);
+    std::copy_n(z + (size_t)bi * stride * 3, (size_t)m[bi] * 3, pd);
+    std::copy_n(R + (size_t)bi * stride * 9, (size_t)m[bi] * 9, pd + 3 * MMAX);
+    pd[DIRECT_DBLS - 2] = gate ? gate[bi] : INFINITY;
+  }
+}
 
 // ekf_update_linear (k_linear, ekf_linear.hip): the measurements of trajectories [b0, b0 + count) checked -- the range inside
 // the bank, lstride in 1..EKF_LINEAR_LMAX, dstride in 1..EKF_LINEAR_ROWS, k[bi] in 0..lstride, d[bi] in 0..dstride, every
@@ -853,8 +888,42 @@ inline const char* plan_linear(const HostPlan* h, int b0, int count, const int* 
   }
   return nullptr;
 }
-// the instantiation of k_linear that serves `kpad` rows: the smallest compile-time row count that holds them
-inline int linear_rows_cap(int kpad) { return kpad <= 4 ? 4 : kpad <= 8 ? 8 : kpad <= 16 ? 16 : LINEAR_ROWS; }
+// The host side of k_linear's table (ekf_device.h: LINEAR_INTS, linear_dbls) for the whole bank, packed by the launch's row cap
+// `dp` and H's column count nsl = 3 + 2 * lstride, from an accepted plan and the arrays it was made from.  First the active
+// bound (h->neff) of every trajectory that brings rows is raised over the highest landmark of its sub-state, as a landmark
+// update of it would (fill_step): a general row correlates its targets.  Then every trajectory gets its bound, the pose as
+// sub-state and no row, those of the range their sub-state, rows (H's leading ns columns, r, R's upper triangle) and gate.
+inline FrontTable linear_table(int dp, int nsl) { return FrontTable{LINEAR_INTS, (size_t)linear_dbls(dp, nsl)}; }
+inline void pack_linear(HostPlan* h, const LinearPlan& lp, int b0, int count, int lstride, const double* H, const double* r,
+                        const double* R, int dstride, const double* gate, std::vector<int>& ints, std::vector<double>& dbls) {
+  const size_t B = (size_t)h->batch;
+  const int dp = front_rows_cap(lp.kpad, LINEAR_ROWS), nsl = 3 + 2 * lstride;
+  const size_t per = (size_t)linear_dbls(dp, nsl);
+  for (int bi = 0; bi < count; ++bi)
+    if (lp.D[bi] > 0) h->neff[b0 + bi] = std::min(h->n[b0 + bi], std::max(h->neff[b0 + bi], 3 + 2 * (lp.lmax[bi] + 1)));
+  ints.assign(B * LINEAR_INTS, 0);
+  dbls.assign(B * per, 0.0);
+  for (size_t b = 0; b < B; ++b) {
+    int* pi = ints.data() + b * LINEAR_INTS;
+    pi[1] = h->opt_active_bound ? std::min(h->neff[b], h->n[b]) : h->n[b];
+    pi[2] = 3;
+    for (int j = 0; j <= LINEAR_NS; ++j) pi[4 + j] = j < 3 ? j : -1;
+  }
+  for (int bi = 0; bi < count; ++bi) {
+    int* pi = ints.data() + (size_t)(b0 + bi) * LINEAR_INTS;
+    double* pd = dbls.data() + (size_t)(b0 + bi) * per;
+    const int D = lp.D[bi], ns = lp.ns[bi];
+    pi[0] = D;
+    pi[2] = ns;
+    std::copy_n(lp.s.data() + (size_t)bi * LINEAR_NS, LINEAR_NS, pi + 4);
+    for (int a = 0; a < D; ++a) {
+      std::copy_n(H + ((size_t)bi * dstride + a) * nsl, ns, pd + (size_t)a * nsl);
+      pd[(size_t)dp * nsl + a] = r[(size_t)bi * dstride + a];
+      for (int q = a; q < D; ++q) pd[(size_t)dp * nsl + dp + (size_t)a * dp + q] = R[((size_t)bi * dstride + a) * dstride + q];
+    }
+    pd[(size_t)dp * nsl + dp + (size_t)dp * dp] = gate ? gate[bi] : INFINITY;
+  }
+}
 
 // ekf_predict_linear (k_predict_pose, ekf_predict_linear.hip): the inputs of trajectories [b0, b0 + count) checked -- the range
 // inside the bank, pose, F and Q given, and for every APPLIED trajectory (apply == NULL: all) finite pose, F and Q (of Q what is

@@ -109,9 +109,10 @@ void launch_factor_multiply(hipStream_t st, const FactorView& w, int f0, int cou
 // rp.rows: the launch's largest new size (grid rows); nb trajectories from b0; src / dst: rp's tables on the device
 void launch_remove(hipStream_t st, const BankView& k, double* mu, const RemovePlan& rp, const int* src, const int* dst,
                    unsigned* rflag, int b0, int nb, unsigned seq);
+// the rank fronts: rows_cap = front_rows_cap(kpad, DIRECT_ROWS / LINEAR_ROWS); plan, meas, out: the parts of the launch's FrontTable
 void launch_direct(hipStream_t st, int rows_cap, const BankView& k, double* dacc, double* mu, const int* plan, const double* meas,
                    double* out, int kpad);
-// rows_cap: linear_rows_cap(kpad); nsl = 3 + 2 * lstride, the columns of the call's H; meas: linear_dbls(rows_cap, nsl) per trajectory
+// nsl = 3 + 2 * lstride, the columns of the call's H; meas: linear_dbls(rows_cap, nsl) per trajectory
 void launch_linear(hipStream_t st, int rows_cap, const BankView& k, double* dacc, double* mu, const int* plan, const double* meas,
                    double* out, int kpad, int nsl, int innovation);
 // trajectories [f.b0, f.b0 + f.count), one record each in `in`; P and mu: f.P and f.mu, written (rows 0..2 and the pose mean);

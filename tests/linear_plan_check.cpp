@@ -1,11 +1,12 @@
-// Sanitizer build of plan_linear (slam-duckietown_amd/csrc/ekf_host_plan.h), the host-side validation and plan of
-// ekf_update_linear:
+// Sanitizer build of plan_linear and pack_linear (slam-duckietown_amd/csrc/ekf_host_plan.h), the host-side validation, plan
+// and launch table of ekf_update_linear:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DEKF_HOST_ONLY
 //       -I slam-duckietown_amd/csrc -I include tests/linear_plan_check.cpp -o linear_plan_check
 // Every refusal the header lists, a legal zero row, d = 0, the state indices and kpad of permuted selections, and randomised
 // calls at the limits (lstride = EKF_LINEAR_LMAX, dstride = EKF_LINEAR_ROWS) whose arrays are allocated to exactly the size
-// the header states, so that a read beyond them is a sanitizer report; any report or failed check ends the run with a
-// non-zero status.  tests/test_linear_cpu.py builds and runs it (CPU only).
+// the header states, so that a read beyond them is a sanitizer report; behind every accepted plan the table pack_linear makes
+// of it, into vectors it sizes itself, against a second, naive indexing of the layout; any report or failed check ends the run
+// with a non-zero status.  tests/test_linear_cpu.py builds and runs it (CPU only).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -49,10 +50,76 @@ struct Call {
   }
 };
 
+// The table of an accepted call, packed on a copy of the bank (pack_linear raises bounds): sizes as the launch's buffer is
+// laid out ({ints | doubles | 2 B results}); every trajectory outside the range its own bound, the pose as sub-state and no
+// row; those inside their plan's sub-state -- state indices inside the state, and below the bound where rows are brought -- with
+// D within the launch's row cap; H, r, R's upper triangle and the gate where a naive indexing of linear_dbls(cap, nsl) puts them.
+static void check_pack(HostPlan h, const Call& c, const LinearPlan& lp) {
+  const double inf = std::numeric_limits<double>::infinity();
+  const std::vector<int> neff0 = h.neff;
+  std::vector<int> ints;
+  std::vector<double> dbls;
+  pack_linear(&h, lp, c.b0, c.count, c.lstride, c.H.data(), c.r.data(), c.R.data(), c.dstride, c.gate.empty() ? nullptr : c.gate.data(),
+              ints, dbls);
+  const size_t B = (size_t)h.batch;
+  const int cap = lp.kpad <= 4 ? 4 : lp.kpad <= 8 ? 8 : lp.kpad <= 16 ? 16 : 32, nsl = 3 + 2 * c.lstride;
+  CHECK(front_rows_cap(lp.kpad, LINEAR_ROWS) == cap && cap >= lp.kpad, "cap %d for kpad %d", cap, lp.kpad);
+  const size_t at_r = (size_t)cap * nsl, at_R = at_r + cap, at_gate = at_R + (size_t)cap * cap, per = at_gate + 2;
+  CHECK((size_t)linear_dbls(cap, nsl) == per && ints.size() == B * 40 && dbls.size() == B * per, "sizes %zu %zu", ints.size(), dbls.size());
+  const FrontTable tab = linear_table(cap, nsl);
+  CHECK(tab.ints == 40 && tab.dbls == per && tab.int_words(B) == B * 20 && tab.words(B) == B * 20 + B * per + 2 * B, "table of %zu words", tab.words(B));
+  for (int b = 0; b < h.batch; ++b) {
+    const int* pi = ints.data() + (size_t)b * 40;
+    const double* pd = dbls.data() + (size_t)b * per;
+    const int bi = b - c.b0;
+    const bool inside = bi >= 0 && bi < c.count;
+    const int D = inside ? lp.D[bi] : 0, ns = inside ? lp.ns[bi] : 3;
+    int want = neff0[b];
+    if (D > 0) want = std::min(h.n[b], std::max(neff0[b], 3 + 2 * (lp.lmax[bi] + 1)));
+    CHECK(h.neff[b] == want && h.neff[b] >= neff0[b] && h.neff[b] <= std::max(neff0[b], h.n[b]), "raised bound of %d: %d", b, h.neff[b]);
+    CHECK(pi[1] == (h.opt_active_bound ? std::min(want, h.n[b]) : h.n[b]), "bound of %d: %d", b, pi[1]);
+    CHECK(pi[0] == D && D <= cap && pi[2] == ns && pi[3] == 0 && pi[4 + 35] == -1, "head of %d: %d %d %d", b, pi[0], pi[2], pi[3]);
+    for (int j = 0; j < 35; ++j) {
+      const int s = pi[4 + j];
+      if (j >= ns) { CHECK(s == -1, "pad entry %d of %d: %d", j, b, s); continue; }
+      CHECK(s >= 0 && s < h.n[b] && (D == 0 || s < pi[1]), "entry %d of %d -> %d (bound %d)", j, b, s, pi[1]);
+      CHECK(s == (j < 3 ? j : 3 + 2 * c.lm[(size_t)bi * c.lstride + (j - 3) / 2] + ((j - 3) & 1)), "entry %d of %d -> %d", j, b, s);
+    }
+    std::vector<double> naive(per, 0.0);
+    for (int a = 0; a < D; ++a) {
+      for (int j = 0; j < ns; ++j) naive[(size_t)a * nsl + j] = c.H[((size_t)bi * c.dstride + a) * nsl + j];
+      naive[at_r + a] = c.r[(size_t)bi * c.dstride + a];
+      for (int q = a; q < D; ++q) naive[at_R + (size_t)a * cap + q] = c.R[((size_t)bi * c.dstride + a) * c.dstride + q];
+    }
+    if (inside) naive[at_gate] = c.gate.empty() ? inf : c.gate[bi];
+    for (size_t e = 0; e < per; ++e) CHECK(pd[e] == naive[e], "double %zu of %d: %g for %g", e, b, pd[e], naive[e]);
+  }
+}
+
+// a call of one trajectory with D rows over the landmarks first + k - 1, ..., first (no order), every entry its own value
+static Call rows_call(int D, int k, int lstride, int dstride, int b0, int first) {
+  Call c;
+  const int nsl = 3 + 2 * lstride;
+  c.b0 = b0, c.count = 1, c.lstride = lstride, c.dstride = dstride;
+  c.k = {k}, c.d = {D};
+  c.lm.assign(lstride, -9);
+  for (int p = 0; p < k; ++p) c.lm[p] = first + k - 1 - p;
+  c.H.assign((size_t)dstride * nsl, 0.0);
+  c.r.assign(dstride, 0.0);
+  c.R.assign((size_t)dstride * dstride, 0.0);
+  for (int a = 0; a < dstride; ++a) {
+    for (int j = 0; j < nsl; ++j) c.H[(size_t)a * nsl + j] = 1000.0 * a + j + 0.25;
+    c.r[a] = a + 0.5;
+    for (int q = 0; q < dstride; ++q) c.R[(size_t)a * dstride + q] = q == a ? 0.01 * (a + 1) : q > a ? 1e-4 + 1e-6 * (a + q) : 1e300;
+  }
+  return c;
+}
+
 int main() {
   HostPlan h;
   h.batch = 3;
   h.n = {3 + 2 * 40, 3 + 2 * 10, 3 + 2 * 20};
+  h.neff = {3 + 2 * 30, 3 + 2 * 10, 3};
   const double inf = std::numeric_limits<double>::infinity(), nan = std::nan("");
   LinearPlan lp;
   {
@@ -67,14 +134,19 @@ int main() {
     for (int j = 5; j < LINEAR_NS; ++j) CHECK(lp.s[LINEAR_NS + j] == -1, "pad %d", j);
     c.lm = {7, 5, 2, 1, -9, -9};                           // a permuted selection: the same entries, permuted
     CHECK(c.plan(h, lp) == nullptr && lp.s[3] == 17 && lp.s[5] == 13 && lp.s[7] == 7 && lp.lmax[0] == 7, "permuted");
+    check_pack(h, c, lp);
     c.gate = {inf, 11.3};
     CHECK(c.plan(h, lp) == nullptr, "gates");
+    check_pack(h, c, lp);
     c.d = {0, 0};
     CHECK(c.plan(h, lp) == nullptr && lp.kpad == 0 && lp.D[0] == 0, "nothing to do");
+    check_pack(h, c, lp);
     c.d = {0, 4};
     CHECK(c.plan(h, lp) == nullptr && lp.kpad == 4 && lp.D[0] == 0 && lp.D[1] == 4, "d = 0 beside d = 4");
+    check_pack(h, c, lp);
     c.k = {0, 0};
     CHECK(c.plan(h, lp) == nullptr && lp.ns[1] == 3 && lp.lmax[1] == -1 && lp.s[LINEAR_NS + 3] == -1, "the pose alone");
+    check_pack(h, c, lp);
   }
   {
     Call c;                                                // a zero row of H is legal: S keeps R's row
@@ -87,6 +159,32 @@ int main() {
     c.R[3 * 4 + 3] = nan;
     c.R[0 * 4 + 3] = nan;                                  // trajectory 0, column 3 >= d
     CHECK(c.plan(h, lp) == nullptr, "ignored entries");
+    check_pack(h, c, lp);
+  }
+  // D at 0, 1 and each edge of a row cap (4 | 5, 8 | 9, 16 | 17, the full 32), k = 0 and k = EKF_LINEAR_LMAX, strides at and far
+  // above the counts: a bank of one, and the last trajectory of three (whose bound starts at the pose: it is raised) with the
+  // active bound on and off
+  {
+    HostPlan one;
+    one.batch = 1;
+    one.n = {3 + 2 * 40};
+    one.neff = {3 + 2 * 25};
+    for (int D : {0, 1, 4, 5, 8, 9, 16, 17, 32})
+      for (int k : {0, EKF_LINEAR_LMAX})
+        for (int wide : {0, 1}) {
+          const int lstride = wide ? EKF_LINEAR_LMAX : std::max(1, k), dstride = wide ? EKF_LINEAR_ROWS : std::max(1, D);
+          Call c = rows_call(D, k, lstride, dstride, 0, 20);
+          CHECK(c.plan(one, lp) == nullptr && lp.D[0] == D && lp.ns[0] == 3 + 2 * k && lp.kpad == ((D + 3) & ~3), "D = %d k = %d", D, k);
+          check_pack(one, c, lp);
+          c = rows_call(D, k, lstride, dstride, 2, 4);
+          c.gate = {7.5};
+          for (int bound : {1, 0}) {
+            h.opt_active_bound = bound;
+            CHECK(c.plan(h, lp) == nullptr && lp.D[0] == D, "D = %d k = %d in the bank of three", D, k);
+            check_pack(h, c, lp);
+          }
+          h.opt_active_bound = 1;
+        }
   }
   auto refused = [&](const Call& c, const char* what) {
     const char* why = c.plan(h, lp);
@@ -162,8 +260,9 @@ int main() {
         }
     }
     CHECK(c.plan(h, lp) == nullptr, "random call %d", it);
-    CHECK(lp.kpad == ((d_hi + 3) & ~3) && lp.kpad <= LINEAR_ROWS && linear_rows_cap(lp.kpad) >= lp.kpad && linear_rows_cap(lp.kpad) <= LINEAR_ROWS,
-          "kpad %d for %d", lp.kpad, d_hi);
+    CHECK(lp.kpad == ((d_hi + 3) & ~3) && lp.kpad <= LINEAR_ROWS && front_rows_cap(lp.kpad, LINEAR_ROWS) >= lp.kpad &&
+              front_rows_cap(lp.kpad, LINEAR_ROWS) <= LINEAR_ROWS, "kpad %d for %d", lp.kpad, d_hi);
+    check_pack(h, c, lp);
     for (int bi = 0; bi < c.count; ++bi) {
       std::vector<unsigned char> seen(h.n[c.b0 + bi], 0);
       CHECK(lp.ns[bi] == 3 + 2 * c.k[bi] && lp.D[bi] == c.d[bi], "sizes");

@@ -191,7 +191,7 @@ struct Handle {
   DBuf<double> dprow3[2], dxg, dbg, dgmu;
   DBuf<unsigned> dsync;
   DBuf<long> dpre[2];
-  DBuf<double> dgbuf, dgate, ddirect, dcolbuf;
+  DBuf<double> dgbuf, dgate, dfront, dcolbuf;
   DBuf<double> lone, with_b, with_c;                   // a group whose first member exists before the group is asked for
   // stream-ordered uploads
   Staged<int> shares2[2];
@@ -364,7 +364,7 @@ static std::vector<Step> script() {
     single("single buffers", [](Handle& h) {
       if (Status st = h.dgbuf.ensure(84 * 88 * BATCH); !st.ok()) return st;
       if (Status st = h.dgate.ensure(BATCH); !st.ok()) return st;
-      if (Status st = h.ddirect.ensure(100 * BATCH); !st.ok()) return st;
+      if (Status st = h.dfront.reserve(100 * BATCH, 0, STREAM); !st.ok()) return st;
       return h.dcolbuf.ensure(83 * 64 * BATCH);
     });
   }

@@ -713,3 +713,33 @@ def test_set_option_ranges_and_removed_names(sd):
                      "beside_min_mb"):
             with pytest.raises(sd.EkfError, match="unknown option " + name):
                 f.set_option(name, 0)
+
+
+def test_update_tables_grow_with_the_calls_on_one_handle(sd):
+    """ekf_update_linear's table is sized by the call (its row cap and H's columns) and shares its buffer with
+    ekf_update_direct's: a handle whose FIRST call is the smallest (one row over the pose) must serve the largest ones
+    (32 rows over 16 landmarks, then 33 direct rows) afterwards.  The twin sees the largest shape first -- a call under a
+    gate nothing passes: rejected, so nothing of it moves -- and then the same three calls: same bits."""
+    from tests import update_cases as uc
+    small, large = uc.linear_case("n40", 0, 1, 0, "z"), uc.linear_case("n40", 0, 32, 16, "z")
+    fix = uc.direct_case("n40", 0, 33)
+
+    def bank():
+        s = uc.stream("n40", 0)
+        f = sd.EkfSlam(len(s[0]), batch=1)
+        f.set_state_diag(s[0], s[1])
+        f.stream_upload(*[np.stack([s[i]], 1) for i in range(2, 7)])
+        f.stream_run(0, uc.steps_of("n40"))
+        return f
+
+    def calls(f):
+        res = [f.update_linear(lms, H, R, z=z, b=0) for lms, H, R, z in (small, large)] + [f.update_direct(*fix)]
+        return res, f.state()
+
+    with bank() as f, bank() as twin:
+        lms, H, R, z = large
+        assert not twin.update_linear(lms, H, R, z=z, gate=1e-300, b=0).applied[0]
+        (got, state), (want, twin_state) = calls(f), calls(twin)
+    assert [r.dof[0] for r in got] == [1, 32, 33] and all(r.applied[0] for r in got)
+    assert [r.nis[0] for r in got] == [r.nis[0] for r in want]
+    assert np.array_equal(state[0], twin_state[0]) and np.array_equal(state[1], twin_state[1])

@@ -120,7 +120,7 @@ def judge(sd, f, b, before, kind, payload, res, name, innovation=False, gate=np.
 def instantiation(sd, f, kind, d_max):
     """The row cap the call's kernel must have been instantiated for, INFERRED from what the API exposes: the pass behind the
     call applied kpad / 4 k-tiles (ekf_last_pass), kpad the bank's largest D padded to 4, and profile class 4 / 5 counts one
-    launch.  The cap itself is update_cases.rows_cap of that kpad -- this suite's copy of linear_rows_cap / direct_rows_cap
+    launch.  The cap itself is update_cases.rows_cap of that kpad -- this suite's copy of front_rows_cap
     (csrc/ekf_host_plan.h), the one argument ekf_api.hip hands the launcher; the template that ran is not observed, and a
     cap larger than kpad needs computes the same and would pass unseen."""
     _, tiles = last_pass(sd, f)

@@ -175,8 +175,8 @@ LINEAR_ROWS = [(1, 0, "z"), (3, 1, "innovation"), (4, 0, "z"), (5, 2, "innovatio
 
 
 def rows_cap(D, direct):
-    """The instantiation a bank whose largest D this is runs in (csrc/ekf_host_plan.h: linear_rows_cap / direct_rows_cap of
-    kpad = D padded to 4)."""
+    """The instantiation a bank whose largest D this is runs in (csrc/ekf_host_plan.h: front_rows_cap of kpad = D padded
+    to 4)."""
     kpad = (D + 3) & ~3
     return 4 if kpad <= 4 else 8 if kpad <= 8 else 16 if kpad <= 16 else (36 if direct else 32)
 
