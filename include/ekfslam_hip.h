@@ -431,6 +431,36 @@ int ekf_join_maps(ekf_handle *dst, const int *dst_b, ekf_handle *src, const int 
                   const double *T /* k x 3 or NULL */, const double *covT /* k x 9 or NULL */,
                   int *first /* k, may be NULL */, int *twin /* k x twin_stride, may be NULL */, int twin_stride);
 
+/* Change of frame on the device: move trajectories [b0, b0+count) of a running filter into another frame, in place, in one launch
+ * (k_transform) -- the world frame became known after the filter had started at the origin (a surveyed tag map, a Vicon
+ * alignment): align first, then anchor (ekf_update_direct), whatever the offset.  T[3*bi..] = (x, y, phi) is the OLD frame
+ * expressed in the NEW one, ekf_join_maps' explicit-mode convention; cov[9*bi..] its covariance (3 x 3 row-major, the upper
+ * triangle is read), or cov == NULL: the frame is known exactly.  With R = rot(phi), J2 = [[0, -1], [1, 0]], Jacobians at the
+ * current means, for every item of the filter's own state:
+ *   landmark  l' = t + R l                      A_l = [I2 | J2 R l]                  B_l = R
+ *   pose      p' = (t + R p_xy, theta + phi)    A_p = [[I2, J2 R p_xy], [0 0 1]]     B_p = diag(R, 1)   (theta is not re-wrapped)
+ *   P'[c1, c2] = B_c1 P[c1, c2] B_c2^T + A_c1 Sigma A_c2^T        (the second term only where cov is given)
+ * -- exact for a Gaussian state: no rank, no covariance pass, one read and one write of the stored upper triangle (of a diagonal
+ * block: three entries; a download afterwards is exactly symmetric).  What is pending is applied first (a pass the caller pays
+ * for); afterwards nothing is pending.  Blocking, and stream-ordered behind everything enqueued.  count = 0 does nothing.
+ * T = (0, 0, 0) with cov == NULL leaves a trajectory bit for bit.  cov == NULL otherwise: the active bound stays, and what is an
+ * exact zero because of it stays +0.0.  cov given: every item becomes correlated with every other, the active bound becomes the
+ * size (as after ekf_join_maps).  Unchanged: sizes, the tag table, noise rows, gate counters, sticky flags, innovation-log and
+ * pose-log rows (the call writes no log row, like ekf_remove_landmarks and ekf_join_maps); the uploaded stream stays runnable
+ * (ranges, bearings and increments are frame-free); trajectories outside the range stay bit for bit.  The world positions of the
+ * last window's tags (ekf_download_tags: xw, yw) are mapped through T, err stays.  A factor held by ekf_factor is a snapshot of
+ * the state it was taken from, as after any other change of state.  A handle on the small-state path stays on it.  Every entry is
+ * a fixed sequence of at most 13 products: the same trajectory gives the same bits alone or in a bank.  With
+ * ekf_set_option("profile_kernels", 1) the launch is class 8 of ekf_profile_read_class.
+ * EKF_ERR_ARG (nothing changed, the handle usable): count < 0, a range outside the bank, T == NULL with count > 0, a non-finite T,
+ * a non-finite cov, a negative diagonal entry of cov, c_ij^2 > c_ii c_jj, or a negative determinant of its symmetrised upper
+ * triangle (beyond the rounding of the determinant itself).  EKF_ERR_STATE: a trajectory of the range carries EKF_FLAG_INTERNAL or
+ * an earlier call on the handle failed half way.
+ * Measured on one MI355X (tools/transform_time.py, profiles/transform.txt), call + sync / kernel alone, with or without cov:
+ * 32 x N = 2000 1.25 / 1.22 ms (0.70 of ekf_copy_trajectories' rate for the same bytes), 1 x N = 2000 75 / 39 us, 1 x N = 8000
+ * 0.69 / 0.65 ms, 256 x N = 20 (small-state path) 70 / 10 us. */
+int ekf_transform(ekf_handle *h, int b0, int count, const double *T /* count x 3 */, const double *cov /* count x 9 or NULL */);
+
 /* Pinned (page-locked, device-visible) host memory for the arrays a binding hands to its caller.  The reference's loop
  * gets a fresh n x n covariance back from every call (src/replay_no_ros.py:229-237, :482): in freshly allocated pageable
  * memory a 128 MB download first faults in and pins 32 768 pages (5 ms on top of 2.3 ms of PCIe time at N = 2000); the
@@ -562,7 +592,7 @@ int ekf_profile_read(ekf_handle *h, double *pass_ms_total, long long *pass_launc
 long long ekf_profile_passes(ekf_handle *h);
 /* With ekf_set_option("profile_kernels", 1) (a diagnostic run: every record costs its stream ~6 us) the other launches of a
  * fused cadence carry event pairs too: cls 1 the solve launch, 2 the chain (or look-ahead gather) launch, 3 the panel launch,
- * 0 the pass; 4 the k_direct launch of ekf_update_direct; 5 the k_linear launch of ekf_update_linear; 6 the k_join launch of ekf_join_maps (with its snapshot launch); 7 the k_predict_pose launch of ekf_predict_linear.  Does not reset: read before ekf_profile_read. */
+ * 0 the pass; 4 the k_direct launch of ekf_update_direct; 5 the k_linear launch of ekf_update_linear; 6 the k_join launch of ekf_join_maps (with its snapshot launch); 7 the k_predict_pose launch of ekf_predict_linear; 8 the k_transform launch of ekf_transform.  Does not reset: read before ekf_profile_read. */
 int ekf_profile_read_class(ekf_handle *h, int cls, double *ms_total, long long *launches);
 /* Options: name (default, allowed values) meaning.  Unknown names and values out of range fail with EKF_ERR_ARG.
  *   "flush_every"         (0, 0..64)    steps per covariance pass; 0 = auto, by "rank_limit"

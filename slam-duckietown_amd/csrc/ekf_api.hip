@@ -239,6 +239,10 @@ struct ekf_handle : ekf::HostPlan {
   // of every destination's pose, its 3 x 3 block and its three pose rows as they stood before the join (join_snap_doubles per pair)
   DeviceBuf<int> djn_tab;
   DeviceBuf<double> djn_snap;
+  // ekf_transform (allocated on first use): the launch's table (plan_transform) and its frames -- the plan's heads, then the means
+  // of the call's range as they stood before the call (transform_frame_doubles per trajectory)
+  DeviceBuf<int> dtf_tab;
+  DeviceBuf<double> dtf_frame;
   // ekf_update_direct / ekf_update_linear (allocated on first use, grown to the larger need: the two calls never overlap, each
   // ends in a synchronise): the table of the front's launch for the bank (ekf_host_plan.h: FrontTable -- the plan's ints, the
   // measurements, the results NIS and applied), its host sides, and each call's plan
@@ -2280,6 +2284,71 @@ extern "C" int ekf_join_maps(ekf_handle* dst, const int* dst_b, ekf_handle* src,
   return EKF_OK;
 }
 
+// Move trajectories [b0, b0 + count) into another frame, in place (k_transform, ekf_transform.hip; the header has the operation).
+// As ekf_remove_landmarks and ekf_join_maps: what is pending is applied first, the old means go behind the heads of the frame
+// heads by one copy on the handle's stream, then ONE launch rewrites the stored triangle and the means.  The host's
+// mirrors follow here: with a covariance the active bound becomes the size (every item is correlated with every other), as a
+// join raises it -- neff, neff_enq, the floor; without one it stays.  The last window's world positions (AssocOut xw, yw) are
+// mapped on the host, as ekf_remove_landmarks renumbers them.  Sizes, the tag table, noise rows, gate counters, sticky flags and
+// log rows do not change, and the uploaded stream stays runnable (ranges, bearings and increments are frame-free).
+extern "C" int ekf_transform(ekf_handle* h, int b0, int count, const double* T, const double* cov) {
+  const char* fn = "ekf_transform";
+  if (int rc = check_b(h, 0, fn)) return rc;
+  TransformPlan tp;
+  if (const char* why = plan_transform(h, b0, count, T, cov, tp)) return bad_arg(h, fn, why);
+  if (count == 0) return EKF_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (int rc = check_internal(h, b0, fn)) return rc;    // (the flags of the whole bank are back)
+  for (int t = b0 + 1; t < b0 + count; ++t)
+    if (h->host_bad[t] || (h->h_flags.p[t] & EKF_FLAG_INTERNAL)) return check_internal(h, t, fn);
+  if (int rc = join_aux(h)) return rc;
+  if (int rc = flush_pending(h)) return rc;
+  if (tp.applied == 0) {                               // T = 0 without a covariance: every trajectory stays bit for bit
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return EKF_OK;
+  }
+  const size_t fs = (size_t)transform_frame_doubles(h->ld);
+  RES_TRY(h, "ekf_transform's table", h->dtf_tab.reserve(tp.tab.size(), (size_t)TF_WORDS * h->batch, h->stream));
+  RES_TRY(h, "ekf_transform's frames", h->dtf_frame.reserve(fs * count, fs * count, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->dtf_tab.p, tp.tab.data(), sizeof(int) * tp.tab.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->dtf_frame.p, tp.head.data(), sizeof(double) * tp.head.size(), hipMemcpyHostToDevice, h->stream));
+  double* mu = h->dmu2[h->cur].p;
+  HIP_TRY(h, hipMemcpyAsync(h->dtf_frame.p + (size_t)TF_HEAD * count, mu + (size_t)b0 * h->ld, sizeof(double) * (size_t)h->ld * count,
+                            hipMemcpyDeviceToDevice, h->stream));
+  // (nontemporal stores unless EKFSLAM_HIP_TRANSFORM_NT=0: tools/transform_time.py measures both, profiles/transform.txt)
+  bool nt = true;
+  if (const char* e = std::getenv("EKFSLAM_HIP_TRANSFORM_NT")) nt = std::atoi(e) != 0;
+  ProfBracket pb;
+  if (int rc = prof_open(h, 8, h->stream, &pb)) return rc;
+  launch_transform(h->stream, nt, bank_view(h), mu, h->dtf_tab.p, h->dtf_frame.p, count, tp.tiles_hi);
+  if (int rc = prof_close(h, &pb)) return rc;
+  HIP_TRY(h, hipGetLastError());
+  if (tp.with_cov) {
+    for (int t = b0; t < b0 + count; ++t) h->neff[t] = h->neff_enq[t] = h->n[t];
+    if (int rc = push_floor(h, true)) return rc;
+  }
+  // the last window's tags_positions record: world positions through T
+  if (h->d_assoc_out.p) {
+    std::vector<AssocOut> ao((size_t)count);
+    HIP_TRY(h, hipMemcpyAsync(ao.data(), h->d_assoc_out.p + b0, sizeof(AssocOut) * count, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int bi = 0; bi < count; ++bi) {
+      if (!tp.tab[(size_t)TF_WORDS * bi + 3]) continue;
+      const double* t = T + 3 * (size_t)bi;
+      const double c = std::cos(t[2]), s = std::sin(t[2]);
+      AssocOut& a = ao[(size_t)bi];
+      for (int i = 0; i < std::min(a.m, AMAX); ++i) {
+        const double x = a.xw[i], y = a.yw[i];
+        a.xw[i] = t[0] + (c * x - s * y);
+        a.yw[i] = t[1] + (s * x + c * y);
+      }
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->d_assoc_out.p + b0, ao.data(), sizeof(AssocOut) * count, hipMemcpyHostToDevice, h->stream));
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return EKF_OK;
+}
+
 extern "C" int ekf_predict(ekf_handle* h, const double* lin, const double* ang) {
   return do_step(h, FLAG_PREDICT, lin, ang, nullptr, nullptr, nullptr, nullptr, 0);
 }
@@ -2678,7 +2747,7 @@ extern "C" int ekf_profile_read(ekf_handle* h, double* pass_ms_total, long long*
 
 // ("profile_kernels" = 1) the same for the cadence's other launches: cls 1 the solve launch, 2 the chain / look-ahead gather
 // launch, 3 the panel launch (0: the covariance pass), 4 k_direct, 5 k_linear, 6 k_join (with its snapshot launch), 7
-// k_predict_pose; does not reset -- read these BEFORE ekf_profile_read
+// k_predict_pose, 8 k_transform; does not reset -- read these BEFORE ekf_profile_read
 extern "C" int ekf_profile_read_class(ekf_handle* h, int cls, double* ms_total, long long* launches) {
   if (!h || !ms_total || !launches) return EKF_ERR_ARG;
   HIP_TRY(h, hipSetDevice(h->device));

@@ -1147,6 +1147,102 @@ inline const char* plan_join(const HostPlan* dst, const int* dst_b, const HostPl
   return nullptr;
 }
 
+// ekf_transform (k_transform, ekf_transform.hip): move trajectories [b0, b0 + count) into another frame, in place.  The state is
+// walked in k_join's items (item 0 the pose, item q landmark q - 1; M = 1 + N of them) and tiles of JOIN_ITEMS x JOIN_ITEMS
+// items of the stored upper triangle.  Ma <= M items lie inside the active bound: an off-diagonal block whose column item is
+// beyond it is an exact zero and stays one (R 0 R^T), so it is not visited; the diagonal blocks beyond the bound (the variances
+// of never-observed landmarks) are.  With a frame covariance every item becomes correlated with every other: Ma = M.
+// transform_tiles counts a trajectory's tiles: the triangle of the ta = ceil(Ma / JOIN_ITEMS) active tile columns, then the
+// diagonal tiles of the tile columns behind them; transform_tile names tile t (row block ib <= column block jb);
+// transform_writes says whether item pair (I, J), I <= J, is written -- by the one tile that holds it.  The pose block (0, 0)
+// belongs to the launch's extra workgroup, with the means.  Plain integer functions, the ones the kernel calls;
+// tests/transform_plan_check.cpp enumerates them.
+constexpr int TF_WORDS = 4;              // per trajectory {trajectory, N, Ma, applied (0: T = 0 without a covariance -- nothing is touched)}
+constexpr int TF_HEAD = 16;              // doubles of a trajectory's frame head: T (3), has-covariance, Sigma (3 x 3 row-major), pad
+__host__ __device__ inline int transform_tile_cols(int items) { return (items + JOIN_ITEMS - 1) / JOIN_ITEMS; }
+__host__ __device__ inline int transform_tiles(int M, int Ma) {
+  const int ta = transform_tile_cols(Ma);
+  return join_tri(ta) + (transform_tile_cols(M) - ta);
+}
+__host__ __device__ inline void transform_tile(int Ma, int t, int* ib, int* jb) {
+  const int ta = transform_tile_cols(Ma), nt = join_tri(ta);
+  if (t >= nt) {                                       // a diagonal tile beyond the active bound
+    *ib = *jb = ta + (t - nt);
+    return;
+  }
+  int s = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+  while (join_tri(s + 1) <= t) ++s;
+  while (join_tri(s) > t) --s;
+  *jb = s;
+  *ib = t - join_tri(s);
+}
+__host__ __device__ inline bool transform_writes(int Ma, int I, int J) { return J >= 1 && (I == J || J < Ma); }
+// doubles per trajectory of the launch's frame buffer: its head (all heads first), and its means as they stood before the call
+inline long transform_frame_doubles(int ld) { return TF_HEAD + (long)ld; }
+
+// The call checked -- the range inside the bank (count == 0: nothing to do), T given and finite, cov NULL or per trajectory
+// finite (of cov what is read: the upper triangle), with a non-negative diagonal, c_ij^2 <= c_ii c_jj (plan_join's test for covT)
+// and no negative determinant (beyond its own rounding, as plan_predict_linear's Q) -- and turned into the launch's table
+// (TF_WORDS ints per trajectory), the heads of the frame records (TF_HEAD doubles per trajectory: T, 1.0 where a covariance is
+// given, the covariance mirrored from its upper triangle) and the grid: the most tiles of any applied trajectory.  The sizes
+// must be current (refresh_sizes).  Returns nullptr, or what is wrong with the arguments.
+struct TransformPlan {
+  int tiles_hi = 0, applied = 0;
+  bool with_cov = false;
+  std::vector<int> tab;
+  std::vector<double> head;
+};
+inline const char* plan_transform(const HostPlan* h, int b0, int count, const double* T, const double* cov, TransformPlan& tp) {
+  if (count < 0) return "count must be >= 0";
+  if (b0 < 0 || b0 > h->batch - count) return BANK_RANGE_WHY;
+  if (count > 0 && !T) return "NULL T";
+  constexpr double eps = 2.220446049250313e-16;
+  tp.tiles_hi = tp.applied = 0;
+  tp.with_cov = cov != nullptr;
+  tp.tab.assign((size_t)count * TF_WORDS, 0);
+  tp.head.assign((size_t)count * TF_HEAD, 0.0);
+  for (int bi = 0; bi < count; ++bi) {
+    const int b = b0 + bi;
+    const double* t = T + 3 * (size_t)bi;
+    double* f = tp.head.data() + (size_t)bi * TF_HEAD;
+    for (int a = 0; a < 3; ++a) {
+      if (!std::isfinite(t[a])) return "non-finite T";
+      f[a] = t[a];
+    }
+    if (cov) {
+      const double* c = cov + 9 * (size_t)bi;
+      for (int a = 0; a < 3; ++a)
+        for (int d = a; d < 3; ++d) {
+          if (!std::isfinite(c[3 * a + d])) return "non-finite cov";
+          f[4 + 3 * a + d] = f[4 + 3 * d + a] = c[3 * a + d];
+        }
+      for (int a = 0; a < 3; ++a) {
+        if (c[4 * a] < 0.0) return "cov has a negative diagonal entry";
+        for (int d = a + 1; d < 3; ++d)
+          if (c[3 * a + d] * c[3 * a + d] > c[4 * a] * c[4 * d]) return "cov is not a covariance (c_ij^2 > c_ii c_jj)";
+      }
+      const double det = c[0] * (c[4] * c[8] - c[5] * c[5]) - c[1] * (c[1] * c[8] - c[5] * c[2]) + c[2] * (c[1] * c[5] - c[4] * c[2]);
+      if (det < -32.0 * eps * c[0] * c[4] * c[8]) return "cov is not a covariance (negative determinant)";
+      f[3] = 1.0;
+    }
+    const int N = (h->n[b] - 3) / 2, M = 1 + N;
+    const int bound = h->opt_active_bound ? std::max(3, std::min(h->neff[b], h->n[b])) : h->n[b];
+    const int Ma = cov ? M : std::min(M, 1 + (bound - 3 + 1) / 2);
+    const bool applied = cov || t[0] != 0.0 || t[1] != 0.0 || t[2] != 0.0;
+    int* w = tp.tab.data() + (size_t)bi * TF_WORDS;
+    w[0] = b;
+    w[1] = N;
+    w[2] = Ma;
+    w[3] = applied ? 1 : 0;
+    if (applied) {
+      tp.applied += 1;
+      tp.tiles_hi = std::max(tp.tiles_hi, transform_tiles(M, Ma));
+    }
+  }
+  if (tp.tiles_hi + 1 > 65535) return "the state is too large for one launch";
+  return nullptr;
+}
+
 // ekf_associate (k_assoc_query / k_assoc_finish, ekf_associate.hip): the launch shape of the query over trajectories
 // [b0, b0 + count).  lane = landmark, a workgroup per chunk of AQ_CHUNK landmarks and trajectory, as k_marginals: N = 2000 x 1 is
 // 32 workgroups on 32 CUs, 32 x N = 2000 is 1024 (four per CU of 256), N = 20 x 256 one per trajectory.  The grid covers the

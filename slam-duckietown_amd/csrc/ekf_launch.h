@@ -105,7 +105,7 @@ void launch_factor_solve(hipStream_t st, const FactorView& w, int f0, int count,
                          double* white, double* quad);
 void launch_factor_multiply(hipStream_t st, const FactorView& w, int f0, int count, int nblk_hi, const double* z, int nrhs,
                             int stride, double* out);
-// ---- state surgery (ekf_remove.hip, ekf_direct.hip, ekf_linear.hip, ekf_predict_linear.hip, ekf_copy.hip, ekf_join.hip, ekf_dense.hip) ----
+// ---- state surgery (ekf_remove.hip, ekf_direct.hip, ekf_linear.hip, ekf_predict_linear.hip, ekf_copy.hip, ekf_join.hip, ekf_transform.hip, ekf_dense.hip) ----
 // rp.rows: the launch's largest new size (grid rows); nb trajectories from b0; src / dst: rp's tables on the device
 void launch_remove(hipStream_t st, const BankView& k, double* mu, const RemovePlan& rp, const int* src, const int* dst,
                    unsigned* rflag, int b0, int nb, unsigned seq);
@@ -125,5 +125,9 @@ void launch_copy_traj(hipStream_t st, bool nt, const BankView& src, const BankVi
 // (join_snap_doubles per pair; explicit mode: the host has uploaded the heads); tab: plan_join's table on the device
 void launch_join(hipStream_t st, const BankView& src, const BankView& dst, const double* mus, double* mud, const int* tab,
                  double* snap, int pairs, int tiles_hi, int na_hi, bool seq);
+// count x (tiles_hi + 1) workgroups, in place on k.P and mu; tab: plan_transform's table on the device, frames: count x
+// transform_frame_doubles(k.ld) doubles -- the plan's heads, then k.ld means per trajectory as they stood before the call;
+// nt: nontemporal stores of the 2 x 2 blocks
+void launch_transform(hipStream_t st, bool nt, const BankView& k, double* mu, const int* tab, const double* frames, int count, int tiles_hi);
 int dense_propagate(hipStream_t st, double* P, double* tmp, const double* F, const double* Q, int n, int ld);
 }  // namespace ekf

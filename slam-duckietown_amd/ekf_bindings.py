@@ -30,7 +30,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .frontend import associate, joint_compatibility, remap_tag_index, resolve_associations
+from .frontend import associate, fit_transform, joint_compatibility, remap_tag_index, resolve_associations
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libekfslam_hip.so"
@@ -140,6 +140,7 @@ ABI = {
     "ekf_remove_landmarks": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_int]),
     "ekf_copy_trajectories": (C.c_int, [C.c_void_p, _ip, C.c_void_p, _ip, C.c_int]),
     "ekf_join_maps": (C.c_int, [C.c_void_p, _ip, C.c_void_p, _ip, C.c_int, _dp, _dp, _ip, _ip, C.c_int]),
+    "ekf_transform": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
     "ekf_predict": (C.c_int, [C.c_void_p, _dp, _dp]),
     "ekf_predict_linear": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _ip]),
     "ekf_update": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _ip, C.c_int]),
@@ -1334,6 +1335,56 @@ class EkfSlam:
         if scalar:
             return MapJoin(int(first[0]), int(count[0]), twins[0].copy())
         return MapJoin(first, count, twins)
+
+    def transform(self, T, cov=None, b: Optional[int] = None):
+        """Move the filter into another frame, in place, on the device (``ekf_transform``): ``T`` = (x, y, phi) is the OLD
+        frame expressed in the NEW one (``join``'s ``transform`` convention; ``frontend.fit_transform`` returns it), ``cov``
+        its 3 x 3 covariance or None when the frame is known exactly.  Every landmark becomes ``t + R l``, the pose
+        ``(t + R p_xy, theta + phi)`` (theta is not wrapped), the covariance ``J P J^T`` (+ ``A cov A^T``): exact for any
+        offset, no rank and no covariance pass.  ``b`` None: the whole bank -- ``T`` (3,) for all or (batch, 3), ``cov``
+        (3, 3) or (batch, 3, 3); ``b`` an int: that trajectory alone, the others stay bit for bit.  What is pending is
+        applied first.  Sizes, ``tag_index()``, noise rows, gate counters, flags and log rows stay; ``tags_positions()``
+        follows; an uploaded stream stays runnable.  Without ``cov`` the active bound stays, with it every item becomes
+        correlated with every other.  ``T`` = 0 without ``cov`` changes nothing, bit for bit.  Blocking; ``EkfError`` with
+        nothing changed for a trajectory outside the bank, a non-finite ``T`` or a ``cov`` that is no covariance."""
+        b0, count = (0, self.batch) if b is None else (int(b), 1)
+        if not -2 ** 31 <= b0 < 2 ** 31:
+            raise EkfError("transform: trajectory index out of range")
+        T = _f64(T)
+        if T.shape not in ((3,), (count, 3)):
+            raise ValueError(f"transform: T must be (3,) or ({count}, 3), got {T.shape}")
+        T = np.ascontiguousarray(np.broadcast_to(T.reshape(-1, 3), (count, 3)))
+        cT = None
+        if cov is not None:
+            cT = _f64(cov)
+            if cT.shape not in ((3, 3), (count, 3, 3)):
+                raise ValueError(f"transform: cov must be (3, 3) or ({count}, 3, 3), got {cT.shape}")
+            cT = np.ascontiguousarray(np.broadcast_to(cT.reshape(-1, 3, 3), (count, 3, 3)))
+        self._check(self._lib.ekf_transform(self._h, b0, count, _p(T), None if cT is None else _p(cT)))
+        # (what the host association keeps per trajectory follows the state: the last window's world positions)
+        for i in range(count):
+            tags = self._host_tags.get(b0 + i)
+            if tags:
+                c, s = math.cos(T[i, 2]), math.sin(T[i, 2])
+                self._host_tags[b0 + i] = {j: [T[i, 0] + (c * v[0] - s * v[1]), T[i, 1] + (s * v[0] + c * v[1])] + list(v[2:])
+                                           for j, v in tags.items()}
+
+    def align_landmarks(self, landmarks, xy, weights=None, b: int = 0) -> np.ndarray:
+        """Align trajectory b with a survey: fit the current means of ``landmarks`` to their surveyed positions ``xy`` (k, 2)
+        (``frontend.fit_transform``, ``weights`` as there; at least two distinct landmarks) and move the filter through the
+        fitted frame with ``transform(T, b=b)`` -- WITHOUT a covariance.  Returns ``T``.  The survey's information goes into
+        the filter once, through ``anchor_landmarks`` afterwards ("align, then anchor"): the alignment only brings the map
+        close enough for that linear update to be valid, whatever the offset was.  Passing the fit's covariance to
+        ``transform`` as well would count the survey twice."""
+        lm = np.asarray(landmarks, dtype=np.int64).reshape(-1)
+        xy = _f64(xy, (len(lm), 2))
+        nl = (self.size(b) - 3) // 2
+        if lm.size and (lm.min() < 0 or lm.max() >= nl):
+            raise EkfError("align_landmarks: landmark index outside the state")
+        mean = self.mean(b)[3:].reshape(-1, 2)
+        T, _cov = fit_transform(mean[lm], xy, weights)
+        self.transform(T, b=b)
+        return T
 
     def fork(self, src: int = 0, dst=None):
         """Fork trajectory ``src`` inside the bank, on the device: ``dst`` (an int, a sequence, or None for every other

@@ -132,6 +132,47 @@ def resolve_associations(cand, nis, min_nis, accept: float, create: float):
     return assign, sorted(new_obs), sorted(dropped)
 
 
+def fit_transform(src_xy, dst_xy, weights=None):
+    """The rigid transform without scale ``T = (x, y, phi)`` that minimises ``sum_i w_i |dst_i - (t + R(phi) src_i)|^2``, and
+    its covariance: ``(T (3,), cov (3, 3))``.  ``T`` is the frame of ``src`` expressed in the frame of ``dst`` -- what
+    ``EkfSlam.transform`` and ``EkfSlam.join(transform=)`` take.  Closed form: weighted centroids c_s, c_d, then on the centred
+    points a_i, b_i ``phi = atan2(sum w a x b, sum w a . b)``, then ``t = c_d - R c_s``.  ``cov = (sum_i w_i A_i^T A_i)^-1``
+    with ``A_i = [I2 | J2 R src_i]``: the estimate's covariance when ``dst_i`` carries noise ``I / w_i``.  ``weights`` None:
+    all one.  ``ValueError`` for unequal lengths, non-finite input, negative weights, or fewer than two distinct points of
+    positive weight (the rotation is then undetermined)."""
+    src = np.asarray(src_xy, dtype=np.float64)
+    dst = np.asarray(dst_xy, dtype=np.float64)
+    if src.ndim != 2 or src.shape[1] != 2 or dst.ndim != 2 or dst.shape[1] != 2:
+        raise ValueError("fit_transform: (k, 2) arrays expected")
+    if src.shape[0] != dst.shape[0]:
+        raise ValueError(f"fit_transform: src and dst must have the same length, got {src.shape[0]} and {dst.shape[0]}")
+    w = np.ones(src.shape[0]) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape[0] != src.shape[0]:
+        raise ValueError("fit_transform: one weight per point expected")
+    if not (np.isfinite(src).all() and np.isfinite(dst).all() and np.isfinite(w).all()):
+        raise ValueError("fit_transform: non-finite input")
+    if (w < 0).any():
+        raise ValueError("fit_transform: negative weight")
+    used = w > 0
+    if len({(float(p[0]), float(p[1])) for p in src[used]}) < 2 or len({(float(p[0]), float(p[1])) for p in dst[used]}) < 2:
+        raise ValueError("fit_transform: at least two distinct points are needed")
+    W = w.sum()
+    cs, cd = (w[:, None] * src).sum(0) / W, (w[:, None] * dst).sum(0) / W
+    a, b = src - cs, dst - cd
+    phi = math.atan2(float((w * (a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0])).sum()), float((w * (a * b).sum(1)).sum()))
+    c, s = math.cos(phi), math.sin(phi)
+    R = np.array([[c, -s], [s, c]])
+    t = cd - R @ cs
+    rs = src @ R.T                                                 # R src_i
+    g = np.stack([-rs[:, 1], rs[:, 0]], axis=1)                    # J2 R src_i
+    info = np.zeros((3, 3))
+    info[0, 0] = info[1, 1] = W
+    info[:2, 2] = info[2, :2] = (w[:, None] * g).sum(0)
+    info[2, 2] = (w * (g * g).sum(1)).sum()
+    cov = np.linalg.inv(info)
+    return np.array([t[0], t[1], phi]), (cov + cov.T) / 2          # (exactly symmetric)
+
+
 def wrap_pi(a):
     """(a + pi) % 2 pi - pi with NumPy remainder semantics, [-pi, pi): how the device wraps a bearing residual."""
     return (a + np.pi) % (2.0 * np.pi) - np.pi

@@ -1,0 +1,481 @@
+"""GPU: the change of frame on the device (ekf_transform, EkfSlam.transform / align_landmarks; k_transform in
+csrc/ekf_transform.hip) against tests/transform_model.py.
+
+Tolerance against the model (the rule of tests/test_gpu_join.py): entrywise |got - ref| <= 1e-13 x bound, bound =
+|J| |P| |J|^T + |A| |Sigma| |A|^T for the covariance and |t| + |R| |l| for the mean.  An entry is at most 13 three-factor
+products, so its forward error is below gamma_40 ~ 4.4e-15 of the bound, the device's sin / cos add about 1e-15: 1e-13 leaves
+roughly 15 x headroom.  What the call only leaves alone is compared bit for bit.  Runs that go on are compared with the oracle
+at the project's TIGHT."""
+import ctypes as C
+from types import SimpleNamespace as NS
+
+import numpy as np
+import pytest
+
+from oracle import ekf_oracle as orc
+from tests import direct_model as dm
+from tests import join_model as jm
+from tests import transform_model as tm
+from tests.conftest import path_ran
+
+pytestmark = pytest.mark.gpu
+
+TIGHT = 1e-10          # the project's bar for a run against the oracle
+TOL = 1e-13            # x the entrywise bound (see above)
+EKF_ERR_ARG, EKF_ERR_STATE = -1, -3
+PHIS = (0.3, np.pi / 2, -2.9)
+COV = np.array([[0.04, 0.01, -0.002], [0.01, 0.09, 0.003], [-0.002, 0.003, 0.002]])
+
+
+@pytest.fixture(scope="module")
+def sd():
+    import slam_duckietown_amd as sd
+    sd.load_library()
+    return sd
+
+
+def same(a, b):
+    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+
+
+def col(x):
+    return x[:, None]
+
+
+def raw00(sd, f, b=0):
+    """P_base[0, 0] of trajectory b as stored (no flush)."""
+    out = np.empty(1)
+    sd.load_library().ekf_debug_snapshot(f._h, b, 0, out.ctypes.data_as(C.POINTER(C.c_double)), 1)
+    return out[0]
+
+
+def uploaded(sd, states, n_max, general=False):
+    """A bank holding the dense states `states`, one per trajectory."""
+    f = sd.EkfSlam(n_max, batch=len(states))
+    if general:
+        f.set_option("small_state", 0)
+    for b, (x, P) in enumerate(states):
+        f.set_state(x, P, b)
+    return f
+
+
+def stepped(sd, N, n_max, steps, m, seed, general=False):
+    """A filter from a diagonal start with `steps` single steps of a synthetic stream behind it: ranks are left pending."""
+    s = orc.synthetic_stream(N, steps, m, seed)
+    f = sd.EkfSlam(n_max)
+    if general:
+        f.set_option("small_state", 0)
+    f.set_state_diag(s[0], s[1])
+    for k in range(steps):
+        f.step(s[2][k], s[3][k], s[4][k], s[5][k], s[6][k])
+    return f
+
+
+def check_model(got, before, T, cov=None, label=""):
+    """`got` against the model applied to `before`; prints the worst ratio to the bound before it asserts."""
+    xm, Pm, bound, mbound = tm.transform_dense(before[0], before[1], T, cov)
+    assert got[0].shape == xm.shape and got[1].shape == Pm.shape
+    eP, em = np.abs(got[1] - Pm), np.abs(got[0] - xm)
+    rP = float(np.max(eP / np.where(bound > 0, bound, 1.0))) if eP.size else 0.0
+    rm = float(np.max(em / np.where(mbound > 0, mbound, 1.0))) if em.size else 0.0
+    print(f"{label}: worst covariance error / bound {rP:.3g}, mean {rm:.3g}")
+    assert (eP <= TOL * bound).all() and (em <= TOL * mbound).all()
+    assert np.array_equal(got[1], got[1].T)
+    return xm, Pm, bound
+
+
+def stream_from(mean, steps, m, seed):
+    """A synthetic stream consistent with a filter's own estimate (the construction of tests/test_gpu_join.py): ranges,
+    bearings and increments only -- the same stream in every frame."""
+    cfg, rng = orc.EkfConfig(), np.random.default_rng(seed)
+    lm, pose, N = mean[3:].reshape(-1, 2), mean[:3].copy(), (len(mean) - 3) // 2
+    lin, ang = np.full(steps, 0.004), np.full(steps, 0.02)
+    idx, zr, zb = np.zeros((steps, m), dtype=np.int32), np.zeros((steps, m)), np.zeros((steps, m))
+    for k in range(steps):
+        pose, _ = orc.motion_model(pose, lin[k], ang[k], cfg)
+        vis = (m * k + np.arange(m)) % N
+        d = lm[vis] - pose[:2]
+        c, s = np.cos(pose[2]), np.sin(pose[2])
+        xr = c * d[:, 0] + s * d[:, 1] + rng.normal(0.0, 0.01, m)
+        yr = -s * d[:, 0] + c * d[:, 1] + rng.normal(0.0, 0.01, m)
+        idx[k], zr[k], zb[k] = vis, np.sqrt(xr ** 2 + yr ** 2), np.arctan2(yr, xr)
+    return lin, ang, idx, zr, zb
+
+
+def oracle_run(state, st):
+    om, oP = state
+    cfg = orc.EkfConfig()
+    for k in range(len(st[0])):
+        om, oP = orc.ekf_step_structured(om, oP, st[0][k], st[1][k], st[2][k], st[3][k], st[4][k], cfg)
+    return om, oP
+
+
+# ---- 1: model parity at the sizes where the kernel can go wrong -----------------------------------------------------------
+@pytest.mark.parametrize("N", [0, 1, 31, 32, 70])
+@pytest.mark.parametrize("with_cov", [False, True])
+def test_model_parity_at_tile_edges(sd, N, with_cov):
+    """N = 0 the pose alone, 1, 31 (the pose plus 31 landmarks fill one tile exactly), 32 (one item spills into a second tile),
+    70 (three tile rows, the last partial)."""
+    rng = np.random.default_rng(200 + N)
+    S = jm.random_state(rng, N)
+    cov = COV if with_cov else None
+    with uploaded(sd, [S], 3 + 2 * N) as f:
+        for phi in PHIS:
+            f.set_state(*S)
+            before = f.state()
+            f.transform([0.7, -0.4, phi], cov)
+            assert f.size() == 3 + 2 * N and f.flags() == 0
+            check_model(f.state(), before, np.array([0.7, -0.4, phi]), cov, f"N {N} cov {with_cov} phi {phi:.2f}")
+
+
+_PANEL = {}
+
+
+def panel_state():
+    """N = 2048 (n = 4099): low rank plus diagonal, every entry non-zero."""
+    if not _PANEL:
+        n = 4099
+        rng = np.random.default_rng(5)
+        U = rng.normal(size=(n, 8)) * 0.2
+        _PANEL["s"] = (np.r_[0.3, -0.2, 0.9, rng.uniform(-2.0, 2.0, n - 3)], U @ U.T + np.diag(rng.uniform(0.5, 2.0, n)))
+    return _PANEL["s"]
+
+
+@pytest.mark.parametrize("with_cov,phi", [(False, 0.3), (True, np.pi / 2), (False, -2.9), (True, 0.3), (False, np.pi / 2), (True, -2.9)])
+def test_across_the_panel_boundary(sd, with_cov, phi):
+    """n_max = 4099 (ld = 4160, two column panels): landmark 2046 holds the columns 4095 | 4096."""
+    x, P = panel_state()
+    T, cov = np.array([0.7, -0.4, phi]), (COV if with_cov else None)
+    with sd.EkfSlam(4099) as f:
+        f.set_state(x, P)
+        f.transform(T, cov)
+        got = f.state()
+        assert f.flags() == 0 and f.size() == 4099
+    xm, Pm, bound = check_model(got, (x, P), T, cov, f"panels cov {with_cov} phi {phi:.2f}")
+    near = slice(3 + 2 * 2044, 3 + 2 * 2048)                        # landmarks 2044 .. 2047: columns 4091 .. 4098
+    for sl in ((slice(None), near), (near, near), (slice(4095, 4097), slice(4095, 4097))):
+        assert np.abs(got[1][sl]).min() > 0.0 and not np.array_equal(got[1][sl], P[sl])
+        assert (np.abs(got[1][sl] - Pm[sl]) <= TOL * bound[sl]).all()
+
+
+# ---- 2: both paths -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("with_cov", [False, True])
+def test_both_paths(sd, both_paths, with_cov):
+    N = 10
+    s = orc.synthetic_stream(N, 3, 4, 61)
+    with sd.EkfSlam(3 + 2 * N) as f:
+        f.set_state_diag(s[0], s[1])
+        f.step(s[2][0], s[3][0], s[4][0], s[5][0], s[6][0])         # (one step first: small_launches counts it)
+        assert path_ran(f, both_paths)
+        before = f.state()
+        T, cov = np.array([-1.5, 2.0, 2.2]), (COV if with_cov else None)
+        f.transform(T, cov)
+        xm, Pm, bound = check_model(f.state(), before, T, cov, f"N 10 {both_paths} cov {with_cov}")
+        for k in (1, 2):
+            f.step(s[2][k], s[3][k], s[4][k], s[5][k], s[6][k])
+        got = f.state()
+        assert path_ran(f, both_paths) and f.flags() == 0
+    cfg = orc.EkfConfig()
+    for k in (1, 2):
+        xm, Pm = orc.ekf_step_dense(xm, Pm, s[2][k], s[3][k], s[4][k], s[5][k], s[6][k], cfg)
+    print("two steps on:", orc.rel_fro(got[0], xm), orc.rel_fro(got[1], Pm))
+    assert orc.rel_fro(got[0], xm) < TIGHT and orc.rel_fro(got[1], Pm) < TIGHT
+
+
+# ---- 3: a bank of three ------------------------------------------------------------------------------------------------------
+def test_bank_of_three(sd):
+    rng = np.random.default_rng(31)
+    S = [jm.random_state(rng, N) for N in (5, 40, 33)]
+    Ts = np.array([[0.5, -1.0, 0.3], [5.0, -3.0, 1.0], [-2.0, 0.25, -2.9]])
+    covs = np.stack([COV, 2.0 * COV, 0.5 * COV])
+    n_max = 3 + 2 * 40
+    with uploaded(sd, S, n_max) as f, uploaded(sd, S, n_max) as g, uploaded(sd, [S[1]], n_max) as alone, \
+            uploaded(sd, [S[1]], n_max) as alone_c:
+        f.transform(Ts[1], b=1)                                     # a call on [1, 2)
+        assert same(f.state(0), S[0]) and same(f.state(2), S[2])
+        one = f.state(1)
+        check_model(one, S[1], Ts[1], None, "bank: trajectory 1 alone")
+        alone.transform(Ts[1])
+        assert same(alone.state(), one)
+        g.transform(Ts)                                             # the whole bank, a frame each
+        for b in range(3):
+            check_model(g.state(b), S[b], Ts[b], None, f"bank: trajectory {b}")
+        assert same(g.state(1), one)                                # the same bits alone and inside the bank
+        g.transform(Ts, covs)
+        alone_c.transform(Ts[1])
+        alone_c.transform(Ts[1], covs[1])
+        assert same(g.state(1), alone_c.state())
+        assert [g.size(b) for b in range(3)] == [13, 83, 69] and all(g.flags(b) == 0 for b in range(3))
+
+
+# ---- 4: pending ranks ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("with_cov", [False, True])
+def test_pending_ranks_are_applied_first(sd, with_cov):
+    mk = lambda: stepped(sd, 50, 3 + 2 * 60, 2, 4, 71, general=True)
+    with mk() as f, mk() as twin:
+        before = twin.state()                                       # the twin's download: what the call must start from
+        assert raw00(sd, f) != before[1][0, 0]                      # ranks are pending at the call
+        print("last pass before:", f.last_pass(), "cadences:", f.cadence_counters())
+        T, cov = np.array([5.0, -3.0, 1.0]), (COV if with_cov else None)
+        f.transform(T, cov)
+        got = f.state()
+        assert raw00(sd, f) == got[1][0, 0]                         # nothing is pending afterwards
+        check_model(got, before, T, cov, f"pending ranks cov {with_cov}")
+
+
+# ---- 5: the active bound -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("with_cov", [False, True])
+def test_active_bound(sd, with_cov):
+    """N = 20, landmarks 16 .. 19 never observed (beyond the bound).  Without a covariance every exact zero stays +0.0 and the
+    filter goes on as the oracle does; with one every cross entry matches the model, and the step behind it -- which would
+    skip everything beyond a bound left where it was -- still matches the oracle."""
+    s = dm.small_stream()
+    cfg = orc.EkfConfig()
+    with sd.EkfSlam(43) as f:
+        f.set_option("small_state", 0)
+        f.set_state_diag(s[0], s[1])
+        for k in range(dm.SMALL_STEPS):
+            f.step(*[a[k] for a in s[2:]])
+        before = f.state()
+        zero = before[1] == 0.0
+        assert zero[3 + 32:, :3 + 32].all() and np.count_nonzero(~zero[3 + 32:, 3 + 32:]) == 8
+        T, cov = np.array([5.0, -3.0, 1.0]), (COV if with_cov else None)
+        f.transform(T, cov)
+        got = f.state()
+        xm, Pm, bound = check_model(got, before, T, cov, f"active bound cov {with_cov}")
+        if with_cov:
+            assert (got[1] != 0.0).all()
+        else:
+            own = np.zeros((43, 43), dtype=bool)                    # an item's own block: rotated, also beyond the bound
+            own[:3, :3] = True
+            for j in range(20):
+                own[3 + 2 * j:5 + 2 * j, 3 + 2 * j:5 + 2 * j] = True
+            assert np.array_equal((got[1] == 0.0) & ~own, zero & ~own) and not np.signbit(got[1][got[1] == 0.0]).any()
+            assert (got[1][own] != 0.0).sum() >= 9 + 3 * 20
+        k = dm.SMALL_STEPS
+        f.step(*[a[k] for a in s[2:]])
+        on = f.state()
+        assert f.flags() == 0
+    xm, Pm = orc.ekf_step_dense(xm, Pm, *[a[k] for a in s[2:]], cfg)
+    print("one step on:", orc.rel_fro(on[0], xm), orc.rel_fro(on[1], Pm))
+    assert orc.rel_fro(on[0], xm) < TIGHT and orc.rel_fro(on[1], Pm) < TIGHT
+
+
+# ---- 6: identity and round trip ---------------------------------------------------------------------------------------------
+def test_identity_and_round_trip(sd):
+    rng = np.random.default_rng(41)
+    S = jm.random_state(rng, 45)
+    S[1][7, 9] = S[1][9, 7] = -0.0                                  # (an entry the identity must not turn into +0.0)
+    with uploaded(sd, [S, S], 3 + 2 * 45) as f:
+        before = f.state(0)
+        f.transform(np.zeros(3))
+        f.transform(np.zeros((2, 3)))
+        f.transform(np.zeros(3), b=1)
+        assert same(f.state(0), before) and same(f.state(1), before) and np.signbit(f.state(0)[1][7, 9])
+        T = np.array([5.0, -3.0, 1.0])
+        f.transform(T, b=0)
+        mid = f.state(0)
+        assert not same(mid, before)
+        f.transform(tm.inverse(T), b=0)
+        got = f.state(0)
+        _, _, b1, m1 = tm.transform_dense(before[0], before[1], T)
+        _, _, b2, m2 = tm.transform_dense(mid[0], mid[1], tm.inverse(T))
+        # two calls, the rule for each: the first one's error, at most TOL x b1 (TOL x m1), is carried through the second's
+        # |J| (|R|), the second adds at most TOL x b2 (TOL x m2)
+        Ra = np.abs(tm.rot(-T[2]))
+        bP = tm._congruence(b1, Ra) + b2
+        bm = np.r_[Ra @ m1[:2], m1[2], (m1[3:].reshape(-1, 2) @ Ra.T).ravel()] + m2
+        eP, em = np.abs(got[1] - before[1]), np.abs(got[0] - before[0])
+        print("round trip: worst error / bound", float(np.max(eP / bP)), float(np.max(em / bm)))
+        assert (eP <= TOL * bP).all() and (em <= TOL * bm).all()
+        assert same(f.state(1), before)
+
+
+# ---- 7: the filter goes on ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("N,n_max,small", [(60, 163, False), (10, 39, True)])
+@pytest.mark.parametrize("with_cov", [False, True])
+def test_the_filter_goes_on(sd, N, n_max, small, with_cov):
+    """The stream uploaded BEFORE the call still runs (ranges, bearings and increments are frame-free), then 30 steps of a
+    new stream, once through run_stream and once through single steps -- against the oracle started from the
+    model-transformed state."""
+    T, cov = np.array([5.0, -3.0, 1.0]), (COV if with_cov else None)
+    s = orc.synthetic_stream(N, 20, 6, 101)
+
+    def mk():
+        f = sd.EkfSlam(n_max)
+        if not small:
+            f.set_option("small_state", 0)
+        f.set_state_diag(s[0], s[1])
+        f.run_stream(*[col(a) for a in s[2:]])
+        return f
+
+    with mk() as a, mk() as b:
+        A = a.state()
+        assert same(b.state(), A)
+        xm, Pm, _, _ = tm.transform_dense(A[0], A[1], T, cov)
+        old = stream_from(xm, 10, 6, 103)
+        for f in (a, b):
+            f.stream_upload(*[col(x) for x in old])
+            f.transform(T, cov)
+            check_model(f.state(), A, T, cov, f"N {N} before the run")
+            f.stream_run(0, 10)                                     # the stream uploaded before the call
+        mid = oracle_run((xm, (Pm + Pm.T) / 2), old)
+        new = stream_from(mid[0], 30, 6, 105)
+        a.run_stream(*[col(x) for x in new])
+        for k in range(30):
+            b.step(*[x[k] for x in new])
+        ga, gb = a.state(), b.state()
+        assert a.flags() == 0 and b.flags() == 0
+        assert path_ran(a, "default_path" if small else "general_kernels") and path_ran(b, "default_path" if small else "general_kernels")
+    om, oP = oracle_run(mid, new)
+    for name, g in (("run_stream", ga), ("single steps", gb)):
+        print(f"N {N} cov {with_cov} after 10 + 30 steps, {name}: mean {orc.rel_fro(g[0], om):.3g} covariance {orc.rel_fro(g[1], oP):.3g}")
+        assert orc.rel_fro(g[0], om) < TIGHT and orc.rel_fro(g[1], oP) < TIGHT
+
+
+# ---- 8: tags, logs and counters --------------------------------------------------------------------------------------------
+def _tag(i, x, z):
+    return NS(tag_id=i, pose_R=np.eye(3), pose_t=np.array([[x], [0.0], [z]]), pose_err=0.0)
+
+
+def test_tags_logs_and_counters(sd):
+    cfg, rng = orc.EkfConfig(), np.random.default_rng(17)
+    ids = [int(i) for i in rng.permutation(500)[:6]]
+    world = {i: np.array([rng.uniform(0.3, 1.0), rng.uniform(-0.5, 0.5)]) for i in ids}
+    truth = np.zeros(3)
+
+    def window(k):
+        c, s = np.cos(truth[2]), np.sin(truth[2])
+        tags = []
+        for i in ids:
+            d = world[i] - truth[:2]
+            xr, yr = c * d[0] + s * d[1] + rng.normal(0, 0.004), -s * d[0] + c * d[1] + rng.normal(0, 0.004)
+            tags.append(_tag(i, -yr, xr))
+        return [(float(k), tags)]
+
+    T = np.array([5.0, -3.0, 1.0])
+    R = tm.rot(T[2])
+    with sd.EkfSlam(3 + 2 * 8) as f:
+        f.log_innovations(64)
+        f.log_poses(64)
+        f.set_nis_gate(confidence=0.999)
+        f.set_noise(0.12, 0.6)
+        for k in range(10):
+            truth, _ = orc.motion_model(truth, 0.004, 0.02, cfg)
+            f.step_detections(0.004, 0.02, window(k))
+        index, pos, before = f.tag_index(), f.tags_positions(), f.state()
+        counters = (f.pose_steps, len(f.innovations().steps), f.gate_counts().tolist(), [x.tolist() for x in f.noise()], f.assoc_fallbacks())
+        assert len(index) == 6 and len(pos) == 6 and counters[0] == 10
+        f.transform(T)
+        check_model(f.state(), before, T, None, "after ten windows")
+        assert f.tag_index() == index
+        moved = f.tags_positions()
+        assert list(moved) == list(pos)
+        for j, v in pos.items():
+            want = T[:2] + R @ np.array(v[:2])
+            assert np.abs(np.array(moved[j][:2]) - want).max() <= 1e-13 * (np.abs(T[:2]) + np.abs(R) @ np.abs(v[:2])).max()
+            assert moved[j][2:] == v[2:]
+        assert (f.pose_steps, len(f.innovations().steps), f.gate_counts().tolist(), [x.tolist() for x in f.noise()], f.assoc_fallbacks()) == counters
+        truth, _ = orc.motion_model(truth, 0.004, 0.02, cfg)
+        f.step_detections(0.004, 0.02, window(10))                  # the next window: the same landmarks, no new one
+        assert f.tag_index() == index and f.size() == 15 and f.assoc_fallbacks() == counters[4] and f.flags() == 0
+        assert f.pose_steps == 11 and sorted(f.tags_positions()) == sorted(pos)
+        got = f.mean()
+        lm_new = T[:2] + np.array([world[i] for i in sorted(index, key=index.get)]) @ R.T
+        assert np.abs(got[3:].reshape(-1, 2) - lm_new).max() < 0.2      # the map lies in the new frame
+
+
+def test_factor_and_profile_class(sd):
+    """A factor is a snapshot of the state it was taken from: as after a step (tests/test_gpu_factor.py), it stays readable bit
+    for bit behind a transform and is replaced by the next factor().  With profile_kernels the launch is class 8."""
+    rng = np.random.default_rng(51)
+    S = jm.random_state(rng, 50)
+    with uploaded(sd, [S], 103) as f:
+        fac = f.factor(0)
+        U0 = fac.upper(0)
+        f.set_option("profile_kernels", 1)
+        f.profile_enable(True)
+        f.transform([5.0, -3.0, 1.0], COV)
+        assert f.profile_read_class(8)[1] == 1 and f.profile_read_class(6)[1] == 0
+        f.profile_enable(False)
+        assert np.array_equal(fac.upper(0), U0)
+        newer = f.factor(0)
+        assert newer.info == 0 and not np.array_equal(newer.upper(0), U0)
+        with pytest.raises(sd.EkfError, match="replaced"):
+            fac.upper(0)
+
+
+# ---- 9: align, then anchor -----------------------------------------------------------------------------------------------------
+def test_align_then_anchor(sd):
+    """tests/transform_model.py: align_case on the device.  The gated anchor is refused before the alignment and leaves the
+    state bit for bit; after align_landmarks it is applied, and the landmark means then lie on the survey as well as a rigid
+    alignment of the unaligned map would have put them, x 1.5 (on the model: 1.05, tests/test_transform_cpu.py)."""
+    from slam_duckietown_amd.evaluation import ate_rmse
+    c = tm.align_case()
+    x, P, survey, anchors, R = c["x"], c["P"], c["survey"], list(c["anchors"]), c["R"]
+    N = (len(x) - 3) // 2
+    with uploaded(sd, [(x, P)], len(x)) as f:
+        before = f.state()
+        r = f.anchor_landmarks(anchors, survey[anchors], R, b=0, confidence=0.99)
+        print("before the alignment: NIS", r.nis[0], "applied", r.applied[0])
+        assert not r.applied[0] and same(f.state(), before)
+        e_aligned = ate_rmse(before[0][3:].reshape(-1, 2), survey, align=True)
+        T = f.align_landmarks(np.arange(N), survey)
+        assert np.abs(T - tm.ALIGN_FRAME).max() < 0.5
+        check_model(f.state(), before, T, None, "aligned")
+        r = f.anchor_landmarks(anchors, survey[anchors], R, b=0, confidence=0.99)
+        print("after the alignment: NIS", r.nis[0], "applied", r.applied[0])
+        assert r.applied[0] and f.flags() == 0
+        e_final = ate_rmse(f.mean()[3:].reshape(-1, 2), survey)
+    print(f"ate: {e_aligned:.4g} with align=True before, {e_final:.4g} without after align + anchor")
+    assert e_final <= tm.ALIGN_MARGIN * e_aligned
+
+
+# ---- 10: errors ----------------------------------------------------------------------------------------------------------------
+def test_bad_arguments_change_nothing(sd):
+    lib = sd.load_library()
+    rng = np.random.default_rng(81)
+    S = [jm.random_state(rng, N) for N in (4, 9, 6)]
+    with uploaded(sd, S, 3 + 2 * 9) as f:
+        unchanged = lambda: all(same(f.state(b), S[b]) for b in range(3))
+        dbl = lambda *v: (C.c_double * len(v))(*v)
+        T0 = dbl(0.1, 0.2, 0.3, 0.1, 0.2, 0.3, 0.1, 0.2, 0.3)
+        C0 = dbl(*([0.01, 0, 0, 0, 0.01, 0, 0, 0, 0.01] * 3))
+        call = lambda b0, count, T=T0, cov=None: lib.ekf_transform(f._h, b0, count, T, cov)
+        for b0, count in ((0, -1), (-1, 1), (3, 1), (1, 3), (0, 4), (4, 0)):                     # count < 0, a range outside the bank
+            assert call(b0, count) == EKF_ERR_ARG and unchanged(), (b0, count)
+            assert b"ekf_transform" in lib.ekf_last_error(f._h)
+        assert call(0, 1, None) == EKF_ERR_ARG and b"NULL T" in lib.ekf_last_error(f._h) and unchanged()
+        for bad in (dbl(np.nan, 0, 0), dbl(0, np.inf, 0), dbl(0, 0, -np.inf)):
+            assert call(1, 1, bad) == EKF_ERR_ARG and b"non-finite T" in lib.ekf_last_error(f._h) and unchanged()
+        for bad in (dbl(np.nan, 0, 0, 0, 1, 0, 0, 0, 1), dbl(-1e-9, 0, 0, 0, 1, 0, 0, 0, 1), dbl(1, 1.01, 0, 0, 1, 0, 0, 0, 1),
+                    dbl(0, 0, 1e-3, 0, 1, 0, 0, 0, 1), dbl(1, 0.9, -0.9, 0, 1, 0.9, 0, 0, 1)):
+            assert call(2, 1, T0, bad) == EKF_ERR_ARG and b"cov" in lib.ekf_last_error(f._h) and unchanged()
+        assert call(0, 3, T0, dbl(*([0.01, 0, 0, 0, 0.01, 0, 0, 0, 0.01] * 2 + [0.01, 0, 0, 0, -1.0, 0, 0, 0, 0.01]))) == EKF_ERR_ARG
+        assert unchanged()                                                                       # (the last trajectory's cov: nothing changed in the others)
+        with pytest.raises(sd.EkfError, match="outside the bank"):
+            f.transform(np.zeros(3), b=3)
+        assert call(0, 0, None) == 0 and call(3, 0, None) == 0 and unchanged()                   # count = 0
+        f.transform([0.1, 0.2, 0.3], b=1)                           # and the handle is usable afterwards
+        check_model(f.state(1), S[1], np.array([0.1, 0.2, 0.3]), None, "after the refusals")
+        assert same(f.state(0), S[0]) and same(f.state(2), S[2])
+        assert call(0, 3, T0, C0) == 0 and f.flags(0) == 0
+
+
+def test_an_undefined_trajectory_is_refused(sd):
+    """A trajectory under EKF_FLAG_INTERNAL (the diagnostic "fused_step" = 2 of tests/test_gpu_join.py: the bounded wait of a
+    single-launch step times out) gives EKF_ERR_STATE."""
+    from slam_duckietown_amd import ekf_bindings as eb
+    lib = sd.load_library()
+    s = orc.synthetic_stream(50, 2, 8, 121)
+    with sd.EkfSlam(3 + 2 * 60) as bad:
+        bad.set_option("active_bound", 0)
+        bad.set_state_diag(s[0], s[1])
+        bad.step(s[2][0], s[3][0], s[4][0], s[5][0], s[6][0])
+        bad.sync()
+        bad.set_option("fused_step", 2)
+        bad.step(s[2][1], s[3][1], s[4][1], s[5][1], s[6][1])
+        T = (C.c_double * 3)(0.1, 0.2, 0.3)
+        assert lib.ekf_transform(bad._h, 0, 1, T, None) == EKF_ERR_STATE
+        assert b"ekf_transform: trajectory 0 carries EKF_FLAG_INTERNAL" in lib.ekf_last_error(bad._h)
+        assert bad.flags(0) & eb.EKF_FLAG_INTERNAL and bad.size() == 103

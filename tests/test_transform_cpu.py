@@ -1,0 +1,251 @@
+"""CPU: the change of frame (EkfSlam.transform, ekf_transform) without a device -- the model (tests/transform_model.py)
+against the independent join model and a dense J P J^T, its group properties, frontend.fit_transform, the "align, then
+anchor" story on the models, plan_transform and the tile enumeration of k_transform under the sanitizers
+(tests/transform_plan_check.cpp), the binding's argument staging with a fake library and the C ABI's argument errors.
+
+Tolerance between two evaluations of the same formulas: entrywise 1e-13 x bound, bound = |J| |P| |J|^T + |A| |Sigma| |A|^T
+(an entry is at most 13 three-factor products: gamma_40 ~ 4.4e-15 of the bound)."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import direct_model as dm
+from tests import join_model as jm
+from tests import transform_model as tm
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TOL = 1e-13
+CHI2_4_099 = 13.276704135987622        # the 0.99 quantile of chi-square with 4 degrees of freedom
+
+
+def close(got, ref, bound, label):
+    e = np.abs(got - ref)
+    print(f"{label}: worst error / bound {float(np.max(e / np.where(bound > 0, bound, 1.0))) if e.size else 0.0:.3g}")
+    return bool((e <= TOL * bound).all())
+
+
+# ---- the model against the join model and a dense product -----------------------------------------------------------------
+@pytest.mark.parametrize("N", [1, 5, 40])
+@pytest.mark.parametrize("with_cov", [False, True])
+def test_against_the_join_model(N, with_cov):
+    """Joining state B onto an empty state (n = 3) in explicit mode is the landmark part of transform(B); the pose rows
+    against J P J^T + A Sigma A^T written out densely."""
+    rng = np.random.default_rng(100 + N)
+    xB, PB = jm.random_state(rng, N)
+    T, cT = jm.random_frame(rng)
+    cov = cT if with_cov else None
+    xA, PA = np.array([0.2, -0.1, 0.4]), np.diag([0.1, 0.2, 0.05])
+    xj, Pj, _, _ = jm.join_dense(xA, PA, xB, PB, T, np.zeros((3, 3)) if cov is None else cov)
+    x, P, bound, mb = tm.transform_dense(xB, PB, T, cov)
+    assert close(P[3:, 3:], Pj[3:, 3:], bound[3:, 3:], f"N {N} cov {with_cov} landmarks") and close(x[3:], xj[3:], mb[3:], "means")
+    # the whole state densely
+    n = 3 + 2 * N
+    R = tm.rot(T[2])
+    J, A = np.zeros((n, n)), np.zeros((n, 3))
+    J[:2, :2], J[2, 2] = R, 1.0
+    A[:2, :2], A[:2, 2], A[2, 2] = np.eye(2), tm.J2 @ R @ xB[:2], 1.0
+    for j in range(N):
+        s = slice(3 + 2 * j, 5 + 2 * j)
+        J[s, s] = R
+        A[s, :2], A[s, 2] = np.eye(2), tm.J2 @ R @ xB[s]
+    Pd = J @ PB @ J.T + (A @ cov @ A.T if with_cov else 0.0)
+    assert close(P, Pd, bound, "dense")
+    assert (np.abs(x[:2] - (T[:2] + R @ xB[:2])) <= TOL * mb[:2]).all() and x[2] == xB[2] + T[2]
+    assert (bound >= np.abs(P) * (1 - 1e-12)).all() and (mb >= np.abs(x) * (1 - 1e-12)).all()
+
+
+# ---- group properties ----------------------------------------------------------------------------------------------------
+def test_group_properties():
+    rng = np.random.default_rng(11)
+    x, P = jm.random_state(rng, 12, never_observed=7)
+    T1, T2 = np.array([5.0, -3.0, 1.0]), np.array([-0.7, 0.4, -2.9])
+    x1, P1, b1, m1 = tm.transform_dense(x, P, T1)
+    xb, Pb, b2, m2 = tm.transform_dense(x1, P1, tm.inverse(T1))
+    assert close(Pb, P, b2, "T then its inverse") and close(xb, x, m2 + m1, "mean")
+    x2, P2, b3, m3 = tm.transform_dense(x1, P1, T2)
+    xc, Pc, bc, mc = tm.transform_dense(x, P, tm.compose(T2, T1))
+    assert close(P2, Pc, b3 + bc, "two transforms against their composition") and close(x2, xc, m3 + mc, "mean")
+    x0, P0, _, _ = tm.transform_dense(x, P, np.zeros(3))
+    assert np.array_equal(x0, x) and np.array_equal(P0, P)                  # the identity, bit for bit
+    for T, cov in ((T1, None), (T2, jm.random_frame(rng)[1])):
+        _, Pn, _, _ = tm.transform_dense(x, P, T, cov)
+        assert np.allclose(Pn, Pn.T, rtol=0, atol=1e-12 * np.abs(Pn).max())
+        np.linalg.cholesky((Pn + Pn.T) / 2)                                  # raises unless positive definite
+    i = 3 + 2 * 7                                                            # the never-observed landmark stays uncorrelated
+    assert not P1[i:i + 2, :i].any() and not P1[i:i + 2, i + 2:].any() and not np.signbit(P1[i:i + 2, :i]).any()
+
+
+# ---- fit_transform --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", [2, 3, 50])
+@pytest.mark.parametrize("phi", [1e-3, np.pi / 2 - 1e-3, -np.pi / 2 + 1e-3, np.pi - 1e-3, -np.pi + 1e-3, 0.0, np.pi / 2, -np.pi / 2])
+def test_fit_recovers_a_known_transform(k, phi):
+    from slam_duckietown_amd.frontend import fit_transform
+    rng = np.random.default_rng(k)
+    src = rng.uniform(-3.0, 3.0, (k, 2))
+    T = np.array([5.0, -3.0, phi])
+    dst = T[:2] + src @ tm.rot(phi).T
+    got, cov = fit_transform(src, dst, rng.uniform(0.5, 2.0, k))
+    print(f"k {k} phi {phi}: error {np.abs(got - T).max():.3g}")
+    assert np.abs(got - T).max() <= 1e-12 and cov.shape == (3, 3) and np.array_equal(cov, cov.T)
+    np.linalg.cholesky(cov)
+
+
+def test_fit_weights_and_covariance():
+    from slam_duckietown_amd.frontend import fit_transform
+    rng = np.random.default_rng(5)
+    src = rng.uniform(-2.0, 2.0, (6, 2))
+    T = np.array([0.4, 0.2, 0.3])
+    dst = T[:2] + src @ tm.rot(T[2]).T
+    bad = dst.copy()
+    bad[0] += [1.0, -1.0]                                                    # one outlier
+    light = fit_transform(src, bad, [1e-6, 1, 1, 1, 1, 1])[0]
+    even = fit_transform(src, bad)[0]
+    heavy = fit_transform(src, bad, [1e6, 1, 1, 1, 1, 1])[0]
+    assert np.abs(light - T).max() < 1e-5 < 0.05 < np.abs(even - T).max() < np.abs(heavy - T).max()
+    r = bad[0] - (heavy[:2] + tm.rot(heavy[2]) @ src[0])
+    assert np.abs(r).max() < 1e-4                                            # the heavy point is fitted
+    # the covariance: the inverse of the Hessian of half the cost at the fit (zero residuals: Gauss-Newton's is the exact one).
+    # Central differences with h = 1e-3: truncation ~ h^2 / 12 of a fourth derivative of size |H|, 1e-7 |H|; rounding
+    # ~ eps cost / h^2 with cost ~ 0 at the fit: together well below the 1e-5 asked here
+    w = rng.uniform(0.5, 2.0, 6)
+    got, cov = fit_transform(src, dst, w)
+
+    def half_cost(p):
+        res = dst - (p[:2] + src @ tm.rot(p[2]).T)
+        return 0.5 * float((w * (res ** 2).sum(1)).sum())
+
+    h, H = 1e-3, np.zeros((3, 3))
+    for a in range(3):
+        for b in range(3):
+            ea, eb = np.eye(3)[a] * h, np.eye(3)[b] * h
+            H[a, b] = (half_cost(got + ea + eb) - half_cost(got + ea - eb) - half_cost(got - ea + eb) + half_cost(got - ea - eb)) / (4 * h * h)
+    print("cov x Hessian:", cov @ H)
+    assert np.allclose(cov @ H, np.eye(3), rtol=0, atol=1e-5)
+
+
+def test_fit_refuses_bad_input():
+    from slam_duckietown_amd.frontend import fit_transform
+    p = np.array([[0.0, 0.0], [1.0, 0.0], [0.0, 2.0]])
+    for src, dst, w in ((p[:1], p[:1], None), (p[[0, 0]], p[:2], None), (p[:2], p[[1, 1]], None), (p, p[:2], None), (p, p, [1.0, 1.0]),
+                        (p * np.nan, p, None), (p, p + np.inf, None), (p, p, [1.0, np.nan, 1.0]), (p, p, [1.0, 0.0, 0.0]), (p, p, [1.0, -1.0, 1.0])):
+        with pytest.raises(ValueError):
+            fit_transform(src, dst, w)
+    T, _ = fit_transform(p, p)
+    assert np.abs(T).max() <= 1e-15
+
+
+# ---- align, then anchor: on the models ------------------------------------------------------------------------------------
+def stacked_nis(x, P, anchors, survey, R):
+    return dm.direct_update(x, P, list(anchors), [survey[j] for j in anchors], [R] * len(anchors))[2]
+
+
+def test_align_then_anchor_on_the_models():
+    """tm.align_case: a mapped state in its own frame and a survey 5 m, -3 m and 1 rad away.  Anchoring two landmarks fails the
+    chi-square gate before the alignment and passes it afterwards; after the anchor the landmark means lie on the survey as
+    well as a rigid alignment of the unaligned map would have put them (x ALIGN_MARGIN)."""
+    from slam_duckietown_amd.evaluation import ate_rmse
+    from slam_duckietown_amd.frontend import fit_transform
+    c = tm.align_case()
+    x, P, survey, anchors, R = c["x"], c["P"], c["survey"], c["anchors"], c["R"]
+    before = stacked_nis(x, P, anchors, survey, R)
+    T, _ = fit_transform(x[3:].reshape(-1, 2), survey)
+    assert np.abs(T - tm.ALIGN_FRAME).max() < 0.5
+    xa, Pa, _, _ = tm.transform_dense(x, P, T)
+    after = stacked_nis(xa, Pa, anchors, survey, R)
+    print(f"stacked NIS of the two anchors: {before:.4g} before the alignment, {after:.4g} after (quantile {CHI2_4_099:.4g})")
+    assert before > CHI2_4_099 > after
+    xf, Pf, _, _, applied = dm.direct_update(xa, Pa, list(anchors), [survey[j] for j in anchors], [R] * 2, gate=CHI2_4_099)
+    assert applied
+    e_aligned = ate_rmse(x[3:].reshape(-1, 2), survey, align=True)
+    e_final = ate_rmse(xf[3:].reshape(-1, 2), survey)
+    print(f"ate: {e_aligned:.4g} with align=True before, {e_final:.4g} without after align + anchor")
+    assert e_final <= tm.ALIGN_MARGIN * e_aligned
+
+
+# ---- the host plan under the sanitizers -----------------------------------------------------------------------------------
+def test_plan_transform_under_the_sanitizers(tmp_path):
+    if shutil.which("g++") is None:
+        pytest.skip("g++ is not available")
+    exe = tmp_path / "transform_plan_check"
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DEKF_HOST_ONLY",
+           "-Wall", "-Werror", "-I", os.path.join(ROOT, "slam-duckietown_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
+           os.path.join(ROOT, "tests", "transform_plan_check.cpp"), "-o", str(exe)]
+    built = subprocess.run(cmd, capture_output=True, text=True)
+    assert built.returncode == 0, built.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600,
+                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "checks passed" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    api = open(os.path.join(ROOT, "slam-duckietown_amd", "csrc", "ekf_api.hip")).read()
+    assert re.search(r"\bplan_transform\(", api) and not re.search(r"^(static|inline)[^\n;]*\bplan_transform\(", api, flags=re.M)
+    assert re.search(r"DeviceBuf<double> dtf_frame;", api) and re.search(r"DeviceBuf<int> dtf_tab;", api)
+    mk = open(os.path.join(ROOT, "slam-duckietown_amd", "csrc", "Makefile")).read()
+    assert "ekf_transform.hip" in mk
+
+
+# ---- the binding and the ABI ----------------------------------------------------------------------------------------------
+def test_binding_stages_frames_without_a_device():
+    """transform hands (b0, count, T, cov) to the library in the C ABI's order, broadcasts one frame over the bank, and the
+    host-side association tables follow; align_landmarks fits the means and passes no covariance."""
+    from slam_duckietown_amd import ekf_bindings as eb
+    import slam_duckietown_amd as sd
+    assert eb.ABI["ekf_transform"][1] == [C.c_void_p, C.c_int, C.c_int, eb._dp, eb._dp]
+    assert sd.fit_transform is sd.frontend.fit_transform
+    seen = []
+    means = {1: np.r_[0.1, 0.2, 0.3, 1.0, 0.0, 0.0, 2.0, -1.0, -1.0]}
+
+    class Lib:
+        def ekf_transform(self, h, b0, count, T, cov):
+            seen.append((h, b0, count, [T[i] for i in range(3 * count)], None if cov is None else [cov[i] for i in range(9 * count)]))
+            return 0
+
+        def ekf_state_size(self, h, b, out):
+            out._obj.value = 9
+            return 0
+
+    f = eb.EkfSlam.__new__(eb.EkfSlam)
+    f._lib, f._h, f.batch = Lib(), "F", 3
+    f._host_index = {1: {7: 0, 9: 1}}
+    f._host_tags = {1: {0: [1.0, 2.0, 0.5, 7, 0.3, 0.1]}}
+    f.mean = lambda b=0: means[b]
+    f.transform([1.0, 2.0, 0.5])
+    assert seen.pop() == ("F", 0, 3, [1.0, 2.0, 0.5] * 3, None)
+    c, s = np.cos(0.5), np.sin(0.5)
+    assert np.allclose(f._host_tags[1][0][:2], [1.0 + c * 1.0 - s * 2.0, 2.0 + s * 1.0 + c * 2.0], rtol=0, atol=1e-15)
+    assert f._host_tags[1][0][2:] == [0.5, 7, 0.3, 0.1] and f._host_index == {1: {7: 0, 9: 1}}
+    cov = np.diag([0.1, 0.2, 0.3])
+    f.transform(np.zeros(3), cov=cov, b=2)
+    assert seen.pop() == ("F", 2, 1, [0.0] * 3, cov.ravel().tolist())
+    f.transform(np.arange(9.0).reshape(3, 3), cov=np.stack([cov, 2 * cov, 3 * cov]))
+    assert seen.pop() == ("F", 0, 3, list(np.arange(9.0)), np.stack([cov, 2 * cov, 3 * cov]).ravel().tolist())
+    for bad in (dict(T=np.zeros(2)), dict(T=np.zeros((2, 3))), dict(T=np.zeros(3), cov=np.zeros((2, 3, 3))), dict(T=np.zeros((3, 3)), b=0)):
+        with pytest.raises(ValueError):
+            f.transform(**bad)
+    assert not seen
+    R = tm.rot(np.pi / 2)
+    survey = np.array([5.0, -3.0]) + means[1][3:7].reshape(2, 2) @ R.T
+    T = f.align_landmarks([0, 1], survey, b=1)
+    assert np.abs(T - [5.0, -3.0, np.pi / 2]).max() < 1e-12
+    h, b0, count, Ts, cv = seen.pop()
+    assert (h, b0, count, cv) == ("F", 1, 1, None) and Ts == list(T)
+    with pytest.raises(eb.EkfError):
+        f.align_landmarks([0, 3], survey, b=1)
+    f._h = None                                                              # (nothing to destroy)
+
+
+def test_argument_errors_need_no_device():
+    """The C ABI refuses a NULL handle before it touches a device, and the symbol is exported and declared."""
+    import __graft_entry__ as ge
+    import slam_duckietown_amd as sd
+    if not os.path.exists(sd.library_path()):
+        ge.build()
+    lib = sd.load_library()
+    assert lib.ekf_transform(None, 0, 0, None, None) == -1
+    header = open(os.path.join(ROOT, "include", "ekfslam_hip.h")).read()
+    assert "int ekf_transform(ekf_handle *h, int b0, int count, const double *T" in header
+    assert "class 8 of ekf_profile_read_class" in header

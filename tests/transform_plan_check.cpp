@@ -1,0 +1,186 @@
+// Sanitizer build of plan_transform and the tile enumeration of k_transform (slam-duckietown_amd/csrc/ekf_host_plan.h), the
+// host-side validation and launch table of ekf_transform:
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DEKF_HOST_ONLY
+//       -I slam-duckietown_amd/csrc -I include tests/transform_plan_check.cpp -o transform_plan_check
+// Every refusal the header lists, the table of accepted calls, the tile counts at N = 0, 30, 31, 32, 63 and 2048, and the
+// enumeration transform_tiles / transform_tile / transform_writes (the integer functions the kernel calls): over those sizes,
+// several active bounds and both layouts, the tiles' item pairs cover every upper-triangle item pair whose column item lies
+// inside the bound, and every diagonal pair, exactly once -- but the pose block, which the launch's extra workgroup writes --
+// and nothing else; expanded to entries, every address lies inside the allocation and no two entries share one.  Any sanitizer
+// report or failed check ends the run with a non-zero status.  tests/test_transform_cpu.py builds and runs it (CPU only).
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <limits>
+#include <vector>
+
+#include "ekf_host_plan.h"
+
+using namespace ekf;
+
+static long checks = 0;
+#define CHECK(cond, ...)                                              \
+  do {                                                                \
+    ++checks;                                                         \
+    if (!(cond)) {                                                    \
+      std::fprintf(stderr, "FAILED %s:%d: %s  [", __FILE__, __LINE__, #cond); \
+      std::fprintf(stderr, __VA_ARGS__);                              \
+      std::fprintf(stderr, "]\n");                                    \
+      std::exit(1);                                                   \
+    }                                                                 \
+  } while (0)
+
+static HostPlan bank(int n_max, std::vector<int> n, std::vector<int> neff = {}) {
+  HostPlan h;
+  h.n_max = n_max;
+  h.rows = (n_max + 63) / 64 * 64;
+  h.ld = h.rows;
+  if (n_max <= 4096) {
+    int p2 = 64;
+    while (p2 < n_max) p2 *= 2;
+    h.ld = p2;
+  }
+  h.batch = (int)n.size();
+  h.pstride = p_alloc(h.rows, h.ld);
+  h.n = n;
+  h.neff = neff.empty() ? n : neff;
+  h.neff_enq = h.neff;
+  return h;
+}
+
+// the item pairs and the entries the launch writes for one trajectory, by the kernel's own enumeration
+static void enumerate(int N, int Ma, const HostPlan& h) {
+  const int n = 3 + 2 * N, M = 1 + N;
+  std::vector<unsigned char> pair((size_t)M * M, 0), hit((size_t)n * n, 0), addr((size_t)h.pstride, 0);
+  const int tiles = transform_tiles(M, Ma);
+  for (int t = 0; t < tiles; ++t) {
+    int ib = -1, jb = -1;
+    transform_tile(Ma, t, &ib, &jb);
+    CHECK(ib >= 0 && ib <= jb && jb * JOIN_ITEMS < M, "N %d Ma %d: tile %d -> (%d, %d)", N, Ma, t, ib, jb);
+    for (int lane = 0; lane < JOIN_ITEMS; ++lane)
+      for (int row = 0; row < JOIN_ITEMS; ++row) {
+        const int I = ib * JOIN_ITEMS + row, J = jb * JOIN_ITEMS + lane;
+        if (J >= M || J < 1 || I > J || !transform_writes(Ma, I, J)) continue;
+        CHECK(!pair[(size_t)I * M + J], "N %d Ma %d: item pair (%d, %d) twice", N, Ma, I, J);
+        pair[(size_t)I * M + J] = 1;
+        const int i0 = I == 0 ? 0 : 1 + 2 * I, ni = I == 0 ? 3 : 2, j0 = 1 + 2 * J;
+        for (int a = 0; a < ni; ++a)
+          for (int b = 0; b < 2; ++b) {
+            const int i = i0 + a, j = j0 + b;
+            if (i > j) continue;                       // (a diagonal block's entry below the diagonal)
+            CHECK(i < n && j < n, "entry (%d, %d) outside n = %d", i, j, n);
+            CHECK(!hit[(size_t)i * n + j], "entry (%d, %d) written twice", i, j);
+            hit[(size_t)i * n + j] = 1;
+            const long at = p_index(h.ld, i, j);
+            CHECK(at >= 0 && at < h.pstride, "address of (%d, %d) outside the allocation", i, j);
+            CHECK(!addr[(size_t)at], "address of (%d, %d) shared", i, j);
+            addr[(size_t)at] = 1;
+          }
+      }
+  }
+  for (int I = 0; I < M; ++I)
+    for (int J = 0; J < M; ++J) {
+      const bool want = I <= J && J >= 1 && (I == J || J < Ma);   // (0, 0): the extra workgroup
+      CHECK(pair[(size_t)I * M + J] == (want ? 1 : 0), "N %d Ma %d: item pair (%d, %d) %s", N, Ma, I, J,
+            want ? "is not visited" : "is visited");
+    }
+  const int na = Ma >= M ? n : 1 + 2 * Ma;             // entries inside the bound: columns below na
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) {
+      const bool same_item = i >= 3 && j >= 3 && (i - 3) / 2 == (j - 3) / 2;
+      const bool want = i <= j && j >= 3 && (j < na || same_item);
+      CHECK(hit[(size_t)i * n + j] == (want ? 1 : 0), "N %d Ma %d: entry (%d, %d) %s", N, Ma, i, j, want ? "is not written" : "is written");
+    }
+}
+
+int main() {
+  const double inf = std::numeric_limits<double>::infinity(), nan = std::nan("");
+  HostPlan h = bank(3 + 2 * 40, {3 + 2 * 10, 3, 3 + 2 * 40, 3 + 2 * 33}, {3 + 2 * 4, 3, 3 + 2 * 40, 3 + 2 * 31});
+  const std::vector<double> T{0.5, -1.0, 0.3, 0.0, 0.0, 0.0, 1.0, 2.0, -3.0, 0.0, 0.0, 1e-300};
+  std::vector<double> cov(36, 0.0);
+  {
+    const double c[9] = {0.04, 0.01, 0.0, 1e300, 0.09, -0.002, 1e300, 1e300, 0.001};   // below the diagonal: never read
+    for (int i = 0; i < 9; ++i) cov[i] = cov[18 + i] = c[i];
+  }
+  TransformPlan tp;
+  // ---- accepted calls ----
+  CHECK(plan_transform(&h, 0, 4, T.data(), nullptr, tp) == nullptr, "the good call");
+  {
+    const int want[16] = {0, 10, 5, 1, 1, 0, 1, 0, 2, 40, 41, 1, 3, 33, 32, 1};
+    for (int i = 0; i < 16; ++i) CHECK(tp.tab[i] == want[i], "table word %d = %d", i, tp.tab[i]);
+    CHECK(tp.applied == 3 && !tp.with_cov && tp.tiles_hi == 3, "applied %d tiles %d", tp.applied, tp.tiles_hi);
+    CHECK(tp.head[0] == 0.5 && tp.head[2] == 0.3 && tp.head[3] == 0.0 && tp.head[4] == 0.0 && tp.head[2 * TF_HEAD + 2] == -3.0, "heads");
+    CHECK(transform_tiles(34, 32) == 2 && transform_tiles(41, 41) == 3, "tiles of trajectories 3 and 2");
+  }
+  CHECK(plan_transform(&h, 0, 4, T.data(), cov.data(), tp) == nullptr, "with a covariance");
+  CHECK(tp.with_cov && tp.applied == 4 && tp.tab[2] == 11 && tp.tab[TF_WORDS + 3] == 1 && tp.tab[3 * TF_WORDS + 2] == 34, "every item active");
+  CHECK(tp.head[3] == 1.0 && tp.head[4] == 0.04 && tp.head[5] == 0.01 && tp.head[7] == 0.01 && tp.head[9] == -0.002 && tp.head[11] == -0.002 &&
+            tp.head[12] == 0.001 && tp.head[TF_HEAD + 4] == 0.0,
+        "the covariance, mirrored from the upper triangle");
+  CHECK(plan_transform(&h, 1, 1, T.data() + 3, nullptr, tp) == nullptr && tp.applied == 0 && tp.tiles_hi == 0, "the identity alone");
+  CHECK(plan_transform(&h, 3, 1, T.data() + 9, nullptr, tp) == nullptr && tp.applied == 1, "a denormal angle is a transform");
+  CHECK(plan_transform(&h, 0, 0, nullptr, nullptr, tp) == nullptr && tp.tab.empty(), "count = 0");
+  CHECK(plan_transform(&h, 4, 0, nullptr, nullptr, tp) == nullptr, "count = 0 at the end of the bank");
+  {
+    HostPlan off = h;
+    off.opt_active_bound = 0;
+    CHECK(plan_transform(&off, 0, 1, T.data(), nullptr, tp) == nullptr && tp.tab[2] == 11, "active_bound off: the whole state");
+    std::vector<double> sing(9, 0.0);                  // rank 1: a a^T with a = (0.5, 1, 2), exact in floating point
+    const double a[3] = {0.5, 1.0, 2.0};
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) sing[3 * i + j] = a[i] * a[j];
+    CHECK(plan_transform(&h, 0, 1, T.data(), sing.data(), tp) == nullptr, "a singular covariance of rank 1");
+    std::vector<double> zero(9, 0.0);
+    CHECK(plan_transform(&h, 0, 1, T.data(), zero.data(), tp) == nullptr && tp.with_cov, "an all-zero covariance");
+  }
+  // ---- refusals ----
+  auto refused = [&](int b0, int count, const double* t, const double* c, const char* what) {
+    TransformPlan p;
+    CHECK(plan_transform(&h, b0, count, t, c, p) != nullptr, "%s was accepted", what);
+  };
+  refused(0, -1, T.data(), nullptr, "count < 0");
+  refused(-1, 1, T.data(), nullptr, "b0 < 0");
+  refused(4, 1, T.data(), nullptr, "b0 past the bank");
+  refused(2, 3, T.data(), nullptr, "the range runs past the bank");
+  refused(5, 0, nullptr, nullptr, "count = 0 outside the bank");
+  refused(0, 2147483647, T.data(), nullptr, "count = INT_MAX");
+  refused(0, 1, nullptr, nullptr, "NULL T");
+  refused(0, 1, nullptr, cov.data(), "NULL T with a covariance");
+  for (int k = 0; k < 3; ++k) {
+    std::vector<double> t = T;
+    t[3 + k] = k == 1 ? inf : nan;
+    refused(0, 2, t.data(), nullptr, "non-finite T");
+  }
+  { std::vector<double> c = cov; c[9 + 5] = nan; refused(0, 2, T.data(), c.data(), "NaN cov"); }
+  { std::vector<double> c = cov; c[8] = inf; refused(0, 1, T.data(), c.data(), "infinite cov"); }
+  { std::vector<double> c = cov; c[0] = -1e-9; refused(0, 1, T.data(), c.data(), "negative diagonal"); }
+  { std::vector<double> c = cov; c[1] = 0.061; refused(0, 1, T.data(), c.data(), "c01^2 > c00 c11"); }
+  { std::vector<double> c = cov; c[9 + 2] = 1e-3; refused(0, 2, T.data(), c.data(), "an off-diagonal entry with a zero diagonal"); }
+  { const double c[9] = {1, 0.9, -0.9, 0, 1, 0.9, 0, 0, 1}; refused(0, 1, T.data(), c, "a negative determinant"); }
+  { std::vector<double> c = cov; c[3] = nan; c[6] = -inf;
+    CHECK(plan_transform(&h, 0, 1, T.data(), c.data(), tp) == nullptr, "below the diagonal is ignored"); }
+
+  // ---- tile counts ----
+  {
+    const int Ns[6] = {0, 30, 31, 32, 63, 2048}, want[6] = {1, 1, 1, 3, 3, 2145};
+    for (int i = 0; i < 6; ++i) {
+      CHECK(transform_tiles(1 + Ns[i], 1 + Ns[i]) == want[i], "N = %d: %d tiles", Ns[i], transform_tiles(1 + Ns[i], 1 + Ns[i]));
+      HostPlan one = bank(4099, {3 + 2 * Ns[i]});
+      CHECK(plan_transform(&one, 0, 1, T.data(), nullptr, tp) == nullptr && tp.tiles_hi == want[i] && tp.tiles_hi + 1 <= 65535, "grid");
+    }
+    CHECK(transform_tiles(2049, 1) == 1 + 64 && transform_tiles(2049, 33) == 3 + 63 && transform_tiles(64, 32) == 2, "diagonal tiles beyond the bound");
+  }
+  // ---- the enumeration: row-major (ld <= 4096) and column panels (n_max = 4099: ld = 4160, two panels) ----
+  {
+    const int Ns[6] = {0, 30, 31, 32, 63, 70};
+    for (int N : Ns)
+      for (int Ma = 1; Ma <= 1 + N; ++Ma) enumerate(N, Ma, bank(3 + 2 * N, {3}));
+    HostPlan big = bank(4099, {3});
+    CHECK(p_panels(big.ld) == 2, "two column panels");
+    const int Mas[5] = {1, 33, 2047, 2048, 2049};
+    for (int Ma : Mas) enumerate(2048, Ma, big);
+    enumerate(70, 71, big);
+  }
+  std::printf("%ld checks passed\n", checks);
+  return 0;
+}
