@@ -18,6 +18,11 @@ classes by the state the call found -- active before the call (the pieces above)
 (own block within 32 eps landmark_init_var, mean within 1e-9, cross terms exact zeros for a direct fix and entrywise for a dense
 H), never observed and not named (mean, variance and whole rows bit for bit, exact zeros) -- and P must be exactly symmetric.
 
+`assert_state_close` judges a WHOLE state after any sequence of calls against a dense model fed the same calls: the landmarks
+are classed by the model's state, not by history -- loose (both variances still at or above half of landmark_init_var: own block
+within 32 eps landmark_init_var, mean within 1e-9, cross terms exactly zero where the model's are, entrywise elsewhere) and
+informed (with the pose: the pieces above) -- plus exact symmetry, size, tag index and flags.
+
 Every assertion message names the piece and the measured value.  A plain module (not a conftest): tests import it.
 """
 import numpy as np
@@ -215,6 +220,81 @@ def assert_update_close(got, want, before, touched, init_var, tol, what="", entr
             nz = np.count_nonzero(rows)
             assert nz == 0, f"{what}never-observed cross terms: {nz} non-zero entries in rows {r[0]}..{r[-1]}"
     return err
+
+
+STATE_PIECES = PIECES + ("loose_block", "loose_mean", "loose_cross")
+
+
+def loose_landmarks(P, init_var):
+    """(loose, informed) landmarks of a state by the state itself: loose = both variances at or above half of `init_var`
+    (never informed by anything: a prior), informed = the rest."""
+    d = np.diag(np.asarray(P))
+    is_loose = (d[3::2] >= 0.5 * init_var) & (d[4::2] >= 0.5 * init_var)
+    lms = np.arange(len(is_loose))
+    return lms[is_loose], lms[~is_loose]
+
+
+def state_errors(got, want, init_var):
+    """What `assert_state_close` measures, without judging it: (mean, P) `got` against (mean, P) `want`, the landmarks classed
+    by `want`.  -> {piece: value}: PIECES on the pose and the informed landmarks; for the loose ones loose_block (own 2 x 2
+    blocks, absolute), loose_mean (relative to max(1, |mean|)), loose_cross (max |dP_ij| / sqrt(wP_ii wP_jj) over their rows,
+    the own block apart, where `want` is not exactly zero) and loose_zeros (entries of those rows that are exactly zero in
+    `want` and not in `got`)."""
+    mu, P = np.asarray(got[0], dtype=float), np.asarray(got[1], dtype=float)
+    wm, wP = np.asarray(want[0], dtype=float), np.asarray(want[1], dtype=float)
+    loose, informed = loose_landmarks(wP, init_var)
+    act = np.concatenate([np.arange(3), landmark_rows(informed)]).astype(np.int64)
+    err = active_errors(mu[act], P[np.ix_(act, act)], wm[act], wP[np.ix_(act, act)])
+    if len(loose):
+        rows = landmark_rows(loose)
+        err["loose_block"] = max(float(np.abs(P[a:a + 2, a:a + 2] - wP[a:a + 2, a:a + 2]).max()) for a in 3 + 2 * loose)
+        err["loose_mean"] = max(float(np.abs(mu[a:a + 2] - wm[a:a + 2]).max() / max(1.0, np.abs(wm[a:a + 2]).max()))
+                                for a in 3 + 2 * loose)
+        g, w = P[rows].copy(), wP[rows].copy()
+        for i, r in enumerate(rows):                      # (the own block is judged above)
+            a = 3 + 2 * ((r - 3) // 2)
+            g[i, a:a + 2] = w[i, a:a + 2] = 0.0
+        zero = w == 0.0
+        err["loose_zeros"] = int(np.count_nonzero(g[zero]))
+        dev = np.abs(g - w) / np.sqrt(np.outer(np.diag(wP)[rows], np.diag(wP)))
+        err["loose_cross"] = float(dev[~zero].max()) if (~zero).any() else 0.0
+    return err
+
+
+def assert_state_close(got, model_state, init_var, tol=1e-9, entry_tol=None, what=""):
+    """A WHOLE state after any sequence of calls: `got` = (mean, P, tag index, flags) of a filter against `model_state` =
+    (mean, P, tag index) of the dense model fed the same calls.  The landmarks are classed by the model's state, not by
+    history (loose_landmarks); returns {piece: measured value}.
+
+    informed landmarks, and the pose: the six PIECES of `active_errors`, each below `tol` (and the 1e-6 bar);
+    loose landmarks: own 2 x 2 block within 32 eps init_var absolutely, mean within 1e-9 relatively (loose_block, loose_mean:
+      `assert_update_close`'s rule for a first-touched landmark); cross terms (loose_cross) exactly zero wherever the model's
+      entry is exactly zero, elsewhere max |dP_ij| / sqrt(P_ii P_jj) below `entry_tol` (a transform with a covariance, a
+      predict_dense: a prior of 1e4 carries correlations, and every later update cancels against it);
+    the whole state: P exactly symmetric, size and tag index equal to the model's, flags 0."""
+    mu, P, tags, flags = got
+    wm, wP, wtags = model_state
+    mu, P = np.asarray(mu), np.asarray(P)
+    n = len(wm)
+    assert len(mu) == n and P.shape == (n, n), f"{what}size: a state of {len(mu)} ({P.shape}) where the model has {n}"
+    assert flags == 0, f"{what}flags: {flags:#x}"
+    assert dict(tags) == dict(wtags), f"{what}tags: tag index {dict(tags)} where the model has {dict(wtags)}"
+    assert np.array_equal(P, P.T), f"{what}asymmetry: P != P^T"
+    err = state_errors((mu, P), (wm, wP), init_var)
+    check_errors(err, tol, what)
+    if "loose_block" in err:
+        eps_v = 32 * np.finfo(float).eps * init_var
+        assert err["loose_block"] <= eps_v, f"{what}loose_block: {err['loose_block']:.3e} exceeds 32 eps init_var = {eps_v:.3e}"
+        assert err["loose_mean"] <= 1e-9, f"{what}loose_mean: {err['loose_mean']:.3e} exceeds 1e-9"
+        assert err["loose_zeros"] == 0, f"{what}loose_cross: {err['loose_zeros']} entries non-zero where the model holds exact zeros"
+        if err["loose_cross"] > 0.0:
+            assert entry_tol is not None and err["loose_cross"] < entry_tol and err["loose_cross"] < REL_TOL, \
+                f"{what}loose_cross: {err['loose_cross']:.3e} exceeds " + ("no bound given" if entry_tol is None else f"{entry_tol:g}")
+    return err
+
+
+def fmt_state(err):
+    return " ".join(f"{k}={err[k]:.2e}" for k in STATE_PIECES if k in err)
 
 
 def fmt_update(err):

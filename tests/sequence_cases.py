@@ -1,0 +1,264 @@
+"""The table of tests/test_gpu_sequence_pairs.py and tests/test_sequence_cpu.py: every ORDERED PAIR of state-changing calls.
+
+Each call of the handle is tested against its own dense model; what the calls share is the per-trajectory bookkeeping of
+csrc/ekf_api.hip (size, the active bound and its mirrors, pending ranks and pose noise, the tag row, the stream, the tables of
+copy / join / transform), and a mirror left stale by one call shows only in the NEXT call that trusts it.  So: a start with ranks
+pending, operation A, operation B, then a continuation (a step and a stream) whose covariance pass reads whatever A and B left
+-- judged after each of the three against ONE dense model of the whole sequence (tests/sequence_model.py), block by block
+(parity_blocks.assert_state_close).  225 pairs, each with a name.
+
+START: direct_model.small_stream at N = 30 -- synthetic_stream(26, 31, 4, seed) over landmarks 0 .. 25, landmarks 26 .. 29 never
+observed at landmark_init_var: n = 63, one column short of the 64-column tile edge of the general kernels, so that growth
+(add_landmarks, join, a window) crosses it.  n_max = 79 (38 landmarks; the largest pair, join + join, reaches 36): the
+small-state path by default, the general kernels under `both_paths`.  Prelude: run_stream of 28 steps, then THREE single steps
+-- all 31 of the stream.  (Two were planned, so that ranks are pending on the general kernels when A starts; but 28 stream steps
+of m = 4 are cadences of 10, 10 and 8 steps, the last one's 64 ranks stay pending, and the second single step fills the 80 of
+"rank_limit": the pass runs behind it and NOTHING is pending.  The third step's 8 ranks are.)
+
+An operation is a function (driver, rng): it draws its arguments from the MODEL's current state -- so it stays valid after a
+renumbering -- and issues the calls through the driver, which hands each to the model and to whatever runs beside it (a filter,
+the model in another precision).  Every argument is therefore the same float64 value for all of them."""
+import functools
+
+import numpy as np
+
+from oracle import ekf_oracle as orc
+from tests import direct_model as dm
+from tests import fuzz_model as fz
+from tests import linear_model as lm
+from tests import motion_model as mm
+from tests import parity_blocks as pb
+from tests import sequence_model as sm
+from tests.test_gpu_join import FRAME, stream_from
+
+INIT_VAR = orc.EkfConfig().landmark_init_var
+N_OBSERVED, N_LANDMARKS, N_MAX = 26, 30, 79
+STREAM_STEPS, SINGLE_STEPS = 28, 3
+SEED = 7
+TOL = 1e-9              # every piece of the informed part against the model (parity_blocks' default against the oracle)
+FLOOR_TOL = 1e-11       # admissibility: the model in float64 against itself in longdouble, every relative-Frobenius piece
+# ENTRY_TOL: the bound of the loose landmarks' cross terms = 10 x the worst entrywise piece (corr_max, mean_landmarks,
+# loose_cross) of the float64 model against the longdouble one over all 225 cases -- the margin update_cases.DENSE_NEVER
+# takes over its own measurement.  tests/test_sequence_cpu.py repeats the measurement and holds this constant to it;
+# profiles/sequence_pairs.txt has the figures.
+ENTRY_FLOOR = 4.0e-11     # measured 3.78e-11: corr_max of "remove_landmarks then update_direct" after the continuation
+ENTRY_TOL = 10 * ENTRY_FLOOR
+
+TAG0 = 100              # landmark j of the start carries tag TAG0 + j
+T_PLAIN = np.array([0.7, -0.4, -2.9])           # transform without a covariance
+T_COV = np.array([-0.3, 0.5, 0.4])              # ... and with COV
+COV = FRAME[1]
+
+
+@functools.lru_cache(maxsize=None)
+def start(seed=SEED):
+    """(mean0, diag0, lin, ang, idx, zr, zb): dm.small_stream generalised to N = 30."""
+    s = orc.synthetic_stream(N_OBSERVED, STREAM_STEPS + SINGLE_STEPS, 4, seed)
+    rng = np.random.default_rng(300 + seed)
+    extra = 2 * (N_LANDMARKS - N_OBSERVED)
+    mean0 = np.concatenate([s[0], rng.uniform(-1.0, 1.0, extra)])
+    diag0 = np.concatenate([s[1], np.full(extra, INIT_VAR)])
+    return (mean0, diag0) + tuple(s[2:])
+
+
+@functools.lru_cache(maxsize=None)
+def sources():
+    """The other handles a case reads, key -> (mean, covariance, tag index): "map3" a 3-landmark filter (join), "map12" a
+    12-landmark one (copy_from); the dense oracle's states, which a handle takes verbatim through set_state."""
+    out = {}
+    for key, (N, steps, m, seed, tag0) in {"map3": (3, 10, 3, 61, 300), "map12": (12, 12, 4, 62, 400)}.items():
+        _, om, oP = dm.run_dense(N, steps, m, seed)
+        out[key] = (om, oP, {tag0 + j: j for j in range(N)})
+    return out
+
+
+class Driver:
+    """Hands every call to the model and to the sinks beside it; operations read `model` for their arguments."""
+
+    def __init__(self, model, *sinks):
+        self.model, self.sinks = model, (model,) + sinks
+        self.calls = []
+
+    def __getattr__(self, name):
+        def call(*args, **kw):
+            self.calls.append(name)
+            for s in self.sinks:
+                getattr(s, name)(*args, **kw)
+        return call
+
+
+# ---- what the operations pick -------------------------------------------------------------------------------------------------
+def pick(tr):
+    """(an informed landmark, a loose one -- the last but one landmark where none is left --, the last landmark), distinct."""
+    loose, informed = pb.loose_landmarks(tr.cov, INIT_VAR)
+    last = tr.n_lm - 1
+    a = int(next(l for l in informed if l != last)) if len(informed) else 0
+    b = int(next((l for l in loose if l not in (a, last)), next(l for l in range(tr.n_lm - 2, -1, -1) if l != a)))
+    return a, b, last
+
+
+def observe(drv, rng, idx):
+    """One step that observes `idx`, consistently with the model's mean (lm.follow_up_obs)."""
+    zr, zb = lm.follow_up_obs(drv.model.tr.mean, idx, int(rng.integers(0, 50)))
+    drv.step1(0.004, 0.02, [int(i) for i in idx], zr, zb)
+
+
+def stream(drv, rng, steps, m):
+    st = stream_from(drv.model.tr.mean, steps, m, int(rng.integers(1 << 30)))
+    drv.run_stream(*st)
+
+
+# ---- the 15 operations --------------------------------------------------------------------------------------------------------
+def op_step(drv, rng):
+    tr = drv.model.tr
+    _, never, last = pick(tr)
+    observe(drv, rng, list(dict.fromkeys([0, never, last])))
+
+
+def op_run_stream(drv, rng):
+    stream(drv, rng, 6, 4)
+
+
+def op_step_detections(drv, rng):
+    """One known tag (the tagged landmark nearest to the pose) and one new one, two frames."""
+    tr = drv.model.tr
+    d = {t: float(np.hypot(*(tr.mean[3 + 2 * j:5 + 2 * j] - tr.mean[:2]))) for t, j in tr.tags.items()}
+    known = min(d, key=d.get)
+    assert d[known] < 1.3
+    new = next(i for i in range(600, 1024) if i not in tr.tags)
+    win = fz.window_of(rng, tr, [known, new], {new: (0.2, 0.8)}, 2)
+    drv.step_detections(0.004, 0.02, win)
+
+
+def op_predict_linear(drv, rng):
+    tr = drv.model.tr
+    drv.predict_linear(*mm.draw(rng, tr.mean, tr.cov, "full"))
+
+
+# predict_dense: F = I + DENSE_F * randn / sqrt(n), dense.  A loose landmark then carries 1e4 * F_ij ~ 0.04 against every other
+# entry (correlation 2e-3 with an informed landmark: a skipped row shows at once), and DENSE_F is as large as admissibility
+# allows: when a loose landmark correlated with another is observed, its 1e4 cancels inside the other's own block, and at
+# DENSE_F = 2e-3 the float64 model itself is 5e-10 off there -- above the 32 eps init_var the judge allows that block -- and at
+# 1e-4 a direct fix of such a landmark leaves the informed means 1.8e-10 sigma off, too near TOL.
+DENSE_F = 3e-5
+
+
+def op_predict_dense(drv, rng):
+    n = len(drv.model.tr.mean)
+    F = np.eye(n) + rng.normal(size=(n, n)) * (DENSE_F / np.sqrt(n))
+    A = rng.normal(size=(n, 3)) * 0.02
+    drv.predict_dense1(F, A @ A.T + np.diag(rng.uniform(1e-4, 1e-3, n)))
+
+
+def op_update_direct(drv, rng):
+    """A pose fix, an informed landmark and a loose one (surveyed within decimetres of its prior mean: dm.case_small).
+
+    The loose landmark's survey has sigma 0.3 .. 0.6 m.  A fix forms v - v^2 / (v + R) with v = 1e4: whatever the code, the
+    result carries up to 32 eps init_var = 7.1e-11 absolutely (assert_update_close's rule for a first-touched block).  Here the
+    fixed landmark is INFORMED afterwards and judged relatively, at TOL = 1e-9 of its variance ~ R: that can hold only for
+    R > 7.1e-11 / 1e-9 = 0.07 m^2.  (dm.make_fixes' sigma of 0.02 .. 0.1 m asks for 1e-9 of 4e-4 .. 1e-2.)"""
+    tr = drv.model.tr
+    a, never, _ = pick(tr)
+    z, R = dm.make_fixes(rng, tr.mean, tr.cov, [dm.POSE, a])
+    sig, rho = rng.uniform(0.3, 0.6, 2), rng.uniform(-0.4, 0.4)
+    Rn, zn = np.zeros((3, 3)), np.zeros(3)
+    Rn[:2, :2] = np.array([[sig[0] ** 2, rho * sig[0] * sig[1]], [rho * sig[0] * sig[1], sig[1] ** 2]])
+    zn[:2] = tr.mean[3 + 2 * never:5 + 2 * never] + np.sqrt(0.01 + sig ** 2) * rng.normal(size=2)
+    drv.update_direct([dm.POSE, a, never], z + [zn], R + [Rn])
+
+
+def op_update_linear(drv, rng):
+    """A relative constraint between an informed and a loose landmark (a dense H: the bound rises): lm.case_panel's."""
+    tr = drv.model.tr
+    a, never, _ = pick(tr)
+    offset = tr.mean[3 + 2 * never:5 + 2 * never] - tr.mean[3 + 2 * a:5 + 2 * a] + np.array([0.1, -0.2])
+    drv.update_linear(*lm.constraint_rows(a, never, offset, np.eye(2) * 0.05 ** 2))
+
+
+def op_transform(drv, rng):
+    drv.transform(T_PLAIN, None)
+
+
+def op_transform_cov(drv, rng):
+    drv.transform(T_COV, COV)
+
+
+def op_join(drv, rng):
+    drv.join("map3", None, None)
+
+
+def op_join_explicit(drv, rng):
+    drv.join("map3", FRAME[0], FRAME[1])
+
+
+def op_remove(drv, rng):
+    a, never, _ = pick(drv.model.tr)
+    drv.remove_landmarks([never, a])
+
+
+def op_add(drv, rng):
+    drv.add_landmarks(rng.uniform(-1.0, 1.0, (2, 2)))
+
+
+def op_copy(drv, rng):
+    drv.copy_in("map12")
+
+
+def op_bound_off(drv, rng):
+    drv.set_option("active_bound", 0)
+    op_step(drv, rng)
+    drv.set_option("active_bound", 1)
+
+
+OPS = (("step", op_step), ("run_stream", op_run_stream), ("step_detections", op_step_detections),
+       ("predict_linear", op_predict_linear), ("predict_dense", op_predict_dense), ("update_direct", op_update_direct),
+       ("update_linear", op_update_linear), ("transform", op_transform), ("transform(cov)", op_transform_cov),
+       ("join", op_join), ("join(explicit)", op_join_explicit), ("remove_landmarks", op_remove),
+       ("add_landmarks", op_add), ("copy_from", op_copy), ("active_bound off/on", op_bound_off))
+PAIRS = [(a, b) for a in range(len(OPS)) for b in range(len(OPS))]
+
+
+def pair_name(a, b):
+    return f"{OPS[a][0]} then {OPS[b][0]}"
+
+
+def setup(drv):
+    """What every case starts from: the block-diagonal start, the start's tags, the default active bound."""
+    s = start()
+    drv.set_option("active_bound", 1)
+    drv.set_state_diag(s[0], s[1])
+    drv.set_tag_index({TAG0 + j: j for j in range(N_LANDMARKS)})
+
+
+def prelude(drv):
+    s = start()
+    k = STREAM_STEPS
+    drv.run_stream(*[x[:k] for x in s[2:]])
+    for k in range(STREAM_STEPS, STREAM_STEPS + SINGLE_STEPS):
+        drv.step1(s[2][k], s[3][k], s[4][k], s[5][k], s[6][k])
+
+
+def continuation(drv, rng):
+    op_step(drv, rng)
+    stream(drv, rng, 4, 3)
+
+
+def run_case(drv, a, b, judge=None):
+    """setup, prelude, A, B, continuation on the driver; `judge(stage)` after the prelude ("start": before A; a filter's judge
+    must not read the state there, ranks are pending), after A, after B and after the continuation ("A", "B", "end")."""
+    rng = np.random.default_rng([SEED, a, b])
+    judge = judge or (lambda stage: None)
+    setup(drv)
+    prelude(drv)
+    judge("start")
+    OPS[a][1](drv, rng)
+    judge("A")
+    OPS[b][1](drv, rng)
+    judge("B")
+    continuation(drv, rng)
+    judge("end")
+
+
+def new_model(dtype=np.float64):
+    s = start()
+    return sm.bank(s[0], s[1], sources(), dtype)

@@ -1,0 +1,236 @@
+"""One dense model of ONE trajectory under the whole state-changing surface of a handle, for tests/sequence_cases.py.
+
+`SeqBank` is tests/fork_model.py's ForkBank (step, update, predict, predict_dense, grow, remove, window, copy_from) plus the
+newer calls, each DELEGATED to the model the project already trusts -- no new mathematics:
+
+    update_direct    direct_model.direct_update_joseph        update_linear    linear_model.linear_update_joseph
+    predict_linear   motion_model.predict_linear              transform        transform_model.transform_dense
+    join             join_model.join_dense (both modes)       set_state / set_state_diag, set_option: bookkeeping only
+
+The methods carry EkfSlam's names and take ONE trajectory's arguments (b = 0), so that a sequence written once runs on the model
+and on a filter (tests/sequence_cases.py's Driver).  The other handles a call reads (`join`, `copy_from`) are named by a key of
+`sources`: key -> (mean, covariance, tag index).
+
+`Traj.seen` follows each call's rule -- which landmarks are correlated with the rest: a dense-H row, a transform with a
+covariance, a sequential join (what it appends) and predict_dense correlate everything they name; a direct fix of a
+never-observed landmark and a transform without a covariance leave the exact zeros.
+
+PRECISION.  `bank(..., dtype=np.longdouble)` runs the SAME functions in extended precision (x87: 64 bits of mantissa): the
+models' code objects are re-bound to a namespace in which `np` is a proxy whose array constructors make `dtype` arrays
+(`dtype=float` included) and whose `linalg.solve` / `linalg.inv` are a pivoted elimination in `dtype` (LAPACK has no extended
+precision; the systems are at most 7 x 7).  Nothing of the models is restated.  Inputs -- measurements, noise constants,
+Jacobians handed in -- are the same float64 values in both precisions; only the arithmetic differs."""
+import sys
+import types
+
+import numpy as np
+
+from tests import direct_model as dm
+from tests import join_model as jm
+from tests import linear_model as lm
+from tests import motion_model as mm
+from tests import transform_model as tm
+from tests.fork_model import ForkBank
+from tests.fuzz_model import Traj
+
+
+class SeqBank(ForkBank):
+    def __init__(self, mean0, diag0, sources=None, base=None):
+        ForkBank.__init__(self, [(mean0, np.diag(np.asarray(diag0, dtype=float)))], base)
+        self.sources = dict(sources or {})
+
+    @property
+    def tr(self):
+        return self.t[0]
+
+    def state(self):
+        """(mean, covariance, tag index) of the trajectory."""
+        return self.tr.mean, self.tr.cov, dict(self.tr.tags)
+
+    # -- bookkeeping ---------------------------------------------------------------------------------------------------------
+    def set_state(self, mean, cov):
+        old = self.tr
+        self.t[0] = Traj(mean, cov, self.base)
+        self.t[0].cfg, self.t[0].rejections = old.cfg, old.rejections
+        d = np.diag(self.tr.cov)
+        off = np.abs(self.tr.cov).sum(axis=0) - np.abs(d)
+        self.tr.seen = (off[3::2] > 0) | (off[4::2] > 0)
+
+    def set_state_diag(self, mean, diag):
+        self.set_state(mean, np.diag(np.asarray(diag, dtype=float)))
+
+    def set_tag_index(self, tags):
+        self.tr.tags = {int(t): int(j) for t, j in tags.items()}
+
+    def set_option(self, name, value):
+        pass                                             # (the active bound changes no result)
+
+    # -- the calls ForkBank has, for one trajectory ----------------------------------------------------------------------------
+    def step1(self, lin, ang, idx, zr, zb):
+        self.step([lin], [ang], [(list(idx), list(zr), list(zb))])
+
+    def run_stream(self, lin, ang, idx, zr, zb):
+        for k in range(len(lin)):
+            self.step1(lin[k], ang[k], idx[k], zr[k], zb[k])
+
+    def step_detections(self, lin, ang, win):
+        self.window([lin], [ang], [win])
+
+    def add_landmarks(self, xy):
+        self.grow(xy, 0)
+
+    def remove_landmarks(self, lms):
+        self.remove([int(l) for l in lms], 0)
+
+    def predict_dense1(self, F, Q):
+        self.predict_dense(np.asarray(F, dtype=float), np.asarray(Q, dtype=float), 0)
+
+    def copy_in(self, key):
+        """copy_from(the handle `key` names): this trajectory is the destination."""
+        mean, cov, tags = self.sources[key]
+        tr = self.tr
+        tr.mean, tr.cov, tr.tags = np.array(mean, dtype=float), np.array(cov, dtype=float), dict(tags)
+        tr.seen = np.ones(tr.n_lm, dtype=bool)
+
+    # -- the newer calls, delegated ------------------------------------------------------------------------------------------
+    def update_direct(self, targets, z, R):
+        tr = self.tr
+        tr.mean, tr.cov, _, _, applied = dm.direct_update_joseph(tr.mean, tr.cov, targets, z, R)
+        assert applied
+
+    def update_linear(self, landmarks, H, R, z):
+        tr = self.tr
+        tr.mean, tr.cov, _, _, applied = lm.linear_update_joseph(tr.mean, tr.cov, landmarks, H, R, z)
+        assert applied
+        tr.seen[np.asarray(landmarks, dtype=int)] = True
+
+    def predict_linear(self, pose, F, Q):
+        tr = self.tr
+        tr.mean, tr.cov = mm.predict_linear(tr.mean, tr.cov, pose, F, Q)
+
+    def transform(self, T, cov=None):
+        tr = self.tr
+        tr.mean, tr.cov = tm.transform_dense(tr.mean, tr.cov, T, cov)[:2]
+        if cov is not None:
+            tr.seen[:] = True
+
+    def join(self, key, transform=None, cov=None):
+        mean, P, tags = self.sources[key]
+        tr = self.tr
+        first, count = tr.n_lm, (len(mean) - 3) // 2
+        tr.mean, tr.cov = jm.join_dense(tr.mean, tr.cov, mean, P, transform, cov, with_bound=False)[:2]
+        tr.seen = np.concatenate([tr.seen, np.ones(count, dtype=bool)])
+        for t, j in tags.items():                          # (a tag this map already holds: the appended twin carries none)
+            tr.tags.setdefault(t, first + j)
+
+
+# ---- the same code in another precision --------------------------------------------------------------------------------------
+_REBOUND = ("oracle.ekf_oracle", "tests.test_gpu_nis_gate", "tests.fuzz_model", "tests.fork_model", "tests.direct_model",
+            "tests.linear_model", "tests.motion_model", "tests.transform_model", "tests.join_model", __name__)
+_CLASSES = ("Traj", "Bank", "ForkBank", "SeqBank")
+
+
+def _elimination(dt):
+    def solve(A, B):
+        A, B = np.array(A, dtype=dt), np.array(B, dtype=dt)
+        n = len(A)
+        X = B.reshape(n, -1).copy()
+        for k in range(n):
+            p = k + int(np.argmax(np.abs(A[k:, k])))
+            if p != k:
+                A[[k, p]], X[[k, p]] = A[[p, k]], X[[p, k]]
+            for i in range(k + 1, n):
+                f = A[i, k] / A[k, k]
+                A[i, k:] -= f * A[k, k:]
+                X[i] -= f * X[k]
+        for k in range(n - 1, -1, -1):
+            X[k] = (X[k] - A[k, k + 1:] @ X[k + 1:]) / A[k, k]
+        return X.reshape(B.shape)
+
+    return types.SimpleNamespace(solve=solve, inv=lambda A: solve(A, np.eye(len(A), dtype=dt)), norm=np.linalg.norm)
+
+
+class _Numpy:
+    """numpy, but floating-point arrays are made in `dt`."""
+
+    def __init__(self, dt):
+        self._dt, self.linalg = dt, _elimination(dt)
+
+    def __getattr__(self, name):
+        return getattr(np, name)
+
+    def _d(self, dtype):
+        return self._dt if dtype is None or dtype is float else dtype
+
+    def zeros(self, shape, dtype=None):
+        return np.zeros(shape, self._d(dtype))
+
+    def ones(self, shape, dtype=None):
+        return np.ones(shape, self._d(dtype))
+
+    def empty(self, shape, dtype=None):
+        return np.empty(shape, self._d(dtype))
+
+    def full(self, shape, value, dtype=None):
+        return np.full(shape, value, self._d(dtype))
+
+    def eye(self, N, M=None, k=0, dtype=None):
+        return np.eye(N, M, k, self._d(dtype))
+
+    def _floating(self, a):
+        return a.astype(self._dt) if a.dtype.kind == "f" and a.dtype != self._dt else a
+
+    def array(self, obj, dtype=None, **kw):
+        return self._floating(np.array(obj, dtype=None if dtype is float else dtype, **kw))
+
+    def asarray(self, obj, dtype=None, **kw):
+        return self._floating(np.asarray(obj, dtype=None if dtype is float else dtype, **kw))
+
+
+def _rebind(name, npx, memo):
+    """The module `name` as a namespace whose functions and model classes see `npx` for numpy and one another's re-bound
+    versions: the same code objects, other globals."""
+    if name in memo:
+        return memo[name]
+    mod = sys.modules[name]
+    ns = types.SimpleNamespace()
+    g = ns.__dict__
+    g.update(vars(mod))
+    memo[name] = ns
+
+    def fn(v):
+        new = types.FunctionType(v.__code__, g, v.__name__, v.__defaults__, v.__closure__)
+        new.__kwdefaults__ = v.__kwdefaults__
+        return new
+
+    for key, v in list(g.items()):
+        if v is np:
+            g[key] = npx
+        elif isinstance(v, types.ModuleType) and v.__name__ in _REBOUND:
+            g[key] = _rebind(v.__name__, npx, memo)
+        elif isinstance(v, types.FunctionType) and v.__module__ in _REBOUND:
+            g[key] = fn(v) if v.__module__ == name else getattr(_rebind(v.__module__, npx, memo), v.__name__)
+        elif isinstance(v, type) and v.__name__ in _CLASSES and v.__module__ in _REBOUND:
+            if v.__module__ != name:
+                g[key] = getattr(_rebind(v.__module__, npx, memo), v.__name__)
+                continue
+            bases = tuple(getattr(_rebind(b.__module__, npx, memo), b.__name__) if b.__name__ in _CLASSES else b
+                          for b in v.__bases__)
+            body = {k: (fn(a) if isinstance(a, types.FunctionType) else
+                        property(fn(a.fget)) if isinstance(a, property) else a)
+                    for k, a in vars(v).items() if k not in ("__dict__", "__weakref__")}
+            g[key] = type(v.__name__, bases, body)
+    return ns
+
+
+_BANKS = {}
+
+
+def bank(mean0, diag0, sources=None, dtype=np.float64):
+    """A SeqBank in `dtype`: float64 is the class above as it stands, anything else the re-bound copy."""
+    dt = np.dtype(dtype)
+    if dt == np.float64:
+        return SeqBank(mean0, diag0, sources)
+    if dt not in _BANKS:
+        _BANKS[dt] = _rebind(__name__, _Numpy(dt), {}).SeqBank
+    return _BANKS[dt](mean0, diag0, sources)
