@@ -1797,7 +1797,7 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
   constexpr int RPW = NKT / 2;                         // ranks of a V strip each of the 8 waves stages
   __shared__ __attribute__((aligned(16))) double vbuf[2][NKT * 256];   // V strip as B fragments: [k-tile][col tile][lane]
   __shared__ __attribute__((aligned(16))) double img[8][16 * 64];      // per wave: 16 x 64 tile image (swizzled)
-  __shared__ int s_unit;
+  __shared__ int s_unit[2];                            // the unit in hand and the one popped ahead (alternating)
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int li = lane & 15, lq = lane >> 4;            // C/D layout coordinates
@@ -1822,10 +1822,12 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
   // units the head is bumped without looking first (one round trip instead of two); a queue found empty is only
   // looked at from then on (the heads are never bumped far beyond their counts).
   bool own_empty = false;
-  // a unit from this XCD's queue, else from the next non-empty one (see rs_queue_count / rs_queue_unit)
-  auto pop = [&]() -> int {
+  const int cnt_own = mode == 4 ? 0 : rs_queue_count(grp, batch, nrb, nch, mode);
+  // a unit from the queues grp + a0, grp + a0 + 1, ...: this XCD's first, else from the next non-empty one (see
+  // rs_queue_count / rs_queue_unit)
+  auto pop_from = [&](int a0) -> int {
     int found = -1;
-    for (int a = 0; a < 8 && found < 0; ++a) {
+    for (int a = a0; a < 8 && found < 0; ++a) {
       const int g2 = (grp + a) & 7;
       const int cnt = rs_queue_count(g2, batch, nrb, nch, mode);
       if (cnt == 0) continue;
@@ -1839,23 +1841,69 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
     }
     return found;
   };
-  int piece = 0;                                       // (mode 4) next piece of this workgroup's share
-  for (;;) {
-    __syncthreads();                                   // every wave is done with the LDS of the previous unit
+  // The hand-over: a workgroup takes its next unit while the one in hand still runs.  Thread 0 bumps the own queue's
+  // head when one or two tiles of the unit are left (pop_issue: the atomic goes out, nothing waits for it; a unit of one
+  // strip issues it in front of its prologue) and turns the answer into the next unit just before the drain (pop_finish:
+  // the round trip to L2 has passed under the tiles in between).  The unit goes to the OTHER word of s_unit: at the
+  // boundary one barrier and one LDS read remain.  Whatever that fast road does not settle -- the own queue has run dry
+  // (the other queues are walked), the first unit, a unit without work -- is popped at the boundary as before
+  // (pop_from, its only call).  Not earlier than the unit's end: the queues hand out longest first to whoever becomes
+  // free, and a workgroup that reserved its next unit at the START of a long one would take it in the wrong order (mode
+  // 1 pairs the longest slab of one trajectory with the shortest of the next by exactly that order).  A workgroup's
+  // sequence of queue operations is that of popping at the boundary: every unit is still handed out exactly once, and a
+  // workgroup that got -1 leaves after the unit in hand.
+  // (the address of the early atomic carries an opaque zero: on a uniform address the compiler would issue it from one
+  //  lane for the whole wave and read the answer back with v_readfirstlane -- waiting for it where it is issued)
+  unsigned u_ahead = 0;
+  int ahead = 0;                                       // (thread 0) 0: nothing settled, 1: s_unit holds the next unit, 2: own queue dry
+  auto pop_issue = [&]() {
+    if (threadIdx.x == 0 && cnt_own > 0 && !own_empty) {
+      unsigned z = 0;
+      asm volatile("" : "+v"(z));
+      u_ahead = atomicAdd(queue + grp * RS_QSTRIDE + z, 1u);
+    }
+  };
+  auto pop_finish = [&](int slot) {
+    if (threadIdx.x == 0 && cnt_own > 0 && !own_empty) {   // (the condition pop_issue saw: own_empty changes at the boundary only)
+      ahead = 2;
+      if (u_ahead < (unsigned)cnt_own) {
+        s_unit[slot] = rs_queue_unit(grp, (int)u_ahead, batch, nrb, nch, mode);
+        ahead = 1;
+      }
+    }
+  };
+  // (mode 4) this workgroup's share: the piece in hand was read one unit ahead as well
+  const int* pc = shares + (long)blockIdx.x * RS_PIECES * 4;
+  int piece = 0;
+  int pc_b = 0, pc_rb = 0, pc_start = 0, pc_count = 0;
+  if (mode == 4) {
+    pc_b = pc[0];
+    pc_rb = pc[1];
+    pc_start = pc[2];
+    pc_count = pc[3];
+  }
+  for (int cur = 0;; cur ^= 1) {
+    if (mode != 4 && threadIdx.x == 0 && ahead != 1) {
+      if (ahead == 2) own_empty = true;                // the early atomic bumped the own head beyond its count
+      s_unit[cur] = pop_from(ahead == 2 ? 1 : 0);
+    }
+    ahead = 0;
+    __syncthreads();                                   // every wave is done with the LDS of the previous unit; s_unit[cur] is written
     int b, rb, u_start, u_count;                       // the unit: strips [u_start, u_start + u_count) of slab rb of trajectory b
     if (mode == 4) {                                   // equal static shares: this workgroup's own list, no queue
-      if (piece >= RS_PIECES) return;
-      const int* pc = shares + ((long)blockIdx.x * RS_PIECES + piece) * 4;
-      ++piece;
-      b = pc[0];
-      rb = pc[1];
-      u_start = pc[2];
-      u_count = pc[3];
+      b = pc_b;
+      rb = pc_rb;
+      u_start = pc_start;
+      u_count = pc_count;
       if (u_count <= 0) return;                        // end of the share: all eight waves leave together
+      ++piece;
+      const int* pn = pc + min(piece, RS_PIECES - 1) * 4;   // the next piece: in SGPRs long before the boundary
+      pc_b = pn[0];
+      pc_rb = pn[1];
+      pc_start = pn[2];
+      pc_count = piece < RS_PIECES ? pn[3] : 0;
     } else {
-      if (threadIdx.x == 0) s_unit = pop();
-      __syncthreads();
-      const int unit = __builtin_amdgcn_readfirstlane(s_unit);   // (an LDS load is a vector value to the compiler)
+      const int unit = __builtin_amdgcn_readfirstlane(s_unit[cur]);   // (an LDS load is a vector value to the compiler)
       if (unit < 0) return;                            // every queue is empty: all eight waves leave together
       const int code = unit & 1023;
       b = (unit >> 10) / nrb;
@@ -1874,6 +1922,7 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
     if (u_start >= S_slab) continue;
     const int j_last = j_right - 64 * u_start;         // first (rightmost) strip of the unit
     const int S = min(u_count, S_slab - u_start);
+    if (mode != 4 && S == 1) pop_issue();              // a unit of one strip: the pop goes out under its first loads
     const bool has_diag = u_start + S == S_slab;       // the unit ends on the strip that holds the diagonal
     const int i0w = i0 + 16 * wave;
     // tiles of this wave: none if its rows lie beyond n; in the strip that holds the diagonal (columns i0..i0+63)
@@ -2127,6 +2176,7 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
         body(F_{}, T_{}, P1{}, t);
         body(F_{}, T_{}, P0{}, t + 1);
       }
+      if (mode != 4) pop_issue();                      // one or two tiles and the drain are left: they cover the round trip
       if (t < S - 1) {                                 // (t is odd here)
         body(F_{}, T_{}, P1{}, t);
         ++t;
@@ -2136,6 +2186,7 @@ __global__ __launch_bounds__(512, 2) void k_flush_rs(double* __restrict__ P, con
         else body(F_{}, F_{}, P0{}, S - 1);
       }
     }
+    if (mode != 4) pop_finish(cur ^ 1);                // (wave 0 always gets here: i0w = i0 < n, so Sw = S >= 1)
     if ((Sw - 1) & 1) drain(P1{});
     else drain(P0{});
   }
