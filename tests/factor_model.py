@@ -6,6 +6,12 @@ map_entropy) where there is no GPU, and the seeded test matrices both test files
 import numpy as np
 
 FB = 64
+EPS = 2.0 ** -53
+
+
+def gamma(k):
+    """Higham's gamma_k = k eps / (1 - k eps), the unit of both test files' bounds."""
+    return k * EPS / (1.0 - k * EPS)
 
 
 def blocked_cholesky(P):

@@ -15,6 +15,7 @@ import numpy as np
 
 from oracle import ekf_oracle as orc
 from tests.fuzz_model import Bank
+from tests.gpu_support import same as same_state
 
 
 class ForkBank(Bank):
@@ -43,10 +44,6 @@ def slot_properties(model):
 
 def dataclass_pair(cfg):
     return (cfg.motion_sigma, cfg.meas_sigma)
-
-
-def same_state(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 
 
 def observations(model, rng, m):

@@ -4,7 +4,7 @@ Test infrastructure only (oracle/ and tests/ helpers).  `Bank` mirrors what each
 
 * per-trajectory noise (`set_noise`): each trajectory predicts and updates under its own EkfConfig; None is the handle's
   config value, `set_noise()` the handle's constants; augmentation, `predict_dense` and the association gate ignore the table;
-* the NIS gate, through tests/test_gpu_nis_gate.py's `gated_update` / `gated_step`: every update leaves (idx, y, S, NIS,
+* the NIS gate, through tests/gated_oracle.py's `gated_update` / `gated_step`: every update leaves (idx, y, S, NIS,
   rejected) in application order, and a rejection leaves the state as it was;
 * margin-safe gating: before an update op is issued, its observations are run on a copy; while some NIS lies within a factor
   of BAND of the threshold, the first such observation is dropped and the rest run again (the set shrinks, so this ends),
@@ -22,8 +22,8 @@ import math
 import numpy as np
 
 from oracle import ekf_oracle as orc
-from tests.test_gpu_innovations import _tag  # noqa: F401  (windows for step_detections)
-from tests.test_gpu_nis_gate import gated_step, gated_update
+from tests.gated_oracle import gated_step
+from tests.gpu_support import tag
 
 BAND = 4.0              # no NIS within a factor of BAND of the threshold
 
@@ -224,5 +224,5 @@ def window_of(rng, tr, ids, new_xz, frames, jitter=0.004):
             pos[i] = (-yr, xr)
         else:
             pos[i] = new_xz[i]
-    return [(0.1 * fr, [_tag(i, x + rng.normal(0, jitter), z + rng.normal(0, jitter)) for i, (x, z) in pos.items()])
+    return [(0.1 * fr, [tag(i, x + rng.normal(0, jitter), z + rng.normal(0, jitter)) for i, (x, z) in pos.items()])
             for fr in range(frames)]

@@ -15,21 +15,9 @@
 #include <set>
 #include <vector>
 
-#include "ekf_host_plan.h"
+#include "plan_check.h"
 
 using namespace ekf;
-
-static long checks = 0;
-#define CHECK(cond, ...)                                              \
-  do {                                                                \
-    ++checks;                                                         \
-    if (!(cond)) {                                                    \
-      std::fprintf(stderr, "FAILED %s:%d: %s  [", __FILE__, __LINE__, #cond); \
-      std::fprintf(stderr, __VA_ARGS__);                              \
-      std::fprintf(stderr, "]\n");                                    \
-      std::exit(1);                                                   \
-    }                                                                 \
-  } while (0)
 
 // ---- the covariance's device layout: an injection into the allocation, row-major inside a panel ----
 static void check_layout() {

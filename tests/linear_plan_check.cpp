@@ -14,21 +14,9 @@
 #include <random>
 #include <vector>
 
-#include "ekf_host_plan.h"
+#include "plan_check.h"
 
 using namespace ekf;
-
-static long checks = 0;
-#define CHECK(cond, ...)                                              \
-  do {                                                                \
-    ++checks;                                                         \
-    if (!(cond)) {                                                    \
-      std::fprintf(stderr, "FAILED %s:%d: %s  [", __FILE__, __LINE__, #cond); \
-      std::fprintf(stderr, __VA_ARGS__);                              \
-      std::fprintf(stderr, "]\n");                                    \
-      std::exit(1);                                                   \
-    }                                                                 \
-  } while (0)
 
 // two trajectories, lstride 3 (ns = 9), dstride 4: trajectory 0 names the landmarks 5, 2, 7 and brings 3 rows, trajectory 1 the
 // landmark 1 (k = 1) and 2 rows

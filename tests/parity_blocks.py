@@ -152,6 +152,11 @@ def landmark_classes(before_P, touched, init_var):
     return lms[~never], lms[never & named], lms[never & ~named]
 
 
+def active_of(P, init_var):
+    """The landmarks of a reference covariance that have been observed (fixed, or tied in) at some time."""
+    return landmark_classes(P, [], init_var)[0]
+
+
 def assert_update_close(got, want, before, touched, init_var, tol, what="", entry_tol=None, first_cross_tol=None):
     """ONE update (direct or linear) applied to a known state: `got` = (mean, P) after the call, `want` the reference's
     result, `before` the state the call found, `touched` the landmarks the call names.  The landmarks fall into three

@@ -24,18 +24,7 @@
 #include <vector>
 
 #include "ekf_resources.h"
-
-static long checks = 0;
-#define CHECK(cond, ...)                                              \
-  do {                                                                \
-    ++checks;                                                         \
-    if (!(cond)) {                                                    \
-      std::fprintf(stderr, "FAILED %s:%d: %s  [", __FILE__, __LINE__, #cond); \
-      std::fprintf(stderr, __VA_ARGS__);                              \
-      std::fprintf(stderr, "]\n");                                    \
-      std::exit(1);                                                   \
-    }                                                                 \
-  } while (0)
+#include "plan_check.h"
 
 // ---- the counting backend ----
 struct Call {

@@ -29,7 +29,7 @@ from tests import linear_model as lm
 from tests import motion_model as mm
 from tests import parity_blocks as pb
 from tests import sequence_model as sm
-from tests.test_gpu_join import FRAME, stream_from
+from tests.streams import FRAME, stream_from
 
 INIT_VAR = orc.EkfConfig().landmark_init_var
 N_OBSERVED, N_LANDMARKS, N_MAX = 26, 30, 79

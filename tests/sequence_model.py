@@ -125,7 +125,7 @@ class SeqBank(ForkBank):
 
 
 # ---- the same code in another precision --------------------------------------------------------------------------------------
-_REBOUND = ("oracle.ekf_oracle", "tests.test_gpu_nis_gate", "tests.fuzz_model", "tests.fork_model", "tests.direct_model",
+_REBOUND = ("oracle.ekf_oracle", "tests.gated_oracle","tests.fuzz_model", "tests.fork_model", "tests.direct_model",
             "tests.linear_model", "tests.motion_model", "tests.transform_model", "tests.join_model", __name__)
 _CLASSES = ("Traj", "Bank", "ForkBank", "SeqBank")
 

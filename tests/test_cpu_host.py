@@ -10,6 +10,7 @@ import pytest
 
 from oracle import ekf_oracle as orc
 from tests import golden_util as gu
+from tests import host_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -40,9 +41,7 @@ def test_library_exports_every_declared_symbol(sd):
         assert name in eb.ABI, f"{name} has no ctypes signature"
     assert sorted(eb.ABI) == names
     # ... and the other way round: nothing named ekf_* leaves the library without a declaration (diagnostics included)
-    import subprocess
-    nm = subprocess.run(["nm", "-D", "--defined-only", sd.library_path()], check=True, capture_output=True, text=True).stdout
-    exported = sorted({ln.split()[-1] for ln in nm.splitlines() if re.fullmatch(r"ekf_[a-z0-9_]+", ln.split()[-1])})
+    exported = sorted(s for s in host_check.exported_symbols(sd.library_path()) if re.fullmatch(r"ekf_[a-z0-9_]+", s))
     assert exported == names, sorted(set(exported) ^ set(names))
 
 
@@ -367,19 +366,7 @@ def test_host_planning_logic_under_the_sanitizers(tmp_path):
     covariance's device layout) compiled with plain g++ under AddressSanitizer + UndefinedBehaviorSanitizer and run
     through tests/host_plan_check.cpp: the enumerations of the tests above plus randomised (batch, size, option,
     m-sequence) invariants of `plan_pass` / `cadence_length` / `fill_step` / `validate_obs`.  CPU only."""
-    import shutil
-    if shutil.which("g++") is None:
-        pytest.skip("g++ is not available")
-    exe = tmp_path / "host_plan_check"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DEKF_HOST_ONLY",
-           "-Wall", "-Werror", "-I", os.path.join(ROOT, "slam-duckietown_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "host_plan_check.cpp"), "-o", str(exe)]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "checks passed" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    host_check.run_under_sanitizers("host_plan_check", tmp_path, 300)
     # the library itself is built from the same header (a stale copy would make this test vacuous)
     api = open(os.path.join(ROOT, "slam-duckietown_amd", "csrc", "ekf_api.hip")).read()
     assert '#include "ekf_host_plan.h"' in api and "struct ekf_handle : ekf::HostPlan" in api
@@ -397,19 +384,7 @@ def test_handle_ownership_types_under_the_sanitizers(tmp_path):
     counting backend that can fail its k-th call replays the handle's allocation script once for every k -- nothing live at
     the end, no double free, a failed group empty and its retry good, no free before the stream has been waited for, no
     pinned copy handed out under an upload in flight, one "new" report per allocation.  CPU only."""
-    import shutil
-    if shutil.which("g++") is None:
-        pytest.skip("g++ is not available")
-    exe = tmp_path / "resources_check"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DEKF_HOST_ONLY",
-           "-Wall", "-Werror", "-I", os.path.join(ROOT, "slam-duckietown_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "resources_check.cpp"), "-o", str(exe)]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "checks passed" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    host_check.run_under_sanitizers("resources_check", tmp_path, 300)
     # the library itself is built from the same header: it includes it, instantiates its types for the HIP backend and
     # defines none of them itself; the header names nothing of HIP
     api = open(os.path.join(ROOT, "slam-duckietown_amd", "csrc", "ekf_api.hip")).read()

@@ -3,20 +3,15 @@
 evaluation.map_nees / map_entropy / information_gain on a stand-in filter backed by the model, and plan_factor under the
 sanitizers (tests/factor_plan_check.cpp)."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import factor_model as fm
+from tests import host_check
+from tests.factor_model import EPS, gamma
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EPS = 2.0 ** -53
-
-
-def gamma(k):
-    return k * EPS / (1.0 - k * EPS)
 
 
 @pytest.mark.parametrize("n", [3, 43, 63, 64, 65, 191, 193, 301])
@@ -136,18 +131,7 @@ def test_map_nees_entropy_and_gain():
 
 def test_plan_factor_under_the_sanitizers(tmp_path):
     """tests/factor_plan_check.cpp, built and run as tests/direct_plan_check.cpp is."""
-    if shutil.which("g++") is None:
-        pytest.skip("g++ is not available")
-    exe = tmp_path / "factor_plan_check"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DEKF_HOST_ONLY",
-           "-Wall", "-Werror", "-I", os.path.join(ROOT, "slam-duckietown_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "factor_plan_check.cpp"), "-o", str(exe)]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "checks passed" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    host_check.run_under_sanitizers("factor_plan_check", tmp_path, 300)
     api = open(os.path.join(ROOT, "slam-duckietown_amd", "csrc", "ekf_api.hip")).read()
     for fn in ("plan_factor", "plan_factor_apply"):
         assert fn + "(" in api

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from tests import fork_model as fm
-from tests.test_noise_bank_cpu import FakeBank
+from tests.fake_bank import FakeBank
 
 
 class ForkingBank(FakeBank):

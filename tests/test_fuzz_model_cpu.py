@@ -8,7 +8,7 @@ import pytest
 from oracle import ekf_oracle as orc
 from slam_duckietown_amd.frontend import remap_tag_index
 from tests import fuzz_model as fm
-from tests.test_gpu_innovations import update_log
+from tests.gated_oracle import update_log
 
 
 def start(N, seed, var=0.05):

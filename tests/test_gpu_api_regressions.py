@@ -8,24 +8,12 @@ import pytest
 
 from oracle import ekf_oracle as orc
 from tests import golden_util as gu
+from tests.gpu_support import close, sd, tag  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 REL_TOL = 1e-6
 TIGHT = 1e-9
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-def close(a, b, tol=TIGHT):
-    r = orc.rel_fro(a, b)
-    assert r < REL_TOL, f"rel Frobenius {r:.3e} exceeds the 1e-6 bar"
-    assert r < tol, f"rel Frobenius {r:.3e} exceeds the expected {tol:g}"
 
 
 def test_drop_in_sees_in_place_edits_of_returned_arrays(sd, both_paths):
@@ -269,10 +257,6 @@ def test_rejected_update_leaves_the_handle_untouched(sd):
             close(P, oP)
 
 
-def _tag(i, x, z):
-    return NS(tag_id=i, pose_R=np.eye(3), pose_t=np.array([[x], [0.0], [z]]), pose_err=0.0)
-
-
 def _raw_step_detections(sd, f, lin, ang, tags):
     """The C entry point itself (one trajectory, one frame), past EkfSlam.step_detections' host-side check of the
     device front end's limits."""
@@ -291,7 +275,7 @@ def test_device_association_drops_before_indexing(sd):
     """The C ABI's device front end with 33 distinct tags in one window (EKF_AMAX = 32): the 33rd is dropped BEFORE it is
     given a landmark index (no uninitialised landmark enters the state), the sticky flag is raised and tags_positions()
     reports it.  (`EkfSlam.step_detections` checks the limits on the host and never sends such a window: next test.)"""
-    tags = [_tag(100 + i, -0.4 + 0.025 * i, 0.6 + 0.01 * i) for i in range(33)]
+    tags = [tag(100 + i, -0.4 + 0.025 * i, 0.6 + 0.01 * i) for i in range(33)]
     with sd.EkfSlam(3 + 2 * 40) as f:
         assert _raw_step_detections(sd, f, 0.01, 0.0, tags) == 0
         assert f.size() == 3 + 2 * 32
@@ -321,13 +305,13 @@ def test_normal_mode_window_stays_on_the_device(sd, both_paths):
         out = []
         for fr in range(frames):
             order = list(ids) if fr % 2 == 0 else list(ids)[::-1]              # the order within a frame wanders
-            tags = [_tag(int(i), base[i][0] + float(rng.normal(0, 0.004)), base[i][1] + float(rng.normal(0, 0.004))) for i in order]
+            tags = [tag(int(i), base[i][0] + float(rng.normal(0, 0.004)), base[i][1] + float(rng.normal(0, 0.004))) for i in order]
             if fr == 1:
                 tags += list(extra)
             out.append((k + fr / 30.0, tags))
         return out
 
-    wins = [window(ids_a, 21, 0.0), window(ids_b, 5, 1.0, extra=(_tag(777, 1.4, 1.4), _tag(55, 0.1, 0.5))),
+    wins = [window(ids_a, 21, 0.0), window(ids_b, 5, 1.0, extra=(tag(777, 1.4, 1.4), tag(55, 0.1, 0.5))),
             window(ids_a[::-1], 21, 2.0)]
     assert sum(len(t) for _s, t in wins[0]) == 126
     with sd.EkfSlam(3 + 2 * 24) as f:
@@ -363,9 +347,9 @@ def test_step_detections_beyond_the_device_limits(sd):
         """`frames` frames, every tag in each (repeated detections are averaged, :315), one beyond the gate, one twice."""
         out = []
         for fr in range(frames):
-            tags = [_tag(int(i), float(base_x[i] + rng.normal(0, 0.004)), float(base_z[i] + rng.normal(0, 0.004))) for i in ids]
+            tags = [tag(int(i), float(base_x[i] + rng.normal(0, 0.004)), float(base_z[i] + rng.normal(0, 0.004))) for i in ids]
             if fr == 0:
-                tags.append(_tag(777, 1.4, 1.4))                   # 1.98 m away: gated (:289), never indexed
+                tags.append(tag(777, 1.4, 1.4))                   # 1.98 m away: gated (:289), never indexed
             out.append((k + 0.1 * fr, tags))
         return out
 
@@ -401,7 +385,7 @@ def test_step_detections_beyond_the_device_limits(sd):
                 close(P, oP[b])
         assert len(oti[0]) == 24 and 777 not in oti[0]
         # a map the handle cannot hold is refused before anything is enqueued
-        more = [_tag(5000 + i, 0.01 * i, 0.5) for i in range(20)]
+        more = [tag(5000 + i, 0.01 * i, 0.5) for i in range(20)]
         before = [f.state(b) for b in range(2)]
         with pytest.raises(sd.EkfError, match="capacity"):
             f.step_detections(0.004, 0.02, [[(9.0, more)], [(9.0, more)]])
@@ -409,10 +393,10 @@ def test_step_detections_beyond_the_device_limits(sd):
             assert np.array_equal(f.state(b)[1], before[b][1]) and f.size(b) == len(before[b][0])
     # below the limits and with small ids the device path is the one that runs (the host overlay is dropped again)
     with sd.EkfSlam(3 + 2 * 40) as f:
-        w17 = [(0.0, [_tag(100 + i, -0.4 + 0.025 * i, 0.6 + 0.01 * i) for i in range(33)])]
+        w17 = [(0.0, [tag(100 + i, -0.4 + 0.025 * i, 0.6 + 0.01 * i) for i in range(33)])]
         f.step_detections(0.004, 0.02, w17)                          # 33 tags (> EKF_AMAX): host, then the device table follows
         assert f.flags() == 0 and f.size() == 3 + 2 * 33 and not f._host_index and f.assoc_fallbacks() == 1
-        w3 = [(1.0, [_tag(100 + i, -0.4 + 0.025 * i, 0.61 + 0.01 * i) for i in (2, 32, 5)] + [_tag(300, 0.2, 0.9)])]
+        w3 = [(1.0, [tag(100 + i, -0.4 + 0.025 * i, 0.61 + 0.01 * i) for i in (2, 32, 5)] + [tag(300, 0.2, 0.9)])]
         om, oP, oti = np.zeros(3), np.eye(3) * 0.1, {}
         om, oP, _ = orc.ekf_pose_estimation_dense(0.02, 0.004, om, oP, 0.7, w17, oti, cfg)
         f.step_detections(0.004, 0.02, w3)                           # device path: the table it was handed knows all 33
@@ -433,7 +417,7 @@ def test_gpu_backend_device_association_beyond_the_device_limits(sd, both_paths)
     for k in range(10):
         count = 36 if k in (2, 6) else 5
         ids = rng.choice(60, size=count, replace=False)
-        tags = [_tag(int(i), float(rng.uniform(-0.5, 0.5)), float(rng.uniform(0.4, 1.2))) for i in ids]
+        tags = [tag(int(i), float(rng.uniform(-0.5, 0.5)), float(rng.uniform(0.4, 1.2))) for i in ids]
         windows.append([(float(k), tags)])
     res = []
     for dev in (False, True):
@@ -661,7 +645,7 @@ def test_handle_churn_leaves_nothing_behind(sd):
     N_cap, N, B, m, steps = 100, 96, 2, 8, 30
     streams = [orc.synthetic_stream(N, steps, m, 9100 + t) for t in range(B)]
     args = tuple(np.stack([s[i] for s in streams], axis=1) for i in (2, 3, 4, 5, 6))
-    window = [(0.0, [_tag(500 + i, -0.3 + 0.2 * i, 0.6 + 0.05 * i) for i in range(3)])]
+    window = [(0.0, [tag(500 + i, -0.3 + 0.2 * i, 0.6 + 0.05 * i) for i in range(3)])]
 
     def life():
         with sd.EkfSlam(3 + 2 * N_cap, batch=B) as f:

@@ -8,7 +8,6 @@ two candidates must equal the reference's two best wherever the reference's scor
 that tolerance (at most 1 % of the observations excused); entries whose unwrapped bearing residual lies within 1e-9 of an odd
 multiple of pi are left out (at most 0.1 %)."""
 import ctypes as C
-from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
@@ -16,19 +15,13 @@ import pytest
 from oracle import ekf_oracle as orc
 from tests import assoc_world as aw
 from tests.conftest import path_ran
+from tests.gpu_support import counters, sd, tag  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 EKF_ERR_ARG = -1
 NIS_TOL, LOGDET_TOL, PATH_TOL = 1e-9, 2e-9, 1e-10
 TOTALS = {"entries": 0, "left_out": 0, "obs": 0, "excused": 0}
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
 
 
 def check_query(f, zr, zb, m=None, meas_sigma=None, what="", res=None):
@@ -120,16 +113,11 @@ def stream_args(streams):
     return tuple(np.stack([np.asarray(s[i]) for s in streams], 1) for i in (2, 3, 4, 5, 6))
 
 
-def dense_start(rng, n):
+def dense_start_from(rng, n):
     A = rng.normal(size=(n, 6)) * 0.3
     P = A @ A.T
     P[np.arange(n), np.arange(n)] += rng.uniform(0.5, 2.0, n)
     return P
-
-
-def counters(sd, f):
-    lib = sd.load_library()
-    return f.cadence_counters(), lib.ekf_debug_chained(f._h), lib.ekf_debug_lookaheads(f._h), f.profile_passes()
 
 
 # ---- states -----------------------------------------------------------------------------------------------------------------
@@ -139,7 +127,7 @@ def test_nothing_pending_and_bit_identical_between_two_calls(sd):
     rng = np.random.default_rng(1)
     with sd.EkfSlam(n, batch=B) as f:
         for b in range(B):
-            f.set_state(rng.normal(size=n), dense_start(rng, n), b)
+            f.set_state(rng.normal(size=n), dense_start_from(rng, n), b)
         zr, zb = obs_around(rng, f, 8)
         a, _ = check_query(f, zr, zb)
         again = f.associate(zr, zb, full=True)
@@ -177,7 +165,7 @@ def test_stream_pieces_ending_mid_cadence_and_non_interference(sd, N, chain):
     n, steps = 3 + 2 * N, 22
     s = orc.synthetic_stream(N, steps, 8, 77)
     rng = np.random.default_rng(5)
-    P0 = dense_start(rng, n)
+    P0 = dense_start_from(rng, n)
     args = tuple(np.asarray(a)[:, None] for a in (s[2], s[3], s[4], s[5], s[6]))
     pieces = [(0, 7), (7, 6), (13, 9)]                      # 56, 104 updates: both boundaries inside a cadence of 40
     zs = [(rng.uniform(0.2, 3.0, (1, 8)), rng.uniform(-3.0, 3.0, (1, 8))) for _ in pieces]
@@ -199,8 +187,8 @@ def test_stream_pieces_ending_mid_cadence_and_non_interference(sd, N, chain):
 
     q, plain = run(True), run(False)
     assert np.array_equal(q[1][0], plain[1][0]) and np.array_equal(q[1][1], plain[1][1])
-    assert q[2] == plain[2]
-    assert q[2][2] > 0 and (q[2][1] > 0) == bool(chain)     # the look-ahead ran, chained where asked
+    assert q[2][:5] == plain[2][:5]                         # cadences, steps covered, chained, look-aheads, passes
+    assert q[2].lookaheads > 0 and (q[2].chained > 0) == bool(chain)     # the look-ahead ran, chained where asked
     # each query against the reference: replay the pieces, flushing after the query this time
     with sd.EkfSlam(n, batch=1) as f:
         f.set_option("chain", chain)
@@ -225,7 +213,7 @@ def test_fused_cadence_against_per_step_kernels(sd):
         with sd.EkfSlam(3 + 2 * N, batch=B) as f:
             f.set_option("fused_cadence", fused)
             for b, s in enumerate(streams):
-                f.set_state(s[0], dense_start(np.random.default_rng(b), 3 + 2 * N), b)
+                f.set_state(s[0], dense_start_from(np.random.default_rng(b), 3 + 2 * N), b)
             if fused:
                 f.run_stream(*stream_args(streams))
                 assert f.cadence_counters()[0] > 0
@@ -357,10 +345,6 @@ def test_after_remove_landmarks(sd):
         assert np.isnan(a.all_nis[0, :, N - 4:]).all() and not np.isnan(a.all_nis[1]).any()
 
 
-def _tag(i, x, z):
-    return NS(tag_id=i, pose_R=np.eye(3), pose_t=np.array([[x], [0.0], [z]]), pose_err=0.0)
-
-
 def test_after_step_detections_grew_the_state(sd):
     """The device-side association grew the maps (sizes refreshed by the query itself), ranks pending.  Twice: with the
     reference's constants (meas_sigma 0.7), checked against the NumPy reference; and with a sharp filter (meas_sigma 0.03), where
@@ -375,7 +359,7 @@ def test_after_step_detections_grew_the_state(sd):
     bz = {i: float(rng.uniform(0.4, 1.1)) for i in ids}
 
     def window(k, win_ids):
-        return [(k + 0.1 * fr, [_tag(i, bx[i] + rng.normal(0, 0.004), bz[i] + rng.normal(0, 0.004)) for i in win_ids])
+        return [(k + 0.1 * fr, [tag(i, bx[i] + rng.normal(0, 0.004), bz[i] + rng.normal(0, 0.004)) for i in win_ids])
                 for fr in range(2)]
 
     for cfg in (sd.EkfConfig(), sd.EkfConfig(motion_sigma=0.02, meas_sigma=0.03)):
@@ -420,7 +404,7 @@ def test_bad_arguments_leave_the_handle_usable(sd):
     rng = np.random.default_rng(12)
     with sd.EkfSlam(3 + 2 * N, batch=B) as f:
         for b in range(B):
-            f.set_state(rng.normal(size=3 + 2 * N), dense_start(rng, 3 + 2 * N), b)
+            f.set_state(rng.normal(size=3 + 2 * N), dense_start_from(rng, 3 + 2 * N), b)
         zr, zb = obs_around(rng, f, 4)
         m = np.full(B, 4, dtype=np.int32)
         cand = np.empty((B, 4, 2), dtype=np.int32)

@@ -20,24 +20,12 @@ import pytest
 
 from oracle import ekf_oracle as orc
 from tests import parity_blocks as pb
+from tests.gpu_support import close, sd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 REL_TOL = 1e-6
 TIGHT = 1e-9
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-def close(a, b, tol=TIGHT):
-    r = orc.rel_fro(a, b)
-    assert r < REL_TOL, f"rel Frobenius {r:.3e} exceeds the 1e-6 bar"
-    assert r < tol, f"rel Frobenius {r:.3e} exceeds the expected {tol:g}"
 
 
 def debug_counters(sd, f):
@@ -48,7 +36,7 @@ def debug_counters(sd, f):
     return a.value, b.value, lib.ekf_debug_lookaheads(f._h), lib.ekf_debug_last_pass_shares(f._h)
 
 
-def dense_start(n, seed):
+def dense_start_rank8(n, seed):
     """A dense SPD covariance (diagonal + rank 8) so that every tile of the pass receives a non-zero update."""
     rng = np.random.default_rng(seed)
     A = rng.normal(size=(n, 8)) * 0.3
@@ -67,7 +55,7 @@ def test_config4_shard_n2000_x32_default_cadence(sd):
     n = 3 + 2 * N
     cfg = orc.EkfConfig()
     streams = [orc.synthetic_stream(N, steps, m, 40 + t) for t in range(K)]
-    starts = [dense_start(n, 7 + t) for t in range(K)]
+    starts = [dense_start_rank8(n, 7 + t) for t in range(K)]
     ref = []
     for t in range(K):
         om, oP = streams[t][0].copy(), starts[t].copy()
@@ -169,7 +157,7 @@ def test_variable_m_leg_n2000_x32_as_benchmarked(sd):
     n = 3 + 2 * N
     cfg = orc.EkfConfig()
     streams = [syn.variable_stream(N, steps, 0, 8, 70 + t) for t in range(K)]
-    starts = [dense_start(n, 17 + t) for t in range(K)]
+    starts = [dense_start_rank8(n, 17 + t) for t in range(K)]
     ref = []
     for t in range(K):
         s = streams[t]
@@ -207,7 +195,7 @@ def test_streaming_80_rank_pass_small(sd):
     cfg = orc.EkfConfig()
     streams = [orc.synthetic_stream(N, steps, m, 60 + t) for t in range(B)]
     n = 3 + 2 * N
-    ref = [(s[0].copy(), dense_start(n, 3 + b)) for b, s in enumerate(streams)]
+    ref = [(s[0].copy(), dense_start_rank8(n, 3 + b)) for b, s in enumerate(streams)]
     with sd.EkfSlam(n, batch=B) as f:
         f.set_option("pass_streaming", 1)
         f.set_option("rank_limit", 80)
@@ -230,7 +218,7 @@ def test_predict_dense_n4003(sd):
     with a general F)."""
     n = 4003
     rng = np.random.default_rng(5)
-    P0 = dense_start(n, 11)
+    P0 = dense_start_rank8(n, 11)
     F = np.eye(n) + rng.normal(size=(n, n)) * (0.1 / np.sqrt(n))
     Nq = rng.normal(size=(n, 8)) * 0.05
     Q = Nq @ Nq.T + np.diag(rng.uniform(0.01, 0.1, n))

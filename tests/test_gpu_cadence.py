@@ -11,7 +11,6 @@ measurement noise amplify a last-bit difference by four orders of magnitude; the
 1e-9 / 1e-6 against the oracle (the
 reference-shaped dense NumPy path, pinned to the reference's golden vectors).
 """
-import ctypes as C
 import os
 
 import numpy as np
@@ -20,25 +19,13 @@ import pytest
 from oracle import ekf_oracle as orc
 from tests import golden_util as gu
 from tests import parity_blocks as pb
+from tests.gpu_support import counters, sd  # noqa: F401
+from tests.streams import dense_start
 
 pytestmark = pytest.mark.gpu
 
 PATH_TOL = 1e-11
 TIGHT = 1e-9
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-def cadences(sd, f):
-    lib = sd.load_library()
-    a, b = C.c_long(), C.c_long()
-    assert lib.ekf_debug_cadences(f._h, C.byref(a), C.byref(b)) == 0
-    return a.value, b.value
 
 
 def cadences_needed(m_col, slots=40, steps_cap=40):
@@ -59,14 +46,6 @@ def cadences_needed(m_col, slots=40, steps_cap=40):
     return c
 
 
-def dense_start(n, seed, rank=6):
-    rng = np.random.default_rng(seed)
-    A = rng.normal(size=(n, rank)) * 0.3
-    P = A @ A.T
-    P[np.arange(n), np.arange(n)] += rng.uniform(0.5, 2.0, n)
-    return P
-
-
 def run_stream(sd, n, B, starts, means, lin, ang, idx, zr, zb, m=None, options=(), diag=False, cfg=None):
     """One handle, the whole stream; returns ([(mean, cov)] per trajectory, fused cadences, steps they covered)."""
     with sd.EkfSlam(n, batch=B, config=cfg) as f:
@@ -80,7 +59,7 @@ def run_stream(sd, n, B, starts, means, lin, ang, idx, zr, zb, m=None, options=(
         f.run_stream(lin, ang, idx, zr, zb, m)
         out = [f.state(b) for b in range(B)]
         assert [f.flags(b) for b in range(B)] == [0] * B
-        c = cadences(sd, f)
+        c = counters(sd, f)[:2]
     return out, c
 
 
@@ -336,16 +315,6 @@ def test_pass_forms_w_from_v_bit_identical(sd):
             assert np.array_equal(res[0][b][0], res[1][b][0]) and np.array_equal(res[0][b][1], res[1][b][1]), (N, b)
 
 
-def lookaheads(sd, f):
-    lib = sd.load_library()
-    return lib.ekf_debug_lookaheads(f._h)
-
-
-def chained(sd, f):
-    lib = sd.load_library()
-    return lib.ekf_debug_chained(f._h)
-
-
 # the three orders a run's cadences can be enqueued in (csrc/ekf_api.hip: enqueue_cadence): chained solves (round 6, default),
 # the round-3 look-ahead, everything one behind the other
 MODES = {"chain": (("lookahead", 1), ("chain", 1)), "lookahead": (("lookahead", 1), ("chain", 0)), "plain": (("lookahead", 0),)}
@@ -376,8 +345,8 @@ def test_lookahead_solve_beside_the_pass(sd, N, B, m, steps):
             res[mode] = [f.state(b) for b in range(B)]
             assert [f.flags(b) for b in range(B)] == [0] * B
             want = (-(-steps * m // 40) - 1) if mode != "plain" else 0       # every cadence but the first is solved ahead
-            assert lookaheads(sd, f) == want, (mode, lookaheads(sd, f), want)
-            assert chained(sd, f) == (want if mode == "chain" else 0), (mode, chained(sd, f))
+            assert counters(sd, f).lookaheads == want, (mode, counters(sd, f).lookaheads, want)
+            assert counters(sd, f).chained == (want if mode == "chain" else 0), (mode, counters(sd, f).chained)
     for mode in ("chain", "lookahead"):
         for b in range(B):
             assert orc.rel_fro(res[mode][b][0], res["plain"][b][0]) < PATH_TOL, mode
@@ -410,8 +379,8 @@ def test_chained_panel_forms_agree(sd):
             f.run_stream(lin, ang, idx, zr, zb, m)
             res[key] = [f.state(b) for b in range(B)]
             assert [f.flags(b) for b in range(B)] == [0] * B
-            nc = cadences(sd, f)[0]
-            assert nc >= 3 and chained(sd, f) == nc - 1
+            nc = counters(sd, f).cadences
+            assert nc >= 3 and counters(sd, f).chained == nc - 1
     for b in range(B):
         assert orc.rel_fro(res["replay_panel"][b][0], res["default"][b][0]) < PATH_TOL
         assert orc.rel_fro(res["replay_panel"][b][1], res["default"][b][1]) < PATH_TOL
@@ -436,10 +405,10 @@ def test_lookahead_with_wandering_landmark_counts(sd):
             f.run_stream(lin, ang, idx, zr, zb, m)
             res[mode] = [f.state(b) for b in range(B)]
             assert [f.flags(b) for b in range(B)] == [0] * B
-            nc = cadences(sd, f)[0]
+            nc = counters(sd, f).cadences
             assert nc == max(cadences_needed(m[:, b]) for b in range(B)) and nc >= 3
-            assert lookaheads(sd, f) == (nc - 1 if mode != "plain" else 0)
-            assert chained(sd, f) == (nc - 1 if mode == "chain" else 0)
+            assert counters(sd, f).lookaheads == (nc - 1 if mode != "plain" else 0)
+            assert counters(sd, f).chained == (nc - 1 if mode == "chain" else 0)
     cfg = orc.EkfConfig()
     for b in range(B):
         om, oP = means[b].copy(), starts[b].copy()
@@ -475,8 +444,8 @@ def test_lookahead_beside_the_row_slab_pass_on_static_shares(sd):
             res[mode] = [f.state(b) for b in range(B)]
             assert [f.flags(b) for b in range(B)] == [0] * B
             assert lib.ekf_debug_last_pass_shares(f._h) >= 1
-            assert (lookaheads(sd, f) >= 4) if mode != "plain" else (lookaheads(sd, f) == 0)
-            assert chained(sd, f) == (lookaheads(sd, f) if mode == "chain" else 0)
+            assert (counters(sd, f).lookaheads >= 4) if mode != "plain" else (counters(sd, f).lookaheads == 0)
+            assert counters(sd, f).chained == (counters(sd, f).lookaheads if mode == "chain" else 0)
     cfg = orc.EkfConfig()
     s = streams[1]
     om, oP = s[0].copy(), starts[1].copy()
@@ -517,7 +486,7 @@ def test_stream_run_in_pieces_with_flushes_and_downloads_in_between(sd):
                 assert np.isfinite(f.covariance_block(0, 0, 3, 3)).all()
         assert k == steps
         mu, P = f.state()
-        assert f.flags() == 0 and lookaheads(sd, f) >= 2
+        assert f.flags() == 0 and counters(sd, f).lookaheads >= 2
     assert orc.rel_fro(mu, whole[0][0]) < PATH_TOL and orc.rel_fro(P, whole[0][1]) < PATH_TOL
 
 
@@ -544,7 +513,7 @@ def test_short_pieces_with_run_end_flush_all_run_fused(sd):
             for k in range(0, steps, 4):                  # 12 landmark updates per piece
                 f.stream_run(k, 4)
             out = [f.state(b) for b in range(B)]
-            covered[ref] = cadences(sd, f)[1]
+            covered[ref] = counters(sd, f).covered
         for b in range(B):
             assert orc.rel_fro(out[b][0], whole[b][0]) < PATH_TOL and orc.rel_fro(out[b][1], whole[b][1]) < PATH_TOL
     assert covered[1] == steps and covered[0] < steps
@@ -707,7 +676,7 @@ def test_random_streams_orders_pieces_and_options_against_the_oracle(sd, case):
         out = [f.state(b) for b in range(B)]
         assert [f.flags(b) for b in range(B)] == [0] * B, (order, opts, pieces)
         if os.environ.get("EKF_FUZZ_VERBOSE"):
-            print("FUZZ", case, order, dict(opts), pieces, "cadences", cadences(sd, f), "w_from_v", sd.load_library().ekf_debug_w_from_v(f._h))
+            print("FUZZ", case, order, dict(opts), pieces, "cadences", counters(sd, f)[:2], "w_from_v", sd.load_library().ekf_debug_w_from_v(f._h))
     cfg = orc.EkfConfig()
     for b in range(B):
         om, oP = means[b].copy(), starts[b].copy()
@@ -794,7 +763,7 @@ def test_run_plan_copies_regrow_on_one_handle(sd):
         assert k == steps
         out = [f.state(b) for b in range(B)]
         assert [f.flags(b) for b in range(B)] == [0] * B
-        assert cadences(sd, f) == (sum(need), steps)
+        assert counters(sd, f)[:2] == (sum(need), steps)
     plain, (pc, _) = run_stream(sd, n, B, starts, means, *args, options=opts + [("fused_cadence", 0)])
     assert pc == 0
     for b in range(B):
@@ -838,7 +807,7 @@ def test_golden_stream_through_the_cadence(sd):
         f.set_state_diag(g["mean0"], g["diag0"])
         f.run_stream(g["lin"], g["ang"], g["idx"], g["zr"], g["zb"])
         mu, P = f.state()
-        assert cadences(sd, f) == (steps // 5, steps) and f.flags() == 0
+        assert counters(sd, f)[:2] == (steps // 5, steps) and f.flags() == 0
     assert orc.rel_fro(mu, g["out_mean"][-1]) < TIGHT
     assert orc.rel_fro(P, g["out_cov"][-1]) < TIGHT
 
@@ -862,7 +831,7 @@ def test_config4_shape_n2000_x32_fused_against_per_step(sd):
             f.run_stream(*args)
             res[fused] = [f.state(b) for b in (0, 1, 30, 31)]
             assert [f.flags(b) for b in range(B)] == [0] * B
-            assert cadences(sd, f) == ((3, 11) if fused else (0, 0))
+            assert counters(sd, f)[:2] == ((3, 11) if fused else (0, 0))
     for a, b in zip(res[1], res[0]):
         assert orc.rel_fro(a[0], b[0]) < PATH_TOL and orc.rel_fro(a[1], b[1]) < PATH_TOL
     assert np.array_equal(res[1][0][1], res[1][2][1]) and np.array_equal(res[1][1][0], res[1][3][0])   # replicas agree bit for bit
@@ -884,7 +853,7 @@ def test_trajectories_of_different_size_in_one_bank(sd):
         f.run_stream(*args)
         together = [f.state(b) for b in range(len(sizes))]
         assert [f.flags(b) for b in range(len(sizes))] == [0] * len(sizes)
-        assert cadences(sd, f)[0] >= 4
+        assert counters(sd, f).cadences >= 4
         assert [f.size(b) for b in range(len(sizes))] == [3 + 2 * N for N in sizes]
     for b, s in enumerate(streams):
         with sd.EkfSlam(n_max, batch=1) as f:
@@ -921,7 +890,7 @@ def test_q_zero_inside_a_cadence_sets_the_flag_and_stays_in_its_trajectory(sd):
         for b in range(2):
             f.set_state(means[b], starts[b], b)
         f.run_stream(*args)
-        assert cadences(sd, f)[0] >= 1
+        assert counters(sd, f).cadences >= 1
         assert f.flags(0) & 1 and f.flags(1) == 0         # EKF_FLAG_NONFINITE
         assert not np.isfinite(f.mean(0)).all()
         mu1, P1 = f.state(1)

@@ -20,6 +20,7 @@ import pytest
 
 from oracle import ekf_oracle as orc
 from tests import parity_blocks as pb
+from tests.gpu_support import counters, sd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -157,17 +158,6 @@ def oracle():
     pool.shutdown(wait=True, cancel_futures=True)
 
 
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-def chained(sd, f):
-    return int(sd.load_library().ekf_debug_chained(f._h))
-
-
 # ----------------------------------------------------------------------------------------------------------------------
 # C. the chained legs as benchmarked
 # ----------------------------------------------------------------------------------------------------------------------
@@ -201,7 +191,7 @@ def test_chained_leg_as_benchmarked(sd, oracle, name):
         f.flush()
         pose_w, lms_w = (np.array(a) for a in f.marginals(0))             # read-only: the schedule stays as benchmarked
         cad_w = f.cadence_counters()
-        chained_w = chained(sd, f)
+        chained_w = counters(sd, f).chained
         f.set_option("profile_stride", profile_stride(name))
         f.profile_enable(True)
         f.stream_run(warm, steps)
@@ -210,7 +200,7 @@ def test_chained_leg_as_benchmarked(sd, oracle, name):
         passes = f.profile_passes()
         f.profile_enable(False)
         cad = f.cadence_counters()
-        n_chained = chained(sd, f)
+        n_chained = counters(sd, f).chained
         kernel = f.last_pass()
         flags = f.flags()
         mu, P = f.state()
@@ -258,7 +248,7 @@ def test_chained_revisits_n2000(sd, oracle):
             f.set_state_diag(s[0], s[1])
             f.run_stream(*s[2:])
             cad = f.cadence_counters()
-            res[mode] = f.state() + (chained(sd, f), f.flags(), f.last_pass())
+            res[mode] = f.state() + (counters(sd, f).chained, f.flags(), f.last_pass())
         assert res[mode][3] == 0, mode
         assert cad == (steps * M // 40, steps), (mode, cad)
     print(f"\nrevisits N=2000: pass {res['chain'][4]}, chained {res['chain'][2]}")
@@ -287,7 +277,7 @@ def test_chained_scattered_n8000(sd, oracle):
         f.set_state_diag(s[0], s[1])
         f.run_stream(*s[2:])
         cad = f.cadence_counters()
-        n_chained, kernel = chained(sd, f), f.last_pass()
+        n_chained, kernel = counters(sd, f).chained, f.last_pass()
         rows = np.concatenate([f.covariance_block(0, 0, 3, n)] + [f.covariance_block(3 + 2 * int(j), 0, 2, n) for j in obs])
         assert f.flags() == 0
         mu, P = f.state()
@@ -328,7 +318,7 @@ def test_two_chained_handles_from_two_host_threads(sd):
             if barrier is not None:
                 barrier.wait()
             f.stream_run(0, steps)
-            out[slot] = f.state() + (f.flags(), chained(sd, f))
+            out[slot] = f.state() + (f.flags(), counters(sd, f).chained)
 
     alone, together = [None, None], [None, None]
     for t in range(2):

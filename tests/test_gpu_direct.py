@@ -19,33 +19,12 @@ from tests import direct_model as dm
 from tests import parity_blocks as pb
 from tests import update_cases as uc
 from tests.conftest import path_ran
+from tests.gpu_support import bank, sd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 TIGHT = 1e-9
 EKF_ERR_ARG, EKF_ERR_STATE = -1, -3
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-def bank(sd, streams, steps=None, config=None, run=True):
-    """A bank over `streams` (one synthetic stream per trajectory, equal shapes), the whole stream uploaded and its first
-    `steps` steps run."""
-    B, n = len(streams), len(streams[0][0])
-    f = sd.EkfSlam(n, batch=B, config=config)
-    for b, s in enumerate(streams):
-        f.set_state_diag(s[0], s[1], b)
-    f.stream_upload(np.stack([s[2] for s in streams], 1), np.stack([s[3] for s in streams], 1),
-                    np.stack([s[4] for s in streams], 1), np.stack([s[5] for s in streams], 1),
-                    np.stack([s[6] for s in streams], 1))
-    if run:
-        f.stream_run(0, steps if steps is not None else len(streams[0][2]))
-    return f
 
 
 def check_against_model(f, b, before, fix, res, gate=np.inf):
@@ -67,11 +46,6 @@ def check_against_model(f, b, before, fix, res, gate=np.inf):
     return mu, P
 
 
-def active_of(P, init_var):
-    """The landmarks of a reference covariance that have been observed (or fixed) at some time."""
-    return pb.landmark_classes(P, [], init_var)[0]
-
-
 def test_small_state_on_both_paths(sd, both_paths):
     """N = 20, 30 steps (landmarks 16 .. 19 never observed): a pose fix plus two landmark fixes, one of them on a
     never-observed landmark, on the small-state path and on the general kernels; one more step."""
@@ -86,7 +60,7 @@ def test_small_state_on_both_paths(sd, both_paths):
         want = orc.ekf_step_dense(mu, P, s[2][dm.SMALL_STEPS], s[3][dm.SMALL_STEPS], s[4][dm.SMALL_STEPS], s[5][dm.SMALL_STEPS], s[6][dm.SMALL_STEPS], orc.EkfConfig())
         got = f.state(0)
         assert orc.rel_fro(got[0], want[0]) <= TIGHT and orc.rel_fro(got[1], want[1]) <= TIGHT
-        err = pb.assert_filter_close(got[0], got[1], want[0], want[1], active_of(want[1], f.config.landmark_init_var),
+        err = pb.assert_filter_close(got[0], got[1], want[0], want[1], pb.active_of(want[1], f.config.landmark_init_var),
                                      mean0=mu, diag0=np.diag(P), tol=TIGHT, what="the step behind it: ")
         print("the step behind it:", pb.fmt(err))
         assert path_ran(f, both_paths)
@@ -249,7 +223,7 @@ def test_life_goes_on(sd, step_between):
             e = orc.rel_fro(mu, om), orc.rel_fro(P, oP)
             print("trajectory %d: rel_fro mean %.2e cov %.2e" % ((b,) + e))
             assert max(e) <= TIGHT
-            err = pb.assert_filter_close(mu, P, om, oP, active_of(oP, f.config.landmark_init_var), tol=TIGHT,
+            err = pb.assert_filter_close(mu, P, om, oP, pb.active_of(oP, f.config.landmark_init_var), tol=TIGHT,
                                          what=f"trajectory {b}: ")
             print("trajectory %d: %s" % (b, pb.fmt(err)))
 

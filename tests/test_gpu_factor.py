@@ -21,23 +21,13 @@ import pytest
 from oracle import ekf_oracle as orc
 from tests import factor_model as fm
 from tests.conftest import path_ran
+from tests.factor_model import EPS, gamma
+from tests.gpu_support import sd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-EPS = 2.0 ** -53
 EKF_ERR_ARG, EKF_ERR_STATE = -1, -3
 _dp = C.POINTER(C.c_double)
-
-
-def gamma(k):
-    return k * EPS / (1.0 - k * EPS)
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
 
 
 def check_factor(name, U, logdet, P, kappa=None):

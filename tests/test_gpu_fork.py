@@ -4,7 +4,6 @@ A copy is exact and moves stored values only: every case compares mean and covar
 source taken just before, then, where the filters go on, twins with each other bit for bit and with the oracle run from that
 download.  Each case names the path that ran (path_ran, cadence_counters / ekf_debug_chained, last_pass)."""
 import ctypes as C
-from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
@@ -12,7 +11,8 @@ import pytest
 from oracle import ekf_oracle as orc
 from tests import fork_model as fm
 from tests.conftest import path_ran
-from tests.test_gpu_nis_gate import gated_step
+from tests.gated_oracle import gated_step
+from tests.gpu_support import raw00, same, sd, tag  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,24 +21,6 @@ ORDER = 1e-11          # what the header guarantees between orders of summation
 EKF_ERR_ARG = -1
 FUZZ_RUNS = 4          # interleavings of the seeded soak (test_seeded_fuzz_against_the_model)
 FUZZ_OPS = 24
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-def same(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
-
-
-def raw00(sd, f, b=0):
-    """P_base[0, 0] of trajectory b as stored (no flush)."""
-    out = np.empty(1)
-    sd.load_library().ekf_debug_snapshot(f._h, b, 0, out.ctypes.data_as(C.POINTER(C.c_double)), 1)
-    return out[0]
 
 
 def bank(x, B):
@@ -216,8 +198,6 @@ def test_across_the_panel_boundary_at_size(sd):
 
 
 # ---- 7: the device association ---------------------------------------------------------------------------------------------
-def _tag(i, x, z):
-    return NS(tag_id=i, pose_R=np.eye(3), pose_t=np.array([[x], [0.0], [z]]), pose_err=0.0)
 
 
 def test_device_association_follows_the_state(sd):
@@ -227,7 +207,7 @@ def test_device_association_follows_the_state(sd):
     bz = {i: float(rng.uniform(0.4, 1.1)) for i in ids}
 
     def window(k, win_ids):
-        return [(k + 0.1 * fr, [_tag(i, bx[i] + rng.normal(0, 0.004), bz[i] + rng.normal(0, 0.004)) for i in win_ids])
+        return [(k + 0.1 * fr, [tag(i, bx[i] + rng.normal(0, 0.004), bz[i] + rng.normal(0, 0.004)) for i in win_ids])
                 for fr in range(2)]
 
     lib = sd.load_library()
@@ -368,7 +348,7 @@ def test_bad_arguments_change_nothing(sd):
 # ---- 11: the tuning sweep from a mapped state ----------------------------------------------------------------------------------
 def test_tune_noise_from_a_mapped_state(sd):
     import slam_duckietown_amd.evaluation as ev
-    from tests.test_gpu_innovations import wandering
+    from tests.streams import wandering
     N, steps = 12, 200
     n = 3 + 2 * N
     means, lin, ang, idx, zr, zb, m = wandering(N, 1, steps, 6, 9400)

@@ -14,18 +14,12 @@ import numpy as np
 import pytest
 
 from oracle import ekf_oracle as orc
+from tests.gpu_support import sd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 REL_TOL = 1e-6
 TIGHT = 1e-8          # (long random sequences from 1e4 initial variances: rounding grows a little beyond the 1e-9 of short runs)
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
 
 
 def close(a, b, what):

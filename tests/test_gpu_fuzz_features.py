@@ -14,7 +14,6 @@ noise(), never the log; the gate off where the main handle has a threshold no up
 handle's rows equal the config) and must stay bit-identical: states, flags and the scheduling counters.
 
 Every case names the path it ran; the last test asserts that the module reached each promise it makes."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -24,7 +23,8 @@ from oracle import ekf_oracle as orc
 from tests import fuzz_model as fm
 from tests import parity_blocks as pb
 from tests.conftest import path_ran
-from tests.test_gpu_nis_gate import check_gated_entries
+from tests.gated_oracle import check_gated_entries
+from tests.gpu_support import raw00, sd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -50,20 +50,6 @@ CASES = {
 PROMISES = {"removal_pending": 0, "marginals_pending": 0, "rejections": 0, "wraps": 0, "detections_distinct_noise": 0,
             "fallbacks": 0, "stale_refused": 0, "whole_bank_removal": 0}
 RAN = set()
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-def raw00(sd, f, b=0):
-    """P_base[0, 0] of trajectory b as stored (no flush)."""
-    out = np.empty(1)
-    sd.load_library().ekf_debug_snapshot(f._h, b, 0, out.ctypes.data_as(C.POINTER(C.c_double)), 1)
-    return out[0]
 
 
 def pending(sd, f, bank, b):

@@ -5,55 +5,19 @@ S (y to 1e-9 absolute, S and NIS to 1e-9 relative), where a dense oracle is affo
 stream on the per-step kernels (1e-10).  Switching the log on must change nothing: same bits of mean and covariance, same
 flags and scheduling counters as the same calls with the log off."""
 import ctypes as C
-from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
 
 from oracle import ekf_oracle as orc
 from tests.conftest import path_ran
+from tests.gated_oracle import AMAX, block_err, step_log, update_log
+from tests.gpu_support import final, same_bits, scheduling, sd, tag  # noqa: F401
+from tests.streams import dense_start, steps_of, wandering
 
 pytestmark = pytest.mark.gpu
 
 EKF_ERR_ARG = -1
-AMAX = 32
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-# ---- the oracle, restated with the innovations -------------------------------------------------------------------------
-def update_log(mean, cov, idx, ranges, bearings, cfg):
-    """orc.update_dense (src/replay_no_ros.py:436-480) that also returns every update's y and S.  (The covariance down-date
-    as cov - K (H cov): the same matrix as (I - K H) cov, in O(n^2).)"""
-    n = len(mean)
-    mean = np.array(mean, dtype=float)
-    Q = np.diag(cfg.meas_noise_diag())
-    ys, Ss = [], []
-    for j, zr, zb in zip(idx, ranges, bearings):
-        t = 3 + 2 * int(j)
-        y, h5 = orc.innovation_and_h5(mean[0:3], mean[t:t + 2], zr, zb)
-        H = np.zeros((2, n))
-        H[:, 0:3] = h5[:, 0:3]
-        H[:, t:t + 2] = h5[:, 3:5]
-        HP = H @ cov
-        S = HP @ H.T + Q
-        K = HP.T @ np.linalg.inv(S)
-        mean = mean + K @ y
-        cov = cov - K @ HP
-        ys.append(np.asarray(y, dtype=float).ravel())
-        Ss.append(S)
-    return mean, cov, np.array(ys).reshape(-1, 2), np.array(Ss).reshape(-1, 2, 2)
-
-
-def step_log(mean, cov, lin, ang, idx, ranges, bearings, cfg, predict=True):
-    if predict:
-        mean, cov = orc.predict_dense(mean, cov, lin, ang, cfg)
-    return update_log(mean, cov, idx, ranges, bearings, cfg)
 
 
 def check_entries(innov, k, b, idx, ys, Ss):
@@ -71,33 +35,6 @@ def check_entries(innov, k, b, idx, ys, Ss):
     assert np.isnan(innov.y[k, b, kept:W]).all() and np.isnan(innov.nis[k, b, kept:W]).all()
 
 
-def block_err(got, want):
-    """Largest relative (Frobenius) error of a stack of 2 x 2 blocks: S's off-diagonal entries are small differences of large
-    products, so each block is compared as a matrix."""
-    got, want = np.asarray(got).reshape(-1, 4), np.asarray(want).reshape(-1, 4)
-    return float(np.max(np.linalg.norm(got - want, axis=1) / np.linalg.norm(want, axis=1))) if len(want) else 0.0
-
-
-def counters(sd, f):
-    lib = sd.load_library()
-    a, b = C.c_long(), C.c_long()
-    assert lib.ekf_debug_cadences(f._h, C.byref(a), C.byref(b)) == 0
-    return (a.value, b.value, lib.ekf_debug_chained(f._h), lib.ekf_debug_lookaheads(f._h), f.profile_passes(),
-            lib.ekf_debug_small_launches(f._h), lib.ekf_debug_fused_fetches(f._h))
-
-
-def final(sd, f):
-    """Everything the log must not change: every trajectory's state and flags, and the scheduling counters."""
-    return [f.state(b) for b in range(f.batch)], [f.flags(b) for b in range(f.batch)], counters(sd, f)
-
-
-def same_bits(a, b):
-    (sa, fa, ca), (sb, fb, cb) = a, b
-    for (ma, Pa), (mb, Pb) in zip(sa, sb):
-        assert np.array_equal(ma, mb) and np.array_equal(Pa, Pb)
-    assert fa == fb and ca == cb
-
-
 def stream_oracle(means, starts, lin, ang, idx, zr, zb, m, cfg, B):
     """Per trajectory and stream step: (idx, y, S) of every update."""
     out = []
@@ -110,46 +47,6 @@ def stream_oracle(means, starts, lin, ang, idx, zr, zb, m, cfg, B):
             rows.append((idx[k, b, :mb], ys, Ss))
         out.append(rows)
     return out
-
-
-def wandering(N, B, steps, hi, seed):
-    """Per trajectory and step m ~ uniform{0..hi} landmarks at scattered indices (tests/test_gpu_cadence.py's stream)."""
-    rng = np.random.default_rng(seed)
-    world = [orc.synthetic_world(N, seed + 1 + t) for t in range(B)]
-    cfg = orc.EkfConfig()
-    lin = np.full((steps, B), 0.004)
-    ang = np.where(np.arange(steps)[:, None] % 7 == 6, 0.005, 0.02) * np.ones((1, B))
-    idx = np.zeros((steps, B, 16), dtype=np.int32)
-    zr = np.zeros((steps, B, 16))
-    zb = np.zeros((steps, B, 16))
-    m = np.zeros((steps, B), dtype=np.int32)
-    pose = [np.zeros(3) for _ in range(B)]
-    for k in range(steps):
-        for b in range(B):
-            pose[b], _ = orc.motion_model(pose[b], lin[k, b], ang[k, b], cfg)
-            mb = int(rng.integers(0, hi + 1))
-            vis = rng.choice(N, size=mb, replace=False)
-            d = world[b][1][vis] - pose[b][0:2]
-            c, s = np.cos(pose[b][2]), np.sin(pose[b][2])
-            xr = c * d[:, 0] + s * d[:, 1] + rng.normal(0, 0.01, mb)
-            yr = -s * d[:, 0] + c * d[:, 1] + rng.normal(0, 0.01, mb)
-            m[k, b] = mb
-            idx[k, b, :mb] = vis
-            zr[k, b, :mb] = np.hypot(xr, yr)
-            zb[k, b, :mb] = np.arctan2(yr, xr)
-    return [w[2] for w in world], lin, ang, idx, zr, zb, m
-
-
-def dense_start(n, seed):
-    rng = np.random.default_rng(seed)
-    A = rng.normal(size=(n, 6)) * 0.3
-    P = A @ A.T
-    P[np.arange(n), np.arange(n)] += rng.uniform(0.5, 2.0, n)
-    return P
-
-
-def steps_of(streams, k):
-    return tuple(np.stack([s[i][k] for s in streams]) if i >= 4 else np.array([s[i][k] for s in streams]) for i in (2, 3, 4, 5, 6))
 
 
 # ---- per-step kernels, update passes, the small-state path ---------------------------------------------------------------
@@ -250,10 +147,6 @@ def test_small_state_steps_against_the_oracle(sd, both_paths):
         check_entries(innov, k, 0, s[4][k], ys, Ss)
 
 
-def _tag(i, x, z):
-    return NS(tag_id=i, pose_R=np.eye(3), pose_t=np.array([[x], [0.0], [z]]), pose_err=0.0)
-
-
 def test_step_detections_with_more_than_sixteen_tags(sd):
     """ekf_step_detections with 20 distinct tags in one window (two update passes, one logged step): idx in the device
     association's order (ekf_download_tags), y and S against the oracle's association + augmentation + step."""
@@ -267,7 +160,7 @@ def test_step_detections_with_more_than_sixteen_tags(sd):
         f.log_innovations(8)
         om, oP, oti = np.zeros(3), np.eye(3) * 0.1, {}
         for k, (win_ids, lin, ang) in enumerate(plan):
-            win = [(k + 0.1 * fr, [_tag(i, bx[i] + rng.normal(0, 0.004), bz[i] + rng.normal(0, 0.004)) for i in win_ids])
+            win = [(k + 0.1 * fr, [tag(i, bx[i] + rng.normal(0, 0.004), bz[i] + rng.normal(0, 0.004)) for i in win_ids])
                    for fr in range(3)]
             f.step_detections(lin, ang, win)
             tags = orc.associate(win, oti, om, cfg)
@@ -306,7 +199,7 @@ def test_packed_cadences_on_a_variable_m_stream(sd, chain):
     _, off = run(False)
     same_bits(on, off)
     assert on[2][0] > 1 and on[2][1] == steps                   # fused cadences ran the whole stream
-    assert (on[2][2] > 0) == bool(chain)
+    assert (on[2].chained > 0) == bool(chain)
     assert (innov.m == m).all()
     ref = stream_oracle(means, starts, lin, ang, idx, zr, zb, m, orc.EkfConfig(), B)
     for b in range(B):
@@ -368,7 +261,7 @@ def test_large_banks_against_the_per_step_kernels(sd, N, B, steps, opts):
             for b, s in enumerate(streams):
                 f.set_state_diag(s[0], s[1], b)
             f.run_stream(*args)
-            res = (f.innovations() if log else None), [f.mean(b) for b in range(B)], counters(sd, f)
+            res = (f.innovations() if log else None), [f.mean(b) for b in range(B)], scheduling(sd, f)
             return res
 
     fused, ref = run(True, 1), run(True, 0)
@@ -377,7 +270,7 @@ def test_large_banks_against_the_per_step_kernels(sd, N, B, steps, opts):
         assert np.array_equal(a, b)
     assert fused[2] == plain[2] and fused[2][0] > 0
     if (N, B) == (2000, 1):
-        assert fused[2][2] > 0                                  # chained
+        assert fused[2].chained > 0
     i, r = fused[0], ref[0]
     assert (i.m == r.m).all() and (i.idx == r.idx).all() and (i.m == 8).all()
     np.testing.assert_allclose(i.y, r.y, rtol=0, atol=1e-10)

@@ -5,7 +5,6 @@ Tolerance against the model: entrywise |got - ref| <= 1e-13 x bound, bound = |J|
 of the bound, the device's sin / cos add about 1e-15: 1e-13 is roughly 25 x headroom over a derived 4e-15.  What a join
 only moves, or leaves, is compared bit for bit.  Runs that go on are compared with the oracle at the project's TIGHT."""
 import ctypes as C
-from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
@@ -13,34 +12,14 @@ import pytest
 from oracle import ekf_oracle as orc
 from tests import join_model as jm
 from tests.conftest import path_ran
+from tests.gpu_support import col, raw00, same, sd, tag, within_bounds  # noqa: F401
+from tests.streams import FRAME, stream_from
 
 pytestmark = pytest.mark.gpu
 
 TIGHT = 1e-10          # the project's bar for a run against the oracle (tests/test_gpu_remove_landmarks.py)
 TOL = 1e-13            # x the entrywise bound (see above)
 EKF_ERR_ARG, EKF_ERR_STATE = -1, -3
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-def same(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
-
-
-def raw00(sd, f, b=0):
-    """P_base[0, 0] of trajectory b as stored (no flush)."""
-    out = np.empty(1)
-    sd.load_library().ekf_debug_snapshot(f._h, b, 0, out.ctypes.data_as(C.POINTER(C.c_double)), 1)
-    return out[0]
-
-
-def col(x):
-    return x[:, None]
 
 
 def mapped(sd, N, n_max, steps, m, seed, general=False, batch=1, online=0):
@@ -68,35 +47,8 @@ def mapped(sd, N, n_max, steps, m, seed, general=False, batch=1, online=0):
 def check_model(got, A, B, T=None, cT=None, label=""):
     """`got` against the dense model of joining state B to state A; prints the worst ratio to the bound before it asserts."""
     xm, Pm, bound, mbound = jm.join_dense(A[0], A[1], B[0], B[1], T, cT)
-    assert got[0].shape == xm.shape and got[1].shape == Pm.shape
-    eP, em = np.abs(got[1] - Pm), np.abs(got[0] - xm)
-    rP = float(np.max(eP / np.where(bound > 0, bound, 1.0))) if eP.size else 0.0
-    rm = float(np.max(em / np.where(mbound > 0, mbound, 1.0))) if em.size else 0.0
-    print(f"{label}: worst covariance error / bound {rP:.3g}, mean {rm:.3g}")
-    assert (eP <= TOL * bound).all() and (em <= TOL * mbound).all()
-    assert np.array_equal(got[1], got[1].T)
+    within_bounds(got, xm, Pm, bound, mbound, TOL, label)
     return xm, Pm
-
-
-def stream_from(mean, steps, m, seed):
-    """A synthetic stream consistent with a filter's own estimate: the robot starts at the mean's pose and observes the mean's
-    landmarks in turn (the construction of oracle.synthetic_stream)."""
-    cfg, rng = orc.EkfConfig(), np.random.default_rng(seed)
-    lm, pose, N = mean[3:].reshape(-1, 2), mean[:3].copy(), (len(mean) - 3) // 2
-    lin, ang = np.full(steps, 0.004), np.full(steps, 0.02)
-    idx, zr, zb = np.zeros((steps, m), dtype=np.int32), np.zeros((steps, m)), np.zeros((steps, m))
-    for k in range(steps):
-        pose, _ = orc.motion_model(pose, lin[k], ang[k], cfg)
-        vis = (m * k + np.arange(m)) % N
-        d = lm[vis] - pose[:2]
-        c, s = np.cos(pose[2]), np.sin(pose[2])
-        xr = c * d[:, 0] + s * d[:, 1] + rng.normal(0.0, 0.01, m)
-        yr = -s * d[:, 0] + c * d[:, 1] + rng.normal(0.0, 0.01, m)
-        idx[k], zr[k], zb[k] = vis, np.sqrt(xr ** 2 + yr ** 2), np.arctan2(yr, xr)
-    return lin, ang, idx, zr, zb
-
-
-FRAME = (np.array([0.7, -0.4, 2.1]), np.array([[0.04, 0.01, -0.002], [0.01, 0.09, 0.003], [-0.002, 0.003, 0.002]]))
 
 
 # ---- 1: the smallest joins, both paths ---------------------------------------------------------------------------------------
@@ -271,8 +223,6 @@ def test_the_filter_goes_on(sd, NA, NB, n_max, small):
 
 
 # ---- 7: the submapping recipe end to end ------------------------------------------------------------------------------------
-def _tag(i, x, z):
-    return NS(tag_id=i, pose_R=np.eye(3), pose_t=np.array([[x], [0.0], [z]]), pose_err=0.0)
 
 
 def test_submapping_recipe(sd):
@@ -291,7 +241,7 @@ def test_submapping_recipe(sd):
         for i in win_ids:
             d = world[i] - truth[:2]
             xr, yr = c * d[0] + s * d[1] + rng.normal(0, 0.004), -s * d[0] + c * d[1] + rng.normal(0, 0.004)
-            tags.append(_tag(i, -yr, xr))
+            tags.append(tag(i, -yr, xr))
         return [(float(k), tags)]
 
     with sd.EkfSlam(3 + 2 * 8) as loc, sd.EkfSlam(3 + 2 * 12) as glob:

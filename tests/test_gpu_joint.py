@@ -14,6 +14,7 @@ from oracle import ekf_oracle as orc
 from tests import assoc_world as aw
 from tests import joint_world as jw
 from tests.conftest import path_ran
+from tests.gpu_support import pbase, sd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -23,24 +24,8 @@ EKF_ERR_ARG = -1
 EKF_JMAX = 64
 
 
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
 def sub_idx(sel):
     return [0, 1, 2] + [3 + 2 * int(j) + d for j in sel for d in range(2)]
-
-
-def pbase(sd, f, b):
-    """P_base of trajectory b, raw, no flush"""
-    lib = sd.load_library()
-    have = lib.ekf_debug_snapshot(f._h, b, 0, None, 0)
-    out = np.empty(have)
-    assert lib.ekf_debug_snapshot(f._h, b, 0, out.ctypes.data_as(C.POINTER(C.c_double)), out.size) == have
-    return out
 
 
 def query_untouched(sd, f, sels, bs):

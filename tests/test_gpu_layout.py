@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 
 from oracle import ekf_oracle as orc
+from tests.gpu_support import close, counters, sd  # noqa: F401
+from tests.streams import dense_start
 
 pytestmark = pytest.mark.gpu
 
@@ -23,34 +25,6 @@ TIGHT = 1e-9
 PPW = 4096                                             # panel width (doubles)
 N_TWO = 2100                                           # n = 4203: panel 0 full, panel 1 holds 107 columns
 EDGE = [2045, 2046, 2047]                              # state indices (4093, 4094), (4095, 4096), (4097, 4098)
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-def cadences(sd, f):
-    lib = sd.load_library()
-    a, b = C.c_long(), C.c_long()
-    assert lib.ekf_debug_cadences(f._h, C.byref(a), C.byref(b)) == 0
-    return a.value, b.value
-
-
-def close(a, b, tol=TIGHT):
-    r = orc.rel_fro(a, b)
-    assert r < REL_TOL, f"rel Frobenius {r:.3e} exceeds the 1e-6 bar"
-    assert r < tol, f"rel Frobenius {r:.3e} exceeds the expected {tol:g}"
-
-
-def dense_start(n, seed, rank=6):
-    rng = np.random.default_rng(seed)
-    A = rng.normal(size=(n, rank)) * 0.3
-    P = A @ A.T
-    P[np.arange(n), np.arange(n)] += rng.uniform(0.5, 2.0, n)
-    return P
 
 
 def edge_stream(N, steps, m, seed):
@@ -125,7 +99,7 @@ def test_steps_on_the_panel_boundary_against_the_oracle(sd, path):
         args = [np.stack([s[i] for s in streams], 1) for i in (2, 3, 4, 5, 6)]
         if path.startswith("fused"):
             f.run_stream(*args)
-            cad, covered = cadences(sd, f)
+            cad, covered = counters(sd, f)[:2]
             assert cad >= 2 and covered >= 10
         else:
             for k in range(steps):

@@ -24,33 +24,12 @@ from tests import linear_model as lm
 from tests import parity_blocks as pb
 from tests import update_cases as uc
 from tests.conftest import path_ran
+from tests.gpu_support import bank, sd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 TIGHT = 1e-9
 EKF_ERR_ARG, EKF_ERR_STATE = -1, -3
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-def bank(sd, streams, steps=None, config=None, run=True):
-    """A bank over `streams` (one synthetic stream per trajectory, equal shapes), the whole stream uploaded and its first
-    `steps` steps run."""
-    B, n = len(streams), len(streams[0][0])
-    f = sd.EkfSlam(n, batch=B, config=config)
-    for b, s in enumerate(streams):
-        f.set_state_diag(s[0], s[1], b)
-    f.stream_upload(np.stack([s[2] for s in streams], 1), np.stack([s[3] for s in streams], 1),
-                    np.stack([s[4] for s in streams], 1), np.stack([s[5] for s in streams], 1),
-                    np.stack([s[6] for s in streams], 1))
-    if run:
-        f.stream_run(0, steps if steps is not None else len(streams[0][2]))
-    return f
 
 
 def check_against_model(f, b, before, meas, res, innovation=False, gate=np.inf):
@@ -73,11 +52,6 @@ def check_against_model(f, b, before, meas, res, innovation=False, gate=np.inf):
     return wm, wP
 
 
-def active_of(P, init_var):
-    """The landmarks of a reference covariance that have been observed (or tied in) at some time."""
-    return pb.landmark_classes(P, [], init_var)[0]
-
-
 def test_small_state_on_both_paths(sd, both_paths):
     """N = 20, 30 steps: a dense H with D = 7 over the pose and three landmarks in z mode, on the small-state path and on the
     general kernels; one more step."""
@@ -96,7 +70,7 @@ def test_small_state_on_both_paths(sd, both_paths):
         e = orc.rel_fro(got[0], want[0]), orc.rel_fro(got[1], want[1])
         print("the step behind it: rel_fro mean %.2e cov %.2e" % e)
         assert max(e) <= TIGHT
-        err = pb.assert_filter_close(got[0], got[1], want[0], want[1], active_of(want[1], f.config.landmark_init_var),
+        err = pb.assert_filter_close(got[0], got[1], want[0], want[1], pb.active_of(want[1], f.config.landmark_init_var),
                                      mean0=mu, diag0=np.diag(P), tol=TIGHT, what="the step behind it: ")
         print("the step behind it:", pb.fmt(err))
         assert path_ran(f, both_paths)
@@ -207,7 +181,7 @@ def test_bank_with_ranks_pending_gate_untouched_rest_and_the_bound(sd):
             print("trajectory %d after ten more steps: rel_fro mean %.2e cov %.2e" % ((b,) + e))
             assert max(e) <= TIGHT
             # (trajectory 1 carries the entrywise difference of its update along: update_cases.DENSE_NEVER)
-            err = pb.assert_filter_close(mu, P, after[b][0], after[b][1], active_of(after[b][1], f.config.landmark_init_var),
+            err = pb.assert_filter_close(mu, P, after[b][0], after[b][1], pb.active_of(after[b][1], f.config.landmark_init_var),
                                          tol=TIGHT, what=f"trajectory {b} after ten more steps: ",
                                          corr_tol=uc.dense_never_bounds(meas[b][0], before[b][1])[0])
             print("trajectory %d after ten more steps: %s" % (b, pb.fmt(err)))

@@ -10,19 +10,13 @@ import pytest
 
 from oracle import ekf_oracle as orc
 from tests.conftest import path_ran
+from tests.gpu_support import pbase, sd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 PATH_TOL = 1e-11
 TIGHT = 1e-9
 EKF_ERR_ARG = -1
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
 
 
 def blocks_of(P, nl):
@@ -37,23 +31,14 @@ def stacked_err(got, want):
     return orc.rel_fro(g, w)
 
 
-def pbase(sd, f, b, count=1 << 24):
-    """(the leading part of) P_base of trajectory b, raw, no flush"""
-    lib = sd.load_library()
-    have = lib.ekf_debug_snapshot(f._h, b, 0, None, 0)
-    out = np.empty(min(have, count))
-    assert lib.ekf_debug_snapshot(f._h, b, 0, out.ctypes.data_as(C.POINTER(C.c_double)), out.size) == have
-    return out
-
-
 def query_untouched(sd, f, bs):
     """marginals() of the whole bank, asserting that it ran no pass and wrote nothing of P_base."""
-    before = [pbase(sd, f, b) for b in bs]
+    before = [pbase(sd, f, b, 1 << 24) for b in bs]
     passes = f.profile_passes()
     res = f.marginals()
     assert f.profile_passes() == passes
     for b, p in zip(bs, before):
-        assert np.array_equal(pbase(sd, f, b), p)
+        assert np.array_equal(pbase(sd, f, b, 1 << 24), p)
     return res
 
 

@@ -14,104 +14,14 @@ import pytest
 
 from oracle import ekf_oracle as orc
 from tests.conftest import path_ran
-from tests.test_gpu_innovations import _tag, block_err, counters, dense_start, final, same_bits, steps_of, wandering
+from tests.gated_oracle import AMAX, G, check_gated_entries, gated_step, gated_update, margin
+from tests.gpu_support import final, same_bits, scheduling, sd, tag  # noqa: F401
+from tests.streams import dense_start, inject, observed_start, wandering
 
 pytestmark = pytest.mark.gpu
 
 EKF_ERR_ARG = -1
-AMAX = 32
-G = 25.0                # threshold of the gated runs
 INERT = 1e300           # a threshold no update reaches
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-# ---- the oracle, gated -------------------------------------------------------------------------------------------------------
-def gated_update(mean, cov, idx, ranges, bearings, cfg, g):
-    """orc.update_dense (src/replay_no_ros.py:436-480) with the gate: an update whose NIS exceeds g leaves mean and covariance
-    as they are.  Returns the state and, per update, y, S, NIS and the decision."""
-    n = len(mean)
-    mean = np.array(mean, dtype=float)
-    Q = np.diag(cfg.meas_noise_diag())
-    ys, Ss, nis, rej = [], [], [], []
-    for j, zr, zb in zip(idx, ranges, bearings):
-        t = 3 + 2 * int(j)
-        y, h5 = orc.innovation_and_h5(mean[0:3], mean[t:t + 2], zr, zb)
-        y = np.asarray(y, dtype=float).ravel()
-        H = np.zeros((2, n))
-        H[:, 0:3] = h5[:, 0:3]
-        H[:, t:t + 2] = h5[:, 3:5]
-        HP = H @ cov
-        S = HP @ H.T + Q
-        v = float(y @ np.linalg.solve(S, y))
-        ys.append(y)
-        Ss.append(S)
-        nis.append(v)
-        rej.append(v > g)
-        if v > g:
-            continue
-        K = HP.T @ np.linalg.inv(S)
-        mean = mean + K @ y
-        cov = cov - K @ HP
-    return mean, cov, np.array(ys).reshape(-1, 2), np.array(Ss).reshape(-1, 2, 2), np.array(nis), np.array(rej, dtype=bool)
-
-
-def gated_step(mean, cov, lin, ang, idx, ranges, bearings, cfg, g, predict=True):
-    if predict:
-        # orc.predict_dense (:368-430) in O(n^2): G only mixes the pose's rows and columns
-        pose, Gm = orc.motion_model(mean[0:3], lin, ang, cfg)
-        mean, cov = np.array(mean, dtype=float), np.array(cov, dtype=float)
-        if not cfg.disable_motion_model:
-            mean[0:3] = pose
-        cov[0:3, :] = Gm @ cov[0:3, :]
-        cov[:, 0:3] = cov[:, 0:3] @ Gm.T
-        cov[0:3, 0:3] += np.diag(cfg.motion_noise_diag())
-    return gated_update(mean, cov, idx, ranges, bearings, cfg, g)
-
-
-def inject(zr, zb, where):
-    """Outliers at (step, [trajectory,] landmark) positions: range + 20 m."""
-    zr = np.array(zr, dtype=float)
-    for pos in where:
-        zr[pos] += 20.0
-    return zr, np.array(zb, dtype=float)
-
-
-def margin(nis, rej, injected, g=G):
-    """The test's own margin: injected updates at >= 2 g, the others at <= g / 2."""
-    nis, injected = np.asarray(nis), np.asarray(injected, dtype=bool)
-    assert injected.any() and (nis[injected] >= 2 * g).all(), nis[injected]
-    assert (nis[~injected] <= g / 2).all(), nis[~injected].max()
-    assert (np.asarray(rej) == injected).all()
-
-
-def observed_start(N, seed):
-    """A start whose landmarks have been observed before: means at synthetic_stream's true positions (its world `seed`),
-    variance 0.01 (a first observation, with its prior variance of 1e4, is never an outlier)."""
-    _, lm, mean0, diag0 = orc.synthetic_world(N, seed)
-    mean0 = mean0.copy()
-    mean0[3:] = lm.ravel()
-    diag0 = diag0.copy()
-    diag0[3:] = 0.01
-    return mean0, diag0
-
-
-def check_gated_entries(innov, k, b, idx, ys, Ss, nis, rej):
-    """Row k, trajectory b of a log against the gated oracle: rejected entries carry the true y, S and NIS."""
-    m = len(idx)
-    assert innov.m[k, b] == m
-    kept = min(m, AMAX)
-    assert list(innov.idx[k, b, :kept]) == [int(i) for i in idx[:kept]]
-    np.testing.assert_allclose(innov.y[k, b, :kept], ys[:kept], rtol=0, atol=1e-9)
-    assert block_err(innov.S[k, b, :kept], Ss[:kept]) < 1e-9
-    np.testing.assert_allclose(innov.nis[k, b, :kept], nis[:kept], rtol=1e-9, atol=0)
-    assert innov.rejected[k, b, :kept].tolist() == [int(r) for r in rej[:kept]]
-    assert (innov.rejected[k, b, kept:] == -1).all()
 
 
 def log_flags_match_nis(innov):
@@ -279,7 +189,7 @@ def test_step_detections_with_more_than_sixteen_tags(sd):
         for k, (win_ids, lin, ang, bad) in enumerate(plan):
             def det(i):
                 x = bx[i] + rng.normal(0, 0.004)
-                return _tag(i, x, -bz[i] if i == bad else bz[i] + rng.normal(0, 0.004))
+                return tag(i, x, -bz[i] if i == bad else bz[i] + rng.normal(0, 0.004))
             win = [(k + 0.1 * fr, [det(i) for i in win_ids]) for fr in range(3)]
             f.step_detections(lin, ang, win)
             new = [i for i in win_ids if i not in oti]
@@ -335,11 +245,11 @@ def test_packed_cadences_against_the_gated_oracle(sd, chain, N, B, steps, hi):
     off, inert, on = run(None), run(INERT), run(G)
     same_bits(inert[2], off[2])
     assert on[2][2] == off[2][2]
-    assert on[2][2][0] > 1 and on[2][2][1] == steps
+    assert on[2][2].cadences > 1 and on[2][2].covered == steps
     if chain:
-        assert on[2][2][2] > 0                                  # ekf_debug_chained
+        assert on[2][2].chained > 0
     else:
-        assert on[2][2][3] > 0                                  # ekf_debug_lookaheads
+        assert on[2][2].lookaheads > 0
     log_flags_match_nis(on[0])
     cfg = orc.EkfConfig()
     for b in range(B):
@@ -387,7 +297,7 @@ def test_stream_pieces_ending_mid_cadence(sd, run_end_flush):
 
     off, inert, on = run(None), run(INERT), run(G)
     same_bits(inert[2], off[2])
-    assert on[2][2] == off[2][2] and on[2][2][0] > 0
+    assert on[2][2] == off[2][2] and on[2][2].cadences > 0
     cfg = orc.EkfConfig()
     om, oP = s[0].copy(), P0.copy()
     nis_all, rej_all, injected = [], [], []
@@ -427,7 +337,7 @@ def test_large_banks_gated_equal_per_step_and_outliers_removed(sd, N, B, steps, 
             for b, s in enumerate(streams):
                 f.set_state_diag(s[0], s[1], b)
             f.run_stream(lin, ang, idx, zr, zb, m)
-            return f.innovations(), f.gate_counts(), [f.mean(b) for b in range(B)], None, counters(sd, f)
+            return f.innovations(), f.gate_counts(), [f.mean(b) for b in range(B)], None, scheduling(sd, f)
 
     fused, per_step = run(G, 1), run(G, 0)
     off, inert = run(None, 1), run(INERT, 1)

@@ -9,22 +9,15 @@ import pytest
 
 from oracle import ekf_oracle as orc
 from tests.conftest import path_ran
-from tests.test_gpu_innovations import block_err, counters, dense_start, final, same_bits, wandering
-from tests.test_gpu_nis_gate import gated_step, inject, margin, observed_start
+from tests.gated_oracle import AMAX, block_err, gated_step, margin
+from tests.gpu_support import counters, final, same_bits, sd  # noqa: F401
+from tests.streams import dense_start, inject, observed_start, wandering
 
 pytestmark = pytest.mark.gpu
 
 EKF_ERR_ARG = -1
-AMAX = 32
 G = 25.0
 BASE = orc.EkfConfig()
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
 
 
 def sigmas(B, seed):
@@ -131,8 +124,8 @@ def test_packed_cadences_distinct_rows(sd, chain, N, B, steps, hi):
             f.set_state(means[b], P0[b], b)
         f.run_stream(lin, ang, idx, zr, zb, m)
         c = counters(sd, f)
-        assert c[0] > 1 and c[1] == steps
-        assert (c[2] > 0) if chain else (c[3] > 0)
+        assert c.cadences > 1 and c.covered == steps
+        assert (c.chained > 0) if chain else (c.lookaheads > 0)
         ref = oracle_stream(means, P0, lin, ang, idx, zr, zb, m, [cfg_of(ms, qs, b) for b in range(B)])
         check_log(f.innovations(), ref, m)
         check_states(f, ref)
@@ -222,7 +215,7 @@ def test_change_between_chained_stream_pieces(sd):
         f.stream_run(0, k)
         f.set_noise(ms2, qs2)
         f.stream_run(k, steps - k)
-        assert counters(sd, f)[2] > 0
+        assert counters(sd, f).chained > 0
         ref = oracle_stream(means, P0, lin, ang, idx, zr, zb, m, [cfg_of(ms, qs, b) for b in range(B)],
                             switch=(k, [cfg_of(ms2, qs2, b) for b in range(B)]))
         check_states(f, ref)

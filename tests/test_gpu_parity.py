@@ -11,24 +11,12 @@ from oracle import ekf_oracle as orc
 from tests import golden_util as gu
 from tests import parity_blocks as pb
 from tests.conftest import path_ran
+from tests.gpu_support import close, sd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 REL_TOL = 1e-6
 TIGHT = 1e-9
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()          # fails loudly if the HIP library is not built
-    return sd
-
-
-def close(a, b, tol=TIGHT):
-    r = orc.rel_fro(a, b)
-    assert r < REL_TOL, f"rel Frobenius {r:.3e} exceeds the 1e-6 bar"
-    assert r < tol, f"rel Frobenius {r:.3e} exceeds the expected {tol:g}"
 
 
 # ---------------------------------------------------------------------------------------------

@@ -14,23 +14,10 @@ import numpy as np
 import pytest
 
 from oracle import ekf_oracle as orc
+from tests.gpu_support import sd  # noqa: F401
+from tests.streams import dense_start
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-def dense_start(n, seed, rank=6):
-    rng = np.random.default_rng(seed)
-    A = rng.normal(size=(n, rank)) * 0.3
-    P = A @ A.T
-    P[np.arange(n), np.arange(n)] += rng.uniform(0.5, 2.0, n)
-    return P
 
 
 def bank_stream(Ns, steps, m, seed, visible=None):

@@ -12,7 +12,8 @@ import pytest
 from oracle import ekf_oracle as orc
 from tests.conftest import path_ran
 from tests.parity_blocks import PATH_CORR_TOL
-from types import SimpleNamespace as NS
+from tests.gpu_support import counters, final, same_bits, sd, tag  # noqa: F401
+from tests.streams import dense_start, steps_of
 
 pytestmark = pytest.mark.gpu
 
@@ -20,48 +21,9 @@ EKF_ERR_ARG = -1
 EKF_ERR_STATE = -3
 
 
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
 # ---- helpers -----------------------------------------------------------------------------------------------------------------
 G = 13.8                                                    # NIS gate of the gated cases: the chi-square(2) quantile at 0.999
 SLOTS = 40                                                  # landmark updates a cadence takes: "rank_limit" / 2, set by the tests
-
-
-def counters(sd, f):
-    lib = sd.load_library()
-    a, b = C.c_long(), C.c_long()
-    assert lib.ekf_debug_cadences(f._h, C.byref(a), C.byref(b)) == 0
-    return (a.value, b.value, lib.ekf_debug_chained(f._h), lib.ekf_debug_lookaheads(f._h), f.profile_passes(),
-            lib.ekf_debug_small_launches(f._h), lib.ekf_debug_fused_fetches(f._h), lib.ekf_debug_w_from_v(f._h), f.last_pass())
-
-
-def final(sd, f):
-    """Everything the log must not change: every trajectory's state and flags, and the scheduling counters."""
-    return [f.state(b) for b in range(f.batch)], [f.flags(b) for b in range(f.batch)], counters(sd, f)
-
-
-def same_bits(a, b):
-    (sa, fa, ca), (sb, fb, cb) = a, b
-    for (ma, Pa), (mb, Pb) in zip(sa, sb):
-        assert np.array_equal(ma, mb) and np.array_equal(Pa, Pb)
-    assert fa == fb and ca == cb
-
-
-def dense_start(n, seed):
-    rng = np.random.default_rng(seed)
-    A = rng.normal(size=(n, 6)) * 0.3
-    P = A @ A.T
-    P[np.arange(n), np.arange(n)] += rng.uniform(0.5, 2.0, n)
-    return P
-
-
-def steps_of(streams, k):
-    return tuple(np.stack([s[i][k] for s in streams]) if i >= 4 else np.array([s[i][k] for s in streams]) for i in (2, 3, 4, 5, 6))
 
 
 def variable_bank(N, B, steps, hi, seed):
@@ -71,7 +33,7 @@ def variable_bank(N, B, steps, hi, seed):
     return ([s[0] for s in st],) + tuple(np.stack([s[i] for s in st], axis=1) for i in (2, 3, 4, 5, 6, 7))
 
 
-def gated_step(mean, cov, lin, ang, idx, ranges, bearings, cfg, g=np.inf):
+def gated_step_count(mean, cov, lin, ang, idx, ranges, bearings, cfg, g=np.inf):
     """The oracle's step (predict_dense, then update_dense's sequential updates) with the NIS gate: an update whose NIS
     exceeds g leaves mean and covariance as they are.  Returns the state and the number of rejections."""
     mean, cov = orc.predict_dense(mean, cov, lin, ang, cfg)
@@ -171,7 +133,7 @@ def test_per_step_kernels_against_the_oracle(sd, fused_step):
             if log:
                 assert f.pose_steps == steps + 5
                 last_row_is_the_filter(f, trace)
-            return trace, final(sd, f)
+            return trace, final(sd, f, counters)
 
     trace, on = run(True)
     _, off = run(False)
@@ -240,7 +202,7 @@ def test_small_state_steps_and_stream(sd, both_paths):
             trace = f.poses() if log else None
             if log:
                 last_row_is_the_filter(f, trace)
-            return trace, final(sd, f)
+            return trace, final(sd, f, counters)
 
     for stream in (False, True):
         trace, on = run(True, stream)
@@ -307,13 +269,13 @@ def test_packed_cadences_on_a_variable_m_stream(sd, chain):
             if log:
                 assert f.pose_steps == steps
                 last_row_is_the_filter(f, trace)
-            return trace, final(sd, f)
+            return trace, final(sd, f, counters)
 
     trace, on = run(steps)
     _, off = run(0)
     same_bits(on, off)
     assert on[2][0] == max(p[1] for p in packs) and on[2][1] == steps   # fused cadences ran the whole stream, cut as restated
-    assert (on[2][2] > 0) == bool(chain)
+    assert (on[2].chained > 0) == bool(chain)
     short, on3 = run(3)                                         # cap below one cadence's steps: the last three rows
     same_bits(on3, off)
     assert short.first == steps - 3 and short.mean.shape[0] == 3
@@ -351,7 +313,7 @@ def test_stream_pieces_ending_mid_cadence(sd, run_end_flush):
             if log:
                 assert f.pose_steps == steps + 1
                 last_row_is_the_filter(f, trace)
-            return trace, final(sd, f)
+            return trace, final(sd, f, counters)
 
     trace, on = run(True)
     _, off = run(False)
@@ -461,7 +423,7 @@ def test_packed_cadences_with_the_gate_and_a_noise_bank(sd, chain):
             rejected = f.gate_counts().tolist() if gate else None
             if log:
                 last_row_is_the_filter(f, trace)
-            return trace, rejected, final(sd, f)
+            return trace, rejected, final(sd, f, counters)
 
     for gate, noise in ((True, True), (True, False), (False, True)):
         trace, rejected, on = run(True, gate, noise)
@@ -473,8 +435,8 @@ def test_packed_cadences_with_the_gate_and_a_noise_bank(sd, chain):
             om, oP, ref, nrej = means[b].copy(), starts[b].copy(), [], 0
             for k in range(steps):
                 mb = int(m[k, b])
-                om, oP, r = gated_step(om, oP, lin[k, b], ang[k, b], idx[k, b, :mb], zr[k, b, :mb], zb[k, b, :mb], cfg,
-                                       G if gate else np.inf)
+                om, oP, r = gated_step_count(om, oP, lin[k, b], ang[k, b], idx[k, b, :mb], zr[k, b, :mb], zb[k, b, :mb], cfg,
+                                             G if gate else np.inf)
                 nrej += r
                 ref.append((om[:3].copy(), oP[:3, :3].copy()))
             if gate:
@@ -509,7 +471,7 @@ def test_small_state_with_the_gate_and_a_noise_bank(sd, both_paths):
             rejected = f.gate_counts().tolist()
             if log:
                 last_row_is_the_filter(f, trace)
-            return trace, rejected, final(sd, f)
+            return trace, rejected, final(sd, f, counters)
 
     trace, rejected, on = run(True)
     _, rejected_off, off = run(False)
@@ -520,15 +482,11 @@ def test_small_state_with_the_gate_and_a_noise_bank(sd, both_paths):
         om, oP, ref, nrej = means[b].copy(), starts[b].copy(), [], 0
         for k in range(steps):
             mb = int(m[k, b])
-            om, oP, r = gated_step(om, oP, lin[k, b], ang[k, b], idx[k, b, :mb], zr[k, b, :mb], zb[k, b, :mb], cfg, G)
+            om, oP, r = gated_step_count(om, oP, lin[k, b], ang[k, b], idx[k, b, :mb], zr[k, b, :mb], zb[k, b, :mb], cfg, G)
             nrej += r
             ref.append((om[:3].copy(), oP[:3, :3].copy()))
         assert rejected[b] == nrej
         check_rows(trace, b, ref)
-
-
-def _tag(i, x, z):
-    return NS(tag_id=i, pose_R=np.eye(3), pose_t=np.array([[x], [0.0], [z]]), pose_err=0.0)
 
 
 def test_step_detections_with_more_than_sixteen_tags(sd, both_paths):
@@ -540,7 +498,7 @@ def test_step_detections_with_more_than_sixteen_tags(sd, both_paths):
     bx = {i: float(rng.uniform(-0.5, 0.5)) for i in ids}
     bz = {i: float(rng.uniform(0.4, 1.1)) for i in ids}
     plan = [(ids[:20], 0.004, 0.02), (ids[4:24], 0.004, 0.005), (ids[:6], 0.003, 0.02)]
-    wins = [[(k + 0.1 * fr, [_tag(i, bx[i] + rng.normal(0, 0.004), bz[i] + rng.normal(0, 0.004)) for i in win_ids])
+    wins = [[(k + 0.1 * fr, [tag(i, bx[i] + rng.normal(0, 0.004), bz[i] + rng.normal(0, 0.004)) for i in win_ids])
              for fr in range(3)] for k, (win_ids, _, _) in enumerate(plan)]
 
     def run(log):
@@ -554,7 +512,7 @@ def test_step_detections_with_more_than_sixteen_tags(sd, both_paths):
             if log:
                 assert f.pose_steps == len(plan)
                 last_row_is_the_filter(f, trace)
-            return trace, final(sd, f)
+            return trace, final(sd, f, counters)
 
     trace, on = run(True)
     _, off = run(False)
@@ -628,7 +586,7 @@ def test_both_logs_together_equal_each_alone(sd):
                 f.set_state(means[b], starts[b], b)
             f.predict(lin[0], ang[0])                          # a row of the pose log, no step of the innovation log
             f.run_stream(lin, ang, idx, zr, zb, m)
-            return (f.innovations() if innov else None), (f.poses() if pose else None), final(sd, f)
+            return (f.innovations() if innov else None), (f.poses() if pose else None), final(sd, f, counters)
 
     i2, p2, both = run(True, True)
     i1, _, a = run(True, False)

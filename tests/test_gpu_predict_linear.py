@@ -16,47 +16,13 @@ from tests import direct_model as dm
 from tests import linear_model as lm
 from tests import motion_model as mm
 from tests.conftest import path_ran
+from tests.gpu_support import bank, raw00, same, sd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 TIGHT = 1e-9
 EKF_ERR_ARG, EKF_ERR_STATE = -1, -3
 I3, Z3 = np.eye(3), np.zeros((3, 3))
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-def bank(sd, streams, steps=None, config=None, run=True, options=()):
-    """A bank over `streams` (one synthetic stream per trajectory, equal shapes), the whole stream uploaded and its first
-    `steps` steps run."""
-    B, n = len(streams), len(streams[0][0])
-    f = sd.EkfSlam(n, batch=B, config=config)
-    for name, value in options:
-        f.set_option(name, value)
-    for b, s in enumerate(streams):
-        f.set_state_diag(s[0], s[1], b)
-    f.stream_upload(np.stack([s[2] for s in streams], 1), np.stack([s[3] for s in streams], 1),
-                    np.stack([s[4] for s in streams], 1), np.stack([s[5] for s in streams], 1),
-                    np.stack([s[6] for s in streams], 1))
-    if run:
-        f.stream_run(0, steps if steps is not None else len(streams[0][2]))
-    return f
-
-
-def same(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
-
-
-def raw00(sd, f, b=0):
-    """P_base[0, 0] of trajectory b as stored (no flush)."""
-    out = np.empty(1)
-    sd.load_library().ekf_debug_snapshot(f._h, b, 0, out.ctypes.data_as(C.POINTER(C.c_double)), 1)
-    return out[0]
 
 
 def check_against_model(got, before, inputs, what=""):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from oracle import ekf_oracle as orc
+from tests.gpu_support import pbase, sd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,13 +22,6 @@ N_MAX = 3 + 2 * 40
 STEPS = 3
 B = len(SIZES)
 DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
 
 
 @pytest.fixture(scope="module")
@@ -146,19 +140,12 @@ def raw_associate(lib, f, w, pin_cand, pin_full):
         return cand.copy(), nis.copy(), ld.copy(), mn.copy(), an.copy(), al.copy()
 
 
-def pbase(lib, f, b):
-    have = lib.ekf_debug_snapshot(f._h, b, 0, None, 0)
-    out = np.empty(have)
-    assert lib.ekf_debug_snapshot(f._h, b, 0, ptr(out), out.size) == have
-    return out
-
-
 def test_pinned_and_ordinary_destinations_agree_and_the_buffer_is_shared(sd, world):
     lib = sd.load_library()
     combos = list(itertools.product((True, False), repeat=2))
     f, fresh = make_filter(sd, world), make_filter(sd, world)
     try:
-        before = [pbase(lib, f, b) for b in range(B)]
+        before = [pbase(sd, f, b) for b in range(B)]
         passes = f.profile_passes()
         # ---- one staging buffer for the three, empty so far: a small need, the largest, a middle one, the small one again, all
         # staged; each against the same query on a fresh handle in the same state
@@ -188,7 +175,7 @@ def test_pinned_and_ordinary_destinations_agree_and_the_buffer_is_shared(sd, wor
         # ---- nothing of the filter has moved ...
         assert f.profile_passes() == passes
         for b in range(B):
-            assert np.array_equal(pbase(lib, f, b), before[b])
+            assert np.array_equal(pbase(sd, f, b), before[b])
         # ---- ... and it goes on: the pending ranks flush to the oracle's state (and to what a handle never queried gives)
         f.flush()
         fresh.flush()

@@ -3,8 +3,6 @@
 Removal is exact and moves stored values only: every case compares mean and covariance bit for bit with np.delete of the
 download taken just before the call, then, where the filter goes on, with the oracle run from that deleted state.  Each case
 names the path that ran (path_ran, cadence_counters / ekf_debug_chained, last_pass)."""
-import ctypes as C
-from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
@@ -13,18 +11,12 @@ from oracle import ekf_oracle as orc
 from slam_duckietown_amd.evaluation import landmark_rejections
 from slam_duckietown_amd.frontend import remap_tag_index
 from tests.conftest import path_ran
-from tests.test_gpu_nis_gate import gated_step
+from tests.gated_oracle import gated_step
+from tests.gpu_support import raw00, same, sd, tag  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 TIGHT = 1e-10
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
 
 
 def deleted(state, lms):
@@ -32,17 +24,6 @@ def deleted(state, lms):
     mu, P = state
     rows = np.array([3 + 2 * l + e for l in sorted(lms) for e in (0, 1)], dtype=int)
     return np.delete(mu, rows), np.delete(np.delete(P, rows, axis=0), rows, axis=1)
-
-
-def same(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
-
-
-def raw00(sd, f, b=0):
-    """P_base[0, 0] of trajectory b as stored (no flush)."""
-    out = np.empty(1)
-    sd.load_library().ekf_debug_snapshot(f._h, b, 0, out.ctypes.data_as(C.POINTER(C.c_double)), 1)
-    return out[0]
 
 
 def kept_stream(N, steps, m, seed, o2n):
@@ -225,8 +206,6 @@ def test_active_bound_on_a_growing_map(sd, active_bound):
 
 
 # ---- 7, 11: the device association, the gate and the log ---------------------------------------------------------------------
-def _tag(i, x, z):
-    return NS(tag_id=i, pose_R=np.eye(3), pose_t=np.array([[x], [0.0], [z]]), pose_err=0.0)
 
 
 def test_device_association_after_removal(sd):
@@ -239,7 +218,7 @@ def test_device_association_after_removal(sd):
     gone = ids[3]
 
     def window(k, win_ids):
-        return [(k + 0.1 * fr, [_tag(i, bx[i] + rng.normal(0, 0.004), bz[i] + rng.normal(0, 0.004)) for i in win_ids])
+        return [(k + 0.1 * fr, [tag(i, bx[i] + rng.normal(0, 0.004), bz[i] + rng.normal(0, 0.004)) for i in win_ids])
                 for fr in range(2)]
 
     def oracle_window(om, oP, oti, win, lin, ang):
@@ -293,8 +272,8 @@ def test_gate_log_and_removal_end_to_end(sd):
     truth = {i: np.array([bz[i], -bx[i]]) for i in ids}           # world position seen from the pose (0, 0, 0)
 
     def window(k, displaced=False):
-        return [(k + 0.1 * fr, [_tag(i, bx[i] + (1.0 if displaced and i == bad else 0.0) + rng.normal(0, 0.003),
-                                     bz[i] + rng.normal(0, 0.003)) for i in ids]) for fr in range(2)]
+        return [(k + 0.1 * fr, [tag(i, bx[i] + (1.0 if displaced and i == bad else 0.0) + rng.normal(0, 0.003),
+                                    bz[i] + rng.normal(0, 0.003)) for i in ids]) for fr in range(2)]
 
     wins = [window(0, displaced=True)] + [window(k) for k in range(1, 6)]
     later = [window(k) for k in range(6, 10)]

@@ -14,29 +14,12 @@ import pytest
 
 from oracle import ekf_oracle as orc
 from tests import golden_util as gu
+from tests.gpu_support import close, counters, sd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 REL_TOL = 1e-6
 TIGHT = 1e-9
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-def close(a, b, tol=TIGHT):
-    r = orc.rel_fro(a, b)
-    assert r < REL_TOL, f"rel Frobenius {r:.3e} exceeds the 1e-6 bar"
-    assert r < tol, f"rel Frobenius {r:.3e} exceeds the expected {tol:g}"
-
-
-def small_launches(sd, f):
-    lib = sd.load_library()
-    return lib.ekf_debug_small_launches(f._h)
 
 
 def test_small_state_is_the_default_up_to_64_landmarks(sd, monkeypatch):
@@ -47,10 +30,10 @@ def test_small_state_is_the_default_up_to_64_landmarks(sd, monkeypatch):
             f.set_state_diag(s[0], s[1])
             for k in range(3):
                 f.step(s[2][k], s[3][k], s[4][k], s[5][k], s[6][k])
-            assert small_launches(sd, f) == expect
+            assert counters(sd, f).small_launches == expect
             f.set_option("small_state", 0)
             f.step(s[2][0], s[3][0], s[4][0], s[5][0], s[6][0])
-            assert small_launches(sd, f) == expect
+            assert counters(sd, f).small_launches == expect
 
 
 @pytest.mark.parametrize("case", ["stream_n20_m8", "stream_n20_m1"])
@@ -69,7 +52,7 @@ def test_golden_streams_step_by_step(sd, case):
                 P = f.covariance()
                 close(P, g["out_cov"][kept[k]])
                 assert np.array_equal(P, P.T)
-        assert f.flags() == 0 and small_launches(sd, f) == len(g["lin"])
+        assert f.flags() == 0 and counters(sd, f).small_launches == len(g["lin"])
 
 
 @pytest.mark.parametrize("case", ["stream_n20_m8", "stream_n20_m1"])
@@ -96,7 +79,7 @@ def test_golden_streams_as_one_launch(sd, case):
                 if c - 1 in kept:
                     close(P, g["out_cov"][kept[c - 1]])
             assert f.flags() == 0
-            assert small_launches(sd, f) == (len(cuts) if small else 0)
+            assert counters(sd, f).small_launches == (len(cuts) if small else 0)
             out[small] = (mu, P)
     close(out[1][0], out[0][0], 1e-10)
     close(out[1][1], out[0][1], 1e-10)
@@ -157,7 +140,7 @@ def test_bank_of_small_filters_of_different_size_against_the_oracle(sd):
                         idx[k, b, :m], zr[k, b, :m], zb[k, b, :m] = o
                         means[b], covs[b] = orc.ekf_step_dense(means[b], covs[b], lins[k, b], angs[k, b], o[0], o[1], o[2], cfg)
                 f.run_stream(lins, angs, idx, zr, zb, ms)
-        assert small_launches(sd, f) > 0
+        assert counters(sd, f).small_launches > 0
         for b in range(B):
             mu, P = f.state(b)
             assert f.flags(b) == 0 and len(mu) == 3 + 2 * sizes[b]
@@ -185,11 +168,6 @@ def test_q_zero_and_growth_on_the_small_path(sd):
         m1, P1 = f.state(1)
         close(m1, om)
         close(P1, oP)
-
-
-def fused_fetches(sd, f):
-    lib = sd.load_library()
-    return lib.ekf_debug_fused_fetches(f._h)
 
 
 @pytest.mark.parametrize("small,batch,which", [(1, 1, 0), (1, 3, 1), (0, 1, 0), (0, 2, 1)])
@@ -231,8 +209,8 @@ def test_step_state_is_step_then_state(sd, small, batch, which):
             close(mu, means[which])
             close(P, covs[which])
         assert f.flags(which) == 0
-        assert fused_fetches(sd, f) == (14 if small else 0)
-        assert fused_fetches(sd, twin) == 0
+        assert counters(sd, f).fused_fetches == (14 if small else 0)
+        assert counters(sd, twin).fused_fetches == 0
         # the state stayed resident: the other trajectories, and the same one read the ordinary way
         for t in range(batch):
             mu, P = f.state(t)
@@ -253,7 +231,7 @@ def test_step_state_reports_what_the_two_calls_report(sd):
         rc = lib.ekf_step_fetch(f._h, one.ctypes.data_as(C.POINTER(C.c_double)), z.ctypes.data_as(C.POINTER(C.c_double)),
                                 None, None, None, np.zeros(1, dtype=np.int32).ctypes.data_as(C.POINTER(C.c_int)), 0, 0,
                                 out_mu.ctypes.data_as(C.POINTER(C.c_double)), out_P.ctypes.data_as(C.POINTER(C.c_double)), 9)
-        assert rc != 0 and small_launches(sd, f) == 0
+        assert rc != 0 and counters(sd, f).small_launches == 0
         mu, P = f.step_state(0.0, 0.0, [], [], [])            # nothing observed, no motion: the pose stays where landmark 0 is
         om, oP = orc.ekf_step_dense(mean, np.eye(7), 0.0, 0.0, [], [], [], orc.EkfConfig())
         close(mu, om)
@@ -262,7 +240,7 @@ def test_step_state_reports_what_the_two_calls_report(sd):
         mu, P = f.step_state(0.0, 0.0, [0], [0.1], [0.0])     # the landmark coincides with the pose: q == 0
         assert not np.isfinite(mu).all()
         assert f.flags() & 1
-        assert fused_fetches(sd, f) == 2
+        assert counters(sd, f).fused_fetches == 2
 
 
 @pytest.mark.parametrize("N,m", [(12, 3), (38, 8)])
@@ -282,7 +260,7 @@ def test_polled_hand_over_carries_an_integrity_trailer(sd, N, m):
             if k % 20 == 0:
                 dm, dP = f.state()
                 assert np.array_equal(mu, dm) and np.array_equal(P, dP)
-        assert fused_fetches(sd, f) == 200 and lib.ekf_debug_fetch_retries(f._h) == 0 and f.flags() == 0
+        assert counters(sd, f).fused_fetches == 200 and lib.ekf_debug_fetch_retries(f._h) == 0 and f.flags() == 0
     om, oP = s[0].copy(), np.diag(s[1])
     for k in range(200):
         om, oP = orc.ekf_step_dense(om, oP, s[2][k], s[3][k], s[4][k], s[5][k], s[6][k], orc.EkfConfig())
@@ -306,7 +284,7 @@ def test_a_bank_that_overfills_the_chip_takes_the_throughput_kernel_bit_identica
         for k in range(3, steps):                           # ... then online steps
             f.step(cols[0][k], cols[1][k], list(cols[2][k]), list(cols[3][k]), list(cols[4][k]))
         big = {b: f.state(b) for b in (0, 5, 333, 799)}
-        assert small_launches(sd, f) == 1 + (steps - 3) and not any(f.flags(b) for b in big)
+        assert counters(sd, f).small_launches == 1 + (steps - 3) and not any(f.flags(b) for b in big)
     for b, (mu, P) in big.items():
         s = base[b % 8]
         with sd.EkfSlam(3 + 2 * N, batch=2) as g:
@@ -349,7 +327,7 @@ def test_banks_take_the_small_path_up_to_64_landmarks(sd, n_lm, n_cap):
         one.set_option("small_state", 1)
         one.set_state_diag(base[0][0], base[0][1])
         one.step(base[0][2][0], base[0][3][0], base[0][4][0], base[0][5][0], base[0][6][0])
-        assert small_launches(sd, one) == 0                  # a single trajectory of this size: the general kernels
+        assert counters(sd, one).small_launches == 0                  # a single trajectory of this size: the general kernels
     for small in (1, 0):
         with sd.EkfSlam(3 + 2 * n_cap, batch=B) as f:
             f.set_option("small_state", small)
@@ -369,7 +347,7 @@ def test_banks_take_the_small_path_up_to_64_landmarks(sd, n_lm, n_cap):
             out[small] = {b: f.state(b) for b in (0, 7, 64, 129)}
             assert np.array_equal(out[small][7][0], mu_f) or k == 2          # (the fused fetch returned the state of step 1)
             assert not any(f.flags(b) for b in out[small])
-            assert small_launches(sd, f) == (1 + 4 if small else 0)          # the stream, then 1 + 1 + 2 launches (20 > 16 landmarks)
+            assert counters(sd, f).small_launches == (1 + 4 if small else 0)          # the stream, then 1 + 1 + 2 launches (20 > 16 landmarks)
     for b in (0, 7, 64, 129):
         s = base[b % 6]
         om, oP = s[0].copy(), (dense0.copy() if b == 7 else np.diag(s[1]))

@@ -7,7 +7,6 @@ products, so its forward error is below gamma_40 ~ 4.4e-15 of the bound, the dev
 roughly 15 x headroom.  What the call only leaves alone is compared bit for bit.  Runs that go on are compared with the oracle
 at the project's TIGHT."""
 import ctypes as C
-from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
@@ -17,6 +16,8 @@ from tests import direct_model as dm
 from tests import join_model as jm
 from tests import transform_model as tm
 from tests.conftest import path_ran
+from tests.gpu_support import col, raw00, same, sd, tag, within_bounds  # noqa: F401
+from tests.streams import stream_from
 
 pytestmark = pytest.mark.gpu
 
@@ -25,28 +26,6 @@ TOL = 1e-13            # x the entrywise bound (see above)
 EKF_ERR_ARG, EKF_ERR_STATE = -1, -3
 PHIS = (0.3, np.pi / 2, -2.9)
 COV = np.array([[0.04, 0.01, -0.002], [0.01, 0.09, 0.003], [-0.002, 0.003, 0.002]])
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
-
-
-def same(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
-
-
-def col(x):
-    return x[:, None]
-
-
-def raw00(sd, f, b=0):
-    """P_base[0, 0] of trajectory b as stored (no flush)."""
-    out = np.empty(1)
-    sd.load_library().ekf_debug_snapshot(f._h, b, 0, out.ctypes.data_as(C.POINTER(C.c_double)), 1)
-    return out[0]
 
 
 def uploaded(sd, states, n_max, general=False):
@@ -74,32 +53,8 @@ def stepped(sd, N, n_max, steps, m, seed, general=False):
 def check_model(got, before, T, cov=None, label=""):
     """`got` against the model applied to `before`; prints the worst ratio to the bound before it asserts."""
     xm, Pm, bound, mbound = tm.transform_dense(before[0], before[1], T, cov)
-    assert got[0].shape == xm.shape and got[1].shape == Pm.shape
-    eP, em = np.abs(got[1] - Pm), np.abs(got[0] - xm)
-    rP = float(np.max(eP / np.where(bound > 0, bound, 1.0))) if eP.size else 0.0
-    rm = float(np.max(em / np.where(mbound > 0, mbound, 1.0))) if em.size else 0.0
-    print(f"{label}: worst covariance error / bound {rP:.3g}, mean {rm:.3g}")
-    assert (eP <= TOL * bound).all() and (em <= TOL * mbound).all()
-    assert np.array_equal(got[1], got[1].T)
+    within_bounds(got, xm, Pm, bound, mbound, TOL, label)
     return xm, Pm, bound
-
-
-def stream_from(mean, steps, m, seed):
-    """A synthetic stream consistent with a filter's own estimate (the construction of tests/test_gpu_join.py): ranges,
-    bearings and increments only -- the same stream in every frame."""
-    cfg, rng = orc.EkfConfig(), np.random.default_rng(seed)
-    lm, pose, N = mean[3:].reshape(-1, 2), mean[:3].copy(), (len(mean) - 3) // 2
-    lin, ang = np.full(steps, 0.004), np.full(steps, 0.02)
-    idx, zr, zb = np.zeros((steps, m), dtype=np.int32), np.zeros((steps, m)), np.zeros((steps, m))
-    for k in range(steps):
-        pose, _ = orc.motion_model(pose, lin[k], ang[k], cfg)
-        vis = (m * k + np.arange(m)) % N
-        d = lm[vis] - pose[:2]
-        c, s = np.cos(pose[2]), np.sin(pose[2])
-        xr = c * d[:, 0] + s * d[:, 1] + rng.normal(0.0, 0.01, m)
-        yr = -s * d[:, 0] + c * d[:, 1] + rng.normal(0.0, 0.01, m)
-        idx[k], zr[k], zb[k] = vis, np.sqrt(xr ** 2 + yr ** 2), np.arctan2(yr, xr)
-    return lin, ang, idx, zr, zb
 
 
 def oracle_run(state, st):
@@ -334,8 +289,6 @@ def test_the_filter_goes_on(sd, N, n_max, small, with_cov):
 
 
 # ---- 8: tags, logs and counters --------------------------------------------------------------------------------------------
-def _tag(i, x, z):
-    return NS(tag_id=i, pose_R=np.eye(3), pose_t=np.array([[x], [0.0], [z]]), pose_err=0.0)
 
 
 def test_tags_logs_and_counters(sd):
@@ -350,7 +303,7 @@ def test_tags_logs_and_counters(sd):
         for i in ids:
             d = world[i] - truth[:2]
             xr, yr = c * d[0] + s * d[1] + rng.normal(0, 0.004), -s * d[0] + c * d[1] + rng.normal(0, 0.004)
-            tags.append(_tag(i, -yr, xr))
+            tags.append(tag(i, -yr, xr))
         return [(float(k), tags)]
 
     T = np.array([5.0, -3.0, 1.0])

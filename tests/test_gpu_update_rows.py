@@ -34,6 +34,7 @@ import pytest
 from oracle import ekf_oracle as orc
 from tests import parity_blocks as pb
 from tests import update_cases as uc
+from tests.gpu_support import same, sd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -44,13 +45,6 @@ FORMS = ("k_flush", "k_flush streaming", "k_flush_rs forced B=3", "k_flush_rs fo
 REACHED = {"linear": set(), "direct": set(), "forms": set()}
 RAN = set()
 RESULTS = []
-
-
-@pytest.fixture(scope="module")
-def sd():
-    import slam_duckietown_amd as sd
-    sd.load_library()
-    return sd
 
 
 def make_bank(sd, base, steps=None):
@@ -131,10 +125,6 @@ def instantiation(sd, f, kind, d_max):
     return cap
 
 
-def same_bits(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
-
-
 # ---- rows: one trajectory, every D ----
 @pytest.mark.parametrize("D,k,mode", uc.LINEAR_ROWS)
 def test_linear_rows(sd, D, k, mode):
@@ -198,7 +188,7 @@ def test_ragged_bank(sd, kind, which):
             assert res.nis[2] > gate[2]
         for b in range(4):
             judge(sd, f, b, before[b], kind, payloads[b], res, name, innovation=True, gate=np.inf if gate is None else gate[b])
-        assert same_bits(f.state(2), before[2])
+        assert same(f.state(2), before[2])
     RAN.add(name)
 
 
@@ -224,7 +214,7 @@ def test_one_trajectory_alone_while_the_others_have_ranks_pending(sd, kind):
         judge(sd, f, uc.LONE, before[uc.LONE], kind, payload, res, name)
         for b in range(4):
             if b != uc.LONE:
-                assert same_bits(f.state(b), before[b]), f"{name}: trajectory {b} differs from the flushed twin"
+                assert same(f.state(b), before[b]), f"{name}: trajectory {b} differs from the flushed twin"
     RAN.add(name)
 
 
@@ -297,7 +287,7 @@ def test_pass_form_row_slabs_forced(sd, kind, base):
                     judge(sd, f, b, before[b], kind, payloads[b], res, f"{form} {kind}")
             out[pk] = [f.state(b) for b in range(B)], before
     for b in range(B):
-        assert same_bits(out[2][1][b], out[0][1][b])                         # the twins entered the call with the same bits
+        assert same(out[2][1][b], out[0][1][b])                         # the twins entered the call with the same bits
     against_k_flush_twin(f"{form} {kind}", out[2][0], out[0][0], range(B))
     REACHED["forms"].add(form)
     RAN.add(f"{form} {kind}")
@@ -332,10 +322,10 @@ def test_pass_form_row_slabs_chosen_by_the_plan(sd, kind):
                 assert kernel.startswith("ekf::k_flush<"), kernel
             out[pk] = {b: f.state(b) for b in before}, before
     for b in list(CHECKED) + list(IDLE):
-        assert same_bits(out[None][1][b], out[0][1][b])                      # the twins entered the call with the same bits
+        assert same(out[None][1][b], out[0][1][b])                      # the twins entered the call with the same bits
     for b in IDLE:
-        assert same_bits(out[None][0][b], out[None][1][b]), f"{form} {kind}: trajectory {b} brought nothing and moved"
-        assert same_bits(out[0][0][b], out[0][1][b]), f"{form} {kind}: trajectory {b} of the k_flush twin moved"
+        assert same(out[None][0][b], out[None][1][b]), f"{form} {kind}: trajectory {b} brought nothing and moved"
+        assert same(out[0][0][b], out[0][1][b]), f"{form} {kind}: trajectory {b} of the k_flush twin moved"
     against_k_flush_twin(f"{form} {kind}", out[None][0], out[0][0], CHECKED)
     REACHED["forms"].add(form)
     RAN.add(f"{form} {kind}")
@@ -402,7 +392,7 @@ def test_call_behind_a_w_from_v_pass(sd, kind):
                 assert kernel.startswith("ekf::k_flush<"), kernel
             out[pk] = {b: f.state(b) for b in before}
             for b in IDLE:
-                assert same_bits(out[pk][b], before[b]), f"{form} {kind}: trajectory {b} brought nothing and moved (pass_kernel {pk})"
+                assert same(out[pk][b], before[b]), f"{form} {kind}: trajectory {b} brought nothing and moved (pass_kernel {pk})"
     against_k_flush_twin(f"{form} {kind}", out[None], out[0], CHECKED)
     REACHED["forms"].add(form)
     RAN.add(f"{form} {kind}")

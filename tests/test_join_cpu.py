@@ -4,12 +4,11 @@ binding's argument staging with a fake library, and the C ABI's argument errors 
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import host_check
 from tests import join_model as jm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -66,18 +65,7 @@ def test_what_stays_stays():
 
 
 def test_plan_join_under_the_sanitizers(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("g++ is not available")
-    exe = tmp_path / "join_plan_check"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DEKF_HOST_ONLY",
-           "-Wall", "-Werror", "-I", os.path.join(ROOT, "slam-duckietown_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "join_plan_check.cpp"), "-o", str(exe)]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "checks passed" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    host_check.run_under_sanitizers("join_plan_check", tmp_path, 600)
     api = open(os.path.join(ROOT, "slam-duckietown_amd", "csrc", "ekf_api.hip")).read()
     assert re.search(r"\bplan_join\(", api) and not re.search(r"^(static|inline)[^\n;]*\bplan_join\(", api, flags=re.M)
     # the snapshot buffer and the table are owned through the types of ekf_resources.h

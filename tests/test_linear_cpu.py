@@ -4,14 +4,13 @@ the sanitizers (no device)."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import ekf_oracle as orc
 from tests import direct_model as dm
+from tests import host_check
 from tests import linear_model as lm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,8 +40,7 @@ def test_header_library_and_binding_declare_the_same_call():
     lib = eb.library_path()
     if not os.path.exists(lib):
         pytest.skip("the library is not built")
-    nm = subprocess.run(["nm", "-D", "--defined-only", lib], check=True, capture_output=True, text=True).stdout
-    assert re.search(r"\bT ekf_update_linear\b", nm)
+    assert host_check.exported_symbols(lib).get("ekf_update_linear") == "T"
 
 
 def forms_agree(mean, cov, lms, H, R, r, innovation=False):
@@ -133,17 +131,6 @@ def test_the_forms_agree_on_a_state_shaped_like_the_panel_case():
 
 
 def test_plan_linear_under_the_sanitizers(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("g++ is not available")
-    exe = tmp_path / "linear_plan_check"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DEKF_HOST_ONLY",
-           "-Wall", "-Werror", "-I", os.path.join(ROOT, "slam-duckietown_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "linear_plan_check.cpp"), "-o", str(exe)]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "checks passed" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    host_check.run_under_sanitizers("linear_plan_check", tmp_path, 300)
     api = open(os.path.join(ROOT, "slam-duckietown_amd", "csrc", "ekf_api.hip")).read()
     assert re.search(r"\bplan_linear\(", api) and not re.search(r"^(static|inline)[^\n;]*\bplan_linear\(", api, flags=re.M)

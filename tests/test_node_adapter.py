@@ -4,7 +4,7 @@ import pytest
 from types import SimpleNamespace
 
 from oracle import ekf_oracle as orc
-from tests.test_replay_driver import OracleBackend
+from tests.oracle_backend import OracleBackend
 
 
 def script(seed=3, ticks=60):

@@ -8,13 +8,12 @@ Tolerance between two evaluations of the same formulas: entrywise 1e-13 x bound,
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import direct_model as dm
+from tests import host_check
 from tests import join_model as jm
 from tests import transform_model as tm
 
@@ -169,18 +168,7 @@ def test_align_then_anchor_on_the_models():
 
 # ---- the host plan under the sanitizers -----------------------------------------------------------------------------------
 def test_plan_transform_under_the_sanitizers(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("g++ is not available")
-    exe = tmp_path / "transform_plan_check"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DEKF_HOST_ONLY",
-           "-Wall", "-Werror", "-I", os.path.join(ROOT, "slam-duckietown_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "transform_plan_check.cpp"), "-o", str(exe)]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "checks passed" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    host_check.run_under_sanitizers("transform_plan_check", tmp_path, 600)
     api = open(os.path.join(ROOT, "slam-duckietown_amd", "csrc", "ekf_api.hip")).read()
     assert re.search(r"\bplan_transform\(", api) and not re.search(r"^(static|inline)[^\n;]*\bplan_transform\(", api, flags=re.M)
     assert re.search(r"DeviceBuf<double> dtf_frame;", api) and re.search(r"DeviceBuf<int> dtf_tab;", api)

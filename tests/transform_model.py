@@ -11,12 +11,9 @@ item of the state x = [pose; landmarks].  With R = rot(phi), J2 = [[0, -1], [1, 
 scale their tolerances by: |J| |P| |J|^T + |A| |Sigma| |A|^T for the covariance, |t| + |R| |l| (|theta| + |phi|) for the mean."""
 import numpy as np
 
+from tests.join_model import rot  # noqa: F401  (the one definition of R = rot(phi); nothing else is shared with that model)
+
 J2 = np.array([[0.0, -1.0], [1.0, 0.0]])
-
-
-def rot(phi):
-    c, s = np.cos(phi), np.sin(phi)
-    return np.array([[c, -s], [s, c]])
 
 
 def _congruence(P, R):

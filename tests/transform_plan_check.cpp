@@ -14,39 +14,9 @@
 #include <limits>
 #include <vector>
 
-#include "ekf_host_plan.h"
+#include "plan_check.h"
 
 using namespace ekf;
-
-static long checks = 0;
-#define CHECK(cond, ...)                                              \
-  do {                                                                \
-    ++checks;                                                         \
-    if (!(cond)) {                                                    \
-      std::fprintf(stderr, "FAILED %s:%d: %s  [", __FILE__, __LINE__, #cond); \
-      std::fprintf(stderr, __VA_ARGS__);                              \
-      std::fprintf(stderr, "]\n");                                    \
-      std::exit(1);                                                   \
-    }                                                                 \
-  } while (0)
-
-static HostPlan bank(int n_max, std::vector<int> n, std::vector<int> neff = {}) {
-  HostPlan h;
-  h.n_max = n_max;
-  h.rows = (n_max + 63) / 64 * 64;
-  h.ld = h.rows;
-  if (n_max <= 4096) {
-    int p2 = 64;
-    while (p2 < n_max) p2 *= 2;
-    h.ld = p2;
-  }
-  h.batch = (int)n.size();
-  h.pstride = p_alloc(h.rows, h.ld);
-  h.n = n;
-  h.neff = neff.empty() ? n : neff;
-  h.neff_enq = h.neff;
-  return h;
-}
 
 // the item pairs and the entries the launch writes for one trajectory, by the kernel's own enumeration
 static void enumerate(int N, int Ma, const HostPlan& h) {
