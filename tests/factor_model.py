@@ -51,6 +51,18 @@ def blocked_cholesky(P):
     return A[:n, :n].copy(), logdet, 0
 
 
+def check_factor(name, U, logdet, P, kappa=None):
+    """Structure, residual and log-determinant of one trajectory's factor against P; prints the ratios to the bounds."""
+    n = P.shape[0]
+    assert U.shape == (n, n) and np.array_equal(U, np.triu(U)) and (np.diag(U) > 0).all()
+    kappa = np.linalg.cond(P) if kappa is None else kappa
+    res = np.linalg.norm(U.T @ U - P) / (gamma(n + 1) * np.linalg.norm(np.abs(U.T) @ np.abs(U)))
+    ref = 2.0 * np.log(np.diag(np.linalg.cholesky(P))).sum()
+    dl = abs(logdet - ref) / (2 * n * gamma(n + 1) * kappa)
+    print(f"{name}: n = {n} kappa = {kappa:.3g} residual / bound = {res:.3g} logdet error / bound = {dl:.3g}")
+    assert res <= 1.0 and dl <= 1.0
+
+
 def spd(n, seed, rank=8, const_diag=False):
     """A seeded SPD matrix "diagonal + low rank", D + V V^T with D in [1, 2] and rows of V of squared length about 3 (so that
     eliminating the rows above an entry takes most of its diagonal away): kappa_2 is about 3 n / 8, 100 at n = 193 and 1700 at

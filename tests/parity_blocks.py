@@ -323,5 +323,39 @@ def assert_marginals_close(pose, lms, oP, observed, diag0=None, tol=1e-9, what="
     return err
 
 
+def marginal_blocks(P):
+    """(pose (3, 3), landmarks (N, 2, 2)): the diagonal blocks of a covariance, as `EkfSlam.marginals(b)` returns them."""
+    P = np.asarray(P)
+    r = np.arange(3, P.shape[0], 2)
+    return P[:3, :3].copy(), np.stack([np.stack([P[r, r], P[r, r + 1]], -1), np.stack([P[r + 1, r], P[r + 1, r + 1]], -1)], -2)
+
+
+def marginal_errors(pose, lms, wP, init_var):
+    """`EkfSlam.marginals(b)` against a dense model's covariance `wP`, the landmarks classed by the model as `loose_landmarks`
+    does: pose and the informed landmarks' blocks by relative Frobenius norm, the loose ones' absolutely (loose_block)."""
+    wpose, wlms = marginal_blocks(np.asarray(wP, dtype=float))
+    loose, informed = loose_landmarks(wP, init_var)
+    err = {"pose": _rel(pose, wpose)}
+    if len(informed):
+        err["landmarks"] = _rel(np.asarray(lms, dtype=float)[informed], wlms[informed])
+    if len(loose):
+        err["loose_block"] = float(np.abs(np.asarray(lms, dtype=float)[loose] - wlms[loose]).max())
+    return err
+
+
+def assert_marginal_blocks_close(pose, lms, wP, init_var, tol=1e-9, what=""):
+    """`assert_state_close`'s rule on the diagonal blocks alone: as many landmark blocks as the model has landmarks, pose and
+    informed blocks below `tol` (and the 1e-6 bar), loose blocks within 32 eps init_var; returns {piece: measured value}."""
+    N = (np.asarray(wP).shape[0] - 3) // 2
+    assert np.shape(pose) == (3, 3) and np.shape(lms) == (N, 2, 2), \
+        f"{what}marginals count: {np.shape(lms)[0]} landmark blocks where the model has {N}"
+    err = marginal_errors(pose, lms, wP, init_var)
+    check_errors(err, tol, what + "marginals ")
+    if "loose_block" in err:
+        eps_v = 32 * np.finfo(float).eps * init_var
+        assert err["loose_block"] <= eps_v, f"{what}marginals loose_block: {err['loose_block']:.3e} exceeds 32 eps init_var = {eps_v:.3e}"
+    return err
+
+
 def fmt(err):
     return " ".join(f"{k}={err[k]:.2e}" for k in PIECES if k in err)

@@ -17,7 +17,10 @@ of m = 4 are cadences of 10, 10 and 8 steps, the last one's 64 ranks stay pendin
 
 An operation is a function (driver, rng): it draws its arguments from the MODEL's current state -- so it stays valid after a
 renumbering -- and issues the calls through the driver, which hands each to the model and to whatever runs beside it (a filter,
-the model in another precision).  Every argument is therefore the same float64 value for all of them."""
+the model in another precision).  Every argument is therefore the same float64 value for all of them.
+
+The same setup, prelude and operations serve tests/test_gpu_queries_after_calls.py and tests/test_queries_after_calls_cpu.py
+(run_query_case, below): ONE operation, then the read-only queries -- no second operation, and no download in between."""
 import functools
 
 import numpy as np
@@ -257,6 +260,108 @@ def run_case(drv, a, b, judge=None):
     judge("B")
     continuation(drv, rng)
     judge("end")
+
+
+def as_got(model):
+    """A model's state as a `got`: NumPy's products leave the last bits of P_ij and P_ji apart, and the judge demands of `got`
+    the exact symmetry the device gives."""
+    mean, cov, tags = model.state()
+    cov = np.asarray(cov, dtype=float)
+    return np.asarray(mean, dtype=float), (cov + cov.T) / 2, tags, 0
+
+
+def model_bound(tr):
+    """The active bound the model's history implies: past the highest landmark correlated with anything."""
+    seen = np.flatnonzero(tr.seen)
+    return 3 + 2 * (int(seen[-1]) + 1) if len(seen) else 3
+
+
+def keep_rows_beyond(before, after, bound):
+    """What a pass -- or a query -- that skips every row at or beyond `bound` leaves: those rows and columns (and means) as
+    they were.  `before`'s covariance is symmetrised first (a model's products leave the last bits of P_ij and P_ji apart)."""
+    mean, cov = np.array(after[0]), np.array(after[1])
+    was = (np.asarray(before[1]) + np.asarray(before[1]).T) / 2
+    mean[bound:], cov[bound:, :], cov[:, bound:] = before[0][bound:], was[bound:, :], was[:, bound:]
+    return mean, cov
+
+
+# ---- one operation, then the read-only queries (tests/test_gpu_queries_after_calls.py) -----------------------------------------
+# The tail: single steps that each see landmark 0 and ONE mid-map informed landmark, mid = min(12, n_lm - 3) (copy_from leaves
+# 12 landmarks).  Their own bound, 3 + 2 (mid + 1), lies far below the bound A left: a query behind them is right only if the
+# bound A established reaches it.  TAIL_STEPS: two, and one more where the second would land exactly on the rank limit and
+# leave nothing pending on the general kernels (the prelude's story) -- no case needs it with these draws.
+TAIL_STEPS = {}
+
+
+def tail_mid(tr):
+    return min(12, tr.n_lm - 3)
+
+
+def tail_bound(tr):
+    return 3 + 2 * (tail_mid(tr) + 1)
+
+
+def query_name(a):
+    return OPS[a][0]
+
+
+def run_query_case(drv, a, judge=None):
+    """setup, prelude, A, the tail; `judge(stage)` after the prelude ("start": ranks are pending), after A ("A") and after the
+    tail ("tail": the last, and the only one that may download).  Draws from its own generator: the 225 pairs stay what they
+    are."""
+    rng = np.random.default_rng([SEED, a, 99])
+    judge = judge or (lambda stage: None)
+    setup(drv)
+    prelude(drv)
+    judge("start")
+    OPS[a][1](drv, rng)
+    judge("A")
+    for _ in range(TAIL_STEPS.get(OPS[a][0], 2)):
+        observe(drv, rng, [0, tail_mid(drv.model.tr)])
+    judge("tail")
+
+
+QUERY_OBS = 4           # observations per associate() query
+
+
+def query_rngs(a):
+    """(the generator of the associate() observations, the generator of joint()'s permutations) of case a."""
+    return np.random.default_rng([11, a]), np.random.default_rng([12, a])
+
+
+def query_obs(rng, mean):
+    """QUERY_OBS unlabelled observations: range and bearing of a random landmark from `mean`, the landmark moved by 0.05 m per
+    axis and the bearing by 0.02 rad (test_gpu_associate's obs_around, for one trajectory)."""
+    N = (len(mean) - 3) // 2
+    zr, zb = np.zeros(QUERY_OBS), np.zeros(QUERY_OBS)
+    for q in range(QUERY_OBS):
+        l = int(rng.integers(N))
+        d = mean[3 + 2 * l:5 + 2 * l] - mean[:2] + rng.normal(0, 0.05, 2)
+        zr[q] = np.hypot(*d)
+        zb[q] = orc.wrap_pi(np.arctan2(d[1], d[0]) - mean[2] + rng.normal(0, 0.02))
+    return zr, zb
+
+
+def query_selection(tr):
+    """The three landmarks of the second joint(): the highest one under the model's bound, a loose one and the tail's `mid` --
+    distinct; where the map has no (other) loose landmark, or two of them coincide, the lowest landmarks not yet named."""
+    top = (model_bound(tr) - 3) // 2 - 1
+    loose = [int(l) for l in pb.loose_landmarks(tr.cov, INIT_VAR)[0] if l != top]
+    sel = list(dict.fromkeys([max(top, 0)] + loose[:1] + [tail_mid(tr)]))
+    return sel + [l for l in range(tr.n_lm) if l not in sel][:3 - len(sel)]
+
+
+def sub_idx(sel):
+    """State indices of joint(sel)'s sub-state: the pose, then the landmarks in the order given."""
+    return [0, 1, 2] + [3 + 2 * int(j) + d for j in sel for d in range(2)]
+
+
+def unpermute(sel, mean, cov):
+    """joint(sel) of ALL landmarks in some order, as the whole state: (mean, covariance) in the state's own order."""
+    ix = np.array(sub_idx(sel))
+    m, P = np.empty(len(ix)), np.empty((len(ix), len(ix)))
+    m[ix], P[np.ix_(ix, ix)] = mean, cov
+    return m, P
 
 
 def new_model(dtype=np.float64):

@@ -20,66 +20,13 @@ from tests.gpu_support import counters, sd, tag  # noqa: F401
 pytestmark = pytest.mark.gpu
 
 EKF_ERR_ARG = -1
-NIS_TOL, LOGDET_TOL, PATH_TOL = 1e-9, 2e-9, 1e-10
-TOTALS = {"entries": 0, "left_out": 0, "obs": 0, "excused": 0}
+PATH_TOL = 1e-10
+TOTALS = aw.TOTALS
 
 
 def check_query(f, zr, zb, m=None, meas_sigma=None, what="", res=None):
-    """f.associate(full=True) of the whole bank against the NumPy reference on the state downloaded after it.  Returns the
-    query's result and the reference's cond(S) per trajectory."""
-    a = f.associate(zr, zb, m, full=True) if res is None else res
-    B, S = a.cand.shape[:2]
-    R, Bg, mm = f._unlabelled(zr, zb, m)
-    sig = np.broadcast_to(f.config.meas_sigma if meas_sigma is None else meas_sigma, (B,))
-    conds = []
-    for b in range(B):
-        mu, P = f.state(b)
-        N, mb = (len(mu) - 3) // 2, int(mm[b])
-        nis, logdet, cond, raw = aw.ref_scores(mu, P, R[b, :mb], Bg[b, :mb], np.array([sig[b] ** 2] * 2))
-        conds.append(cond)
-        assert np.isnan(a.all_nis[b, :, N:]).all() and np.isnan(a.all_logdet[b, :, N:]).all(), what
-        assert np.isnan(a.all_nis[b, mb:]).all() and (a.cand[b, mb:] == -1).all() and np.isnan(a.min_nis[b, mb:]).all(), what
-        assert np.isnan(a.nis[b, mb:]).all() and np.isnan(a.logdet[b, mb:]).all(), what
-        if mb == 0:
-            continue
-        if N == 0:
-            assert (a.cand[b] == -1).all() and np.isnan(a.nis[b]).all() and np.isnan(a.min_nis[b]).all(), what
-            continue
-        got_nis, got_ld = a.all_nis[b, :mb, :N], a.all_logdet[b, :mb, :N]
-        near = np.abs(np.mod(raw, 2 * np.pi) - np.pi) < 1e-9          # the wrap may fall either way there
-        TOTALS["entries"] += near.size
-        TOTALS["left_out"] += int(near.sum())
-        assert near.sum() <= 1e-3 * near.size, what
-        e_nis = np.abs(got_nis - nis) / np.abs(nis)
-        e_ld = np.abs(got_ld - logdet[None, :])
-        print(f"{what}trajectory {b}: N={N} m={mb} NIS rel err / cond max {np.nanmax(np.where(near, 0, e_nis / cond)):.2e} "
-              f"logdet abs err / cond max {np.nanmax(e_ld / cond):.2e} cond max {cond.max():.2e}")
-        assert not np.isnan(got_nis).any() and not np.isnan(got_ld).any(), what
-        assert (np.where(near, 0.0, e_nis) <= NIS_TOL * cond[None, :]).all(), what
-        assert (e_ld <= LOGDET_TOL * cond[None, :]).all(), what
-        # the candidates: the query's own numbers first (same lane, same bits), then against the reference's order
-        gd = got_nis + got_ld
-        for q in range(mb):
-            for c in range(min(2, N)):
-                j = a.cand[b, q, c]
-                assert 0 <= j < N and a.nis[b, q, c] == got_nis[q, j] and a.logdet[b, q, c] == got_ld[q, j], what
-            order = np.argsort(gd[q], kind="stable")
-            assert list(a.cand[b, q, :min(2, N)]) == list(order[:2]), what   # ascending d, ties to the lower index
-            if N == 1:
-                assert a.cand[b, q, 1] == -1 and np.isnan(a.nis[b, q, 1])
-            assert a.min_nis[b, q] == got_nis[q].min(), what
-        tol_d = NIS_TOL * cond[None, :] * np.abs(nis) + LOGDET_TOL * cond[None, :]
-        d_ref = nis + logdet[None, :]
-        for q in range(mb):
-            TOTALS["obs"] += 1
-            order = np.argsort(d_ref[q], kind="stable")
-            clear = all(d_ref[q, order[r + 1]] - d_ref[q, order[r]] > tol_d[q, order[r + 1]] + tol_d[q, order[r]]
-                        for r in range(min(2, N - 1)))
-            if not clear or near[q].any():
-                TOTALS["excused"] += 1
-                continue
-            assert list(a.cand[b, q, :min(2, N)]) == list(order[:2]), (what, b, q)
-    return a, conds
+    """aw.check_query against the state downloaded after the query."""
+    return aw.check_query(f, f.state, zr, zb, m, meas_sigma, what, res)
 
 
 def obs_around(rng, f, m, b_count=None):

@@ -21,25 +21,13 @@ import pytest
 from oracle import ekf_oracle as orc
 from tests import factor_model as fm
 from tests.conftest import path_ran
-from tests.factor_model import EPS, gamma
+from tests.factor_model import EPS, check_factor, gamma
 from tests.gpu_support import sd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 EKF_ERR_ARG, EKF_ERR_STATE = -1, -3
 _dp = C.POINTER(C.c_double)
-
-
-def check_factor(name, U, logdet, P, kappa=None):
-    """Structure, residual and log-determinant of one trajectory's factor against P; prints the ratios to the bounds."""
-    n = P.shape[0]
-    assert U.shape == (n, n) and np.array_equal(U, np.triu(U)) and (np.diag(U) > 0).all()
-    kappa = np.linalg.cond(P) if kappa is None else kappa
-    res = np.linalg.norm(U.T @ U - P) / (gamma(n + 1) * np.linalg.norm(np.abs(U.T) @ np.abs(U)))
-    ref = 2.0 * np.log(np.diag(np.linalg.cholesky(P))).sum()
-    dl = abs(logdet - ref) / (2 * n * gamma(n + 1) * kappa)
-    print(f"{name}: n = {n} kappa = {kappa:.3g} residual / bound = {res:.3g} logdet error / bound = {dl:.3g}")
-    assert res <= 1.0 and dl <= 1.0
 
 
 def upload(f, b, P, seed=0):

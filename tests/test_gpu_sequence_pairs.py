@@ -10,14 +10,13 @@ the continuation's pass; the failure carries the pair's name.
 
 The handles are made once per path and every case resets them (set_option, set_state_diag, set_tag_index: part of the
 surface under test); a case that fails drops them, so that the next one starts from new handles."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from tests import parity_blocks as pb
 from tests import sequence_cases as sc
 from tests.conftest import path_ran
+from tests.sequence_device import Device
 
 pytestmark = pytest.mark.gpu
 
@@ -35,92 +34,6 @@ def sd():
     HANDLES.clear()
 
 
-class Device:
-    """The filter beside the model: tests/sequence_model.py's method names on an EkfSlam handle (trajectory 0), the handles
-    of sequence_cases.sources() beside it."""
-
-    def __init__(self, sd):
-        self.sd, self.f = sd, sd.EkfSlam(sc.N_MAX)
-        self.src = {}
-        for key, (mean, cov, tags) in sc.sources().items():
-            h = sd.EkfSlam(len(mean))
-            h.set_state(mean, cov)
-            h.set_tag_index(tags)
-            got = h.state()
-            assert np.array_equal(got[0], mean) and np.array_equal(np.triu(got[1]), np.triu(cov))
-            self.src[key] = h
-
-    def close(self):
-        for h in [self.f] + list(self.src.values()):
-            h.close()
-
-    def raw00(self):
-        """P_base[0, 0] as stored (no flush)."""
-        out = np.empty(1)
-        self.sd.load_library().ekf_debug_snapshot(self.f._h, 0, 0, out.ctypes.data_as(C.POINTER(C.c_double)), 1)
-        return float(out[0])
-
-    def got(self):
-        f = self.f
-        mean, cov = f.state()
-        assert f.size() == len(mean)
-        return mean, cov, f.tag_index(), f.flags()
-
-    def set_option(self, name, value):
-        self.f.set_option(name, value)
-
-    def set_state_diag(self, mean, diag):
-        self.f.set_state_diag(mean, diag)
-
-    def set_tag_index(self, tags):
-        self.f.set_tag_index(tags)
-
-    def step1(self, lin, ang, idx, zr, zb):
-        self.f.step(lin, ang, [int(i) for i in idx], [float(x) for x in zr], [float(x) for x in zb])
-
-    def run_stream(self, lin, ang, idx, zr, zb):
-        self.f.run_stream(lin, ang, idx, zr, zb)
-
-    def step_detections(self, lin, ang, win):
-        self.f.step_detections(lin, ang, win)
-        assert self.f.assoc_fallbacks() == 0               # a device-side window
-
-    def predict_linear(self, pose, F, Q):
-        self.f.predict_linear(pose, F, Q, b=0)
-
-    def predict_dense1(self, F, Q):
-        self.f.predict_dense(F, Q)
-
-    def update_direct(self, targets, z, R):
-        assert self.f.update_direct(targets, z, R).applied.all()
-
-    def update_linear(self, landmarks, H, R, z):
-        assert self.f.update_linear(landmarks, H, R, z=z, b=0).applied.all()
-
-    def transform(self, T, cov=None):
-        self.f.transform(T, cov, b=0)
-
-    def join(self, key, transform=None, cov=None):
-        first = (self.f.size() - 3) // 2
-        r = self.f.join(self.src[key], transform=transform, cov=cov)
-        assert (r.first, r.count) == (first, (self.src[key].size() - 3) // 2)
-
-    def remove_landmarks(self, lms):
-        self.f.remove_landmarks(lms)
-
-    def add_landmarks(self, xy):
-        self.f.add_landmarks(xy)
-
-    def copy_in(self, key):
-        self.f.copy_from(self.src[key])
-
-
-def model_bound(tr):
-    """The active bound the model's history implies: past the highest landmark correlated with anything."""
-    seen = np.flatnonzero(tr.seen)
-    return 3 + 2 * (int(seen[-1]) + 1) if len(seen) else 3
-
-
 @pytest.mark.parametrize("a,b", sc.PAIRS, ids=[sc.pair_name(a, b).replace(" ", "_").replace("/", "-") for a, b in sc.PAIRS])
 def test_pair(sd, both_paths, a, b):
     general = both_paths == "general_kernels"
@@ -131,7 +44,7 @@ def test_pair(sd, both_paths, a, b):
 
     def judge(stage):
         tr = model.tr
-        bounds[stage] = (model_bound(tr), len(tr.mean))
+        bounds[stage] = (sc.model_bound(tr), len(tr.mean))
         if stage == "start":
             # ranks pending: the stored P_base[0, 0] is not the covariance's.  The model and the filter agree to 1e-9 (asserted
             # after A), one pending single step alone adds 0.01 of pose noise: a difference above 1e-6 is what is pending

@@ -19,14 +19,6 @@ ENTRYWISE = ("corr_max", "mean_landmarks", "loose_cross")
 EPS_V = 32 * np.finfo(float).eps * sc.INIT_VAR
 
 
-def as_got(model):
-    """A model's state as a `got`: NumPy's products leave the last bits of P_ij and P_ji apart, and the judge demands of `got`
-    the exact symmetry the device gives."""
-    mean, cov, tags = model.state()
-    cov = np.asarray(cov, dtype=float)
-    return np.asarray(mean, dtype=float), (cov + cov.T) / 2, tags, 0
-
-
 @pytest.fixture(scope="module")
 def floors():
     """(a, b) -> {stage: {piece: float64 model against longdouble model}}."""
@@ -40,7 +32,7 @@ def floors():
             assert mld.tr.cov.dtype == np.longdouble and m64.tr.cov.dtype == np.float64
             assert len(m64.tr.mean) == len(mld.tr.mean) and m64.tr.tags == mld.tr.tags
             assert np.array_equal(m64.tr.seen, mld.tr.seen)
-            stages[stage] = pb.state_errors(as_got(m64)[:2], mld.state()[:2], sc.INIT_VAR)
+            stages[stage] = pb.state_errors(sc.as_got(m64)[:2], mld.state()[:2], sc.INIT_VAR)
 
         sc.run_case(sc.Driver(m64, mld), a, b, judge)
         out[a, b] = stages
@@ -115,13 +107,6 @@ def reference(ops):
     return m, d, rng
 
 
-def keep_rows_beyond(before, after, bound):
-    """What a pass that skips every row at or beyond `bound` leaves: those rows and columns (and means) as they were."""
-    mean, cov = np.array(after[0]), np.array(after[1])
-    mean[bound:], cov[bound:, :], cov[:, bound:] = before[0][bound:], before[1][bound:, :], before[1][:, bound:]
-    return mean, cov
-
-
 def judged(got, model, entry_tol=sc.ENTRY_TOL):
     return pb.assert_state_close((got[0], (got[1] + got[1].T) / 2, model.tr.tags, 0), model.state(), sc.INIT_VAR, sc.TOL, entry_tol)
 
@@ -131,7 +116,7 @@ def test_a_bound_one_landmark_too_low_is_caught():
     before = (m.tr.mean.copy(), m.tr.cov.copy())
     sc.observe(d, rng, [0, 25])                            # the highest informed landmark: the bound must cover it
     judged(m.state(), m)
-    got = keep_rows_beyond(before, m.state(), 3 + 2 * 25)
+    got = sc.keep_rows_beyond(before, m.state(), 3 + 2 * 25)
     with pytest.raises(AssertionError, match="landmarks: .* exceeds|corr_max: .* exceeds"):
         judged(got, m)
 
@@ -160,7 +145,7 @@ def test_a_bound_that_did_not_rise_after_a_transform_with_a_covariance_is_caught
     sc.observe(d, rng, [0, 3])
     err = judged(m.state(), m)
     assert err["loose_cross"] < 1e-15 and len(pb.loose_landmarks(m.tr.cov, sc.INIT_VAR)[0]) == 4
-    got = keep_rows_beyond(before, m.state(), 3 + 2 * 26)         # the bound of before the transform
+    got = sc.keep_rows_beyond(before, m.state(), 3 + 2 * 26)         # the bound of before the transform
     with pytest.raises(AssertionError, match="loose_cross|loose_mean"):
         judged(got, m)
 
