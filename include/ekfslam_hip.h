@@ -519,6 +519,59 @@ int ekf_update(ekf_handle *h, const int *idx, const double *range, const double 
 int ekf_step(ekf_handle *h, const double *lin, const double *ang, const int *idx,
              const double *range, const double *bearing, const int *m, int stride);
 
+/* Localisation on a FROZEN MAP: pose-only steps for a run that drives on a map it considers finished -- the second lap, a fleet of
+ * forked hypotheses relocalising against one map, the localisation phase behind a noise tuning.  The Schmidt-Kalman ("consider")
+ * update: per observation of landmark l (state indices t = 3 + 2l, t + 1), H = [H_p | H_l] from the filter's own linearisation at
+ * the current pose and the frozen landmark mean, S = H P H^T + R on the five indices exactly as ekf_step forms it, and the gain
+ * K = [K_p; 0] with K_p = (P H^T)[0:3] S^-1: the landmarks' uncertainty and their correlations with the pose enter S and the pose
+ * rows, the landmarks themselves do not move.  pose += K_p y, and with the Joseph form (I - K H) P (I - K H)^T + K R K^T
+ *     P[r,r] <- P[r,r] - K_p S K_p^T,   P[r,c] <- (I - K_p H_p) P[r,c] - K_p H_l P[t:t+2, c]  (c >= 3),   P[a,b] as it was (a, b >= 3)
+ * Unlike "treat the map as perfect" the result stays consistent; it differs from full SLAM's except on an exactly known map
+ * (P[a,b] = 0 for all b where a >= 3: there the two agree to rounding).  No claim is made that the pose covariance exceeds full
+ * SLAM's: with sequentially re-linearised updates it need not.
+ * ekf_localize_step: prediction (ekf_predict's motion model and noise) + the frozen-map update of idx[b*stride + 0..m[b]) in that
+ * order, for the whole bank; ekf_localize_update: the update alone, behind ekf_predict, ekf_predict_linear or an odometry
+ * prediction; ekf_localize_run: steps [first, first + count) of the uploaded stream (ekf_stream_upload) in localisation mode, back
+ * to back without a host synchronisation -- the same two kernels per step reading the stream's records, the same bits as the same
+ * steps through ekf_localize_step.  Arguments as ekf_step's / ekf_stream_run's; more than EKF_MMAX observations of a trajectory
+ * run as several passes, the prediction in the first.  One difference: an index MAY come twice in one call (the second observation
+ * is linearised at the pose the first one left; the SLAM update keys observations by index and refuses that).
+ * Two launches per step (pass): k_loc_solve, one wave per trajectory, runs the prediction and the sequential chain on the
+ * compressed set {0, 1, 2, t_j, t_j + 1} and collapses the step to x_c <- A x_c + sum_j B_j P[t_j:t_j+2, c]; k_loc_rows applies
+ * that to every column of the pose rows in one fully parallel O(n m) launch.  Never a covariance pass, no rank.
+ * Written: rows 0..2 of the stored triangle below the (raised) active bound, the pose mean, the sticky flags.
+ * Left alone, bit for bit: landmark means and every P(a, b) with a, b >= 3; sizes, tag table, noise rows, the uploaded stream
+ * (which stays runnable); ekf_profile_passes and ekf_debug_cadences / _chained / _lookaheads do not move, and the call is never
+ * counted for "flush_every" or "rank_limit"; a handle on the small-state path stays on it (the kernels work on P_base in global
+ * memory in both layouts, and read their records from the pinned ring as that path's steps do).
+ * Ranks pending at entry: the call first runs the ordinary covariance pass, once (as ekf_flush), and then works on P_base with
+ * nothing pending; it leaves nothing pending, so later localisation calls run no pass at all.
+ * Active bound: an observation correlates the pose with the landmark it names: the call raises the bound over the highest
+ * landmark observed, as ekf_update_linear does (also over one the NIS gate then rejects).
+ * On this path too: ekf_set_noise's row supplies R and the motion noise; the NIS gate rejects an observation with K_p = 0 -- the
+ * state is then BIT-IDENTICAL to the same call without that observation (given the same active bound), the gate counter counts
+ * it and the other observations of the step are applied; the innovation log gets one step per call (y, S, NIS, the rejected bit),
+ * the pose log one row per call (a lone ekf_localize_update logs as a lone ekf_update); the config flags
+ * enable_measurement_model, enable_circular_interpolation, disable_motion_model and arc_threshold act as on the other paths.
+ * Degenerate geometry (pose on the landmark, q = 0) gives NaN as there and EKF_FLAG_NONFINITE.
+ * Every sum runs in observation order: a trajectory's bits depend neither on its slot nor on its neighbours.
+ * ASYNCHRONOUS like ekf_step.  EKF_ERR_ARG (nothing changed): NULL arrays, a count outside [0, stride], an index outside the
+ * trajectory's map; ekf_localize_run: EKF_ERR_STATE for a range outside the uploaded stream or a stream the state no longer
+ * fits, as ekf_stream_run.  EKF_ERR_STATE after an earlier call failed half way.  The sticky flags are not read back.
+ * With ekf_set_option("profile_kernels", 1) the launches are classes 9 (k_loc_solve) and 10 (k_loc_rows) of ekf_profile_read_class.
+ * Measured on one MI355X (tools/localize_time.py, profiles/localize.txt), device time per step for the whole bank, m = 8, every
+ * state index active, 40 steps behind a dense start; the passes ekf_step causes are charged to it: 32 x N = 2000 30 us
+ * (ekf_localize_run 27) against ekf_step 186 and ekf_stream_run 160; 1 x N = 8000 23 (20) against 93 and 78; 1 x N = 2000 22 (19)
+ * against 31 and 17 -- NOT faster than the chained SLAM cadence there: two launches and a sequential chain of ~1.5 us per
+ * observation in one wave are the floor (k_loc_solve 14 us, k_loc_rows 8 us between their event pairs) --; 256 x N = 20 24 (19)
+ * against 19 and 10: slower than the small-state path, which keeps P in LDS across a whole stream.  The map staying fixed is
+ * the feature either way. */
+int ekf_localize_step(ekf_handle *h, const double *lin, const double *ang, const int *idx,
+                      const double *range, const double *bearing, const int *m, int stride);
+int ekf_localize_update(ekf_handle *h, const int *idx, const double *range, const double *bearing,
+                        const int *m, int stride);
+int ekf_localize_run(ekf_handle *h, int first, int count);
+
 /* ekf_step followed by ekf_download_state(h, b, mu, P, n), as ONE call: one iteration of the reference's loop
  * (`mean, covariance, tags = EKF_pose_estimation(...)`, src/replay_no_ros.py:229-237; the return at :482 hands back the
  * whole state every call).  Same results as the two calls.  On the small-state path (option "small_state") the step's
@@ -592,7 +645,7 @@ int ekf_profile_read(ekf_handle *h, double *pass_ms_total, long long *pass_launc
 long long ekf_profile_passes(ekf_handle *h);
 /* With ekf_set_option("profile_kernels", 1) (a diagnostic run: every record costs its stream ~6 us) the other launches of a
  * fused cadence carry event pairs too: cls 1 the solve launch, 2 the chain (or look-ahead gather) launch, 3 the panel launch,
- * 0 the pass; 4 the k_direct launch of ekf_update_direct; 5 the k_linear launch of ekf_update_linear; 6 the k_join launch of ekf_join_maps (with its snapshot launch); 7 the k_predict_pose launch of ekf_predict_linear; 8 the k_transform launch of ekf_transform.  Does not reset: read before ekf_profile_read. */
+ * 0 the pass; 4 the k_direct launch of ekf_update_direct; 5 the k_linear launch of ekf_update_linear; 6 the k_join launch of ekf_join_maps (with its snapshot launch); 7 the k_predict_pose launch of ekf_predict_linear; 8 the k_transform launch of ekf_transform; 9 and 10 the k_loc_solve and k_loc_rows launches of ekf_localize_*.  Does not reset: read before ekf_profile_read. */
 int ekf_profile_read_class(ekf_handle *h, int cls, double *ms_total, long long *launches);
 /* Options: name (default, allowed values) meaning.  Unknown names and values out of range fail with EKF_ERR_ARG.
  *   "flush_every"         (0, 0..64)    steps per covariance pass; 0 = auto, by "rank_limit"

@@ -256,6 +256,9 @@ struct ekf_handle : ekf::HostPlan {
   DeviceBuf<PredictIn> d_pred;
   PinnedBuf<PredictIn> h_pred;
   ekf::PredictPlan predict_plan;
+  // ekf_localize_* (allocated on first use): what k_loc_solve hands to k_loc_rows, one record per trajectory; consecutive steps
+  // reuse it in stream order
+  DeviceBuf<LocRec> dloc;
   std::string err;
 };
 
@@ -2407,6 +2410,144 @@ extern "C" int ekf_step(ekf_handle* h, const double* lin, const double* ang, con
   return do_step(h, FLAG_PREDICT | FLAG_UPDATE, lin, ang, idx, range, bearing, m, stride);
 }
 
+// ---- localisation on a frozen map (ekf_localize_step / _update / _run; k_loc_solve + k_loc_rows, ekf_localize.hip) ----
+// Every entry is loc_begin -- what runs on the second stream is joined, what is pending is applied by the ordinary pass, once:
+// the kernels work on P_base with nothing pending, and leave nothing pending -- then per step (per update pass of a step) loc_pass:
+// the two launches in their profile brackets (classes 9 and 10), the innovation log's copy of the solve's y / S^-1 (k_innov_step
+// reads them where k_solve leaves its own), and behind a step its pose-log row (k_pose_step, on either path as for
+// ekf_predict_linear).  Neither pending_k / pending_steps nor any counter moves and cur / dcur do not flip: the pose mean is
+// written in place.  A failure after the first launch leaves every trajectory undefined (host_bad: EKF_ERR_STATE from then on).
+static int loc_begin(ekf_handle* h) {
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (int rc = join_aux(h)) return rc;
+  if (int rc = flush_pending(h)) return rc;
+  RES_TRY(h, "the localisation records", h->dloc.reserve((size_t)h->batch, 0, h->stream));
+  return EKF_OK;
+}
+static int loc_pass(ekf_handle* h, const StepIn* in, int groups) {
+  const BankView bank = bank_view(h);
+  ProfBracket pb;
+  if (int rc = prof_open(h, 9, h->stream, &pb)) return rc;
+  launch_loc_solve(h->stream, bank, h->dmu2[h->cur].p, in, h->dfloor.p, h->dloc.p, h->dcfg);
+  if (int rc = prof_close(h, &pb)) return rc;
+  if (int rc = prof_open(h, 10, h->stream, &pb)) return rc;
+  launch_loc_rows(h->stream, bank, h->dloc.p, groups);
+  if (int rc = prof_close(h, &pb)) return rc;
+  if (h->dinnov.p && h->lg_slot >= 0)
+    launch_innov_step(h->stream, in, h->dso.p, h->dcfg.enable_measurement_model, h->dcfg.gate_rej != nullptr, h->batch,
+                      innov_log(h, h->lg_slot, h->lg_jbase));
+  HIP_TRY(h, hipGetLastError());
+  return EKF_OK;
+}
+static int loc_pose_row(ekf_handle* h) {
+  if (!h->dpose.p || h->pl_slot < 0) return EKF_OK;
+  launch_pose_step(h->stream, pending_view(h, 0, h->batch), pose_log(h, h->pl_slot));
+  HIP_TRY(h, hipGetLastError());
+  return EKF_OK;
+}
+static int loc_half_failed(ekf_handle* h, int rc) {
+  std::fill(h->host_bad.begin(), h->host_bad.end(), (unsigned char)1);
+  return rc;
+}
+
+static int do_localize(ekf_handle* h, const char* fn, int base_flags, const double* lin, const double* ang, const int* idx,
+                       const double* range, const double* bearing, const int* m, int stride) {
+  if (!h) return EKF_ERR_ARG;
+  LogScope log_scope{h};
+  if (int rc = check_host_bad(h, fn)) return rc;
+  if (int rc = refresh_sizes(h)) return rc;
+  const bool upd = (base_flags & FLAG_UPDATE) != 0, pred = (base_flags & FLAG_PREDICT) != 0;
+  LocPlan lp;
+  if (const char* why = plan_localize(h, pred, upd, lin, ang, idx, range, bearing, m, stride, lp)) return bad_arg(h, fn, why);
+  if (int rc = loc_begin(h)) return rc;
+  if (int rc = push_floor(h, false)) return rc;
+  const bool direct = small_path(h);                     // (the workgroups fetch their records from the pinned ring: see do_step)
+  const bool logged = h->dinnov.p && upd;                // (a lone prediction is not a logged step)
+  h->pl_slot = h->dpose.p ? (long)(h->pose_steps % h->pose_cap) : -1;
+  for (int p = 0; p < lp.passes; ++p) {
+    h->lg_slot = logged ? (long)(h->innov_steps % h->innov_cap) : -1;
+    h->lg_jbase = MMAX * p;
+    int slot;
+    if (int rc = ring_take(h, &slot)) return p ? loc_half_failed(h, rc) : rc;
+    StepIn* hs = h->h_ring.p + (size_t)slot * h->batch;
+    StepIn* ds = h->d_ring.p + (size_t)slot * h->batch;
+    const int flags = (upd ? FLAG_UPDATE : 0) | ((pred && p == 0) ? FLAG_PREDICT : 0);
+    for (int b = 0; b < h->batch; ++b) {
+      const int mb = (upd && h->cfg.enable_measurement_model) ? m[b] : 0;
+      const long off = (long)b * stride;
+      // (fill_step raises the host's bound over the pass's landmarks: a general row correlates the pose with the landmark it names)
+      fill_step(hs[b], h->n[b], h->neff[b], pred ? lin[b] : 0.0, pred ? ang[b] : 0.0, flags, idx ? idx + off : nullptr,
+                range ? range + off : nullptr, bearing ? bearing + off : nullptr, mb, p);
+      h->neff_enq[b] = h->opt_active_bound ? h->neff[b] : h->n[b];
+    }
+    if (!direct) {
+      if (hipMemcpyAsync(ds, hs, sizeof(StepIn) * h->batch, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+        return loc_half_failed(h, fail(h, EKF_ERR_HIP, std::string(fn) + ": the records' upload failed"));
+      if (int rc = ring_done(h, slot)) return loc_half_failed(h, rc);
+    }
+    if (int rc = loc_pass(h, direct ? hs : ds, loc_rows_groups(loc_bound_hi(h)))) return loc_half_failed(h, rc);
+    if (direct)
+      if (int rc = ring_done(h, slot)) return loc_half_failed(h, rc);   // (the slot is free once the kernels have run)
+  }
+  if (logged) h->innov_steps += 1;
+  if (int rc = loc_pose_row(h)) return loc_half_failed(h, rc);
+  if (h->dpose.p) h->pose_steps += 1;
+  return EKF_OK;
+}
+
+extern "C" int ekf_localize_step(ekf_handle* h, const double* lin, const double* ang, const int* idx, const double* range,
+                                 const double* bearing, const int* m, int stride) {
+  if (!h) return EKF_ERR_ARG;
+  HIP_TRY(h, hipSetDevice(h->device));
+  return do_localize(h, "ekf_localize_step", FLAG_PREDICT | FLAG_UPDATE, lin, ang, idx, range, bearing, m, stride);
+}
+
+extern "C" int ekf_localize_update(ekf_handle* h, const int* idx, const double* range, const double* bearing, const int* m,
+                                   int stride) {
+  if (!h) return EKF_ERR_ARG;
+  HIP_TRY(h, hipSetDevice(h->device));
+  return do_localize(h, "ekf_localize_update", FLAG_UPDATE, nullptr, nullptr, idx, range, bearing, m, stride);
+}
+
+// Steps [first, first + count) of the uploaded stream in localisation mode: the same two launches per step, reading StepIn from
+// the stream buffer, back to back without a host synchronisation.  The stream itself is not touched and stays runnable.
+extern "C" int ekf_localize_run(ekf_handle* h, int first, int count) {
+  const char* fn = "ekf_localize_run";
+  if (!h) return EKF_ERR_ARG;
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (int rc = check_host_bad(h, fn)) return rc;
+  if (int rc = refresh_sizes(h)) return rc;
+  if (first < 0 || count < 0 || first + count > h->stream_steps)
+    return fail(h, EKF_ERR_STATE, "ekf_localize_run: range outside the uploaded stream");
+  if (h->stream_stale)
+    return fail(h, EKF_ERR_STATE, "ekf_localize_run: landmarks were removed (ekf_remove_landmarks) after the stream was uploaded: its "
+                                  "landmark indices and sizes refer to the state before; upload the stream again");
+  for (int b = 0; b < h->batch; ++b)                   // the state may have been replaced since the upload
+    if (h->stream_maxlm[b] > (h->n[b] - 3) / 2)
+      return fail(h, EKF_ERR_STATE, "ekf_localize_run: the uploaded stream observes landmarks the current state does not have");
+  if (count == 0) return EKF_OK;
+  if (int rc = loc_begin(h)) return rc;
+  if (int rc = push_floor(h, true)) return rc;
+  LogScope log_scope{h};
+  const long cap = h->innov_cap, pcap = h->pose_cap;
+  const int* own_last = h->stream_own.data() + (size_t)(first + count - 1) * h->batch;
+  const int groups = loc_rows_groups(loc_bound_hi(h, own_last));
+  for (int k = first; k < first + count; ++k) {
+    h->lg_slot = h->dinnov.p ? (long)((h->innov_steps + (k - first)) % cap) : -1;
+    h->lg_jbase = 0;
+    h->pl_slot = h->dpose.p ? (long)((h->pose_steps + (k - first)) % pcap) : -1;
+    if (int rc = loc_pass(h, h->d_stream.p + (size_t)k * h->batch, groups)) return loc_half_failed(h, rc);
+    if (int rc = loc_pose_row(h)) return loc_half_failed(h, rc);
+  }
+  if (h->dinnov.p) h->innov_steps += count;
+  if (h->dpose.p) h->pose_steps += count;
+  for (int b = 0; b < h->batch; ++b) {
+    h->neff[b] = std::max(h->neff[b], std::min(h->n[b], own_last[b]));
+    h->neff_enq[b] = h->opt_active_bound ? h->neff[b] : h->n[b];
+  }
+  return EKF_OK;
+}
+
 // ekf_step + ekf_download_state(b) in one call: what one iteration of the reference's loop is (EKF_pose_estimation returns
 // mean and covariance every call, src/replay_no_ros.py:229-237, :482).  On the small-state path the step's own launch
 // leaves trajectory b's state in pinned host memory (k_small_stream's host_out): one launch and one synchronisation per call.
@@ -2747,7 +2888,7 @@ extern "C" int ekf_profile_read(ekf_handle* h, double* pass_ms_total, long long*
 
 // ("profile_kernels" = 1) the same for the cadence's other launches: cls 1 the solve launch, 2 the chain / look-ahead gather
 // launch, 3 the panel launch (0: the covariance pass), 4 k_direct, 5 k_linear, 6 k_join (with its snapshot launch), 7
-// k_predict_pose, 8 k_transform; does not reset -- read these BEFORE ekf_profile_read
+// k_predict_pose, 8 k_transform, 9 k_loc_solve, 10 k_loc_rows; does not reset -- read these BEFORE ekf_profile_read
 extern "C" int ekf_profile_read_class(ekf_handle* h, int cls, double* ms_total, long long* launches) {
   if (!h || !ms_total || !launches) return EKF_ERR_ARG;
   HIP_TRY(h, hipSetDevice(h->device));

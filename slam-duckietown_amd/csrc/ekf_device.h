@@ -79,6 +79,22 @@ struct alignas(16) PredictIn {
   double pad[2];
 };
 static_assert(sizeof(PredictIn) == 192, "PredictIn is 192 bytes");
+// ekf_localize_* (k_loc_solve -> k_loc_rows, ekf_localize.hip): what one step's (one update pass's) sequential chain hands to
+// the row kernel for one trajectory.  A column x_c = P(0..2, c), c >= 3, of the pose rows becomes
+//     A x_c + sum_j B[j] [P(t[j], c); P(t[j] + 1, c)]       (A 3 x 3 and B[j] 3 x 2 row-major, j < m in observation order)
+// below `bound`, the active bound of the step (the record's, raised to the handle's floor).  rej: bit j set = the NIS gate rejected
+// observation j (B[j] = 0; the row kernel skips it); apply == 0: the step neither predicts nor observes -- nothing is touched.
+constexpr int LOC_THREADS = 256;        // k_loc_rows: columns per workgroup
+struct alignas(16) LocRec {
+  double A[9];
+  double B[MMAX][6];
+  int t[MMAX];
+  int m, bound;
+  unsigned rej;
+  int apply;
+  double pad;
+};
+static_assert(sizeof(LocRec) == 928 && sizeof(LocRec) % 16 == 0, "LocRec is 928 bytes");
 __host__ __device__ __forceinline__ int p_lds(int ld) { return ld < PPW ? ld : PPW; }
 __host__ __device__ __forceinline__ long p_col(int ld, int j) { return (long)(j >> 12) * ((long)ld * PPW) + (j & (PPW - 1)); }
 // the same as a 32-bit byte offset (ekf_create bounds one covariance by 4 GiB)

@@ -979,6 +979,57 @@ inline const char* plan_predict_linear(const HostPlan* h, int b0, int count, con
   return nullptr;
 }
 
+// ---- localisation on a frozen map (ekf_localize_step / _update / _run: k_loc_solve + k_loc_rows, ekf_localize.hip) ----
+// The arguments of a step checked as ekf_step checks its own, in its order -- lin / ang where the call predicts, m and the stride,
+// every count in [0, stride], the observation arrays where anything is observed, every index inside its trajectory's map -- with
+// one difference: an index may come TWICE in one call.  The frozen-map update is defined for it (the second observation is
+// linearised at the pose the first one left, the landmark has not moved), where the SLAM update keys observations by index
+// (validate_obs).  A call with more than MMAX observations of a trajectory runs in loc_passes passes of two launches each, the
+// prediction in the first one only (fill_step cuts the list, as for do_step).
+// Returns nullptr, or what is wrong (then nothing of `lp` is to be used and no handle state has changed).
+struct LocPlan {
+  int m_hi = 0, passes = 1;
+};
+inline int loc_passes(int m_hi) { return std::max(1, (m_hi + MMAX - 1) / MMAX); }
+inline const char* plan_localize(const HostPlan* h, bool pred, bool upd, const double* lin, const double* ang, const int* idx,
+                                 const double* range, const double* bearing, const int* m, int stride, LocPlan& lp) {
+  if (pred && (!lin || !ang)) return "NULL lin/ang";
+  if (upd && (!m || stride < 0)) return "NULL m / bad stride";
+  lp.m_hi = 0;
+  const bool meas = upd && h->cfg.enable_measurement_model;
+  if (meas)
+    for (int b = 0; b < h->batch; ++b) {
+      if (m[b] < 0 || m[b] > stride) return "m[b] must be in [0, stride]";
+      lp.m_hi = std::max(lp.m_hi, m[b]);
+    }
+  if (lp.m_hi > 0 && (!idx || !range || !bearing)) return "NULL observation arrays";
+  if (lp.m_hi > 0)
+    for (int b = 0; b < h->batch; ++b) {
+      const int n_lm = (h->n[b] - 3) / 2;
+      for (int i = 0; i < m[b]; ++i) {
+        const int id = idx[(long)b * stride + i];
+        if (id < 0 || id >= n_lm) return "landmark index outside the current state (add_landmarks first)";
+      }
+    }
+  lp.passes = loc_passes(lp.m_hi);
+  return nullptr;
+}
+// The column groups of k_loc_rows' grid: LOC_THREADS columns each, up to the largest active bound a record of the launch can
+// carry -- per trajectory the host's bound (which fill_step has raised over the call's landmarks) or the handle's floor,
+// whichever is larger, and where `own` is given (a run: the stream's own bound per trajectory at the run's last step) that
+// too; the whole state with the shortcut off or while the device has grown the sizes.
+inline int loc_bound_hi(const HostPlan* h, const int* own = nullptr) {
+  int hi = 3;
+  for (int b = 0; b < h->batch; ++b) {
+    int want = std::max(h->neff[b], h->floor_host[b]);
+    if (own) want = std::max(want, own[b]);
+    if (!h->opt_active_bound || h->sizes_dirty) want = h->sizes_dirty ? h->n_max : h->n[b];
+    hi = std::max(hi, std::min(want, h->sizes_dirty ? h->n_max : h->n[b]));
+  }
+  return hi;
+}
+inline int loc_rows_groups(int n_hi) { return (std::max(n_hi, 3) + LOC_THREADS - 1) / LOC_THREADS; }
+
 // ekf_copy_trajectories (k_copy_traj, ekf_copy.hip): the k pairs (src_b[i] of `src` -> dst_b[i] of `dst`) checked -- indices
 // inside their banks, no destination twice, inside one handle no trajectory both read and written, the same device, every
 // source's size within the destination's n_max -- and grouped by source: a group is one source and up to COPY_FANOUT of its

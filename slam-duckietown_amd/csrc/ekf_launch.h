@@ -105,7 +105,7 @@ void launch_factor_solve(hipStream_t st, const FactorView& w, int f0, int count,
                          double* white, double* quad);
 void launch_factor_multiply(hipStream_t st, const FactorView& w, int f0, int count, int nblk_hi, const double* z, int nrhs,
                             int stride, double* out);
-// ---- state surgery (ekf_remove.hip, ekf_direct.hip, ekf_linear.hip, ekf_predict_linear.hip, ekf_copy.hip, ekf_join.hip, ekf_transform.hip, ekf_dense.hip) ----
+// ---- state surgery (ekf_remove.hip, ekf_direct.hip, ekf_linear.hip, ekf_predict_linear.hip, ekf_localize.hip, ekf_copy.hip, ekf_join.hip, ekf_transform.hip, ekf_dense.hip) ----
 // rp.rows: the launch's largest new size (grid rows); nb trajectories from b0; src / dst: rp's tables on the device
 void launch_remove(hipStream_t st, const BankView& k, double* mu, const RemovePlan& rp, const int* src, const int* dst,
                    unsigned* rflag, int b0, int nb, unsigned seq);
@@ -118,6 +118,13 @@ void launch_linear(hipStream_t st, int rows_cap, const BankView& k, double* dacc
 // trajectories [f.b0, f.b0 + f.count), one record each in `in`; P and mu: f.P and f.mu, written (rows 0..2 and the pose mean);
 // n_hi: the largest bound of a record that applies (plan_predict_linear); f.kb > 0: the form that gathers the pending ranks
 void launch_predict_pose(hipStream_t st, const PendingView& f, double* P, double* mu, const PredictIn* in, int n_hi);
+// ekf_localize_* (ekf_localize.hip): the whole bank, one StepIn each in `in` (device copy, uploaded stream or the pinned ring).
+// The solve writes the pose mean into `mu` in place, the pose block into k.P, the records `rec` (one per trajectory of the bank)
+// and, for the logs, k.so[b].it[j].y / .si, k.so[b].rej and k.so[b].neff; the row launch, behind it on the same stream, applies
+// the records to rows 0..2 of k.P: `groups` column groups (ekf_host_plan.h: loc_rows_groups of the bank's largest bound)
+void launch_loc_solve(hipStream_t st, const BankView& k, double* mu, const StepIn* in, const int* neff_floor, LocRec* rec,
+                      const DeviceConfig& cfg);
+void launch_loc_rows(hipStream_t st, const BankView& k, const LocRec* rec, int groups);
 // groups x (tiles of the largest source + 1) workgroups; tab: plan_copy's table on the device
 void launch_copy_traj(hipStream_t st, bool nt, const BankView& src, const BankView& dst, const double* mus, double* mud,
                       const int* tab, int groups, int n_hi);

@@ -145,6 +145,9 @@ ABI = {
     "ekf_predict_linear": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _ip]),
     "ekf_update": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _ip, C.c_int]),
     "ekf_step": (C.c_int, [C.c_void_p, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
+    "ekf_localize_step": (C.c_int, [C.c_void_p, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
+    "ekf_localize_update": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _ip, C.c_int]),
+    "ekf_localize_run": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ekf_host_alloc": (C.c_void_p, [C.c_size_t]),
     "ekf_host_free": (None, [C.c_void_p]),
     "ekf_step_fetch": (C.c_int, [C.c_void_p, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int, C.c_int, _dp, _dp, C.c_int]),
@@ -511,6 +514,7 @@ class EkfSlam:
         self._stages = {}
         self._out = None
         self._pose_cap = 0                                   # ring size of the pose log (log_poses); 0: off
+        self._stream_steps = 0                               # steps of the uploaded stream (stream_upload)
         self._factor_generation = 0                          # counts factor() and release_factor(): a CovFactor is live while it matches
 
     # -- plumbing ------------------------------------------------------------------------------
@@ -1429,6 +1433,28 @@ class EkfSlam:
         pI, pR, pB, pm, stride = self._obs(idx, ranges, bearings)
         self._check(self._lib.ekf_step(self._h, self._plin, self._pang, pI, pR, pB, pm, stride))
 
+    # -- localisation on a frozen map ------------------------------------------------------------
+    def localize(self, lin, ang, idx, ranges, bearings):
+        """predict + the frozen-map (Schmidt-Kalman) update (``ekf_localize_step``): the pose and rows 0..2 of P move, landmark
+        means and every P[a, b] with a, b >= 3 stay bit for bit; no rank, never a covariance pass (ranks pending at entry are
+        applied first, once).  Arguments as ``step``; an index may come twice."""
+        self._per_traj(lin, "lin", self._lin)
+        self._per_traj(ang, "ang", self._ang)
+        pI, pR, pB, pm, stride = self._obs(idx, ranges, bearings)
+        self._check(self._lib.ekf_localize_step(self._h, self._plin, self._pang, pI, pR, pB, pm, stride))
+
+    def localize_update(self, idx, ranges, bearings):
+        """The frozen-map update alone (``ekf_localize_update``), behind ``predict``, ``predict_linear`` or ``predict_odometry``."""
+        pI, pR, pB, pm, stride = self._obs(idx, ranges, bearings)
+        self._check(self._lib.ekf_localize_update(self._h, pI, pR, pB, pm, stride))
+
+    def run_localize(self, first: int = 0, count: Optional[int] = None):
+        """Steps [first, first + count) of the uploaded stream (``stream_upload``; default: to its end) in localisation mode
+        (``ekf_localize_run``): asynchronous, the same bits as the same steps through ``localize``."""
+        if count is None:
+            count = self._stream_steps - int(first)
+        self._check(self._lib.ekf_localize_run(self._h, int(first), int(count)))
+
     def step_state(self, lin, ang, idx, ranges, bearings, b: int = 0):
         """``step`` followed by ``state(b)`` as one library call (``ekf_step_fetch``): one iteration of the reference's
         loop, which gets mean and covariance back from every call (src/replay_no_ros.py:229-237).  On the small-state
@@ -1592,6 +1618,7 @@ class EkfSlam:
         m = np.full((steps, self.batch), stride, dtype=np.int32) if m is None else _i32(m).reshape(steps, self.batch)
         self._check(self._lib.ekf_stream_upload(self._h, steps, _p(lin), _p(ang), _p(idx, _ip), _p(ranges),
                                                 _p(bearings), _p(m, _ip), stride))
+        self._stream_steps = steps
         return steps
 
     def stream_run(self, first: int, count: int):
@@ -1629,7 +1656,8 @@ class EkfSlam:
 
     def profile_read_class(self, cls: int):
         """(total ms, number) of the bracketed launches of class `cls` (1 solve, 2 chain / gather, 3 panel, 4 the k_direct launch of
-        update_direct, 5 the k_linear launch of update_linear, 6 the k_join launch of join, 7 the k_predict_pose launch of predict_linear; needs the option
+        update_direct, 5 the k_linear launch of update_linear, 6 the k_join launch of join, 7 the k_predict_pose launch of predict_linear,
+        9 / 10 the k_loc_solve / k_loc_rows launches of localize; needs the option
         "profile_kernels"); read before `profile_read`, which resets."""
         ms, cnt = C.c_double(), C.c_longlong()
         self._check(self._lib.ekf_profile_read_class(self._h, int(cls), C.byref(ms), C.byref(cnt)))
