@@ -84,3 +84,13 @@ class Device:
 
     def copy_in(self, key):
         self.f.copy_from(self.src[key])
+
+    def localize1(self, lin, ang, idx, zr, zb):
+        self.f.localize(lin, ang, [int(i) for i in idx], [float(x) for x in zr], [float(x) for x in zb])
+
+    def localize_update1(self, idx, zr, zb):
+        self.f.localize_update([int(i) for i in idx], [float(x) for x in zr], [float(x) for x in zb])
+
+    def run_localize_stream(self, lin, ang, idx, zr, zb):
+        self.f.stream_upload(lin, ang, idx, zr, zb)
+        self.f.run_localize(0, len(lin))

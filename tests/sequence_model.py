@@ -6,6 +6,7 @@ newer calls, each DELEGATED to the model the project already trusts -- no new ma
     update_direct    direct_model.direct_update_joseph        update_linear    linear_model.linear_update_joseph
     predict_linear   motion_model.predict_linear              transform        transform_model.transform_dense
     join             join_model.join_dense (both modes)       set_state / set_state_diag, set_option: bookkeeping only
+    localize1, localize_update1, run_localize_stream          localize_model.literal_step (the trajectory's own cfg)
 
 The methods carry EkfSlam's names and take ONE trajectory's arguments (b = 0), so that a sequence written once runs on the model
 and on a filter (tests/sequence_cases.py's Driver).  The other handles a call reads (`join`, `copy_from`) are named by a key of
@@ -13,7 +14,8 @@ and on a filter (tests/sequence_cases.py's Driver).  The other handles a call re
 
 `Traj.seen` follows each call's rule -- which landmarks are correlated with the rest: a dense-H row, a transform with a
 covariance, a sequential join (what it appends) and predict_dense correlate everything they name; a direct fix of a
-never-observed landmark and a transform without a covariance leave the exact zeros.
+never-observed landmark and a transform without a covariance leave the exact zeros.  A localisation call makes every landmark it
+names seen -- its pose cross-covariance becomes non-zero -- while the landmark's own block and mean do not move.
 
 PRECISION.  `bank(..., dtype=np.longdouble)` runs the SAME functions in extended precision (x87: 64 bits of mantissa): the
 models' code objects are re-bound to a namespace in which `np` is a proxy whose array constructors make `dtype` arrays
@@ -28,6 +30,7 @@ import numpy as np
 from tests import direct_model as dm
 from tests import join_model as jm
 from tests import linear_model as lm
+from tests import localize_model as lcm
 from tests import motion_model as mm
 from tests import transform_model as tm
 from tests.fork_model import ForkBank
@@ -123,10 +126,25 @@ class SeqBank(ForkBank):
         for t, j in tags.items():                          # (a tag this map already holds: the appended twin carries none)
             tr.tags.setdefault(t, first + j)
 
+    # -- localisation on a frozen map: localize_model.literal_step, one call per step -----------------------------------------
+    def localize1(self, lin, ang, idx, zr, zb, predict=True):
+        tr = self.tr
+        idx = [int(j) for j in idx]
+        tr.mean, tr.cov = lcm.literal_step(tr.mean, tr.cov, lin, ang, idx, zr, zb, tr.cfg, predict=predict)
+        tr.seen[np.asarray(idx, dtype=int)] = True
+
+    def localize_update1(self, idx, zr, zb):
+        self.localize1(0.0, 0.0, idx, zr, zb, predict=False)
+
+    def run_localize_stream(self, lin, ang, idx, zr, zb):
+        for k in range(len(lin)):
+            self.localize1(lin[k], ang[k], idx[k], zr[k], zb[k])
+
 
 # ---- the same code in another precision --------------------------------------------------------------------------------------
 _REBOUND = ("oracle.ekf_oracle", "tests.gated_oracle","tests.fuzz_model", "tests.fork_model", "tests.direct_model",
-            "tests.linear_model", "tests.motion_model", "tests.transform_model", "tests.join_model", __name__)
+            "tests.linear_model", "tests.localize_model", "tests.motion_model", "tests.transform_model", "tests.join_model",
+            __name__)
 _CLASSES = ("Traj", "Bank", "ForkBank", "SeqBank")
 
 

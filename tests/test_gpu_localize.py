@@ -13,6 +13,7 @@ import pytest
 
 from oracle import ekf_oracle as orc
 from tests import localize_model as lm
+from tests import sequence_cases as sc
 from tests import streams
 from tests.conftest import path_ran
 from tests.gpu_support import bank, counters, pbase, same, sd  # noqa: F401
@@ -412,4 +413,70 @@ def test_pose_on_the_landmark_sets_nonfinite(sd, both_paths):
         mu = f.mean(0)
         assert np.isnan(mu[:3]).all() and np.array_equal(mu[3:], bad[3:])
         assert np.array_equal(frozen_part(sd, f, 0)[0], frozen[0]) and same(f.state(1), other)
+        assert path_ran(f, both_paths)
+
+
+# ---- 13: an uneven bank: three sizes and three bounds under one launch grid ----------------------------------------------------
+def pose_rows(sd, f, b):
+    """Rows 0..2 of trajectory b's stored P_base, every stored column (n_max = 79: a leading dimension of 128)."""
+    assert f.n_max == 79
+    return pbase(sd, f, b).reshape(-1, 128)[:3].copy()
+
+
+def test_uneven_bank(sd, both_paths):
+    """One handle, n = (23, 63, 79).  Trajectory 0 and 2 are dense; trajectory 1 is the pair table's start after its prelude
+    (tests/sequence_cases.py): bound 55, four loose landmarks with exact zeros.  Four localize calls with m = (2, 3, 0), the
+    third naming a loose landmark of trajectory 1, then one localize_update in which trajectory 2 has m = 0.  The smallest
+    sizes that put three different bounds under one launch grid."""
+    s = sc.start()
+    sizes, bound1, T, K0 = (23, 63, 79), 3 + 2 * sc.N_OBSERVED, sc.STREAM_STEPS + sc.SINGLE_STEPS, sc.STREAM_STEPS
+    rng = np.random.default_rng(13)
+    lin, ang = np.zeros((T, 3)), np.zeros((T, 3))
+    idx, zr, zb, m = np.zeros((T, 3, 4), dtype=np.int32), np.zeros((T, 3, 4)), np.zeros((T, 3, 4)), np.zeros((T, 3), dtype=np.int32)
+    lin[:, 1], ang[:, 1], idx[:, 1], zr[:, 1], zb[:, 1], m[:, 1] = s[2][:T], s[3][:T], s[4][:T], s[5][:T], s[6][:T], 4
+    want1 = sc.new_model()
+    drv = sc.Driver(want1)
+    sc.setup(drv)
+    sc.prelude(drv)
+    with sd.EkfSlam(79, batch=3) as f:
+        f.set_state(orc.synthetic_world(10, 21)[2], streams.dense_start(23, 5), 0)
+        f.set_state_diag(s[0], s[1], 1)
+        f.set_state(orc.synthetic_world(38, 22)[2], streams.dense_start(79, 6), 2)
+        f.run_stream(lin[:K0], ang[:K0], idx[:K0], zr[:K0], zb[:K0], m[:K0])     # the prelude: trajectories 0 and 2 see nothing
+        for k in range(K0, T):
+            f.step(lin[k], ang[k], [[], idx[k, 1], []], [[], zr[k, 1], []], [[], zb[k, 1], []])
+        f.flush()
+        f.profile_enable(True)
+        model = [f.state(b) for b in range(3)]             # taken once, before the first call
+        assert [len(x[0]) for x in model] == list(sizes) == [f.size(b) for b in range(3)]
+        check(f, 1, (want1.tr.mean, want1.tr.cov), "uneven bank, trajectory 1: the pair table's start")
+        assert not model[1][1][:bound1, bound1:].any() and model[0][1][:3, 3:].all() and model[2][1][:3, 3:].all()
+        frozen = [frozen_part(sd, f, b) for b in range(3)]
+        raw = [pose_rows(sd, f, b) for b in range(3)]
+        sched = scheduling(sd, f)
+        named = ([[1, 7], [9, 0], [4, 4], [2, 8]],
+                 [[3, 12, 3], [25, 0, 14], [27, 5, 1], [8, 27, 20]],       # landmark 27 is loose: named in the third call
+                 [[], [], [], []])
+        for k in range(4):
+            obs = [observe(model[b][0], named[b][k], rng) for b in range(3)]
+            w = 0.02 if k % 2 else 0.005
+            f.localize(0.004, w, [o[0] for o in obs], [o[1] for o in obs], [o[2] for o in obs])
+            for b in range(3):
+                model[b] = lm.literal_step(*model[b], 0.004, w, *obs[b], CFG)
+            if k < 2:                                      # no loose landmark named yet: nothing at or beyond the bound moves
+                assert np.array_equal(pose_rows(sd, f, 1)[:, bound1:], raw[1][:, bound1:]), f"call {k}: columns beyond the bound moved"
+        assert pose_rows(sd, f, 1)[:, 3 + 2 * 27:5 + 2 * 27].all()
+        whole = (pbase(sd, f, 2), f.mean(2))
+        obs = [observe(model[0][0], [5, 3], rng), observe(model[1][0], [26, 10, 27], rng), observe(model[2][0], [], rng)]
+        f.localize_update([o[0] for o in obs], [o[1] for o in obs], [o[2] for o in obs])
+        for b in range(3):
+            model[b] = lm.literal_step(*model[b], 0.0, 0.0, *obs[b], CFG, predict=False)
+        assert np.array_equal(pbase(sd, f, 2), whole[0]) and np.array_equal(f.mean(2), whole[1]), "m = 0: the trajectory moved"
+        assert scheduling(sd, f) == sched                  # no covariance pass, no cadence
+        for b in range(3):
+            after = pose_rows(sd, f, b)
+            assert np.array_equal(after[:, sizes[b]:], raw[b][:, sizes[b]:]), f"trajectory {b}: columns beyond n = {sizes[b]} moved"
+            assert not np.array_equal(after[:, :sizes[b]], raw[b][:, :sizes[b]])
+            check(f, b, model[b], f"uneven bank, trajectory {b} (n = {sizes[b]})")
+            assert frozen_same(frozen_part(sd, f, b), frozen[b]), f"trajectory {b}: the map moved"
         assert path_ran(f, both_paths)

@@ -1,5 +1,5 @@
 """GPU: every read-only query behind every state-changing call (tests/sequence_cases.py: run_query_case; the model is
-tests/sequence_model.py's, tests/test_queries_after_calls_cpu.py shows that the 15 cases are admissible and the judge not blind).
+tests/sequence_model.py's, tests/test_queries_after_calls_cpu.py shows that the 18 cases are admissible and the judge not blind).
 
 marginals(), joint() and associate() read the filter "as the covariance pass would leave it" through the mirrors the
 state-changing calls maintain: the size word, the mean's current buffer, the pending pose noise, the padded rank count and the
@@ -18,7 +18,8 @@ left, so a query behind them is right only if A's bound reached it.  After A and
 Then, after the tail only: state() -- it flushes -- against the model; the pending-time joint() and marginals() within 1e-11 of
 the download (the project's bound for pending ranks summed in another order); the same queries with nothing pending equal to the
 download bit for bit; factor() against the downloaded covariance.  On the general kernels ranks must be pending behind the tail
-in every case, and behind A at least for predict_linear and step; the small-state path never has any, and its queries before and
+in every case, and behind A at least for predict_linear and step -- and NOT behind a localisation call, which applies what is
+pending at entry and appends no rank; the small-state path never has any, and its queries before and
 after the download agree bit for bit.
 
 Handles are made once per path and reset per case; a failed assertion drops them, a refused or failed call ends the module."""
@@ -40,7 +41,7 @@ pytestmark = pytest.mark.gpu
 
 PATH_TOL = 1e-11        # a query with ranks pending against the flushed download (test_gpu_joint, test_gpu_marginals)
 PATHS = ("default_path", "general_kernels")
-BOUND_MUST_RISE = ("step", "step_detections", "predict_dense", "update_linear", "transform(cov)", "join")
+BOUND_MUST_RISE = ("step", "step_detections", "predict_dense", "update_linear", "transform(cov)", "join") + sc.LOCALIZE_OPS
 PENDING_AT_A = ("predict_linear", "step")
 HANDLES = {}            # path -> Device
 RECORD = {"cases": set(), "pending": {}, "bounds": {}, "worst": {}, "distance": {}, "seconds": 0.0}
@@ -134,6 +135,8 @@ def test_queries_after(sd, both_paths, a):
         what = f"{name}, after {stage}, "
         if general and (stage == "tail" or sc.query_name(a) in PENDING_AT_A):
             assert RECORD["pending"][a, stage, both_paths], f"{what}no ranks pending (P_base[0, 0] = {dev.raw00()})"
+        if general and stage == "A" and sc.query_name(a) in sc.LOCALIZE_OPS:
+            assert not RECORD["pending"][a, stage, both_paths], f"{what}something is pending (P_base[0, 0] = {dev.raw00()})"
         q, err = queries(sd, dev, model, rngs, what)
         RECORD["worst"][both_paths, a, stage] = err
         if stage != "tail":
@@ -182,10 +185,10 @@ def test_queries_after(sd, both_paths, a):
 
 
 def test_the_module_kept_its_promises():
-    """Every operation ran on both paths; on the general kernels ranks were pending behind the tail in all 15 cases and behind
-    A for predict_linear and step; the bound A left lies above the bound before A and above the tail's own for the six
-    operations that must raise it; no observation excused, no entry left out.  Prints the worst of every piece per operation
-    and stage, and the pending-time queries' distance from the download (profiles/queries_after_calls.txt)."""
+    """Every operation ran on both paths; on the general kernels ranks were pending behind the tail in all 18 cases and behind
+    A for predict_linear and step, and nothing behind a localisation A; the bound A left lies above the bound before A and above
+    the tail's own for the nine operations that must raise it; no observation excused, no entry left out.  Prints the worst of
+    every piece per operation and stage, and the pending-time queries' distance from the download (profiles/queries_after_calls.txt)."""
     for (path, a, stage), w in sorted(RECORD["worst"].items()):
         print(f"DEVICE {path:15s} {sc.query_name(a):20s} {stage:5s} {pb.fmt_state(w)} | marginals "
               + " ".join(f"{k[5:]}={v:.2e}" for k, v in w.items() if k.startswith("marg_")))
@@ -199,6 +202,7 @@ def test_the_module_kept_its_promises():
     names = [sc.query_name(a) for a in CASES]
     assert all(RECORD["pending"][a, "tail", "general_kernels"] for a in CASES)
     assert all(RECORD["pending"][names.index(op), "A", "general_kernels"] for op in PENDING_AT_A)
+    assert not any(RECORD["pending"][names.index(op), "A", "general_kernels"] for op in sc.LOCALIZE_OPS)
     for op in BOUND_MUST_RISE:
         b = RECORD["bounds"][names.index(op)]
         assert b["A"][0] > b["start"][0] and b["A"][0] > b["A"][1] and b["tail"][0] == b["A"][0], (op, b)

@@ -1,5 +1,5 @@
 """GPU: every ordered pair of state-changing calls against ONE dense model (tests/sequence_cases.py has the table and the
-reasons, tests/sequence_model.py the model, tests/test_sequence_cpu.py shows that the 225 cases are admissible and the judge
+reasons, tests/sequence_model.py the model, tests/test_sequence_cpu.py shows that the 324 cases are admissible and the judge
 not blind).
 
 Per case: the block-diagonal start, 28 stream steps and three single steps (on the general kernels ranks are pending),
@@ -7,6 +7,9 @@ operation A, operation B, then a continuation (a step and a 4-step stream) -- ju
 continuation with parity_blocks.assert_state_close: the informed part piece by piece at 1e-9, the loose landmarks on their
 own scale, exact zeros, exact symmetry, size, tag index, flags.  A stale bound, floor or size word left by A shows in B or in
 the continuation's pass; the failure carries the pair's name.
+
+Localisation (the last three operations) applies what is pending at entry and appends no rank: on the general kernels the
+stored P_base[0, 0] read BEFORE the download behind such an A or B is the downloaded P[0, 0], bit for bit.
 
 The handles are made once per path and every case resets them (set_option, set_state_diag, set_tag_index: part of the
 surface under test); a case that fails drops them, so that the next one starts from new handles."""
@@ -21,7 +24,7 @@ from tests.sequence_device import Device
 pytestmark = pytest.mark.gpu
 
 HANDLES = {}            # path -> Device
-RECORD = {"cases": set(), "pending": {}, "first": set(), "second": set(), "bound_rose": [], "worst": {}}
+RECORD = {"cases": set(), "pending": {}, "first": set(), "second": set(), "bound_rose": [], "worst": {}, "nothing_pending": set()}
 
 
 @pytest.fixture(scope="module")
@@ -53,7 +56,12 @@ def test_pair(sd, both_paths, a, b):
             if general:
                 assert RECORD["pending"][a, b, both_paths], f"{name}: no ranks pending at A (P_base[0, 0] = {raw}, P[0, 0] = {want})"
             return
+        op = sc.OPS[a if stage == "A" else b][0] if stage in ("A", "B") else None
+        raw = dev.raw00()
         got = dev.got()
+        if general and op in sc.LOCALIZE_OPS:
+            assert raw == got[1][0, 0], f"{name}, after {stage}: {op} left something pending (P_base[0, 0] = {raw}, P[0, 0] = {got[1][0, 0]})"
+            RECORD["nothing_pending"].add((op, stage))
         err = pb.assert_state_close(got, model.state(), sc.INIT_VAR, sc.TOL, sc.ENTRY_TOL, what=f"{name}, after {stage}: ")
         bounds["P00"] = float(got[1][0, 0])
         assert path_ran(dev.f, both_paths), f"{name}, after {stage}: not the path {both_paths}"
@@ -83,8 +91,8 @@ def test_pair(sd, both_paths, a, b):
 
 def test_the_module_kept_its_promises():
     """Every pair ran on both paths; ranks were pending at A in every general-kernels case; every operation ran in both
-    positions on both paths; some case left the bound below n before B raised it.  Prints the worst of every piece per
-    operation and position (profiles/sequence_pairs.txt)."""
+    positions on both paths; some case left the bound below n before B raised it; nothing was pending behind a
+    localisation call.  Prints the worst of every piece per operation and position (profiles/sequence_pairs.txt)."""
     for (path, pos, op), w in sorted(RECORD["worst"].items()):
         print(f"DEVICE {path:15s} {sc.OPS[op][0]:20s} {pos:6s} {pb.fmt_state(w)}")
     paths = ("default_path", "general_kernels")
@@ -94,3 +102,4 @@ def test_the_module_kept_its_promises():
     assert RECORD["first"] == want and RECORD["second"] == want
     print("bound below n before B, at n after it:", len(RECORD["bound_rose"]), "cases, e.g.", RECORD["bound_rose"][:3])
     assert RECORD["bound_rose"]
+    assert RECORD["nothing_pending"] == {(op, st) for op in sc.LOCALIZE_OPS for st in ("A", "B")}

@@ -1,6 +1,6 @@
 """CPU: what makes tests/test_gpu_sequence_pairs.py a statement about device code (no GPU).
 
-Admissibility: every one of the 225 ordered pairs of tests/sequence_cases.py is run on the dense model twice -- in float64, as
+Admissibility: every one of the 324 ordered pairs of tests/sequence_cases.py is run on the dense model twice -- in float64, as
 the GPU test runs it, and in longdouble (tests/sequence_model.py: the same code, 64 bits of mantissa) -- and judged after A,
 after B and after the continuation.  Every relative-Frobenius piece of that comparison is at most FLOOR_TOL = 1e-11 (the rule
 of tests/test_update_blocks_cpu.py), so TOL = 1e-9 on the GPU is two decades above what the inputs' conditioning explains;
@@ -13,6 +13,7 @@ import pytest
 
 from tests import parity_blocks as pb
 from tests import sequence_cases as sc
+from tests import sequence_model as sm
 
 FROBENIUS = ("pose", "cross", "landmarks", "mean_pose")
 ENTRYWISE = ("corr_max", "mean_landmarks", "loose_cross")
@@ -44,8 +45,8 @@ def worst(floors, pieces):
                for st, e in stages.items() for p in pieces if p in e)
 
 
-def test_all_225_pairs_are_admissible(floors):
-    assert len(floors) == 225 == len(sc.OPS) ** 2 and all(set(s) == {"start", "A", "B", "end"} for s in floors.values())
+def test_all_324_pairs_are_admissible(floors):
+    assert len(floors) == 324 == len(sc.OPS) ** 2 and all(set(s) == {"start", "A", "B", "end"} for s in floors.values())
     for pos, name in ((0, "first"), (1, "second")):
         for i, (op, _) in enumerate(sc.OPS):
             w = {p: max((e[p] for ab, stages in floors.items() if ab[pos] == i for e in stages.values() if p in e), default=0.0)
@@ -71,7 +72,7 @@ def test_entry_tol_is_ten_times_the_measured_floor(floors):
 
 def test_the_table_is_what_it_promises():
     s = sc.start()
-    assert len(s[0]) == 63 and sc.N_MAX == 79 and len(sc.OPS) == 15 and len(set(n for n, _ in sc.OPS)) == 15
+    assert len(s[0]) == 63 and sc.N_MAX == 79 and len(sc.OPS) == 18 and len(set(n for n, _ in sc.OPS)) == 18
     assert set(np.unique(s[4][:sc.STREAM_STEPS + sc.SINGLE_STEPS])) == set(range(sc.N_OBSERVED))
     sizes, calls = {}, {}
     for a, b in sc.PAIRS:
@@ -84,7 +85,8 @@ def test_the_table_is_what_it_promises():
     every = set().union(*calls.values())
     assert every >= {"step1", "run_stream", "step_detections", "predict_linear", "predict_dense1", "update_direct",
                      "update_linear", "transform", "join", "remove_landmarks", "add_landmarks", "copy_in", "set_option",
-                     "set_state_diag", "set_tag_index"}
+                     "set_state_diag", "set_tag_index", "localize1", "localize_update1", "run_localize_stream"}
+    assert [n for n, _ in sc.OPS[15:]] == list(sc.LOCALIZE_OPS)      # appended: the 225 older pairs keep their ids and draws
     # the start: 26 informed landmarks, 4 loose ones with exact zeros; growth crosses the 64-column edge
     m = sc.new_model()
     d = sc.Driver(m)
@@ -148,6 +150,76 @@ def test_a_bound_that_did_not_rise_after_a_transform_with_a_covariance_is_caught
     got = sc.keep_rows_beyond(before, m.state(), 3 + 2 * 26)         # the bound of before the transform
     with pytest.raises(AssertionError, match="loose_cross|loose_mean"):
         judged(got, m)
+
+
+# ---- localisation: no pass repairs a pose-row column that a call skipped -------------------------------------------------------
+START_BOUND = 3 + 2 * sc.N_OBSERVED                        # the bound of the start after its prelude: 55
+PIECE = "(pose|cross|landmarks|corr_max|mean_pose|mean_landmarks|loose_block|loose_mean|loose_cross): "
+
+
+def stale_bound_bank():
+    """A model whose localisation leaves P(0..2, c) and its mirror as they were for every c at or beyond max(the start's
+    bound, the call's own bound): what k_loc_rows does when the operation before it did not raise the bound it trusts."""
+    class StaleBound(sm.SeqBank):
+        def localize1(self, lin, ang, idx, zr, zb, predict=True):
+            was = self.tr.cov.copy()
+            super().localize1(lin, ang, idx, zr, zb, predict)
+            c = max(START_BOUND, 3 + 2 * (max(int(j) for j in idx) + 1))
+            self.tr.cov[:3, c:], self.tr.cov[c:, :3] = was[:3, c:], was[c:, :3]
+
+    s = sc.start()
+    return StaleBound(s[0], s[1], sc.sources())
+
+
+RAISES_THE_BOUND = ("transform(cov)", "predict_dense", "join", "update_linear", "step", "step_detections")
+
+
+@pytest.mark.parametrize("op", sc.LOCALIZE_OPS)
+def test_localisation_under_a_bound_that_A_did_not_raise_is_caught(op):
+    """Behind each operation that correlates columns at or beyond the start's bound, for each of the three localisation
+    operations.  The weakest of the 18 is transform(cov) then localize_update -- no prediction, so the stale columns differ only
+    by K_p (H P)[:, c], and c is a loose landmark's: every informed piece passes and loose_cross, measured 1.9e-9,
+    stands against ENTRY_TOL = 4e-10, a factor of 5; the next, transform(cov) then localize, has loose_cross at 5.5e-7
+    (profiles/localize_pairs.txt)."""
+    names = [n for n, _ in sc.OPS]
+    for first in RAISES_THE_BOUND:
+        m, bad = sc.new_model(), stale_bound_bank()
+        d = sc.Driver(m, bad)
+        sc.setup(d)
+        sc.prelude(d)
+        rng = np.random.default_rng([5, names.index(first), names.index(op)])
+        sc.OPS[names.index(first)][1](d, rng)
+        assert sc.model_bound(m.tr) > START_BOUND and np.array_equal(bad.tr.cov, m.tr.cov), first
+        sc.OPS[names.index(op)][1](d, rng)
+        judged(sc.as_got(m), m)
+        with pytest.raises(AssertionError, match=PIECE) as why:
+            judged(sc.as_got(bad), m)
+        e = pb.state_errors(sc.as_got(bad)[:2], m.state()[:2], sc.INIT_VAR)
+        print(f"MUTANT stale bound  {first:16s} then {op:16s} {pb.fmt_state(e)} | {why.value}")
+        if (first, op) == ("transform(cov)", "localize_update"):
+            assert "loose_cross" in str(why.value) and max(e[p] for p in pb.PIECES) < sc.TOL
+
+
+def test_a_pass_that_skips_what_localize_correlated_is_caught():
+    """localize names a loose landmark: its pose cross-covariance is non-zero now, and the next SLAM step's pass moves its own
+    block too.  A pass with the bound of before the call leaves that block as it was."""
+    m, d, rng = reference([sc.op_localize])
+    assert sc.model_bound(m.tr) == START_BOUND + 2 and m.tr.cov[:3, START_BOUND:START_BOUND + 2].any()
+    before = (m.tr.mean.copy(), m.tr.cov.copy())
+    sc.observe(d, rng, [0, 3])
+    judged(m.state(), m)
+    got = sc.keep_rows_beyond(before, m.state(), START_BOUND)
+    with pytest.raises(AssertionError, match="loose_block"):
+        judged(got, m)
+
+
+def test_a_landmark_mean_moved_behind_localize_is_caught():
+    m, d, rng = reference([sc.op_localize])
+    mean, cov, _ = m.state()
+    mean = mean.copy()
+    mean[3 + 2 * 5] += 1e-7
+    with pytest.raises(AssertionError, match="mean_landmarks"):
+        judged((mean, cov), m)
 
 
 def test_the_judge_names_the_whole_state_pieces():
