@@ -1,4 +1,5 @@
 """One dense model of ONE trajectory under the whole state-changing surface of a handle, for tests/sequence_cases.py.
+(tests/sequence_bank_cases.py runs the same class over a BANK: see "A BANK" below; at B = 1 nothing differs.)
 
 `SeqBank` is tests/fork_model.py's ForkBank (step, update, predict, predict_dense, grow, remove, window, copy_from) plus the
 newer calls, each DELEGATED to the model the project already trusts -- no new mathematics:
@@ -16,6 +17,12 @@ and on a filter (tests/sequence_cases.py's Driver).  The other handles a call re
 covariance, a sequential join (what it appends) and predict_dense correlate everything they name; a direct fix of a
 never-observed landmark and a transform without a covariance leave the exact zeros.  A localisation call makes every landmark it
 names seen -- its pose cross-covariance becomes non-zero -- while the landmark's own block and mean do not move.
+
+A BANK.  `SeqBank([(mean, diag), ...])` keeps one trajectory per start and a TARGET slot: `tr` is `t[target]`, and every
+per-trajectory method above acts on the target (B = 1: slot 0, as ever).  The calls that take the whole bank at once carry one
+entry per slot: bank_step, bank_stream, bank_detections, bank_localize, bank_localize_stream -- loops over Bank.step,
+Bank.window and localize_model.literal_step, nothing else.  Two calls need a second slot of the SAME bank: `fork(src, dst)`
+(ForkBank's, through copy_from) and `join_slot(src)`, join_model.join_dense with slot `src` as the source.
 
 PRECISION.  `bank(..., dtype=np.longdouble)` runs the SAME functions in extended precision (x87: 64 bits of mantissa): the
 models' code objects are re-bound to a namespace in which `np` is a proxy whose array constructors make `dtype` arrays
@@ -38,23 +45,27 @@ from tests.fuzz_model import Traj
 
 
 class SeqBank(ForkBank):
-    def __init__(self, mean0, diag0, sources=None, base=None):
-        ForkBank.__init__(self, [(mean0, np.diag(np.asarray(diag0, dtype=float)))], base)
+    def __init__(self, mean0, diag0=None, sources=None, base=None):
+        """(mean0, diag0): one trajectory; diag0 None: `mean0` is a list of (mean, diag) starts, one per slot of a bank."""
+        starts = [(mean0, diag0)] if diag0 is not None else list(mean0)
+        ForkBank.__init__(self, [(m, np.diag(np.asarray(d, dtype=float))) for m, d in starts], base)
         self.sources = dict(sources or {})
+        self.target = 0
 
     @property
     def tr(self):
-        return self.t[0]
+        return self.t[self.target]
 
-    def state(self):
-        """(mean, covariance, tag index) of the trajectory."""
-        return self.tr.mean, self.tr.cov, dict(self.tr.tags)
+    def state(self, b=None):
+        """(mean, covariance, tag index) of the target trajectory (b given: of slot b)."""
+        tr = self.tr if b is None else self.t[b]
+        return tr.mean, tr.cov, dict(tr.tags)
 
     # -- bookkeeping ---------------------------------------------------------------------------------------------------------
     def set_state(self, mean, cov):
         old = self.tr
-        self.t[0] = Traj(mean, cov, self.base)
-        self.t[0].cfg, self.t[0].rejections = old.cfg, old.rejections
+        self.t[self.target] = Traj(mean, cov, self.base)
+        self.tr.cfg, self.tr.rejections = old.cfg, old.rejections
         d = np.diag(self.tr.cov)
         off = np.abs(self.tr.cov).sum(axis=0) - np.abs(d)
         self.tr.seen = (off[3::2] > 0) | (off[4::2] > 0)
@@ -68,7 +79,8 @@ class SeqBank(ForkBank):
     def set_option(self, name, value):
         pass                                             # (the active bound changes no result)
 
-    # -- the calls ForkBank has, for one trajectory ----------------------------------------------------------------------------
+    # -- the calls ForkBank has, for one trajectory (step1, run_stream, step_detections: a bank of ONE; a larger bank takes the
+    #    bank_* calls below, which name every slot) ---------------------------------------------------------------------------
     def step1(self, lin, ang, idx, zr, zb):
         self.step([lin], [ang], [(list(idx), list(zr), list(zb))])
 
@@ -80,13 +92,13 @@ class SeqBank(ForkBank):
         self.window([lin], [ang], [win])
 
     def add_landmarks(self, xy):
-        self.grow(xy, 0)
+        self.grow(xy, self.target)
 
     def remove_landmarks(self, lms):
-        self.remove([int(l) for l in lms], 0)
+        self.remove([int(l) for l in lms], self.target)
 
     def predict_dense1(self, F, Q):
-        self.predict_dense(np.asarray(F, dtype=float), np.asarray(Q, dtype=float), 0)
+        self.predict_dense(np.asarray(F, dtype=float), np.asarray(Q, dtype=float), self.target)
 
     def copy_in(self, key):
         """copy_from(the handle `key` names): this trajectory is the destination."""
@@ -118,7 +130,15 @@ class SeqBank(ForkBank):
             tr.seen[:] = True
 
     def join(self, key, transform=None, cov=None):
-        mean, P, tags = self.sources[key]
+        self._append(*self.sources[key], transform, cov)
+
+    def join_slot(self, src, transform=None, cov=None):
+        """join with slot `src` of this bank as the source (only read)."""
+        assert src != self.target
+        s = self.t[src]
+        self._append(s.mean, s.cov, s.tags, transform, cov)
+
+    def _append(self, mean, P, tags, transform, cov):
         tr = self.tr
         first, count = tr.n_lm, (len(mean) - 3) // 2
         tr.mean, tr.cov = jm.join_dense(tr.mean, tr.cov, mean, P, transform, cov, with_bound=False)[:2]
@@ -128,7 +148,9 @@ class SeqBank(ForkBank):
 
     # -- localisation on a frozen map: localize_model.literal_step, one call per step -----------------------------------------
     def localize1(self, lin, ang, idx, zr, zb, predict=True):
-        tr = self.tr
+        self._localize(self.tr, lin, ang, idx, zr, zb, predict)
+
+    def _localize(self, tr, lin, ang, idx, zr, zb, predict):
         idx = [int(j) for j in idx]
         tr.mean, tr.cov = lcm.literal_step(tr.mean, tr.cov, lin, ang, idx, zr, zb, tr.cfg, predict=predict)
         tr.seen[np.asarray(idx, dtype=int)] = True
@@ -139,6 +161,29 @@ class SeqBank(ForkBank):
     def run_localize_stream(self, lin, ang, idx, zr, zb):
         for k in range(len(lin)):
             self.localize1(lin[k], ang[k], idx[k], zr[k], zb[k])
+
+    # -- the calls that take the whole bank: one entry per slot --------------------------------------------------------------
+    def bank_step(self, lin, ang, obs):
+        """step: lin, ang [B]; obs per slot (idx, zr, zb)."""
+        self.step(list(lin), list(ang), [(list(i), list(r), list(z)) for i, r, z in obs])
+
+    def bank_stream(self, lin, ang, idx, zr, zb, m):
+        """run_stream: lin, ang [K, B]; idx, zr, zb [K, B, stride]; m [K, B] valid entries."""
+        for k in range(len(lin)):
+            self.bank_step(lin[k], ang[k], [(idx[k][b][:m[k][b]], zr[k][b][:m[k][b]], zb[k][b][:m[k][b]])
+                                            for b in range(len(self.t))])
+
+    def bank_detections(self, lin, ang, wins):
+        self.window(list(lin), list(ang), list(wins))
+
+    def bank_localize(self, lin, ang, obs, predict=True):
+        for b, tr in enumerate(self.t):
+            self._localize(tr, lin[b], ang[b], obs[b][0], obs[b][1], obs[b][2], predict)
+
+    def bank_localize_stream(self, lin, ang, idx, zr, zb, m):
+        for k in range(len(lin)):
+            self.bank_localize(lin[k], ang[k], [(idx[k][b][:m[k][b]], zr[k][b][:m[k][b]], zb[k][b][:m[k][b]])
+                                                for b in range(len(self.t))])
 
 
 # ---- the same code in another precision --------------------------------------------------------------------------------------
@@ -245,7 +290,8 @@ _BANKS = {}
 
 
 def bank(mean0, diag0, sources=None, dtype=np.float64):
-    """A SeqBank in `dtype`: float64 is the class above as it stands, anything else the re-bound copy."""
+    """A SeqBank in `dtype`: float64 is the class above as it stands, anything else the re-bound copy.  (diag0 None: `mean0`
+    is a list of starts, one per slot.)"""
     dt = np.dtype(dtype)
     if dt == np.float64:
         return SeqBank(mean0, diag0, sources)
