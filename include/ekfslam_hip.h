@@ -593,6 +593,35 @@ int ekf_download_tags(ekf_handle *h, int b, int *m, int *idx, int *tag_id, doubl
 int ekf_download_tag_index(ekf_handle *h, int b, int *tag_of_index, int capacity, int *n_landmarks);
 int ekf_upload_tag_index(ekf_handle *h, int b, const int *tag_of_index, int n_landmarks);
 
+/* Localisation from raw detections: the device-side front end in front of ekf_localize_step, for a lap over a finished map.
+ * Arguments and argument checks are ekf_step_detections'; the semantics are ekf_localize_step's on whatever the window MATCHES.
+ * k_loc_associate, one wave per trajectory, walks the window exactly as the mapping front end does -- chunks of 64 detections,
+ * IGNORE_TAGS, the gate of ekf_set_association, ids outside [0, 1024) set EKF_FLAG_ASSOC, one slot per distinct tag in order of
+ * first appearance, per-tag averaging, range and bearing, the world guess from the pose before the prediction: a tag's averaged
+ * (range, bearing) has the bits ekf_step_detections would give it -- with one difference: the map is frozen.  A tag the table
+ * does not know, or whose table entry points at or beyond the trajectory's landmark count, is UNMATCHED: it is skipped without
+ * a flag and its id is kept for ekf_download_unmatched.  More than EKF_AMAX distinct matched tags: the surplus is dropped with
+ * EKF_FLAG_ASSOC.  The matched tags then run as ekf_localize_step runs them -- k_loc_solve and k_loc_rows, a second pair for the
+ * tags beyond EKF_MMAX -- with no host round trip in between: the state ends BIT FOR BIT as after ekf_localize_step with the idx,
+ * range and bearing ekf_download_tags reports, and the innovation log and the pose log get the same rows.
+ * Never written: the tag table (ekf_download_tag_index returns what it returned before), the sizes, the landmark means, every
+ * P(a, b) with a, b >= 3.  Ranks pending at entry are applied first, once.  The active bound is raised over the matched landmarks
+ * on the device.  ekf_set_noise's rows, the NIS gate, enable_measurement_model (off: prediction only) and the "active_bound"
+ * option act as on ekf_localize_step.  ASYNCHRONOUS like ekf_step_detections; EKF_ERR_ARG changes nothing; a failure behind the
+ * first launch leaves every trajectory undefined (EKF_ERR_STATE until uploaded again), as for ekf_localize_step.
+ * ekf_download_tags returns the matched tags of the window (n landmarks or fewer, update order).
+ * ekf_download_unmatched: the distinct unmatched ids of trajectory b's last localisation window in order of first appearance --
+ * *m their number, the first min(*m, capacity, EKF_AMAX) of them in tag_id (may be NULL with capacity 0).  Blocking.
+ * EKF_ERR_STATE if no localisation window has run on the handle.
+ * Measured on one MI355X (tools/localize_detections_time.py, profiles/localize_detections.txt), 8 tags x 3 frames per trajectory:
+ * k_loc_associate alone 14 - 16 us whatever the bank (class 11 of ekf_profile_read_class).  Through the Python binding a window
+ * costs 679 us for 32 x N = 2000, 45 us for 1 x N = 2000 and 5.3 ms for 256 x N = 20 -- host-bound, as ekf_step_detections is on
+ * the same window (737, 48, 5.3 ms): the binding packs one detection at a time -- against 6.5 ms, 254 us and 29.6 ms for tag
+ * table + mean download, host association and ekf_localize_step. */
+int ekf_localize_detections(ekf_handle *h, const double *lin, const double *ang, const int *count,
+                            const int *tag_id, const double *pose_t, const double *pose_err, int stride);
+int ekf_download_unmatched(ekf_handle *h, int b, int *m, int *tag_id, int capacity);
+
 /* Streams of pre-uploaded inputs ([step][batch] and [step][batch][stride] arrays, stride <= EKF_MMAX; m[step][batch] landmarks
  * each -- any count per step and trajectory, 0 included: what the windows of src/replay_no_ros.py:280-301 hold).
  * ekf_stream_upload copies and validates `steps` steps of inputs into HBM (blocking);
@@ -645,7 +674,7 @@ int ekf_profile_read(ekf_handle *h, double *pass_ms_total, long long *pass_launc
 long long ekf_profile_passes(ekf_handle *h);
 /* With ekf_set_option("profile_kernels", 1) (a diagnostic run: every record costs its stream ~6 us) the other launches of a
  * fused cadence carry event pairs too: cls 1 the solve launch, 2 the chain (or look-ahead gather) launch, 3 the panel launch,
- * 0 the pass; 4 the k_direct launch of ekf_update_direct; 5 the k_linear launch of ekf_update_linear; 6 the k_join launch of ekf_join_maps (with its snapshot launch); 7 the k_predict_pose launch of ekf_predict_linear; 8 the k_transform launch of ekf_transform; 9 and 10 the k_loc_solve and k_loc_rows launches of ekf_localize_*.  Does not reset: read before ekf_profile_read. */
+ * 0 the pass; 4 the k_direct launch of ekf_update_direct; 5 the k_linear launch of ekf_update_linear; 6 the k_join launch of ekf_join_maps (with its snapshot launch); 7 the k_predict_pose launch of ekf_predict_linear; 8 the k_transform launch of ekf_transform; 9 and 10 the k_loc_solve and k_loc_rows launches of ekf_localize_*; 11 the k_loc_associate launch of ekf_localize_detections.  Does not reset: read before ekf_profile_read. */
 int ekf_profile_read_class(ekf_handle *h, int cls, double *ms_total, long long *launches);
 /* Options: name (default, allowed values) meaning.  Unknown names and values out of range fail with EKF_ERR_ARG.
  *   "flush_every"         (0, 0..64)    steps per covariance pass; 0 = auto, by "rank_limit"

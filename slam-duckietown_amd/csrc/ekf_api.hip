@@ -259,6 +259,9 @@ struct ekf_handle : ekf::HostPlan {
   // ekf_localize_* (allocated on first use): what k_loc_solve hands to k_loc_rows, one record per trajectory; consecutive steps
   // reuse it in stream order
   DeviceBuf<LocRec> dloc;
+  // ekf_localize_detections (allocated on first use): per trajectory, the tags of its last localisation window that its map does
+  // not hold (k_loc_associate; ekf_download_unmatched).  A property of the slot: a copy or a join leaves it as it is
+  DeviceBuf<LocUnmatched> d_unmatched;
   std::string err;
 };
 
@@ -2545,6 +2548,92 @@ extern "C" int ekf_localize_run(ekf_handle* h, int first, int count) {
     h->neff[b] = std::max(h->neff[b], std::min(h->n[b], own_last[b]));
     h->neff_enq[b] = h->opt_active_bound ? h->neff[b] : h->n[b];
   }
+  return EKF_OK;
+}
+
+// One window of raw detections per trajectory in localisation mode: ekf_localize_step on whatever the window matches, with the
+// association on the device (k_loc_associate, ekf_loc_assoc.hip) -- no tag table or pose comes back to the host.  What the call
+// launches is plan_localize_detections' (ekf_host_plan.h).  loc_begin, the association's buffers, the DetIn records through the
+// ring (as ekf_step_detections), k_loc_associate into d_assoc_step / d_assoc_out / d_unmatched, then loc_pass on the first records
+// and, where a window may match more than MMAX tags, on the update-only rest; log rows as do_localize writes them.
+// The active bound: the device raises dneff over the landmarks it matched and bakes it into the records; the host's mirror
+// follows through sizes_dirty (refresh_sizes reads dn -- unchanged: the size never moves -- and dneff back before anything uses
+// them; loc_bound_hi, push_floor and the step paths honour the flag as they do behind ekf_step_detections).
+extern "C" int ekf_localize_detections(ekf_handle* h, const double* lin, const double* ang, const int* count, const int* tag_id,
+                                       const double* pose_t, const double* pose_err, int stride) {
+  const char* fn = "ekf_localize_detections";
+  if (!h) return EKF_ERR_ARG;
+  HIP_TRY(h, hipSetDevice(h->device));
+  LogScope log_scope{h};
+  if (int rc = check_host_bad(h, fn)) return rc;
+  LocDetPlan lp;
+  if (const char* why = plan_localize_detections(h, lin, ang, count, tag_id, pose_t, pose_err, stride, lp)) return bad_arg(h, fn, why);
+  if (int rc = loc_begin(h)) return rc;
+  if (int rc = assoc_init(h)) return rc;
+  if (!h->d_unmatched.p) {
+    RES_TRY(h, "the unmatched-tag records", h->d_unmatched.reserve((size_t)h->batch, 0, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_unmatched.p, 0, sizeof(LocUnmatched) * h->batch, h->stream));
+  }
+  if (int rc = push_floor(h, false)) return rc;
+  int slot;
+  if (int rc = ring_take(h, &slot)) return rc;
+  DetIn* hs = h->h_det.p + (size_t)slot * h->batch;
+  DetIn* ds = h->d_det.p + (size_t)slot * h->batch;
+  for (int b = 0; b < h->batch; ++b) {
+    DetIn& d = hs[b];
+    d.lin = lin[b];
+    d.ang = ang[b];
+    d.count = count[b];
+    d.pad = 0;
+    for (int i = 0; i < count[b]; ++i) {
+      const long e = (long)b * stride + i;
+      d.tag_id[i] = tag_id[e];
+      d.pose_err[i] = pose_err[e];
+      d.pose_t[i][0] = pose_t[3 * e];
+      d.pose_t[i][1] = pose_t[3 * e + 1];
+      d.pose_t[i][2] = pose_t[3 * e + 2];
+    }
+  }
+  // the host's view of the active bound must be on the device before the first device-side window
+  if (!h->sizes_dirty)
+    HIP_TRY(h, hipMemcpyAsync(h->dneff.p, h->neff.data(), sizeof(int) * h->batch, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(ds, hs, sizeof(DetIn) * h->batch, hipMemcpyHostToDevice, h->stream));
+  if (int rc = ring_done(h, slot)) return rc;
+  h->acfg.active_bound = h->opt_active_bound;
+  ProfBracket pb;
+  if (int rc = prof_open(h, 11, h->stream, &pb)) return rc;
+  launch_loc_associate(h->stream, bank_view(h), ds, h->dtagmap.p, h->dneff.p, h->dmu2[h->cur].p, h->d_assoc_step.p, h->d_assoc_out.p,
+                       h->d_unmatched.p, h->acfg);
+  if (int rc = prof_close(h, &pb)) return loc_half_failed(h, rc);
+  if (hipGetLastError() != hipSuccess) return loc_half_failed(h, fail(h, EKF_ERR_HIP, std::string(fn) + ": the association's launch failed"));
+  h->sizes_dirty = true;
+  const bool logged = h->dinnov.p != nullptr;
+  h->pl_slot = h->dpose.p ? (long)(h->pose_steps % h->pose_cap) : -1;
+  for (int p = 0; p < lp.passes; ++p) {
+    h->lg_slot = logged ? (long)(h->innov_steps % h->innov_cap) : -1;
+    h->lg_jbase = MMAX * p;
+    if (int rc = loc_pass(h, h->d_assoc_step.p + (size_t)p * h->batch, lp.groups)) return loc_half_failed(h, rc);
+  }
+  if (logged) h->innov_steps += 1;
+  if (int rc = loc_pose_row(h)) return loc_half_failed(h, rc);
+  if (h->dpose.p) h->pose_steps += 1;
+  return EKF_OK;
+}
+
+// The distinct tag ids of trajectory b's last localisation window that its map does not hold, in order of first appearance: *m
+// their number, the first min(*m, capacity, EKF_AMAX) of them into tag_id.  Blocking.
+extern "C" int ekf_download_unmatched(ekf_handle* h, int b, int* m, int* tag_id, int capacity) {
+  const char* fn = "ekf_download_unmatched";
+  if (int rc = check_b(h, b, fn)) return rc;
+  if (!m || capacity < 0 || (capacity > 0 && !tag_id)) return bad_arg(h, fn, "NULL m, or a capacity without an array");
+  if (!h->d_unmatched.p) return fail(h, EKF_ERR_STATE, std::string(fn) + ": no localisation window has run (ekf_localize_detections)");
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (int rc = check_internal(h, b, fn)) return rc;
+  LocUnmatched u;
+  HIP_TRY(h, hipMemcpyAsync(&u, h->d_unmatched.p + b, sizeof(u), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  *m = u.total;
+  for (int i = 0; i < std::min(std::min(u.total, AMAX), capacity); ++i) tag_id[i] = u.tag_id[i];
   return EKF_OK;
 }
 

@@ -256,6 +256,14 @@ struct AssocOut {                       // what the reference returns as tags_po
   double xw[AMAX], yw[AMAX], err[AMAX], range[AMAX], bearing[AMAX];
 };
 
+// ekf_localize_detections (k_loc_associate, ekf_loc_assoc.hip): the tags of a trajectory's last localisation window that its frozen
+// map does not hold -- `total` distinct ids, the first AMAX of them in order of first appearance (-1 beyond).
+struct LocUnmatched {
+  int total;
+  int pad;
+  int tag_id[AMAX];
+};
+
 struct AssocConfig {
   double gate2;                         // 1.5^2 (:289)
   double init_var;                      // 1e4   (:356-357)

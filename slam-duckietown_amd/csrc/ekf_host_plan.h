@@ -1030,6 +1030,44 @@ inline int loc_bound_hi(const HostPlan* h, const int* own = nullptr) {
 }
 inline int loc_rows_groups(int n_hi) { return (std::max(n_hi, 3) + LOC_THREADS - 1) / LOC_THREADS; }
 
+// ekf_localize_detections (k_loc_associate -> k_loc_solve -> k_loc_rows): the arguments checked as ekf_step_detections checks its
+// own -- lin, ang, count, the stride, every count in [0, min(stride, EKF_DMAX)], the detection arrays where anything is detected --
+// and what the call launches.  m_hi: the most distinct tag ids of any trajectory's window, capped at AMAX (an upper bound of what
+// the device matches -- ignored, gated, unknown and bad ids count --, the bound ekf_step_detections selects its kernels by; 0 with
+// the measurement model off); passes: a second k_loc_solve / k_loc_rows pair on the update-only records where m_hi > MMAX.
+// groups: k_loc_rows' grid.  The device raises a trajectory's bound over the landmarks it matches, which the host does not know:
+// where anything may be matched the grid covers the largest state (n_max while the sizes are dirty), else the bound mirrors as
+// for the other localisation calls (loc_bound_hi); a workgroup beyond its trajectory's bound returns at once.
+// Returns nullptr, or what is wrong (then nothing of `lp` is to be used and no handle state has changed).
+struct LocDetPlan {
+  int m_hi = 0, passes = 1, groups = 1;
+};
+inline const char* plan_localize_detections(const HostPlan* h, const double* lin, const double* ang, const int* count,
+                                            const int* tag_id, const double* pose_t, const double* pose_err, int stride,
+                                            LocDetPlan& lp) {
+  if (!lin || !ang || !count || stride < 0) return "NULL array";
+  int m_hi = 0;
+  for (int b = 0; b < h->batch; ++b) {
+    const int c = count[b];
+    if (c < 0 || c > stride || c > DMAX) return "count must be <= min(stride, EKF_DMAX)";
+    if (c > 0 && (!tag_id || !pose_t || !pose_err)) return "NULL detection arrays";
+    const long off = (long)b * stride;
+    int distinct = 0;
+    for (int i = 0; i < c; ++i) {
+      bool seen = false;
+      for (int k = 0; k < i; ++k) seen |= (tag_id[off + k] == tag_id[off + i]);
+      distinct += seen ? 0 : 1;
+    }
+    m_hi = std::max(m_hi, std::min(distinct, AMAX));
+  }
+  if (!h->cfg.enable_measurement_model) m_hi = 0;
+  lp.m_hi = m_hi;
+  lp.passes = m_hi > MMAX ? 2 : 1;
+  const int n_hi = h->sizes_dirty ? h->n_max : *std::max_element(h->n.begin(), h->n.end());
+  lp.groups = loc_rows_groups(m_hi > 0 ? n_hi : loc_bound_hi(h));
+  return nullptr;
+}
+
 // ekf_copy_trajectories (k_copy_traj, ekf_copy.hip): the k pairs (src_b[i] of `src` -> dst_b[i] of `dst`) checked -- indices
 // inside their banks, no destination twice, inside one handle no trajectory both read and written, the same device, every
 // source's size within the destination's n_max -- and grouped by source: a group is one source and up to COPY_FANOUT of its

@@ -105,7 +105,7 @@ void launch_factor_solve(hipStream_t st, const FactorView& w, int f0, int count,
                          double* white, double* quad);
 void launch_factor_multiply(hipStream_t st, const FactorView& w, int f0, int count, int nblk_hi, const double* z, int nrhs,
                             int stride, double* out);
-// ---- state surgery (ekf_remove.hip, ekf_direct.hip, ekf_linear.hip, ekf_predict_linear.hip, ekf_localize.hip, ekf_copy.hip, ekf_join.hip, ekf_transform.hip, ekf_dense.hip) ----
+// ---- state surgery (ekf_remove.hip, ekf_direct.hip, ekf_linear.hip, ekf_predict_linear.hip, ekf_localize.hip, ekf_loc_assoc.hip, ekf_copy.hip, ekf_join.hip, ekf_transform.hip, ekf_dense.hip) ----
 // rp.rows: the launch's largest new size (grid rows); nb trajectories from b0; src / dst: rp's tables on the device
 void launch_remove(hipStream_t st, const BankView& k, double* mu, const RemovePlan& rp, const int* src, const int* dst,
                    unsigned* rflag, int b0, int nb, unsigned seq);
@@ -125,6 +125,11 @@ void launch_predict_pose(hipStream_t st, const PendingView& f, double* P, double
 void launch_loc_solve(hipStream_t st, const BankView& k, double* mu, const StepIn* in, const int* neff_floor, LocRec* rec,
                       const DeviceConfig& cfg);
 void launch_loc_rows(hipStream_t st, const BankView& k, const LocRec* rec, int groups);
+// ekf_localize_detections (ekf_loc_assoc.hip): the whole bank, one DetIn each in `det`; reads tagmap, k.nact and the pose in `mu`,
+// writes step_out[b] and step_out[k.batch + b] (what the two launch_loc_solve of the call read), assoc_out[b], unmatched[b],
+// neff_dev[b] (raised over the matched landmarks) and k.flags -- nothing else
+void launch_loc_associate(hipStream_t st, const BankView& k, const DetIn* det, const int* tagmap, int* neff_dev, const double* mu,
+                          StepIn* step_out, AssocOut* assoc_out, LocUnmatched* unmatched, const AssocConfig& cfg);
 // groups x (tiles of the largest source + 1) workgroups; tab: plan_copy's table on the device
 void launch_copy_traj(hipStream_t st, bool nt, const BankView& src, const BankView& dst, const double* mus, double* mud,
                       const int* tab, int groups, int n_hi);

@@ -30,7 +30,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .frontend import associate, fit_transform, joint_compatibility, remap_tag_index, resolve_associations
+from .frontend import associate, associate_known, fit_transform, joint_compatibility, remap_tag_index, resolve_associations
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libekfslam_hip.so"
@@ -156,6 +156,8 @@ ABI = {
     "ekf_download_tags": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
     "ekf_download_tag_index": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_int, _ip]),
     "ekf_upload_tag_index": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_int]),
+    "ekf_localize_detections": (C.c_int, [C.c_void_p, _dp, _dp, _ip, _ip, _dp, _dp, C.c_int]),
+    "ekf_download_unmatched": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, C.c_int]),
     "ekf_stream_upload": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
     "ekf_stream_run": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ekf_run_stream": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
@@ -505,6 +507,7 @@ class EkfSlam:
         self._assoc_gate, self._assoc_ignore = self.config.gate_range, tuple(self.config.ignore_tags)
         self._host_index = {}
         self._host_tags = {}
+        self._host_unmatched = {}                            # localize_detections' host route: the last window's unmatched ids
         # per-call staging arrays and their ctypes pointers, made once: `ndarray.ctypes.data_as` costs ~2 us per argument,
         # seven of them were most of what an online step of a small filter cost on the host (the library copies everything
         # it needs out of these arrays before the call returns)
@@ -1516,6 +1519,11 @@ class EkfSlam:
             self._lib.ekf_debug_note_assoc_fallback(self._h)       # (counted: ekf_debug_assoc_fallbacks / assoc_fallbacks())
             return self._step_detections_host(lin, ang, detections)
         self._host_tags.clear()
+        self._detections_call(self._lib.ekf_step_detections, detections)
+
+    def _detections_call(self, entry, detections):
+        """One window per trajectory, frames concatenated in order, into the arrays ``ekf_step_detections`` and
+        ``ekf_localize_detections`` take; lin / ang are in the staging arrays."""
         flat = [[tag for _stamp, tags in win for tag in tags] for win in detections]
         count = np.array([len(w) for w in flat], dtype=np.int32)
         stride = max(1, int(count.max()))
@@ -1527,8 +1535,64 @@ class EkfSlam:
                 ids[b, i] = tag.tag_id
                 pt[b, i] = np.asarray(tag.pose_t, dtype=np.float64).ravel()[:3]
                 pe[b, i] = tag.pose_err
-        self._check(self._lib.ekf_step_detections(self._h, self._plin, self._pang, _p(count, _ip), _p(ids, _ip), _p(pt), _p(pe),
-                                                  stride))
+        self._check(entry(self._h, self._plin, self._pang, _p(count, _ip), _p(ids, _ip), _p(pt), _p(pe), stride))
+
+    # -- localisation from raw detections --------------------------------------------------------
+    def localize_detections(self, lin, ang, detections):
+        """``localize`` on whatever one window of raw detections per trajectory matches (``ekf_localize_detections``): window
+        format and batch handling as ``step_detections``, but the map is frozen -- a tag the trajectory's TAG_INDEX does not
+        hold is skipped and reported by ``unmatched_tags``, nothing is added, the table and the sizes stay as they are.
+        Association, gate, averaging and the step run on the GPU with no host round trip; ``tags_positions`` returns the matched
+        tags.  The call takes the host route -- ``tag_index`` + ``mean`` + ``frontend.associate_known`` + ``localize``, counted
+        in ``assoc_fallbacks()`` -- when a window does not fit the device front end (``step_detections`` has the limits) or a
+        trajectory's TAG_INDEX lives on the host because it holds ids the device table cannot."""
+        self._per_traj(lin, "lin", self._lin)
+        self._per_traj(ang, "ang", self._ang)
+        if self.batch == 1 and (len(detections) == 0 or isinstance(detections[0], tuple)):
+            detections = [detections]
+        if len(detections) != self.batch:
+            raise ValueError("detections: one window per trajectory expected")
+        if self._host_index or not all(self._window_fits_device(win) for win in detections):
+            self._lib.ekf_debug_note_assoc_fallback(self._h)
+            return self._localize_detections_host(self._lin.copy(), self._ang.copy(), detections)
+        self._localize_detections_device(detections)
+
+    def _localize_detections_device(self, detections):
+        self._host_tags.clear()
+        self._host_unmatched.clear()
+        self._detections_call(self._lib.ekf_localize_detections, detections)
+
+    def _localize_detections_host(self, lin, ang, detections):
+        tags_all, unmatched_all = [], []
+        for b, win in enumerate(detections):
+            index = self.tag_index(b)                              # (the host's while it is in charge; no stand-in ids)
+            tags, unmatched = associate_known(win, index, self.mean(b)[:3], self._assoc_gate, self._assoc_ignore,
+                                              n_landmarks=(self.size(b) - 3) // 2)
+            tags_all.append(tags)
+            unmatched_all.append(unmatched)
+        idx = [list(t.keys()) for t in tags_all]
+        self.localize(lin, ang, idx, [[t[k][4] for k in ks] for t, ks in zip(tags_all, idx)],
+                      [[t[k][5] for k in ks] for t, ks in zip(tags_all, idx)])
+        for b, (tags, unmatched) in enumerate(zip(tags_all, unmatched_all)):
+            self._host_tags[b] = tags
+            self._host_unmatched[b] = unmatched
+
+    def unmatched_tags(self, b: int = 0) -> list:
+        """The distinct tag ids of trajectory b's last ``localize_detections`` window that its map does not hold, in order of
+        first appearance (``ekf_download_unmatched``: the first EKF_AMAX of them; the host route keeps all)."""
+        if b in self._host_unmatched:
+            return [int(t) for t in self._host_unmatched[b]]
+        m = C.c_int()
+        ids = np.full(EKF_AMAX, -1, dtype=np.int32)
+        self._check(self._lib.ekf_download_unmatched(self._h, b, C.byref(m), _p(ids, _ip), EKF_AMAX))
+        return [int(t) for t in ids[:min(m.value, EKF_AMAX)]]
+
+    def reset_pose(self, pose, cov, b: Optional[int] = None):
+        """The kidnapped-robot entry: the pose mean replaced by ``pose``, the pose block set to ``cov`` (3, 3), every
+        pose-landmark cross term dropped; the map stays.  ``predict_linear(pose, F = 0, Q = cov)``: ``b`` None resets the whole
+        bank (``pose`` (B, 3) or one for all), ``b`` given that trajectory alone."""
+        count = self.batch if b is None else 1
+        self.predict_linear(np.broadcast_to(np.asarray(pose, dtype=np.float64), (count, 3)), np.zeros((3, 3)), cov, b=b)
 
     def _step_detections_host(self, lin, ang, detections):
         """The same window through the host association (see step_detections): what the reference does at :280-360 with

@@ -7,6 +7,7 @@ odometry scalars.  O(#detections) Python, mirrors the reference's semantics exac
   delta_phi      src/replay_no_ros.py:250-266
   displacement   src/replay_no_ros.py:484-497
 
+`associate_known` is `associate` against a frozen map (localisation mode: unknown tags are reported, never added).
 `resolve_associations` has no counterpart in the reference (which trusts tag ids): it turns the candidates the device's
 likelihood query (``EkfSlam.associate``) returns for one trajectory's unlabelled observations into an assignment.
 """
@@ -66,6 +67,11 @@ def associate(detections, tag_index: Dict[int, int], pose, gate_range: float = 1
                 acc[0] += tx
                 acc[1] += tz
                 acc[2].append(tag.pose_err)
+    return _averaged(seen, pose)
+
+
+def _averaged(seen, pose):
+    """What ``associate`` and ``associate_known`` return for the window's sums ``{landmark: [sum tx, sum tz, errs, tag id]}``."""
     x0, y0, th = float(pose[0]), float(pose[1]), float(pose[2])
     result = {}
     for lm, (sx, sz, errs, tid) in seen.items():
@@ -82,6 +88,41 @@ def associate(detections, tag_index: Dict[int, int], pose, gate_range: float = 1
         brg = np.arctan2(y_r, x_r)
         result[lm] = [x0 + rng * np.cos(brg + th), y0 + rng * np.sin(brg + th), err, tid, rng, brg]
     return result
+
+
+def associate_known(detections, tag_index: Dict[int, int], pose, gate_range: float = 1.5,
+                    ignore_tags: Sequence[int] = (), n_landmarks=None):
+    """``associate`` against a FROZEN map (localisation): ``tag_index`` is read, never written.  A tag it does not hold -- or,
+    with ``n_landmarks`` given, one whose index lies at or beyond it -- is unmatched: it takes no part and its id is recorded.
+    Ignored tags and tags beyond the gate are dropped before that, as in ``associate`` (:286-289).
+
+    Returns ``(tags, unmatched)``: ``tags`` as ``associate`` returns them, with the same numbers (the same sums in the same
+    order), and the distinct unmatched ids in order of first appearance."""
+    gate2 = gate_range ** 2
+    seen: Dict[int, List] = {}
+    unmatched: List[int] = []
+    for _stamp, tags in detections:
+        for tag in tags:
+            tid = tag.tag_id
+            if tid in ignore_tags:
+                continue
+            t = tag.pose_t
+            tx, tz = float(t[0][0]), float(t[2][0])
+            if tz * tz + tx * tx > gate2:
+                continue
+            lm = tag_index.get(tid)
+            if lm is None or (n_landmarks is not None and lm >= n_landmarks):
+                if tid not in unmatched:
+                    unmatched.append(tid)
+                continue
+            acc = seen.get(lm)
+            if acc is None:
+                seen[lm] = [tx, tz, [tag.pose_err], tid]
+            else:
+                acc[0] += tx
+                acc[1] += tz
+                acc[2].append(tag.pose_err)
+    return _averaged(seen, pose), unmatched
 
 
 def remap_tag_index(tag_index: Dict[int, int], old_to_new) -> Dict[int, int]:

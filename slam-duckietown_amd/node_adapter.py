@@ -33,11 +33,14 @@ from .frontend import delta_phi, displacement
 
 class EkfNodeAdapter:
     def __init__(self, backend=None, wheel_radius: float = 0.0318, baseline: float = 0.1,
-                 persistent_tag_index: bool = True, device_association: bool = False):
+                 persistent_tag_index: bool = True, device_association: bool = False, localize: bool = False):
+        """localize=True: the node drives on a finished map handed over with ``set_map`` -- every tick is a pose-only step on
+        the frozen map (``GpuBackend(localize=True)``; a backend of the caller's needs ``set_map``), unknown tags are skipped."""
         if backend is None:
             from .replay import GpuBackend
-            backend = GpuBackend(device_association=device_association)
+            backend = GpuBackend(device_association=device_association, localize=localize)
         self.backend = backend
+        self.localize = localize
         self.backend.set_state(np.array([0.0, 0.0, 0.0]), np.eye(3) * 0.1)       # node :56-57
         self.wheel_radius, self.baseline = wheel_radius, baseline                # :180-181
         self.persistent_tag_index = persistent_tag_index
@@ -49,6 +52,13 @@ class EkfNodeAdapter:
         self.tags = {}
         self.path = []                                # acc_pos
         self._lock = threading.Lock()
+
+    def set_map(self, mean, cov, tag_index):
+        """The finished map of a localising node: the state (its pose included) and the tag-id -> landmark-index map."""
+        if not self.localize:
+            raise ValueError("set_map: the adapter was not created with localize=True")
+        self.backend.set_map(np.asarray(mean, dtype=float), np.asarray(cov, dtype=float), tag_index)
+        self.tag_index = dict(tag_index)
 
     def on_left_encoder(self, ticks: int, resolution: int):
         if self.resolution is None:

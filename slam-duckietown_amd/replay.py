@@ -50,22 +50,29 @@ class ReplayResult:
 class GpuBackend:
     """Runs association on the host and augmentation + predict + update on the MI355X."""
 
-    def __init__(self, config=None, capacity: int = 79, device: int = 0, device_association: bool = False):
+    def __init__(self, config=None, capacity: int = 79, device: int = 0, device_association: bool = False,
+                 localize: bool = False):
         """capacity: n_max of the first handle (79 = 38 landmarks: the small-state path, one launch per window -- the
         reference's map has 12, src/replay_no_ros.py:26); the handle is re-created with twice the room when the map outgrows it.
         device_association=True: association / gate / averaging / augmentation run on the GPU too
         (`EkfSlam.step_detections`).  The device front end has limits the reference does not (16 distinct tags
         and 64 detections per window, tag ids below 1024, a fixed capacity): every window is checked against them
         on the host first; the state is regrown when the map would not fit, and a window beyond the per-window
-        limits takes the host association (which has none) for that window."""
+        limits takes the host association (which has none) for that window.
+        localize=True: a lap over a finished map (`set_map`): every window is one `EkfSlam.localize_detections` -- association
+        against the frozen map and the pose-only step on the GPU, a window beyond the front end's limits through the host for
+        that window --, the handle never grows and the caller's TAG_INDEX is never touched; `unmatched` holds the unknown tags
+        of the last window."""
         from .ekf_bindings import EkfConfig, EkfSlam
         self.config = config or EkfConfig()
         self.device_association = device_association
+        self.localize = localize
+        self.unmatched = []
         self._make = lambda cap: EkfSlam(cap | 1, 1, device, self.config)
         self.filt = self._make(capacity)
         self._cache = None            # (mean, covariance) of the device state when the last step brought them back with it
         self._dev_index = None        # device_association: the device's tag table as last downloaded (one download per window)
-        if device_association:
+        if device_association or localize:
             self.filt.set_association(self.config.gate_range, self.config.ignore_tags)
 
     def set_state(self, mean, cov):
@@ -75,9 +82,14 @@ class GpuBackend:
         if n > self.filt.n_max:
             self.filt.close()
             self.filt = self._make(max(n, 2 * self.filt.n_max - 3))
-            if self.device_association:
+            if self.device_association or self.localize:
                 self.filt.set_association(self.config.gate_range, self.config.ignore_tags)
         self.filt.set_state(mean, cov)
+
+    def set_map(self, mean, cov, tag_index):
+        """The finished map a localising backend drives on: state and TAG_INDEX (tag ids in [0, 1024): the device's table)."""
+        self.set_state(mean, cov)
+        self.filt.set_tag_index({int(t): int(j) for t, j in tag_index.items()})
 
     def _grow(self, n_needed):
         self._cache = None
@@ -119,6 +131,10 @@ class GpuBackend:
     def step(self, ang, lin, detections, tag_index) -> dict:
         from .ekf_bindings import EKF_AMAX, EKF_DMAX, EKF_TAGMAX
         cached, self._cache = self._cache, None
+        if self.localize:                                         # (tag_index is the caller's: not read, not written)
+            self.filt.localize_detections(lin, ang, detections)
+            self.unmatched = self.filt.unmatched_tags()
+            return self.filt.tags_positions()
         if self.device_association:
             dev_index = dict(self._dev_index) if self._dev_index is not None else self.filt.tag_index()
             if tag_index and not dev_index:                       # a pre-filled TAG_INDEX (god mode) goes to the device
@@ -180,7 +196,7 @@ def _payload(line: str) -> str:
 def replay(source, backend=None, delta_time: float = 0.7, detector: Optional[Callable] = None,
            god_key: Optional[Sequence[int]] = None, wheel_radius: float = 0.0318, baseline: float = 0.1,
            resolution: int = 135, motion_sigma: float = 0.1, on_window: Optional[Callable] = None,
-           fast_mode: bool = False) -> ReplayResult:
+           fast_mode: bool = False, localize: bool = False, map_state=None) -> ReplayResult:
     """Replay an ``events.csv`` (directory, file path, or an iterable of lines) through the EKF.
 
     ``backend`` defaults to ``GpuBackend()``; it needs ``set_state / pose / state / step`` (tests inject a
@@ -188,7 +204,15 @@ def replay(source, backend=None, delta_time: float = 0.7, detector: Optional[Cal
     ``fast_mode`` is the reference's ``ENABLE_FAST_MODE`` (:32): frames are only queued when they arrive
     (:122-123) and, at every window boundary, the detector runs on the LAST FIVE frames queued so far -- the
     queue is never emptied, so a window with fewer than five frames reaches back into earlier ones (:216-227).
+    ``localize=True`` replays the log over a finished map ``map_state = (mean, covariance, tag_index)`` -- a second lap: the
+    run starts from that state (its pose included) instead of the origin, every window is a pose-only step on the frozen map
+    (``GpuBackend(localize=True)``; a backend of the caller's needs ``set_map``), unknown tags are skipped, and the result's
+    ``tag_index`` is the map's.  ``god_key`` has no meaning there and is refused.
     """
+    if localize and (map_state is None or god_key is not None):
+        raise ValueError("replay(localize=True) needs map_state = (mean, covariance, tag_index) and no god_key")
+    if map_state is not None and not localize:
+        raise ValueError("map_state is only read with localize=True")
     base_dir = None
     if isinstance(source, (str, os.PathLike)):
         path = os.fspath(source)
@@ -202,15 +226,19 @@ def replay(source, backend=None, delta_time: float = 0.7, detector: Optional[Cal
         lines = list(source)
     own_backend = backend is None
     if backend is None:
-        backend = GpuBackend()
-    backend.set_state(np.array([0.0, 0.0, 0.0]), np.eye(3) * motion_sigma)        # :69-70
+        backend = GpuBackend(localize=localize)
+    tag_index: Dict[int, int] = {}
+    if localize:
+        backend.set_map(np.asarray(map_state[0], dtype=float), np.asarray(map_state[1], dtype=float), map_state[2])
+        tag_index = dict(map_state[2])
+    else:
+        backend.set_state(np.array([0.0, 0.0, 0.0]), np.eye(3) * motion_sigma)    # :69-70
 
     prev_ltick = prev_rtick = curr_ltick = curr_rtick = False                    # :74-78
     prev_stamp = False                                                           # :81
-    tag_index: Dict[int, int] = {}
     window: list = []
     image_list: list = []                                                        # fast mode: every frame so far (:123)
-    poses, path_xy, measured = [], [(0, 0)], []
+    poses, path_xy, measured = [], [(float(map_state[0][0]), float(map_state[0][1])) if localize else (0, 0)], []
     ground_truth, landmarks = [], None
     camera_params = [340, 336, 328, 257]                                         # :93
     windows = 0

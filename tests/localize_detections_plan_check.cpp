@@ -1,0 +1,148 @@
+// Sanitizer build of the host side of ekf_localize_detections (slam-duckietown_amd/csrc/ekf_host_plan.h:
+// plan_localize_detections; ekf_device.h: LocUnmatched):
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DEKF_HOST_ONLY
+//       -I slam-duckietown_amd/csrc -I include tests/localize_detections_plan_check.cpp -o localize_detections_plan_check
+// The pass count at 0, 16, 17 and 32 distinct ids (and beyond: the cap), the k_loc_rows grid from the bound mirrors with
+// sizes_dirty and without, every argument error with the plan left as it was, and randomised windows whose arrays are allocated to
+// exactly the size the call states, so that a read beyond them is a sanitizer report; any report or failed check ends the run
+// with a non-zero status.
+#include <cstring>
+#include <random>
+#include <vector>
+
+#include "plan_check.h"
+
+using namespace ekf;
+
+static HostPlan make_bank(int n_max, std::vector<int> n, std::vector<int> neff) {
+  HostPlan h = bank(n_max, n, neff);
+  h.floor_host.assign(n.size(), 3);
+  h.cfg.enable_measurement_model = 1;
+  return h;
+}
+
+struct Windows {
+  std::vector<double> lin, ang, pose_t, pose_err;
+  std::vector<int> count, tag_id;
+  int stride;
+  Windows(int batch, int stride_, std::vector<int> count_) : lin((size_t)batch, 0.004), ang((size_t)batch, 0.02),
+                                                             pose_t((size_t)batch * stride_ * 3, 0.5), pose_err((size_t)batch * stride_, 0.0),
+                                                             count(std::move(count_)), tag_id((size_t)batch * stride_, 0), stride(stride_) {}
+  // trajectory b sees `distinct` ids, each in `frames` frames
+  void fill(int b, int distinct, int frames) {
+    for (int i = 0; i < distinct * frames; ++i) tag_id[(size_t)b * stride + i] = 100 + i % distinct;
+  }
+  const char* plan(const HostPlan& h, LocDetPlan& lp) const {
+    return plan_localize_detections(&h, lin.data(), ang.data(), count.data(), tag_id.data(), pose_t.data(), pose_err.data(), stride, lp);
+  }
+};
+
+static bool says(const char* why, const char* part) { return why && std::strstr(why, part); }
+static bool unused(const LocDetPlan& lp) { return lp.m_hi == -7 && lp.passes == -7 && lp.groups == -7; }
+
+int main() {
+  CHECK(sizeof(LocUnmatched) == 8 + 4 * AMAX && AMAX == 2 * MMAX, "LocUnmatched is %zu bytes", sizeof(LocUnmatched));
+  const int N = 300;                                           // 603 state indices: three column groups of 256
+  HostPlan h = make_bank(3 + 2 * N, {3 + 2 * N, 3 + 2 * 10, 3 + 2 * 100}, {3 + 2 * 12, 3 + 2 * 10, 3});
+  LocDetPlan lp;
+  // ---- the pass count: 0, 16, 17, 32 distinct ids, three frames each; 40: the cap ----
+  const int want_m[5][3] = {{0, 0, 1}, {16, 16, 1}, {17, 17, 2}, {32, 32, 2}, {40, 32, 2}};
+  for (const auto& w : want_m) {
+    Windows c(3, 3 * 40, {0, 3 * w[0], 0});
+    c.fill(1, w[0], 3);
+    CHECK(c.plan(h, lp) == nullptr, "a good call was refused");
+    CHECK(lp.m_hi == w[1] && lp.passes == w[2], "%d distinct ids: m_hi %d passes %d", w[0], lp.m_hi, lp.passes);
+  }
+  // ---- the grid ----
+  {
+    Windows none(3, 4, {0, 0, 0});
+    CHECK(none.plan(h, lp) == nullptr && lp.m_hi == 0 && lp.passes == 1, "no detection");
+    CHECK(lp.groups == loc_rows_groups(loc_bound_hi(&h)) && lp.groups == 1, "nothing can be matched: the bound mirrors (%d)", lp.groups);
+    HostPlan f = h;
+    f.floor_host = {3 + 2 * 200, 3, 3};
+    CHECK(none.plan(f, lp) == nullptr && lp.groups == 2, "the floor raises the grid (%d)", lp.groups);
+    Windows one(3, 4, {0, 0, 2});
+    CHECK(one.plan(h, lp) == nullptr && lp.m_hi == 1, "one id twice");
+    CHECK(lp.groups == loc_rows_groups(3 + 2 * N) && lp.groups == 3, "a match may raise any bound to its size (%d)", lp.groups);
+    f = h;
+    f.opt_active_bound = 0;
+    CHECK(none.plan(f, lp) == nullptr && lp.groups == 3, "the shortcut off: the whole state (%d)", lp.groups);
+    // the device has moved sizes or bounds since the host last read them: only n_max bounds the states
+    HostPlan g = make_bank(3 + 2 * 600, {3 + 2 * N, 3 + 2 * 10, 3 + 2 * 100}, {3 + 2 * 12, 3 + 2 * 10, 3});
+    CHECK(one.plan(g, lp) == nullptr && lp.groups == 3, "clean mirrors: the largest size");
+    g.sizes_dirty = true;
+    CHECK(one.plan(g, lp) == nullptr && lp.groups == loc_rows_groups(3 + 2 * 600) && lp.groups == 5, "sizes_dirty, a match: n_max (%d)", lp.groups);
+    CHECK(none.plan(g, lp) == nullptr && lp.groups == 5, "sizes_dirty, no match: n_max (%d)", lp.groups);
+    HostPlan off = h;
+    off.cfg.enable_measurement_model = 0;                      // prediction only: nothing is matched
+    Windows many(3, 60, {60, 0, 0});
+    many.fill(0, 20, 3);
+    CHECK(many.plan(off, lp) == nullptr && lp.m_hi == 0 && lp.passes == 1 && lp.groups == 1, "measurement model off");
+  }
+  // ---- the refusals, in ekf_step_detections' order; the plan stays unused ----
+  {
+    Windows c(3, 4, {4, 0, 3});
+    auto refused = [&](const char* why, const char* part, const char* what) {
+      CHECK(says(why, part), "%s: %s", what, why ? why : "accepted");
+      CHECK(unused(lp), "%s: the plan was written", what);
+    };
+    lp = LocDetPlan{-7, -7, -7};
+    refused(plan_localize_detections(&h, nullptr, c.ang.data(), c.count.data(), c.tag_id.data(), c.pose_t.data(), c.pose_err.data(), 4, lp), "NULL array", "NULL lin");
+    refused(plan_localize_detections(&h, c.lin.data(), nullptr, c.count.data(), c.tag_id.data(), c.pose_t.data(), c.pose_err.data(), 4, lp), "NULL array", "NULL ang");
+    refused(plan_localize_detections(&h, c.lin.data(), c.ang.data(), nullptr, c.tag_id.data(), c.pose_t.data(), c.pose_err.data(), 4, lp), "NULL array", "NULL count");
+    refused(plan_localize_detections(&h, c.lin.data(), c.ang.data(), c.count.data(), c.tag_id.data(), c.pose_t.data(), c.pose_err.data(), -1, lp), "NULL array", "stride < 0");
+    Windows over = c;
+    over.count[2] = 5;
+    refused(over.plan(h, lp), "count must be", "count > stride");
+    over.count[2] = -1;
+    refused(over.plan(h, lp), "count must be", "count < 0");
+    Windows big(1, DMAX + 1, {DMAX + 1});
+    HostPlan one = make_bank(3 + 2 * 5, {3 + 2 * 5}, {3});
+    refused(big.plan(one, lp), "count must be", "count > EKF_DMAX");
+    refused(plan_localize_detections(&h, c.lin.data(), c.ang.data(), c.count.data(), nullptr, c.pose_t.data(), c.pose_err.data(), 4, lp), "NULL detection arrays", "NULL tag_id");
+    refused(plan_localize_detections(&h, c.lin.data(), c.ang.data(), c.count.data(), c.tag_id.data(), nullptr, c.pose_err.data(), 4, lp), "NULL detection arrays", "NULL pose_t");
+    refused(plan_localize_detections(&h, c.lin.data(), c.ang.data(), c.count.data(), c.tag_id.data(), c.pose_t.data(), nullptr, 4, lp), "NULL detection arrays", "NULL pose_err");
+    Windows none(3, 0, {0, 0, 0});
+    CHECK(plan_localize_detections(&h, none.lin.data(), none.ang.data(), none.count.data(), nullptr, nullptr, nullptr, 0, lp) == nullptr && lp.m_hi == 0,
+          "no detection: no detection array is read");
+    Windows full(1, DMAX, {DMAX});
+    full.fill(0, 8, DMAX / 8);
+    CHECK(full.plan(one, lp) == nullptr && lp.m_hi == 8 && lp.passes == 1, "EKF_DMAX detections");
+  }
+  // ---- randomised windows, arrays of exactly the stated size ----
+  std::mt19937 rng(11);
+  for (int trial = 0; trial < 300; ++trial) {
+    const int batch = 1 + (int)(rng() % 4), stride = (int)(rng() % 90);
+    std::vector<int> n, neff, count;
+    for (int b = 0; b < batch; ++b) {
+      const int nl = (int)(rng() % 200);
+      n.push_back(3 + 2 * nl);
+      neff.push_back(3 + 2 * (int)(rng() % (nl + 1)));
+      count.push_back(stride == 0 || rng() % 4 == 0 ? 0 : (int)(rng() % (stride + 1)));
+    }
+    HostPlan r = make_bank(3 + 2 * 200, n, neff);
+    r.sizes_dirty = rng() % 5 == 0;
+    Windows c(batch, stride, count);
+    int want = 0;
+    for (int b = 0; b < batch; ++b) {
+      const int pool = 1 + (int)(rng() % 45);
+      std::vector<unsigned char> seen(1024, 0);
+      int distinct = 0;
+      for (int i = 0; i < count[(size_t)b]; ++i) {
+        const int id = (int)(rng() % pool) - 1;                // (-1: a bad id counts like any other)
+        c.tag_id[(size_t)b * stride + i] = id;
+        distinct += seen[(size_t)(id + 1)] ? 0 : 1;
+        seen[(size_t)(id + 1)] = 1;
+      }
+      want = std::max(want, std::min(distinct, AMAX));
+    }
+    CHECK(c.plan(r, lp) == nullptr, "trial %d refused", trial);
+    CHECK(lp.m_hi == want && lp.passes == (want > MMAX ? 2 : 1), "trial %d: m_hi %d (want %d) passes %d", trial, lp.m_hi, want, lp.passes);
+    const int n_hi = *std::max_element(n.begin(), n.end());
+    CHECK(lp.groups >= 1 && lp.groups <= loc_rows_groups(r.n_max), "trial %d: groups %d", trial, lp.groups);
+    if (!r.sizes_dirty && want > 0) CHECK(lp.groups * LOC_THREADS >= n_hi && lp.groups == loc_rows_groups(n_hi), "trial %d: the grid covers every state", trial);
+    if (r.sizes_dirty) CHECK(lp.groups == loc_rows_groups(r.n_max), "trial %d: dirty", trial);
+  }
+  std::printf("%ld checks passed\n", checks);
+  return 0;
+}
