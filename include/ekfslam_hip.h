@@ -622,6 +622,57 @@ int ekf_localize_detections(ekf_handle *h, const double *lin, const double *ang,
                             const int *tag_id, const double *pose_t, const double *pose_err, int stride);
 int ekf_download_unmatched(ekf_handle *h, int b, int *m, int *tag_id, int capacity);
 
+/* A bank of pose hypotheses on ONE frozen map: global localisation (the kidnapped robot) with hundreds or thousands of candidate
+ * poses.  A forked slot of a handle carries its own copy of the whole stored triangle, 8 n^2 bytes; on a frozen map every copy
+ * is identical, and what differs between two hypotheses is the pose mean, the pose block and the pose rows P(0..2, :).  The bank
+ * stores the map once and 24 bytes per column of the handle's row stride + 1040 bytes per hypothesis.  Measured on one MI355X
+ * (tools/hypotheses_time.py, profiles/hypotheses.txt; m = 8, shared observations, call + sync per step for all hypotheses):
+ * N = 2000: K = 32 31 us (ekf_localize_step on 32 forked slots: 30 us) in 135 MB against 4.2 GB, K = 1024 162 us, K = 4096 729 us;
+ * N = 8000, K = 32: 35 us against 37 us, 2.1 GB against 68 GB.  ekf_hyp_adopt: 81 us at N = 2000, 421 us at N = 8000.
+ * ekf_hyp_create applies what is pending on `h`, copies slot b's stored triangle, mean and tag-table row -- a SNAPSHOT: nothing
+ * the handle does afterwards reaches the bank, and nothing needs invalidating -- and seeds `count` hypotheses (1 .. 65536) with the
+ * slot's pose, pose block and pose rows.  The bank takes the handle's config flags, the slot's noise pair (ekf_set_noise), the
+ * handle's NIS gate threshold and, at creation, the slot's active bound.  Blocking.  Errors go to ekf_last_error of `h`.
+ * ekf_hyp_step / ekf_hyp_update are ekf_localize_step / ekf_localize_update for every hypothesis: the same kernel arithmetic in the
+ * same order, so a hypothesis ends BIT FOR BIT as a forked slot given the same calls would, whatever `count` and wherever it sits
+ * in the bank.  motion_stride 0: lin[0], ang[0] for every hypothesis, 1: lin[k], ang[k].  obs_stride 0: ONE list of m[0]
+ * observations idx / range / bearing [0, m[0]) for every hypothesis (tags carry their ids: the common case; one record is
+ * uploaded), 1: hypothesis k's m[k] observations at [k * stride, k * stride + m[k]).  m <= EKF_MMAX per call: a longer list is
+ * refused; split it into a step and update-only calls.  An index may come twice; indices are checked against the map.
+ * Every observation, whether or not the gate then rejects it, adds -1/2 (y^T S^-1 y + ln det S + 2 ln 2 pi) to the hypothesis's
+ * loglik (a term that is not finite is left out) and counts in n_obs; a rejection counts in n_rej and leaves pose, block and rows
+ * bit-identical to the call without that observation.  ASYNCHRONOUS on the bank's own stream.
+ * ekf_hyp_reset: the kidnapped-robot entry for hypotheses [k0, k0 + count): pose mean and pose block (cov: 3 x 3 row-major, the
+ * upper triangle is read) set, the pose rows zeroed, loglik, counters and flags cleared, the bound back to the map's -- what
+ * ekf_predict_linear with F = 0, Q = cov does to a slot.  Asynchronous.
+ * ekf_hyp_download (blocking; every output may be NULL): pose count x 3, cov count x 9 (the block, mirrored), loglik, n_obs, n_rej
+ * and the sticky flags (EKF_FLAG_NONFINITE) of hypotheses [k0, k0 + count).  ekf_hyp_download_rows: hypothesis k's P(0..2, 0..n) as
+ * 3 x n row-major, n the map's size.
+ * ekf_hyp_set_nis_gate: as ekf_set_nis_gate, for the bank (the rejections are the hypotheses' n_rej).
+ * ekf_hyp_adopt writes hypothesis k's pose mean, pose block and pose rows into slot b of `h` -- any handle on the same device
+ * whose slot b has the map as its frozen part.  Blocking: it waits for the bank's stream, applies what is pending on `h`, and
+ * compares on the device the slot's size, landmark means and every stored P(a, c), 3 <= a <= c < n, with the bank's map, bit for
+ * bit.  On any difference nothing is written and the call fails with EKF_ERR_STATE.  The slot's active bound is raised to the
+ * hypothesis's.
+ * Every call returns EKF_ERR_ARG for a NULL bank, a range outside it or a bad argument, with nothing changed; the message is in
+ * ekf_hyp_last_error.  Not part of a bank: raw detections, likelihood association per hypothesis, the innovation and pose logs,
+ * per-hypothesis noise, resampling. */
+typedef struct ekf_hypotheses ekf_hypotheses;
+int ekf_hyp_create(ekf_handle *h, int b, int count, ekf_hypotheses **out);
+int ekf_hyp_destroy(ekf_hypotheses *hy);
+int ekf_hyp_reset(ekf_hypotheses *hy, int k0, int count, const double *pose /* count x 3 */, const double *cov /* count x 9 */);
+int ekf_hyp_step(ekf_hypotheses *hy, const double *lin, const double *ang, int motion_stride, const int *idx,
+                 const double *range, const double *bearing, const int *m, int stride, int obs_stride);
+int ekf_hyp_update(ekf_hypotheses *hy, const int *idx, const double *range, const double *bearing, const int *m, int stride,
+                   int obs_stride);
+int ekf_hyp_download(ekf_hypotheses *hy, int k0, int count, double *pose, double *cov /* count x 9 */, double *loglik,
+                     long long *n_obs, long long *n_rej, unsigned *flags);
+int ekf_hyp_download_rows(ekf_hypotheses *hy, int k, double *rows /* 3 x n */, int n);
+int ekf_hyp_set_nis_gate(ekf_hypotheses *hy, double threshold);
+int ekf_hyp_adopt(ekf_hypotheses *hy, int k, ekf_handle *h, int b);
+int ekf_hyp_sync(ekf_hypotheses *hy);
+const char *ekf_hyp_last_error(ekf_hypotheses *hy);
+
 /* Streams of pre-uploaded inputs ([step][batch] and [step][batch][stride] arrays, stride <= EKF_MMAX; m[step][batch] landmarks
  * each -- any count per step and trajectory, 0 included: what the windows of src/replay_no_ros.py:280-301 hold).
  * ekf_stream_upload copies and validates `steps` steps of inputs into HBM (blocking);

@@ -3132,3 +3132,261 @@ extern "C" int ekf_set_option(ekf_handle* h, const char* name, int value) {
   }
   return fail(h, EKF_ERR_ARG, std::string("unknown option ") + name);
 }
+
+// ---- the hypothesis bank (ekf_hyp_*; k_hyp_solve + k_hyp_rows, k_hyp_fill, k_hyp_compare, k_hyp_adopt: ekf_hypotheses.hip) ----
+// One frozen map -- a snapshot of a slot's stored triangle and mean, taken at creation: nothing couples the bank to the handle
+// afterwards -- and `count` pose hypotheses on it.  The bank owns its stream; steps are asynchronous on it.  A step is the
+// records' upload (one record where motion and observations are shared), k_hyp_solve and k_hyp_rows; what the call launches is
+// plan_hyp_step's (ekf_host_plan.h).  ekf_hyp_adopt is the one call that touches a handle again: it waits for the bank's stream,
+// applies what is pending on the handle (loc_begin's rule), compares the slot's frozen part with the bank's map on the device and
+// only then writes the hypothesis's pose part into the slot, on the handle's stream.
+struct ekf_hypotheses : ekf::HypBank {
+  DeviceConfig dcfg{};            // the source's config, the slot's noise pair folded into rd / qd; no table, no counters
+  bool gate = false;              // the bank's NIS gate (dcfg.nis_gate: the threshold)
+  hipStream_t stream = nullptr;
+  DeviceBuf<double> dmap, dmu;    // the map: one trajectory's stored triangle in the source handle's layout, and its mean
+  DeviceBuf<int> dtag;            // the slot's tag-table row (TAGMAX ints; empty where the source had no table)
+  DeviceBuf<HypState> dst;
+  DeviceBuf<double> dX;           // count x 3 x ldx: the pose rows
+  DeviceBuf<LocRec> drec;
+  StagedUpload<StepIn> recs;      // a call's records: the pinned copy is rewritten once the previous upload has run
+  StagedUpload<double> init;      // ekf_hyp_reset's poses and covariances
+  DeviceBuf<unsigned> dcmp;       // ekf_hyp_adopt: the compare's mismatch count
+  std::vector<HypState> host_st;
+  std::string err;
+};
+
+static int hyp_fail(ekf_hypotheses* hy, int code, const std::string& msg) {
+  if (hy) hy->err = msg; else g_create_error = msg;
+  return code;
+}
+#define HYP_TRY(hy, expr)                                                                  \
+  do {                                                                                     \
+    hipError_t e_ = (expr);                                                                \
+    if (e_ != hipSuccess)                                                                  \
+      return hyp_fail(hy, EKF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+#define HYP_RES(hy, what, expr)                                                            \
+  do {                                                                                     \
+    const res::Status s_ = (expr);                                                         \
+    if (!s_.ok())                                                                          \
+      return hyp_fail(hy, EKF_ERR_HIP, std::string(what) + (s_.bytes ? ": allocation of " + std::to_string(s_.bytes) + " bytes" : std::string()) + \
+                                           ": " + hipGetErrorString((hipError_t)s_.err));  \
+  } while (0)
+
+static HypView hyp_view(const ekf_hypotheses* hy) {
+  return HypView{hy->dmap.p, hy->dmu.p, hy->dst.p, hy->dX.p, hy->drec.p, hy->n, hy->ld, hy->ldx, hy->count};
+}
+
+extern "C" const char* ekf_hyp_last_error(ekf_hypotheses* hy) { return hy ? hy->err.c_str() : g_create_error.c_str(); }
+
+static int hyp_free(ekf_hypotheses* hy) {
+  (void)hipSetDevice(hy->device);
+  if (hy->stream) {
+    (void)hipStreamSynchronize(hy->stream);
+    (void)hipStreamDestroy(hy->stream);
+  }
+  delete hy;
+  return EKF_OK;
+}
+
+extern "C" int ekf_hyp_destroy(ekf_hypotheses* hy) {
+  if (!hy) return EKF_ERR_ARG;
+  return hyp_free(hy);
+}
+
+// the allocations and the snapshot of ekf_hyp_create, on the handle's stream (the source's kernels run there)
+static int hyp_build(ekf_handle* h, int b, ekf_hypotheses* hy) {
+  HIP_TRY(h, hipStreamCreateWithFlags(&hy->stream, hipStreamNonBlocking));
+  const size_t K = (size_t)hy->count;
+  RES_TRY(h, "the bank's map", res::ensure_group(nullptr, res::want(hy->dmap, (size_t)hy->pstride), res::want(hy->dmu, (size_t)hy->ld)));
+  RES_TRY(h, "the hypotheses", res::ensure_group(nullptr, res::want(hy->dst, K), res::want(hy->dX, K * 3 * (size_t)hy->ldx),
+                                                 res::want(hy->drec, K), res::want(hy->dcmp, (size_t)1)));
+  HIP_TRY(h, hipMemcpyAsync(hy->dmap.p, h->dP.p + (size_t)b * h->pstride, sizeof(double) * (size_t)hy->pstride, hipMemcpyDeviceToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(hy->dmu.p, h->dmu2[h->cur].p + (size_t)b * h->ld, sizeof(double) * (size_t)hy->ld, hipMemcpyDeviceToDevice, h->stream));
+  if (h->dtagmap.p) {
+    RES_TRY(h, "the bank's tag-table row", hy->dtag.ensure((size_t)TAGMAX));
+    HIP_TRY(h, hipMemcpyAsync(hy->dtag.p, h->dtagmap.p + (size_t)b * TAGMAX, sizeof(int) * TAGMAX, hipMemcpyDeviceToDevice, h->stream));
+  }
+  launch_hyp_fill(h->stream, hyp_view(hy), nullptr, 0, hy->count, hyp_fill_groups(hy->ldx), hy->bound0);
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return EKF_OK;
+}
+
+extern "C" int ekf_hyp_create(ekf_handle* h, int b, int count, ekf_hypotheses** out) {
+  const char* fn = "ekf_hyp_create";
+  if (!h) return EKF_ERR_ARG;
+  if (!out) return bad_arg(h, fn, "NULL out");
+  *out = nullptr;
+  if (int rc = check_b(h, b, fn)) return rc;
+  if (const char* why = plan_hyp_create(h->n[b], count)) return bad_arg(h, fn, why);
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (int rc = join_aux(h)) return rc;
+  if (int rc = flush_pending(h)) return rc;
+  if (int rc = check_internal(h, b, fn)) return rc;
+  ekf_hypotheses* hy = new ekf_hypotheses();
+  hy->device = h->device;
+  hy->n = h->n[b];
+  hy->ld = h->ld;
+  hy->ldx = h->ld;
+  hy->pstride = h->pstride;
+  hy->count = count;
+  hy->cfg = h->cfg;
+  hy->bound0 = h->opt_active_bound ? std::min(h->n[b], std::max(h->neff[b], 3)) : h->n[b];
+  hy->bound_hi = hy->bound0;
+  hy->dcfg = h->dcfg;
+  hy->gate = h->dcfg.gate_rej != nullptr;
+  hy->dcfg.gate_rej = nullptr;
+  if (h->dcfg.noise) {                                   // the slot's row of the noise table, as the table holds it
+    double r[NOISE_ROW];
+    noise_row_of(h->noise_ms[(size_t)b], h->noise_qs[(size_t)b], r);
+    std::copy_n(r, 3, hy->dcfg.rd);
+    std::copy_n(r + 3, 2, hy->dcfg.qd);
+  }
+  hy->dcfg.noise = nullptr;
+  if (int rc = hyp_build(h, b, hy)) {
+    hyp_free(hy);
+    return rc;
+  }
+  *out = hy;
+  return EKF_OK;
+}
+
+extern "C" int ekf_hyp_set_nis_gate(ekf_hypotheses* hy, double threshold) {
+  if (!hy) return EKF_ERR_ARG;
+  if (!(threshold > 0.0)) return hyp_fail(hy, EKF_ERR_ARG, "ekf_hyp_set_nis_gate: the threshold must be > 0 (INFINITY: off)");
+  hy->gate = !std::isinf(threshold);
+  hy->dcfg.nis_gate = threshold;
+  return EKF_OK;
+}
+
+static int hyp_step(ekf_hypotheses* hy, const char* fn, bool pred, const double* lin, const double* ang, int motion_stride,
+                    const int* idx, const double* range, const double* bearing, const int* m, int stride, int obs_stride) {
+  if (!hy) return EKF_ERR_ARG;
+  HypStepPlan hp;
+  if (const char* why = plan_hyp_step(hy, pred, lin, ang, motion_stride, idx, range, bearing, m, stride, obs_stride, hp))
+    return hyp_fail(hy, EKF_ERR_ARG, std::string(fn) + ": " + why);
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  StepIn* hs = nullptr;
+  HYP_RES(hy, "the records", hy->recs.begin((size_t)hp.nrec, (size_t)hp.nrec, hy->stream, &hs));
+  fill_hyp_records(hy, pred, lin, ang, motion_stride, idx, range, bearing, m, stride, obs_stride, hp, hs);
+  HYP_RES(hy, "the records' upload", hy->recs.commit((size_t)hp.nrec, hy->stream));
+  hy->bound_hi = hp.bound_hi;
+  const HypView v = hyp_view(hy);
+  launch_hyp_solve(hy->stream, v, hy->recs.device(), hp.rec_stride, hy->dcfg, hy->gate);
+  launch_hyp_rows(hy->stream, v, hp.groups);
+  HYP_TRY(hy, hipGetLastError());
+  return EKF_OK;
+}
+
+extern "C" int ekf_hyp_step(ekf_hypotheses* hy, const double* lin, const double* ang, int motion_stride, const int* idx,
+                            const double* range, const double* bearing, const int* m, int stride, int obs_stride) {
+  return hyp_step(hy, "ekf_hyp_step", true, lin, ang, motion_stride, idx, range, bearing, m, stride, obs_stride);
+}
+
+extern "C" int ekf_hyp_update(ekf_hypotheses* hy, const int* idx, const double* range, const double* bearing, const int* m,
+                              int stride, int obs_stride) {
+  return hyp_step(hy, "ekf_hyp_update", false, nullptr, nullptr, 0, idx, range, bearing, m, stride, obs_stride);
+}
+
+extern "C" int ekf_hyp_reset(ekf_hypotheses* hy, int k0, int count, const double* pose, const double* cov) {
+  if (!hy) return EKF_ERR_ARG;
+  if (const char* why = plan_hyp_range(hy, k0, count)) return hyp_fail(hy, EKF_ERR_ARG, std::string("ekf_hyp_reset: ") + why);
+  if (count == 0) return EKF_OK;
+  std::vector<double> packed(12 * (size_t)count);
+  if (const char* why = plan_hyp_reset(hy, k0, count, pose, cov, packed.data()))
+    return hyp_fail(hy, EKF_ERR_ARG, std::string("ekf_hyp_reset: ") + why);
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  double* stage = nullptr;
+  HYP_RES(hy, "the reset's poses", hy->init.begin(packed.size(), packed.size(), hy->stream, &stage));
+  std::memcpy(stage, packed.data(), sizeof(double) * packed.size());
+  HYP_RES(hy, "the reset's upload", hy->init.commit(packed.size(), hy->stream));
+  launch_hyp_fill(hy->stream, hyp_view(hy), hy->init.device(), k0, count, hyp_fill_groups(hy->ldx), hy->bound0);
+  HYP_TRY(hy, hipGetLastError());
+  return EKF_OK;
+}
+
+extern "C" int ekf_hyp_sync(ekf_hypotheses* hy) {
+  if (!hy) return EKF_ERR_ARG;
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  HYP_TRY(hy, hipStreamSynchronize(hy->stream));
+  return EKF_OK;
+}
+
+// Blocking; every output may be NULL.  cov: count x 9, the block mirrored.
+extern "C" int ekf_hyp_download(ekf_hypotheses* hy, int k0, int count, double* pose, double* cov, double* loglik, long long* n_obs,
+                                long long* n_rej, unsigned* flags) {
+  if (!hy) return EKF_ERR_ARG;
+  if (const char* why = plan_hyp_range(hy, k0, count)) return hyp_fail(hy, EKF_ERR_ARG, std::string("ekf_hyp_download: ") + why);
+  if (count == 0) return EKF_OK;
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  hy->host_st.resize((size_t)count);
+  HYP_TRY(hy, hipMemcpyAsync(hy->host_st.data(), hy->dst.p + k0, sizeof(HypState) * (size_t)count, hipMemcpyDeviceToHost, hy->stream));
+  HYP_TRY(hy, hipStreamSynchronize(hy->stream));
+  for (int i = 0; i < count; ++i) {
+    const HypState& s = hy->host_st[(size_t)i];
+    if (pose) std::copy_n(s.pose, 3, pose + 3 * (size_t)i);
+    if (cov)
+      for (int a = 0; a < 3; ++a)
+        for (int c = 0; c < 3; ++c) cov[9 * (size_t)i + 3 * a + c] = s.blk[hyp_blk(std::min(a, c), std::max(a, c))];
+    if (loglik) loglik[i] = s.loglik;
+    if (n_obs) n_obs[i] = s.n_obs;
+    if (n_rej) n_rej[i] = s.n_rej;
+    if (flags) flags[i] = s.flags;
+  }
+  return EKF_OK;
+}
+
+extern "C" int ekf_hyp_download_rows(ekf_hypotheses* hy, int k, double* rows, int n) {
+  if (!hy) return EKF_ERR_ARG;
+  if (const char* why = plan_hyp_range(hy, k, 1)) return hyp_fail(hy, EKF_ERR_ARG, std::string("ekf_hyp_download_rows: ") + why);
+  if (!rows || n != hy->n) return hyp_fail(hy, EKF_ERR_ARG, "ekf_hyp_download_rows: NULL rows, or n is not the map's size");
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  HYP_TRY(hy, hipMemcpy2DAsync(rows, sizeof(double) * (size_t)n, hy->dX.p + (size_t)k * 3 * hy->ldx, sizeof(double) * (size_t)hy->ldx,
+                               sizeof(double) * (size_t)n, 3, hipMemcpyDeviceToHost, hy->stream));
+  HYP_TRY(hy, hipStreamSynchronize(hy->stream));
+  HypState s;
+  HYP_TRY(hy, hipMemcpy(&s, hy->dst.p + k, sizeof(HypState), hipMemcpyDeviceToHost));
+  for (int r = 0; r < 3; ++r)                            // (columns 0..2 of the rows are the pose block, mirrored)
+    for (int c = 0; c < 3; ++c) rows[(size_t)r * n + c] = s.blk[hyp_blk(std::min(r, c), std::max(r, c))];
+  return EKF_OK;
+}
+
+// Hypothesis k's pose, block and rows into slot b of `h`, whose frozen part must be the bank's map bit for bit.  Blocking.
+extern "C" int ekf_hyp_adopt(ekf_hypotheses* hy, int k, ekf_handle* h, int b) {
+  const char* fn = "ekf_hyp_adopt";
+  if (!hy) return EKF_ERR_ARG;
+  if (!h) return hyp_fail(hy, EKF_ERR_ARG, "ekf_hyp_adopt: NULL handle");
+  if (const char* why = plan_hyp_range(hy, k, 1)) return hyp_fail(hy, EKF_ERR_ARG, std::string(fn) + ": " + why);
+  if (int rc = check_b(h, b, fn)) return hyp_fail(hy, rc, h->err);
+  if (h->device != hy->device) return hyp_fail(hy, EKF_ERR_ARG, "ekf_hyp_adopt: the handle is on another device");
+  if (int rc = check_host_bad(h, fn)) return hyp_fail(hy, rc, h->err);
+  HIP_TRY(h, hipSetDevice(h->device));
+  HYP_TRY(hy, hipStreamSynchronize(hy->stream));
+  if (int rc = join_aux(h)) return hyp_fail(hy, rc, h->err);
+  if (int rc = flush_pending(h)) return hyp_fail(hy, rc, h->err);
+  if (h->n[b] != hy->n)
+    return hyp_fail(hy, EKF_ERR_STATE, "ekf_hyp_adopt: the slot's size " + std::to_string(h->n[b]) + " is not the map's " + std::to_string(hy->n));
+  const HypView v = hyp_view(hy);
+  double* Pb = h->dP.p + (size_t)b * h->pstride;
+  double* mub = h->dmu2[h->cur].p + (size_t)b * h->ld;
+  unsigned mismatch = 0;
+  HYP_TRY(hy, hipMemsetAsync(hy->dcmp.p, 0, sizeof(unsigned), h->stream));
+  launch_hyp_compare(h->stream, v, Pb, mub, h->ld, hyp_compare_groups(hy->n), hy->dcmp.p);
+  HYP_TRY(hy, hipGetLastError());
+  HYP_TRY(hy, hipMemcpyAsync(&mismatch, hy->dcmp.p, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+  HypState s;
+  HYP_TRY(hy, hipMemcpyAsync(&s, hy->dst.p + k, sizeof(HypState), hipMemcpyDeviceToHost, h->stream));
+  HYP_TRY(hy, hipStreamSynchronize(h->stream));
+  if (mismatch)
+    return hyp_fail(hy, EKF_ERR_STATE, "ekf_hyp_adopt: the slot's frozen part is not the bank's map: " + std::to_string(mismatch) +
+                                           " of its landmark means and stored entries P(a, b), a, b >= 3, differ; nothing was written");
+  const int bound = std::min(h->n[b], std::max(h->neff[b], s.bound));
+  launch_hyp_adopt(h->stream, v, k, Pb, mub, h->ld, h->dso.p + b, bound, hyp_adopt_groups(hy->n));
+  HYP_TRY(hy, hipGetLastError());
+  h->neff[b] = bound;
+  h->neff_enq[b] = h->opt_active_bound ? h->neff[b] : h->n[b];
+  HYP_TRY(hy, hipStreamSynchronize(h->stream));
+  return EKF_OK;
+}

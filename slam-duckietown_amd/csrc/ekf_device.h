@@ -95,6 +95,30 @@ struct alignas(16) LocRec {
   double pad;
 };
 static_assert(sizeof(LocRec) == 928 && sizeof(LocRec) % 16 == 0, "LocRec is 928 bytes");
+// ekf_hyp_* (ekf_hypotheses.hip): a bank of K pose hypotheses on ONE frozen map.  The map is a copy of a slot's stored triangle in
+// the handle's layout (p_index / p_col / p_lds with the handle's ld) and of its mean; a hypothesis is this record plus its pose
+// rows X[3][ldx] (P(r, c) at X[r * ldx + c], zero at and beyond its bound) and the LocRec its solve hands to its row launch.
+// blk: the pose block's stored entries (0,0) (0,1) (0,2) (1,1) (1,2) (2,2).  loglik: the sum over every observation the
+// hypothesis has seen, gated out or not, of -1/2 (y^T S^-1 y + ln det S + 2 ln 2 pi) (terms that are not finite are left out,
+// as evaluation.nis_consistency leaves them out); n_obs / n_rej count the observations and the gate's rejections.
+struct alignas(16) HypState {
+  double pose[3];
+  double blk[6];
+  double loglik;
+  long long n_obs, n_rej;
+  unsigned flags;
+  int bound;
+  double pad;
+};
+static_assert(sizeof(HypState) == 112, "HypState is 112 bytes");
+__host__ __device__ constexpr int hyp_blk(int lo, int hi) { return 3 * lo - lo * (lo - 1) / 2 + (hi - lo); }
+constexpr int HYP_THREADS = LOC_THREADS;   // k_hyp_rows / k_hyp_seed / k_hyp_reset / k_hyp_adopt: columns per workgroup
+constexpr int HYP_CMP_THREADS = 256;       // k_hyp_compare: columns per workgroup, one row per blockIdx.y
+// What the bank's launches take: the shared map (read only behind the seed), its mean, and the hypotheses' arrays.
+struct HypView {
+  const double* map; const double* mu; HypState* st; double* X; LocRec* rec;
+  int n, ld, ldx, count;
+};
 __host__ __device__ __forceinline__ int p_lds(int ld) { return ld < PPW ? ld : PPW; }
 __host__ __device__ __forceinline__ long p_col(int ld, int j) { return (long)(j >> 12) * ((long)ld * PPW) + (j & (PPW - 1)); }
 // the same as a 32-bit byte offset (ekf_create bounds one covariance by 4 GiB)

@@ -1068,6 +1068,110 @@ inline const char* plan_localize_detections(const HostPlan* h, const double* lin
   return nullptr;
 }
 
+// ---- the hypothesis bank (ekf_hyp_*: k_hyp_solve + k_hyp_rows, k_hyp_fill, k_hyp_compare, k_hyp_adopt; ekf_hypotheses.hip) ----
+// What the planning functions read of a bank (ekf_hypotheses derives from this): the map's size and layout (the source handle's
+// ld), the stride of a hypothesis's pose rows, the number of hypotheses, the map's active bound at creation (what a reset puts
+// back) and an upper bound of every hypothesis's bound (the device raises them; this mirror only sizes k_hyp_rows' grid).
+inline void fill_step(StepIn& s, int n_b, int& bound, double lin, double ang, int flags, const int* idx, const double* range,
+                      const double* bearing, int m, int p);
+struct HypBank {
+  int device = 0, n = 0, ld = 0, ldx = 0, count = 0;
+  long pstride = 0;
+  ekf_config cfg{};
+  int bound0 = 3, bound_hi = 3;
+};
+constexpr int HYP_COUNT_MAX = 1 << 16;                   // hypotheses of one bank (a grid dimension of the bank's launches)
+// the bytes a hypothesis costs: its record, its three pose rows, its solve's record
+inline size_t hyp_bytes_per(int ldx) { return sizeof(HypState) + 3 * sizeof(double) * (size_t)ldx + sizeof(LocRec); }
+inline int hyp_fill_groups(int ldx) { return (std::max(ldx, 1) + HYP_THREADS - 1) / HYP_THREADS; }
+inline int hyp_adopt_groups(int n) { return (std::max(n, 1) + HYP_THREADS - 1) / HYP_THREADS; }
+inline int hyp_compare_groups(int n) { return (std::max(n, 1) + HYP_CMP_THREADS - 1) / HYP_CMP_THREADS; }
+inline const char* plan_hyp_create(int n, int count) {
+  if (count < 1 || count > HYP_COUNT_MAX) return "count must be in [1, 65536]";
+  if (n < 3 || (n - 3) % 2 != 0) return "the source slot's size is not 3 + 2 N";
+  return nullptr;
+}
+inline const char* plan_hyp_range(const HypBank* hy, int k0, int count) {
+  if (k0 < 0 || count < 0 || k0 > hy->count || count > hy->count - k0) return "hypothesis range outside the bank";
+  return nullptr;
+}
+// A step / an update of the bank checked as plan_localize checks a slot's -- in its order, an index may come twice -- with the two
+// stride modes: motion_stride 0 = one (lin, ang) for every hypothesis, 1 = one each; obs_stride 0 = one list (m[0] observations at
+// idx / range / bearing [0, m[0])) for every hypothesis, 1 = hypothesis k's m[k] observations at [k * stride, k * stride + m[k]).
+// A list longer than EKF_MMAX is refused: the caller splits it into a step and update-only calls.  What the call launches: nrec
+// records (one where both modes are 0, else one per hypothesis), rec_stride between the records k_hyp_solve reads, and
+// k_hyp_rows' column groups up to bound_hi, the bank's bound raised over the highest landmark named.
+// Returns nullptr, or what is wrong (then nothing of `hp` is to be used and nothing has changed).
+struct HypStepPlan {
+  int nrec = 1, rec_stride = 0, m_hi = 0, bound_hi = 3, groups = 1;
+};
+inline const char* plan_hyp_step(const HypBank* hy, bool pred, const double* lin, const double* ang, int motion_stride, const int* idx,
+                                 const double* range, const double* bearing, const int* m, int stride, int obs_stride,
+                                 HypStepPlan& hp) {
+  if (pred && (!lin || !ang)) return "NULL lin/ang";
+  if (pred && motion_stride != 0 && motion_stride != 1) return "motion_stride must be 0 (shared) or 1 (one per hypothesis)";
+  if (!m || stride < 0) return "NULL m / bad stride";
+  if (obs_stride != 0 && obs_stride != 1) return "obs_stride must be 0 (shared) or 1 (one list per hypothesis)";
+  const int lists = obs_stride ? hy->count : 1;
+  const bool meas = hy->cfg.enable_measurement_model != 0;
+  hp.m_hi = 0;
+  if (meas)
+    for (int k = 0; k < lists; ++k) {
+      if (m[k] < 0 || m[k] > stride) return "m[k] must be in [0, stride]";
+      if (m[k] > MMAX) return "more than EKF_MMAX observations in one call: split the list into a step and update-only calls";
+      hp.m_hi = std::max(hp.m_hi, m[k]);
+    }
+  if (hp.m_hi > 0 && (!idx || !range || !bearing)) return "NULL observation arrays";
+  int id_hi = -1;
+  if (hp.m_hi > 0) {
+    const int n_lm = (hy->n - 3) / 2;
+    for (int k = 0; k < lists; ++k)
+      for (int i = 0; i < m[k]; ++i) {
+        const int id = idx[(long)k * stride + i];
+        if (id < 0 || id >= n_lm) return "landmark index outside the map";
+        id_hi = std::max(id_hi, id);
+      }
+  }
+  const bool per = (pred && motion_stride == 1) || obs_stride == 1;
+  hp.nrec = per ? hy->count : 1;
+  hp.rec_stride = per ? 1 : 0;
+  hp.bound_hi = std::min(hy->n, std::max(hy->bound_hi, 3 + 2 * (id_hi + 1)));
+  hp.groups = loc_rows_groups(hp.bound_hi);
+  return nullptr;
+}
+// The hp.nrec records of a planned call (the bound travels on the device: StepIn::neff is not read)
+inline void fill_hyp_records(const HypBank* hy, bool pred, const double* lin, const double* ang, int motion_stride, const int* idx,
+                             const double* range, const double* bearing, const int* m, int stride, int obs_stride,
+                             const HypStepPlan& hp, StepIn* out) {
+  const bool meas = hy->cfg.enable_measurement_model != 0;
+  for (int k = 0; k < hp.nrec; ++k) {
+    const int km = pred ? k * motion_stride : 0, ko = k * obs_stride;
+    const long off = (long)ko * stride;
+    int unused = 3;
+    fill_step(out[k], hy->n, unused, pred ? lin[km] : 0.0, pred ? ang[km] : 0.0, FLAG_UPDATE | (pred ? FLAG_PREDICT : 0),
+              idx ? idx + off : nullptr, range ? range + off : nullptr, bearing ? bearing + off : nullptr, meas ? m[ko] : 0, 0);
+  }
+}
+// ekf_hyp_reset's arguments: count poses and count 3 x 3 covariances (row-major; the upper triangle is read), finite, no negative
+// variance; packs k_hyp_fill's count x 12 doubles into `init`.
+inline const char* plan_hyp_reset(const HypBank* hy, int k0, int count, const double* pose, const double* cov, double* init) {
+  if (const char* why = plan_hyp_range(hy, k0, count)) return why;
+  if (count > 0 && (!pose || !cov)) return "NULL pose or cov";
+  for (int i = 0; i < count; ++i)
+    for (int a = 0; a < 3; ++a) {
+      if (!std::isfinite(pose[3 * (size_t)i + a])) return "non-finite pose";
+      for (int c = a; c < 3; ++c)
+        if (!std::isfinite(cov[9 * (size_t)i + 3 * a + c])) return "non-finite cov";
+      if (cov[9 * (size_t)i + 4 * a] < 0.0) return "cov has a negative diagonal entry";
+    }
+  for (int i = 0; i < count; ++i) {
+    std::copy_n(pose + 3 * (size_t)i, 3, init + 12 * (size_t)i);
+    for (int a = 0; a < 3; ++a)
+      for (int c = 0; c < 3; ++c) init[12 * (size_t)i + 3 + 3 * a + c] = cov[9 * (size_t)i + 3 * std::min(a, c) + std::max(a, c)];
+  }
+  return nullptr;
+}
+
 // ekf_copy_trajectories (k_copy_traj, ekf_copy.hip): the k pairs (src_b[i] of `src` -> dst_b[i] of `dst`) checked -- indices
 // inside their banks, no destination twice, inside one handle no trajectory both read and written, the same device, every
 // source's size within the destination's n_max -- and grouped by source: a group is one source and up to COPY_FANOUT of its

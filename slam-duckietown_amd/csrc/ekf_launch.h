@@ -105,7 +105,7 @@ void launch_factor_solve(hipStream_t st, const FactorView& w, int f0, int count,
                          double* white, double* quad);
 void launch_factor_multiply(hipStream_t st, const FactorView& w, int f0, int count, int nblk_hi, const double* z, int nrhs,
                             int stride, double* out);
-// ---- state surgery (ekf_remove.hip, ekf_direct.hip, ekf_linear.hip, ekf_predict_linear.hip, ekf_localize.hip, ekf_loc_assoc.hip, ekf_copy.hip, ekf_join.hip, ekf_transform.hip, ekf_dense.hip) ----
+// ---- state surgery (ekf_remove.hip, ekf_direct.hip, ekf_linear.hip, ekf_predict_linear.hip, ekf_localize.hip, ekf_loc_assoc.hip, ekf_hypotheses.hip, ekf_copy.hip, ekf_join.hip, ekf_transform.hip, ekf_dense.hip) ----
 // rp.rows: the launch's largest new size (grid rows); nb trajectories from b0; src / dst: rp's tables on the device
 void launch_remove(hipStream_t st, const BankView& k, double* mu, const RemovePlan& rp, const int* src, const int* dst,
                    unsigned* rflag, int b0, int nb, unsigned seq);
@@ -130,6 +130,15 @@ void launch_loc_rows(hipStream_t st, const BankView& k, const LocRec* rec, int g
 // neff_dev[b] (raised over the matched landmarks) and k.flags -- nothing else
 void launch_loc_associate(hipStream_t st, const BankView& k, const DetIn* det, const int* tagmap, int* neff_dev, const double* mu,
                           StepIn* step_out, AssocOut* assoc_out, LocUnmatched* unmatched, const AssocConfig& cfg);
+// ---- the hypothesis bank (ekf_hypotheses.hip); v: the bank (ekf_device.h: HypView), every shape from ekf_host_plan.h's plan_hyp_* ----
+// one StepIn for all hypotheses (rec_stride 0) or one each (1); the solve leaves v.rec, the row launch behind it applies them
+void launch_hyp_solve(hipStream_t st, const HypView& v, const StepIn* in, int rec_stride, const DeviceConfig& cfg, bool gate);
+void launch_hyp_rows(hipStream_t st, const HypView& v, int groups);
+// hypotheses [k0, k0 + count): init = nullptr seeds them from the map copy's pose part, else count x 12 doubles {pose, cov}
+void launch_hyp_fill(hipStream_t st, const HypView& v, const double* init, int k0, int count, int groups, int bound0);
+// the bank's map against a slot's P_base / mean (layout ldb): *mismatch += entries whose bits differ
+void launch_hyp_compare(hipStream_t st, const HypView& v, const double* Pb, const double* mub, int ldb, int groups, unsigned* mismatch);
+void launch_hyp_adopt(hipStream_t st, const HypView& v, int k, double* Pb, double* mub, int ldb, SolveOut* so_b, int bound, int groups);
 // groups x (tiles of the largest source + 1) workgroups; tab: plan_copy's table on the device
 void launch_copy_traj(hipStream_t st, bool nt, const BankView& src, const BankView& dst, const double* mus, double* mud,
                       const int* tab, int groups, int n_hi);

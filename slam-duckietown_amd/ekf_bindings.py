@@ -158,6 +158,18 @@ ABI = {
     "ekf_upload_tag_index": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_int]),
     "ekf_localize_detections": (C.c_int, [C.c_void_p, _dp, _dp, _ip, _ip, _dp, _dp, C.c_int]),
     "ekf_download_unmatched": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, C.c_int]),
+    "ekf_hyp_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "ekf_hyp_destroy": (C.c_int, [C.c_void_p]),
+    "ekf_hyp_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
+    "ekf_hyp_step": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _ip, _dp, _dp, _ip, C.c_int, C.c_int]),
+    "ekf_hyp_update": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _ip, C.c_int, C.c_int]),
+    "ekf_hyp_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                   C.POINTER(C.c_uint)]),
+    "ekf_hyp_download_rows": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int]),
+    "ekf_hyp_set_nis_gate": (C.c_int, [C.c_void_p, C.c_double]),
+    "ekf_hyp_adopt": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "ekf_hyp_sync": (C.c_int, [C.c_void_p]),
+    "ekf_hyp_last_error": (C.c_char_p, [C.c_void_p]),
     "ekf_stream_upload": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
     "ekf_stream_run": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ekf_run_stream": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
@@ -481,6 +493,176 @@ class CovFactor:
         draws = (z[0] if self._single else z)
         out = self.multiply(draws)
         return out + (means[0] if self._single else means)
+
+
+class HypothesisBank:
+    """``count`` pose hypotheses localising on ONE frozen map (``EkfSlam.hypotheses``; ``ekf_hyp_*``): the map -- a snapshot of a
+    slot's landmark means and of every P[a, b] with a, b >= 3 -- is stored once, a hypothesis is its pose mean, pose block and
+    pose rows P[0:3, :].  Every hypothesis steps with ``EkfSlam.localize``'s arithmetic and ends with ``localize``'s bits;
+    each accumulates the log-likelihood of its innovations on the device.  Stepping calls are asynchronous on the bank's stream;
+    the reads block.  Close it (or use it as a context manager) to release the device memory."""
+
+    def __init__(self, lib, handle, count: int, n: int):
+        self._lib, self._h = lib, handle
+        self.count, self.n = int(count), int(n)
+
+    # -- plumbing ------------------------------------------------------------------------------
+    def _live(self):
+        if not (getattr(self, "_h", None) and self._h.value):
+            raise EkfError("the hypothesis bank has been closed")
+        return self._h
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise EkfError(f"status {rc}: {self._lib.ekf_hyp_last_error(self._h).decode()}")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.ekf_hyp_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _motion(self, lin, ang):
+        """(lin, ang, motion_stride): scalars are shared by every hypothesis, arrays of ``count`` give one pair each."""
+        lin, ang = np.atleast_1d(_f64(lin)).ravel(), np.atleast_1d(_f64(ang)).ravel()
+        if len(lin) == 1 and len(ang) == 1:
+            return lin, ang, 0
+        lin, ang = np.broadcast_to(lin, (self.count,)).copy(), np.broadcast_to(ang, (self.count,)).copy()
+        return lin, ang, 1
+
+    def _obs(self, idx, ranges, bearings):
+        """(idx, ranges, bearings, m, obs_stride) as padded 2-D arrays: one flat list is shared by every hypothesis; a list of
+        ``count`` lists (or [count, m] arrays) gives one list each."""
+        shared = len(idx) == 0 or np.ndim(idx[0]) == 0
+        lists = [(idx, ranges, bearings)] if shared else list(zip(idx, ranges, bearings))
+        if not shared and len(lists) != self.count:
+            raise ValueError(f"observations: one list for all, or {self.count} lists expected")
+        lens = [len(i) for i, _, _ in lists]
+        I = np.zeros((len(lists), max(1, max(lens))), dtype=np.int32)
+        R, B = np.zeros(I.shape), np.zeros(I.shape)
+        for k, (i, r, b) in enumerate(lists):
+            if len(r) != lens[k] or len(b) != lens[k]:
+                raise ValueError("idx / ranges / bearings lengths differ")
+            I[k, :lens[k]], R[k, :lens[k]], B[k, :lens[k]] = i, r, b
+        return I, R, B, np.asarray(lens, dtype=np.int32), 0 if shared else 1
+
+    def _passes(self, I, R, B, m):
+        """The padded lists cut into passes of at most EKF_MMAX observations (the library takes one pass per call)."""
+        for lo in range(0, max(1, int(m.max())), EKF_MMAX):
+            mp = np.clip(m - lo, 0, EKF_MMAX).astype(np.int32)
+            w = max(1, int(mp.max()))
+            yield (np.ascontiguousarray(I[:, lo:lo + w]), np.ascontiguousarray(R[:, lo:lo + w]),
+                   np.ascontiguousarray(B[:, lo:lo + w]), mp, w)
+
+    # -- the filter ----------------------------------------------------------------------------
+    def step(self, lin, ang, idx, ranges, bearings):
+        """``EkfSlam.localize`` for every hypothesis.  ``lin`` / ``ang``: scalars (one motion for all) or ``count`` values;
+        observations: one flat list for all (tags carry their ids: the common case) or one list per hypothesis.  More than
+        EKF_MMAX observations run as a step plus update-only calls, as ``localize`` runs them."""
+        h = self._live()
+        lin, ang, ms = self._motion(lin, ang)
+        I, R, B, m, os_ = self._obs(idx, ranges, bearings)
+        for p, (Ip, Rp, Bp, mp, w) in enumerate(self._passes(I, R, B, m)):
+            if p == 0:
+                self._check(self._lib.ekf_hyp_step(h, _p(lin), _p(ang), ms, _p(Ip, _ip), _p(Rp), _p(Bp), _p(mp, _ip), w, os_))
+            else:
+                self._check(self._lib.ekf_hyp_update(h, _p(Ip, _ip), _p(Rp), _p(Bp), _p(mp, _ip), w, os_))
+
+    def update(self, idx, ranges, bearings):
+        """``EkfSlam.localize_update`` for every hypothesis (observations as for ``step``)."""
+        h = self._live()
+        I, R, B, m, os_ = self._obs(idx, ranges, bearings)
+        for Ip, Rp, Bp, mp, w in self._passes(I, R, B, m):
+            self._check(self._lib.ekf_hyp_update(h, _p(Ip, _ip), _p(Rp), _p(Bp), _p(mp, _ip), w, os_))
+
+    def reset(self, poses, cov, k=None):
+        """``EkfSlam.reset_pose`` for hypotheses: pose means ``poses`` ((count, 3), or one for all), pose blocks ``cov`` ((3, 3)
+        for all, or (count, 3, 3)), every pose-landmark cross term dropped, log-likelihood and counters cleared.  ``k`` None:
+        the whole bank; an int: that hypothesis; (k0, count): a range."""
+        h = self._live()
+        k0, cnt = (0, self.count) if k is None else ((int(k), 1) if np.ndim(k) == 0 else (int(k[0]), int(k[1])))
+        poses = np.ascontiguousarray(np.broadcast_to(_f64(poses), (max(cnt, 0), 3)))
+        cov = np.ascontiguousarray(np.broadcast_to(_f64(cov), (max(cnt, 0), 3, 3)))
+        self._check(self._lib.ekf_hyp_reset(h, k0, cnt, _p(poses), _p(cov)))
+
+    def _download(self):
+        h = self._live()
+        K = self.count
+        pose, cov, ll = np.empty((K, 3)), np.empty((K, 3, 3)), np.empty(K)
+        nobs, nrej, fl = np.empty(K, dtype=np.int64), np.empty(K, dtype=np.int64), np.empty(K, dtype=np.uint32)
+        self._check(self._lib.ekf_hyp_download(h, 0, K, _p(pose), _p(cov), _p(ll), _p(nobs, C.POINTER(C.c_longlong)),
+                                               _p(nrej, C.POINTER(C.c_longlong)), _p(fl, C.POINTER(C.c_uint))))
+        return pose, cov, ll, nobs, nrej, fl
+
+    def poses(self):
+        """(mean (count, 3), cov (count, 3, 3)) of every hypothesis."""
+        pose, cov = self._download()[:2]
+        return pose, cov
+
+    @property
+    def loglik(self) -> np.ndarray:
+        """Per hypothesis, the Gaussian log-likelihood of every innovation it has seen since its seed or last reset, gated out
+        or not: the sum ``evaluation.nis_consistency`` forms from an innovation log."""
+        return self._download()[2]
+
+    @property
+    def observed(self) -> np.ndarray:
+        return self._download()[3]
+
+    @property
+    def rejected(self) -> np.ndarray:
+        """Per hypothesis, the observations the NIS gate rejected (``EkfSlam.gate_counts`` of a slot)."""
+        return self._download()[4]
+
+    def flags(self) -> np.ndarray:
+        return self._download()[5]
+
+    def rows(self, k: int) -> np.ndarray:
+        """Hypothesis k's P[0:3, :] (3, n): the pose block, then the pose-landmark cross terms."""
+        out = np.empty((3, self.n))
+        self._check(self._lib.ekf_hyp_download_rows(self._live(), int(k), _p(out), self.n))
+        return out
+
+    @staticmethod
+    def weights_of(loglik) -> np.ndarray:
+        """exp(loglik - max), normalised: the posterior weights of hypotheses with equal priors.  -inf and NaN weigh nothing;
+        with no finite log-likelihood (or a +inf) the weight is shared equally among the largest."""
+        ll = np.asarray(loglik, dtype=np.float64)
+        ll = np.where(np.isnan(ll), -np.inf, ll)
+        top = ll.max() if ll.size else 0.0
+        w = (ll == top).astype(np.float64) if np.isinf(top) else np.exp(ll - top)
+        return w / w.sum() if ll.size else w
+
+    def weights(self) -> np.ndarray:
+        return self.weights_of(self.loglik)
+
+    def best(self) -> int:
+        """The hypothesis with the largest log-likelihood (the first of equals)."""
+        return int(np.argmax(self.weights()))
+
+    def adopt(self, k: int, f: "EkfSlam", b: int = 0):
+        """Hypothesis k's pose, pose block and pose rows into trajectory ``b`` of ``f``, whose landmark means and P[3:, 3:] must
+        be the bank's map bit for bit (a fork of the slot the bank was made from): checked on the device first; on a
+        difference ``EkfError`` and nothing written."""
+        self._check(self._lib.ekf_hyp_adopt(self._live(), int(k), f._h, int(b)))
+
+    def set_nis_gate(self, threshold: Optional[float] = None, confidence: Optional[float] = None):
+        """``EkfSlam.set_nis_gate`` for the bank; rejections are counted per hypothesis (``rejected``)."""
+        self._check(self._lib.ekf_hyp_set_nis_gate(self._live(), EkfSlam.nis_gate_threshold(threshold, confidence)))
+
+    def sync(self):
+        self._check(self._lib.ekf_hyp_sync(self._live()))
 
 
 class EkfSlam:
@@ -1593,6 +1775,16 @@ class EkfSlam:
         bank (``pose`` (B, 3) or one for all), ``b`` given that trajectory alone."""
         count = self.batch if b is None else 1
         self.predict_linear(np.broadcast_to(np.asarray(pose, dtype=np.float64), (count, 3)), np.zeros((3, 3)), cov, b=b)
+
+    def hypotheses(self, count: int, b: int = 0) -> "HypothesisBank":
+        """A bank of ``count`` pose hypotheses on trajectory b's map as it stands now (``ekf_hyp_create``): the map is copied
+        once -- nothing this filter does afterwards reaches the bank --, every hypothesis starts from b's pose, and the bank
+        takes this filter's config, b's noise pair and the NIS gate.  Seed them with ``HypothesisBank.reset``
+        (``frontend.poses_on_circle``), step them, rank them (``evaluation.resolve_hypotheses``) and write the winner back with
+        ``HypothesisBank.adopt``."""
+        hy = C.c_void_p()
+        self._check(self._lib.ekf_hyp_create(self._h, int(b), int(count), C.byref(hy)))
+        return HypothesisBank(self._lib, hy, count, self.size(b))
 
     def _step_detections_host(self, lin, ang, detections):
         """The same window through the host association (see step_detections): what the reference does at :280-360 with

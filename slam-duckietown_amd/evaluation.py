@@ -347,6 +347,35 @@ def nis_consistency(innov, confidence: float = 0.95) -> NisConsistency:
                           loglik, total)
 
 
+class HypothesisResolution(NamedTuple):
+    best: int                        # the hypothesis with the largest log-likelihood (the first of equals)
+    weight: float                    # its normalised weight exp(loglik - max) / sum
+    separated: bool                  # the runner-up's weight is below (1 - confidence) x the best's
+    runner_up: int                   # the second-best hypothesis (-1 in a bank of one)
+    ratio: float                     # runner-up weight / best weight (0 in a bank of one)
+
+
+def resolve_hypotheses(bank, confidence: float = 0.99) -> HypothesisResolution:
+    """Has a hypothesis bank (``EkfSlam.hypotheses``; or an array of log-likelihoods) settled on one pose?  The best hypothesis,
+    its posterior weight under equal priors, and whether it is SEPARATED: the runner-up's weight, relative to the best's, is
+    below ``1 - confidence``.  Hypotheses without a finite log-likelihood weigh nothing; equal log-likelihoods are never
+    separated."""
+    from .ekf_bindings import HypothesisBank
+    if not 0.0 < float(confidence) < 1.0:
+        raise ValueError(f"resolve_hypotheses: confidence must lie in (0, 1), got {confidence!r}")
+    w = HypothesisBank.weights_of(bank.loglik if hasattr(bank, "loglik") else bank)
+    if w.size == 0:
+        raise ValueError("resolve_hypotheses: an empty bank")
+    best = int(np.argmax(w))
+    if w.size == 1:
+        return HypothesisResolution(best, float(w[best]), True, -1, 0.0)
+    rest = w.copy()
+    rest[best] = -1.0
+    second = int(np.argmax(rest))
+    ratio = float(w[second] / w[best])
+    return HypothesisResolution(best, float(w[best]), ratio < 1.0 - float(confidence), second, ratio)
+
+
 class LandmarkRejections(NamedTuple):
     applied: np.ndarray              # (B, L) int64: updates of landmark l that trajectory b applied
     rejected: np.ndarray             # (B, L) int64: ... that the NIS gate rejected (L = largest logged index + 1)

@@ -219,6 +219,20 @@ def wrap_pi(a):
     return (a + np.pi) % (2.0 * np.pi) - np.pi
 
 
+def poses_on_circle(landmark_xy, range_, bearing, count: int) -> np.ndarray:
+    """The ``count`` poses (count, 3) consistent with ONE range/bearing sighting of a landmark at a known position: positions on
+    the circle of radius ``range_`` around it, headings evenly spaced over [-pi, pi) -- heading theta puts the robot at
+    landmark - range (cos(theta + bearing), sin(theta + bearing)).  The seeding of a kidnapped robot's hypotheses
+    (``HypothesisBank.reset``); neighbours are 2 pi / count apart in heading."""
+    count = int(count)
+    if count < 1:
+        raise ValueError("poses_on_circle: count must be >= 1")
+    lm = np.asarray(landmark_xy, dtype=np.float64).reshape(2)
+    th = -np.pi + 2.0 * np.pi * np.arange(count) / count
+    a = th + float(bearing)
+    return np.stack([lm[0] - float(range_) * np.cos(a), lm[1] - float(range_) * np.sin(a), th], axis=1)
+
+
 def measurement_h(pose, landmark_xy):
     """Range/bearing model of one landmark seen from ``pose`` (x, y, theta): ``(zhat (2,), H5 (2, 5))``, the predicted
     observation and its Jacobian on (x, y, theta, lx, ly) -- src/replay_no_ros.py:443-469 as the device evaluates them
