@@ -656,7 +656,29 @@ int ekf_download_unmatched(ekf_handle *h, int b, int *m, int *tag_id, int capaci
  * hypothesis's.
  * Every call returns EKF_ERR_ARG for a NULL bank, a range outside it or a bad argument, with nothing changed; the message is in
  * ekf_hyp_last_error.  Not part of a bank: raw detections, likelihood association per hypothesis, the innovation and pose logs,
- * per-hypothesis noise, resampling. */
+ * per-hypothesis noise.
+ * ekf_hypotheses_weigh / ekf_hypotheses_resample (their errors too go to ekf_hyp_last_error) keep a bank running: the weights'
+ * statistics and a systematic resampling ON THE DEVICE -- the pose rows are what moves, 393 MB at count = 4096, N = 2000.  Every
+ * output of both may be NULL; a call blocks exactly when one is not, else it is asynchronous on the bank's stream like ekf_hyp_step.
+ * Their scratch -- 20 bytes per hypothesis -- is allocated at the first call of either.
+ * Weights: w_k ~ exp(loglik_k - max) over the hypotheses whose log-likelihood is finite and whose sticky EKF_FLAG_NONFINITE is
+ * clear; the others weigh nothing.  live = the hypotheses with w_k > 0, ess = (sum w)^2 / sum w^2, logmean = max + ln sum
+ * exp(loglik - max) - ln count, the bank's evidence under equal priors.  A degenerate bank (nothing weighs): ess = 0, live = 0,
+ * logmean = -inf, and resampling it is the identity: nothing is written, ancestors[k] = k, offspring[k] = 1.
+ * Resampling with the offset u in [0, 1): with C_k the inclusive cumulative sum of the normalised weights, t_k = clamp(ceil(count
+ * C_k - u), 0, count), t = count from the last live hypothesis on, offspring[k] = t_k - t_(k-1).  Survivors stay in place
+ * (ancestors[k] = k wherever offspring[k] >= 1); the i-th dead slot in ascending order takes the i-th entry of the list in which
+ * each ancestor, ascending, appears offspring - 1 times: its pose, block, bound, flags, n_obs, n_rej and pose rows, bit for bit.
+ * Every hypothesis's loglik becomes logmean: the weights are uniform afterwards and the evidence carries on.
+ * split = s in (0, 1) makes the copies useful (deterministic filters would stay identical for ever): every slot whose ancestor has
+ * two or more offspring -- the survivor too -- moves its pose mean by s L z_k (L: the lower Cholesky factor of its pose block, a
+ * pivot <= 0 or not finite zeroing its column; z: count x 3 standard normal draws, the caller's) and keeps (1 - s^2) of its pose
+ * block and pose rows: localize's Schmidt-Kalman update for a pose fix drawn from the ancestor's own distribution, so the
+ * children's mixture has the ancestor's pose marginal and the map stays frozen.  The heading is not wrapped; no log-likelihood
+ * term is added; slots of ancestors with one offspring stay bit for bit.  Refused (EKF_ERR_ARG, nothing changed): u outside
+ * [0, 1) or not finite, split outside [0, 1), split > 0 with NULL or non-finite z, z given with split == 0.
+ * Measured on one MI355X (tools/hyp_resample_time.py, profiles/hyp_resample.txt; N = 2000, call + sync with every output NULL):
+ * count = 4096 at ess = count / 2 105 us, 182 with a split; 4095 copies of one source 114 and 250; ekf_hyp_step there: 657. */
 typedef struct ekf_hypotheses ekf_hypotheses;
 int ekf_hyp_create(ekf_handle *h, int b, int count, ekf_hypotheses **out);
 int ekf_hyp_destroy(ekf_hypotheses *hy);
@@ -672,6 +694,9 @@ int ekf_hyp_set_nis_gate(ekf_hypotheses *hy, double threshold);
 int ekf_hyp_adopt(ekf_hypotheses *hy, int k, ekf_handle *h, int b);
 int ekf_hyp_sync(ekf_hypotheses *hy);
 const char *ekf_hyp_last_error(ekf_hypotheses *hy);
+int ekf_hypotheses_weigh(ekf_hypotheses *hy, double *ess, double *logmean, int *live);
+int ekf_hypotheses_resample(ekf_hypotheses *hy, double u, double split, const double *z /* count x 3, or NULL iff split == 0 */,
+                            int *ancestors /* count */, int *offspring /* count */, double *ess, double *logmean);
 
 /* Streams of pre-uploaded inputs ([step][batch] and [step][batch][stride] arrays, stride <= EKF_MMAX; m[step][batch] landmarks
  * each -- any count per step and trajectory, 0 included: what the windows of src/replay_no_ros.py:280-301 hold).

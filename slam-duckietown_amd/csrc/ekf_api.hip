@@ -3152,6 +3152,10 @@ struct ekf_hypotheses : ekf::HypBank {
   StagedUpload<StepIn> recs;      // a call's records: the pinned copy is rewritten once the previous upload has run
   StagedUpload<double> init;      // ekf_hyp_reset's poses and covariances
   DeviceBuf<unsigned> dcmp;       // ekf_hyp_adopt: the compare's mismatch count
+  DeviceBuf<HypWeighOut> dhead;   // ekf_hypotheses_weigh / _resample (made at the first of either): the weights' header,
+  DeviceBuf<double> dw;           // the weights,
+  DeviceBuf<int> dplan;           // ancestors, offspring and the surplus scan (hyp_resample_ints)
+  HypWeighOut host_head{};
   std::vector<HypState> host_st;
   std::string err;
 };
@@ -3389,4 +3393,68 @@ extern "C" int ekf_hyp_adopt(ekf_hypotheses* hy, int k, ekf_handle* h, int b) {
   h->neff_enq[b] = h->opt_active_bound ? h->neff[b] : h->n[b];
   HYP_TRY(hy, hipStreamSynchronize(h->stream));
   return EKF_OK;
+}
+
+// ---- weights and resampling (k_hyp_weigh, k_hyp_plan, k_hyp_copy, k_hyp_split; shapes: plan_hyp_resample) ----
+// The scratch of both calls, made at the first: a header, count weights, 3 count ints.
+static int hyp_resample_view(ekf_hypotheses* hy, HypResampleView& rs) {
+  const size_t K = (size_t)hy->count;
+  HYP_RES(hy, "the resampling's scratch", res::ensure_group(nullptr, res::want(hy->dhead, (size_t)1), res::want(hy->dw, K),
+                                                            res::want(hy->dplan, hyp_resample_ints(hy->count))));
+  rs = HypResampleView{hy->dhead.p, hy->dw.p, hy->dplan.p, hy->dplan.p + K, hy->dplan.p + 2 * K};
+  return EKF_OK;
+}
+
+// the header into ess / logmean / live, the plan into ancestors / offspring: blocks if any of them is asked for
+static int hyp_resample_outputs(ekf_hypotheses* hy, const HypResampleView& rs, int* ancestors, int* offspring, double* ess,
+                                double* logmean, int* live) {
+  if (!ancestors && !offspring && !ess && !logmean && !live) return EKF_OK;
+  const size_t K = (size_t)hy->count;
+  if (ess || logmean || live)
+    HYP_TRY(hy, hipMemcpyAsync(&hy->host_head, rs.head, sizeof(HypWeighOut), hipMemcpyDeviceToHost, hy->stream));
+  if (ancestors) HYP_TRY(hy, hipMemcpyAsync(ancestors, rs.anc, sizeof(int) * K, hipMemcpyDeviceToHost, hy->stream));
+  if (offspring) HYP_TRY(hy, hipMemcpyAsync(offspring, rs.off, sizeof(int) * K, hipMemcpyDeviceToHost, hy->stream));
+  HYP_TRY(hy, hipStreamSynchronize(hy->stream));
+  if (ess) *ess = hy->host_head.ess;
+  if (logmean) *logmean = hy->host_head.logmean;
+  if (live) *live = hy->host_head.live;
+  return EKF_OK;
+}
+
+extern "C" int ekf_hypotheses_weigh(ekf_hypotheses* hy, double* ess, double* logmean, int* live) {
+  if (!hy) return EKF_ERR_ARG;
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  HypResampleView rs;
+  if (int rc = hyp_resample_view(hy, rs)) return rc;
+  launch_hyp_weigh(hy->stream, hyp_view(hy), rs, hyp_plan_chunk(hy->count));
+  HYP_TRY(hy, hipGetLastError());
+  return hyp_resample_outputs(hy, rs, nullptr, nullptr, ess, logmean, live);
+}
+
+extern "C" int ekf_hypotheses_resample(ekf_hypotheses* hy, double u, double split, const double* z, int* ancestors, int* offspring,
+                                       double* ess, double* logmean) {
+  if (!hy) return EKF_ERR_ARG;
+  HypResamplePlan rp;
+  if (const char* why = plan_hyp_resample(hy, u, split, z, rp))
+    return hyp_fail(hy, EKF_ERR_ARG, std::string("ekf_hypotheses_resample: ") + why);
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  HypResampleView rs;
+  if (int rc = hyp_resample_view(hy, rs)) return rc;
+  if (rp.split) {                                        // (before the first launch: a failed upload leaves the bank alone)
+    const size_t nz = 3 * (size_t)hy->count;
+    double* stage = nullptr;
+    HYP_RES(hy, "the split's draws", hy->init.begin(nz, 12 * (size_t)hy->count, hy->stream, &stage));
+    std::memcpy(stage, z, sizeof(double) * nz);
+    HYP_RES(hy, "the draws' upload", hy->init.commit(nz, hy->stream));
+  }
+  const HypView v = hyp_view(hy);
+  // (nontemporal stores unless EKFSLAM_HIP_HYP_COPY_NT=0: tools/hyp_resample_time.py measures both, profiles/hyp_resample.txt)
+  bool nt = true;
+  if (const char* e = std::getenv("EKFSLAM_HIP_HYP_COPY_NT")) nt = std::atoi(e) != 0;
+  launch_hyp_weigh(hy->stream, v, rs, rp.chunk);
+  launch_hyp_plan(hy->stream, v, rs, rp);
+  launch_hyp_copy(hy->stream, nt, v, rs, rp.groups);
+  if (rp.split) launch_hyp_split(hy->stream, v, rs, rp, hy->init.device());
+  HYP_TRY(hy, hipGetLastError());
+  return hyp_resample_outputs(hy, rs, ancestors, offspring, ess, logmean, nullptr);
 }

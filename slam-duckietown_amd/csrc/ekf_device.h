@@ -119,6 +119,23 @@ struct HypView {
   const double* map; const double* mu; HypState* st; double* X; LocRec* rec;
   int n, ld, ldx, count;
 };
+// ekf_hypotheses_weigh / ekf_hypotheses_resample (k_hyp_weigh, k_hyp_plan, k_hyp_copy, k_hyp_split).  The header k_hyp_weigh
+// leaves: top = the largest log-likelihood that weighs, sum / sum2 = the sums of w = exp(loglik - top) and of w^2, live = the
+// hypotheses with w > 0, last = the last of them (-1: none), ess = sum^2 / sum2 and logmean = top + ln sum - ln K (0 and -inf in
+// a degenerate bank: live == 0).  The launches behind it read the header on the device, so a resampling needs no host round trip.
+constexpr int HYP_PLAN_THREADS = 1024;                 // k_hyp_weigh / k_hyp_plan: ONE workgroup, a chunk of ceil(K / 1024) <= 64 records per thread
+constexpr int HYP_COPY_COLS = 2 * HYP_THREADS;         // k_hyp_copy / k_hyp_split: columns per workgroup, 16 bytes per lane and row
+struct alignas(16) HypWeighOut {
+  double top, sum, sum2, ess, logmean;
+  int live, last;
+  double pad;
+};
+static_assert(sizeof(HypWeighOut) == 64, "HypWeighOut is 64 bytes");
+// head: the header; w: K weights (not normalised); anc / off: the plan (ancestors, offspring); exc: K ints of scratch, the
+// exclusive scan of the surplus offspring (offspring - 1 of every survivor) the dead slots search
+struct HypResampleView {
+  HypWeighOut* head; double* w; int* anc; int* off; int* exc;
+};
 __host__ __device__ __forceinline__ int p_lds(int ld) { return ld < PPW ? ld : PPW; }
 __host__ __device__ __forceinline__ long p_col(int ld, int j) { return (long)(j >> 12) * ((long)ld * PPW) + (j & (PPW - 1)); }
 // the same as a 32-bit byte offset (ekf_create bounds one covariance by 4 GiB)

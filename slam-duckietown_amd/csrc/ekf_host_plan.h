@@ -1172,6 +1172,40 @@ inline const char* plan_hyp_reset(const HypBank* hy, int k0, int count, const do
   return nullptr;
 }
 
+// ekf_hypotheses_weigh / ekf_hypotheses_resample (k_hyp_weigh, k_hyp_plan: ONE workgroup of HYP_PLAN_THREADS, thread t on the
+// records [t * chunk, (t + 1) * chunk); k_hyp_copy, k_hyp_split: grid (K, column groups) -- the hypothesis on x, so that K =
+// 65536 is a legal grid --, a workgroup on HYP_COPY_COLS columns of one hypothesis's three rows).  u: the systematic resampler's
+// offset in [0, 1); split: s in [0, 1), 0 = copies only; z: count x 3 standard normal draws, read where s > 0.  keep = 1 - s^2 is
+// formed here, once.  Returns nullptr, or what is wrong (then nothing has changed).
+inline int hyp_plan_chunk(int count) { return (std::max(count, 1) + HYP_PLAN_THREADS - 1) / HYP_PLAN_THREADS; }
+inline int hyp_copy_groups(int ldx) { return (std::max(ldx, 1) + HYP_COPY_COLS - 1) / HYP_COPY_COLS; }
+// the ints and doubles of scratch a bank's resampling keeps on the device: ancestors, offspring, surplus scan; weights
+inline size_t hyp_resample_ints(int count) { return 3 * (size_t)count; }
+struct HypResamplePlan {
+  int chunk = 1, groups = 1;
+  bool split = false;
+  double u = 0.0, s = 0.0, keep = 1.0;
+};
+inline const char* plan_hyp_resample(const HypBank* hy, double u, double split, const double* z, HypResamplePlan& rp) {
+  if (!(u >= 0.0 && u < 1.0)) return "u must be in [0, 1)";
+  if (!(split >= 0.0 && split < 1.0)) return "split must be in [0, 1)";
+  if (split > 0.0) {
+    if (!z) return "split > 0 needs z (count x 3 standard normal draws)";
+    for (size_t i = 0; i < 3 * (size_t)hy->count; ++i)
+      if (!std::isfinite(z[i])) return "non-finite z";
+  } else if (z) {
+    return "z given with split == 0";
+  }
+  if (hy->count < 1 || hy->count > HYP_COUNT_MAX || hy->ldx < 2 || hy->ldx % 2 != 0) return "the bank's shape";
+  rp.chunk = hyp_plan_chunk(hy->count);
+  rp.groups = hyp_copy_groups(hy->ldx);
+  rp.split = split > 0.0;
+  rp.u = u;
+  rp.s = split;
+  rp.keep = 1.0 - split * split;
+  return nullptr;
+}
+
 // ekf_copy_trajectories (k_copy_traj, ekf_copy.hip): the k pairs (src_b[i] of `src` -> dst_b[i] of `dst`) checked -- indices
 // inside their banks, no destination twice, inside one handle no trajectory both read and written, the same device, every
 // source's size within the destination's n_max -- and grouped by source: a group is one source and up to COPY_FANOUT of its

@@ -15,6 +15,20 @@
 //   k_hyp_compare one thread per stored entry (a, c), 3 <= a <= c < n, of the bank's map and of a slot's P_base, and per landmark
 //                 mean: counts the entries whose bits differ (vector atomics on one word).
 //   k_hyp_adopt   writes hypothesis k's pose, block and rows into a slot whose frozen part the compare found identical.
+//   k_hyp_weigh   ONE workgroup: w_k = exp(loglik_k - top) over the hypotheses that weigh (finite log-likelihood, no sticky
+//                 NONFINITE flag), their sums, the effective sample size and the bank's evidence into a header on the device.
+//   k_hyp_plan    ONE workgroup: systematic resampling from that header -- four block-wide scans (the weights; the running maximum
+//                 of t_k = ceil(K C_k - u), which makes the offspring counts non-negative and their sum K in ANY summation order;
+//                 the dead slots' ranks; the survivors' surplus offspring) over chunks each thread walks in order, re-reading its
+//                 weights from L2 instead of holding 64 doubles in registers.  Survivors stay in place; dead slot number i takes
+//                 the i-th surplus offspring, found by bisection in the surplus scan.
+//   k_hyp_copy    grid (K, column groups): a dead slot takes its ancestor's rows, 16 bytes per lane, and its record; a survivor's
+//                 workgroups leave at once.  Every source is a survivor and no survivor's rows are written: no hazard, no second
+//                 copy of X.  Every hypothesis's loglik becomes the header's logmean.  NT: nontemporal stores (ekf_copy.hip's); they
+//                 bought nothing that holds -- 4095 copies of one source at N = 2000, call + sync: 114.0 us against 111.1 with
+//                 plain stores, 48.9 against 49.4 for 1023 (profiles/hyp_resample.txt); the kernel writes 403 MB in 66 .. 70 us.
+//   k_hyp_split   the same grid, after the copy: every slot whose ancestor has two or more offspring moves its pose by s L z_k
+//                 (L: the lower Cholesky factor of its pose block) and keeps (1 - s^2) of its block and rows, in place.
 // The active bound of a hypothesis lives on the device: the solve raises it over the landmarks of its record exactly as
 // fill_step raises a slot's on the host, so the columns the row launch touches are the ones k_loc_rows would touch.
 #include <algorithm>
@@ -22,6 +36,7 @@
 #include "ekf_device.h"
 
 #include "ekf_devfn.h"
+#include "ekf_host_plan.h"
 #include "ekf_launch.h"
 #include "ekf_loc_chain.h"
 
@@ -170,6 +185,270 @@ __global__ __launch_bounds__(HYP_THREADS) void k_hyp_adopt(const HypState* __res
     }
     so_b->neff = bound;
   }
+}
+
+// ---- weights, systematic resampling, split --------------------------------------------------------------------------------------
+struct HypAdd {
+  template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
+};
+struct HypMax {
+  template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a > b ? a : b; }
+};
+
+// Exclusive scan over the workgroup's threads in thread order (blockDim.x: whole waves, at most 16): a wave scans by shuffles, the
+// waves' totals go through sh[16] and every thread combines them in wave order.  *total: the combination of all threads.  The
+// order is fixed, so the same inputs give the same bits; integer sums and maxima are exact in any order.
+template <class T, class Op>
+__device__ __forceinline__ T hyp_block_scan(T v, T ident, Op op, T* sh, T* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  T inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const T o = __shfl_up(inc, d, 64);
+    if (lane >= d) inc = op(o, inc);
+  }
+  T exc = __shfl_up(inc, 1, 64);
+  if (lane == 0) exc = ident;
+  __syncthreads();                                       // (sh may still be read by the scan before this one)
+  if (lane == 63) sh[wave] = inc;
+  __syncthreads();
+  T off = ident, all = ident;
+  for (int q = 0; q < nw; ++q) {
+    if (q == wave) off = all;
+    all = op(all, sh[q]);
+  }
+  *total = all;
+  return op(off, exc);
+}
+
+// A hypothesis weighs where its log-likelihood is finite and its sticky NONFINITE flag is clear.
+__device__ __forceinline__ bool hyp_weighs(const HypState& s) {
+  return fabs(s.loglik) <= 1.79769313486231570815e308 && !(s.flags & EKF_FLAG_NONFINITE);
+}
+
+// ONE workgroup; thread t on the records [t * chunk, (t + 1) * chunk) (chunk * HYP_PLAN_THREADS >= K)
+__global__ __launch_bounds__(HYP_PLAN_THREADS) void k_hyp_weigh(const HypState* __restrict__ st, double* __restrict__ w,
+                                                                HypWeighOut* __restrict__ head, int K, int chunk) {
+  __shared__ double shd[16];
+  __shared__ int shi[16];
+  const int k0 = min(K, (int)threadIdx.x * chunk), k1 = min(K, k0 + chunk);
+  const double ninf = -__builtin_huge_val();
+  double mine = ninf, top;
+  for (int k = k0; k < k1; ++k)
+    if (hyp_weighs(st[k])) mine = fmax(mine, st[k].loglik);
+  hyp_block_scan(mine, ninf, HypMax(), shd, &top);
+  double s = 0.0, s2 = 0.0;
+  int live = 0, last = -1;
+  for (int k = k0; k < k1; ++k) {
+    const double wk = hyp_weighs(st[k]) ? exp(st[k].loglik - top) : 0.0;
+    w[k] = wk;
+    if (wk > 0.0) {
+      s += wk;
+      s2 += wk * wk;
+      live += 1;
+      last = k;
+    }
+  }
+  double sum, sum2;
+  int nlive, nlast;
+  hyp_block_scan(s, 0.0, HypAdd(), shd, &sum);
+  hyp_block_scan(s2, 0.0, HypAdd(), shd, &sum2);
+  hyp_block_scan(live, 0, HypAdd(), shi, &nlive);
+  hyp_block_scan(last, -1, HypMax(), shi, &nlast);
+  if (threadIdx.x == 0) {
+    head->top = top;
+    head->sum = sum;
+    head->sum2 = sum2;
+    head->ess = nlive > 0 ? sum * sum / sum2 : 0.0;
+    head->logmean = nlive > 0 ? top + log(sum / (double)K) : ninf;   // (uniform weights: sum == K, the evidence is `top` itself)
+    head->live = nlive;
+    head->last = nlast;
+    head->pad = 0.0;
+  }
+}
+
+// t_k before the running maximum: K at the last hypothesis that weighs (the cumulative sum ends at 1 by definition, not by
+// rounding), else ceil(K C_k - u) inside [0, K]
+__device__ __forceinline__ int hyp_raw_t(int k, int last, int K, double run, double total, double u) {
+  if (k >= last) return K;
+  const double x = ceil((double)K * (run / total) - u);
+  return (int)fmin(fmax(x, 0.0), (double)K);
+}
+
+// ONE workgroup, the chunks of k_hyp_weigh.  anc / off / exc are written and read back by different threads of the workgroup
+// (behind a barrier): no __restrict__ on them.
+__global__ __launch_bounds__(HYP_PLAN_THREADS) void k_hyp_plan(const HypWeighOut* __restrict__ head, const double* __restrict__ w,
+                                                               int* anc, int* off, int* exc, int K, int chunk, double u) {
+  __shared__ double shd[16];
+  __shared__ int shi[16];
+  const int k0 = min(K, (int)threadIdx.x * chunk), k1 = min(K, k0 + chunk);
+  if (head->live == 0) {                                 // (the whole workgroup) a degenerate bank: the identity
+    for (int k = k0; k < k1; ++k) {
+      anc[k] = k;
+      off[k] = 1;
+    }
+    return;
+  }
+  const double total = head->sum;
+  const int last = head->last;
+  // 1: the weights' scan -- this thread's cumulative sums start at `base`
+  double part = 0.0, unused;
+  for (int k = k0; k < k1; ++k) part += w[k];
+  const double base = hyp_block_scan(part, 0.0, HypAdd(), shd, &unused);
+  // 2: the running maximum of t over the hypotheses that weigh
+  double run = base;
+  int hi = 0, ti;
+  for (int k = k0; k < k1; ++k)
+    if (w[k] > 0.0) {
+      run += w[k];
+      hi = max(hi, hyp_raw_t(k, last, K, run, total, u));
+    }
+  int tprev = hyp_block_scan(hi, 0, HypMax(), shi, &ti);
+  // offspring: t_k - t_{k-1}; a hypothesis that weighs nothing carries t on and has none
+  run = base;
+  int ndead = 0, nextra = 0;
+  for (int k = k0; k < k1; ++k) {
+    int tk = tprev;
+    if (w[k] > 0.0) {
+      run += w[k];
+      tk = max(tprev, hyp_raw_t(k, last, K, run, total, u));
+    }
+    const int o = tk - tprev;
+    off[k] = o;
+    ndead += o == 0 ? 1 : 0;
+    nextra += o > 1 ? o - 1 : 0;
+    tprev = tk;
+  }
+  // 3, 4: the dead slots' ranks and the survivors' surplus offspring
+  int rank = hyp_block_scan(ndead, 0, HypAdd(), shi, &ti);
+  int extra = hyp_block_scan(nextra, 0, HypAdd(), shi, &ti);
+  for (int k = k0; k < k1; ++k) {
+    const int o = off[k];
+    exc[k] = extra;
+    if (o >= 1) {
+      anc[k] = k;                                        // survivors stay in place
+      extra += o - 1;
+    }
+  }
+  __syncthreads();
+  // dead slot number `rank` takes surplus offspring number `rank`: the last a with exc[a] <= rank (it has exc[a + 1] > rank, so
+  // at least one surplus offspring: a survivor)
+  for (int k = k0; k < k1; ++k) {
+    if (off[k] != 0) continue;
+    int lo = 0, up = K - 1;
+    while (lo < up) {
+      const int mid = (lo + up + 1) >> 1;
+      if (exc[mid] <= rank) lo = mid; else up = mid - 1;
+    }
+    anc[k] = lo;
+    rank += 1;
+  }
+}
+
+typedef double hyp_d2 __attribute__((ext_vector_type(2)));
+
+// grid (K, column groups of HYP_COPY_COLS): hypothesis blockIdx.x.  X is read (the ancestor's rows) and written (the dead slot's)
+// through one pointer; the two never coincide: an ancestor is a survivor, and a survivor's workgroups leave before they store.
+// The record travels field by field without loglik, which every hypothesis -- survivors too -- gets from the header.
+template <bool NT>
+__global__ __launch_bounds__(HYP_THREADS) void k_hyp_copy(HypState* st, double* X, const HypWeighOut* __restrict__ head,
+                                                          const int* __restrict__ anc, int ldx) {
+  if (head->live == 0) return;
+  const int k = blockIdx.x, a = anc[k];
+  const bool rec = blockIdx.y == 0 && threadIdx.x == 0;
+  if (a == k) {
+    if (rec) st[k].loglik = head->logmean;
+    return;
+  }
+  const int c = 2 * ((int)blockIdx.y * HYP_THREADS + (int)threadIdx.x);
+  if (c < ldx) {
+    const double* s = X + (long)a * 3 * ldx + c;
+    double* d = X + (long)k * 3 * ldx + c;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const hyp_d2 v = *reinterpret_cast<const hyp_d2*>(s + (long)r * ldx);
+      hyp_d2* p = reinterpret_cast<hyp_d2*>(d + (long)r * ldx);
+      if (NT) __builtin_nontemporal_store(v, p);
+      else *p = v;
+    }
+  }
+  if (rec) {
+    const HypState& s = st[a];
+    HypState& d = st[k];
+    for (int i = 0; i < 3; ++i) d.pose[i] = s.pose[i];
+    for (int i = 0; i < 6; ++i) d.blk[i] = s.blk[i];
+    d.loglik = head->logmean;
+    d.n_obs = s.n_obs;
+    d.n_rej = s.n_rej;
+    d.flags = s.flags;
+    d.bound = s.bound;
+  }
+}
+
+__device__ __forceinline__ bool hyp_pivot(double d) { return d > 0.0 && d <= 1.79769313486231570815e308; }
+
+// The grid of k_hyp_copy, behind it; a slot touches only itself.  z: K x 3 draws; s: the split, keep = 1 - s^2 (the host's).
+__global__ __launch_bounds__(HYP_THREADS) void k_hyp_split(HypState* __restrict__ st, double* __restrict__ X,
+                                                           const HypWeighOut* __restrict__ head, const int* __restrict__ anc,
+                                                           const int* __restrict__ off, const double* __restrict__ z, int ldx,
+                                                           double s, double keep) {
+  if (head->live == 0) return;
+  const int k = blockIdx.x;
+  if (off[anc[k]] < 2) return;                           // (the whole workgroup: the slot stays bit for bit)
+  const int c = 2 * ((int)blockIdx.y * HYP_THREADS + (int)threadIdx.x);
+  if (c < ldx) {
+    double* x = X + (long)k * 3 * ldx + c;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      hyp_d2* p = reinterpret_cast<hyp_d2*>(x + (long)r * ldx);
+      hyp_d2 v = *p;
+      v.x *= keep;
+      v.y *= keep;
+      *p = v;
+    }
+  }
+  if (blockIdx.y == 0 && threadIdx.x == 0) {
+    HypState& h = st[k];
+    // the lower Cholesky factor of the block before scaling; a pivot <= 0 or not finite zeroes its column
+    double l00 = 0.0, l10 = 0.0, l20 = 0.0, l11 = 0.0, l21 = 0.0, l22 = 0.0;
+    if (hyp_pivot(h.blk[0])) {
+      l00 = sqrt(h.blk[0]);
+      l10 = h.blk[1] / l00;
+      l20 = h.blk[2] / l00;
+    }
+    const double d1 = h.blk[3] - l10 * l10;
+    if (hyp_pivot(d1)) {
+      l11 = sqrt(d1);
+      l21 = (h.blk[4] - l20 * l10) / l11;
+    }
+    const double d2 = h.blk[5] - l20 * l20 - l21 * l21;
+    if (hyp_pivot(d2)) l22 = sqrt(d2);
+    const double z0 = z[3 * (long)k], z1 = z[3 * (long)k + 1], z2 = z[3 * (long)k + 2];
+    h.pose[0] += s * (l00 * z0);
+    h.pose[1] += s * (l10 * z0 + l11 * z1);
+    h.pose[2] += s * (l20 * z0 + l21 * z1 + l22 * z2);    // (not wrapped: the motion model takes any heading)
+    for (int i = 0; i < 6; ++i) h.blk[i] *= keep;
+  }
+}
+
+void launch_hyp_weigh(hipStream_t st, const HypView& v, const HypResampleView& rs, int chunk) {
+  hipLaunchKernelGGL(k_hyp_weigh, dim3(1), dim3(HYP_PLAN_THREADS), 0, st, v.st, rs.w, rs.head, v.count, chunk);
+}
+
+void launch_hyp_plan(hipStream_t st, const HypView& v, const HypResampleView& rs, const HypResamplePlan& rp) {
+  hipLaunchKernelGGL(k_hyp_plan, dim3(1), dim3(HYP_PLAN_THREADS), 0, st, rs.head, rs.w, rs.anc, rs.off, rs.exc, v.count, rp.chunk, rp.u);
+}
+
+void launch_hyp_copy(hipStream_t st, bool nt, const HypView& v, const HypResampleView& rs, int groups) {
+  if (nt)
+    hipLaunchKernelGGL(k_hyp_copy<true>, dim3(v.count, groups), dim3(HYP_THREADS), 0, st, v.st, v.X, rs.head, rs.anc, v.ldx);
+  else
+    hipLaunchKernelGGL(k_hyp_copy<false>, dim3(v.count, groups), dim3(HYP_THREADS), 0, st, v.st, v.X, rs.head, rs.anc, v.ldx);
+}
+
+void launch_hyp_split(hipStream_t st, const HypView& v, const HypResampleView& rs, const HypResamplePlan& rp, const double* z) {
+  hipLaunchKernelGGL(k_hyp_split, dim3(v.count, rp.groups), dim3(HYP_THREADS), 0, st, v.st, v.X, rs.head, rs.anc, rs.off, z, v.ldx,
+                     rp.s, rp.keep);
 }
 
 void launch_hyp_solve(hipStream_t st, const HypView& v, const StepIn* in, int rec_stride, const DeviceConfig& cfg, bool gate) {

@@ -5,7 +5,7 @@
 #include "ekf_device.h"
 
 namespace ekf {
-struct PassPlan; struct RemovePlan;   // ekf_host_plan.h
+struct PassPlan; struct RemovePlan; struct HypResamplePlan;   // ekf_host_plan.h
 // ---- per-step kernels (ekf_kernels.hip) ----
 // What a step's solve takes beside the views; the single-launch step also the handle's dmbox (throughput shape), dready, step_seq
 struct StepArgs {
@@ -139,6 +139,13 @@ void launch_hyp_fill(hipStream_t st, const HypView& v, const double* init, int k
 // the bank's map against a slot's P_base / mean (layout ldb): *mismatch += entries whose bits differ
 void launch_hyp_compare(hipStream_t st, const HypView& v, const double* Pb, const double* mub, int ldb, int groups, unsigned* mismatch);
 void launch_hyp_adopt(hipStream_t st, const HypView& v, int k, double* Pb, double* mub, int ldb, SolveOut* so_b, int bound, int groups);
+// weights, resampling and split (rs: ekf_device.h: HypResampleView; rp: plan_hyp_resample's).  weigh leaves rs.head and rs.w;
+// plan reads them and leaves rs.anc / rs.off; copy and split read those and the header -- a degenerate bank is left alone
+void launch_hyp_weigh(hipStream_t st, const HypView& v, const HypResampleView& rs, int chunk);
+void launch_hyp_plan(hipStream_t st, const HypView& v, const HypResampleView& rs, const HypResamplePlan& rp);
+void launch_hyp_copy(hipStream_t st, bool nt, const HypView& v, const HypResampleView& rs, int groups);
+// z: count x 3 draws on the device
+void launch_hyp_split(hipStream_t st, const HypView& v, const HypResampleView& rs, const HypResamplePlan& rp, const double* z);
 // groups x (tiles of the largest source + 1) workgroups; tab: plan_copy's table on the device
 void launch_copy_traj(hipStream_t st, bool nt, const BankView& src, const BankView& dst, const double* mus, double* mud,
                       const int* tab, int groups, int n_hi);

@@ -170,6 +170,8 @@ ABI = {
     "ekf_hyp_adopt": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "ekf_hyp_sync": (C.c_int, [C.c_void_p]),
     "ekf_hyp_last_error": (C.c_char_p, [C.c_void_p]),
+    "ekf_hypotheses_weigh": (C.c_int, [C.c_void_p, _dp, _dp, _ip]),
+    "ekf_hypotheses_resample": (C.c_int, [C.c_void_p, C.c_double, C.c_double, _dp, _ip, _ip, _dp, _dp]),
     "ekf_stream_upload": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
     "ekf_stream_run": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ekf_run_stream": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
@@ -401,6 +403,16 @@ class MapJoin(typing.NamedTuple):
     first: np.ndarray      # (k,) int32
     count: np.ndarray      # (k,) int32
     twins: np.ndarray      # (k, N_B hi) int32, -1 beyond a source's landmarks
+
+
+class HypothesisResampling(typing.NamedTuple):
+    """What ``HypothesisBank.resample`` reports: per slot the hypothesis it now holds (``ancestors[k] == k``: a survivor, in
+    place) and per hypothesis its number of offspring, the effective sample size of the weights that were resampled and the
+    bank's evidence ``logmean`` (every hypothesis's log-likelihood afterwards)."""
+    ancestors: np.ndarray  # (count,) int32
+    offspring: np.ndarray  # (count,) int32
+    ess: float
+    logmean: float
 
 
 EKF_FACTOR_RHS = 16       # (include/ekfslam_hip.h)
@@ -650,6 +662,54 @@ class HypothesisBank:
     def best(self) -> int:
         """The hypothesis with the largest log-likelihood (the first of equals)."""
         return int(np.argmax(self.weights()))
+
+    # -- weights and resampling on the device ---------------------------------------------------
+    def _weigh(self):
+        ess, logmean, live = C.c_double(), C.c_double(), C.c_int()
+        self._check(self._lib.ekf_hypotheses_weigh(self._live(), C.byref(ess), C.byref(logmean), C.byref(live)))
+        return ess.value, logmean.value, live.value
+
+    def ess(self) -> float:
+        """The effective sample size (sum w)^2 / sum w^2 of the weights, formed on the device (``ekf_hypotheses_weigh``): unlike
+        ``weights``, a hypothesis whose sticky non-finite flag is set weighs nothing.  0 where nothing weighs."""
+        return self._weigh()[0]
+
+    def evidence(self) -> float:
+        """max + ln sum exp(loglik - max) - ln count: the log of the mean likelihood, the bank's evidence under equal priors
+        (-inf where nothing weighs)."""
+        return self._weigh()[1]
+
+    def live(self) -> int:
+        """The hypotheses with a weight above zero."""
+        return self._weigh()[2]
+
+    def resample(self, u=None, split: float = 0.0, z=None, rng=None) -> HypothesisResampling:
+        """Systematic resampling on the device (``ekf_hypotheses_resample``) with the offset ``u`` in [0, 1): survivors stay in
+        place, dead slots take the surplus offspring's pose, block, rows and counters bit for bit, and every log-likelihood
+        becomes the bank's evidence.  ``split`` = s in (0, 1) spreads the copies: every slot of an ancestor with two or more
+        offspring moves its pose by ``s L z[k]`` (L L^T = its pose block) and keeps ``1 - s^2`` of its block and rows, so that
+        the children's mixture has the ancestor's pose marginal.  ``u`` and ``z`` ((count, 3) standard normal) are drawn from
+        ``rng`` (default ``np.random.default_rng()``) where they are not given.  Blocking."""
+        h = self._live()
+        split = float(split)
+        if (u is None or (split > 0.0 and z is None)) and rng is None:
+            rng = np.random.default_rng()
+        u = float(rng.random()) if u is None else float(u)
+        if z is not None:                                  # (given without a split: the library refuses it)
+            z = np.ascontiguousarray(np.broadcast_to(_f64(z), (self.count, 3)))
+        elif split > 0.0:
+            z = rng.standard_normal((self.count, 3))
+        anc, off = np.empty(self.count, dtype=np.int32), np.empty(self.count, dtype=np.int32)
+        ess, logmean = C.c_double(), C.c_double()
+        self._check(self._lib.ekf_hypotheses_resample(h, u, split, None if z is None else _p(z), _p(anc, _ip), _p(off, _ip),
+                                                      C.byref(ess), C.byref(logmean)))
+        return HypothesisResampling(anc, off, ess.value, logmean.value)
+
+    def resample_if(self, fraction: float = 0.5, **kw) -> Optional[HypothesisResampling]:
+        """``resample(**kw)`` when the effective sample size has fallen below ``fraction * count``; else None."""
+        if self.ess() < float(fraction) * self.count:
+            return self.resample(**kw)
+        return None
 
     def adopt(self, k: int, f: "EkfSlam", b: int = 0):
         """Hypothesis k's pose, pose block and pose rows into trajectory ``b`` of ``f``, whose landmark means and P[3:, 3:] must

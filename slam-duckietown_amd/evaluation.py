@@ -376,6 +376,43 @@ def resolve_hypotheses(bank, confidence: float = 0.99) -> HypothesisResolution:
     return HypothesisResolution(best, float(w[best]), ratio < 1.0 - float(confidence), second, ratio)
 
 
+class MixturePose(NamedTuple):
+    mean: np.ndarray                 # (3,) the weighted mean pose, the heading averaged on the circle
+    cov: np.ndarray                  # (3, 3) sum w (P_k + d_k d_k^T), d_k the deviation from the mean (heading wrapped)
+    weights: np.ndarray              # (K,) the weights used
+
+
+def mixture_pose(bank, weights=None) -> MixturePose:
+    """The mean and covariance of a hypothesis bank's pose mixture sum_k w_k N(pose_k, P_k): what a Gaussian-sum localiser
+    reports between resamplings.  ``bank``: a ``HypothesisBank`` (anything with ``poses()`` and ``loglik``; a hypothesis whose
+    ``flags()`` are set weighs nothing, as on the device) or a pair (poses (K, 3), blocks (K, 3, 3)) with ``weights``.  The heading
+    is averaged on the circle -- atan2 of the weighted sine and cosine -- and deviations from it are wrapped to [-pi, pi)."""
+    from .ekf_bindings import HypothesisBank
+    if hasattr(bank, "poses"):
+        poses, blocks = bank.poses()
+        if weights is None:
+            ll = np.array(bank.loglik, dtype=np.float64)
+            if hasattr(bank, "flags"):
+                ll = np.where(np.asarray(bank.flags()) != 0, -np.inf, ll)
+            weights = HypothesisBank.weights_of(ll)
+    else:
+        poses, blocks = bank
+    poses, blocks = np.asarray(poses, dtype=np.float64).reshape(-1, 3), np.asarray(blocks, dtype=np.float64).reshape(-1, 3, 3)
+    w = np.full(len(poses), 1.0 / max(len(poses), 1)) if weights is None else np.asarray(weights, dtype=np.float64)
+    if len(poses) == 0 or w.shape != (len(poses),) or not w.sum() > 0.0:
+        raise ValueError("mixture_pose: an empty bank, or weights that do not match it or sum to nothing")
+    w = w / w.sum()
+    use = w > 0.0                                                              # (a dead hypothesis may hold NaN: 0 * NaN)
+    p, P, w = poses[use], blocks[use], w[use]
+    mean = np.array([w @ p[:, 0], w @ p[:, 1], np.arctan2(w @ np.sin(p[:, 2]), w @ np.cos(p[:, 2]))])
+    d = p - mean
+    d[:, 2] = wrap_angle(d[:, 2])
+    cov = np.einsum("k,kij->ij", w, P) + np.einsum("k,ki,kj->ij", w, d, d)
+    out = np.zeros(len(poses))
+    out[use] = w
+    return MixturePose(mean, 0.5 * (cov + cov.T), out)
+
+
 class LandmarkRejections(NamedTuple):
     applied: np.ndarray              # (B, L) int64: updates of landmark l that trajectory b applied
     rejected: np.ndarray             # (B, L) int64: ... that the NIS gate rejected (L = largest logged index + 1)
