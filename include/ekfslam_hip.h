@@ -584,7 +584,9 @@ int ekf_step_fetch(ekf_handle *h, const double *lin, const double *ang, const in
  * followed by the fused step: one window of raw AprilTag detections per trajectory, frames concatenated in
  * order -- count[b] detections at tag_id / pose_t (x, y, z of tag.pose_t) / pose_err [b*stride + i].  The tag-id
  * -> landmark-index table lives on the device (ekf_download_tag_index); ekf_download_tags returns what the
- * reference returns as tags_positions for the last window.  ekf_set_association sets gate and IGNORE_TAGS. */
+ * reference returns as tags_positions for the last window.  ekf_set_association sets gate and IGNORE_TAGS.
+ * EKF_ERR_ARG (a NULL array it needs, stride < 0, a count outside [0, min(stride, EKF_DMAX)]) changes nothing: the window is
+ * checked before anything is allocated, pushed or taken from the input ring. */
 int ekf_set_association(ekf_handle *h, double gate_range, const int *ignore_tags, int n_ignore);
 int ekf_step_detections(ekf_handle *h, const double *lin, const double *ang, const int *count, const int *tag_id,
                         const double *pose_t, const double *pose_err, int stride);

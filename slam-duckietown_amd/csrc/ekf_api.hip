@@ -75,6 +75,7 @@ template <class T> using DeviceBuf = res::DeviceBuf<T, HipBackend>;
 template <class T> using PinnedBuf = res::PinnedBuf<T, HipBackend>;
 template <class T> using StagedUpload = res::StagedUpload<T, HipBackend>;
 using Event = res::Event<HipBackend>;
+using InputRing = res::InputRing<HipBackend, RING, RING_GROUP>;
 
 struct ekf_handle : ekf::HostPlan {
   DeviceConfig dcfg{};
@@ -91,9 +92,7 @@ struct ekf_handle : ekf::HostPlan {
   DeviceBuf<double> dfac;         // pending factors restricted to the gathered indices (k_solve -> k_panels)
   DeviceBuf<StepIn> d_ring;
   PinnedBuf<StepIn> h_ring;
-  Event ring_ev[RING / RING_GROUP];   // one event per group of slots (see ring_take)
-  bool ring_open[RING / RING_GROUP]{};
-  int ring_pos = 0;
+  InputRing ring;                 // the slots of h_ring / d_ring, h_det / d_det and h_pred / d_pred: one position, one set of events
   DeviceBuf<StepIn> d_stream;
   DeviceBuf<int> dfloor;          // per trajectory floor of the active bound, applied by k_solve (see push_floor)
   DeviceBuf<double> dF, dQ, dTmp; // dense path, allocated on first use (one group)
@@ -252,7 +251,7 @@ struct ekf_handle : ekf::HostPlan {
   ekf::DirectPlan direct_plan;
   ekf::LinearPlan linear_plan;
   // ekf_predict_linear (allocated on first use): the input ring of k_predict_pose's records, RING slots of batch records used
-  // in the order of h_ring / d_ring and under the same events (ring_take / ring_done), and the call's plan
+  // in the order of h_ring / d_ring and under the same events (`ring`), and the call's plan
   DeviceBuf<PredictIn> d_pred;
   PinnedBuf<PredictIn> h_pred;
   ekf::PredictPlan predict_plan;
@@ -502,7 +501,7 @@ extern "C" int ekf_create(int device, int n_max, int batch, const ekf_config* cf
   CREATE_RES("d_ring", h->d_ring.ensure(B * RING));
   CREATE_RES("h_ring", h->h_ring.ensure(B * RING));
   CREATE_RES("h_flags", h->h_flags.ensure(B));
-  for (auto& ev : h->ring_ev) CREATE_RES("ring_ev", ev.ensure());
+  CREATE_RES("the input ring's events", h->ring.ensure());
   CREATE_RES("t0", h->t0.ensure(true));
   CREATE_RES("t1", h->t1.ensure(true));
   CREATE_TRY(hipMemsetAsync(h->dP.p, 0, sizeof(double) * (size_t)h->pstride * batch, h->stream));
@@ -1852,100 +1851,89 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
   return EKF_OK;
 }
 
-// The input rings (h_ring / d_ring, h_det / d_det): RING slots used in order.  A slot may be refilled by the host once the
-// work that read it has run; that is tracked per GROUP of slots -- the event of a group is recorded behind the launch that
-// read its last slot and waited for when the ring comes round to its first slot again.
-static int ring_take(ekf_handle* h, int* slot) {
-  const int s = h->ring_pos, g = s / RING_GROUP;
-  h->ring_pos = (s + 1) % RING;
-  if (s % RING_GROUP == 0) {
-    if (h->ring_open[g]) HIP_TRY(h, hipStreamSynchronize(h->stream));   // (a failed call left the group without its event)
-    else RES_TRY(h, "ring_ev", h->ring_ev[g].wait_if_recorded());
-  }
-  h->ring_open[g] = true;
-  *slot = s;
+// The input ring (res::InputRing; h_ring / d_ring, h_det / d_det, h_pred / d_pred share its slots).  A call takes a slot, fills
+// the pinned records `hs` of it, submits them, launches on *in and reports the launch:
+//   staged path: the records are copied to `ds`, which the kernels read;
+//   direct path (the small-state path): the one workgroup per trajectory fetches its 352-byte record straight from the pinned
+//   ring (one coalesced read over PCIe, ~1.5 us) -- a staged host-to-device copy in front of the kernel costs 5 - 10 us of
+//   latency per step, which at these sizes is a third of the step -- and the slot is free once the kernel has run.
+constexpr const char* RING_WHAT = "the input ring";
+template <class T> struct RingSlot { int slot = 0; T *hs = nullptr, *ds = nullptr; };
+template <class T, class H, class D>
+static int ring_take(ekf_handle* h, H& host, D& dev, RingSlot<T>* r) {
+  RES_TRY(h, RING_WHAT, h->ring.take(h->stream, &r->slot));
+  r->hs = host.p + (size_t)r->slot * h->batch;
+  r->ds = dev.p + (size_t)r->slot * h->batch;
   return EKF_OK;
 }
-static int ring_done(ekf_handle* h, int slot) {
-  if (slot % RING_GROUP != RING_GROUP - 1) return EKF_OK;
-  const int g = slot / RING_GROUP;
-  RES_TRY(h, "ring_ev", h->ring_ev[g].record(h->stream));
-  h->ring_open[g] = false;
+template <class T>
+static int ring_submit(ekf_handle* h, const RingSlot<T>& r, bool direct, size_t count, const T** in) {
+  RES_TRY(h, RING_WHAT, h->ring.submit(r.slot, direct, r.ds, r.hs, sizeof(T) * count, h->stream));
+  *in = direct ? r.hs : r.ds;
+  return EKF_OK;
+}
+template <class T>
+static int ring_launched(ekf_handle* h, const RingSlot<T>& r, bool direct) {
+  RES_TRY(h, RING_WHAT, h->ring.launched(r.slot, direct, h->stream));
   return EKF_OK;
 }
 
-// While an entry point enqueues: which launches log innovations (see ekf_handle::lg_slot); nothing is logged outside one.
+// While an entry point enqueues `steps` logged steps: the log rows of its launches (ekf_handle::lg_slot, pl_slot).  `innov`: the
+// call logs innovations (a lone prediction does not); every call is a row of the pose log.  The counters move in commit() only:
+// a call that returns early has logged nothing.  Nothing is logged outside a scope.
 struct LogScope {
   ekf_handle* h;
-  ~LogScope() {
-    h->lg_slot = -1;
-    h->lg_tslot = -1;
+  bool innov, pose;
+  int steps;
+  LogScope(ekf_handle* h_, bool innov_, int steps_ = 1) : h(h_), innov(innov_ && h_->dinnov.p), pose(h_->dpose.p), steps(steps_) { step(0); }
+  void step(int k) {                                   // step k of the call's span
+    h->lg_slot = innov ? (long)((h->innov_steps + k) % h->innov_cap) : -1;
     h->lg_jbase = 0;
-    h->pl_slot = -1;
-    h->pl_tslot = -1;
+    h->pl_slot = pose ? (long)((h->pose_steps + k) % h->pose_cap) : -1;
+  }
+  void pass(int p) { h->lg_jbase = MMAX * p; }         // update pass p of the call's one step: its landmarks from MMAX * p on
+  // the span is steps [first, first + steps) of the uploaded stream: its kernels log stream step t in row (lg_tslot + t) % cap
+  void stream(int first) {
+    const long cap = h->innov_cap, pcap = h->pose_cap;
+    if (innov) h->lg_tslot = (long)(((h->innov_steps - first) % cap + cap) % cap);
+    if (pose) h->pl_tslot = (long)(((h->pose_steps - first) % pcap + pcap) % pcap);
+  }
+  void commit() {
+    if (innov) h->innov_steps += steps;
+    if (pose) h->pose_steps += steps;
+  }
+  ~LogScope() {
+    h->lg_slot = h->lg_tslot = h->pl_slot = h->pl_tslot = -1;
+    h->lg_jbase = 0;
   }
 };
 
-static int do_step(ekf_handle* h, int base_flags, const double* lin, const double* ang, const int* idx,
+static int do_step(ekf_handle* h, const char* fn, int base_flags, const double* lin, const double* ang, const int* idx,
                    const double* range, const double* bearing, const int* m, int stride, int fetch_b = -1) {
   if (!h) return EKF_ERR_ARG;
-  LogScope log_scope{h};
-  if (int rc = check_host_bad(h, "ekf_step")) return rc;
+  if (int rc = check_host_bad(h, fn)) return rc;
   if (int rc = refresh_sizes(h)) return rc;
   const bool upd = (base_flags & FLAG_UPDATE) != 0, pred = (base_flags & FLAG_PREDICT) != 0;
-  if (pred && (!lin || !ang)) return fail(h, EKF_ERR_ARG, "NULL lin/ang");
-  if (upd && (!m || stride < 0)) return fail(h, EKF_ERR_ARG, "NULL m / bad stride");
-  int m_hi = 0;
-  if (upd && h->cfg.enable_measurement_model)
-    for (int b = 0; b < h->batch; ++b) {
-      if (m[b] < 0 || m[b] > stride) return fail(h, EKF_ERR_ARG, "m[b] must be in [0, stride]");
-      m_hi = std::max(m_hi, m[b]);
-    }
-  if (m_hi > 0 && (!idx || !range || !bearing)) return fail(h, EKF_ERR_ARG, "NULL observation arrays");
-  if (m_hi > 0) {                                      // everything is checked before any handle state changes
-    std::vector<unsigned char> seen;
-    for (int b = 0; b < h->batch; ++b)
-      if (const char* why = validate_obs(h, b, idx + (long)b * stride, m[b], seen)) return fail(h, EKF_ERR_ARG, why);
-  }
+  ObsPlan op;                                            // everything is checked before any handle state changes
+  if (const char* why = plan_obs_lists(h, pred, upd, true, lin, ang, idx, range, bearing, m, stride, op)) return bad_arg(h, fn, why);
   HIP_TRY(h, hipSetDevice(h->device));
   if (int rc = push_floor(h, false)) return rc;
-  const int passes = std::max(1, (m_hi + MMAX - 1) / MMAX);
-  const bool logged = h->dinnov.p && upd;                // (a lone prediction is not a logged step)
-  h->pl_slot = h->dpose.p ? (long)(h->pose_steps % h->pose_cap) : -1;   // (the pose log: every call is a row)
-  for (int p = 0; p < passes; ++p) {
-    h->lg_slot = logged ? (long)(h->innov_steps % h->innov_cap) : -1;
-    h->lg_jbase = MMAX * p;
-    int slot;
-    if (int rc = ring_take(h, &slot)) return rc;
-    StepIn* hs = h->h_ring.p + (size_t)slot * h->batch;
-    StepIn* ds = h->d_ring.p + (size_t)slot * h->batch;
-    int flags = (upd ? FLAG_UPDATE : 0) | ((pred && p == 0) ? FLAG_PREDICT : 0);
-    int m_pass_hi = 0;
-    for (int b = 0; b < h->batch; ++b) {
-      const int mb = (upd && h->cfg.enable_measurement_model) ? m[b] : 0;
-      const long off = (long)b * stride;
-      fill_step(hs[b], h->n[b], h->neff[b], pred ? lin[b] : 0.0, pred ? ang[b] : 0.0, flags,
-                idx ? idx + off : nullptr, range ? range + off : nullptr, bearing ? bearing + off : nullptr, mb, p);
-      m_pass_hi = std::max(m_pass_hi, hs[b].m);
-      h->neff_enq[b] = h->opt_active_bound ? h->neff[b] : h->n[b];
-    }
-    h->fetch_b = p == passes - 1 ? fetch_b : -1;
-    if (small_path(h)) {
-      // small-state path: the one workgroup per trajectory fetches its 352-byte record straight from the pinned ring (one
-      // coalesced read over PCIe, ~1.5 us) -- a staged host-to-device copy in front of the kernel costs 5 - 10 us of latency
-      // per step, which at these sizes is a third of the step
-      if (int rc = enqueue_pass(h, hs, m_pass_hi)) return rc;
-      if (int rc = ring_done(h, slot)) return rc;                // (the slot is free once the kernel has run)
-      continue;
-    }
-    HIP_TRY(h, hipMemcpyAsync(ds, hs, sizeof(StepIn) * h->batch, hipMemcpyHostToDevice, h->stream));
-    if (int rc = ring_done(h, slot)) return rc;
-    if (int rc = enqueue_pass(h, ds, m_pass_hi)) return rc;
+  LogScope log(h, upd);
+  for (int p = 0; p < op.passes; ++p) {
+    log.pass(p);
+    const bool direct = small_path(h);
+    RingSlot<StepIn> r;
+    if (int rc = ring_take(h, h->h_ring, h->d_ring, &r)) return rc;
+    const int m_pass_hi = fill_step_records(h, pred, upd, lin, ang, idx, range, bearing, m, stride, p, r.hs);
+    h->fetch_b = p == op.passes - 1 ? fetch_b : -1;
+    const StepIn* in;
+    if (int rc = ring_submit(h, r, direct, (size_t)h->batch, &in)) return rc;
+    if (int rc = enqueue_pass(h, in, m_pass_hi)) return rc;
+    if (int rc = ring_launched(h, r, direct)) return rc;
   }
   h->fetch_b = -1;
-  if (logged) h->innov_steps += 1;
   if (int rc = log_pose_step(h)) return rc;
-  if (h->dpose.p) h->pose_steps += 1;
+  log.commit();
   return EKF_OK;
 }
 
@@ -1968,6 +1956,18 @@ static int assoc_init(ekf_handle* h) {
   return EKF_OK;
 }
 
+// One window per trajectory through the ring (staged on every path), for both detection entries; *in: the device's records.
+static int upload_detections(ekf_handle* h, const double* lin, const double* ang, const int* count, const int* tag_id,
+                             const double* pose_t, const double* pose_err, int stride, const DetIn** in) {
+  RingSlot<DetIn> r;
+  if (int rc = ring_take(h, h->h_det, h->d_det, &r)) return rc;
+  fill_det_records(h, lin, ang, count, tag_id, pose_t, pose_err, stride, r.hs);
+  // the host's view of the active bound must be on the device before the first device-side window
+  if (!h->sizes_dirty)
+    HIP_TRY(h, hipMemcpyAsync(h->dneff.p, h->neff.data(), sizeof(int) * h->batch, hipMemcpyHostToDevice, h->stream));
+  return ring_submit(h, r, false, (size_t)h->batch, in);
+}
+
 extern "C" int ekf_set_association(ekf_handle* h, double gate_range, const int* ignore_tags, int n_ignore) {
   if (!h) return EKF_ERR_ARG;
   if (n_ignore < 0 || n_ignore > IGNMAX || (n_ignore > 0 && !ignore_tags))
@@ -1980,50 +1980,19 @@ extern "C" int ekf_set_association(ekf_handle* h, double gate_range, const int* 
 
 extern "C" int ekf_step_detections(ekf_handle* h, const double* lin, const double* ang, const int* count,
                                    const int* tag_id, const double* pose_t, const double* pose_err, int stride) {
+  const char* fn = "ekf_step_detections";
   if (!h) return EKF_ERR_ARG;
-  if (!lin || !ang || !count || stride < 0) return fail(h, EKF_ERR_ARG, "ekf_step_detections: NULL array");
-  if (int rc = check_host_bad(h, "ekf_step_detections")) return rc;
+  if (int rc = check_host_bad(h, fn)) return rc;
+  // (checked before anything is allocated, pushed or taken; m_hi, an upper bound of the landmarks observed this window, selects
+  //  the kernel instantiation)
+  int m_hi = 0;
+  if (const char* why = plan_det_windows(h, lin, ang, count, tag_id, pose_t, pose_err, stride, &m_hi)) return bad_arg(h, fn, why);
   if (int rc = assoc_init(h)) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   if (int rc = push_floor(h, false)) return rc;
-  // an upper bound of the landmarks observed this window (distinct tag ids) selects the kernel instantiation
-  int m_hi = 0;
-  int slot;
-  if (int rc = ring_take(h, &slot)) return rc;
-  DetIn* hs = h->h_det.p + (size_t)slot * h->batch;
-  DetIn* ds = h->d_det.p + (size_t)slot * h->batch;
-  for (int b = 0; b < h->batch; ++b) {
-    const int c = count[b];
-    if (c < 0 || c > stride || c > DMAX) return fail(h, EKF_ERR_ARG, "ekf_step_detections: count must be <= min(stride, EKF_DMAX)");
-    if (c > 0 && (!tag_id || !pose_t || !pose_err)) return fail(h, EKF_ERR_ARG, "ekf_step_detections: NULL detection arrays");
-    DetIn& d = hs[b];
-    d.lin = lin[b];
-    d.ang = ang[b];
-    d.count = c;
-    d.pad = 0;
-    int distinct = 0;
-    for (int i = 0; i < c; ++i) {
-      const long e = (long)b * stride + i;
-      d.tag_id[i] = tag_id[e];
-      d.pose_err[i] = pose_err[e];
-      d.pose_t[i][0] = pose_t[3 * e];
-      d.pose_t[i][1] = pose_t[3 * e + 1];
-      d.pose_t[i][2] = pose_t[3 * e + 2];
-      bool seen = false;
-      for (int k = 0; k < i; ++k) seen |= (d.tag_id[k] == d.tag_id[i]);
-      distinct += seen ? 0 : 1;
-    }
-    m_hi = std::max(m_hi, std::min(distinct, AMAX));
-  }
-  if (!h->cfg.enable_measurement_model) m_hi = 0;
-  LogScope log_scope{h};
-  h->lg_slot = h->dinnov.p ? (long)(h->innov_steps % h->innov_cap) : -1;
-  h->pl_slot = h->dpose.p ? (long)(h->pose_steps % h->pose_cap) : -1;
-  // the host's view of the active bound must be on the device before the first device-side window
-  if (!h->sizes_dirty)
-    HIP_TRY(h, hipMemcpyAsync(h->dneff.p, h->neff.data(), sizeof(int) * h->batch, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(ds, hs, sizeof(DetIn) * h->batch, hipMemcpyHostToDevice, h->stream));
-  if (int rc = ring_done(h, slot)) return rc;
+  const DetIn* ds;
+  if (int rc = upload_detections(h, lin, ang, count, tag_id, pose_t, pose_err, stride, &ds)) return rc;
+  LogScope log(h, true);
   const int mcap = cap_for(std::min(m_hi, MMAX));
   if (((h->pending_k + ranks_for(mcap) + 3) & ~3) > KTOT)   // (what the step's kernels will write: see enqueue_pass)
     if (int rc = flush_pending(h)) return rc;
@@ -2038,12 +2007,11 @@ extern "C" int ekf_step_detections(ekf_handle* h, const double* lin, const doubl
   // (more than EKF_MMAX distinct tags in some trajectory's window: a second pass with the rest -- an update without a
   //  prediction; trajectories that had fewer find m = 0 there)
   if (int rc = enqueue_pass(h, h->d_assoc_step.p, std::min(m_hi, MMAX))) return rc;
-  h->lg_jbase = MMAX;
+  log.pass(1);
   if (m_hi > MMAX)
     if (int rc = enqueue_pass(h, h->d_assoc_step.p + h->batch, m_hi - MMAX)) return rc;
-  if (h->dinnov.p) h->innov_steps += 1;
   if (int rc = log_pose_step(h)) return rc;
-  if (h->dpose.p) h->pose_steps += 1;
+  log.commit();
   return EKF_OK;
 }
 
@@ -2356,7 +2324,7 @@ extern "C" int ekf_transform(ekf_handle* h, int b0, int count, const double* T, 
 }
 
 extern "C" int ekf_predict(ekf_handle* h, const double* lin, const double* ang) {
-  return do_step(h, FLAG_PREDICT, lin, ang, nullptr, nullptr, nullptr, nullptr, 0);
+  return do_step(h, "ekf_predict", FLAG_PREDICT, lin, ang, nullptr, nullptr, nullptr, nullptr, 0);
 }
 
 // A prediction with the caller's motion model (k_predict_pose, ekf_predict_linear.hip): enqueued like ekf_predict -- the records go
@@ -2375,42 +2343,37 @@ extern "C" int ekf_predict_linear(ekf_handle* h, int b0, int count, const double
   const size_t B = (size_t)h->batch;
   RES_TRY(h, "ekf_predict_linear's input ring", res::ensure_group(nullptr, res::want(h->d_pred, B * RING), res::want(h->h_pred, B * RING)));
   if (int rc = join_aux(h)) return rc;
-  int slot;
-  if (int rc = ring_take(h, &slot)) return rc;
-  PredictIn* hs = h->h_pred.p + (size_t)slot * B;
-  PredictIn* ds = h->d_pred.p + (size_t)slot * B;
-  std::copy(pp.rec.begin(), pp.rec.end(), hs);
-  // (small-state path: the workgroups fetch their record straight from the pinned ring, as that path's steps do -- see do_step)
+  RingSlot<PredictIn> r;
+  if (int rc = ring_take(h, h->h_pred, h->d_pred, &r)) return rc;
+  std::copy(pp.rec.begin(), pp.rec.end(), r.hs);
   const bool direct = small_path(h);
-  if (!direct) {
-    HIP_TRY(h, hipMemcpyAsync(ds, hs, sizeof(PredictIn) * (size_t)count, hipMemcpyHostToDevice, h->stream));
-    if (int rc = ring_done(h, slot)) return rc;
-  }
+  const PredictIn* in;
+  if (int rc = ring_submit(h, r, direct, (size_t)count, &in)) return rc;
   if (pp.n_hi > 0) {
     ProfBracket pb;
     if (int rc = prof_open(h, 7, h->stream, &pb)) return rc;
-    launch_predict_pose(h->stream, pending_view(h, b0, count), h->dP.p, h->dmu2[h->cur].p, direct ? hs : ds, pp.n_hi);
+    launch_predict_pose(h->stream, pending_view(h, b0, count), h->dP.p, h->dmu2[h->cur].p, in, pp.n_hi);
     if (int rc = prof_close(h, &pb)) return rc;
     HIP_TRY(h, hipGetLastError());
   }
-  if (direct)
-    if (int rc = ring_done(h, slot)) return rc;              // (the slot is free once the kernel has run)
-  if (h->dpose.p) {                                    // a logged step, as a lone ekf_predict
-    launch_pose_step(h->stream, pending_view(h, 0, h->batch), pose_log(h, (long)(h->pose_steps % h->pose_cap)));
+  if (int rc = ring_launched(h, r, direct)) return rc;
+  LogScope log(h, false);                              // a logged step, as a lone ekf_predict
+  if (log.pose) {
+    launch_pose_step(h->stream, pending_view(h, 0, h->batch), pose_log(h, h->pl_slot));
     HIP_TRY(h, hipGetLastError());
-    h->pose_steps += 1;
   }
+  log.commit();
   return EKF_OK;
 }
 
 extern "C" int ekf_update(ekf_handle* h, const int* idx, const double* range, const double* bearing,
                           const int* m, int stride) {
-  return do_step(h, FLAG_UPDATE, nullptr, nullptr, idx, range, bearing, m, stride);
+  return do_step(h, "ekf_update", FLAG_UPDATE, nullptr, nullptr, idx, range, bearing, m, stride);
 }
 
 extern "C" int ekf_step(ekf_handle* h, const double* lin, const double* ang, const int* idx,
                         const double* range, const double* bearing, const int* m, int stride) {
-  return do_step(h, FLAG_PREDICT | FLAG_UPDATE, lin, ang, idx, range, bearing, m, stride);
+  return do_step(h, "ekf_step", FLAG_PREDICT | FLAG_UPDATE, lin, ang, idx, range, bearing, m, stride);
 }
 
 // ---- localisation on a frozen map (ekf_localize_step / _update / _run; k_loc_solve + k_loc_rows, ekf_localize.hip) ----
@@ -2456,7 +2419,6 @@ static int loc_half_failed(ekf_handle* h, int rc) {
 static int do_localize(ekf_handle* h, const char* fn, int base_flags, const double* lin, const double* ang, const int* idx,
                        const double* range, const double* bearing, const int* m, int stride) {
   if (!h) return EKF_ERR_ARG;
-  LogScope log_scope{h};
   if (int rc = check_host_bad(h, fn)) return rc;
   if (int rc = refresh_sizes(h)) return rc;
   const bool upd = (base_flags & FLAG_UPDATE) != 0, pred = (base_flags & FLAG_PREDICT) != 0;
@@ -2464,37 +2426,21 @@ static int do_localize(ekf_handle* h, const char* fn, int base_flags, const doub
   if (const char* why = plan_localize(h, pred, upd, lin, ang, idx, range, bearing, m, stride, lp)) return bad_arg(h, fn, why);
   if (int rc = loc_begin(h)) return rc;
   if (int rc = push_floor(h, false)) return rc;
-  const bool direct = small_path(h);                     // (the workgroups fetch their records from the pinned ring: see do_step)
-  const bool logged = h->dinnov.p && upd;                // (a lone prediction is not a logged step)
-  h->pl_slot = h->dpose.p ? (long)(h->pose_steps % h->pose_cap) : -1;
+  const bool direct = small_path(h);
+  LogScope log(h, upd);
   for (int p = 0; p < lp.passes; ++p) {
-    h->lg_slot = logged ? (long)(h->innov_steps % h->innov_cap) : -1;
-    h->lg_jbase = MMAX * p;
-    int slot;
-    if (int rc = ring_take(h, &slot)) return p ? loc_half_failed(h, rc) : rc;
-    StepIn* hs = h->h_ring.p + (size_t)slot * h->batch;
-    StepIn* ds = h->d_ring.p + (size_t)slot * h->batch;
-    const int flags = (upd ? FLAG_UPDATE : 0) | ((pred && p == 0) ? FLAG_PREDICT : 0);
-    for (int b = 0; b < h->batch; ++b) {
-      const int mb = (upd && h->cfg.enable_measurement_model) ? m[b] : 0;
-      const long off = (long)b * stride;
-      // (fill_step raises the host's bound over the pass's landmarks: a general row correlates the pose with the landmark it names)
-      fill_step(hs[b], h->n[b], h->neff[b], pred ? lin[b] : 0.0, pred ? ang[b] : 0.0, flags, idx ? idx + off : nullptr,
-                range ? range + off : nullptr, bearing ? bearing + off : nullptr, mb, p);
-      h->neff_enq[b] = h->opt_active_bound ? h->neff[b] : h->n[b];
-    }
-    if (!direct) {
-      if (hipMemcpyAsync(ds, hs, sizeof(StepIn) * h->batch, hipMemcpyHostToDevice, h->stream) != hipSuccess)
-        return loc_half_failed(h, fail(h, EKF_ERR_HIP, std::string(fn) + ": the records' upload failed"));
-      if (int rc = ring_done(h, slot)) return loc_half_failed(h, rc);
-    }
-    if (int rc = loc_pass(h, direct ? hs : ds, loc_rows_groups(loc_bound_hi(h)))) return loc_half_failed(h, rc);
-    if (direct)
-      if (int rc = ring_done(h, slot)) return loc_half_failed(h, rc);   // (the slot is free once the kernels have run)
+    log.pass(p);
+    RingSlot<StepIn> r;
+    if (int rc = ring_take(h, h->h_ring, h->d_ring, &r)) return p ? loc_half_failed(h, rc) : rc;
+    // (the fill raises the host's bound over the pass's landmarks: a general row correlates the pose with the landmark it names)
+    fill_step_records(h, pred, upd, lin, ang, idx, range, bearing, m, stride, p, r.hs);
+    const StepIn* in;
+    if (int rc = ring_submit(h, r, direct, (size_t)h->batch, &in)) return loc_half_failed(h, rc);
+    if (int rc = loc_pass(h, in, loc_rows_groups(loc_bound_hi(h)))) return loc_half_failed(h, rc);
+    if (int rc = ring_launched(h, r, direct)) return loc_half_failed(h, rc);
   }
-  if (logged) h->innov_steps += 1;
   if (int rc = loc_pose_row(h)) return loc_half_failed(h, rc);
-  if (h->dpose.p) h->pose_steps += 1;
+  log.commit();
   return EKF_OK;
 }
 
@@ -2531,19 +2477,15 @@ extern "C" int ekf_localize_run(ekf_handle* h, int first, int count) {
   if (count == 0) return EKF_OK;
   if (int rc = loc_begin(h)) return rc;
   if (int rc = push_floor(h, true)) return rc;
-  LogScope log_scope{h};
-  const long cap = h->innov_cap, pcap = h->pose_cap;
+  LogScope log(h, true, count);
   const int* own_last = h->stream_own.data() + (size_t)(first + count - 1) * h->batch;
   const int groups = loc_rows_groups(loc_bound_hi(h, own_last));
   for (int k = first; k < first + count; ++k) {
-    h->lg_slot = h->dinnov.p ? (long)((h->innov_steps + (k - first)) % cap) : -1;
-    h->lg_jbase = 0;
-    h->pl_slot = h->dpose.p ? (long)((h->pose_steps + (k - first)) % pcap) : -1;
+    log.step(k - first);
     if (int rc = loc_pass(h, h->d_stream.p + (size_t)k * h->batch, groups)) return loc_half_failed(h, rc);
     if (int rc = loc_pose_row(h)) return loc_half_failed(h, rc);
   }
-  if (h->dinnov.p) h->innov_steps += count;
-  if (h->dpose.p) h->pose_steps += count;
+  log.commit();
   for (int b = 0; b < h->batch; ++b) {
     h->neff[b] = std::max(h->neff[b], std::min(h->n[b], own_last[b]));
     h->neff_enq[b] = h->opt_active_bound ? h->neff[b] : h->n[b];
@@ -2564,7 +2506,6 @@ extern "C" int ekf_localize_detections(ekf_handle* h, const double* lin, const d
   const char* fn = "ekf_localize_detections";
   if (!h) return EKF_ERR_ARG;
   HIP_TRY(h, hipSetDevice(h->device));
-  LogScope log_scope{h};
   if (int rc = check_host_bad(h, fn)) return rc;
   LocDetPlan lp;
   if (const char* why = plan_localize_detections(h, lin, ang, count, tag_id, pose_t, pose_err, stride, lp)) return bad_arg(h, fn, why);
@@ -2575,30 +2516,8 @@ extern "C" int ekf_localize_detections(ekf_handle* h, const double* lin, const d
     HIP_TRY(h, hipMemsetAsync(h->d_unmatched.p, 0, sizeof(LocUnmatched) * h->batch, h->stream));
   }
   if (int rc = push_floor(h, false)) return rc;
-  int slot;
-  if (int rc = ring_take(h, &slot)) return rc;
-  DetIn* hs = h->h_det.p + (size_t)slot * h->batch;
-  DetIn* ds = h->d_det.p + (size_t)slot * h->batch;
-  for (int b = 0; b < h->batch; ++b) {
-    DetIn& d = hs[b];
-    d.lin = lin[b];
-    d.ang = ang[b];
-    d.count = count[b];
-    d.pad = 0;
-    for (int i = 0; i < count[b]; ++i) {
-      const long e = (long)b * stride + i;
-      d.tag_id[i] = tag_id[e];
-      d.pose_err[i] = pose_err[e];
-      d.pose_t[i][0] = pose_t[3 * e];
-      d.pose_t[i][1] = pose_t[3 * e + 1];
-      d.pose_t[i][2] = pose_t[3 * e + 2];
-    }
-  }
-  // the host's view of the active bound must be on the device before the first device-side window
-  if (!h->sizes_dirty)
-    HIP_TRY(h, hipMemcpyAsync(h->dneff.p, h->neff.data(), sizeof(int) * h->batch, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(ds, hs, sizeof(DetIn) * h->batch, hipMemcpyHostToDevice, h->stream));
-  if (int rc = ring_done(h, slot)) return rc;
+  const DetIn* ds;
+  if (int rc = upload_detections(h, lin, ang, count, tag_id, pose_t, pose_err, stride, &ds)) return rc;
   h->acfg.active_bound = h->opt_active_bound;
   ProfBracket pb;
   if (int rc = prof_open(h, 11, h->stream, &pb)) return rc;
@@ -2607,16 +2526,13 @@ extern "C" int ekf_localize_detections(ekf_handle* h, const double* lin, const d
   if (int rc = prof_close(h, &pb)) return loc_half_failed(h, rc);
   if (hipGetLastError() != hipSuccess) return loc_half_failed(h, fail(h, EKF_ERR_HIP, std::string(fn) + ": the association's launch failed"));
   h->sizes_dirty = true;
-  const bool logged = h->dinnov.p != nullptr;
-  h->pl_slot = h->dpose.p ? (long)(h->pose_steps % h->pose_cap) : -1;
+  LogScope log(h, true);
   for (int p = 0; p < lp.passes; ++p) {
-    h->lg_slot = logged ? (long)(h->innov_steps % h->innov_cap) : -1;
-    h->lg_jbase = MMAX * p;
+    log.pass(p);
     if (int rc = loc_pass(h, h->d_assoc_step.p + (size_t)p * h->batch, lp.groups)) return loc_half_failed(h, rc);
   }
-  if (logged) h->innov_steps += 1;
   if (int rc = loc_pose_row(h)) return loc_half_failed(h, rc);
-  if (h->dpose.p) h->pose_steps += 1;
+  log.commit();
   return EKF_OK;
 }
 
@@ -2652,7 +2568,7 @@ extern "C" int ekf_step_fetch(ekf_handle* h, const double* lin, const double* an
     if (int rc = pack_buffer(h)) return rc;
     want = b;
   }
-  const int rc_step = do_step(h, FLAG_PREDICT | FLAG_UPDATE, lin, ang, idx, range, bearing, m, stride, want);
+  const int rc_step = do_step(h, "ekf_step_fetch", FLAG_PREDICT | FLAG_UPDATE, lin, ang, idx, range, bearing, m, stride, want);
   h->fetch_b = -1;
   if (rc_step) return rc_step;
   if (!h->fetched) return ekf_download_state(h, b, mu, P, n);
@@ -2706,17 +2622,17 @@ extern "C" int ekf_stream_upload(ekf_handle* h, int steps, const double* lin, co
   if (!lin || !ang || !m || stride < 0) return fail(h, EKF_ERR_ARG, "ekf_stream_upload: NULL array");
   if (stride > MMAX) return fail(h, EKF_ERR_ARG, "ekf_stream_upload: stride must be <= EKF_MMAX");
   const size_t count = (size_t)steps * h->batch;
-  // validate the whole stream before anything of the previous one is replaced
-  std::vector<unsigned char> seen;
-  for (int k = 0; k < steps; ++k)
-    for (int b = 0; b < h->batch; ++b) {
-      const size_t e = (size_t)k * h->batch + b;
-      const int mb = h->cfg.enable_measurement_model ? m[e] : 0;
-      if (m[e] < 0 || m[e] > stride) return fail(h, EKF_ERR_ARG, "ekf_stream_upload: m out of range");
-      if (mb > 0 && (!idx || !range || !bearing)) return fail(h, EKF_ERR_ARG, "ekf_stream_upload: NULL observation arrays");
-      if (mb > 0)
-        if (const char* why = validate_obs(h, b, idx + e * stride, mb, seen)) return fail(h, EKF_ERR_ARG, why);
-    }
+  // validate the whole stream before anything of the previous one is replaced: every count (also with the measurement
+  // model off, where a single step's counts are not read), then each step as ekf_step checks a call
+  for (size_t e = 0; e < count; ++e)
+    if (m[e] < 0 || m[e] > stride) return fail(h, EKF_ERR_ARG, "ekf_stream_upload: m out of range");
+  for (int k = 0; k < steps; ++k) {
+    const size_t e = (size_t)k * h->batch, o = e * stride;
+    ObsPlan op;
+    if (const char* why = plan_obs_lists(h, true, true, true, lin + e, ang + e, idx ? idx + o : nullptr, range ? range + o : nullptr,
+                                         bearing ? bearing + o : nullptr, m + e, stride, op))
+      return bad_arg(h, "ekf_stream_upload", why);
+  }
   std::vector<StepIn> host(count);
   h->stream_mhi.assign(steps, 0);
   h->stream_m.assign(count, 0);
@@ -2760,27 +2676,18 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
       return fail(h, EKF_ERR_STATE, "ekf_stream_run: the uploaded stream observes landmarks the current state does not have");
   HIP_TRY(h, hipSetDevice(h->device));
   if (int rc = push_floor(h, true)) return rc;
-  // (innovation log: stream step t goes to ring row (lg_tslot + t) % innov_cap, i.e. step `first` to row innov_steps)
-  LogScope log_scope{h};
-  const long cap = h->innov_cap;
-  if (h->dinnov.p) h->lg_tslot = (long)(((h->innov_steps - first) % cap + cap) % cap);
-  const long pcap = h->pose_cap;                       // (the pose log: the same numbering on its own counter)
-  if (h->dpose.p) h->pl_tslot = (long)(((h->pose_steps - first) % pcap + pcap) % pcap);
-  auto log_at = [&](int k) {
-    h->lg_slot = h->dinnov.p ? (h->lg_tslot + k) % cap : -1;
-    h->pl_slot = h->dpose.p ? (h->pl_tslot + k) % pcap : -1;
-  };
+  LogScope log(h, true, count);
+  log.stream(first);
   if (small_path(h) && count > 0) {
     // the whole range as ONE launch (in pieces of 4096 steps: a bounded kernel), P resident in LDS across all its steps
     for (int k = first; k < first + count; k += 4096) {
-      log_at(k);
+      log.step(k - first);
       if (int rc = enqueue_small(h, h->d_stream.p + (size_t)k * h->batch, std::min(4096, first + count - k))) return rc;
     }
     for (int b = 0; b < h->batch; ++b)
       h->neff[b] = std::max(h->neff[b], std::min(h->n[b], h->stream_own[(size_t)(first + count - 1) * h->batch + b]));
     h->neff_enq = h->neff;
-    if (h->dinnov.p) h->innov_steps += count;
-    if (h->dpose.p) h->pose_steps += count;
+    log.commit();
     return EKF_OK;
   }
   for (int k = first; k < first + count;) {
@@ -2833,13 +2740,12 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
     }
     for (int b = 0; b < h->batch; ++b)
       h->neff_enq[b] = std::min(h->n[b], std::max(h->floor_host[b], h->stream_own[(size_t)k * h->batch + b]));
-    log_at(k);
+    log.step(k - first);
     if (int rc = enqueue_pass(h, h->d_stream.p + (size_t)k * h->batch, h->stream_mhi[k])) return rc;
     if (int rc = log_pose_step(h)) return rc;
     ++k;
   }
-  if (h->dinnov.p) h->innov_steps += count;
-  if (h->dpose.p) h->pose_steps += count;
+  log.commit();
   if (count > 0)
     for (int b = 0; b < h->batch; ++b)
       h->neff[b] = std::max(h->neff[b], std::min(h->n[b], h->stream_own[(size_t)(first + count - 1) * h->batch + b]));

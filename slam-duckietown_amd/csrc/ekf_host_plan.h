@@ -659,16 +659,68 @@ inline int plan_small(const HostPlan* h, int n_hi) {
 // Validate one trajectory's whole observation list (all device passes of it) before any handle state changes:
 // indices inside the current state, no index twice (the reference keys observations by landmark index,
 // replay_no_ros.py:312-313).
+// `unique` = false: an index may come twice (localisation on a frozen map, see plan_obs_lists).
 // Returns nullptr when the list is good, else what is wrong with it.
-inline const char* validate_obs(const HostPlan* h, int b, const int* idx, int m, std::vector<unsigned char>& seen) {
+inline const char* validate_obs(const HostPlan* h, int b, const int* idx, int m, std::vector<unsigned char>& seen, bool unique = true) {
   const int n_lm = (h->n[b] - 3) / 2;
-  seen.assign((size_t)std::max(n_lm, 1), 0);
+  if (unique) seen.assign((size_t)std::max(n_lm, 1), 0);
   for (int i = 0; i < m; ++i) {
     const int id = idx[i];
     if (id < 0 || id >= n_lm) return "landmark index outside the current state (add_landmarks first)";
+    if (!unique) continue;
     if (seen[id]) return "duplicate landmark index in one update (the reference keys observations by index, replay_no_ros.py:312-313)";
     seen[id] = 1;
   }
+  return nullptr;
+}
+
+// ---- the observation lists of ekf_step / _update / _predict, ekf_localize_step / _update, and ekf_stream_upload per stream step ----
+// One call's arguments checked before any handle state changes, in this order: lin / ang where the call predicts, m and the
+// stride, every count in [0, stride], the observation arrays where anything is observed, every index inside its trajectory's map
+// (validate_obs).  `unique`: SLAM refuses an index that comes twice in one trajectory's list; the frozen-map update is defined
+// for it (the second observation is linearised at the pose the first one left, the landmark has not moved).  With the measurement
+// model off neither counts nor lists are read.  m_hi: the most observations of any trajectory; more than MMAX of them run in
+// `passes` device passes, the prediction in the first one only (fill_step cuts the list).  Returns nullptr, or what is wrong.
+struct ObsPlan { int m_hi = 0, passes = 1; };
+inline int loc_passes(int m_hi) { return std::max(1, (m_hi + MMAX - 1) / MMAX); }
+inline const char* plan_obs_lists(const HostPlan* h, bool pred, bool upd, bool unique, const double* lin, const double* ang, const int* idx,
+                                  const double* range, const double* bearing, const int* m, int stride, ObsPlan& op) {
+  if (pred && (!lin || !ang)) return "NULL lin/ang";
+  if (upd && (!m || stride < 0)) return "NULL m / bad stride";
+  op.m_hi = 0;
+  if (upd && h->cfg.enable_measurement_model)
+    for (int b = 0; b < h->batch; ++b) {
+      if (m[b] < 0 || m[b] > stride) return "m[b] must be in [0, stride]";
+      op.m_hi = std::max(op.m_hi, m[b]);
+    }
+  if (op.m_hi > 0 && (!idx || !range || !bearing)) return "NULL observation arrays";
+  if (op.m_hi > 0) {
+    std::vector<unsigned char> seen;
+    for (int b = 0; b < h->batch; ++b)
+      if (const char* why = validate_obs(h, b, idx + (long)b * stride, m[b], seen, unique)) return why;
+  }
+  op.passes = loc_passes(op.m_hi);
+  return nullptr;
+}
+
+// ---- the detection windows of ekf_step_detections and ekf_localize_detections: lin, ang, count and the stride; every count in
+// [0, min(stride, EKF_DMAX)]; the detection arrays where anything is detected.  *m_hi: the most distinct tag ids of any window,
+// capped at AMAX -- an upper bound of what the device matches (ignored, gated, unknown and bad ids count), the bound both entries
+// select their kernels by; 0 with the measurement model off.  Returns nullptr, or what is wrong (then *m_hi is not written).
+inline const char* plan_det_windows(const HostPlan* h, const double* lin, const double* ang, const int* count, const int* tag_id,
+                                    const double* pose_t, const double* pose_err, int stride, int* m_hi) {
+  if (!lin || !ang || !count || stride < 0) return "NULL array";
+  int hi = 0;
+  for (int b = 0; b < h->batch; ++b) {
+    const int c = count[b];
+    if (c < 0 || c > stride || c > DMAX) return "count must be <= min(stride, EKF_DMAX)";
+    if (c > 0 && (!tag_id || !pose_t || !pose_err)) return "NULL detection arrays";
+    const int* ids = c > 0 ? tag_id + (long)b * stride : nullptr;
+    int distinct = 0;
+    for (int i = 0; i < c; ++i) distinct += std::find(ids, ids + i, ids[i]) == ids + i ? 1 : 0;
+    hi = std::max(hi, std::min(distinct, AMAX));
+  }
+  *m_hi = h->cfg.enable_measurement_model ? hi : 0;
   return nullptr;
 }
 
@@ -980,39 +1032,11 @@ inline const char* plan_predict_linear(const HostPlan* h, int b0, int count, con
 }
 
 // ---- localisation on a frozen map (ekf_localize_step / _update / _run: k_loc_solve + k_loc_rows, ekf_localize.hip) ----
-// The arguments of a step checked as ekf_step checks its own, in its order -- lin / ang where the call predicts, m and the stride,
-// every count in [0, stride], the observation arrays where anything is observed, every index inside its trajectory's map -- with
-// one difference: an index may come TWICE in one call.  The frozen-map update is defined for it (the second observation is
-// linearised at the pose the first one left, the landmark has not moved), where the SLAM update keys observations by index
-// (validate_obs).  A call with more than MMAX observations of a trajectory runs in loc_passes passes of two launches each, the
-// prediction in the first one only (fill_step cuts the list, as for do_step).
-// Returns nullptr, or what is wrong (then nothing of `lp` is to be used and no handle state has changed).
-struct LocPlan {
-  int m_hi = 0, passes = 1;
-};
-inline int loc_passes(int m_hi) { return std::max(1, (m_hi + MMAX - 1) / MMAX); }
+// The arguments of a step are plan_obs_lists' with an index allowed TWICE in one call; each of its passes is two launches.
+using LocPlan = ObsPlan;
 inline const char* plan_localize(const HostPlan* h, bool pred, bool upd, const double* lin, const double* ang, const int* idx,
                                  const double* range, const double* bearing, const int* m, int stride, LocPlan& lp) {
-  if (pred && (!lin || !ang)) return "NULL lin/ang";
-  if (upd && (!m || stride < 0)) return "NULL m / bad stride";
-  lp.m_hi = 0;
-  const bool meas = upd && h->cfg.enable_measurement_model;
-  if (meas)
-    for (int b = 0; b < h->batch; ++b) {
-      if (m[b] < 0 || m[b] > stride) return "m[b] must be in [0, stride]";
-      lp.m_hi = std::max(lp.m_hi, m[b]);
-    }
-  if (lp.m_hi > 0 && (!idx || !range || !bearing)) return "NULL observation arrays";
-  if (lp.m_hi > 0)
-    for (int b = 0; b < h->batch; ++b) {
-      const int n_lm = (h->n[b] - 3) / 2;
-      for (int i = 0; i < m[b]; ++i) {
-        const int id = idx[(long)b * stride + i];
-        if (id < 0 || id >= n_lm) return "landmark index outside the current state (add_landmarks first)";
-      }
-    }
-  lp.passes = loc_passes(lp.m_hi);
-  return nullptr;
+  return plan_obs_lists(h, pred, upd, false, lin, ang, idx, range, bearing, m, stride, lp);
 }
 // The column groups of k_loc_rows' grid: LOC_THREADS columns each, up to the largest active bound a record of the launch can
 // carry -- per trajectory the host's bound (which fill_step has raised over the call's landmarks) or the handle's floor,
@@ -1030,11 +1054,8 @@ inline int loc_bound_hi(const HostPlan* h, const int* own = nullptr) {
 }
 inline int loc_rows_groups(int n_hi) { return (std::max(n_hi, 3) + LOC_THREADS - 1) / LOC_THREADS; }
 
-// ekf_localize_detections (k_loc_associate -> k_loc_solve -> k_loc_rows): the arguments checked as ekf_step_detections checks its
-// own -- lin, ang, count, the stride, every count in [0, min(stride, EKF_DMAX)], the detection arrays where anything is detected --
-// and what the call launches.  m_hi: the most distinct tag ids of any trajectory's window, capped at AMAX (an upper bound of what
-// the device matches -- ignored, gated, unknown and bad ids count --, the bound ekf_step_detections selects its kernels by; 0 with
-// the measurement model off); passes: a second k_loc_solve / k_loc_rows pair on the update-only records where m_hi > MMAX.
+// ekf_localize_detections (k_loc_associate -> k_loc_solve -> k_loc_rows): the window checked by plan_det_windows, which gives
+// m_hi, and what the call launches.  passes: a second k_loc_solve / k_loc_rows pair on the update-only records where m_hi > MMAX.
 // groups: k_loc_rows' grid.  The device raises a trajectory's bound over the landmarks it matches, which the host does not know:
 // where anything may be matched the grid covers the largest state (n_max while the sizes are dirty), else the bound mirrors as
 // for the other localisation calls (loc_bound_hi); a workgroup beyond its trajectory's bound returns at once.
@@ -1045,22 +1066,8 @@ struct LocDetPlan {
 inline const char* plan_localize_detections(const HostPlan* h, const double* lin, const double* ang, const int* count,
                                             const int* tag_id, const double* pose_t, const double* pose_err, int stride,
                                             LocDetPlan& lp) {
-  if (!lin || !ang || !count || stride < 0) return "NULL array";
   int m_hi = 0;
-  for (int b = 0; b < h->batch; ++b) {
-    const int c = count[b];
-    if (c < 0 || c > stride || c > DMAX) return "count must be <= min(stride, EKF_DMAX)";
-    if (c > 0 && (!tag_id || !pose_t || !pose_err)) return "NULL detection arrays";
-    const long off = (long)b * stride;
-    int distinct = 0;
-    for (int i = 0; i < c; ++i) {
-      bool seen = false;
-      for (int k = 0; k < i; ++k) seen |= (tag_id[off + k] == tag_id[off + i]);
-      distinct += seen ? 0 : 1;
-    }
-    m_hi = std::max(m_hi, std::min(distinct, AMAX));
-  }
-  if (!h->cfg.enable_measurement_model) m_hi = 0;
+  if (const char* why = plan_det_windows(h, lin, ang, count, tag_id, pose_t, pose_err, stride, &m_hi)) return why;
   lp.m_hi = m_hi;
   lp.passes = m_hi > MMAX ? 2 : 1;
   const int n_hi = h->sizes_dirty ? h->n_max : *std::max_element(h->n.begin(), h->n.end());
@@ -1621,6 +1628,39 @@ inline void fill_step(StepIn& s, int n_b, int& bound, double lin, double ang, in
   bound = std::min(bound, n_b);
   s.neff = bound;                                      // (k_solve raises it to the handle's floor, see push_floor)
   s.pad = 0;
+}
+// Pass p of a call plan_obs_lists accepted, into out[0, batch): the prediction in pass 0 only.  Raises the host's bound neff[b] over
+// the pass's landmarks (fill_step) and sets neff_enq[b] to what the records carry.  Returns the most observations of any record.
+inline int fill_step_records(HostPlan* h, bool pred, bool upd, const double* lin, const double* ang, const int* idx, const double* range,
+                             const double* bearing, const int* m, int stride, int p, StepIn* out) {
+  const int flags = (upd ? FLAG_UPDATE : 0) | ((pred && p == 0) ? FLAG_PREDICT : 0);
+  int m_pass_hi = 0;
+  for (int b = 0; b < h->batch; ++b) {
+    const int mb = (upd && h->cfg.enable_measurement_model) ? m[b] : 0;
+    const long off = (long)b * stride;
+    fill_step(out[b], h->n[b], h->neff[b], pred ? lin[b] : 0.0, pred ? ang[b] : 0.0, flags, idx ? idx + off : nullptr,
+              range ? range + off : nullptr, bearing ? bearing + off : nullptr, mb, p);
+    m_pass_hi = std::max(m_pass_hi, out[b].m);
+    h->neff_enq[b] = h->opt_active_bound ? h->neff[b] : h->n[b];
+  }
+  return m_pass_hi;
+}
+// The batch's windows of a call plan_det_windows accepted, into out[0, batch): count[b] detections each, nothing beyond them is read.
+inline void fill_det_records(const HostPlan* h, const double* lin, const double* ang, const int* count, const int* tag_id,
+                             const double* pose_t, const double* pose_err, int stride, DetIn* out) {
+  for (int b = 0; b < h->batch; ++b) {
+    DetIn& d = out[b];
+    d.lin = lin[b];
+    d.ang = ang[b];
+    d.count = count[b];
+    d.pad = 0;
+    for (int i = 0; i < count[b]; ++i) {
+      const long e = (long)b * stride + i;
+      d.tag_id[i] = tag_id[e];
+      d.pose_err[i] = pose_err[e];
+      std::copy_n(pose_t + 3 * e, 3, d.pose_t[i]);
+    }
+  }
 }
 
 }  // namespace ekf

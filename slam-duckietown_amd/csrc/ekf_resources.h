@@ -209,5 +209,53 @@ template <class T, class B> struct StagedUpload {
   T* device() const { return dev.p; }
 };
 
+// The input ring: SLOTS slots of per-trajectory records, used in order.  The caller keeps the buffers -- a pinned and a device one
+// of SLOTS slots each; several pairs may share one ring -- and indexes them with the slot take() hands out.  The host may refill a
+// pinned slot once the work that read it has run, tracked per GROUP of slots: the group's event is recorded behind the work that
+// read its last slot and waited for when the ring comes round to its first slot again.  A call goes take, fill the pinned slot,
+// submit, launch, launched.  Staged (`direct` = false): submit copies the slot to the device, which the kernels read, and the slot
+// is done; direct: the kernels read the pinned slot itself and the slot is done behind their launch.  A call that fails between
+// take and the end leaves its group open with no event behind it: the next trip round waits for the whole stream.
+template <class B, int SLOTS, int GROUP> struct InputRing {
+  static_assert(SLOTS % GROUP == 0, "whole groups");
+  Event<B> ev[SLOTS / GROUP];
+  bool open[SLOTS / GROUP] = {};
+  int pos = 0;
+  Status ensure() {
+    for (auto& e : ev)
+      if (Status s = e.ensure(); !s.ok()) return s;
+    return {};
+  }
+  // (a failed take leaves the ring where it was: the slot has not been waited for)
+  Status take(typename B::Stream st, int* slot) {
+    const int s = pos, g = s / GROUP;
+    if (s % GROUP == 0) {
+      if (open[g]) {                                   // (a failed call left the group without its event)
+        if (int e = B::stream_wait(st)) return {e, 0};
+      } else if (Status w = ev[g].wait_if_recorded(); !w.ok()) {
+        return w;
+      }
+    }
+    pos = (s + 1) % SLOTS;
+    open[g] = true;
+    *slot = s;
+    return {};
+  }
+  Status submit(int slot, bool direct, void* dev, const void* host, size_t bytes, typename B::Stream st) {
+    if (direct) return {};
+    if (int e = B::copy_to_device(dev, host, bytes, st)) return {e, 0};
+    return done(slot, st);
+  }
+  Status launched(int slot, bool direct, typename B::Stream st) { return direct ? done(slot, st) : Status{}; }
+
+ private:
+  Status done(int slot, typename B::Stream st) {
+    if (slot % GROUP != GROUP - 1) return {};
+    if (Status s = ev[slot / GROUP].record(st); !s.ok()) return s;
+    open[slot / GROUP] = false;
+    return {};
+  }
+};
+
 }  // namespace res
 }  // namespace ekf

@@ -414,6 +414,164 @@ static void check_step_records(std::mt19937& rng) {
   }
 }
 
+// The shared planner of the observation lists (plan_obs_lists: ekf_step / _update / _predict, ekf_localize_step / _update,
+// ekf_stream_upload per step) in both modes, and the record fill of a planned call (fill_step_records).  Every call is generated
+// with its faults known -- a NULL it needs, a count outside [0, stride], an index outside the map, a duplicate -- and the planner
+// refuses exactly the calls that have one it reads; arrays have exactly the stated size.
+static void check_obs_planner(std::mt19937& rng) {
+  int refused = 0, accepted = 0, empty_null = 0, update_only = 0;
+  for (int it = 0; it < 6000; ++it) {
+    const int batch = rng() % 2 ? 1 : 3;
+    const int strides[] = {0, 1, 16, 17, 33}, stride = strides[rng() % 5];
+    std::vector<int> n;
+    for (int b = 0; b < batch; ++b) n.push_back(3 + 2 * (b == 0 ? 33 + (int)(rng() % 20) : b == 1 ? 1 + (int)(rng() % 5) : 17));
+    std::vector<int> neff;
+    for (int b = 0; b < batch; ++b) neff.push_back(3 + 2 * (int)(rng() % ((n[(size_t)b] - 3) / 2 + 1)));
+    HostPlan h = bank(3 + 2 * 60, n, neff);
+    h.cfg.enable_measurement_model = rng() % 4 != 0;
+    h.opt_active_bound = rng() % 5 != 0;
+    const bool meas = h.cfg.enable_measurement_model != 0, unique = rng() % 2 == 0;
+    const bool pred = rng() % 3 != 0, upd = !pred || rng() % 3 != 0;
+    // the call: distinct indices inside each map, in random order
+    std::vector<double> lin((size_t)batch, 0.004), ang((size_t)batch, 0.02), range((size_t)batch * stride), bearing((size_t)batch * stride);
+    std::vector<int> idx((size_t)batch * stride, 0), m((size_t)batch, 0);
+    const bool nothing = rng() % 6 == 0;
+    for (int b = 0; b < batch; ++b) {
+      const int nl = (n[(size_t)b] - 3) / 2;
+      m[(size_t)b] = nothing ? 0 : (int)(rng() % (std::min(stride, nl) + 1));
+      std::vector<int> perm((size_t)nl);
+      for (int i = 0; i < nl; ++i) perm[(size_t)i] = i;
+      std::shuffle(perm.begin(), perm.end(), rng);
+      for (int i = 0; i < m[(size_t)b]; ++i) {
+        idx[(size_t)b * stride + i] = perm[(size_t)i];
+        range[(size_t)b * stride + i] = 1.0 + 0.01 * i + b;
+        bearing[(size_t)b * stride + i] = 0.1 - 0.001 * i;
+      }
+    }
+    // the faults
+    const bool null_motion = rng() % 8 == 0, null_m = rng() % 12 == 0, null_obs = rng() % 8 == 0;
+    bool bad_count = false, outside = false, dup = false;
+    const int fb = (int)(rng() % batch);
+    if (rng() % 8 == 0) {
+      m[(size_t)fb] = rng() % 2 ? stride + 1 : -1;
+      bad_count = true;
+    }
+    int m_hi = 0;
+    for (int b = 0; b < batch; ++b) m_hi = std::max(m_hi, m[(size_t)b]);
+    if (!bad_count && m[(size_t)fb] > 0 && rng() % 6 == 0) {
+      idx[(size_t)fb * stride + rng() % m[(size_t)fb]] = rng() % 2 ? (n[(size_t)fb] - 3) / 2 + (int)(rng() % 2) : -1;
+      outside = true;
+    }
+    if (!bad_count && !outside && m[(size_t)fb] > 1 && rng() % 6 == 0) {
+      const int i = 1 + (int)(rng() % (m[(size_t)fb] - 1));
+      idx[(size_t)fb * stride + i] = idx[(size_t)fb * stride + rng() % i];
+      dup = true;
+    }
+    const bool lists_read = upd && meas && !null_m && !bad_count && m_hi > 0;
+    const bool want_refused = (pred && null_motion) || (upd && null_m) || (upd && meas && !null_m && bad_count) ||
+                              (lists_read && (null_obs || outside || (unique && dup)));
+    const unsigned gone_motion = null_motion ? 1 + rng() % 3 : 0, gone_obs = null_obs ? 1 + rng() % 7 : 0;   // (bit sets: which are NULL)
+    const double *plin = gone_motion & 1 ? nullptr : lin.data(), *pang = gone_motion & 2 ? nullptr : ang.data();
+    const int* pidx = gone_obs & 1 ? nullptr : idx.data();
+    const double *prange = gone_obs & 2 ? nullptr : range.data(), *pbearing = gone_obs & 4 ? nullptr : bearing.data();
+    ObsPlan op;
+    const char* why = plan_obs_lists(&h, pred, upd, unique, plin, pang, pidx, prange, pbearing, null_m ? nullptr : m.data(), stride, op);
+    CHECK((why != nullptr) == want_refused,
+          "trial %d: %s (pred %d upd %d meas %d unique %d; NULL motion %d m %d lists %d; bad count %d outside %d dup %d; m_hi %d)", it,
+          why ? why : "accepted", pred, upd, meas, unique, null_motion, null_m, null_obs, bad_count, outside, dup, m_hi);
+    if (why) {
+      ++refused;
+      continue;
+    }
+    ++accepted;
+    const int want_hi = upd && meas ? m_hi : 0;        // (a direct count: nothing is observed with the model off or without an update)
+    CHECK(op.m_hi == want_hi && op.passes == std::max(1, (want_hi + MMAX - 1) / MMAX), "trial %d: m_hi %d passes %d for %d", it, op.m_hi,
+          op.passes, want_hi);
+    empty_null += want_hi == 0 && null_obs;
+    update_only += !pred && null_motion;
+    LocPlan lp;                                          // (what SLAM takes localisation takes, with the same plan)
+    CHECK(plan_localize(&h, pred, upd, plin, pang, pidx, prange, pbearing, null_m ? nullptr : m.data(), stride, lp) == nullptr &&
+              lp.m_hi == op.m_hi && lp.passes == op.passes, "trial %d: plan_localize differs", it);
+    // ---- the records of the planned call: fill_step_records against a plain loop over fill_step ----
+    HostPlan g = h, ref = h;
+    std::vector<int> got_idx[3];
+    for (int p = 0; p < op.passes; ++p) {
+      std::vector<StepIn> out((size_t)batch), want((size_t)batch);
+      std::memset(out.data(), 0xAB, sizeof(StepIn) * out.size());
+      std::memset(want.data(), 0xAB, sizeof(StepIn) * want.size());
+      const std::vector<int> before = g.neff;
+      const int pass_hi = fill_step_records(&g, pred, upd, plin, pang, pidx, prange, pbearing, null_m ? nullptr : m.data(), stride, p, out.data());
+      int want_pass_hi = 0;
+      for (int b = 0; b < batch; ++b) {
+        const long off = (long)b * stride;
+        fill_step(want[(size_t)b], ref.n[(size_t)b], ref.neff[(size_t)b], pred ? lin[(size_t)b] : 0.0, pred ? ang[(size_t)b] : 0.0,
+                  (upd ? FLAG_UPDATE : 0) | (pred && p == 0 ? FLAG_PREDICT : 0), pidx ? pidx + off : nullptr, prange ? prange + off : nullptr,
+                  pbearing ? pbearing + off : nullptr, upd && meas ? m[(size_t)b] : 0, p);
+        want_pass_hi = std::max(want_pass_hi, want[(size_t)b].m);
+        const StepIn& s = out[(size_t)b];
+        CHECK(((s.flags & FLAG_PREDICT) != 0) == (pred && p == 0) && ((s.flags & FLAG_UPDATE) != 0) == upd, "trial %d: flags of pass %d", it, p);
+        CHECK(g.neff[(size_t)b] >= before[(size_t)b] && g.neff[(size_t)b] <= g.n[(size_t)b] && s.neff == g.neff[(size_t)b], "trial %d: bound", it);
+        CHECK(g.neff_enq[(size_t)b] == (g.opt_active_bound ? g.neff[(size_t)b] : g.n[(size_t)b]), "trial %d: the enqueued bound", it);
+        for (int i = 0; i < s.m; ++i) got_idx[b].push_back(s.idx[i]);
+      }
+      CHECK(std::memcmp(out.data(), want.data(), sizeof(StepIn) * out.size()) == 0, "trial %d: pass %d differs from the plain loop", it, p);
+      CHECK(pass_hi == want_pass_hi, "trial %d: pass %d holds %d, reported %d", it, p, want_pass_hi, pass_hi);
+    }
+    CHECK(g.neff == ref.neff, "trial %d: bounds differ from the plain loop", it);
+    for (int b = 0; b < batch; ++b) {                    // every observation exactly once, in order
+      const int mb = upd && meas ? m[(size_t)b] : 0;
+      CHECK((int)got_idx[b].size() == mb, "trial %d: trajectory %d carries %zu of %d", it, b, got_idx[b].size(), mb);
+      for (int i = 0; i < mb; ++i) CHECK(got_idx[b][(size_t)i] == idx[(size_t)b * stride + i], "trial %d: order", it);
+    }
+  }
+  CHECK(refused > 1000 && accepted > 1000 && empty_null > 20 && update_only > 20, "coverage: %d refused, %d accepted, %d / %d", refused,
+        accepted, empty_null, update_only);
+}
+
+// fill_det_records: exactly count[b] detections per trajectory out of the strided arrays, which end with the last trajectory's
+// last detection (a read past count[b] there is a sanitizer report), nothing written past them.
+static void check_det_records(std::mt19937& rng) {
+  for (int it = 0; it < 2000; ++it) {
+    const int batch = rng() % 2 ? 1 : 3;
+    const int strides[] = {0, 1, 5, 40, DMAX}, stride = strides[rng() % 5];
+    HostPlan h = bank(3 + 2 * 10, std::vector<int>((size_t)batch, 3 + 2 * 10));
+    h.cfg.enable_measurement_model = 1;
+    std::vector<int> count;
+    for (int b = 0; b < batch; ++b) count.push_back(rng() % 4 == 0 ? 0 : (int)(rng() % (stride + 1)));
+    const size_t len = (size_t)(batch - 1) * stride + count.back();
+    std::vector<double> lin, ang, pose_t(3 * len), pose_err(len);
+    std::vector<int> tag_id(len);
+    for (int b = 0; b < batch; ++b) lin.push_back(0.01 * b + 0.001 * it), ang.push_back(-0.02 * b);
+    for (size_t e = 0; e < len; ++e) {
+      tag_id[e] = (int)(rng() % 50);
+      pose_err[e] = 0.5 + e;
+      for (int c = 0; c < 3; ++c) pose_t[3 * e + c] = 10.0 * e + c;
+    }
+    int m_hi = -1;
+    CHECK(plan_det_windows(&h, lin.data(), ang.data(), count.data(), len ? tag_id.data() : nullptr, len ? pose_t.data() : nullptr,
+                           len ? pose_err.data() : nullptr, stride, &m_hi) == nullptr && m_hi >= 0 && m_hi <= AMAX, "trial %d refused", it);
+    std::vector<DetIn> out((size_t)batch);
+    std::memset(out.data(), 0xAB, sizeof(DetIn) * out.size());
+    DetIn untouched;
+    std::memset(&untouched, 0xAB, sizeof untouched);
+    fill_det_records(&h, lin.data(), ang.data(), count.data(), len ? tag_id.data() : nullptr, len ? pose_t.data() : nullptr,
+                     len ? pose_err.data() : nullptr, stride, out.data());
+    for (int b = 0; b < batch; ++b) {
+      const DetIn& d = out[(size_t)b];
+      CHECK(d.lin == lin[(size_t)b] && d.ang == ang[(size_t)b] && d.count == count[(size_t)b] && d.pad == 0, "trial %d: head of %d", it, b);
+      for (int i = 0; i < DMAX; ++i) {
+        const size_t e = (size_t)b * stride + i;
+        if (i < count[(size_t)b])
+          CHECK(d.tag_id[i] == tag_id[e] && d.pose_err[i] == pose_err[e] && d.pose_t[i][0] == pose_t[3 * e] && d.pose_t[i][1] == pose_t[3 * e + 1] &&
+                    d.pose_t[i][2] == pose_t[3 * e + 2], "trial %d: detection %d of %d", it, i, b);
+        else
+          CHECK(d.tag_id[i] == untouched.tag_id[i] && std::memcmp(&d.pose_err[i], &untouched.pose_err[i], sizeof(double)) == 0 &&
+                    std::memcmp(d.pose_t[i], untouched.pose_t[i], 3 * sizeof(double)) == 0, "trial %d: entry %d of %d was written", it, i, b);
+      }
+    }
+  }
+}
+
 // The scaffold of the read-only queries and the log rings: bank_range_ok, pending_kb, plan_staging, ring_range_ok, ring_pieces.
 static void check_scaffold(std::mt19937& rng) {
   // the range check against its plain statement, sums in 64 bits; counts near INT_MAX must not overflow
@@ -551,6 +709,8 @@ int main() {
   check_planning(rng);
   check_launch_plans(rng);
   check_step_records(rng);
+  check_obs_planner(rng);
+  check_det_records(rng);
   check_scaffold(rng);
   std::printf("host_plan_check: %ld checks passed\n", checks);
   return 0;

@@ -111,6 +111,7 @@ int main() {
   }
   // ---- randomised windows, arrays of exactly the stated size ----
   std::mt19937 rng(11);
+  int over_amax = 0;
   for (int trial = 0; trial < 300; ++trial) {
     const int batch = 1 + (int)(rng() % 4), stride = (int)(rng() % 90);
     std::vector<int> n, neff, count;
@@ -138,11 +139,17 @@ int main() {
     }
     CHECK(c.plan(r, lp) == nullptr, "trial %d refused", trial);
     CHECK(lp.m_hi == want && lp.passes == (want > MMAX ? 2 : 1), "trial %d: m_hi %d (want %d) passes %d", trial, lp.m_hi, want, lp.passes);
+    // ekf_step_detections plans the same window with plan_det_windows alone: the same bound, repeated ids and more than AMAX included
+    int step_hi = -1;
+    CHECK(plan_det_windows(&r, c.lin.data(), c.ang.data(), c.count.data(), c.tag_id.data(), c.pose_t.data(), c.pose_err.data(), stride,
+                           &step_hi) == nullptr && step_hi == lp.m_hi, "trial %d: the two detection entries plan m_hi %d and %d", trial, step_hi, lp.m_hi);
+    over_amax += want == AMAX;
     const int n_hi = *std::max_element(n.begin(), n.end());
     CHECK(lp.groups >= 1 && lp.groups <= loc_rows_groups(r.n_max), "trial %d: groups %d", trial, lp.groups);
     if (!r.sizes_dirty && want > 0) CHECK(lp.groups * LOC_THREADS >= n_hi && lp.groups == loc_rows_groups(n_hi), "trial %d: the grid covers every state", trial);
     if (r.sizes_dirty) CHECK(lp.groups == loc_rows_groups(r.n_max), "trial %d: dirty", trial);
   }
+  CHECK(over_amax > 0, "no random window reached the cap of AMAX distinct ids");
   std::printf("%ld checks passed\n", checks);
   return 0;
 }

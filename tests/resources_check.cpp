@@ -10,6 +10,9 @@
 // Asserted: nothing live at the end and no double free; a failed group leaves every member empty and its retry succeeds; a
 // buffer is never freed while a stream still uses it; a pinned copy is never handed out between a commit and the wait for that
 // commit's event; every group reports "new" exactly once per allocation.  tests/test_cpu_host.py builds and runs it (CPU only).
+// The input ring (InputRing) is driven in the order the step entries drive it, both paths mixed: a pinned slot is never handed
+// out between its upload (staged path) or its launch (direct path) and the wait for its group's event, a take behind a failed
+// call waits for the stream once and the ring goes on.
 // Only the TYPES are under test here: ring_resize and upload below restate what the call sites of ekf_api.hip do with them and
 // share no code with them, so a call site that drifted (no release before the new ring, the wrong copy of a pair) is not seen
 // here -- the call sites are covered by the GPU tests (tests/test_gpu_cadence.py::test_run_plan_copies_regrow_on_one_handle,
@@ -37,13 +40,13 @@ struct World {
   long calls = 0, fail_at = -1;
   bool failed = false;                                 // the injected failure has happened
   std::set<void*> device, pinned;
+  std::map<const void*, size_t> extent;                // allocation -> its bytes
   std::set<int> events;
   int next_event = 1;
   std::map<const void*, int> used_on;                  // buffer -> stream whose work in flight uses it
   std::map<const void*, int> upload_event;             // pinned copy -> event behind the upload that still reads it
   std::map<const void*, int> upload_bare;              // pinned copy -> stream of an upload with no event behind it (yet)
   std::map<int, int> recorded_on;                      // event (recorded, not yet waited for) -> stream
-  const void* last_copy_src = nullptr;
 };
 static World* W = nullptr;
 
@@ -81,7 +84,16 @@ struct CountingBackend {
     *p = std::malloc(bytes);
     std::memset(*p, 0xAB, bytes);
     live.insert(*p);
+    W->extent[*p] = bytes;
     return 0;
+  }
+  // [p, p + bytes) lies inside one live allocation of `live` (the ring's slots are parts of their buffers)
+  static bool inside(const std::set<void*>& live, const void* p, size_t bytes) {
+    auto it = W->extent.upper_bound(p);
+    if (it == W->extent.begin()) return false;
+    --it;
+    const char *base = static_cast<const char*>(it->first), *q = static_cast<const char*>(p);
+    return live.count(const_cast<void*>(it->first)) == 1 && q + bytes <= base + it->second;
   }
   static int release(std::set<void*>& live, const char* name, void* p) {
     const bool fail = hit(name, p, 0);
@@ -89,6 +101,7 @@ struct CountingBackend {
     CHECK(W->used_on.count(p) == 0, "%s of %p while stream %d still uses it", name, p, W->used_on[p]);
     CHECK(!uploading(p), "%s of %p while its upload has not run", name, p);
     live.erase(p);
+    W->extent.erase(p);
     std::free(p);
     return fail ? ERR : 0;
   }
@@ -115,11 +128,14 @@ struct CountingBackend {
     CHECK(W->events.count(e) == 1, "record of event %d", e);
     event_done(e);                                     // (a new record replaces the old one)
     W->recorded_on[e] = st;
-    if (W->last_copy_src) {
-      W->upload_event[W->last_copy_src] = e;
-      W->upload_bare.erase(W->last_copy_src);
-    }
-    W->last_copy_src = nullptr;
+    // (stream order: the event is behind every upload enqueued on the stream so far, not only the last one)
+    for (auto it = W->upload_bare.begin(); it != W->upload_bare.end();)
+      if (it->second == st) {
+        W->upload_event[it->first] = e;
+        it = W->upload_bare.erase(it);
+      } else {
+        ++it;
+      }
     return 0;
   }
   static int event_wait(Event e) {
@@ -136,11 +152,11 @@ struct CountingBackend {
   }
   static int copy_to_device(void* dst, const void* src, size_t bytes, Stream st) {
     if (hit("copy_to_device", src, (long)bytes)) return ERR;
-    CHECK(W->device.count(dst) == 1 && W->pinned.count(const_cast<void*>(src)) == 1, "copy %p <- %p", dst, src);
+    CHECK(inside(W->device, dst, bytes) && inside(W->pinned, src, bytes), "copy %p <- %p", dst, src);
     std::memcpy(dst, src, bytes);                      // (the sanitizer checks both capacities)
     W->used_on[dst] = st;
+    W->upload_event.erase(src);
     W->upload_bare[src] = st;                          // (until the event behind it is recorded only the stream can be waited for)
-    W->last_copy_src = src;
     return 0;
   }
 };
@@ -167,7 +183,8 @@ struct Handle {
   PBuf<long> h_ring;
   PBuf<unsigned> h_flags;
   PBuf<double> h_pack{7};                              // (the one allocated with a flag of its own, on first use)
-  Ev ev_fork, ev_pass, ring_ev[RING / 4], t0, t1;
+  Ev ev_fork, ev_pass, t0, t1;
+  InputRing<B, RING, 4> ring;                          // (the slots of h_ring / d_ring)
   std::vector<Ev> prof_pool;
   // first-use groups
   DBuf<int> dtagmap, dneff;
@@ -298,15 +315,14 @@ static std::vector<Step> script() {
     if (Status st = h.d_ring.ensure(BATCH * RING); !st.ok()) return st;
     if (Status st = h.h_ring.ensure(BATCH * RING); !st.ok()) return st;
     if (Status st = h.h_flags.ensure(BATCH); !st.ok()) return st;
-    for (auto& e : h.ring_ev)
-      if (Status st = e.ensure(); !st.ok()) return st;
+    if (Status st = h.ring.ensure(); !st.ok()) return st;
     if (Status st = h.t0.ensure(true); !st.ok()) return st;
     return h.t1.ensure(true);
   });
   // ---- the step ring's events: recorded per group of slots, waited for only once recorded ----
   single("ring events", [](Handle& h) {
     for (int round = 0; round < 2; ++round)
-      for (auto& e : h.ring_ev) {
+      for (auto& e : h.ring.ev) {
         const long before = W->calls;
         const bool recorded = e.recorded;
         if (Status st = e.wait_if_recorded(); !st.ok()) return st;
@@ -314,6 +330,45 @@ static std::vector<Step> script() {
         if (Status st = e.record(STREAM); !st.ok()) return st;
         CHECK(e.recorded, "record sets the bit");
       }
+    return Status{};
+  });
+  // ---- the input ring itself, as the step entries of ekf_api.hip drive it: 3 x RING calls of take, fill, submit, launch,
+  //      launched, the staged and the direct order mixed.  A call that fails returns at once (the entry's early return); the
+  //      retry goes on from wherever the ring stands, with the failed call's group left open ----
+  single("input ring", [](Handle& h) {
+    for (int i = 0; i < 3 * RING; ++i) {
+      const bool direct = i % 3 == 1;
+      const int s = h.ring.pos, g = s / 4;
+      const bool was_open = h.ring.open[g], recorded = h.ring.ev[g].recorded;
+      const long before = W->calls;
+      int slot = -1;
+      if (Status st = h.ring.take(STREAM, &slot); !st.ok()) {
+        CHECK(h.ring.pos == s && h.ring.open[g] == was_open, "a failed take leaves the ring where it was");
+        return st;
+      }
+      CHECK(slot == s && h.ring.pos == (s + 1) % RING && h.ring.open[g], "slots are handed out in order: %d at %d", slot, s);
+      const std::string waited = W->calls > before ? W->log[(size_t)before].name : "";
+      if (s % 4 != 0) CHECK(W->calls == before, "inside a group nothing is waited for");
+      else if (was_open) CHECK(W->calls == before + 1 && waited == "stream_wait", "a group a failed call left open: the stream is waited for, once");
+      else CHECK(W->calls == before + (recorded ? 1 : 0) && (!recorded || waited == "event_wait"), "the group's event is waited for, if recorded");
+      long *hs = h.h_ring.p + (size_t)slot * BATCH, *ds = h.d_ring.p + (size_t)slot * BATCH;
+      CHECK(!B::uploading(hs), "slot %d was handed out while the work that reads it had not run", slot);
+      for (int b = 0; b < BATCH; ++b) hs[b] = 100L * i + b;
+      if (Status st = h.ring.submit(slot, direct, ds, hs, sizeof(long) * BATCH, STREAM); !st.ok()) {
+        CHECK(h.ring.open[g], "a failed submit leaves the group open");
+        return st;
+      }
+      if (direct) W->upload_bare[hs] = STREAM;           // the launch marker: a kernel on the stream reads the pinned slot itself
+      else CHECK(ds[BATCH - 1] == 100L * i + BATCH - 1 && B::uploading(hs), "the staged path copies the slot");
+      in_flight(h.d_ring, STREAM);
+      if (Status st = h.ring.launched(slot, direct, STREAM); !st.ok()) {
+        CHECK(h.ring.open[g], "a failed record leaves the group open");
+        return st;
+      }
+      if (slot % 4 == 3)
+        CHECK(!h.ring.open[g] && W->upload_event.count(hs) == 1 && W->upload_event[hs] == h.ring.ev[g].ev,
+              "the group's event is behind the work that read its last slot");
+    }
     return Status{};
   });
   // ---- first-use allocations ----

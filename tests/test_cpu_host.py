@@ -257,9 +257,11 @@ def test_every_entry_point_selects_its_device():
     # (device work: a runtime call, a launcher, or an allocating, uploading or event method of the ownership types of
     #  csrc/ekf_resources.h, through which those runtime calls now go -- `begin` with arguments: not a container's)
     gpu = re.compile(r"\bhip(?!SetDevice)[A-Z]\w*\s*\(|\blaunch_\w+\s*\(|\bdense_propagate\s*\("
-                     r"|\.(?:ensure|reserve|commit|record|wait_if_recorded)\s*\(|\.begin\s*\(\s*[^\s)]|\b(?:ensure_group|release_group)\b[^(\n]*\(")
+                     r"|\.(?:ensure|reserve|commit|record|wait_if_recorded|take|submit|launched)\s*\(|\.begin\s*\(\s*[^\s)]"
+                     r"|\b(?:ensure_group|release_group)\b[^(\n]*\(")
     for site in ("h->dgate.ensure(", "h->noise.begin(rows", "h->noise.commit(", "h->d_stream.reserve(", "res::ensure_group(&fresh",
-                 "res::release_group<HipBackend>(h->stream", "h->t0.record(", "h->ring_ev[g].wait_if_recorded("):
+                 "res::release_group<HipBackend>(h->stream", "h->t0.record(", "h->ring.take(h->stream", "h->ring.submit(r.slot",
+                 "h->ring.launched(r.slot"):
         assert site in text and gpu.search(site), site       # the pattern sees the sites it is meant for
     assert not gpu.search("std::max_element(h->n.begin(), h->n.end())")
 
@@ -370,7 +372,9 @@ def test_host_planning_logic_under_the_sanitizers(tmp_path):
     # the library itself is built from the same header (a stale copy would make this test vacuous)
     api = open(os.path.join(ROOT, "slam-duckietown_amd", "csrc", "ekf_api.hip")).read()
     assert '#include "ekf_host_plan.h"' in api and "struct ekf_handle : ekf::HostPlan" in api
-    for fn in ("plan_pass", "plan_cadences", "cadences_possible", "fill_step", "validate_obs", "build_pass_shares", "order_pass_shares",
+    # (validate_obs is reached through plan_obs_lists, the one planner of every entry's observation lists)
+    for fn in ("plan_pass", "plan_cadences", "cadences_possible", "fill_step", "plan_obs_lists", "plan_det_windows", "fill_step_records",
+               "fill_det_records", "build_pass_shares", "order_pass_shares",
                "plan_step", "pass_due_after_step", "plan_cadence_step", "plan_chain_run", "chain_gather_workgroups", "small_path",
                "plan_small"):
         assert re.search(r"\b%s\(" % fn, api), fn                      # called from the API ...
@@ -392,6 +396,7 @@ def test_handle_ownership_types_under_the_sanitizers(tmp_path):
     for name in ("DeviceBuf", "PinnedBuf", "StagedUpload", "Event"):
         assert re.search(r"using %s = res::%s<(T, )?HipBackend>;" % (name, name), api), name
         assert not re.search(r"\b(struct|class)\s+%s\b" % name, api), name
+    assert "using InputRing = res::InputRing<HipBackend, RING, RING_GROUP>;" in api and not re.search(r"\b(struct|class)\s+InputRing\b", api)
     for fn in ("ensure_group", "release_group"):
         assert re.search(r"\bres::%s\b" % fn, api), fn
         assert not re.search(r"^(static|inline|template)[^\n;]*\b%s\(" % fn, api, flags=re.M), fn
