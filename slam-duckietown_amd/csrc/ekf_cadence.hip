@@ -96,11 +96,9 @@ __device__ __forceinline__ int cad_positions(const CadPlan& pl, const StepIn* __
   }
   int cnt = 0, lo = 0;
   if (tid < pl.ns) {
-    const StepIn* st = in + ((long)(pl.t0 + tid) * batch + b);
-    const int m = ((st->flags & FLAG_UPDATE) && cfg.enable_measurement_model) ? min(st->m, MMAX) : 0;
-    lo = tid == 0 ? pl.j0 : 0;
-    const int hi = tid == pl.ns - 1 ? min(pl.jend, m) : m;
-    cnt = max(hi - lo, 0);
+    const CadRange r = cad_step_range(pl, in + ((long)(pl.t0 + tid) * batch + b), tid, cfg.enable_measurement_model);
+    lo = r.lo;
+    cnt = r.cnt;
   }
   if (tid <= CAD_SLOTS) {
     cntS[tid] = tid < CAD_SLOTS ? cnt : 0;

@@ -1,5 +1,6 @@
-// Device-side helpers shared by the kernel translation units (ekf_kernels.hip, ekf_cadence.hip): LDS hand-off
-// macros, the measurement model of src/replay_no_ros.py:443-469, buffer-instruction accessors.  gfx950 only.
+// Device-side helpers shared by the kernel translation units: LDS hand-off macros, the motion model of
+// src/replay_no_ros.py:368-417 and the measurement model of :443-469, a cadence step's landmark range, buffer-instruction
+// accessors.  gfx950 only.
 #pragma once
 #include <type_traits>
 
@@ -77,6 +78,38 @@ __device__ __forceinline__ double wrap_pi(double a) {
   return r - M_PI;
 }
 
+// The motion model of src/replay_no_ros.py:368-417 at the pose (x, y, th): the new pose and G[0,2], G[1,2] of its Jacobian.
+// The ONE statement of it on the device: every kernel that predicts -- solve_body (ekf_kernels.hip), the cadence chain
+// (ekf_solve_cad_body.inc), small_step (ekf_small.hip), loc_solve_body (ekf_loc_chain.h) -- calls it; each keeps its own test
+// of the step's FLAG_PREDICT, its own way of fetching the pose and of publishing the result.  (disable_motion_model leaves the
+// pose and a zero Jacobian; the callers that test it in front of the call keep the branch their kernels had.)
+struct Motion {
+  double x, y, th, g0, g1;
+};
+__device__ __forceinline__ Motion motion_model(double x, double y, double th, double lin, double ang, const DeviceConfig& cfg) {
+  Motion r{x, y, th, 0.0, 0.0};
+  if (cfg.disable_motion_model) return r;
+  double s0, c0;
+  sincos(th, &s0, &c0);
+  if (cfg.enable_circular_interpolation && fabs(ang) > cfg.arc_threshold) {   // :390 arc
+    double s1, c1;
+    sincos(th + ang, &s1, &c1);
+    const double rr = lin / ang;
+    r.x += -rr * s0 + rr * s1;
+    r.y += rr * c0 - rr * c1;
+    r.th = wrap_pi(th + ang);                            // :397
+    r.g0 = -rr * c0 + rr * c1;                           // :401
+    r.g1 = -rr * s0 + rr * s1;                           // :402
+  } else {                                               // :376 straight / :405-417 linear mode
+    r.x += lin * c0;
+    r.y += lin * s0;
+    if (!cfg.enable_circular_interpolation) r.th = th + ang;   // no wrap (:409); :381 keeps theta
+    r.g0 = -lin * s0;
+    r.g1 = lin * c0;
+  }
+  return r;
+}
+
 // 1 / x from the hardware estimate (v_rcp_f64: ~1e-8 relative... in fact 2^-26) and two Newton steps -- each squares the error:
 // <= 1 ulp for finite NORMAL x whose reciprocal is normal too; inf / NaN / 0 behave like the IEEE division (1/0 = inf,
 // 1/inf = 0, NaN through).  Where the estimate itself is not finite or zero -- x subnormal (v_rcp_f64 gives inf there), 0 or
@@ -147,6 +180,20 @@ __device__ __forceinline__ double read_lane(double v, int src) {
 __device__ __forceinline__ void innovation(const LinGeom& g, double z_range, double z_bearing, double& y0, double& y1) {
   y0 = z_range - g.sq;                                            // :455
   y1 = wrap_pi(z_bearing - (atan2(g.dy, g.dx) - g.th));           // :453-458
+}
+
+// Touched step p of a cadence (CadPlan): its landmark count m (none while the measurement model is off) and the part of them
+// this cadence applies, [lo, lo + cnt) -- the first step starts at the plan's j0, the last one ends at its jend.  The ONE
+// statement of it: cad_positions (ekf_cadence.hip), the column gather of ekf_solve_cad_body.inc and k_innov_cad
+// (ekf_innovations.hip) each run their own prefix sum over cnt.
+struct CadRange {
+  int m, lo, cnt;
+};
+__device__ __forceinline__ CadRange cad_step_range(const CadPlan& pl, const StepIn* st, int p, int meas) {
+  const int m = ((st->flags & FLAG_UPDATE) && meas) ? min(st->m, MMAX) : 0;
+  const int lo = p == 0 ? pl.j0 : 0;
+  const int hi = p == pl.ns - 1 ? min(pl.jend, m) : m;
+  return CadRange{m, lo, max(hi - lo, 0)};
 }
 
 constexpr int RS_QSTRIDE = 32;          // k_flush_rs: words between the per-XCD queue heads (one cache line each)

@@ -8,6 +8,8 @@
 // filter's buffers only and wait for nothing.  (The small-state path keeps no records in memory: k_small_stream's LOG
 // instantiations write the log themselves, ekf_small.hip.)
 #include "ekf_device.h"
+
+#include "ekf_devfn.h"
 #include "ekf_launch.h"
 
 namespace ekf {
@@ -51,23 +53,22 @@ __global__ __launch_bounds__(64) void k_innov_step(const StepIn* __restrict__ in
 // row (slot0 + t) % cap, landmark j at position j; every touched step's row gets its full count (a step cut by a cadence
 // boundary is written by both cadences, its positions from j0 on by the second).  Steps that a later step of the same
 // launch overwrites in the ring (cap < ns) are skipped, so no two threads write one place.  One workgroup of 64 threads per
-// trajectory; cad_positions' arithmetic (ekf_cadence.hip), restated.
+// trajectory; the steps' ranges are cad_step_range's, the prefix sum over them is this kernel's own.
 __global__ __launch_bounds__(64) void k_innov_cad(const StepIn* __restrict__ in, const CadPlan* __restrict__ plan,
                                                   const CadOut* __restrict__ co, int meas, int gate, int batch, InnovLog lg) {
   static_assert(CAD_SLOTS <= 64, "one thread per touched step");
   __shared__ int cntS[CAD_SLOTS + 1], loS[CAD_SLOTS + 1], firstS[CAD_SLOTS + 1];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const CadPlan pl = plan[b];
-  const int ns = min(pl.ns, CAD_SLOTS);
+  CadPlan pl = plan[b];
+  pl.ns = min(pl.ns, CAD_SLOTS);
+  const int ns = pl.ns;
   const int pskip = ns - lg.cap;                             // steps p < pskip are overwritten by step p + cap
   int cnt = 0, lo = 0;
   if (tid < ns) {
-    const StepIn& st = in[(long)(pl.t0 + tid) * batch + b];
-    const int m = ((st.flags & FLAG_UPDATE) && meas) ? min(st.m, MMAX) : 0;
-    lo = tid == 0 ? pl.j0 : 0;
-    const int hi = tid == ns - 1 ? min(pl.jend, m) : m;
-    cnt = max(hi - lo, 0);
-    if (tid >= pskip) lg.m[(long)((lg.slot0 + pl.t0 + tid) % lg.cap) * batch + b] = m;
+    const CadRange r = cad_step_range(pl, in + ((long)(pl.t0 + tid) * batch + b), tid, meas);
+    lo = r.lo;
+    cnt = r.cnt;
+    if (tid >= pskip) lg.m[(long)((lg.slot0 + pl.t0 + tid) % lg.cap) * batch + b] = r.m;
   }
   if (tid <= CAD_SLOTS) {
     cntS[tid] = tid < CAD_SLOTS ? cnt : 0;

@@ -26,8 +26,6 @@ void launch_flush(hipStream_t st, const PassPlan& p, const BankView& k, const do
 // hand-out as planned (plan_pass), or one equal static share per workgroup (mode 4) where `shares` is given; wv: w_from_v
 void launch_flush_rs(hipStream_t st, const PassPlan& p, const BankView& k, const double* dacc, const int* shares, const CadOut* wv);
 int flush_rs_queue_words();
-void launch_associate(hipStream_t st, const BankView& k, const DetIn* det, int* tagmap, int* neff_dev, double* mu, StepIn* step_out,
-                      AssocOut* assoc_out, const AssocConfig& cfg, int n_max, int pending_k);
 // one trajectory: Pb, mub, flag_b are its covariance, mean and flags word
 void launch_add_landmarks(hipStream_t st, double* Pb, double* mub, int ld, int n_old, int n_new, double var, const double* xy);
 void launch_fill_diag(hipStream_t st, double* Pb, int ld, int n, const double* diag);
@@ -125,6 +123,10 @@ void launch_predict_pose(hipStream_t st, const PendingView& f, double* P, double
 void launch_loc_solve(hipStream_t st, const BankView& k, double* mu, const StepIn* in, const int* neff_floor, LocRec* rec,
                       const DeviceConfig& cfg);
 void launch_loc_rows(hipStream_t st, const BankView& k, const LocRec* rec, int groups);
+// ekf_step_detections (ekf_loc_assoc.hip): the whole bank, one DetIn each in `det`; writes the tag table, k.nact, the new landmarks'
+// means in `mu`, their rows / columns of k.P (zeros in k.V / k.W for the pending_k ranks), step_out, assoc_out, neff_dev, k.flags
+void launch_associate(hipStream_t st, const BankView& k, const DetIn* det, int* tagmap, int* neff_dev, double* mu, StepIn* step_out,
+                      AssocOut* assoc_out, const AssocConfig& cfg, int n_max, int pending_k);
 // ekf_localize_detections (ekf_loc_assoc.hip): the whole bank, one DetIn each in `det`; reads tagmap, k.nact and the pose in `mu`,
 // writes step_out[b] and step_out[k.batch + b] (what the two launch_loc_solve of the call read), assoc_out[b], unmatched[b],
 // neff_dev[b] (raised over the matched landmarks) and k.flags -- nothing else

@@ -1,174 +1,139 @@
-// k_loc_associate: the device-side front end of ekf_localize_detections (gfx950, wave64) -- one window of raw AprilTag detections
-// per trajectory turned into the StepIn records k_loc_solve (ekf_localize.hip) consumes, against a FROZEN map: tag-table lookup,
-// IGNORE_TAGS, the 1.5 m gate, per-tag averaging, range and bearing (src/replay_no_ros.py:280-337), and nothing of :341-360 --
-// no landmark is ever added.  One workgroup of ONE wave per trajectory, grid = batch.
-// The walk is a COPY of k_associate's (ekf_kernels.hip; that kernel's bits are pinned all over the suite and it is not touched,
-// as loc_motion is a copy of the step kernels' motion model): the same DetIn records, chunks of 64 detections, the ignore list,
-// t2^2 + t0^2 > gate2, ids outside [0, TAGMAX) set EKF_FLAG_ASSOC, one slot per distinct tag in order of first appearance, sums
-// then a division by the count, xr = t2, yr = -t0, sqrt, atan2, the world guess from the pose BEFORE the prediction -- in that
-// order, without contraction, so a tag's averaged (range, bearing) has the bits k_associate would give it.
-// What differs: a tag the table does not know, or whose entry points at or beyond the trajectory's landmark count (a stale row),
-// is UNMATCHED -- no slot, no flag, nothing changes; its id goes to the trajectory's LocUnmatched record, distinct ids in order of
-// first appearance (the first AMAX of them; `total` counts all).  More than AMAX distinct MATCHED tags: the surplus is dropped
-// with EKF_FLAG_ASSOC, as in mapping.  Which ids were already seen as unmatched is a 1024-bit set held in registers (lane l < 32
-// holds ids 32 l .. 32 l + 31), the list itself one id per lane: the walk's only LDS traffic stays k_associate's.
-// Written: step_out[b] (FLAG_PREDICT | FLAG_UPDATE, up to MMAX observations) and step_out[batch + b] (the update-only rest),
-// assoc_out[b] (the matched tags, n_after = n), unmatched[b], neff_dev[b] (raised over the matched landmarks, capped at n: a
-// consider update correlates the pose with every landmark it names, and only the device knows which those are), the sticky flag.
-// NOT written: tagmap, nact, P_base, V, W, the mean.
+// The device-side front ends that turn one window of raw AprilTag detections per trajectory into the StepIn records a solve
+// consumes (gfx950, wave64): k_associate for ekf_step_detections, on a map that grows, and k_loc_associate for
+// ekf_localize_detections, on a FROZEN one.  One workgroup of ONE wave per trajectory, grid = batch.  Both run the walk of
+// ekf_det_walk.h -- the DetIn records in chunks of 64, the ignore list, the gate, ids outside [0, TAGMAX), one slot per distinct
+// tag in order of first appearance, the sums, the per-tag mean, range, bearing and world guess, the two StepIn records and the
+// AssocOut record -- so a tag's averaged (range, bearing) has the same bits on both.  What is written here is what differs: what
+// a detection gets whose tag has no slot in the window yet, and what the window does to the filter.
 #include "ekf_device.h"
 
+#include "ekf_det_walk.h"
 #include "ekf_devfn.h"
 #include "ekf_launch.h"
 
 namespace ekf {
 
+// ---------------------------------------------------------------------------------------------
+// k_associate: association, gate, averaging and augmentation of one window (src/replay_no_ros.py:280-360).  The reference's
+// dictionaries have no limits (:280-301) and its normal mode hands over a 0.7 s window of every camera frame (:17: 21 frames x
+// every tag in view), so up to EKF_DMAX = 256 detections are walked and up to EKF_AMAX = 32 distinct tags are taken (two update
+// passes of EKF_MMAX landmarks).  A tag the table does not know gets the next landmark index (:294-295) and an entry in the
+// table, unless the state is full; the new landmarks' means, the zeroing of their rows / columns and the new diagonal (:341-360)
+// are spread over the lanes.  Writes the StepIn records, the tags_positions record, the new state size and the active bound.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_associate(const DetIn* __restrict__ det, int* __restrict__ tagmap,
+                                                  int* __restrict__ nact, int* __restrict__ neff_dev,
+                                                  double* __restrict__ mu, double* __restrict__ P,
+                                                  double* __restrict__ V, double* __restrict__ W,
+                                                  StepIn* __restrict__ step_out,
+                                                  AssocOut* __restrict__ assoc_out,
+                                                  unsigned* __restrict__ flags, AssocConfig cfg, int ld,
+                                                  long pstride, int n_max, int pending_k, int batch) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const DetIn& d = det[b];
+  int* tm = tagmap + (long)b * TAGMAX;
+  double* mub = mu + (long)b * ld;
+  double* Pb = P + (long)b * pstride;
+  double* Vb = V + (long)b * KTOT * ld;
+  double* Wb = W + (long)b * KTOT * ld;
+  __shared__ DetWalkShared sh;
+  const int n_old = nact[b];
+  const int nl_old = (n_old - 3) / 2;
+  int nl = nl_old;                                     // (uniform)
+  const int m = det_walk(sh, d, tm, cfg, min(d.count, DMAX), flags + b, lane, [&](int id, int lm, int m, unsigned& bad) {
+    // a detection that cannot be taken is dropped BEFORE it gets a landmark index: an index handed out here with no
+    // measurement behind it would leave an uninitialised landmark in the state
+    if (m >= AMAX) { bad |= EKF_FLAG_ASSOC; return -1; }
+    if (lm < 0) {                                      // (a tag new in this window has a slot from its first detection on and never comes here again)
+      if (3 + 2 * (nl + 1) > n_max) { bad |= EKF_FLAG_ASSOC; return -1; }          // :294-295
+      lm = nl++;
+      if (lane == 0) tm[id] = lm;
+    }
+    return lm;
+  });
+  const int n_new = 3 + 2 * nl;
+  AssocOut& ao = assoc_out[b];
+  const double px = mub[0], py = mub[1], pth = mub[2];         // pose BEFORE the prediction (:331-332)
+  if (lane < AMAX) {
+    const DetTag t = det_tag_out(sh, lane, m, px, py, pth, step_out, batch, b, ao);
+    if (t.lm >= nl_old) {                                                         // :359-360
+      mub[3 + 2 * t.lm] = t.xw;
+      mub[4 + 2 * t.lm] = t.yw;
+    }
+  }
+  // augmentation (:341-360): zero the new rows/columns, set the new diagonal; pending ranks see zeros
+  const int dn = n_new - n_old;
+  const int ld16 = ld >> 4;
+  for (long e = lane; e < (long)n_new * dn; e += 64) {
+    const int r = (int)(e / dn), q = n_old + (int)(e - (long)r * dn);
+    Pb[p_index(ld, r, q)] = (r == q) ? cfg.init_var : 0.0;
+    if (r < n_old) Pb[p_index(ld, q, r)] = 0.0;
+  }
+  for (int e = lane; e < pending_k * dn; e += 64) {
+    const int k = e / dn, q = n_old + (e - k * dn);
+    Vb[(long)k * ld + q] = 0.0;
+    Wb[wm_index(ld16, k, q)] = 0.0;
+  }
+  if (lane == 0) {
+    det_tail(sh, d, cfg, m, n_new, neff_dev, step_out, batch, b, ao);
+    nact[b] = n_new;
+  }
+}
+
+void launch_associate(hipStream_t st, const BankView& k, const DetIn* det, int* tagmap, int* neff_dev, double* mu, StepIn* step_out,
+                      AssocOut* assoc_out, const AssocConfig& cfg, int n_max, int pending_k) {
+  hipLaunchKernelGGL(k_associate, dim3(k.batch), dim3(64), 0, st, det, tagmap, k.nact, neff_dev, mu, k.P, k.V, k.W, step_out,
+                     assoc_out, k.flags, cfg, k.ld, k.pstride, n_max, pending_k, k.batch);
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_loc_associate: :280-337 against a frozen map, and nothing of :341-360 -- no landmark is ever added.  A tag the table does
+// not know, or whose entry points at or beyond the trajectory's landmark count (a stale row), is UNMATCHED -- no slot, no flag,
+// nothing changes; its id goes to the trajectory's LocUnmatched record, distinct ids in order of first appearance (the first
+// AMAX of them; `total` counts all).  More than AMAX distinct MATCHED tags: the surplus is dropped with EKF_FLAG_ASSOC, as in
+// mapping.  Which ids were already seen as unmatched is a 1024-bit set held in registers (lane l < 32 holds ids 32 l ..
+// 32 l + 31), the list itself one id per lane: the only LDS traffic is the walk's.
+// Written: step_out[b] (FLAG_PREDICT | FLAG_UPDATE, up to MMAX observations) and step_out[batch + b] (the update-only rest),
+// assoc_out[b] (the matched tags, n_after = n), unmatched[b], neff_dev[b] (raised over the matched landmarks, capped at n: a
+// consider update correlates the pose with every landmark it names, and only the device knows which those are), the sticky flag.
+// NOT written: tagmap, nact, P_base, V, W, the mean.
+// ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_loc_associate(const DetIn* __restrict__ det, const int* __restrict__ tagmap,
                                                       const int* __restrict__ nact, int* __restrict__ neff_dev,
                                                       const double* __restrict__ mu, StepIn* __restrict__ step_out,
                                                       AssocOut* __restrict__ assoc_out, LocUnmatched* __restrict__ unmatched,
                                                       unsigned* __restrict__ flags, AssocConfig cfg, int ld, int batch) {
-#pragma clang fp contract(off)
   const int b = blockIdx.x, lane = threadIdx.x;
   const DetIn& d = det[b];
-  const int* tm = tagmap + (long)b * TAGMAX;
   const double* mub = mu + (long)b * ld;
-  __shared__ int s_idx[AMAX], s_tag[AMAX], s_cnt[AMAX];
-  __shared__ double s_t[AMAX][3], s_err[AMAX];
-  __shared__ int c_id[64], c_lm[64], c_ok[64];         // the chunk: tag id, its landmark index in the table (-1: none), 1 = taken / 2 = bad id
-  __shared__ double c_t[64][3], c_e[64];
+  __shared__ DetWalkShared sh;
   const int n = nact[b];
   const int nl = (n - 3) / 2;
-  int m = 0, un = 0;                                   // (uniform: every lane walks the same sequence)
-  unsigned bad = 0;
+  int un = 0;                                          // (uniform)
   unsigned un_seen = 0;                                // lane l < 32: bit i = id 32 l + i was unmatched before in this window
   int un_id = -1;                                      // lane l < AMAX: the l-th distinct unmatched id
-  const int count = min(d.count, DMAX);
-  if (lane < AMAX) {
-    s_idx[lane] = -1;
-    s_tag[lane] = -1;
-    s_cnt[lane] = 0;
-    s_t[lane][0] = s_t[lane][1] = s_t[lane][2] = 0.0;
-    s_err[lane] = 0.0;
-  }
-  for (int q0 = 0; q0 < count; q0 += 64) {
-    const int q = q0 + lane;
-    int id = -1, lm = -1, ok = 0;
-    double t0 = 0.0, t1 = 0.0, t2 = 0.0, er = 0.0;
-    if (q < count) {
-      id = d.tag_id[q];
-      t0 = d.pose_t[q][0];
-      t1 = d.pose_t[q][1];
-      t2 = d.pose_t[q][2];
-      er = d.pose_err[q];
-      if (id < 0 || id >= TAGMAX) ok = 2;
-      else {
-        bool ign = false;
-        for (int u = 0; u < cfg.n_ignore; ++u) ign |= (cfg.ignore[u] == id);       // :286
-        if (!ign && !(t2 * t2 + t0 * t0 > cfg.gate2)) {                            // :289
-          ok = 1;
-          lm = tm[id];
-        }
+  const int m = det_walk(sh, d, tagmap + (long)b * TAGMAX, cfg, min(d.count, DMAX), flags + b, lane,
+                         [&](int id, int lm, int m, unsigned& bad) {
+    if (lm < 0 || lm >= nl) {                          // unknown to the table, or a stale row: unmatched (0 <= id < TAGMAX here)
+      const unsigned bit = 1u << (id & 31);
+      if (!__ballot(lane == (id >> 5) && (un_seen & bit))) {
+        if (lane == (id >> 5)) un_seen |= bit;
+        if (lane == un) un_id = id;                    // (un >= 64: no lane; only lanes < AMAX are stored)
+        ++un;
       }
+      return -1;
     }
-    WAVE_LDS_SYNC();                                   // (the previous chunk's walk has read its entries)
-    c_id[lane] = id;
-    c_lm[lane] = lm;
-    c_ok[lane] = ok;
-    c_t[lane][0] = t0;
-    c_t[lane][1] = t1;
-    c_t[lane][2] = t2;
-    c_e[lane] = er;
-    WAVE_LDS_SYNC();
-    const int nq = min(64, count - q0);
-    for (int u = 0; u < nq; ++u) {                     // in order: what a detection gets depends on the ones before it
-      const int ok_u = c_ok[u];
-      if (ok_u == 2) { bad |= EKF_FLAG_ASSOC; continue; }
-      if (ok_u == 0) continue;
-      const int id_u = c_id[u];
-      const unsigned long long hit = __ballot(lane < m && s_tag[lane] == id_u);    // the tag's slot in this window, if it has one
-      int slot = hit ? __builtin_ctzll(hit) : -1;
-      if (slot < 0) {
-        const int lm_u = c_lm[u];
-        if (lm_u < 0 || lm_u >= nl) {                  // unknown to the table, or a stale row: unmatched (0 <= id_u < TAGMAX here)
-          const unsigned bit = 1u << (id_u & 31);
-          if (!__ballot(lane == (id_u >> 5) && (un_seen & bit))) {
-            if (lane == (id_u >> 5)) un_seen |= bit;
-            if (lane == un) un_id = id_u;              // (un >= 64: no lane; only lanes < AMAX are stored)
-            ++un;
-          }
-          continue;
-        }
-        if (m >= AMAX) { bad |= EKF_FLAG_ASSOC; continue; }
-        slot = m++;
-        if (lane == 0) {
-          s_idx[slot] = lm_u;
-          s_tag[slot] = id_u;
-        }
-      }
-      if (lane == 0) {
-        s_t[slot][0] += c_t[u][0];                                                  // np.mean(..., axis=0): :315
-        s_t[slot][1] += c_t[u][1];
-        s_t[slot][2] += c_t[u][2];
-        s_err[slot] += c_e[u];                                                      // :317
-        s_cnt[slot] += 1;
-      }
-      WAVE_LDS_SYNC();                                 // (the next detection's search reads the slots)
-    }
-  }
-  if (bad && lane == 0) atomicOr(&flags[b], bad);
-  WAVE_LDS_SYNC();
+    if (m >= AMAX) { bad |= EKF_FLAG_ASSOC; return -1; }
+    return lm;
+  });
   AssocOut& ao = assoc_out[b];
   const double px = mub[0], py = mub[1], pth = mub[2];         // pose BEFORE the prediction (:331-332)
   if (lane < AMAX) {
-    StepIn& so = step_out[(long)(lane / MMAX) * batch + b];
-    const int sl = lane % MMAX;
-    if (lane < m) {
-      const double k = (double)s_cnt[lane];
-      const double t0 = s_t[lane][0] / k, t2 = s_t[lane][2] / k;
-      const double xr = t2, yr = -t0;                                             // :321
-      const double rng = sqrt(xr * xr + yr * yr);                                 // :329
-      const double brg = atan2(yr, xr);                                           // :330
-      const double xw = px + rng * cos(brg + pth), yw = py + rng * sin(brg + pth);
-      const int lm = s_idx[lane];
-      so.idx[sl] = lm;
-      so.range[sl] = rng;
-      so.bearing[sl] = brg;
-      ao.idx[lane] = lm;
-      ao.tag_id[lane] = s_tag[lane];
-      ao.xw[lane] = xw;
-      ao.yw[lane] = yw;
-      ao.err[lane] = s_err[lane] / k;
-      ao.range[lane] = rng;
-      ao.bearing[lane] = brg;
-    } else {
-      so.idx[sl] = 0;
-      so.range[sl] = 0.0;
-      so.bearing[sl] = 0.0;
-    }
+    det_tag_out(sh, lane, m, px, py, pth, step_out, batch, b, ao);
     unmatched[b].tag_id[lane] = lane < un ? un_id : -1;
   }
   if (lane == 0) {
-    int bound = neff_dev[b];
-    for (int u = 0; u < m; ++u) bound = max(bound, 3 + 2 * (s_idx[u] + 1));
-    bound = min(bound, n);
-    neff_dev[b] = bound;
-    StepIn& s0 = step_out[b];
-    StepIn& s1 = step_out[(long)batch + b];
-    s0.lin = d.lin;
-    s0.ang = d.ang;
-    s0.m = min(m, MMAX);
-    s0.flags = FLAG_PREDICT | FLAG_UPDATE;
-    s0.neff = cfg.active_bound ? bound : n;
-    s0.pad = 0;
-    s1.lin = 0.0;                                      // the landmarks beyond the first pass: an update without a prediction
-    s1.ang = 0.0;
-    s1.m = max(m - MMAX, 0);
-    s1.flags = FLAG_UPDATE;
-    s1.neff = s0.neff;
-    s1.pad = 0;
-    ao.m = m;
-    ao.n_after = n;
+    det_tail(sh, d, cfg, m, n, neff_dev, step_out, batch, b, ao);
     unmatched[b].total = un;
     unmatched[b].pad = 0;
   }

@@ -15,35 +15,6 @@
 
 namespace ekf {
 
-// The motion model of src/replay_no_ros.py:368-417 at the pose (x, y, th): the new pose and G[0,2], G[1,2] of its Jacobian
-// (a copy of its own: the step kernels keep theirs, whose bits must not move).
-struct LocMotion {
-  double x, y, th, g0, g1;
-};
-__device__ __forceinline__ LocMotion loc_motion(double x, double y, double th, double lin, double ang, const DeviceConfig& cfg) {
-  LocMotion r{x, y, th, 0.0, 0.0};
-  if (cfg.disable_motion_model) return r;
-  double s0, c0;
-  sincos(th, &s0, &c0);
-  if (cfg.enable_circular_interpolation && fabs(ang) > cfg.arc_threshold) {   // :390 arc
-    double s1, c1;
-    sincos(th + ang, &s1, &c1);
-    const double rr = lin / ang;
-    r.x += -rr * s0 + rr * s1;
-    r.y += rr * c0 - rr * c1;
-    r.th = wrap_pi(th + ang);                            // :397
-    r.g0 = -rr * c0 + rr * c1;                           // :401
-    r.g1 = -rr * s0 + rr * s1;                           // :402
-  } else {                                               // :376 straight / :405-417 linear mode
-    r.x += lin * c0;
-    r.y += lin * s0;
-    if (!cfg.enable_circular_interpolation) r.th = th + ang;   // no wrap (:409); :381 keeps theta
-    r.g0 = -lin * s0;
-    r.g1 = lin * c0;
-  }
-  return r;
-}
-
 // v <- v - K (H_p v + H_l w): one 3-vector of the chain (h: the 2 x 5 Jacobian, k: K_p 3 x 2)
 __device__ __forceinline__ void loc_apply(double (&v)[3], double w0, double w1, const double (&h)[2][5], const double (&k)[3][2]) {
   const double u0 = fma(h[0][4], w1, fma(h[0][3], w0, fma(h[0][2], v[2], fma(h[0][1], v[1], h[0][0] * v[0]))));
@@ -115,7 +86,7 @@ __device__ __forceinline__ void loc_solve_body(const StepIn& s, int n, int bound
 
   // ---- the prediction: x <- G x, pose block G P_pp G^T + rd (:428-430) ----
   if (do_pred) {
-    const LocMotion mo = loc_motion(px, py, pth, lin, ang, cfg);
+    const Motion mo = motion_model(px, py, pth, lin, ang, cfg);
     px = mo.x, py = mo.y, pth = mo.th;
     const double g0 = mo.g0, g1 = mo.g1;
     xv[0] = fma(g0, xv[2], xv[0]);

@@ -46,33 +46,13 @@ __device__ __forceinline__ void small_step(double* __restrict__ Pl, double* __re
   if (do_pred) {
     if (tid == 0) {
       const double th = mu[2];
-      double g0 = 0.0, g1 = 0.0, nx = mu[0], ny = mu[1], nth = th;
-      if (!cfg.disable_motion_model) {
-        const double lin = s.lin, ang = s.ang;
-        double s0, c0;
-        sincos(th, &s0, &c0);
-        if (cfg.enable_circular_interpolation && fabs(ang) > cfg.arc_threshold) {   // :390 arc
-          double s1, c1;
-          sincos(th + ang, &s1, &c1);
-          const double r = lin / ang;
-          nx += -r * s0 + r * s1;
-          ny += r * c0 - r * c1;
-          nth = wrap_pi(th + ang);                          // :397
-          g0 = -r * c0 + r * c1;                            // :401
-          g1 = -r * s0 + r * s1;                            // :402
-        } else {                                            // :376 straight / :405-417 linear mode
-          nx += lin * c0;
-          ny += lin * s0;
-          if (!cfg.enable_circular_interpolation) nth = th + ang;   // no wrap (:409); :381 keeps theta
-          g0 = -lin * s0;
-          g1 = lin * c0;
-        }
-      }
-      mu[0] = nx;
-      mu[1] = ny;
-      mu[2] = nth;
-      sc[0] = g0;
-      sc[1] = g1;
+      Motion mo{mu[0], mu[1], th, 0.0, 0.0};
+      if (!cfg.disable_motion_model) mo = motion_model(mo.x, mo.y, mo.th, s.lin, s.ang, cfg);
+      mu[0] = mo.x;
+      mu[1] = mo.y;
+      mu[2] = mo.th;
+      sc[0] = mo.g0;
+      sc[1] = mo.g1;
     }
     __syncthreads();
     const double g0 = sc[0], g1 = sc[1];

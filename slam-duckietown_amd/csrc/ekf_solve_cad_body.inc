@@ -43,7 +43,7 @@
       const CadPlan pl = plan[b];
       const int n = nact[b];
       if (i0 >= n || i0 >= min(n, pl.neff) || pl.nslots == 0) continue;   // (uniform) nothing of this wave is replayed
-      // the positions C_u of trajectory b, by this wave alone (cad_positions restated for one wave: lane p = touched step p)
+      // the positions C_u of trajectory b, by this wave alone (cad_positions' shape for one wave: lane p = touched step p)
       int* Cw = CsG[wave];
       int* cw = cntG[wave];
       Cw[lane] = lane < 3 ? lane : 0;
@@ -52,10 +52,9 @@
       const StepIn* st = nullptr;
       if (lane < pl.ns) {
         st = in + ((long)(pl.t0 + lane) * batch + b);
-        const int m = ((st->flags & FLAG_UPDATE) && cfg.enable_measurement_model) ? min(st->m, MMAX) : 0;
-        lo = lane == 0 ? pl.j0 : 0;
-        const int hi = lane == pl.ns - 1 ? min(pl.jend, m) : m;
-        cnt = max(hi - lo, 0);
+        const CadRange r = cad_step_range(pl, st, lane, cfg.enable_measurement_model);
+        lo = r.lo;
+        cnt = r.cnt;
       }
       if (lane <= CAD_SLOTS) cw[lane] = lane < CAD_SLOTS ? cnt : 0;
       WAVE_LDS_SYNC();
@@ -233,38 +232,18 @@
     const double2 la = laS[t];
     const bool do_pred = (fS[t] & FLAG_PREDICT) != 0;
     const double th = read_lane(mu0, 2);
-    double g0 = 0.0, g1 = 0.0, nx = read_lane(mu0, 0), ny = read_lane(mu0, 1), nth = th;
-    if (do_pred && !cfg.disable_motion_model) {
-      const double lin = la.x, ang = la.y;
-      double s0, c0;
-      sincos(th, &s0, &c0);
-      if (cfg.enable_circular_interpolation && fabs(ang) > cfg.arc_threshold) {   // :390 arc
-        double s1, c1;
-        sincos(th + ang, &s1, &c1);
-        const double r = lin / ang;
-        nx += -r * s0 + r * s1;
-        ny += r * c0 - r * c1;
-        nth = wrap_pi(th + ang);                       // :397
-        g0 = -r * c0 + r * c1;                         // :401
-        g1 = -r * s0 + r * s1;                         // :402
-      } else {                                         // :376 straight / :405-417 linear mode
-        nx += lin * c0;
-        ny += lin * s0;
-        if (!cfg.enable_circular_interpolation) nth = th + ang;   // no wrap (:409); :381 keeps theta
-        g0 = -lin * s0;
-        g1 = lin * c0;
-      }
-    }
-    if (lane < 3) mu0 = lane == 0 ? nx : (lane == 1 ? ny : nth);
+    Motion mo{read_lane(mu0, 0), read_lane(mu0, 1), th, 0.0, 0.0};
+    if (do_pred && !cfg.disable_motion_model) mo = motion_model(mo.x, mo.y, mo.th, la.x, la.y, cfg);
+    if (lane < 3) mu0 = lane == 0 ? mo.x : (lane == 1 ? mo.y : mo.th);
     if (do_pred) {
       rdsum0 += NZ ? nz.rd[0] : cfg.rd[0];
       rdsum1 += NZ ? nz.rd[1] : cfg.rd[1];
       rdsum2 += NZ ? nz.rd[2] : cfg.rd[2];
     }
     if (lane == 0) {
-      mot[0] = g0;
-      mot[1] = g1;
-      *reinterpret_cast<double2*>(o.g[t]) = make_double2(g0, g1);
+      mot[0] = mo.g0;
+      mot[1] = mo.g1;
+      *reinterpret_cast<double2*>(o.g[t]) = make_double2(mo.g0, mo.g1);
     }
   };
   auto jacobian_at_mean = [&](int p, int par) {        // landmark at positions p, p + 1: publishes hS[par], keeps the geometry

@@ -1,10 +1,12 @@
-"""GPU: motion and measurement geometry at its edges, on every path that carries a copy of it.
+"""GPU: motion and measurement geometry at its edges, on every path that runs it.  The paths share the arithmetic itself --
+motion_model, linearize_h and innovation (csrc/ekf_devfn.h), the detection walk (csrc/ekf_det_walk.h) -- and differ in how they
+fetch the pose, publish the result and order the work around it, which is what each row below names.
 
 The case table of tests/geometry_cases.py -- scripts of twelve steps in banks of up to 16 slots -- runs on every path below, and
 every path is judged against the longdouble model of tests/geometry_model.py (localisation: against tests/localize_model.py fed the
 same inputs) on every logged y, S and NIS, every pose-log row, the final mean and covariance block by block, and flags == 0:
 
-  step                 the general kernels, "fused_step" 0 and 1          (motion model: ekf_kernels.hip k_solve)
+  step                 the general kernels, "fused_step" 0 and 1          (ekf_kernels.hip solve_body)
   predict + update     the general kernels
   run_stream           fused cadences with "chain" 0; chained solves -- the bank, and one script repeated in 16 slots --; the
                        per-step stream with "fused_cadence" 0             (ekf_solve_cad_body.inc: step heads and cut steps)
