@@ -126,10 +126,9 @@ struct ekf_handle : ekf::HostPlan {
   DeviceBuf<SolveOut> dmbox;      // per trajectory: that solve's header and records, written through (mailbox_publish)
   unsigned step_seq = 0;          // sequence number of the last single-launch step
   // per trajectory: head + per-landmark records of a cadence (allocated on first use).  Two copies, used alternately by
-  // consecutive cadences (`cpar`): in a chained run the next cadence's solve writes its records while this cadence's panel
-  // launch still reads these
+  // consecutive cadences (`run.cpar`): in a chained run the next cadence's solve writes its records while this cadence's panel
+  // launch still reads these.  (The cadences' counters, parities and statistics: ekf_host_plan.h, CadRun -- h->run.)
   DeviceBuf<CadOut> dcad2[2];
-  int cpar = 0;
   // Chained solves (round 6; "chain"): the solves of a run follow one another on the handle's stream -- the next cadence's
   // block comes from this cadence's records (k_chain_cad) -- while panel launch and covariance pass of every cadence run
   // on the second stream.  dprow3: rows 0..2 of every P after a cadence, left by its panel launch (batch x 3 x ld, two copies
@@ -138,22 +137,12 @@ struct ekf_handle : ekf::HostPlan {
   DeviceBuf<double> dgmu;
   DeviceBuf<double> dxg, dbg;     // the chain launch's gathered rows (batch x 84 x 88 each): written by its gather workgroups
   DeviceBuf<unsigned> dsync;      // device-scope counters of the chained run's hand-overs (ekf_cadence.hip: SYNC_*)
-  unsigned gather_count = 0;      // gather workgroups launched so far (what the next chain workgroups wait for)
-  unsigned sigma = 0;             // chained transitions so far (the value the run's counters SYNC_SOLVE / SYNC_PASS carry)
-  // a cadence's inputs formed one cadence ahead (CadPre): two copies, by the cadence's serial number (pre_serial: whose inputs a
-  // copy holds; serials count every cadence of the handle)
-  DeviceBuf<CadPre> dpre[2];
-  long pre_serial[2] = {-1, -1};
-  long cad_serial = 0;
+  DeviceBuf<CadPre> dpre[2];      // a cadence's inputs formed one cadence ahead: two copies (run.pre_serial: whose inputs a copy holds)
   Event ev_pass;                  // recorded on the second stream when a chain of cadences ends (join_aux): the only event of the chained order
-  bool aux_pass = false;          // a covariance pass is in flight on the second stream (ev_pass recorded behind it)
-  long w_from_v_passes = 0;       // statistics: passes that formed W from V ("w_from_v")
   int opt_run_end_flush = 0;      // 1 = ekf_stream_run applies what its last cadence left pending, so that the next call starts fused
-  long chained = 0;               // statistics: cadences whose block came from k_chain_cad
   // The mirrored column entries of a cadence's panel launch, gathered by extra workgroups of its solve launch and laid down
   // as rows (batch x 83 x ld doubles, allocated on first use; not for banks where that would exceed 1 GiB; "col_gather")
   DeviceBuf<double> dcolbuf;
-  long cadences = 0, cadence_traj_steps = 0;   // statistics: fused cadences launched, trajectory-steps they completed
   // The packed cadences of the ekf_stream_run in flight (ekf_host_plan.h: plan_cadences): one CadPlan per (cadence,
   // trajectory), planned on the host for the whole run and uploaded once, stream-ordered, out of pinned memory.  Two copies,
   // used alternately: the host may plan the next run while the upload of this one has not executed yet.
@@ -165,7 +154,6 @@ struct ekf_handle : ekf::HostPlan {
   hipStream_t aux = nullptr;
   Event ev_fork, ev_join;
   DeviceBuf<double> dgbuf;        // per trajectory: the next cadence's block, gathered while this one's ranks are pending
-  long lookaheads = 0;
   long assoc_fallbacks = 0;       // statistics: windows a binding took through the host association (ekf_debug_note_assoc_fallback)
   long small_launches = 0;        // statistics: launches of the small-state path (k_small_stream)
   long fused_fetches = 0;         // statistics: ekf_step_fetch calls answered by the step's own launch
@@ -666,9 +654,8 @@ static BankView bank_view(const ekf_handle* h) { return BankView{h->dP.p, h->dV.
 // rows BEFORE it (taken from P_base by launch_snap_pose in front of a chained run's first cadence), dprow3[cpar] where its panel
 // launch leaves them.  CAD_NEXT: the cadence after the handle's current one -- every parity the other way round --, for the
 // solve enqueue_cadence runs ahead (chained: before it flips the handle; look-ahead: behind the flip, the same copies).
-enum CadWhich { CAD_THIS = 0, CAD_NEXT = 1 };
 static StepBufs step_bufs(const ekf_handle* h, CadWhich which = CAD_THIS) {
-  const int cur = h->cur ^ which, dcur = h->dcur ^ which, cpar = h->cpar ^ which;
+  const int cur = h->cur ^ which, dcur = h->dcur ^ which, cpar = h->run.cpar ^ which;
   return StepBufs{h->dmu2[cur].p, h->dmu2[cur ^ 1].p, h->ddacc2[dcur].p, h->ddacc2[dcur ^ 1].p, h->dcad2[cpar].p, h->dprow3[cpar ^ 1].p,
                   h->dprow3[cpar].p};
 }
@@ -1404,6 +1391,14 @@ static int prof_close(ekf_handle* h, ProfBracket* pb) {
   if (pb->e1) HIP_TRY(h, hipEventRecord(pb->e1, pb->st));
   return EKF_OK;
 }
+// `launch()` inside such a pair
+template <class Launch>
+static int launch_profiled(ekf_handle* h, int cls, hipStream_t st, Launch launch) {
+  ProfBracket pb;
+  if (int rc = prof_open(h, cls, st, &pb)) return rc;
+  launch();
+  return prof_close(h, &pb);
+}
 
 // Apply the pending low-rank update to P_base:  P_base += W V + diag(dacc)  (one pass over P), on stream `st` (the
 // handle's own unless the look-ahead of ekf_stream_run sends it to the second one).
@@ -1487,10 +1482,7 @@ static int front_run(ekf_handle* h, const char* fn, int b0, int count, const Fro
     double* dout = dmeas + B * tab.dbls;
     HIP_TRY(h, hipMemcpyAsync(dplan, h->front_ints.data(), sizeof(int) * h->front_ints.size(), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(dmeas, h->front_dbls.data(), sizeof(double) * h->front_dbls.size(), hipMemcpyHostToDevice, h->stream));
-    ProfBracket pb;
-    if (int rc = prof_open(h, cls, h->stream, &pb)) return rc;
-    launch(dplan, dmeas, dout);
-    if (int rc = prof_close(h, &pb)) return rc;
+    if (int rc = launch_profiled(h, cls, h->stream, [&] { launch(dplan, dmeas, dout); })) return rc;
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(h->front_out.data(), dout, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->stream));
     for (size_t b = 0; b < B; ++b) h->neff_enq[b] = h->front_ints[b * tab.ints + 1];
@@ -1648,33 +1640,51 @@ static int upload_run_plan(ekf_handle* h) {
   return EKF_OK;
 }
 
-// Cadence c of the run in flight (h->run_plan, uploaded): one solve launch, one panel launch; the covariance pass follows
-// when it is due -- behind every cadence but the run's last, and behind that one when its slots are used up.
-//
-// Small launches, where the covariance pass leaves CUs free (the column-strip kernel on at least ~48 MB of covariance; the
-// row-slab pass on static shares: a few long trajectories), do not run solve -> panel -> pass -> solve one behind the
-// other: the only true dependency between two cadences of a trajectory is the sequential landmark recurrence
-// (src/replay_no_ros.py:436-480: landmark j + 1 is linearised at the mean landmark j produced).
-//   * CHAINED SOLVES (round 6, "chain" = 1): every solve of the run also records the pose block behind its cadence
-//     (k_solve_cad<true>: CadOut::posefin); k_chain_cad forms the next cadence's block and mean from the cadence's records and
-//     from P_base as it stood BEFORE the cadence, so the handle's stream runs  solve_c -> chain_{c+1} -> solve_{c+1} -> ...  while
-//     the second stream runs  gate -> panel_c -> pass_c -> mark -> gate -> ...  Hand-overs are device-scope counters (ekf_cadence.hip:
-//     SYNC_*): the gate waits for solve_c (announced by chain_{c+1}'s start); panel_c ends when chain_{c+1}'s gather workgroups
-//     have read what the pass rewrites and solve_{c+1} has been placed; chain_{c+1}'s gathers wait for the mark behind pass_{c-1}.
-//     A transition is ENQUEUED chain, solve, gate, panel, pass, mark: every wait is for an earlier-enqueued launch.  Two copies of
-//     the records, of the pose rows (dprow3) and of the inputs formed ahead (CadPre), used alternately.
-//   * LOOK-AHEAD (round 3, "chain" = 0): panel_c -> k_gather_cad (the next block from P_base and the ranks still pending) ->
-//     { pass_c on the second stream | solve_{c+1} } -> join.
-// `presolved` says that this cadence's solve has already been enqueued one of these ways; *next_presolved that the next
-// one's now is.
-// (ekf_host_plan.h: plan_cadence_step decides all of it, beside_the_pass where a pass leaves CUs to the next solve.)
+// What a planned piece of a run needs before its first cadence (h->run_plan holds the piece): whether its solves are chained --
+// decided per piece; whether a cadence is chained to the next is decided where the pass between them is planned
+// (plan_cadence_step) -- and everything a cadence touches: the chained set is one group; it shares the records and the block
+// buffer with the look-ahead's set, whose block buffer is allocated where a look-ahead first runs (enqueue_cadence).
+static int prepare_piece(ekf_handle* h) {
+  h->chain_run = plan_chain_run(h, h->run_plan.ncad);
+  h->chain_gw = chain_gather_workgroups(h->batch, h->cu_count);
+  const size_t B = (size_t)h->batch;
+  if (!h->chain_run) {
+    RES_TRY(h, "the cadence records", res::ensure_group(nullptr, res::want(h->dcad2[0], B), res::want(h->dcad2[1], B)));
+    return EKF_OK;
+  }
+  const size_t gw = B * 84 * 88;
+  bool fresh;
+  RES_TRY(h, "the chained run's buffers",
+          res::ensure_group(&fresh, res::want(h->dcad2[0], B), res::want(h->dcad2[1], B),
+                            res::want(h->dgbuf, (size_t)cadence_gbuf_doubles() * B),
+                            res::want(h->dprow3[0], 3 * (size_t)h->ld * B), res::want(h->dprow3[1], 3 * (size_t)h->ld * B),
+                            res::want(h->dxg, gw), res::want(h->dbg, gw), res::want(h->dsync, (size_t)chain_sync_words()),
+                            res::want(h->dpre[0], B), res::want(h->dpre[1], B), res::want(h->dgmu, 128 * B)));
+  if (fresh) {
+    HIP_TRY(h, hipMemsetAsync(h->dsync.p, 0, sizeof(unsigned) * chain_sync_words(), h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // (the second stream's launches read the counters too)
+  }
+  // the pose rows "before the first cadence": where the previous cadence's panel launch would have left them
+  launch_snap_pose(h->stream, bank_view(h), bank_n_hi(h, false), step_bufs(h).prow3_in);
+  HIP_TRY(h, hipGetLastError());
+  return EKF_OK;
+}
 
+// ---- the fused cadences of ekf_stream_run: what is launched, on which stream and in which order is ekf_host_plan.h's
+// plan_cadence_launches (the three orders -- serial, look-ahead, chained -- are described there); here the list is executed ----
+
+// one event recorded on `from`, waited for by `to`
+static int hand_over(ekf_handle* h, const char* what, Event& ev, hipStream_t from, hipStream_t to) {
+  RES_TRY(h, what, ev.record(from));
+  HIP_TRY(h, hipStreamWaitEvent(to, ev.ev, 0));
+  return EKF_OK;
+}
 // whatever is still running on the second stream is waited for by the handle's own stream
+// (ev_pass: behind the last chained pass, one event per chain of cadences)
 static int join_aux(ekf_handle* h) {
-  if (!h->aux_pass) return EKF_OK;
-  RES_TRY(h, "ev_pass", h->ev_pass.record(h->aux));    // (behind the last chained pass: one event per chain of cadences)
-  HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_pass.ev, 0));
-  h->aux_pass = false;
+  if (!h->run.aux_pass) return EKF_OK;
+  if (int rc = hand_over(h, "ev_pass", h->ev_pass, h->aux, h->stream)) return rc;
+  h->run.aux_pass = false;
   return EKF_OK;
 }
 
@@ -1686,7 +1696,15 @@ static void log_cadence(ekf_handle* h, const CadPlan* dpl, const CadOut* co) {
                    innov_log(h, h->lg_tslot, 0));
 }
 
+// Cadence c of the run in flight (h->run_plan, uploaded).  The optional buffers its plan may want exist before its first launch
+// (between the enqueue of a launch that waits on a device-side counter and the enqueue of the launch that advances it the host
+// must not block -- an allocation may); then one loop over the planned ops.  A failure before the marked op (no_way_back) has been
+// launched returns its error, with CadRun put back to what has in fact been enqueued (the plan advanced it as a whole); once
+// it has, the rest of the list is still enqueued, but for the pass -- no device-side wait is left without its counterpart --,
+// both streams are synchronised and every trajectory is marked undefined (EKF_ERR_STATE from then on, until it is uploaded again).
 static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_presolved) {
+  static const char* const OP_NAME[] = {"solve", "innovation log", "chain", "gate", "panel", "covariance pass", "mark", "gather", "fork", "join",
+                                        "join of the second stream"};
   *next_presolved = false;
   const RunPlan& rp = h->run_plan;
   // (the pose log: k_solve_cad_plog writes stream step t's row (pl_tslot + t) % pose_cap itself; nullptr: off)
@@ -1694,13 +1712,9 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
   const PoseLog* plg = h->dpose.p && h->pl_tslot >= 0 ? &plg_on : nullptr;
   const int n_hi = bank_n_hi(h, false);
   const CadPlan* dpl = h->plan2[h->plan_cur].device() + (size_t)c * h->batch;
+  const CadPlan* const row[2] = {dpl, dpl + h->batch};
   const BankView bank = bank_view(h);
-  StepBufs cad = step_bufs(h, CAD_THIS);               // this cadence's buffers ...
-  const StepBufs next = step_bufs(h, CAD_NEXT);        // ... and the next one's, for the solve enqueued ahead (chained, look-ahead)
-  if (!h->chain_run) cad.prow3_out = nullptr;          // (only a chained run keeps the pose rows)
-  const long serial = h->cad_serial++;                 // this cadence's number (CadPre copies are looked up by it)
   for (int b = 0; b < h->batch; ++b) h->neff_enq[b] = rp.entries[(size_t)c * h->batch + b].neff;
-  // what follows the panel launch is decided before anything is launched (chained: it goes to the second stream)
   CadStepPlan cp = plan_cadence_step(h, rp, c, n_hi, presolved);
   if (cp.gather_cols && !h->dcolbuf.ensure((size_t)h->batch * CAD_CU * h->ld).ok()) {
     // (an optional optimisation: where its buffer cannot be had the panel launch gathers everything itself, bit-identically)
@@ -1708,146 +1722,98 @@ static int enqueue_cadence(ekf_handle* h, int c, bool presolved, bool* next_pres
     h->opt_col_gather = 0;
     cp = plan_cadence_step(h, rp, c, n_hi, presolved);
   }
-  double* colbuf = cp.gather_cols ? h->dcolbuf.p : nullptr;
-  if (!presolved) {
-    if (int rc = join_aux(h)) return rc;
-    ProfBracket pb;
-    if (int rc = prof_open(h, 1, h->stream, &pb)) return rc;
-    SolveCadArgs sx;
-    sx.colbuf = colbuf, sx.col_wgs = cp.col_wgs;
-    sx.chain = h->chain_run;
-    launch_solve_cad(h->stream, bank, cad, h->d_stream.p, dpl, h->dcfg, n_hi, sx, plg);
-    if (int rc = prof_close(h, &pb)) return rc;
-    log_cadence(h, dpl, cad.cad);
-  }
-  const bool due = cp.due, beside = cp.beside, chain_next = cp.chain_next, wv = cp.w_from_v;
-  const int ranks = 2 * rp.slots_hi[c], nrp = (ranks + 3) & ~3;   // every trajectory writes the busiest one's ranks (zeros beyond its own)
-  hipStream_t pst = h->stream;                         // the panel launch's stream
-  PanelCadArgs px{nrp, cp.panel, wv, colbuf};
-  const CadPlan* dpl2 = dpl + h->batch;
+  if (cp.beside && !cp.chain_next)                     // (a chained run's set holds it: prepare_piece)
+    RES_TRY(h, "the look-ahead's block buffer", h->dgbuf.ensure((size_t)cadence_gbuf_doubles() * h->batch));
+  // this cadence's buffers and the next one's, for the solve enqueued ahead (the same copies before and behind the PANEL op's flip)
+  const StepBufs bufs[2] = {step_bufs(h, CAD_THIS), step_bufs(h, CAD_NEXT)};
+  const CadRun before = h->run;
+  const CadLaunches L = plan_cadence_launches(h, rp, c, n_hi, presolved, cp);
   int rc = EKF_OK;
-  if (chain_next) {
-    // ---- chained.  The handle's stream: chain_{c+1} -> solve_{c+1}; the second stream: [gate ->] panel_c -> pass_c -> mark.
-    // No event: a hand-over through the command processor costs the waiting stream 7 us behind a record and ~19 us across
-    // streams (profiles/r06_chained_solves.txt); the counters cost a load.  ENQUEUED IN THIS ORDER: every device-side wait is
-    // for a launch that is already in its queue (chain_{c+1}'s gathers: the previous transition's mark; panel_c: chain_{c+1}'s
-    // start and gathers, solve_{c+1}'s start), so nothing can hang where the runtime maps both streams onto one hardware queue --
-    // and the host calls nothing that may block in between (every buffer exists before the run).
-    h->sigma += 1u;
-    const int gw = chain_gather_workgroups(h->batch, h->cu_count);
-    h->gather_count += (unsigned)(h->batch * gw);
-    ProfBracket pbc, pbs;
-    if (int rc2 = prof_open(h, 2, h->stream, &pbc)) return rc2;
-    // the next cadence's inputs if an earlier chain launch formed them; the one after it: formed by this launch
-    const CadPre* pre_in = h->pre_serial[(serial + 1) & 1] == serial + 1 ? h->dpre[(serial + 1) & 1].p : nullptr;
-    CadPre* pre_out = c + 2 < rp.ncad ? h->dpre[(serial + 2) & 1].p : nullptr;
-    ChainArgs cx{h->dgbuf.p, h->dgmu.p, h->dxg.p, h->dbg.p, h->dsync.p};
-    cx.sigma = h->sigma, cx.gather_target = h->gather_count, cx.gw = gw, cx.wait_pass = h->aux_pass;
-    cx.pre_in = pre_in, cx.pre_out = pre_out, cx.plan2 = pre_out ? dpl2 + h->batch : nullptr;
-    launch_chain_cad(h->stream, bank, cad, h->d_stream.p, dpl2, h->dcfg, cx);
-    if (pre_out) h->pre_serial[(serial + 2) & 1] = serial + 2;
-    if (int rc2 = prof_close(h, &pbc)) return rc2;
-    if (int rc2 = prof_open(h, 1, h->stream, &pbs)) return rc2;
-    SolveCadArgs sx;                                   // (block and mean from the chain launch: one part, no columns to gather)
-    sx.gbuf = h->dgbuf.p, sx.gparts = 1;
-    sx.chain = true;
-    sx.gmu = h->dgmu.p, sx.sync = h->dsync.p, sx.start_sigma = h->sigma, sx.pre = pre_in;
-    launch_solve_cad(h->stream, bank, next, h->d_stream.p, dpl2, h->dcfg, n_hi, sx, plg);
-    if (int rc2 = prof_close(h, &pbs)) return rc2;
-    log_cadence(h, dpl2, next.cad);                    // (enqueued before the gate: it waits for nothing)
-    // From here on the next cadence's solve overwrites the pose mean and the pending-noise buffer: a failure below cannot be
-    // undone.  Whatever happens the streams are joined, and a failure marks every trajectory undefined (EKF_ERR_STATE from
-    // then on, until it is uploaded again).
-    if (hipGetLastError() != hipSuccess) rc = fail(h, EKF_ERR_HIP, "chained solves: launch of the next cadence's solve failed");
-    // (a one-lane gate in front of the panel launch: ~5 us of the second stream, which has them to spare, and no workgroup of
-    //  a large launch ever spins)
-    launch_gate(h->aux, h->dsync.p, h->sigma, h->dflags.p, h->batch);
-    pst = h->aux;
-    px.sync = h->dsync.p, px.tail_target = h->gather_count, px.start_sigma = h->sigma;
-  } else if (int rc2 = join_aux(h)) {
-    return rc2;
-  }
-  {
-    ProfBracket pb;
-    if (int rc2 = prof_open(h, 3, pst, &pb)) return rc2;
-    launch_panels_cad(pst, bank, cad, n_hi, px);
-    if (int rc2 = prof_close(h, &pb)) return rc2;
-  }
-  if (hipGetLastError() != hipSuccess && rc == EKF_OK) rc = fail(h, EKF_ERR_HIP, "fused cadence: launch of the panel kernel failed");
-  h->dcur ^= 1;
-  h->cur ^= 1;
-  h->cpar ^= 1;
-  h->pending_k += ranks;
-  h->pending_steps += rp.steps_hi[c];
-  h->cadences += 1;
-  h->cadence_traj_steps += rp.steps_sum[c];
-  if (chain_next) {
-    // pass_c behind the panel launch on the second stream, then the mark the next chain launch's gather workgroups wait for
-    if (rc == EKF_OK) rc = flush_pending(h, h->aux);
-    launch_mark(h->aux, h->dsync.p, h->sigma);
-    if (hipGetLastError() != hipSuccess && rc == EKF_OK) rc = fail(h, EKF_ERR_HIP, "chained solves: launch of the mark failed");
-    h->aux_pass = true;
-    if (rc != EKF_OK) {
-      (void)hipStreamSynchronize(h->aux);
-      (void)hipStreamSynchronize(h->stream);
-      h->aux_pass = false;
-      std::fill(h->host_bad.begin(), h->host_bad.end(), (unsigned char)1);
-      return rc;
+  bool committed = false;                              // the marked op's launch has been attempted
+  unsigned done = 0;                                   // op kinds that went out (bit per kind)
+  std::string first_err;
+  for (int i = 0; i < L.n; ++i) {
+    const CadOp& op = L.op[i];
+    if (rc != EKF_OK && op.kind == OP_PASS) continue;
+    const hipStream_t st = op.stream == ON_AUX ? h->aux : h->stream;
+    const StepBufs& s = bufs[op.which];
+    int e = EKF_OK;
+    switch (op.kind) {
+      case OP_SOLVE: {
+        SolveCadArgs sx;
+        sx.gbuf = op.gparts ? h->dgbuf.p : nullptr, sx.gparts = op.gparts;
+        sx.colbuf = op.colbuf ? h->dcolbuf.p : nullptr, sx.col_wgs = op.col_wgs;
+        sx.chain = op.chain;
+        if (op.sync) sx.gmu = h->dgmu.p, sx.sync = h->dsync.p;
+        sx.start_sigma = op.sigma, sx.pre = op.pre_in >= 0 ? h->dpre[op.pre_in].p : nullptr;
+        e = launch_profiled(h, op.cls, st, [&] {
+          committed = committed || op.no_way_back;
+          launch_solve_cad(st, bank, s, h->d_stream.p, row[op.which], h->dcfg, n_hi, sx, plg);
+        });
+        break;
+      }
+      case OP_LOG: log_cadence(h, row[op.which], s.cad); break;
+      case OP_CHAIN: {
+        ChainArgs cx{h->dgbuf.p, h->dgmu.p, h->dxg.p, h->dbg.p, h->dsync.p};
+        cx.sigma = op.sigma, cx.gather_target = op.target, cx.gw = op.gw, cx.wait_pass = op.wait_pass;
+        cx.pre_in = op.pre_in >= 0 ? h->dpre[op.pre_in].p : nullptr, cx.pre_out = op.pre_out >= 0 ? h->dpre[op.pre_out].p : nullptr;
+        cx.plan2 = op.plan2 ? row[op.which] + h->batch : nullptr;
+        e = launch_profiled(h, op.cls, st, [&] { launch_chain_cad(st, bank, bufs[CAD_THIS], h->d_stream.p, row[op.which], h->dcfg, cx); });
+        break;
+      }
+      case OP_GATE: launch_gate(st, h->dsync.p, op.sigma, h->dflags.p, h->batch); break;
+      case OP_PANEL: {
+        PanelCadArgs px{op.nrp, op.form, op.skipw, op.colbuf ? h->dcolbuf.p : nullptr};
+        if (op.sync) px.sync = h->dsync.p, px.tail_target = op.target, px.start_sigma = op.sigma;
+        StepBufs pb = s;
+        if (!op.keep_prow3) pb.prow3_out = nullptr;
+        e = launch_profiled(h, op.cls, st, [&] { launch_panels_cad(st, bank, pb, n_hi, px); });
+        h->dcur ^= 1;
+        h->cur ^= 1;
+        h->pending_k += op.ranks;
+        h->pending_steps = op.steps_after;
+        break;
+      }
+      case OP_PASS: e = flush_pending(h, st, op.wv ? s.cad : nullptr); break;
+      case OP_MARK: launch_mark(st, h->dsync.p, op.sigma); break;
+      case OP_GATHER:
+        e = launch_profiled(h, op.cls, st, [&] { launch_gather_cad(st, bank, s.dacc_in, h->d_stream.p, row[op.which], op.kb, h->dcfg, h->dgbuf.p); });
+        break;
+      case OP_FORK: e = hand_over(h, "ev_fork", h->ev_fork, h->stream, h->aux); break;
+      case OP_JOIN: e = hand_over(h, "ev_join", h->ev_join, h->aux, h->stream); break;
+      case OP_JOIN_AUX: e = hand_over(h, "ev_pass", h->ev_pass, h->aux, h->stream); break;
     }
-    h->chained += 1;
-    h->lookaheads += 1;
-    *next_presolved = true;
-    return EKF_OK;
+    // (the launches are checked where the cadence's own kernels go out: a failed log or gate launch shows at the next of them,
+    //  the pass and the events' hand-overs check themselves)
+    const bool check = op.kind == OP_SOLVE || op.kind == OP_CHAIN || op.kind == OP_PANEL || op.kind == OP_MARK || op.kind == OP_GATHER;
+    if (e == EKF_OK && check && hipGetLastError() != hipSuccess)
+      e = fail(h, EKF_ERR_HIP, std::string("fused cadence: launch of the ") + OP_NAME[op.kind] + (op.which == CAD_NEXT ? " (next cadence) failed" : " failed"));
+    if (e == EKF_OK) {
+      done |= 1u << op.kind;
+      continue;
+    }
+    if (!committed) {
+      // what the plan advanced and the launches did not: the parity and the cadence's count move with the panel launch, the
+      // inputs formed ahead with the chain launch, the second stream stays to be joined unless the join went out; the other
+      // statistics count completed cadences.  sigma, gather_count and the serial only grow: they mirror the device's counters.
+      CadRun& r = h->run;
+      if (!(done & 1u << OP_PANEL)) r.cpar = before.cpar, r.cadences = before.cadences, r.cadence_traj_steps = before.cadence_traj_steps;
+      if (!(done & 1u << OP_CHAIN)) r.pre_serial[0] = before.pre_serial[0], r.pre_serial[1] = before.pre_serial[1];
+      r.aux_pass = before.aux_pass && !(done & 1u << OP_JOIN_AUX);
+      r.lookaheads = before.lookaheads, r.chained = before.chained, r.w_from_v_passes = before.w_from_v_passes;
+      return e;
+    }
+    if (rc == EKF_OK) rc = e, first_err = h->err;
   }
-  if (rc != EKF_OK) return rc;
-  if (h->pending_k == 0) {                             // nothing observed anywhere in the bank: the panel launch has applied the noise
-    h->pending_steps = 0;
-    return EKF_OK;
-  }
-  if (!due) return EKF_OK;
-  if (!beside) {
-    if (wv) h->w_from_v_passes += 1;
-    return flush_pending(h, nullptr, wv ? cad.cad : nullptr);
-  }
-  RES_TRY(h, "the look-ahead's block buffer", h->dgbuf.ensure((size_t)cadence_gbuf_doubles() * h->batch));
-  // ---- look-ahead: gather (stream) -> { pass (second stream) | solve of the next cadence (stream) } -> join ----
-  const int kb = pending_kb(h);
-  {
-    ProfBracket pb;
-    if (int rc2 = prof_open(h, 2, h->stream, &pb)) return rc2;
-    launch_gather_cad(h->stream, bank, next.dacc_in, h->d_stream.p, dpl2, kb, h->dcfg, h->dgbuf.p);
-    if (int rc2 = prof_close(h, &pb)) return rc2;
-  }
-  HIP_TRY(h, hipGetLastError());
-  RES_TRY(h, "ev_fork", h->ev_fork.record(h->stream));
-  HIP_TRY(h, hipStreamWaitEvent(h->aux, h->ev_fork.ev, 0));
-  // (the solve first: it is ready to go the moment the gather ends, the pass has an event to wait for -- the one
-  //  workgroup per trajectory finds its CU before the pass fills the chip)
-  {
-    ProfBracket pb;
-    if (int rc2 = prof_open(h, 1, h->stream, &pb)) return rc2;
-    SolveCadArgs sx;                                   // (the block in the gather's parts; the mean is the handle's)
-    sx.gbuf = h->dgbuf.p, sx.gparts = (kb + 7) / 8;
-    sx.chain = h->chain_run;
-    launch_solve_cad(h->stream, bank, next, h->d_stream.p, dpl2, h->dcfg, n_hi, sx, plg);
-    if (int rc2 = prof_close(h, &pb)) return rc2;
-  }
-  log_cadence(h, dpl2, next.cad);
-  // From here on the next cadence's solve has overwritten the pose mean and the pending-noise buffer: a failure
-  // below cannot be undone.  Whatever happens the two streams are joined again, and a failure marks every trajectory
-  // undefined (EKF_ERR_STATE from then on, until it is uploaded again).
-  if (hipGetLastError() != hipSuccess) rc = fail(h, EKF_ERR_HIP, "look-ahead: launch of the next cadence's solve failed");
-  if (rc == EKF_OK) rc = flush_pending(h, h->aux);
-  const hipError_t ej = (hipError_t)h->ev_join.record(h->aux).err;
-  const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(h->stream, h->ev_join.ev, 0) : ej;   // whatever follows on the handle's stream follows the pass
-  if (rc == EKF_OK && ew != hipSuccess) rc = fail(h, EKF_ERR_HIP, std::string("look-ahead: joining the streams failed: ") + hipGetErrorString(ew));
   if (rc != EKF_OK) {
     (void)hipStreamSynchronize(h->aux);
+    (void)hipStreamSynchronize(h->stream);
+    h->run.aux_pass = false;
     std::fill(h->host_bad.begin(), h->host_bad.end(), (unsigned char)1);
+    h->err = first_err;
     return rc;
   }
-  h->lookaheads += 1;
-  *next_presolved = true;
+  *next_presolved = L.next_presolved;
   return EKF_OK;
 }
 
@@ -2125,9 +2091,11 @@ static int pair_flush(ekf_handle* dst, ekf_handle* src, const char* fn) {
 //   dcad2, dcolbuf         a cadence's records and gathered columns: consumed by its own panel launch and pass.
 //   dprow3                 pose rows behind a chained cadence: every chained run starts by taking them from P_base (launch_snap_pose).
 //   dgmu, dgbuf, dxg, dbg  the next cadence's block and mean, formed inside a run for its next solve; a run's last cadence forms none.
-//   dpre, pre_serial       inputs formed one cadence ahead: looked up by the handle's cadence serial, which only grows, and never
-//                          formed beyond the run's last cadence.
-//   dsync, dqueue, drm_flag, rm_seq, step_seq, sigma, gather_count   counters of the handle, not of a trajectory.
+//   dpre, run.pre_serial   inputs formed one cadence ahead: looked up by the handle's cadence serial (CadRun::cad_serial), which
+//                          only grows, and never formed beyond the run's last cadence.
+//   dsync, dqueue, drm_flag, rm_seq, step_seq, and CadRun's sigma and gather_count (h->run)   counters of the handle, not of a
+//                          trajectory; the rest of CadRun is parities, serials and statistics of the handle too: a copy or a join
+//                          leaves the whole struct alone.
 //   dfloor                 uploaded from the host's bound by push_floor below.
 //   dneff                  the device's copy of the bound: written from the host's before the next device-side window (the sizes
 //                          of both handles are refreshed first, so the host's are current).
@@ -2209,11 +2177,11 @@ extern "C" int ekf_join_maps(ekf_handle* dst, const int* dst_b, ekf_handle* src,
   HIP_TRY(dst, hipMemcpyAsync(dst->djn_tab.p, jp.tab.data(), sizeof(int) * jp.tab.size(), hipMemcpyHostToDevice, dst->stream));
   if (!jp.seq)
     HIP_TRY(dst, hipMemcpyAsync(dst->djn_snap.p, jp.frame.data(), sizeof(double) * jp.frame.size(), hipMemcpyHostToDevice, dst->stream));
-  ProfBracket pb;
-  if (int rc = prof_open(dst, 6, dst->stream, &pb)) return rc;
-  launch_join(dst->stream, bank_view(src), bank_view(dst), src->dmu2[src->cur].p, dst->dmu2[dst->cur].p, dst->djn_tab.p, dst->djn_snap.p,
-              k, jp.tiles_hi, jp.na_hi, jp.seq);
-  if (int rc = prof_close(dst, &pb)) return rc;
+  if (int rc = launch_profiled(dst, 6, dst->stream, [&] {
+        launch_join(dst->stream, bank_view(src), bank_view(dst), src->dmu2[src->cur].p, dst->dmu2[dst->cur].p, dst->djn_tab.p,
+                    dst->djn_snap.p, k, jp.tiles_hi, jp.na_hi, jp.seq);
+      }))
+    return rc;
   HIP_TRY(dst, hipGetLastError());
   for (int i = 0; i < k; ++i) {
     const int* w = jp.tab.data() + (size_t)JOIN_PAIR_WORDS * i;
@@ -2292,10 +2260,8 @@ extern "C" int ekf_transform(ekf_handle* h, int b0, int count, const double* T, 
   // (nontemporal stores unless EKFSLAM_HIP_TRANSFORM_NT=0: tools/transform_time.py measures both, profiles/transform.txt)
   bool nt = true;
   if (const char* e = std::getenv("EKFSLAM_HIP_TRANSFORM_NT")) nt = std::atoi(e) != 0;
-  ProfBracket pb;
-  if (int rc = prof_open(h, 8, h->stream, &pb)) return rc;
-  launch_transform(h->stream, nt, bank_view(h), mu, h->dtf_tab.p, h->dtf_frame.p, count, tp.tiles_hi);
-  if (int rc = prof_close(h, &pb)) return rc;
+  if (int rc = launch_profiled(h, 8, h->stream, [&] { launch_transform(h->stream, nt, bank_view(h), mu, h->dtf_tab.p, h->dtf_frame.p, count, tp.tiles_hi); }))
+    return rc;
   HIP_TRY(h, hipGetLastError());
   if (tp.with_cov) {
     for (int t = b0; t < b0 + count; ++t) h->neff[t] = h->neff_enq[t] = h->n[t];
@@ -2350,10 +2316,8 @@ extern "C" int ekf_predict_linear(ekf_handle* h, int b0, int count, const double
   const PredictIn* in;
   if (int rc = ring_submit(h, r, direct, (size_t)count, &in)) return rc;
   if (pp.n_hi > 0) {
-    ProfBracket pb;
-    if (int rc = prof_open(h, 7, h->stream, &pb)) return rc;
-    launch_predict_pose(h->stream, pending_view(h, b0, count), h->dP.p, h->dmu2[h->cur].p, in, pp.n_hi);
-    if (int rc = prof_close(h, &pb)) return rc;
+    if (int rc = launch_profiled(h, 7, h->stream, [&] { launch_predict_pose(h->stream, pending_view(h, b0, count), h->dP.p, h->dmu2[h->cur].p, in, pp.n_hi); }))
+      return rc;
     HIP_TRY(h, hipGetLastError());
   }
   if (int rc = ring_launched(h, r, direct)) return rc;
@@ -2392,13 +2356,9 @@ static int loc_begin(ekf_handle* h) {
 }
 static int loc_pass(ekf_handle* h, const StepIn* in, int groups) {
   const BankView bank = bank_view(h);
-  ProfBracket pb;
-  if (int rc = prof_open(h, 9, h->stream, &pb)) return rc;
-  launch_loc_solve(h->stream, bank, h->dmu2[h->cur].p, in, h->dfloor.p, h->dloc.p, h->dcfg);
-  if (int rc = prof_close(h, &pb)) return rc;
-  if (int rc = prof_open(h, 10, h->stream, &pb)) return rc;
-  launch_loc_rows(h->stream, bank, h->dloc.p, groups);
-  if (int rc = prof_close(h, &pb)) return rc;
+  if (int rc = launch_profiled(h, 9, h->stream, [&] { launch_loc_solve(h->stream, bank, h->dmu2[h->cur].p, in, h->dfloor.p, h->dloc.p, h->dcfg); }))
+    return rc;
+  if (int rc = launch_profiled(h, 10, h->stream, [&] { launch_loc_rows(h->stream, bank, h->dloc.p, groups); })) return rc;
   if (h->dinnov.p && h->lg_slot >= 0)
     launch_innov_step(h->stream, in, h->dso.p, h->dcfg.enable_measurement_model, h->dcfg.gate_rej != nullptr, h->batch,
                       innov_log(h, h->lg_slot, h->lg_jbase));
@@ -2519,11 +2479,11 @@ extern "C" int ekf_localize_detections(ekf_handle* h, const double* lin, const d
   const DetIn* ds;
   if (int rc = upload_detections(h, lin, ang, count, tag_id, pose_t, pose_err, stride, &ds)) return rc;
   h->acfg.active_bound = h->opt_active_bound;
-  ProfBracket pb;
-  if (int rc = prof_open(h, 11, h->stream, &pb)) return rc;
-  launch_loc_associate(h->stream, bank_view(h), ds, h->dtagmap.p, h->dneff.p, h->dmu2[h->cur].p, h->d_assoc_step.p, h->d_assoc_out.p,
-                       h->d_unmatched.p, h->acfg);
-  if (int rc = prof_close(h, &pb)) return loc_half_failed(h, rc);
+  if (int rc = launch_profiled(h, 11, h->stream, [&] {
+        launch_loc_associate(h->stream, bank_view(h), ds, h->dtagmap.p, h->dneff.p, h->dmu2[h->cur].p, h->d_assoc_step.p,
+                             h->d_assoc_out.p, h->d_unmatched.p, h->acfg);
+      }))
+    return loc_half_failed(h, rc);
   if (hipGetLastError() != hipSuccess) return loc_half_failed(h, fail(h, EKF_ERR_HIP, std::string(fn) + ": the association's launch failed"));
   h->sizes_dirty = true;
   LogScope log(h, true);
@@ -2701,34 +2661,7 @@ extern "C" int ekf_stream_run(ekf_handle* h, int first, int count) {
       const int piece_end = std::min(first + count, k + 8192);
       plan_cadences(h, k, piece_end, h->run_plan);
       if (int rc = upload_run_plan(h)) return rc;
-      // chained solves: decided per piece; whether a cadence is chained to the next is decided where the pass between them
-      // is planned (plan_cadence_step)
-      h->chain_run = plan_chain_run(h, h->run_plan.ncad);
-      // (everything a cadence touches exists before the piece's first launch: between the enqueue of a chained launch that
-      //  waits on a device-side counter and the enqueue of the launch that advances it the host must not block -- an
-      //  allocation may.  The chained set is one group; it shares the records and the block buffer with the look-ahead's
-      //  set, whose block buffer is allocated where a look-ahead first runs: enqueue_cadence.)
-      const size_t B = (size_t)h->batch;
-      if (!h->chain_run) {
-        RES_TRY(h, "the cadence records", res::ensure_group(nullptr, res::want(h->dcad2[0], B), res::want(h->dcad2[1], B)));
-      } else {
-        const int n_hi = bank_n_hi(h, false);
-        const size_t gw = B * 84 * 88;
-        bool fresh;
-        RES_TRY(h, "the chained run's buffers",
-                res::ensure_group(&fresh, res::want(h->dcad2[0], B), res::want(h->dcad2[1], B),
-                                  res::want(h->dgbuf, (size_t)cadence_gbuf_doubles() * B),
-                                  res::want(h->dprow3[0], 3 * (size_t)h->ld * B), res::want(h->dprow3[1], 3 * (size_t)h->ld * B),
-                                  res::want(h->dxg, gw), res::want(h->dbg, gw), res::want(h->dsync, (size_t)chain_sync_words()),
-                                  res::want(h->dpre[0], B), res::want(h->dpre[1], B), res::want(h->dgmu, 128 * B)));
-        if (fresh) {
-          HIP_TRY(h, hipMemsetAsync(h->dsync.p, 0, sizeof(unsigned) * chain_sync_words(), h->stream));
-          HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the second stream's launches read the counters too)
-        }
-        // the pose rows "before the first cadence": where the previous cadence's panel launch would have left them
-        launch_snap_pose(h->stream, bank_view(h), n_hi, step_bufs(h).prow3_in);
-        HIP_TRY(h, hipGetLastError());
-      }
+      if (int rc = prepare_piece(h)) return rc;
       bool presolved = false;                          // the next cadence's solve has been enqueued already (chained / look-ahead)
       for (int c = 0; c < h->run_plan.ncad; ++c)
         if (int rc = enqueue_cadence(h, c, presolved, &presolved)) return rc;
@@ -2921,19 +2854,19 @@ extern "C" int ekf_debug_last_pass_shares(ekf_handle* h) { return h ? h->last_sh
 // they covered: tests assert that the path they mean to check is the one that ran
 extern "C" int ekf_debug_cadences(ekf_handle* h, long* cadences, long* steps) {
   if (!h) return EKF_ERR_ARG;
-  if (cadences) *cadences = h->cadences;
-  if (steps) *steps = h->cadence_traj_steps / std::max(h->batch, 1);
+  if (cadences) *cadences = h->run.cadences;
+  if (steps) *steps = h->run.cadence_traj_steps / std::max(h->batch, 1);
   return EKF_OK;
 }
 // (diagnostics section of the header) how many of them had their solve run beside the previous covariance pass
-extern "C" long ekf_debug_lookaheads(ekf_handle* h) { return h ? h->lookaheads : -1; }
+extern "C" long ekf_debug_lookaheads(ekf_handle* h) { return h ? h->run.lookaheads : -1; }
 // (diagnostics section of the header) host fallbacks of the device-side association, as the binding reported them
 extern "C" long ekf_debug_assoc_fallbacks(ekf_handle* h) { return h ? h->assoc_fallbacks : -1; }
 extern "C" void ekf_debug_note_assoc_fallback(ekf_handle* h) { if (h) h->assoc_fallbacks += 1; }
 // (diagnostics section of the header) ... and how many of those had their block formed by k_chain_cad (chained solves)
-extern "C" long ekf_debug_chained(ekf_handle* h) { return h ? h->chained : -1; }
+extern "C" long ekf_debug_chained(ekf_handle* h) { return h ? h->run.chained : -1; }
 // ... and covariance passes that formed their W fragments from V and the records ("w_from_v")
-extern "C" long ekf_debug_w_from_v(ekf_handle* h) { return h ? h->w_from_v_passes : -1; }
+extern "C" long ekf_debug_w_from_v(ekf_handle* h) { return h ? h->run.w_from_v_passes : -1; }
 extern "C" int ekf_debug_last_pass_wv(ekf_handle* h) { return h ? h->last_wv : -1; }
 // (diagnostics section of the header) launches of the small-state path so far
 extern "C" long ekf_debug_small_launches(ekf_handle* h) { return h ? h->small_launches : -1; }
@@ -2943,10 +2876,10 @@ extern "C" long ekf_debug_fetch_retries(ekf_handle* h) { return h ? h->fetch_ret
 
 // (diagnostics section of the header) the fused cadence's record of trajectory b (head + per-landmark records)
 extern "C" long ekf_debug_cad(ekf_handle* h, int b, void* dst, long bytes) {
-  if (!h || b < 0 || b >= h->batch || !h->dcad2[h->cpar ^ 1].p) return -1;
+  if (!h || b < 0 || b >= h->batch || !h->dcad2[h->run.cpar ^ 1].p) return -1;
   if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return -1;
   const long have = (long)sizeof(CadOut);
-  if (dst && bytes > 0 && hipMemcpy(dst, h->dcad2[h->cpar ^ 1].p + b, (size_t)std::min(bytes, have), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (dst && bytes > 0 && hipMemcpy(dst, h->dcad2[h->run.cpar ^ 1].p + b, (size_t)std::min(bytes, have), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   return have;
 }
 

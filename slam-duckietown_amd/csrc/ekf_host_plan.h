@@ -18,6 +18,24 @@ namespace ekf {
 
 constexpr int RS_ROWS = 128;            // rows of a slab of the row-slab pass = 8 waves x 16
 
+// The state of the fused cadences of ekf_stream_run, carried from cadence to cadence and from run to run: what
+// plan_cadence_launches reads and advances (plain counters and parities: the buffers they select are the handle's).
+struct CadRun {
+  int cpar = 0;                   // which copy of the records (dcad2) and pose rows (dprow3) the next cadence uses: flips per cadence
+  unsigned sigma = 0;             // chained transitions so far (the value the run's counters SYNC_SOLVE / SYNC_PASS carry)
+  unsigned gather_count = 0;      // gather workgroups launched so far (what the next chain workgroups wait for)
+  // a cadence's inputs formed one cadence ahead (CadPre): two copies, by the cadence's serial number (pre_serial: whose inputs a
+  // copy holds; serials count every cadence of the handle)
+  long cad_serial = 0;
+  long pre_serial[2] = {-1, -1};
+  bool aux_pass = false;          // a covariance pass is in flight on the second stream (JOIN_AUX / join_aux makes the handle's wait)
+  // statistics
+  long cadences = 0, cadence_traj_steps = 0;   // fused cadences launched, trajectory-steps they completed
+  long lookaheads = 0;            // cadences whose solve ran beside the previous pass (look-ahead and chained)
+  long chained = 0;               // ... of those: cadences whose block came from k_chain_cad
+  long w_from_v_passes = 0;       // passes that formed W from V ("w_from_v")
+};
+
 // What the planning functions read of a handle (ekf_handle derives from this).
 struct HostPlan {
   int device = 0, n_max = 0, ld = 0, rows = 0, batch = 0;
@@ -48,7 +66,11 @@ struct HostPlan {
   int opt_panel_shape = 0;        // diagnostics: 0 = the panel launch's shape by its size; 1 k_panels_cad_ks, 2 k_panels_cad<1>, 3 k_panels_cad<4> whatever the size
   int opt_panel_tform = 1;        // 1 = a chained cadence's panel launch in the latency regime takes the triangular-solve form (k_panels_cad_tf)
   int opt_col_gather = 1;         // 1 = the solve gathers the panel launch's mirrored column entries beside it, 0 = the panel launch gathers everything itself
-  bool chain_run = false;         // the run in flight records the transforms (every solve is k_solve_cad<true>)
+  // the piece of a run in flight, decided before its first cadence (ekf_api.hip: prepare_piece): its solves record the transforms
+  // (every solve is k_solve_cad<true>), and the gather workgroups per trajectory of its chain launches (chain_gather_workgroups)
+  bool chain_run = false;
+  int chain_gw = 1;
+  CadRun run;                     // the fused cadences' state (plan_cadence_launches)
   int opt_small_state = 1;        // 1 = small filters (n_max <= 79: up to 38 landmarks) run in ONE workgroup, P in LDS (ekf_small.hip)
   int opt_rows_per_block = 0;     // 0 = auto (flush kernel: rows per workgroup, multiple of 16)
   int opt_pass_chunk = 0;         // 0 = auto (k_flush_rs: strips per unit)
@@ -559,7 +581,7 @@ inline void plan_cadences(const HostPlan* h, int k, int end, RunPlan& rp) {
 
 // ---- a fused cadence and what follows it (ekf_api.hip: enqueue_cadence, ekf_stream_run) ----
 // Small launches, where the covariance pass leaves CUs free, run the next cadence's solve beside the pass (look-ahead) or chain
-// the solves (see enqueue_cadence).  Worth it where the pass is the column-strip kernel -- the row-slab pass fills every CU by
+// the solves (see plan_cadence_launches).  Worth it where the pass is the column-strip kernel -- the row-slab pass fills every CU by
 // itself -- and long enough to pay for the gather and the two cross-stream hand-overs, ~25 us together: from ~48 MB of
 // covariance (LOOKAHEAD_MIN_MB; the chained order, whose hand-overs are counters instead of events, at every size: it wins at
 // every size tried, N = 12 .. 1000, banks of 1 .. 32: +25 .. +43 %).  N = 2000 x 1: 38.7 k -> 45.1 k steps/s, x 2: 57.6 k ->
@@ -635,6 +657,167 @@ inline CadStepPlan plan_cadence_step(const HostPlan* h, const RunPlan& rp, int c
   p.w_from_v = h->opt_w_from_v && p.due && !p.beside && h->pending_k == 0 && ranks > 0 &&
                (p.panel == PANEL_ONE || p.panel == PANEL_FOUR) && plan_pass(h, pend_after).kernel == 2;
   return p;
+}
+
+// ---- a cadence's launches, in the order they are enqueued (ekf_api.hip: enqueue_cadence only executes the list) ----
+// Cadence c of the run in flight (the run plan `rp`, uploaded): one solve launch, one panel launch; the covariance pass follows
+// when it is due -- behind every cadence but the run's last, and behind that one when its slots are used up.
+//
+// Small launches, where the covariance pass leaves CUs free (the column-strip kernel on at least ~48 MB of covariance; the
+// row-slab pass on static shares: a few long trajectories), do not run solve -> panel -> pass -> solve one behind the
+// other: the only true dependency between two cadences of a trajectory is the sequential landmark recurrence
+// (src/replay_no_ros.py:436-480: landmark j + 1 is linearised at the mean landmark j produced).  Three orders:
+//   * SERIAL: [solve_c, log] -> panel_c -> pass_c where one is due and ranks are pending, all on the handle's stream.
+//   * CHAINED SOLVES (round 6, "chain" = 1): every solve of the run also records the pose block behind its cadence
+//     (k_solve_cad<true>: CadOut::posefin); k_chain_cad forms the next cadence's block and mean from the cadence's records and
+//     from P_base as it stood BEFORE the cadence, so the handle's stream runs  solve_c -> chain_{c+1} -> solve_{c+1} -> ...  while
+//     the second stream runs  gate -> panel_c -> pass_c -> mark -> gate -> ...  Hand-overs are device-scope counters (ekf_cadence.hip:
+//     SYNC_*): the gate waits for solve_c (announced by chain_{c+1}'s start); panel_c ends when chain_{c+1}'s gather workgroups
+//     have read what the pass rewrites and solve_{c+1} has been placed; chain_{c+1}'s gathers wait for the mark behind pass_{c-1}.
+//     No event: a hand-over through the command processor costs the waiting stream 7 us behind a record and ~19 us across
+//     streams (profiles/r06_chained_solves.txt); the counters cost a load.  Two copies of the records, of the pose rows (dprow3)
+//     and of the inputs formed ahead (CadPre), used alternately.
+//     A transition is ENQUEUED chain, solve, gate, panel, pass, mark: every device-side wait is for a launch that is already in
+//     its queue (chain_{c+1}'s gathers: the previous transition's mark; panel_c: chain_{c+1}'s start and gathers, solve_{c+1}'s
+//     start), so nothing can hang where the runtime maps both streams onto one hardware queue -- and the host calls nothing
+//     that may block in between (every buffer exists before the cadence's first launch).  tests/host_plan_check.cpp
+//     (check_cadence_orders) walks whole runs of these lists and checks exactly that.
+//   * LOOK-AHEAD (round 3, "chain" = 0): panel_c -> k_gather_cad (the next block from P_base and the ranks still pending) ->
+//     fork -> solve_{c+1} (first: it is ready to go the moment the gather ends, the pass has an event to wait for -- the one
+//     workgroup per trajectory finds its CU before the pass fills the chip) | pass_c on the second stream -> join.
+// `presolved` says that this cadence's solve has already been enqueued one of these ways; next_presolved that the next one's
+// now is.  plan_cadence_step decides the flags (beside_the_pass where a pass leaves CUs to the next solve); this function turns
+// them into the list and advances h->run.  The host's pending_k / pending_steps move where the list is executed: the PANEL op
+// carries what it adds, the PASS clears them (flush_pending).
+enum CadOpKind {
+  OP_SOLVE, OP_LOG, OP_CHAIN, OP_GATE, OP_PANEL, OP_PASS, OP_MARK, OP_GATHER,
+  OP_FORK,             // record ev_fork on the handle's stream, the second stream waits
+  OP_JOIN,             // record ev_join on the second stream, the handle's waits
+  OP_JOIN_AUX,         // the handle's stream waits for the chained passes in flight on the second (ev_pass)
+};
+enum CadStream { ON_MAIN, ON_AUX };                    // the handle's stream, its second stream
+enum CadWhich { CAD_THIS = 0, CAD_NEXT = 1 };          // this cadence's buffers and plan row, or those of the one after it
+struct CadOp {
+  int kind = OP_SOLVE, stream = ON_MAIN;
+  int which = CAD_THIS;    // (CHAIN reads this cadence's buffers whichever: `which` is the cadence whose block it forms)
+  int cls = -1;            // profile class of its event pair: 1 solve, 2 chain / gather, 3 panel; 0 the pass (its own sampled pair); -1 none
+  bool no_way_back = false;   // from this op on the next cadence's solve overwrites the pose mean and the pending-noise buffer:
+                              // a failure cannot be undone (enqueue_cadence joins the streams and marks every trajectory undefined)
+  bool sync = false;       // SOLVE, PANEL: takes part in the chained hand-overs (SOLVE: block and mean are the chain launch's)
+  unsigned sigma = 0;      // CHAIN, GATE, MARK: the transition; SOLVE, PANEL: start_sigma
+  unsigned target = 0;     // CHAIN: gather_target; PANEL: tail_target
+  // SOLVE (SolveCadArgs)
+  int gparts = 0;          // parts of the block in the block buffer (0: the solve gathers its block itself)
+  bool chain = false;      // the instantiation that records the cadence's transform
+  bool colbuf = false;     // SOLVE, PANEL: the mirrored column entries go through the column buffer
+  int col_wgs = 0;
+  // CHAIN (ChainArgs); pre_in also SOLVE: the copy of CadPre read / written, -1: none
+  int pre_in = -1, pre_out = -1, gw = 1;
+  bool wait_pass = false, plan2 = false;   // plan2: the plan row of the cadence after the next follows (for pre_out)
+  // PANEL (PanelCadArgs), and what the host's pending counts become behind it
+  int nrp = 0, form = 0, ranks = 0, steps_after = 0;
+  bool skipw = false, keep_prow3 = false;
+  int kb = 0;              // GATHER: the pending ranks in whole k-tiles
+  bool wv = false;         // PASS: forms W from V
+};
+constexpr int CAD_OPS_MAX = 12;
+struct CadLaunches {
+  int n = 0;
+  CadOp op[CAD_OPS_MAX];
+  bool next_presolved = false;
+  CadOp& add(int kind, int stream, int which, int cls) {
+    CadOp& o = op[n++];
+    o.kind = kind, o.stream = stream, o.which = which, o.cls = cls;
+    return o;
+  }
+};
+// `cp`: plan_cadence_step's answer for the same arguments (the caller has it: it decides which optional buffers must exist)
+inline CadLaunches plan_cadence_launches(HostPlan* h, const RunPlan& rp, int c, int n_hi, bool presolved, const CadStepPlan& cp) {
+  CadLaunches L;
+  CadRun& r = h->run;
+  const long serial = r.cad_serial++;                  // this cadence's number (CadPre copies are looked up by it)
+  const int ranks = 2 * rp.slots_hi[c];                // every trajectory writes the busiest one's ranks (zeros beyond its own)
+  const int pend_after = h->pending_k + ranks;
+  auto join_aux = [&] {                                // whatever is still running on the second stream is waited for
+    if (r.aux_pass) L.add(OP_JOIN_AUX, ON_MAIN, CAD_THIS, -1);
+    r.aux_pass = false;
+  };
+  auto solve = [&](int which) -> CadOp& {
+    CadOp& s = L.add(OP_SOLVE, ON_MAIN, which, 1);
+    s.chain = h->chain_run;
+    return s;
+  };
+  if (!presolved) {
+    join_aux();
+    CadOp& s = solve(CAD_THIS);
+    s.colbuf = cp.gather_cols, s.col_wgs = cp.col_wgs;
+    L.add(OP_LOG, ON_MAIN, CAD_THIS, -1);
+  }
+  CadOp panel;
+  panel.kind = OP_PANEL, panel.cls = 3;
+  panel.nrp = (ranks + 3) & ~3, panel.form = cp.panel, panel.skipw = cp.w_from_v, panel.colbuf = cp.gather_cols;
+  panel.keep_prow3 = h->chain_run;                      // (only a chained run keeps the pose rows)
+  panel.ranks = ranks;
+  panel.steps_after = pend_after == 0 ? 0 : h->pending_steps + rp.steps_hi[c];   // (nothing observed anywhere in the bank: the panel launch applies the noise)
+  if (cp.chain_next) {
+    // the handle's stream: chain_{c+1} -> solve_{c+1}; the second stream: gate -> panel_c -> pass_c -> mark
+    r.sigma += 1u;
+    const int gw = h->chain_gw;
+    r.gather_count += (unsigned)(h->batch * gw);
+    CadOp& ch = L.add(OP_CHAIN, ON_MAIN, CAD_NEXT, 2);
+    ch.sigma = r.sigma, ch.target = r.gather_count, ch.gw = gw, ch.wait_pass = r.aux_pass;
+    // the next cadence's inputs if an earlier chain launch formed them; the one after it: formed by this launch
+    ch.pre_in = r.pre_serial[(serial + 1) & 1] == serial + 1 ? (int)((serial + 1) & 1) : -1;
+    ch.pre_out = c + 2 < rp.ncad ? (int)((serial + 2) & 1) : -1;
+    ch.plan2 = ch.pre_out >= 0;
+    if (ch.pre_out >= 0) r.pre_serial[ch.pre_out] = serial + 2;
+    CadOp& s = solve(CAD_NEXT);                        // (block and mean from the chain launch: one part, no columns to gather)
+    s.no_way_back = true;
+    s.gparts = 1, s.chain = true, s.sync = true, s.sigma = r.sigma, s.pre_in = ch.pre_in;
+    L.add(OP_LOG, ON_MAIN, CAD_NEXT, -1);              // (enqueued before the gate: it waits for nothing)
+    // (a one-lane gate in front of the panel launch: ~5 us of the second stream, which has them to spare, and no workgroup of
+    //  a large launch ever spins)
+    L.add(OP_GATE, ON_AUX, CAD_THIS, -1).sigma = r.sigma;
+    panel.stream = ON_AUX, panel.sync = true, panel.target = r.gather_count, panel.sigma = r.sigma;
+  } else {
+    join_aux();
+  }
+  L.op[L.n++] = panel;
+  r.cpar ^= 1;
+  r.cadences += 1;
+  r.cadence_traj_steps += rp.steps_sum[c];
+  if (cp.chain_next) {
+    // pass_c behind the panel launch on the second stream, then the mark the next chain launch's gather workgroups wait for
+    L.add(OP_PASS, ON_AUX, CAD_THIS, 0);
+    L.add(OP_MARK, ON_AUX, CAD_THIS, -1).sigma = r.sigma;
+    r.aux_pass = true;
+    r.chained += 1;
+    r.lookaheads += 1;
+    L.next_presolved = true;
+    return L;
+  }
+  if (pend_after == 0 || !cp.due) return L;
+  if (!cp.beside) {
+    if (cp.w_from_v) r.w_from_v_passes += 1;
+    L.add(OP_PASS, ON_MAIN, CAD_THIS, 0).wv = cp.w_from_v;
+    return L;
+  }
+  // look-ahead: gather (stream) -> { pass (second stream) | solve of the next cadence (stream) } -> join
+  const int kb = (pend_after + 3) & ~3;                // (pending_kb behind the panel launch)
+  L.add(OP_GATHER, ON_MAIN, CAD_NEXT, 2).kb = kb;
+  L.add(OP_FORK, ON_MAIN, CAD_THIS, -1);
+  CadOp& s = solve(CAD_NEXT);                          // (the block in the gather's parts; the mean is the handle's)
+  s.no_way_back = true;
+  s.gparts = (kb + 7) / 8;
+  L.add(OP_LOG, ON_MAIN, CAD_NEXT, -1);
+  L.add(OP_PASS, ON_AUX, CAD_THIS, 0);
+  L.add(OP_JOIN, ON_AUX, CAD_THIS, -1);                // whatever follows on the handle's stream follows the pass
+  r.lookaheads += 1;
+  L.next_presolved = true;
+  return L;
+}
+inline CadLaunches plan_cadence_launches(HostPlan* h, const RunPlan& rp, int c, int n_hi, bool presolved) {
+  return plan_cadence_launches(h, rp, c, n_hi, presolved, plan_cadence_step(h, rp, c, n_hi, presolved));
 }
 
 // ---- the small-state path (ekf_small.hip): a filter bank whose covariances fit the LDS of a CU runs whole streams of steps per

@@ -372,6 +372,252 @@ static void check_launch_plans(std::mt19937& rng) {
   }
 }
 
+// ---- a run's launch order (plan_cadence_launches): whole runs walked cadence by cadence on a model of the two in-order queues
+// and the four device-scope counters of ekf_cadence.hip, carrying CadRun and the pending counts as enqueue_cadence does ----
+struct OrderModel {
+  long seq = 0;                                        // the global enqueue sequence, across cadences, pieces and both streams
+  std::set<unsigned> solve_done, pass_done, solve_started, gathers_done;   // values SYNC_SOLVE / _PASS / _START / _GATHER will reach: their producers are enqueued
+  bool mark_outstanding = false;                       // a mark is on the second stream and the handle's has not waited for it
+  int aux_open = 0;                                    // launches on the second stream no join covers yet
+  long pre_serial[2] = {-1, -1};                       // whose inputs a CadPre copy holds ...
+  int pre_piece[2] = {-1, -1}, piece = 0;              // ... and the piece that formed them
+  int ahead_set = -1;                                  // the buffer set the solve enqueued ahead writes (-1: none ahead)
+  long chained = 0, lookahead = 0, serial = 0;         // transitions walked, by order
+};
+enum { ORDER_SERIAL, ORDER_LOOKAHEAD, ORDER_CHAINED };
+
+// One piece of a run (ekf_stream_run: plan_chain_run, the cadences, join_aux).  `want`: the order every cadence but the last
+// must take (-1: any); the last is serial.
+static void walk_piece(HostPlan& h, const RunPlan& rp, int n_hi, OrderModel& M, int want) {
+  h.chain_run = plan_chain_run(&h, rp.ncad);          // (ekf_api.hip: prepare_piece)
+  const int gw = h.chain_gw = chain_gather_workgroups(h.batch, h.cu_count);
+  bool presolved = false;
+  for (int c = 0; c < rp.ncad; ++c) {
+    const HostPlan before = h;
+    const CadStepPlan cp = plan_cadence_step(&before, rp, c, n_hi, presolved);
+    const CadLaunches L = plan_cadence_launches(&h, rp, c, n_hi, presolved);
+    const CadRun &r0 = before.run, &r1 = h.run;
+    const long serial = r0.cad_serial;
+    const int ranks = 2 * rp.slots_hi[c], pend_after = before.pending_k + ranks;
+    CHECK(L.n >= 1 && L.n <= CAD_OPS_MAX, "%d ops", L.n);
+    const CadOp *chain = nullptr, *ahead = nullptr, *own = nullptr, *panel = nullptr, *pass = nullptr, *gate = nullptr;
+    bool fork = false, join = false, committed = false;
+    const int solved_into = presolved ? M.ahead_set : -1;   // the set the previous cadence's list had this one's solve write
+    std::vector<int> on[2];                            // the kinds per stream, in order (the logs and the leading join apart)
+    for (int i = 0; i < L.n; ++i) {
+      const CadOp& op = L.op[i];
+      ++M.seq;
+      CHECK(op.stream == ON_MAIN || op.stream == ON_AUX, "stream %d", op.stream);
+      CHECK(op.which == CAD_THIS || op.which == CAD_NEXT, "which %d", op.which);
+      if (op.no_way_back) CHECK(op.kind == OP_SOLVE && op.which == CAD_NEXT && !committed, "no-way-back mark on op %d", op.kind);
+      committed = committed || op.no_way_back;
+      if (op.kind != OP_LOG && op.kind != OP_JOIN_AUX) on[op.stream].push_back(op.kind);
+      if (op.stream == ON_AUX && op.kind != OP_JOIN) M.aux_open += 1;
+      switch (op.kind) {
+        case OP_JOIN_AUX:
+          CHECK(i == 0 && op.stream == ON_MAIN && r0.aux_pass && M.mark_outstanding, "JOIN_AUX at %d", i);
+          M.mark_outstanding = false, M.aux_open = 0;
+          break;
+        case OP_SOLVE:
+          CHECK(op.stream == ON_MAIN && op.cls == 1, "solve on %d class %d", op.stream, op.cls);
+          if (op.which == CAD_THIS) {
+            own = &op;
+            CHECK(!presolved && !M.mark_outstanding && !chain && !panel, "a cadence's own solve");   // (behind everything on the second stream)
+            CHECK(!op.sync && op.gparts == 0 && op.pre_in < 0 && op.chain == before.chain_run, "own solve's arguments");
+          } else {
+            ahead = &op;
+            M.ahead_set = r0.cpar ^ CAD_NEXT;
+            CHECK(c + 1 < rp.ncad && op.gparts >= 1 && !op.colbuf && op.col_wgs == 0, "solve ahead");
+            // chained: block and mean are the chain launch's, already in this queue.  The solve itself waits on no counter
+            // (ekf_solve_cad_body.inc): with start_sigma it only ANNOUNCES that it has been placed (SYNC_START), for its panel
+            if (op.sync) {
+              CHECK(chain && op.sigma == chain->sigma && op.gparts == 1 && op.chain && op.pre_in == chain->pre_in, "chained solve");
+              M.solve_started.insert(op.sigma);
+            } else {
+              CHECK(fork && op.sigma == 0 && op.pre_in < 0 && op.chain == before.chain_run, "look-ahead solve");
+            }
+          }
+          break;
+        case OP_LOG: CHECK(op.stream == ON_MAIN && i > 0 && L.op[i - 1].kind == OP_SOLVE && L.op[i - 1].which == op.which, "log"); break;
+        case OP_CHAIN:
+          chain = &op;
+          CHECK(op.stream == ON_MAIN && op.which == CAD_NEXT && op.cls == 2, "chain");
+          CHECK(op.sigma == r0.sigma + 1u && op.target == r0.gather_count + (unsigned)(h.batch * gw) && op.gw == gw, "chain counters");
+          CHECK(op.wait_pass == M.mark_outstanding, "wait_pass %d, a mark outstanding %d", op.wait_pass, M.mark_outstanding);
+          if (op.wait_pass) CHECK(M.pass_done.count(op.sigma - 1u), "the chain's gathers wait for a mark that is not enqueued");
+          if (op.pre_in >= 0)
+            CHECK(M.pre_serial[op.pre_in] == serial + 1 && M.pre_piece[op.pre_in] == M.piece, "pre_in: copy %d holds %ld of piece %d", op.pre_in,
+                  M.pre_serial[op.pre_in], M.pre_piece[op.pre_in]);
+          else
+            for (int q = 0; q < 2; ++q) CHECK(!(M.pre_serial[q] == serial + 1 && M.pre_piece[q] == M.piece), "inputs formed ahead are not used");
+          CHECK((op.pre_out >= 0) == (c + 2 < rp.ncad) && op.plan2 == (op.pre_out >= 0) && (op.pre_out < 0 || op.pre_out != op.pre_in), "pre_out");
+          if (op.pre_out >= 0) M.pre_serial[op.pre_out] = serial + 2, M.pre_piece[op.pre_out] = M.piece;
+          M.solve_done.insert(op.sigma);               // (its start announces this cadence's solve, in front of it on the stream)
+          M.gathers_done.insert(op.target);
+          break;
+        case OP_GATE:
+          gate = &op;
+          CHECK(op.stream == ON_AUX && M.solve_done.count(op.sigma), "the gate waits for a chain launch that is not enqueued");
+          break;
+        case OP_PANEL:
+          panel = &op;
+          CHECK(op.which == CAD_THIS && op.cls == 3 && op.nrp == ((ranks + 3) & ~3) && op.ranks == ranks && op.form == cp.panel, "panel");
+          CHECK(op.skipw == cp.w_from_v && op.colbuf == cp.gather_cols && op.keep_prow3 == before.chain_run, "panel flags");
+          CHECK(presolved ? solved_into == r0.cpar : solved_into < 0, "the panel reads set %d, the solve ahead wrote %d", r0.cpar, solved_into);
+          if (op.sync) {
+            CHECK(op.stream == ON_AUX && chain && gate && ahead, "chained panel");
+            CHECK(op.target == chain->target && op.sigma == chain->sigma, "tail_target %u, gather_target %u", op.target, chain->target);
+            CHECK(M.gathers_done.count(op.target) && M.solve_started.count(op.sigma), "the panel waits for launches that are not enqueued");
+          } else {
+            CHECK(op.stream == ON_MAIN && !chain && !M.mark_outstanding, "panel on the handle's stream");
+          }
+          h.pending_k += op.ranks, h.pending_steps = op.steps_after;
+          CHECK(h.pending_steps == (pend_after == 0 ? 0 : before.pending_steps + rp.steps_hi[c]), "pending steps");
+          break;
+        case OP_PASS:
+          pass = &op;
+          CHECK(panel && h.pending_k > 0 && op.cls == 0 && op.wv == (cp.w_from_v && op.stream == ON_MAIN), "pass");
+          h.pending_k = 0, h.pending_steps = 0;
+          break;
+        case OP_MARK:
+          CHECK(op.stream == ON_AUX && pass && chain && op.sigma == chain->sigma && i == L.n - 1, "mark");
+          M.pass_done.insert(op.sigma);
+          M.mark_outstanding = true;
+          break;
+        case OP_GATHER:
+          CHECK(op.stream == ON_MAIN && op.which == CAD_NEXT && op.cls == 2 && panel && op.kb == ((h.pending_k + 3) & ~3) && op.kb > 0, "gather");
+          break;
+        case OP_FORK:
+          CHECK(op.stream == ON_MAIN && !fork && M.aux_open == 0, "fork");
+          fork = true;
+          break;
+        case OP_JOIN:
+          CHECK(op.stream == ON_AUX && fork && !join && i == L.n - 1, "join");
+          join = true, M.aux_open = 0;
+          break;
+        default: CHECK(false, "op kind %d", op.kind);
+      }
+    }
+    CHECK(fork == join, "a fork without its join in the same cadence");
+    CHECK((own != nullptr) == !presolved, "presolved %d, own solve %d", presolved, own != nullptr);
+    if (own) CHECK(own->colbuf == cp.gather_cols && own->col_wgs == cp.col_wgs, "column gather");
+    // per-stream order, by the order the list takes
+    const int order = chain ? ORDER_CHAINED : fork ? ORDER_LOOKAHEAD : ORDER_SERIAL;
+    std::vector<int> main_want, aux_want;
+    if (own) main_want.push_back(OP_SOLVE);
+    if (order == ORDER_CHAINED) {
+      main_want.insert(main_want.end(), {OP_CHAIN, OP_SOLVE});
+      aux_want = {OP_GATE, OP_PANEL, OP_PASS, OP_MARK};
+      M.chained += 1;
+    } else if (order == ORDER_LOOKAHEAD) {
+      main_want.insert(main_want.end(), {OP_PANEL, OP_GATHER, OP_FORK, OP_SOLVE});
+      aux_want = {OP_PASS, OP_JOIN};
+      M.lookahead += 1;
+    } else {
+      main_want.push_back(OP_PANEL);
+      if (cp.due && pend_after > 0) main_want.push_back(OP_PASS);
+      M.serial += 1;
+    }
+    CHECK(on[ON_MAIN] == main_want && on[ON_AUX] == aux_want, "cadence %d of %d: order %d, %zu + %zu ops", c, rp.ncad, order, on[ON_MAIN].size(),
+          on[ON_AUX].size());
+    if (want >= 0) CHECK(order == (c + 1 < rp.ncad ? want : ORDER_SERIAL), "cadence %d of %d takes order %d, not %d", c, rp.ncad, order, want);
+    // agreement with plan_cadence_step, the counters and the statistics
+    CHECK((pass != nullptr) == (cp.due && pend_after > 0) && (order != ORDER_SERIAL) == cp.beside && (order == ORDER_CHAINED) == cp.chain_next, "flags");
+    CHECK(L.next_presolved == (order != ORDER_SERIAL) && (ahead != nullptr) == L.next_presolved, "next_presolved");
+    CHECK(r1.cad_serial == serial + 1 && r1.cpar == (r0.cpar ^ 1) && h.chain_run == before.chain_run, "serial and parity");
+    CHECK(r1.sigma == r0.sigma + (order == ORDER_CHAINED ? 1u : 0u), "sigma");
+    CHECK(r1.gather_count == r0.gather_count + (order == ORDER_CHAINED ? (unsigned)(h.batch * gw) : 0u), "gather_count");
+    CHECK(r1.aux_pass == M.mark_outstanding, "aux_pass %d, a mark outstanding %d", r1.aux_pass, M.mark_outstanding);
+    for (int q = 0; q < 2; ++q)
+      if (M.pre_piece[q] == M.piece) CHECK(r1.pre_serial[q] == M.pre_serial[q], "pre_serial[%d]", q);
+    CHECK(r1.cadences == r0.cadences + 1 && r1.cadence_traj_steps == r0.cadence_traj_steps + rp.steps_sum[c], "cadence statistics");
+    CHECK(r1.lookaheads == r0.lookaheads + (order != ORDER_SERIAL) && r1.chained == r0.chained + (order == ORDER_CHAINED), "look-ahead statistics");
+    CHECK(r1.w_from_v_passes == r0.w_from_v_passes + (order == ORDER_SERIAL && pass && cp.w_from_v), "w_from_v statistics");
+    if (order != ORDER_CHAINED) CHECK(M.aux_open == 0, "launches left on the second stream behind a cadence that is not chained");
+    if (!L.next_presolved) M.ahead_set = -1;
+    presolved = L.next_presolved;
+  }
+  CHECK(!presolved, "a solve enqueued ahead of a run's end");
+  if (h.run.aux_pass) {                                // ekf_stream_run's join_aux behind the last cadence
+    ++M.seq;
+    h.run.aux_pass = false, M.mark_outstanding = false, M.aux_open = 0;
+  }
+  CHECK(M.aux_open == 0 && !M.mark_outstanding, "launches outstanding on the second stream behind a run");
+  M.piece += 1;
+}
+
+static RunPlan run_of(const std::vector<int>& slots, int steps_each, int batch) {
+  RunPlan rp;
+  rp.ncad = (int)slots.size();
+  rp.slots_hi = slots;
+  rp.steps_hi.assign(slots.size(), steps_each);
+  rp.steps_sum.assign(slots.size(), (long)steps_each * batch);
+  return rp;
+}
+
+static void check_cadence_orders(std::mt19937& rng) {
+  OrderModel total;
+  // the random handles of check_launch_plans, runs of 1 .. 6 cadences, a second piece on the same state
+  for (int it = 0; it < 6000; ++it) {
+    HostPlan h = random_plan(rng);
+    h.sizes_dirty = false;                             // (cadences run on sizes read back, with nothing pending)
+    h.pending_k = h.pending_steps = 0;
+    h.opt_chain = rng() % 4 != 0;
+    h.opt_w_from_v = rng() % 4 != 0;
+    h.opt_panel_shape = rng() % 3 == 0 ? (int)(rng() % 4) : 0;
+    h.opt_panel_tform = rng() % 4 != 0;
+    h.opt_col_gather = rng() % 4 != 0;
+    if (rng() % 2) h.neff = h.neff_enq = h.n;          // (every index active: where a pass is long enough for a solve beside it)
+    const int n_hi = *std::max_element(h.n.begin(), h.n.end());
+    OrderModel M;
+    for (int piece = 0; piece < 2; ++piece) {
+      std::vector<int> slots(1 + rng() % 6);
+      for (int& s : slots) s = rng() % 5 == 0 ? 0 : rng() % 3 == 0 ? CAD_SLOTS : 1 + (int)(rng() % CAD_SLOTS);
+      walk_piece(h, run_of(slots, (int)(rng() % (CAD_SLOTS + 1)), h.batch), n_hi, M, -1);
+      h.pending_k = h.pending_steps = 0;               // (between two pieces what the last cadence left pending is applied)
+    }
+    total.chained += M.chained, total.lookahead += M.lookahead, total.serial += M.serial;
+  }
+  CHECK(total.chained > 0 && total.lookahead > 0, "the random draws walked %ld chained and %ld look-ahead transitions", total.chained, total.lookahead);
+  std::printf("cadence orders walked by the random draws alone: %ld chained, %ld look-ahead, %ld serial transitions\n", total.chained,
+              total.lookahead, total.serial);
+  // fixed cases: 256 CUs, every index active, nothing pending, runs of 1, 2 and 3 full cadences (the last one's pass is due: its
+  // slots are used up), two pieces each
+  struct Fixed { int batch, N, lookahead, chain, want; };
+  const Fixed fixed[] = {{1, 100, 1, 1, ORDER_CHAINED}, {2, 100, 1, 1, ORDER_CHAINED}, {40, 100, 1, 1, ORDER_CHAINED},
+                         {1, 1250, 1, 0, ORDER_LOOKAHEAD},
+                         {1, 100, 0, 1, ORDER_SERIAL},  {1, 100, 1, 0, ORDER_SERIAL}, {41, 100, 1, 1, ORDER_SERIAL}, {32, 2000, 1, 1, ORDER_SERIAL}};
+  for (const Fixed& f : fixed)
+    for (int ncad = 1; ncad <= 3; ++ncad) {
+      HostPlan h = bank(3 + 2 * f.N, std::vector<int>(f.batch, 3 + 2 * f.N));
+      h.cu_count = 256;
+      h.floor_host.assign(f.batch, 3);
+      h.opt_lookahead = f.lookahead, h.opt_chain = f.chain;
+      OrderModel M;
+      for (int piece = 0; piece < 2; ++piece) {
+        const RunPlan rp = run_of(std::vector<int>(ncad, CAD_SLOTS), 5, f.batch);
+        walk_piece(h, rp, h.n_max, M, f.want);
+        CHECK(h.pending_k == 0, "a run whose last cadence uses its slots up leaves %d ranks pending", h.pending_k);
+        if (f.batch == 32 && f.N == 2000) {
+          const CadStepPlan cp = plan_cadence_step(&h, rp, 0, h.n_max, false);
+          CHECK(cp.w_from_v && cp.panel == PANEL_FOUR && h.run.w_from_v_passes == (long)ncad * (piece + 1), "the headline bank's form");
+        }
+      }
+      total.chained += M.chained, total.lookahead += M.lookahead, total.serial += M.serial;
+    }
+  {                                                    // a cadence that observes nothing with nothing pending: the panel launch applies the noise
+    HostPlan h = bank(203, std::vector<int>(1, 203));
+    h.cu_count = 256;
+    h.floor_host.assign(1, 3);
+    OrderModel M;
+    walk_piece(h, run_of({0, CAD_SLOTS, 0, 7}, 5, 1), h.n_max, M, -1);
+    CHECK(h.pending_k == 14 && M.chained + M.lookahead + M.serial == 4, "a run with empty cadences");
+    total.chained += M.chained, total.lookahead += M.lookahead, total.serial += M.serial;
+  }
+  CHECK(total.chained > 0 && total.lookahead > 0 && total.serial > 0, "an order was never walked");
+  std::printf("cadence orders walked: %ld chained, %ld look-ahead, %ld serial transitions\n", total.chained, total.lookahead, total.serial);
+}
+
 static void check_step_records(std::mt19937& rng) {
   for (int it = 0; it < 3000; ++it) {
     HostPlan h;
@@ -708,6 +954,7 @@ int main() {
   check_shares(rng);
   check_planning(rng);
   check_launch_plans(rng);
+  check_cadence_orders(rng);
   check_step_records(rng);
   check_obs_planner(rng);
   check_det_records(rng);
