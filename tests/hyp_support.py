@@ -6,6 +6,7 @@ import numpy as np
 from oracle import ekf_oracle as orc
 from tests import resample_model as rm
 from tests import streams
+from tests.gpu_support import pbase
 
 SLAM_STEPS = 30
 
@@ -56,6 +57,28 @@ def sparse_handle(sd, B, N, slam_lms, seed):
     if B > 1:
         f.fork(0)
     return f
+
+
+def frozen_part(sd, f, b):
+    """What a localisation call or an adopt must leave alone, raw: every stored P(a, b) with a, b >= 3 -- also below the diagonal
+    and in the padding --, and the landmark means (tests/test_gpu_localize.py's)."""
+    raw = pbase(sd, f, b)
+    n_max = f.n_max
+    if n_max <= 4096:
+        ld = 64
+        while ld < n_max:
+            ld *= 2
+        rows = raw.reshape(-1, ld)[3:].copy()
+        rows[:, :3] = 0.0
+    else:
+        ld = (n_max + 63) // 64 * 64
+        rows = raw.reshape(-1, ld, 4096)[:, 3:].copy()
+        rows[0, :, :3] = 0.0
+    return rows, f.mean(b)[3:].copy()
+
+
+def frozen_same(a, b):
+    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 
 
 def assert_same_bits(bank, k, f, b, what):

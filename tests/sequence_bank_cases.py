@@ -20,7 +20,7 @@ every slot.  Case (a, b): A targets slot 0 and B slot 2 when a + b is even, else
 and second on both slots.  Each slot sees at most ONE operation, so slot 2 grows to at most 37 landmarks (join) and the largest
 state changes hands inside the table: join on slot 0 gives 69 where remove_landmarks on slot 2 gives 67, copy_from gives 27.
 
-OPERATIONS: the 18 functions of sequence_cases.OPS verbatim, plus two that B = 1 cannot hold:
+OPERATIONS: the 21 functions of sequence_cases.OPS verbatim, plus two that B = 1 cannot hold:
 
     fork          the target becomes a twin of slot 1 (EkfSlam.fork: copy_from inside one handle);
     join(slot)    the target appends slot 1's map (EkfSlam.join with `other` the handle itself): slot 1 is only read, with ranks
@@ -30,8 +30,9 @@ OPERATIONS: the 18 functions of sequence_cases.OPS verbatim, plus two that B = 1
                   38, n = 79 = n_max exactly), one step of the whole bank that sees landmark 0 and `tail_mid` in every slot (the
                   removal flushed: this makes ranks pending again, in slot 1 too), then the join.
 
-BANK-WIDE CALLS.  step, run_stream, step_detections, the three localisation calls (and the active_bound option) take the whole
-bank.  The operation's own inputs go to the TARGET; every other slot gets an IDLE input: the same increments, and observations
+BANK-WIDE CALLS.  step, run_stream, step_detections, the three localisation calls, localize_detections (and the active_bound
+option) take the whole bank; the two hypothesis operations make their bank on the TARGET slot and adopt into it: targeted calls,
+held to the bystander rule.  The operation's own inputs go to the TARGET; every other slot gets an IDLE input: the same increments, and observations
 of landmark 0 and `tail_mid` of its own map, consistent with its own model mean -- informed landmarks far below its bound, so
 that an idle slot's own call never raises a bound that A should have raised.  BankDriver makes this expansion ONCE, from the
 float64 model's state, and hands every sink (the model, the model in longdouble, the filter) the same float64 arguments.
@@ -187,6 +188,12 @@ class BankDriver:
     def run_localize_stream(self, lin, ang, idx, zr, zb):
         self.send("bank_localize_stream", False, *self.bank_of_stream(lin, ang, idx, zr, zb))
 
+    def localize_detections(self, lin, ang, win, unmatched):
+        """(an idle window holds tags of the slot's own table only: nothing of it may come back unmatched)"""
+        n = len(self.model.t)
+        self.send("bank_localize_detections", False, [lin] * n, [ang] * n, self.per_slot(win, self.idle_window),
+                  self.per_slot(list(unmatched), lambda tr: []))
+
 
 # ---- the two operations only a bank can hold -----------------------------------------------------------------------------------
 def op_fork(drv, rng):
@@ -203,10 +210,13 @@ def op_join_slot(drv, rng):
     drv.join_slot(BYSTANDER)
 
 
-OPS = sc.OPS + (("fork", op_fork), ("join(slot)", op_join_slot))
+# (fork and join(slot) keep the indices 18 and 19 they had: the 400 older cases keep their slots, ids and draws; the three
+# operations sequence_cases gained since follow them)
+SHARED_BEFORE = 18
+OPS = sc.OPS[:SHARED_BEFORE] + (("fork", op_fork), ("join(slot)", op_join_slot)) + sc.OPS[SHARED_BEFORE:]
 PAIRS = [(a, b) for a in range(len(OPS)) for b in range(len(OPS))]
 TARGETED = ("set_state_diag", "set_tag_index", "predict_linear", "predict_dense1", "update_direct", "update_linear", "transform",
-            "join", "join_slot", "fork", "remove_landmarks", "add_landmarks", "copy_in")
+            "join", "join_slot", "fork", "remove_landmarks", "add_landmarks", "copy_in", "hyp_adopt", "hyp_resample_adopt")
 
 
 def pair_name(a, b):

@@ -5,7 +5,8 @@ csrc/ekf_api.hip (size, the active bound and its mirrors, pending ranks and pose
 copy / join / transform), and a mirror left stale by one call shows only in the NEXT call that trusts it.  So: a start with ranks
 pending, operation A, operation B, then a continuation (a step and a stream) whose covariance pass reads whatever A and B left
 -- judged after each of the three against ONE dense model of the whole sequence (tests/sequence_model.py), block by block
-(parity_blocks.assert_state_close).  18 operations, 324 pairs, each with a name (225 until localisation joined the table).
+(parity_blocks.assert_state_close).  21 operations, 441 pairs, each with a name (225 until localisation joined the table, 324
+until localisation from detections and the hypothesis bank did).
 
 START: direct_model.small_stream at N = 30 -- synthetic_stream(26, 31, 4, seed) over landmarks 0 .. 25, landmarks 26 .. 29 never
 observed at landmark_init_var: n = 63, one column short of the 64-column tile edge of the general kernels, so that growth
@@ -26,9 +27,11 @@ import functools
 import numpy as np
 
 from oracle import ekf_oracle as orc
+from slam_duckietown_amd import frontend
 from tests import direct_model as dm
 from tests import fuzz_model as fz
 from tests import linear_model as lm
+from tests import localize_model as lcm
 from tests import motion_model as mm
 from tests import parity_blocks as pb
 from tests import sequence_model as sm
@@ -112,7 +115,7 @@ def stream(drv, rng, steps, m):
     drv.run_stream(*st)
 
 
-# ---- the 18 operations --------------------------------------------------------------------------------------------------------
+# ---- the 21 operations --------------------------------------------------------------------------------------------------------
 def op_step(drv, rng):
     tr = drv.model.tr
     _, never, last = pick(tr)
@@ -258,14 +261,137 @@ def op_run_localize(drv, rng):
     drv.run_localize_stream(lin, ang, idx, zr, zb)
 
 
-# (the three localisation operations are APPENDED: the 225 pairs before them keep their ids and their draws)
+# ---- localisation from raw detections ------------------------------------------------------------------------------------------
+# ekf_localize_detections raises its bound ON THE DEVICE, from whatever the window matched, and the host follows through the
+# `sizes_dirty` read-back.  Two windows, as the localisation operations above have two parts: window one shows the tags of `a` and
+# the tail's `mid` and one tag the table does not hold (it must come back unmatched and add nothing); window two the tags of
+# landmark 0 and of a loose landmark.  The operation asserts ON THE MODEL that each window matches exactly what it intends.
+GATE = 1.39             # fz.window_of leaves a known tag out beyond 1.4 m from the pose; the device's gate is 1.5 m
+
+
+def pose_distance(tr, j):
+    return float(np.hypot(*(tr.mean[3 + 2 * j:5 + 2 * j] - tr.mean[:2])))
+
+
+def tags_in_gate(tr):
+    """The landmarks whose tag a camera at the model's pose has in front of the gate."""
+    tagged = set(tr.tags.values())
+    return [j for j in range(tr.n_lm) if j in tagged and pose_distance(tr, j) < GATE]
+
+
+def informed_in_gate(tr):
+    """(`a`, the tail's `mid`) for window one.  The start's landmark 12 lies 1.3 m from the pose: where a call has moved the
+    pose away from it (a split does, by decimetres) the highest informed landmark BELOW it that is in range stands in -- its
+    bound is lower still --, and likewise the lowest one in range for `a`."""
+    informed = set(int(l) for l in pb.loose_landmarks(tr.cov, INIT_VAR)[1])
+    near = [j for j in tags_in_gate(tr) if j in informed and j <= tail_mid(tr)]
+    assert len(near) >= 2, near
+    return near[0], near[-1]
+
+
+def loose_in_gate(tr):
+    """The landmark window two names beside landmark 0: `pick`'s loose landmark where it carries a tag in front of the gate;
+    else the tagged loose landmark nearest to the pose; where no tagged loose landmark is in range (behind copy_from), the
+    highest-indexed tagged landmark in range."""
+    near = tags_in_gate(tr)
+    never = pick(tr)[1]
+    if never in near:
+        return never
+    loose = [j for j in near if j in pb.loose_landmarks(tr.cov, INIT_VAR)[0]]
+    return min(loose, key=lambda j: pose_distance(tr, j)) if loose else max(near)
+
+
+def detection_window(drv, rng, lms, unknown=()):
+    """A two-frame window of the tags of landmarks `lms` and the ids `unknown`, and the assertion that the model's association
+    matches exactly `lms` and reports exactly `unknown`.  -> (window, unmatched ids)."""
+    tr = drv.model.tr
+    tag_of = {j: t for t, j in tr.tags.items()}
+    ids = [tag_of[j] for j in dict.fromkeys(lms)] + list(unknown)
+    win = fz.window_of(rng, tr, ids, {t: (0.2, 0.8) for t in unknown}, 2)
+    tags, unmatched = frontend.associate_known(win, tr.tags, tr.mean[:3], tr.cfg.gate_range, tr.cfg.ignore_tags,
+                                               n_landmarks=tr.n_lm)
+    assert sorted(tags) == sorted(set(lms)) and unmatched == list(unknown), (sorted(tags), lms, unmatched)
+    assert all(t[4] < tr.cfg.gate_range - 0.05 for t in tags.values())             # (well inside the gate: no decision near it)
+    return win, unmatched
+
+
+def op_localize_detections(drv, rng):
+    tr = drv.model.tr
+    new = next(i for i in range(600, 1024) if i not in tr.tags)
+    drv.localize_detections(0.004, 0.02, *detection_window(drv, rng, informed_in_gate(tr), [new]))
+    tr = drv.model.tr
+    low = 0 if 0 in tags_in_gate(tr) else informed_in_gate(tr)[0]
+    drv.localize_detections(0.004, 0.005, *detection_window(drv, rng, [low, loose_in_gate(tr)]))
+
+
+# ---- a hypothesis bank made behind A, stepped, and adopted back -----------------------------------------------------------------
+# ekf_hyp_create takes the slot's bound from the host mirror after flush_pending, k_hyp_rows updates only below it, and
+# ekf_hyp_adopt writes the bound's mirrors itself: the only way a pose part written OUTSIDE the handle comes back into it.  Three
+# hypotheses on the target's map as A left it; step one shares the part-one observations (`a` and the tail's `mid`), step two
+# names the loose landmark; then one hypothesis is adopted and the bank closed.  The model is two localize1 calls.
+HYP_COUNT = 3
+HYP_MOTION = ((0.004, 0.02), (0.004, 0.005))
+HYP_OFF = (0.5, 1.0)                                                # the reset hypothesis: half a metre and one radian off
+HYP_COV = np.diag([0.03 ** 2, 0.03 ** 2, 0.015 ** 2])               # the reset hypothesis' pose block
+RESAMPLE_U, SPLIT = 0.5, 0.3
+PLAN_MARGIN = 1e-6
+
+
+def hyp_parts(drv, rng):
+    """((idx, zr, zb) of part one, (idx, zr, zb) of part two), both as the model's mean sees them now."""
+    tr = drv.model.tr
+    a, never, _ = pick(tr)
+    return tuple((idx,) + tuple(localize_obs(drv, rng, idx)) for idx in ([a, tail_mid(tr)], [0, never]))
+
+
+def reset_offset(tr, one):
+    """Half a metre and one radian off the model's pose, in the direction (of eight) and the sense (of two) in which the
+    part-one observations weigh the reset hypothesis LEAST against one that stays.  The table's meas_sigma is 0.7 (metres and
+    radians): two observations seen a radian off cost a hypothesis one to three units of log-likelihood, no more, and in an
+    unlucky direction the bearing the half metre adds cancels the radian.  The plan needs its weight below 1 / 6 of the sum."""
+    stay, log = (tr.mean, tr.cov), []
+    lcm.literal_step(*stay, *HYP_MOTION[0], *one, tr.cfg, log=log)
+    ll, offs = {}, {}
+    for k in range(8):
+        for sense in (1.0, -1.0):
+            offs[k, sense] = np.array([HYP_OFF[0] * np.cos(k * np.pi / 4), HYP_OFF[0] * np.sin(k * np.pi / 4), sense * HYP_OFF[1]])
+            mean, cov, log0 = tr.mean.copy(), tr.cov.copy(), []
+            mean[:3] = mean[:3] + offs[k, sense]
+            cov[:3, :], cov[:, :3] = 0.0, 0.0
+            cov[:3, :3] = HYP_COV
+            lcm.literal_step(mean, cov, *HYP_MOTION[0], *one, tr.cfg, log=log0)
+            ll[k, sense] = sm.loglik(log0)
+    return offs[min(ll, key=ll.get)]
+
+
+def op_hyp_adopt(drv, rng):
+    """Step two gives one list per hypothesis: hypothesis 1, the one adopted, the part-two observations; 0 and 2 two informed
+    landmarks each, all four distinct, so that a list handed to the wrong hypothesis shows."""
+    one, two = hyp_parts(drv, rng)
+    informed = [int(l) for l in pb.loose_landmarks(drv.model.tr.cov, INIT_VAR)[1] if l not in two[0]]
+    lists = [(idx,) + tuple(localize_obs(drv, rng, idx)) for idx in (informed[2:4], informed[4:6])]
+    drv.hyp_adopt(HYP_MOTION, one, [lists[0], two, lists[1]], 1)
+
+
+def op_hyp_resample_adopt(drv, rng):
+    """Hypothesis 0 is reset half a metre and one radian off before step one: its rows are zero and its own bound is 3, where
+    hypotheses 1 and 2 carry the slot's.  resample(u = 0.5, split = 0.3) leaves it no offspring, slot 0 takes hypothesis 1's
+    bound, rows and record (k_hyp_copy) and is split (k_hyp_split); step two names the loose landmark, and slot 0 is adopted."""
+    one, two = hyp_parts(drv, rng)
+    pose0 = drv.model.tr.mean[:3] + reset_offset(drv.model.tr, one)
+    drv.hyp_resample_adopt(HYP_MOTION, one, two, pose0, HYP_COV, RESAMPLE_U, SPLIT, rng.standard_normal((HYP_COUNT, 3)))
+
+
+# (the localisation operations are APPENDED, three and then three more: the pairs before them keep their ids and their draws)
 OPS = (("step", op_step), ("run_stream", op_run_stream), ("step_detections", op_step_detections),
        ("predict_linear", op_predict_linear), ("predict_dense", op_predict_dense), ("update_direct", op_update_direct),
        ("update_linear", op_update_linear), ("transform", op_transform), ("transform(cov)", op_transform_cov),
        ("join", op_join), ("join(explicit)", op_join_explicit), ("remove_landmarks", op_remove),
        ("add_landmarks", op_add), ("copy_from", op_copy), ("active_bound off/on", op_bound_off),
-       ("localize", op_localize), ("localize_update", op_localize_update), ("run_localize", op_run_localize))
-LOCALIZE_OPS = ("localize", "localize_update", "run_localize")
+       ("localize", op_localize), ("localize_update", op_localize_update), ("run_localize", op_run_localize),
+       ("localize_detections", op_localize_detections), ("hyp_adopt", op_hyp_adopt),
+       ("hyp_resample_adopt", op_hyp_resample_adopt))
+LOCALIZE_OPS = ("localize", "localize_update", "run_localize", "localize_detections", "hyp_adopt", "hyp_resample_adopt")
 PAIRS = [(a, b) for a in range(len(OPS)) for b in range(len(OPS))]
 
 

@@ -4,6 +4,7 @@ import ctypes as C
 import numpy as np
 
 from tests import gpu_support as gs
+from tests import hyp_support as hs
 from tests import sequence_cases as sc
 
 
@@ -18,6 +19,52 @@ def source_handles(sd):
         assert np.array_equal(got[0], mean) and np.array_equal(np.triu(got[1]), np.triu(cov))
         src[key] = h
     return src
+
+
+def localize_window(f, lin, ang, wins, unmatched):
+    """EkfSlam.localize_detections on a device-side window per slot: afterwards every slot's unmatched ids are exactly
+    `unmatched[b]`, and its tag table and size what they were (nothing is added on a frozen map)."""
+    before = [(f.tag_index(b), f.size(b)) for b in range(f.batch)]
+    f.localize_detections(lin, ang, wins)
+    assert f.assoc_fallbacks() == 0                        # a device-side window
+    for b in range(f.batch):
+        got = f.unmatched_tags(b)
+        assert got == [int(t) for t in unmatched[b]], f"slot {b}: unmatched tags {got}, the window's unknown ids are {unmatched[b]}"
+        assert (f.tag_index(b), f.size(b)) == before[b], f"slot {b}: localize_detections changed the tag table or the size"
+
+
+def hyp_bank_adopt(sd, f, b, k, drive):
+    """A bank of sequence_cases.HYP_COUNT hypotheses on slot b's map as it stands, driven by `drive(bank)`, hypothesis k adopted
+    into the slot and the bank closed.  Raw and bit for bit: the adoption left the slot's frozen part alone, and the slot's pose
+    mean, block and rows are the hypothesis's."""
+    with f.hypotheses(sc.HYP_COUNT, b=b) as bank:
+        drive(bank)
+        f.covariance_block(0, 0, 3, f.size(b), b)          # (a download mirrors the stored triangle: before the snapshot)
+        frozen = hs.frozen_part(sd, f, b)
+        bank.adopt(k, f, b)
+        assert hs.frozen_same(hs.frozen_part(sd, f, b), frozen), f"slot {b}: adopt moved the slot's map"
+        hs.assert_same_bits(bank, k, f, b, f"slot {b} behind adopt({k})")
+
+
+def hyp_two_steps(motion, one, lists):
+    def drive(bank):
+        bank.step(*motion[0], *_obs(one))
+        bank.step(*motion[1], *(list(x) for x in zip(*(_obs(o) for o in lists))))
+    return drive
+
+
+def hyp_resampled(motion, one, two, pose0, cov0, u, s, z):
+    def drive(bank):
+        bank.reset(pose0, cov0, k=0)
+        bank.step(*motion[0], *_obs(one))
+        r = bank.resample(u=u, split=s, z=z)
+        assert r.ancestors[0] != 0 and r.offspring[0] == 0 and r.offspring[r.ancestors[0]] >= 2, (r.ancestors, r.offspring)
+        bank.step(*motion[1], *_obs(two))
+    return drive
+
+
+def _obs(o):
+    return [int(i) for i in o[0]], [float(x) for x in o[1]], [float(x) for x in o[2]]
 
 
 class Device:
@@ -101,6 +148,15 @@ class Device:
     def run_localize_stream(self, lin, ang, idx, zr, zb):
         self.f.stream_upload(lin, ang, idx, zr, zb)
         self.f.run_localize(0, len(lin))
+
+    def localize_detections(self, lin, ang, win, unmatched):
+        localize_window(self.f, lin, ang, [win], [unmatched])
+
+    def hyp_adopt(self, motion, one, lists, k):
+        hyp_bank_adopt(self.sd, self.f, 0, k, hyp_two_steps(motion, one, lists))
+
+    def hyp_resample_adopt(self, motion, one, two, *rest):
+        hyp_bank_adopt(self.sd, self.f, 0, 0, hyp_resampled(motion, one, two, *rest))
 
 
 class BankDevice:
@@ -198,6 +254,12 @@ class BankDevice:
     def copy_in(self, key):
         self.f.copy_from(self.src[key], 0, self.target)
 
+    def hyp_adopt(self, motion, one, lists, k):
+        hyp_bank_adopt(self.sd, self.f, self.target, k, hyp_two_steps(motion, one, lists))
+
+    def hyp_resample_adopt(self, motion, one, two, *rest):
+        hyp_bank_adopt(self.sd, self.f, self.target, 0, hyp_resampled(motion, one, two, *rest))
+
     # -- the calls that take the whole bank --------------------------------------------------------------------------------------
     def bank_step(self, lin, ang, obs):
         self.f.step(lin, ang, *self._lists(obs))
@@ -218,6 +280,9 @@ class BankDevice:
     def bank_localize_stream(self, lin, ang, idx, zr, zb, m):
         self.f.stream_upload(lin, ang, idx, zr, zb, m)
         self.f.run_localize(0, len(lin))
+
+    def bank_localize_detections(self, lin, ang, wins, unmatched):
+        localize_window(self.f, lin, ang, wins, unmatched)
 
     @staticmethod
     def _lists(obs):

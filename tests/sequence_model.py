@@ -8,6 +8,10 @@ newer calls, each DELEGATED to the model the project already trusts -- no new ma
     predict_linear   motion_model.predict_linear              transform        transform_model.transform_dense
     join             join_model.join_dense (both modes)       set_state / set_state_diag, set_option: bookkeeping only
     localize1, localize_update1, run_localize_stream          localize_model.literal_step (the trajectory's own cfg)
+    localize_detections                                       loc_det_world.model_window (frontend.associate_known, then
+                                                              literal_step: Bank.window's arrangement for step_detections)
+    hyp_adopt, hyp_resample_adopt                             literal_step per hypothesis; resample_model.plan / margin on the
+                                                              model's own log-likelihoods, resample_model.split_dense
 
 The methods carry EkfSlam's names and take ONE trajectory's arguments (b = 0), so that a sequence written once runs on the model
 and on a filter (tests/sequence_cases.py's Driver).  The other handles a call reads (`join`, `copy_from`) are named by a key of
@@ -29,6 +33,7 @@ models' code objects are re-bound to a namespace in which `np` is a proxy whose 
 (`dtype=float` included) and whose `linalg.solve` / `linalg.inv` are a pivoted elimination in `dtype` (LAPACK has no extended
 precision; the systems are at most 7 x 7).  Nothing of the models is restated.  Inputs -- measurements, noise constants,
 Jacobians handed in -- are the same float64 values in both precisions; only the arithmetic differs."""
+import dataclasses
 import sys
 import types
 
@@ -37,8 +42,10 @@ import numpy as np
 from tests import direct_model as dm
 from tests import join_model as jm
 from tests import linear_model as lm
+from tests import loc_det_world as ldw
 from tests import localize_model as lcm
 from tests import motion_model as mm
+from tests import resample_model as rsm
 from tests import transform_model as tm
 from tests.fork_model import ForkBank
 from tests.fuzz_model import Traj
@@ -162,6 +169,43 @@ class SeqBank(ForkBank):
         for k in range(len(lin)):
             self.localize1(lin[k], ang[k], idx[k], zr[k], zb[k])
 
+    # -- localisation from raw detections: what the window matches, then one localisation step ---------------------------------
+    def localize_detections(self, lin, ang, win, unmatched):
+        self._localize_window(self.tr, lin, ang, win, unmatched)
+
+    def _localize_window(self, tr, lin, ang, win, unmatched):
+        (tr.mean, tr.cov), tags, un = ldw.model_window(tr.mean, tr.cov, tr.tags, win, lin, ang, cfg=tr.cfg)
+        assert list(un) == list(unmatched), (un, unmatched)
+        tr.seen[np.asarray(list(tags), dtype=int)] = True
+
+    # -- a hypothesis bank on the target's map, stepped twice, one hypothesis adopted -------------------------------------------
+    def hyp_adopt(self, motion, one, lists, k):
+        """Step one with the shared list `one`, step two with one list per hypothesis: the slot ends as hypothesis k does."""
+        self.localize1(*motion[0], *one)
+        self.localize1(*motion[1], *lists[k])
+
+    def hyp_resample_adopt(self, motion, one, two, pose0, cov0, u, s, z):
+        """Hypothesis 0 reset to (pose0, cov0), step one for all three, the resampling plan from the model's own log-likelihoods
+        (resample_model.plan; its margin keeps the plan from depending on rounding), the split, step two, slot 0 adopted."""
+        tr = self.tr
+        mean, cov = self._hyp_resampled(motion[0], one, pose0, cov0, u, s, z)
+        tr.mean, tr.cov = lcm.literal_step(mean, cov, *motion[1], *two, tr.cfg)
+        tr.seen[np.asarray(list(one[0]) + list(two[0]), dtype=int)] = True
+
+    def _hyp_resampled(self, motion, one, pose0, cov0, u, s, z):
+        """Slot 0 of the bank behind step one and the resampling: its ancestor's state, split."""
+        tr = self.tr
+        states, ll = [_reset(tr.mean, tr.cov, pose0, cov0), (tr.mean, tr.cov), (tr.mean, tr.cov)], np.zeros(3)
+        for h in range(3):
+            log = []
+            states[h] = lcm.literal_step(*states[h], *motion, *one, tr.cfg, log=log)
+            ll[h] = loglik(log)
+        flags = np.zeros(3, dtype=np.uint32)
+        anc, off, W = rsm.plan(ll, flags, u)
+        assert anc[0] != 0 and off[0] == 0 and off[anc[0]] >= 2, (anc, off, ll)
+        assert rsm.margin(ll, flags, u) >= 1e-6, (rsm.margin(ll, flags, u), ll)
+        return rsm.split_dense(*states[anc[0]], s, np.asarray(z)[0])
+
     # -- the calls that take the whole bank: one entry per slot --------------------------------------------------------------
     def bank_step(self, lin, ang, obs):
         """step: lin, ang [B]; obs per slot (idx, zr, zb)."""
@@ -185,11 +229,30 @@ class SeqBank(ForkBank):
             self.bank_localize(lin[k], ang[k], [(idx[k][b][:m[k][b]], zr[k][b][:m[k][b]], zb[k][b][:m[k][b]])
                                                 for b in range(len(self.t))])
 
+    def bank_localize_detections(self, lin, ang, wins, unmatched):
+        for b, tr in enumerate(self.t):
+            self._localize_window(tr, lin[b], ang[b], wins[b], unmatched[b])
+
+
+def _reset(mean, cov, pose, block):
+    """reset_pose on a dense state (hypotheses_model.reset_state): the pose and its block replaced, the cross terms dropped."""
+    mean, cov = np.array(mean), np.array(cov)
+    mean[:3] = pose
+    cov[:3, :], cov[:, :3] = 0.0, 0.0
+    cov[:3, :3] = block
+    return mean, cov
+
+
+def loglik(log):
+    """The sum a hypothesis accumulates, from literal_step's records (hypotheses_model.loglik_of; det S of a 2 x 2 written out:
+    LAPACK has no extended precision)."""
+    return sum(-0.5 * (nis + np.log(S[0, 0] * S[1, 1] - S[0, 1] * S[1, 0]) + 2.0 * np.log(2.0 * np.pi)) for _, _, S, nis, _ in log)
+
 
 # ---- the same code in another precision --------------------------------------------------------------------------------------
 _REBOUND = ("oracle.ekf_oracle", "tests.gated_oracle","tests.fuzz_model", "tests.fork_model", "tests.direct_model",
             "tests.linear_model", "tests.localize_model", "tests.motion_model", "tests.transform_model", "tests.join_model",
-            __name__)
+            "tests.loc_det_world", "tests.resample_model", __name__)
 _CLASSES = ("Traj", "Bank", "ForkBank", "SeqBank")
 
 
@@ -273,7 +336,7 @@ def _rebind(name, npx, memo):
             g[key] = _rebind(v.__name__, npx, memo)
         elif isinstance(v, types.FunctionType) and v.__module__ in _REBOUND:
             g[key] = fn(v) if v.__module__ == name else getattr(_rebind(v.__module__, npx, memo), v.__name__)
-        elif isinstance(v, type) and v.__name__ in _CLASSES and v.__module__ in _REBOUND:
+        elif isinstance(v, type) and v.__name__ in _CLASSES and v.__module__ in _REBOUND and not dataclasses.is_dataclass(v):
             if v.__module__ != name:
                 g[key] = getattr(_rebind(v.__module__, npx, memo), v.__name__)
                 continue

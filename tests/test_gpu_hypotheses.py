@@ -21,6 +21,7 @@ from tests import localize_model as lm
 from tests import streams
 from tests.conftest import path_ran
 from tests.gpu_support import pbase, sd  # noqa: F401
+from tests.hyp_support import assert_same_bits, frozen_part, frozen_same
 from tests.parity_blocks import assert_state_close, fmt_state
 
 pytestmark = pytest.mark.gpu
@@ -45,42 +46,10 @@ def observe(mean, lms, rng, noise=0.01):
     return lms.astype(np.int32), zr, zb
 
 
-def frozen_part(sd, f, b):
-    """What a localisation call or an adopt must leave alone, raw: every stored P(a, b) with a, b >= 3 -- also below the diagonal
-    and in the padding --, and the landmark means (tests/test_gpu_localize.py's)."""
-    raw = pbase(sd, f, b)
-    n_max = f.n_max
-    if n_max <= 4096:
-        ld = 64
-        while ld < n_max:
-            ld *= 2
-        rows = raw.reshape(-1, ld)[3:].copy()
-        rows[:, :3] = 0.0
-    else:
-        ld = (n_max + 63) // 64 * 64
-        rows = raw.reshape(-1, ld, 4096)[:, 3:].copy()
-        rows[0, :, :3] = 0.0
-    return rows, f.mean(b)[3:].copy()
-
-
-def frozen_same(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
-
-
 def slot_pose_part(f, b):
     """(pose mean, P[0:3, :]) of trajectory b; the pose block comes mirrored from its stored upper triangle."""
     n = f.size(b)
     return f.mean(b)[:3].copy(), f.covariance_block(0, 0, 3, n, b)
-
-
-def assert_same_bits(bank, k, f, b, what):
-    pose, rows = slot_pose_part(f, b)
-    hp, hc = bank.poses()
-    hr = bank.rows(k)
-    assert np.isfinite(hp[k]).all() and np.isfinite(hr).all(), f"{what}: NaN"
-    assert np.array_equal(hp[k], pose), f"{what}: pose mean {hp[k]} where the slot has {pose}"
-    assert np.array_equal(hc[k], rows[:, :3]), f"{what}: pose block"
-    assert np.array_equal(hr, rows), f"{what}: pose rows differ in {int((hr != rows).sum())} entries"
 
 
 def mapped_bank(sd, B, N=20, seed=11):

@@ -1,5 +1,5 @@
 """GPU: every read-only query behind every state-changing call (tests/sequence_cases.py: run_query_case; the model is
-tests/sequence_model.py's, tests/test_queries_after_calls_cpu.py shows that the 18 cases are admissible and the judge not blind).
+tests/sequence_model.py's, tests/test_queries_after_calls_cpu.py shows that the 21 cases are admissible and the judge not blind).
 
 marginals(), joint() and associate() read the filter "as the covariance pass would leave it" through the mirrors the
 state-changing calls maintain: the size word, the mean's current buffer, the pending pose noise, the padded rank count and the
@@ -18,8 +18,8 @@ left, so a query behind them is right only if A's bound reached it.  After A and
 Then, after the tail only: state() -- it flushes -- against the model; the pending-time joint() and marginals() within 1e-11 of
 the download (the project's bound for pending ranks summed in another order); the same queries with nothing pending equal to the
 download bit for bit; factor() against the downloaded covariance.  On the general kernels ranks must be pending behind the tail
-in every case, and behind A at least for predict_linear and step -- and NOT behind a localisation call, which applies what is
-pending at entry and appends no rank; the small-state path never has any, and its queries before and
+in every case, and behind A at least for predict_linear and step -- and NOT behind a localisation call (localize_detections and the two
+hypothesis-bank operations included), which applies what is pending at entry and appends no rank; the small-state path never has any, and its queries before and
 after the download agree bit for bit.
 
 Handles are made once per path and reset per case; a failed assertion drops them, a refused or failed call ends the module."""
@@ -185,9 +185,9 @@ def test_queries_after(sd, both_paths, a):
 
 
 def test_the_module_kept_its_promises():
-    """Every operation ran on both paths; on the general kernels ranks were pending behind the tail in all 18 cases and behind
+    """Every operation ran on both paths; on the general kernels ranks were pending behind the tail in all 21 cases and behind
     A for predict_linear and step, and nothing behind a localisation A; the bound A left lies above the bound before A and above
-    the tail's own for the nine operations that must raise it; no observation excused, no entry left out.  Prints the worst of
+    the tail's own for the twelve operations that must raise it; no observation excused, no entry left out.  Prints the worst of
     every piece per operation and stage, and the pending-time queries' distance from the download (profiles/queries_after_calls.txt)."""
     for (path, a, stage), w in sorted(RECORD["worst"].items()):
         print(f"DEVICE {path:15s} {sc.query_name(a):20s} {stage:5s} {pb.fmt_state(w)} | marginals "

@@ -1,6 +1,6 @@
 """GPU: the ordered pairs of state-changing calls in an UNEVEN BANK, call A on one slot and call B on another, against ONE dense
 model of the bank (tests/sequence_bank_cases.py has the table and the reasons, tests/sequence_model.py the model,
-tests/test_sequence_bank_cpu.py shows that the 400 cases are admissible and the judge not blind).
+tests/test_sequence_bank_cpu.py shows that the 529 cases are admissible and the judge not blind).
 
 Per case: three slots of 63, 47 and 71 states in ONE handle, the prelude for the whole bank (on the general kernels ranks are
 pending in every slot), operation A on slot 0 or 2, operation B on the other, then a continuation over the whole bank.
@@ -9,16 +9,18 @@ After A and after B there is NO download: every slot's whole state is read throu
 landmarks and judged by parity_blocks.assert_state_close against its model slot -- TOL, ENTRY_TOL, exact symmetry, exact zeros,
 size, tag index, flags -- so B starts on whatever A left pending in every slot.  After the continuation state(b) of every slot,
 under the same judge; on the general kernels a pass kernel has run and the stored P_base[0, 0] of every slot is the downloaded
-one.  Behind a localisation operation nothing is pending in any slot.
+one.  Behind a localisation operation -- localize_detections and the two hypothesis-bank operations among the six -- nothing is
+pending in any slot.
 
-Around every TARGETED call, every slot the call does not name is held to the bystander rule (sequence_bank_cases.
+Around every TARGETED call -- hyp_adopt and hyp_resample_adopt are two: the bank is made on the target slot and adopted into
+it --, every slot the call does not name is held to the bystander rule (sequence_bank_cases.
 assert_bystander): mean bit for bit, covariance within PATH_TOL of the read before the call, and the stored P_base untouched
 where nothing was pending.  Behind fork the target's stored triangle and mean are slot 1's over slot 1's size, bit for bit.
 
 Two more cases (run_edge_case) raise slot 2's bound over the 64-column tile edge behind a linear / direct update, where every
-slot's bound lay below it: the one thing the 400 pairs cannot show of front_run's per-slot mirror (profiles/sequence_bank.txt).
+slot's bound lay below it: the one thing the pairs cannot show of front_run's per-slot mirror (profiles/sequence_bank.txt).
 
-Time on one MI355X: 14 s for the 805 tests, 0.043 s for the slowest case.
+Time on one MI355X: 21 s for the 1063 tests, 0.064 s for the slowest case (14 s for 805 before the last three operations).
 
 The handles are made once per path and every case resets them; a failed assertion drops them, any other exception ends the
 session: nothing more is started on a device after a refused or failed call."""
@@ -159,10 +161,11 @@ def test_a_front_raises_one_slots_bound_over_the_tile_edge(sd, both_paths, i):
 
 
 def test_the_module_kept_its_promises():
-    """All 400 pairs ran on both paths; every operation ran in both positions on both acting slots; the largest state changed
+    """All 529 pairs ran on both paths; each of the 23 operations ran in both positions on both acting slots; the largest state changed
     slots in some case; on the general kernels some case had ranks pending in the slots B does not name when B ran; the
     bystander's P_base comparison was exercised (nothing pending at a targeted call) on both paths, and so was the bound for
-    pending ranks on the general kernels; nothing was pending, in any slot, behind a localisation operation.  Prints the worst
+    pending ranks on the general kernels; nothing was pending, in any slot, behind any of the six localisation-like
+    operations.  Prints the worst
     of every piece per operation, position and slot, and the time (profiles/sequence_bank.txt)."""
     for (path, op, pos, s), w in sorted(RECORD["worst"].items()):
         print(f"DEVICE {path:15s} {bc.OPS[op][0]:20s} {pos} slot {s} {pb.fmt_state(w)}")

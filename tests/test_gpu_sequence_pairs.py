@@ -1,5 +1,5 @@
 """GPU: every ordered pair of state-changing calls against ONE dense model (tests/sequence_cases.py has the table and the
-reasons, tests/sequence_model.py the model, tests/test_sequence_cpu.py shows that the 324 cases are admissible and the judge
+reasons, tests/sequence_model.py the model, tests/test_sequence_cpu.py shows that the 441 cases are admissible and the judge
 not blind).
 
 Per case: the block-diagonal start, 28 stream steps and three single steps (on the general kernels ranks are pending),
@@ -8,8 +8,12 @@ continuation with parity_blocks.assert_state_close: the informed part piece by p
 own scale, exact zeros, exact symmetry, size, tag index, flags.  A stale bound, floor or size word left by A shows in B or in
 the continuation's pass; the failure carries the pair's name.
 
-Localisation (the last three operations) applies what is pending at entry and appends no rank: on the general kernels the
-stored P_base[0, 0] read BEFORE the download behind such an A or B is the downloaded P[0, 0], bit for bit.
+Localisation (the last six operations: localize, localize_update, run_localize, localize_detections and the two that make a
+hypothesis bank on the map as it stands and adopt one hypothesis back, hyp_adopt and hyp_resample_adopt) applies what is pending
+at entry and appends no rank: on the general kernels the stored P_base[0, 0] read BEFORE the download behind such an A or B is
+the downloaded P[0, 0], bit for bit.  The filter's side of those three asserts more than the state (tests/sequence_device.py):
+the unmatched ids, the tag table and the size around localize_detections; around adopt the slot's frozen part and the adopted
+pose part, raw and bit for bit.
 
 The handles are made once per path and every case resets them (set_option, set_state_diag, set_tag_index: part of the
 surface under test); a case that fails drops them, so that the next one starts from new handles."""
@@ -90,9 +94,9 @@ def test_pair(sd, both_paths, a, b):
 
 
 def test_the_module_kept_its_promises():
-    """Every pair ran on both paths; ranks were pending at A in every general-kernels case; every operation ran in both
-    positions on both paths; some case left the bound below n before B raised it; nothing was pending behind a
-    localisation call.  Prints the worst of every piece per operation and position (profiles/sequence_pairs.txt)."""
+    """Every one of the 441 pairs ran on both paths; ranks were pending at A in every general-kernels case; each of the 21
+    operations ran in both positions on both paths; some case left the bound below n before B raised it; nothing was pending
+    behind any of the six localisation-like operations, first or second.  Prints the worst of every piece per operation and position (profiles/sequence_pairs.txt)."""
     for (path, pos, op), w in sorted(RECORD["worst"].items()):
         print(f"DEVICE {path:15s} {sc.OPS[op][0]:20s} {pos:6s} {pb.fmt_state(w)}")
     paths = ("default_path", "general_kernels")

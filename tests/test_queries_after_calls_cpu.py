@@ -1,13 +1,13 @@
 """CPU: what makes tests/test_gpu_queries_after_calls.py a statement about device code (no GPU).
 
-Admissibility: each of the 18 cases of sequence_cases.run_query_case (one operation, then a tail of single steps whose own
+Admissibility: each of the 21 cases of sequence_cases.run_query_case (one operation, then a tail of single steps whose own
 bound lies mid-map) runs on the dense model in float64 and in longdouble, compared after A and after the tail: every
 relative-Frobenius piece at most FLOOR_TOL, every entrywise piece at most ENTRY_FLOOR, a loose landmark's own block within a
 quarter of what the judge allows -- the constants of the pairs table, unchanged.  The associate() reference alone excuses no
 observation and leaves out no entry for the observations the GPU module draws.
 
 The judge is not blind.  The mutant is a query whose bound is too low: entries at or beyond `bound` keep their value from
-before the tail (sequence_cases.keep_rows_beyond).  With the tail steps' own bound it fails the joint judge in all 18 cases
+before the tail (sequence_cases.keep_rows_beyond).  With the tail steps' own bound it fails the joint judge in all 21 cases
 and the marginals judge; with the bound of before A it fails wherever A raised the bound over landmarks the tail's ranks
 reach -- at least step, step_detections, predict_dense, update_linear, transform(cov) and join."""
 import types
@@ -98,7 +98,7 @@ def caught(case, bound):
     return None
 
 
-def test_all_18_cases_are_admissible(cases):
+def test_all_cases_are_admissible(cases):
     for a, name in enumerate(NAMES):
         assert set(cases[a]) == {"start", "A", "tail"}
         for stage in ("A", "tail"):
@@ -134,11 +134,11 @@ def test_the_cases_are_what_they_promise(cases):
 def test_the_reference_alone_excuses_nothing(cases):
     t = cases["totals"]
     print(f"ASSOCIATE reference alone: {t}, worst cond(S) {cases['cond']:.3g}")
-    assert t["obs"] == 2 * sc.QUERY_OBS * len(sc.OPS) == 144 and t["entries"] == 4232
+    assert t["obs"] == 2 * sc.QUERY_OBS * len(sc.OPS) == 168 and t["entries"] == 4952
     assert t["excused"] == 0 and t["left_out"] == 0
 
 
-def test_a_query_with_the_tails_own_bound_is_caught_in_all_18_cases(cases):
+def test_a_query_with_the_tails_own_bound_is_caught_in_all_cases(cases):
     for a, name in enumerate(NAMES):
         why = caught(cases[a], cases[a]["A"]["tail_bound"])
         print(f"MUTANT tail's own bound   {name:20s} {why}")

@@ -1,6 +1,6 @@
 """CPU: what makes tests/test_gpu_sequence_bank.py a statement about device code (no GPU).
 
-Admissibility: every one of the 400 cases of tests/sequence_bank_cases.py is run on the dense bank model twice -- in float64, as
+Admissibility: every one of the 529 cases of tests/sequence_bank_cases.py is run on the dense bank model twice -- in float64, as
 the GPU test runs it, and in longdouble (tests/sequence_model.py: the same code, 64 bits of mantissa) -- and every SLOT is judged
 after A, after B and after the continuation under sequence_cases' own constants: every relative-Frobenius piece at most
 FLOOR_TOL, every entrywise piece at most ENTRY_FLOOR (a tenth of ENTRY_TOL).  No case is excused; one set of draws was chosen for
@@ -54,8 +54,8 @@ def pieces(runs, names):
             for s, e in enumerate(errs) for p in names if p in e]
 
 
-def test_all_400_cases_are_admissible(runs):
-    assert len(runs) == 400 == len(bc.OPS) ** 2 and all(set(r[0]) == {"start", "A", "B", "end"} for r in runs.values())
+def test_all_cases_are_admissible(runs):
+    assert len(runs) == 529 == len(bc.OPS) ** 2 and all(set(r[0]) == {"start", "A", "B", "end"} for r in runs.values())
     for pos, name in ((0, "first"), (1, "second")):
         for i, op in enumerate(NAMES):
             for slot in range(bc.B):
@@ -76,7 +76,7 @@ def test_all_400_cases_are_admissible(runs):
 
 def test_the_entrywise_floor_stays_under_the_shared_constant(runs):
     """ENTRY_TOL is sequence_cases' constant, unchanged: ten times ENTRY_FLOOR, which bounds the worst entrywise piece of all
-    400 bank cases too (fork and join(slot) included; profiles/sequence_bank.txt has the figures)."""
+    529 bank cases too (fork and join(slot) included; profiles/sequence_bank.txt has the figures)."""
     w = max(pieces(runs, ENTRYWISE))
     print(f"FLOOR worst entrywise piece: {w[4]} = {w[0]:.2e} ({w[1]}, after {w[2]}, slot {w[3]}); ENTRY_FLOOR = {sc.ENTRY_FLOOR:g}")
     for op in ("fork", "join(slot)"):
@@ -88,8 +88,8 @@ def test_the_entrywise_floor_stays_under_the_shared_constant(runs):
 
 def test_the_table_is_what_it_promises(runs):
     ss = bc.starts()
-    assert [len(s[0]) for s in ss] == [63, 47, 71] and sc.N_MAX == 79 and len(bc.OPS) == 20 and len(set(NAMES)) == 20
-    assert bc.OPS[:18] == sc.OPS and NAMES[18:] == ["fork", "join(slot)"]
+    assert [len(s[0]) for s in ss] == [63, 47, 71] and sc.N_MAX == 79 and len(bc.OPS) == 23 and len(set(NAMES)) == 23
+    assert bc.OPS[:18] == sc.OPS[:18] and NAMES[18:20] == ["fork", "join(slot)"] and bc.OPS[20:] == sc.OPS[18:] and len(sc.OPS) == 21
     tags = [set(range(t0, t0 + n)) for _, n, _, t0 in bc.SLOTS]
     assert not (tags[0] & tags[1] or tags[1] & tags[2] or tags[0] & tags[2]) and len({s for _, _, s, _ in bc.SLOTS}) == 3
     for s, (n_obs, _, _, _) in zip(ss, bc.SLOTS):
@@ -118,13 +118,14 @@ def test_the_table_is_what_it_promises(runs):
     assert (join, remove) in hands and len(hands) > 20
     # every operation first and second on both acting slots; the bystander is never named
     seen = {(x, pos, bc.targets(a, b)[pos]) for a, b in bc.PAIRS for pos, x in enumerate((a, b))}
-    assert seen == {(x, pos, s) for x in range(20) for pos in (0, 1) for s in bc.ACTING}
+    assert seen == {(x, pos, s) for x in range(23) for pos in (0, 1) for s in bc.ACTING}
     behind_setup = 1 + 2 * bc.B                              # set_option, then (set_state_diag, set_tag_index) per slot
     for (a, b), (_, _, calls) in runs.items():
         assert all(slot != bc.BYSTANDER for _, slot in calls[behind_setup:]), bc.pair_name(a, b)
         assert {n for n, slot in calls if slot is not None} <= set(bc.TARGETED), calls
     every = set().union(*({n for n, _ in r[2]} for r in runs.values()))
-    assert every == set(bc.TARGETED) | {"set_option", "bank_step", "bank_stream", "bank_detections", "bank_localize", "bank_localize_stream"}
+    assert every == set(bc.TARGETED) | {"set_option", "bank_step", "bank_stream", "bank_detections", "bank_localize", "bank_localize_stream",
+                                           "bank_localize_detections"}
 
 
 def test_an_idle_slot_never_raises_its_own_bound():

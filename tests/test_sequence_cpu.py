@@ -1,6 +1,6 @@
 """CPU: what makes tests/test_gpu_sequence_pairs.py a statement about device code (no GPU).
 
-Admissibility: every one of the 324 ordered pairs of tests/sequence_cases.py is run on the dense model twice -- in float64, as
+Admissibility: every one of the 441 ordered pairs of tests/sequence_cases.py is run on the dense model twice -- in float64, as
 the GPU test runs it, and in longdouble (tests/sequence_model.py: the same code, 64 bits of mantissa) -- and judged after A,
 after B and after the continuation.  Every relative-Frobenius piece of that comparison is at most FLOOR_TOL = 1e-11 (the rule
 of tests/test_update_blocks_cpu.py), so TOL = 1e-9 on the GPU is two decades above what the inputs' conditioning explains;
@@ -45,8 +45,8 @@ def worst(floors, pieces):
                for st, e in stages.items() for p in pieces if p in e)
 
 
-def test_all_324_pairs_are_admissible(floors):
-    assert len(floors) == 324 == len(sc.OPS) ** 2 and all(set(s) == {"start", "A", "B", "end"} for s in floors.values())
+def test_all_pairs_are_admissible(floors):
+    assert len(floors) == 441 == len(sc.OPS) ** 2 and all(set(s) == {"start", "A", "B", "end"} for s in floors.values())
     for pos, name in ((0, "first"), (1, "second")):
         for i, (op, _) in enumerate(sc.OPS):
             w = {p: max((e[p] for ab, stages in floors.items() if ab[pos] == i for e in stages.values() if p in e), default=0.0)
@@ -72,7 +72,7 @@ def test_entry_tol_is_ten_times_the_measured_floor(floors):
 
 def test_the_table_is_what_it_promises():
     s = sc.start()
-    assert len(s[0]) == 63 and sc.N_MAX == 79 and len(sc.OPS) == 18 and len(set(n for n, _ in sc.OPS)) == 18
+    assert len(s[0]) == 63 and sc.N_MAX == 79 and len(sc.OPS) == 21 and len(set(n for n, _ in sc.OPS)) == 21
     assert set(np.unique(s[4][:sc.STREAM_STEPS + sc.SINGLE_STEPS])) == set(range(sc.N_OBSERVED))
     sizes, calls = {}, {}
     for a, b in sc.PAIRS:
@@ -85,8 +85,10 @@ def test_the_table_is_what_it_promises():
     every = set().union(*calls.values())
     assert every >= {"step1", "run_stream", "step_detections", "predict_linear", "predict_dense1", "update_direct",
                      "update_linear", "transform", "join", "remove_landmarks", "add_landmarks", "copy_in", "set_option",
-                     "set_state_diag", "set_tag_index", "localize1", "localize_update1", "run_localize_stream"}
-    assert [n for n, _ in sc.OPS[15:]] == list(sc.LOCALIZE_OPS)      # appended: the 225 older pairs keep their ids and draws
+                     "set_state_diag", "set_tag_index", "localize1", "localize_update1", "run_localize_stream",
+                     "localize_detections", "hyp_adopt", "hyp_resample_adopt"}
+    assert [n for n, _ in sc.OPS[15:]] == list(sc.LOCALIZE_OPS) and len(sc.LOCALIZE_OPS) == 6    # appended: the older pairs keep their ids and draws
+    assert [n for n, _ in sc.OPS[15:18]] == ["localize", "localize_update", "run_localize"]
     # the start: 26 informed landmarks, 4 loose ones with exact zeros; growth crosses the 64-column edge
     m = sc.new_model()
     d = sc.Driver(m)
@@ -159,13 +161,37 @@ PIECE = "(pose|cross|landmarks|corr_max|mean_pose|mean_landmarks|loose_block|loo
 
 def stale_bound_bank():
     """A model whose localisation leaves P(0..2, c) and its mirror as they were for every c at or beyond max(the start's
-    bound, the call's own bound): what k_loc_rows does when the operation before it did not raise the bound it trusts."""
+    bound, the call's own bound): what k_loc_rows does when the operation before it did not raise the bound it trusts -- and
+    k_hyp_rows, when ekf_hyp_create took a bound from before A for the bank (planted mistake a)."""
+    def stale(call, named):
+        def wrapped(self, *args, **kw):
+            tr = self.tr
+            was = tr.cov.copy()
+            call(self, *args, **kw)
+            c = max(START_BOUND, 3 + 2 * (max(int(j) for j in named(tr, *args)) + 1))
+            tr.cov[:3, c:], tr.cov[c:, :3] = was[:3, c:], was[c:, :3]
+        return wrapped
+
+    def matched(tr, lin, ang, win, unmatched):
+        return [tr.tags[t.tag_id] for _, tags in win for t in tags if t.tag_id in tr.tags]
+
     class StaleBound(sm.SeqBank):
-        def localize1(self, lin, ang, idx, zr, zb, predict=True):
-            was = self.tr.cov.copy()
-            super().localize1(lin, ang, idx, zr, zb, predict)
-            c = max(START_BOUND, 3 + 2 * (max(int(j) for j in idx) + 1))
-            self.tr.cov[:3, c:], self.tr.cov[c:, :3] = was[:3, c:], was[c:, :3]
+        localize1 = stale(sm.SeqBank.localize1, lambda tr, lin, ang, idx, *rest, **kw: idx)
+        localize_detections = stale(sm.SeqBank.localize_detections, matched)
+
+        def hyp_resample_adopt(self, motion, one, two, pose0, cov0, u, s, z):
+            """(step one and step two each under their own bound; the split in between keeps 1 - s^2 of every column)"""
+            tr = self.tr
+            was = (1.0 - s * s) * tr.cov
+            mean, cov = self._hyp_resampled(motion[0], one, pose0, cov0, u, s, z)
+            for obs, step in ((one, None), (two, motion[1])):
+                if step is not None:
+                    was = cov
+                    mean, cov = sm.lcm.literal_step(mean, cov, *step, *obs, tr.cfg)
+                c = max(START_BOUND, 3 + 2 * (max(int(j) for j in obs[0]) + 1))
+                cov[:3, c:], cov[c:, :3] = was[:3, c:], was[c:, :3]
+            tr.mean, tr.cov = mean, cov
+            tr.seen[np.asarray(list(one[0]) + list(two[0]), dtype=int)] = True
 
     s = sc.start()
     return StaleBound(s[0], s[1], sc.sources())
@@ -176,8 +202,9 @@ RAISES_THE_BOUND = ("transform(cov)", "predict_dense", "join", "update_linear", 
 
 @pytest.mark.parametrize("op", sc.LOCALIZE_OPS)
 def test_localisation_under_a_bound_that_A_did_not_raise_is_caught(op):
-    """Behind each operation that correlates columns at or beyond the start's bound, for each of the three localisation
-    operations.  The weakest of the 18 is transform(cov) then localize_update -- no prediction, so the stale columns differ only
+    """Behind each operation that correlates columns at or beyond the start's bound -- transform(cov) and join among them --,
+    for each of the six localisation-like operations (hyp_adopt is two localize1 calls: the mutant's too).  The weakest of the
+    first 18 is transform(cov) then localize_update -- no prediction, so the stale columns differ only
     by K_p (H P)[:, c], and c is a loose landmark's: every informed piece passes and loose_cross, measured 1.9e-9,
     stands against ENTRY_TOL = 4e-10, a factor of 5; the next, transform(cov) then localize, has loose_cross at 5.5e-7
     (profiles/localize_pairs.txt)."""
@@ -211,6 +238,112 @@ def test_a_pass_that_skips_what_localize_correlated_is_caught():
     got = sc.keep_rows_beyond(before, m.state(), START_BOUND)
     with pytest.raises(AssertionError, match="loose_block"):
         judged(got, m)
+
+
+@pytest.mark.parametrize("op", (sc.op_hyp_adopt, sc.op_hyp_resample_adopt), ids=("hyp_adopt", "hyp_resample_adopt"))
+def test_an_adoption_that_leaves_the_bound_where_it_was_is_caught(op):
+    """Planted mistake b.  The adopted hypothesis named a loose landmark: the pose rows it brings reach past the slot's bound,
+    and ekf_hyp_adopt must raise every mirror.  A pass with the bound of before the adoption -- B = step's, or the
+    continuation's -- leaves that landmark's rows as they were."""
+    m, d, rng = reference([op])
+    assert sc.model_bound(m.tr) == START_BOUND + 2 and m.tr.cov[:3, START_BOUND:START_BOUND + 2].any()
+    before = (m.tr.mean.copy(), m.tr.cov.copy())
+    sc.op_step(d, rng)
+    judged(m.state(), m)
+    got = sc.keep_rows_beyond(before, m.state(), START_BOUND)
+    with pytest.raises(AssertionError, match="landmarks: .* exceeds") as why:      # (the step observed it: informed now)
+        judged(got, m)
+    print(f"MUTANT adoption, bound not raised: {why.value}")
+
+
+@pytest.mark.parametrize("first", ("transform(cov)", "join"))
+def test_a_resampling_copy_that_keeps_the_dead_slots_bound_is_caught(first):
+    """Planted mistake c.  Hypothesis 0 was reset: its own bound is 3.  k_hyp_copy gives slot 0 the ancestor's rows; with the
+    dead slot's bound kept, step two updates the columns below its OWN bound only (it names the first loose landmark) and every
+    column beyond -- correlated by A -- stays what the copy brought."""
+    class DeadBound(sm.SeqBank):
+        def hyp_resample_adopt(self, motion, one, two, *rest):
+            tr = self.tr
+            mean, cov = self._hyp_resampled(motion[0], one, *rest)
+            tr.mean, tr.cov = sm.lcm.literal_step(mean, cov, *motion[1], *two, tr.cfg)
+            c = max(3, 3 + 2 * (max(two[0]) + 1))
+            tr.cov[:3, c:], tr.cov[c:, :3] = cov[:3, c:], cov[c:, :3]
+            tr.seen[np.asarray(list(one[0]) + list(two[0]), dtype=int)] = True
+
+    names = [n for n, _ in sc.OPS]
+    s = sc.start()
+    m, bad = sc.new_model(), DeadBound(s[0], s[1], sc.sources())
+    d = sc.Driver(m, bad)
+    sc.setup(d)
+    sc.prelude(d)
+    rng = np.random.default_rng([6, names.index(first)])
+    sc.OPS[names.index(first)][1](d, rng)
+    sc.op_hyp_resample_adopt(d, rng)
+    judged(sc.as_got(m), m)
+    with pytest.raises(AssertionError, match=PIECE) as why:
+        judged(sc.as_got(bad), m)
+    print(f"MUTANT copy keeps the dead slot's bound, behind {first}: {why.value}")
+
+
+class LooseTable(sm.SeqBank):
+    """localize_detections on a tag table that is not the model's: `wrong(tr, unmatched)` is the table the window meets."""
+    wrong = None
+
+    def _localize_window(self, tr, lin, ang, win, unmatched):
+        (tr.mean, tr.cov), tags, _ = sm.ldw.model_window(tr.mean, tr.cov, self.wrong(tr, unmatched), win, lin, ang, cfg=tr.cfg)
+        tr.seen[np.asarray(list(tags), dtype=int)] = True
+
+
+def test_localize_detections_matching_the_unknown_tag_is_caught():
+    """Planted mistake d, first half: the id the table does not hold is matched all the same (to the tail's landmark)."""
+    class Matches(LooseTable):
+        wrong = staticmethod(lambda tr, unmatched: {**tr.tags, **{t: sc.tail_mid(tr) for t in unmatched}})
+
+    s = sc.start()
+    m, bad = sc.new_model(), Matches(s[0], s[1], sc.sources())
+    d = sc.Driver(m, bad)
+    sc.setup(d)
+    sc.prelude(d)
+    sc.op_localize_detections(d, np.random.default_rng(8))
+    assert d.calls.count("localize_detections") == 2
+    judged(sc.as_got(m), m)
+    with pytest.raises(AssertionError, match=PIECE) as why:
+        judged(sc.as_got(bad), m)
+    print(f"MUTANT the unknown tag matched: {why.value}")
+
+
+def test_localize_detections_on_a_table_a_removal_left_stale_is_caught():
+    """Planted mistake d, second half: behind remove_landmarks the table kept its old numbering -- the tag of the last landmark
+    points past the map (the association must not follow it: the window's match is lost) and every other tag one or two
+    landmarks too far.  The operation's own two windows, then one that shows the last landmark's tag."""
+    class Stale(LooseTable):
+        def remove_landmarks(self, lms):
+            old = dict(self.tr.tags)
+            sm.SeqBank.remove_landmarks(self, lms)
+            self.stale = old
+
+        wrong = lambda self, tr, unmatched: self.stale
+
+    s = sc.start()
+    m, bad = sc.new_model(), Stale(s[0], s[1], sc.sources())
+    d = sc.Driver(m, bad)
+    sc.setup(d)
+    sc.prelude(d)
+    rng = np.random.default_rng(9)
+    sc.op_remove(d, rng)
+    last = m.tr.n_lm - 1
+    assert bad.stale[sc.TAG0 + 29] == 29 > last == m.tr.tags[sc.TAG0 + 29] and np.array_equal(bad.tr.cov, m.tr.cov)
+    before = (bad.tr.mean.copy(), bad.tr.cov.copy())
+    assert last in sc.tags_in_gate(m.tr)
+    d.localize_detections(0.004, 0.02, *sc.detection_window(d, rng, [last]))
+    judged(sc.as_got(m), m)
+    assert np.array_equal(bad.tr.cov[3:, 3:], before[1][3:, 3:]) and not bad.tr.cov[:3, 3 + 2 * last:].any()    # (nothing matched)
+    with pytest.raises(AssertionError, match="loose_cross|pose") as why:
+        judged(sc.as_got(bad), m)
+    print(f"MUTANT a stale entry past the map: {why.value}")
+    sc.op_localize_detections(d, rng)                      # (the other entries: each one or two landmarks off)
+    with pytest.raises(AssertionError, match=PIECE):
+        judged(sc.as_got(bad), m)
 
 
 def test_a_landmark_mean_moved_behind_localize_is_caught():
