@@ -657,8 +657,8 @@ int ekf_download_unmatched(ekf_handle *h, int b, int *m, int *tag_id, int capaci
  * bit.  On any difference nothing is written and the call fails with EKF_ERR_STATE.  The slot's active bound is raised to the
  * hypothesis's.
  * Every call returns EKF_ERR_ARG for a NULL bank, a range outside it or a bad argument, with nothing changed; the message is in
- * ekf_hyp_last_error.  Not part of a bank: raw detections, likelihood association per hypothesis, the innovation and pose logs,
- * per-hypothesis noise.
+ * ekf_hyp_last_error.  Not part of a bank: raw detections, likelihood association per hypothesis, the per-hypothesis innovation
+ * and pose logs, per-hypothesis noise.
  * ekf_hypotheses_weigh / ekf_hypotheses_resample (their errors too go to ekf_hyp_last_error) keep a bank running: the weights'
  * statistics and a systematic resampling ON THE DEVICE -- the pose rows are what moves, 393 MB at count = 4096, N = 2000.  Every
  * output of both may be NULL; a call blocks exactly when one is not, else it is asynchronous on the bank's stream like ekf_hyp_step.
@@ -680,7 +680,39 @@ int ekf_download_unmatched(ekf_handle *h, int b, int *m, int *tag_id, int capaci
  * term is added; slots of ancestors with one offspring stay bit for bit.  Refused (EKF_ERR_ARG, nothing changed): u outside
  * [0, 1) or not finite, split outside [0, 1), split > 0 with NULL or non-finite z, z given with split == 0.
  * Measured on one MI355X (tools/hyp_resample_time.py, profiles/hyp_resample.txt; N = 2000, call + sync with every output NULL):
- * count = 4096 at ess = count / 2 105 us, 182 with a split; 4095 copies of one source 114 and 250; ekf_hyp_step there: 657. */
+ * count = 4096 at ess = count / 2 105 us, 182 with a split; 4095 copies of one source 114 and 250; ekf_hyp_step there: 657.
+ * An uploaded stream, run with the resampling decided ON THE DEVICE (errors: ekf_hyp_last_error; every EKF_ERR_ARG leaves the bank
+ * bit for bit).  ekf_hypotheses_stream_upload is ekf_hyp_step's arguments with a leading [step] axis: lin / ang [steps] (motion_stride 0)
+ * or [steps][count]; idx / range / bearing [steps][stride] and m [steps] (obs_stride 0) or [steps][count][stride] and
+ * [steps][count].  Every step is checked as ekf_hyp_step checks it (m <= EKF_MMAX, indices inside the map, an index may come
+ * twice; as there, a range or bearing that is not finite is taken and flags the hypothesis that sees it) and packed into the
+ * records a step uploads -- one per step where both strides are 0, else count, 352 B each -- which are copied to the device.
+ * Blocking.  A new upload replaces the old one, steps == 0 frees it.  The map is frozen, so the stream never goes stale: resets,
+ * resamplings, single steps and adoptions between runs leave it runnable.  A failed allocation returns EKF_ERR_HIP with the byte
+ * count and leaves the bank usable, without a stream.
+ * ekf_hypotheses_run enqueues steps [first, first + count), back to back, ASYNCHRONOUS on the bank's stream like ekf_hyp_step; u and z
+ * are staged by the call (it blocks only where the previous call's staged draws have not been uploaded yet).  Per step s:
+ * ekf_hyp_step's two launches on the step's records; with ess_fraction > 0 or the log on, the weights (ekf_hypotheses_weigh's
+ * launch); with the log on, the mixture row; with ess_fraction > 0, ekf_hypotheses_resample's launches with the offset
+ * u[s - first], the split `split` and the draws z[(s - first) * count * 3 ..], GATED ON THE DEVICE: they act only where something
+ * weighs and ess < ess_fraction * count (one double product formed on the host), and otherwise leave at once and write nothing --
+ * the log-likelihoods stay, the weights carry on.  The bank ends bit for bit as after ekf_hyp_step and, where ess <
+ * ess_fraction * count, ekf_hypotheses_resample per step.  ess_fraction above 1 resamples at every step in which something weighs.
+ * No device-side wait, no second stream, no graph: plain stream-ordered launches.  EKF_ERR_ARG: a range outside the stream,
+ * ess_fraction negative or not finite, split outside [0, 1), split > 0 with ess_fraction == 0, u NULL with ess_fraction > 0 or
+ * given with 0, z NULL with split > 0 or given with 0, a u outside [0, 1), a z that is not finite.  EKF_ERR_STATE: no stream.
+ * ekf_hypotheses_mixture (blocking; every output may be NULL) forms on the device the bank's pose mixture sum_k w_k N(pose_k, block_k):
+ * mean = (sum w x, sum w y, atan2(sum w sin theta, sum w cos theta)) over the normalised weights, cov (3 x 3, symmetric) = sum w
+ * (block_k + d_k d_k^T), d_k the deviation from the mean with its heading wrapped to [-pi, pi), both over the hypotheses with
+ * w > 0 only (a dead one may hold NaN); ess, logmean and live as ekf_hypotheses_weigh gives them; best = the first hypothesis
+ * that weighs and has the largest log-likelihood.  Where nothing weighs: NaN, ess 0, logmean -inf, live 0, best -1.  It changes
+ * nothing a later call can see.  Every sum has a fixed order: the same bank gives the same bits here and in the log.
+ * ekf_hypotheses_log(capacity > 0) keeps the last `capacity` steps' rows in a device ring and restarts the count at 0; capacity 0
+ * switches the log off (after a stream synchronisation).  Neither changes a bit of the bank.  Only ekf_hypotheses_run's steps write
+ * rows: a row is the mixture BEHIND THE STEP'S UPDATE AND BEFORE ITS RESAMPLING -- the exact posterior summary, which a resampling
+ * keeps only in expectation -- and `resampled`, whether the step's resampling acted.  ekf_hypotheses_log_steps: the steps logged.
+ * ekf_hypotheses_download_log (blocking, stream-ordered; every output may be NULL): steps [first, first + count), which must be among
+ * the last `capacity` logged (else EKF_ERR_ARG); EKF_ERR_STATE while the log is off. */
 typedef struct ekf_hypotheses ekf_hypotheses;
 int ekf_hyp_create(ekf_handle *h, int b, int count, ekf_hypotheses **out);
 int ekf_hyp_destroy(ekf_hypotheses *hy);
@@ -699,6 +731,15 @@ const char *ekf_hyp_last_error(ekf_hypotheses *hy);
 int ekf_hypotheses_weigh(ekf_hypotheses *hy, double *ess, double *logmean, int *live);
 int ekf_hypotheses_resample(ekf_hypotheses *hy, double u, double split, const double *z /* count x 3, or NULL iff split == 0 */,
                             int *ancestors /* count */, int *offspring /* count */, double *ess, double *logmean);
+int ekf_hypotheses_stream_upload(ekf_hypotheses *hy, int steps, const double *lin, const double *ang, int motion_stride,
+                          const int *idx, const double *range, const double *bearing, const int *m, int stride, int obs_stride);
+int ekf_hypotheses_run(ekf_hypotheses *hy, int first, int count, double ess_fraction, double split,
+                const double *u /* count, NULL iff ess_fraction == 0 */, const double *z /* count x K x 3, NULL iff split == 0 */);
+int ekf_hypotheses_mixture(ekf_hypotheses *hy, double *mean /* 3 */, double *cov /* 9 */, double *ess, double *logmean, int *live, int *best);
+int ekf_hypotheses_log(ekf_hypotheses *hy, int capacity);
+int ekf_hypotheses_log_steps(ekf_hypotheses *hy, long long *logged);
+int ekf_hypotheses_download_log(ekf_hypotheses *hy, long long first, int count, double *mean /* count x 3 */, double *cov /* count x 9 */,
+                         double *ess, double *logmean, int *live, int *best, int *resampled);
 
 /* Streams of pre-uploaded inputs ([step][batch] and [step][batch][stride] arrays, stride <= EKF_MMAX; m[step][batch] landmarks
  * each -- any count per step and trajectory, 0 included: what the windows of src/replay_no_ros.py:280-301 hold).

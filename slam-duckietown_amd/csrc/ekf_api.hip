@@ -2978,7 +2978,9 @@ extern "C" int ekf_set_option(ekf_handle* h, const char* name, int value) {
 // records' upload (one record where motion and observations are shared), k_hyp_solve and k_hyp_rows; what the call launches is
 // plan_hyp_step's (ekf_host_plan.h).  ekf_hyp_adopt is the one call that touches a handle again: it waits for the bank's stream,
 // applies what is pending on the handle (loc_begin's rule), compares the slot's frozen part with the bank's map on the device and
-// only then writes the hypothesis's pose part into the slot, on the handle's stream.
+// only then writes the hypothesis's pose part into the slot, on the handle's stream.  ekf_hypotheses_run steps through records uploaded
+// once (ekf_hypotheses_stream_upload), with the resampling gated on the device and, while ekf_hypotheses_log is on, a mixture row per step:
+// what it launches is plan_hyp_run's.
 struct ekf_hypotheses : ekf::HypBank {
   DeviceConfig dcfg{};            // the source's config, the slot's noise pair folded into rd / qd; no table, no counters
   bool gate = false;              // the bank's NIS gate (dcfg.nis_gate: the threshold)
@@ -2994,6 +2996,10 @@ struct ekf_hypotheses : ekf::HypBank {
   DeviceBuf<HypWeighOut> dhead;   // ekf_hypotheses_weigh / _resample (made at the first of either): the weights' header,
   DeviceBuf<double> dw;           // the weights,
   DeviceBuf<int> dplan;           // ancestors, offspring and the surplus scan (hyp_resample_ints)
+  DeviceBuf<StepIn> dstream;      // ekf_hypotheses_stream_upload: stream_steps x stream_nrec records
+  StagedUpload<double> draws;     // ekf_hypotheses_run's z: count x K x 3
+  DeviceBuf<HypMixRow> dlog;      // ekf_hypotheses_log: the ring of log_cap rows
+  DeviceBuf<HypMixRow> dmix;      // ekf_hypotheses_mixture's scratch row
   HypWeighOut host_head{};
   std::vector<HypState> host_st;
   std::string err;
@@ -3244,6 +3250,13 @@ static int hyp_resample_view(ekf_hypotheses* hy, HypResampleView& rs) {
   return EKF_OK;
 }
 
+// k_hyp_copy's stores: nontemporal unless EKFSLAM_HIP_HYP_COPY_NT=0 (tools/hyp_resample_time.py measures both,
+// profiles/hyp_resample.txt)
+static bool hyp_copy_nt() {
+  const char* e = std::getenv("EKFSLAM_HIP_HYP_COPY_NT");
+  return e ? std::atoi(e) != 0 : true;
+}
+
 // the header into ess / logmean / live, the plan into ancestors / offspring: blocks if any of them is asked for
 static int hyp_resample_outputs(ekf_hypotheses* hy, const HypResampleView& rs, int* ancestors, int* offspring, double* ess,
                                 double* logmean, int* live) {
@@ -3287,13 +3300,165 @@ extern "C" int ekf_hypotheses_resample(ekf_hypotheses* hy, double u, double spli
     HYP_RES(hy, "the draws' upload", hy->init.commit(nz, hy->stream));
   }
   const HypView v = hyp_view(hy);
-  // (nontemporal stores unless EKFSLAM_HIP_HYP_COPY_NT=0: tools/hyp_resample_time.py measures both, profiles/hyp_resample.txt)
-  bool nt = true;
-  if (const char* e = std::getenv("EKFSLAM_HIP_HYP_COPY_NT")) nt = std::atoi(e) != 0;
   launch_hyp_weigh(hy->stream, v, rs, rp.chunk);
   launch_hyp_plan(hy->stream, v, rs, rp);
-  launch_hyp_copy(hy->stream, nt, v, rs, rp.groups);
+  launch_hyp_copy(hy->stream, hyp_copy_nt(), v, rs, rp);
   if (rp.split) launch_hyp_split(hy->stream, v, rs, rp, hy->init.device());
   HYP_TRY(hy, hipGetLastError());
   return hyp_resample_outputs(hy, rs, ancestors, offspring, ess, logmean, nullptr);
+}
+
+// ---- the uploaded stream, its run, the mixture and its log (plan_hyp_stream, plan_hyp_run, plan_hyp_log; k_hyp_mixture) ----
+// An allocation of `what` failed: the message with the byte count; the runtime's sticky error is cleared, the bank stays usable.
+static int hyp_alloc_fail(ekf_hypotheses* hy, const std::string& what, const res::Status& s) {
+  (void)hipGetLastError();
+  return hyp_fail(hy, EKF_ERR_HIP, what + ": allocation of " + std::to_string(s.bytes) + " bytes: " + hipGetErrorString((hipError_t)s.err));
+}
+
+// Blocking.  The map is frozen, so nothing the bank does afterwards makes the records stale.
+extern "C" int ekf_hypotheses_stream_upload(ekf_hypotheses* hy, int steps, const double* lin, const double* ang, int motion_stride,
+                                     const int* idx, const double* range, const double* bearing, const int* m, int stride,
+                                     int obs_stride) {
+  if (!hy) return EKF_ERR_ARG;
+  HypStreamPlan sp;
+  if (const char* why = plan_hyp_stream(hy, steps, lin, ang, motion_stride, idx, range, bearing, m, stride, obs_stride, sp))
+    return hyp_fail(hy, EKF_ERR_ARG, std::string("ekf_hypotheses_stream_upload: ") + why);
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  std::vector<StepIn> recs(sp.records());
+  fill_hyp_stream(hy, lin, ang, motion_stride, idx, range, bearing, m, stride, obs_stride, sp, recs.data());
+  // (a run in flight still reads the old records: release_group waits for the stream)
+  HYP_RES(hy, "ekf_hypotheses_stream_upload", res::release_group<HipBackend>(hy->stream, hy->dstream));
+  hy->stream_steps = 0;
+  hy->stream_bound.clear();
+  if (sp.steps == 0) return EKF_OK;
+  if (const res::Status s = hy->dstream.ensure(sp.records()); !s.ok())
+    return hyp_alloc_fail(hy, "ekf_hypotheses_stream_upload: the stream of " + std::to_string(sp.steps) + " steps", s);
+  HYP_TRY(hy, hipMemcpyAsync(hy->dstream.p, recs.data(), sizeof(StepIn) * recs.size(), hipMemcpyHostToDevice, hy->stream));
+  HYP_TRY(hy, hipStreamSynchronize(hy->stream));
+  hy->stream_steps = sp.steps;
+  hy->stream_nrec = sp.nrec;
+  hy->stream_rec_stride = sp.rec_stride;
+  hy->stream_bound = std::move(sp.bound);
+  return EKF_OK;
+}
+
+// Asynchronous on the bank's stream: plain stream-ordered launches, each behind the one before it.  Blocks only in the draws'
+// StagedUpload, where the previous call's upload has not run yet.
+extern "C" int ekf_hypotheses_run(ekf_hypotheses* hy, int first, int count, double ess_fraction, double split, const double* u,
+                           const double* z) {
+  if (!hy) return EKF_ERR_ARG;
+  if (!hyp_stream_loaded(hy)) return hyp_fail(hy, EKF_ERR_STATE, "ekf_hypotheses_run: no stream uploaded (ekf_hypotheses_stream_upload)");
+  HypRunPlan rp;
+  if (const char* why = plan_hyp_run(hy, first, count, ess_fraction, split, u, z, rp))
+    return hyp_fail(hy, EKF_ERR_ARG, std::string("ekf_hypotheses_run: ") + why);
+  if (count == 0) return EKF_OK;
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  HypResampleView rs{};
+  if (rp.weigh)
+    if (int rc = hyp_resample_view(hy, rs)) return rc;
+  const size_t nz = 3 * (size_t)hy->count;               // a step's draws
+  if (rp.rs.split) {                                     // (before the first launch: a failed upload leaves the bank alone)
+    double* stage = nullptr;
+    HYP_RES(hy, "the run's draws", hy->draws.begin(nz * (size_t)count, nz * (size_t)count, hy->stream, &stage));
+    std::memcpy(stage, z, sizeof(double) * nz * (size_t)count);
+    HYP_RES(hy, "the draws' upload", hy->draws.commit(nz * (size_t)count, hy->stream));
+  }
+  const HypView v = hyp_view(hy);
+  const bool nt = hyp_copy_nt();
+  HypResamplePlan step = rp.rs;
+  for (int i = 0; i < count; ++i) {
+    launch_hyp_solve(hy->stream, v, hy->dstream.p + rp.rec_offset(i), rp.rec_stride, hy->dcfg, hy->gate);
+    launch_hyp_rows(hy->stream, v, rp.groups[(size_t)i]);
+    if (rp.weigh) launch_hyp_weigh(hy->stream, v, rs, step.chunk);
+    if (rp.mixture) launch_hyp_mixture(hy->stream, v, rs, step, hy->dlog.p + (hy->log_steps + i) % hy->log_cap);
+    if (rp.resample) {
+      step.u = u[i];
+      launch_hyp_plan(hy->stream, v, rs, step);
+      launch_hyp_copy(hy->stream, nt, v, rs, step);
+      if (step.split) launch_hyp_split(hy->stream, v, rs, step, hy->draws.device() + nz * (size_t)i);
+    }
+  }
+  hy->bound_hi = rp.bound_hi;
+  if (rp.mixture) hy->log_steps += count;
+  HYP_TRY(hy, hipGetLastError());
+  return EKF_OK;
+}
+
+// a row into the outputs' entry i (each may be NULL); the covariance mirrored to 3 x 3
+static void hyp_row_out(const HypMixRow& r, size_t i, double* mean, double* cov, double* ess, double* logmean, int* live, int* best,
+                        int* resampled) {
+  if (mean) std::copy_n(r.mean, 3, mean + 3 * i);
+  if (cov)
+    for (int a = 0; a < 3; ++a)
+      for (int c = 0; c < 3; ++c) cov[9 * i + 3 * a + c] = r.cov[hyp_blk(std::min(a, c), std::max(a, c))];
+  if (ess) ess[i] = r.ess;
+  if (logmean) logmean[i] = r.logmean;
+  if (live) live[i] = r.live;
+  if (best) best[i] = r.best;
+  if (resampled) resampled[i] = r.resampled;
+}
+
+// Blocking.  k_hyp_weigh + k_hyp_mixture on the bank as it stands, into scratch every later call forms anew.
+extern "C" int ekf_hypotheses_mixture(ekf_hypotheses* hy, double* mean, double* cov, double* ess, double* logmean, int* live, int* best) {
+  if (!hy) return EKF_ERR_ARG;
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  HypResampleView rs;
+  if (int rc = hyp_resample_view(hy, rs)) return rc;
+  if (const res::Status s = hy->dmix.ensure(1); !s.ok()) return hyp_alloc_fail(hy, "ekf_hypotheses_mixture: the row", s);
+  HypResamplePlan rp;
+  rp.chunk = hyp_plan_chunk(hy->count);
+  rp.ess_min = 0.0;                                      // (no resampling stands behind this row)
+  const HypView v = hyp_view(hy);
+  launch_hyp_weigh(hy->stream, v, rs, rp.chunk);
+  launch_hyp_mixture(hy->stream, v, rs, rp, hy->dmix.p);
+  HYP_TRY(hy, hipGetLastError());
+  HypMixRow r;
+  HYP_TRY(hy, hipMemcpyAsync(&r, hy->dmix.p, sizeof(HypMixRow), hipMemcpyDeviceToHost, hy->stream));
+  HYP_TRY(hy, hipStreamSynchronize(hy->stream));
+  hyp_row_out(r, 0, mean, cov, ess, logmean, live, best, nullptr);
+  return EKF_OK;
+}
+
+// ekf_log_poses' design for the bank: a device ring of the last `capacity` rows, written by ekf_hypotheses_run's steps only.
+extern "C" int ekf_hypotheses_log(ekf_hypotheses* hy, int capacity) {
+  if (!hy) return EKF_ERR_ARG;
+  if (const char* why = plan_hyp_log(capacity)) return hyp_fail(hy, EKF_ERR_ARG, std::string("ekf_hypotheses_log: ") + why);
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  // (launches in flight still write the old ring: release_group waits for the stream)
+  HYP_RES(hy, "ekf_hypotheses_log", res::release_group<HipBackend>(hy->stream, hy->dlog));
+  hy->log_cap = 0;
+  hy->log_steps = 0;
+  if (capacity == 0) return EKF_OK;
+  if (const res::Status s = hy->dlog.ensure((size_t)capacity); !s.ok())
+    return hyp_alloc_fail(hy, "ekf_hypotheses_log: the ring of " + std::to_string(capacity) + " steps", s);
+  hy->log_cap = capacity;
+  return EKF_OK;
+}
+
+extern "C" int ekf_hypotheses_log_steps(ekf_hypotheses* hy, long long* logged) {
+  if (!hy || !logged) return EKF_ERR_ARG;
+  *logged = hy->log_steps;
+  return EKF_OK;
+}
+
+// Blocking and stream-ordered; every output may be NULL.
+extern "C" int ekf_hypotheses_download_log(ekf_hypotheses* hy, long long first, int count, double* mean, double* cov, double* ess,
+                                    double* logmean, int* live, int* best, int* resampled) {
+  if (!hy) return EKF_ERR_ARG;
+  if (!hy->dlog.p) return hyp_fail(hy, EKF_ERR_STATE, "ekf_hypotheses_download_log: the log is off (ekf_hypotheses_log)");
+  if (!ring_range_ok(first, count, hy->log_steps, hy->log_cap))
+    return hyp_fail(hy, EKF_ERR_ARG, "ekf_hypotheses_download_log: steps [" + std::to_string(first) + ", " + std::to_string(first + count) +
+                                         ") are not among the last " + std::to_string(hy->log_cap) + " of the " +
+                                         std::to_string(hy->log_steps) + " logged");
+  if (count == 0) return EKF_OK;
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  std::vector<HypMixRow> hr((size_t)count);
+  const RingPieces rp = ring_pieces(first, count, hy->log_cap);
+  for (int i = 0; i < rp.n; ++i) {
+    const RingPieces::Piece& c = rp.piece[i];
+    HYP_TRY(hy, hipMemcpyAsync(hr.data() + c.done, hy->dlog.p + c.slot, sizeof(HypMixRow) * (size_t)c.rows, hipMemcpyDeviceToHost, hy->stream));
+  }
+  HYP_TRY(hy, hipStreamSynchronize(hy->stream));
+  for (size_t i = 0; i < hr.size(); ++i) hyp_row_out(hr[i], i, mean, cov, ess, logmean, live, best, resampled);
+  return EKF_OK;
 }

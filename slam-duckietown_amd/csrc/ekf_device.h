@@ -136,6 +136,19 @@ static_assert(sizeof(HypWeighOut) == 64, "HypWeighOut is 64 bytes");
 struct HypResampleView {
   HypWeighOut* head; double* w; int* anc; int* off; int* exc;
 };
+// ekf_hypotheses_mixture / ekf_hypotheses_run's log (k_hyp_mixture): the bank's pose mixture sum_k w_k N(pose_k, blk_k) behind k_hyp_weigh's
+// header and weights -- the mean (the heading averaged on the circle), the covariance's stored entries in hyp_blk's order (the
+// deviations' heading wrapped), the header's ess / logmean / live, best = the first hypothesis that weighs and whose loglik is
+// the header's top (-1: none), and resampled = whether a resampling gated by ess_min acts on this header (hyp_gate_open).  A
+// degenerate bank (live == 0): NaN mean and covariance, best = -1.
+struct alignas(16) HypMixRow {
+  double mean[3];
+  double cov[6];
+  double ess, logmean;
+  int live, best, resampled, pad0;
+  double pad;
+};
+static_assert(sizeof(HypMixRow) == 112, "HypMixRow is 112 bytes");
 __host__ __device__ __forceinline__ int p_lds(int ld) { return ld < PPW ? ld : PPW; }
 __host__ __device__ __forceinline__ long p_col(int ld, int j) { return (long)(j >> 12) * ((long)ld * PPW) + (j & (PPW - 1)); }
 // the same as a 32-bit byte offset (ekf_create bounds one covariance by 4 GiB)

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <utility>
 #include <vector>
 
@@ -1269,6 +1270,13 @@ struct HypBank {
   long pstride = 0;
   ekf_config cfg{};
   int bound0 = 3, bound_hi = 3;
+  // the uploaded stream (ekf_hypotheses_stream_upload; plan_hyp_stream): its steps, the records of a step and the stride between the
+  // records k_hyp_solve reads, and per step the bound over the landmarks it names (3: none)
+  int stream_steps = 0, stream_nrec = 1, stream_rec_stride = 0;
+  std::vector<int> stream_bound;
+  // the mixture log (ekf_hypotheses_log): the ring's rows (0: off) and the steps logged since it was switched on
+  int log_cap = 0;
+  long long log_steps = 0;
 };
 constexpr int HYP_COUNT_MAX = 1 << 16;                   // hypotheses of one bank (a grid dimension of the bank's launches)
 // the bytes a hypothesis costs: its record, its three pose rows, its solve's record
@@ -1375,6 +1383,8 @@ struct HypResamplePlan {
   int chunk = 1, groups = 1;
   bool split = false;
   double u = 0.0, s = 0.0, keep = 1.0;
+  // the device's gate (hyp_gate_open): plan, copy and split act where live > 0 and ess < ess_min.  +inf: wherever anything weighs
+  double ess_min = std::numeric_limits<double>::infinity();
 };
 inline const char* plan_hyp_resample(const HypBank* hy, double u, double split, const double* z, HypResamplePlan& rp) {
   if (!(u >= 0.0 && u < 1.0)) return "u must be in [0, 1)";
@@ -1393,6 +1403,136 @@ inline const char* plan_hyp_resample(const HypBank* hy, double u, double split, 
   rp.u = u;
   rp.s = split;
   rp.keep = 1.0 - split * split;
+  return nullptr;
+}
+
+// ekf_hypotheses_stream_upload: ekf_hyp_step's arguments with a leading [step] axis -- lin / ang [steps] (motion_stride 0) or [steps][K];
+// idx / range / bearing [steps][stride] and m [steps] (obs_stride 0) or [steps][K][stride] and [steps][K] -- every step checked by
+// plan_hyp_step.  What the upload packs: nrec records per step (one where both strides are 0, else K), step s's at record
+// s * nrec, and per step the bound over the landmarks it names, from which a run raises the bank's mirror.
+// Returns nullptr, or what is wrong (then nothing of `sp` is to be used and nothing has changed).
+struct HypStreamPlan {
+  int steps = 0, nrec = 1, rec_stride = 0;
+  std::vector<int> bound;
+  size_t records() const { return (size_t)steps * (size_t)nrec; }
+};
+struct HypStreamArgs {                                   // one step's slices of the upload's arrays
+  const double *lin, *ang;
+  const int* idx;
+  const double *range, *bearing;
+  const int* m;
+};
+inline HypStreamArgs hyp_stream_step(const HypBank* hy, int s, const double* lin, const double* ang, int motion_stride, const int* idx,
+                                     const double* range, const double* bearing, const int* m, int stride, int obs_stride) {
+  const size_t mo = (size_t)s * (size_t)(motion_stride ? hy->count : 1), lists = (size_t)s * (size_t)(obs_stride ? hy->count : 1);
+  const size_t oo = lists * (size_t)stride;
+  return HypStreamArgs{lin + mo, ang + mo, idx ? idx + oo : nullptr, range ? range + oo : nullptr, bearing ? bearing + oo : nullptr,
+                       m + lists};
+}
+inline const char* plan_hyp_stream(const HypBank* hy, int steps, const double* lin, const double* ang, int motion_stride,
+                                   const int* idx, const double* range, const double* bearing, const int* m, int stride,
+                                   int obs_stride, HypStreamPlan& sp) {
+  if (steps < 0) return "steps must be >= 0";
+  sp = HypStreamPlan{};
+  if (steps == 0) return nullptr;                        // (frees the stream)
+  if (!lin || !ang) return "NULL lin/ang";
+  if (motion_stride != 0 && motion_stride != 1) return "motion_stride must be 0 (shared) or 1 (one per hypothesis)";
+  if (!m || stride < 0) return "NULL m / bad stride";
+  if (obs_stride != 0 && obs_stride != 1) return "obs_stride must be 0 (shared) or 1 (one list per hypothesis)";
+  HypBank probe;                                         // the bank without its mirror: a step's own bound
+  probe.n = hy->n;
+  probe.count = hy->count;
+  probe.cfg = hy->cfg;
+  sp.bound.resize((size_t)steps);
+  HypStepPlan hp;
+  for (int s = 0; s < steps; ++s) {
+    const HypStreamArgs a = hyp_stream_step(hy, s, lin, ang, motion_stride, idx, range, bearing, m, stride, obs_stride);
+    if (const char* why = plan_hyp_step(&probe, true, a.lin, a.ang, motion_stride, a.idx, a.range, a.bearing, a.m, stride, obs_stride, hp))
+      return why;
+    sp.bound[(size_t)s] = hp.bound_hi;
+  }
+  sp.steps = steps;
+  sp.nrec = hp.nrec;
+  sp.rec_stride = hp.rec_stride;
+  return nullptr;
+}
+// The sp.records() records of a planned upload, step s's from out[s * sp.nrec] on (fill_hyp_records')
+inline void fill_hyp_stream(const HypBank* hy, const double* lin, const double* ang, int motion_stride, const int* idx,
+                            const double* range, const double* bearing, const int* m, int stride, int obs_stride,
+                            const HypStreamPlan& sp, StepIn* out) {
+  HypStepPlan hp;
+  hp.nrec = sp.nrec;
+  hp.rec_stride = sp.rec_stride;
+  for (int s = 0; s < sp.steps; ++s) {
+    const HypStreamArgs a = hyp_stream_step(hy, s, lin, ang, motion_stride, idx, range, bearing, m, stride, obs_stride);
+    fill_hyp_records(hy, true, a.lin, a.ang, motion_stride, a.idx, a.range, a.bearing, a.m, stride, obs_stride, hp,
+                     out + (size_t)s * (size_t)sp.nrec);
+  }
+}
+inline bool hyp_stream_loaded(const HypBank* hy) { return hy->stream_steps > 0; }
+
+// ekf_hypotheses_run: steps [first, first + count) of the uploaded stream.  Per step k_hyp_solve + k_hyp_rows on the step's records
+// (rec_offset) and, as the plan says: k_hyp_weigh (weigh: a resampling or the log needs the header), k_hyp_mixture into the
+// log's next row (mixture: the log is on), k_hyp_plan + k_hyp_copy (resample: ess_fraction > 0) and k_hyp_split (rs.split).  The
+// three resampling launches are gated on the device by rs.ess_min = ess_fraction * K, the double HypothesisBank.resample_if
+// compares with; rs holds their shapes, the call sets rs.u per step.  groups[i]: k_hyp_rows' grid for step first + i, from the
+// bank's mirror raised over the landmarks of the steps run so far; bound_hi: the mirror behind the run.
+// u: count offsets in [0, 1), NULL iff ess_fraction == 0; z: count x K x 3 finite draws, NULL iff split == 0.
+// Returns nullptr, or what is wrong (then nothing of `rp` is to be used and nothing has changed).
+struct HypRunPlan {
+  int first = 0, count = 0, nrec = 1, rec_stride = 0, bound_hi = 3;
+  bool weigh = false, mixture = false, resample = false;
+  HypResamplePlan rs;
+  std::vector<int> groups;
+  size_t rec_offset(int i) const { return (size_t)(first + i) * (size_t)nrec; }
+};
+inline const char* plan_hyp_run(const HypBank* hy, int first, int count, double ess_fraction, double split, const double* u,
+                                const double* z, HypRunPlan& rp) {
+  if (first < 0 || count < 0 || first > hy->stream_steps || count > hy->stream_steps - first) return "range outside the uploaded stream";
+  if (!(ess_fraction >= 0.0) || !std::isfinite(ess_fraction)) return "ess_fraction must be finite and >= 0";
+  if (!(split >= 0.0 && split < 1.0)) return "split must be in [0, 1)";
+  if (split > 0.0 && ess_fraction == 0.0) return "split > 0 needs ess_fraction > 0: nothing is resampled";
+  if (ess_fraction > 0.0) {
+    if (!u) return "ess_fraction > 0 needs u (count offsets in [0, 1))";
+    for (int i = 0; i < count; ++i)
+      if (!(u[i] >= 0.0 && u[i] < 1.0)) return "u must be in [0, 1)";
+  } else if (u) {
+    return "u given with ess_fraction == 0";
+  }
+  if (split > 0.0) {
+    if (!z) return "split > 0 needs z (count x K x 3 standard normal draws)";
+    for (size_t i = 0; i < 3 * (size_t)count * (size_t)hy->count; ++i)
+      if (!std::isfinite(z[i])) return "non-finite z";
+  } else if (z) {
+    return "z given with split == 0";
+  }
+  if (hy->count < 1 || hy->count > HYP_COUNT_MAX || hy->ldx < 2 || hy->ldx % 2 != 0) return "the bank's shape";
+  rp = HypRunPlan{};
+  rp.first = first;
+  rp.count = count;
+  rp.nrec = hy->stream_nrec;
+  rp.rec_stride = hy->stream_rec_stride;
+  rp.mixture = hy->log_cap > 0;
+  rp.resample = ess_fraction > 0.0;
+  rp.weigh = rp.resample || rp.mixture;
+  rp.rs.chunk = hyp_plan_chunk(hy->count);
+  rp.rs.groups = hyp_copy_groups(hy->ldx);
+  rp.rs.split = split > 0.0;
+  rp.rs.s = split;
+  rp.rs.keep = 1.0 - split * split;
+  rp.rs.ess_min = ess_fraction * (double)hy->count;
+  rp.bound_hi = hy->bound_hi;
+  rp.groups.resize((size_t)count);
+  for (int i = 0; i < count; ++i) {
+    rp.bound_hi = std::min(hy->n, std::max(rp.bound_hi, hy->stream_bound[(size_t)(first + i)]));
+    rp.groups[(size_t)i] = loc_rows_groups(rp.bound_hi);
+  }
+  return nullptr;
+}
+// ekf_hypotheses_log: a ring of `capacity` HypMixRow (0: off)
+inline const char* plan_hyp_log(int capacity) {
+  if (capacity < 0) return "capacity must be >= 0";
+  if ((size_t)capacity * sizeof(HypMixRow) > ((size_t)1 << 36)) return "the ring would exceed 64 GiB";
   return nullptr;
 }
 

@@ -29,6 +29,10 @@
 //                 plain stores, 48.9 against 49.4 for 1023 (profiles/hyp_resample.txt); the kernel writes 403 MB in 66 .. 70 us.
 //   k_hyp_split   the same grid, after the copy: every slot whose ancestor has two or more offspring moves its pose by s L z_k
 //                 (L: the lower Cholesky factor of its pose block) and keeps (1 - s^2) of its block and rows, in place.
+//   k_hyp_mixture ONE workgroup behind k_hyp_weigh: the bank's pose mixture -- mean, covariance, best hypothesis -- with the header's
+//                 ess, evidence and live count into one HypMixRow: ekf_hypotheses_mixture's answer and a row of ekf_hypotheses_run's log.
+// k_hyp_plan, k_hyp_copy and k_hyp_split take the resampling's decision on the device (hyp_gate_open: something weighs and ess <
+// ess_min): ekf_hypotheses_resample passes +inf, ekf_hypotheses_run the host's fraction * K, and a closed gate writes nothing.
 // The active bound of a hypothesis lives on the device: the solve raises it over the landmarks of its record exactly as
 // fill_step raises a slot's on the host, so the columns the row launch touches are the ones k_loc_rows would touch.
 #include <algorithm>
@@ -226,6 +230,13 @@ __device__ __forceinline__ bool hyp_weighs(const HypState& s) {
   return fabs(s.loglik) <= 1.79769313486231570815e308 && !(s.flags & EKF_FLAG_NONFINITE);
 }
 
+// The resampling's gate, taken on the device: k_hyp_plan, k_hyp_copy and k_hyp_split act where something weighs and the effective
+// sample size has fallen below ess_min -- HypothesisBank.resample_if's comparison of the same two doubles.  ess_min = +inf
+// (ekf_hypotheses_resample): wherever something weighs; ess is finite there.
+__device__ __forceinline__ bool hyp_gate_open(const HypWeighOut* head, double ess_min) {
+  return head->live > 0 && head->ess < ess_min;
+}
+
 // ONE workgroup; thread t on the records [t * chunk, (t + 1) * chunk) (chunk * HYP_PLAN_THREADS >= K)
 __global__ __launch_bounds__(HYP_PLAN_THREADS) void k_hyp_weigh(const HypState* __restrict__ st, double* __restrict__ w,
                                                                 HypWeighOut* __restrict__ head, int K, int chunk) {
@@ -278,7 +289,8 @@ __device__ __forceinline__ int hyp_raw_t(int k, int last, int K, double run, dou
 // ONE workgroup, the chunks of k_hyp_weigh.  anc / off / exc are written and read back by different threads of the workgroup
 // (behind a barrier): no __restrict__ on them.
 __global__ __launch_bounds__(HYP_PLAN_THREADS) void k_hyp_plan(const HypWeighOut* __restrict__ head, const double* __restrict__ w,
-                                                               int* anc, int* off, int* exc, int K, int chunk, double u) {
+                                                               int* anc, int* off, int* exc, int K, int chunk, double u,
+                                                               double ess_min) {
   __shared__ double shd[16];
   __shared__ int shi[16];
   const int k0 = min(K, (int)threadIdx.x * chunk), k1 = min(K, k0 + chunk);
@@ -289,6 +301,7 @@ __global__ __launch_bounds__(HYP_PLAN_THREADS) void k_hyp_plan(const HypWeighOut
     }
     return;
   }
+  if (!hyp_gate_open(head, ess_min)) return;             // (the whole workgroup) the gate is closed: nothing is written
   const double total = head->sum;
   const int last = head->last;
   // 1: the weights' scan -- this thread's cumulative sums start at `base`
@@ -352,8 +365,8 @@ typedef double hyp_d2 __attribute__((ext_vector_type(2)));
 // The record travels field by field without loglik, which every hypothesis -- survivors too -- gets from the header.
 template <bool NT>
 __global__ __launch_bounds__(HYP_THREADS) void k_hyp_copy(HypState* st, double* X, const HypWeighOut* __restrict__ head,
-                                                          const int* __restrict__ anc, int ldx) {
-  if (head->live == 0) return;
+                                                          const int* __restrict__ anc, int ldx, double ess_min) {
+  if (!hyp_gate_open(head, ess_min)) return;             // (loglik too stays: the weights carry on to the next step)
   const int k = blockIdx.x, a = anc[k];
   const bool rec = blockIdx.y == 0 && threadIdx.x == 0;
   if (a == k) {
@@ -391,8 +404,8 @@ __device__ __forceinline__ bool hyp_pivot(double d) { return d > 0.0 && d <= 1.7
 __global__ __launch_bounds__(HYP_THREADS) void k_hyp_split(HypState* __restrict__ st, double* __restrict__ X,
                                                            const HypWeighOut* __restrict__ head, const int* __restrict__ anc,
                                                            const int* __restrict__ off, const double* __restrict__ z, int ldx,
-                                                           double s, double keep) {
-  if (head->live == 0) return;
+                                                           double s, double keep, double ess_min) {
+  if (!hyp_gate_open(head, ess_min)) return;
   const int k = blockIdx.x;
   if (off[anc[k]] < 2) return;                           // (the whole workgroup: the slot stays bit for bit)
   const int c = 2 * ((int)blockIdx.y * HYP_THREADS + (int)threadIdx.x);
@@ -431,24 +444,86 @@ __global__ __launch_bounds__(HYP_THREADS) void k_hyp_split(HypState* __restrict_
   }
 }
 
+struct HypMin {
+  template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a < b ? a : b; }
+};
+
+// ONE workgroup behind k_hyp_weigh, on its chunks: the bank's mixture pose into *row (evaluation.mixture_pose's quantities).
+// Two sweeps over the hypotheses with w > 0 -- a dead one may hold NaN and is skipped, not multiplied by 0 --: the weighted sums
+// of x, y, sin theta, cos theta, then with the mean known the six stored entries of sum w (blk + d d^T), d's heading wrapped.
+// Every sum is a thread's chunk in order, then hyp_block_scan's fixed order: the same bank gives the same bits from any caller.
+__global__ __launch_bounds__(HYP_PLAN_THREADS) void k_hyp_mixture(const HypState* __restrict__ st, const double* __restrict__ w,
+                                                                  const HypWeighOut* __restrict__ head,
+                                                                  HypMixRow* __restrict__ row, int K, int chunk, double ess_min) {
+  __shared__ double shd[16];
+  __shared__ int shi[16];
+  const int k0 = min(K, (int)threadIdx.x * chunk), k1 = min(K, k0 + chunk);
+  const double top = head->top, total = head->sum;
+  double part[4] = {0.0, 0.0, 0.0, 0.0}, sum[4];
+  int first = K, best;
+  for (int k = k0; k < k1; ++k) {
+    const double wk = w[k];
+    if (!(wk > 0.0)) continue;
+    const HypState& s = st[k];
+    part[0] += wk * s.pose[0];
+    part[1] += wk * s.pose[1];
+    part[2] += wk * sin(s.pose[2]);
+    part[3] += wk * cos(s.pose[2]);
+    if (first == K && s.loglik == top) first = k;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) hyp_block_scan(part[i], 0.0, HypAdd(), shd, &sum[i]);
+  hyp_block_scan(first, K, HypMin(), shi, &best);
+  const double mean[3] = {sum[0] / total, sum[1] / total, atan2(sum[2], sum[3])};
+  double cp[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, cov[6];
+  for (int k = k0; k < k1; ++k) {
+    const double wk = w[k];
+    if (!(wk > 0.0)) continue;
+    const HypState& s = st[k];
+    const double d[3] = {s.pose[0] - mean[0], s.pose[1] - mean[1], wrap_pi(s.pose[2] - mean[2])};
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int c = a; c < 3; ++c) cp[hyp_blk(a, c)] += wk * (s.blk[hyp_blk(a, c)] + d[a] * d[c]);
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) hyp_block_scan(cp[i], 0.0, HypAdd(), shd, &cov[i]);
+  if (threadIdx.x == 0) {
+    const bool any = head->live > 0;
+    const double nan = __builtin_nan("");
+    for (int i = 0; i < 3; ++i) row->mean[i] = any ? mean[i] : nan;
+    for (int i = 0; i < 6; ++i) row->cov[i] = any ? cov[i] / total : nan;
+    row->ess = head->ess;
+    row->logmean = head->logmean;
+    row->live = head->live;
+    row->best = any && best < K ? best : -1;
+    row->resampled = hyp_gate_open(head, ess_min) ? 1 : 0;
+    row->pad0 = 0;
+    row->pad = 0.0;
+  }
+}
+
 void launch_hyp_weigh(hipStream_t st, const HypView& v, const HypResampleView& rs, int chunk) {
   hipLaunchKernelGGL(k_hyp_weigh, dim3(1), dim3(HYP_PLAN_THREADS), 0, st, v.st, rs.w, rs.head, v.count, chunk);
 }
 
 void launch_hyp_plan(hipStream_t st, const HypView& v, const HypResampleView& rs, const HypResamplePlan& rp) {
-  hipLaunchKernelGGL(k_hyp_plan, dim3(1), dim3(HYP_PLAN_THREADS), 0, st, rs.head, rs.w, rs.anc, rs.off, rs.exc, v.count, rp.chunk, rp.u);
+  hipLaunchKernelGGL(k_hyp_plan, dim3(1), dim3(HYP_PLAN_THREADS), 0, st, rs.head, rs.w, rs.anc, rs.off, rs.exc, v.count, rp.chunk, rp.u,
+                     rp.ess_min);
 }
 
-void launch_hyp_copy(hipStream_t st, bool nt, const HypView& v, const HypResampleView& rs, int groups) {
+void launch_hyp_copy(hipStream_t st, bool nt, const HypView& v, const HypResampleView& rs, const HypResamplePlan& rp) {
   if (nt)
-    hipLaunchKernelGGL(k_hyp_copy<true>, dim3(v.count, groups), dim3(HYP_THREADS), 0, st, v.st, v.X, rs.head, rs.anc, v.ldx);
+    hipLaunchKernelGGL(k_hyp_copy<true>, dim3(v.count, rp.groups), dim3(HYP_THREADS), 0, st, v.st, v.X, rs.head, rs.anc, v.ldx,
+                       rp.ess_min);
   else
-    hipLaunchKernelGGL(k_hyp_copy<false>, dim3(v.count, groups), dim3(HYP_THREADS), 0, st, v.st, v.X, rs.head, rs.anc, v.ldx);
+    hipLaunchKernelGGL(k_hyp_copy<false>, dim3(v.count, rp.groups), dim3(HYP_THREADS), 0, st, v.st, v.X, rs.head, rs.anc, v.ldx,
+                       rp.ess_min);
 }
 
 void launch_hyp_split(hipStream_t st, const HypView& v, const HypResampleView& rs, const HypResamplePlan& rp, const double* z) {
   hipLaunchKernelGGL(k_hyp_split, dim3(v.count, rp.groups), dim3(HYP_THREADS), 0, st, v.st, v.X, rs.head, rs.anc, rs.off, z, v.ldx,
-                     rp.s, rp.keep);
+                     rp.s, rp.keep, rp.ess_min);
 }
 
 void launch_hyp_solve(hipStream_t st, const HypView& v, const StepIn* in, int rec_stride, const DeviceConfig& cfg, bool gate) {
@@ -475,6 +550,10 @@ void launch_hyp_adopt(hipStream_t st, const HypView& v, int k, double* Pb, doubl
                       int groups) {
   hipLaunchKernelGGL(k_hyp_adopt, dim3(groups), dim3(HYP_THREADS), 0, st, v.st + k, v.X + (long)k * 3 * v.ldx, v.ldx, Pb, mub, ldb,
                      v.n, so_b, bound);
+}
+
+void launch_hyp_mixture(hipStream_t st, const HypView& v, const HypResampleView& rs, const HypResamplePlan& rp, HypMixRow* row) {
+  hipLaunchKernelGGL(k_hyp_mixture, dim3(1), dim3(HYP_PLAN_THREADS), 0, st, v.st, rs.w, rs.head, row, v.count, rp.chunk, rp.ess_min);
 }
 
 }  // namespace ekf

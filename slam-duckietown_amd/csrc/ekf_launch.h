@@ -145,9 +145,11 @@ void launch_hyp_adopt(hipStream_t st, const HypView& v, int k, double* Pb, doubl
 // plan reads them and leaves rs.anc / rs.off; copy and split read those and the header -- a degenerate bank is left alone
 void launch_hyp_weigh(hipStream_t st, const HypView& v, const HypResampleView& rs, int chunk);
 void launch_hyp_plan(hipStream_t st, const HypView& v, const HypResampleView& rs, const HypResamplePlan& rp);
-void launch_hyp_copy(hipStream_t st, bool nt, const HypView& v, const HypResampleView& rs, int groups);
+void launch_hyp_copy(hipStream_t st, bool nt, const HypView& v, const HypResampleView& rs, const HypResamplePlan& rp);
 // z: count x 3 draws on the device
 void launch_hyp_split(hipStream_t st, const HypView& v, const HypResampleView& rs, const HypResamplePlan& rp, const double* z);
+// behind weigh: the bank's mixture pose into *row; row->resampled: whether rp.ess_min's gate is open on this header
+void launch_hyp_mixture(hipStream_t st, const HypView& v, const HypResampleView& rs, const HypResamplePlan& rp, HypMixRow* row);
 // groups x (tiles of the largest source + 1) workgroups; tab: plan_copy's table on the device
 void launch_copy_traj(hipStream_t st, bool nt, const BankView& src, const BankView& dst, const double* mus, double* mud,
                       const int* tab, int groups, int n_hi);

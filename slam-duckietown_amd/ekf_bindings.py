@@ -172,6 +172,12 @@ ABI = {
     "ekf_hyp_last_error": (C.c_char_p, [C.c_void_p]),
     "ekf_hypotheses_weigh": (C.c_int, [C.c_void_p, _dp, _dp, _ip]),
     "ekf_hypotheses_resample": (C.c_int, [C.c_void_p, C.c_double, C.c_double, _dp, _ip, _ip, _dp, _dp]),
+    "ekf_hypotheses_stream_upload": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _ip, _dp, _dp, _ip, C.c_int, C.c_int]),
+    "ekf_hypotheses_run": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, _dp, _dp]),
+    "ekf_hypotheses_mixture": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _ip, _ip]),
+    "ekf_hypotheses_log": (C.c_int, [C.c_void_p, C.c_int]),
+    "ekf_hypotheses_log_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    "ekf_hypotheses_download_log": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, _ip]),
     "ekf_stream_upload": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
     "ekf_stream_run": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ekf_run_stream": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
@@ -413,6 +419,31 @@ class HypothesisResampling(typing.NamedTuple):
     offspring: np.ndarray  # (count,) int32
     ess: float
     logmean: float
+
+
+class HypothesisMixture(typing.NamedTuple):
+    """What ``HypothesisBank.mixture`` returns: ``evaluation.MixturePose``'s mean and covariance, formed on the device (the
+    weights stay there), and what the weights say of the bank.  A bank in which nothing weighs: NaN, ess 0, evidence -inf,
+    best -1."""
+    mean: np.ndarray       # (3,) the weighted mean pose, the heading averaged on the circle
+    cov: np.ndarray        # (3, 3) sum w (P_k + d_k d_k^T), exactly symmetric
+    ess: float
+    evidence: float
+    live: int
+    best: int              # the first hypothesis with the largest log-likelihood that weighs
+
+
+class HypothesisTrace(typing.NamedTuple):
+    """What ``HypothesisBank.trace`` returns: T logged steps of ``run``, each row the bank's mixture behind the step's update
+    and BEFORE its resampling -- the exact posterior summary; a resampling keeps it only in expectation."""
+    mean: np.ndarray       # (T, 3)
+    cov: np.ndarray        # (T, 3, 3)
+    ess: np.ndarray        # (T,)
+    evidence: np.ndarray   # (T,)
+    live: np.ndarray       # (T,) int32
+    best: np.ndarray       # (T,) int32
+    resampled: np.ndarray  # (T,) bool: the step's resampling acted
+    first: int = 0         # step number of row 0 since the log was switched on
 
 
 EKF_FACTOR_RHS = 16       # (include/ekfslam_hip.h)
@@ -710,6 +741,97 @@ class HypothesisBank:
         if self.ess() < float(fraction) * self.count:
             return self.resample(**kw)
         return None
+
+    # -- an uploaded stream, run with the resampling decided on the device ------------------------
+    def _pack_stream(self, lin, ang, idx, ranges, bearings):
+        """``step``'s arguments per step into ``ekf_hypotheses_stream_upload``'s arrays: (lin, ang, motion_stride, idx, ranges,
+        bearings, m, stride, obs_stride), the observation lists padded to the longest.  Every step must agree on shared or
+        per-hypothesis motion and observations."""
+        steps = len(idx)
+        if not (len(lin) == len(ang) == len(ranges) == len(bearings) == steps):
+            raise ValueError("upload_stream: lin, ang, idx, ranges and bearings must hold one entry per step")
+        motions = [self._motion(l, a) for l, a in zip(lin, ang)]
+        obs = [self._obs(i, r, b) for i, r, b in zip(idx, ranges, bearings)]
+        if len({mo[2] for mo in motions}) > 1 or len({o[4] for o in obs}) > 1:
+            raise ValueError("upload_stream: every step must give its motion, and every step its observations, the same way: "
+                             "shared by the bank, or one per hypothesis")
+        ms, os_ = (motions[0][2], obs[0][4]) if steps else (0, 0)
+        lists, w = (self.count if os_ else 1), max([1] + [o[0].shape[1] for o in obs])
+        L, A = np.zeros((steps, self.count if ms else 1)), np.zeros((steps, self.count if ms else 1))
+        I, m = np.zeros((steps, lists, w), dtype=np.int32), np.zeros((steps, lists), dtype=np.int32)
+        R, B = np.zeros(I.shape), np.zeros(I.shape)
+        for s in range(steps):
+            L[s], A[s] = motions[s][0], motions[s][1]
+            Is, Rs, Bs, m[s], _ = obs[s]
+            I[s, :, :Is.shape[1]], R[s, :, :Is.shape[1]], B[s, :, :Is.shape[1]] = Is, Rs, Bs
+        return L, A, ms, I, R, B, m, w, os_
+
+    def upload_stream(self, lin, ang, idx, ranges, bearings):
+        """A whole recorded run into device memory (``ekf_hypotheses_stream_upload``; blocking): per step the arguments of ``step`` --
+        ``lin[s]`` / ``ang[s]`` scalars or ``count`` values, ``idx[s]`` / ``ranges[s]`` / ``bearings[s]`` one flat list or one
+        list per hypothesis, at most EKF_MMAX observations --, every step the same way.  A new upload replaces the old one; no
+        steps frees it.  The map is frozen, so the stream stays runnable whatever the bank does between runs."""
+        h = self._live()
+        L, A, ms, I, R, B, m, w, os_ = self._pack_stream(lin, ang, idx, ranges, bearings)
+        self._check(self._lib.ekf_hypotheses_stream_upload(h, len(L), _p(L), _p(A), ms, _p(I, _ip), _p(R), _p(B), _p(m, _ip), w, os_))
+        self._stream_steps = len(L)
+
+    def run(self, first: int = 0, count: Optional[int] = None, fraction: float = 0.5, split: float = 0.0, u=None, z=None, rng=None):
+        """Steps [first, first + count) of the uploaded stream (default: to its end), back to back and asynchronous
+        (``ekf_hypotheses_run``): each is ``step`` followed by ``resample_if(fraction, u=u[s], split=split, z=z[s])`` with the
+        decision taken on the device from the same effective sample size -- the same bits, and no host round trip.
+        ``fraction`` 0: no resampling.  ``u`` (count,) and ``z`` (count, K, 3) are drawn from ``rng`` where they are needed and
+        not given.  With the log on (``log``) every step writes a row of ``trace()``."""
+        h = self._live()
+        first, fraction, split = int(first), float(fraction), float(split)
+        count = getattr(self, "_stream_steps", 0) - first if count is None else int(count)
+        if ((fraction > 0.0 and u is None) or (split > 0.0 and z is None)) and rng is None:
+            rng = np.random.default_rng()
+        if u is not None:                                  # (given without a fraction: the library refuses it)
+            u = np.ascontiguousarray(np.broadcast_to(_f64(u), (max(count, 0),)))
+        elif fraction > 0.0:
+            u = rng.random(max(count, 0))
+        if z is not None:
+            z = np.ascontiguousarray(np.broadcast_to(_f64(z), (max(count, 0), self.count, 3)))
+        elif split > 0.0:
+            z = rng.standard_normal((max(count, 0), self.count, 3))
+        self._check(self._lib.ekf_hypotheses_run(h, first, count, fraction, split, None if u is None else _p(u), None if z is None else _p(z)))
+
+    def mixture(self) -> HypothesisMixture:
+        """The bank's pose mixture formed on the device (``ekf_hypotheses_mixture``; blocking): ``evaluation.mixture_pose``'s mean and
+        covariance -- that function stays the host reference -- with the weights' ess, evidence, live count and best."""
+        mean, cov = np.empty(3), np.empty((3, 3))
+        ess, ev, live, best = C.c_double(), C.c_double(), C.c_int(), C.c_int()
+        self._check(self._lib.ekf_hypotheses_mixture(self._live(), _p(mean), _p(cov), C.byref(ess), C.byref(ev), C.byref(live), C.byref(best)))
+        return HypothesisMixture(mean, cov, ess.value, ev.value, live.value, best.value)
+
+    def log(self, capacity: int):
+        """Keeps the mixture of the last ``capacity`` steps of ``run`` on the device (``ekf_hypotheses_log``); restarts the count.
+        0 switches the log off.  ``step`` / ``update`` write no rows."""
+        self._check(self._lib.ekf_hypotheses_log(self._live(), int(capacity)))
+        self._log_cap = int(capacity)
+
+    def logged(self) -> int:
+        """Steps logged since ``log`` switched the log on."""
+        n = C.c_longlong(0)
+        self._check(self._lib.ekf_hypotheses_log_steps(self._live(), C.byref(n)))
+        return int(n.value)
+
+    def trace(self, first: Optional[int] = None, count: Optional[int] = None) -> HypothesisTrace:
+        """Steps [first, first + count) of the log (default: every step still in the ring): the bank behind each step's update
+        and before its resampling.  Blocking, one copy.  ``evaluation.trajectory_ate`` takes it."""
+        total = self.logged()
+        if first is None:
+            first = max(0, total - getattr(self, "_log_cap", 0)) if count is None else max(0, total - int(count))
+        if count is None:
+            count = total - int(first)
+        first, count = int(first), int(count)
+        T = max(count, 0)
+        mean, cov, ess, ev = np.empty((T, 3)), np.empty((T, 3, 3)), np.empty(T), np.empty(T)
+        live, best, res = np.empty(T, dtype=np.int32), np.empty(T, dtype=np.int32), np.empty(T, dtype=np.int32)
+        self._check(self._lib.ekf_hypotheses_download_log(self._live(), first, count, _p(mean), _p(cov), _p(ess), _p(ev), _p(live, _ip),
+                                                   _p(best, _ip), _p(res, _ip)))
+        return HypothesisTrace(mean, cov, ess, ev, live, best, res != 0, first)
 
     def adopt(self, k: int, f: "EkfSlam", b: int = 0):
         """Hypothesis k's pose, pose block and pose rows into trajectory ``b`` of ``f``, whose landmark means and P[3:, 3:] must

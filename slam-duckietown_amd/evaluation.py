@@ -176,8 +176,11 @@ def trajectory_ate(trace, truth_xy, align: bool = False) -> np.ndarray:
     """``ate_rmse`` of every trajectory of a pose trace (``EkfSlam.poses()``) over its logged steps: (B,).
 
     `truth_xy` is (T, 2) -- one ground-truth path shared by the bank -- or (T, B, 2), row k the truth at the time of the
-    trace's row k."""
+    trace's row k.  A hypothesis bank's trace (``HypothesisBank.trace()``: one mixture mean per step, (T, 3)) counts as a bank
+    of one."""
     mean = np.asarray(trace.mean, dtype=float)
+    if mean.ndim == 2:
+        mean = mean[:, None, :]
     T, B = mean.shape[0], mean.shape[1]
     truth = np.asarray(truth_xy, dtype=float)
     if truth.shape == (T, 2):

@@ -8,7 +8,7 @@ __path__.insert(0, _os.path.join(_os.path.dirname(_os.path.dirname(_os.path.absp
                                  "slam-duckietown_amd"))
 
 from .ekf_bindings import (  # noqa: E402,F401
-    Associations, CovFactor, EKF_pose_estimation, EkfConfig, EkfError, EkfSlam, HypothesisBank, HypothesisResampling, Innovations, MapJoin, PoseTrace, build_library, compose_pose, device_count, library_path, load_library,
+    Associations, CovFactor, EKF_pose_estimation, EkfConfig, EkfError, EkfSlam, HypothesisBank, HypothesisMixture, HypothesisResampling, HypothesisTrace, Innovations, MapJoin, PoseTrace, build_library, compose_pose, device_count, library_path, load_library,
     predict, update,
 )
 from .frontend import associate, delta_phi, displacement, fit_transform, poses_on_circle, resolve_associations  # noqa: E402,F401
