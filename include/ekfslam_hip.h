@@ -657,8 +657,8 @@ int ekf_download_unmatched(ekf_handle *h, int b, int *m, int *tag_id, int capaci
  * bit.  On any difference nothing is written and the call fails with EKF_ERR_STATE.  The slot's active bound is raised to the
  * hypothesis's.
  * Every call returns EKF_ERR_ARG for a NULL bank, a range outside it or a bad argument, with nothing changed; the message is in
- * ekf_hyp_last_error.  Not part of a bank: raw detections, likelihood association per hypothesis, the per-hypothesis innovation
- * and pose logs, per-hypothesis noise.
+ * ekf_hyp_last_error.  Not part of a bank: likelihood association per hypothesis, the per-hypothesis innovation and pose logs,
+ * per-hypothesis noise.
  * ekf_hypotheses_weigh / ekf_hypotheses_resample (their errors too go to ekf_hyp_last_error) keep a bank running: the weights'
  * statistics and a systematic resampling ON THE DEVICE -- the pose rows are what moves, 393 MB at count = 4096, N = 2000.  Every
  * output of both may be NULL; a call blocks exactly when one is not, else it is asynchronous on the bank's stream like ekf_hyp_step.
@@ -712,7 +712,37 @@ int ekf_download_unmatched(ekf_handle *h, int b, int *m, int *tag_id, int capaci
  * rows: a row is the mixture BEHIND THE STEP'S UPDATE AND BEFORE ITS RESAMPLING -- the exact posterior summary, which a resampling
  * keeps only in expectation -- and `resampled`, whether the step's resampling acted.  ekf_hypotheses_log_steps: the steps logged.
  * ekf_hypotheses_download_log (blocking, stream-ordered; every output may be NULL): steps [first, first + count), which must be among
- * the last `capacity` logged (else EKF_ERR_ARG); EKF_ERR_STATE while the log is off. */
+ * the last `capacity` logged (else EKF_ERR_ARG); EKF_ERR_STATE while the log is off.
+ * Windows of RAW DETECTIONS, single and streamed (errors: ekf_hyp_last_error; every EKF_ERR_ARG leaves the bank bit for bit).  The
+ * bank's tag-table row (the source slot's, copied at creation) and its map are frozen and the walk of a window reads no pose, so a
+ * window is associated ONCE, on the device, for every hypothesis (k_hyp_associate: ekf_localize_detections' walk and its rules -- the
+ * ignore list, the gate, ids outside [0, 1024) dropped with EKF_FLAG_ASSOC, one slot per distinct tag in order of first
+ * appearance, per-tag averaging; a tag the row does not know or whose entry lies beyond the map is UNMATCHED: skipped, reported,
+ * no flag; more than EKF_AMAX distinct matched tags: the surplus dropped with EKF_FLAG_ASSOC), and a tag's averaged (range,
+ * bearing) has the bits ekf_localize_detections gives it.  The bank takes the handle's association settings at creation, as it
+ * takes the noise pair and the NIS gate; ekf_hypotheses_set_association (ekf_set_association's argument rules) changes them for later
+ * calls and uploads -- a stream already uploaded is NOT associated again.  EKF_ERR_STATE: the source slot had no tag table.
+ * ekf_hypotheses_step_detections: ONE window and ONE motion for every hypothesis (the robot has one camera; per-hypothesis motion
+ * stays with ekf_hyp_step), asynchronous on the bank's stream: the window's upload, the association, then ekf_hyp_step's two
+ * launches on the first EKF_MMAX matched tags and, where the window holds more than EKF_MMAX distinct ids, ekf_hyp_update's on the
+ * rest -- a hypothesis ends bit for bit as after ekf_hyp_step + ekf_hyp_update with the lists ekf_hypotheses_download_tags reports,
+ * and a second pass that finds nothing to apply leaves every hypothesis bit for bit.  EKF_ERR_ARG: count outside [0, EKF_DMAX], NULL
+ * arrays with count > 0, lin or ang not finite.
+ * ekf_hypotheses_detections_upload (blocking): `steps` windows -- lin / ang / count [steps], tag_id / pose_err [steps][stride], pose_t
+ * [steps][stride][3] -- copied, associated in ONE launch (a wave per window) and kept as the bank's stream with each step's matched
+ * tags, unmatched ids and flag; ekf_hypotheses_run runs it exactly as it runs an index stream, with a second solve / rows pair in the
+ * steps that matched more than EKF_MMAX tags (weighing, the log's row and the resampling follow the step's last pass).  It replaces
+ * an earlier stream of either kind, as ekf_hypotheses_stream_upload replaces this one; steps == 0 frees it; a refused call leaves
+ * the earlier stream; a failed allocation returns EKF_ERR_HIP with the byte count and leaves the bank usable, without a stream.
+ * ekf_hypotheses_download_tags (blocking; every output may be NULL; the arrays hold EKF_AMAX entries): the window of `step` of the
+ * uploaded detection stream, or with step == -1 the last single window -- *m matched tags in update order (landmark index, tag
+ * id, averaged error, range, bearing), *n_unmatched distinct unmatched ids and the first EKF_AMAX of them (-1 beyond), and the
+ * window's flag (0 or EKF_FLAG_ASSOC).  EKF_ERR_STATE if no such window exists.
+ * Measured on one MI355X (tools/hyp_detections_time.py, profiles/hyp_detections.txt; N = 2000, 8 tags x 3 frames, 200 windows,
+ * host-clocked): the window's upload and the association add 13 .. 14 us to a step (200 calls behind one sync against ekf_hyp_step
+ * with the reported lists); one window, call + sync, against the host's association + ekf_hyp_step: 72 / 86 us at count = 32,
+ * 207 / 223 at 1024, 802 / 817 at 4096; the upload of 200 windows 2.5 ms against 6.5 with the host's association; ekf_hypotheses_run
+ * per step on the detection stream and on the index stream of the same lists: 23.1 / 23.1, 159.0 / 159.0, 752.3 / 752.5. */
 typedef struct ekf_hypotheses ekf_hypotheses;
 int ekf_hyp_create(ekf_handle *h, int b, int count, ekf_hypotheses **out);
 int ekf_hyp_destroy(ekf_hypotheses *hy);
@@ -740,6 +770,14 @@ int ekf_hypotheses_log(ekf_hypotheses *hy, int capacity);
 int ekf_hypotheses_log_steps(ekf_hypotheses *hy, long long *logged);
 int ekf_hypotheses_download_log(ekf_hypotheses *hy, long long first, int count, double *mean /* count x 3 */, double *cov /* count x 9 */,
                          double *ess, double *logmean, int *live, int *best, int *resampled);
+int ekf_hypotheses_set_association(ekf_hypotheses *hy, double gate_range, const int *ignore_tags, int n_ignore);
+int ekf_hypotheses_step_detections(ekf_hypotheses *hy, double lin, double ang, int count,
+                                   const int *tag_id, const double *pose_t /* count x 3 */, const double *pose_err);
+int ekf_hypotheses_detections_upload(ekf_hypotheses *hy, int steps, const double *lin, const double *ang, const int *count,
+                                     const int *tag_id, const double *pose_t, const double *pose_err, int stride);
+int ekf_hypotheses_download_tags(ekf_hypotheses *hy, int step /* -1: the last single window */, int *m, int *idx, int *tag_id,
+                                 double *err, double *range, double *bearing, int *n_unmatched, int *unmatched /* EKF_AMAX */,
+                                 unsigned *flags);
 
 /* Streams of pre-uploaded inputs ([step][batch] and [step][batch][stride] arrays, stride <= EKF_MMAX; m[step][batch] landmarks
  * each -- any count per step and trajectory, 0 included: what the windows of src/replay_no_ros.py:280-301 hold).

@@ -2996,7 +2996,17 @@ struct ekf_hypotheses : ekf::HypBank {
   DeviceBuf<HypWeighOut> dhead;   // ekf_hypotheses_weigh / _resample (made at the first of either): the weights' header,
   DeviceBuf<double> dw;           // the weights,
   DeviceBuf<int> dplan;           // ancestors, offspring and the surplus scan (hyp_resample_ints)
-  DeviceBuf<StepIn> dstream;      // ekf_hypotheses_stream_upload: stream_steps x stream_nrec records
+  DeviceBuf<StepIn> dstream;      // ekf_hypotheses_stream_upload: stream_steps x stream_nrec records; _detections_upload: 2 x stream_steps
+  AssocConfig acfg{};             // the association's gate and ignore list: the source's at creation (ekf_hypotheses_set_association)
+  StagedUpload<DetIn> det;        // ekf_hypotheses_step_detections' window
+  DeviceBuf<StepIn> dwin_step;    // ... and what k_hyp_associate leaves of it: the two records,
+  DeviceBuf<AssocOut> dwin_assoc; // the matched tags,
+  DeviceBuf<LocUnmatched> dwin_un;   // the unmatched ids
+  DeviceBuf<unsigned> dwin_flags; // and the window's flag
+  bool win_valid = false;         // a single window has run
+  DeviceBuf<AssocOut> dstream_assoc;   // a detection stream's per-step AssocOut, LocUnmatched and flag (empty: an index stream)
+  DeviceBuf<LocUnmatched> dstream_un;
+  DeviceBuf<unsigned> dstream_flags;
   StagedUpload<double> draws;     // ekf_hypotheses_run's z: count x K x 3
   DeviceBuf<HypMixRow> dlog;      // ekf_hypotheses_log: the ring of log_cap rows
   DeviceBuf<HypMixRow> dmix;      // ekf_hypotheses_mixture's scratch row
@@ -3056,6 +3066,7 @@ static int hyp_build(ekf_handle* h, int b, ekf_hypotheses* hy) {
   if (h->dtagmap.p) {
     RES_TRY(h, "the bank's tag-table row", hy->dtag.ensure((size_t)TAGMAX));
     HIP_TRY(h, hipMemcpyAsync(hy->dtag.p, h->dtagmap.p + (size_t)b * TAGMAX, sizeof(int) * TAGMAX, hipMemcpyDeviceToDevice, h->stream));
+    hy->has_tags = true;
   }
   launch_hyp_fill(h->stream, hyp_view(hy), nullptr, 0, hy->count, hyp_fill_groups(hy->ldx), hy->bound0);
   HIP_TRY(h, hipGetLastError());
@@ -3094,6 +3105,8 @@ extern "C" int ekf_hyp_create(ekf_handle* h, int b, int count, ekf_hypotheses** 
     std::copy_n(r + 3, 2, hy->dcfg.qd);
   }
   hy->dcfg.noise = nullptr;
+  hy->acfg = h->acfg;
+  hy->acfg.active_bound = 0;                             // (a hypothesis's bound lives in its HypState: the records' neff is not read)
   if (int rc = hyp_build(h, b, hy)) {
     hyp_free(hy);
     return rc;
@@ -3315,6 +3328,17 @@ static int hyp_alloc_fail(ekf_hypotheses* hy, const std::string& what, const res
   return hyp_fail(hy, EKF_ERR_HIP, what + ": allocation of " + std::to_string(s.bytes) + " bytes: " + hipGetErrorString((hipError_t)s.err));
 }
 
+// The uploaded stream of either kind released (a run in flight still reads the old records: release_group waits for the
+// stream) and the bank's mirror of it cleared: the bank stays usable without a stream.
+static int hyp_stream_drop(ekf_hypotheses* hy, const char* fn) {
+  HYP_RES(hy, fn, res::release_group<HipBackend>(hy->stream, hy->dstream, hy->dstream_assoc, hy->dstream_un, hy->dstream_flags));
+  hy->stream_steps = 0;
+  hy->stream_bound.clear();
+  hy->stream_passes.clear();
+  hy->stream_pass_stride = 0;
+  return EKF_OK;
+}
+
 // Blocking.  The map is frozen, so nothing the bank does afterwards makes the records stale.
 extern "C" int ekf_hypotheses_stream_upload(ekf_hypotheses* hy, int steps, const double* lin, const double* ang, int motion_stride,
                                      const int* idx, const double* range, const double* bearing, const int* m, int stride,
@@ -3326,10 +3350,7 @@ extern "C" int ekf_hypotheses_stream_upload(ekf_hypotheses* hy, int steps, const
   HYP_TRY(hy, hipSetDevice(hy->device));
   std::vector<StepIn> recs(sp.records());
   fill_hyp_stream(hy, lin, ang, motion_stride, idx, range, bearing, m, stride, obs_stride, sp, recs.data());
-  // (a run in flight still reads the old records: release_group waits for the stream)
-  HYP_RES(hy, "ekf_hypotheses_stream_upload", res::release_group<HipBackend>(hy->stream, hy->dstream));
-  hy->stream_steps = 0;
-  hy->stream_bound.clear();
+  if (int rc = hyp_stream_drop(hy, "ekf_hypotheses_stream_upload")) return rc;
   if (sp.steps == 0) return EKF_OK;
   if (const res::Status s = hy->dstream.ensure(sp.records()); !s.ok())
     return hyp_alloc_fail(hy, "ekf_hypotheses_stream_upload: the stream of " + std::to_string(sp.steps) + " steps", s);
@@ -3347,7 +3368,7 @@ extern "C" int ekf_hypotheses_stream_upload(ekf_hypotheses* hy, int steps, const
 extern "C" int ekf_hypotheses_run(ekf_hypotheses* hy, int first, int count, double ess_fraction, double split, const double* u,
                            const double* z) {
   if (!hy) return EKF_ERR_ARG;
-  if (!hyp_stream_loaded(hy)) return hyp_fail(hy, EKF_ERR_STATE, "ekf_hypotheses_run: no stream uploaded (ekf_hypotheses_stream_upload)");
+  if (!hyp_stream_loaded(hy)) return hyp_fail(hy, EKF_ERR_STATE, "ekf_hypotheses_run: no stream uploaded (ekf_hypotheses_stream_upload / ekf_hypotheses_detections_upload)");
   HypRunPlan rp;
   if (const char* why = plan_hyp_run(hy, first, count, ess_fraction, split, u, z, rp))
     return hyp_fail(hy, EKF_ERR_ARG, std::string("ekf_hypotheses_run: ") + why);
@@ -3367,8 +3388,10 @@ extern "C" int ekf_hypotheses_run(ekf_hypotheses* hy, int first, int count, doub
   const bool nt = hyp_copy_nt();
   HypResamplePlan step = rp.rs;
   for (int i = 0; i < count; ++i) {
-    launch_hyp_solve(hy->stream, v, hy->dstream.p + rp.rec_offset(i), rp.rec_stride, hy->dcfg, hy->gate);
-    launch_hyp_rows(hy->stream, v, rp.groups[(size_t)i]);
+    for (int p = 0; p < rp.passes[(size_t)i]; ++p) {     // (a detection stream's step with more than MMAX tags: two)
+      launch_hyp_solve(hy->stream, v, hy->dstream.p + rp.rec_offset(i, p), rp.rec_stride, hy->dcfg, hy->gate);
+      launch_hyp_rows(hy->stream, v, rp.groups[(size_t)i]);
+    }
     if (rp.weigh) launch_hyp_weigh(hy->stream, v, rs, step.chunk);
     if (rp.mixture) launch_hyp_mixture(hy->stream, v, rs, step, hy->dlog.p + (hy->log_steps + i) % hy->log_cap);
     if (rp.resample) {
@@ -3460,5 +3483,130 @@ extern "C" int ekf_hypotheses_download_log(ekf_hypotheses* hy, long long first, 
   }
   HYP_TRY(hy, hipStreamSynchronize(hy->stream));
   for (size_t i = 0; i < hr.size(); ++i) hyp_row_out(hr[i], i, mean, cov, ess, logmean, live, best, resampled);
+  return EKF_OK;
+}
+
+// ---- a bank's windows of raw detections (plan_hyp_detections, plan_hyp_detection_stream; k_hyp_associate: ekf_loc_assoc.hip) ----
+// The bank's tag-table row and its map are frozen and the walk of a window reads no pose, so a window is associated ONCE for
+// every hypothesis: k_hyp_associate leaves the shared records k_hyp_solve reads with rec_stride 0.  A single window is staged and
+// associated in front of its solves, asynchronously; a whole stream is associated at its upload, in one launch, and
+// ekf_hypotheses_run then runs it as it runs an index stream.  A later ekf_hypotheses_set_association reaches later calls and
+// uploads only: an uploaded stream is not associated again.
+extern "C" int ekf_hypotheses_set_association(ekf_hypotheses* hy, double gate_range, const int* ignore_tags, int n_ignore) {
+  if (!hy) return EKF_ERR_ARG;
+  if (n_ignore < 0 || n_ignore > IGNMAX || (n_ignore > 0 && !ignore_tags))
+    return hyp_fail(hy, EKF_ERR_ARG, "ekf_hypotheses_set_association: at most 16 ignored tags");
+  hy->acfg.gate2 = gate_range * gate_range;
+  hy->acfg.n_ignore = n_ignore;
+  for (int i = 0; i < n_ignore; ++i) hy->acfg.ignore[i] = ignore_tags[i];
+  return EKF_OK;
+}
+
+// Asynchronous on the bank's stream: the window's upload, k_hyp_associate on it, then the planned solve / rows pairs on the two
+// shared records.  A second pass whose record turns out empty (fewer than MMAX + 1 tags matched) applies nothing: k_hyp_solve
+// leaves the HypState and k_hyp_rows leaves at once (LocRec::apply).
+extern "C" int ekf_hypotheses_step_detections(ekf_hypotheses* hy, double lin, double ang, int count, const int* tag_id,
+                                              const double* pose_t, const double* pose_err) {
+  const char* fn = "ekf_hypotheses_step_detections";
+  if (!hy) return EKF_ERR_ARG;
+  HypDetPlan dp;
+  if (const char* why = plan_hyp_detections(hy, lin, ang, count, tag_id, pose_t, pose_err, dp))
+    return hyp_fail(hy, dp.code, std::string(fn) + ": " + why);
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  bool fresh = false;
+  HYP_RES(hy, "the window's records", res::ensure_group(&fresh, res::want(hy->dwin_step, (size_t)2), res::want(hy->dwin_assoc, (size_t)1),
+                                                        res::want(hy->dwin_un, (size_t)1), res::want(hy->dwin_flags, (size_t)1)));
+  if (fresh) HYP_TRY(hy, hipMemsetAsync(hy->dwin_assoc.p, 0, sizeof(AssocOut), hy->stream));   // (the kernel writes the m slots taken)
+  DetIn* hs = nullptr;
+  HYP_RES(hy, "the window", hy->det.begin(1, 1, hy->stream, &hs));
+  fill_hyp_det_records(1, &lin, &ang, &count, tag_id, pose_t, pose_err, count, hs);
+  HYP_RES(hy, "the window's upload", hy->det.commit(1, hy->stream));
+  const HypView v = hyp_view(hy);
+  launch_hyp_associate(hy->stream, v, hy->dtag.p, hy->det.device(), 1, hy->dwin_step.p, hy->dwin_assoc.p, hy->dwin_un.p,
+                       hy->dwin_flags.p, hy->acfg);
+  hy->win_valid = true;
+  hy->bound_hi = dp.bound_hi;
+  for (int p = 0; p < dp.passes; ++p) {
+    launch_hyp_solve(hy->stream, v, hy->dwin_step.p + p, 0, hy->dcfg, hy->gate);
+    launch_hyp_rows(hy->stream, v, dp.groups);
+  }
+  HYP_TRY(hy, hipGetLastError());
+  return EKF_OK;
+}
+
+// Blocking.  The windows are copied and associated in one launch (a wave per window); the records stay as the bank's stream with
+// each step's AssocOut, LocUnmatched and flag, and each step's matched count and highest landmark come back, so that a run's
+// bounds and passes are exact.  Replaces an earlier stream of either kind; a refused call leaves it.
+extern "C" int ekf_hypotheses_detections_upload(ekf_hypotheses* hy, int steps, const double* lin, const double* ang, const int* count,
+                                                const int* tag_id, const double* pose_t, const double* pose_err, int stride) {
+  const char* fn = "ekf_hypotheses_detections_upload";
+  if (!hy) return EKF_ERR_ARG;
+  HypDetStreamPlan sp;
+  if (const char* why = plan_hyp_detection_stream(hy, steps, lin, ang, count, tag_id, pose_t, pose_err, stride, sp))
+    return hyp_fail(hy, sp.code, std::string(fn) + ": " + why);
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  std::vector<DetIn> wins((size_t)sp.steps);
+  fill_hyp_det_records(sp.steps, lin, ang, count, tag_id, pose_t, pose_err, stride, wins.data());
+  if (int rc = hyp_stream_drop(hy, fn)) return rc;
+  if (sp.steps == 0) return EKF_OK;
+  const size_t S = (size_t)sp.steps;
+  DeviceBuf<DetIn> ddet;                                 // (the windows themselves are not kept)
+  if (const res::Status s = res::ensure_group(nullptr, res::want(hy->dstream, sp.records()), res::want(hy->dstream_assoc, S),
+                                              res::want(hy->dstream_un, S), res::want(hy->dstream_flags, S), res::want(ddet, S));
+      !s.ok())
+    return hyp_alloc_fail(hy, std::string(fn) + ": the stream of " + std::to_string(sp.steps) + " windows", s);
+  hipError_t e = hipMemsetAsync(hy->dstream_assoc.p, 0, sizeof(AssocOut) * S, hy->stream);   // (the kernel writes the slots taken)
+  if (e == hipSuccess) e = hipMemcpyAsync(ddet.p, wins.data(), sizeof(DetIn) * S, hipMemcpyHostToDevice, hy->stream);
+  std::vector<AssocOut> ao(S);
+  if (e == hipSuccess) {
+    launch_hyp_associate(hy->stream, hyp_view(hy), hy->dtag.p, ddet.p, sp.steps, hy->dstream.p, hy->dstream_assoc.p,
+                         hy->dstream_un.p, hy->dstream_flags.p, hy->acfg);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(ao.data(), hy->dstream_assoc.p, sizeof(AssocOut) * S, hipMemcpyDeviceToHost, hy->stream);
+  const hipError_t es = hipStreamSynchronize(hy->stream);   // (also on a failure: ddet and the host arrays leave with this call)
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) {
+    (void)hyp_stream_drop(hy, fn);
+    return hyp_fail(hy, EKF_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+  }
+  finish_hyp_detection_stream(hy, ao.data(), sp);
+  hy->stream_steps = sp.steps;
+  hy->stream_nrec = 1;
+  hy->stream_rec_stride = 0;
+  hy->stream_bound = std::move(sp.bound);
+  hy->stream_passes = std::move(sp.passes);
+  hy->stream_pass_stride = S;
+  return EKF_OK;
+}
+
+// Blocking; every output may be NULL.  idx / tag_id / err / range / bearing and unmatched: EKF_AMAX entries each.
+extern "C" int ekf_hypotheses_download_tags(ekf_hypotheses* hy, int step, int* m, int* idx, int* tag_id, double* err, double* range,
+                                            double* bearing, int* n_unmatched, int* unmatched, unsigned* flags) {
+  if (!hy) return EKF_ERR_ARG;
+  int code = EKF_ERR_ARG;
+  if (const char* why = plan_hyp_download_tags(hy, step, hy->win_valid, &code))
+    return hyp_fail(hy, code, std::string("ekf_hypotheses_download_tags: ") + why);
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  const bool single = step < 0;
+  const size_t at = single ? 0 : (size_t)step;
+  AssocOut a;
+  LocUnmatched u;
+  unsigned f = 0;
+  HYP_TRY(hy, hipMemcpyAsync(&a, (single ? hy->dwin_assoc.p : hy->dstream_assoc.p) + at, sizeof(a), hipMemcpyDeviceToHost, hy->stream));
+  HYP_TRY(hy, hipMemcpyAsync(&u, (single ? hy->dwin_un.p : hy->dstream_un.p) + at, sizeof(u), hipMemcpyDeviceToHost, hy->stream));
+  HYP_TRY(hy, hipMemcpyAsync(&f, (single ? hy->dwin_flags.p : hy->dstream_flags.p) + at, sizeof(f), hipMemcpyDeviceToHost, hy->stream));
+  HYP_TRY(hy, hipStreamSynchronize(hy->stream));
+  if (m) *m = a.m;
+  for (int i = 0; i < AMAX; ++i) {
+    if (idx) idx[i] = a.idx[i];
+    if (tag_id) tag_id[i] = a.tag_id[i];
+    if (err) err[i] = a.err[i];
+    if (range) range[i] = a.range[i];
+    if (bearing) bearing[i] = a.bearing[i];
+    if (unmatched) unmatched[i] = u.tag_id[i];
+  }
+  if (n_unmatched) *n_unmatched = u.total;
+  if (flags) *flags = f;
   return EKF_OK;
 }

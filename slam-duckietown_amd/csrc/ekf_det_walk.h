@@ -1,6 +1,7 @@
-// The walk over one window of raw AprilTag detections (src/replay_no_ros.py:280-337), shared by the two kernels that run it
-// (ekf_loc_assoc.hip): k_associate on a growing map (ekf_step_detections) and k_loc_associate on a frozen one
-// (ekf_localize_detections).  ONE wave per trajectory; every lane calls every function here.
+// The walk over one window of raw AprilTag detections (src/replay_no_ros.py:280-337), shared by the three kernels that run it
+// (ekf_loc_assoc.hip): k_associate on a growing map (ekf_step_detections), k_loc_associate on a frozen one
+// (ekf_localize_detections) and k_hyp_associate on a hypothesis bank's (ekf_hypotheses_step_detections / _detections_upload).
+// ONE wave per window; every lane calls every function here.
 //   det_walk      the detections in chunks of 64 -- per chunk every lane fetches ITS detection (id, the id's landmark index from
 //                 the tag table, IGNORE_TAGS, the gate): one memory round trip for 64 detections -- then, detection by detection
 //                 and without touching memory, what depends on their ORDER: one slot per distinct tag in order of first
@@ -8,8 +9,9 @@
 //                 detection gets whose tag has no slot in this window yet is the caller's `admit`.
 //   det_tag_out   lane = slot: the sums divided by the count, xr = t2, yr = -t0, sqrt, atan2, the world guess from the pose
 //                 BEFORE the prediction, into the slot's places of the two StepIn records and of the AssocOut record.
-//   det_tail      (lane 0) the active bound raised over the window's landmarks and the heads of the two StepIn records.
-// The two kernels give a tag the same averaged (range, bearing) bits because this is the only statement of that arithmetic; it
+//   det_tail      (lane 0) the active bound raised over the window's landmarks and the heads of the two StepIn records
+//                 (det_heads: the heads alone, where the bound lives elsewhere).
+// The kernels give a tag the same averaged (range, bearing) bits because this is the only statement of that arithmetic; it
 // runs without contraction, and `#pragma clang fp contract(off)` is lexical: every function with arithmetic carries its own.
 #pragma once
 #include "ekf_device.h"
@@ -149,31 +151,37 @@ __device__ __forceinline__ DetTag det_tag_out(const DetWalkShared& sh, int lane,
   return r;
 }
 
-// (lane 0) the trajectory's active bound raised over the window's landmarks and capped at the state's size after the window;
-// the heads of its two StepIn records -- [b]: the prediction and the first MMAX landmarks, [batch + b]: the rest, an update
-// without a prediction -- and of `ao`.
-__device__ __forceinline__ void det_tail(const DetWalkShared& sh, const DetIn& d, const AssocConfig& cfg, int m, int n_after,
-                                         int* neff_dev, StepIn* step_out, int batch, int b, AssocOut& ao) {
-  int bound = neff_dev[b];
-  for (int u = 0; u < m; ++u) bound = max(bound, 3 + 2 * (sh.idx[u] + 1));
-  bound = min(bound, n_after);
-  neff_dev[b] = bound;
+// (lane 0) the heads of a window's two StepIn records -- [b]: the prediction and the first MMAX landmarks, [batch + b]: the
+// rest, an update without a prediction -- with the active bound `neff` both carry, and of `ao`.
+__device__ __forceinline__ void det_heads(const DetIn& d, int m, int neff, int n_after, StepIn* step_out, int batch, int b,
+                                          AssocOut& ao) {
   StepIn& s0 = step_out[b];
   StepIn& s1 = step_out[(long)batch + b];
   s0.lin = d.lin;
   s0.ang = d.ang;
   s0.m = min(m, MMAX);
   s0.flags = FLAG_PREDICT | FLAG_UPDATE;
-  s0.neff = cfg.active_bound ? bound : n_after;
+  s0.neff = neff;
   s0.pad = 0;
   s1.lin = 0.0;
   s1.ang = 0.0;
   s1.m = max(m - MMAX, 0);
   s1.flags = FLAG_UPDATE;
-  s1.neff = s0.neff;
+  s1.neff = neff;
   s1.pad = 0;
   ao.m = m;
   ao.n_after = n_after;
+}
+
+// (lane 0) the trajectory's active bound raised over the window's landmarks and capped at the state's size after the window,
+// then det_heads with it.
+__device__ __forceinline__ void det_tail(const DetWalkShared& sh, const DetIn& d, const AssocConfig& cfg, int m, int n_after,
+                                         int* neff_dev, StepIn* step_out, int batch, int b, AssocOut& ao) {
+  int bound = neff_dev[b];
+  for (int u = 0; u < m; ++u) bound = max(bound, 3 + 2 * (sh.idx[u] + 1));
+  bound = min(bound, n_after);
+  neff_dev[b] = bound;
+  det_heads(d, m, cfg.active_bound ? bound : n_after, n_after, step_out, batch, b, ao);
 }
 
 }  // namespace ekf

@@ -891,18 +891,25 @@ inline const char* plan_obs_lists(const HostPlan* h, bool pred, bool upd, bool u
 // [0, min(stride, EKF_DMAX)]; the detection arrays where anything is detected.  *m_hi: the most distinct tag ids of any window,
 // capped at AMAX -- an upper bound of what the device matches (ignored, gated, unknown and bad ids count), the bound both entries
 // select their kernels by; 0 with the measurement model off.  Returns nullptr, or what is wrong (then *m_hi is not written).
+// One window of c detections, the w-th of arrays with `stride` detections per window; *distinct: its distinct tag ids, capped at AMAX.
+inline const char* plan_det_window(int c, int stride, long w, const int* tag_id, const double* pose_t, const double* pose_err,
+                                   int* distinct) {
+  if (c < 0 || c > stride || c > DMAX) return "count must be <= min(stride, EKF_DMAX)";
+  if (c > 0 && (!tag_id || !pose_t || !pose_err)) return "NULL detection arrays";
+  const int* ids = c > 0 ? tag_id + w * stride : nullptr;
+  int d = 0;
+  for (int i = 0; i < c; ++i) d += std::find(ids, ids + i, ids[i]) == ids + i ? 1 : 0;
+  *distinct = std::min(d, AMAX);
+  return nullptr;
+}
 inline const char* plan_det_windows(const HostPlan* h, const double* lin, const double* ang, const int* count, const int* tag_id,
                                     const double* pose_t, const double* pose_err, int stride, int* m_hi) {
   if (!lin || !ang || !count || stride < 0) return "NULL array";
   int hi = 0;
   for (int b = 0; b < h->batch; ++b) {
-    const int c = count[b];
-    if (c < 0 || c > stride || c > DMAX) return "count must be <= min(stride, EKF_DMAX)";
-    if (c > 0 && (!tag_id || !pose_t || !pose_err)) return "NULL detection arrays";
-    const int* ids = c > 0 ? tag_id + (long)b * stride : nullptr;
     int distinct = 0;
-    for (int i = 0; i < c; ++i) distinct += std::find(ids, ids + i, ids[i]) == ids + i ? 1 : 0;
-    hi = std::max(hi, std::min(distinct, AMAX));
+    if (const char* why = plan_det_window(count[b], stride, b, tag_id, pose_t, pose_err, &distinct)) return why;
+    hi = std::max(hi, distinct);
   }
   *m_hi = h->cfg.enable_measurement_model ? hi : 0;
   return nullptr;
@@ -1274,6 +1281,13 @@ struct HypBank {
   // records k_hyp_solve reads, and per step the bound over the landmarks it names (3: none)
   int stream_steps = 0, stream_nrec = 1, stream_rec_stride = 0;
   std::vector<int> stream_bound;
+  // a detection stream (ekf_hypotheses_detections_upload; plan_hyp_detection_stream): per step its update passes (1, or 2 where
+  // it matched more than MMAX tags; empty: an index stream, one pass each) and the records between a step's first pass and its
+  // second (k_hyp_associate's layout: the stream's steps)
+  std::vector<int> stream_passes;
+  size_t stream_pass_stride = 0;
+  // whether the source slot had a tag table at creation (the bank's row of it: what a window of detections is walked against)
+  bool has_tags = false;
   // the mixture log (ekf_hypotheses_log): the ring's rows (0: off) and the steps logged since it was switched on
   int log_cap = 0;
   long long log_steps = 0;
@@ -1484,7 +1498,11 @@ struct HypRunPlan {
   bool weigh = false, mixture = false, resample = false;
   HypResamplePlan rs;
   std::vector<int> groups;
-  size_t rec_offset(int i) const { return (size_t)(first + i) * (size_t)nrec; }
+  // a detection stream: step first + i runs passes[i] solve / rows pairs (an index stream: 1 each), pass p on the records at
+  // rec_offset(i, p); weighing, the mixture row and the resampling follow the step's last pass
+  std::vector<int> passes;
+  size_t pass_stride = 0;
+  size_t rec_offset(int i, int p = 0) const { return (size_t)(first + i) * (size_t)nrec + (size_t)p * pass_stride; }
 };
 inline const char* plan_hyp_run(const HypBank* hy, int first, int count, double ess_fraction, double split, const double* u,
                                 const double* z, HypRunPlan& rp) {
@@ -1523,10 +1541,93 @@ inline const char* plan_hyp_run(const HypBank* hy, int first, int count, double 
   rp.rs.ess_min = ess_fraction * (double)hy->count;
   rp.bound_hi = hy->bound_hi;
   rp.groups.resize((size_t)count);
+  rp.passes.assign((size_t)count, 1);
+  rp.pass_stride = hy->stream_pass_stride;
   for (int i = 0; i < count; ++i) {
     rp.bound_hi = std::min(hy->n, std::max(rp.bound_hi, hy->stream_bound[(size_t)(first + i)]));
     rp.groups[(size_t)i] = loc_rows_groups(rp.bound_hi);
+    if (!hy->stream_passes.empty()) rp.passes[(size_t)i] = hy->stream_passes[(size_t)(first + i)];
   }
+  return nullptr;
+}
+
+// ---- a bank's windows of raw detections (k_hyp_associate -> k_hyp_solve -> k_hyp_rows; ekf_loc_assoc.hip) ----
+// ekf_hypotheses_step_detections: ONE window and ONE motion for every hypothesis, checked as plan_det_windows checks a window
+// (plan_det_window), lin / ang finite.  m_hi: the window's distinct ids capped at AMAX -- an upper bound of what the device
+// matches -- and 0 with the measurement model off; passes: a second k_hyp_solve / k_hyp_rows pair on the update-only record where
+// m_hi > MMAX (a record that turns out empty leaves every hypothesis bit for bit: loc_solve_body's `apply`).  The device raises
+// each hypothesis's bound over the landmarks it matched, which the host does not know: where anything may match, the mirror
+// bound_hi becomes n and k_hyp_rows' grid covers the map -- a workgroup beyond its hypothesis's bound returns at once, no bit
+// depends on the grid.  code: what a refusal returns -- EKF_ERR_STATE for a bank whose source slot had no tag table.
+// Returns nullptr, or what is wrong (then nothing of `dp` but `code` is to be used and nothing has changed).
+struct HypDetPlan {
+  int m_hi = 0, passes = 1, bound_hi = 3, groups = 1, code = EKF_ERR_ARG;
+};
+inline const char* plan_hyp_detections(const HypBank* hy, double lin, double ang, int count, const int* tag_id, const double* pose_t,
+                                       const double* pose_err, HypDetPlan& dp) {
+  dp = HypDetPlan{};
+  if (!hy->has_tags) {
+    dp.code = EKF_ERR_STATE;
+    return "the bank's source slot had no tag table (no ekf_step_detections / ekf_upload_tag_index before ekf_hyp_create)";
+  }
+  if (!std::isfinite(lin) || !std::isfinite(ang)) return "non-finite lin / ang";
+  int distinct = 0;
+  if (const char* why = plan_det_window(count, DMAX, 0, tag_id, pose_t, pose_err, &distinct)) return why;
+  dp.m_hi = hy->cfg.enable_measurement_model ? distinct : 0;
+  dp.passes = dp.m_hi > MMAX ? 2 : 1;
+  dp.bound_hi = dp.m_hi > 0 ? hy->n : hy->bound_hi;
+  dp.groups = loc_rows_groups(dp.bound_hi);
+  return nullptr;
+}
+// ekf_hypotheses_detections_upload: `steps` windows -- lin / ang / count [steps], tag_id / pose_err [steps][stride], pose_t
+// [steps][stride][3] --, every step checked as plan_hyp_detections checks its window.  What the upload holds: 2 * steps records
+// in k_hyp_associate's layout (step s's first pass at record s, its second at steps + s).  bound / passes are exact and come
+// from the device: finish_hyp_detection_stream, from the AssocOut records the association left.
+struct HypDetStreamPlan {
+  int steps = 0, code = EKF_ERR_ARG;
+  std::vector<int> bound, passes;
+  size_t records() const { return 2 * (size_t)steps; }
+};
+inline const char* plan_hyp_detection_stream(const HypBank* hy, int steps, const double* lin, const double* ang, const int* count,
+                                             const int* tag_id, const double* pose_t, const double* pose_err, int stride,
+                                             HypDetStreamPlan& sp) {
+  sp = HypDetStreamPlan{};
+  if (steps < 0) return "steps must be >= 0";
+  if (steps == 0) return nullptr;                        // (frees the stream)
+  if (!hy->has_tags) {
+    sp.code = EKF_ERR_STATE;
+    return "the bank's source slot had no tag table (no ekf_step_detections / ekf_upload_tag_index before ekf_hyp_create)";
+  }
+  if (!lin || !ang || !count || stride < 0) return "NULL array";
+  for (int s = 0; s < steps; ++s) {
+    if (!std::isfinite(lin[s]) || !std::isfinite(ang[s])) return "non-finite lin / ang";
+    int distinct = 0;
+    if (const char* why = plan_det_window(count[s], stride, s, tag_id, pose_t, pose_err, &distinct)) return why;
+  }
+  sp.steps = steps;
+  return nullptr;
+}
+// The stream's exact shape from the association's records ao[0, steps): per step the bound over the landmarks it matched (3:
+// none), as plan_hyp_stream gives an index stream's, and its passes.
+inline void finish_hyp_detection_stream(const HypBank* hy, const AssocOut* ao, HypDetStreamPlan& sp) {
+  sp.bound.assign((size_t)sp.steps, 3);
+  sp.passes.assign((size_t)sp.steps, 1);
+  const bool meas = hy->cfg.enable_measurement_model != 0;
+  for (int s = 0; s < sp.steps; ++s) {
+    const int m = meas ? std::max(0, std::min(ao[s].m, AMAX)) : 0;
+    int id_hi = -1;
+    for (int i = 0; i < m; ++i) id_hi = std::max(id_hi, ao[s].idx[i]);
+    sp.bound[(size_t)s] = std::min(hy->n, std::max(3, 3 + 2 * (id_hi + 1)));
+    sp.passes[(size_t)s] = m > MMAX ? 2 : 1;
+  }
+}
+// ekf_hypotheses_download_tags: step -1 = the last single window (`single`: whether one has run), else a step of a detection stream
+inline const char* plan_hyp_download_tags(const HypBank* hy, int step, bool single, int* code) {
+  *code = EKF_ERR_ARG;
+  if (step < -1) return "step must be -1 (the last single window) or a step of the uploaded detection stream";
+  *code = EKF_ERR_STATE;
+  if (step == -1) return single ? nullptr : "no window of detections has run (ekf_hypotheses_step_detections)";
+  if (hy->stream_passes.empty() || step >= hy->stream_steps) return "no such step in an uploaded detection stream (ekf_hypotheses_detections_upload)";
   return nullptr;
 }
 // ekf_hypotheses_log: a ring of `capacity` HypMixRow (0: off)
@@ -1968,22 +2069,29 @@ inline int fill_step_records(HostPlan* h, bool pred, bool upd, const double* lin
   }
   return m_pass_hi;
 }
+// Window w of arrays with `stride` detections per window, c detections, into `d`: nothing beyond them is read.
+inline void fill_det_record(DetIn& d, double lin, double ang, int c, int stride, long w, const int* tag_id, const double* pose_t,
+                            const double* pose_err) {
+  d.lin = lin;
+  d.ang = ang;
+  d.count = c;
+  d.pad = 0;
+  for (int i = 0; i < c; ++i) {
+    const long e = w * stride + i;
+    d.tag_id[i] = tag_id[e];
+    d.pose_err[i] = pose_err[e];
+    std::copy_n(pose_t + 3 * e, 3, d.pose_t[i]);
+  }
+}
 // The batch's windows of a call plan_det_windows accepted, into out[0, batch): count[b] detections each, nothing beyond them is read.
 inline void fill_det_records(const HostPlan* h, const double* lin, const double* ang, const int* count, const int* tag_id,
                              const double* pose_t, const double* pose_err, int stride, DetIn* out) {
-  for (int b = 0; b < h->batch; ++b) {
-    DetIn& d = out[b];
-    d.lin = lin[b];
-    d.ang = ang[b];
-    d.count = count[b];
-    d.pad = 0;
-    for (int i = 0; i < count[b]; ++i) {
-      const long e = (long)b * stride + i;
-      d.tag_id[i] = tag_id[e];
-      d.pose_err[i] = pose_err[e];
-      std::copy_n(pose_t + 3 * e, 3, d.pose_t[i]);
-    }
-  }
+  for (int b = 0; b < h->batch; ++b) fill_det_record(out[b], lin[b], ang[b], count[b], stride, b, tag_id, pose_t, pose_err);
+}
+// The `steps` windows of a call plan_hyp_detection_stream accepted (steps = 1: plan_hyp_detections), into out[0, steps).
+inline void fill_hyp_det_records(int steps, const double* lin, const double* ang, const int* count, const int* tag_id,
+                                 const double* pose_t, const double* pose_err, int stride, DetIn* out) {
+  for (int s = 0; s < steps; ++s) fill_det_record(out[s], lin[s], ang[s], count[s], stride, s, tag_id, pose_t, pose_err);
 }
 
 }  // namespace ekf

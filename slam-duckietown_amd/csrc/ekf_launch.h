@@ -132,6 +132,11 @@ void launch_associate(hipStream_t st, const BankView& k, const DetIn* det, int* 
 // neff_dev[b] (raised over the matched landmarks) and k.flags -- nothing else
 void launch_loc_associate(hipStream_t st, const BankView& k, const DetIn* det, const int* tagmap, int* neff_dev, const double* mu,
                           StepIn* step_out, AssocOut* assoc_out, LocUnmatched* unmatched, const AssocConfig& cfg);
+// a hypothesis bank's windows (grid = windows, det[w] each) against the bank's tag-table row: writes step_out[w] and
+// step_out[windows + w] (the shared records the bank's solves read with rec_stride 0), assoc_out[w], unmatched[w] and flags[w]
+// -- nothing of the bank itself
+void launch_hyp_associate(hipStream_t st, const HypView& v, const int* tagrow, const DetIn* det, int windows, StepIn* step_out,
+                          AssocOut* assoc_out, LocUnmatched* unmatched, unsigned* flags, const AssocConfig& cfg);
 // ---- the hypothesis bank (ekf_hypotheses.hip); v: the bank (ekf_device.h: HypView), every shape from ekf_host_plan.h's plan_hyp_* ----
 // one StepIn for all hypotheses (rec_stride 0) or one each (1); the solve leaves v.rec, the row launch behind it applies them
 void launch_hyp_solve(hipStream_t st, const HypView& v, const StepIn* in, int rec_stride, const DeviceConfig& cfg, bool gate);

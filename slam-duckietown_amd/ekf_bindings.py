@@ -178,6 +178,10 @@ ABI = {
     "ekf_hypotheses_log": (C.c_int, [C.c_void_p, C.c_int]),
     "ekf_hypotheses_log_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "ekf_hypotheses_download_log": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, _ip]),
+    "ekf_hypotheses_set_association": (C.c_int, [C.c_void_p, C.c_double, _ip, C.c_int]),
+    "ekf_hypotheses_step_detections": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int, _ip, _dp, _dp]),
+    "ekf_hypotheses_detections_upload": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp, C.c_int]),
+    "ekf_hypotheses_download_tags": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _ip, _dp, _dp, _dp, _ip, _ip, C.POINTER(C.c_uint)]),
     "ekf_stream_upload": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
     "ekf_stream_run": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ekf_run_stream": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
@@ -255,6 +259,24 @@ def _i32(a):
 
 def _p(a, typ=_dp):
     return a.ctypes.data_as(typ)
+
+
+def _pack_windows(windows):
+    """Windows of raw detections -- each the reference's ``[(timestamp, [tag, ...])]`` list -- with their frames concatenated in
+    order, into the arrays the detection entries take: (count (W,), tag ids (W, stride), pose_t (W, stride, 3), pose_err
+    (W, stride), stride), padded to the longest window (stride >= 1)."""
+    flat = [[tag for _stamp, tags in win for tag in tags] for win in windows]
+    count = np.array([len(w) for w in flat], dtype=np.int32)
+    stride = max(1, int(count.max())) if len(flat) else 1
+    ids = np.zeros((len(flat), stride), dtype=np.int32)
+    pt = np.zeros((len(flat), stride, 3))
+    pe = np.zeros((len(flat), stride))
+    for b, w in enumerate(flat):
+        for i, tag in enumerate(w):
+            ids[b, i] = tag.tag_id
+            pt[b, i] = np.asarray(tag.pose_t, dtype=np.float64).ravel()[:3]
+            pe[b, i] = tag.pose_err
+    return count, ids, pt, pe, stride
 
 
 def compose_pose(pose, delta):
@@ -796,6 +818,75 @@ class HypothesisBank:
         elif split > 0.0:
             z = rng.standard_normal((max(count, 0), self.count, 3))
         self._check(self._lib.ekf_hypotheses_run(h, first, count, fraction, split, None if u is None else _p(u), None if z is None else _p(z)))
+
+    # -- windows of raw detections: one association on the device for every hypothesis -----------
+    def set_association(self, gate_range: float = 1.5, ignore_tags: Sequence[int] = ()):
+        """``EkfSlam.set_association`` for the bank (``ekf_hypotheses_set_association``), which took the filter's settings when it
+        was made: for later ``step_detections`` and ``upload_detections``.  An uploaded stream is not associated again."""
+        ig = _i32(list(ignore_tags)) if len(ignore_tags) else None
+        self._check(self._lib.ekf_hypotheses_set_association(self._live(), float(gate_range), _p(ig, _ip) if ig is not None else None,
+                                                             len(ignore_tags)))
+
+    @staticmethod
+    def _pack_detections(windows):
+        """``EkfSlam.localize_detections``' windows through its packer.  A bank has NO host fallback, unlike ``EkfSlam``: a window
+        beyond the device's limits -- more than EKF_DMAX detections, a tag id outside [0, 1024) -- raises ``ValueError``."""
+        for s, win in enumerate(windows):
+            tags = [tag for _stamp, frame in win for tag in frame]
+            if len(tags) > EKF_DMAX:
+                raise ValueError(f"window {s}: {len(tags)} detections, more than EKF_DMAX = {EKF_DMAX}; a bank has no host association")
+            bad = [int(t.tag_id) for t in tags if not 0 <= int(t.tag_id) < EKF_TAGMAX]
+            if bad:
+                raise ValueError(f"window {s}: tag id {bad[0]} outside [0, {EKF_TAGMAX}); a bank has no host association")
+        return _pack_windows(windows)
+
+    def step_detections(self, lin, ang, detections):
+        """``EkfSlam.localize_detections`` for every hypothesis (``ekf_hypotheses_step_detections``): ONE window -- the reference's
+        ``[(timestamp, [tag, ...])]`` list -- and one motion ``lin`` / ``ang`` for the whole bank.  The window is associated once
+        on the device against the bank's tag table (the source slot's at ``EkfSlam.hypotheses``): ignore list, gate, per-tag
+        averaging; a tag the map does not hold is skipped and reported by ``unmatched_tags``.  Every hypothesis then takes
+        ``step`` with the lists ``tags()`` reports, bit for bit.  Asynchronous.  Unlike ``EkfSlam`` there is no silent host
+        route: a window beyond the device's limits raises ``ValueError`` (``_pack_detections``)."""
+        h = self._live()
+        count, ids, pt, pe, _ = self._pack_detections([detections])
+        self._check(self._lib.ekf_hypotheses_step_detections(h, float(lin), float(ang), int(count[0]), _p(ids, _ip), _p(pt), _p(pe)))
+
+    def upload_detections(self, lin, ang, windows):
+        """A recorded run of windows into device memory (``ekf_hypotheses_detections_upload``; blocking): ``lin[s]``, ``ang[s]``
+        and ``windows[s]`` as ``step_detections`` takes them.  Every window is associated at the upload, in one launch; ``run``
+        then runs the stream as it runs an index stream, and ``tags(step=s)`` / ``unmatched_tags(step=s)`` report step s.
+        Replaces an earlier stream of either kind; no windows frees it.  ``ValueError`` as for ``step_detections``."""
+        h = self._live()
+        L, A = np.atleast_1d(_f64(lin)).ravel(), np.atleast_1d(_f64(ang)).ravel()
+        if not (len(L) == len(A) == len(windows)):
+            raise ValueError("upload_detections: lin, ang and windows must hold one entry per step")
+        count, ids, pt, pe, stride = self._pack_detections(windows)
+        self._check(self._lib.ekf_hypotheses_detections_upload(h, len(windows), _p(L), _p(A), _p(count, _ip), _p(ids, _ip), _p(pt), _p(pe),
+                                                               stride))
+        self._stream_steps = len(windows)
+
+    def _window(self, step):
+        m, nu, fl = C.c_int(), C.c_int(), C.c_uint()
+        idx, tid, un = (np.zeros(EKF_AMAX, dtype=np.int32) for _ in range(3))
+        err, rng, brg = (np.zeros(EKF_AMAX) for _ in range(3))
+        self._check(self._lib.ekf_hypotheses_download_tags(self._live(), -1 if step is None else int(step), C.byref(m), _p(idx, _ip),
+                                                           _p(tid, _ip), _p(err), _p(rng), _p(brg), C.byref(nu), _p(un, _ip), C.byref(fl)))
+        return m.value, idx, tid, err, rng, brg, nu.value, un, fl.value
+
+    def tags(self, step: Optional[int] = None) -> dict:
+        """The matched tags of the last ``step_detections`` window (``step`` None) or of step ``step`` of the uploaded detection
+        stream, in update order: {landmark: (tag_id, err, range, bearing)} (``ekf_hypotheses_download_tags``; blocking)."""
+        m, idx, tid, err, rng, brg = self._window(step)[:6]
+        return {int(idx[i]): (int(tid[i]), float(err[i]), float(rng[i]), float(brg[i])) for i in range(m)}
+
+    def unmatched_tags(self, step: Optional[int] = None) -> list:
+        """The distinct tag ids of that window the map does not hold, in order of first appearance (the first EKF_AMAX)."""
+        w = self._window(step)
+        return [int(t) for t in w[7][:min(w[6], EKF_AMAX)]]
+
+    def window_flags(self, step: Optional[int] = None) -> int:
+        """That window's flag: EKF_FLAG_ASSOC where a tag id was outside [0, 1024) or more than EKF_AMAX distinct tags matched."""
+        return int(self._window(step)[8])
 
     def mixture(self) -> HypothesisMixture:
         """The bank's pose mixture formed on the device (``ekf_hypotheses_mixture``; blocking): ``evaluation.mixture_pose``'s mean and
@@ -1888,17 +1979,7 @@ class EkfSlam:
     def _detections_call(self, entry, detections):
         """One window per trajectory, frames concatenated in order, into the arrays ``ekf_step_detections`` and
         ``ekf_localize_detections`` take; lin / ang are in the staging arrays."""
-        flat = [[tag for _stamp, tags in win for tag in tags] for win in detections]
-        count = np.array([len(w) for w in flat], dtype=np.int32)
-        stride = max(1, int(count.max()))
-        ids = np.zeros((self.batch, stride), dtype=np.int32)
-        pt = np.zeros((self.batch, stride, 3))
-        pe = np.zeros((self.batch, stride))
-        for b, w in enumerate(flat):
-            for i, tag in enumerate(w):
-                ids[b, i] = tag.tag_id
-                pt[b, i] = np.asarray(tag.pose_t, dtype=np.float64).ravel()[:3]
-                pe[b, i] = tag.pose_err
+        count, ids, pt, pe, stride = _pack_windows(detections)
         self._check(entry(self._h, self._plin, self._pang, _p(count, _ip), _p(ids, _ip), _p(pt), _p(pe), stride))
 
     # -- localisation from raw detections --------------------------------------------------------

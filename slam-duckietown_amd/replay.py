@@ -318,3 +318,83 @@ def replay(source, backend=None, delta_time: float = 0.7, detector: Optional[Cal
     finally:
         if own_backend:
             backend.close()
+
+
+class _WindowRecorder:
+    """A backend for ``replay`` that runs no filter: it keeps what every window would have handed to one."""
+
+    def __init__(self):
+        self.steps = []                                            # (lin, ang, window) per EKF step
+
+    def set_map(self, mean, cov, tag_index):
+        self._state = (np.asarray(mean, dtype=float), np.asarray(cov, dtype=float))
+
+    def pose(self):
+        return self._state[0][:3]
+
+    def state(self):
+        return self._state
+
+    def step(self, ang, lin, detections, tag_index):
+        self.steps.append((float(lin), float(ang), list(detections)))
+        return {}
+
+
+@dataclasses.dataclass
+class RelocalizeResult:
+    trace: object                           # HypothesisTrace: the bank's pose mixture behind every window
+    tags: List[dict]                        # per window {landmark: (tag_id, err, range, bearing)}, update order
+    unmatched: List[list]                   # per window the distinct tag ids the map does not hold
+    filter: object                          # EkfSlam on the map with the best hypothesis adopted (the caller closes it)
+    best: int
+    windows: int
+
+
+def relocalize(source, map_state, seeds, seed_cov, fraction: float = 0.5, split: float = 0.5, rng=None, delta_time: float = 0.7,
+               config=None, noise: Optional[dict] = None, nis_gate: Optional[float] = None, device: int = 0,
+               **replay_kw) -> RelocalizeResult:
+    """The kidnapped robot from a log: a bank of ``len(seeds)`` pose hypotheses (``frontend.poses_on_circle``; each with the pose
+    block ``seed_cov``) on the finished map ``map_state = (mean, covariance, tag_index)`` is driven through the whole log on the
+    device.  ``source`` is what ``replay`` takes -- the log is cut into windows by the driver's own windowing (``delta_time``,
+    ``replay_kw``: detector, wheel geometry, fast_mode) -- or a list of ``(lin, ang, window)`` already cut.  The windows are
+    uploaded and associated once (``HypothesisBank.upload_detections``) and run back to back with the log on and the resampling
+    decided on the device (``fraction``, ``split``, ``rng``); no window goes through the host's association, and one beyond the
+    device's limits raises ``ValueError``.  ``noise``: ``EkfSlam.set_noise``'s keywords; ``nis_gate``: a threshold for the bank.
+    Returns the trace, every window's matched and unmatched tags, and the filter with the best hypothesis adopted."""
+    from .ekf_bindings import EkfConfig, EkfError, EkfSlam
+    if isinstance(source, (list, tuple)) and len(source) and isinstance(source[0], tuple) and len(source[0]) == 3:
+        steps = [(float(lin), float(ang), list(win)) for lin, ang, win in source]
+    else:
+        rec = _WindowRecorder()
+        replay(source, backend=rec, delta_time=delta_time, localize=True, map_state=map_state, **replay_kw)
+        steps = rec.steps
+    if not steps:
+        raise ValueError("relocalize: the log holds no window")
+    cfg = config or EkfConfig()
+    mean, cov = np.asarray(map_state[0], dtype=float), np.asarray(map_state[1], dtype=float)
+    seeds = np.atleast_2d(np.asarray(seeds, dtype=float))
+    filt = EkfSlam(len(mean), 1, device, cfg)
+    try:
+        filt.set_state(mean, cov)
+        filt.set_tag_index({int(t): int(j) for t, j in map_state[2].items()})
+        filt.set_association(cfg.gate_range, cfg.ignore_tags)
+        if noise:
+            filt.set_noise(**noise)
+        with filt.hypotheses(len(seeds)) as bank:
+            if nis_gate is not None:
+                bank.set_nis_gate(nis_gate)
+            bank.reset(seeds, seed_cov)
+            bank.log(len(steps))
+            bank.upload_detections([s[0] for s in steps], [s[1] for s in steps], [s[2] for s in steps])
+            bank.run(0, len(steps), fraction=fraction, split=split, rng=rng)
+            trace = bank.trace()
+            tags = [bank.tags(step=s) for s in range(len(steps))]
+            unmatched = [bank.unmatched_tags(step=s) for s in range(len(steps))]
+            best = bank.mixture().best
+            if best < 0:
+                raise EkfError("relocalize: no hypothesis weighs anything behind the last window")
+            bank.adopt(best, filt)
+    except BaseException:
+        filt.close()
+        raise
+    return RelocalizeResult(trace, tags, unmatched, filt, int(best), len(steps))
