@@ -657,8 +657,8 @@ int ekf_download_unmatched(ekf_handle *h, int b, int *m, int *tag_id, int capaci
  * bit.  On any difference nothing is written and the call fails with EKF_ERR_STATE.  The slot's active bound is raised to the
  * hypothesis's.
  * Every call returns EKF_ERR_ARG for a NULL bank, a range outside it or a bad argument, with nothing changed; the message is in
- * ekf_hyp_last_error.  Not part of a bank: likelihood association per hypothesis, the per-hypothesis innovation and pose logs,
- * per-hypothesis noise.
+ * ekf_hyp_last_error.  Not part of a bank: a STREAM of unlabelled steps inside ekf_hypotheses_run, joint compatibility per
+ * hypothesis, the per-hypothesis innovation and pose logs, per-hypothesis noise.
  * ekf_hypotheses_weigh / ekf_hypotheses_resample (their errors too go to ekf_hyp_last_error) keep a bank running: the weights'
  * statistics and a systematic resampling ON THE DEVICE -- the pose rows are what moves, 393 MB at count = 4096, N = 2000.  Every
  * output of both may be NULL; a call blocks exactly when one is not, else it is asynchronous on the bank's stream like ekf_hyp_step.
@@ -742,7 +742,47 @@ int ekf_download_unmatched(ekf_handle *h, int b, int *m, int *tag_id, int capaci
  * host-clocked): the window's upload and the association add 13 .. 14 us to a step (200 calls behind one sync against ekf_hyp_step
  * with the reported lists); one window, call + sync, against the host's association + ekf_hyp_step: 72 / 86 us at count = 32,
  * 207 / 223 at 1024, 802 / 817 at 4096; the upload of 200 windows 2.5 ms against 6.5 with the host's association; ekf_hypotheses_run
- * per step on the detection stream and on the index stream of the same lists: 23.1 / 23.1, 159.0 / 159.0, 752.3 / 752.5. */
+ * per step on the detection stream and on the index stream of the same lists: 23.1 / 23.1, 159.0 / 159.0, 752.3 / 752.5.
+ * UNLABELLED observations, associated per hypothesis ON THE DEVICE (errors: ekf_hyp_last_error; every EKF_ERR_ARG leaves the bank
+ * bit for bit).  Which landmark an observation belongs to depends on the pose, so it differs between hypotheses: k_hyp_score
+ * (ekf_hyp_assoc.hip) scores, for each hypothesis, every landmark of the map against every observation of ONE list of m <=
+ * EKF_MMAX (range, bearing) pairs -- the robot has one camera -- exactly as ekf_associate scores them for a slot: from the joint
+ * 5 x 5 covariance of (pose, landmark) -- the hypothesis's pose block and pose rows, the map's landmark block -- S = H5 P5 H5^T +
+ * Q with the bank's measurement noise, NIS = y^T S^-1 y (bearing wrapped) and the score d = NIS + ln det S, by the one function
+ * both kernels call.  Per observation the two landmarks of smallest d, best first: a strictly smaller score replaces, ties stay
+ * with the lower landmark index, a NaN never wins, an empty map or all-NaN scores give -1 / NaN.  A hypothesis's result depends
+ * on its own state, the map and the observations, not on count, on k or on which hypotheses share the call.
+ * ekf_hypotheses_associate (blocking, stream-ordered behind the bank's stream; it changes nothing a later call can see): the
+ * scores of hypotheses [k0, k0 + count), shaped as ekf_associate's outputs with stride = m: cand count x m x 2, cand_nis /
+ * cand_logdet count x m x 2, min_nis count x m (each of the three may be NULL), all_nis / all_logdet count x m x cap, both or
+ * neither, cap >= the map's landmark count (entries beyond it: NaN).  Destinations in pinned memory (ekf_host_alloc) are written
+ * directly, others through one copy each.  EKF_ERR_ARG: a range outside the bank, m outside 0..EKF_MMAX, an observation that is
+ * not finite, NULL cand, all_* given singly or with a short cap.
+ * ekf_hypotheses_step_unlabelled (ASYNCHRONOUS on the bank's stream): ekf_hyp_step's two launches on a prediction-only record
+ * (motion_stride as there), then k_hyp_score, which also RESOLVES each hypothesis's assignment on the device and writes its step
+ * record and assignment row -- nothing is downloaded --, then the bank's solve and row launches on those records (the bank's NIS
+ * gate still acts inside the update).  The resolve is frontend.resolve_associations with no new landmarks (the map is frozen):
+ * the observations are taken in ascending order of their best candidate's NIS (stable, NaN last); each takes its first candidate,
+ * of two, that no earlier observation took, and is ACCEPTED iff that candidate's NIS <= accept (NaN compares false), else
+ * DROPPED.  The accepted pairs update the hypothesis in observation order.  miss: a finite log-likelihood, normally <= 0, that
+ * every dropped observation adds to the hypothesis's loglik -- the clutter term without which a hypothesis that matches nothing
+ * is never penalised (evaluation.clutter_loglik gives a default): with dropped > 0 and miss != 0, loglik += dropped * miss (one
+ * product, one addition) before the update's solve runs; otherwise loglik is not written by the scoring.  n_obs / n_rej count
+ * only what the update then sees.  ekf_hypotheses_update_unlabelled is the same call without the prediction.  With the
+ * measurement model off the observations are ignored, as ekf_hyp_update ignores them.  EKF_ERR_ARG: lin, ang or an observation
+ * not finite, m outside 0..EKF_MMAX, accept negative or NaN (INFINITY: every candidate is accepted), miss not finite.
+ * THE GUARANTEE: after ekf_hypotheses_step_unlabelled every hypothesis is BIT FOR BIT what it is after ekf_hyp_step with m = 0,
+ * then ekf_hypotheses_associate, then frontend.resolve_associations with create = +inf on the host from the downloaded rows,
+ * then ekf_hyp_update with the resulting per-hypothesis lists -- with miss = 0 including loglik, n_obs, n_rej, flags and bound --
+ * and the downloaded assignment equals the host's.
+ * ekf_hypotheses_download_assignment (blocking): rows [k0, k0 + count) of the last unlabelled step's assignment, EKF_MMAX ints
+ * each: the landmark of every accepted observation, -1 for dropped ones and beyond m; kept until the next unlabelled call.
+ * EKF_ERR_STATE before the first unlabelled step.  The records (352 B per hypothesis), the assignment rows and the query's staging
+ * buffer are allocated at first use; a failed allocation returns EKF_ERR_HIP with the byte count and leaves the bank usable.
+ * Measured on one MI355X (tools/hyp_associate_time.py, profiles/hyp_associate.txt; N = 2000, m = 8, us, count = 32 / 1024 / 4096):
+ * ekf_hypotheses_associate call + sync 266 / 359 / 1037; k_hyp_score alone, between an event pair, 186 / 267 / 844;
+ * ekf_hypotheses_step_unlabelled per step over 200 steps behind one sync 233 / 453 / 1620, ekf_hyp_step with the true ids there
+ * 28 / 138 / 620; one step + sync 251 / 475 / 1665 against 731 / 11 661 / 50 723 for the host sequence of the guarantee. */
 typedef struct ekf_hypotheses ekf_hypotheses;
 int ekf_hyp_create(ekf_handle *h, int b, int count, ekf_hypotheses **out);
 int ekf_hyp_destroy(ekf_hypotheses *hy);
@@ -778,6 +818,14 @@ int ekf_hypotheses_detections_upload(ekf_hypotheses *hy, int steps, const double
 int ekf_hypotheses_download_tags(ekf_hypotheses *hy, int step /* -1: the last single window */, int *m, int *idx, int *tag_id,
                                  double *err, double *range, double *bearing, int *n_unmatched, int *unmatched /* EKF_AMAX */,
                                  unsigned *flags);
+int ekf_hypotheses_associate(ekf_hypotheses *hy, int k0, int count, const double *range, const double *bearing, int m,
+                             int *cand, double *cand_nis, double *cand_logdet, double *min_nis,
+                             double *all_nis, double *all_logdet, int cap);
+int ekf_hypotheses_step_unlabelled(ekf_hypotheses *hy, const double *lin, const double *ang, int motion_stride,
+                                   const double *range, const double *bearing, int m, double accept, double miss);
+int ekf_hypotheses_update_unlabelled(ekf_hypotheses *hy, const double *range, const double *bearing, int m,
+                                     double accept, double miss);
+int ekf_hypotheses_download_assignment(ekf_hypotheses *hy, int k0, int count, int *assign /* count x EKF_MMAX */);
 
 /* Streams of pre-uploaded inputs ([step][batch] and [step][batch][stride] arrays, stride <= EKF_MMAX; m[step][batch] landmarks
  * each -- any count per step and trajectory, 0 included: what the windows of src/replay_no_ros.py:280-301 hold).
@@ -914,6 +962,11 @@ long ekf_debug_snapshot(ekf_handle *h, int b, int which, double *dst, long count
  * pieces of the longest share, 0 if one would need more than 16). */
 int ekf_debug_pass_units(int batch, int nrb, int nch, int mode, int *out, int cap);
 int ekf_debug_pass_shares(int batch, int n_hi, int workgroups, int *out);
+/* k_hyp_score alone (tools/hyp_associate_time.py): `reps` launches of ekf_hypotheses_associate's query over the whole bank --
+ * candidates only, into the query's staging buffer, nothing copied back -- between one event pair on the bank's stream;
+ * *us_per_launch: the pair's time / reps in microseconds.  Blocking; changes nothing of the bank.  The arguments are checked as
+ * the query's; reps >= 1. */
+int ekf_debug_hyp_score_time(ekf_hypotheses *hy, const double *range, const double *bearing, int m, int reps, double *us_per_launch);
 
 #ifdef __cplusplus
 }

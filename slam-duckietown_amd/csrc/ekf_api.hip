@@ -3010,6 +3010,10 @@ struct ekf_hypotheses : ekf::HypBank {
   StagedUpload<double> draws;     // ekf_hypotheses_run's z: count x K x 3
   DeviceBuf<HypMixRow> dlog;      // ekf_hypotheses_log: the ring of log_cap rows
   DeviceBuf<HypMixRow> dmix;      // ekf_hypotheses_mixture's scratch row
+  StagedUpload<double> uobs;      // an unlabelled step's observations: EKF_MMAX ranges, then EKF_MMAX bearings
+  DeviceBuf<StepIn> durec;        // ... the records k_hyp_score leaves, one per hypothesis (made at the first unlabelled step),
+  DeviceBuf<int> dassign;         // and the assignment rows, count x EKF_MMAX
+  DeviceBuf<double> dquery;       // ekf_hypotheses_associate: the observations, then the destinations that are not pinned
   HypWeighOut host_head{};
   std::vector<HypState> host_st;
   std::string err;
@@ -3608,5 +3612,141 @@ extern "C" int ekf_hypotheses_download_tags(ekf_hypotheses* hy, int step, int* m
   }
   if (n_unmatched) *n_unmatched = u.total;
   if (flags) *flags = f;
+  return EKF_OK;
+}
+
+// ---- a bank's unlabelled observations (plan_hyp_associate, plan_hyp_unlabelled; k_hyp_score: ekf_hyp_assoc.hip) ----
+// The query is a read-only query of the bank as ekf_associate is one of a handle -- the Query scaffold with the bank's own
+// staging buffer, on the bank's stream --; a step from unlabelled observations is ekf_hyp_step's prediction, k_hyp_score writing
+// one record and one assignment row per hypothesis on the device, then the bank's solve and row launches on those records: no
+// host round trip.  The records, the assignment rows and the staging buffer are made at the first call that needs them.
+static int hyp_unlabelled_scratch(ekf_hypotheses* hy, const char* fn) {
+  const size_t K = (size_t)hy->count;
+  HYP_RES(hy, std::string(fn) + ": the records and assignment rows",
+          res::ensure_group(nullptr, res::want(hy->durec, K), res::want(hy->dassign, K * (size_t)MMAX)));
+  return EKF_OK;
+}
+
+// Blocking, stream-ordered behind the bank's stream; changes nothing a later call can see.
+extern "C" int ekf_hypotheses_associate(ekf_hypotheses* hy, int k0, int count, const double* range, const double* bearing, int m,
+                                        int* cand, double* cand_nis, double* cand_logdet, double* min_nis, double* all_nis,
+                                        double* all_logdet, int cap) {
+  const char* fn = "ekf_hypotheses_associate";
+  if (!hy) return EKF_ERR_ARG;
+  HypAssocPlan ap;
+  if (const char* why = plan_hyp_associate(hy, k0, count, range, bearing, m, cand, all_nis, all_logdet, cap, ap))
+    return hyp_fail(hy, EKF_ERR_ARG, std::string(fn) + ": " + why);
+  if (count == 0 || m == 0) return EKF_OK;               // (every output is empty)
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  const size_t obs = (size_t)count * (size_t)m, full_words = obs * (size_t)ap.cap_eff;
+  Query q{};
+  q.plan.inputs = 2 * (size_t)MMAX;                      // range, bearing
+  q.add(cand, obs);                                      // (2 ints per observation)
+  q.add(cand_nis, obs * 2);
+  q.add(cand_logdet, obs * 2);
+  q.add(min_nis, obs);
+  q.add(all_nis, full_words);
+  q.add(all_logdet, full_words);
+  HYP_RES(hy, std::string(fn) + ": the staging buffer", hy->dquery.reserve(plan_staging(q.plan), 0, hy->stream));
+  for (int i = 0; i < q.plan.ndst; ++i)
+    if (q.plan.dst[i].staged) q.dev[i] = hy->dquery.p + q.plan.dst[i].at;
+  double *dzr = hy->dquery.p, *dzb = dzr + MMAX;
+  HYP_TRY(hy, hipMemcpyAsync(dzr, range, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, hy->stream));
+  HYP_TRY(hy, hipMemcpyAsync(dzb, bearing, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, hy->stream));
+  const HypScoreOut o{q.out<int>(0), q.out<double>(1), q.out<double>(2), q.out<double>(3), q.out<double>(4), q.out<double>(5),
+                      ap.cap_eff, nullptr, nullptr, 0.0, 0.0};
+  launch_hyp_score(hy->stream, hyp_view(hy), hy->dcfg, k0, count, ap.chunks, dzr, dzb, m, o);
+  HYP_TRY(hy, hipGetLastError());
+  for (int i = 0; i < q.plan.ndst; ++i)
+    if (q.plan.dst[i].staged)
+      HYP_TRY(hy, hipMemcpyAsync(q.host[i], q.dev[i], sizeof(double) * q.plan.dst[i].words, hipMemcpyDeviceToHost, hy->stream));
+  HYP_TRY(hy, hipStreamSynchronize(hy->stream));
+  return EKF_OK;
+}
+
+static int hyp_unlabelled(ekf_hypotheses* hy, const char* fn, bool pred, const double* lin, const double* ang, int motion_stride,
+                          const double* range, const double* bearing, int m, double accept, double miss) {
+  if (!hy) return EKF_ERR_ARG;
+  HypUnlabelledPlan up;
+  if (const char* why = plan_hyp_unlabelled(hy, pred, lin, ang, motion_stride, range, bearing, m, accept, miss, up))
+    return hyp_fail(hy, EKF_ERR_ARG, std::string(fn) + ": " + why);
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  if (int rc = hyp_unlabelled_scratch(hy, fn)) return rc;
+  double* zs = nullptr;
+  HYP_RES(hy, std::string(fn) + ": the observations", hy->uobs.begin(2 * (size_t)MMAX, 2 * (size_t)MMAX, hy->stream, &zs));
+  if (pred) {                                            // ekf_hyp_step's two launches on a prediction-only record
+    const int none = 0;
+    if (int rc = hyp_step(hy, fn, true, lin, ang, motion_stride, nullptr, nullptr, nullptr, &none, 0, 0)) return rc;
+  }
+  for (int q = 0; q < MMAX; ++q) {
+    zs[q] = q < up.m ? range[q] : 0.0;
+    zs[MMAX + q] = q < up.m ? bearing[q] : 0.0;
+  }
+  HYP_RES(hy, std::string(fn) + ": the observations' upload", hy->uobs.commit(2 * (size_t)MMAX, hy->stream));
+  const HypView v = hyp_view(hy);
+  const HypScoreOut o{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, hy->durec.p, hy->dassign.p, accept, miss};
+  launch_hyp_score(hy->stream, v, hy->dcfg, 0, hy->count, up.chunks, hy->uobs.device(), hy->uobs.device() + MMAX, up.m, o);
+  hy->unlabelled_run = true;
+  hy->bound_hi = up.bound_hi;
+  launch_hyp_solve(hy->stream, v, hy->durec.p, 1, hy->dcfg, hy->gate);
+  launch_hyp_rows(hy->stream, v, up.groups);
+  HYP_TRY(hy, hipGetLastError());
+  return EKF_OK;
+}
+
+// Asynchronous on the bank's stream.
+extern "C" int ekf_hypotheses_step_unlabelled(ekf_hypotheses* hy, const double* lin, const double* ang, int motion_stride,
+                                              const double* range, const double* bearing, int m, double accept, double miss) {
+  return hyp_unlabelled(hy, "ekf_hypotheses_step_unlabelled", true, lin, ang, motion_stride, range, bearing, m, accept, miss);
+}
+
+extern "C" int ekf_hypotheses_update_unlabelled(ekf_hypotheses* hy, const double* range, const double* bearing, int m, double accept,
+                                                double miss) {
+  return hyp_unlabelled(hy, "ekf_hypotheses_update_unlabelled", false, nullptr, nullptr, 0, range, bearing, m, accept, miss);
+}
+
+// Blocking.  assign: count x EKF_MMAX, the landmark of every accepted observation of the last unlabelled step, -1 elsewhere.
+extern "C" int ekf_hypotheses_download_assignment(ekf_hypotheses* hy, int k0, int count, int* assign) {
+  if (!hy) return EKF_ERR_ARG;
+  int code = EKF_ERR_ARG;
+  if (const char* why = plan_hyp_assignment(hy, k0, count, assign, &code))
+    return hyp_fail(hy, code, std::string("ekf_hypotheses_download_assignment: ") + why);
+  if (count == 0) return EKF_OK;
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  HYP_TRY(hy, hipMemcpyAsync(assign, hy->dassign.p + (size_t)k0 * MMAX, sizeof(int) * (size_t)count * MMAX, hipMemcpyDeviceToHost, hy->stream));
+  HYP_TRY(hy, hipStreamSynchronize(hy->stream));
+  return EKF_OK;
+}
+
+// (diagnostics section of the header) the query's launch alone, `reps` times between one event pair on the bank's stream
+extern "C" int ekf_debug_hyp_score_time(ekf_hypotheses* hy, const double* range, const double* bearing, int m, int reps,
+                                        double* us_per_launch) {
+  const char* fn = "ekf_debug_hyp_score_time";
+  if (!hy) return EKF_ERR_ARG;
+  int cand_probe = 0;
+  HypAssocPlan ap;
+  if (const char* why = plan_hyp_associate(hy, 0, hy->count, range, bearing, m, &cand_probe, nullptr, nullptr, 0, ap))
+    return hyp_fail(hy, EKF_ERR_ARG, std::string(fn) + ": " + why);
+  if (reps < 1 || !us_per_launch) return hyp_fail(hy, EKF_ERR_ARG, std::string(fn) + ": reps must be >= 1 and us_per_launch given");
+  HYP_TRY(hy, hipSetDevice(hy->device));
+  const size_t obs = (size_t)hy->count * (size_t)std::max(m, 1);
+  HYP_RES(hy, std::string(fn) + ": the staging buffer", hy->dquery.reserve(2 * (size_t)MMAX + 6 * obs, 0, hy->stream));
+  double *dzr = hy->dquery.p, *dzb = dzr + MMAX, *out = dzb + MMAX;
+  if (m > 0) {
+    HYP_TRY(hy, hipMemcpyAsync(dzr, range, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, hy->stream));
+    HYP_TRY(hy, hipMemcpyAsync(dzb, bearing, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, hy->stream));
+  }
+  const HypScoreOut o{reinterpret_cast<int*>(out), out + obs, out + 3 * obs, out + 5 * obs, nullptr, nullptr, 0, nullptr, nullptr, 0.0, 0.0};
+  res::Event<HipBackend> t0, t1;
+  HYP_RES(hy, "t0", t0.ensure(true));
+  HYP_RES(hy, "t1", t1.ensure(true));
+  HYP_RES(hy, "t0", t0.record(hy->stream));
+  for (int r = 0; r < reps; ++r) launch_hyp_score(hy->stream, hyp_view(hy), hy->dcfg, 0, hy->count, ap.chunks, dzr, dzb, m, o);
+  HYP_RES(hy, "t1", t1.record(hy->stream));
+  HYP_TRY(hy, hipGetLastError());
+  HYP_RES(hy, "t1", t1.wait_if_recorded());
+  float ms = 0.f;
+  HYP_TRY(hy, hipEventElapsedTime(&ms, t0.ev, t1.ev));
+  *us_per_launch = 1e3 * (double)ms / reps;
   return EKF_OK;
 }

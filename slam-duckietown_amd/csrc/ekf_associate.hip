@@ -22,6 +22,7 @@
 
 #include "ekf_device.h"
 
+#include "ekf_assoc_score.h"
 #include "ekf_devfn.h"
 #include "ekf_launch.h"
 
@@ -30,31 +31,11 @@ namespace ekf {
 constexpr int AQ_WAVES = 4;
 static_assert(AQ_CHUNK == 64, "lane = landmark: a chunk is one wave of landmarks");
 constexpr int AQ_SUMS = 9;              // per lane: the landmark block (3) and the 3 x 2 cross block (6) over the ranks
-constexpr int AQ_PART = 9;              // doubles of a partial record: (d, landmark, NIS, ln det S) x 2, smallest NIS
 
 struct AssocTile {
   double v0[4], v1[4], w0[4], w1[4];    // V[k][i], V[k][i + 1], W[i][k], W[i + 1][k] for the 4 ranks of a k-tile
 };
-
-// The running two best of one observation: a candidate that is not NaN takes a place it is strictly smaller than.
-struct AssocBest {
-  double d[2], nis[2], ld[2], lm[2];
-  __device__ __forceinline__ void clear() {
-    const double nanv = __builtin_nan("");
-    d[0] = d[1] = nis[0] = nis[1] = ld[0] = ld[1] = nanv;
-    lm[0] = lm[1] = -1.0;
-  }
-  __device__ __forceinline__ void offer(double dv, double lv, double nv, double ldv) {
-    if (!(dv == dv) || lv < 0.0) return;
-    if (lm[0] < 0.0 || dv < d[0]) {
-      d[1] = d[0]; lm[1] = lm[0]; nis[1] = nis[0]; ld[1] = ld[0];
-      d[0] = dv; lm[0] = lv; nis[0] = nv; ld[0] = ldv;
-    } else if (lm[1] < 0.0 || dv < d[1]) {
-      d[1] = dv; lm[1] = lv; nis[1] = nv; ld[1] = ldv;
-    }
-  }
-};
-__device__ __forceinline__ double nan_min(double a, double v) { return (v == v && (!(a == a) || v < a)) ? v : a; }
+// (the scoring arithmetic, AssocBest and nan_min: ekf_assoc_score.h, shared with k_hyp_score)
 
 __global__ __launch_bounds__(64 * AQ_WAVES) void k_assoc_query(
     const double* __restrict__ P, const double* __restrict__ V, const double* __restrict__ W, const double* __restrict__ dacc,
@@ -256,53 +237,8 @@ __global__ __launch_bounds__(64 * AQ_WAVES) void k_assoc_query(
     p5[3][3] = i < bound ? base00 + r[0] : base00;
     p5[3][4] = p5[4][3] = i + 1 < bound ? base01 + r[1] : base01;
     p5[4][4] = i + 1 < bound ? base11 + r[2] : base11;
-    // d, q, z^ and H5 (src/replay_no_ros.py:443-469; q == 0 gives NaN like NumPy's 0/0)
-    const double dx = m5[3] - m5[0], dy = m5[4] - m5[1];
-    const double qq = dx * dx + dy * dy, sq = sqrt(qq);
-    const double zhat1 = atan2(dy, dx) - m5[2];
-    double h[2][5];
-    h[0][0] = (-sq * dx) / qq;
-    h[0][1] = (-sq * dy) / qq;
-    h[0][2] = 0.0 / qq;
-    h[0][3] = (sq * dx) / qq;
-    h[0][4] = (sq * dy) / qq;
-    h[1][0] = dy / qq;
-    h[1][1] = -dx / qq;
-    h[1][2] = -qq / qq;
-    h[1][3] = -dy / qq;
-    h[1][4] = dx / qq;
-    double t5[2][5], S[2][2];
-#pragma unroll
-    for (int rr = 0; rr < 2; ++rr)
-#pragma unroll
-      for (int c = 0; c < 5; ++c) {
-        double acc = 0.0;
-#pragma unroll
-        for (int a = 0; a < 5; ++a) acc = fma(h[rr][a], p5[a][c], acc);
-        t5[rr][c] = acc;
-      }
-#pragma unroll
-    for (int rr = 0; rr < 2; ++rr)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        double acc = 0.0;
-#pragma unroll
-        for (int a = 0; a < 5; ++a) acc = fma(t5[rr][a], h[c][a], acc);
-        S[rr][c] = acc;
-      }
     const double* qd = cfg.noise ? cfg.noise + (long)NOISE_ROW * b + 3 : cfg.qd;   // Q_b (ekf_set_noise's row if the table is set)
-    S[0][0] += qd[0];
-    S[1][1] += qd[1];
-    const double det = S[0][0] * S[1][1] - S[0][1] * S[1][0];
-    const double ia = S[1][1] / det, ib = -S[0][1] / det, ic = -S[1][0] / det, id = S[0][0] / det;
-    logdet = log(det);
-#pragma unroll
-    for (int q = 0; q < MMAX; ++q)
-      if (q < mb) {                                    // (uniform)
-        const double y0 = zr[bi * stride + q] - sq;
-        const double y1 = wrap_pi(zb[bi * stride + q] - zhat1);
-        nis_q[q] = innov_nis(y0, y1, ia, ib, ic, id);
-      }
+    assoc_score(p5, m5, qd, zr + bi * stride, zb + bi * stride, mb, nis_q, logdet);   // (ekf_assoc_score.h)
   }
   sl[lane] = logdet;
 #pragma unroll

@@ -174,6 +174,19 @@ struct StepIn {
   double bearing[MMAX];
 };
 
+// k_hyp_score (ekf_hyp_assoc.hip): one workgroup of HS_WAVES waves per hypothesis, lane = landmark within a chunk of HS_CHUNK.
+// Where it writes.  Query mode (cand set; step nullptr): ekf_associate's outputs with stride = m for the hypotheses of the
+// launch's range, row = hypothesis - k0 -- cand_nis / cand_logdet / min_nis may be nullptr, all_nis / all_logdet come together
+// or not at all with `cap` landmarks per row.  Step mode (step set; cand nullptr): hypothesis k's record step[k] and assignment
+// row assign[k * MMAX ..], indexed by the hypothesis itself; accept: the NIS an observation's candidate must not exceed, miss:
+// the log-likelihood every dropped observation adds to the hypothesis.
+constexpr int HS_WAVES = 4;
+constexpr int HS_CHUNK = 64;
+struct HypScoreOut {
+  int* cand; double *cand_nis, *cand_logdet, *min_nis, *all_nis, *all_logdet; int cap;
+  StepIn* step; int* assign; double accept, miss;
+};
+
 // What one sequential iteration (one observed landmark j, src/replay_no_ros.py:436-480) hands to
 // the panel kernel, expressed on the compressed index set C.  Pairs are stored adjacent so that a
 // single 16-byte LDS broadcast read fetches both rows of a 2-row quantity.

@@ -1291,6 +1291,8 @@ struct HypBank {
   // the mixture log (ekf_hypotheses_log): the ring's rows (0: off) and the steps logged since it was switched on
   int log_cap = 0;
   long long log_steps = 0;
+  // whether an unlabelled step has run (ekf_hypotheses_step_unlabelled / _update_unlabelled): the assignment rows hold its result
+  bool unlabelled_run = false;
 };
 constexpr int HYP_COUNT_MAX = 1 << 16;                   // hypotheses of one bank (a grid dimension of the bank's launches)
 // the bytes a hypothesis costs: its record, its three pose rows, its solve's record
@@ -1630,6 +1632,69 @@ inline const char* plan_hyp_download_tags(const HypBank* hy, int step, bool sing
   if (hy->stream_passes.empty() || step >= hy->stream_steps) return "no such step in an uploaded detection stream (ekf_hypotheses_detections_upload)";
   return nullptr;
 }
+// ---- a bank's unlabelled observations (k_hyp_score -> k_hyp_solve -> k_hyp_rows; ekf_hyp_assoc.hip) ----
+// k_hyp_score's launch: one workgroup of HS_WAVES waves per hypothesis of the range; `chunks` chunks of HS_CHUNK landmarks cover
+// the map and, where the query writes the full matrices, their `cap` columns (the columns beyond the map are NaN).
+inline int hyp_score_chunks(int n, int cap) { return (std::max((n - 3) / 2, std::max(cap, 0)) + HS_CHUNK - 1) / HS_CHUNK; }
+// ekf_hypotheses_associate: ONE list of m observations for hypotheses [k0, k0 + count).  cap_eff: the columns of the full
+// matrices (0 without them).  Returns nullptr, or what is wrong (then nothing of `ap` is to be used and nothing has changed).
+struct HypAssocPlan {
+  int chunks = 0, cap_eff = 0;
+};
+inline const char* plan_hyp_associate(const HypBank* hy, int k0, int count, const double* range, const double* bearing, int m,
+                                      const int* cand, const double* all_nis, const double* all_logdet, int cap, HypAssocPlan& ap) {
+  ap = HypAssocPlan{};
+  if (const char* why = plan_hyp_range(hy, k0, count)) return why;
+  if (m < 0 || m > MMAX) return "m must lie in 0..EKF_MMAX";
+  if (m > 0 && (!range || !bearing)) return "NULL observations";
+  for (int q = 0; q < m; ++q)
+    if (!std::isfinite(range[q]) || !std::isfinite(bearing[q])) return "non-finite observation";
+  if (!cand) return "NULL cand";
+  if ((all_nis == nullptr) != (all_logdet == nullptr)) return "all_nis and all_logdet are given together or not at all";
+  if (all_nis && cap < (hy->n - 3) / 2) return "cap is below the map's landmark count";
+  ap.cap_eff = all_nis ? cap : 0;
+  ap.chunks = hyp_score_chunks(hy->n, ap.cap_eff);
+  return nullptr;
+}
+// ekf_hypotheses_step_unlabelled (pred) / ekf_hypotheses_update_unlabelled: the motion as plan_hyp_step takes it, ONE list of m
+// observations for every hypothesis, accept >= 0 (+inf: every candidate), miss finite.  m: the observations the launch scores --
+// none while the measurement model is off, as ekf_hyp_update packs none --; chunks: k_hyp_score's; the host does not know what
+// the device matches, so where anything may match the mirror bound_hi becomes n and k_hyp_rows' grid (groups) covers the map, as
+// plan_hyp_detections has it.  Returns nullptr, or what is wrong (then nothing of `up` is to be used and nothing has changed).
+struct HypUnlabelledPlan {
+  int m = 0, chunks = 0, bound_hi = 3, groups = 1;
+};
+inline const char* plan_hyp_unlabelled(const HypBank* hy, bool pred, const double* lin, const double* ang, int motion_stride,
+                                       const double* range, const double* bearing, int m, double accept, double miss,
+                                       HypUnlabelledPlan& up) {
+  up = HypUnlabelledPlan{};
+  if (pred && (!lin || !ang)) return "NULL lin/ang";
+  if (pred && motion_stride != 0 && motion_stride != 1) return "motion_stride must be 0 (shared) or 1 (one per hypothesis)";
+  if (pred)
+    for (int k = 0; k < (motion_stride ? hy->count : 1); ++k)
+      if (!std::isfinite(lin[k]) || !std::isfinite(ang[k])) return "non-finite lin / ang";
+  if (m < 0 || m > MMAX) return "m must lie in 0..EKF_MMAX";
+  if (m > 0 && (!range || !bearing)) return "NULL observations";
+  for (int q = 0; q < m; ++q)
+    if (!std::isfinite(range[q]) || !std::isfinite(bearing[q])) return "non-finite observation";
+  if (!(accept >= 0.0)) return "accept must be >= 0 (INFINITY: every candidate is accepted)";
+  if (!std::isfinite(miss)) return "miss must be finite";
+  up.m = hy->cfg.enable_measurement_model ? m : 0;
+  up.chunks = hyp_score_chunks(hy->n, 0);
+  up.bound_hi = up.m > 0 && hy->n > 3 ? hy->n : hy->bound_hi;
+  up.groups = loc_rows_groups(up.bound_hi);
+  return nullptr;
+}
+// ekf_hypotheses_download_assignment: rows [k0, k0 + count) of the last unlabelled step's assignment
+inline const char* plan_hyp_assignment(const HypBank* hy, int k0, int count, const int* assign, int* code) {
+  *code = EKF_ERR_ARG;
+  if (const char* why = plan_hyp_range(hy, k0, count)) return why;
+  if (count > 0 && !assign) return "NULL assign";
+  *code = EKF_ERR_STATE;
+  if (!hy->unlabelled_run) return "no unlabelled step has run (ekf_hypotheses_step_unlabelled / ekf_hypotheses_update_unlabelled)";
+  return nullptr;
+}
+
 // ekf_hypotheses_log: a ring of `capacity` HypMixRow (0: off)
 inline const char* plan_hyp_log(int capacity) {
   if (capacity < 0) return "capacity must be >= 0";

@@ -155,6 +155,12 @@ void launch_hyp_copy(hipStream_t st, bool nt, const HypView& v, const HypResampl
 void launch_hyp_split(hipStream_t st, const HypView& v, const HypResampleView& rs, const HypResamplePlan& rp, const double* z);
 // behind weigh: the bank's mixture pose into *row; row->resampled: whether rp.ess_min's gate is open on this header
 void launch_hyp_mixture(hipStream_t st, const HypView& v, const HypResampleView& rs, const HypResamplePlan& rp, HypMixRow* row);
+// ---- a bank's unlabelled observations (ekf_hyp_assoc.hip) ----
+// hypotheses [k0, k0 + count) against the m observations zr / zb (device; one list for all); chunks: plan_hyp_associate's.  o
+// (ekf_device.h: HypScoreOut) chooses the mode: the query's outputs, or the records and assignment rows launch_hyp_solve reads
+// behind it with rec_stride 1 -- then st[k].loglik is the one thing of the bank the launch writes
+void launch_hyp_score(hipStream_t st, const HypView& v, const DeviceConfig& cfg, int k0, int count, int chunks, const double* zr,
+                      const double* zb, int m, const HypScoreOut& o);
 // groups x (tiles of the largest source + 1) workgroups; tab: plan_copy's table on the device
 void launch_copy_traj(hipStream_t st, bool nt, const BankView& src, const BankView& dst, const double* mus, double* mud,
                       const int* tab, int groups, int n_hi);

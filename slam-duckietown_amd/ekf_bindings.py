@@ -182,6 +182,10 @@ ABI = {
     "ekf_hypotheses_step_detections": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int, _ip, _dp, _dp]),
     "ekf_hypotheses_detections_upload": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp, C.c_int]),
     "ekf_hypotheses_download_tags": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _ip, _dp, _dp, _dp, _ip, _ip, C.POINTER(C.c_uint)]),
+    "ekf_hypotheses_associate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int]),
+    "ekf_hypotheses_step_unlabelled": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp, _dp, C.c_int, C.c_double, C.c_double]),
+    "ekf_hypotheses_update_unlabelled": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, C.c_double, C.c_double]),
+    "ekf_hypotheses_download_assignment": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip]),
     "ekf_stream_upload": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
     "ekf_stream_run": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ekf_run_stream": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, _dp, _ip, C.c_int]),
@@ -215,6 +219,7 @@ ABI = {
     "ekf_debug_snapshot": (C.c_long, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_long]),
     "ekf_debug_pass_units": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_int]),
     "ekf_debug_pass_shares": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip]),
+    "ekf_debug_hyp_score_time": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, C.c_int, _dp]),
 }
 
 
@@ -404,6 +409,17 @@ class Associations(typing.NamedTuple):
     min_nis: np.ndarray   # (B, S)     the smallest NIS over ALL landmarks
     all_nis: Optional[np.ndarray] = None      # (B, S, N_hi)  with full=True: every landmark's NIS (NaN beyond the map)
     all_logdet: Optional[np.ndarray] = None   # (B, S, N_hi)  ... and ln det S
+
+
+class HypothesisAssociations(typing.NamedTuple):
+    """What ``HypothesisBank.associate()`` returns for K hypotheses and one list of m observations (-1 / NaN where the map is
+    empty or every score is NaN)."""
+    cand: np.ndarray      # (K, m, 2)  int32: the landmarks of the two smallest scores d = NIS + ln det S, best first
+    nis: np.ndarray       # (K, m, 2)  their NIS = y^T S^-1 y
+    logdet: np.ndarray    # (K, m, 2)  their ln det S
+    min_nis: np.ndarray   # (K, m)     the smallest NIS over ALL landmarks
+    all_nis: Optional[np.ndarray] = None      # (K, m, N)  with full=True: every landmark's NIS
+    all_logdet: Optional[np.ndarray] = None   # (K, m, N)  ... and ln det S
 
 
 class DirectUpdate(typing.NamedTuple):
@@ -887,6 +903,69 @@ class HypothesisBank:
     def window_flags(self, step: Optional[int] = None) -> int:
         """That window's flag: EKF_FLAG_ASSOC where a tag id was outside [0, 1024) or more than EKF_AMAX distinct tags matched."""
         return int(self._window(step)[8])
+
+    # -- unlabelled observations -----------------------------------------------------------------
+    @staticmethod
+    def _unlabelled(ranges, bearings):
+        """One flat list of at most EKF_MMAX (range, bearing) pairs as two float64 arrays."""
+        R, B = np.atleast_1d(_f64(ranges)).ravel(), np.atleast_1d(_f64(bearings)).ravel()
+        if np.ndim(ranges) > 1 or np.ndim(bearings) > 1 or len(R) != len(B):
+            raise ValueError("unlabelled observations: ONE flat list of ranges and one of bearings, of equal length, for every hypothesis")
+        if len(R) > EKF_MMAX:
+            raise ValueError(f"unlabelled observations: at most {EKF_MMAX} in one call")
+        return R, B
+
+    def associate(self, ranges, bearings, full: bool = False, k=None) -> HypothesisAssociations:
+        """``EkfSlam.associate`` per hypothesis (``ekf_hypotheses_associate``; blocking, changes nothing): ONE list of unlabelled
+        range/bearing observations scored against every landmark of the map from each hypothesis's own pose, pose block and
+        pose rows -- the scores ``associate`` gives on a slot that adopted the hypothesis, bit for bit.  ``k`` None: the whole
+        bank; an int: that hypothesis; (k0, count): a range.  ``full=True`` adds the (K, m, N) matrices of NIS and ln det S.
+        ``frontend.resolve_associations`` turns one hypothesis's rows into an assignment; ``step_unlabelled`` does all of it
+        on the device."""
+        h = self._live()
+        k0, cnt = (0, self.count) if k is None else ((int(k), 1) if np.ndim(k) == 0 else (int(k[0]), int(k[1])))
+        R, B = self._unlabelled(ranges, bearings)
+        m, K = len(R), max(cnt, 0)
+        cand = np.empty((K, m, 2), dtype=np.int32)
+        nis, logdet, mn = np.empty((K, m, 2)), np.empty((K, m, 2)), np.empty((K, m))
+        all_nis = all_ld = None
+        cap = 0
+        if full:
+            cap = (self.n - 3) // 2
+            big = K * m * cap > 0
+            all_nis = _pinned.empty(self._lib, (K, m, cap)) if big else np.empty((K, m, cap))
+            all_ld = _pinned.empty(self._lib, (K, m, cap)) if big else np.empty((K, m, cap))
+        self._check(self._lib.ekf_hypotheses_associate(h, k0, cnt, _p(R), _p(B), m, _p(cand, _ip), _p(nis), _p(logdet), _p(mn),
+                                                       _p(all_nis) if full else None, _p(all_ld) if full else None, cap))
+        return HypothesisAssociations(cand, nis, logdet, mn, all_nis, all_ld)
+
+    def step_unlabelled(self, lin, ang, ranges, bearings, accept: float = 9.21, miss: float = 0.0):
+        """A localisation step from observations WITHOUT ids (``ekf_hypotheses_step_unlabelled``; asynchronous, no host round
+        trip): the prediction (``lin`` / ``ang`` as for ``step``), then per hypothesis ``associate``'s scores,
+        ``frontend.resolve_associations`` with no new landmarks -- an observation whose candidate's NIS exceeds ``accept`` is
+        dropped --, and ``update`` with what was accepted: the bits of that sequence run on the host.  ``miss``: the
+        log-likelihood every dropped observation adds to its hypothesis (``evaluation.clutter_loglik`` gives a default; 0:
+        a hypothesis that matches nothing is never penalised).  ``assignments()`` reports what was matched."""
+        h = self._live()
+        lin, ang, ms = self._motion(lin, ang)
+        R, B = self._unlabelled(ranges, bearings)
+        self._check(self._lib.ekf_hypotheses_step_unlabelled(h, _p(lin), _p(ang), ms, _p(R), _p(B), len(R), float(accept), float(miss)))
+        self._unlabelled_m = len(R)
+
+    def update_unlabelled(self, ranges, bearings, accept: float = 9.21, miss: float = 0.0):
+        """``step_unlabelled`` without the prediction (``ekf_hypotheses_update_unlabelled``)."""
+        h = self._live()
+        R, B = self._unlabelled(ranges, bearings)
+        self._check(self._lib.ekf_hypotheses_update_unlabelled(h, _p(R), _p(B), len(R), float(accept), float(miss)))
+        self._unlabelled_m = len(R)
+
+    def assignments(self) -> np.ndarray:
+        """(K, m) int32: per hypothesis the landmark of every observation of the last ``step_unlabelled`` /
+        ``update_unlabelled`` that was accepted, -1 for the dropped ones (``ekf_hypotheses_download_assignment``; blocking).
+        ``EkfError`` before the first unlabelled step."""
+        out = np.empty((self.count, EKF_MMAX), dtype=np.int32)
+        self._check(self._lib.ekf_hypotheses_download_assignment(self._live(), 0, self.count, _p(out, _ip)))
+        return out[:, :getattr(self, "_unlabelled_m", EKF_MMAX)].copy()
 
     def mixture(self) -> HypothesisMixture:
         """The bank's pose mixture formed on the device (``ekf_hypotheses_mixture``; blocking): ``evaluation.mixture_pose``'s mean and

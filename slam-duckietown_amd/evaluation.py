@@ -379,6 +379,19 @@ def resolve_hypotheses(bank, confidence: float = 0.99) -> HypothesisResolution:
     return HypothesisResolution(best, float(w[best]), ratio < 1.0 - float(confidence), second, ratio)
 
 
+def clutter_loglik(accept: float, meas_sigma: float) -> float:
+    """A default for ``HypothesisBank.step_unlabelled``'s ``miss``: the log-likelihood of an observation sitting exactly on the
+    acceptance boundary under the measurement noise R = meas_sigma^2 I alone, ``-1/2 (accept + ln det R + 2 ln 2 pi)``.  An
+    observation a hypothesis cannot match then costs it what the worst match it would still have accepted costs under the
+    tightest S a landmark can have; without such a term a hypothesis that matches nothing is never penalised."""
+    accept, meas_sigma = float(accept), float(meas_sigma)
+    if not (accept >= 0.0 and math.isfinite(accept)):
+        raise ValueError(f"clutter_loglik: accept must be finite and >= 0, got {accept!r}")
+    if not (meas_sigma > 0.0 and math.isfinite(meas_sigma)):
+        raise ValueError(f"clutter_loglik: meas_sigma must be finite and > 0, got {meas_sigma!r}")
+    return -0.5 * (accept + 4.0 * math.log(meas_sigma) + 2.0 * math.log(2.0 * math.pi))
+
+
 class MixturePose(NamedTuple):
     mean: np.ndarray                 # (3,) the weighted mean pose, the heading averaged on the circle
     cov: np.ndarray                  # (3, 3) sum w (P_k + d_k d_k^T), d_k the deviation from the mean (heading wrapped)
